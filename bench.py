@@ -19,6 +19,10 @@ dominant kernel (db_scan_topk) by its ALGORITHMIC bytes (4*D*rows scanned per la
 mean duration measured with hipEvents on the kernel's own stream (chip_profile_*).  `cpu_baseline` times the
 oracle's reference-faithful fp64 path (three separate GEMVs, single thread like the reference's
 dot_product_th) on a bounded sample.
+
+  --dump-outputs DIR: after the timed steps, the record the LAST timed tick returned to its caller (capi.TickResult) is written
+  as DIR/tick_<field>.npy, one float64 array per field.  The DB, the planted revisits and the tick positions come from fixed
+  seeds, so two builds of the library run with the same arguments can be compared file for file.
 """
 from __future__ import annotations
 
@@ -439,6 +443,15 @@ def run_ticks(chip, tick_ls, params, inflight, stamps=None):
     return out
 
 
+def dump_outputs(result, out_dir):
+    """--dump-outputs: one tick record as a caller receives it (capi.TickResult), DIR/tick_<field>.npy, float64 (row indices and
+    the status / found flags are exact in it), every field a 1-D array: status, found, idx_curr, idx_prev, score (1), argmax, maxv (3)."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, v in result.as_dict().items():
+        np.save(out_dir / f"tick_{name}.npy", np.atleast_1d(np.asarray(v, dtype=np.float64)))
+
+
 def check_results(results, exp):
     """sanity (not the parity check -- that is tests/ -m gpu): planted revisits must fire with the planted index"""
     for r, e in zip(results, exp):
@@ -738,6 +751,8 @@ def main():
                     help="skip the legs over the reference's production shapes (8192-D x 29k float rows, 4096-D x 1M double rows; ctxs of their own, 34 GB)")
     ap.add_argument("--paced-ticks", type=int, default=40,
                     help="N = 1: synchronous ticks at the reference's 10 Hz cadence per mode and position (0 = skip; each costs 0.1 s)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the record of the last timed tick as DIR/tick_<field>.npy (float64), for comparing two builds on the same arguments")
     args = ap.parse_args()
     global UNIT_DATA
     UNIT_DATA = args.data == "unit"
@@ -1042,7 +1057,10 @@ def main():
     scan_ms, n_launch, bytes_last, span_ms = chip.profile_scan()
     chip.profile_enable(False)
 
+    assert len(results) == args.steps
     check_results(results, expect[args.warmup:])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(results[-1], args.dump_outputs)
 
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64)
@@ -1103,7 +1121,7 @@ def main():
                         "sharding": "single GPU" if n_gpus == 1 else (f"{world} replicas of the whole DB, independent tick streams, no collective" if replicated
                                                                       else f"row round-robin over {n_gpus} GPUs + all-gather of top-k"),
                         "descriptor_queries_per_s": 3 * args.steps / elapsed,
-                        "preflight": os.environ.get("BENCH_PREFLIGHT"),   # scripts/preflight_8gpu.sh: verdict of the device-count-gated tests, run before this line
+                        "preflight": os.environ.get("BENCH_PREFLIGHT"),   # scripts/preflight_8gpu.sh: verdict of the tests that span the node's devices, run before this line
                         "db_fill_s": t_fill, "arch": info["arch"], "n_cus": info["n_cus"]}),
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,

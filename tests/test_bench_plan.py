@@ -69,6 +69,20 @@ def test_size_legs_do_not_disturb_each_other():
             assert (r["found"] == 0) if e is None else (r["found"] == 1 and (r["idx_curr"], r["idx_prev"]) == e), (rows, l, e, r)
 
 
+def test_dump_outputs_writes_the_tick_record_field_by_field(tmp_path):
+    """bench.py --dump-outputs: every field of the record a tick returns, as a 1-D float64 array of its own, values unchanged."""
+    from cerebro_amd import capi
+    r = capi.TickResult(status=2, found=1, idx_curr=1_000_049, idx_prev=987_654, score=0.98046875)
+    r.argmax[:] = [987_654, 987_653, 12]
+    r.maxv[:] = [0.98046875, 0.9765625, 0.125]
+    bench.dump_outputs(r, tmp_path / "out")
+    got = {f.stem: np.load(f) for f in (tmp_path / "out").iterdir()}
+    assert set(got) == {"tick_" + name for name, _ in capi.TickResult._fields_}
+    assert all(a.dtype == np.float64 and a.ndim == 1 for a in got.values())
+    for name, v in r.as_dict().items():
+        assert got["tick_" + name].tolist() == (v if isinstance(v, list) else [v])
+
+
 def test_eigen_probe_reports_absence_or_a_number():
     """bench.py probes for a real Eigen at run time; without one it says so instead of assuming."""
     import bench

@@ -60,6 +60,9 @@ CHIP_SCAN_FORM_ONE_ROW, CHIP_SCAN_FORM_ROWS = 1, 2
 CHIP_SAMPLER_FRESH, CHIP_SAMPLER_THEIA_PERSISTENT = 0, 1
 
 CHIP_TICK_SKIPPED, CHIP_TICK_TOO_SHORT, CHIP_TICK_SCANNED = 0, 1, 2
+CHIP_MATCH_MAX_KEYPOINTS = 16384
+CHIP_ORB_DESC_BYTES = 32
+CHIP_SET_AB, CHIP_SET_BA = 0, 1
 
 
 class ChipError(RuntimeError):
@@ -96,6 +99,24 @@ class RansacParams(C.Structure):
 class RansacSummary(C.Structure):
     _fields_ = [("n_iterations", C.c_int32), ("n_inliers", C.c_int32), ("best_hypothesis", C.c_int32),
                 ("n_models", C.c_int32), ("best_cost", C.c_double)]
+
+
+class MatchFrame(C.Structure):
+    _fields_ = [("desc", C.c_void_p), ("kp_xy", C.c_void_p), ("n", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("xyz", C.c_void_p)]
+
+
+class MatchSummary(C.Structure):
+    _fields_ = [("n_matches_all", C.c_int32), ("n_matches_gms", C.c_int32), ("n_3d2d_ab", C.c_int32), ("n_3d2d_ba", C.c_int32),
+                ("n_3d3d", C.c_int32), ("n_out_of_image", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class MatchSetsOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("uv", "uv_d", "X_ab", "uvn_ab", "X_ba", "uvn_ba", "A_3d3d", "B_3d3d",
+                                          "match_query_idx", "match_train_idx")]
 
 
 class Info(C.Structure):
@@ -156,6 +177,14 @@ _SIGS = {
                                   C.POINTER(RansacSummary)]),
     "chip_icp_ransac_enqueue": (C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(RansacParams)]),
     "chip_icp_ransac_collect": (C.c_int, [_P, _P, C.POINTER(C.c_float), _P, C.POINTER(RansacSummary)]),
+    "chip_build_has_match": (C.c_int, []),
+    "chip_orb_match": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P]),
+    "chip_gms_filter": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P,
+                                  C.POINTER(C.c_int32)]),
+    "chip_match_pair": (C.c_int, [_P, C.POINTER(MatchFrame), C.POINTER(MatchFrame), _P, C.POINTER(MatchSummary)]),
+    "chip_match_read_sets": (C.c_int, [_P, C.POINTER(MatchSetsOut)]),
+    "chip_pnp_ransac_matched": (C.c_int, [_P, C.c_int32, C.POINTER(RansacParams), _P, C.POINTER(C.c_float), _P, C.POINTER(RansacSummary)]),
+    "chip_icp_ransac_matched": (C.c_int, [_P, C.POINTER(RansacParams), _P, C.POINTER(C.c_float), _P, C.POINTER(RansacSummary)]),
     "chip_get_info": (C.c_int, [_P, C.POINTER(Info)]),
     "chip_profile_enable": (C.c_int, [_P, C.c_int32]),
     "chip_profile_reset": (C.c_int, [_P]),
@@ -544,6 +573,91 @@ class Chip:
         return dict(status=st, confidence=float(conf.value), T=T.reshape(4, 4).T.copy(), mask=mask[:N].copy(),
                     summary=dict(n_iterations=summ.n_iterations, n_inliers=summ.n_inliers,
                                  best_hypothesis=summ.best_hypothesis, n_models=summ.n_models, best_cost=summ.best_cost))
+
+    # -- candidate verification front end (ORB matching, GMS, correspondence sets)
+    def orb_match(self, d1: np.ndarray, d2: np.ndarray):
+        """-> (train_idx, distance) int32 per query descriptor; ties -> the lowest train index; no train descriptors: -1 / -1"""
+        d1 = np.ascontiguousarray(d1, dtype=np.uint8).reshape(-1, CHIP_ORB_DESC_BYTES)
+        d2 = np.ascontiguousarray(d2, dtype=np.uint8).reshape(-1, CHIP_ORB_DESC_BYTES)
+        n1, n2 = d1.shape[0], d2.shape[0]
+        idx = np.full(max(n1, 1), -1, dtype=np.int32)
+        dist = np.full(max(n1, 1), -1, dtype=np.int32)
+        self._chk(self.lib.chip_orb_match(self.h, _ptr(d1), n1, _ptr(d2), n2, _ptr(idx), _ptr(dist)), "chip_orb_match")
+        return idx[:n1].copy(), dist[:n1].copy()
+
+    def gms_filter(self, kp1: np.ndarray, size1, kp2: np.ndarray, size2, query_idx, train_idx) -> np.ndarray:
+        """size = (width, height) -> uint8 inlier mask in match order"""
+        kp1 = np.ascontiguousarray(kp1, dtype=np.float32).reshape(-1, 2)
+        kp2 = np.ascontiguousarray(kp2, dtype=np.float32).reshape(-1, 2)
+        q = np.ascontiguousarray(query_idx, dtype=np.int32)
+        t = np.ascontiguousarray(train_idx, dtype=np.int32)
+        assert q.shape == t.shape
+        n = q.shape[0]
+        mask = np.zeros(max(n, 1), dtype=np.uint8)
+        cnt = C.c_int32()
+        self._chk(self.lib.chip_gms_filter(self.h, _ptr(kp1), kp1.shape[0], size1[0], size1[1], _ptr(kp2), kp2.shape[0], size2[0], size2[1],
+                                           _ptr(q), _ptr(t), n, _ptr(mask), C.byref(cnt)), "chip_gms_filter")
+        assert cnt.value == int(mask[:n].sum())
+        return mask[:n].copy()
+
+    @staticmethod
+    def _match_frame(f: dict):
+        desc = np.ascontiguousarray(f["desc"], dtype=np.uint8).reshape(-1, CHIP_ORB_DESC_BYTES)
+        kp = np.ascontiguousarray(f["kp"], dtype=np.float32).reshape(-1, 2)
+        xyz = np.ascontiguousarray(f["xyz"], dtype=np.float32)
+        assert xyz.ndim == 3 and xyz.shape[2] == 3 and desc.shape[0] == kp.shape[0]
+        return MatchFrame(desc.ctypes.data, kp.ctypes.data, kp.shape[0], xyz.shape[1], xyz.shape[0], xyz.ctypes.data), (desc, kp, xyz)
+
+    def match_pair(self, frame_a: dict, frame_b: dict, Kinv: np.ndarray, read_sets: bool = True) -> dict:
+        """The whole stage for frames dict(desc (n, 32) uint8, kp (n, 2) float32, xyz (H, W, 3) float32).  The five sets stay on the
+        device for pnp_matched / icp_matched; read_sets also copies them out (chip_match_read_sets)."""
+        fa, keep_a = self._match_frame(frame_a)
+        fb, keep_b = self._match_frame(frame_b)
+        Ki = np.ascontiguousarray(Kinv, dtype=np.float64).reshape(9)
+        sm = MatchSummary()
+        self._chk(self.lib.chip_match_pair(self.h, C.byref(fa), C.byref(fb), _ptr(Ki), C.byref(sm)), "chip_match_pair")
+        out = dict(summary=sm.as_dict())
+        if read_sets:
+            out.update(self.match_read_sets(sm))
+        return out
+
+    def match_read_sets(self, sm: MatchSummary) -> dict:
+        g, ab, ba, dd = sm.n_matches_gms, sm.n_3d2d_ab, sm.n_3d2d_ba, sm.n_3d3d
+        shapes = dict(uv=(g, 2), uv_d=(g, 2), X_ab=(ab, 3), uvn_ab=(ab, 2), X_ba=(ba, 3), uvn_ba=(ba, 2), A_3d3d=(dd, 3), B_3d3d=(dd, 3))
+        arrs = {k: np.full(shp, np.nan, dtype=np.float64) for k, shp in shapes.items()}
+        arrs["match_query_idx"] = np.full(g, -1, dtype=np.int32)
+        arrs["match_train_idx"] = np.full(g, -1, dtype=np.int32)
+        o = MatchSetsOut(**{k: (v.ctypes.data if v.size else None) for k, v in arrs.items()})
+        self._chk(self.lib.chip_match_read_sets(self.h, C.byref(o)), "chip_match_read_sets")
+        return arrs
+
+    def _matched(self, st: int, where: str, N: int, T, conf, mask, summ):
+        if st == CHIP_ERR_TOO_FEW_POINTS:
+            return dict(status=st, confidence=-1.0, T=None, mask=None, summary=None)
+        self._chk(st, where)
+        return dict(status=st, confidence=float(conf.value), T=T.reshape(4, 4).T.copy(), mask=mask[:N].copy(),
+                    summary=dict(n_iterations=summ.n_iterations, n_inliers=summ.n_inliers, best_hypothesis=summ.best_hypothesis,
+                                 n_models=summ.n_models, best_cost=summ.best_cost))
+
+    def pnp_matched(self, which: int, N: int, params: RansacParams | None = None):
+        """chip_pnp_ransac on the device-resident set `which` (CHIP_SET_AB / CHIP_SET_BA) of the last match_pair; N = that set's count"""
+        p = params or default_ransac_params()
+        T = np.empty(16, dtype=np.float64)
+        conf = C.c_float()
+        mask = np.zeros(max(N, 1), dtype=np.uint8)
+        summ = RansacSummary()
+        st = self.lib.chip_pnp_ransac_matched(self.h, which, C.byref(p), _ptr(T), C.byref(conf), _ptr(mask), C.byref(summ))
+        return self._matched(st, "chip_pnp_ransac_matched", N, T, conf, mask, summ)
+
+    def icp_matched(self, N: int, params: RansacParams | None = None):
+        """chip_icp_ransac on the device-resident 3d-3d set of the last match_pair; N = n_3d3d"""
+        p = params or default_icp_params()
+        T = np.empty(16, dtype=np.float64)
+        conf = C.c_float()
+        mask = np.zeros(max(N, 1), dtype=np.uint8)
+        summ = RansacSummary()
+        st = self.lib.chip_icp_ransac_matched(self.h, C.byref(p), _ptr(T), C.byref(conf), _ptr(mask), C.byref(summ))
+        return self._matched(st, "chip_icp_ransac_matched", N, T, conf, mask, summ)
 
     # -- introspection / profiling
     def info(self) -> dict:

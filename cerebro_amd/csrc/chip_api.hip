@@ -499,6 +499,7 @@ void ctx_destroy(chip_ctx *c)
     pnp_destroy(c);
     icp_destroy(c);
     batch_destroy(c);
+    match_destroy(c);
     for (void *p : c->segs) (void)hipFree(p);
     if (c->seg_table_dev) (void)hipFree(c->seg_table_dev);
     if (c->ring_dev) (void)hipFree(c->ring_dev);

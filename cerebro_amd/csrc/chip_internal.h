@@ -264,6 +264,8 @@ struct Ctx {
     void *pnp_state = nullptr;
     void *icp_state = nullptr;   // icp.hip, created on first use
     void *batch_state = nullptr; // batch.hip, created on first use
+    void *match_state = nullptr; // match.hip, created on first use
+    std::mutex match_mu;         // serialises the matching calls of a ctx; taken BEFORE pnp_mu / icp_mu (chip_*_ransac_matched)
 
     mutable hipError_t last_hip = hipSuccess;
 };
@@ -379,6 +381,13 @@ int pnp_create(Ctx *c);
 void pnp_destroy(Ctx *c);
 void icp_destroy(Ctx *c);
 void batch_destroy(Ctx *c);
+void match_destroy(Ctx *c);   // match.hip
+// the solvers on correspondence sets that already are in device memory (match.hip's sets): same kernels, same results as the
+// host-pointer entries chip_pnp_ransac / chip_icp_ransac; the caller has validated the arguments and holds match_mu
+int pnp_ransac_device(Ctx *c, const double *X_dev, const double *uv_dev, int32_t N, const chip_ransac_params *p, double *T_colmajor,
+                      float *confidence, uint8_t *inlier_mask, chip_ransac_summary *summary);
+int icp_ransac_device(Ctx *c, const double *A_dev, const double *B_dev, int32_t N, const chip_ransac_params *p, double *T_colmajor,
+                      float *confidence, uint8_t *inlier_mask, chip_ransac_summary *summary);
 
 }  // namespace chip
 

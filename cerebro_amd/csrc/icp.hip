@@ -314,7 +314,7 @@ extern "C" void chip_icp_params_default(chip_ransac_params *p)
 // The estimation is split in two so that it can run underneath something else (its kernel is tiny and the PnP kernels leave
 // the GPU 92-95 % idle): enqueue = H2D of the points + the kernel on the ICP stream, no synchronisation; collect = wait, replay
 // theia's selection rule, fetch the winner.  chip_icp_ransac is enqueue + collect.
-static int icp_enqueue_locked(chip_ctx *c, const double *A, const double *B, int32_t N, const chip_ransac_params *p)
+static int icp_enqueue_locked(Ctx *c, const double *A, const double *B, int32_t N, const chip_ransac_params *p, bool dev_in = false)
 {
     CHIP_HIP(c, hipSetDevice(c->device));
     if (!c->icp_state) {
@@ -330,10 +330,13 @@ static int icp_enqueue_locked(chip_ctx *c, const double *A, const double *B, int
     if (rc != CHIP_OK) return rc;
     const int words = (N + 63) / 64;
     hipStream_t s = st->stream;
-    CHIP_HIP(c, hipMemcpyAsync(st->A, A, sizeof(double) * 3 * (size_t)N, hipMemcpyHostToDevice, s));
-    CHIP_HIP(c, hipMemcpyAsync(st->B, B, sizeof(double) * 3 * (size_t)N, hipMemcpyHostToDevice, s));
+    if (!dev_in) {
+        CHIP_HIP(c, hipMemcpyAsync(st->A, A, sizeof(double) * 3 * (size_t)N, hipMemcpyHostToDevice, s));
+        CHIP_HIP(c, hipMemcpyAsync(st->B, B, sizeof(double) * 3 * (size_t)N, hipMemcpyHostToDevice, s));
+    }
     IcpArgs a;
-    a.A = st->A; a.B = st->B; a.N = N; a.S = S; a.seed = p->seed; a.thresh = p->error_thresh; a.use_mle = p->use_mle;
+    // dev_in: A / B ARE device memory (icp_ransac_device), read where they lie
+    a.A = dev_in ? A : st->A; a.B = dev_in ? B : st->B; a.N = N; a.S = S; a.seed = p->seed; a.thresh = p->error_thresh; a.use_mle = p->use_mle;
     a.mask_words = words; a.T_out = st->T_out; a.cost = st->cost; a.nin = st->nin; a.valid = st->valid; a.mask = st->mask;
     a.H = H; a.T_dev = st->T_dev; a.valid_dev = st->valid_dev;
     a.sample_in = nullptr;
@@ -355,7 +358,7 @@ static int icp_enqueue_locked(chip_ctx *c, const double *A, const double *B, int
     return CHIP_OK;
 }
 
-static int icp_collect_locked(chip_ctx *c, double T_colmajor[16], float *confidence, uint8_t *inlier_mask, chip_ransac_summary *summary)
+static int icp_collect_locked(Ctx *c, double T_colmajor[16], float *confidence, uint8_t *inlier_mask, chip_ransac_summary *summary)
 {
     IcpState *st = static_cast<IcpState *>(c->icp_state);
     if (!st || !st->pending) return CHIP_ERR_BUSY;
@@ -429,6 +432,18 @@ extern "C" int chip_icp_ransac(chip_ctx *c, const double *A, const double *B, in
     if (rc != CHIP_OK) return rc;
     std::lock_guard<std::mutex> lk(c->icp_mu);
     rc = icp_enqueue_locked(c, A, B, N, p);
+    if (rc != CHIP_OK) return rc;
+    return icp_collect_locked(c, T_colmajor, confidence, inlier_mask, summary);
+}
+
+// chip_icp_ransac on sets that already are in device memory (match.hip): no staging copy, otherwise the same call
+int chip::icp_ransac_device(Ctx *c, const double *A_dev, const double *B_dev, int32_t N, const chip_ransac_params *p, double *T_colmajor,
+                            float *confidence, uint8_t *inlier_mask, chip_ransac_summary *summary)
+{
+    int rc = icp_check_args(A_dev, B_dev, N, p);
+    if (rc != CHIP_OK) return rc;
+    std::lock_guard<std::mutex> lk(c->icp_mu);
+    rc = icp_enqueue_locked(c, A_dev, B_dev, N, p, true);
     if (rc != CHIP_OK) return rc;
     return icp_collect_locked(c, T_colmajor, confidence, inlier_mask, summary);
 }

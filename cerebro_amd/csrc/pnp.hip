@@ -2430,7 +2430,7 @@ static int pnp_reserve(Ctx *c, PnpState *st, int N, int H, int words, int P)
 // Up to kPnpMaxBatch problems in one pair of launches; problem i's outputs are exactly those of a single-problem call.
 static int pnp_run(Ctx *c, PnpState *st, int P, const double *const *X, const double *const *uv, const int32_t *N,
                    const chip_ransac_params *p, const uint64_t *seeds, double *T_colmajor, float *confidence,
-                   uint8_t *const *inlier_mask, chip_ransac_summary *summary)
+                   uint8_t *const *inlier_mask, chip_ransac_summary *summary, bool dev_in = false)
 {
     // tuning only (CHIP_PNP_HOST_TIMING=1): host-side phases of a call, averaged, printed at process exit
     struct HostTiming {
@@ -2456,18 +2456,24 @@ static int pnp_run(Ctx *c, PnpState *st, int P, const double *const *X, const do
     std::memset(&ea, 0, sizeof ea);
     st->uv = st->X + 3 * (size_t)Ntot;
     for (int i = 0, off = 0; i < P; off += N[i], i++) {
+        PnpProblem pr;
+        pr.N = N[i]; pr.pad_ = 0;
+        pr.seed = seeds ? seeds[i] : p->seed;
+        if (dev_in) {   // X[i] / uv[i] ARE device memory (pnp_ransac_device): both kernels read them where they lie
+            pr.X = X[i]; pr.uv = uv[i];
+            ea.prob[i] = sa.prob[i] = pr;
+            continue;
+        }
         std::memcpy(st->h_in + 3 * (size_t)off, X[i], sizeof(double) * 3 * (size_t)N[i]);
         std::memcpy(st->h_in + 3 * (size_t)Ntot + 2 * (size_t)off, uv[i], sizeof(double) * 2 * (size_t)N[i]);
-        PnpProblem pr;
-        pr.X = st->X + 3 * (size_t)off; pr.uv = st->uv + 2 * (size_t)off; pr.N = N[i]; pr.pad_ = 0;
-        pr.seed = seeds ? seeds[i] : p->seed;
+        pr.X = st->X + 3 * (size_t)off; pr.uv = st->uv + 2 * (size_t)off;
         ea.prob[i] = pr;                                   // pnp_eig_score: the device copy (made by pnp_build_solve)
         pr.X = st->d_hin + 3 * (size_t)off; pr.uv = st->d_hin + 3 * (size_t)Ntot + 2 * (size_t)off;
         sa.prob[i] = pr;                                   // pnp_build_solve: the pinned host buffer, in place
     }
     // no H2D copy: see SolveArgs.  (CHIP_PNP_H2D=1 restores it for A/B runs.)
     static const bool want_h2d = std::getenv("CHIP_PNP_H2D") != nullptr;
-    if (want_h2d) {
+    if (want_h2d && !dev_in) {
         CHIP_HIP(c, hipMemcpyAsync(st->X, st->h_in, sizeof(double) * 5 * (size_t)Ntot, hipMemcpyHostToDevice, s));
         for (int i = 0; i < P; i++) sa.prob[i] = ea.prob[i];
     }
@@ -2481,7 +2487,7 @@ static int pnp_run(Ctx *c, PnpState *st, int P, const double *const *X, const do
     }
     sa.H = H; sa.S = S; sa.tab = st->tab_dev;
     sa.Sg = st->Sg; sa.Tg = st->Tg; sa.sample = st->sample; sa.ok = st->ok;
-    sa.in_host = want_h2d ? nullptr : st->d_hin; sa.in_dev = st->X; sa.n_in = 5 * (int64_t)Ntot;
+    sa.in_host = (want_h2d || dev_in) ? nullptr : st->d_hin; sa.in_dev = st->X; sa.n_in = 5 * (int64_t)Ntot;
     const size_t lds = kSolveLds;
     static const bool want_stamps = std::getenv("CHIP_PNP_STAMPS") != nullptr;
     if (want_stamps) {
@@ -2582,6 +2588,21 @@ static int pnp_run(Ctx *c, PnpState *st, int P, const double *const *X, const do
     }
     if (ht.on) { const double t4 = ht_now(); ht.acc[0] += ht1 - ht0; ht.acc[1] += ht2 - ht1; ht.acc[2] += ht3 - ht2; ht.acc[3] += t4 - ht3; ht.acc[4] += t4 - ht0; ht.n++; }
     return CHIP_OK;
+}
+
+int pnp_ransac_device(Ctx *c, const double *X_dev, const double *uv_dev, int32_t N, const chip_ransac_params *p, double *T_colmajor,
+                      float *confidence, uint8_t *inlier_mask, chip_ransac_summary *summary)
+{
+    if (N < 20) return CHIP_ERR_TOO_FEW_POINTS;  // DlsPnpWithRansac.cpp:136-139
+    const int32_t S = p->sample_size;
+    if (S < 3 || S > kSampleMax || S > N || p->n_hypotheses < 0 || p->max_iterations < 1) return CHIP_ERR_UNSUPPORTED;
+    if (p->sampler != CHIP_SAMPLER_FRESH && p->sampler != CHIP_SAMPLER_THEIA_PERSISTENT) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->pnp_mu);
+    CHIP_HIP(c, hipSetDevice(c->device));
+    PnpState *st = static_cast<PnpState *>(c->pnp_state);
+    if (!st) return CHIP_ERR_INVALID_ARG;
+    uint8_t *masks[1] = {inlier_mask};
+    return pnp_run(c, st, 1, &X_dev, &uv_dev, &N, p, nullptr, T_colmajor, confidence, masks, summary, true);
 }
 
 }  // namespace chip

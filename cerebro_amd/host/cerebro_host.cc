@@ -469,6 +469,104 @@ bool compute_three_way_pose(chip_ctx *ctx, const PosePairInput &in, ProcessedLoo
     return true;
 }
 
+// ---- the stage in front of the three poses
+bool StaticPointFeatureMatching::gms_point_feature_matches(chip_ctx *ctx, const float *kp1, const uint8_t *d1, int n1, int width1, int height1,
+                                                           const float *kp2, const uint8_t *d2, int n2, int width2, int height2,
+                                                           std::vector<std::array<double, 2>> &uv, std::vector<std::array<double, 2>> &uv_d)
+{
+    uv.clear();
+    uv_d.clear();
+    if (n1 <= 0 || n2 <= 0) return n1 == 0 || n2 == 0;   // no descriptors on one side: no matches
+    std::vector<int32_t> query((size_t)n1), train((size_t)n1), dist((size_t)n1);
+    if (chip_orb_match(ctx, d1, n1, d2, n2, train.data(), dist.data()) != CHIP_OK) return false;                 // :38-41
+    for (int i = 0; i < n1; i++) query[(size_t)i] = i;
+    std::vector<uint8_t> inl((size_t)n1);
+    int32_t n_inl = 0;
+    if (chip_gms_filter(ctx, kp1, n1, width1, height1, kp2, n2, width2, height2, query.data(), train.data(), n1, inl.data(), &n_inl) != CHIP_OK)
+        return false;                                                                                               // :50-52
+    for (int i = 0; i < n1; i++)                                                                                    // :60-68, MiscUtils.cpp:132-142
+        if (inl[(size_t)i]) {
+            const int t = train[(size_t)i];
+            uv.push_back({(double)kp1[2 * i], (double)kp1[2 * i + 1]});
+            uv_d.push_back({(double)kp2[2 * t], (double)kp2[2 * t + 1]});
+        }
+    return true;
+}
+
+// (int)uv(1,k), (int)uv(0,k) with the range check the reference leaves out (a pixel outside the image drops the match)
+static const float *pixel_3d(const float *img, int width, int height, const std::array<double, 2> &p)
+{
+    if (!(p[0] > -1.0 && p[0] < (double)width && p[1] > -1.0 && p[1] < (double)height)) return nullptr;
+    return img + 3 * ((size_t)(int)p[1] * (size_t)width + (size_t)(int)p[0]);
+}
+static bool depth_rejected(float z) { return z < 0.1 || z > 25.; }   // PointFeatureMatching.cpp:122: the float widened to double
+
+bool StaticPointFeatureMatching::make_3d_2d_collection__using__pfmatches_and_disparity(
+    const double Kinv[9], const std::vector<std::array<double, 2>> &uv, const float *_3dImage_uv, int width, int height,
+    const std::vector<std::array<double, 2>> &uv_d, std::vector<std::array<double, 2>> &feature_position_uv,
+    std::vector<std::array<double, 2>> &feature_position_uv_d, std::vector<std::array<double, 3>> &world_point)
+{
+    feature_position_uv.clear();
+    feature_position_uv_d.clear();
+    world_point.clear();
+    if (uv.size() != uv_d.size() || !_3dImage_uv || width <= 0 || height <= 0) return false;   // :102-110
+    const auto normalised = [&](const std::array<double, 2> &p) {                               // :114-115, rows 0 and 1 of Kinv * (u, v, 1)
+        return std::array<double, 2>{(Kinv[0] * p[0] + Kinv[1] * p[1]) + Kinv[2], (Kinv[3] * p[0] + Kinv[4] * p[1]) + Kinv[5]};
+    };
+    for (size_t k = 0; k < uv.size(); k++) {
+        const float *pt = pixel_3d(_3dImage_uv, width, height, uv[k]);                          // :121
+        if (!pt || depth_rejected(pt[2])) continue;                                             // :122-123
+        feature_position_uv.push_back(normalised(uv[k]));
+        feature_position_uv_d.push_back(normalised(uv_d[k]));
+        world_point.push_back({(double)pt[0], (double)pt[1], (double)pt[2]});
+    }
+    return true;
+}
+
+bool StaticPointFeatureMatching::make_3d_3d_collection__using__pfmatches_and_disparity(
+    const std::vector<std::array<double, 2>> &uv, const float *_3dImage_uv, int width, int height, const std::vector<std::array<double, 2>> &uv_d,
+    const float *_3dImage_uv_d, int width_d, int height_d, std::vector<std::array<double, 3>> &uv_X, std::vector<std::array<double, 3>> &uvd_Y)
+{
+    uv_X.clear();
+    uvd_Y.clear();
+    if (uv.size() != uv_d.size() || !_3dImage_uv || !_3dImage_uv_d || width <= 0 || height <= 0 || width_d <= 0 || height_d <= 0) return false;
+    for (size_t k = 0; k < uv.size(); k++) {
+        const float *pa = pixel_3d(_3dImage_uv, width, height, uv[k]), *pb = pixel_3d(_3dImage_uv_d, width_d, height_d, uv_d[k]);   // :180-181
+        if (!pa || !pb || depth_rejected(pa[2]) || depth_rejected(pb[2])) continue;                                                     // :183-184
+        uv_X.push_back({(double)pa[0], (double)pa[1], (double)pa[2]});
+        uvd_Y.push_back({(double)pb[0], (double)pb[1], (double)pb[2]});
+    }
+    return true;
+}
+
+bool verify_candidate(chip_ctx *ctx, const chip_match_frame &frame_a, const chip_match_frame &frame_b, const double Kinv[9],
+                      ProcessedLoopCandidate &pc, uint64_t seed, chip_match_summary *summary)
+{
+    chip_match_summary sm{};
+    const int rc = chip_match_pair(ctx, &frame_a, &frame_b, Kinv, &sm);
+    if (summary) *summary = sm;
+    if (rc != CHIP_OK) return false;
+    if (sm.n_matches_gms < 150) return false;                       // Cerebro.cpp:1487-1493
+    pc.pf_matches = sm.n_matches_gms;                               // :1505
+    chip_ransac_params pp, pi;
+    chip_ransac_params_default(&pp);
+    chip_icp_params_default(&pi);
+    if (seed) { pp.seed = seed; pi.seed = seed ^ 0x9E3779B97F4A7C15ull; }   // the seeds of compute_three_way_pose
+    std::array<double, 16> op1{}, op2_a_T_b{}, op2{}, icp{};
+    float g1 = -1.f, g2 = -1.f, g3 = -1.f;
+    if (chip_pnp_ransac_matched(ctx, CHIP_SET_AB, &pp, op1.data(), &g1, nullptr, nullptr) != CHIP_OK) g1 = -1.f;            // :1518
+    pp.seed += 1;
+    if (chip_pnp_ransac_matched(ctx, CHIP_SET_BA, &pp, op2_a_T_b.data(), &g2, nullptr, nullptr) != CHIP_OK) g2 = -1.f;      // :1572
+    matrix4_inverse_rigid(op2_a_T_b.data(), op2.data());                                                                    // :1582
+    if (chip_icp_ransac_matched(ctx, &pi, icp.data(), &g3, nullptr, nullptr) != CHIP_OK) g3 = -1.f;                          // :1629
+    for (int i = 0; i < 16; i++)                                    // :1678
+        if (op1[i] != op1[i] || op2[i] != op2[i] || icp[i] != icp[i]) return false;
+    if (g1 < 0 || g2 < 0 || g3 < 0) return false;
+    pc.opX_b_T_a = {op1, op2, icp};                                 // :1706-1719
+    pc.opX_goodness = {g1, g2, g3};
+    return true;
+}
+
 void matrix4_to_pose(const double T[16], double position[3], double q[4])
 {
     position[0] = T[12]; position[1] = T[13]; position[2] = T[14];

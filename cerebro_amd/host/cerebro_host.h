@@ -180,6 +180,37 @@ struct PosePairInput {
 // Returns false when one of the three poses has NaN/Inf (the candidate is skipped).
 bool compute_three_way_pose(chip_ctx *ctx, const PosePairInput &in, ProcessedLoopCandidate &proc_candi, uint64_t seed = 0);
 
+// ---------------------------------------------------------------------------------------------------------------
+// The stage in front of the three poses (src/utils/PointFeatureMatching.cpp, Cerebro.cpp:1484-1512,1566,1624), from the point where
+// ORB has run: keypoints + descriptors + 3-D images in.  Matching, GMS and the gathers run in libcerebro_hip.so
+// (include/cerebro_hip.h, "candidate verification front end", has the definitions and the departures from the reference).
+struct StaticPointFeatureMatching {
+    // gms_point_feature_matches (:5-71) without detectAndCompute: BFMatcher(NORM_HAMMING).match + gms_matcher + dmatch_2_eigen.
+    // kp*: n x 2 float pixels (cv::KeyPoint::pt), d*: n x 32 bytes; uv / uv_d: the N surviving matches as pixel pairs (the
+    // reference's 3 x N homogeneous matrices without the row of ones).  Returns false on a library error.
+    static bool gms_point_feature_matches(chip_ctx *ctx, const float *kp1, const uint8_t *d1, int n1, int width1, int height1,
+                                          const float *kp2, const uint8_t *d2, int n2, int width2, int height2,
+                                          std::vector<std::array<double, 2>> &uv, std::vector<std::array<double, 2>> &uv_d);
+    // :95-154.  _3dImage_uv: height x width x 3 float (CV_32FC3).  Kinv: row-major 3 x 3 (stereogeom->get_K().inverse()).
+    static bool make_3d_2d_collection__using__pfmatches_and_disparity(const double Kinv[9], const std::vector<std::array<double, 2>> &uv,
+                                                                      const float *_3dImage_uv, int width, int height,
+                                                                      const std::vector<std::array<double, 2>> &uv_d,
+                                                                      std::vector<std::array<double, 2>> &feature_position_uv,
+                                                                      std::vector<std::array<double, 2>> &feature_position_uv_d,
+                                                                      std::vector<std::array<double, 3>> &world_point);
+    // :159-195
+    static bool make_3d_3d_collection__using__pfmatches_and_disparity(const std::vector<std::array<double, 2>> &uv, const float *_3dImage_uv,
+                                                                      int width, int height, const std::vector<std::array<double, 2>> &uv_d,
+                                                                      const float *_3dImage_uv_d, int width_d, int height_d,
+                                                                      std::vector<std::array<double, 3>> &uv_X,
+                                                                      std::vector<std::array<double, 3>> &uvd_Y);
+};
+// One candidate, "keypoints + descriptors + 3-D images in, ready for makeLoopEdgeMsgWithConsistencyCheck out": chip_match_pair ->
+// the "< 150 matches" reject (Cerebro.cpp:1487) -> pf_matches (:1505) -> the three poses on the device-resident sets (seeds as
+// compute_three_way_pose) -> NaN gate (:1678).  One upload; nothing but counts and poses returns to the host.
+bool verify_candidate(chip_ctx *ctx, const chip_match_frame &frame_a, const chip_match_frame &frame_b, const double Kinv[9],
+                      ProcessedLoopCandidate &proc_candi, uint64_t seed = 0, chip_match_summary *summary = nullptr);
+
 // PoseManipUtils::R2ypr (src/utils/PoseManipUtils.cpp:148-163), degrees, from a column-major 4x4
 void matrix4_to_rawyprt(const double T_colmajor[16], double ypr_deg[3], double t[3]);
 void matrix4_inverse_rigid(const double T[16], double Tinv[16]);

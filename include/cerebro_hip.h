@@ -354,6 +354,90 @@ int chip_icp_ransac_collect(chip_ctx *ctx, double T_colmajor[16], float *confide
                             chip_ransac_summary *summary /* may be NULL */);
 
 
+/* ------------------------------------------------------------------------------------------ candidate verification front end
+ * Replaces what the loop-candidate consumer runs per candidate BETWEEN the descriptor scan and the three pose solves:
+ *   BFMatcher(NORM_HAMMING).match(d1, d2) over ORB descriptors          src/utils/PointFeatureMatching.cpp:38-41
+ *   gms_matcher(kp1, size1, kp2, size2, matches).GetInlierMask(.., false, false)   :50-52, src/utils/GMSMatcher/gms_matcher.{h,cpp}
+ *   the "< 150 matches" reject and pf_matches                           src/Cerebro.cpp:1487,1505
+ *   make_3d_2d_collection__using__pfmatches_and_disparity (a->b, b->a)  PointFeatureMatching.cpp:95-154, Cerebro.cpp:1512,1566
+ *   make_3d_3d_collection__using__pfmatches_and_disparity               PointFeatureMatching.cpp:159-195, Cerebro.cpp:1624
+ * ORB detection / description, rectification and the depth images stay with the caller (OpenCV).  Everything here is integer or
+ * single-operation IEEE arithmetic: the device results equal a CPU restatement (tests/np_mirror_match.py) bit for bit.
+ *
+ * Definitions (this library's, stated where the reference leans on OpenCV or leaves behaviour undefined):
+ *   - descriptors are 32 bytes (256 bits), keypoints are (x, y) float pairs = cv::KeyPoint::pt, at most CHIP_MATCH_MAX_KEYPOINTS per image;
+ *   - brute-force match: for query i the train index of minimum Hamming distance, ties -> the LOWEST train index (the first minimum
+ *     of a scan in index order, which is what OpenCV's batchDistance keeps); with n2 == 0 there are no matches (train_idx = distance = -1);
+ *   - GMS: points normalised x / width, y / height in float; left and right grid 20 x 20; four passes with the left grid shifted by
+ *     0 / half a cell in x / y / both (gms_matcher.h:143-182: floor(x * 20 [+ 0.5]) with the product rounded to float and the + 0.5 done
+ *     in double; passes 2-4 reject a shifted coordinate < 1 or >= 20, pass 1 rejects >= 20), the right cell computed once (:184-189);
+ *     per pass the 400 x 400 table of match counts per (left, right) cell, per left cell the right cell of maximal count (ties -> the
+ *     lowest right index, gms_matcher.cpp:112-121), its score = sum of the table over the 3 x 3 neighbourhoods (same offset on both
+ *     sides, neighbours outside either grid skipped), rejected iff score < 6.0 * sqrt(double(sum of the left neighbours' match counts)
+ *     / number of neighbour pairs) (:128-146); a match is an inlier iff in ANY pass its (left, right) cell pair is the accepted pair of
+ *     its left cell (:169-177).  A cell index outside [0, 400) -- keypoints outside their image, where the reference indexes out of
+ *     bounds or compares against its -1 / -2 sentinels -- makes the match take no part in that pass (right cell: in any pass);
+ *   - correspondence sets: pixel (int)u, (int)v (truncation, as PointFeatureMatching.cpp:121,180) of the H x W x 3 float image
+ *     (CV_32FC3 layout); a point is dropped iff z < 0.1 || z > 25. with the float z widened to double (:122,:182) -- so z = 0.1f passes
+ *     (0.1f > 0.1), and so does NaN, as in the reference; normalised coordinates = the first two rows of Kinv * (u, v, 1) in fp64,
+ *     (r0 * u + r1 * v) + r2 without contraction; the caller supplies Kinv (the library does not invert).  A pixel outside its 3-D
+ *     image (the reference would read out of bounds) drops the match from the sets that need that image; n_out_of_image counts the
+ *     GMS inliers with at least one such pixel.
+ * Not on chip_create_multi ctxs (CHIP_ERR_UNSUPPORTED, as chip_set_stream).  Work is enqueued on the ctx stream; one matching
+ * thread per ctx next to the appender / tick threads, like the PnP caller (cerebro_node.cpp:509); chip_set_stream must not run
+ * concurrently with these calls.  Scratch is allocated on first use and freed by chip_destroy.                                      */
+#define CHIP_MATCH_MAX_KEYPOINTS 16384
+#define CHIP_ORB_DESC_BYTES 32
+int chip_build_has_match(void);     /* 1: this build of the library contains the stage (chip_info keeps its ABI 7 layout) */
+
+int chip_orb_match(chip_ctx *ctx, const uint8_t *d1, int32_t n1, const uint8_t *d2, int32_t n2,
+                   int32_t *train_idx /* n1 */, int32_t *distance /* n1 */);
+/* kp*_xy: n* x 2 floats; matches as (query_idx[i] into kp1, train_idx[i] into kp2), CHIP_ERR_RANGE if one points outside;
+ * inlier: n_matches bytes (0 / 1) in match order */
+int chip_gms_filter(chip_ctx *ctx, const float *kp1_xy, int32_t n1, int32_t w1, int32_t h1,
+                    const float *kp2_xy, int32_t n2, int32_t w2, int32_t h2,
+                    const int32_t *query_idx, const int32_t *train_idx, int32_t n_matches,
+                    uint8_t *inlier /* n_matches */, int32_t *n_inliers);
+
+typedef struct {
+    const uint8_t *desc;      /* n x CHIP_ORB_DESC_BYTES                                      */
+    const float   *kp_xy;     /* n x 2, pixels                                                */
+    int32_t        n;
+    int32_t        width, height;   /* of the image AND of xyz                                */
+    const float   *xyz;       /* height x width x 3 (CV_32FC3), the frame's 3-D image, host   */
+} chip_match_frame;
+typedef struct {
+    int32_t n_matches_all;    /* matches_all.size()                  PointFeatureMatching.cpp:41  */
+    int32_t n_matches_gms;    /* uv.cols() = pf_matches              Cerebro.cpp:1487,1505        */
+    int32_t n_3d2d_ab;        /* world_point_uv.size()               Cerebro.cpp:1512             */
+    int32_t n_3d2d_ba;        /* world_point_uv_d.size()             Cerebro.cpp:1566             */
+    int32_t n_3d3d;           /* uv_X.size()                         Cerebro.cpp:1624             */
+    int32_t n_out_of_image;
+} chip_match_summary;
+/* The whole stage for the pair (a, b): a's descriptors are the queries, b's the train set (gms_point_feature_matches(a, b, uv, uv_d),
+ * Cerebro.cpp:1484).  One upload, nothing returns to the host in between but the six counts.  The five sets stay on the device,
+ * attached to the ctx, until the next chip_match_pair. */
+int chip_match_pair(chip_ctx *ctx, const chip_match_frame *a, const chip_match_frame *b, const double Kinv_rowmajor[9],
+                    chip_match_summary *summary);
+typedef struct {
+    double  *uv, *uv_d;               /* n_matches_gms x 2: pixels of the GMS inliers in a and in b (the float keypoints as doubles) */
+    double  *X_ab, *uvn_ab;           /* n_3d2d_ab x 3 / x 2: a's 3-D points, their normalised projections in b  */
+    double  *X_ba, *uvn_ba;           /* n_3d2d_ba x 3 / x 2: b's 3-D points, their normalised projections in a  */
+    double  *A_3d3d, *B_3d3d;         /* n_3d3d x 3 each                                                          */
+    int32_t *match_query_idx, *match_train_idx;   /* n_matches_gms each: the GMS inliers as keypoint indices      */
+} chip_match_sets_out;
+/* host copies of what the last chip_match_pair left on the device; every pointer may be NULL; capacities = that summary's counts */
+int chip_match_read_sets(chip_ctx *ctx, chip_match_sets_out *out);
+/* The existing solvers on the device-resident sets, without the host round trip: results are those of chip_pnp_ransac /
+ * chip_icp_ransac on the copied-out sets, bit for bit (same kernels, a device-pointer entry next to the host-pointer one).
+ * which: CHIP_SET_AB = PNP(world_point_uv, feature_position_uv_d) -> b_T_a (Cerebro.cpp:1518), CHIP_SET_BA = the role-swapped call
+ * -> a_T_b (:1572).  inlier_mask: that set's count bytes, may be NULL.  CHIP_ERR_BUSY before any chip_match_pair. */
+enum { CHIP_SET_AB = 0, CHIP_SET_BA = 1 };
+int chip_pnp_ransac_matched(chip_ctx *ctx, int32_t which, const chip_ransac_params *p, double T_colmajor[16], float *confidence,
+                            uint8_t *inlier_mask, chip_ransac_summary *summary /* may be NULL */);
+int chip_icp_ransac_matched(chip_ctx *ctx, const chip_ransac_params *p, double T_colmajor[16], float *confidence,
+                            uint8_t *inlier_mask, chip_ransac_summary *summary /* may be NULL */);
+
 /* ------------------------------------------------------------------------------------------ introspection */
 typedef struct {
     int32_t abi_version;

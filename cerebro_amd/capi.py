@@ -178,6 +178,10 @@ _SIGS = {
     "chip_icp_ransac_enqueue": (C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(RansacParams)]),
     "chip_icp_ransac_collect": (C.c_int, [_P, _P, C.POINTER(C.c_float), _P, C.POINTER(RansacSummary)]),
     "chip_build_has_match": (C.c_int, []),
+    "chip_build_has_tick_coalesce": (C.c_int, []),
+    "chip_debug_coalesce_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "chip_debug_coalesce_force": (C.c_int, [_P, C.c_int32]),
+    "chip_debug_coalesce_decide": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "chip_orb_match": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P]),
     "chip_gms_filter": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P,
                                   C.POINTER(C.c_int32)]),
@@ -471,6 +475,16 @@ class Chip:
 
     def last_l(self) -> int:
         return int(self.lib.chip_loop_last_l(self.h))
+
+    def coalesce_stats(self) -> tuple[int, int]:
+        """(passes that served more than one pipelined tick, ticks those passes served) -- chip_debug_coalesce_stats"""
+        passes, ticks = C.c_int64(), C.c_int64()
+        self._chk(self.lib.chip_debug_coalesce_stats(self.h, C.byref(passes), C.byref(ticks)), "chip_debug_coalesce_stats")
+        return passes.value, ticks.value
+
+    def coalesce_force(self, on: bool):
+        """tests: while on, a pipelined tick that may share a pass parks even when no scan of the ctx is running"""
+        self._chk(self.lib.chip_debug_coalesce_force(self.h, 1 if on else 0), "chip_debug_coalesce_force")
 
     def scan_local(self, l: int, dev_out_ptr: int, topk: int = CHIP_DEFAULT_TOPK, params: DotParams | None = None) -> int:
         p = params or default_dot_params()

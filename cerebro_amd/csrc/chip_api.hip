@@ -39,6 +39,7 @@ const char *chip_strerror(int status)
 
 int chip_abi_version(void) { return CHIP_ABI_VERSION; }
 int chip_build_scan_forms(void) { return scan_forms_built(); }
+int chip_build_has_tick_coalesce(void) { return 1; }
 int chip_build_test_hooks(void)
 {
 #ifdef CHIP_TEST_HOOKS
@@ -492,6 +493,7 @@ void ctx_destroy(chip_ctx *c)
     if (!c) return;
     if (c->group) { group_destroy(c); delete c; return; }
     (void)hipSetDevice(c->device);
+    { std::lock_guard<std::mutex> qlk(c->query_mu); (void)coalesce_flush(c); }   // parked ticks run like every other enqueued tick
     resident_stop(c);
     (void)hipDeviceSynchronize();
     resident_free(c);
@@ -596,7 +598,9 @@ static int create_impl(chip_ctx *c, int64_t capacity_hint, int elem)
             if (ns >= 3 + i) CHIP_HIP(c, hipStreamCreateWithFlags(&c->s_scan_x[i], hipStreamNonBlocking));
     }
     for (int i = 0; i < Ctx::kRing; i++) {
-        CHIP_HIP(c, hipMalloc(&c->partial_dev[i], (size_t)c->max_grid * CHIP_MAX_NQ * CHIP_MAX_TOPK * sizeof(chip_topk_entry)));
+        // [max_grid][CHIP_MAX_NQ][CHIP_MAX_TOPK] of one launch, or [kMultiMaxTicks][max_grid][3][CHIP_MAX_TOPK] of a pass that serves several ticks
+        constexpr size_t kListsPerGroup = 3 * kMultiMaxTicks > CHIP_MAX_NQ ? 3 * kMultiMaxTicks : CHIP_MAX_NQ;
+        CHIP_HIP(c, hipMalloc(&c->partial_dev[i], (size_t)c->max_grid * kListsPerGroup * CHIP_MAX_TOPK * sizeof(chip_topk_entry)));
         CHIP_HIP(c, hipEventCreateWithFlags(&c->ev_scan[i], hipEventDisableTiming));
         CHIP_HIP(c, hipEventCreateWithFlags(&c->ev_merged[i], hipEventDisableTiming));
     }
@@ -606,6 +610,10 @@ static int create_impl(chip_ctx *c, int64_t capacity_hint, int elem)
         CHIP_HIP(c, hipMalloc(&c->pair_ctr_dev, (size_t)Ctx::kRing * Ctx::kPairCtrs * Ctx::kPairStride * sizeof(uint32_t)));
         CHIP_HIP(c, hipMemset(c->pair_ctr_dev, 0, (size_t)Ctx::kRing * Ctx::kPairCtrs * Ctx::kPairStride * sizeof(uint32_t)));
     }
+    // pipelined ticks that arrive while a long scan is running share one DB pass: at most this many per pass (0 = never; coalesce_* below)
+    c->coalesce_max = env_int("CHIP_TICK_COALESCE", kMultiMaxTicks);
+    if (c->coalesce_max < 2) c->coalesce_max = 0;
+    if (c->coalesce_max > kMultiMaxTicks) c->coalesce_max = kMultiMaxTicks;
     c->tick_fused = env_int("CHIP_TICK_FUSED", 1) != 0;
     c->tick_poll = env_int("CHIP_TICK_POLL", 1) != 0;
     // opt-in: synchronous ticks over cache-sized prefixes go to a scan instance that stays on the chip (chip_internal.h ResidentCmd)
@@ -762,6 +770,7 @@ int enqueue_scan_merge(Ctx *c, int64_t k, const void *const *q, int nq, int K, i
     if (merge_stream) *merge_stream = s_merge;
     if (!same_stream) {
         CHIP_HIP(c, hipEventRecord(c->ev_scan[b], s_scan));
+        if (tick && !short_scan) { c->pass_ev = c->ev_scan[b]; c->pass_no++; }   // the scan later ticks may park behind (coalesce_*)
         if (c->ring_dev) c->last_scan_ev[s_scan == c->s_scan2 ? 1 : 0] = c->ev_scan[b];   // caller holds ring_mu (RingGuard)
         CHIP_HIP(c, hipStreamWaitEvent(c->s_query, c->ev_scan[b], 0));
     }
@@ -872,6 +881,130 @@ int64_t published_rows(const Ctx *c)
     return c->rows_global;
 }
 
+// One tick as a pass of its own: scan (K1) + merge and decision (K2), the slot's completion event.  query_mu held.
+static int tick_submit(Ctx *c, int64_t k, int64_t l, const chip_dot_params *p, const void *const *q, Slot &s)
+{
+    hipStream_t s_done = c->s_query;
+    hipEvent_t merged = nullptr;
+    s.poll = false;
+    if (c->tick_poll) { s.seq_want = ++c->tick_seq; c->next_seq_dev = s.seq_dev; c->next_seq_val = s.seq_want; }
+    const int rc = enqueue_scan_merge(c, k, q, 3, CHIP_DEFAULT_TOPK, l, p, nullptr, s.dev, true, &s_done, &merged);
+    c->next_seq_dev = nullptr;
+    if (rc != CHIP_OK) return rc;
+    s.poll = c->tick_poll && c->last_enqueue_fused;   // the fused kernel stores the completion word itself
+    // a same-stream tick is complete when its merge is: one event record per tick (the list buffer's merge event; the buffer is
+    // not reused before kRing = 64 further enqueues, and at most CHIP_MAX_INFLIGHT - 1 = 63 ticks are uncollected)
+    if (merged) s.wait_ev = merged;
+    else { CHIP_HIP(c, hipEventRecord(s.done, s_done)); s.wait_ev = s.done; }
+    s.pass_no = c->pass_no;
+    return CHIP_OK;
+}
+
+// ---- several pipelined ticks per DB pass ----
+// A caller that keeps ticks in flight (chip_loop_tick_enqueue ahead of chip_loop_tick_collect) has the library stream the same
+// prefix once per tick.  Ticks do not depend on one another (status and last_l are settled at enqueue, the query rows are
+// published rows), so T of them can share ONE pass with 3 T queries (kernels.hip db_scan_topk_multi): an enqueue that finds a
+// scan of this ctx still running PARKS its tick instead of launching it, and parked ticks leave together.
+//   * nothing running, nothing parked: the tick is launched at once, alone, exactly as before;
+//   * a scan running: park; the T_max-th parked tick sends all of them off as one pass;
+//   * nothing stays parked while its caller can no longer release it -- see coalesce_flush's callers (listed in cerebro_hip.h).
+// Only long scans (beyond scan_overlap_bytes: the launches that run alone on the scan stream) of a plain single-GPU ctx on its
+// own streams, float rows.  The synchronous tick, the fused / resident short ticks and the paced figures never come here.
+int coalesce_decide(int n_parked, int t_max, bool scan_running)
+{
+    if (t_max < 2) return kCoalesceLaunch;
+    if (!scan_running) return n_parked > 0 ? kCoalesceParkFlush : kCoalesceLaunch;   // the scan they parked behind has ended: leave with this one
+    return n_parked + 1 >= t_max ? kCoalesceParkFlush : kCoalescePark;
+}
+
+// most ticks a pass over [0, k) may serve on this ctx; 0: the tick does not coalesce
+static int coalesce_ticks_max(const Ctx *c, int64_t k)
+{
+    if (c->coalesce_max < 2 || c->tick_sync_now || c->nranks != 1 || c->xchg || c->parent || c->group || !c->own_query_stream) return 0;
+    if ((double)k * c->D * c->elem <= c->scan_overlap_bytes) return 0;
+    const int fit = scan_multi_max_ticks(c);
+    const int t = fit < c->coalesce_max ? fit : c->coalesce_max;
+    return t >= 2 ? t : 0;
+}
+
+// T >= 2 parked ticks as one pass: one launch of db_scan_topk_multi on the scan stream, then K2 once per tick on the ctx stream,
+// each on its own block of lists and followed by its slot's completion event.
+static int coalesce_submit(Ctx *c, int T)
+{
+    const int b = (int)(c->n_enqueued++ % Ctx::kRing);
+    const int K = CHIP_DEFAULT_TOPK;
+    MultiScanArgs a{};
+    a.seg_table = c->seg_table_dev;
+    a.seg_shift = c->seg_shift;
+    a.seg_mask = c->seg_rows - 1;
+    a.D = c->D;
+    a.K = K;
+    a.partial = c->partial_dev[b];
+    for (int t = 0; t < T; t++) {
+        a.k[t] = c->parked[t].k;
+        if (a.k[t] > a.n_rows) a.n_rows = a.k[t];
+        for (int i = 0; i < 3; i++) a.q[3 * t + i] = c->parked[t].q[i];
+    }
+    const int grid = scan_multi_grid(c);
+    c->last_enqueue_fused = false;
+    if (hipEventQuery(c->ev_merged[b]) != hipSuccess) CHIP_HIP(c, hipStreamWaitEvent(c->s_scan, c->ev_merged[b], 0));
+    hipEvent_t e1 = nullptr;
+    if (c->prof_on) {   // one event pair per pass; a pass reads the prefix once
+        while (c->prof_used + 2 > c->prof_ev.size()) {
+            hipEvent_t e;
+            CHIP_HIP(c, hipEventCreate(&e));
+            c->prof_ev.push_back(e);
+        }
+        e1 = c->prof_ev[c->prof_used + 1];
+        CHIP_HIP(c, hipEventRecord(c->prof_ev[c->prof_used], c->s_scan));
+        c->prof_used += 2;
+        c->prof_bytes_last = (double)a.n_rows * c->D * c->elem;
+    }
+    int rc = launch_scan_multi(c, c->s_scan, a, T, grid);
+    if (rc != CHIP_OK) return rc;
+    if (e1) CHIP_HIP(c, hipEventRecord(e1, c->s_scan));
+    CHIP_HIP(c, hipEventRecord(c->ev_scan[b], c->s_scan));
+    c->pass_ev = c->ev_scan[b];
+    c->pass_no++;
+    CHIP_HIP(c, hipStreamWaitEvent(c->s_query, c->ev_scan[b], 0));
+    for (int t = 0; t < T; t++) {
+        const Ctx::ParkedTick &pt = c->parked[t];
+        MergeArgs m;
+        m.in = c->partial_dev[b] + (size_t)t * grid * 3 * K;
+        m.n_lists = grid;
+        m.K = K;
+        m.out = nullptr;
+        m.result = pt.slot->dev;
+        m.l = pt.l;
+        m.locality = pt.p.locality;
+        m.thresh = pt.p.thresh;
+        rc = launch_merge(c, c->s_query, m, 3);
+        if (rc != CHIP_OK) return rc;
+        CHIP_HIP(c, hipEventRecord(pt.slot->done, c->s_query));
+        pt.slot->wait_ev = pt.slot->done;
+        pt.slot->poll = false;
+        pt.slot->pass_no = c->pass_no;
+    }
+    CHIP_HIP(c, hipEventRecord(c->ev_merged[b], c->s_query));
+    c->coalesce_passes++;
+    c->coalesce_ticks += T;
+    return CHIP_OK;
+}
+
+int coalesce_flush(Ctx *c)
+{
+    const int T = c->n_parked;
+    if (T == 0) return CHIP_OK;
+    c->n_parked = 0;
+    const Ctx::ParkedTick &p0 = c->parked[0];
+    const int rc = T == 1 ? tick_submit(c, p0.k, p0.l, &p0.p, p0.q, *p0.slot) : coalesce_submit(c, T);
+    for (int t = 0; t < T; t++) {
+        c->parked[t].slot->parked = false;
+        if (rc != CHIP_OK) c->parked[t].slot->err = rc;   // the enqueue has long returned: the tick's collect reports it
+    }
+    return rc;
+}
+
 static int tick_enqueue_slot(Ctx *c, int64_t l, const chip_dot_params *p, Slot &s)
 {
     if (s.in_flight) return CHIP_ERR_BUSY;
@@ -903,6 +1036,7 @@ static int tick_enqueue_slot(Ctx *c, int64_t l, const chip_dot_params *p, Slot &
         rc = query_row_ptrs(c, rows, 3, l, q);
         if (rc != CHIP_OK) return rc;
         if (resident_eligible(c, k)) {
+            (void)coalesce_flush(c);
             rc = resident_tick_enqueue(c, k, l, p, s);
             if (rc == CHIP_OK) {
                 s.immediate = false;
@@ -915,18 +1049,21 @@ static int tick_enqueue_slot(Ctx *c, int64_t l, const chip_dot_params *p, Slot &
             s.resident = false;
             s.poll = false;
         }
-        hipStream_t s_done = c->s_query;
-        hipEvent_t merged = nullptr;
-        s.poll = false;
-        if (c->tick_poll) { s.seq_want = ++c->tick_seq; c->next_seq_dev = s.seq_dev; c->next_seq_val = s.seq_want; }
-        rc = enqueue_scan_merge(c, k, q, 3, CHIP_DEFAULT_TOPK, l, p, nullptr, s.dev, true, &s_done, &merged);
-        c->next_seq_dev = nullptr;
-        if (rc != CHIP_OK) return rc;
-        s.poll = c->tick_poll && c->last_enqueue_fused;   // the fused kernel stores the completion word itself
-        // a same-stream tick is complete when its merge is: one event record per tick (the list buffer's merge event; the buffer is
-        // not reused before kRing = 64 further enqueues, and at most CHIP_MAX_INFLIGHT - 1 = 63 ticks are uncollected)
-        if (merged) s.wait_ev = merged;
-        else { CHIP_HIP(c, hipEventRecord(s.done, s_done)); s.wait_ev = s.done; }
+        const int t_max = coalesce_ticks_max(c, k);
+        const int act = t_max < 2 ? kCoalesceLaunch
+                                  : coalesce_decide(c->n_parked, t_max, c->coalesce_force || (c->pass_ev && hipEventQuery(c->pass_ev) == hipErrorNotReady));
+        if (act == kCoalesceLaunch) {
+            (void)coalesce_flush(c);   // submission order stays call order (a failure is reported by the collects of the ticks it concerns)
+            rc = tick_submit(c, k, l, p, q, s);
+            if (rc != CHIP_OK) return rc;
+        } else {
+            Ctx::ParkedTick &pt = c->parked[c->n_parked++];
+            pt.slot = &s; pt.k = k; pt.l = l; pt.p = *p;
+            for (int i = 0; i < 3; i++) pt.q[i] = q[i];
+            s.parked = true;
+            s.err = 0;
+            if (act == kCoalesceParkFlush) (void)coalesce_flush(c);
+        }
         s.immediate = false;
         s.in_flight = true;
     }
@@ -937,6 +1074,18 @@ static int tick_enqueue_slot(Ctx *c, int64_t l, const chip_dot_params *p, Slot &
 int tick_collect_slot(Ctx *c, Slot &s, chip_tick_result *out)
 {
     if (!s.in_flight) return CHIP_ERR_BUSY;
+    // A parked tick leaves now (with whatever is parked next to it).  A collect that is about to block on the NEWEST pass submitted
+    // sends the parked ticks off first: nothing is queued behind that pass, and the GPU would run dry until the caller returns.
+    if (s.parked) (void)coalesce_flush(c);
+    else if (c->n_parked > 0 && !s.immediate && !s.resident && s.pass_no == c->pass_no && hipEventQuery(s.wait_ev ? s.wait_ev : s.done) == hipErrorNotReady)
+        (void)coalesce_flush(c);
+    if (s.err != 0) {   // the pass this tick was part of could not be submitted: as a tick whose enqueue had failed
+        const int rc = s.err;
+        s.err = 0;
+        s.in_flight = false;
+        if (s.last_l_ptr && *s.last_l_ptr == s.tick_l) *s.last_l_ptr = s.prev_last_l;
+        return rc;
+    }
     if (!s.immediate) {
         // A fused tick's last workgroup writes the record into the slot's pinned host memory and THEN stores the slot's completion word
         // with a system-scope release: polling that word (acquire) hands the record over ~4-5 us before the stream's event would -- the
@@ -1297,6 +1446,7 @@ int chip_set_stream(chip_ctx *c, void *hip_stream)
     if (c->group || c->xchg) return CHIP_ERR_UNSUPPORTED;   // the library owns the exchange and its stream ordering
     std::lock_guard<std::mutex> lk(c->query_mu);
     CHIP_HIP(c, hipSetDevice(c->device));
+    (void)coalesce_flush(c);
     CHIP_HIP(c, hipStreamSynchronize(c->s_query));
     resident_stop(c);                       // ticks of a ctx on a caller's stream are launched behind that stream's work
     if (c->own_query_stream) CHIP_HIP(c, hipStreamDestroy(c->s_query));
@@ -1311,6 +1461,7 @@ int chip_reset_stream(chip_ctx *c)
     if (c->group) return CHIP_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> lk(c->query_mu);
     CHIP_HIP(c, hipSetDevice(c->device));
+    (void)coalesce_flush(c);
     if (c->own_query_stream) return CHIP_OK;
     CHIP_HIP(c, hipStreamSynchronize(c->s_query));
     CHIP_HIP(c, hipStreamCreateWithFlags(&c->s_query, hipStreamNonBlocking));
@@ -1323,6 +1474,7 @@ int chip_synchronize(chip_ctx *c)
     if (!c) return CHIP_ERR_INVALID_ARG;
     if (c->group) return group_synchronize(c);
     CHIP_HIP(c, hipSetDevice(c->device));
+    { std::lock_guard<std::mutex> qlk(c->query_mu); (void)coalesce_flush(c); }
     CHIP_HIP(c, hipStreamSynchronize(c->s_append));
     CHIP_HIP(c, hipStreamSynchronize(c->s_scan));
     if (c->s_scan2) CHIP_HIP(c, hipStreamSynchronize(c->s_scan2));
@@ -1347,6 +1499,7 @@ int chip_resident_pause(chip_ctx *c)
     if (!c) return CHIP_ERR_INVALID_ARG;
     if (c->group) return CHIP_OK;                 // group / sharded ctxs never run the resident instance
     (void)hipSetDevice(c->device);
+    { std::lock_guard<std::mutex> qlk(c->query_mu); (void)coalesce_flush(c); }
     resident_pause(c);
     return CHIP_OK;
 }
@@ -1419,6 +1572,7 @@ static int query_common(chip_ctx *c, int64_t k, const int64_t *query_rows, const
     if (!query_rows && !vectors) return CHIP_ERR_INVALID_ARG;
     if (c->group) return group_query(c, k, query_rows, vectors, vec_elem, nq, topk, scores, idx);
     std::lock_guard<std::mutex> qlk(c->query_mu);
+    (void)coalesce_flush(c);
     CHIP_HIP(c, hipSetDevice(c->device));
     const void *q[CHIP_MAX_NQ];
     RingGuard rg(c);
@@ -1463,6 +1617,7 @@ int chip_query_scores(chip_ctx *c, int64_t k, int64_t query_row, double *u)
     if (out_of_range && !collective) return CHIP_ERR_RANGE;
     if (c->group) return group_scores(c, k, query_row, u);
     std::lock_guard<std::mutex> qlk(c->query_mu);
+    (void)coalesce_flush(c);
     CHIP_HIP(c, hipSetDevice(c->device));
     const void *q[1];
     RingGuard rg(c);
@@ -1539,6 +1694,7 @@ int chip_scan_local(chip_ctx *c, int64_t l, const chip_dot_params *p, int32_t to
     if (topk < 1 || topk > CHIP_MAX_TOPK) return CHIP_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> qlk(c->query_mu);
     CHIP_HIP(c, hipSetDevice(c->device));
+    (void)coalesce_flush(c);
     int64_t k = 0;
     int rc = tick_prepare(published_rows(c), c->last_l, l, p, status, &k);
     if (rc == CHIP_OK && *status == CHIP_TICK_TOO_SHORT) c->last_l = l;
@@ -1564,6 +1720,7 @@ int chip_merge_decide(chip_ctx *c, int64_t l, const chip_dot_params *p, const vo
     if (topk < 1 || topk > CHIP_MAX_TOPK) return CHIP_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> qlk(c->query_mu);
     CHIP_HIP(c, hipSetDevice(c->device));
+    (void)coalesce_flush(c);
     Slot &s = c->slots[CHIP_MAX_INFLIGHT - 1];
     int rc = merge_enqueue_slot(c, l, p, dev_gathered, n_lists, topk, s);
     if (rc != CHIP_OK) return rc;
@@ -1578,6 +1735,7 @@ int chip_merge_decide_enqueue(chip_ctx *c, int64_t l, const chip_dot_params *p, 
     if (topk < 1 || topk > CHIP_MAX_TOPK) return CHIP_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> qlk(c->query_mu);
     CHIP_HIP(c, hipSetDevice(c->device));
+    (void)coalesce_flush(c);
     return merge_enqueue_slot(c, l, p, dev_gathered, n_lists, topk, c->slots[slot]);
 }
 
@@ -1620,6 +1778,32 @@ int chip_debug_resident_stats(chip_ctx *c, int64_t *ticks, int64_t *launches)
     return CHIP_OK;
 }
 
+// Several pipelined ticks per DB pass (coalesce_* above).  Passes that served more than one tick and the ticks they served, so that
+// a test can see that ticks did share a pass; CHIP_ERR_INVALID_ARG on a group.
+int chip_debug_coalesce_stats(chip_ctx *c, int64_t *passes, int64_t *ticks)
+{
+    if (!c || !passes || !ticks || c->group) return CHIP_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> qlk(c->query_mu);
+    *passes = c->coalesce_passes;
+    *ticks = c->coalesce_ticks;
+    return CHIP_OK;
+}
+
+// While on, a tick that may share a pass parks even when no scan of the ctx is running -- whether a small test scan is still running
+// when the next enqueue arrives is a race the tests must not depend on.  Everything that releases parked ticks works as always;
+// switching it off releases them.
+int chip_debug_coalesce_force(chip_ctx *c, int32_t on)
+{
+    if (!c || c->group) return CHIP_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> qlk(c->query_mu);
+    c->coalesce_force = on != 0;
+    if (!on) { (void)hipSetDevice(c->device); (void)coalesce_flush(c); }
+    return CHIP_OK;
+}
+
+// The parking policy alone (no ctx, no device): kCoalesceLaunch / Park / ParkFlush for a tick that could share a pass.
+int chip_debug_coalesce_decide(int32_t n_parked, int32_t t_max, int32_t scan_running) { return coalesce_decide(n_parked, t_max, scan_running != 0); }
+
 // ... and where its command lines live: -1 no instance has been set up yet, 0 pinned host memory + relay, 1 workgroup 0's line in
 // device memory behind the PCIe BAR + relay, 2 every workgroup's line written by the host through the BAR
 int chip_debug_resident_mode(chip_ctx *c)
@@ -1637,6 +1821,7 @@ int chip_debug_scan_stamps(chip_ctx *c, unsigned long long *out, int64_t n_waves
     if (!c || !out || c->group || !c->stamps_dev || n_waves > (int64_t)c->max_grid * 16 + 16) return CHIP_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> qlk(c->query_mu);
     CHIP_HIP(c, hipSetDevice(c->device));
+    (void)coalesce_flush(c);
     resident_stop(c);
     CHIP_HIP(c, hipDeviceSynchronize());
     CHIP_HIP(c, hipMemcpy(out, c->stamps_dev, (size_t)n_waves * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
@@ -1648,6 +1833,8 @@ int chip_profile_enable(chip_ctx *c, int32_t on)
     if (!c) return CHIP_ERR_INVALID_ARG;
     if (c->group) return group_profile_enable(c, on);
     std::lock_guard<std::mutex> qlk(c->query_mu);
+    (void)hipSetDevice(c->device);
+    (void)coalesce_flush(c);        // a pass is timed as a whole or not at all
     if (on) resident_stop(c);       // profiled launches want the chip as a launch finds it
     c->prof_on = on != 0;
     return CHIP_OK;
@@ -1658,6 +1845,8 @@ int chip_profile_reset(chip_ctx *c)
     if (!c) return CHIP_ERR_INVALID_ARG;
     if (c->group) c = static_cast<chip_ctx *>(group_root(c));
     std::lock_guard<std::mutex> qlk(c->query_mu);
+    (void)hipSetDevice(c->device);
+    (void)coalesce_flush(c);
     c->prof_used = 0;
     return CHIP_OK;
 }
@@ -1672,6 +1861,7 @@ int chip_profile_scan(chip_ctx *c, double *total_ms, int64_t *n_launches, double
     }
     std::lock_guard<std::mutex> qlk(c->query_mu);
     CHIP_HIP(c, hipSetDevice(c->device));
+    (void)coalesce_flush(c);
     CHIP_HIP(c, hipStreamSynchronize(c->s_scan));
     if (c->s_scan2) CHIP_HIP(c, hipStreamSynchronize(c->s_scan2));
     CHIP_HIP(c, hipStreamSynchronize(c->s_query));

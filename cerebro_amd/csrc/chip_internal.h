@@ -75,6 +75,20 @@ struct ResidentArgs {
                                       //    nothing but its own decision to leave
 };
 
+// ---- several ticks in one DB pass (kernels.hip db_scan_topk_multi, chip_api.hip coalesce_*) ----
+constexpr int kMultiMaxTicks = 3;                   // ticks of 3 queries each that one pass can serve (9 fp32 queries of 4096 elements = 144 KiB of LDS)
+struct MultiScanArgs {
+    const void *const *seg_table;                   // as ScanArgs (plain single-GPU ctx, float rows: global index == local row)
+    int32_t seg_shift;
+    int64_t seg_mask;
+    int64_t n_rows;                                 // rows [0, n_rows) are read: the longest prefix of the pass
+    int32_t D;
+    int32_t K;
+    int64_t k[kMultiMaxTicks];                      // tick t sees rows [0, k[t])
+    const void *q[3 * kMultiMaxTicks];              // queries of tick t: q[3 t .. 3 t + 2] (device, float, D each, 16-B aligned)
+    chip_topk_entry *partial;                       // [tick][gridDim.x][3][K]: every tick's block of lists is what ONE launch of db_scan_topk leaves
+};
+
 struct MergeArgs {
     const chip_topk_entry *in;      // [n_lists][NQ][K]
     int32_t n_lists;
@@ -92,6 +106,9 @@ struct Ctx;
 int launch_resident(Ctx *c, hipStream_t s, const ResidentArgs &ra, int grid);   // CHIP_ERR_UNSUPPORTED in a build without the rows form
 int launch_scan(Ctx *c, hipStream_t s, const ScanArgs &a, int nq, int grid);
 int launch_merge(Ctx *c, hipStream_t s, const MergeArgs &a, int nq);
+int scan_multi_max_ticks(const Ctx *c);   // ticks one pass of db_scan_topk_multi can serve on this ctx (0 / 2 / 3: storage type, D, LDS)
+int scan_multi_grid(const Ctx *c);
+int launch_scan_multi(Ctx *c, hipStream_t s, const MultiScanArgs &a, int n_ticks, int grid);
 int scan_grid_for(const Ctx *c, int64_t n_rows, int nq, bool q64);
 bool scan_q64(const Ctx *c, int nq, bool long_scan);
 int scan_rows_form(const Ctx *c, int64_t n_rows, int nq, int grid, bool q64, bool sync_tick = false);
@@ -115,6 +132,9 @@ struct Slot {
     unsigned long long seq_want = 0;    // value the fused tick in flight will store there
     bool poll = false;                  // collect by polling seq_host instead of waiting for the event
     bool resident = false;              // the tick went to the resident scan instance: there is no event, the completion word is all
+    bool parked = false;                // enqueued, not yet submitted: waits for company in Ctx::parked (chip_api.hip coalesce_*)
+    uint64_t pass_no = 0;               // Ctx::pass_no of the long scan that serves this tick
+    int32_t err = 0;                    // the pass this tick left with could not be submitted: collect returns this
     int64_t *last_l_ptr = nullptr;      // ... and where to restore it if the tick comes back CHIP_TICK_FAILED (only while no newer
                                         //     tick has been enqueued: *last_l_ptr == tick_l)
 };
@@ -238,6 +258,16 @@ struct Ctx {
     Slot slots[CHIP_MAX_INFLIGHT];
     int64_t last_l = 0;
 
+    // --- several pipelined ticks per DB pass (chip_api.hip coalesce_*; query_mu) ---
+    struct ParkedTick { Slot *slot; int64_t k, l; chip_dot_params p; const void *q[3]; };
+    int32_t coalesce_max = 3;            // CHIP_TICK_COALESCE: 0 = every tick is a pass of its own, 2 / 3 = at most that many ticks per pass
+    bool coalesce_force = false;         // chip_debug_coalesce_force: park even when no scan is running (tests)
+    ParkedTick parked[kMultiMaxTicks];
+    int32_t n_parked = 0;
+    hipEvent_t pass_ev = nullptr;        // end of the newest long scan submitted (one of ev_scan[])
+    uint64_t pass_no = 0;                // long scans submitted so far
+    int64_t coalesce_passes = 0, coalesce_ticks = 0;   // passes of more than one tick / the ticks they served (chip_debug_coalesce_stats)
+
     // --- scan tuning (resolved at create; CHIP_SCAN_* env overrides for A/B runs) ---
     int32_t scan_block = 0;       // 0 = auto
     int32_t scan_blocks_per_cu = 2;
@@ -324,6 +354,11 @@ int merge_enqueue_out(Ctx *c, const void *dev_gathered, int32_t n_lists, int nq,
 int tick_prepare(int64_t rows_global, int64_t last_l, int64_t l, const chip_dot_params *p, int32_t *status, int64_t *k_out);
 void fill_immediate(chip_tick_result *r, int32_t status);
 int tick_collect_slot(Ctx *c, Slot &s, chip_tick_result *out);
+// Parking policy of the pipelined tick (no device needed): what an enqueue does with a tick that could share a pass, given the ticks
+// already parked, the most one pass may serve and whether a scan of this ctx is still running.
+enum { kCoalesceLaunch = 0, kCoalescePark = 1, kCoalesceParkFlush = 2 };
+int coalesce_decide(int n_parked, int t_max, bool scan_running);
+int coalesce_flush(Ctx *c);     // every parked tick leaves now, together, as one pass (query_mu held); no-op with nothing parked
 int sync_topk_out(Ctx *c, int nq, int K, double *scores, int64_t *idx);
 int ctx_scores_local(Ctx *c, int64_t k, const void *q, double *u_global, int64_t stride_mul, int64_t stride_add);
 int env_int(const char *name, int dflt);

@@ -188,9 +188,9 @@ __device__ __forceinline__ void wave_topk_offer(double s, int64_t gi, int K, int
 }
 
 // Block merge: wpb sorted lists of K per query -> one sorted list of K per query in a.partial[blockIdx.x], by waves 0..NQ-1.
-template <int NQ>
-__device__ __forceinline__ void block_merge_store(const ScanArgs &a, char *smem, const double (&my_s)[NQ], const int64_t (&my_i)[NQ],
-                                                  int K, int lane, int wave, int wpb)
+template <int NQ, typename OutOf>
+__device__ __forceinline__ void block_merge_store(char *smem, const double (&my_s)[NQ], const int64_t (&my_i)[NQ],
+                                                  int K, int lane, int wave, int wpb, OutOf out_of)
 {
     __syncthreads();  // all waves done with the staged queries; reuse LDS
     chip_topk_entry *cand = reinterpret_cast<chip_topk_entry *>(smem);  // [wpb][NQ][K]
@@ -217,7 +217,7 @@ __device__ __forceinline__ void block_merge_store(const ScanArgs &a, char *smem,
                 ci[h] = t.idx;
             } else { cs[h] = -INFINITY; ci[h] = -1; }
         }
-        chip_topk_entry *outp = a.partial + ((int64_t)blockIdx.x * NQ + q) * K;
+        chip_topk_entry *outp = out_of(q);   // where this query's list of K goes
         for (int j = 0; j < K; j++) {
             double bs = cs[0];
             int64_t bi = ci[0];
@@ -240,8 +240,8 @@ __device__ __forceinline__ void block_merge_store(const ScanArgs &a, char *smem,
 
 // The same for a WAVE-UNIFORM row through the scalar cache: the table is read with s_load (constant address space; entries of
 // published rows never change), so the lookup neither costs a vector-memory round trip nor touches vmcnt.
-template <typename T>
-__device__ __forceinline__ const T *row_base_uniform(const ScanArgs &a, int64_t r)
+template <typename T, typename Args>
+__device__ __forceinline__ const T *row_base_uniform(const Args &a, int64_t r)
 {
     typedef const uint64_t __attribute__((address_space(4))) *ctab;
     const uint64_t seg = ((ctab)(uintptr_t)a.seg_table)[r >> a.seg_shift];
@@ -303,7 +303,138 @@ __global__ __launch_bounds__(1024) void db_scan_topk(ScanArgs a)
         for (int q = 0; q < NQ; q++) wave_topk_offer(acc[0][q], gi, K, lane, my_s[q], my_i[q], thr_s[q], thr_i[q]);
     }
 
-    block_merge_store<NQ>(a, smem, my_s, my_i, K, lane, wave, wpb);
+    block_merge_store<NQ>(smem, my_s, my_i, K, lane, wave, wpb, [&](int q) { return a.partial + ((int64_t)blockIdx.x * NQ + q) * K; });
+}
+
+// ------------------------------------------------------------------------------------------------ K1, several ticks per pass
+// db_scan_topk_multi<T>: ONE pass over rows [0, max k_t) answers T queued ticks of 3 queries each (chip_api.hip coalesce_*): the
+// pass is as HBM-bound as a one-tick launch, so T ticks cost one DB read.  Float rows of whole 4 KiB batches, plain ctx.
+//   * same bits: per (row, query) exactly rows_dot's order -- lane L accumulates elements j*256 + 4L + c (j ascending, c = 0..3)
+//     into one fp64 accumulator by fma, then the xor butterfly; the queries sit in LDS as fp32 ([3T][D], 144 KiB at T = 3,
+//     D = 4096) and are converted at use (fp32 x fp32 is exact in fp64 wherever the conversion happens);
+//   * register blocking: R = 4 rows per wave in flight, U = 4 KiB of each per batch (16 KiB per wave, one workgroup of 8 waves per
+//     CU), every query vector read (ds_read_b128) and converted ONCE per 4 rows: per row vector and lane 4 row conversions +
+//     3T x (1 conversion + 4 fma) = 49 VALU instructions at T = 3 against 16 (4 + 12) for one tick in db_scan_topk;
+//   * per-tick prefix: a row is offered to tick t's lists only if row < k_t (wave-uniform compare); the running lists stay in
+//     VGPRs (lane j < K: the j-th best), the admission thresholds in SGPRs;
+//   * output [tick][workgroup][3][K]: the merge + decision kernel runs unchanged, once per tick, on its own block of lists.
+constexpr int kMultiR = 4, kMultiU = 4, kMultiBlock = 512;
+
+__device__ __forceinline__ void wave_topk_offer_sthr(double s, int64_t gi, int K, int lane, double &my_s, int64_t &my_i, double &thr_s, int64_t &thr_i)
+{
+    if (key_gt(s, gi, thr_s, thr_i)) {   // wave-uniform; NaN never enters
+        const bool worse = key_gt(s, gi, my_s, my_i);
+        const unsigned long long m = __ballot(worse) & ((1ull << K) - 1ull);
+        const int pos = __builtin_ctzll(m);
+        const double up_s = __shfl_up(my_s, 1, 64);
+        const int64_t up_i = __shfl_up(my_i, 1, 64);
+        if (lane < K) {
+            if (lane > pos) { my_s = up_s; my_i = up_i; }
+            else if (lane == pos) { my_s = s; my_i = gi; }
+        }
+        thr_s = readlane_f64(my_s, K - 1);
+        thr_i = readlane_i64(my_i, K - 1);
+    }
+}
+
+template <int NTICKS>
+__global__ __launch_bounds__(kMultiBlock) void db_scan_topk_multi(MultiScanArgs a)
+{
+    constexpr int NQ = 3 * NTICKS, R = kMultiR, U = kMultiU;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float *qs = reinterpret_cast<float *>(smem);  // [NQ][D]
+    const int D = a.D;
+    const int K = a.K;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wpb = blockDim.x >> 6;
+
+    for (int e = tid * 4; e < D; e += blockDim.x * 4) {   // all 3T loads of a lane in flight together (L2-resident after the first workgroup)
+        f32x4 w[NQ];
+#pragma unroll
+        for (int q = 0; q < NQ; q++) w[q] = *as_global(reinterpret_cast<const f32x4 *>(static_cast<const float *>(a.q[q]) + e));
+#pragma unroll
+        for (int q = 0; q < NQ; q++) *reinterpret_cast<f32x4 *>(qs + q * D + e) = w[q];
+    }
+    __syncthreads();
+
+    double my_s[NQ], thr_s[NQ];
+    int64_t my_i[NQ], thr_i[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; q++) { my_s[q] = -INFINITY; my_i[q] = -1; thr_s[q] = -INFINITY; thr_i[q] = -1; }
+
+    // Row -> wave map: as db_scan_topk (wave g owns rows g, g + tw, ...), four consecutive rows of that sequence at a time -- all
+    // waves together read one window of 4 tw consecutive rows that slides through the DB.  A wave whose last rows fall beyond the
+    // pass re-reads its first row in their place (in bounds, never offered).
+    const int64_t tw = (int64_t)gridDim.x * wpb;
+    const int e0 = lane * 4;
+    for (int64_t r0 = (int64_t)blockIdx.x * wpb + wave; r0 < a.n_rows; r0 += R * tw) {
+        const float *row[R];
+#pragma unroll
+        for (int rr = 0; rr < R; rr++) {
+            const int64_t r = r0 + rr * tw;
+            row[rr] = row_base_uniform<float>(a, r < a.n_rows ? r : r0);
+        }
+        double acc[R][NQ];
+#pragma unroll
+        for (int rr = 0; rr < R; rr++)
+#pragma unroll
+            for (int q = 0; q < NQ; q++) acc[rr][q] = 0.0;
+        for (int base = 0; base < D; base += 256 * U) {
+            // the R * U loads of a batch issued back to back and consumed behind COUNTED waits (the load stream of rows_dot, NT == 6)
+            f32x4 v[R][U];
+            const char *mid[R];
+#pragma unroll
+            for (int rr = 0; rr < R; rr++) mid[rr] = reinterpret_cast<const char *>(row[rr] + base + e0) + 2048;
+#pragma unroll
+            for (int u = 0; u < U; u++)      // the first KiB of every row first: the arithmetic starts when 4 of the 16 loads are back
+#pragma unroll
+                for (int rr = 0; rr < R; rr++)
+                    asm volatile("global_load_dwordx4 %0, %1, off offset:%2 nt" : "=v"(v[rr][u]) : "v"(mid[rr]), "n"(u * 1024 - 2048) : "memory");
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                double x[R][4];
+#pragma unroll
+                for (int rr = 0; rr < R; rr++) {   // loads return in order: load (rr, u) is done once at most this many are outstanding
+                    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(v[rr][u]) : "n"((U - 1 - u) * R + (R - 1 - rr)) : "memory");
+#pragma unroll
+                    for (int c = 0; c < 4; c++) x[rr][c] = (double)v[rr][u][c];
+                }
+                const float *qv = qs + base + u * 256 + e0;
+#pragma unroll
+                for (int q = 0; q < NQ; q++) {
+                    const f32x4 w = *reinterpret_cast<const f32x4 *>(qv + q * D);
+#pragma unroll
+                    for (int c = 0; c < 4; c++) {
+                        const double wd = (double)w[c];
+#pragma unroll
+                        for (int rr = 0; rr < R; rr++) acc[rr][q] = __builtin_fma(wd, x[rr][c], acc[rr][q]);
+                    }
+                }
+            }
+        }
+        // all R x 3T butterflies first, in one basic block: they are independent, so their cross-lane round trips overlap (behind the
+        // offers' branches each would be a serial chain of six, with only two waves per SIMD to hide it)
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1)
+#pragma unroll
+            for (int rr = 0; rr < R; rr++)
+#pragma unroll
+                for (int q = 0; q < NQ; q++) acc[rr][q] = acc[rr][q] + __shfl_xor(acc[rr][q], m, 64);
+#pragma unroll
+        for (int rr = 0; rr < R; rr++) {
+            const int64_t r = r0 + rr * tw;
+            if (r < a.n_rows) {
+#pragma unroll
+                for (int q = 0; q < NQ; q++)
+                    if (r < a.k[q / 3]) wave_topk_offer_sthr(acc[rr][q], r, K, lane, my_s[q], my_i[q], thr_s[q], thr_i[q]);
+            }
+        }
+    }
+
+    block_merge_store<NQ>(smem, my_s, my_i, K, lane, wave, wpb,
+                          [&](int q) { return a.partial + (((int64_t)(q / 3) * gridDim.x + blockIdx.x) * 3 + q % 3) * K; });
 }
 
 // ------------------------------------------------------------------------------------------------ K1, wide double rows
@@ -367,7 +498,7 @@ __global__ __launch_bounds__(1024) void db_scan_topk_wide(ScanArgs a)
 #pragma unroll
         for (int q = 0; q < NQ; q++) wave_topk_offer(acc[q], gi, K, lane, my_s[q], my_i[q], thr_s[q], thr_i[q]);
     }
-    block_merge_store<NQ>(a, smem, my_s, my_i, K, lane, wave, wpb);
+    block_merge_store<NQ>(smem, my_s, my_i, K, lane, wave, wpb, [&](int q) { return a.partial + ((int64_t)blockIdx.x * NQ + q) * K; });
 }
 
 // ------------------------------------------------------------------------------------------------ K1, row-batched form
@@ -1525,6 +1656,35 @@ int launch_scan(Ctx *c, hipStream_t s, const ScanArgs &a, int nq, int grid)
         return CHIP_ERR_UNSUPPORTED;   // chip_create bounds D so that two double queries always fit
     }
     return c->elem == 8 ? launch_scan_T<double>(c, s, a, nq, grid, lds, block) : launch_scan_T<float>(c, s, a, nq, grid, lds, block);
+}
+
+// Several ticks per pass (db_scan_topk_multi).  How many ticks one pass can serve on this ctx: float rows of whole 4 KiB batches
+// on a plain ctx whose 3 T staged fp32 queries fit the LDS (D = 4096: 3; D = 8192: none) -- 0 when there is no such form.
+int scan_multi_max_ticks(const Ctx *c)
+{
+    if (c->elem != 4 || (int64_t)c->D * 4 % 4096 != 0 || c->nranks != 1 || c->scan_variant != 0 || c->scan_rows > 0) return 0;
+    const int fit = (int)((160 * 1024) / ((size_t)3 * c->D * 4));
+    return fit >= kMultiMaxTicks ? kMultiMaxTicks : (fit >= 2 ? fit : 0);
+}
+
+int scan_multi_grid(const Ctx *c) { return c->n_cus < c->max_grid ? c->n_cus : c->max_grid; }   // one 8-wave workgroup per CU
+
+template <int NTICKS>
+static int launch_scan_multi_t(Ctx *c, hipStream_t s, const MultiScanArgs &a, int grid, size_t lds)
+{
+    CHIP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(db_scan_topk_multi<NTICKS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((db_scan_topk_multi<NTICKS>), dim3(grid), dim3(kMultiBlock), lds, s, a);
+    CHIP_HIP(c, hipGetLastError());
+    return CHIP_OK;
+}
+
+int launch_scan_multi(Ctx *c, hipStream_t s, const MultiScanArgs &a, int n_ticks, int grid)
+{
+    const size_t lds_q = (size_t)3 * n_ticks * a.D * 4, lds_m = (size_t)(kMultiBlock / 64) * 3 * n_ticks * a.K * sizeof(chip_topk_entry);
+    const size_t lds = lds_q > lds_m ? lds_q : lds_m;
+    if (n_ticks < 2 || n_ticks > scan_multi_max_ticks(c) || lds > 160 * 1024 || grid < 1 || grid > c->max_grid || a.K < 1 || a.K > CHIP_MAX_TOPK)
+        return CHIP_ERR_UNSUPPORTED;
+    return n_ticks == 2 ? launch_scan_multi_t<2>(c, s, a, grid, lds) : launch_scan_multi_t<3>(c, s, a, grid, lds);
 }
 
 int launch_resident(Ctx *c, hipStream_t s, const ResidentArgs &ra, int grid)

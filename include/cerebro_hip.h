@@ -253,12 +253,34 @@ int chip_loop_tick(chip_ctx *ctx, int64_t l, const chip_dot_params *p, chip_tick
 int chip_resident_pause(chip_ctx *ctx);
 int chip_resident_resume(chip_ctx *ctx);
 /* Pipelined form: enqueue up to CHIP_MAX_INFLIGHT - 1 ticks without host synchronisation, collect later.  Scans run
- * back to back on an internal stream; the one-workgroup merge of tick i (ctx stream) overlaps the scan of tick i+1. */
+ * back to back on an internal stream; the one-workgroup merge of tick i (ctx stream) overlaps the scan of tick i+1.
+ *
+ * Ticks that share a DB pass.  Queued ticks do not depend on one another (status and last_l are settled at enqueue, the queries
+ * are published rows), so on a plain single-GPU ctx with float rows, on its own streams, an enqueue over a LONG prefix (beyond
+ * CHIP_SCAN_OVERLAP_GIB, 8 GiB) that finds a scan of the ctx still running PARKS its tick instead of launching it; parked ticks
+ * leave together as ONE pass over [0, max k) with 3 T queries (T <= CHIP_TICK_COALESCE, default 3; 0 = off), every tick seeing
+ * only its own prefix [0, k_t).  Results, status codes, CHIP_ERR_BUSY, last_l, chip_loop_reset, skipped / too-short ticks in
+ * between, appends between enqueue and collect and out-of-order collects are exactly those of ticks launched one by one.  A tick
+ * that arrives while no scan is running is launched at once, alone; chip_loop_tick, short prefixes and caller-supplied streams
+ * (chip_set_stream) never park.  Nothing stays parked while its caller cannot release it.  Parked ticks are submitted by:
+ *   chip_loop_tick_enqueue of the T-th tick, or of any tick that does not park;   chip_loop_tick_collect of a parked slot, and a
+ *   collect that is about to block on the newest pass submitted;   chip_loop_tick;   chip_query_rows / _vectors_* / _scores;
+ *   chip_scan_local, chip_merge_decide[_enqueue];   chip_synchronize, chip_destroy, chip_set_stream / chip_reset_stream,
+ *   chip_resident_pause, chip_profile_enable / _reset / _scan.
+ * A HIP failure while a pass is submitted is returned by the collect of each tick it concerned.  With profiling on a pass is one
+ * launch: one event pair, bytes_per_launch_last = the bytes of that pass. */
 #define CHIP_MAX_INFLIGHT 64
 int chip_loop_tick_enqueue(chip_ctx *ctx, int64_t l, const chip_dot_params *p, int32_t slot);
 int chip_loop_tick_collect(chip_ctx *ctx, int32_t slot, chip_tick_result *out);
 int64_t chip_loop_last_l(const chip_ctx *ctx);
 void chip_loop_reset(chip_ctx *ctx);
+int chip_build_has_tick_coalesce(void);   /* 1: this build can serve several pipelined ticks with one pass (ABI 7, additive) */
+/* Test aids.  _stats: passes that served more than one tick and the ticks they served.  _force: while on, a tick that may share a
+ * pass parks even when no scan is running (the release rules above are unchanged; switching it off releases).  _decide: the parking
+ * policy alone, no ctx: 0 launch now, 1 park, 2 park and release all, for n_parked ticks waiting, t_max per pass, a scan running or not. */
+int chip_debug_coalesce_stats(chip_ctx *ctx, int64_t *passes, int64_t *ticks);
+int chip_debug_coalesce_force(chip_ctx *ctx, int32_t on);
+int chip_debug_coalesce_decide(int32_t n_parked, int32_t t_max, int32_t scan_running);
 
 /* Sharded tick, three phases (host does the exchange between 1 and 2):
  *  1. chip_scan_local: scan this rank's share of rows [0,k), k = l - lag, for the three queries l-1,l-2,l-3 and

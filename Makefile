@@ -1,6 +1,6 @@
 # Build of the MI355X loop-detection core (gfx950 only) and of the CPU oracle (test infrastructure).
-#   make            -> cerebro_amd/lib/libcerebro_hip.so  + oracle/_build/liboracle.so
-#   make lib / make oracle / make clean
+#   make            -> cerebro_amd/lib/libcerebro_hip.so  + oracle/_build/liboracle.so  (+ oracle/_ref/libgms_ref.so, see `ref`)
+#   make lib / make oracle / make ref / make clean
 ROCM       ?= /opt/rocm
 HIPCC      ?= $(ROCM)/bin/hipcc
 ARCH       ?= gfx950
@@ -17,7 +17,7 @@ HIP_SRCS   := $(CSRC)/kernels.hip $(CSRC)/chip_api.hip $(CSRC)/chip_multi.hip $(
 HIP_OBJS   := $(HIP_SRCS:$(CSRC)/%.hip=$(LIBDIR)/%.o)
 ORC_SRCS   := $(wildcard oracle/*.c)
 
-all: lib oracle host testlibs verify
+all: lib oracle host testlibs verify ref
 lib: $(LIBDIR)/libcerebro_hip.so
 oracle: oracle/_build/liboracle.so oracle/_build/liboracle_eispack.so oracle/_build/liboracle_stats.so oracle/_build/liboracle_flops.so
 host: $(LIBDIR)/libcerebro_host.so $(LIBDIR)/cerebro_replay $(LIBDIR)/minimal_loop_detector $(LIBDIR)/sync_tick_latency $(LIBDIR)/verify_candidate
@@ -103,7 +103,25 @@ $(LIBDIR)/sync_tick_latency: examples/sync_tick_latency.cc include/cerebro_hip.h
 $(LIBDIR)/verify_candidate: examples/verify_candidate.cc $(LIBDIR)/libcerebro_host.so
 	$(CXX) -O2 -std=c++17 -Wall -Wextra examples/verify_candidate.cc -o $@ -L$(LIBDIR) -lcerebro_host -lcerebro_hip -Wl,-rpath,'$$ORIGIN' -lpthread
 
+# ---- the reference's own GMS matcher as a compiled checker (test infrastructure: tests/gms_ref_lib.py, tests/test_gms_ref_mirror.py).
+# gms_matcher.{h,cpp} are compiled BY PATH from the reference tree against the stand-in oracle/ref_gms/opencv2/opencv.hpp; nothing of
+# them is in this repository and oracle/_ref/ is git-ignored.  Plain IEEE arithmetic: no contraction, no fast-math, no -march.
+# Where there is no reference tree the goal does nothing and succeeds (a library built elsewhere travels with the checkout;
+# `make clean` leaves it alone for that reason).  -D_GLIBCXX_ASSERTIONS: a std::vector index outside its vector aborts.
+REFERENCE  ?= /root/reference
+REF_GMS    := $(REFERENCE)/src/utils/GMSMatcher
+REFFLAGS   ?= -O2 -std=c++14 -ffp-contract=off -fPIC -D_GLIBCXX_ASSERTIONS
+ifneq ($(wildcard $(REF_GMS)/gms_matcher.cpp),)
+ref: oracle/_ref/libgms_ref.so
+oracle/_ref/libgms_ref.so: oracle/ref_gms/gms_ref.cc oracle/ref_gms/opencv2/opencv.hpp $(REF_GMS)/gms_matcher.cpp $(REF_GMS)/gms_matcher.h
+	@mkdir -p oracle/_ref
+	$(CXX) $(REFFLAGS) -shared -Ioracle/ref_gms -I$(REF_GMS) oracle/ref_gms/gms_ref.cc $(REF_GMS)/gms_matcher.cpp -o $@
+else
+ref:
+	@echo "make ref: no reference tree at $(REFERENCE): nothing to build"
+endif
+
 clean:
 	rm -rf $(LIBDIR) oracle/_build tests/fakerccl/_build
 
-.PHONY: all lib oracle host testlibs verify clean
+.PHONY: all lib oracle host testlibs verify ref clean

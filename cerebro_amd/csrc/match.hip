@@ -28,7 +28,7 @@ namespace chip {
 constexpr int kMatchMax = CHIP_MATCH_MAX_KEYPOINTS;
 constexpr int kBfThreads = 256;
 constexpr int kBfTile = 1024;            // train descriptors per LDS tile: 1024 x 32 B = 32 KiB
-constexpr int kGrid = 20;                // mGridSizeLeft = Size(20, 20) (gms_matcher.h:62); right grid = left x mScaleRatios[0] = 1.0 (:230-231)
+constexpr int kGrid = 20;                // mGridSizeLeft = Size(20, 20) (gms_matcher.h:62); right grid = left x the scale ratio of index 0 = 1.0 (:46, :230-231)
 constexpr int kCells = kGrid * kGrid;    // 400
 constexpr int kOneWg = 1024;             // gms_filter / pose_sets_build: one workgroup of 16 waves
 constexpr int kMaxImageSide = 16384;

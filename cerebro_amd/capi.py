@@ -58,6 +58,9 @@ CHIP_COMM_ID_BYTES = 128
 CHIP_EXCHANGE_NONE, CHIP_EXCHANGE_RCCL, CHIP_EXCHANGE_COPY = 0, 1, 2
 CHIP_SCAN_FORM_ONE_ROW, CHIP_SCAN_FORM_ROWS = 1, 2
 CHIP_SAMPLER_FRESH, CHIP_SAMPLER_THEIA_PERSISTENT = 0, 1
+CHIP_SCAN_FAMILY_NONE, CHIP_SCAN_FAMILY_ONE_ROW, CHIP_SCAN_FAMILY_WIDE, CHIP_SCAN_FAMILY_ROWS, CHIP_SCAN_FAMILY_MULTI = 0, 1, 2, 3, 4
+CHIP_SCAN_CALL_QUERY, CHIP_SCAN_CALL_TICK, CHIP_SCAN_CALL_TICK_SYNC = 0, 1, 2
+SCAN_FAMILY_NAMES = {0: "none", 1: "one_row", 2: "wide", 3: "rows", 4: "multi"}
 
 CHIP_TICK_SKIPPED, CHIP_TICK_TOO_SHORT, CHIP_TICK_SCANNED = 0, 1, 2
 CHIP_MATCH_MAX_KEYPOINTS = 16384
@@ -117,6 +120,17 @@ class MatchSummary(C.Structure):
 class MatchSetsOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("uv", "uv_d", "X_ab", "uvn_ab", "X_ba", "uvn_ba", "A_3d3d", "B_3d3d",
                                           "match_query_idx", "match_train_idx")]
+
+
+class ScanLaunch(C.Structure):
+    """chip_debug_scan_launch: which kernel a top-k scan launch is (test aid)"""
+    _fields_ = [(n, C.c_int32) for n in ("family", "elem", "nq", "K", "U", "NT", "FULL", "NG", "R", "NTL", "ticks", "q64", "claimed", "fused",
+                                         "grid", "block", "wg_per_cu", "lds_bytes")] + [("n_rows", C.c_int64), ("launches", C.c_int64)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_}
+        d["family"] = SCAN_FAMILY_NAMES[d["family"]]
+        return d
 
 
 class Info(C.Structure):
@@ -182,6 +196,8 @@ _SIGS = {
     "chip_debug_coalesce_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "chip_debug_coalesce_force": (C.c_int, [_P, C.c_int32]),
     "chip_debug_coalesce_decide": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
+    "chip_debug_last_scan": (C.c_int, [_P, C.POINTER(ScanLaunch)]),
+    "chip_debug_scan_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(ScanLaunch)]),
     "chip_orb_match": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P]),
     "chip_gms_filter": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P,
                                   C.POINTER(C.c_int32)]),
@@ -277,6 +293,18 @@ def default_icp_params() -> RansacParams:
     p = RansacParams()
     load_library().chip_icp_params_default(C.byref(p))
     return p
+
+
+def scan_plan(D: int, elem: int, nq: int, K: int, n_rows: int, call: int = CHIP_SCAN_CALL_QUERY, n_cus: int = 256, check: bool = True):
+    """chip_debug_scan_plan: the kernel a plain single-GPU ctx created under the CURRENT environment would launch for this scan, as
+    ScanLaunch.as_dict() -- no device needed.  check=False: (status, dict) instead of raising on a status other than CHIP_OK."""
+    out = ScanLaunch()
+    rc = load_library().chip_debug_scan_plan(D, elem, nq, K, n_rows, call, n_cus, C.byref(out))
+    if not check:
+        return rc, out.as_dict()
+    if rc != CHIP_OK:
+        raise ChipError(rc, "chip_debug_scan_plan")
+    return out.as_dict()
 
 
 def comm_unique_id() -> bytes:
@@ -485,6 +513,12 @@ class Chip:
     def coalesce_force(self, on: bool):
         """tests: while on, a pipelined tick that may share a pass parks even when no scan of the ctx is running"""
         self._chk(self.lib.chip_debug_coalesce_force(self.h, 1 if on else 0), "chip_debug_coalesce_force")
+
+    def last_scan(self) -> dict:
+        """which kernel the last top-k scan of this ctx ran (chip_debug_last_scan): ScanLaunch.as_dict()"""
+        out = ScanLaunch()
+        self._chk(self.lib.chip_debug_last_scan(self.h, C.byref(out)), "chip_debug_last_scan")
+        return out.as_dict()
 
     def scan_local(self, l: int, dev_out_ptr: int, topk: int = CHIP_DEFAULT_TOPK, params: DotParams | None = None) -> int:
         p = params or default_dot_params()

@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
+#include <memory>
 #include <new>
 
 using namespace chip;
@@ -535,6 +536,33 @@ void ctx_destroy(chip_ctx *c)
     delete c;
 }
 
+// Every variable that decides WHICH scan kernel a launch is, read in one place: chip_create and the device-free planner
+// (chip_debug_scan_plan) both come here, so a plan is made under exactly the knobs a ctx created now would run under.
+void scan_read_knobs(Ctx *c)
+{
+    c->scan_block = env_int("CHIP_SCAN_BLOCK", 0);   // 0 = chosen from D per launch (kernels.hip scan_shape)
+    if (c->scan_block != 256 && c->scan_block != 512 && c->scan_block != 768 && c->scan_block != 1024) c->scan_block = 0;
+    c->scan_blocks_per_cu = env_int("CHIP_SCAN_BPC", 2);
+    if (c->scan_blocks_per_cu < 1) c->scan_blocks_per_cu = 1;
+    c->scan_variant = env_int("CHIP_SCAN_VARIANT", 0);
+    c->scan_rows = env_int("CHIP_SCAN_ROWS", 0);
+    c->scan_depth = env_int("CHIP_SCAN_DEPTH", 1);      // 1 = the product's claimed stream; 2..4: experimental forms (kernels.hip scan_rows_body)
+    if (c->scan_depth < 1 || c->scan_depth > 7) c->scan_depth = 1;
+    { const int st = env_int("CHIP_SCAN_STAGGER", 0); if (st > 0 && st < 4096) c->scan_depth |= st << 8; }   // tuning builds only (kernels.hip)
+    c->scan_claim = env_int("CHIP_SCAN_CLAIM", -1);   // -1 = auto (full-occupancy launches of the row-batched kernel), 0 = never, 1 = always
+    c->tick_same_stream = env_int("CHIP_TICK_SAME_STREAM", 1) != 0;
+    c->scan_short_bpc = env_int("CHIP_SCAN_SHORT_BPC", 1);
+    c->scan_plain_bytes = (double)env_int("CHIP_SCAN_PLAIN_MIB", 768) * 1024 * 1024;
+    c->scan_half_bytes = (double)env_int("CHIP_SCAN_HALF_MIB", 192) * 1024 * 1024;
+    c->scan_sync_plain_bytes = (double)env_int("CHIP_SCAN_SYNC_PLAIN_MIB", 4096) * 1024 * 1024;
+    c->scan_overlap_bytes = (double)env_int("CHIP_SCAN_OVERLAP_GIB", 8) * 1024 * 1024 * 1024;
+    // a sharded ctx gets three small kernels per tick through its ctx stream underneath the scans: keep slots free for them
+    c->scan_reserve = env_int("CHIP_SCAN_RESERVE", c->nranks > 1 ? 4 : 0);
+    c->max_grid = 512;  // K2 (one 512-thread workgroup) keeps one partial list per thread
+    c->scan_streams = env_int("CHIP_SCAN_STREAMS", c->nranks > 1 ? 2 : 4);   // tick streams (create_impl)
+    c->tick_fused = env_int("CHIP_TICK_FUSED", 1) != 0;
+}
+
 static int create_impl(chip_ctx *c, int64_t capacity_hint, int elem)
 {
     hipDeviceProp_t prop;
@@ -559,25 +587,7 @@ static int create_impl(chip_ctx *c, int64_t capacity_hint, int elem)
     CHIP_HIP(c, hipMalloc(&c->flags_dev, sizeof(uint32_t)));
     CHIP_HIP(c, hipHostMalloc(&c->flags_host, sizeof(uint32_t), hipHostMallocDefault));
 
-    c->scan_block = env_int("CHIP_SCAN_BLOCK", 0);   // 0 = chosen from D per launch (kernels.hip scan_shape)
-    if (c->scan_block != 256 && c->scan_block != 512 && c->scan_block != 768 && c->scan_block != 1024) c->scan_block = 0;
-    c->scan_blocks_per_cu = env_int("CHIP_SCAN_BPC", 2);
-    if (c->scan_blocks_per_cu < 1) c->scan_blocks_per_cu = 1;
-    c->scan_variant = env_int("CHIP_SCAN_VARIANT", 0);
-    c->scan_rows = env_int("CHIP_SCAN_ROWS", 0);
-    c->scan_depth = env_int("CHIP_SCAN_DEPTH", 1);      // 1 = the product's claimed stream; 2..4: experimental forms (kernels.hip scan_rows_body)
-    if (c->scan_depth < 1 || c->scan_depth > 7) c->scan_depth = 1;
-    { const int st = env_int("CHIP_SCAN_STAGGER", 0); if (st > 0 && st < 4096) c->scan_depth |= st << 8; }   // tuning builds only (kernels.hip)
-    c->scan_claim = env_int("CHIP_SCAN_CLAIM", -1);   // -1 = auto (full-occupancy launches of the row-batched kernel), 0 = never, 1 = always
-    c->tick_same_stream = env_int("CHIP_TICK_SAME_STREAM", 1) != 0;
-    c->scan_short_bpc = env_int("CHIP_SCAN_SHORT_BPC", 1);
-    c->scan_plain_bytes = (double)env_int("CHIP_SCAN_PLAIN_MIB", 768) * 1024 * 1024;
-    c->scan_half_bytes = (double)env_int("CHIP_SCAN_HALF_MIB", 192) * 1024 * 1024;
-    c->scan_sync_plain_bytes = (double)env_int("CHIP_SCAN_SYNC_PLAIN_MIB", 4096) * 1024 * 1024;
-    c->scan_overlap_bytes = (double)env_int("CHIP_SCAN_OVERLAP_GIB", 8) * 1024 * 1024 * 1024;
-    // a sharded ctx gets three small kernels per tick through its ctx stream underneath the scans: keep slots free for them
-    c->scan_reserve = env_int("CHIP_SCAN_RESERVE", c->nranks > 1 ? 4 : 0);
-    c->max_grid = 512;  // K2 (one 512-thread workgroup) keeps one partial list per thread
+    scan_read_knobs(c);
     {
         const int pr = env_int("CHIP_SCAN_STREAM_PRIORITY", 0);   // tuning only: 0 = default class, 1 = highest, -1 = lowest
         if (pr == 0) CHIP_HIP(c, hipStreamCreateWithFlags(&c->s_scan, hipStreamNonBlocking));
@@ -592,7 +602,7 @@ static int create_impl(chip_ctx *c, int64_t capacity_hint, int elem)
         // is ~37 us of scan, ~15 us of one-workgroup merge and ~12 us of launch / event gap per stream (rocprofv3 timeline,
         // profiles/r03_tick_timeline_10k.md), so two streams leave the memory system idle a third of the time.  Sharded / group
         // contexts (merge + exchange on the ctx stream) use the first two only.
-        const int ns = env_int("CHIP_SCAN_STREAMS", c->nranks > 1 ? 2 : 4);
+        const int ns = c->scan_streams;
         if (ns >= 2) CHIP_HIP(c, hipStreamCreateWithFlags(&c->s_scan2, hipStreamNonBlocking));
         for (int i = 0; i < 2; i++)
             if (ns >= 3 + i) CHIP_HIP(c, hipStreamCreateWithFlags(&c->s_scan_x[i], hipStreamNonBlocking));
@@ -614,7 +624,6 @@ static int create_impl(chip_ctx *c, int64_t capacity_hint, int elem)
     c->coalesce_max = env_int("CHIP_TICK_COALESCE", kMultiMaxTicks);
     if (c->coalesce_max < 2) c->coalesce_max = 0;
     if (c->coalesce_max > kMultiMaxTicks) c->coalesce_max = kMultiMaxTicks;
-    c->tick_fused = env_int("CHIP_TICK_FUSED", 1) != 0;
     c->tick_poll = env_int("CHIP_TICK_POLL", 1) != 0;
     // opt-in: synchronous ticks over cache-sized prefixes go to a scan instance that stays on the chip (chip_internal.h ResidentCmd)
     c->tick_resident = env_int("CHIP_TICK_RESIDENT", 0) != 0 && (scan_forms_built() & CHIP_SCAN_FORM_ROWS) != 0;
@@ -679,6 +688,27 @@ int ctx_create(chip_ctx **out, int32_t D, int64_t capacity_hint, int32_t device,
     return CHIP_OK;
 }
 
+bool scan_policy(const Ctx *c, int64_t n_local, int nq, bool sync_tick, ScanArgs *a, int *grid)
+{
+    const double bytes = (double)n_local * c->D * c->elem;
+    const bool short_scan = bytes <= c->scan_overlap_bytes;
+    a->q64 = scan_q64(c, nq, !short_scan) ? 1 : 0;
+    *grid = scan_grid_for(c, n_local, nq, a->q64 != 0);
+    a->rows_form = scan_rows_form(c, n_local, nq, *grid, a->q64 != 0, sync_tick);
+    a->plain_loads = bytes <= c->scan_plain_bytes ? 1 : 0;
+    // rows claimed within the workgroup: measured -2 % on the synchronous 29k / 45k tick (two workgroups per CU), neutral at 10k (one
+    // workgroup per CU: the launch is too short for the waves to drift apart) -- profiles/r05_short_scan.md
+    a->dyn_claim = (a->rows_form == 1 && (c->scan_claim == 1 || (c->scan_claim < 0 && *grid > c->n_cus))) ? c->scan_depth : 0;
+    return short_scan;
+}
+
+// fused tick: one launch (kernels.hip fused_tick_finish) -- same-stream short ticks through the row-batched kernel, decision wanted,
+// no list output
+bool scan_tick_fused(const Ctx *c, bool same_stream, const ScanArgs &a, bool decision_only, int nq)
+{
+    return same_stream && a.rows_form > 0 && c->tick_fused && decision_only && nq == 3;
+}
+
 // Enqueue K1 (scan + per-workgroup top-k, on s_scan) and K2 (cross-workgroup merge [+ accept decision], on the ctx
 // stream behind an event) for nq queries over the global prefix [0,k).  out (device or pinned host, optional) gets
 // [nq][K]; res (optional) the decision record of Cerebro.cpp:1056.  Consecutive calls pipeline: scans run back to
@@ -693,7 +723,9 @@ int enqueue_scan_merge(Ctx *c, int64_t k, const void *const *q, int nq, int K, i
     // 125k 317 -> 308, 500k 1191 -> 1157; at 1M the gain is < 1 %, and launches that overlap would no longer have a
     // meaningful per-launch duration for the roofline, so long scans and profiled runs stay on one stream).  Anything that
     // uploads its queries on s_scan first stays on s_scan.
-    const bool short_scan = (double)local_count(c, k) * c->D * c->elem <= c->scan_overlap_bytes;
+    ScanArgs a;
+    int grid = 0;
+    const bool short_scan = scan_policy(c, local_count(c, k), nq, tick && c->tick_sync_now, &a, &grid);
     hipStream_t s_scan = (tick && short_scan && !c->prof_on && c->s_scan2 && (c->n_enqueued & 1)) ? c->s_scan2 : c->s_scan;
     // (same-stream short ticks rotate over all tick streams: see below)
     const bool same_stream = tick && short_scan && !c->prof_on && c->nranks == 1 && !c->xchg && !c->parent && c->own_query_stream &&
@@ -704,7 +736,6 @@ int enqueue_scan_merge(Ctx *c, int64_t k, const void *const *q, int nq, int K, i
         while (ns < 4 && ring[ns]) ns++;
         s_scan = ring[c->n_same_stream++ % (uint64_t)ns];
     }
-    ScanArgs a;
     a.seg_table = c->seg_table_dev;
     a.seg_shift = c->seg_shift;
     a.seg_mask = c->seg_rows - 1;
@@ -715,17 +746,8 @@ int enqueue_scan_merge(Ctx *c, int64_t k, const void *const *q, int nq, int K, i
     a.idx_mul = c->nranks;
     a.idx_add = c->nranks == 1 ? 0 : c->rank;
     a.partial = c->partial_dev[b];
-    a.q64 = scan_q64(c, nq, !short_scan) ? 1 : 0;
-    const int grid = scan_grid_for(c, a.n_rows, nq, a.q64 != 0);
-    a.rows_form = scan_rows_form(c, a.n_rows, nq, grid, a.q64 != 0, tick && c->tick_sync_now);
-    a.plain_loads = (double)a.n_rows * c->D * c->elem <= c->scan_plain_bytes ? 1 : 0;
     a.stamps = c->stamps_dev;
-    // rows claimed within the workgroup: measured -2 % on the synchronous 29k / 45k tick (two workgroups per CU), neutral at 10k (one
-    // workgroup per CU: the launch is too short for the waves to drift apart) -- profiles/r05_short_scan.md
-    a.dyn_claim = (a.rows_form == 1 && (c->scan_claim == 1 || (c->scan_claim < 0 && grid > c->n_cus))) ? c->scan_depth : 0;
-    // fused tick: one launch (kernels.hip fused_tick_finish) -- same-stream short ticks through the row-batched kernel, decision wanted,
-    // no list output
-    const bool fused = same_stream && a.rows_form > 0 && c->tick_fused && res != nullptr && out == nullptr && nq == 3 && p != nullptr;
+    const bool fused = scan_tick_fused(c, same_stream, a, res != nullptr && out == nullptr && p != nullptr, nq);
     if (fused) {
         a.K = 1;
         a.fused_result = res;
@@ -1803,6 +1825,47 @@ int chip_debug_coalesce_force(chip_ctx *c, int32_t on)
 
 // The parking policy alone (no ctx, no device): kCoalesceLaunch / Park / ParkFlush for a tick that could share a pass.
 int chip_debug_coalesce_decide(int32_t n_parked, int32_t t_max, int32_t scan_running) { return coalesce_decide(n_parked, t_max, scan_running != 0); }
+
+// WHICH kernel the last top-k scan of this ctx was (launch_scan / launch_scan_multi keep the record where they choose the
+// instantiation); parked ticks are submitted first, so that the record is the launch of the calls made so far.
+int chip_debug_last_scan(chip_ctx *c, chip_debug_scan_launch *out)
+{
+    if (!c || !out || c->group) return CHIP_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> qlk(c->query_mu);
+    (void)hipSetDevice(c->device);
+    (void)coalesce_flush(c);
+    *out = c->last_scan;
+    return CHIP_OK;
+}
+
+// The same record without a device: a ctx that exists on the host only (D, storage type, CU count, the knobs of the environment as
+// chip_create reads them), then the functions the enqueue path runs -- scan_policy, scan_tick_fused, scan_select.  A plain
+// single-GPU ctx on its own streams, profiling off, the resident instance off.
+int chip_debug_scan_plan(int32_t D, int32_t elem, int32_t nq, int32_t K, int64_t n_rows, int32_t call, int32_t n_cus, chip_debug_scan_launch *out)
+{
+    if (!out || D <= 0 || (elem != 4 && elem != 8) || nq < 1 || nq > CHIP_MAX_NQ || K < 1 || K > CHIP_MAX_TOPK || n_rows < 0 || n_cus < 1 ||
+        call < CHIP_SCAN_CALL_QUERY || call > CHIP_SCAN_CALL_TICK_SYNC)
+        return CHIP_ERR_INVALID_ARG;
+    // what chip_create refuses (ctx_create)
+    if (D % 4 != 0 || (size_t)D * 4 * CHIP_MAX_NQ > 160 * 1024 || (elem == 8 && (size_t)D * 8 * 2 > 160 * 1024)) return CHIP_ERR_UNSUPPORTED;
+    std::unique_ptr<Ctx> c(new (std::nothrow) Ctx());
+    if (!c) return CHIP_ERR_OOM;
+    c->D = D;
+    c->elem = elem;
+    c->n_cus = n_cus;
+    scan_read_knobs(c.get());
+    const bool tick = call != CHIP_SCAN_CALL_QUERY;
+    ScanArgs a{};
+    int grid = 0;
+    const bool short_scan = scan_policy(c.get(), n_rows, nq, call == CHIP_SCAN_CALL_TICK_SYNC, &a, &grid);
+    a.n_rows = n_rows;
+    a.D = D;
+    a.K = K;
+    const bool same_stream = tick && short_scan && c->scan_streams >= 2 && c->tick_same_stream;   // (enqueue_scan_merge, on a plain ctx)
+    chip_tick_result dummy;
+    if (scan_tick_fused(c.get(), same_stream, a, tick, nq)) { a.K = 1; a.fused_result = &dummy; }
+    return scan_select(c.get(), a, nq, grid, out);
+}
 
 // ... and where its command lines live: -1 no instance has been set up yet, 0 pinned host memory + relay, 1 workgroup 0's line in
 // device memory behind the PCIe BAR + relay, 2 every workgroup's line written by the host through the BAR

@@ -112,6 +112,9 @@ int launch_scan_multi(Ctx *c, hipStream_t s, const MultiScanArgs &a, int n_ticks
 int scan_grid_for(const Ctx *c, int64_t n_rows, int nq, bool q64);
 bool scan_q64(const Ctx *c, int nq, bool long_scan);
 int scan_rows_form(const Ctx *c, int64_t n_rows, int nq, int grid, bool q64, bool sync_tick = false);
+// Which instantiation a launch of K1 is (family, template arguments, shape, LDS): the ONE place that chooses it.  launch_scan launches
+// what this says and keeps the record (Ctx::last_scan, chip_debug_last_scan); chip_debug_scan_plan calls it on a ctx without a device.
+int scan_select(const Ctx *c, const ScanArgs &a, int nq, int grid, chip_debug_scan_launch *f);
 int scan_forms_built();              // CHIP_SCAN_FORM_* bits of this build (-DCHIP_NO_ROWS_FORM leaves the row-batched kernel out)
 int launch_scores(Ctx *c, hipStream_t s, const ScanArgs &a, double *out_dev);   // K1s: all scores of one query, out[local row]
 int launch_store_rows(Ctx *c, hipStream_t s, const void *src, int src_elem, int64_t n, int64_t first_global, uint32_t *flags_dev, bool write_ring,
@@ -267,12 +270,14 @@ struct Ctx {
     hipEvent_t pass_ev = nullptr;        // end of the newest long scan submitted (one of ev_scan[])
     uint64_t pass_no = 0;                // long scans submitted so far
     int64_t coalesce_passes = 0, coalesce_ticks = 0;   // passes of more than one tick / the ticks they served (chip_debug_coalesce_stats)
+    chip_debug_scan_launch last_scan{};  // the last top-k scan launched (launch_scan / launch_scan_multi; query_mu): chip_debug_last_scan
 
     // --- scan tuning (resolved at create; CHIP_SCAN_* env overrides for A/B runs) ---
     int32_t scan_block = 0;       // 0 = auto
     int32_t scan_blocks_per_cu = 2;
     int32_t scan_reserve = 0;
     int32_t scan_variant = 0;
+    int32_t scan_streams = 4;      // CHIP_SCAN_STREAMS: tick streams created (1: s_scan alone, 2: + s_scan2, 3 / 4: + s_scan_x)
     bool tick_same_stream = true;  // short ticks of a plain ctx: merge on the scan's stream (CHIP_TICK_SAME_STREAM=0 disables)
     int32_t scan_depth = 1;       // CHIP_SCAN_DEPTH: batches of a wave's load stream in flight in the claimed row-batched kernel (1 or 2)
     int32_t scan_claim = -1;      // CHIP_SCAN_CLAIM: rows claimed within the workgroup (row-batched kernel, R = 1): -1 auto, 0 never (static row -> wave map), 1 always
@@ -362,6 +367,12 @@ int coalesce_flush(Ctx *c);     // every parked tick leaves now, together, as on
 int sync_topk_out(Ctx *c, int nq, int K, double *scores, int64_t *idx);
 int ctx_scores_local(Ctx *c, int64_t k, const void *q, double *u_global, int64_t stride_mul, int64_t stride_add);
 int env_int(const char *name, int dflt);
+void scan_read_knobs(Ctx *c);   // every CHIP_SCAN_* / CHIP_TICK_* variable that decides WHICH scan is launched -> Ctx (chip_create and chip_debug_scan_plan)
+// The per-launch policy of a top-k scan over n_local rows: a.q64, a.rows_form, a.plain_loads, a.dyn_claim and the grid.  Returns whether
+// the scan is a short one (up to scan_overlap_bytes).
+bool scan_policy(const Ctx *c, int64_t n_local, int nq, bool sync_tick, ScanArgs *a, int *grid);
+// A tick as ONE launch (kernels.hip fused_tick_finish): same-stream short ticks through the row-batched kernel, decision wanted, no list output
+bool scan_tick_fused(const Ctx *c, bool same_stream, const ScanArgs &a, bool decision_only, int nq);
 void resident_stop(Ctx *c);    // retire the resident scan instance and wait until it has left the chip (no-op without one): called before
                                // anything that rewrites the segment table, frees device memory or wants the chip to itself
 // resident_stop + NO new instance until resident_resume: ticks that arrive meanwhile are launched.  For sections that free / allocate

@@ -1452,54 +1452,51 @@ static int launch_scan_k(Ctx *c, hipStream_t s, const ScanArgs &a, int grid, siz
     return CHIP_OK;
 }
 
-template <typename T, int NQ, int U, int NT, int R>
-static int launch_scan_t(Ctx *c, hipStream_t s, const ScanArgs &a, int grid, size_t lds, int block)
-{
-    return a.D % (64 * Vec16<T>::N * U) == 0 ? launch_scan_k<T, NQ, U, true, NT, R>(c, s, a, grid, lds, block)
-                                             : launch_scan_k<T, NQ, U, false, NT, R>(c, s, a, grid, lds, block);
-}
-
 // Load path of K1.  Production (scan_variant 0): 4 x 16-B non-temporal loads per lane issued back to back from inline asm and
 // consumed behind counted waits (rows_dot, NT == 6) -- with compiler-scheduled loads (variant 1, the round-1 kernel: U = 8
 // builtin loads) hipcc sinks each load next to its use and a wave runs with 1-2 KiB in flight at 110 VGPRs; the asm form
 // keeps 4 KiB per wave in flight at 66 VGPRs (short scans +5-7 %, 1M rows equal: profiles/r02_scan_load_path.txt).  Rows
 // of whole 2 KiB batches use 2 loads per batch (D = 1536: +6 %); anything else (D * elem % 2048 != 0) takes the builtin path.
 // CHIP_SCAN_VARIANT >= 2: further A/B variants, only in builds with -DCHIP_SCAN_TUNING_VARIANTS.
+// The choice itself is scan_select() below; this launches the instantiation a record names -- one that does not exist is an error.
 template <typename T, int NQ>
-static int launch_scan_q(Ctx *c, hipStream_t s, const ScanArgs &a, int grid, size_t lds, int block)
+static int launch_scan_q(Ctx *c, hipStream_t s, const ScanArgs &a, const chip_debug_scan_launch &f)
 {
-#ifdef CHIP_SCAN_TUNING_VARIANTS
-    switch (c->scan_variant) {
-        case 2: return launch_scan_t<T, NQ, 16, 1, 1>(c, s, a, grid, lds, block);
-        case 3: return launch_scan_t<T, NQ, 8, 0, 1>(c, s, a, grid, lds, block);
-        case 4: return launch_scan_t<T, NQ, 4, 1, 1>(c, s, a, grid, lds, block);
-        case 7: return launch_scan_t<T, NQ, 8, 2, 1>(c, s, a, grid, lds, block);
-        case 8: return launch_scan_t<T, NQ, 8, 3, 1>(c, s, a, grid, lds, block);
-        case 9: return launch_scan_t<T, NQ, 8, 4, 1>(c, s, a, grid, lds, block);
-        case 10: return launch_scan_t<T, NQ, 8, 5, 1>(c, s, a, grid, lds, block);
-        case 11: if ((int64_t)a.D * sizeof(T) % 8192 == 0) return launch_scan_k<T, NQ, 8, true, 6, 1>(c, s, a, grid, lds, block); break;
-        default: break;
-    }
-#endif
-    if constexpr (sizeof(T) == 4) {
-        if (a.q64) return launch_scan_k<T, NQ, 4, true, 8, 1>(c, s, a, grid, lds, block);   // scan_q64() said so (float rows only)
-    }
+    const int grid = f.grid, block = f.block;
+    const size_t lds = (size_t)f.lds_bytes;
+    if (f.family == CHIP_SCAN_FAMILY_ROWS) {   // scan_rows_form() said so: whole 4 KiB batches, R rows per wave in one continuous load stream
 #ifndef CHIP_NO_ROWS_FORM
-    if (a.rows_form > 0) {   // scan_rows_form() said so: whole 4 KiB batches, R rows per wave in one continuous load stream
-        const bool ntl = a.plain_loads == 0;
+        const bool ntl = f.NTL != 0;
         if constexpr (NQ <= 3) {   // (four queries x R > 1 rows of accumulators do not fit the compiler's 80 registers: R = 1 only)
-            if (a.rows_form >= 3) return ntl ? launch_scan_rows<T, NQ, 3, true>(c, s, a, grid, lds, block) : launch_scan_rows<T, NQ, 3, false>(c, s, a, grid, lds, block);
-            if (a.rows_form == 2) return ntl ? launch_scan_rows<T, NQ, 2, true>(c, s, a, grid, lds, block) : launch_scan_rows<T, NQ, 2, false>(c, s, a, grid, lds, block);
+            if (f.R == 3) return ntl ? launch_scan_rows<T, NQ, 3, true>(c, s, a, grid, lds, block) : launch_scan_rows<T, NQ, 3, false>(c, s, a, grid, lds, block);
+            if (f.R == 2) return ntl ? launch_scan_rows<T, NQ, 2, true>(c, s, a, grid, lds, block) : launch_scan_rows<T, NQ, 2, false>(c, s, a, grid, lds, block);
         }
-        return ntl ? launch_scan_rows<T, NQ, 1, true>(c, s, a, grid, lds, block) : launch_scan_rows<T, NQ, 1, false>(c, s, a, grid, lds, block);
-    }
+        if (f.R == 1) return ntl ? launch_scan_rows<T, NQ, 1, true>(c, s, a, grid, lds, block) : launch_scan_rows<T, NQ, 1, false>(c, s, a, grid, lds, block);
 #endif
-    if (c->scan_variant != 1) {   // rows of whole 4 KiB / 2 KiB batches (one load per batch measured slower than the builtin path)
-        const int64_t row_bytes = (int64_t)a.D * sizeof(T);
-        if (row_bytes % 4096 == 0) return launch_scan_k<T, NQ, 4, true, 6, 1>(c, s, a, grid, lds, block);
-        if (row_bytes % 2048 == 0) return launch_scan_k<T, NQ, 2, true, 6, 1>(c, s, a, grid, lds, block);
+        return CHIP_ERR_UNSUPPORTED;
     }
-    return launch_scan_t<T, NQ, 8, 1, 1>(c, s, a, grid, lds, block);
+    if (f.family != CHIP_SCAN_FAMILY_ONE_ROW) return CHIP_ERR_UNSUPPORTED;
+    const bool full = f.FULL != 0;
+    if constexpr (sizeof(T) == 4) {
+        if (f.U == 4 && f.NT == 8 && full) return launch_scan_k<T, NQ, 4, true, 8, 1>(c, s, a, grid, lds, block);   // scan_q64() said so (float rows only)
+    }
+    if (f.U == 4 && f.NT == 6 && full) return launch_scan_k<T, NQ, 4, true, 6, 1>(c, s, a, grid, lds, block);
+    if (f.U == 2 && f.NT == 6 && full) return launch_scan_k<T, NQ, 2, true, 6, 1>(c, s, a, grid, lds, block);
+#define CHIP_SCAN_EITHER(U_, NT_) \
+    if (f.U == U_ && f.NT == NT_) return full ? launch_scan_k<T, NQ, U_, true, NT_, 1>(c, s, a, grid, lds, block) : launch_scan_k<T, NQ, U_, false, NT_, 1>(c, s, a, grid, lds, block);
+    CHIP_SCAN_EITHER(8, 1)
+#ifdef CHIP_SCAN_TUNING_VARIANTS
+    CHIP_SCAN_EITHER(16, 1)
+    CHIP_SCAN_EITHER(8, 0)
+    CHIP_SCAN_EITHER(4, 1)
+    CHIP_SCAN_EITHER(8, 2)
+    CHIP_SCAN_EITHER(8, 3)
+    CHIP_SCAN_EITHER(8, 4)
+    CHIP_SCAN_EITHER(8, 5)
+    if (f.U == 8 && f.NT == 6 && full) return launch_scan_k<T, NQ, 8, true, 6, 1>(c, s, a, grid, lds, block);
+#endif
+#undef CHIP_SCAN_EITHER
+    return CHIP_ERR_UNSUPPORTED;
 }
 
 // Workgroup shape of K1.  The nq query descriptors sit in LDS (nq*D*elem bytes per workgroup), so the shape follows D:
@@ -1618,44 +1615,117 @@ int scan_grid_for(const Ctx *c, int64_t n_rows, int nq, bool q64)
 }
 
 template <typename T>
-static int launch_scan_T(Ctx *c, hipStream_t s, const ScanArgs &a, int nq, int grid, size_t lds, int block)
+static int launch_scan_T(Ctx *c, hipStream_t s, const ScanArgs &a, const chip_debug_scan_launch &f)
 {
-    switch (nq) {
-        case 1: return launch_scan_q<T, 1>(c, s, a, grid, lds, block);
-        case 2: return launch_scan_q<T, 2>(c, s, a, grid, lds, block);
-        case 3: return launch_scan_q<T, 3>(c, s, a, grid, lds, block);
-        case 4: return launch_scan_q<T, 4>(c, s, a, grid, lds, block);
+    switch (f.nq) {
+        case 1: return launch_scan_q<T, 1>(c, s, a, f);
+        case 2: return launch_scan_q<T, 2>(c, s, a, f);
+        case 3: return launch_scan_q<T, 3>(c, s, a, f);
+        case 4: return launch_scan_q<T, 4>(c, s, a, f);
     }
     return CHIP_ERR_UNSUPPORTED;
 }
 
 template <int NQ, int NG>
-static int launch_scan_wide(Ctx *c, hipStream_t s, const ScanArgs &a, int grid, size_t lds, int block)
+static int launch_scan_wide(Ctx *c, hipStream_t s, const ScanArgs &a, const chip_debug_scan_launch &f)
 {
-    if (a.D % 512 == 0) {
-        CHIP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(db_scan_topk_wide<NQ, NG, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int grid = f.grid, block = f.block, lds = f.lds_bytes;
+    if (f.FULL) {
+        CHIP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(db_scan_topk_wide<NQ, NG, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         hipLaunchKernelGGL((db_scan_topk_wide<NQ, NG, true>), dim3(grid), dim3(block), lds, s, a);
     } else {
-        CHIP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(db_scan_topk_wide<NQ, NG, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        CHIP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(db_scan_topk_wide<NQ, NG, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         hipLaunchKernelGGL((db_scan_topk_wide<NQ, NG, false>), dim3(grid), dim3(block), lds, s, a);
     }
     CHIP_HIP(c, hipGetLastError());
     return CHIP_OK;
 }
 
-int launch_scan(Ctx *c, hipStream_t s, const ScanArgs &a, int nq, int grid)
+// WHICH kernel a launch of K1 is: family, template arguments, shape and LDS, from the ctx (knobs, D, storage type), the per-launch
+// policy already in `a` (q64, rows_form, plain_loads, dyn_claim, K, the fused tick) and the grid.  Needs no device.
+int scan_select(const Ctx *c, const ScanArgs &a, int nq, int grid, chip_debug_scan_launch *f)
 {
+    *f = chip_debug_scan_launch{};
+    if (nq < 1 || nq > CHIP_MAX_NQ) return CHIP_ERR_UNSUPPORTED;
     int block, bpc;
     scan_shape(c, nq, a.q64 != 0, &block, &bpc);
     const size_t lds = scan_lds_bytes(c, nq, a.K, block, a.q64 != 0, a.rows_form > 0);
     if (lds > 160 * 1024 || grid > 512) return CHIP_ERR_UNSUPPORTED;  // K2 holds one partial list per thread
+    f->elem = c->elem;
+    f->nq = nq;
+    f->K = a.K;
+    f->q64 = a.q64 != 0;
+    f->fused = a.fused_result != nullptr;
+    f->grid = grid;
+    f->block = block;
+    f->wg_per_cu = bpc;
+    f->lds_bytes = (int32_t)lds;
+    f->n_rows = a.n_rows;
+    const int64_t row_bytes = (int64_t)c->D * c->elem;
     if (const int ng = scan_wide_ng(c, nq); ng > 0 && !a.q64 && a.rows_form == 0) {   // double rows wider than the LDS holds nq queries of
-        if (nq == 3 && ng == 1) return launch_scan_wide<3, 1>(c, s, a, grid, lds, block);
-        if (nq == 4 && ng == 1) return launch_scan_wide<4, 1>(c, s, a, grid, lds, block);
-        if (nq == 4 && ng == 2) return launch_scan_wide<4, 2>(c, s, a, grid, lds, block);
-        return CHIP_ERR_UNSUPPORTED;   // chip_create bounds D so that two double queries always fit
+        if (!((nq == 3 && ng == 1) || (nq == 4 && (ng == 1 || ng == 2)))) return CHIP_ERR_UNSUPPORTED;   // chip_create bounds D so that two double queries always fit
+        f->family = CHIP_SCAN_FAMILY_WIDE;
+        f->NG = ng;
+        f->FULL = c->D % 512 == 0;
+        return CHIP_OK;
     }
-    return c->elem == 8 ? launch_scan_T<double>(c, s, a, nq, grid, lds, block) : launch_scan_T<float>(c, s, a, nq, grid, lds, block);
+    f->family = CHIP_SCAN_FAMILY_ONE_ROW;
+    f->R = 1;
+#ifdef CHIP_SCAN_TUNING_VARIANTS
+    {
+        int u = 0, nt = 0;
+        switch (c->scan_variant) {
+            case 2: u = 16; nt = 1; break;
+            case 3: u = 8; nt = 0; break;
+            case 4: u = 4; nt = 1; break;
+            case 7: u = 8; nt = 2; break;
+            case 8: u = 8; nt = 3; break;
+            case 9: u = 8; nt = 4; break;
+            case 10: u = 8; nt = 5; break;
+            case 11: if (row_bytes % 8192 == 0) { u = 8; nt = 6; } break;
+            default: break;
+        }
+        if (u) { f->U = u; f->NT = nt; f->FULL = row_bytes % (1024 * u) == 0; return CHIP_OK; }
+    }
+#endif
+    if (c->elem == 4 && a.q64) { f->U = 4; f->NT = 8; f->FULL = 1; return CHIP_OK; }   // scan_q64() said so (float rows only)
+#ifndef CHIP_NO_ROWS_FORM
+    if (a.rows_form > 0) {   // scan_rows_form() said so: whole 4 KiB batches, R rows per wave in one continuous load stream
+        f->family = CHIP_SCAN_FAMILY_ROWS;
+        f->R = nq <= 3 ? (a.rows_form >= 3 ? 3 : a.rows_form) : 1;   // (four queries: R = 1 only, launch_scan_q)
+        f->NTL = a.plain_loads == 0;
+        f->claimed = a.dyn_claim != 0;
+        return CHIP_OK;
+    }
+#endif
+    f->FULL = 1;
+    if (c->scan_variant != 1) {   // rows of whole 4 KiB / 2 KiB batches (one load per batch measured slower than the builtin path)
+        if (row_bytes % 4096 == 0) { f->U = 4; f->NT = 6; return CHIP_OK; }
+        if (row_bytes % 2048 == 0) { f->U = 2; f->NT = 6; return CHIP_OK; }
+    }
+    f->U = 8;   // the builtin path: 8 x 16 B per lane and step, the last step of a row guarded unless rows are whole steps
+    f->NT = 1;
+    f->FULL = row_bytes % 8192 == 0;
+    return CHIP_OK;
+}
+
+int launch_scan(Ctx *c, hipStream_t s, const ScanArgs &a, int nq, int grid)
+{
+    chip_debug_scan_launch f;
+    int rc = scan_select(c, a, nq, grid, &f);
+    if (rc != CHIP_OK) return rc;
+    if (f.family == CHIP_SCAN_FAMILY_WIDE) {
+        if (nq == 3 && f.NG == 1) rc = launch_scan_wide<3, 1>(c, s, a, f);
+        else if (nq == 4 && f.NG == 1) rc = launch_scan_wide<4, 1>(c, s, a, f);
+        else if (nq == 4 && f.NG == 2) rc = launch_scan_wide<4, 2>(c, s, a, f);
+        else rc = CHIP_ERR_UNSUPPORTED;
+    } else {
+        rc = c->elem == 8 ? launch_scan_T<double>(c, s, a, f) : launch_scan_T<float>(c, s, a, f);
+    }
+    if (rc != CHIP_OK) return rc;
+    f.launches = c->last_scan.launches + 1;
+    c->last_scan = f;
+    return CHIP_OK;
 }
 
 // Several ticks per pass (db_scan_topk_multi).  How many ticks one pass can serve on this ctx: float rows of whole 4 KiB batches
@@ -1684,7 +1754,26 @@ int launch_scan_multi(Ctx *c, hipStream_t s, const MultiScanArgs &a, int n_ticks
     const size_t lds = lds_q > lds_m ? lds_q : lds_m;
     if (n_ticks < 2 || n_ticks > scan_multi_max_ticks(c) || lds > 160 * 1024 || grid < 1 || grid > c->max_grid || a.K < 1 || a.K > CHIP_MAX_TOPK)
         return CHIP_ERR_UNSUPPORTED;
-    return n_ticks == 2 ? launch_scan_multi_t<2>(c, s, a, grid, lds) : launch_scan_multi_t<3>(c, s, a, grid, lds);
+    const int rc = n_ticks == 2 ? launch_scan_multi_t<2>(c, s, a, grid, lds) : launch_scan_multi_t<3>(c, s, a, grid, lds);
+    if (rc != CHIP_OK) return rc;
+    chip_debug_scan_launch f{};
+    f.family = CHIP_SCAN_FAMILY_MULTI;
+    f.elem = 4;
+    f.nq = 3 * n_ticks;
+    f.K = a.K;
+    f.U = kMultiU;
+    f.FULL = 1;
+    f.R = kMultiR;
+    f.NTL = 1;
+    f.ticks = n_ticks;
+    f.grid = grid;
+    f.block = kMultiBlock;
+    f.wg_per_cu = 1;
+    f.lds_bytes = (int32_t)lds;
+    f.n_rows = a.n_rows;
+    f.launches = c->last_scan.launches + 1;
+    c->last_scan = f;
+    return CHIP_OK;
 }
 
 int launch_resident(Ctx *c, hipStream_t s, const ResidentArgs &ra, int grid)

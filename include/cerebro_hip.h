@@ -282,6 +282,46 @@ int chip_debug_coalesce_stats(chip_ctx *ctx, int64_t *passes, int64_t *ticks);
 int chip_debug_coalesce_force(chip_ctx *ctx, int32_t on);
 int chip_debug_coalesce_decide(int32_t n_parked, int32_t t_max, int32_t scan_running);
 
+/* Test aids (ABI 7, additive): WHICH kernel a top-k scan ran.  The scan dispatcher chooses between four kernel families and their
+ * template instantiations from the prefix size, the row size, the query count, the kind of call and the CHIP_SCAN_* knobs; all of
+ * them compute the same bits, and tests/test_scan_forms_gpu.py holds every one of them to that.  The record is filled where the
+ * instantiation is chosen, host side only: no kernel argument, nothing on the device depends on it.  Fields a family does not have are 0.
+ *   chip_debug_last_scan  the last top-k scan launch of this ctx (family 0 before the first one); `launches` counts them.
+ *   chip_debug_scan_plan  the same record WITHOUT a device or a ctx: what a plain single-GPU ctx of n_cus compute units, created
+ *                         under the CHIP_SCAN_* / CHIP_TICK_* variables of the environment as it is now, on its own streams and with
+ *                         profiling off, launches for nq queries (K list entries each) over n_rows rows of D elements of elem
+ *                         bytes -- computed by the functions the enqueue path itself runs.  Returns what that launch would
+ *                         return (CHIP_OK, CHIP_ERR_UNSUPPORTED, ...); `launches` stays 0. */
+#define CHIP_SCAN_FAMILY_NONE    0
+#define CHIP_SCAN_FAMILY_ONE_ROW 1   /* db_scan_topk<T, NQ, U, FULL, NT, 1>: one row per wave at a time                          */
+#define CHIP_SCAN_FAMILY_WIDE    2   /* db_scan_topk_wide<NQ, NG, FULL>: double rows, NG of the NQ queries read in place           */
+#define CHIP_SCAN_FAMILY_ROWS    3   /* db_scan_topk_rows<T, NQ, R, NTL>: R rows per wave in flight; carries the fused tick        */
+#define CHIP_SCAN_FAMILY_MULTI   4   /* db_scan_topk_multi<T>: `ticks` pipelined ticks of three queries share one pass             */
+#define CHIP_SCAN_CALL_QUERY      0  /* chip_query_rows / chip_query_vectors_*: lists out                                         */
+#define CHIP_SCAN_CALL_TICK       1  /* chip_loop_tick_enqueue: a pipelined tick                                                   */
+#define CHIP_SCAN_CALL_TICK_SYNC  2  /* chip_loop_tick: the synchronous tick                                                       */
+typedef struct {
+    int32_t family;        /* CHIP_SCAN_FAMILY_*                                                                                   */
+    int32_t elem;          /* storage element size: 4 float rows, 8 double rows                                                    */
+    int32_t nq, K;         /* queries of the launch (multi: 3 per tick) and list entries kept per query (a fused tick keeps 1)     */
+    int32_t U, NT, FULL;   /* one-row: 16-byte loads per lane and batch, load path (1 builtin, 6 asm-issued, 8 asm-issued with fp64-staged
+                              queries), rows of whole batches;  wide / multi: FULL / U alone                                       */
+    int32_t NG;            /* wide: queries read in place                                                                          */
+    int32_t R, NTL;        /* rows / multi: rows per wave and pass;  rows: 1 non-temporal loads                                    */
+    int32_t ticks;         /* multi: ticks served by the pass                                                                      */
+    int32_t q64;           /* queries staged in LDS as fp64                                                                        */
+    int32_t claimed;       /* rows: the waves of a workgroup claim their rows from a counter instead of the static map            */
+    int32_t fused;         /* rows: the launch writes the tick's decision record itself, no merge kernel follows                   */
+    int32_t grid, block;   /* workgroups, threads per workgroup                                                                    */
+    int32_t wg_per_cu;     /* workgroups of that shape a compute unit is meant to hold (their LDS must fit 160 KiB together)       */
+    int32_t lds_bytes;     /* dynamic LDS per workgroup                                                                            */
+    int64_t n_rows;        /* local rows the launch reads                                                                          */
+    int64_t launches;      /* top-k scan launches of the ctx so far, this one included                                             */
+} chip_debug_scan_launch;
+int chip_debug_last_scan(chip_ctx *ctx, chip_debug_scan_launch *out);
+int chip_debug_scan_plan(int32_t D, int32_t elem, int32_t nq, int32_t K, int64_t n_rows, int32_t call, int32_t n_cus,
+                         chip_debug_scan_launch *out);
+
 /* Sharded tick, three phases (host does the exchange between 1 and 2):
  *  1. chip_scan_local: scan this rank's share of rows [0,k), k = l - lag, for the three queries l-1,l-2,l-3 and
  *     leave its 3 x topk list (chip_topk_entry, global indices) in DEVICE memory at dev_out (caller-owned,

@@ -178,3 +178,51 @@ def test_full_size_pipelined_ticks_equal_synchronous_ticks(monkeypatch):
         assert pipelined(chip, ls, p, 16) == want
         passes, ticks = chip.coalesce_stats()
         assert passes >= 4 and ticks > passes          # a 2.4 ms scan outlasts the enqueues behind it
+
+
+@pytest.mark.parametrize("tmax", [2, 3])
+def test_shared_pass_at_its_pass_boundary(monkeypatch, tmax):
+    """The shared pass gives every wave R = 4 rows per pass (one 8-wave workgroup per CU: W waves, 4 W rows per pass).  Windows of forced-
+    parked ticks whose prefixes (a) lie on both sides of a pass boundary, (b) are ten rows, about W rows and the whole DB in ONE pass,
+    (c) hold a duplicate pair whose upper copy is the LAST row of one tick and beyond the prefix of another: every record equals, byte
+    for byte, the record of the same tick issued alone with coalescing off, one per window the CPU oracle's, and last_scan() says which
+    kernel served the window."""
+    p = every_tick_params()
+    with make_chip(monkeypatch, tmax) as chip:          # the geometry, from a first forced window
+        for s in range(tmax):
+            chip.loop_tick_enqueue(L0 + 3 * s, s, p)
+        ls = chip.last_scan()
+        assert (ls["family"], ls["ticks"], ls["R"], ls["nq"], ls["elem"]) == ("multi", tmax, 4, 3 * tmax, 4), ls
+        W, R = ls["grid"] * ls["block"] // 64, ls["R"]
+        assert ls["n_rows"] == L0 + 3 * (tmax - 1) - 50 and 2 * R * W + 100 < N_ROWS
+        for s in range(tmax):
+            chip.loop_tick_collect(s)
+    P = R * W
+    windows = [[P - 2, P + 1, P + 4], [2 * P + 4, 2 * P - 2, 2 * P + 1], [P, 2 * P, P - 1], [10, W + 3, N_ROWS - 50], [N_ROWS - 50, W - 1, 10],
+               [DUP_HI + 1, DUP_HI - 1, DUP_HI + 4], [DUP_HI, DUP_HI + 1, N_ROWS - 50]]       # prefixes k; the tick is l = k + 50
+    windows = [w[:tmax] for w in windows] + ([[w[0], w[2]] for w in windows] if tmax == 2 else [])
+    all_l = sorted({k + 50 for w in windows for k in w})
+    alone, _ = one_by_one(monkeypatch, all_l, p)
+    alone = dict(zip(all_l, alone))
+    db = oracle_lib.synth_rows(SEED, range(N_ROWS), D, PLANTS)
+    op = oracle_lib.default_params()
+    op.min_new = -(1 << 30)
+    with make_chip(monkeypatch, tmax) as chip:
+        launches = chip.last_scan()["launches"]
+        for w in windows:
+            before = chip.coalesce_stats()
+            for s, k in enumerate(w):
+                chip.loop_tick_enqueue(k + 50, s, p)
+            ls = chip.last_scan()
+            launches += 1
+            assert (ls["family"], ls["ticks"], ls["n_rows"], ls["launches"]) == ("multi", len(w), max(w), launches), (w, ls)
+            assert tuple(a - b for a, b in zip(chip.coalesce_stats(), before)) == (1, len(w))
+            got = [bytes(chip.loop_tick_collect(s)) for s in range(len(w))]
+            assert got == [alone[k + 50] for k in w], (w, [i for i, k in enumerate(w) if got[i] != alone[k + 50]])
+            k = min(w)
+            o = oracle_lib.LoopOracle(db, op).tick(k + 50)
+            r = rec(got[w.index(k)])
+            assert r.status == capi.CHIP_TICK_SCANNED and list(r.argmax) == o["argmax"] and r.found == o["found"] and r.idx_prev == o["idx_prev"]
+            assert [float(x).hex() for x in r.maxv] == [float(x).hex() for x in o["maxv"]] and float(r.score).hex() == float(o["score"]).hex()
+        # the planted pair: the tick whose LAST row is the upper copy reports it, the tick whose prefix ends just before it the lower copy
+        assert list(rec(alone[DUP_HI + 1 + 50]).argmax) == [DUP_HI] * 3 and list(rec(alone[DUP_HI + 50]).argmax) == [DUP_LO] * 3

@@ -9,7 +9,7 @@
 // belongs on the matrix cores: v_mfma_f32_32x32x2_f32 is exact fp32 (bit-for-bit a k-ordered fmaf chain,
 // cdna_hip_programming.md 3) at the 157 TFLOP/s vector rate.
 //
-// K_B db_gemm_topk<KC, NST, WN, KL> : grid (P workgroups) x (query tiles).  Tile = 64 WN queries x 64 WN DB rows on 2 x WN waves,
+// K_B db_gemm_topk<KC, WN, KL> : grid (P workgroups) x (query tiles).  Tile = 64 WN queries x 64 WN DB rows on 2 x WN waves,
 //   each wave owning WN x 2 MFMA 32x32 accumulators (64 WN queries x 64 DB rows):
 //     WN = 4: 256 x 256 on 8 waves, one workgroup per CU -- 16 MFMAs per 6 fragment reads, one workgroup barrier per 128 MFMAs,
 //             the DB streamed once per 256 queries; used when the padded query count is a multiple of 256 (0.84 of the fp32
@@ -38,6 +38,7 @@ constexpr int CT_LD = 128 + 1;      // score tile in LDS [tile queries][129]: 12
 // placed at b * kBBlock + (b & 3) floats -- rotated by 0..3 floats, which the LDS-DMA honours (its destination base only needs
 // 4-byte alignment: scripts/probes/glds_align_probe.hip) -- 4 floats of padding per block keep the rotated blocks apart.
 constexpr int kBBlock = 8 * 32 + 4;
+constexpr int NST = 2;              // stages of the LDS ring a tile's K chunks go through (four at one workgroup per CU measured slower)
 constexpr int kMaxQTiles = 4096;    // query tiles per call (grid.y); 4096 x 128 queries
 __device__ __forceinline__ constexpr int b_row_off(int row) { return (row >> 3) * kBBlock + ((row >> 3) & 3) + (row & 7) * 32; }
 
@@ -114,9 +115,8 @@ __device__ __forceinline__ void list_kth(const TopList<KL> &L, int K, float &ts,
 //                  slot swizzle -- 32 rows, 8 slots, one float offset: round 2 ran that way until the probe showed the
 //                  destination base of an LDS-DMA may be any multiple of 4 bytes.)
 // The LDS-DMA is issued from inline asm ON PURPOSE: hipcc tracks the builtin form and, not knowing which stage a load fills,
-// drains ALL of them (s_waitcnt vmcnt(0)) at every barrier.  Untracked, the loads of the next NST-1 chunks stay in flight
-// across barriers and the loop waits with counted s_waitcnt vmcnt(8 (NST-2)): vmcnt retires in order, so "at most n
-// outstanding" == "everything but the newest n loads has landed".
+// drains ALL of them (s_waitcnt vmcnt(0)) at every barrier.  Untracked, the loads of the next chunk stay in flight
+// underneath this chunk's MFMAs and the loop waits for them itself, once, at the barrier that ends the chunk.
 // M0 (the wave-uniform LDS destination base) is written in the same statement that uses it (cdna_hip_programming.md, asm notes).
 __device__ __forceinline__ void glds16(const float *gsrc, uint32_t lds_byte_addr_wave_uniform)
 {
@@ -130,12 +130,10 @@ __device__ __forceinline__ uint32_t lds_addr(const void *p)
 {
     return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
 }
-// at most 8 * CHUNKS LDS-DMA loads still in flight, own LDS reads done, workgroup barrier
-__device__ __forceinline__ void wait_loads_and_barrier(int chunks_in_flight)
+// every LDS-DMA load has landed, own LDS reads done, workgroup barrier
+__device__ __forceinline__ void wait_loads_and_barrier()
 {
-    if (chunks_in_flight >= 2) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    else if (chunks_in_flight == 1) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
 // Qt[qtile][chunk][k][row] <- Q[qtile * TM + row][chunk * KC + k], TM = rows of a query tile (128 or 256)
@@ -156,7 +154,7 @@ __global__ __launch_bounds__(256) void transpose_queries(const float *__restrict
 
 // WN = waves along the DB rows of a tile (2 or 4); a wave owns WN x 2 MFMA 32x32 blocks (64 WN queries x 64 DB rows), the
 // workgroup tile is 64 WN x 64 WN (128 x 128 with 4 waves, 256 x 256 with 8), 2 x WN waves, 8 LDS-DMA per wave per chunk either way.
-template <int KC, int NST, int WN, int KL>
+template <int KC, int WN, int KL>
 __global__ __launch_bounds__(128 * WN) void db_gemm_topk(BatchArgs a)
 {
     static_assert(KC == 32, "one K-chunk = 8 slots of 4 floats per DB row");
@@ -245,26 +243,20 @@ __global__ __launch_bounds__(128 * WN) void db_gemm_topk(BatchArgs a)
 #pragma unroll
             for (int j = 0; j < 8; j++) stage_load_one(c, j);
         };
-#pragma unroll
-        for (int c = 0; c < NST - 1; c++)
-            if (c < n_chunks) stage_load(c);
-        {
-            const int issued = n_chunks < NST - 1 ? n_chunks : NST - 1;
-            wait_loads_and_barrier(issued - 1);   // chunk 0 has landed
-        }
+        if (n_chunks > 0) stage_load(0);
+        wait_loads_and_barrier();   // chunk 0 has landed
         // the K loop, instantiated for whole tiles (NRB = WN row blocks per wave) and for query halves (NRB = WN / 2)
         auto k_loop = [&](auto nrb_tag) {
             constexpr int NRB = decltype(nrb_tag)::value;
             for (int c = 0; c < n_chunks; c++) {
                 const float *St = S0 + (c % NST) * STAGE;
-                // chunk c + NST - 1 goes to the stage last read in iteration c-1 (barrier since).  When its 8 LDS-DMA instructions are
+                // chunk c + 1 goes to the stage last read in iteration c-1 (barrier since).  When its 8 LDS-DMA instructions are
                 // issued matters (a burst keeps a wave from issuing MFMAs for ~300 cycles; a late load is waited for at the barrier):
-                //   4 stages            one in front of each of the 8 MFMA groups of this iteration (the chunk is needed 3 iterations on);
-                //   2 stages, 128 tile  all 8 at once at the top (the other workgroup's wave fills the gap: 119.4 TF vs 114.8 spread);
-                //   2 stages, 256 tile  two in front of each of MFMA groups 1..4 (both waves of a SIMD belong to this workgroup and burst
-                //                       together: 0.814 of peak vs 0.792 for the burst, 0.805 for groups 0..3, 0.76 for one per group).
-                const bool prefetch = c + NST - 1 < n_chunks;
-                if (NST == 2 && WN == 2 && prefetch) stage_load(c + NST - 1);
+                //   128 tile  all 8 at once at the top (the other workgroup's wave fills the gap: 119.4 TF vs 114.8 spread);
+                //   256 tile  two in front of each of MFMA groups 1..4 (both waves of a SIMD belong to this workgroup and burst
+                //             together: 0.814 of peak vs 0.792 for the burst, 0.805 for groups 0..3, 0.76 for one per group).
+                const bool prefetch = c + 1 < n_chunks;
+                if (WN == 2 && prefetch) stage_load(c + 1);
                 // fragments of k-steps (2 k4, 2 k4 + 1) in f[k4 & 1]: [2 i + t] = A row block i, [2 WN + 2 j + t] = B block j;
                 // the next pair is read before this pair's 4 WN MFMAs are issued
                 float f[2][2 * WN + 4];
@@ -282,8 +274,7 @@ __global__ __launch_bounds__(128 * WN) void db_gemm_topk(BatchArgs a)
                 __builtin_amdgcn_sched_group_barrier(0x100, NRB + 2, 0);  // the reads of the first pair
 #pragma unroll
                 for (int k4 = 0; k4 < KC / 4; k4++) {
-                    if (NST > 2 && prefetch) stage_load_one(c + NST - 1, k4);
-                    if (NST == 2 && WN == 4 && prefetch && k4 >= 1 && k4 <= 4) { stage_load_one(c + 1, 2 * k4 - 2); stage_load_one(c + 1, 2 * k4 - 1); }
+                    if (WN == 4 && prefetch && k4 >= 1 && k4 <= 4) { stage_load_one(c + 1, 2 * k4 - 2); stage_load_one(c + 1, 2 * k4 - 1); }
                     if (k4 + 1 < KC / 4) rd(k4 + 1, f[(k4 + 1) & 1]);
 #pragma unroll
                     for (int t = 0; t < 2; t++) {
@@ -299,12 +290,8 @@ __global__ __launch_bounds__(128 * WN) void db_gemm_topk(BatchArgs a)
                     __builtin_amdgcn_sched_group_barrier(0x100, NRB + 2, 0);   // DS reads (ds_read2)
                     __builtin_amdgcn_sched_group_barrier(0x008, 4 * NRB, 0);   // MFMA
                 }
-                // chunk c+1 has landed (everything but the NST-2 newest chunks), every wave is done reading stage c % NST
-                {
-                    int newer = n_chunks - (c + 2);   // chunks after c+1 that have been issued: min(NST - 2, n_chunks - c - 2)
-                    if (newer > NST - 2) newer = NST - 2;
-                    wait_loads_and_barrier(newer < 0 ? 0 : newer);
-                }
+                // chunk c+1 has landed (no chunk behind it has been issued), every wave is done reading stage c % NST
+                wait_loads_and_barrier();
             }
         };
         if (half_unit) k_loop(std::integral_constant<int, WN / 2>{});
@@ -433,12 +420,10 @@ int batch_local_enqueue(Ctx *c, int64_t k, const float *queries, int32_t Q, int3
     const int64_t n_rows = local_count(c, k);
     // Tile shape: 256 x 256 with 8 waves (one workgroup per CU: 16 MFMAs per 6 fragment reads, one barrier per 128 MFMAs, the DB
     // streamed once per 256 queries) when the padded query count is a multiple of 256, else 128 x 128 with 4 waves.
-    // CHIP_BATCH_TILE=128 forces the small tile; CHIP_BATCH_STAGES=4 selects its 4-stage / one-workgroup-per-CU variant.
-    const bool wide = Qpad % 256 == 0 && env_int("CHIP_BATCH_TILE", 256) >= 256;
+    const bool wide = Qpad % 256 == 0;
     const int TM = wide ? 256 : BM, TN = TM;
     const int qtiles = Qpad / TM;
-    const int nst = !wide && env_int("CHIP_BATCH_STAGES", 2) >= 4 ? 4 : 2;
-    const int wgs = wide || nst == 4 ? 1 : 2;            // workgroups per CU
+    const int wgs = wide ? 1 : 2;            // workgroups per CU
     int64_t tiles = (n_rows + TN - 1) / TN;
     if (tiles < 1) tiles = 1;
     int64_t P = (wgs * (int64_t)c->n_cus + qtiles - 1) / qtiles;   // workgroups per query tile (each ends with one list per query): at most 512
@@ -484,7 +469,7 @@ int batch_local_enqueue(Ctx *c, int64_t k, const float *queries, int32_t Q, int3
     a.n_rows = n_rows; a.D = D; a.Q = st->Q; a.Qt = st->Qt; a.Qpad = Qpad; a.K = topk; a.tile_ctr = st->tile_ctr;
     a.idx_mul = c->nranks; a.idx_add = c->nranks == 1 ? 0 : c->rank; a.partial = st->partial;
     constexpr int KCsel = 32;
-    const size_t lds_gemm = sizeof(float) * (size_t)nst * ((size_t)TM * KCsel + (size_t)(TN / 8) * kBBlock) /* stages x (A + B) */;
+    const size_t lds_gemm = sizeof(float) * NST * ((size_t)TM * KCsel + (size_t)(TN / 8) * kBBlock) /* stages x (A + B) */;
     const size_t lds_ct = sizeof(float) * (size_t)TM * CT_LD;
     const size_t lds = lds_gemm > lds_ct ? lds_gemm : lds_ct;
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -502,8 +487,8 @@ int batch_local_enqueue(Ctx *c, int64_t k, const float *queries, int32_t Q, int3
         return CHIP_OK;
     };
     int lrc;
-    if (topk <= 8) lrc = wide ? launch(db_gemm_topk<KCsel, 2, 4, 8>, 512) : nst == 4 ? launch(db_gemm_topk<KCsel, 4, 2, 8>, 256) : launch(db_gemm_topk<KCsel, 2, 2, 8>, 256);
-    else lrc = wide ? launch(db_gemm_topk<KCsel, 2, 4, CHIP_MAX_TOPK>, 512) : nst == 4 ? launch(db_gemm_topk<KCsel, 4, 2, CHIP_MAX_TOPK>, 256) : launch(db_gemm_topk<KCsel, 2, 2, CHIP_MAX_TOPK>, 256);
+    if (topk <= 8) lrc = wide ? launch(db_gemm_topk<KCsel, 4, 8>, 512) : launch(db_gemm_topk<KCsel, 2, 8>, 256);
+    else lrc = wide ? launch(db_gemm_topk<KCsel, 4, CHIP_MAX_TOPK>, 512) : launch(db_gemm_topk<KCsel, 2, CHIP_MAX_TOPK>, 256);
     if (lrc != CHIP_OK) return lrc;
     CHIP_HIP(c, hipGetLastError());
     if (e1) CHIP_HIP(c, hipEventRecord(e1, s));

@@ -374,7 +374,7 @@ static int resident_tick_enqueue(Ctx *c, int64_t k, int64_t l, const chip_dot_pa
     cmd.seq_ptr = (uint64_t)(uintptr_t)s.seq_dev;
     cmd.seq_val = s.seq_want;
     // rows claimed within the workgroup: beyond cache-sized prefixes, as for launches (29k rows: 92.3 -> 91.7 us; neutral at 10k)
-    cmd.dyn_claim = (c->scan_claim == 1 || (c->scan_claim < 0 && (double)k * c->D * c->elem > c->scan_half_bytes)) ? 1u : 0u;   // (the instance runs the product stream only)
+    cmd.dyn_claim = (c->scan_claim == 1 || (c->scan_claim < 0 && (double)k * c->D * c->elem > c->scan_half_bytes)) ? 1u : 0u;
     c->res_pending = cmd;
     resident_write_line(c, cmd);           // (before the launch: an instance must never find the previous one's leave mark in its lines)
     if (launch) {
@@ -523,7 +523,6 @@ void ctx_destroy(chip_ctx *c)
     if (c->scores_dev) (void)hipFree(c->scores_dev);
     if (c->stamps_dev) (void)hipFree(c->stamps_dev);
     if (c->tickets_dev) (void)hipFree(c->tickets_dev);
-    if (c->pair_ctr_dev) (void)hipFree(c->pair_ctr_dev);
     if (c->seq_host_all) (void)hipHostFree(c->seq_host_all);
     for (Slot &s : c->slots) {
         if (s.done) (void)hipEventDestroy(s.done);
@@ -546,9 +545,6 @@ void scan_read_knobs(Ctx *c)
     if (c->scan_blocks_per_cu < 1) c->scan_blocks_per_cu = 1;
     c->scan_variant = env_int("CHIP_SCAN_VARIANT", 0);
     c->scan_rows = env_int("CHIP_SCAN_ROWS", 0);
-    c->scan_depth = env_int("CHIP_SCAN_DEPTH", 1);      // 1 = the product's claimed stream; 2..4: experimental forms (kernels.hip scan_rows_body)
-    if (c->scan_depth < 1 || c->scan_depth > 7) c->scan_depth = 1;
-    { const int st = env_int("CHIP_SCAN_STAGGER", 0); if (st > 0 && st < 4096) c->scan_depth |= st << 8; }   // tuning builds only (kernels.hip)
     c->scan_claim = env_int("CHIP_SCAN_CLAIM", -1);   // -1 = auto (full-occupancy launches of the row-batched kernel), 0 = never, 1 = always
     c->tick_same_stream = env_int("CHIP_TICK_SAME_STREAM", 1) != 0;
     c->scan_short_bpc = env_int("CHIP_SCAN_SHORT_BPC", 1);
@@ -588,15 +584,7 @@ static int create_impl(chip_ctx *c, int64_t capacity_hint, int elem)
     CHIP_HIP(c, hipHostMalloc(&c->flags_host, sizeof(uint32_t), hipHostMallocDefault));
 
     scan_read_knobs(c);
-    {
-        const int pr = env_int("CHIP_SCAN_STREAM_PRIORITY", 0);   // tuning only: 0 = default class, 1 = highest, -1 = lowest
-        if (pr == 0) CHIP_HIP(c, hipStreamCreateWithFlags(&c->s_scan, hipStreamNonBlocking));
-        else {
-            int lo = 0, hi = 0;
-            CHIP_HIP(c, hipDeviceGetStreamPriorityRange(&lo, &hi));
-            CHIP_HIP(c, hipStreamCreateWithPriority(&c->s_scan, hipStreamNonBlocking, pr > 0 ? hi : lo));
-        }
-    }
+    CHIP_HIP(c, hipStreamCreateWithFlags(&c->s_scan, hipStreamNonBlocking));
     {
         // Tick streams.  Short ticks of a plain ctx run scan + merge on ONE stream and rotate over up to four of them: a 10k-row tick
         // is ~37 us of scan, ~15 us of one-workgroup merge and ~12 us of launch / event gap per stream (rocprofv3 timeline,
@@ -616,10 +604,6 @@ static int create_impl(chip_ctx *c, int64_t capacity_hint, int elem)
     }
     CHIP_HIP(c, hipMalloc(&c->tickets_dev, Ctx::kRing * sizeof(int32_t)));
     CHIP_HIP(c, hipMemset(c->tickets_dev, 0, Ctx::kRing * sizeof(int32_t)));
-    if ((c->scan_depth & 255) == 7) {   // tuning builds only (pair-claimed stream, profiles/r06_short_scan.md): the product allocates nothing for it
-        CHIP_HIP(c, hipMalloc(&c->pair_ctr_dev, (size_t)Ctx::kRing * Ctx::kPairCtrs * Ctx::kPairStride * sizeof(uint32_t)));
-        CHIP_HIP(c, hipMemset(c->pair_ctr_dev, 0, (size_t)Ctx::kRing * Ctx::kPairCtrs * Ctx::kPairStride * sizeof(uint32_t)));
-    }
     // pipelined ticks that arrive while a long scan is running share one DB pass: at most this many per pass (0 = never; coalesce_* below)
     c->coalesce_max = env_int("CHIP_TICK_COALESCE", kMultiMaxTicks);
     if (c->coalesce_max < 2) c->coalesce_max = 0;
@@ -698,7 +682,7 @@ bool scan_policy(const Ctx *c, int64_t n_local, int nq, bool sync_tick, ScanArgs
     a->plain_loads = bytes <= c->scan_plain_bytes ? 1 : 0;
     // rows claimed within the workgroup: measured -2 % on the synchronous 29k / 45k tick (two workgroups per CU), neutral at 10k (one
     // workgroup per CU: the launch is too short for the waves to drift apart) -- profiles/r05_short_scan.md
-    a->dyn_claim = (a->rows_form == 1 && (c->scan_claim == 1 || (c->scan_claim < 0 && *grid > c->n_cus))) ? c->scan_depth : 0;
+    a->dyn_claim = (a->rows_form == 1 && (c->scan_claim == 1 || (c->scan_claim < 0 && *grid > c->n_cus))) ? 1 : 0;
     return short_scan;
 }
 
@@ -752,8 +736,6 @@ int enqueue_scan_merge(Ctx *c, int64_t k, const void *const *q, int nq, int K, i
         a.K = 1;
         a.fused_result = res;
         a.fused_ticket = c->tickets_dev + b;
-        // tuning builds, CHIP_SCAN_DEPTH=7 only: rows claimed by PAIRS of workgroups (b, b + grid / 2: the older and the younger workgroup of a CU) from one counter
-        if ((a.dyn_claim & 255) == 7 && c->pair_ctr_dev && (grid & 15) == 0 && grid / 2 <= Ctx::kPairCtrs) a.pair_ctr = c->pair_ctr_dev + (size_t)b * Ctx::kPairCtrs * Ctx::kPairStride;
         a.tick_l = l;
         a.locality = p->locality;
         a.thresh = p->thresh;

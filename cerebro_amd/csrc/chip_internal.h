@@ -34,7 +34,6 @@ struct ScanArgs {
     // decision record itself -- a tick is then ONE launch.  fused_result == nullptr: lists only, K2 follows as a launch of its own.
     chip_tick_result *fused_result = nullptr;
     int32_t *fused_ticket = nullptr;        // arrival counter of this launch's list buffer (0 at launch, reset by the last workgroup)
-    uint32_t *pair_ctr = nullptr;           // [gridDim / 2] row-claim counters shared by workgroups b and b + gridDim / 2 (0 at launch, reset by the last workgroup); nullptr: rows are claimed per workgroup
     unsigned long long *fused_seq = nullptr; // completion word of the tick's slot in pinned host memory: written (system-scope RELEASE) after the
     unsigned long long fused_seq_val = 0;    // record, so that a host that polls it sees the record complete (chip_api.hip tick_collect_slot)
     int64_t tick_l = 0;
@@ -202,9 +201,6 @@ struct Ctx {
     hipEvent_t ev_scan[kRing] = {};             // scan into buffer b finished
     hipEvent_t ev_merged[kRing] = {};           // merge out of buffer b finished
     int32_t *tickets_dev = nullptr;             // [kRing] arrival counters of the fused tick (one per list buffer)
-    uint32_t *pair_ctr_dev = nullptr;           // [kRing][kPairCtrs][kPairStride] row-claim counters of workgroup pairs (pair-claimed stream of the fused tick)
-    static constexpr int kPairCtrs = 256;
-    static constexpr int kPairStride = 32;      // uint32s: every counter has a 128-byte line to itself (the pairs of a launch sit on eight XCDs)
     unsigned long long *seq_host_all = nullptr; // [CHIP_MAX_INFLIGHT] completion words of the slots (pinned)
     unsigned long long tick_seq = 0;            // last value handed out
     bool tick_poll = true;                      // CHIP_TICK_POLL: fused ticks are collected by polling the completion word
@@ -279,7 +275,6 @@ struct Ctx {
     int32_t scan_variant = 0;
     int32_t scan_streams = 4;      // CHIP_SCAN_STREAMS: tick streams created (1: s_scan alone, 2: + s_scan2, 3 / 4: + s_scan_x)
     bool tick_same_stream = true;  // short ticks of a plain ctx: merge on the scan's stream (CHIP_TICK_SAME_STREAM=0 disables)
-    int32_t scan_depth = 1;       // CHIP_SCAN_DEPTH: batches of a wave's load stream in flight in the claimed row-batched kernel (1 or 2)
     int32_t scan_claim = -1;      // CHIP_SCAN_CLAIM: rows claimed within the workgroup (row-batched kernel, R = 1): -1 auto, 0 never (static row -> wave map), 1 always
     int32_t scan_rows = 0;        // CHIP_SCAN_ROWS: 0 = auto (prefixes up to scan_plain_bytes), 1..3 = row-batched kernel with that R for every scan, -1 = never
     double scan_plain_bytes = 768.0 * 1024 * 1024;   // prefixes up to this size: rows form, R = 1, temporal loads (CHIP_SCAN_PLAIN_MIB)

@@ -26,8 +26,6 @@ typedef double f64x2 __attribute__((ext_vector_type(2)));
 // scan -> per-wave register top-K -> per-block LDS merge -> one sorted partial list per workgroup in global memory.
 // The cross-workgroup merge (+ accept decision) is K2 on the ctx stream, behind an event, so that it overlaps the
 // NEXT tick's scan (a fused last-workgroup merge was measured to serialise ~28 us per tick).
-// One 16-byte streaming load of a DB row chunk.  POLICY 1 (production) = the non-temporal hint; 0 = plain; 2..5 = other
-// gfx950 cache-policy bit combinations, reachable only through CHIP_SCAN_VARIANT in tuning builds.
 template <typename T> struct Vec16;                       // 16 bytes of storage elements = one lane's share of a wave load
 template <> struct Vec16<float> { typedef f32x4 type; static constexpr int N = 4; };
 template <> struct Vec16<double> { typedef f64x2 type; static constexpr int N = 2; };
@@ -41,19 +39,11 @@ __device__ __forceinline__ const __attribute__((address_space(1))) V *as_global(
     return (const __attribute__((address_space(1))) V *)p;
 }
 
-template <int POLICY, typename V>
+// One 16-byte streaming load of a DB row chunk with the non-temporal hint, scheduled by the compiler (rows_dot, NT == 1).
+template <typename V>
 __device__ __forceinline__ V stream_load(const V *p)
 {
-    if constexpr (POLICY == 0) return *as_global(p);
-    else if constexpr (POLICY == 1) return __builtin_nontemporal_load(as_global(p));
-    else {
-        V v;
-        if constexpr (POLICY == 2) asm volatile("global_load_dwordx4 %0, %1, off sc1 nt" : "=v"(v) : "v"(p) : "memory");
-        else if constexpr (POLICY == 3) asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1 nt" : "=v"(v) : "v"(p) : "memory");
-        else if constexpr (POLICY == 4) asm volatile("global_load_dwordx4 %0, %1, off sc0 nt" : "=v"(v) : "v"(p) : "memory");
-        else asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(v) : "v"(p) : "memory");
-        return v;
-    }
+    return __builtin_nontemporal_load(as_global(p));
 }
 
 // Dot products of one DB row with NQ staged queries in the fixed order of DESIGN.md 3: lane L accumulates elements
@@ -91,16 +81,9 @@ __device__ __forceinline__ void rows_dot(const T *const (&row)[R], const T *qs, 
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const int e = base + u * CH + e0;
-                if (FULL || e < D) v[rr][u] = stream_load<NT>(reinterpret_cast<const V *>(row[rr] + e));
+                if (FULL || e < D) v[rr][u] = stream_load(reinterpret_cast<const V *>(row[rr] + e));
             }
         }
-        }
-        if constexpr (NT >= 2 && NT != 6 && NT != 8) {   // inline-asm loads: the compiler does not track them
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int rr = 0; rr < R; rr++)
-#pragma unroll
-                for (int u = 0; u < U; u++) asm volatile("" : "+v"(v[rr][u]));
         }
 #pragma unroll
         for (int u = 0; u < U; u++) {
@@ -768,10 +751,6 @@ __device__ __forceinline__ void fused_tick_finish(const ScanArgs &a, const RowsP
         }
     }
     if (xstamp && tid == 0) xstamp[6] = (unsigned long long)wall_clock64();
-    // the workgroup pairs' row-claim counters of this launch's list buffer: back to zero for the launch that reuses it (every workgroup
-    // has claimed its last row before it took the ticket, and this is the workgroup that took the last one)
-    if (a.pair_ctr != nullptr)
-        for (int i = tid; i < (int)(gridDim.x >> 1); i += (int)blockDim.x) __hip_atomic_store(a.pair_ctr + (size_t)i * 32, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
     if (wave != 0) return;
     if (xstamp && tid == 0) xstamp[7] = (unsigned long long)wall_clock64();
@@ -913,14 +892,6 @@ __device__ __forceinline__ void scan_rows_body(const ScanArgs &a, const RowsPass
         asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
     }
 
-#ifdef CHIP_SCAN_TUNING_VARIANTS
-    // CHIP_SCAN_STAGGER=n (tuning builds): wave w of a workgroup starts consuming n x 64 x w cycles late -- are the one-workgroup-per-CU
-    // shapes slow (6.6-6.9 TB/s) because their waves run in lockstep?
-    if constexpr (!RESIDENT) {
-        const int st = t.dyn_claim >> 8;
-        for (int i = 0; i < st * wave; i++) __builtin_amdgcn_s_sleep(1);
-    }
-#endif
     if (stamp && lane == 0) stamp[1] = wall_clock64();
     // running top-K lists: LDS behind the queries (this wave's NQ lists are touched by this wave only)
     chip_topk_entry *lists = reinterpret_cast<chip_topk_entry *>(smem + (size_t)NQ * D * sizeof(T));
@@ -979,6 +950,8 @@ __device__ __forceinline__ void scan_rows_body(const ScanArgs &a, const RowsPass
         // Here the workgroup's rows -- unit u = row (u / wpb) * tw + blockIdx * wpb + u % wpb, the same set as before -- are handed
         // out by an LDS counter: a wave claims its next unit while it starts on the current one (the ds_add_rtn has a whole row,
         // ~8 us, to come back), so the waves of a workgroup run dry within one row of each other.
+        // (Deeper streams, early re-issue at raised priority and rows claimed by workgroup pairs were tried and measured neutral or
+        //  negative: profiles/r06_short_scan.md §2; the code was last carried by commit af4232e.)
         uint32_t *ctr = reinterpret_cast<uint32_t *>(smem + (size_t)NQ * D * sizeof(T) + (size_t)wpb * NQ * CHIP_MAX_TOPK * sizeof(chip_topk_entry));
         const int64_t wg0 = (int64_t)blockIdx.x * wpb;
         int n_units = 0;
@@ -989,230 +962,6 @@ __device__ __forceinline__ void scan_rows_body(const ScanArgs &a, const RowsPass
         auto unit_row = [&](int u) { return (int64_t)(u / wpb) * tw + wg0 + (u % wpb); };
         // (the counter was set to wpb by wave 0 before the staging barrier; unit `wave` is this wave's first, loaded above)
         int cur = wave;
-        bool experimental = false;
-#ifdef CHIP_SCAN_TUNING_VARIANTS   // A/B builds only (make EXTRA_HIPFLAGS=-DCHIP_SCAN_TUNING_VARIANTS): the product kernel carries the product stream alone
-        // ---- experimental forms of the claimed stream, selected by t.dyn_claim (CHIP_SCAN_DEPTH; the default, 1, is the loop below);
-        //      all measured neutral or negative (profiles/r06_short_scan.md §2) ----
-        //   2: TWO batches (8 KiB) of every wave in flight, the unit still one claimed row (round 6; profiles/r06_short_scan.md §2):
-        //      slots 0..3 (v80..v95) hold the even batches of a row, slots 4..7 (v96..v111) the odd ones; consuming slot s re-issues it for
-        //      the batch two ahead, across the row boundary into the next claimed row, so behind every slot exactly 7 younger loads are
-        //      outstanding.  Steady state 7.6 -> 8.6 TB/s at 29k rows, but the OLDER workgroup of every CU takes all of the gain.
-        //   3 / 4: depth 1 / depth 2 with the slot's re-issue moved IN FRONT of its arithmetic and both at raised issue priority: what
-        //      starves the younger workgroup is not memory but the vector pipe's oldest-first arbitration -- a wave re-issues a slot only
-        //      after that slot's 12 fp64 fmas, and a young wave's fmas queue behind every older wave's burst, so its load pipeline runs
-        //      with gaps.  Here the wait + conversion of a slot (4 v_cvt) and the load that refills it run at s_setprio 3, the fmas at 0.
-        //   One accumulator chain per query in ascending element order in every form: same bits.
-#define CHIP_ROWSX_ISSUE(slot, chunk, byte_off, rowp) rows_issue<NTL, rows_slot_reg<1>(slot, 0), (chunk) * 1024>((byte_off) + lane_off, rowp)
-#define CHIP_ROWSX_STEP(slot, chunk, base, CNT, DO_ISSUE, byte_off, rowp)                                               \
-    do {                                                                                                                \
-        __builtin_amdgcn_sched_barrier(0);                                                                              \
-        const int e_ = (base) + (chunk) * CH + lane * N;                                                                \
-        V w_[NQ];                                                                                                       \
-        _Pragma("unroll") for (int q = 0; q < NQ; q++) w_[q] = *reinterpret_cast<const V *>(qs + q * D + e_);           \
-        if constexpr (EARLY) {                                                                                          \
-            double va_[2], vb_[2];                                                                                      \
-            __builtin_amdgcn_s_setprio(3);                                                                              \
-            rows_take<rows_slot_reg<1>(slot, 0), CNT, 0>(va_, T());                                                     \
-            rows_take<rows_slot_reg<1>(slot, 0), CNT, 1>(vb_, T());                                                     \
-            if (DO_ISSUE) CHIP_ROWSX_ISSUE(slot, chunk, byte_off, rowp);                                                \
-            __builtin_amdgcn_s_setprio(0);                                                                              \
-            __builtin_amdgcn_sched_barrier(0);                                                                          \
-            _Pragma("unroll") for (int c = 0; c < N / 2; c++)                                                           \
-                _Pragma("unroll") for (int q = 0; q < NQ; q++) acc[0][q] = __builtin_fma((double)w_[q][c], va_[c], acc[0][q]); \
-            _Pragma("unroll") for (int c = 0; c < N / 2; c++)                                                           \
-                _Pragma("unroll") for (int q = 0; q < NQ; q++) acc[0][q] = __builtin_fma((double)w_[q][N / 2 + c], vb_[c], acc[0][q]); \
-            __builtin_amdgcn_sched_barrier(0);                                                                          \
-        } else {                                                                                                        \
-            _Pragma("unroll") for (int h_ = 0; h_ < 2; h_++) {                                                          \
-                double vd_[2];                                                                                          \
-                if (h_ == 0) rows_take<rows_slot_reg<1>(slot, 0), CNT, 0>(vd_, T());                                    \
-                else rows_take<rows_slot_reg<1>(slot, 0), CNT, 1>(vd_, T());                                            \
-                _Pragma("unroll") for (int c = 0; c < N / 2; c++)                                                       \
-                    _Pragma("unroll") for (int q = 0; q < NQ; q++)                                                      \
-                        acc[0][q] = __builtin_fma((double)w_[q][h_ * (N / 2) + c], vd_[c], acc[0][q]);                  \
-                __builtin_amdgcn_sched_barrier(0);                                                                      \
-            }                                                                                                           \
-            if (DO_ISSUE) CHIP_ROWSX_ISSUE(slot, chunk, byte_off, rowp);                                                \
-        }                                                                                                               \
-    } while (0)
-        auto finish_row = [&](int unit) {
-            const int64_t r = unit_row(unit);
-#pragma unroll
-            for (int q = 0; q < NQ; q++) {
-                const double s = butterfly_sum(acc[0][q]);
-                acc[0][q] = 0.0;
-                wave_topk_offer_lds(s, r * a.idx_mul + a.idx_add, K, lane, mylists + q * CHIP_MAX_TOPK, thr_s[q], thr_i[q]);
-            }
-        };
-        auto stream_depth2 = [&](auto early_tag) {
-            constexpr bool EARLY = decltype(early_tag)::value;
-            const T *rowp = row[0], *nrow = row[0];
-            if (cur < n_units) {   // batch 1 of the first row (batch 0 went out in front of the staging barrier)
-                CHIP_ROWSX_ISSUE(4, 0, 4096u, rowp); CHIP_ROWSX_ISSUE(5, 1, 4096u, rowp); CHIP_ROWSX_ISSUE(6, 2, 4096u, rowp); CHIP_ROWSX_ISSUE(7, 3, 4096u, rowp);
-            }
-            while (cur < n_units) {
-                uint32_t nxt_v = 0;
-                if (lane == 0) nxt_v = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                int nxt = 0;
-                bool more = false;
-                for (int bb = 0; bb < nb; bb += 2) {
-                    const int base0 = bb * (CH * U), base1 = base0 + CH * U;
-                    const T *ra = rowp;
-                    uint32_t oa = (uint32_t)(bb + 2) * 4096u;
-                    bool ahead = true;
-                    if (bb + 2 == nb) {                      // the two batches ahead are the next claimed row's first two
-                        nxt = __builtin_amdgcn_readfirstlane((int)nxt_v);
-                        more = nxt < n_units;
-                        ahead = more;
-                        oa = 0u;
-                        if (more) { nrow = uniform_ptr(row_base_uniform<T>(a, unit_row(nxt))); ra = nrow; }
-                    }
-                    if (ahead) {
-                        CHIP_ROWSX_STEP(0, 0, base0, 7, 1, oa, ra); CHIP_ROWSX_STEP(1, 1, base0, 7, 1, oa, ra);
-                        CHIP_ROWSX_STEP(2, 2, base0, 7, 1, oa, ra); CHIP_ROWSX_STEP(3, 3, base0, 7, 1, oa, ra);
-                        CHIP_ROWSX_STEP(4, 0, base1, 7, 1, oa + 4096u, ra); CHIP_ROWSX_STEP(5, 1, base1, 7, 1, oa + 4096u, ra);
-                        CHIP_ROWSX_STEP(6, 2, base1, 7, 1, oa + 4096u, ra); CHIP_ROWSX_STEP(7, 3, base1, 7, 1, oa + 4096u, ra);
-                    } else {                                 // the wave's last two batches: nothing is re-issued
-                        CHIP_ROWSX_STEP(0, 0, base0, 7, 0, 0u, ra); CHIP_ROWSX_STEP(1, 1, base0, 6, 0, 0u, ra);
-                        CHIP_ROWSX_STEP(2, 2, base0, 5, 0, 0u, ra); CHIP_ROWSX_STEP(3, 3, base0, 4, 0, 0u, ra);
-                        CHIP_ROWSX_STEP(4, 0, base1, 3, 0, 0u, ra); CHIP_ROWSX_STEP(5, 1, base1, 2, 0, 0u, ra);
-                        CHIP_ROWSX_STEP(6, 2, base1, 1, 0, 0u, ra); CHIP_ROWSX_STEP(7, 3, base1, 0, 0, 0u, ra);
-                    }
-                }
-                finish_row(cur);
-                cur = more ? nxt : n_units;
-                rowp = nrow;
-            }
-        };
-        auto stream_depth1 = [&](auto early_tag) {
-            constexpr bool EARLY = decltype(early_tag)::value;
-            const T *rowp = row[0];
-            while (cur < n_units) {
-                uint32_t nxt_v = 0;
-                if (lane == 0) nxt_v = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                int nxt = 0;
-                bool more = false;
-                for (int bb = 0; bb < nb; bb++) {
-                    const int base0 = bb * (CH * U);
-                    const T *ra = rowp;
-                    uint32_t oa = (uint32_t)(bb + 1) * 4096u;
-                    bool ahead = true;
-                    if (bb + 1 == nb) {
-                        nxt = __builtin_amdgcn_readfirstlane((int)nxt_v);
-                        more = nxt < n_units;
-                        ahead = more;
-                        oa = 0u;
-                        if (more) { rowp = uniform_ptr(row_base_uniform<T>(a, unit_row(nxt))); ra = rowp; }
-                    }
-                    if (ahead) {
-                        CHIP_ROWSX_STEP(0, 0, base0, 3, 1, oa, ra); CHIP_ROWSX_STEP(1, 1, base0, 3, 1, oa, ra);
-                        CHIP_ROWSX_STEP(2, 2, base0, 3, 1, oa, ra); CHIP_ROWSX_STEP(3, 3, base0, 3, 1, oa, ra);
-                    } else {
-                        CHIP_ROWSX_STEP(0, 0, base0, 3, 0, 0u, ra); CHIP_ROWSX_STEP(1, 1, base0, 2, 0, 0u, ra);
-                        CHIP_ROWSX_STEP(2, 2, base0, 1, 0, 0u, ra); CHIP_ROWSX_STEP(3, 3, base0, 0, 0, 0u, ra);
-                    }
-                }
-                finish_row(cur);
-                cur = more ? nxt : n_units;
-            }
-        };
-        //   7: depth 2 with the rows claimed by PAIRS of workgroups -- b and b + gridDim / 2, i.e. (round-robin dispatch) the older and the
-        //      younger workgroup of a CU, on the same XCD -- from ONE counter in device memory: the older workgroup, which the memory path
-        //      prefers, simply takes more rows, so both run dry together.  The claim is a global atomic with return, issued from asm at the
-        //      START of a row into v112 (an asm-owned register depth 2 leaves free) and read two batches later: it sits in the in-order
-        //      vector-memory queue, so the waits of the row's first two batches allow ONE more outstanding operation (vmcnt 8 instead of 7)
-        //      and by the time the third batch is waited for it has returned -- no wait of its own.  Pair unit p -> row: ascending in p
-        //      (round, workgroup b's wpb rows, workgroup b + G/2's wpb rows), so "p names a row" is a prefix property.
-        auto stream_pair2 = [&]() {
-            constexpr bool EARLY = false;
-            const int G = (int)gridDim.x, Hh = G >> 1;
-            const int b1 = (int)blockIdx.x < Hh ? (int)blockIdx.x : (int)blockIdx.x - Hh, b2 = b1 + Hh;
-            const int second = (int)blockIdx.x >= Hh ? 1 : 0;
-            uint32_t *pctr = a.pair_ctr + (size_t)b1 * 32;   // a 128-byte line per pair (Ctx::kPairStride)
-            auto units_of = [&](int b) {
-                const int64_t w0 = (int64_t)b * wpb;
-                if (t.n_rows <= w0) return 0;
-                const int64_t span = t.n_rows - w0, pf = span / tw, rem = span - pf * tw;
-                return (int)(pf * wpb + (rem < wpb ? rem : wpb));
-            };
-            const int n_pair = units_of(b1) + units_of(b2);
-            auto prow = [&](int p) {
-                const int round = p / (2 * wpb), o = p - round * 2 * wpb;
-                return (int64_t)round * tw + (o < wpb ? (int64_t)b1 * wpb + o : (int64_t)b2 * wpb + (o - wpb));
-            };
-            auto finish_prow = [&](int p) {
-                const int64_t r = prow(p);
-#pragma unroll
-                for (int q = 0; q < NQ; q++) {
-                    const double s = butterfly_sum(acc[0][q]);
-                    acc[0][q] = 0.0;
-                    wave_topk_offer_lds(s, r * a.idx_mul + a.idx_add, K, lane, mylists + q * CHIP_MAX_TOPK, thr_s[q], thr_i[q]);
-                }
-            };
-            const uint64_t pc = (uint64_t)(uintptr_t)pctr;
-            const uint32_t one = 1u;
-            int pcur = second * wpb + wave;          // this wave's first pair unit = the row whose first batch is already in flight
-            const T *rowp = row[0], *nrow = row[0];
-            if (pcur < n_pair) {
-                CHIP_ROWSX_ISSUE(4, 0, 4096u, rowp); CHIP_ROWSX_ISSUE(5, 1, 4096u, rowp); CHIP_ROWSX_ISSUE(6, 2, 4096u, rowp); CHIP_ROWSX_ISSUE(7, 3, 4096u, rowp);
-            }
-            while (pcur < n_pair) {
-                // the claim of the NEXT row: lane 0 alone, result in v112 (pre-add value; units 0 .. 2 wpb - 1 are the waves' first rows).
-                // Agent scope (sc1): the counter is reset by the launch's LAST workgroup, which may sit on another XCD -- an atomic resolved
-                // in this XCD's L2 alone would leave a dirty line there for the end-of-kernel write-back to put on top of that reset
-                asm volatile("s_mov_b64 s[72:73], exec\n\ts_mov_b64 exec, 1\n\tglobal_atomic_add v112, %0, %1, off sc0 sc1\n\ts_mov_b64 exec, s[72:73]"
-                             ::"v"(pc), "v"(one) : "memory", "s72", "s73");
-                int nxt = 0;
-                bool more = false;
-                for (int bb = 0; bb < nb; bb += 2) {
-                    const int base0 = bb * (CH * U), base1 = base0 + CH * U;
-                    const T *ra = rowp;
-                    uint32_t oa = (uint32_t)(bb + 2) * 4096u;
-                    bool ahead = true;
-                    if (bb + 2 == nb) {
-                        // (nb >= 4: the claim was issued two batches ago; the wait the next take would do anyway also covers it)
-                        int got;
-                        asm volatile("s_waitcnt vmcnt(7)\n\tv_readfirstlane_b32 %0, v112" : "=s"(got)::"memory");
-                        nxt = got + 2 * wpb;
-                        more = nxt < n_pair;
-                        ahead = more;
-                        oa = 0u;
-                        if (more) { nrow = uniform_ptr(row_base_uniform<T>(a, prow(nxt))); ra = nrow; }
-                    }
-                    if (bb == 0) {       // the claim is younger than these two batches' loads: one more operation may stay outstanding
-                        CHIP_ROWSX_STEP(0, 0, base0, 8, 1, oa, ra); CHIP_ROWSX_STEP(1, 1, base0, 8, 1, oa, ra);
-                        CHIP_ROWSX_STEP(2, 2, base0, 8, 1, oa, ra); CHIP_ROWSX_STEP(3, 3, base0, 8, 1, oa, ra);
-                        CHIP_ROWSX_STEP(4, 0, base1, 8, 1, oa + 4096u, ra); CHIP_ROWSX_STEP(5, 1, base1, 8, 1, oa + 4096u, ra);
-                        CHIP_ROWSX_STEP(6, 2, base1, 8, 1, oa + 4096u, ra); CHIP_ROWSX_STEP(7, 3, base1, 8, 1, oa + 4096u, ra);
-                    } else if (ahead) {
-                        CHIP_ROWSX_STEP(0, 0, base0, 7, 1, oa, ra); CHIP_ROWSX_STEP(1, 1, base0, 7, 1, oa, ra);
-                        CHIP_ROWSX_STEP(2, 2, base0, 7, 1, oa, ra); CHIP_ROWSX_STEP(3, 3, base0, 7, 1, oa, ra);
-                        CHIP_ROWSX_STEP(4, 0, base1, 7, 1, oa + 4096u, ra); CHIP_ROWSX_STEP(5, 1, base1, 7, 1, oa + 4096u, ra);
-                        CHIP_ROWSX_STEP(6, 2, base1, 7, 1, oa + 4096u, ra); CHIP_ROWSX_STEP(7, 3, base1, 7, 1, oa + 4096u, ra);
-                    } else {
-                        CHIP_ROWSX_STEP(0, 0, base0, 7, 0, 0u, ra); CHIP_ROWSX_STEP(1, 1, base0, 6, 0, 0u, ra);
-                        CHIP_ROWSX_STEP(2, 2, base0, 5, 0, 0u, ra); CHIP_ROWSX_STEP(3, 3, base0, 4, 0, 0u, ra);
-                        CHIP_ROWSX_STEP(4, 0, base1, 3, 0, 0u, ra); CHIP_ROWSX_STEP(5, 1, base1, 2, 0, 0u, ra);
-                        CHIP_ROWSX_STEP(6, 2, base1, 1, 0, 0u, ra); CHIP_ROWSX_STEP(7, 3, base1, 0, 0, 0u, ra);
-                    }
-                }
-                finish_prow(pcur);
-                pcur = more ? nxt : n_pair;
-                rowp = nrow;
-            }
-        };
-        // (the resident instance runs the product form only: its register budget is the tightest of the three kernels that inline this body)
-        if constexpr (!RESIDENT) {
-            const int form = t.dyn_claim & 255;
-            experimental = form >= 2;
-            if (form == 7 && (nb & 1) == 0 && nb >= 4 && a.pair_ctr != nullptr) stream_pair2();
-            else if (form == 2 && (nb & 1) == 0) stream_depth2(std::false_type{});
-            else if (form == 4 && (nb & 1) == 0) stream_depth2(std::true_type{});
-            else if (form == 3 || form == 4) stream_depth1(std::true_type{});
-            else experimental = false;
-        }
-#endif
-        if (!experimental)
         while (cur < n_units) {
             uint32_t nxt_v = 0;                                 // next unit, claimed by lane 0 alone: needed at this row's last batch
             if (lane == 0) nxt_v = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1251,10 +1000,6 @@ __device__ __forceinline__ void scan_rows_body(const ScanArgs &a, const RowsPass
             }
             cur = more ? nxt : n_units;
         }
-#ifdef CHIP_SCAN_TUNING_VARIANTS
-#undef CHIP_ROWSX_STEP
-#undef CHIP_ROWSX_ISSUE
-#endif
       }
     } else
     for (int t = 0; t < total; t++) {
@@ -1457,7 +1202,6 @@ static int launch_scan_k(Ctx *c, hipStream_t s, const ScanArgs &a, int grid, siz
 // builtin loads) hipcc sinks each load next to its use and a wave runs with 1-2 KiB in flight at 110 VGPRs; the asm form
 // keeps 4 KiB per wave in flight at 66 VGPRs (short scans +5-7 %, 1M rows equal: profiles/r02_scan_load_path.txt).  Rows
 // of whole 2 KiB batches use 2 loads per batch (D = 1536: +6 %); anything else (D * elem % 2048 != 0) takes the builtin path.
-// CHIP_SCAN_VARIANT >= 2: further A/B variants, only in builds with -DCHIP_SCAN_TUNING_VARIANTS.
 // The choice itself is scan_select() below; this launches the instantiation a record names -- one that does not exist is an error.
 template <typename T, int NQ>
 static int launch_scan_q(Ctx *c, hipStream_t s, const ScanArgs &a, const chip_debug_scan_launch &f)
@@ -1482,20 +1226,7 @@ static int launch_scan_q(Ctx *c, hipStream_t s, const ScanArgs &a, const chip_de
     }
     if (f.U == 4 && f.NT == 6 && full) return launch_scan_k<T, NQ, 4, true, 6, 1>(c, s, a, grid, lds, block);
     if (f.U == 2 && f.NT == 6 && full) return launch_scan_k<T, NQ, 2, true, 6, 1>(c, s, a, grid, lds, block);
-#define CHIP_SCAN_EITHER(U_, NT_) \
-    if (f.U == U_ && f.NT == NT_) return full ? launch_scan_k<T, NQ, U_, true, NT_, 1>(c, s, a, grid, lds, block) : launch_scan_k<T, NQ, U_, false, NT_, 1>(c, s, a, grid, lds, block);
-    CHIP_SCAN_EITHER(8, 1)
-#ifdef CHIP_SCAN_TUNING_VARIANTS
-    CHIP_SCAN_EITHER(16, 1)
-    CHIP_SCAN_EITHER(8, 0)
-    CHIP_SCAN_EITHER(4, 1)
-    CHIP_SCAN_EITHER(8, 2)
-    CHIP_SCAN_EITHER(8, 3)
-    CHIP_SCAN_EITHER(8, 4)
-    CHIP_SCAN_EITHER(8, 5)
-    if (f.U == 8 && f.NT == 6 && full) return launch_scan_k<T, NQ, 8, true, 6, 1>(c, s, a, grid, lds, block);
-#endif
-#undef CHIP_SCAN_EITHER
+    if (f.U == 8 && f.NT == 1) return full ? launch_scan_k<T, NQ, 8, true, 1, 1>(c, s, a, grid, lds, block) : launch_scan_k<T, NQ, 8, false, 1, 1>(c, s, a, grid, lds, block);
     return CHIP_ERR_UNSUPPORTED;
 }
 
@@ -1671,23 +1402,6 @@ int scan_select(const Ctx *c, const ScanArgs &a, int nq, int grid, chip_debug_sc
     }
     f->family = CHIP_SCAN_FAMILY_ONE_ROW;
     f->R = 1;
-#ifdef CHIP_SCAN_TUNING_VARIANTS
-    {
-        int u = 0, nt = 0;
-        switch (c->scan_variant) {
-            case 2: u = 16; nt = 1; break;
-            case 3: u = 8; nt = 0; break;
-            case 4: u = 4; nt = 1; break;
-            case 7: u = 8; nt = 2; break;
-            case 8: u = 8; nt = 3; break;
-            case 9: u = 8; nt = 4; break;
-            case 10: u = 8; nt = 5; break;
-            case 11: if (row_bytes % 8192 == 0) { u = 8; nt = 6; } break;
-            default: break;
-        }
-        if (u) { f->U = u; f->NT = nt; f->FULL = row_bytes % (1024 * u) == 0; return CHIP_OK; }
-    }
-#endif
     if (c->elem == 4 && a.q64) { f->U = 4; f->NT = 8; f->FULL = 1; return CHIP_OK; }   // scan_q64() said so (float rows only)
 #ifndef CHIP_NO_ROWS_FORM
     if (a.rows_form > 0) {   // scan_rows_form() said so: whole 4 KiB batches, R rows per wave in one continuous load stream

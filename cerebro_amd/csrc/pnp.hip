@@ -200,8 +200,6 @@ constexpr int kPnpMaxBatch = 8;
 struct SolveArgs {
     PnpProblem prob[kPnpMaxBatch];
     int32_t H, S;
-    int32_t slot0;          // first slot of this launch (a batch may be issued as several launch pairs)
-    int32_t factor_prio;    // > 0: the LU's factor wave runs at raised issue priority (s_setprio)
     const PnpTables *tab;
     double *Sg;         // [H][729]  action matrices
     double *Tg;         // [H][27]   translation factor (t = Tfac * vec(R))
@@ -260,7 +258,7 @@ __global__ __launch_bounds__(kSolveThreads) __attribute__((amdgpu_waves_per_eu(4
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
-    const int slot = blockIdx.x + a.slot0;
+    const int slot = blockIdx.x;
     const int pi = slot / a.H;
     const int hyp = slot - pi * a.H;                               // hypothesis index within its problem (keys the RNG)
     const PnpProblem pr = a.prob[pi];
@@ -646,9 +644,8 @@ __global__ __launch_bounds__(kSolveThreads) __attribute__((amdgpu_waves_per_eu(4
     };
 
     // The factor wave's chain is the LU's critical path and it shares its SIMD with matrix waves streaming fp64 FMAs: at equal
-    // priority it gets one issue slot in ~4 (shader-clock split: ~20 cycles per dependent instruction).  Raised priority lets the
-    // arbiter pick it whenever it is ready; the matrix waves fill the slots its latencies leave.  CHIP_PNP_PRIO (tuning knob).
-    if (is_factor && a.factor_prio > 0) __builtin_amdgcn_s_setprio(3);
+    // priority it gets one issue slot in ~4 (shader-clock split: ~20 cycles per dependent instruction).  Raising its issue priority
+    // was measured to change nothing (profiles/r03_pnp_pmc.md).
     if (is_factor) { load_panel(0); factor_panel(std::integral_constant<int, kPanel>{}, 0, 0); }
     __syncthreads();
     // tuning only (CHIP_PNP_STAMPS): per-phase shader-clock totals of the LU, wave 0 (a matrix wave) and wave 6 (the factor wave)
@@ -808,7 +805,6 @@ __global__ __launch_bounds__(kSolveThreads) __attribute__((amdgpu_waves_per_eu(4
     }
 #undef F_STAMP
 #undef LU_STAMP
-    __builtin_amdgcn_s_setprio(0);
     if (singular) {
         if (tid == 0) a.ok[slot] = 0;
         return;
@@ -1499,7 +1495,8 @@ __device__ __forceinline__ void qr_sweep_head_asm(int n, uint32_t hs0, int lane,
 struct EigArgs {
     PnpProblem prob[kPnpMaxBatch];
     int32_t H, S;
-    int32_t slot0, pad2_;
+    int32_t slot0, pad2_;   // always 0 (one launch covers the batch).  Still read by pnp_eig_score: without that add the hand-scheduled QR loop
+                            // starts 16 bytes earlier and the kernel measured ~2 % slower; goes once the loop's placement is pinned
     double thresh;
     int32_t use_mle;
     double *Sg;             // [H][729]  in: the action matrices; scratch of the loop-form back-substitution afterwards
@@ -2332,8 +2329,6 @@ struct PnpState {
     int32_t *nin = nullptr, *valid = nullptr, *nsol = nullptr;
     unsigned long long *mask = nullptr;
     unsigned long long *stamps = nullptr;                // tuning only (CHIP_PNP_STAMPS): [H][8] of pnp_eig_score, then [H][16] of pnp_build_solve
-    hipStream_t s2 = nullptr;                            // second launch-pair stream of a split batch (CHIP_PNP_GROUPS)
-    hipEvent_t ev_in = nullptr, ev_g2 = nullptr;
     int32_t stamps_n = 0;
 };
 
@@ -2366,9 +2361,6 @@ static void pnp_free_dev(PnpState *st)
     (void)hipHostFree(st->h_cost); (void)hipHostFree(st->h_T); (void)hipHostFree(st->h_nin); (void)hipHostFree(st->h_valid);
     (void)hipHostFree(st->h_nsol); (void)hipHostFree(st->h_mask); (void)hipHostFree(st->h_sample_in);
     (void)hipFree(st->stamps);
-    if (st->s2) (void)hipStreamDestroy(st->s2);
-    if (st->ev_in) (void)hipEventDestroy(st->ev_in);
-    if (st->ev_g2) (void)hipEventDestroy(st->ev_g2);
 }
 
 void pnp_destroy(Ctx *c)
@@ -2471,12 +2463,7 @@ static int pnp_run(Ctx *c, PnpState *st, int P, const double *const *X, const do
         pr.X = st->d_hin + 3 * (size_t)off; pr.uv = st->d_hin + 3 * (size_t)Ntot + 2 * (size_t)off;
         sa.prob[i] = pr;                                   // pnp_build_solve: the pinned host buffer, in place
     }
-    // no H2D copy: see SolveArgs.  (CHIP_PNP_H2D=1 restores it for A/B runs.)
-    static const bool want_h2d = std::getenv("CHIP_PNP_H2D") != nullptr;
-    if (want_h2d && !dev_in) {
-        CHIP_HIP(c, hipMemcpyAsync(st->X, st->h_in, sizeof(double) * 5 * (size_t)Ntot, hipMemcpyHostToDevice, s));
-        for (int i = 0; i < P; i++) sa.prob[i] = ea.prob[i];
-    }
+    // no H2D copy: see SolveArgs
     if (ht.on) ht1 = ht_now();
     if (p->sampler == CHIP_SAMPLER_THEIA_PERSISTENT) {   // one persistent permutation per problem, hypotheses 0..H-1 in order
         for (int i = 0; i < P; i++) {
@@ -2487,7 +2474,7 @@ static int pnp_run(Ctx *c, PnpState *st, int P, const double *const *X, const do
     }
     sa.H = H; sa.S = S; sa.tab = st->tab_dev;
     sa.Sg = st->Sg; sa.Tg = st->Tg; sa.sample = st->sample; sa.ok = st->ok;
-    sa.in_host = (want_h2d || dev_in) ? nullptr : st->d_hin; sa.in_dev = st->X; sa.n_in = 5 * (int64_t)Ntot;
+    sa.in_host = dev_in ? nullptr : st->d_hin; sa.in_dev = st->X; sa.n_in = 5 * (int64_t)Ntot;
     const size_t lds = kSolveLds;
     static const bool want_stamps = std::getenv("CHIP_PNP_STAMPS") != nullptr;
     if (want_stamps) {
@@ -2518,37 +2505,15 @@ static int pnp_run(Ctx *c, PnpState *st, int P, const double *const *X, const do
 #endif
     ea.T_out = st->T_out; ea.cost = st->cost; ea.nin = st->nin; ea.valid = st->valid; ea.nsol = st->nsol; ea.mask = st->mask;
     if (want_stamps) ea.stamps = st->stamps;
-    // A batch of several problems may go out as `groups` launch pairs on as many streams (CHIP_PNP_GROUPS, tuning): both kernels are
-    // latency chains that leave issue slots free, so build(group g+1) can run underneath eig(group g).  Measured NEGATIVE twice: two
-    // groups -3 % (round 5), and the fully pipelined form -- pnp_build_solve of consecutive slot groups back to back on one stream,
-    // pnp_eig_score(g) on a second, lower-priority stream behind build(g)'s event -- 1.7-2.1 M hyp/s against 2.52 M for one launch pair
-    // (round 6, profiles/r06_pnp.md): the two kernels do not share a CU's REGISTER FILE -- four resident eigen waves (4 x 128 rows)
-    // leave room for ONE pnp_build_solve workgroup (784 rows) instead of two, whatever the stream priorities say.
-    static const int want_groups = [] { const char *e = std::getenv("CHIP_PNP_GROUPS"); return e ? std::atoi(e) : 1; }();
-    static const int want_prio = [] { const char *e = std::getenv("CHIP_PNP_PRIO"); return e ? std::atoi(e) : 0; }();   // measured: no effect (profiles/r03_pnp_pmc.md)
-    sa.factor_prio = want_prio;
-    int groups = want_groups < 1 ? 1 : (want_groups > 2 ? 2 : want_groups);
-    if (groups > P) groups = P;
-    if (groups > 1 && !st->s2) {
-        CHIP_HIP(c, hipStreamCreateWithFlags(&st->s2, hipStreamNonBlocking));
-        CHIP_HIP(c, hipEventCreateWithFlags(&st->ev_in, hipEventDisableTiming));
-        CHIP_HIP(c, hipEventCreateWithFlags(&st->ev_g2, hipEventDisableTiming));
-    }
-    if (groups > 1) CHIP_HIP(c, hipEventRecord(st->ev_in, s));   // inputs (and the stamp memset) are on the device
-    for (int g = 0; g < groups; g++) {
-        const int p0 = (int)((long long)P * g / groups), p1 = (int)((long long)P * (g + 1) / groups);
-        hipStream_t sg = g == 0 ? s : st->s2;
-        if (g > 0) CHIP_HIP(c, hipStreamWaitEvent(sg, st->ev_in, 0));
-        sa.slot0 = ea.slot0 = p0 * H;
-        const int nslots = (p1 - p0) * H;
-        if (want_stamps) hipLaunchKernelGGL(pnp_build_solve<true>, dim3(nslots), dim3(kSolveThreads), lds, sg, sa);
-        else hipLaunchKernelGGL(pnp_build_solve<false>, dim3(nslots), dim3(kSolveThreads), lds, sg, sa);
-        CHIP_HIP(c, hipGetLastError());
-        if (want_stamps) hipLaunchKernelGGL(pnp_eig_score<true>, dim3(nslots), dim3(64), 0, sg, ea);
-        else hipLaunchKernelGGL(pnp_eig_score<false>, dim3(nslots), dim3(64), 0, sg, ea);
-        CHIP_HIP(c, hipGetLastError());
-        if (g > 0) { CHIP_HIP(c, hipEventRecord(st->ev_g2, sg)); CHIP_HIP(c, hipStreamWaitEvent(s, st->ev_g2, 0)); }
-    }
+    // One launch pair for the whole batch.  Splitting it so that pnp_build_solve of one group runs underneath pnp_eig_score of another
+    // cannot pay: the two kernels share a CU's register file -- four resident eigen waves (4 x 128 rows) leave room for ONE
+    // pnp_build_solve workgroup (784 rows) instead of two (measured negative twice, profiles/r06_pnp.md; code last in commit af4232e).
+    if (want_stamps) hipLaunchKernelGGL(pnp_build_solve<true>, dim3(P * H), dim3(kSolveThreads), lds, s, sa);
+    else hipLaunchKernelGGL(pnp_build_solve<false>, dim3(P * H), dim3(kSolveThreads), lds, s, sa);
+    CHIP_HIP(c, hipGetLastError());
+    if (want_stamps) hipLaunchKernelGGL(pnp_eig_score<true>, dim3(P * H), dim3(64), 0, s, ea);
+    else hipLaunchKernelGGL(pnp_eig_score<false>, dim3(P * H), dim3(64), 0, s, ea);
+    CHIP_HIP(c, hipGetLastError());
     if (ht.on) ht2 = ht_now();
     CHIP_HIP(c, hipStreamSynchronize(s));   // every per-hypothesis result is in host memory now
     if (ht.on) ht3 = ht_now();

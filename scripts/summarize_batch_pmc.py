@@ -29,9 +29,9 @@ md += ["", f"Derived: `GRBM_GUI_ACTIVE` / 8 XCDs = {gui:.3e} cycles per launch; 
        "is read as `ds_read2_b32` column reads over unpadded 128-B rows (4-way), which costs LDS-array cycles",
        f"(`SQ_LDS_IDX_ACTIVE` {rows['SQ_LDS_IDX_ACTIVE'][1]:.3e}, i.e. {rows['SQ_LDS_IDX_ACTIVE'][1] / 256 / gui:.2f} of the launch per CU) instead of VALU issue slots;",
        f"`SQ_WAIT_INST_LDS` / (4 x `SQ_WAVE_CYCLES`) = {rows['SQ_WAIT_INST_LDS'][1] / (4 * rows['SQ_WAVE_CYCLES'][1]):.4f} of wave time.", "",
-       "Throughput of the same launch on the same box (`scripts/gpu_batch_variants.py`, hipEvents):", ""] + [f"    {v}" for v in variants] + ["",
+       "Throughput of the same launch on the same box (hipEvents; the sweep script is in the git history up to commit `af4232e`):", ""] + [f"    {v}" for v in variants] + ["",
        "This quantity varies between the boxes of the pool: two stages 119.4 / 118.3 / 111.1 / 117.5 TFLOP/s on four boxes (0.71-0.76 of 157.3),",
-       "four stages (one workgroup per CU, `CHIP_BATCH_STAGES=4`) 112.4 / 113.1 / 112.3 / 113.0; round-1 kernel 110.9 / 105-106.", "",
+       "a four-stage variant at one workgroup per CU, since removed, measured 112.4 / 113.1 / 112.3 / 113.0; round-1 kernel 110.9 / 105-106.", "",
        "On the way (four-stage variant with 16-B fragment reads + `v_cndmask`, one workgroup per CU, 104 TFLOP/s): MFMA busy 0.668 with ONE wave",
        "per SIMD, `SQ_LDS_BANK_CONFLICT` 3.4e5 (none), `SQ_WAIT_INST_LDS` 0.2 % -- LDS idle, HBM modest, so the wave's own instruction stream was",
        "what the matrix pipe waited for; round-1 kernel: MFMA busy 0.716 at two waves per SIMD, `FETCH_SIZE` 1.68e7 KiB.", "",

@@ -174,7 +174,7 @@ KNOB_SETTINGS = [{}] + [{"CHIP_SCAN_ROWS": v} for v in ("-1", "1", "2", "3")] + 
     {"CHIP_SCAN_SHORT_BPC": "0"}, {"CHIP_SCAN_PLAIN_MIB": "0"}, {"CHIP_SCAN_HALF_MIB": "0"}, {"CHIP_SCAN_SYNC_PLAIN_MIB": "0"},
     {"CHIP_SCAN_OVERLAP_GIB": "0"}, {"CHIP_SCAN_RESERVE": "4"}, {"CHIP_SCAN_VARIANT": "1"}, {"CHIP_SCAN_VARIANT": "7"}, {"CHIP_TICK_FUSED": "0"}]
 SCAN_ENV = sorted({k for c in CASES for k in c.env} | {k for s in KNOB_SETTINGS for k in s} |
-                  {"CHIP_SCAN_BLOCK", "CHIP_SCAN_BPC", "CHIP_SCAN_DEPTH", "CHIP_SCAN_STAGGER", "CHIP_SCAN_STREAMS", "CHIP_TICK_SAME_STREAM"})
+                  {"CHIP_SCAN_BLOCK", "CHIP_SCAN_BPC", "CHIP_SCAN_STREAMS", "CHIP_TICK_SAME_STREAM"})
 
 CALL_CODE = {QUERY: 0, TICK: 1, SYNC: 2}         # CHIP_SCAN_CALL_*
 

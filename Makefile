@@ -13,7 +13,7 @@ ORCFLAGS   ?= -O2 -mfma -ffp-contract=off -fopenmp -fPIC -Wall -Wextra
 
 LIBDIR     := cerebro_amd/lib
 CSRC       := cerebro_amd/csrc
-HIP_SRCS   := $(CSRC)/kernels.hip $(CSRC)/chip_api.hip $(CSRC)/chip_multi.hip $(CSRC)/pnp.hip $(CSRC)/icp.hip $(CSRC)/batch.hip $(CSRC)/match.hip
+HIP_SRCS   := $(CSRC)/kernels.hip $(CSRC)/chip_api.hip $(CSRC)/resident.hip $(CSRC)/chip_multi.hip $(CSRC)/pnp.hip $(CSRC)/icp.hip $(CSRC)/batch.hip $(CSRC)/match.hip
 HIP_OBJS   := $(HIP_SRCS:$(CSRC)/%.hip=$(LIBDIR)/%.o)
 ORC_SRCS   := $(wildcard oracle/*.c)
 
@@ -27,7 +27,7 @@ testlibs: tests/fakerccl/_build/libfakerccl.so $(LIBDIR)/norows/libcerebro_hip.s
 # CHIP_TEST_BATCH_OOM, CHIP_TEST_RESIDENT_SKIP_MASTER) and the knobs that change what a kernel computes (CHIP_PNP_BACKSUB,
 # CHIP_PNP_DEBUG_STOP) exist ONLY here.  `make lib` -- the product -- compiles none of them in (chip_get_info().test_hooks == 0);
 # tests/ load this one for the tests that inject faults (cerebro_amd.capi.use_hooks_library).  Never deploy it.
-HOOK_SRCS  := chip_api chip_multi pnp
+HOOK_SRCS  := chip_api resident chip_multi pnp
 HOOK_OBJS  := $(HOOK_SRCS:%=$(LIBDIR)/hooks/%.o)
 $(LIBDIR)/hooks/%.o: $(CSRC)/%.hip $(CSRC)/chip_internal.h $(CSRC)/ransac_common.h $(CSRC)/topk_merge.h include/cerebro_hip.h
 	@mkdir -p $(LIBDIR)/hooks

@@ -414,7 +414,7 @@ int batch_local_enqueue(Ctx *c, int64_t k, const float *queries, int32_t Q, int3
         if (!c->batch_state) return CHIP_ERR_OOM;
     }
     BatchState *st = static_cast<BatchState *>(c->batch_state);
-    ResidentPause paused(c, c->tick_resident);   // the many-query scan fills every CU (and may free / allocate): no resident scan instance until it returns
+    ResidentPause paused(c);   // the many-query scan fills every CU (and may free / allocate): no resident scan instance until it returns
     const int D = c->D;
     const int Qpad = batch_qpad(Q);
     const int64_t n_rows = local_count(c, k);
@@ -472,14 +472,10 @@ int batch_local_enqueue(Ctx *c, int64_t k, const float *queries, int32_t Q, int3
     const size_t lds_gemm = sizeof(float) * NST * ((size_t)TM * KCsel + (size_t)(TN / 8) * kBBlock) /* stages x (A + B) */;
     const size_t lds_ct = sizeof(float) * (size_t)TM * CT_LD;
     const size_t lds = lds_gemm > lds_ct ? lds_gemm : lds_ct;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipEvent_t e1 = nullptr;
     if (c->prof_on) {
-        if (c->prof_used + 2 > c->prof_ev.size())
-            for (int i = 0; i < 2; i++) { hipEvent_t e; CHIP_HIP(c, hipEventCreate(&e)); c->prof_ev.push_back(e); }
-        e0 = c->prof_ev[c->prof_used]; e1 = c->prof_ev[c->prof_used + 1];
-        c->prof_used += 2;
-        c->prof_bytes_last = (double)n_rows * D * 4.0 * qtiles;   // the DB is streamed once per query tile
-        CHIP_HIP(c, hipEventRecord(e0, s));
+        const int prc = prof_begin(c, s, (double)n_rows * D * 4.0 * qtiles, &e1);   // the DB is streamed once per query tile
+        if (prc != CHIP_OK) return prc;
     }
     auto launch = [&](auto kernel, int threads) -> int {
         CHIP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

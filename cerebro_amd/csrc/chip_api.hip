@@ -8,7 +8,6 @@
 #include "chip_internal.h"
 #include <cmath>
 #include <cstdlib>
-#include <chrono>
 #include <cstring>
 #include <memory>
 #include <new>
@@ -94,347 +93,6 @@ int env_int(const char *name, int dflt)
     return v && *v ? std::atoi(v) : dflt;
 }
 
-// ------------------------------------------------------------------------------------------------ resident scan instance
-static inline void host_store_fence()
-{
-#if defined(__x86_64__) || defined(__i386__)
-    __builtin_ia32_sfence();                        // drains the write-combining buffers of the BAR mapping
-#else
-    __atomic_thread_fence(__ATOMIC_SEQ_CST);
-#endif
-}
-// (CHIP_TICK_RESIDENT=1; kernels.hip db_scan_resident, chip_internal.h ResidentCmd).  Host side: one command at a time; the line is
-// written head first, tail last (x86 stores stay in order; the fences keep the compiler from moving them).
-static void resident_write_line(Ctx *c, const ResidentCmd &cmd)
-{
-    if (c->res_direct) {
-        // every workgroup's own line, through the write-combining BAR mapping: eight 8-byte stores per line in address order (head first,
-        // tail last; a full 64-byte line leaves the CPU as one PCIe write), one fence for all of them
-        ResidentCmd t = cmd;
-        t.tail = t.head;
-        uint64_t w[8];
-        std::memcpy(w, &t, 64);
-        volatile uint64_t *d = reinterpret_cast<volatile uint64_t *>(c->res_cmd_host);
-        int first = 0;
-#ifdef CHIP_TEST_HOOKS   // test build only (make testlibs -> cerebro_amd/lib/hooks/): the product library has no fault injection
-        // CHIP_TEST_RESIDENT_SKIP_MASTER=k: the k-th command never reaches workgroup 0's line -- the other workgroups run it, workgroup 0
-        // leaves at its lease without it: exactly what a command posted in the moment the lease runs out can look like (tests drive
-        // resident_collect's recovery with it)
-        if (cmd.n_rows >= 0 && c->res_test_skip_master > 0 && c->res_ticks + 1 == c->res_test_skip_master && !c->res_test_skipped) {
-            first = 1;
-            c->res_test_skipped = true;
-        }
-#endif
-        for (int j = first; j < c->res_grid; j++)
-            for (int i = 0; i < 8; i++) d[j * 8 + i] = w[i];
-        host_store_fence();
-        return;
-    }
-    ResidentCmd *d = c->res_cmd_host;
-    __atomic_store_n(&d->head, cmd.head, __ATOMIC_RELAXED);
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-    d->locality = cmd.locality;
-    d->n_rows = cmd.n_rows;
-    d->tick_l = cmd.tick_l;
-    d->thresh = cmd.thresh;
-    d->result = cmd.result;
-    d->seq_ptr = cmd.seq_ptr;
-    d->seq_val = cmd.seq_val;
-    d->dyn_claim = cmd.dyn_claim;
-    __atomic_store_n(&d->tail, cmd.head, __ATOMIC_RELEASE);
-    // a line in device memory is written through the write-combining BAR mapping: push it out (one full 64-byte line = one PCIe write)
-    if (c->res_cmd_in_vram) host_store_fence();
-}
-
-static uint32_t resident_next_number(Ctx *c)
-{
-    uint32_t n = c->res_cmd_no + 1;
-    if (n == 0u || n == kResidentLeave) n = 1u;
-    c->res_cmd_no = n;
-    return n;
-}
-
-static void resident_free(Ctx *c)
-{
-    if (c->s_resident) { (void)hipStreamDestroy(c->s_resident); c->s_resident = nullptr; }
-    if (c->res_pinned) { (void)hipHostFree(c->res_pinned); c->res_pinned = nullptr; }
-    if (c->res_cmd_vram) { (void)hipFree(c->res_cmd_vram); c->res_cmd_vram = nullptr; }
-    if (c->res_cmd_dev) { (void)hipFree(c->res_cmd_dev); c->res_cmd_dev = nullptr; }
-    if (c->res_partial) { (void)hipFree(c->res_partial); c->res_partial = nullptr; }
-    if (c->res_ticket) { (void)hipFree(c->res_ticket); c->res_ticket = nullptr; }
-    c->res_cmd_host = nullptr; c->res_cmd_hostdev = nullptr; c->res_exit_host = nullptr; c->res_exit_hostdev = nullptr;
-    c->res_cmd_in_vram = false; c->res_direct = false;
-    c->res_ready = false;
-}
-
-// does a pattern the CPU stores through the BAR mapping of `v` (64 bytes of device memory) read back through a copy?  Leaves zeros.
-static bool bar_write_probe(void *v)
-{
-    if (hipMemset(v, 0, 64) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return false;
-    uint32_t back[16] = {0};
-    volatile uint32_t *w = static_cast<volatile uint32_t *>(v);
-    for (int i = 0; i < 16; i++) w[i] = 0x5eed0000u + (uint32_t)i;
-    host_store_fence();
-    bool ok = hipMemcpy(back, v, 64, hipMemcpyDeviceToHost) == hipSuccess;
-    for (int i = 0; ok && i < 16; i++) ok = back[i] == 0x5eed0000u + (uint32_t)i;
-    for (int i = 0; i < 16; i++) w[i] = 0u;
-    host_store_fence();
-    return ok;
-}
-
-static int resident_alloc_body(Ctx *c)
-{
-    // A stream of the HIGHEST priority: the runtime multiplexes streams onto a few hardware queues per priority level, and a packet
-    // behind the resident kernel in its queue would wait for the instance to leave (measured: a tick stream that shared the queue
-    // stalled for the whole lease).  The ctx's other streams are of the default priority, so this one gets a queue to itself.
-    int pr_lo = 0, pr_hi = 0;
-    CHIP_HIP(c, hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi));
-    CHIP_HIP(c, hipStreamCreateWithPriority(&c->s_resident, hipStreamNonBlocking, pr_hi));
-    void *h = nullptr;
-    CHIP_HIP(c, hipHostMalloc(&h, 128, hipHostMallocDefault));   // the command line + the line of the exit word
-    std::memset(h, 0, 128);
-    c->res_pinned = h;
-    c->res_cmd_host = static_cast<ResidentCmd *>(h);
-    c->res_exit_host = reinterpret_cast<unsigned long long *>(static_cast<char *>(h) + 64);
-    void *hd = nullptr;
-    CHIP_HIP(c, hipHostGetDevicePointer(&hd, h, 0));
-    c->res_cmd_hostdev = static_cast<uint32_t *>(hd);
-    c->res_exit_hostdev = reinterpret_cast<unsigned long long *>(static_cast<char *>(hd) + 64);
-    // Where the command line lives.  With a large PCIe BAR the host can store straight into device memory, and a posted write that the
-    // device then finds locally beats a line the device has to fetch over PCIe (ping-pong with one polling wave: 1.89 us against 2.52,
-    // scripts/probes/bar_pingpong.hip).  Used when the device says so AND a pattern written that way into THE buffer itself reads back
-    // through a copy (probing a throw-away allocation says nothing about this one); CHIP_RESIDENT_BAR=0 keeps the line in
-    // pinned host memory.
-    // CHIP_RESIDENT_BAR=2 (the default) goes one step further: the host writes EVERY workgroup's line that way (16 KiB per command,
-    // 0.6 us of host time) and nobody relays: 10k rows 35.9-36.4 -> 34.7-35.0 us.  1: only workgroup 0's line, relayed on the device.
-    c->res_grid = c->n_cus * (c->scan_short_bpc > 0 ? c->scan_short_bpc : 1);
-    if (c->res_grid > c->max_grid) c->res_grid = c->max_grid;
-    CHIP_HIP(c, hipMalloc((void **)&c->res_cmd_dev, (size_t)c->max_grid * 64));
-    CHIP_HIP(c, hipMemset(c->res_cmd_dev, 0, (size_t)c->max_grid * 64));
-    const int bar_mode = env_int("CHIP_RESIDENT_BAR", 2);
-    int large_bar = 0;
-    if (bar_mode != 0 && hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, c->device) == hipSuccess && large_bar) {
-        if (bar_mode == 2) {
-            // the workgroups' lines themselves are the host's target (line 0 is workgroup 0's): probe the first and the last line of them
-            if (bar_write_probe(c->res_cmd_dev) && bar_write_probe(reinterpret_cast<char *>(c->res_cmd_dev) + (size_t)(c->max_grid - 1) * 64)) {
-                c->res_cmd_in_vram = true;
-                c->res_direct = true;
-                c->res_cmd_host = reinterpret_cast<ResidentCmd *>(c->res_cmd_dev);
-                c->res_cmd_hostdev = c->res_cmd_dev;
-            }
-        }
-        if (!c->res_direct) {                   // mode 1, or mode 2 whose lines are not host-writable: one line of its own, relayed on the device
-            void *v = nullptr;
-            if (hipMalloc(&v, 64) == hipSuccess) {
-                if (bar_write_probe(v)) {
-                    c->res_cmd_vram = v;
-                    c->res_cmd_in_vram = true;
-                    c->res_cmd_host = static_cast<ResidentCmd *>(v);
-                    c->res_cmd_hostdev = static_cast<uint32_t *>(v);
-                } else {
-                    (void)hipFree(v);
-                }
-            }
-        }
-    }
-    CHIP_HIP(c, hipMalloc((void **)&c->res_partial, (size_t)c->max_grid * CHIP_MAX_NQ * CHIP_MAX_TOPK * sizeof(chip_topk_entry)));
-    CHIP_HIP(c, hipMalloc((void **)&c->res_ticket, 64));
-    return CHIP_OK;
-}
-
-// res_mu held.  Either everything exists afterwards (res_ready, published last) or nothing does and the mode is off for this ctx: the
-// caller falls back to the launched tick (a half-built state must not be entered by the next tick).
-static int resident_alloc(Ctx *c)
-{
-    if (c->res_ready) return CHIP_OK;
-    const int rc = resident_alloc_body(c);
-    if (rc != CHIP_OK) {
-        resident_free(c);
-        c->tick_resident = false;
-        std::fprintf(stderr, "[cerebro_hip] resident scan instance: allocation failed (%s) -- this ctx launches its ticks\n", chip_strerror(rc));
-        return CHIP_ERR_UNSUPPORTED;
-    }
-    c->res_ready = true;
-    return CHIP_OK;
-}
-
-// A new instance behind whatever the stream still holds (the previous one on its way out).  res_mu held.
-static int resident_launch(Ctx *c)
-{
-    ResidentArgs ra;
-    ScanArgs &a = ra.base;
-    a.seg_table = c->seg_table_dev;
-    a.seg_shift = c->seg_shift;
-    a.seg_mask = c->seg_rows - 1;
-    a.n_rows = 0;
-    a.D = c->D;
-    a.K = 1;
-    for (int i = 0; i < CHIP_MAX_NQ; i++) a.q[i] = nullptr;
-    a.idx_mul = 1;
-    a.idx_add = 0;
-    a.partial = c->res_partial;
-    a.rows_form = 1;
-    a.plain_loads = 1;
-    a.fused_ticket = c->res_ticket;
-    a.stamps = c->stamps_dev;            // tuning only (CHIP_SCAN_STAMPS=1)
-    ra.cmd_host = c->res_cmd_hostdev;
-    ra.cmd_dev = c->res_cmd_dev;
-    ra.exit_host = c->res_exit_hostdev;
-    ra.instance = ++c->res_instance;
-    ra.lease_ticks = (unsigned long long)c->res_lease_ms * 100000ull;   // s_memrealtime: 100 MHz
-    ra.done = c->res_done;
-    ra.direct = c->res_direct ? 1u : 0u;
-    // the workgroups' lines still hold what the previous instance was told last (its leave mark included), the ticket whatever it left.
-    // (direct mode: the lines are the host's to write -- the caller has posted the command the new instance is to find there)
-    if (!c->res_direct) CHIP_HIP(c, hipMemsetAsync(c->res_cmd_dev, 0, (size_t)c->max_grid * 64, c->s_resident));
-    CHIP_HIP(c, hipMemsetAsync(c->res_ticket, 0, 64, c->s_resident));
-    int rc = launch_resident(c, c->s_resident, ra, c->res_grid);
-    if (rc != CHIP_OK) return rc;
-    c->res_alive = true;
-    c->res_launches++;
-    return CHIP_OK;
-}
-
-static bool resident_has_left(const Ctx *c)
-{
-    return __atomic_load_n(c->res_exit_host, __ATOMIC_ACQUIRE) == c->res_instance;
-}
-
-static void resident_stop_locked(Ctx *c)
-{
-    if (!c->res_ready || !c->res_alive) return;
-    if (c->res_busy && c->res_slot) {   // a command is still running: let it finish (its collector only reads the completion word)
-        const volatile unsigned long long *w = c->res_slot->seq_host;
-        for (long spin = 0; spin < (1L << 28) && __atomic_load_n(w, __ATOMIC_ACQUIRE) != c->res_slot->seq_want && !resident_has_left(c); spin++) {}
-    }
-    if (!resident_has_left(c)) {
-        ResidentCmd cmd{};
-        cmd.head = resident_next_number(c);
-        cmd.n_rows = -1;
-        resident_write_line(c, cmd);
-        c->res_done = cmd.head;          // nobody runs a leave command twice
-    }
-    (void)hipStreamSynchronize(c->s_resident);
-    c->res_alive = false;
-}
-
-void resident_stop(Ctx *c)
-{
-    if (!c->tick_resident) return;
-    std::lock_guard<std::mutex> lk(c->res_mu);
-    resident_stop_locked(c);
-}
-
-void resident_pause(Ctx *c)
-{
-    std::lock_guard<std::mutex> lk(c->res_mu);
-    c->res_inhibit++;                    // from here on resident_tick_enqueue launches nothing (it checks under this mutex)
-    resident_stop_locked(c);
-}
-
-void resident_resume(Ctx *c)
-{
-    std::lock_guard<std::mutex> lk(c->res_mu);
-    if (c->res_inhibit > 0) c->res_inhibit--;
-}
-
-static bool resident_eligible(Ctx *c, int64_t k)
-{
-    if (!c->tick_resident || c->nranks != 1 || c->xchg || c->parent || c->group || !c->own_query_stream || c->prof_on || !c->tick_fused ||
-        !c->tick_poll || c->res_busy)
-        return false;
-    // One workgroup per CU, so that the ctx's other kernels (append, PnP, ICP) still find registers and LDS next to the instance.  That
-    // shape is what a launch gives a cache-sized prefix anyway, and a synchronous tick loses nothing with it up to the reference's own
-    // capacity (29k rows: 93.9-94.7 us launched with one workgroup per CU, 93.8-94.1 with two; profiles/r05_resident.md).
-    if ((double)k * c->D * c->elem > c->res_max_bytes) return false;
-    const int grid = c->n_cus * (c->scan_short_bpc > 0 ? c->scan_short_bpc : 1);
-    return scan_rows_form(c, k, 3, grid, false) == 1;
-}
-
-constexpr int kResidentPaused = 1;   // (internal, > 0: not a status code) the mode is paused, launch this tick
-
-// The tick as a command to the resident instance (launched here if there is none, or if the last one has left).  query_mu held.
-static int resident_tick_enqueue(Ctx *c, int64_t k, int64_t l, const chip_dot_params *p, Slot &s)
-{
-    std::lock_guard<std::mutex> lk(c->res_mu);
-    if (c->res_inhibit > 0) return kResidentPaused;   // a section that frees / allocates / rewrites the table is open: this tick is launched
-    int rc = resident_alloc(c);
-    if (rc != CHIP_OK) return rc;
-    if (c->res_alive && resident_has_left(c)) c->res_alive = false;
-    const bool launch = !c->res_alive;
-    if (launch && c->res_direct) (void)hipStreamSynchronize(c->s_resident);   // the old instance is gone before its lines are rewritten
-    s.seq_want = ++c->tick_seq;
-    ResidentCmd cmd{};
-    cmd.head = resident_next_number(c);
-    cmd.locality = p->locality;
-    cmd.n_rows = k;
-    cmd.tick_l = l;
-    cmd.thresh = p->thresh;
-    cmd.result = (uint64_t)(uintptr_t)s.dev;
-    cmd.seq_ptr = (uint64_t)(uintptr_t)s.seq_dev;
-    cmd.seq_val = s.seq_want;
-    // rows claimed within the workgroup: beyond cache-sized prefixes, as for launches (29k rows: 92.3 -> 91.7 us; neutral at 10k)
-    cmd.dyn_claim = (c->scan_claim == 1 || (c->scan_claim < 0 && (double)k * c->D * c->elem > c->scan_half_bytes)) ? 1u : 0u;
-    c->res_pending = cmd;
-    resident_write_line(c, cmd);           // (before the launch: an instance must never find the previous one's leave mark in its lines)
-    if (launch) {
-        rc = resident_launch(c);
-        if (rc != CHIP_OK) return rc;
-    }
-    c->res_busy = true;
-    c->res_slot = &s;
-    c->res_ticks++;
-    s.poll = true;
-    s.resident = true;
-    s.wait_ev = nullptr;
-    return CHIP_OK;
-}
-
-// Wait for the command's completion word.  An instance that left before it saw the command (its lease ran out just then) is replaced:
-// the new one finds the line and runs it.
-static int resident_collect(Ctx *c, Slot &s)
-{
-    const volatile unsigned long long *w = s.seq_host;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned long spin = 1;; spin++) {
-        if (__atomic_load_n(w, __ATOMIC_ACQUIRE) == s.seq_want) break;
-        if ((spin & 0x3ff) == 0) {
-            std::lock_guard<std::mutex> lk(c->res_mu);
-            if (__atomic_load_n(w, __ATOMIC_ACQUIRE) == s.seq_want) break;
-            if (!c->res_alive || resident_has_left(c)) {   // left by its lease, or retired by another thread (resident_stop) before it saw the line
-                c->res_alive = false;
-                if (c->res_direct) {
-                    // some workgroups may have found the command in their lines while workgroup 0 was already leaving: send everybody
-                    // home, wait until the instance is gone, then post the command again for a new one
-                    ResidentCmd bye{};
-                    bye.head = bye.tail = kResidentLeave;
-                    bye.n_rows = -1;
-                    resident_write_line(c, bye);
-                    (void)hipStreamSynchronize(c->s_resident);
-                    if (__atomic_load_n(w, __ATOMIC_ACQUIRE) == s.seq_want) break;   // (it had run after all)
-                }
-                // (one line for all: it may hold the leave command of a resident_stop that gave up waiting for this one)
-                resident_write_line(c, c->res_pending);
-                const int rc = resident_launch(c);
-                if (rc != CHIP_OK) { c->res_busy = false; c->res_slot = nullptr; s.resident = false; return rc; }
-            }
-            if ((spin & 0xfffff) == 0 && std::chrono::duration_cast<std::chrono::seconds>(std::chrono::steady_clock::now() - t0).count() > 30) {
-                c->last_hip = hipErrorLaunchTimeOut;
-                c->res_busy = false;          // whatever state the instance is in, its lease ends it; later ticks may try again
-                c->res_slot = nullptr;
-                s.resident = false;
-                return CHIP_ERR_HIP;
-            }
-        }
-    }
-    std::lock_guard<std::mutex> lk(c->res_mu);
-    c->res_busy = false;
-    c->res_slot = nullptr;
-    c->res_done = c->res_cmd_no;
-    s.resident = false;
-    return CHIP_OK;
-}
-
 static int ensure_capacity(Ctx *c, int64_t local_rows)
 {
     // caller holds append_mu
@@ -443,7 +101,7 @@ static int ensure_capacity(Ctx *c, int64_t local_rows)
     bool grew = false;
     // the segment table is about to change: no instance from here until the table is final (an instance reads the table through
     // caches nothing invalidates while it lives; rows of the new segment are published only after this function returns)
-    ResidentPause paused(c, c->tick_resident && (int64_t)c->segs.size() < need);
+    ResidentPause paused(c, (int64_t)c->segs.size() < need);
     while ((int64_t)c->segs.size() < need) {
         void *p = nullptr;
         CHIP_HIP(c, hipMalloc(&p, (size_t)c->seg_rows * c->D * c->elem));
@@ -464,7 +122,7 @@ static int ensure_capacity(Ctx *c, int64_t local_rows)
 // switch to double rows on the first append), with the append lock held or before the ctx is published.
 static int configure_storage(Ctx *c, int elem)
 {
-    ResidentPause paused(c, c->tick_resident);
+    ResidentPause paused(c);
     for (void *p : c->segs) (void)hipFree(p);
     {
         std::lock_guard<std::mutex> lk(c->mu);
@@ -497,7 +155,7 @@ void ctx_destroy(chip_ctx *c)
     { std::lock_guard<std::mutex> qlk(c->query_mu); (void)coalesce_flush(c); }   // parked ticks run like every other enqueued tick
     resident_stop(c);
     (void)hipDeviceSynchronize();
-    resident_free(c);
+    resident_destroy(c);
     exchange_destroy(c);
     pnp_destroy(c);
     icp_destroy(c);
@@ -609,14 +267,7 @@ static int create_impl(chip_ctx *c, int64_t capacity_hint, int elem)
     if (c->coalesce_max < 2) c->coalesce_max = 0;
     if (c->coalesce_max > kMultiMaxTicks) c->coalesce_max = kMultiMaxTicks;
     c->tick_poll = env_int("CHIP_TICK_POLL", 1) != 0;
-    // opt-in: synchronous ticks over cache-sized prefixes go to a scan instance that stays on the chip (chip_internal.h ResidentCmd)
-    c->tick_resident = env_int("CHIP_TICK_RESIDENT", 0) != 0 && (scan_forms_built() & CHIP_SCAN_FORM_ROWS) != 0;
-    c->res_max_bytes = (double)env_int("CHIP_RESIDENT_MAX_MIB", 512) * 1024 * 1024;   // 32k rows of 4096 floats: the reference's capacity is 29k
-    c->res_lease_ms = env_int("CHIP_RESIDENT_LEASE_MS", 250);
-#ifdef CHIP_TEST_HOOKS
-    c->res_test_skip_master = env_int("CHIP_TEST_RESIDENT_SKIP_MASTER", 0);
-#endif
-    if (c->res_lease_ms < 1) c->res_lease_ms = 1;
+    resident_read_knobs(c);
     CHIP_HIP(c, hipHostMalloc(&c->seq_host_all, sizeof(unsigned long long) * CHIP_MAX_INFLIGHT, hipHostMallocDefault));
     std::memset(c->seq_host_all, 0, sizeof(unsigned long long) * CHIP_MAX_INFLIGHT);
     CHIP_HIP(c, hipHostMalloc(&c->topk_host, (size_t)CHIP_MAX_NQ * CHIP_MAX_TOPK * sizeof(chip_topk_entry), hipHostMallocDefault));
@@ -693,13 +344,46 @@ bool scan_tick_fused(const Ctx *c, bool same_stream, const ScanArgs &a, bool dec
     return same_stream && a.rows_form > 0 && c->tick_fused && decision_only && nq == 3;
 }
 
+bool tick_merge_on_scan_stream(const Ctx *c, bool tick, bool short_scan, bool second_tick_stream, bool caller_accepts)
+{
+    return tick && short_scan && !c->prof_on && c->nranks == 1 && !c->xchg && !c->parent && c->own_query_stream && second_tick_stream &&
+           caller_accepts && c->tick_same_stream;
+}
+
+MergeArgs merge_args(const chip_topk_entry *in, int32_t n_lists, int32_t K, chip_topk_entry *out, chip_tick_result *result, int64_t l, const chip_dot_params *p)
+{
+    MergeArgs m;
+    m.in = in;
+    m.n_lists = n_lists;
+    m.K = K;
+    m.out = out;
+    m.result = result;
+    m.l = l;
+    m.locality = p ? p->locality : 0;
+    m.thresh = p ? p->thresh : 0.0;
+    return m;
+}
+
+int prof_begin(Ctx *c, hipStream_t s, double bytes, hipEvent_t *stop)
+{
+    while (c->prof_used + 2 > c->prof_ev.size()) {
+        hipEvent_t e;
+        CHIP_HIP(c, hipEventCreate(&e));
+        c->prof_ev.push_back(e);
+    }
+    hipEvent_t start = c->prof_ev[c->prof_used];
+    *stop = c->prof_ev[c->prof_used + 1];
+    c->prof_used += 2;
+    c->prof_bytes_last = bytes;
+    CHIP_HIP(c, hipEventRecord(start, s));
+    return CHIP_OK;
+}
+
 // Enqueue K1 (scan + per-workgroup top-k, on s_scan) and K2 (cross-workgroup merge [+ accept decision], on the ctx
-// stream behind an event) for nq queries over the global prefix [0,k).  out (device or pinned host, optional) gets
-// [nq][K]; res (optional) the decision record of Cerebro.cpp:1056.  Consecutive calls pipeline: scans run back to
+// stream behind an event) for rq.nq queries over the global prefix [0,rq.k).  rq.out (device or pinned host, optional) gets
+// [nq][K]; rq.res (optional) the decision record of Cerebro.cpp:1056.  Consecutive calls pipeline: scans run back to
 // back on s_scan while the previous merge (and whatever the caller enqueues after it on the ctx stream) proceeds.
-int enqueue_scan_merge(Ctx *c, int64_t k, const void *const *q, int nq, int K, int64_t l,
-                       const chip_dot_params *p, chip_topk_entry *out, chip_tick_result *res, bool tick, hipStream_t *merge_stream,
-                       hipEvent_t *merged_ev)
+int enqueue_scan_merge(Ctx *c, const ScanRequest &rq, ScanReceipt *rcpt)
 {
     const int b = (int)(c->n_enqueued++ % Ctx::kRing);
     // Ticks (queries already resident) over a short prefix alternate between two scan streams so that the ramp-down of
@@ -709,61 +393,43 @@ int enqueue_scan_merge(Ctx *c, int64_t k, const void *const *q, int nq, int K, i
     // uploads its queries on s_scan first stays on s_scan.
     ScanArgs a;
     int grid = 0;
-    const bool short_scan = scan_policy(c, local_count(c, k), nq, tick && c->tick_sync_now, &a, &grid);
-    hipStream_t s_scan = (tick && short_scan && !c->prof_on && c->s_scan2 && (c->n_enqueued & 1)) ? c->s_scan2 : c->s_scan;
+    const int nq = rq.nq;
+    const bool short_scan = scan_policy(c, local_count(c, rq.k), nq, rq.tick && rq.sync_tick, &a, &grid);
+    hipStream_t s_scan = (rq.tick && short_scan && !c->prof_on && c->s_scan2 && (c->n_enqueued & 1)) ? c->s_scan2 : c->s_scan;
     // (same-stream short ticks rotate over all tick streams: see below)
-    const bool same_stream = tick && short_scan && !c->prof_on && c->nranks == 1 && !c->xchg && !c->parent && c->own_query_stream &&
-                             c->s_scan2 && merge_stream && c->tick_same_stream;
+    const bool same_stream = tick_merge_on_scan_stream(c, rq.tick, short_scan, c->s_scan2 != nullptr, rq.merge_on_scan_stream);
     if (same_stream) {
         hipStream_t ring[4] = {c->s_scan, c->s_scan2, c->s_scan_x[0], c->s_scan_x[1]};
         int ns = 2;
         while (ns < 4 && ring[ns]) ns++;
         s_scan = ring[c->n_same_stream++ % (uint64_t)ns];
     }
-    a.seg_table = c->seg_table_dev;
-    a.seg_shift = c->seg_shift;
-    a.seg_mask = c->seg_rows - 1;
-    a.n_rows = local_count(c, k);
-    a.D = c->D;
-    a.K = K;
-    for (int i = 0; i < CHIP_MAX_NQ; i++) a.q[i] = i < nq ? q[i] : nullptr;
+    scan_args_db(c, &a);
+    a.n_rows = local_count(c, rq.k);
+    a.K = rq.K;
+    for (int i = 0; i < CHIP_MAX_NQ; i++) a.q[i] = i < nq ? rq.q[i] : nullptr;
     a.idx_mul = c->nranks;
     a.idx_add = c->nranks == 1 ? 0 : c->rank;
     a.partial = c->partial_dev[b];
     a.stamps = c->stamps_dev;
-    const bool fused = scan_tick_fused(c, same_stream, a, res != nullptr && out == nullptr && p != nullptr, nq);
+    const bool fused = scan_tick_fused(c, same_stream, a, rq.res != nullptr && rq.out == nullptr && rq.p != nullptr, nq);
     if (fused) {
         a.K = 1;
-        a.fused_result = res;
+        a.fused_result = rq.res;
         a.fused_ticket = c->tickets_dev + b;
-        a.tick_l = l;
-        a.locality = p->locality;
-        a.thresh = p->thresh;
-        a.fused_seq = c->next_seq_dev;       // (nullptr unless tick_enqueue_slot asked for a pollable completion)
-        a.fused_seq_val = c->next_seq_val;
+        a.tick_l = rq.l;
+        a.locality = rq.p->locality;
+        a.thresh = rq.p->thresh;
+        a.fused_seq = rq.seq_dev;            // (nullptr unless the caller asked for a pollable completion)
+        a.fused_seq_val = rq.seq_val;
     }
-    c->last_enqueue_fused = fused;
-    c->next_seq_dev = nullptr;
 
     // The merge that last read this buffer ran kRing ticks ago; only when it is not already complete (a stalled ctx
     // stream) does the scan stream need a barrier packet -- in steady state this costs nothing.
     if (hipEventQuery(c->ev_merged[b]) != hipSuccess) CHIP_HIP(c, hipStreamWaitEvent(s_scan, c->ev_merged[b], 0));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->prof_on) {
-        if (c->prof_used + 2 > c->prof_ev.size()) {
-            for (int i = 0; i < 2; i++) {
-                hipEvent_t e;
-                CHIP_HIP(c, hipEventCreate(&e));
-                c->prof_ev.push_back(e);
-            }
-        }
-        e0 = c->prof_ev[c->prof_used];
-        e1 = c->prof_ev[c->prof_used + 1];
-        c->prof_used += 2;
-        c->prof_bytes_last = (double)a.n_rows * c->D * c->elem;
-        CHIP_HIP(c, hipEventRecord(e0, s_scan));
-    }
-    int rc = launch_scan(c, s_scan, a, nq, grid);
+    hipEvent_t e1 = nullptr;
+    int rc = c->prof_on ? prof_begin(c, s_scan, (double)a.n_rows * c->D * c->elem, &e1) : CHIP_OK;
+    if (rc == CHIP_OK) rc = launch_scan(c, s_scan, a, nq, grid);
     if (rc != CHIP_OK) return rc;
     if (e1) CHIP_HIP(c, hipEventRecord(e1, s_scan));
     // Short ticks of a plain single-GPU ctx keep the merge on the scan's OWN stream: the tick is then two launches and two event
@@ -771,32 +437,21 @@ int enqueue_scan_merge(Ctx *c, int64_t k, const void *const *q, int nq, int K, i
     // merge(i) still overlaps scan(i+1).  At 10k rows the tick is host-enqueue-bound otherwise (round 2: 21-34 us of API calls per
     // tick against a ~20 us kernel).  Anything with an exchange, an external ctx stream or profiling keeps the ctx-stream merge.
     hipStream_t s_merge = same_stream ? s_scan : c->s_query;
-    if (merge_stream) *merge_stream = s_merge;
+    if (rcpt) { rcpt->merge_stream = s_merge; rcpt->fused = fused; rcpt->done_ev = same_stream ? c->ev_merged[b] : nullptr; }   // same-stream tick: the merge event (recorded below) IS the tick's completion event
     if (!same_stream) {
         CHIP_HIP(c, hipEventRecord(c->ev_scan[b], s_scan));
-        if (tick && !short_scan) { c->pass_ev = c->ev_scan[b]; c->pass_no++; }   // the scan later ticks may park behind (coalesce_*)
+        if (rq.tick && !short_scan) { c->pass_ev = c->ev_scan[b]; c->pass_no++; }   // the scan later ticks may park behind (coalesce_*)
         if (c->ring_dev) c->last_scan_ev[s_scan == c->s_scan2 ? 1 : 0] = c->ev_scan[b];   // caller holds ring_mu (RingGuard)
         CHIP_HIP(c, hipStreamWaitEvent(c->s_query, c->ev_scan[b], 0));
     }
 
     if (fused) {   // the scan's last workgroup has written the decision record: the scan's end IS the tick's end
         CHIP_HIP(c, hipEventRecord(c->ev_merged[b], s_scan));
-        if (merged_ev) *merged_ev = c->ev_merged[b];
         return CHIP_OK;
     }
-    MergeArgs m;
-    m.in = c->partial_dev[b];
-    m.n_lists = grid;
-    m.K = K;
-    m.out = out;
-    m.result = res;
-    m.l = l;
-    m.locality = p ? p->locality : 0;
-    m.thresh = p ? p->thresh : 0.0;
-    rc = launch_merge(c, s_merge, m, nq);
+    rc = launch_merge(c, s_merge, merge_args(c->partial_dev[b], grid, rq.K, rq.out, rq.res, rq.l, rq.p), nq);
     if (rc != CHIP_OK) return rc;
     CHIP_HIP(c, hipEventRecord(c->ev_merged[b], s_merge));
-    if (merged_ev) *merged_ev = same_stream ? c->ev_merged[b] : nullptr;   // same-stream tick: this IS the tick's completion event
     return CHIP_OK;
 }
 
@@ -860,7 +515,7 @@ int upload_query_vectors(Ctx *c, const void *queries, int src_elem, int nq, cons
 // Host part of the tick (Cerebro.cpp:960-966, :1019-1022).  Returns CHIP_TICK_* in *status.  last_l is NOT written here:
 // the caller commits it once the tick has actually been enqueued (or at once for TOO_SHORT), so a failed enqueue leaves the
 // state as the reference's loop would (it only reaches :1098 at the end of an executed pass).
-int tick_prepare(int64_t n, int64_t last_l, int64_t l, const chip_dot_params *p, int32_t *status, int64_t *k_out)
+static int tick_prepare(int64_t n, int64_t last_l, int64_t l, const chip_dot_params *p, int32_t *status, int64_t *k_out)
 {
     if (l < 0 || l > n) return CHIP_ERR_RANGE;
     if (l - last_l < p->min_new) { *status = CHIP_TICK_SKIPPED; return CHIP_OK; }  // :962-966, last_l untouched
@@ -871,7 +526,7 @@ int tick_prepare(int64_t n, int64_t last_l, int64_t l, const chip_dot_params *p,
     return CHIP_OK;
 }
 
-void fill_immediate(chip_tick_result *r, int32_t status)
+static void fill_immediate(chip_tick_result *r, int32_t status)
 {
     std::memset(r, 0, sizeof *r);
     r->status = status;
@@ -885,22 +540,39 @@ int64_t published_rows(const Ctx *c)
     return c->rows_global;
 }
 
-// One tick as a pass of its own: scan (K1) + merge and decision (K2), the slot's completion event.  query_mu held.
-static int tick_submit(Ctx *c, int64_t k, int64_t l, const chip_dot_params *p, const void *const *q, Slot &s)
+int tick_begin(Slot &s, int64_t n_rows, int64_t *last_l, int64_t l, const chip_dot_params *p, int32_t *status, int64_t *k)
 {
-    hipStream_t s_done = c->s_query;
-    hipEvent_t merged = nullptr;
-    s.poll = false;
-    if (c->tick_poll) { s.seq_want = ++c->tick_seq; c->next_seq_dev = s.seq_dev; c->next_seq_val = s.seq_want; }
-    const int rc = enqueue_scan_merge(c, k, q, 3, CHIP_DEFAULT_TOPK, l, p, nullptr, s.dev, true, &s_done, &merged);
-    c->next_seq_dev = nullptr;
+    if (s.state != SlotState::Free) return CHIP_ERR_BUSY;
+    const int rc = tick_prepare(n_rows, *last_l, l, p, status, k);
     if (rc != CHIP_OK) return rc;
-    s.poll = c->tick_poll && c->last_enqueue_fused;   // the fused kernel stores the completion word itself
+    s.prev_last_l = *last_l;
+    s.tick_l = l;
+    s.last_l_ptr = last_l;
+    if (*status != CHIP_TICK_SCANNED) {
+        if (*status == CHIP_TICK_TOO_SHORT) *last_l = l;   // :1098 (the else-branch of :1022 still ends the pass)
+        fill_immediate(s.host, *status);
+        s.state = SlotState::Immediate;
+    }
+    return CHIP_OK;
+}
+
+// One tick as a pass of its own: scan (K1) + merge and decision (K2), the slot's completion event.  query_mu held.
+static int tick_submit(Ctx *c, int64_t k, int64_t l, const chip_dot_params *p, const void *const *q, bool sync_tick, Slot &s)
+{
+    ScanRequest rq;
+    rq.k = k; rq.q = q; rq.nq = 3; rq.K = CHIP_DEFAULT_TOPK;
+    rq.res = s.dev; rq.l = l; rq.p = p;
+    rq.tick = true; rq.sync_tick = sync_tick; rq.merge_on_scan_stream = true;
+    if (c->tick_poll) { s.seq_want = ++c->tick_seq; rq.seq_dev = s.seq_dev; rq.seq_val = s.seq_want; }
+    ScanReceipt done;
+    const int rc = enqueue_scan_merge(c, rq, &done);
+    if (rc != CHIP_OK) return rc;
     // a same-stream tick is complete when its merge is: one event record per tick (the list buffer's merge event; the buffer is
     // not reused before kRing = 64 further enqueues, and at most CHIP_MAX_INFLIGHT - 1 = 63 ticks are uncollected)
-    if (merged) s.wait_ev = merged;
-    else { CHIP_HIP(c, hipEventRecord(s.done, s_done)); s.wait_ev = s.done; }
+    if (done.done_ev) s.wait_ev = done.done_ev;
+    else { CHIP_HIP(c, hipEventRecord(s.done, done.merge_stream)); s.wait_ev = s.done; }
     s.pass_no = c->pass_no;
+    s.state = c->tick_poll && done.fused ? SlotState::Poll : SlotState::Event;   // the fused kernel stores the completion word itself
     return CHIP_OK;
 }
 
@@ -922,9 +594,9 @@ int coalesce_decide(int n_parked, int t_max, bool scan_running)
 }
 
 // most ticks a pass over [0, k) may serve on this ctx; 0: the tick does not coalesce
-static int coalesce_ticks_max(const Ctx *c, int64_t k)
+static int coalesce_ticks_max(const Ctx *c, int64_t k, bool sync_tick)
 {
-    if (c->coalesce_max < 2 || c->tick_sync_now || c->nranks != 1 || c->xchg || c->parent || c->group || !c->own_query_stream) return 0;
+    if (c->coalesce_max < 2 || sync_tick || c->nranks != 1 || c->xchg || c->parent || c->group || !c->own_query_stream) return 0;
     if ((double)k * c->D * c->elem <= c->scan_overlap_bytes) return 0;
     const int fit = scan_multi_max_ticks(c);
     const int t = fit < c->coalesce_max ? fit : c->coalesce_max;
@@ -938,10 +610,7 @@ static int coalesce_submit(Ctx *c, int T)
     const int b = (int)(c->n_enqueued++ % Ctx::kRing);
     const int K = CHIP_DEFAULT_TOPK;
     MultiScanArgs a{};
-    a.seg_table = c->seg_table_dev;
-    a.seg_shift = c->seg_shift;
-    a.seg_mask = c->seg_rows - 1;
-    a.D = c->D;
+    scan_args_db(c, &a);
     a.K = K;
     a.partial = c->partial_dev[b];
     for (int t = 0; t < T; t++) {
@@ -950,21 +619,10 @@ static int coalesce_submit(Ctx *c, int T)
         for (int i = 0; i < 3; i++) a.q[3 * t + i] = c->parked[t].q[i];
     }
     const int grid = scan_multi_grid(c);
-    c->last_enqueue_fused = false;
     if (hipEventQuery(c->ev_merged[b]) != hipSuccess) CHIP_HIP(c, hipStreamWaitEvent(c->s_scan, c->ev_merged[b], 0));
-    hipEvent_t e1 = nullptr;
-    if (c->prof_on) {   // one event pair per pass; a pass reads the prefix once
-        while (c->prof_used + 2 > c->prof_ev.size()) {
-            hipEvent_t e;
-            CHIP_HIP(c, hipEventCreate(&e));
-            c->prof_ev.push_back(e);
-        }
-        e1 = c->prof_ev[c->prof_used + 1];
-        CHIP_HIP(c, hipEventRecord(c->prof_ev[c->prof_used], c->s_scan));
-        c->prof_used += 2;
-        c->prof_bytes_last = (double)a.n_rows * c->D * c->elem;
-    }
-    int rc = launch_scan_multi(c, c->s_scan, a, T, grid);
+    hipEvent_t e1 = nullptr;   // one event pair per pass; a pass reads the prefix once
+    int rc = c->prof_on ? prof_begin(c, c->s_scan, (double)a.n_rows * c->D * c->elem, &e1) : CHIP_OK;
+    if (rc == CHIP_OK) rc = launch_scan_multi(c, c->s_scan, a, T, grid);
     if (rc != CHIP_OK) return rc;
     if (e1) CHIP_HIP(c, hipEventRecord(e1, c->s_scan));
     CHIP_HIP(c, hipEventRecord(c->ev_scan[b], c->s_scan));
@@ -973,20 +631,11 @@ static int coalesce_submit(Ctx *c, int T)
     CHIP_HIP(c, hipStreamWaitEvent(c->s_query, c->ev_scan[b], 0));
     for (int t = 0; t < T; t++) {
         const Ctx::ParkedTick &pt = c->parked[t];
-        MergeArgs m;
-        m.in = c->partial_dev[b] + (size_t)t * grid * 3 * K;
-        m.n_lists = grid;
-        m.K = K;
-        m.out = nullptr;
-        m.result = pt.slot->dev;
-        m.l = pt.l;
-        m.locality = pt.p.locality;
-        m.thresh = pt.p.thresh;
-        rc = launch_merge(c, c->s_query, m, 3);
+        rc = launch_merge(c, c->s_query, merge_args(c->partial_dev[b] + (size_t)t * grid * 3 * K, grid, K, nullptr, pt.slot->dev, pt.l, &pt.p), 3);
         if (rc != CHIP_OK) return rc;
         CHIP_HIP(c, hipEventRecord(pt.slot->done, c->s_query));
         pt.slot->wait_ev = pt.slot->done;
-        pt.slot->poll = false;
+        pt.slot->state = SlotState::Event;
         pt.slot->pass_no = c->pass_no;
     }
     CHIP_HIP(c, hipEventRecord(c->ev_merged[b], c->s_query));
@@ -1001,37 +650,25 @@ int coalesce_flush(Ctx *c)
     if (T == 0) return CHIP_OK;
     c->n_parked = 0;
     const Ctx::ParkedTick &p0 = c->parked[0];
-    const int rc = T == 1 ? tick_submit(c, p0.k, p0.l, &p0.p, p0.q, *p0.slot) : coalesce_submit(c, T);
-    for (int t = 0; t < T; t++) {
-        c->parked[t].slot->parked = false;
-        if (rc != CHIP_OK) c->parked[t].slot->err = rc;   // the enqueue has long returned: the tick's collect reports it
+    const int rc = T == 1 ? tick_submit(c, p0.k, p0.l, &p0.p, p0.q, false, *p0.slot) : coalesce_submit(c, T);
+    for (int t = 0; t < T && rc != CHIP_OK; t++) {   // the enqueue has long returned: the tick's collect reports it
+        c->parked[t].slot->state = SlotState::Failed;
+        c->parked[t].slot->err = rc;
     }
     return rc;
 }
 
-static int tick_enqueue_slot(Ctx *c, int64_t l, const chip_dot_params *p, Slot &s)
+static int tick_enqueue_slot(Ctx *c, int64_t l, const chip_dot_params *p, bool sync_tick, Slot &s)
 {
-    if (s.in_flight) return CHIP_ERR_BUSY;
     int32_t status = 0;
     int64_t k = 0;
     // With an exchange attached the ranks may see different published lengths (each has its own appender): l > n on THIS rank is
     // then not a reason to leave the collective call -- the rank takes part with the failure mark (xchg_tick_enqueue).
     const int64_t n_pub = published_rows(c);
-    int rc = tick_prepare(c->xchg ? INT64_MAX : n_pub, c->last_l, l, p, &status, &k);
-    if (rc != CHIP_OK) return rc;
-    s.poll = false;
-    s.prev_last_l = c->last_l;
-    s.tick_l = l;
-    s.last_l_ptr = &c->last_l;
-    if (status != CHIP_TICK_SCANNED) {
-        if (status == CHIP_TICK_TOO_SHORT) c->last_l = l;   // :1098 (the else-branch of :1022 still ends the pass)
-        fill_immediate(s.host, status);
-        s.immediate = true;
-        s.in_flight = true;
-        return CHIP_OK;
-    }
+    int rc = tick_begin(s, c->xchg ? INT64_MAX : n_pub, &c->last_l, l, p, &status, &k);
+    if (rc != CHIP_OK || status != CHIP_TICK_SCANNED) return rc;
     if (c->xchg) {   // sharded ctx with its exchange inside the library: scan -> local merge -> all-gather -> merge + decision
-        rc = xchg_tick_enqueue(c, l, k, p, s, l > n_pub);
+        rc = xchg_tick_enqueue(c, l, k, p, sync_tick, s, l > n_pub);
         if (rc != CHIP_OK) return rc;
     } else {
         const int64_t rows[3] = {l - 1, l - 2, l - 3};  // v, vm, vmm (:987-989)
@@ -1042,34 +679,23 @@ static int tick_enqueue_slot(Ctx *c, int64_t l, const chip_dot_params *p, Slot &
         if (resident_eligible(c, k)) {
             (void)coalesce_flush(c);
             rc = resident_tick_enqueue(c, k, l, p, s);
-            if (rc == CHIP_OK) {
-                s.immediate = false;
-                s.in_flight = true;
-                c->last_l = l;             // :1098
-                return CHIP_OK;
-            }
-            if (rc != CHIP_ERR_UNSUPPORTED && rc != kResidentPaused) return rc;
-            if (rc == CHIP_ERR_UNSUPPORTED) c->tick_resident = false;      // this ctx's shape has no resident form: every tick is launched from here on
-            s.resident = false;
-            s.poll = false;
+            if (rc == CHIP_OK) { c->last_l = l; return CHIP_OK; }   // :1098
+            if (rc != CHIP_ERR_UNSUPPORTED && rc != kResidentPaused) return rc;   // (no resident form on this ctx, or paused: launch the tick)
         }
-        const int t_max = coalesce_ticks_max(c, k);
+        const int t_max = coalesce_ticks_max(c, k, sync_tick);
         const int act = t_max < 2 ? kCoalesceLaunch
                                   : coalesce_decide(c->n_parked, t_max, c->coalesce_force || (c->pass_ev && hipEventQuery(c->pass_ev) == hipErrorNotReady));
         if (act == kCoalesceLaunch) {
             (void)coalesce_flush(c);   // submission order stays call order (a failure is reported by the collects of the ticks it concerns)
-            rc = tick_submit(c, k, l, p, q, s);
+            rc = tick_submit(c, k, l, p, q, sync_tick, s);
             if (rc != CHIP_OK) return rc;
         } else {
             Ctx::ParkedTick &pt = c->parked[c->n_parked++];
             pt.slot = &s; pt.k = k; pt.l = l; pt.p = *p;
             for (int i = 0; i < 3; i++) pt.q[i] = q[i];
-            s.parked = true;
-            s.err = 0;
+            s.state = SlotState::Parked;
             if (act == kCoalesceParkFlush) (void)coalesce_flush(c);
         }
-        s.immediate = false;
-        s.in_flight = true;
     }
     c->last_l = l;                     // :1098
     return CHIP_OK;
@@ -1077,41 +703,47 @@ static int tick_enqueue_slot(Ctx *c, int64_t l, const chip_dot_params *p, Slot &
 
 int tick_collect_slot(Ctx *c, Slot &s, chip_tick_result *out)
 {
-    if (!s.in_flight) return CHIP_ERR_BUSY;
     // A parked tick leaves now (with whatever is parked next to it).  A collect that is about to block on the NEWEST pass submitted
     // sends the parked ticks off first: nothing is queued behind that pass, and the GPU would run dry until the caller returns.
-    if (s.parked) (void)coalesce_flush(c);
-    else if (c->n_parked > 0 && !s.immediate && !s.resident && s.pass_no == c->pass_no && hipEventQuery(s.wait_ev ? s.wait_ev : s.done) == hipErrorNotReady)
+    if (s.state == SlotState::Parked) (void)coalesce_flush(c);
+    else if (c->n_parked > 0 && (s.state == SlotState::Event || s.state == SlotState::Poll) && s.pass_no == c->pass_no &&
+             hipEventQuery(s.wait_ev) == hipErrorNotReady)
         (void)coalesce_flush(c);
-    if (s.err != 0) {   // the pass this tick was part of could not be submitted: as a tick whose enqueue had failed
-        const int rc = s.err;
-        s.err = 0;
-        s.in_flight = false;
+    switch (s.state) {
+    case SlotState::Free:
+    case SlotState::Parked:      // (coalesce_flush leaves no slot parked)
+        return CHIP_ERR_BUSY;
+    case SlotState::Failed:      // the pass this tick was part of could not be submitted: as a tick whose enqueue had failed
+        s.state = SlotState::Free;
         if (s.last_l_ptr && *s.last_l_ptr == s.tick_l) *s.last_l_ptr = s.prev_last_l;
-        return rc;
+        return s.err;
+    case SlotState::Immediate:
+        break;
+    case SlotState::Resident: {
+        const int rc = resident_collect(c, s);
+        if (rc != CHIP_OK) { s.state = SlotState::Free; return rc; }
+        break;
     }
-    if (!s.immediate) {
+    case SlotState::Poll: {
         // A fused tick's last workgroup writes the record into the slot's pinned host memory and THEN stores the slot's completion word
         // with a system-scope release: polling that word (acquire) hands the record over ~4-5 us before the stream's event would -- the
         // end-of-kernel cache maintenance, the event's barrier packet and its signal are off the synchronous tick's critical path.  The
         // event is still recorded (it orders the reuse of the list buffer); it is only waited for if the word does not arrive.
         bool done = false;
-        if (s.resident) {
-            const int rc = resident_collect(c, s);
-            if (rc != CHIP_OK) { s.in_flight = false; s.poll = false; return rc; }
-            done = true;
-        } else if (s.poll) {
-            const volatile unsigned long long *w = s.seq_host;
-            for (long spin = 0; spin < (1L << 24) && !done; spin++) {
-                done = __atomic_load_n(w, __ATOMIC_ACQUIRE) == s.seq_want;
-                if (!done && (spin & 0x3fff) == 0x3fff && hipEventQuery(s.wait_ev ? s.wait_ev : s.done) != hipErrorNotReady) break;   // finished or failed: let the event say which
-            }
+        const volatile unsigned long long *w = s.seq_host;
+        for (long spin = 0; spin < (1L << 24) && !done; spin++) {
+            done = __atomic_load_n(w, __ATOMIC_ACQUIRE) == s.seq_want;
+            if (!done && (spin & 0x3fff) == 0x3fff && hipEventQuery(s.wait_ev) != hipErrorNotReady) break;   // finished or failed: let the event say which
         }
-        if (!done) CHIP_HIP(c, hipEventSynchronize(s.wait_ev ? s.wait_ev : s.done));
-        s.poll = false;
+        if (done) break;
+    }
+        [[fallthrough]];   // the word did not arrive
+    case SlotState::Event:
+        CHIP_HIP(c, hipEventSynchronize(s.wait_ev));   // (a failure leaves the slot as it is)
+        break;
     }
     *out = *s.host;
-    s.in_flight = false;
+    s.state = SlotState::Free;
     if (out->status == CHIP_TICK_FAILED) {   // a shard could not take part: the tick had no effect (:1098 was not reached)
         // Roll last_l back only while this tick is still the newest one enqueued.  With ticks pipelined, a later tick may have been
         // enqueued (and may succeed) meanwhile: its commit of last_l stands, exactly as if the reference's sequential loop had
@@ -1122,7 +754,7 @@ int tick_collect_slot(Ctx *c, Slot &s, chip_tick_result *out)
             // that never reached :1098): hand it this tick's predecessor instead, so that a run of failed ticks unwinds to the last_l
             // of the newest tick that did not fail.  The successor is the in-flight slot whose prev_last_l is this l.
             for (Slot &o : c->slots)
-                if (&o != &s && o.in_flight && o.last_l_ptr == s.last_l_ptr && o.prev_last_l == s.tick_l) o.prev_last_l = s.prev_last_l;
+                if (&o != &s && o.state != SlotState::Free && o.last_l_ptr == s.last_l_ptr && o.prev_last_l == s.tick_l) o.prev_last_l = s.prev_last_l;
         }
         fill_immediate(out, CHIP_TICK_FAILED);
         return CHIP_ERR_SHARD_FAILED;
@@ -1356,38 +988,20 @@ static int read_rows(chip_ctx *c, const int64_t *rows, int64_t n, void *out, int
 
 int merge_enqueue_slot(Ctx *c, int64_t l, const chip_dot_params *p, const void *dev_gathered, int32_t n_lists, int32_t topk, Slot &s)
 {
-    if (s.in_flight) return CHIP_ERR_BUSY;
-    MergeArgs m;
-    m.in = (const chip_topk_entry *)dev_gathered;
-    m.n_lists = n_lists;
-    m.K = topk;
-    m.out = nullptr;
-    m.result = s.dev;   // pinned + mapped: no D2H copy
-    m.l = l;
-    m.locality = p->locality;
-    m.thresh = p->thresh;
-    int rc = launch_merge(c, c->s_query, m, 3);
+    if (s.state != SlotState::Free) return CHIP_ERR_BUSY;
+    // (the record goes to s.dev, pinned + mapped: no D2H copy)
+    int rc = launch_merge(c, c->s_query, merge_args((const chip_topk_entry *)dev_gathered, n_lists, topk, nullptr, s.dev, l, p), 3);
     if (rc != CHIP_OK) return rc;
     CHIP_HIP(c, hipEventRecord(s.done, c->s_query));
     s.wait_ev = s.done;
-    s.immediate = false;
-    s.in_flight = true;
+    s.state = SlotState::Event;
     return CHIP_OK;
 }
 
 // merge of gathered [n_lists][nq][K] lists into out[nq][K] on the ctx stream, no decision
 int merge_enqueue_out(Ctx *c, const void *dev_gathered, int32_t n_lists, int nq, int32_t topk, chip_topk_entry *out)
 {
-    MergeArgs m;
-    m.in = (const chip_topk_entry *)dev_gathered;
-    m.n_lists = n_lists;
-    m.K = topk;
-    m.out = out;
-    m.result = nullptr;
-    m.l = 0;
-    m.locality = 0;
-    m.thresh = 0.0;
-    return launch_merge(c, c->s_query, m, nq);
+    return launch_merge(c, c->s_query, merge_args((const chip_topk_entry *)dev_gathered, n_lists, topk, out, nullptr, 0, nullptr), nq);
 }
 
 // All scores of one query over this ctx's share of the prefix [0,k): u_global[local * mul + add] = score (host buffer).
@@ -1402,11 +1016,8 @@ int ctx_scores_local(Ctx *c, int64_t k, const void *q, double *u_global, int64_t
         c->scores_cap = cap;
     }
     ScanArgs a;
-    a.seg_table = c->seg_table_dev;
-    a.seg_shift = c->seg_shift;
-    a.seg_mask = c->seg_rows - 1;
+    scan_args_db(c, &a);
     a.n_rows = n_rows;
-    a.D = c->D;
     a.K = 1;
     for (int i = 0; i < CHIP_MAX_NQ; i++) a.q[i] = i == 0 ? q : nullptr;
     a.idx_mul = mul;
@@ -1486,33 +1097,7 @@ int chip_synchronize(chip_ctx *c)
         if (x) CHIP_HIP(c, hipStreamSynchronize(x));
     CHIP_HIP(c, hipStreamSynchronize(c->s_query));
     CHIP_HIP(c, hipStreamSynchronize(c->s_pnp));
-    {   // a tick that went to the resident scan instance is on no stream: it is complete when its slot's completion word says so
-        std::lock_guard<std::mutex> lk(c->res_mu);
-        if (c->res_busy && c->res_slot) {
-            const volatile unsigned long long *w = c->res_slot->seq_host;
-            for (long spin = 0; spin < (1L << 28) && __atomic_load_n(w, __ATOMIC_ACQUIRE) != c->res_slot->seq_want && c->res_alive && !resident_has_left(c); spin++) {}
-        }
-    }
-    return CHIP_OK;
-}
-
-// Public form of the pause the library takes around its own frees / allocations (include/cerebro_hip.h): an integrator brackets
-// device-wide operations of OTHER libraries in the same process with it.  No-ops (CHIP_OK) on ctxs without the resident mode.
-int chip_resident_pause(chip_ctx *c)
-{
-    if (!c) return CHIP_ERR_INVALID_ARG;
-    if (c->group) return CHIP_OK;                 // group / sharded ctxs never run the resident instance
-    (void)hipSetDevice(c->device);
-    { std::lock_guard<std::mutex> qlk(c->query_mu); (void)coalesce_flush(c); }
-    resident_pause(c);
-    return CHIP_OK;
-}
-
-int chip_resident_resume(chip_ctx *c)
-{
-    if (!c) return CHIP_ERR_INVALID_ARG;
-    if (c->group) return CHIP_OK;
-    resident_resume(c);
+    resident_wait_command(c);
     return CHIP_OK;
 }
 
@@ -1588,7 +1173,9 @@ static int query_common(chip_ctx *c, int64_t k, const int64_t *query_rows, const
     }
     rc = query_rows ? query_row_ptrs(c, query_rows, nq, n, q) : upload_query_vectors(c, vectors, vec_elem, nq, q);
     if (rc != CHIP_OK) return rc;
-    rc = enqueue_scan_merge(c, k, q, nq, topk, 0, nullptr, c->topk_dev, nullptr, false, nullptr, nullptr);
+    ScanRequest rq;
+    rq.k = k; rq.q = q; rq.nq = nq; rq.K = topk; rq.out = c->topk_dev;
+    rc = enqueue_scan_merge(c, rq);
     if (rc != CHIP_OK) return rc;
     return sync_topk_out(c, nq, topk, scores, idx);
 }
@@ -1651,9 +1238,7 @@ int chip_loop_tick(chip_ctx *c, int64_t l, const chip_dot_params *p, chip_tick_r
     std::lock_guard<std::mutex> qlk(c->query_mu);
     CHIP_HIP(c, hipSetDevice(c->device));
     Slot &s = c->slots[CHIP_MAX_INFLIGHT - 1];
-    c->tick_sync_now = true;            // (query_mu held) the scan form of this tick is chosen for its latency: kernels.hip scan_rows_form
-    int rc = tick_enqueue_slot(c, l, p, s);
-    c->tick_sync_now = false;
+    int rc = tick_enqueue_slot(c, l, p, true, s);   // synchronous: the scan form of this tick is chosen for its latency (kernels.hip scan_rows_form)
     if (rc != CHIP_OK) return rc;
     return tick_collect_slot(c, s, out);
 }
@@ -1665,7 +1250,7 @@ int chip_loop_tick_enqueue(chip_ctx *c, int64_t l, const chip_dot_params *p, int
     if (c->nranks != 1 && !c->xchg) return CHIP_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> qlk(c->query_mu);
     CHIP_HIP(c, hipSetDevice(c->device));
-    return tick_enqueue_slot(c, l, p, c->slots[slot]);
+    return tick_enqueue_slot(c, l, p, false, c->slots[slot]);
 }
 
 int chip_loop_tick_collect(chip_ctx *c, int32_t slot, chip_tick_result *out)
@@ -1711,7 +1296,10 @@ int chip_scan_local(chip_ctx *c, int64_t l, const chip_dot_params *p, int32_t to
     // scan on s_scan, then (behind an event) the local merge on the ctx stream writes this rank's 3 x topk list to
     // dev_out: everything the caller enqueues next on the ctx stream (the all-gather) is ordered after it, while the
     // next tick's scan is free to start as soon as this scan ends.
-    rc = enqueue_scan_merge(c, k, q, 3, topk, l, nullptr, (chip_topk_entry *)dev_out, nullptr, true, nullptr, nullptr);
+    ScanRequest rq;
+    rq.k = k; rq.q = q; rq.nq = 3; rq.K = topk; rq.out = (chip_topk_entry *)dev_out;
+    rq.l = l; rq.tick = true;
+    rc = enqueue_scan_merge(c, rq);
     if (rc == CHIP_OK) c->last_l = l;  // :1098
     return rc;
 }
@@ -1771,17 +1359,6 @@ int chip_get_info(const chip_ctx *c, chip_info *info)
     return CHIP_OK;
 }
 
-// Tuning aid, not part of the ABI (no declaration in cerebro_hip.h): how many ticks the resident scan instance (CHIP_TICK_RESIDENT=1) has
-// served and how many instances were launched for them -- tests use it to prove which path a tick took.
-int chip_debug_resident_stats(chip_ctx *c, int64_t *ticks, int64_t *launches)
-{
-    if (!c || !ticks || !launches || c->group) return CHIP_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(c->res_mu);
-    *ticks = c->res_ticks;
-    *launches = c->res_launches;
-    return CHIP_OK;
-}
-
 // Several pipelined ticks per DB pass (coalesce_* above).  Passes that served more than one tick and the ticks they served, so that
 // a test can see that ticks did share a pass; CHIP_ERR_INVALID_ARG on a group.
 int chip_debug_coalesce_stats(chip_ctx *c, int64_t *passes, int64_t *ticks)
@@ -1821,7 +1398,7 @@ int chip_debug_last_scan(chip_ctx *c, chip_debug_scan_launch *out)
 }
 
 // The same record without a device: a ctx that exists on the host only (D, storage type, CU count, the knobs of the environment as
-// chip_create reads them), then the functions the enqueue path runs -- scan_policy, scan_tick_fused, scan_select.  A plain
+// chip_create reads them), then the functions the enqueue path runs -- scan_policy, tick_merge_on_scan_stream, scan_tick_fused, scan_select.  A plain
 // single-GPU ctx on its own streams, profiling off, the resident instance off.
 int chip_debug_scan_plan(int32_t D, int32_t elem, int32_t nq, int32_t K, int64_t n_rows, int32_t call, int32_t n_cus, chip_debug_scan_launch *out)
 {
@@ -1843,20 +1420,10 @@ int chip_debug_scan_plan(int32_t D, int32_t elem, int32_t nq, int32_t K, int64_t
     a.n_rows = n_rows;
     a.D = D;
     a.K = K;
-    const bool same_stream = tick && short_scan && c->scan_streams >= 2 && c->tick_same_stream;   // (enqueue_scan_merge, on a plain ctx)
+    const bool same_stream = tick_merge_on_scan_stream(c.get(), tick, short_scan, c->scan_streams >= 2, tick);   // (every tick of the library accepts: tick_submit)
     chip_tick_result dummy;
     if (scan_tick_fused(c.get(), same_stream, a, tick, nq)) { a.K = 1; a.fused_result = &dummy; }
     return scan_select(c.get(), a, nq, grid, out);
-}
-
-// ... and where its command lines live: -1 no instance has been set up yet, 0 pinned host memory + relay, 1 workgroup 0's line in
-// device memory behind the PCIe BAR + relay, 2 every workgroup's line written by the host through the BAR
-int chip_debug_resident_mode(chip_ctx *c)
-{
-    if (!c || c->group) return -1;
-    std::lock_guard<std::mutex> lk(c->res_mu);
-    if (!c->s_resident) return -1;
-    return c->res_direct ? 2 : (c->res_cmd_in_vram ? 1 : 0);
 }
 
 // Tuning aid, not part of the ABI (no declaration in cerebro_hip.h): with CHIP_SCAN_STAMPS=1 the row-batched scan kernel leaves four

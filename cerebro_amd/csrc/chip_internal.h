@@ -41,7 +41,7 @@ struct ScanArgs {
     double thresh = 0.0;
 };
 
-// ---- resident scan (opt-in: CHIP_TICK_RESIDENT=1; kernels.hip db_scan_resident, chip_api.hip resident_*) ----
+// ---- resident scan (opt-in: CHIP_TICK_RESIDENT=1; kernels.hip db_scan_resident, resident.hip) ----
 // A synchronous tick over a cache-sized prefix is ~4 us of host API up to the doorbell + ~3 us from the doorbell to the first wave in
 // front of a ~29 us kernel (profiles/r05_short_scan.md).  With the mode on, ONE instance of the row-batched scan stays on the chip (one
 // workgroup per CU, the shape such a tick launches anyway) and runs the scan body once per COMMAND: the host writes a 64-byte line in
@@ -121,24 +121,62 @@ int launch_store_rows(Ctx *c, hipStream_t s, const void *src, int src_elem, int6
 int launch_synth(Ctx *c, hipStream_t s, int64_t first_global, int64_t n, uint64_t seed,
                  const int64_t *plant_dst_dev, const int64_t *plant_src_dev, const int32_t *plant_kind_dev, int64_t n_plant, int unit);
 
+// How a slot is collected (tick_collect_slot).  Set once per tick, where it is known (the writer is named on the right):
+enum class SlotState : uint8_t {
+    Free,        // nothing enqueued                                                              tick_collect_slot (every way out but a failed wait)
+    Immediate,   // result already final on the host (skipped / too short)                        tick_begin
+    Parked,      // enqueued, not yet submitted: waits for company in Ctx::parked                 tick_enqueue_slot
+    Event,       // wait for wait_ev                                                              tick_submit, coalesce_submit, merge_enqueue_slot (exchange / group ticks)
+    Poll,        // poll seq_host for seq_want, wait_ev if the word does not arrive               tick_submit (fused launch, CHIP_TICK_POLL)
+    Resident,    // command to the resident scan instance: no event, the completion word is all  resident_tick_enqueue
+    Failed,      // the pass this tick left with could not be submitted: collect returns err     coalesce_flush
+};
+
 struct Slot {
     hipEvent_t done = nullptr;
     hipEvent_t wait_ev = nullptr;       // what collect waits for: `done`, or the merge event of the tick's list buffer (same-stream ticks)
     chip_tick_result *host = nullptr;   // pinned
     chip_tick_result *dev = nullptr;
-    bool in_flight = false;
-    bool immediate = false;             // result already final on host (skipped / too short)
+    SlotState state = SlotState::Free;
     int64_t prev_last_l = 0;            // last_l before this tick was enqueued ...
     int64_t tick_l = 0;                 // ... the l this tick committed ...
     unsigned long long *seq_host = nullptr, *seq_dev = nullptr;   // completion word of this slot (pinned, device-mapped)
     unsigned long long seq_want = 0;    // value the fused tick in flight will store there
-    bool poll = false;                  // collect by polling seq_host instead of waiting for the event
-    bool resident = false;              // the tick went to the resident scan instance: there is no event, the completion word is all
-    bool parked = false;                // enqueued, not yet submitted: waits for company in Ctx::parked (chip_api.hip coalesce_*)
     uint64_t pass_no = 0;               // Ctx::pass_no of the long scan that serves this tick
-    int32_t err = 0;                    // the pass this tick left with could not be submitted: collect returns this
+    int32_t err = 0;                    // SlotState::Failed: what collect returns
     int64_t *last_l_ptr = nullptr;      // ... and where to restore it if the tick comes back CHIP_TICK_FAILED (only while no newer
                                         //     tick has been enqueued: *last_l_ptr == tick_l)
+};
+
+// ---- resident scan instance (resident.hip): everything the opt-in mode keeps.  Guarded by `mu`, which queriers (query_mu held) and the
+// appender (append_mu held) take LAST; `enabled` and `busy` are written with query_mu held as well: the tick path reads them under it alone.
+struct Resident {
+    bool enabled = false;                   // CHIP_TICK_RESIDENT=1 in a build with the row-batched kernel, and no set-up has failed
+    double max_bytes = 512.0 * 1024 * 1024; // prefixes up to this size take it (CHIP_RESIDENT_MAX_MIB)
+    int32_t lease_ms = 250;                 // CHIP_RESIDENT_LEASE_MS
+    hipStream_t stream = nullptr;
+    void *pinned = nullptr, *cmd_vram = nullptr;   // the allocations behind the pointers below
+    bool cmd_in_vram = false;               // the command line is in device memory, written by the host through the PCIe BAR
+    bool direct = false;                    // ... and so is every workgroup's own line (no relay): CHIP_RESIDENT_BAR=2
+    ResidentCmd pending{};                  // the command in flight (re-posted to an instance launched for it)
+    int64_t test_skip_master = 0;           // test hook (CHIP_TEST_RESIDENT_SKIP_MASTER)
+    bool test_skipped = false;
+    ResidentCmd *cmd_host = nullptr;        // the line as the host writes it + its device address
+    uint32_t *cmd_hostdev = nullptr;
+    uint32_t *cmd_dev = nullptr;
+    unsigned long long *exit_host = nullptr, *exit_hostdev = nullptr;
+    chip_topk_entry *partial = nullptr;
+    int32_t *ticket = nullptr;
+    unsigned long long instance = 0;        // id of the instance launched last (0: none yet)
+    bool alive = false;                     // launched and not yet seen to have left
+    bool ready = false;                     // resident_alloc has completed: every buffer above exists (published LAST)
+    int32_t inhibit = 0;                    // > 0: no instance may be launched (resident_pause .. resident_resume); ticks are launched meanwhile
+    bool busy = false;                      // a command is in flight (one at a time)
+    uint32_t cmd_no = 0, done = 0;          // last number posted / last number seen complete
+    int32_t grid = 0;
+    Slot *slot = nullptr;                   // the slot of the command in flight
+    int64_t ticks = 0, launches = 0;        // ticks it has served / instances launched (chip_debug_resident_stats)
+    std::mutex mu;
 };
 
 struct Exchange;   // chip_multi.hip: how a sharded ctx trades its per-shard top-k lists (RCCL communicator / device copies)
@@ -204,37 +242,8 @@ struct Ctx {
     unsigned long long *seq_host_all = nullptr; // [CHIP_MAX_INFLIGHT] completion words of the slots (pinned)
     unsigned long long tick_seq = 0;            // last value handed out
     bool tick_poll = true;                      // CHIP_TICK_POLL: fused ticks are collected by polling the completion word
-    unsigned long long *next_seq_dev = nullptr; // set by tick_enqueue_slot for the enqueue that follows; taken (and cleared) by a fused launch
-    unsigned long long next_seq_val = 0;
-    bool last_enqueue_fused = false;
     bool tick_fused = true;                     // CHIP_TICK_FUSED=0 disables
-    // resident scan instance (CHIP_TICK_RESIDENT=1; chip_api.hip resident_*): guarded by query_mu like the slots
-    bool tick_resident = false;
-    double res_max_bytes = 512.0 * 1024 * 1024; // prefixes up to this size take it (CHIP_RESIDENT_MAX_MIB)
-    int32_t res_lease_ms = 250;                 // CHIP_RESIDENT_LEASE_MS
-    hipStream_t s_resident = nullptr;
-    void *res_pinned = nullptr, *res_cmd_vram = nullptr;   // the allocations behind the pointers below
-    bool res_cmd_in_vram = false;               // the command line is in device memory, written by the host through the PCIe BAR
-    bool res_direct = false;                    // ... and so is every workgroup's own line (no relay): CHIP_RESIDENT_BAR=2
-    ResidentCmd res_pending{};                  // the command in flight (re-posted to an instance launched for it)
-    int64_t res_test_skip_master = 0;           // test hook (CHIP_TEST_RESIDENT_SKIP_MASTER)
-    bool res_test_skipped = false;
-    ResidentCmd *res_cmd_host = nullptr;        // the line as the host writes it + its device address
-    uint32_t *res_cmd_hostdev = nullptr;
-    uint32_t *res_cmd_dev = nullptr;
-    unsigned long long *res_exit_host = nullptr, *res_exit_hostdev = nullptr;
-    chip_topk_entry *res_partial = nullptr;
-    int32_t *res_ticket = nullptr;
-    unsigned long long res_instance = 0;        // id of the instance launched last (0: none yet)
-    bool res_alive = false;                     // launched and not yet seen to have left
-    bool res_ready = false;                     // resident_alloc has completed: every buffer below exists (published LAST)
-    int32_t res_inhibit = 0;                    // > 0: no instance may be launched (resident_pause .. resident_resume); ticks are launched meanwhile
-    bool res_busy = false;                      // a command is in flight (one at a time)
-    uint32_t res_cmd_no = 0, res_done = 0;      // last number posted / last number seen complete
-    int32_t res_grid = 0;
-    Slot *res_slot = nullptr;                   // the slot of the command in flight
-    int64_t res_ticks = 0, res_launches = 0;    // ticks it has served / instances launched (chip_debug_resident_stats)
-    std::mutex res_mu;                          // the instance's state: queriers (query_mu held) and the appender (append_mu held) take it last
+    Resident res;                               // resident scan instance (CHIP_TICK_RESIDENT=1; resident.hip)
     uint64_t n_enqueued = 0;
     int32_t max_grid = 0;
     chip_topk_entry *topk_dev = nullptr;      // [CHIP_MAX_NQ][CHIP_MAX_TOPK]
@@ -279,7 +288,6 @@ struct Ctx {
     int32_t scan_rows = 0;        // CHIP_SCAN_ROWS: 0 = auto (prefixes up to scan_plain_bytes), 1..3 = row-batched kernel with that R for every scan, -1 = never
     double scan_plain_bytes = 768.0 * 1024 * 1024;   // prefixes up to this size: rows form, R = 1, temporal loads (CHIP_SCAN_PLAIN_MIB)
     double scan_sync_plain_bytes = 4096.0 * 1024 * 1024;   // SYNCHRONOUS ticks: the row-batched (fused, one-launch) form up to this size (CHIP_SCAN_SYNC_PLAIN_MIB)
-    bool tick_sync_now = false;      // the tick being enqueued is a synchronous chip_loop_tick (query_mu held): form chosen for latency, not throughput
     double scan_half_bytes = 192.0 * 1024 * 1024;    // prefixes up to this size: launches take half of every CU's workgroup slots (CHIP_SCAN_HALF_MIB)
     int32_t scan_short_bpc = 1;       // workgroups per CU of a launch over a cache-sized prefix (CHIP_SCAN_SHORT_BPC; 0 = as any other)
     double scan_overlap_bytes = 8.0 * 1024 * 1024 * 1024;   // launches up to this size alternate between the two scan streams (CHIP_SCAN_OVERLAP_GIB)
@@ -347,12 +355,41 @@ int ctx_append_synthetic(Ctx *c, int64_t n, uint64_t seed, const int64_t *plant_
 int ctx_read_row(Ctx *c, int64_t g, int64_t total, void *out);          // one row, storage type, async on s_query
 int query_row_ptrs(Ctx *c, const int64_t *rows, int nq, int64_t n_global, const void **q);
 int upload_query_vectors(Ctx *c, const void *queries, int src_elem, int nq, const void **q);   // -> qvec_dev (on s_scan)
-int enqueue_scan_merge(Ctx *c, int64_t k, const void *const *q, int nq, int K, int64_t l, const chip_dot_params *p,
-                       chip_topk_entry *out, chip_tick_result *res, bool tick, hipStream_t *merge_stream, hipEvent_t *merged_ev = nullptr);
+struct ScanRequest {                        // what enqueue_scan_merge is asked for; with its receipt, on the caller's stack
+    int64_t k = 0;                          // the global prefix [0, k)
+    const void *const *q = nullptr;         // nq query descriptors (device, storage type)
+    int nq = 0;
+    int K = 0;
+    chip_topk_entry *out = nullptr;         // [nq][K] lists (device or pinned host); null: none
+    chip_tick_result *res = nullptr;        // decision record of Cerebro.cpp:1056 (needs p); null: no decision
+    int64_t l = 0;                          // tick position
+    const chip_dot_params *p = nullptr;
+    bool tick = false;                      // the queries are resident rows: the launch may leave s_scan for another tick stream
+    bool sync_tick = false;                 // a synchronous chip_loop_tick: the scan form is chosen for latency, not throughput
+    bool merge_on_scan_stream = false;      // the caller accepts the scan's stream as the merge stream (it orders what follows by the receipt)
+    unsigned long long *seq_dev = nullptr;  // completion word a FUSED launch stores seq_val to (null: none)
+    unsigned long long seq_val = 0;
+};
+struct ScanReceipt {
+    hipStream_t merge_stream = nullptr;     // the stream the merge (or the fused scan) ran on
+    hipEvent_t done_ev = nullptr;           // the tick's completion event, if it has one of its own (merge on the scan's stream); else null
+    bool fused = false;                     // the launch was the one-launch tick: the kernel stores the completion word itself
+};
+int enqueue_scan_merge(Ctx *c, const ScanRequest &rq, ScanReceipt *rcpt = nullptr);
+// "This tick's merge stays on the scan's stream", from facts (enqueue_scan_merge and, on a ctx without streams, chip_debug_scan_plan)
+bool tick_merge_on_scan_stream(const Ctx *c, bool tick, bool short_scan, bool second_tick_stream, bool caller_accepts);
+template <class Args> inline void scan_args_db(const Ctx *c, Args *a)   // the segment-table / D part of a ScanArgs / MultiScanArgs
+{
+    a->seg_table = c->seg_table_dev; a->seg_shift = c->seg_shift; a->seg_mask = c->seg_rows - 1; a->D = c->D;
+}
+MergeArgs merge_args(const chip_topk_entry *in, int32_t n_lists, int32_t K, chip_topk_entry *out, chip_tick_result *result, int64_t l, const chip_dot_params *p);
+// A profiled launch (prof_on): the next start / stop event pair (prof_ev grows on demand), start recorded on s; the caller records *stop
+int prof_begin(Ctx *c, hipStream_t s, double bytes, hipEvent_t *stop);
 int merge_enqueue_slot(Ctx *c, int64_t l, const chip_dot_params *p, const void *dev_gathered, int32_t n_lists, int32_t topk, Slot &s);
 int merge_enqueue_out(Ctx *c, const void *dev_gathered, int32_t n_lists, int nq, int32_t topk, chip_topk_entry *out);
-int tick_prepare(int64_t rows_global, int64_t last_l, int64_t l, const chip_dot_params *p, int32_t *status, int64_t *k_out);
-void fill_immediate(chip_tick_result *r, int32_t status);
+// The head of every tick: busy check, the reference's bookkeeping against n_rows published rows, what a CHIP_TICK_FAILED rolls back, and for
+// SKIPPED / TOO_SHORT the immediate result with its last_l commit.  CHIP_TICK_SCANNED: the caller enqueues the scan over [0, *k) and commits *last_l.
+int tick_begin(Slot &s, int64_t n_rows, int64_t *last_l, int64_t l, const chip_dot_params *p, int32_t *status, int64_t *k);
 int tick_collect_slot(Ctx *c, Slot &s, chip_tick_result *out);
 // Parking policy of the pipelined tick (no device needed): what an enqueue does with a tick that could share a pass, given the ticks
 // already parked, the most one pass may serve and whether a scan of this ctx is still running.
@@ -368,11 +405,20 @@ void scan_read_knobs(Ctx *c);   // every CHIP_SCAN_* / CHIP_TICK_* variable that
 bool scan_policy(const Ctx *c, int64_t n_local, int nq, bool sync_tick, ScanArgs *a, int *grid);
 // A tick as ONE launch (kernels.hip fused_tick_finish): same-stream short ticks through the row-batched kernel, decision wanted, no list output
 bool scan_tick_fused(const Ctx *c, bool same_stream, const ScanArgs &a, bool decision_only, int nq);
+// ---- resident.hip: the resident scan instance ----
+void resident_read_knobs(Ctx *c);   // CHIP_TICK_RESIDENT, CHIP_RESIDENT_*, CHIP_TEST_RESIDENT_SKIP_MASTER (chip_create)
+bool resident_eligible(Ctx *c, int64_t k);   // query_mu held
+constexpr int kResidentPaused = 1;   // (internal, > 0: not a status code) the mode is paused, launch this tick
+int resident_tick_enqueue(Ctx *c, int64_t k, int64_t l, const chip_dot_params *p, Slot &s);   // CHIP_OK: s is SlotState::Resident
+int resident_collect(Ctx *c, Slot &s);
+void resident_wait_command(Ctx *c);   // chip_synchronize: a command in flight is on no stream, its slot's completion word says when it is complete
+void resident_destroy(Ctx *c);        // ctx_destroy, after the device is idle
 void resident_stop(Ctx *c);    // retire the resident scan instance and wait until it has left the chip (no-op without one): called before
                                // anything that rewrites the segment table, frees device memory or wants the chip to itself
 // resident_stop + NO new instance until resident_resume: ticks that arrive meanwhile are launched.  For sections that free / allocate
 // device memory (hipFree waits for the whole device -- a tick thread relaunching the instance in between would make it wait for as long
-// as ticks keep coming: ADVICE r5) or rewrite the segment table.  Nests; chip_resident_pause / _resume are the public form.
+// as ticks keep coming: ADVICE r5) or rewrite the segment table.  Nests; chip_resident_pause / _resume are the public form.  Without an
+// instance a pause is one uncontended mutex and a counter.
 void resident_pause(Ctx *c);
 void resident_resume(Ctx *c);
 struct ResidentPause {          // scope guard: every early return of a CHIP_HIP(...) inside the section resumes
@@ -392,7 +438,7 @@ void exchange_destroy(Ctx *c);
 int exchange_comm_ranks(const Ctx *c);      // ncclCommCount of the attached communicator, 0 if none
 void group_destroy(Ctx *c);
 // sharded ctx with an RCCL communicator attached (one process per GPU): scan -> local merge -> all-gather -> merge, all enqueued
-int xchg_tick_enqueue(Ctx *c, int64_t l, int64_t k, const chip_dot_params *p, Slot &s, bool fail_local);
+int xchg_tick_enqueue(Ctx *c, int64_t l, int64_t k, const chip_dot_params *p, bool sync_tick, Slot &s, bool fail_local);
 int xchg_query(Ctx *c, int64_t k, const void *const *q, int nq, int K, double *scores, int64_t *idx, bool fail_local);
 int xchg_fetch_rows(Ctx *c, const int64_t *rows, int nq, int64_t n_local_published, const void **q, bool *fail_local);
 // group ctx (chip_create_multi): every entry point of the header that makes sense on a group

@@ -266,7 +266,7 @@ int exchange_comm_ranks(const Ctx *c)
 // merge kernel of every rank sees the mark (topk_merge.h) and the call fails with CHIP_ERR_SHARD_FAILED on all of them alike --
 // communicators never go out of step, the caller retries.  Only HIP / RCCL errors are hard.
 // caller: tick_enqueue_slot (query_mu held, device current, tick_prepare said SCANNED)
-int xchg_tick_enqueue(Ctx *c, int64_t l, int64_t k, const chip_dot_params *p, Slot &s, bool fail_local)
+int xchg_tick_enqueue(Ctx *c, int64_t l, int64_t k, const chip_dot_params *p, bool sync_tick, Slot &s, bool fail_local)
 {
     Exchange *x = c->xchg;
     const int K = CHIP_DEFAULT_TOPK;
@@ -283,7 +283,10 @@ int xchg_tick_enqueue(Ctx *c, int64_t l, int64_t k, const chip_dot_params *p, Sl
     const chip_topk_entry *mine = x->failed_list;
     int rc_local = CHIP_OK;
     if (!fail_local) {
-        rc_local = enqueue_scan_merge(c, k, q, 3, K, l, nullptr, x->local(b), nullptr, true, nullptr);   // scan streams -> local merge on the ctx stream
+        ScanRequest rq;   // scan streams -> local merge on the ctx stream
+        rq.k = k; rq.q = q; rq.nq = 3; rq.K = K; rq.out = x->local(b);
+        rq.l = l; rq.tick = true; rq.sync_tick = sync_tick;
+        rc_local = enqueue_scan_merge(c, rq);
         if (rc_local == CHIP_OK) mine = x->local(b);
         // a HIP error / OOM of THIS rank's enqueue: the peers have posted their all-gather -- take part with the mark (they
         // get CHIP_ERR_SHARD_FAILED for this tick, the communicator stays in step), report the local error afterwards
@@ -326,7 +329,9 @@ int xchg_query(Ctx *c, int64_t k, const void *const *q, int nq, int K, double *s
     const chip_topk_entry *mine = x->failed_list;
     int rc_local = CHIP_OK;
     if (!fail_local) {
-        rc_local = enqueue_scan_merge(c, k, q, nq, K, 0, nullptr, x->local(b), nullptr, false, nullptr);
+        ScanRequest rq;
+        rq.k = k; rq.q = q; rq.nq = nq; rq.K = K; rq.out = x->local(b);
+        rc_local = enqueue_scan_merge(c, rq);
         if (rc_local == CHIP_OK) mine = x->local(b);   // else: take part with the mark, report the local error afterwards (see xchg_tick_enqueue)
     }
     CHIP_NCCL(c, rccl().AllGather(mine, x->gathered(b), sizeof(chip_topk_entry) * nq * K, ncclChar, x->comm, c->s_query));
@@ -637,8 +642,12 @@ static int sub_scan(Group *G, int g, const GroupScan &j, int b, std::atomic<int>
     chip_topk_entry *dst = direct ? root->xchg->gathered(b) + (size_t)g * list : x->local(b);
     int rc;
     // (fetched query rows were copied on s_scan: such a scan must run there too, i.e. not as a stream-alternating "tick")
-    if (!soft) rc = enqueue_scan_merge(c, j.k, q, j.nq, j.K, j.l, nullptr, dst, nullptr, j.tick && j.from_ring, nullptr);
-    else rc = hipMemcpyAsync(dst, x->failed_list, sizeof(chip_topk_entry) * list, hipMemcpyDeviceToDevice, c->s_query) == hipSuccess ? CHIP_OK : CHIP_ERR_HIP;
+    if (!soft) {
+        ScanRequest rq;
+        rq.k = j.k; rq.q = q; rq.nq = j.nq; rq.K = j.K; rq.out = dst;
+        rq.l = j.l; rq.tick = j.tick && j.from_ring;
+        rc = enqueue_scan_merge(c, rq);
+    } else rc = hipMemcpyAsync(dst, x->failed_list, sizeof(chip_topk_entry) * list, hipMemcpyDeviceToDevice, c->s_query) == hipSuccess ? CHIP_OK : CHIP_ERR_HIP;
     if (rc != CHIP_OK) return fail_hard(rc);
     if (G->transport == CHIP_EXCHANGE_RCCL) {
         // one thread per device, each on its own communicator of the clique: the classic multi-threaded NCCL layout (no group call)
@@ -695,26 +704,11 @@ int group_tick_enqueue(Ctx *gc, int64_t l, const chip_dot_params *p, int32_t slo
     std::lock_guard<std::mutex> qlk(gc->query_mu);
     if (G->broken) return CHIP_ERR_GROUP_BROKEN;
     Slot &s = root->slots[slot];
-    if (s.in_flight) return CHIP_ERR_BUSY;
-    int64_t n;
-    {
-        std::lock_guard<std::mutex> lk(gc->mu);
-        n = gc->rows_global;
-    }
+    const int64_t n = published_rows(gc);
     int32_t status = 0;
     int64_t k = 0;
-    int rc = tick_prepare(n, gc->last_l, l, p, &status, &k);
-    if (rc != CHIP_OK) return rc;
-    s.prev_last_l = gc->last_l;
-    s.tick_l = l;
-    s.last_l_ptr = &gc->last_l;
-    if (status != CHIP_TICK_SCANNED) {
-        if (status == CHIP_TICK_TOO_SHORT) gc->last_l = l;
-        fill_immediate(s.host, status);
-        s.immediate = true;
-        s.in_flight = true;
-        return CHIP_OK;
-    }
+    int rc = tick_begin(s, n, &gc->last_l, l, p, &status, &k);
+    if (rc != CHIP_OK || status != CHIP_TICK_SCANNED) return rc;
     const int64_t rows[3] = {l - 1, l - 2, l - 3};  // v, vm, vmm (Cerebro.cpp:987-989)
     GroupScan j;
     j.k = k; j.l = l; j.nq = 3; j.K = CHIP_DEFAULT_TOPK; j.rows = rows; j.n_global = l; j.p = p; j.slot = &s; j.tick = true;
@@ -744,10 +738,7 @@ int group_query(Ctx *gc, int64_t k, const int64_t *rows, const void *vectors, in
     if (G->broken) return CHIP_ERR_GROUP_BROKEN;
     GroupScan j;
     j.k = k; j.nq = nq; j.K = K; j.rows = rows; j.vectors = vectors; j.vec_elem = vec_elem;
-    {
-        std::lock_guard<std::mutex> lk(gc->mu);
-        j.n_global = gc->rows_global;
-    }
+    j.n_global = published_rows(gc);
     int rc = group_scan(G, j);
     if (rc != CHIP_OK) return rc;
     CHIP_HIP(root, hipSetDevice(root->device));
@@ -758,11 +749,7 @@ int group_scores(Ctx *gc, int64_t k, int64_t query_row, double *u)
 {
     Group *G = gc->group;
     std::lock_guard<std::mutex> qlk(gc->query_mu);
-    int64_t n;
-    {
-        std::lock_guard<std::mutex> lk(gc->mu);
-        n = gc->rows_global;
-    }
+    const int64_t n = published_rows(gc);
     if (G->broken) return CHIP_ERR_GROUP_BROKEN;
     const int ng = (int)G->subs.size();
     GroupScan j;

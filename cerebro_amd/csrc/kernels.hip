@@ -1072,7 +1072,7 @@ static int launch_scan_rows(Ctx *c, hipStream_t s, const ScanArgs &a, int grid, 
 // (agent-scope loads: 256 pollers on 256 different lines, no hot spot).  The command reaches the waves of a workgroup through LDS.
 // What the instance may read without a cache invalidation per command: published DB rows are immutable and a row is first read after
 // it has been published, so no cache ever holds an older copy of one; the SEGMENT TABLE does change when the DB opens a new segment,
-// so the host retires the instance before it touches the table (chip_api.hip resident_stop) and the next tick launches a new one.
+// so the host retires the instance before it touches the table (resident.hip resident_stop) and the next tick launches a new one.
 // Every wait has a way out: workgroup 0 leaves (and sends the others home) after lease_ticks without a command, the others after four
 // times that without a go word, so a host that died -- or a workgroup that never became resident -- cannot hold the chip.
 __device__ __forceinline__ uint32_t uni32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }

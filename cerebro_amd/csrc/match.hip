@@ -317,7 +317,7 @@ static int match_state(Ctx *c, MatchState **out)
     MatchState *st = static_cast<MatchState *>(c->match_state);
     *out = st;
     if (st->ready) return CHIP_OK;
-    ResidentPause paused(c, c->tick_resident);   // allocations may wait for the whole device: no resident scan instance meanwhile (as pnp_reserve)
+    ResidentPause paused(c);   // allocations may wait for the whole device: no resident scan instance meanwhile (as pnp_reserve)
     const size_t n = kMatchMax;
     CHIP_HIP(c, hipMalloc(&st->d1, n * CHIP_ORB_DESC_BYTES));
     CHIP_HIP(c, hipMalloc(&st->d2, n * CHIP_ORB_DESC_BYTES));
@@ -347,7 +347,7 @@ static int match_state(Ctx *c, MatchState **out)
 static int match_reserve_image(Ctx *c, float **buf, size_t *cap, size_t want)
 {
     if (want <= *cap) return CHIP_OK;
-    ResidentPause paused(c, c->tick_resident);
+    ResidentPause paused(c);
     (void)hipFree(*buf);
     *buf = nullptr; *cap = 0;
     CHIP_HIP(c, hipMalloc(buf, want * sizeof(float)));

@@ -2377,7 +2377,7 @@ static int pnp_reserve(Ctx *c, PnpState *st, int N, int H, int words, int P)
 {
     // hipFree waits for the whole device: not with a resident scan instance on it, and none launched by the tick thread until the last
     // allocation below is done (at 10 Hz the lease never runs out, the frees would wait for as long as ticks keep coming)
-    ResidentPause paused(c, c->tick_resident && (N > st->cap_N || H > st->cap_H || words > st->cap_words));
+    ResidentPause paused(c, N > st->cap_N || H > st->cap_H || words > st->cap_words);
     if (N > st->cap_N) {
         (void)hipFree(st->X); (void)hipHostFree(st->h_in);
         st->X = st->uv = st->h_in = nullptr; st->cap_N = 0;

@@ -1,5 +1,5 @@
 """GPU tests of the resident scan instance (opt-in, CHIP_TICK_RESIDENT=1: cerebro_amd/csrc/kernels.hip db_scan_resident,
-chip_api.hip resident_*): synchronous ticks over cache-sized prefixes are COMMANDS to a kernel that stays on the chip instead of
+resident.hip): synchronous ticks over cache-sized prefixes are COMMANDS to a kernel that stays on the chip instead of
 launches.  The bar is the one of every other tick path -- the 64-byte decision record byte for byte -- against the two-launch path
 (CHIP_TICK_FUSED=0: ordinary kernel-boundary visibility) and, for one tick, against the CPU oracle; plus the life cycle: an instance
 whose lease ran out is replaced, appended rows are seen, a new DB segment retires it, other kernels of the ctx run next to it, ticks

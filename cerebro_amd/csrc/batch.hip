@@ -381,22 +381,19 @@ __global__ __launch_bounds__(512) void topk_merge_batch(BatchMergeArgs a)
 }
 
 struct BatchState {
-    float *Q = nullptr, *Qt = nullptr;
-    uint32_t *tile_ctr = nullptr;     // one counter per query tile (kMaxQTiles)
-    chip_topk_entry *partial = nullptr, *out = nullptr, *h_out = nullptr;
-    int64_t cap_q = 0, cap_partial = 0, cap_out = 0;
+    DevBuf<float> Q, Qt;
+    DevBuf<uint32_t> tile_ctr;        // one counter per query tile (kMaxQTiles)
+    DevBuf<chip_topk_entry> partial, out;
+    PinnedBuf<chip_topk_entry> h_out;
     // sharded DBs (chip_multi.hip): every shard's [Qpad][K] list side by side, and the merged result of the whole DB
-    chip_topk_entry *gathered = nullptr, *merged = nullptr;
-    int64_t cap_gathered = 0, cap_merged = 0;
+    DevBuf<chip_topk_entry> gathered, merged;
     hipEvent_t ev_done = nullptr;     // this shard's list is complete (recorded on its scan stream)
 };
 
 void batch_destroy(Ctx *c)
 {
-    BatchState *st = static_cast<BatchState *>(c->batch_state);
+    BatchState *st = c->batch_state;
     if (!st) return;
-    (void)hipFree(st->Q); (void)hipFree(st->Qt); (void)hipFree(st->tile_ctr); (void)hipFree(st->partial); (void)hipFree(st->out); (void)hipHostFree(st->h_out);
-    (void)hipFree(st->gathered); (void)hipFree(st->merged);
     if (st->ev_done) (void)hipEventDestroy(st->ev_done);
     delete st;
     c->batch_state = nullptr;
@@ -413,7 +410,7 @@ int batch_local_enqueue(Ctx *c, int64_t k, const float *queries, int32_t Q, int3
         c->batch_state = new (std::nothrow) BatchState();
         if (!c->batch_state) return CHIP_ERR_OOM;
     }
-    BatchState *st = static_cast<BatchState *>(c->batch_state);
+    BatchState *st = c->batch_state;
     ResidentPause paused(c);   // the many-query scan fills every CU (and may free / allocate): no resident scan instance until it returns
     const int D = c->D;
     const int Qpad = batch_qpad(Q);
@@ -434,25 +431,13 @@ int batch_local_enqueue(Ctx *c, int64_t k, const float *queries, int32_t Q, int3
     if (P < 1) P = 1;
 
     hipStream_t s = c->s_scan;
-    if ((int64_t)Qpad * D > st->cap_q) {
-        (void)hipFree(st->Q); st->Q = nullptr; st->cap_q = 0;
-        (void)hipFree(st->Qt); st->Qt = nullptr;
-        CHIP_HIP(c, hipMalloc(&st->Q, sizeof(float) * (size_t)Qpad * D));
-        CHIP_HIP(c, hipMalloc(&st->Qt, sizeof(float) * (size_t)Qpad * D));
-        st->cap_q = (int64_t)Qpad * D;
-    }
-    if (P * Qpad * topk > st->cap_partial) {
-        (void)hipFree(st->partial); st->partial = nullptr; st->cap_partial = 0;
-        CHIP_HIP(c, hipMalloc(&st->partial, sizeof(chip_topk_entry) * (size_t)(P * Qpad * topk)));
-        st->cap_partial = P * Qpad * topk;
-    }
-    if ((int64_t)Qpad * topk > st->cap_out) {
-        (void)hipFree(st->out); (void)hipHostFree(st->h_out); st->out = st->h_out = nullptr; st->cap_out = 0;
-        CHIP_HIP(c, hipMalloc(&st->out, sizeof(chip_topk_entry) * (size_t)Qpad * topk));
-        CHIP_HIP(c, hipHostMalloc(&st->h_out, sizeof(chip_topk_entry) * (size_t)Qpad * topk, hipHostMallocDefault));
-        st->cap_out = (int64_t)Qpad * topk;
-    }
-    if (!st->tile_ctr) CHIP_HIP(c, hipMalloc(&st->tile_ctr, sizeof(uint32_t) * kMaxQTiles));
+    int rc = st->Q.reserve(c, (size_t)Qpad * D);
+    if (rc == CHIP_OK) rc = st->Qt.reserve(c, (size_t)Qpad * D);
+    if (rc == CHIP_OK) rc = st->partial.reserve(c, (size_t)(P * Qpad * topk));
+    if (rc == CHIP_OK) rc = st->out.reserve(c, (size_t)Qpad * topk);
+    if (rc == CHIP_OK) rc = st->h_out.reserve(c, (size_t)Qpad * topk);
+    if (rc == CHIP_OK) rc = st->tile_ctr.reserve(c, kMaxQTiles);
+    if (rc != CHIP_OK) return rc;
     if (qtiles > kMaxQTiles) return CHIP_ERR_UNSUPPORTED;
     CHIP_HIP(c, hipMemsetAsync(st->tile_ctr, 0, sizeof(uint32_t) * kMaxQTiles, s));
     CHIP_HIP(c, hipMemsetAsync(st->Q, 0, sizeof(float) * (size_t)Qpad * D, s));
@@ -465,7 +450,7 @@ int batch_local_enqueue(Ctx *c, int64_t k, const float *queries, int32_t Q, int3
     }
 
     BatchArgs a;
-    a.seg_table = reinterpret_cast<const float *const *>(c->seg_table_dev); a.seg_shift = c->seg_shift; a.seg_mask = c->seg_rows - 1;
+    a.seg_table = reinterpret_cast<const float *const *>(c->seg_table_dev.get()); a.seg_shift = c->seg_shift; a.seg_mask = c->seg_rows - 1;
     a.n_rows = n_rows; a.D = D; a.Q = st->Q; a.Qt = st->Qt; a.Qpad = Qpad; a.K = topk; a.tile_ctr = st->tile_ctr;
     a.idx_mul = c->nranks; a.idx_add = c->nranks == 1 ? 0 : c->rank; a.partial = st->partial;
     constexpr int KCsel = 32;
@@ -500,14 +485,14 @@ int batch_local_enqueue(Ctx *c, int64_t k, const float *queries, int32_t Q, int3
 // D2H of a finished [Q][topk] list on the ctx's scan stream + conversion to the caller's arrays (synchronises that stream)
 int batch_deliver(Ctx *c, const chip_topk_entry *list_dev, int32_t Q, int32_t topk, float *scores, int64_t *idx)
 {
-    BatchState *st = static_cast<BatchState *>(c->batch_state);
+    chip_topk_entry *const h_out = c->batch_state->h_out.host();
     hipStream_t s = c->s_scan;
-    CHIP_HIP(c, hipMemcpyAsync(st->h_out, list_dev, sizeof(chip_topk_entry) * (size_t)Q * topk, hipMemcpyDeviceToHost, s));
+    CHIP_HIP(c, hipMemcpyAsync(h_out, list_dev, sizeof(chip_topk_entry) * (size_t)Q * topk, hipMemcpyDeviceToHost, s));
     CHIP_HIP(c, hipStreamSynchronize(s));
-    if (st->h_out[0].idx == kFailedShardIdx) return CHIP_ERR_SHARD_FAILED;   // a shard took part with the failure mark (chip_multi.hip)
+    if (h_out[0].idx == kFailedShardIdx) return CHIP_ERR_SHARD_FAILED;   // a shard took part with the failure mark (chip_multi.hip)
     for (int64_t i = 0; i < (int64_t)Q * topk; i++) {
-        if (scores) scores[i] = (float)st->h_out[i].score;
-        if (idx) idx[i] = st->h_out[i].idx;
+        if (scores) scores[i] = (float)h_out[i].score;
+        if (idx) idx[i] = h_out[i].idx;
     }
     return CHIP_OK;
 }
@@ -519,18 +504,10 @@ int batch_exchange_buffers(Ctx *c, int n_lists, int32_t Qpad, int32_t topk, chip
         c->batch_state = new (std::nothrow) BatchState();
         if (!c->batch_state) return CHIP_ERR_OOM;
     }
-    BatchState *st = static_cast<BatchState *>(c->batch_state);
-    const int64_t ng = (int64_t)n_lists * Qpad * topk, nm = (int64_t)Qpad * topk;
-    if (ng > st->cap_gathered) {
-        (void)hipFree(st->gathered); st->gathered = nullptr; st->cap_gathered = 0;
-        CHIP_HIP(c, hipMalloc(&st->gathered, sizeof(chip_topk_entry) * (size_t)ng));
-        st->cap_gathered = ng;
-    }
-    if (nm > st->cap_merged) {
-        (void)hipFree(st->merged); st->merged = nullptr; st->cap_merged = 0;
-        CHIP_HIP(c, hipMalloc(&st->merged, sizeof(chip_topk_entry) * (size_t)nm));
-        st->cap_merged = nm;
-    }
+    BatchState *st = c->batch_state;
+    int rc = st->gathered.reserve(c, (size_t)n_lists * Qpad * topk);
+    if (rc == CHIP_OK) rc = st->merged.reserve(c, (size_t)Qpad * topk);
+    if (rc != CHIP_OK) return rc;
     if (!st->ev_done) CHIP_HIP(c, hipEventCreateWithFlags(&st->ev_done, hipEventDisableTiming));
     if (gathered) *gathered = st->gathered;
     if (merged) *merged = st->merged;

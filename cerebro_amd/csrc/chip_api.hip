@@ -128,8 +128,8 @@ static int configure_storage(Ctx *c, int elem)
         std::lock_guard<std::mutex> lk(c->mu);
         c->segs.clear();
     }
-    if (c->ring_dev) { (void)hipFree(c->ring_dev); c->ring_dev = nullptr; }
-    if (c->qvec_dev) { (void)hipFree(c->qvec_dev); c->qvec_dev = nullptr; }
+    c->ring_dev.release();
+    c->qvec_dev.release();
     c->elem = elem;
     // segment geometry: power-of-two rows, ~512 MiB (float rows) / ~1 GiB (double rows) each
     int64_t rows = kSegBytesTarget / ((int64_t)c->D * 4);
@@ -140,13 +140,16 @@ static int configure_storage(Ctx *c, int elem)
     c->seg_rows = 1ll << shift;
     CHIP_HIP(c, hipMemset(c->seg_table_dev, 0, kMaxSegs * sizeof(void *)));
     if (c->nranks > 1) {
-        CHIP_HIP(c, hipMalloc(&c->ring_dev, (size_t)CHIP_RING_ROWS * c->D * elem));
+        const int rc = c->ring_dev.reserve(c, (size_t)CHIP_RING_ROWS * c->D * elem);
+        if (rc != CHIP_OK) return rc;
         CHIP_HIP(c, hipMemset(c->ring_dev, 0, (size_t)CHIP_RING_ROWS * c->D * elem));
     }
-    CHIP_HIP(c, hipMalloc(&c->qvec_dev, (size_t)CHIP_MAX_NQ * c->D * elem));
-    return CHIP_OK;
+    return c->qvec_dev.reserve(c, (size_t)CHIP_MAX_NQ * c->D * elem);
 }
 
+// Drains the ctx, then destroys what is not memory.  The buffers the ctx owns (its DevBuf / PinnedBuf members) are freed by their destructors
+// at the `delete c` at the end, the units' by their *_destroy: all of it after the drain and with the ctx's device still current, for every
+// sub-context of a group as well (group_destroy comes here once per sub-context).
 void ctx_destroy(chip_ctx *c)
 {
     if (!c) return;
@@ -162,13 +165,7 @@ void ctx_destroy(chip_ctx *c)
     batch_destroy(c);
     match_destroy(c);
     for (void *p : c->segs) (void)hipFree(p);
-    if (c->seg_table_dev) (void)hipFree(c->seg_table_dev);
-    if (c->ring_dev) (void)hipFree(c->ring_dev);
-    if (c->stage_dev) (void)hipFree(c->stage_dev);
-    if (c->flags_dev) (void)hipFree(c->flags_dev);
-    if (c->flags_host) (void)hipHostFree(c->flags_host);
     for (int i = 0; i < Ctx::kRing; i++) {
-        if (c->partial_dev[i]) (void)hipFree(c->partial_dev[i]);
         if (c->ev_scan[i]) (void)hipEventDestroy(c->ev_scan[i]);
         if (c->ev_merged[i]) (void)hipEventDestroy(c->ev_merged[i]);
     }
@@ -176,16 +173,8 @@ void ctx_destroy(chip_ctx *c)
     if (c->s_scan2) (void)hipStreamDestroy(c->s_scan2);
     for (hipStream_t x : c->s_scan_x)
         if (x) (void)hipStreamDestroy(x);
-    if (c->topk_host) (void)hipHostFree(c->topk_host);
-    if (c->qvec_dev) (void)hipFree(c->qvec_dev);
-    if (c->scores_dev) (void)hipFree(c->scores_dev);
-    if (c->stamps_dev) (void)hipFree(c->stamps_dev);
-    if (c->tickets_dev) (void)hipFree(c->tickets_dev);
-    if (c->seq_host_all) (void)hipHostFree(c->seq_host_all);
-    for (Slot &s : c->slots) {
+    for (Slot &s : c->slots)
         if (s.done) (void)hipEventDestroy(s.done);
-        if (s.host) (void)hipHostFree(s.host);
-    }
     for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
     if (c->own_query_stream && c->s_query) (void)hipStreamDestroy(c->s_query);
     if (c->s_append) (void)hipStreamDestroy(c->s_append);
@@ -232,14 +221,15 @@ static int create_impl(chip_ctx *c, int64_t capacity_hint, int elem)
     CHIP_HIP(c, hipStreamCreateWithFlags(&c->s_query, hipStreamNonBlocking));
     CHIP_HIP(c, hipStreamCreateWithFlags(&c->s_append, hipStreamNonBlocking));
     CHIP_HIP(c, hipStreamCreateWithFlags(&c->s_pnp, hipStreamNonBlocking));
-    CHIP_HIP(c, hipMalloc(&c->seg_table_dev, kMaxSegs * sizeof(void *)));
-    int rc = configure_storage(c, elem);
+    int rc = c->seg_table_dev.alloc(c, kMaxSegs);
+    if (rc == CHIP_OK) rc = configure_storage(c, elem);
     if (rc != CHIP_OK) return rc;
     c->stage_bytes = 64ull << 20;
     if (c->stage_bytes < (size_t)c->D * 8 * 64) c->stage_bytes = (size_t)c->D * 8 * 64;
-    CHIP_HIP(c, hipMalloc(&c->stage_dev, c->stage_bytes));
-    CHIP_HIP(c, hipMalloc(&c->flags_dev, sizeof(uint32_t)));
-    CHIP_HIP(c, hipHostMalloc(&c->flags_host, sizeof(uint32_t), hipHostMallocDefault));
+    rc = c->stage_dev.alloc(c, c->stage_bytes);
+    if (rc == CHIP_OK) rc = c->flags_dev.alloc(c, 1);
+    if (rc == CHIP_OK) rc = c->flags_host.alloc(c, 1);
+    if (rc != CHIP_OK) return rc;
 
     scan_read_knobs(c);
     CHIP_HIP(c, hipStreamCreateWithFlags(&c->s_scan, hipStreamNonBlocking));
@@ -256,11 +246,13 @@ static int create_impl(chip_ctx *c, int64_t capacity_hint, int elem)
     for (int i = 0; i < Ctx::kRing; i++) {
         // [max_grid][CHIP_MAX_NQ][CHIP_MAX_TOPK] of one launch, or [kMultiMaxTicks][max_grid][3][CHIP_MAX_TOPK] of a pass that serves several ticks
         constexpr size_t kListsPerGroup = 3 * kMultiMaxTicks > CHIP_MAX_NQ ? 3 * kMultiMaxTicks : CHIP_MAX_NQ;
-        CHIP_HIP(c, hipMalloc(&c->partial_dev[i], (size_t)c->max_grid * kListsPerGroup * CHIP_MAX_TOPK * sizeof(chip_topk_entry)));
+        rc = c->partial_dev[i].alloc(c, (size_t)c->max_grid * kListsPerGroup * CHIP_MAX_TOPK);
+        if (rc != CHIP_OK) return rc;
         CHIP_HIP(c, hipEventCreateWithFlags(&c->ev_scan[i], hipEventDisableTiming));
         CHIP_HIP(c, hipEventCreateWithFlags(&c->ev_merged[i], hipEventDisableTiming));
     }
-    CHIP_HIP(c, hipMalloc(&c->tickets_dev, Ctx::kRing * sizeof(int32_t)));
+    rc = c->tickets_dev.alloc(c, Ctx::kRing);
+    if (rc != CHIP_OK) return rc;
     CHIP_HIP(c, hipMemset(c->tickets_dev, 0, Ctx::kRing * sizeof(int32_t)));
     // pipelined ticks that arrive while a long scan is running share one DB pass: at most this many per pass (0 = never; coalesce_* below)
     c->coalesce_max = env_int("CHIP_TICK_COALESCE", kMultiMaxTicks);
@@ -268,20 +260,22 @@ static int create_impl(chip_ctx *c, int64_t capacity_hint, int elem)
     if (c->coalesce_max > kMultiMaxTicks) c->coalesce_max = kMultiMaxTicks;
     c->tick_poll = env_int("CHIP_TICK_POLL", 1) != 0;
     resident_read_knobs(c);
-    CHIP_HIP(c, hipHostMalloc(&c->seq_host_all, sizeof(unsigned long long) * CHIP_MAX_INFLIGHT, hipHostMallocDefault));
-    std::memset(c->seq_host_all, 0, sizeof(unsigned long long) * CHIP_MAX_INFLIGHT);
-    CHIP_HIP(c, hipHostMalloc(&c->topk_host, (size_t)CHIP_MAX_NQ * CHIP_MAX_TOPK * sizeof(chip_topk_entry), hipHostMallocDefault));
-    CHIP_HIP(c, hipHostGetDevicePointer((void **)&c->topk_dev, c->topk_host, 0));
+    rc = c->seq_all.alloc(c, CHIP_MAX_INFLIGHT);
+    if (rc != CHIP_OK) return rc;
+    std::memset(c->seq_all.host(), 0, sizeof(unsigned long long) * CHIP_MAX_INFLIGHT);
+    rc = c->topk.alloc(c, (size_t)CHIP_MAX_NQ * CHIP_MAX_TOPK);
+    if (rc != CHIP_OK) return rc;
     for (Slot &s : c->slots) {
         CHIP_HIP(c, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
         // pinned + mapped: the deciding workgroup stores the record here directly, no D2H copy kernel per tick
-        CHIP_HIP(c, hipHostMalloc(&s.host, sizeof(chip_tick_result), hipHostMallocDefault));
-        CHIP_HIP(c, hipHostGetDevicePointer((void **)&s.dev, s.host, 0));
-        s.seq_host = c->seq_host_all + (&s - c->slots);
-        CHIP_HIP(c, hipHostGetDevicePointer((void **)&s.seq_dev, s.seq_host, 0));
+        rc = s.rec.alloc(c, 1);
+        if (rc != CHIP_OK) return rc;
+        s.seq_host = c->seq_all.host() + (&s - c->slots);
+        s.seq_dev = c->seq_all.dev() + (&s - c->slots);
     }
     if (env_int("CHIP_SCAN_STAMPS", 0)) {
-        CHIP_HIP(c, hipMalloc(&c->stamps_dev, ((size_t)c->max_grid * 16 * 4 + 64) * sizeof(unsigned long long)));   // (+ 8 launch-wide stamps behind the waves')
+        rc = c->stamps_dev.alloc(c, (size_t)c->max_grid * 16 * 4 + 64);   // (+ 8 launch-wide stamps behind the waves')
+        if (rc != CHIP_OK) return rc;
         CHIP_HIP(c, hipMemset(c->stamps_dev, 0, ((size_t)c->max_grid * 16 * 4 + 64) * sizeof(unsigned long long)));
     }
     rc = pnp_create(c);
@@ -508,7 +502,7 @@ int upload_query_vectors(Ctx *c, const void *queries, int src_elem, int nq, cons
         CHIP_HIP(c, hipMemcpyAsync(c->qvec_dev, c->qconv.data(), n * c->elem, hipMemcpyHostToDevice, c->s_scan));
         CHIP_HIP(c, hipStreamSynchronize(c->s_scan));   // qconv is pageable and reused
     }
-    for (int i = 0; i < nq; i++) q[i] = static_cast<char *>(c->qvec_dev) + (size_t)i * c->D * c->elem;
+    for (int i = 0; i < nq; i++) q[i] = c->qvec_dev + (size_t)i * c->D * c->elem;
     return CHIP_OK;
 }
 
@@ -550,7 +544,7 @@ int tick_begin(Slot &s, int64_t n_rows, int64_t *last_l, int64_t l, const chip_d
     s.last_l_ptr = last_l;
     if (*status != CHIP_TICK_SCANNED) {
         if (*status == CHIP_TICK_TOO_SHORT) *last_l = l;   // :1098 (the else-branch of :1022 still ends the pass)
-        fill_immediate(s.host, *status);
+        fill_immediate(s.rec.host(), *status);
         s.state = SlotState::Immediate;
     }
     return CHIP_OK;
@@ -561,7 +555,7 @@ static int tick_submit(Ctx *c, int64_t k, int64_t l, const chip_dot_params *p, c
 {
     ScanRequest rq;
     rq.k = k; rq.q = q; rq.nq = 3; rq.K = CHIP_DEFAULT_TOPK;
-    rq.res = s.dev; rq.l = l; rq.p = p;
+    rq.res = s.rec.dev(); rq.l = l; rq.p = p;
     rq.tick = true; rq.sync_tick = sync_tick; rq.merge_on_scan_stream = true;
     if (c->tick_poll) { s.seq_want = ++c->tick_seq; rq.seq_dev = s.seq_dev; rq.seq_val = s.seq_want; }
     ScanReceipt done;
@@ -631,7 +625,7 @@ static int coalesce_submit(Ctx *c, int T)
     CHIP_HIP(c, hipStreamWaitEvent(c->s_query, c->ev_scan[b], 0));
     for (int t = 0; t < T; t++) {
         const Ctx::ParkedTick &pt = c->parked[t];
-        rc = launch_merge(c, c->s_query, merge_args(c->partial_dev[b] + (size_t)t * grid * 3 * K, grid, K, nullptr, pt.slot->dev, pt.l, &pt.p), 3);
+        rc = launch_merge(c, c->s_query, merge_args(c->partial_dev[b] + (size_t)t * grid * 3 * K, grid, K, nullptr, pt.slot->rec.dev(), pt.l, &pt.p), 3);
         if (rc != CHIP_OK) return rc;
         CHIP_HIP(c, hipEventRecord(pt.slot->done, c->s_query));
         pt.slot->wait_ev = pt.slot->done;
@@ -742,7 +736,7 @@ int tick_collect_slot(Ctx *c, Slot &s, chip_tick_result *out)
         CHIP_HIP(c, hipEventSynchronize(s.wait_ev));   // (a failure leaves the slot as it is)
         break;
     }
-    *out = *s.host;
+    *out = *s.rec.host();
     s.state = SlotState::Free;
     if (out->status == CHIP_TICK_FAILED) {   // a shard could not take part: the tick had no effect (:1098 was not reached)
         // Roll last_l back only while this tick is still the newest one enqueued.  With ticks pipelined, a later tick may have been
@@ -765,10 +759,10 @@ int tick_collect_slot(Ctx *c, Slot &s, chip_tick_result *out)
 int sync_topk_out(Ctx *c, int nq, int K, double *scores, int64_t *idx)
 {
     CHIP_HIP(c, hipStreamSynchronize(c->s_query));  // the last block stored the list into pinned host memory
-    if (c->topk_host[0].idx == -2) return CHIP_ERR_SHARD_FAILED;   // kFailedShardIdx: a shard could not take part (every rank sees it)
+    if (c->topk.host()[0].idx == -2) return CHIP_ERR_SHARD_FAILED;   // kFailedShardIdx: a shard could not take part (every rank sees it)
     for (int i = 0; i < nq * K; i++) {
-        if (scores) scores[i] = c->topk_host[i].score;
-        if (idx) idx[i] = c->topk_host[i].idx;
+        if (scores) scores[i] = c->topk.host()[i].score;
+        if (idx) idx[i] = c->topk.host()[i].idx;
     }
     return CHIP_OK;
 }
@@ -816,7 +810,7 @@ static int append_pass(Ctx *c, const void *desc, int src_elem, int64_t first, in
 // bit0 = a value that is not float32-representable went into float rows, bit1 = NaN / Inf.
 int append_store_db(Ctx *c, const void *desc, int src_elem, int64_t first, int64_t n, bool owner_only, uint32_t *bad)
 {
-    *c->flags_host = 0;
+    *c->flags_host.host() = 0;
     CHIP_HIP(c, hipMemsetAsync(c->flags_dev, 0, sizeof(uint32_t), c->s_append));
     int rc;
     if (owner_only && c->nranks > 1) {
@@ -828,9 +822,9 @@ int append_store_db(Ctx *c, const void *desc, int src_elem, int64_t first, int64
         rc = append_pass(c, desc, src_elem, first, 0, n, 1, false);
     }
     if (rc != CHIP_OK) return rc;
-    CHIP_HIP(c, hipMemcpyAsync(c->flags_host, c->flags_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_append));
+    CHIP_HIP(c, hipMemcpyAsync(c->flags_host.host(), c->flags_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_append));
     CHIP_HIP(c, hipStreamSynchronize(c->s_append));
-    *bad = *c->flags_host;
+    *bad = *c->flags_host.host();
     return CHIP_OK;
 }
 
@@ -903,22 +897,21 @@ int ctx_append(Ctx *c, const void *desc, int src_elem, int64_t n, uint32_t flags
 
 int synth_generate(Ctx *c, int64_t first, int64_t n, uint64_t seed, const int64_t *plant_dst, const int64_t *plant_src, const int32_t *plant_kind, int64_t n_plant, int unit)
 {
-    int64_t *pd = nullptr, *ps = nullptr;
-    int32_t *pk = nullptr;
+    ResidentPause paused(c, n_plant > 0);   // declared first: the plant arrays below are freed before it resumes
+    DevBuf<int64_t> pd, ps;
+    DevBuf<int32_t> pk;
     if (n_plant > 0) {
-        CHIP_HIP(c, hipMalloc(&pd, n_plant * sizeof(int64_t)));
-        CHIP_HIP(c, hipMalloc(&ps, n_plant * sizeof(int64_t)));
-        CHIP_HIP(c, hipMalloc(&pk, n_plant * sizeof(int32_t)));
+        int rc = pd.reserve(c, (size_t)n_plant);
+        if (rc == CHIP_OK) rc = ps.reserve(c, (size_t)n_plant);
+        if (rc == CHIP_OK) rc = pk.reserve(c, (size_t)n_plant);
+        if (rc != CHIP_OK) return rc;
         CHIP_HIP(c, hipMemcpyAsync(pd, plant_dst, n_plant * sizeof(int64_t), hipMemcpyHostToDevice, c->s_append));
         CHIP_HIP(c, hipMemcpyAsync(ps, plant_src, n_plant * sizeof(int64_t), hipMemcpyHostToDevice, c->s_append));
         CHIP_HIP(c, hipMemcpyAsync(pk, plant_kind, n_plant * sizeof(int32_t), hipMemcpyHostToDevice, c->s_append));
     }
     int rc = ring_begin_append(c, first + n);   // same ordering against in-flight scans as ctx_append
     if (rc == CHIP_OK) rc = launch_synth(c, c->s_append, first, n, seed, pd, ps, pk, n_plant, unit);
-    hipError_t e = hipStreamSynchronize(c->s_append);
-    if (pd) (void)hipFree(pd);
-    if (ps) (void)hipFree(ps);
-    if (pk) (void)hipFree(pk);
+    hipError_t e = hipStreamSynchronize(c->s_append);   // before the plant arrays go
     if (rc != CHIP_OK) return rc;
     CHIP_HIP(c, e);
     return CHIP_OK;
@@ -989,8 +982,8 @@ static int read_rows(chip_ctx *c, const int64_t *rows, int64_t n, void *out, int
 int merge_enqueue_slot(Ctx *c, int64_t l, const chip_dot_params *p, const void *dev_gathered, int32_t n_lists, int32_t topk, Slot &s)
 {
     if (s.state != SlotState::Free) return CHIP_ERR_BUSY;
-    // (the record goes to s.dev, pinned + mapped: no D2H copy)
-    int rc = launch_merge(c, c->s_query, merge_args((const chip_topk_entry *)dev_gathered, n_lists, topk, nullptr, s.dev, l, p), 3);
+    // (the record goes to s.rec, pinned + mapped: no D2H copy)
+    int rc = launch_merge(c, c->s_query, merge_args((const chip_topk_entry *)dev_gathered, n_lists, topk, nullptr, s.rec.dev(), l, p), 3);
     if (rc != CHIP_OK) return rc;
     CHIP_HIP(c, hipEventRecord(s.done, c->s_query));
     s.wait_ev = s.done;
@@ -1009,11 +1002,9 @@ int ctx_scores_local(Ctx *c, int64_t k, const void *q, double *u_global, int64_t
 {
     const int64_t n_rows = local_count(c, k);
     if (n_rows == 0) return CHIP_OK;
-    if (n_rows > c->scores_cap) {
-        if (c->scores_dev) { (void)hipFree(c->scores_dev); c->scores_dev = nullptr; c->scores_cap = 0; }
-        const int64_t cap = n_rows + n_rows / 4 + 1024;
-        CHIP_HIP(c, hipMalloc(&c->scores_dev, (size_t)cap * sizeof(double)));
-        c->scores_cap = cap;
+    if ((size_t)n_rows > c->scores_dev.capacity()) {
+        const int rc = c->scores_dev.reserve(c, (size_t)(n_rows + n_rows / 4 + 1024));
+        if (rc != CHIP_OK) return rc;
     }
     ScanArgs a;
     scan_args_db(c, &a);
@@ -1174,7 +1165,7 @@ static int query_common(chip_ctx *c, int64_t k, const int64_t *query_rows, const
     rc = query_rows ? query_row_ptrs(c, query_rows, nq, n, q) : upload_query_vectors(c, vectors, vec_elem, nq, q);
     if (rc != CHIP_OK) return rc;
     ScanRequest rq;
-    rq.k = k; rq.q = q; rq.nq = nq; rq.K = topk; rq.out = c->topk_dev;
+    rq.k = k; rq.q = q; rq.nq = nq; rq.K = topk; rq.out = c->topk.dev();
     rc = enqueue_scan_merge(c, rq);
     if (rc != CHIP_OK) return rc;
     return sync_topk_out(c, nq, topk, scores, idx);

@@ -101,6 +101,46 @@ struct MergeArgs {
 
 struct Ctx;
 
+// ---- owned memory: an array of T in device memory (DevBuf) or in pinned, device-mapped host memory (PinnedBuf).  Freed by the destructor.
+// reserve(): grow-only scratch.  Nothing but a compare when n fits; otherwise the old array is freed and n elements are allocated inside a
+// ResidentPause (hipFree waits for the whole device, see resident_pause), so no free of a live ctx happens outside a pause.  A unit that
+// regrows several buffers in one go keeps ONE pause of its own over the group (pauses nest): that is what stops the tick thread relaunching
+// an instance between two frees.  Contents are not kept; after a failure the buffer is empty and the status is CHIP_HIP's.
+// alloc(): the one allocation of a fixed-size buffer, WITHOUT a pause: for create (no instance can exist yet) and for code that holds
+// Resident::mu (resident_alloc_body) -- resident_pause takes that mutex, so reserve() must never be called with it held.
+template <class T> class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    int alloc(Ctx *c, size_t n);
+    int reserve(Ctx *c, size_t n);
+    void release() { if (p_) (void)hipFree(p_); p_ = nullptr; cap_ = 0; }
+    T *get() const { return p_; }
+    operator T *() const { return p_; }
+    size_t capacity() const { return cap_; }
+private:
+    T *p_ = nullptr;
+    size_t cap_ = 0;   // elements
+};
+template <class T> class PinnedBuf {
+public:
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { release(); }
+    int alloc(Ctx *c, size_t n);
+    int reserve(Ctx *c, size_t n);
+    void release() { if (h_) (void)hipHostFree(h_); h_ = d_ = nullptr; cap_ = 0; }
+    T *host() const { return h_; }
+    T *dev() const { return d_; }   // the same memory as the device addresses it
+    size_t capacity() const { return cap_; }
+private:
+    T *h_ = nullptr, *d_ = nullptr;
+    size_t cap_ = 0;
+};
+
 // kernels.hip
 int launch_resident(Ctx *c, hipStream_t s, const ResidentArgs &ra, int grid);   // CHIP_ERR_UNSUPPORTED in a build without the rows form
 int launch_scan(Ctx *c, hipStream_t s, const ScanArgs &a, int nq, int grid);
@@ -135,12 +175,11 @@ enum class SlotState : uint8_t {
 struct Slot {
     hipEvent_t done = nullptr;
     hipEvent_t wait_ev = nullptr;       // what collect waits for: `done`, or the merge event of the tick's list buffer (same-stream ticks)
-    chip_tick_result *host = nullptr;   // pinned
-    chip_tick_result *dev = nullptr;
+    PinnedBuf<chip_tick_result> rec;    // the decision record: the deciding workgroup stores it straight into host memory
     SlotState state = SlotState::Free;
     int64_t prev_last_l = 0;            // last_l before this tick was enqueued ...
     int64_t tick_l = 0;                 // ... the l this tick committed ...
-    unsigned long long *seq_host = nullptr, *seq_dev = nullptr;   // completion word of this slot (pinned, device-mapped)
+    unsigned long long *seq_host = nullptr, *seq_dev = nullptr;   // completion word of this slot (in Ctx::seq_all)
     unsigned long long seq_want = 0;    // value the fused tick in flight will store there
     uint64_t pass_no = 0;               // Ctx::pass_no of the long scan that serves this tick
     int32_t err = 0;                    // SlotState::Failed: what collect returns
@@ -155,7 +194,8 @@ struct Resident {
     double max_bytes = 512.0 * 1024 * 1024; // prefixes up to this size take it (CHIP_RESIDENT_MAX_MIB)
     int32_t lease_ms = 250;                 // CHIP_RESIDENT_LEASE_MS
     hipStream_t stream = nullptr;
-    void *pinned = nullptr, *cmd_vram = nullptr;   // the allocations behind the pointers below
+    PinnedBuf<char> pinned;                 // the allocations behind the pointers below: 128 bytes, the command line + the line of the exit word
+    DevBuf<char> cmd_vram;                  // ... one line in device memory (CHIP_RESIDENT_BAR=1)
     bool cmd_in_vram = false;               // the command line is in device memory, written by the host through the PCIe BAR
     bool direct = false;                    // ... and so is every workgroup's own line (no relay): CHIP_RESIDENT_BAR=2
     ResidentCmd pending{};                  // the command in flight (re-posted to an instance launched for it)
@@ -163,10 +203,10 @@ struct Resident {
     bool test_skipped = false;
     ResidentCmd *cmd_host = nullptr;        // the line as the host writes it + its device address
     uint32_t *cmd_hostdev = nullptr;
-    uint32_t *cmd_dev = nullptr;
+    DevBuf<uint32_t> cmd_dev;               // [max_grid] lines of 64 bytes
     unsigned long long *exit_host = nullptr, *exit_hostdev = nullptr;
-    chip_topk_entry *partial = nullptr;
-    int32_t *ticket = nullptr;
+    DevBuf<chip_topk_entry> partial;
+    DevBuf<int32_t> ticket;                 // one 64-byte line
     unsigned long long instance = 0;        // id of the instance launched last (0: none yet)
     bool alive = false;                     // launched and not yet seen to have left
     bool ready = false;                     // resident_alloc has completed: every buffer above exists (published LAST)
@@ -179,6 +219,10 @@ struct Resident {
     std::mutex mu;
 };
 
+struct PnpState;   // pnp.hip / icp.hip / batch.hip / match.hip: a unit's scratch, created on first use (PnP: at create)
+struct IcpState;
+struct BatchState;
+struct MatchState;
 struct Exchange;   // chip_multi.hip: how a sharded ctx trades its per-shard top-k lists (RCCL communicator / device copies)
 struct Group;      // chip_multi.hip: a ctx made of G per-device sub-contexts driven from one process
 
@@ -198,8 +242,8 @@ struct Ctx {
     int32_t seg_shift = 0;
     int64_t seg_rows = 0;
     std::vector<void *> segs;            // host copy of the table
-    void **seg_table_dev = nullptr;      // device table [kMaxSegs]
-    void *ring_dev = nullptr;            // [CHIP_RING_ROWS][D]  most recent rows (all ranks)
+    DevBuf<void *> seg_table_dev;        // device table [kMaxSegs]
+    DevBuf<char> ring_dev;               // [CHIP_RING_ROWS][D]  most recent rows (all ranks)
     int64_t rows_global = 0;             // published length (guarded by mu)
     int64_t rows_local = 0;
     int64_t lossy_rows = 0;
@@ -217,10 +261,10 @@ struct Ctx {
     bool own_query_stream = true;
 
     // --- append staging ---
-    void *stage_dev = nullptr;           // staging for host descriptors
+    DevBuf<char> stage_dev;              // staging for host descriptors
     size_t stage_bytes = 0;
-    uint32_t *flags_dev = nullptr;       // bit0: not-f32-representable, bit1: non-finite
-    uint32_t *flags_host = nullptr;      // pinned
+    DevBuf<uint32_t> flags_dev;          // bit0: not-f32-representable, bit1: non-finite
+    PinnedBuf<uint32_t> flags_host;
 
     // --- query scratch ---
     // Scans run back-to-back on s_scan; the merge of tick i runs on the ctx stream (s_query) behind ev_scan[b], so
@@ -234,25 +278,23 @@ struct Ctx {
     hipStream_t s_scan2 = nullptr;   // second scan stream for short scans (CHIP_SCAN_STREAMS=1 disables)
     hipStream_t s_scan_x[2] = {};    // third / fourth stream of the same-stream short tick (CHIP_SCAN_STREAMS, default 4)
     uint64_t n_same_stream = 0;      // same-stream ticks so far (round robin over the tick streams)
-    chip_topk_entry *partial_dev[kRing] = {};   // [max_grid][CHIP_MAX_NQ][CHIP_MAX_TOPK]
+    DevBuf<chip_topk_entry> partial_dev[kRing]; // [max_grid][CHIP_MAX_NQ][CHIP_MAX_TOPK]
     int32_t partial_lists[kRing] = {};                               // grid of the scan that filled it
     hipEvent_t ev_scan[kRing] = {};             // scan into buffer b finished
     hipEvent_t ev_merged[kRing] = {};           // merge out of buffer b finished
-    int32_t *tickets_dev = nullptr;             // [kRing] arrival counters of the fused tick (one per list buffer)
-    unsigned long long *seq_host_all = nullptr; // [CHIP_MAX_INFLIGHT] completion words of the slots (pinned)
+    DevBuf<int32_t> tickets_dev;                // [kRing] arrival counters of the fused tick (one per list buffer)
+    PinnedBuf<unsigned long long> seq_all;      // [CHIP_MAX_INFLIGHT] completion words of the slots
     unsigned long long tick_seq = 0;            // last value handed out
     bool tick_poll = true;                      // CHIP_TICK_POLL: fused ticks are collected by polling the completion word
     bool tick_fused = true;                     // CHIP_TICK_FUSED=0 disables
     Resident res;                               // resident scan instance (CHIP_TICK_RESIDENT=1; resident.hip)
     uint64_t n_enqueued = 0;
     int32_t max_grid = 0;
-    chip_topk_entry *topk_dev = nullptr;      // [CHIP_MAX_NQ][CHIP_MAX_TOPK]
-    chip_topk_entry *topk_host = nullptr;     // pinned, device-visible: the last block writes results straight here
+    PinnedBuf<chip_topk_entry> topk;          // [CHIP_MAX_NQ][CHIP_MAX_TOPK]: the last block writes results straight here
 
-    void *qvec_dev = nullptr;                 // [CHIP_MAX_NQ][D] external query vectors (storage type)
-    double *scores_dev = nullptr;             // chip_query_scores scratch (grown on demand)
-    unsigned long long *stamps_dev = nullptr; // tuning only (CHIP_SCAN_STAMPS=1): [max_grid * 16 waves][4]
-    int64_t scores_cap = 0;
+    DevBuf<char> qvec_dev;                    // [CHIP_MAX_NQ][D] external query vectors (storage type)
+    DevBuf<double> scores_dev;                // chip_query_scores scratch (grown on demand)
+    DevBuf<unsigned long long> stamps_dev;    // tuning only (CHIP_SCAN_STAMPS=1): [max_grid * 16 waves][4]
 
     // --- sharded tick inside the library (chip_multi.hip) ---
     std::vector<char> qconv;                  // host conversion scratch of external query vectors
@@ -299,10 +341,10 @@ struct Ctx {
     double prof_bytes_last = 0.0;
 
     // --- pnp scratch (pnp.hip) ---
-    void *pnp_state = nullptr;
-    void *icp_state = nullptr;   // icp.hip, created on first use
-    void *batch_state = nullptr; // batch.hip, created on first use
-    void *match_state = nullptr; // match.hip, created on first use
+    PnpState *pnp_state = nullptr;
+    IcpState *icp_state = nullptr;
+    BatchState *batch_state = nullptr;
+    MatchState *match_state = nullptr;
     std::mutex match_mu;         // serialises the matching calls of a ctx; taken BEFORE pnp_mu / icp_mu (chip_*_ransac_matched)
 
     mutable hipError_t last_hip = hipSuccess;
@@ -329,7 +371,7 @@ inline char *row_ptr_host(const Ctx *c, int64_t local) {
     return static_cast<char *>(c->segs[(size_t)(local >> c->seg_shift)]) + (local & (c->seg_rows - 1)) * (int64_t)c->D * c->elem;
 }
 inline char *ring_ptr(const Ctx *c, int64_t g) {
-    return static_cast<char *>(c->ring_dev) + (g % CHIP_RING_ROWS) * (int64_t)c->D * c->elem;
+    return c->ring_dev + (g % CHIP_RING_ROWS) * (int64_t)c->D * c->elem;
 }
 
 // ---- chip_api.hip: single-ctx building blocks, shared with chip_multi.hip ----
@@ -429,6 +471,37 @@ struct ResidentPause {          // scope guard: every early return of a CHIP_HIP
     ResidentPause(const ResidentPause &) = delete;
     ResidentPause &operator=(const ResidentPause &) = delete;
 };
+template <class T> int DevBuf<T>::alloc(Ctx *c, size_t n)   // (the buffer is empty)
+{
+    const hipError_t e = hipMalloc((void **)&p_, n * sizeof(T));
+    if (e != hipSuccess) p_ = nullptr;
+    CHIP_HIP(c, e);
+    cap_ = n;
+    return CHIP_OK;
+}
+template <class T> int DevBuf<T>::reserve(Ctx *c, size_t n)
+{
+    if (n <= cap_) return CHIP_OK;
+    ResidentPause paused(c);
+    release();
+    return alloc(c, n);
+}
+template <class T> int PinnedBuf<T>::alloc(Ctx *c, size_t n)
+{
+    hipError_t e = hipHostMalloc((void **)&h_, n * sizeof(T), hipHostMallocDefault);
+    if (e != hipSuccess) h_ = nullptr;
+    else if ((e = hipHostGetDevicePointer((void **)&d_, h_, 0)) != hipSuccess) release();
+    CHIP_HIP(c, e);
+    cap_ = n;
+    return CHIP_OK;
+}
+template <class T> int PinnedBuf<T>::reserve(Ctx *c, size_t n)
+{
+    if (n <= cap_) return CHIP_OK;
+    ResidentPause paused(c);
+    release();
+    return alloc(c, n);
+}
 constexpr uint32_t kCreateStoreMask = 3u;   // CHIP_CREATE_STORE_F32 | CHIP_CREATE_STORE_F64
 
 // ---- chip_multi.hip: exchange of per-shard lists inside the library (RCCL / device copies), groups of sub-contexts ----

@@ -169,12 +169,12 @@ static bool comm_init_run(const std::shared_ptr<CommInitJob> &job)
 struct Exchange {
     ncclComm_t comm = nullptr;
     int world = 1;
-    chip_topk_entry *local_ring = nullptr;      // [kXRing][kListEntries]          this shard's lists of a tick
-    chip_topk_entry *gathered_ring = nullptr;   // [kXRing][world][kListEntries]   all shards' lists ([world][nq][K] packed)
+    DevBuf<chip_topk_entry> local_ring;         // [kXRing][kListEntries]          this shard's lists of a tick
+    DevBuf<chip_topk_entry> gathered_ring;      // [kXRing][world][kListEntries]   all shards' lists ([world][nq][K] packed)
     hipEvent_t ev_local[kXRing] = {};           // copy exchange: this shard's list of tick b is written
-    chip_topk_entry *failed_list = nullptr;     // [kListEntries] of (-inf, kFailedShardIdx): what a shard that cannot take part sends
-    int32_t *agree_dev = nullptr;               // [1 + world]: this rank's "I can take part" word, then every rank's (xchg_agree)
-    int32_t *agree_host = nullptr;              // pinned, [1 + world]
+    DevBuf<chip_topk_entry> failed_list;        // [kListEntries] of (-inf, kFailedShardIdx): what a shard that cannot take part sends
+    DevBuf<int32_t> agree_dev;                  // [1 + world]: this rank's "I can take part" word, then every rank's (xchg_agree)
+    PinnedBuf<int32_t> agree_host;              // [1 + world]
     uint64_t n = 0;                             // ticks / queries exchanged so far (one-process-per-GPU layout)
     uint64_t n_calls = 0;                       // collective calls seen by this shard (test hook below)
     int test_fail_every = 0;                    // CHIP_TEST_FAIL_SHARD="rank:every": this shard fails its validation on every
@@ -189,17 +189,20 @@ static int exchange_create(Ctx *c, int world, bool need_gathered)
     if (!x) return CHIP_ERR_OOM;
     c->xchg = x;
     x->world = world;
-    CHIP_HIP(c, hipMalloc(&x->local_ring, sizeof(chip_topk_entry) * kXRing * kListEntries));
-    if (need_gathered) CHIP_HIP(c, hipMalloc(&x->gathered_ring, sizeof(chip_topk_entry) * kXRing * kListEntries * (size_t)world));
+    int rc = x->local_ring.alloc(c, (size_t)kXRing * kListEntries);
+    if (rc == CHIP_OK && need_gathered) rc = x->gathered_ring.alloc(c, (size_t)kXRing * kListEntries * (size_t)world);
+    if (rc != CHIP_OK) return rc;
     for (int i = 0; i < kXRing; i++) CHIP_HIP(c, hipEventCreateWithFlags(&x->ev_local[i], hipEventDisableTiming));
     {
         std::vector<chip_topk_entry> mark((size_t)kListEntries);
         for (chip_topk_entry &e : mark) { e.score = -INFINITY; e.idx = kFailedShardIdx; }
-        CHIP_HIP(c, hipMalloc(&x->failed_list, sizeof(chip_topk_entry) * kListEntries));
+        rc = x->failed_list.alloc(c, kListEntries);
+        if (rc != CHIP_OK) return rc;
         CHIP_HIP(c, hipMemcpy(x->failed_list, mark.data(), sizeof(chip_topk_entry) * kListEntries, hipMemcpyHostToDevice));
     }
-    CHIP_HIP(c, hipMalloc(&x->agree_dev, sizeof(int32_t) * (size_t)(1 + world)));
-    CHIP_HIP(c, hipHostMalloc(&x->agree_host, sizeof(int32_t) * (size_t)(1 + world), hipHostMallocDefault));
+    rc = x->agree_dev.alloc(c, (size_t)(1 + world));
+    if (rc == CHIP_OK) rc = x->agree_host.alloc(c, (size_t)(1 + world));
+    if (rc != CHIP_OK) return rc;
 #ifdef CHIP_TEST_HOOKS
     if (const char *t = std::getenv("CHIP_TEST_FAIL_SHARD")) {
         int r = -1, every = 0;
@@ -241,11 +244,6 @@ void exchange_destroy(Ctx *c)
     if (!x) return;
     (void)hipSetDevice(c->device);
     if (x->comm && rccl().ok) (void)rccl().CommDestroy(x->comm);
-    if (x->local_ring) (void)hipFree(x->local_ring);
-    if (x->gathered_ring) (void)hipFree(x->gathered_ring);
-    if (x->failed_list) (void)hipFree(x->failed_list);
-    if (x->agree_dev) (void)hipFree(x->agree_dev);
-    if (x->agree_host) (void)hipHostFree(x->agree_host);
     for (hipEvent_t e : x->ev_local)
         if (e) (void)hipEventDestroy(e);
     delete x;
@@ -309,7 +307,7 @@ int xchg_fetch_rows(Ctx *c, const int64_t *rows, int nq, int64_t n_local_publish
         const int64_t g = rows[i];
         if (g < 0) return CHIP_ERR_RANGE;                 // the same on every rank
         const int owner = (int)(g % x->world);
-        char *dst = static_cast<char *>(c->qvec_dev) + (size_t)i * rb;
+        char *dst = c->qvec_dev + (size_t)i * rb;
         const void *src = dst;
         if (owner == c->rank) {
             if (g >= n_local_published) *fail_local = true;   // garbage goes out, and the failure mark with it
@@ -336,7 +334,7 @@ int xchg_query(Ctx *c, int64_t k, const void *const *q, int nq, int K, double *s
     }
     CHIP_NCCL(c, rccl().AllGather(mine, x->gathered(b), sizeof(chip_topk_entry) * nq * K, ncclChar, x->comm, c->s_query));
     if (rc_local != CHIP_OK) return rc_local;
-    const int rc = merge_enqueue_out(c, x->gathered(b), x->world, nq, K, c->topk_dev);
+    const int rc = merge_enqueue_out(c, x->gathered(b), x->world, nq, K, c->topk.dev());
     if (rc != CHIP_OK) return rc;
     return sync_topk_out(c, nq, K, scores, idx);
 }
@@ -607,7 +605,7 @@ static int sub_query_rows(Group *G, int g, const GroupScan &j, const void **q)
         if (r < 0 || r >= j.n_global) return CHIP_ERR_RANGE;
         Ctx *o = G->subs[(size_t)(r % ng)];
         const void *src = row_ptr_host(o, local_of(o, r));      // published rows never move
-        char *dst = static_cast<char *>(c->qvec_dev) + (size_t)i * rb;
+        char *dst = c->qvec_dev + (size_t)i * rb;
         if (o->device == c->device) CHIP_HIP(c, hipMemcpyAsync(dst, src, rb, hipMemcpyDeviceToDevice, c->s_scan));
         else CHIP_HIP(c, hipMemcpyPeerAsync(dst, c->device, src, o->device, rb, c->s_scan));
         q[i] = dst;
@@ -655,7 +653,7 @@ static int sub_scan(Group *G, int g, const GroupScan &j, int b, std::atomic<int>
         if (nr != ncclSuccess) { c->last_comm = (int)nr; return fail_hard(CHIP_ERR_COMM); }
         if (g == 0) {
             rc = j.p ? merge_enqueue_slot(c, j.l, j.p, x->gathered(b), x->world, j.K, *j.slot)
-                     : merge_enqueue_out(c, x->gathered(b), x->world, j.nq, j.K, c->topk_dev);
+                     : merge_enqueue_out(c, x->gathered(b), x->world, j.nq, j.K, c->topk.dev());
             if (rc != CHIP_OK) return fail_hard(rc);
         }
     } else if (g != 0) {
@@ -680,7 +678,7 @@ static int root_gather_merge(Group *G, const GroupScan &j, int b)
                                               sizeof(chip_topk_entry) * list, root->s_query));
     }
     if (j.p) return merge_enqueue_slot(root, j.l, j.p, rx->gathered(b), (int)G->subs.size(), j.K, *j.slot);
-    return merge_enqueue_out(root, rx->gathered(b), (int)G->subs.size(), j.nq, j.K, root->topk_dev);
+    return merge_enqueue_out(root, rx->gathered(b), (int)G->subs.size(), j.nq, j.K, root->topk.dev());
 }
 
 static int group_scan(Group *G, const GroupScan &j)
@@ -832,13 +830,13 @@ int group_query_batch(Ctx *gc, int64_t k, const float *queries, int32_t Q, int32
 static int xchg_agree(Ctx *c, bool ok_local, bool *all_ok)
 {
     Exchange *x = c->xchg;
-    x->agree_host[0] = ok_local ? 1 : 0;
-    CHIP_HIP(c, hipMemcpyAsync(x->agree_dev, x->agree_host, sizeof(int32_t), hipMemcpyHostToDevice, c->s_query));
+    x->agree_host.host()[0] = ok_local ? 1 : 0;
+    CHIP_HIP(c, hipMemcpyAsync(x->agree_dev, x->agree_host.host(), sizeof(int32_t), hipMemcpyHostToDevice, c->s_query));
     CHIP_NCCL(c, rccl().AllGather(x->agree_dev, x->agree_dev + 1, sizeof(int32_t), ncclChar, x->comm, c->s_query));
-    CHIP_HIP(c, hipMemcpyAsync(x->agree_host + 1, x->agree_dev + 1, sizeof(int32_t) * (size_t)x->world, hipMemcpyDeviceToHost, c->s_query));
+    CHIP_HIP(c, hipMemcpyAsync(x->agree_host.host() + 1, x->agree_dev + 1, sizeof(int32_t) * (size_t)x->world, hipMemcpyDeviceToHost, c->s_query));
     CHIP_HIP(c, hipStreamSynchronize(c->s_query));
     bool all = true;
-    for (int r = 0; r < x->world; r++) all = all && x->agree_host[1 + r] == 1;
+    for (int r = 0; r < x->world; r++) all = all && x->agree_host.host()[1 + r] == 1;
     *all_ok = all;
     return CHIP_OK;
 }

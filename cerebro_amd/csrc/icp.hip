@@ -237,36 +237,20 @@ __global__ __launch_bounds__(64) void icp_score(IcpArgs a)
 }
 
 struct IcpState {
-    double *A = nullptr, *B = nullptr, *T_out = nullptr, *cost = nullptr, *T_dev = nullptr;
-    int32_t *nin = nullptr, *valid = nullptr, *valid_dev = nullptr;
-    int32_t *h_sample_in = nullptr, *d_sample_in = nullptr;   // persistent-sampler table (pinned host + device view)
-    std::vector<int32_t> perm;
-    unsigned long long *mask = nullptr;
-    int32_t cap_N = 0, cap_H = 0, cap_words = 0;
-    double *h_cost = nullptr, *h_T = nullptr;
-    int32_t *h_nin = nullptr, *h_valid = nullptr;
-    unsigned long long *h_mask = nullptr;
+    DevBuf<double> A, B, T_dev;
+    DevBuf<int32_t> valid_dev;
+    RansacResults res;                 // what icp_score leaves per hypothesis (as in pnp.hip: no D2H copies, one sync per call)
     hipStream_t stream = nullptr;      // the ICP stream (not the PnP stream: the two estimations may overlap)
     bool pending = false;              // an enqueued estimation awaits chip_icp_ransac_collect
     int32_t pend_N = 0, pend_H = 0;
     chip_ransac_params pend_params{};
 };
 
-static void icp_free(IcpState *st)
-{
-    (void)hipFree(st->A); (void)hipFree(st->B); (void)hipFree(st->T_dev); (void)hipFree(st->valid_dev);   // T_out/cost/nin/valid/mask are device views of the pinned host buffers below
-    (void)hipHostFree(st->h_cost); (void)hipHostFree(st->h_T); (void)hipHostFree(st->h_nin); (void)hipHostFree(st->h_valid); (void)hipHostFree(st->h_mask); (void)hipHostFree(st->h_sample_in);
-    const hipStream_t keep = st->stream;   // buffers are regrown, the stream lives as long as the ctx
-    *st = IcpState();
-    st->stream = keep;
-}
-
 void icp_destroy(Ctx *c)
 {
-    IcpState *st = static_cast<IcpState *>(c->icp_state);
+    IcpState *st = c->icp_state;
     if (!st) return;
-    if (st->stream) { (void)hipStreamSynchronize(st->stream); (void)hipStreamDestroy(st->stream); st->stream = nullptr; }
-    icp_free(st);
+    if (st->stream) { (void)hipStreamSynchronize(st->stream); (void)hipStreamDestroy(st->stream); }
     delete st;
     c->icp_state = nullptr;
 }
@@ -274,29 +258,15 @@ void icp_destroy(Ctx *c)
 static int icp_reserve(Ctx *c, IcpState *st, int N, int H)
 {
     const int words = (N + 63) / 64;
-    if (N <= st->cap_N && H <= st->cap_H && words <= st->cap_words) return CHIP_OK;
-    const int nN = N > st->cap_N ? N : st->cap_N, nH = H > st->cap_H ? H : st->cap_H, nW = words > st->cap_words ? words : st->cap_words;
-    ResidentPause paused(c);   // hipFree waits for the whole device: no resident scan instance on it until the last allocation is done
-    icp_free(st);
-    CHIP_HIP(c, hipMalloc(&st->A, sizeof(double) * 3 * (size_t)nN));
-    CHIP_HIP(c, hipMalloc(&st->B, sizeof(double) * 3 * (size_t)nN));
-    CHIP_HIP(c, hipMalloc(&st->T_dev, sizeof(double) * 16 * (size_t)nH));
-    CHIP_HIP(c, hipMalloc(&st->valid_dev, sizeof(int32_t) * (size_t)nH));
-    // per-hypothesis results go straight to pinned, device-mapped host memory (as in pnp.hip): no D2H copies, one sync per call
-    CHIP_HIP(c, hipHostMalloc(&st->h_cost, sizeof(double) * (size_t)nH, hipHostMallocDefault));
-    CHIP_HIP(c, hipHostMalloc(&st->h_T, sizeof(double) * 16 * (size_t)nH, hipHostMallocDefault));
-    CHIP_HIP(c, hipHostMalloc(&st->h_nin, sizeof(int32_t) * (size_t)nH, hipHostMallocDefault));
-    CHIP_HIP(c, hipHostMalloc(&st->h_valid, sizeof(int32_t) * (size_t)nH, hipHostMallocDefault));
-    CHIP_HIP(c, hipHostMalloc(&st->h_mask, sizeof(unsigned long long) * (size_t)nH * nW, hipHostMallocDefault));
-    CHIP_HIP(c, hipHostMalloc(&st->h_sample_in, sizeof(int32_t) * kSampleMax * (size_t)nH, hipHostMallocDefault));
-    CHIP_HIP(c, hipHostGetDevicePointer((void **)&st->d_sample_in, st->h_sample_in, 0));
-    CHIP_HIP(c, hipHostGetDevicePointer((void **)&st->cost, st->h_cost, 0));
-    CHIP_HIP(c, hipHostGetDevicePointer((void **)&st->T_out, st->h_T, 0));
-    CHIP_HIP(c, hipHostGetDevicePointer((void **)&st->nin, st->h_nin, 0));
-    CHIP_HIP(c, hipHostGetDevicePointer((void **)&st->valid, st->h_valid, 0));
-    CHIP_HIP(c, hipHostGetDevicePointer((void **)&st->mask, st->h_mask, 0));
-    st->cap_N = nN; st->cap_H = nH; st->cap_words = nW;
-    return CHIP_OK;
+    const size_t nN = 3 * (size_t)N, nH = (size_t)H;
+    // one pause over the group: hipFree waits for the whole device, no resident scan instance on it until the last allocation is done
+    ResidentPause paused(c, nN > st->A.capacity() || nH > st->valid_dev.capacity() || !st->res.fits(H, words));
+    int rc = st->A.reserve(c, nN);
+    if (rc == CHIP_OK) rc = st->B.reserve(c, nN);
+    if (rc == CHIP_OK) rc = st->T_dev.reserve(c, 16 * nH);
+    if (rc == CHIP_OK) rc = st->valid_dev.reserve(c, nH);
+    if (rc == CHIP_OK) rc = st->res.reserve(c, H, words);
+    return rc;
 }
 
 }  // namespace chip
@@ -321,7 +291,7 @@ static int icp_enqueue_locked(Ctx *c, const double *A, const double *B, int32_t 
         c->icp_state = new (std::nothrow) IcpState();
         if (!c->icp_state) return CHIP_ERR_OOM;
     }
-    IcpState *st = static_cast<IcpState *>(c->icp_state);
+    IcpState *st = c->icp_state;
     if (st->pending) return CHIP_ERR_BUSY;
     if (!st->stream) CHIP_HIP(c, hipStreamCreateWithFlags(&st->stream, hipStreamNonBlocking));
     const int32_t S = p->sample_size;
@@ -337,15 +307,15 @@ static int icp_enqueue_locked(Ctx *c, const double *A, const double *B, int32_t 
     IcpArgs a;
     // dev_in: A / B ARE device memory (icp_ransac_device), read where they lie
     a.A = dev_in ? A : st->A; a.B = dev_in ? B : st->B; a.N = N; a.S = S; a.seed = p->seed; a.thresh = p->error_thresh; a.use_mle = p->use_mle;
-    a.mask_words = words; a.T_out = st->T_out; a.cost = st->cost; a.nin = st->nin; a.valid = st->valid; a.mask = st->mask;
+    a.mask_words = words; a.T_out = st->res.T.dev(); a.cost = st->res.cost.dev(); a.nin = st->res.nin.dev(); a.valid = st->res.valid.dev(); a.mask = st->res.mask.dev();
     a.H = H; a.T_dev = st->T_dev; a.valid_dev = st->valid_dev;
     a.sample_in = nullptr;
     if (p->sampler == CHIP_SAMPLER_THEIA_PERSISTENT) {
-        st->perm.resize((size_t)N);
-        ransac_sample_table_persistent(p->seed, H, N, S, kSampleMax, st->perm.data(), st->h_sample_in);
-        a.sample_in = st->d_sample_in;
+        st->res.perm.resize((size_t)N);
+        ransac_sample_table_persistent(p->seed, H, N, S, kSampleMax, st->res.perm.data(), st->res.sample_in.host());
+        a.sample_in = st->res.sample_in.dev();
     }
-    for (int i = 0; i < kSampleMax; i++) {   // N - i >= 20 - 16 > 1 (icp_check_args), so the quotient fits 64 bits
+    for (int i = 0; i < kSampleMax; i++) {   // N - i >= 20 - 16 > 1 (ransac_check_params), so the quotient fits 64 bits
         const uint64_t d = (uint64_t)(N - (i < S ? i : 0));
         a.magic[i] = (uint64_t)((((unsigned __int128)1) << 64) / d);
     }
@@ -360,49 +330,19 @@ static int icp_enqueue_locked(Ctx *c, const double *A, const double *B, int32_t 
 
 static int icp_collect_locked(Ctx *c, double T_colmajor[16], float *confidence, uint8_t *inlier_mask, chip_ransac_summary *summary)
 {
-    IcpState *st = static_cast<IcpState *>(c->icp_state);
+    IcpState *st = c->icp_state;
     if (!st || !st->pending) return CHIP_ERR_BUSY;
     CHIP_HIP(c, hipSetDevice(c->device));
     CHIP_HIP(c, hipStreamSynchronize(st->stream));
     st->pending = false;
-    const chip_ransac_params *p = &st->pend_params;
-    const int32_t N = st->pend_N, S = p->sample_size;
-    const int H = st->pend_H, words = (N + 63) / 64;
-    double best_cost = DBL_MAX;
-    int32_t n_models = 0, num_it = 0;
-    const int32_t best_h = ransac_select(p, N, H, st->h_valid, st->h_cost, st->h_nin, &num_it, &n_models, &best_cost);
-    int32_t nin = 0;
-    if (best_h >= 0) {
-        std::memcpy(T_colmajor, st->h_T + 16 * (size_t)best_h, sizeof(double) * 16);
-        nin = st->h_nin[best_h];
-        const unsigned long long *hm = st->h_mask + (size_t)best_h * words;
-        if (inlier_mask)
-            for (int i = 0; i < N; i++) inlier_mask[i] = (uint8_t)((hm[i >> 6] >> (i & 63)) & 1ull);
-        const double ratio = (double)nin / (double)N;
-        *confidence = (float)(1.0 - std::pow(1.0 - std::pow(ratio, (double)S), (double)num_it));  // summary.confidence (:121)
-    } else {
-        for (int i = 0; i < 16; i++) T_colmajor[i] = NAN;
-        if (inlier_mask) std::memset(inlier_mask, 0, (size_t)N);
-        *confidence = 0.0f;
-    }
-    if (summary) {
-        summary->n_iterations = num_it;
-        summary->n_inliers = nin;
-        summary->best_hypothesis = best_h;
-        summary->n_models = n_models;
-        summary->best_cost = best_h >= 0 ? best_cost : INFINITY;
-    }
+    ransac_report(&st->pend_params, st->pend_N, st->pend_H, (st->pend_N + 63) / 64, st->res, 0, T_colmajor, confidence, inlier_mask, summary);
     return CHIP_OK;
 }
 
 static int icp_check_args(const double *A, const double *B, int32_t N, const chip_ransac_params *p)
 {
     if (!A || !B || !p) return CHIP_ERR_INVALID_ARG;
-    if (N < 20) return CHIP_ERR_TOO_FEW_POINTS;  // DlsPnpWithRansac.cpp:19-22
-    const int32_t S = p->sample_size;
-    if (S < 3 || S > kSampleMax || S > N || p->n_hypotheses < 0 || p->max_iterations < 1) return CHIP_ERR_UNSUPPORTED;
-    if (p->sampler != CHIP_SAMPLER_FRESH && p->sampler != CHIP_SAMPLER_THEIA_PERSISTENT) return CHIP_ERR_UNSUPPORTED;
-    return CHIP_OK;
+    return ransac_check_params(p, N);
 }
 
 extern "C" int chip_icp_ransac_enqueue(chip_ctx *c, const double *A, const double *B, int32_t N, const chip_ransac_params *p)

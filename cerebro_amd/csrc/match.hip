@@ -274,37 +274,22 @@ __global__ __launch_bounds__(kOneWg) void pose_sets_build(SetsArgs a)
 // ------------------------------------------------------------------------------------------------ host side
 struct MatchState {
     // inputs / intermediates, sized for kMatchMax keypoints once
-    uint8_t *d1 = nullptr, *d2 = nullptr;
-    float2 *kp1 = nullptr, *kp2 = nullptr;
-    int32_t *qidx = nullptr, *tidx = nullptr, *dist = nullptr, *table = nullptr, *counts = nullptr;
-    uint8_t *inlier = nullptr;
+    DevBuf<uint8_t> d1, d2;
+    DevBuf<float2> kp1, kp2;
+    DevBuf<int32_t> qidx, tidx, dist, table, counts;
+    DevBuf<uint8_t> inlier;
     // the five sets chip_match_pair leaves on the device
-    double *uv = nullptr, *uv_d = nullptr, *X_ab = nullptr, *uvn_ab = nullptr, *X_ba = nullptr, *uvn_ba = nullptr, *A = nullptr, *B = nullptr;
-    int32_t *mq = nullptr, *mt = nullptr;
-    float *xyz_a = nullptr, *xyz_b = nullptr;   // grown on demand
-    size_t cap_a = 0, cap_b = 0;                // floats
-    int32_t *h_counts = nullptr;                // pinned
-    bool ready = false, have_sets = false;
+    DevBuf<double> uv, uv_d, X_ab, uvn_ab, X_ba, uvn_ba, A, B;
+    DevBuf<int32_t> mq, mt;
+    DevBuf<float> xyz_a, xyz_b;                 // grown on demand
+    PinnedBuf<int32_t> h_counts;
+    bool have_sets = false;
     chip_match_summary last{};
 };
 
-static void match_free(MatchState *st)
-{
-    (void)hipFree(st->d1); (void)hipFree(st->d2); (void)hipFree(st->kp1); (void)hipFree(st->kp2);
-    (void)hipFree(st->qidx); (void)hipFree(st->tidx); (void)hipFree(st->dist); (void)hipFree(st->table); (void)hipFree(st->counts);
-    (void)hipFree(st->inlier);
-    (void)hipFree(st->uv); (void)hipFree(st->uv_d); (void)hipFree(st->X_ab); (void)hipFree(st->uvn_ab); (void)hipFree(st->X_ba);
-    (void)hipFree(st->uvn_ba); (void)hipFree(st->A); (void)hipFree(st->B); (void)hipFree(st->mq); (void)hipFree(st->mt);
-    (void)hipFree(st->xyz_a); (void)hipFree(st->xyz_b);
-    (void)hipHostFree(st->h_counts);
-}
-
 void match_destroy(Ctx *c)
 {
-    MatchState *st = static_cast<MatchState *>(c->match_state);
-    if (!st) return;
-    match_free(st);
-    delete st;
+    delete c->match_state;
     c->match_state = nullptr;
 }
 
@@ -314,45 +299,33 @@ static int match_state(Ctx *c, MatchState **out)
         c->match_state = new (std::nothrow) MatchState();
         if (!c->match_state) return CHIP_ERR_OOM;
     }
-    MatchState *st = static_cast<MatchState *>(c->match_state);
+    MatchState *st = c->match_state;
     *out = st;
-    if (st->ready) return CHIP_OK;
-    ResidentPause paused(c);   // allocations may wait for the whole device: no resident scan instance meanwhile (as pnp_reserve)
+    if (st->h_counts.capacity()) return CHIP_OK;   // reserved last: everything below exists
+    ResidentPause paused(c);   // one pause over the group (as pnp_reserve); a call after a failure keeps what the failed one obtained
     const size_t n = kMatchMax;
-    CHIP_HIP(c, hipMalloc(&st->d1, n * CHIP_ORB_DESC_BYTES));
-    CHIP_HIP(c, hipMalloc(&st->d2, n * CHIP_ORB_DESC_BYTES));
-    CHIP_HIP(c, hipMalloc(&st->kp1, n * sizeof(float2)));
-    CHIP_HIP(c, hipMalloc(&st->kp2, n * sizeof(float2)));
-    CHIP_HIP(c, hipMalloc(&st->qidx, n * sizeof(int32_t)));
-    CHIP_HIP(c, hipMalloc(&st->tidx, n * sizeof(int32_t)));
-    CHIP_HIP(c, hipMalloc(&st->dist, n * sizeof(int32_t)));
-    CHIP_HIP(c, hipMalloc(&st->table, (size_t)kCells * kCells * sizeof(int32_t)));
-    CHIP_HIP(c, hipMalloc(&st->counts, 8 * sizeof(int32_t)));
-    CHIP_HIP(c, hipMalloc(&st->inlier, n));
-    CHIP_HIP(c, hipMalloc(&st->uv, n * 2 * sizeof(double)));
-    CHIP_HIP(c, hipMalloc(&st->uv_d, n * 2 * sizeof(double)));
-    CHIP_HIP(c, hipMalloc(&st->X_ab, n * 3 * sizeof(double)));
-    CHIP_HIP(c, hipMalloc(&st->uvn_ab, n * 2 * sizeof(double)));
-    CHIP_HIP(c, hipMalloc(&st->X_ba, n * 3 * sizeof(double)));
-    CHIP_HIP(c, hipMalloc(&st->uvn_ba, n * 2 * sizeof(double)));
-    CHIP_HIP(c, hipMalloc(&st->A, n * 3 * sizeof(double)));
-    CHIP_HIP(c, hipMalloc(&st->B, n * 3 * sizeof(double)));
-    CHIP_HIP(c, hipMalloc(&st->mq, n * sizeof(int32_t)));
-    CHIP_HIP(c, hipMalloc(&st->mt, n * sizeof(int32_t)));
-    CHIP_HIP(c, hipHostMalloc(&st->h_counts, 8 * sizeof(int32_t), hipHostMallocDefault));
-    st->ready = true;
-    return CHIP_OK;
-}
-
-static int match_reserve_image(Ctx *c, float **buf, size_t *cap, size_t want)
-{
-    if (want <= *cap) return CHIP_OK;
-    ResidentPause paused(c);
-    (void)hipFree(*buf);
-    *buf = nullptr; *cap = 0;
-    CHIP_HIP(c, hipMalloc(buf, want * sizeof(float)));
-    *cap = want;
-    return CHIP_OK;
+    int rc = st->d1.reserve(c, n * CHIP_ORB_DESC_BYTES);
+    if (rc == CHIP_OK) rc = st->d2.reserve(c, n * CHIP_ORB_DESC_BYTES);
+    if (rc == CHIP_OK) rc = st->kp1.reserve(c, n);
+    if (rc == CHIP_OK) rc = st->kp2.reserve(c, n);
+    if (rc == CHIP_OK) rc = st->qidx.reserve(c, n);
+    if (rc == CHIP_OK) rc = st->tidx.reserve(c, n);
+    if (rc == CHIP_OK) rc = st->dist.reserve(c, n);
+    if (rc == CHIP_OK) rc = st->table.reserve(c, (size_t)kCells * kCells);
+    if (rc == CHIP_OK) rc = st->counts.reserve(c, 8);
+    if (rc == CHIP_OK) rc = st->inlier.reserve(c, n);
+    if (rc == CHIP_OK) rc = st->uv.reserve(c, n * 2);
+    if (rc == CHIP_OK) rc = st->uv_d.reserve(c, n * 2);
+    if (rc == CHIP_OK) rc = st->X_ab.reserve(c, n * 3);
+    if (rc == CHIP_OK) rc = st->uvn_ab.reserve(c, n * 2);
+    if (rc == CHIP_OK) rc = st->X_ba.reserve(c, n * 3);
+    if (rc == CHIP_OK) rc = st->uvn_ba.reserve(c, n * 2);
+    if (rc == CHIP_OK) rc = st->A.reserve(c, n * 3);
+    if (rc == CHIP_OK) rc = st->B.reserve(c, n * 3);
+    if (rc == CHIP_OK) rc = st->mq.reserve(c, n);
+    if (rc == CHIP_OK) rc = st->mt.reserve(c, n);
+    if (rc == CHIP_OK) rc = st->h_counts.reserve(c, 8);
+    return rc;
 }
 
 static hipStream_t match_stream(Ctx *c)
@@ -364,7 +337,7 @@ static hipStream_t match_stream(Ctx *c)
 static int launch_bf(Ctx *c, hipStream_t s, MatchState *st, int n1, int n2)
 {
     hipLaunchKernelGGL(orb_bf_match, dim3((n1 + kBfThreads - 1) / kBfThreads), dim3(kBfThreads), 0, s,
-                       reinterpret_cast<const uint4 *>(st->d1), n1, reinterpret_cast<const uint4 *>(st->d2), n2, st->tidx, st->dist);
+                       reinterpret_cast<const uint4 *>(st->d1.get()), n1, reinterpret_cast<const uint4 *>(st->d2.get()), n2, st->tidx.get(), st->dist.get());
     CHIP_HIP(c, hipGetLastError());
     return CHIP_OK;
 }
@@ -438,9 +411,9 @@ extern "C" int chip_gms_filter(chip_ctx *c, const float *kp1_xy, int32_t n1, int
     rc = launch_gms(c, s, st, false, n_matches, w1, h1, w2, h2);
     if (rc != CHIP_OK) return rc;
     CHIP_HIP(c, hipMemcpyAsync(inlier, st->inlier, (size_t)n_matches, hipMemcpyDeviceToHost, s));
-    CHIP_HIP(c, hipMemcpyAsync(st->h_counts, st->counts + 7, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    CHIP_HIP(c, hipMemcpyAsync(st->h_counts.host(), st->counts + 7, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     CHIP_HIP(c, hipStreamSynchronize(s));
-    *n_inliers = st->h_counts[0];
+    *n_inliers = st->h_counts.host()[0];
     return CHIP_OK;
 }
 
@@ -462,8 +435,8 @@ extern "C" int chip_match_pair(chip_ctx *c, const chip_match_frame *a, const chi
     const int n1 = a->n, n2 = b->n;
     if (n1 > 0 && n2 > 0) {                    // an empty train set gives no matches (BFMatcher on an empty descriptor matrix)
         const size_t fa = 3 * (size_t)a->width * a->height, fb = 3 * (size_t)b->width * b->height;
-        rc = match_reserve_image(c, &st->xyz_a, &st->cap_a, fa);
-        if (rc == CHIP_OK) rc = match_reserve_image(c, &st->xyz_b, &st->cap_b, fb);
+        rc = st->xyz_a.reserve(c, fa);
+        if (rc == CHIP_OK) rc = st->xyz_b.reserve(c, fb);
         if (rc != CHIP_OK) return rc;
         hipStream_t s = match_stream(c);
         CHIP_HIP(c, hipMemcpyAsync(st->d1, a->desc, (size_t)n1 * CHIP_ORB_DESC_BYTES, hipMemcpyHostToDevice, s));
@@ -483,14 +456,14 @@ extern "C" int chip_match_pair(chip_ctx *c, const chip_match_frame *a, const chi
         sa.A = st->A; sa.B = st->B; sa.mq = st->mq; sa.mt = st->mt; sa.counts = st->counts;
         hipLaunchKernelGGL(pose_sets_build, dim3(1), dim3(kOneWg), 0, s, sa);
         CHIP_HIP(c, hipGetLastError());
-        CHIP_HIP(c, hipMemcpyAsync(st->h_counts, st->counts, kNSets * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        CHIP_HIP(c, hipMemcpyAsync(st->h_counts.host(), st->counts, kNSets * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         CHIP_HIP(c, hipStreamSynchronize(s));
         sm.n_matches_all = n1;
-        sm.n_matches_gms = st->h_counts[kSetUv];
-        sm.n_3d2d_ab = st->h_counts[kSetAb];
-        sm.n_3d2d_ba = st->h_counts[kSetBa];
-        sm.n_3d3d = st->h_counts[kSet33];
-        sm.n_out_of_image = st->h_counts[kSetOut];
+        sm.n_matches_gms = st->h_counts.host()[kSetUv];
+        sm.n_3d2d_ab = st->h_counts.host()[kSetAb];
+        sm.n_3d2d_ba = st->h_counts.host()[kSetBa];
+        sm.n_3d3d = st->h_counts.host()[kSet33];
+        sm.n_out_of_image = st->h_counts.host()[kSetOut];
     }
     st->last = sm;
     st->have_sets = true;
@@ -503,7 +476,7 @@ extern "C" int chip_match_read_sets(chip_ctx *c, chip_match_sets_out *out)
     if (!c || !out) return CHIP_ERR_INVALID_ARG;
     if (c->group) return CHIP_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> lk(c->match_mu);
-    MatchState *st = static_cast<MatchState *>(c->match_state);
+    MatchState *st = c->match_state;
     if (!st || !st->have_sets) return CHIP_ERR_BUSY;
     CHIP_HIP(c, hipSetDevice(c->device));
     hipStream_t s = match_stream(c);
@@ -532,7 +505,7 @@ extern "C" int chip_pnp_ransac_matched(chip_ctx *c, int32_t which, const chip_ra
     if (!c || !p || !T_colmajor || !confidence || (which != CHIP_SET_AB && which != CHIP_SET_BA)) return CHIP_ERR_INVALID_ARG;
     if (c->group) return CHIP_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> lk(c->match_mu);
-    MatchState *st = static_cast<MatchState *>(c->match_state);
+    MatchState *st = c->match_state;
     if (!st || !st->have_sets) return CHIP_ERR_BUSY;
     if (which == CHIP_SET_AB) return pnp_ransac_device(c, st->X_ab, st->uvn_ab, st->last.n_3d2d_ab, p, T_colmajor, confidence, inlier_mask, summary);
     return pnp_ransac_device(c, st->X_ba, st->uvn_ba, st->last.n_3d2d_ba, p, T_colmajor, confidence, inlier_mask, summary);
@@ -544,7 +517,7 @@ extern "C" int chip_icp_ransac_matched(chip_ctx *c, const chip_ransac_params *p,
     if (!c || !p || !T_colmajor || !confidence) return CHIP_ERR_INVALID_ARG;
     if (c->group) return CHIP_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> lk(c->match_mu);
-    MatchState *st = static_cast<MatchState *>(c->match_state);
+    MatchState *st = c->match_state;
     if (!st || !st->have_sets) return CHIP_ERR_BUSY;
     return icp_ransac_device(c, st->A, st->B, st->last.n_3d3d, p, T_colmajor, confidence, inlier_mask, summary);
 }

@@ -2309,26 +2309,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 
 // ------------------------------------------------------------------------------------------------ host side
 struct PnpState {
-    PnpTables *tab_dev = nullptr;
+    DevBuf<PnpTables> tab_dev;
     // device scratch, grown on demand
-    double *X = nullptr, *uv = nullptr;   // device: one allocation, [X of all problems | uv of all problems]
-    double *h_in = nullptr;               // pinned, device-mapped staging of the same layout: pnp_build_solve reads it in place (d_hin)
-    double *d_hin = nullptr;              // device view of h_in
-    int32_t cap_N = 0;
-    double *Sg = nullptr, *Tg = nullptr;
-    int32_t *sample = nullptr, *ok = nullptr;
-    int32_t *h_sample_in = nullptr, *d_sample_in = nullptr;   // CHIP_SAMPLER_THEIA_PERSISTENT: the host-sequenced sample table (pinned) + its device view
-    std::vector<int32_t> perm;                                // ... and the permutation it is sequenced on
-    int32_t cap_H = 0, cap_words = 0;
-    // Per-hypothesis results live in pinned, device-mapped HOST memory: pnp_eig_score stores them straight across PCIe (a few
-    // hundred KB per call, posted while the kernel runs), so a call needs no D2H copy and a single stream synchronisation.
-    double *h_cost = nullptr, *h_T = nullptr;            // host views
-    int32_t *h_nin = nullptr, *h_valid = nullptr, *h_nsol = nullptr;
-    unsigned long long *h_mask = nullptr;
-    double *cost = nullptr, *T_out = nullptr;            // device views of the same allocations
-    int32_t *nin = nullptr, *valid = nullptr, *nsol = nullptr;
-    unsigned long long *mask = nullptr;
-    unsigned long long *stamps = nullptr;                // tuning only (CHIP_PNP_STAMPS): [H][8] of pnp_eig_score, then [H][16] of pnp_build_solve
+    DevBuf<double> X;                     // [X of all problems | uv of all problems]
+    PinnedBuf<double> h_in;               // staging of the same layout: pnp_build_solve reads it in place (SolveArgs)
+    DevBuf<double> Sg, Tg;
+    DevBuf<int32_t> sample, ok;
+    RansacResults res;                    // what pnp_eig_score leaves per hypothesis ...
+    PinnedBuf<int32_t> nsol;              // ... and its solution count
+    DevBuf<unsigned long long> stamps;    // tuning only (CHIP_PNP_STAMPS): [H][8] of pnp_eig_score, then [H][16] of pnp_build_solve
     int32_t stamps_n = 0;
 };
 
@@ -2340,83 +2329,43 @@ int pnp_create(Ctx *c)
     PnpTables t;
     std::memset(&t, 0, sizeof t);
     build_tables(t);
-    CHIP_HIP(c, hipMalloc(&st->tab_dev, sizeof(PnpTables)));
+    const int rc = st->tab_dev.alloc(c, 1);
+    if (rc != CHIP_OK) return rc;
     CHIP_HIP(c, hipMemcpy(st->tab_dev, &t, sizeof t, hipMemcpyHostToDevice));
-    CHIP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(pnp_build_solve<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 102 * 1024));
+    // (this block stays first: the order in which the kernel templates are first named is their order in the code object)
     if (const char *e = std::getenv("CHIP_PNP_OCCUPANCY"); e && e[0] == '1') {   // tuning only: resident workgroups per CU of the kernel pair
         int nb = -1, ne = -1;
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(pnp_build_solve<false>), kSolveThreads, kSolveLds);
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&ne, reinterpret_cast<const void *>(pnp_eig_score<false>), 64, 0);
         std::fprintf(stderr, "pnp occupancy: pnp_build_solve %d workgroups per CU, pnp_eig_score %d waves per CU\n", nb, ne);
     }
+    CHIP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(pnp_build_solve<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 102 * 1024));
     CHIP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(pnp_build_solve<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 102 * 1024));
     return CHIP_OK;
 }
 
-static void pnp_free_dev(PnpState *st)
-{
-    (void)hipFree(st->X); (void)hipHostFree(st->h_in);   // uv lives inside the X allocation
-    (void)hipFree(st->Sg); (void)hipFree(st->Tg);
-    (void)hipFree(st->sample); (void)hipFree(st->ok);
-    (void)hipHostFree(st->h_cost); (void)hipHostFree(st->h_T); (void)hipHostFree(st->h_nin); (void)hipHostFree(st->h_valid);
-    (void)hipHostFree(st->h_nsol); (void)hipHostFree(st->h_mask); (void)hipHostFree(st->h_sample_in);
-    (void)hipFree(st->stamps);
-}
-
 void pnp_destroy(Ctx *c)
 {
-    PnpState *st = static_cast<PnpState *>(c->pnp_state);
-    if (!st) return;
-    pnp_free_dev(st);
-    (void)hipFree(st->tab_dev);
-    delete st;
+    delete c->pnp_state;
     c->pnp_state = nullptr;
 }
 
-static int pnp_reserve(Ctx *c, PnpState *st, int N, int H, int words, int P)
+static int pnp_reserve(Ctx *c, PnpState *st, int N, int H, int words)
 {
-    // hipFree waits for the whole device: not with a resident scan instance on it, and none launched by the tick thread until the last
-    // allocation below is done (at 10 Hz the lease never runs out, the frees would wait for as long as ticks keep coming)
-    ResidentPause paused(c, N > st->cap_N || H > st->cap_H || words > st->cap_words);
-    if (N > st->cap_N) {
-        (void)hipFree(st->X); (void)hipHostFree(st->h_in);
-        st->X = st->uv = st->h_in = nullptr; st->cap_N = 0;
-        CHIP_HIP(c, hipMalloc(&st->X, sizeof(double) * 5 * (size_t)N));
-        CHIP_HIP(c, hipHostMalloc(&st->h_in, sizeof(double) * 5 * (size_t)N, hipHostMallocDefault));
-        CHIP_HIP(c, hipHostGetDevicePointer((void **)&st->d_hin, st->h_in, 0));
-        st->cap_N = N;
-    }
-    if (H > st->cap_H || words > st->cap_words) {
-        const int nh = H > st->cap_H ? H : st->cap_H, nw = words > st->cap_words ? words : st->cap_words;
-        (void)hipFree(st->Sg); (void)hipFree(st->Tg); (void)hipFree(st->sample); (void)hipFree(st->ok);
-        (void)hipHostFree(st->h_cost); (void)hipHostFree(st->h_T); (void)hipHostFree(st->h_nin); (void)hipHostFree(st->h_valid);
-        (void)hipHostFree(st->h_nsol); (void)hipHostFree(st->h_mask); (void)hipHostFree(st->h_sample_in);
-        st->h_sample_in = nullptr;
-        st->Sg = st->Tg = nullptr; st->sample = st->ok = nullptr;
-        st->h_cost = st->h_T = nullptr; st->h_nin = st->h_valid = st->h_nsol = nullptr; st->h_mask = nullptr;
-        st->cap_H = st->cap_words = 0;
-        CHIP_HIP(c, hipMalloc(&st->Sg, sizeof(double) * 729 * (size_t)nh));
-        CHIP_HIP(c, hipMalloc(&st->Tg, sizeof(double) * 27 * (size_t)nh));
-        CHIP_HIP(c, hipMalloc(&st->sample, sizeof(int32_t) * kSampleMax * (size_t)nh));
-        CHIP_HIP(c, hipMalloc(&st->ok, sizeof(int32_t) * (size_t)nh));
-        CHIP_HIP(c, hipHostMalloc(&st->h_cost, sizeof(double) * (size_t)nh, hipHostMallocDefault));
-        CHIP_HIP(c, hipHostMalloc(&st->h_T, sizeof(double) * 16 * (size_t)nh, hipHostMallocDefault));
-        CHIP_HIP(c, hipHostMalloc(&st->h_nin, sizeof(int32_t) * (size_t)nh, hipHostMallocDefault));
-        CHIP_HIP(c, hipHostMalloc(&st->h_valid, sizeof(int32_t) * (size_t)nh, hipHostMallocDefault));
-        CHIP_HIP(c, hipHostMalloc(&st->h_nsol, sizeof(int32_t) * (size_t)nh, hipHostMallocDefault));
-        CHIP_HIP(c, hipHostMalloc(&st->h_mask, sizeof(unsigned long long) * (size_t)nh * nw, hipHostMallocDefault));
-        CHIP_HIP(c, hipHostMalloc(&st->h_sample_in, sizeof(int32_t) * kSampleMax * (size_t)nh, hipHostMallocDefault));
-        CHIP_HIP(c, hipHostGetDevicePointer((void **)&st->d_sample_in, st->h_sample_in, 0));
-        CHIP_HIP(c, hipHostGetDevicePointer((void **)&st->cost, st->h_cost, 0));
-        CHIP_HIP(c, hipHostGetDevicePointer((void **)&st->T_out, st->h_T, 0));
-        CHIP_HIP(c, hipHostGetDevicePointer((void **)&st->nin, st->h_nin, 0));
-        CHIP_HIP(c, hipHostGetDevicePointer((void **)&st->valid, st->h_valid, 0));
-        CHIP_HIP(c, hipHostGetDevicePointer((void **)&st->nsol, st->h_nsol, 0));
-        CHIP_HIP(c, hipHostGetDevicePointer((void **)&st->mask, st->h_mask, 0));
-        st->cap_H = nh; st->cap_words = nw;
-    }
-    (void)P;
-    return CHIP_OK;
+    const size_t nN = 5 * (size_t)N, nH = (size_t)H;
+    // One pause over the whole group.  hipFree waits for the whole device: not with a resident scan instance on it, and none launched by the
+    // tick thread until the last allocation below is done (at 10 Hz the lease never runs out, the frees would wait for as long as
+    // ticks keep coming)
+    ResidentPause paused(c, nN > st->X.capacity() || nH > st->ok.capacity() || !st->res.fits(H, words));
+    int rc = st->X.reserve(c, nN);
+    if (rc == CHIP_OK) rc = st->h_in.reserve(c, nN);
+    if (rc == CHIP_OK) rc = st->Sg.reserve(c, 729 * nH);
+    if (rc == CHIP_OK) rc = st->Tg.reserve(c, 27 * nH);
+    if (rc == CHIP_OK) rc = st->sample.reserve(c, kSampleMax * nH);
+    if (rc == CHIP_OK) rc = st->ok.reserve(c, nH);
+    if (rc == CHIP_OK) rc = st->res.reserve(c, H, words);
+    if (rc == CHIP_OK) rc = st->nsol.reserve(c, nH);
+    return rc;
 }
 
 // Up to kPnpMaxBatch problems in one pair of launches; problem i's outputs are exactly those of a single-problem call.
@@ -2438,7 +2387,7 @@ static int pnp_run(Ctx *c, PnpState *st, int P, const double *const *X, const do
     const int H = ransac_initial_iterations(p);
     int Ntot = 0, words = 0;
     for (int i = 0; i < P; i++) { Ntot += N[i]; const int w = (N[i] + 63) / 64; words = w > words ? w : words; }
-    int rc = pnp_reserve(c, st, Ntot, P * H, words, P);
+    int rc = pnp_reserve(c, st, Ntot, P * H, words);
     if (rc != CHIP_OK) return rc;
     hipStream_t s = c->s_pnp;
 
@@ -2446,7 +2395,7 @@ static int pnp_run(Ctx *c, PnpState *st, int P, const double *const *X, const do
     EigArgs ea;
     std::memset(&sa, 0, sizeof sa);
     std::memset(&ea, 0, sizeof ea);
-    st->uv = st->X + 3 * (size_t)Ntot;
+    double *const X_dev = st->X, *const uv_dev = X_dev + 3 * (size_t)Ntot, *const in_host = st->h_in.host(), *const in_hostdev = st->h_in.dev();
     for (int i = 0, off = 0; i < P; off += N[i], i++) {
         PnpProblem pr;
         pr.N = N[i]; pr.pad_ = 0;
@@ -2456,32 +2405,32 @@ static int pnp_run(Ctx *c, PnpState *st, int P, const double *const *X, const do
             ea.prob[i] = sa.prob[i] = pr;
             continue;
         }
-        std::memcpy(st->h_in + 3 * (size_t)off, X[i], sizeof(double) * 3 * (size_t)N[i]);
-        std::memcpy(st->h_in + 3 * (size_t)Ntot + 2 * (size_t)off, uv[i], sizeof(double) * 2 * (size_t)N[i]);
-        pr.X = st->X + 3 * (size_t)off; pr.uv = st->uv + 2 * (size_t)off;
+        std::memcpy(in_host + 3 * (size_t)off, X[i], sizeof(double) * 3 * (size_t)N[i]);
+        std::memcpy(in_host + 3 * (size_t)Ntot + 2 * (size_t)off, uv[i], sizeof(double) * 2 * (size_t)N[i]);
+        pr.X = X_dev + 3 * (size_t)off; pr.uv = uv_dev + 2 * (size_t)off;
         ea.prob[i] = pr;                                   // pnp_eig_score: the device copy (made by pnp_build_solve)
-        pr.X = st->d_hin + 3 * (size_t)off; pr.uv = st->d_hin + 3 * (size_t)Ntot + 2 * (size_t)off;
+        pr.X = in_hostdev + 3 * (size_t)off; pr.uv = in_hostdev + 3 * (size_t)Ntot + 2 * (size_t)off;
         sa.prob[i] = pr;                                   // pnp_build_solve: the pinned host buffer, in place
     }
     // no H2D copy: see SolveArgs
     if (ht.on) ht1 = ht_now();
     if (p->sampler == CHIP_SAMPLER_THEIA_PERSISTENT) {   // one persistent permutation per problem, hypotheses 0..H-1 in order
         for (int i = 0; i < P; i++) {
-            st->perm.resize((size_t)N[i]);
-            ransac_sample_table_persistent(seeds ? seeds[i] : p->seed, H, N[i], S, kSampleMax, st->perm.data(), st->h_sample_in + (size_t)i * H * kSampleMax);
+            st->res.perm.resize((size_t)N[i]);
+            ransac_sample_table_persistent(seeds ? seeds[i] : p->seed, H, N[i], S, kSampleMax, st->res.perm.data(), st->res.sample_in.host() + (size_t)i * H * kSampleMax);
         }
-        sa.sample_in = st->d_sample_in;
+        sa.sample_in = st->res.sample_in.dev();
     }
     sa.H = H; sa.S = S; sa.tab = st->tab_dev;
     sa.Sg = st->Sg; sa.Tg = st->Tg; sa.sample = st->sample; sa.ok = st->ok;
-    sa.in_host = dev_in ? nullptr : st->d_hin; sa.in_dev = st->X; sa.n_in = 5 * (int64_t)Ntot;
+    sa.in_host = dev_in ? nullptr : in_hostdev; sa.in_dev = X_dev; sa.n_in = 5 * (int64_t)Ntot;
     const size_t lds = kSolveLds;
     static const bool want_stamps = std::getenv("CHIP_PNP_STAMPS") != nullptr;
     if (want_stamps) {
         if (st->stamps_n < P * H) {
-            (void)hipFree(st->stamps);
-            st->stamps = nullptr; st->stamps_n = 0;
-            CHIP_HIP(c, hipMalloc(&st->stamps, sizeof(unsigned long long) * 32 * (size_t)P * H));
+            st->stamps_n = 0;
+            rc = st->stamps.reserve(c, 32 * (size_t)P * H);
+            if (rc != CHIP_OK) return rc;
             st->stamps_n = P * H;
         }
         CHIP_HIP(c, hipMemsetAsync(st->stamps, 0, sizeof(unsigned long long) * 32 * (size_t)st->stamps_n, s));
@@ -2503,7 +2452,8 @@ static int pnp_run(Ctx *c, PnpState *st, int P, const double *const *X, const do
         ea.backsub_loop = loop_form;
     }
 #endif
-    ea.T_out = st->T_out; ea.cost = st->cost; ea.nin = st->nin; ea.valid = st->valid; ea.nsol = st->nsol; ea.mask = st->mask;
+    ea.T_out = st->res.T.dev(); ea.cost = st->res.cost.dev(); ea.nin = st->res.nin.dev(); ea.valid = st->res.valid.dev(); ea.nsol = st->nsol.dev();
+    ea.mask = st->res.mask.dev();
     if (want_stamps) ea.stamps = st->stamps;
     // One launch pair for the whole batch.  Splitting it so that pnp_build_solve of one group runs underneath pnp_eig_score of another
     // cannot pay: the two kernels share a CU's register file -- four resident eigen waves (4 x 128 rows) leave room for ONE
@@ -2518,39 +2468,10 @@ static int pnp_run(Ctx *c, PnpState *st, int P, const double *const *X, const do
     CHIP_HIP(c, hipStreamSynchronize(s));   // every per-hypothesis result is in host memory now
     if (ht.on) ht3 = ht_now();
 
-    // K7: theia::Ransac::Estimate's sequential rule replayed over the per-hypothesis results
-    int32_t best_h[kPnpMaxBatch], num_it[kPnpMaxBatch], n_models[kPnpMaxBatch];
-    double best_cost[kPnpMaxBatch];
-    for (int i = 0; i < P; i++) {
-        best_cost[i] = DBL_MAX; n_models[i] = 0; num_it[i] = 0;
-        const size_t o = (size_t)i * H;
-        best_h[i] = ransac_select(p, N[i], H, st->h_valid + o, st->h_cost + o, st->h_nin + o, &num_it[i], &n_models[i], &best_cost[i]);
-    }
-    for (int i = 0; i < P; i++) {
-        double *T = T_colmajor + 16 * (size_t)i;
-        uint8_t *im = inlier_mask ? inlier_mask[i] : nullptr;
-        int32_t nin = 0;
-        if (best_h[i] >= 0) {
-            std::memcpy(T, st->h_T + 16 * ((size_t)i * H + best_h[i]), sizeof(double) * 16);
-            nin = st->h_nin[(size_t)i * H + best_h[i]];
-            const unsigned long long *hm = st->h_mask + ((size_t)i * H + best_h[i]) * words;
-            if (im)
-                for (int k = 0; k < N[i]; k++) im[k] = (uint8_t)((hm[k >> 6] >> (k & 63)) & 1ull);
-            const double ratio = (double)nin / (double)N[i];
-            confidence[i] = (float)(1.0 - std::pow(1.0 - std::pow(ratio, (double)S), (double)num_it[i]));  // summary.confidence (:240)
-        } else {
-            for (int k = 0; k < 16; k++) T[k] = NAN;   // reference: uninitialised Matrix4d (:204); caller NaN-checks
-            if (im) std::memset(im, 0, (size_t)N[i]);
-            confidence[i] = 0.0f;
-        }
-        if (summary) {
-            summary[i].n_iterations = num_it[i];
-            summary[i].n_inliers = nin;
-            summary[i].best_hypothesis = best_h[i];
-            summary[i].n_models = n_models[i];
-            summary[i].best_cost = best_h[i] >= 0 ? best_cost[i] : INFINITY;
-        }
-    }
+    // K7: theia::Ransac::Estimate's sequential rule replayed over the per-hypothesis results, problem by problem
+    for (int i = 0; i < P; i++)
+        ransac_report(p, N[i], H, words, st->res, (size_t)i * H, T_colmajor + 16 * (size_t)i, confidence + i, inlier_mask ? inlier_mask[i] : nullptr,
+                      summary ? summary + i : nullptr);
     if (ht.on) { const double t4 = ht_now(); ht.acc[0] += ht1 - ht0; ht.acc[1] += ht2 - ht1; ht.acc[2] += ht3 - ht2; ht.acc[3] += t4 - ht3; ht.acc[4] += t4 - ht0; ht.n++; }
     return CHIP_OK;
 }
@@ -2558,13 +2479,11 @@ static int pnp_run(Ctx *c, PnpState *st, int P, const double *const *X, const do
 int pnp_ransac_device(Ctx *c, const double *X_dev, const double *uv_dev, int32_t N, const chip_ransac_params *p, double *T_colmajor,
                       float *confidence, uint8_t *inlier_mask, chip_ransac_summary *summary)
 {
-    if (N < 20) return CHIP_ERR_TOO_FEW_POINTS;  // DlsPnpWithRansac.cpp:136-139
-    const int32_t S = p->sample_size;
-    if (S < 3 || S > kSampleMax || S > N || p->n_hypotheses < 0 || p->max_iterations < 1) return CHIP_ERR_UNSUPPORTED;
-    if (p->sampler != CHIP_SAMPLER_FRESH && p->sampler != CHIP_SAMPLER_THEIA_PERSISTENT) return CHIP_ERR_UNSUPPORTED;
+    const int rc = ransac_check_params(p, N);
+    if (rc != CHIP_OK) return rc;
     std::lock_guard<std::mutex> lk(c->pnp_mu);
     CHIP_HIP(c, hipSetDevice(c->device));
-    PnpState *st = static_cast<PnpState *>(c->pnp_state);
+    PnpState *st = c->pnp_state;
     if (!st) return CHIP_ERR_INVALID_ARG;
     uint8_t *masks[1] = {inlier_mask};
     return pnp_run(c, st, 1, &X_dev, &uv_dev, &N, p, nullptr, T_colmajor, confidence, masks, summary, true);
@@ -2580,7 +2499,7 @@ extern "C" int chip_debug_pnp_stamps(chip_ctx *c, unsigned long long *out, int32
     if (!c || !out) return CHIP_ERR_INVALID_ARG;
     if (c->group) c = static_cast<chip_ctx *>(chip::group_root(c));
     std::lock_guard<std::mutex> lk(c->pnp_mu);
-    PnpState *st = static_cast<PnpState *>(c->pnp_state);
+    PnpState *st = c->pnp_state;
     if (!st || !st->stamps || n_hyp > st->stamps_n) return CHIP_ERR_INVALID_ARG;
     CHIP_HIP(c, hipSetDevice(c->device));
     CHIP_HIP(c, hipStreamSynchronize(c->s_pnp));
@@ -2593,7 +2512,7 @@ extern "C" int chip_debug_pnp_solve_stamps(chip_ctx *c, unsigned long long *out,
     if (!c || !out) return CHIP_ERR_INVALID_ARG;
     if (c->group) c = static_cast<chip_ctx *>(chip::group_root(c));
     std::lock_guard<std::mutex> lk(c->pnp_mu);
-    PnpState *st = static_cast<PnpState *>(c->pnp_state);
+    PnpState *st = c->pnp_state;
     if (!st || !st->stamps || n_hyp > st->stamps_n) return CHIP_ERR_INVALID_ARG;
     CHIP_HIP(c, hipSetDevice(c->device));
     CHIP_HIP(c, hipStreamSynchronize(c->s_pnp));
@@ -2607,17 +2526,14 @@ extern "C" int chip_pnp_ransac_batch(chip_ctx *c, int32_t P, const double *const
 {
     if (!c || P < 0 || (P > 0 && (!X || !uv || !N)) || !p || !T_colmajor || !confidence) return CHIP_ERR_INVALID_ARG;
     if (c->group) c = static_cast<chip_ctx *>(chip::group_root(c));   // 1k x 512 is far too small to shard: devices[0] (SURVEY 8e "replicas only")
-    const int32_t S = p->sample_size;
     for (int i = 0; i < P; i++) {
         if (!X[i] || !uv[i]) return CHIP_ERR_INVALID_ARG;
-        if (N[i] < 20) return CHIP_ERR_TOO_FEW_POINTS;  // DlsPnpWithRansac.cpp:136-139
-        if (S > N[i]) return CHIP_ERR_UNSUPPORTED;
+        const int rc = ransac_check_params(p, N[i]);
+        if (rc != CHIP_OK) return rc;
     }
-    if (S < 3 || S > kSampleMax || p->n_hypotheses < 0 || p->max_iterations < 1) return CHIP_ERR_UNSUPPORTED;
-    if (p->sampler != CHIP_SAMPLER_FRESH && p->sampler != CHIP_SAMPLER_THEIA_PERSISTENT) return CHIP_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> lk(c->pnp_mu);
     CHIP_HIP(c, hipSetDevice(c->device));
-    PnpState *st = static_cast<PnpState *>(c->pnp_state);
+    PnpState *st = c->pnp_state;
     if (!st) return CHIP_ERR_INVALID_ARG;
     for (int i0 = 0; i0 < P; i0 += kPnpMaxBatch) {
         const int n = P - i0 < kPnpMaxBatch ? P - i0 : kPnpMaxBatch;

@@ -1,9 +1,11 @@
 // ransac_common.h -- pieces shared by the batched RANSAC legs (pnp.hip, icp.hip): the counter-based RNG + sampler
-// (device) and theia::Ransac's sequential selection rule replayed on the host (K7).
+// (device) and the host side of a call: parameter check, the per-hypothesis result block, theia::Ransac's sequential selection
+// rule replayed on the host (K7) and the report of its winner.
 #pragma once
 #include "chip_internal.h"
 #include <cfloat>
 #include <cmath>
+#include <cstring>
 
 namespace chip {
 
@@ -124,6 +126,74 @@ inline int32_t ransac_select(const chip_ransac_params *p, int32_t N, int32_t H, 
     *n_models_out = n_models;
     *best_cost_out = best_cost;
     return best_h;
+}
+
+// What both entry points refuse, in the order they report it (the callers check their pointers first)
+inline int ransac_check_params(const chip_ransac_params *p, int32_t N)
+{
+    if (N < 20) return CHIP_ERR_TOO_FEW_POINTS;  // DlsPnpWithRansac.cpp:136-139 (PnP) / :19-22 (ICP)
+    const int32_t S = p->sample_size;
+    if (S < 3 || S > kSampleMax || S > N || p->n_hypotheses < 0 || p->max_iterations < 1) return CHIP_ERR_UNSUPPORTED;
+    if (p->sampler != CHIP_SAMPLER_FRESH && p->sampler != CHIP_SAMPLER_THEIA_PERSISTENT) return CHIP_ERR_UNSUPPORTED;
+    return CHIP_OK;
+}
+
+// Per-hypothesis results live in pinned, device-mapped HOST memory: the scoring kernel stores them straight across PCIe (a few
+// hundred KB per call, posted while the kernel runs), so a call needs no D2H copy and a single stream synchronisation.
+struct RansacResults {
+    PinnedBuf<double> cost, T;                 // [H], [H][16]
+    PinnedBuf<int32_t> nin, valid;             // [H]
+    PinnedBuf<unsigned long long> mask;        // [H][words]
+    PinnedBuf<int32_t> sample_in;              // CHIP_SAMPLER_THEIA_PERSISTENT: the host-sequenced sample table [H][kSampleMax] ...
+    std::vector<int32_t> perm;                 // ... and the permutation it is sequenced on
+    int32_t cap_H = 0, cap_words = 0;
+    bool fits(int H, int words) const { return H <= cap_H && words <= cap_words; }
+    int reserve(Ctx *c, int H, int words)      // H and words never shrink; the caller holds one ResidentPause over its whole group
+    {
+        if (fits(H, words)) return CHIP_OK;
+        const size_t nh = (size_t)(H > cap_H ? H : cap_H), nw = (size_t)(words > cap_words ? words : cap_words);
+        cap_H = cap_words = 0;
+        int rc = cost.reserve(c, nh);
+        if (rc == CHIP_OK) rc = T.reserve(c, 16 * nh);
+        if (rc == CHIP_OK) rc = nin.reserve(c, nh);
+        if (rc == CHIP_OK) rc = valid.reserve(c, nh);
+        if (rc == CHIP_OK) rc = mask.reserve(c, nh * nw);
+        if (rc == CHIP_OK) rc = sample_in.reserve(c, kSampleMax * nh);
+        if (rc != CHIP_OK) return rc;
+        cap_H = (int32_t)nh; cap_words = (int32_t)nw;
+        return CHIP_OK;
+    }
+};
+
+// The end of a call: ransac_select over hypotheses [first_hyp, first_hyp + H) of r (rows of `words` mask words), then the winner's
+// pose, inlier mask and confidence -- or, without one, the reference's uninitialised Matrix4d as 16 NaNs (the caller NaN-checks).
+inline void ransac_report(const chip_ransac_params *p, int32_t N, int H, int words, const RansacResults &r, size_t first_hyp,
+                          double *T_colmajor, float *confidence, uint8_t *inlier_mask, chip_ransac_summary *summary)
+{
+    double best_cost = DBL_MAX;
+    int32_t n_models = 0, num_it = 0, nin = 0;
+    const int32_t best_h = ransac_select(p, N, H, r.valid.host() + first_hyp, r.cost.host() + first_hyp, r.nin.host() + first_hyp, &num_it, &n_models, &best_cost);
+    if (best_h >= 0) {
+        const size_t h = first_hyp + (size_t)best_h;
+        std::memcpy(T_colmajor, r.T.host() + 16 * h, sizeof(double) * 16);
+        nin = r.nin.host()[h];
+        const unsigned long long *hm = r.mask.host() + h * (size_t)words;
+        if (inlier_mask)
+            for (int i = 0; i < N; i++) inlier_mask[i] = (uint8_t)((hm[i >> 6] >> (i & 63)) & 1ull);
+        const double ratio = (double)nin / (double)N;
+        *confidence = (float)(1.0 - std::pow(1.0 - std::pow(ratio, (double)p->sample_size), (double)num_it));  // summary.confidence (DlsPnpWithRansac.cpp:240 / :121)
+    } else {
+        for (int i = 0; i < 16; i++) T_colmajor[i] = NAN;
+        if (inlier_mask) std::memset(inlier_mask, 0, (size_t)N);
+        *confidence = 0.0f;
+    }
+    if (summary) {
+        summary->n_iterations = num_it;
+        summary->n_inliers = nin;
+        summary->best_hypothesis = best_h;
+        summary->n_models = n_models;
+        summary->best_cost = best_h >= 0 ? best_cost : INFINITY;
+    }
 }
 
 }  // namespace chip

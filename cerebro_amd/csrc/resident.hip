@@ -82,11 +82,7 @@ static uint32_t resident_next_number(Ctx *c)
 void resident_destroy(Ctx *c)
 {
     if (c->res.stream) { (void)hipStreamDestroy(c->res.stream); c->res.stream = nullptr; }
-    if (c->res.pinned) { (void)hipHostFree(c->res.pinned); c->res.pinned = nullptr; }
-    if (c->res.cmd_vram) { (void)hipFree(c->res.cmd_vram); c->res.cmd_vram = nullptr; }
-    if (c->res.cmd_dev) { (void)hipFree(c->res.cmd_dev); c->res.cmd_dev = nullptr; }
-    if (c->res.partial) { (void)hipFree(c->res.partial); c->res.partial = nullptr; }
-    if (c->res.ticket) { (void)hipFree(c->res.ticket); c->res.ticket = nullptr; }
+    c->res.pinned.release(); c->res.cmd_vram.release(); c->res.cmd_dev.release(); c->res.partial.release(); c->res.ticket.release();
     c->res.cmd_host = nullptr; c->res.cmd_hostdev = nullptr; c->res.exit_host = nullptr; c->res.exit_hostdev = nullptr;
     c->res.cmd_in_vram = false; c->res.direct = false;
     c->res.ready = false;
@@ -124,16 +120,15 @@ static int resident_alloc_body(Ctx *c)
     int pr_lo = 0, pr_hi = 0;
     CHIP_HIP(c, hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi));
     CHIP_HIP(c, hipStreamCreateWithPriority(&c->res.stream, hipStreamNonBlocking, pr_hi));
-    void *h = nullptr;
-    CHIP_HIP(c, hipHostMalloc(&h, 128, hipHostMallocDefault));   // the command line + the line of the exit word
+    // (alloc, not reserve, throughout: Resident::mu is held and a pause would take it again)
+    int rc = c->res.pinned.alloc(c, 128);   // the command line + the line of the exit word
+    if (rc != CHIP_OK) return rc;
+    char *h = c->res.pinned.host(), *hd = c->res.pinned.dev();
     std::memset(h, 0, 128);
-    c->res.pinned = h;
-    c->res.cmd_host = static_cast<ResidentCmd *>(h);
-    c->res.exit_host = reinterpret_cast<unsigned long long *>(static_cast<char *>(h) + 64);
-    void *hd = nullptr;
-    CHIP_HIP(c, hipHostGetDevicePointer(&hd, h, 0));
-    c->res.cmd_hostdev = static_cast<uint32_t *>(hd);
-    c->res.exit_hostdev = reinterpret_cast<unsigned long long *>(static_cast<char *>(hd) + 64);
+    c->res.cmd_host = reinterpret_cast<ResidentCmd *>(h);
+    c->res.exit_host = reinterpret_cast<unsigned long long *>(h + 64);
+    c->res.cmd_hostdev = reinterpret_cast<uint32_t *>(hd);
+    c->res.exit_hostdev = reinterpret_cast<unsigned long long *>(hd + 64);
     // Where the command line lives.  With a large PCIe BAR the host can store straight into device memory, and a posted write that the
     // device then finds locally beats a line the device has to fetch over PCIe (ping-pong with one polling wave: 1.89 us against 2.52,
     // scripts/probes/bar_pingpong.hip).  Used when the device says so AND a pattern written that way into THE buffer itself reads back
@@ -142,37 +137,36 @@ static int resident_alloc_body(Ctx *c)
     // CHIP_RESIDENT_BAR=2 (the default) goes one step further: the host writes EVERY workgroup's line that way (16 KiB per command,
     // 0.6 us of host time) and nobody relays: 10k rows 35.9-36.4 -> 34.7-35.0 us.  1: only workgroup 0's line, relayed on the device.
     c->res.grid = resident_grid(c);
-    CHIP_HIP(c, hipMalloc((void **)&c->res.cmd_dev, (size_t)c->max_grid * 64));
+    rc = c->res.cmd_dev.alloc(c, (size_t)c->max_grid * 16);
+    if (rc != CHIP_OK) return rc;
     CHIP_HIP(c, hipMemset(c->res.cmd_dev, 0, (size_t)c->max_grid * 64));
     const int bar_mode = env_int("CHIP_RESIDENT_BAR", 2);
     int large_bar = 0;
     if (bar_mode != 0 && hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, c->device) == hipSuccess && large_bar) {
         if (bar_mode == 2) {
             // the workgroups' lines themselves are the host's target (line 0 is workgroup 0's): probe the first and the last line of them
-            if (bar_write_probe(c->res.cmd_dev) && bar_write_probe(reinterpret_cast<char *>(c->res.cmd_dev) + (size_t)(c->max_grid - 1) * 64)) {
+            if (bar_write_probe(c->res.cmd_dev.get()) && bar_write_probe(c->res.cmd_dev + (size_t)(c->max_grid - 1) * 16)) {
                 c->res.cmd_in_vram = true;
                 c->res.direct = true;
-                c->res.cmd_host = reinterpret_cast<ResidentCmd *>(c->res.cmd_dev);
+                c->res.cmd_host = reinterpret_cast<ResidentCmd *>(c->res.cmd_dev.get());
                 c->res.cmd_hostdev = c->res.cmd_dev;
             }
         }
         if (!c->res.direct) {                   // mode 1, or mode 2 whose lines are not host-writable: one line of its own, relayed on the device
-            void *v = nullptr;
-            if (hipMalloc(&v, 64) == hipSuccess) {
-                if (bar_write_probe(v)) {
-                    c->res.cmd_vram = v;
+            if (c->res.cmd_vram.alloc(c, 64) == CHIP_OK) {
+                if (bar_write_probe(c->res.cmd_vram.get())) {
                     c->res.cmd_in_vram = true;
-                    c->res.cmd_host = static_cast<ResidentCmd *>(v);
-                    c->res.cmd_hostdev = static_cast<uint32_t *>(v);
+                    c->res.cmd_host = reinterpret_cast<ResidentCmd *>(c->res.cmd_vram.get());
+                    c->res.cmd_hostdev = reinterpret_cast<uint32_t *>(c->res.cmd_vram.get());
                 } else {
-                    (void)hipFree(v);
+                    c->res.cmd_vram.release();
                 }
             }
         }
     }
-    CHIP_HIP(c, hipMalloc((void **)&c->res.partial, (size_t)c->max_grid * CHIP_MAX_NQ * CHIP_MAX_TOPK * sizeof(chip_topk_entry)));
-    CHIP_HIP(c, hipMalloc((void **)&c->res.ticket, 64));
-    return CHIP_OK;
+    rc = c->res.partial.alloc(c, (size_t)c->max_grid * CHIP_MAX_NQ * CHIP_MAX_TOPK);
+    if (rc == CHIP_OK) rc = c->res.ticket.alloc(c, 16);
+    return rc;
 }
 
 // Resident::mu held.  Either everything exists afterwards (ready, published last) or nothing does and the mode is off for this ctx: the
@@ -293,7 +287,7 @@ int resident_tick_enqueue(Ctx *c, int64_t k, int64_t l, const chip_dot_params *p
     cmd.n_rows = k;
     cmd.tick_l = l;
     cmd.thresh = p->thresh;
-    cmd.result = (uint64_t)(uintptr_t)s.dev;
+    cmd.result = (uint64_t)(uintptr_t)s.rec.dev();
     cmd.seq_ptr = (uint64_t)(uintptr_t)s.seq_dev;
     cmd.seq_val = s.seq_want;
     // rows claimed within the workgroup: beyond cache-sized prefixes, as for launches (29k rows: 92.3 -> 91.7 us; neutral at 10k)

@@ -58,6 +58,7 @@ CHIP_COMM_ID_BYTES = 128
 CHIP_EXCHANGE_NONE, CHIP_EXCHANGE_RCCL, CHIP_EXCHANGE_COPY = 0, 1, 2
 CHIP_SCAN_FORM_ONE_ROW, CHIP_SCAN_FORM_ROWS = 1, 2
 CHIP_SAMPLER_FRESH, CHIP_SAMPLER_THEIA_PERSISTENT = 0, 1
+CHIP_RANSAC_LEG_PNP, CHIP_RANSAC_LEG_ICP = 0, 1
 CHIP_SCAN_FAMILY_NONE, CHIP_SCAN_FAMILY_ONE_ROW, CHIP_SCAN_FAMILY_WIDE, CHIP_SCAN_FAMILY_ROWS, CHIP_SCAN_FAMILY_MULTI = 0, 1, 2, 3, 4
 CHIP_SCAN_CALL_QUERY, CHIP_SCAN_CALL_TICK, CHIP_SCAN_CALL_TICK_SYNC = 0, 1, 2
 SCAN_FAMILY_NAMES = {0: "none", 1: "one_row", 2: "wide", 3: "rows", 4: "multi"}
@@ -133,6 +134,11 @@ class ScanLaunch(C.Structure):
         return d
 
 
+class RansacShape(C.Structure):
+    """chip_debug_ransac_shape: the launch a per-hypothesis record belongs to (test aid)"""
+    _fields_ = [(n, C.c_int32) for n in ("P", "H", "N", "words", "S", "sampler")]
+
+
 class Info(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("D", C.c_int32), ("device", C.c_int32), ("shard_rank", C.c_int32),
                 ("shard_count", C.c_int32), ("n_cus", C.c_int32), ("rows_global", C.c_int64),
@@ -191,6 +197,9 @@ _SIGS = {
                                   C.POINTER(RansacSummary)]),
     "chip_icp_ransac_enqueue": (C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(RansacParams)]),
     "chip_icp_ransac_collect": (C.c_int, [_P, _P, C.POINTER(C.c_float), _P, C.POINTER(RansacSummary)]),
+    "chip_debug_ransac_record": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(RansacShape), _P, _P, _P, _P, _P, _P, _P]),
+    "chip_debug_pnp_stage": (C.c_int, [_P, C.c_int32, _P, _P, _P]),
+    "chip_debug_pnp_keep_stage": (C.c_int, [_P, C.c_int32]),
     "chip_build_has_match": (C.c_int, []),
     "chip_build_has_tick_coalesce": (C.c_int, []),
     "chip_debug_coalesce_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -621,6 +630,39 @@ class Chip:
         return dict(status=st, confidence=float(conf.value), T=T.reshape(4, 4).T.copy(), mask=mask[:N].copy(),
                     summary=dict(n_iterations=summ.n_iterations, n_inliers=summ.n_inliers,
                                  best_hypothesis=summ.best_hypothesis, n_models=summ.n_models, best_cost=summ.best_cost))
+
+    # -- test aids: every hypothesis of the last estimation
+    def ransac_record(self, leg: int = CHIP_RANSAC_LEG_PNP, problem: int = 0) -> dict:
+        """chip_debug_ransac_record: the record of every hypothesis of the last PnP launch (problem `problem` of it) or of the last collected
+        ICP estimation: P, H, N, words, S, sampler and valid[H], cost[H], nin[H], T[H, 16] (column-major), mask[H, words] (uint64);
+        PnP also nsol[H] and sample[H, S].  Rejected hypotheses: T = NaN, mask row 0."""
+        sh = self.ransac_record_shape(leg, problem)
+        H, W, S = sh["H"], sh["words"], sh["S"]
+        r = dict(valid=np.empty(H, np.int32), cost=np.empty(H, np.float64), nin=np.empty(H, np.int32), T=np.empty((H, 16), np.float64),
+                 mask=np.empty((H, W), np.uint64))
+        if leg == CHIP_RANSAC_LEG_PNP:
+            r.update(nsol=np.empty(H, np.int32), sample=np.empty((H, S), np.int32))
+        ptrs = [_ptr(r[k]) if k in r else None for k in ("valid", "cost", "nin", "T", "mask", "nsol", "sample")]
+        self._chk(self.lib.chip_debug_ransac_record(self.h, leg, problem, None, *ptrs), "chip_debug_ransac_record")
+        r.update(sh)
+        return r
+
+    def pnp_stage(self, problem: int = 0) -> dict:
+        """chip_debug_pnp_stage: what pnp_build_solve handed to pnp_eig_score in the last PnP launch: ok[H], Tg[H, 27], Sg[H, 27, 27] (NaN
+        where ok is 0; exactly what the first kernel wrote only for launches made under pnp_keep_stage(True))"""
+        H = self.ransac_record_shape(CHIP_RANSAC_LEG_PNP, problem)["H"]
+        r = dict(ok=np.empty(H, np.int32), Tg=np.empty((H, 27), np.float64), Sg=np.empty((H, 27, 27), np.float64))
+        self._chk(self.lib.chip_debug_pnp_stage(self.h, problem, _ptr(r["ok"]), _ptr(r["Tg"]), _ptr(r["Sg"])), "chip_debug_pnp_stage")
+        return r
+
+    def ransac_record_shape(self, leg: int = CHIP_RANSAC_LEG_PNP, problem: int = 0) -> dict:
+        sh = RansacShape()
+        self._chk(self.lib.chip_debug_ransac_record(self.h, leg, problem, C.byref(sh), *([None] * 7)), "chip_debug_ransac_record")
+        return {k: int(getattr(sh, k)) for k, _ in RansacShape._fields_}
+
+    def pnp_keep_stage(self, on: bool = True):
+        """while on, a PnP launch copies the action matrices aside between its two kernels (pnp_stage()'s Sg)"""
+        self._chk(self.lib.chip_debug_pnp_keep_stage(self.h, 1 if on else 0), "chip_debug_pnp_keep_stage")
 
     # -- candidate verification front end (ORB matching, GMS, correspondence sets)
     def orb_match(self, d1: np.ndarray, d2: np.ndarray):

@@ -548,6 +548,9 @@ int pnp_ransac_device(Ctx *c, const double *X_dev, const double *uv_dev, int32_t
                       float *confidence, uint8_t *inlier_mask, chip_ransac_summary *summary);
 int icp_ransac_device(Ctx *c, const double *A_dev, const double *B_dev, int32_t N, const chip_ransac_params *p, double *T_colmajor,
                       float *confidence, uint8_t *inlier_mask, chip_ransac_summary *summary);
+// chip_debug_ransac_record's ICP leg (icp.hip; the PnP leg lives with its state in pnp.hip): c is a plain ctx, every output may be null
+int icp_debug_record(Ctx *c, chip_debug_ransac_shape *shape, int32_t *valid, double *cost, int32_t *nin, double *T_colmajor,
+                     unsigned long long *mask);
 
 }  // namespace chip
 

@@ -242,6 +242,7 @@ struct IcpState {
     RansacResults res;                 // what icp_score leaves per hypothesis (as in pnp.hip: no D2H copies, one sync per call)
     hipStream_t stream = nullptr;      // the ICP stream (not the PnP stream: the two estimations may overlap)
     bool pending = false;              // an enqueued estimation awaits chip_icp_ransac_collect
+    bool collected = false;            // pend_* and res describe a finished estimation (test aid: chip_debug_ransac_record)
     int32_t pend_N = 0, pend_H = 0;
     chip_ransac_params pend_params{};
 };
@@ -293,6 +294,7 @@ static int icp_enqueue_locked(Ctx *c, const double *A, const double *B, int32_t 
     }
     IcpState *st = c->icp_state;
     if (st->pending) return CHIP_ERR_BUSY;
+    st->collected = false;
     if (!st->stream) CHIP_HIP(c, hipStreamCreateWithFlags(&st->stream, hipStreamNonBlocking));
     const int32_t S = p->sample_size;
     const int H = ransac_initial_iterations(p);
@@ -335,6 +337,7 @@ static int icp_collect_locked(Ctx *c, double T_colmajor[16], float *confidence, 
     CHIP_HIP(c, hipSetDevice(c->device));
     CHIP_HIP(c, hipStreamSynchronize(st->stream));
     st->pending = false;
+    st->collected = true;
     ransac_report(&st->pend_params, st->pend_N, st->pend_H, (st->pend_N + 63) / 64, st->res, 0, T_colmajor, confidence, inlier_mask, summary);
     return CHIP_OK;
 }
@@ -374,6 +377,21 @@ extern "C" int chip_icp_ransac(chip_ctx *c, const double *A, const double *B, in
     rc = icp_enqueue_locked(c, A, B, N, p);
     if (rc != CHIP_OK) return rc;
     return icp_collect_locked(c, T_colmajor, confidence, inlier_mask, summary);
+}
+
+// Test aid (cerebro_hip.h chip_debug_ransac_record, ICP leg): every hypothesis of the last collected estimation
+int chip::icp_debug_record(Ctx *c, chip_debug_ransac_shape *shape, int32_t *valid, double *cost, int32_t *nin, double *T_colmajor,
+                           unsigned long long *mask)
+{
+    std::lock_guard<std::mutex> lk(c->icp_mu);
+    IcpState *st = c->icp_state;
+    if (!st || st->pending || !st->collected) return CHIP_ERR_BUSY;
+    CHIP_HIP(c, hipSetDevice(c->device));
+    CHIP_HIP(c, hipStreamSynchronize(st->stream));
+    const int words = (st->pend_N + 63) / 64;
+    if (shape) { shape->P = 1; shape->H = st->pend_H; shape->N = st->pend_N; shape->words = words; shape->S = st->pend_params.sample_size; shape->sampler = st->pend_params.sampler; }
+    ransac_record_copy(st->res, 0, st->pend_H, words, st->pend_N, valid, cost, nin, T_colmajor, mask);
+    return CHIP_OK;
 }
 
 // chip_icp_ransac on sets that already are in device memory (match.hip): no staging copy, otherwise the same call

@@ -2319,6 +2319,10 @@ struct PnpState {
     PinnedBuf<int32_t> nsol;              // ... and its solution count
     DevBuf<unsigned long long> stamps;    // tuning only (CHIP_PNP_STAMPS): [H][8] of pnp_eig_score, then [H][16] of pnp_build_solve
     int32_t stamps_n = 0;
+    // test aids (chip_debug_ransac_record / chip_debug_pnp_stage): the shape of the most recent finished launch, P == 0: none
+    struct Last { int32_t P = 0, H = 0, S = 0, words = 0, sampler = 0, N[kPnpMaxBatch] = {}; bool kept = false; } last;
+    bool keep_stage = false;              // chip_debug_pnp_keep_stage: a launch copies Sg aside between its two kernels
+    DevBuf<double> Sg_kept;
 };
 
 int pnp_create(Ctx *c)
@@ -2365,6 +2369,7 @@ static int pnp_reserve(Ctx *c, PnpState *st, int N, int H, int words)
     if (rc == CHIP_OK) rc = st->ok.reserve(c, nH);
     if (rc == CHIP_OK) rc = st->res.reserve(c, H, words);
     if (rc == CHIP_OK) rc = st->nsol.reserve(c, nH);
+    if (rc == CHIP_OK && st->keep_stage) rc = st->Sg_kept.reserve(c, 729 * nH);
     return rc;
 }
 
@@ -2387,6 +2392,7 @@ static int pnp_run(Ctx *c, PnpState *st, int P, const double *const *X, const do
     const int H = ransac_initial_iterations(p);
     int Ntot = 0, words = 0;
     for (int i = 0; i < P; i++) { Ntot += N[i]; const int w = (N[i] + 63) / 64; words = w > words ? w : words; }
+    st->last.P = 0;
     int rc = pnp_reserve(c, st, Ntot, P * H, words);
     if (rc != CHIP_OK) return rc;
     hipStream_t s = c->s_pnp;
@@ -2461,6 +2467,7 @@ static int pnp_run(Ctx *c, PnpState *st, int P, const double *const *X, const do
     if (want_stamps) hipLaunchKernelGGL(pnp_build_solve<true>, dim3(P * H), dim3(kSolveThreads), lds, s, sa);
     else hipLaunchKernelGGL(pnp_build_solve<false>, dim3(P * H), dim3(kSolveThreads), lds, s, sa);
     CHIP_HIP(c, hipGetLastError());
+    if (st->keep_stage) CHIP_HIP(c, hipMemcpyAsync(st->Sg_kept, st->Sg, sizeof(double) * 729 * (size_t)P * H, hipMemcpyDeviceToDevice, s));
     if (want_stamps) hipLaunchKernelGGL(pnp_eig_score<true>, dim3(P * H), dim3(64), 0, s, ea);
     else hipLaunchKernelGGL(pnp_eig_score<false>, dim3(P * H), dim3(64), 0, s, ea);
     CHIP_HIP(c, hipGetLastError());
@@ -2472,6 +2479,8 @@ static int pnp_run(Ctx *c, PnpState *st, int P, const double *const *X, const do
     for (int i = 0; i < P; i++)
         ransac_report(p, N[i], H, words, st->res, (size_t)i * H, T_colmajor + 16 * (size_t)i, confidence + i, inlier_mask ? inlier_mask[i] : nullptr,
                       summary ? summary + i : nullptr);
+    st->last.P = P; st->last.H = H; st->last.S = S; st->last.words = words; st->last.sampler = p->sampler; st->last.kept = st->keep_stage;
+    for (int i = 0; i < P; i++) st->last.N[i] = N[i];
     if (ht.on) { const double t4 = ht_now(); ht.acc[0] += ht1 - ht0; ht.acc[1] += ht2 - ht1; ht.acc[2] += ht3 - ht2; ht.acc[3] += t4 - ht3; ht.acc[4] += t4 - ht0; ht.n++; }
     return CHIP_OK;
 }
@@ -2517,6 +2526,79 @@ extern "C" int chip_debug_pnp_solve_stamps(chip_ctx *c, unsigned long long *out,
     CHIP_HIP(c, hipSetDevice(c->device));
     CHIP_HIP(c, hipStreamSynchronize(c->s_pnp));
     CHIP_HIP(c, hipMemcpy(out, st->stamps + 8 * (size_t)st->stamps_n, sizeof(unsigned long long) * 24 * (size_t)n_hyp, hipMemcpyDeviceToHost));
+    return CHIP_OK;
+}
+
+// Test aids (cerebro_hip.h): the per-hypothesis record of the last launch, and what its first kernel handed to the second
+static int pnp_debug_last(chip_ctx *c, int32_t problem, PnpState **st_out)   // pnp_mu held
+{
+    PnpState *st = c->pnp_state;
+    if (!st || st->last.P == 0) return CHIP_ERR_BUSY;
+    if (problem < 0 || problem >= st->last.P) return CHIP_ERR_INVALID_ARG;
+    CHIP_HIP(c, hipSetDevice(c->device));
+    CHIP_HIP(c, hipStreamSynchronize(c->s_pnp));
+    *st_out = st;
+    return CHIP_OK;
+}
+
+extern "C" int chip_debug_ransac_record(chip_ctx *c, int32_t leg, int32_t problem, chip_debug_ransac_shape *shape, int32_t *valid,
+                                        double *cost, int32_t *nin, double *T_colmajor, uint64_t *mask, int32_t *nsol, int32_t *sample)
+{
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "mask words");
+    if (!c || (leg != CHIP_RANSAC_LEG_PNP && leg != CHIP_RANSAC_LEG_ICP)) return CHIP_ERR_INVALID_ARG;
+    if (c->group) c = static_cast<chip_ctx *>(chip::group_root(c));
+    if (leg == CHIP_RANSAC_LEG_ICP) {
+        if (problem != 0 || nsol || sample) return CHIP_ERR_INVALID_ARG;
+        return icp_debug_record(c, shape, valid, cost, nin, T_colmajor, reinterpret_cast<unsigned long long *>(mask));
+    }
+    std::lock_guard<std::mutex> lk(c->pnp_mu);
+    PnpState *st = nullptr;
+    const int rc = pnp_debug_last(c, problem, &st);
+    if (rc != CHIP_OK) return rc;
+    const PnpState::Last &l = st->last;
+    const size_t first = (size_t)problem * l.H;
+    if (shape) { shape->P = l.P; shape->H = l.H; shape->N = l.N[problem]; shape->words = l.words; shape->S = l.S; shape->sampler = l.sampler; }
+    ransac_record_copy(st->res, first, l.H, l.words, l.N[problem], valid, cost, nin, T_colmajor, reinterpret_cast<unsigned long long *>(mask));
+    if (nsol) std::memcpy(nsol, st->nsol.host() + first, sizeof(int32_t) * (size_t)l.H);
+    if (sample) {   // the device's table has kSampleMax columns
+        std::vector<int32_t> tmp((size_t)l.H * kSampleMax);
+        CHIP_HIP(c, hipMemcpy(tmp.data(), st->sample + first * kSampleMax, sizeof(int32_t) * tmp.size(), hipMemcpyDeviceToHost));
+        for (int h = 0; h < l.H; h++)
+            for (int i = 0; i < l.S; i++) sample[(size_t)h * l.S + i] = tmp[(size_t)h * kSampleMax + i];
+    }
+    return CHIP_OK;
+}
+
+extern "C" int chip_debug_pnp_stage(chip_ctx *c, int32_t problem, int32_t *ok, double *Tg, double *Sg)
+{
+    if (!c) return CHIP_ERR_INVALID_ARG;
+    if (c->group) c = static_cast<chip_ctx *>(chip::group_root(c));
+    std::lock_guard<std::mutex> lk(c->pnp_mu);
+    PnpState *st = nullptr;
+    const int rc = pnp_debug_last(c, problem, &st);
+    if (rc != CHIP_OK) return rc;
+    const size_t H = (size_t)st->last.H, first = (size_t)problem * H;
+    std::vector<int32_t> okv(H);
+    CHIP_HIP(c, hipMemcpy(okv.data(), st->ok + first, sizeof(int32_t) * H, hipMemcpyDeviceToHost));
+    if (ok) std::memcpy(ok, okv.data(), sizeof(int32_t) * H);
+    if (Tg) CHIP_HIP(c, hipMemcpy(Tg, st->Tg + 27 * first, sizeof(double) * 27 * H, hipMemcpyDeviceToHost));
+    if (Sg) {
+        const double *src = st->last.kept ? st->Sg_kept : st->Sg;
+        CHIP_HIP(c, hipMemcpy(Sg, src + 729 * first, sizeof(double) * 729 * H, hipMemcpyDeviceToHost));
+        for (size_t h = 0; h < H; h++)   // pnp_build_solve leaves the slot of a singular system as it was
+            if (!okv[h])
+                for (int e = 0; e < 729; e++) Sg[729 * h + e] = NAN;
+    }
+    return CHIP_OK;
+}
+
+extern "C" int chip_debug_pnp_keep_stage(chip_ctx *c, int32_t on)
+{
+    if (!c) return CHIP_ERR_INVALID_ARG;
+    if (c->group) c = static_cast<chip_ctx *>(chip::group_root(c));
+    std::lock_guard<std::mutex> lk(c->pnp_mu);
+    if (!c->pnp_state) return CHIP_ERR_INVALID_ARG;
+    c->pnp_state->keep_stage = on != 0;
     return CHIP_OK;
 }
 

@@ -1,6 +1,6 @@
 // ransac_common.h -- pieces shared by the batched RANSAC legs (pnp.hip, icp.hip): the counter-based RNG + sampler
 // (device) and the host side of a call: parameter check, the per-hypothesis result block, theia::Ransac's sequential selection
-// rule replayed on the host (K7) and the report of its winner.
+// rule replayed on the host (K7), the report of its winner and the copy-out of the whole block (test aid).
 #pragma once
 #include "chip_internal.h"
 #include <cfloat>
@@ -193,6 +193,27 @@ inline void ransac_report(const chip_ransac_params *p, int32_t N, int H, int wor
         summary->best_hypothesis = best_h;
         summary->n_models = n_models;
         summary->best_cost = best_h >= 0 ? best_cost : INFINITY;
+    }
+}
+
+// Test aid (chip_debug_ransac_record): hypotheses [first_hyp, first_hyp + H) of r, rows of `words` mask words, as a copy with defined
+// content everywhere.  The kernels write neither T nor the mask row of a rejected hypothesis, nor the mask words beyond a problem's own
+// ceil(N / 64) (a batched launch gives every row the stride of its widest problem): those slots hold what an earlier call left there.
+// The copy has T = NaN and mask = 0 in them, so that whole arrays can be compared.  Every output may be null.
+inline void ransac_record_copy(const RansacResults &r, size_t first_hyp, int H, int words, int32_t N, int32_t *valid, double *cost,
+                               int32_t *nin, double *T, unsigned long long *mask)
+{
+    const int32_t *v = r.valid.host() + first_hyp;
+    if (valid) std::memcpy(valid, v, sizeof(int32_t) * (size_t)H);
+    if (cost) std::memcpy(cost, r.cost.host() + first_hyp, sizeof(double) * (size_t)H);
+    if (nin) std::memcpy(nin, r.nin.host() + first_hyp, sizeof(int32_t) * (size_t)H);
+    const int own = (N + 63) / 64;
+    for (int h = 0; h < H; h++) {
+        if (T)
+            for (int e = 0; e < 16; e++) T[16 * (size_t)h + e] = v[h] ? r.T.host()[16 * (first_hyp + h) + e] : (double)NAN;
+        if (mask)
+            for (int w = 0; w < words; w++)
+                mask[(size_t)h * words + w] = (v[h] && w < own) ? r.mask.host()[(first_hyp + h) * (size_t)words + w] : 0ull;
     }
 }
 

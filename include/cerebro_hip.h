@@ -359,7 +359,8 @@ typedef struct {
     int32_t max_iterations;      /* 50     :210 */
     int32_t min_iterations;      /* 5      :211 */
     int32_t use_mle;             /* 1      :212 */
-    int32_t sample_size;         /* 15     DlsPnpWithRansac.h:45 */
+    int32_t sample_size;         /* 15     DlsPnpWithRansac.h:45; 3 .. 16 and <= N accepted (else CHIP_ERR_UNSUPPORTED), each value
+                                    held to the oracle hypothesis by hypothesis for PnP and ICP */
     double  failure_probability; /* 0.01   theia::RansacParameters default */
     uint64_t seed;               /* counter-based sampler seed (Theia's is time-seeded => nondeterministic) */
     int32_t n_hypotheses;        /* 0 = adaptive reference mode */
@@ -414,6 +415,44 @@ int chip_icp_ransac(chip_ctx *ctx, const double *A, const double *B, int32_t N, 
 int chip_icp_ransac_enqueue(chip_ctx *ctx, const double *A, const double *B, int32_t N, const chip_ransac_params *p);
 int chip_icp_ransac_collect(chip_ctx *ctx, double T_colmajor[16], float *confidence, uint8_t *inlier_mask /* may be NULL */,
                             chip_ransac_summary *summary /* may be NULL */);
+
+/* Test aids (ABI 7, additive): the record of EVERY hypothesis of the most recent estimation of a ctx, not only of its winner.
+ * Both kernel pairs leave valid / cost / inlier count / pose / inlier mask per hypothesis (and the selection rule is replayed over
+ * them on the host); these calls copy that out.  They read what a finished call left behind: they take the estimation's lock, wait
+ * for the leg's stream, change nothing and launch nothing.  tests/test_ransac_hypotheses_gpu.py holds every row to the oracle.
+ *   chip_debug_ransac_record  leg CHIP_RANSAC_LEG_PNP: problem `problem` of the last LAUNCH of chip_pnp_ransac / _batch / _matched
+ *                             (a batch of more than 8 problems runs as several launches of up to 8; the record is that of the last
+ *                             launch, its problems numbered from 0); leg CHIP_RANSAC_LEG_ICP: the last collected chip_icp_ransac /
+ *                             _collect / _matched (problem 0).  *shape first (it sizes the arrays), then any of
+ *                               valid[H], cost[H], nin[H], T[H][16] column-major, mask[H][words] (bit i & 63 of word i >> 6 = point i),
+ *                               PnP only: nsol[H] (cheirality-valid solutions; -1 singular system, -2 eigenvalue iteration gave up),
+ *                                         sample[H][S] (the sampler's indices as pnp_build_solve used them).
+ *                             Every output may be NULL.  The content is defined everywhere: a rejected hypothesis (valid 0) has cost
+ *                             +inf, nin 0, T = NaN and an all-zero mask row -- the kernels do not write T or the mask of such a
+ *                             hypothesis, nor the mask words beyond a problem's own ceil(N / 64) in a batch whose rows have the
+ *                             stride of its widest problem; the copy is filled here, on the host.  In the adaptive mode
+ *                             (n_hypotheses == 0) H is the initial iteration count: the rows after summary.n_iterations are there too.
+ *   chip_debug_pnp_stage      what pnp_build_solve handed to pnp_eig_score in that launch, copied from device memory:
+ *                             ok[H] (0: singular elimination), Tg[H][27] (t = Tg * vec(R)), Sg[H][27][27] (the action matrix; NaN
+ *                             where ok is 0).  The rare loop form of the back-substitution in pnp_eig_score uses a hypothesis's Sg
+ *                             slot as scratch, so Sg is what pnp_build_solve wrote only for launches made while
+ *   chip_debug_pnp_keep_stage is on: the launch then copies Sg aside between the two kernels (device to device, off by default).
+ * CHIP_ERR_BUSY: no finished estimation on that leg (none yet, the last one failed, or an ICP enqueue awaits its collect);
+ * CHIP_ERR_INVALID_ARG: unknown leg, problem outside the launch, nsol / sample asked of the ICP leg.  Group ctxs: devices[0].      */
+#define CHIP_RANSAC_LEG_PNP 0
+#define CHIP_RANSAC_LEG_ICP 1
+typedef struct {
+    int32_t P;       /* problems of the launch                                             */
+    int32_t H;       /* hypotheses per problem                                             */
+    int32_t N;       /* correspondences of this problem                                    */
+    int32_t words;   /* mask words per row: ceil(N / 64) of the launch's widest problem    */
+    int32_t S;       /* sample size                                                        */
+    int32_t sampler; /* CHIP_SAMPLER_*                                                     */
+} chip_debug_ransac_shape;
+int chip_debug_ransac_record(chip_ctx *ctx, int32_t leg, int32_t problem, chip_debug_ransac_shape *shape, int32_t *valid, double *cost,
+                             int32_t *nin, double *T_colmajor, uint64_t *mask, int32_t *nsol, int32_t *sample);
+int chip_debug_pnp_stage(chip_ctx *ctx, int32_t problem, int32_t *ok, double *Tg, double *Sg);
+int chip_debug_pnp_keep_stage(chip_ctx *ctx, int32_t on);
 
 
 /* ------------------------------------------------------------------------------------------ candidate verification front end

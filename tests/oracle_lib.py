@@ -322,6 +322,8 @@ def _bind_pnp():
     lib.orc_dls_pnp.argtypes = [V, V, C.c_int32, V, V, V, C.c_int32]
     lib.orc_pnp_hypothesis.restype = C.c_int
     lib.orc_pnp_hypothesis.argtypes = [V, V, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, V, V]
+    lib.orc_pnp_hypothesis_sampled.restype = C.c_int
+    lib.orc_pnp_hypothesis_sampled.argtypes = [V, V, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, V, V]
     lib.orc_ransac_params_default.argtypes = [C.POINTER(OrcRansacParams)]
     lib.orc_ransac_max_iterations.restype = C.c_int32
     lib.orc_ransac_max_iterations.argtypes = [C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32]
@@ -398,6 +400,16 @@ def pnp_hypothesis(X, uv, seed, hyp, S=15):
     return ok, T.reshape(4, 4).T.copy(), smp
 
 
+def pnp_hypothesis_sampled(X, uv, seed, hyp, sample=None, S=15):
+    """the hypothesis of a GIVEN sample (a row of ransac_sample_persistent); sample=None: ransac_sample(seed, hyp)"""
+    X = np.ascontiguousarray(X, dtype=np.float64); uv = np.ascontiguousarray(uv, dtype=np.float64)
+    T = np.full(16, np.nan)
+    if sample is not None:
+        sample = np.ascontiguousarray(sample, dtype=np.int32); S = sample.size
+    ok = _bind_pnp().orc_pnp_hypothesis_sampled(_p(X), _p(uv), X.shape[0], seed, hyp, S, None if sample is None else _p(sample), _p(T))
+    return ok, T.reshape(4, 4).T.copy()
+
+
 def score_model(T, X, uv, thresh=0.03, use_mle=1):
     X = np.ascontiguousarray(X, dtype=np.float64); uv = np.ascontiguousarray(uv, dtype=np.float64)
     Tc = np.ascontiguousarray(np.asarray(T, dtype=np.float64).T.reshape(16))  # column-major
@@ -439,6 +451,9 @@ def _bind_icp():
     lib.orc_icp_error.argtypes = [V, V, V]
     lib.orc_icp_hypothesis.restype = C.c_int
     lib.orc_icp_hypothesis.argtypes = [V, V, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, V, C.POINTER(C.c_double)]
+    lib.orc_icp_hypothesis_sampled.restype = C.c_int
+    lib.orc_icp_hypothesis_sampled.argtypes = [V, V, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, V, V, C.POINTER(C.c_double)]
+    lib.orc_icp_score_model.argtypes = [V, V, V, C.c_int32, C.c_double, C.c_int32, V, V, V]
     lib.orc_icp_params_default.argtypes = [C.POINTER(OrcRansacParams)]
     lib.orc_icp_ransac.restype = C.c_int
     lib.orc_icp_ransac.argtypes = [V, V, C.c_int32, C.POINTER(OrcRansacParams), V, C.POINTER(C.c_float), V, C.POINTER(OrcRansacSummary)]
@@ -466,6 +481,25 @@ def icp_hypothesis(A, B, seed, hyp, S=10):
     T = np.empty(16); s = C.c_double()
     ok = _bind_icp().orc_icp_hypothesis(_p(A), _p(B), A.shape[0], seed, hyp, S, _p(T), C.byref(s))
     return ok, T.reshape(4, 4).T.copy(), s.value
+
+
+def icp_hypothesis_sampled(A, B, seed, hyp, sample=None, S=10):
+    """the hypothesis of a GIVEN sample (a row of ransac_sample_persistent); sample=None: ransac_sample(seed, hyp); scale is NaN
+    where Umeyama itself gives up (the gate is never reached)"""
+    A = np.ascontiguousarray(A, dtype=np.float64); B = np.ascontiguousarray(B, dtype=np.float64)
+    T = np.full(16, np.nan); s = C.c_double(np.nan)
+    if sample is not None:
+        sample = np.ascontiguousarray(sample, dtype=np.int32); S = sample.size
+    ok = _bind_icp().orc_icp_hypothesis_sampled(_p(A), _p(B), A.shape[0], seed, hyp, S, None if sample is None else _p(sample), _p(T), C.byref(s))
+    return ok, T.reshape(4, 4).T.copy(), s.value
+
+
+def icp_score_model(T, A, B, thresh=0.1, use_mle=1):
+    A = np.ascontiguousarray(A, dtype=np.float64); B = np.ascontiguousarray(B, dtype=np.float64)
+    Tc = np.ascontiguousarray(np.asarray(T, dtype=np.float64).T.reshape(16))  # column-major
+    cost = C.c_double(); nin = C.c_int32(); mask = np.zeros(A.shape[0], dtype=np.uint8)
+    _bind_icp().orc_icp_score_model(_p(Tc), _p(A), _p(B), A.shape[0], thresh, use_mle, C.byref(cost), C.byref(nin), _p(mask))
+    return cost.value, nin.value, mask
 
 
 def icp_ransac(A, B, params: OrcRansacParams | None = None):

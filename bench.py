@@ -5,7 +5,10 @@ A "step" is one tick of Cerebro::descrip_N__dot__descrip_0_N (src/Cerebro.cpp:95
 descriptors (rows l-1, l-2, l-3) against the DB prefix [0, l-50), top-k, accept rule -- on the workload
 BASELINE.json's metric is quoted on: synthetic 4096-D fp32 descriptors x 1M keyframes.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
+  A plain run does what the headline needs and nothing else: fill the DB, W warm-up ticks, K timed ticks, one JSON line.  --full adds
+  every other figure, each from work of its own outside the timed ticks: the hipEvent pass that prices `roofline` per launch, the
+  `sizes` / `shapes` / `paced_10hz` / `resident_tick` / `pnp` / `icp` / `batch` legs and the CPU baselines (about a minute more).
   N > 1 (torchrun, one rank per GPU): the 1M-row DB is row-sharded round-robin over the N GPUs (BASELINE
   config 4, strong scaling); each tick = local scan -> RCCL all-gather of 3 x top-k (score,index) per rank
   -> merge + decision on every rank.  The collective lives INSIDE libcerebro_hip.so (chip_comm_init_rank +
@@ -14,11 +17,11 @@ BASELINE.json's metric is quoted on: synthetic 4096-D fp32 descriptors x 1M keyf
   N > 1 WITHOUT torchrun (--gpus N, WORLD_SIZE unset): ONE process drives the N GPUs through chip_create_multi
   (the reference's process shape: one thread of one process, cerebro_node.cpp:499).
 
-Prints ONE JSON line (rank 0).  `value` = ticks/s with the DB resident in HBM.  `roofline` prices the
+Prints ONE JSON line (rank 0).  `value` = ticks/s with the DB resident in HBM.  With --full, `roofline` prices the
 dominant kernel (db_scan_topk) by its ALGORITHMIC bytes (4*D*rows scanned per launch) over its
-mean duration measured with hipEvents on the kernel's own stream (chip_profile_*).  `cpu_baseline` times the
+mean duration measured with hipEvents on the kernel's own stream (chip_profile_*), and `cpu_baseline` times the
 oracle's reference-faithful fp64 path (three separate GEMVs, single thread like the reference's
-dot_product_th) on a bounded sample.
+dot_product_th) on a bounded sample.  Without it no launch is timed and `roofline` says so: achieved, frac and traffic are null.
 
   --dump-outputs DIR: after the timed steps, the record the LAST timed tick returned to its caller (capi.TickResult) is written
   as DIR/tick_<field>.npy, one float64 array per field.  The DB, the planted revisits and the tick positions come from fixed
@@ -724,6 +727,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="outside the timed steps, also measure everything that is not the headline (per-launch roofline pass, size / shape / paced / "
+                         "resident / PnP / ICP / many-query legs, CPU baselines); the options below that skip or size a leg only matter with it")
     ap.add_argument("--rows", type=int, default=1_000_000, help="DB rows scanned per tick (k)")
     ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU baseline work (0 = skip)")
     ap.add_argument("--cpu-sample", type=int, default=20000, help="columns in the CPU baseline sample")
@@ -761,7 +767,7 @@ def main():
     # 69.6 us for a launched tick at 10 Hz where the standalone tool on an otherwise idle box reads 52 us, and blamed the bench
     # process's held contexts.  Running it here, and again once every context exists (after_contexts), measures that blame.
     paced_first = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.gpus == 1 and not args.no_sizes and not args.force_sharded and not args.force_group \
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.gpus == 1 and not args.no_sizes and not args.force_sharded and not args.force_group \
             and args.storage == "f32" and args.paced_ticks > 0 and args.rows >= 1_000_000:
         paced_first = paced_tick_leg(10_000, n=args.paced_ticks)
 
@@ -806,7 +812,8 @@ def main():
     n_ticks = args.warmup + args.steps
     # the 10k / 100k legs (N = 1) tick over shorter prefixes of the same DB: their planted query rows are DB rows of the
     # longer scans, so the longer plans keep their revisited rows out of those windows
-    # (29k rows = the reference's own capacity, Cerebro.cpp:946)
+    # (29k rows = the reference's own capacity, Cerebro.cpp:946).  The legs' rows are planted whether or not the legs run (--full):
+    # a plain run and a --full run tick over the same database.
     leg_rows = [r for r in (10_000, 29_000, 100_000) if r + 4000 < args.rows] if int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.gpus == 1 \
         and not args.no_sizes and not args.force_sharded and not args.force_group else []
     windows = [(r, r + LAG + 3 * 260 + 3) for r in leg_rows]
@@ -1045,17 +1052,18 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
 
-    # Roofline pass (outside the timed region): the same launches again with hipEvents bracketing every db_scan_topk
-    # launch on the stream it runs on.  Kept out of the throughput loop because each timing event is a barrier packet
-    # between back-to-back scans (~5 us each).
-    n_prof = min(args.steps, 30)
-    chip.loop_reset()
-    chip.profile_enable(True)
-    chip.profile_reset()
-    run(ls[args.warmup:args.warmup + n_prof])
-    barrier()
-    scan_ms, n_launch, bytes_last, span_ms = chip.profile_scan()
-    chip.profile_enable(False)
+    if args.full:
+        # Roofline pass (outside the timed region): the same launches again with hipEvents bracketing every db_scan_topk
+        # launch on the stream it runs on.  Kept out of the throughput loop because each timing event is a barrier packet
+        # between back-to-back scans (~5 us each).
+        n_prof = min(args.steps, 30)
+        chip.loop_reset()
+        chip.profile_enable(True)
+        chip.profile_reset()
+        run(ls[args.warmup:args.warmup + n_prof])
+        barrier()
+        scan_ms, n_launch, bytes_last, span_ms = chip.profile_scan()
+        chip.profile_enable(False)
 
     assert len(results) == args.steps
     check_results(results, expect[args.warmup:])
@@ -1074,17 +1082,31 @@ def main():
         shards = 1 if replicated else n_gpus
         local_rows = (args.rows + shards - 1) // shards
         alg_bytes = 4.0 * D * local_rows                       # one pass of the prefix as fp32 (this GPU's share), whatever the storage type
-        avg_s = scan_ms / 1e3 / max(1, n_launch)              # per-launch duration (what rocprofv3 --stats reports)
-        achieved = alg_bytes / avg_s / 1e9 if avg_s > 0 else 0.0
-        traffic = traffic_source = None
-        pj = ROOT / "profiles" / "scan_traffic.json"
-        # the committed PMC measurement is of the headline launch (4096-D x 1M fp32 rows on one GPU); other shapes report null
-        if pj.exists() and D == 4096 and args.rows == 1_000_000 and n_gpus == 1 and args.storage == "f32":
-            try:
-                traffic = json.loads(pj.read_text()).get("hbm_bytes_per_launch")
-                traffic_source = "profiles/scan_traffic.json (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE of this launch shape, separate run; not re-measured in this run)"
-            except Exception:
-                traffic = None
+        if args.full:
+            avg_s = scan_ms / 1e3 / max(1, n_launch)              # per-launch duration (what rocprofv3 --stats reports)
+            achieved = alg_bytes / avg_s / 1e9 if avg_s > 0 else 0.0
+            traffic = traffic_source = None
+            pj = ROOT / "profiles" / "scan_traffic.json"
+            # the committed PMC measurement is of the headline launch (4096-D x 1M fp32 rows on one GPU); other shapes report null
+            if pj.exists() and D == 4096 and args.rows == 1_000_000 and n_gpus == 1 and args.storage == "f32":
+                try:
+                    traffic = json.loads(pj.read_text()).get("hbm_bytes_per_launch")
+                    traffic_source = "profiles/scan_traffic.json (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE of this launch shape, separate run; not re-measured in this run)"
+                except Exception:
+                    traffic = None
+            roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+                        "kernel": "db_scan_topk", "avg_kernel_ms": avg_s * 1e3, "launches": n_launch,
+                        "measured": "hipEvents around each launch on the kernel's stream, separate pass of the same ticks",
+                        "algorithmic_bytes_per_launch": alg_bytes,
+                        "pure_read_ceiling": {"value": READ_CEILING_GBS, "unit": "GB/s", "frac_of_it": achieved / READ_CEILING_GBS,
+                                              "source": "profiles/r02_hbm_read_probe.txt: do-nothing reader in the scan's access shape, on another MI355X"}}
+        else:
+            # No launch was timed, and ms_per_step cannot stand in for one: pipelined ticks share passes over the DB (tick coalescing),
+            # so 4*D*rows per STEP would price bytes that were never read.
+            roofline = {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None, "traffic": None,
+                        "kernel": "db_scan_topk", "algorithmic_bytes_per_launch": alg_bytes,
+                        "measured": "not in this run: the per-launch figures come from a hipEvent pass of its own (--full)"}
         out = {
             "metric": f"loop-queries/sec (ticks of 3 descriptors vs {D}-D x {fmt_rows(args.rows)} DB)",   # same string at every N; PnP-RANSAC hypotheses/sec: see "pnp" (N = 1)
             "value": (world if replicated else 1) * args.steps / elapsed,   # replicas each run `steps` ticks of their own
@@ -1123,15 +1145,9 @@ def main():
                         "descriptor_queries_per_s": 3 * args.steps / elapsed,
                         "preflight": os.environ.get("BENCH_PREFLIGHT"),   # scripts/preflight_8gpu.sh: verdict of the tests that span the node's devices, run before this line
                         "db_fill_s": t_fill, "arch": info["arch"], "n_cus": info["n_cus"]}),
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         "kernel": "db_scan_topk", "avg_kernel_ms": avg_s * 1e3, "launches": n_launch,
-                         "measured": "hipEvents around each launch on the kernel's stream, separate pass of the same ticks",
-                         "algorithmic_bytes_per_launch": alg_bytes,
-                         "pure_read_ceiling": {"value": READ_CEILING_GBS, "unit": "GB/s", "frac_of_it": achieved / READ_CEILING_GBS,
-                                               "source": "profiles/r02_hbm_read_probe.txt: do-nothing reader in the scan's access shape, another box of the pool"}},
+            "roofline": roofline,
         }
-        if size_plans:
+        if args.full and size_plans:
             out["sizes"] = {fmt_rows(r): size_leg(chip, r, plan, params, args.inflight) for r, plan in sorted(size_plans.items())}
             out["sizes"][fmt_rows(args.rows)] = {"db_rows": args.rows, "value": out["value"], "unit": "loop-queries/s", "ms_per_step": out["ms_per_step"],
                                                  "steps": args.steps,
@@ -1153,19 +1169,19 @@ def main():
                                          "while this bench process holds its contexts (DB, tick streams, PnP / ICP / batch buffers); `spin` = the caller "
                                          "busy-waits through the 100 ms instead of sleeping (same GPU idle time, host core awake): the difference to the "
                                          "slept figures is the waking host, what remains above the back-to-back tick is the idle hardware queue"}
-        if size_plans and single and args.storage == "f32" and (capi.load_library().chip_build_scan_forms() & 2):
+        if args.full and size_plans and single and args.storage == "f32" and (capi.load_library().chip_build_scan_forms() & 2):
             # the opt-in resident scan instance at the two sizes of the reference's operating range (ctxs of their own, a few hundred ms)
             out["resident_tick"] = {fmt_rows(r): resident_leg(r) for r in (10_000, 29_000)}
-        if size_plans and single and args.storage == "f32" and D == 4096 and args.rows >= 1_000_000 and not args.no_shapes:
+        if args.full and size_plans and single and args.storage == "f32" and D == 4096 and args.rows >= 1_000_000 and not args.no_shapes:
             # the reference's two production shapes, each on a ctx of its own
             out["shapes"] = {shape_name(29_000, 8192): shape_leg(29_000, 8192, "f32", args.inflight),
                              shape_name(1_000_000, 4096, "f64"): shape_leg(1_000_000, 4096, "f64", args.inflight, n_ticks=60)}
-        if single and not args.no_pnp:
+        if args.full and single and not args.no_pnp:
             out["pnp"] = pnp_leg(chip, min(args.cpu_budget, 5.0))
             out["icp"] = icp_leg(chip)
-        if single and not args.no_batch and args.storage == "f32":
+        if args.full and single and not args.no_batch and args.storage == "f32":
             out["batch"] = batch_leg(chip, args.rows)
-        if n_gpus == 1 and world == 1 and args.cpu_budget > 0:
+        if args.full and n_gpus == 1 and world == 1 and args.cpu_budget > 0:
             eig = eigen_baseline(args.cpu_sample, min(args.cpu_budget, 10.0))
             cols_per_s, n, dt = cpu_baseline(args.cpu_sample, args.cpu_budget * 2 / 3, "eigen")
             if eig is not None:   # the reference's own Eigen statements, on this host

@@ -29,7 +29,7 @@ def test_bench_under_torchrun(n, extra, hook):
         port = s.getsockname()[1]
     env = dict(os.environ, BENCH_DIST_BACKEND="gloo", **hook)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", str(n), "--steps", "24", "--warmup", "4", "--rows", "60000"] + extra
+           "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", str(n), "--steps", "24", "--warmup", "4", "--rows", "60000", "--full"] + extra
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -47,8 +47,9 @@ def test_bench_under_torchrun(n, extra, hook):
     assert "cpu_baseline" not in j and "pnp" not in j          # rank 0 at N = 1 only
 
 
-def _run_single(args):
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "24", "--warmup", "4", "--cpu-budget", "0", "--no-pnp", "--no-batch"] + args,
+def _run_single(args, full=True):
+    """--full: the per-launch roofline pass and the size legs run too (no CPU baselines, no PnP / ICP / many-query leg)."""
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "24", "--warmup", "4"] + (["--full", "--cpu-budget", "0", "--no-pnp", "--no-batch"] if full else []) + args,
                        cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -106,6 +107,32 @@ def test_bench_sizes_key_and_f64_storage():
     assert j["roofline"]["traffic"] is None and "ms_per_step_median" not in j
     j64 = _run_single(["--rows", "60000", "--storage", "f64", "--no-sizes"])
     assert "fp64 rows" in j64["config"]["storage"] and j64["roofline"]["algorithmic_bytes_per_launch"] == 4.0 * 4096 * 60000
+
+
+def test_bench_plain_run_is_the_headline_alone_over_the_same_db(tmp_path):
+    """Without --full the run fills the DB, warms up, times its steps and prints the line: no leg, no baseline, no pass of its own for
+    the roofline (its per-launch figures are null and say why).  The size legs' rows are planted all the same, so the timed ticks see
+    the database of a --full run: both dump the same record, file for file."""
+    import numpy as np
+    j = _run_single(["--rows", "200000", "--dump-outputs", str(tmp_path / "plain")], full=False)
+    assert not set(j) & {"sizes", "shapes", "paced_10hz", "resident_tick", "pnp", "icp", "batch", "eigen_probe", "roofline_context",
+                         "cpu_baseline", "cpu_baseline_eigen", "cpu_baseline_chain", "cpu_baseline_all_cores"}, sorted(j)
+    assert j["metric"] == "loop-queries/sec (ticks of 3 descriptors vs 4096-D x 200k DB)" and j["unit"] == "loop-queries/s"
+    assert j["higher_is_better"] is True and j["dtype"] == "f64" and j["n_gpus"] == 1 and j["steps"] == 24 and j["warmup"] == 4
+    assert j["value"] > 0 and abs(j["value"] * j["ms_per_step"] - 1e3) < 1e-6
+    r = j["roofline"]
+    assert list(r)[:6] == ["bound", "achieved", "peak", "unit", "frac", "traffic"] and r["achieved"] is None and r["frac"] is None and r["traffic"] is None
+    assert "--full" in r["measured"] and not any(k.startswith(("achieved_", "frac_", "avg_")) for k in r)     # no launch timed, none priced
+    assert j["config"]["exchange"] == "none" and list(j["config"])[0] == "workload" and j["details"]["rccl_ranks"] == 0
+    jf = _run_single(["--rows", "200000", "--dump-outputs", str(tmp_path / "full")])
+    assert "sizes" in jf and jf["roofline"]["achieved"] > 0
+    for k in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "scaling", "data"):
+        assert j[k] == jf[k], k
+    names = sorted(p.name for p in (tmp_path / "plain").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "full").iterdir()) and "tick_idx_prev.npy" in names
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "plain" / n), np.load(tmp_path / "full" / n)), n
+    assert np.load(tmp_path / "plain" / "tick_status.npy")[0] == 2
 
 
 def _with_env(env, args):

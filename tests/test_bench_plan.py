@@ -146,6 +146,21 @@ def test_record_layout_keeps_both_halves_of_the_metric_inside_what_the_driver_ke
     assert roof["frac"] == 0.8625 and roof["achieved"] == 6900.0 and roof["kernel"] == "db_scan_topk" and json_rt["value"] == 422.0
 
 
+def test_record_layout_of_a_plain_run():
+    """Without --full no leg runs and nothing is measured per launch: the contract's keys of `roofline` stay, in place, as nulls,
+    `config` is the run's own."""
+    rec = _synthetic_record()
+    for k in ("sizes", "shapes", "paced_10hz", "resident_tick", "pnp", "icp", "batch"):
+        del rec[k]
+    rec["roofline"] = {"bound": "hbm", "achieved": None, "peak": 8000.0, "unit": "GB/s", "frac": None, "traffic": None,
+                       "kernel": "db_scan_topk", "algorithmic_bytes_per_launch": 1.6384e10, "measured": "not in this run"}
+    out = bench.finalize_record(rec)
+    assert list(out["roofline"]) == ["bound", "achieved", "peak", "unit", "frac", "traffic", "algorithmic_bytes_per_launch", "kernel", "measured"]
+    assert out["roofline"]["achieved"] is None and out["roofline"]["frac"] is None and out["roofline"]["traffic"] is None
+    assert list(out["config"]) == ["workload", "db_rows", "D", "queries_per_tick", "topk", "storage", "sharding", "exchange"]
+    assert "roofline_context" not in out and "config_more" not in out and out["value"] == 422.0
+
+
 def test_record_layout_without_legs_and_with_too_many_config_keys():
     rec = _synthetic_record(n_gpus=8)
     for k in ("sizes", "shapes", "paced_10hz", "resident_tick", "pnp", "icp", "batch"):

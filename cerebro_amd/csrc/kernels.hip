@@ -170,23 +170,11 @@ __device__ __forceinline__ void wave_topk_offer(double s, int64_t gi, int K, int
     }
 }
 
-// Block merge: wpb sorted lists of K per query -> one sorted list of K per query in a.partial[blockIdx.x], by waves 0..NQ-1.
+// Block merge: wpb sorted lists of K per query, cand[wpb][NQ][K] in LDS -> one sorted list of K per query at out_of(q), by waves 0..NQ-1.
 template <int NQ, typename OutOf>
-__device__ __forceinline__ void block_merge_store(char *smem, const double (&my_s)[NQ], const int64_t (&my_i)[NQ],
-                                                  int K, int lane, int wave, int wpb, OutOf out_of)
+__device__ __forceinline__ void block_merge_cand(const chip_topk_entry *cand, int K, int lane, int wave, int wpb, OutOf out_of)
 {
-    __syncthreads();  // all waves done with the staged queries; reuse LDS
-    chip_topk_entry *cand = reinterpret_cast<chip_topk_entry *>(smem);  // [wpb][NQ][K]
-    if (lane < K) {
-#pragma unroll
-        for (int q = 0; q < NQ; q++) {
-            chip_topk_entry t;
-            t.score = my_s[q];
-            t.idx = my_i[q];
-            cand[(wave * NQ + q) * K + lane] = t;
-        }
-    }
-    __syncthreads();
+    __syncthreads();  // every wave's lists are in LDS
     for (int q = wave; q < NQ; q += wpb) {
         const int ncand = wpb * K;  // <= 16 waves * 16 = 256 -> at most 4 per lane
         double cs[4];
@@ -221,6 +209,25 @@ __device__ __forceinline__ void block_merge_store(char *smem, const double (&my_
     }
 }
 
+// The same for lists held in registers: they go to LDS over the staged queries first.
+template <int NQ, typename OutOf>
+__device__ __forceinline__ void block_merge_store(char *smem, const double (&my_s)[NQ], const int64_t (&my_i)[NQ],
+                                                  int K, int lane, int wave, int wpb, OutOf out_of)
+{
+    __syncthreads();  // all waves done with the staged queries; reuse LDS
+    chip_topk_entry *cand = reinterpret_cast<chip_topk_entry *>(smem);  // [wpb][NQ][K]
+    if (lane < K) {
+#pragma unroll
+        for (int q = 0; q < NQ; q++) {
+            chip_topk_entry t;
+            t.score = my_s[q];
+            t.idx = my_i[q];
+            cand[(wave * NQ + q) * K + lane] = t;
+        }
+    }
+    block_merge_cand<NQ>(cand, K, lane, wave, wpb, out_of);
+}
+
 // The same for a WAVE-UNIFORM row through the scalar cache: the table is read with s_load (constant address space; entries of
 // published rows never change), so the lookup neither costs a vector-memory round trip nor touches vmcnt.
 template <typename T, typename Args>
@@ -229,6 +236,16 @@ __device__ __forceinline__ const T *row_base_uniform(const Args &a, int64_t r)
     typedef const uint64_t __attribute__((address_space(4))) *ctab;
     const uint64_t seg = ((ctab)(uintptr_t)a.seg_table)[r >> a.seg_shift];
     return reinterpret_cast<const T *>((uintptr_t)seg) + (r & a.seg_mask) * (int64_t)a.D;
+}
+
+// a wave-uniform pointer the compiler cannot prove uniform (it came out of the segment table) -> SGPR pair
+template <typename P>
+__device__ __forceinline__ const P *uniform_ptr(const P *p)
+{
+    const uint64_t b = (uint64_t)(uintptr_t)p;
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32));
+    return reinterpret_cast<const P *>((uintptr_t)(((uint64_t)hi << 32) | lo));
 }
 
 template <typename T, int NQ, int U, bool FULL, int NT, int R>
@@ -298,33 +315,105 @@ __global__ __launch_bounds__(1024) void db_scan_topk(ScanArgs a)
 //   * register blocking: R = 4 rows per wave in flight, U = 4 KiB of each per batch (16 KiB per wave, one workgroup of 8 waves per
 //     CU), every query vector read (ds_read_b128) and converted ONCE per 4 rows: per row vector and lane 4 row conversions +
 //     3T x (1 conversion + 4 fma) = 49 VALU instructions at T = 3 against 16 (4 + 12) for one tick in db_scan_topk;
-//   * per-tick prefix: a row is offered to tick t's lists only if row < k_t (wave-uniform compare); the running lists stay in
-//     VGPRs (lane j < K: the j-th best), the admission thresholds in SGPRs;
+//   * per-tick prefix: a row is offered to tick t's lists only if row < k_t (wave-uniform compare); the running lists sit in LDS
+//     behind the queries ([wave][3T][K] entries), the admission thresholds in SGPRs;
 //   * output [tick][workgroup][3][K]: the merge + decision kernel runs unchanged, once per tick, on its own block of lists.
 constexpr int kMultiR = 4, kMultiU = 4, kMultiBlock = 512;
 
-__device__ __forceinline__ void wave_topk_offer_sthr(double s, int64_t gi, int K, int lane, double &my_s, int64_t &my_i, double &thr_s, int64_t &thr_i)
+// The R x U = 16 load slots of a wave (1 KiB each) are PHYSICAL registers v[kMultiVgprBase ..] that the compiler does not own, as in
+// db_scan_topk_rows below (same reason, same technique: amdgpu_num_vgpr leaves the top of the file to the asm statements, which name
+// their targets literally and convert out of them in the statement that waits; tests/test_codeobj_multi.py checks the partition).
+constexpr int kMultiVgprBase = 192;
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
+#error "db_scan_topk_multi names physical VGPRs: gfx950 (MI355X) only -- build with --offload-arch=gfx950"
+#endif
+#define CHIP_MULTI_CLOBBERS                                                                                                             \
+    "v192", "v193", "v194", "v195", "v196", "v197", "v198", "v199", "v200", "v201", "v202", "v203", "v204", "v205", "v206", "v207",     \
+    "v208", "v209", "v210", "v211", "v212", "v213", "v214", "v215", "v216", "v217", "v218", "v219", "v220", "v221", "v222", "v223",     \
+    "v224", "v225", "v226", "v227", "v228", "v229", "v230", "v231", "v232", "v233", "v234", "v235", "v236", "v237", "v238", "v239",     \
+    "v240", "v241", "v242", "v243", "v244", "v245", "v246", "v247", "v248", "v249", "v250", "v251", "v252", "v253", "v254", "v255"
+// slot (u, rr): KiB u of the batch of row rr -> v[reg : reg + 3]
+__host__ __device__ constexpr int multi_slot_reg(int u, int rr) { return kMultiVgprBase + 4 * (u * kMultiR + rr); }
+
+// 1 KiB of a row (16 bytes per lane) into a slot: wave-uniform row base in an SGPR pair, one shared 32-bit lane offset
+template <int REG, int OFF>
+__device__ __forceinline__ void multi_issue(uint32_t voff, const float *row_uniform)
+{
+    asm volatile("global_load_dwordx4 v[%2:%3], %0, %1 offset:%4 nt" ::"v"(voff), "s"(row_uniform), "n"(REG), "n"(REG + 3), "n"(OFF) : "memory");
+}
+// wait until at most CNT row loads are outstanding (they return in order), then hand the slot's four elements to the compiler as fp64:
+// once this statement has been issued the slot may be loaded again
+template <int REG, int CNT>
+__device__ __forceinline__ void multi_take(double (&d)[4])
+{
+    asm volatile("s_waitcnt vmcnt(%4)\n\tv_cvt_f64_f32 %0, v[%5]\n\tv_cvt_f64_f32 %1, v[%6]\n\tv_cvt_f64_f32 %2, v[%7]\n\tv_cvt_f64_f32 %3, v[%8]"
+                 : "=v"(d[0]), "=v"(d[1]), "=v"(d[2]), "=v"(d[3])
+                 : "n"(CNT), "n"(REG), "n"(REG + 1), "n"(REG + 2), "n"(REG + 3)
+                 : "memory");
+}
+
+// The running top-K lists of the multi-tick and the row-batched kernels live in LDS behind the staged queries, only the admission
+// threshold (the K-th entry) stays in SGPRs: after warm-up an offer is rare, and lists held in VGPRs (as in db_scan_topk) would cost
+// 4 NQ registers of kernels that keep 16 load slots per wave in flight.
+__device__ __forceinline__ void wave_topk_offer_lds(double s, int64_t gi, int K, int lane, chip_topk_entry *list, double &thr_s, int64_t &thr_i)
 {
     if (key_gt(s, gi, thr_s, thr_i)) {   // wave-uniform; NaN never enters
-        const bool worse = key_gt(s, gi, my_s, my_i);
+        chip_topk_entry me, up;
+        me.score = -INFINITY; me.idx = -1; up = me;
+        if (lane < K) { me = list[lane]; if (lane > 0) up = list[lane - 1]; }
+        const bool worse = key_gt(s, gi, me.score, me.idx);
         const unsigned long long m = __ballot(worse) & ((1ull << K) - 1ull);
         const int pos = __builtin_ctzll(m);
-        const double up_s = __shfl_up(my_s, 1, 64);
-        const int64_t up_i = __shfl_up(my_i, 1, 64);
         if (lane < K) {
-            if (lane > pos) { my_s = up_s; my_i = up_i; }
-            else if (lane == pos) { my_s = s; my_i = gi; }
+            if (lane > pos) me = up;
+            else if (lane == pos) { me.score = s; me.idx = gi; }
+            list[lane] = me;      // every read of the old list precedes this write in program order (one wave, in-order LDS)
         }
-        thr_s = readlane_f64(my_s, K - 1);
-        thr_i = readlane_i64(my_i, K - 1);
+        thr_s = readlane_f64(me.score, K - 1);
+        thr_i = readlane_i64(me.idx, K - 1);
+    }
+}
+
+// the value of the lane that the DPP control CTRL pairs this lane with (all lanes active)
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double v)
+{
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+
+// Admission of a row to one running list of the multi-tick kernel.  The score comes in SGPRs (every lane holds the same bits after the
+// butterfly), so the compare is a scalar branch and the threshold stays in SGPRs.  A wave meets its rows in ascending order, so gi is
+// larger than every index already in its lists and key_gt(s, gi, thr_s, thr_i) is just s >= thr_s (false for NaN, which never
+// enters): the K-th index need not be kept.  The list's LDS address is formed inside the branch (hoisted out of the scan loop, the
+// 3T x 2 addresses would be held in registers for an insertion that is rare after the first rows).
+__device__ __forceinline__ void multi_offer(double s_uniform, int64_t gi, int K, int lane, chip_topk_entry *list, double &thr_s)
+{
+    if (s_uniform >= thr_s) {
+        asm volatile("" : "+v"(lane));
+        chip_topk_entry me, up;
+        me.score = -INFINITY; me.idx = -1; up = me;
+        if (lane < K) { me = list[lane]; if (lane > 0) up = list[lane - 1]; }
+        const bool worse = key_gt(s_uniform, gi, me.score, me.idx);
+        const unsigned long long m = __ballot(worse) & ((1ull << K) - 1ull);
+        const int pos = __builtin_ctzll(m);
+        if (lane < K) {
+            if (lane > pos) me = up;
+            else if (lane == pos) { me.score = s_uniform; me.idx = gi; }
+            list[lane] = me;      // every read of the old list precedes this write in program order (one wave, in-order LDS)
+        }
+        thr_s = readlane_f64(me.score, K - 1);
     }
 }
 
 template <int NTICKS>
-__global__ __launch_bounds__(kMultiBlock) void db_scan_topk_multi(MultiScanArgs a)
+__global__ __launch_bounds__(kMultiBlock) __attribute__((amdgpu_num_vgpr(kMultiVgprBase / 2))) void db_scan_topk_multi(MultiScanArgs a)
 {
     constexpr int NQ = 3 * NTICKS, R = kMultiR, U = kMultiU;
+    static_assert(kMultiVgprBase + 4 * R * U <= 256, "load slots beyond the register file of an 8-wave workgroup");
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    asm volatile("" ::: CHIP_MULTI_CLOBBERS);                       // makes the code object allocate the asm-owned registers
     float *qs = reinterpret_cast<float *>(smem);  // [NQ][D]
     const int D = a.D;
     const int K = a.K;
@@ -342,82 +431,147 @@ __global__ __launch_bounds__(kMultiBlock) void db_scan_topk_multi(MultiScanArgs 
     }
     __syncthreads();
 
-    double my_s[NQ], thr_s[NQ];
-    int64_t my_i[NQ], thr_i[NQ];
+    // running top-K lists: LDS behind the queries, [wave][3T][K] (this wave's lists are touched by this wave only until the merge)
+    chip_topk_entry *lists = reinterpret_cast<chip_topk_entry *>(smem + (size_t)NQ * D * sizeof(float));
+    chip_topk_entry *mylists = lists + (size_t)wave * NQ * K;
+    double thr_s[NQ];   // score of the K-th entry of each list (SGPRs)
 #pragma unroll
-    for (int q = 0; q < NQ; q++) { my_s[q] = -INFINITY; my_i[q] = -1; thr_s[q] = -INFINITY; thr_i[q] = -1; }
+    for (int q = 0; q < NQ; q++) {
+        thr_s[q] = -INFINITY;
+        if (lane < K) { chip_topk_entry t; t.score = -INFINITY; t.idx = -1; mylists[q * K + lane] = t; }
+    }
 
-    // Row -> wave map: as db_scan_topk (wave g owns rows g, g + tw, ...), four consecutive rows of that sequence at a time -- all
-    // waves together read one window of 4 tw consecutive rows that slides through the DB.  A wave whose last rows fall beyond the
-    // pass re-reads its first row in their place (in bounds, never offered).
+    // Row -> wave map: as db_scan_topk (wave g owns rows g, g + tw, ...), four consecutive rows of that sequence (a GROUP) at a time --
+    // all waves together read one window of 4 tw consecutive rows that slides through the DB.  A row of a group that falls beyond the
+    // pass is replaced by the wave's first row (in bounds, never offered).
+    //
+    // The wave walks the (group, 4 KiB batch) sequence of its rows as ONE stream: slot (u, rr) is loaded again -- for the next batch of
+    // the group, or the first batch of the next group -- in the statement after the one that converted its contents, so 15-16 KiB per
+    // wave are in flight through the arithmetic, through the butterflies and through the offers, and every wait is vmcnt(15).
+    // Nothing is ever loaded from outside rows [0, n_rows): every base comes from row_of() below, i.e. from a row < n_rows through
+    // the segment table, and every offset is below one row's length.
     const int64_t tw = (int64_t)gridDim.x * wpb;
+    const int64_t rbase = (int64_t)blockIdx.x * wpb + wave;
+    const int nb = D / (256 * U);                                                             // batches per row
+    const int ngroups = rbase < a.n_rows ? (int)((a.n_rows - 1 - rbase) / (R * tw)) + 1 : 0;  // groups of this wave (wave-uniform)
+    const int total = ngroups * nb;
+    const uint32_t lane_off = (uint32_t)lane * 16u;
     const int e0 = lane * 4;
-    for (int64_t r0 = (int64_t)blockIdx.x * wpb + wave; r0 < a.n_rows; r0 += R * tw) {
-        const float *row[R];
+    auto row_of = [&](int group, int rr) {
+        const int64_t r = rbase + ((int64_t)group * R + rr) * tw;
+        return uniform_ptr(row_base_uniform<float>(a, r < a.n_rows ? r : rbase));
+    };
+    const float *row[R], *nrow[R];   // bases the NEXT loads read from, and those of the group after (looked up one group ahead; SGPRs)
+    if (total > 0) {
 #pragma unroll
-        for (int rr = 0; rr < R; rr++) {
-            const int64_t r = r0 + rr * tw;
-            row[rr] = row_base_uniform<float>(a, r < a.n_rows ? r : r0);
+        for (int rr = 0; rr < R; rr++) { row[rr] = row_of(0, rr); nrow[rr] = row[rr]; }
+        if (ngroups > 1) {
+#pragma unroll
+            for (int rr = 0; rr < R; rr++) nrow[rr] = row_of(1, rr);
         }
-        double acc[R][NQ];
+#define CHIP_MULTI_ISSUE_ROW(u, rr, voff) multi_issue<multi_slot_reg(u, rr), (u) * 1024>(voff, row[rr])
+#define CHIP_MULTI_ISSUE_SLOT(u, voff) do { CHIP_MULTI_ISSUE_ROW(u, 0, voff); CHIP_MULTI_ISSUE_ROW(u, 1, voff); CHIP_MULTI_ISSUE_ROW(u, 2, voff); CHIP_MULTI_ISSUE_ROW(u, 3, voff); } while (0)
+        CHIP_MULTI_ISSUE_SLOT(0, lane_off); CHIP_MULTI_ISSUE_SLOT(1, lane_off); CHIP_MULTI_ISSUE_SLOT(2, lane_off); CHIP_MULTI_ISSUE_SLOT(3, lane_off);
+    }
+
+    double acc[R][NQ];
 #pragma unroll
-        for (int rr = 0; rr < R; rr++)
+    for (int rr = 0; rr < R; rr++)
 #pragma unroll
-            for (int q = 0; q < NQ; q++) acc[rr][q] = 0.0;
-        for (int base = 0; base < D; base += 256 * U) {
-            // the R * U loads of a batch issued back to back and consumed behind COUNTED waits (the load stream of rows_dot, NT == 6)
-            f32x4 v[R][U];
-            const char *mid[R];
+        for (int q = 0; q < NQ; q++) acc[rr][q] = 0.0;
+
+    // One batch per iteration.  Per KiB u: each row's slot is taken (converted) and loaded again at byte offset noff of row[]; then the
+    // 3T query vectors, each read from LDS two vectors ahead of its use (counted lgkmcnt waits), converted once and multiplied into
+    // the four rows.  Per (row, query): j ascending, c = 0..3 -- rows_dot's order.  What the slots load next: the next batch of the
+    // group; at the group's last batch the first batch of the wave's next group; at the wave's last batch the first KiBs of the rows
+    // it has just read once more (in bounds, taken by nobody), so that one loop body and one wait count serve the whole stream.
+    int b = 0, group = 0;
+    for (int t = 0; t < total; t++) {
+        const int base = b * (256 * U);
+        uint32_t noff = (uint32_t)(base + 256 * U) * 4u;
+        if (b + 1 == nb) {
+            noff = 0;
+            if (group + 1 < ngroups) {   // the slots start on the next group; its successor's bases are looked up for the boundary after
 #pragma unroll
-            for (int rr = 0; rr < R; rr++) mid[rr] = reinterpret_cast<const char *>(row[rr] + base + e0) + 2048;
+                for (int rr = 0; rr < R; rr++) row[rr] = nrow[rr];
+                if (group + 2 < ngroups) {
 #pragma unroll
-            for (int u = 0; u < U; u++)      // the first KiB of every row first: the arithmetic starts when 4 of the 16 loads are back
-#pragma unroll
-                for (int rr = 0; rr < R; rr++)
-                    asm volatile("global_load_dwordx4 %0, %1, off offset:%2 nt" : "=v"(v[rr][u]) : "v"(mid[rr]), "n"(u * 1024 - 2048) : "memory");
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                double x[R][4];
-#pragma unroll
-                for (int rr = 0; rr < R; rr++) {   // loads return in order: load (rr, u) is done once at most this many are outstanding
-                    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(v[rr][u]) : "n"((U - 1 - u) * R + (R - 1 - rr)) : "memory");
-#pragma unroll
-                    for (int c = 0; c < 4; c++) x[rr][c] = (double)v[rr][u][c];
-                }
-                const float *qv = qs + base + u * 256 + e0;
-#pragma unroll
-                for (int q = 0; q < NQ; q++) {
-                    const f32x4 w = *reinterpret_cast<const f32x4 *>(qv + q * D);
-#pragma unroll
-                    for (int c = 0; c < 4; c++) {
-                        const double wd = (double)w[c];
-#pragma unroll
-                        for (int rr = 0; rr < R; rr++) acc[rr][q] = __builtin_fma(wd, x[rr][c], acc[rr][q]);
-                    }
+                    for (int rr = 0; rr < R; rr++) nrow[rr] = row_of(group + 2, rr);
                 }
             }
         }
-        // all R x 3T butterflies first, in one basic block: they are independent, so their cross-lane round trips overlap (behind the
-        // offers' branches each would be a serial chain of six, with only two waves per SIMD to hide it)
+        {
+            constexpr int S = U * NQ;
+            const float *qv = qs + base + e0;
+            const uint32_t voff = noff + lane_off;
+            f32x4 w[S];
+            w[0] = *reinterpret_cast<const f32x4 *>(qv);
+            w[1] = *reinterpret_cast<const f32x4 *>(qv + D);
+            double x[R][4];
 #pragma unroll
-        for (int m = 32; m >= 1; m >>= 1)
+            for (int s = 0; s < S; s++) {
+                const int u = s / NQ, q = s % NQ;
+                if (q == 0) {
+#define CHIP_MULTI_TAKE_ROW(uu, rr) if (u == uu) { multi_take<multi_slot_reg(uu, rr), R * U - 1>(x[rr]); CHIP_MULTI_ISSUE_ROW(uu, rr, voff); }
+#define CHIP_MULTI_TAKE_SLOT(uu) CHIP_MULTI_TAKE_ROW(uu, 0) CHIP_MULTI_TAKE_ROW(uu, 1) CHIP_MULTI_TAKE_ROW(uu, 2) CHIP_MULTI_TAKE_ROW(uu, 3)
+                    CHIP_MULTI_TAKE_SLOT(0) CHIP_MULTI_TAKE_SLOT(1) CHIP_MULTI_TAKE_SLOT(2) CHIP_MULTI_TAKE_SLOT(3)
+#undef CHIP_MULTI_TAKE_SLOT
+#undef CHIP_MULTI_TAKE_ROW
+                }
+                if (s + 2 < S) w[s + 2] = *reinterpret_cast<const f32x4 *>(qv + ((s + 2) % NQ) * D + ((s + 2) / NQ) * 256);
+#pragma unroll
+                for (int c = 0; c < 4; c++) {
+                    const double wd = (double)w[s][c];
+#pragma unroll
+                    for (int rr = 0; rr < R; rr++) acc[rr][q] = __builtin_fma(wd, x[rr][c], acc[rr][q]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        if (++b == nb) {
+            // the rows of this group are complete.  All R x 3T butterflies first, in one basic block: they are independent, so their
+            // cross-lane round trips overlap (behind the offers' branches each would be a serial chain of six).  Steps 32 and 16 cross
+            // the 16-lane rows and go through LDS (ds_bpermute); steps 8, 4, 2, 1 stay inside a row and take the partner's value by
+            // DPP: row_ror:8 IS lane ^ 8; after step 8 a value depends on lane & 7 only, so row_ror:4 delivers the bits of lane ^ 4,
+            // and the quad permutations are lane ^ 2 and lane ^ 1 -- the same pairs, and a + b == b + a: the same bits as the xor tree.
+#pragma unroll
+            for (int m = 32; m >= 16; m >>= 1)
+#pragma unroll
+                for (int rr = 0; rr < R; rr++)
+#pragma unroll
+                    for (int q = 0; q < NQ; q++) acc[rr][q] = acc[rr][q] + __shfl_xor(acc[rr][q], m, 64);
 #pragma unroll
             for (int rr = 0; rr < R; rr++)
 #pragma unroll
-                for (int q = 0; q < NQ; q++) acc[rr][q] = acc[rr][q] + __shfl_xor(acc[rr][q], m, 64);
+                for (int q = 0; q < NQ; q++) {
+                    double v = acc[rr][q];
+                    v = v + dpp_f64<0x128>(v);
+                    v = v + dpp_f64<0x124>(v);
+                    v = v + dpp_f64<0x4E>(v);
+                    v = v + dpp_f64<0xB1>(v);
+                    acc[rr][q] = v;
+                }
 #pragma unroll
-        for (int rr = 0; rr < R; rr++) {
-            const int64_t r = r0 + rr * tw;
-            if (r < a.n_rows) {
+            for (int rr = 0; rr < R; rr++) {
+                const int64_t r = rbase + ((int64_t)group * R + rr) * tw;
+                if (r < a.n_rows) {
 #pragma unroll
-                for (int q = 0; q < NQ; q++)
-                    if (r < a.k[q / 3]) wave_topk_offer_sthr(acc[rr][q], r, K, lane, my_s[q], my_i[q], thr_s[q], thr_i[q]);
+                    for (int q = 0; q < NQ; q++)
+                        if (r < a.k[q / 3]) multi_offer(readlane_f64(acc[rr][q], 0), r, K, lane, mylists + q * K, thr_s[q]);
+                }
+#pragma unroll
+                for (int q = 0; q < NQ; q++) acc[rr][q] = 0.0;
             }
+            b = 0;
+            group++;
         }
     }
+#undef CHIP_MULTI_ISSUE_SLOT
+#undef CHIP_MULTI_ISSUE_ROW
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the read-ahead of the wave's last batch
 
-    block_merge_store<NQ>(smem, my_s, my_i, K, lane, wave, wpb,
-                          [&](int q) { return a.partial + (((int64_t)(q / 3) * gridDim.x + blockIdx.x) * 3 + q % 3) * K; });
+    block_merge_cand<NQ>(lists, K, lane, wave, wpb,
+                         [&](int q) { return a.partial + (((int64_t)(q / 3) * gridDim.x + blockIdx.x) * 3 + q % 3) * K; });
 }
 
 // ------------------------------------------------------------------------------------------------ K1, wide double rows
@@ -510,38 +664,6 @@ __device__ __forceinline__ void glds16_q(const void *gsrc_lane, uint32_t lds_bas
                  : "=&s"(keep)
                  : "v"(gsrc_lane), "s"(lds_base_wave_uniform)
                  : "memory");
-}
-
-// a wave-uniform pointer the compiler cannot prove uniform (it came out of the segment table) -> SGPR pair
-template <typename P>
-__device__ __forceinline__ const P *uniform_ptr(const P *p)
-{
-    const uint64_t b = (uint64_t)(uintptr_t)p;
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32));
-    return reinterpret_cast<const P *>((uintptr_t)(((uint64_t)hi << 32) | lo));
-}
-
-// The running top-K lists of the row-batched kernel live in LDS ([wave][query][CHIP_MAX_TOPK] entries behind the staged
-// queries), only the admission threshold (the K-th entry) stays in SGPRs: after warm-up an offer is rare, and lists held in
-// VGPRs (as in db_scan_topk) would cost 4 NQ registers of a kernel that keeps R x 16 of them in flight as load targets.
-__device__ __forceinline__ void wave_topk_offer_lds(double s, int64_t gi, int K, int lane, chip_topk_entry *list, double &thr_s, int64_t &thr_i)
-{
-    if (key_gt(s, gi, thr_s, thr_i)) {   // wave-uniform; NaN never enters
-        chip_topk_entry me, up;
-        me.score = -INFINITY; me.idx = -1; up = me;
-        if (lane < K) { me = list[lane]; if (lane > 0) up = list[lane - 1]; }
-        const bool worse = key_gt(s, gi, me.score, me.idx);
-        const unsigned long long m = __ballot(worse) & ((1ull << K) - 1ull);
-        const int pos = __builtin_ctzll(m);
-        if (lane < K) {
-            if (lane > pos) me = up;
-            else if (lane == pos) { me.score = s; me.idx = gi; }
-            list[lane] = me;      // every read of the old list precedes this write in program order (one wave, in-order LDS)
-        }
-        thr_s = readlane_f64(me.score, K - 1);
-        thr_i = readlane_i64(me.idx, K - 1);
-    }
 }
 
 // Block merge over the LDS lists: wpb sorted lists of K per query -> one sorted list of K per query in a.partial[blockIdx.x].
@@ -1447,7 +1569,8 @@ int launch_scan(Ctx *c, hipStream_t s, const ScanArgs &a, int nq, int grid)
 int scan_multi_max_ticks(const Ctx *c)
 {
     if (c->elem != 4 || (int64_t)c->D * 4 % 4096 != 0 || c->nranks != 1 || c->scan_variant != 0 || c->scan_rows > 0) return 0;
-    const int fit = (int)((160 * 1024) / ((size_t)3 * c->D * 4));
+    // per tick: 3 fp32 queries and the 8 waves' 3 running lists of CHIP_DEFAULT_TOPK entries (the K the tick path asks for)
+    const int fit = (int)((160 * 1024) / ((size_t)3 * c->D * 4 + (size_t)(kMultiBlock / 64) * 3 * CHIP_DEFAULT_TOPK * sizeof(chip_topk_entry)));
     return fit >= kMultiMaxTicks ? kMultiMaxTicks : (fit >= 2 ? fit : 0);
 }
 
@@ -1464,8 +1587,8 @@ static int launch_scan_multi_t(Ctx *c, hipStream_t s, const MultiScanArgs &a, in
 
 int launch_scan_multi(Ctx *c, hipStream_t s, const MultiScanArgs &a, int n_ticks, int grid)
 {
-    const size_t lds_q = (size_t)3 * n_ticks * a.D * 4, lds_m = (size_t)(kMultiBlock / 64) * 3 * n_ticks * a.K * sizeof(chip_topk_entry);
-    const size_t lds = lds_q > lds_m ? lds_q : lds_m;
+    // the staged queries and, behind them, the waves' running lists ([wave][3T][K]: 9 KiB at T = 3, K = 8; a K that does not fit is refused)
+    const size_t lds = (size_t)3 * n_ticks * a.D * 4 + (size_t)(kMultiBlock / 64) * 3 * n_ticks * a.K * sizeof(chip_topk_entry);
     if (n_ticks < 2 || n_ticks > scan_multi_max_ticks(c) || lds > 160 * 1024 || grid < 1 || grid > c->max_grid || a.K < 1 || a.K > CHIP_MAX_TOPK)
         return CHIP_ERR_UNSUPPORTED;
     const int rc = n_ticks == 2 ? launch_scan_multi_t<2>(c, s, a, grid, lds) : launch_scan_multi_t<3>(c, s, a, grid, lds);

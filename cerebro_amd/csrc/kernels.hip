@@ -310,13 +310,15 @@ __global__ __launch_bounds__(1024) void db_scan_topk(ScanArgs a)
 // db_scan_topk_multi<T>: ONE pass over rows [0, max k_t) answers T queued ticks of 3 queries each (chip_api.hip coalesce_*): the
 // pass is as HBM-bound as a one-tick launch, so T ticks cost one DB read.  Float rows of whole 4 KiB batches, plain ctx.
 //   * same bits: per (row, query) exactly rows_dot's order -- lane L accumulates elements j*256 + 4L + c (j ascending, c = 0..3)
-//     into one fp64 accumulator by fma, then the xor butterfly; the queries sit in LDS as fp32 ([3T][D], 144 KiB at T = 3,
+//     into one fp64 accumulator by fma, then the xor butterfly's pairing tree (formed transposed for the four rows of a group at
+//     once, on gfx950's lane swaps: see the reduction below); the queries sit in LDS as fp32 ([3T][D], 144 KiB at T = 3,
 //     D = 4096) and are converted at use (fp32 x fp32 is exact in fp64 wherever the conversion happens);
 //   * register blocking: R = 4 rows per wave in flight, U = 4 KiB of each per batch (16 KiB per wave, one workgroup of 8 waves per
 //     CU), every query vector read (ds_read_b128) and converted ONCE per 4 rows: per row vector and lane 4 row conversions +
 //     3T x (1 conversion + 4 fma) = 49 VALU instructions at T = 3 against 16 (4 + 12) for one tick in db_scan_topk;
 //   * per-tick prefix: a row is offered to tick t's lists only if row < k_t (wave-uniform compare); the running lists sit in LDS
-//     behind the queries ([wave][3T][K] entries), the admission thresholds in SGPRs;
+//     behind the queries ([wave][3T][K] entries), the admission thresholds in SGPRs; one vector compare per query tells whether any
+//     row of a group can enter a list at all;
 //   * output [tick][workgroup][3][K]: the merge + decision kernel runs unchanged, once per tick, on its own block of lists.
 constexpr int kMultiR = 4, kMultiU = 4, kMultiBlock = 512;
 
@@ -374,17 +376,35 @@ __device__ __forceinline__ void wave_topk_offer_lds(double s, int64_t gi, int K,
     }
 }
 
-// the value of the lane that the DPP control CTRL pairs this lane with (all lanes active)
+// the value of the lane that the DPP control CTRL pairs this lane with (all lanes active).  The controls used here (row_ror, quad_perm)
+// read a valid lane for every lane, so the `old` operand never shows: bound_ctrl saves the compiler the move that would fill it in.
 template <int CTRL>
 __device__ __forceinline__ double dpp_f64(double v)
 {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, true);
     return __hiloint2double(hi, lo);
 }
 
-// Admission of a row to one running list of the multi-tick kernel.  The score comes in SGPRs (every lane holds the same bits after the
-// butterfly), so the compare is a scalar branch and the threshold stays in SGPRs.  A wave meets its rows in ascending order, so gi is
+// gfx950's half exchanges on both dwords of a pair of doubles.  swap32: lanes 32-63 of a change places with lanes 0-31 of b;
+// swap16: the odd 16-lane rows of a with the even rows of b.  (Builtins: the compiler places the wait states a VALU write of an operand needs.)
+__device__ __forceinline__ void swap32_f64(double &a, double &b)
+{
+    const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
+    const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
+    a = __hiloint2double((int)hi[0], (int)lo[0]);
+    b = __hiloint2double((int)hi[1], (int)lo[1]);
+}
+__device__ __forceinline__ void swap16_f64(double &a, double &b)
+{
+    const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
+    const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
+    a = __hiloint2double((int)hi[0], (int)lo[0]);
+    b = __hiloint2double((int)hi[1], (int)lo[1]);
+}
+
+// Admission of a row to one running list of the multi-tick kernel.  The score comes in SGPRs (all 16 lanes of the row's share of the wave hold the same bits
+// after the reduction), so the compare is a scalar branch and the threshold stays in SGPRs.  A wave meets its rows in ascending order, so gi is
 // larger than every index already in its lists and key_gt(s, gi, thr_s, thr_i) is just s >= thr_s (false for NaN, which never
 // enters): the K-th index need not be kept.  The list's LDS address is formed inside the branch (hoisted out of the scan loop, the
 // 3T x 2 addresses would be held in registers for an insertion that is rare after the first rows).
@@ -529,39 +549,52 @@ __global__ __launch_bounds__(kMultiBlock) __attribute__((amdgpu_num_vgpr(kMultiV
             }
         }
         if (++b == nb) {
-            // the rows of this group are complete.  All R x 3T butterflies first, in one basic block: they are independent, so their
-            // cross-lane round trips overlap (behind the offers' branches each would be a serial chain of six).  Steps 32 and 16 cross
-            // the 16-lane rows and go through LDS (ds_bpermute); steps 8, 4, 2, 1 stay inside a row and take the partner's value by
-            // DPP: row_ror:8 IS lane ^ 8; after step 8 a value depends on lane & 7 only, so row_ror:4 delivers the bits of lane ^ 4,
-            // and the quad permutations are lane ^ 2 and lane ^ 1 -- the same pairs, and a + b == b + a: the same bits as the xor tree.
+            // The rows of this group are complete: R x 3T lane sums, all in one basic block ahead of the offers' branches.  Per query the
+            // xor butterfly's pairing tree (m = 32, 16, 8, 4, 2, 1: lane l with lane l ^ m) is computed TRANSPOSED, each row's tree in a
+            // quarter of the lanes, without LDS:
+            //   step 32: swap32(rows 0, 2), one addition: lanes 0-31 hold row 0's a[l] + a[l ^ 32], lanes 32-63 row 2's; likewise rows 1, 3;
+            //   step 16: swap16 of the two results, one addition: 16-lane row k of s[q] holds the sums of data row k after steps 32 and 16;
+            //   steps 8, 4, 2, 1 stay inside a 16-lane row and take the partner's value by DPP: row_ror:8 IS lane ^ 8; after step 8 a value
+            //     depends on lane & 7 only, so row_ror:4 delivers the bits of lane ^ 4, and the quad permutations are lane ^ 2 and lane ^ 1.
+            // The same pairs as butterfly_sum, and a + b == b + a: all 16 lanes of row k end with the bits lane 0 of the full tree holds.
+            static_assert(R == 4, "the transposed reduction folds four rows into the four 16-lane rows of a wave");
+            double s[NQ];
 #pragma unroll
-            for (int m = 32; m >= 16; m >>= 1)
+            for (int q = 0; q < NQ; q++) {
+                swap32_f64(acc[0][q], acc[2][q]);
+                swap32_f64(acc[1][q], acc[3][q]);
+                double p02 = acc[0][q] + acc[2][q], p13 = acc[1][q] + acc[3][q];
+                swap16_f64(p02, p13);
+                double v = p02 + p13;
+                v = v + dpp_f64<0x128>(v);
+                v = v + dpp_f64<0x124>(v);
+                v = v + dpp_f64<0x4E>(v);
+                v = v + dpp_f64<0xB1>(v);
+                s[q] = v;
+            }
+            // Offers.  One vector compare per query first: s[q] holds the four rows' scores against query q, and a threshold only rises
+            // while the group is offered, so a score that the loop below would admit is >= the threshold the group starts with (NaN on
+            // neither side).  No lane set: nothing of this group enters any list.  Otherwise the rows are offered one by one, in
+            // order, each against the threshold as it stands then.  (A lane may be set by a row some tick must not see, or by the stand-in
+            // of a row beyond the pass: that costs the walk below, which tests both, and nothing else.)
+            unsigned long long hit = 0;
 #pragma unroll
-                for (int rr = 0; rr < R; rr++)
+            for (int q = 0; q < NQ; q++) hit |= __ballot(s[q] >= thr_s[q]);
+            if (hit) {
 #pragma unroll
-                    for (int q = 0; q < NQ; q++) acc[rr][q] = acc[rr][q] + __shfl_xor(acc[rr][q], m, 64);
+                for (int rr = 0; rr < R; rr++) {
+                    const int64_t r = rbase + ((int64_t)group * R + rr) * tw;
+                    if (r < a.n_rows) {
+#pragma unroll
+                        for (int q = 0; q < NQ; q++)
+                            if (r < a.k[q / 3]) multi_offer(readlane_f64(s[q], 16 * rr), r, K, lane, mylists + q * K, thr_s[q]);
+                    }
+                }
+            }
 #pragma unroll
             for (int rr = 0; rr < R; rr++)
 #pragma unroll
-                for (int q = 0; q < NQ; q++) {
-                    double v = acc[rr][q];
-                    v = v + dpp_f64<0x128>(v);
-                    v = v + dpp_f64<0x124>(v);
-                    v = v + dpp_f64<0x4E>(v);
-                    v = v + dpp_f64<0xB1>(v);
-                    acc[rr][q] = v;
-                }
-#pragma unroll
-            for (int rr = 0; rr < R; rr++) {
-                const int64_t r = rbase + ((int64_t)group * R + rr) * tw;
-                if (r < a.n_rows) {
-#pragma unroll
-                    for (int q = 0; q < NQ; q++)
-                        if (r < a.k[q / 3]) multi_offer(readlane_f64(acc[rr][q], 0), r, K, lane, mylists + q * K, thr_s[q]);
-                }
-#pragma unroll
                 for (int q = 0; q < NQ; q++) acc[rr][q] = 0.0;
-            }
             b = 0;
             group++;
         }

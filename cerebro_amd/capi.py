@@ -207,6 +207,7 @@ _SIGS = {
     "chip_debug_coalesce_decide": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "chip_debug_last_scan": (C.c_int, [_P, C.POINTER(ScanLaunch)]),
     "chip_debug_scan_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(ScanLaunch)]),
+    "chip_debug_multi_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(ScanLaunch)]),
     "chip_orb_match": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P]),
     "chip_gms_filter": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P,
                                   C.POINTER(C.c_int32)]),
@@ -313,6 +314,18 @@ def scan_plan(D: int, elem: int, nq: int, K: int, n_rows: int, call: int = CHIP_
         return rc, out.as_dict()
     if rc != CHIP_OK:
         raise ChipError(rc, "chip_debug_scan_plan")
+    return out.as_dict()
+
+
+def multi_plan(D: int, elem: int, n_ticks: int, K: int = CHIP_DEFAULT_TOPK, n_cus: int = 256, check: bool = True):
+    """chip_debug_multi_plan: the pass that serves n_ticks pipelined ticks together on a plain single-GPU ctx, as ScanLaunch.as_dict() (q64 =
+    queries staged as fp64, NG = queries read in place) -- no device needed.  check=False: (status, dict) instead of raising."""
+    out = ScanLaunch()
+    rc = load_library().chip_debug_multi_plan(D, elem, n_ticks, K, n_cus, C.byref(out))
+    if not check:
+        return rc, out.as_dict()
+    if rc != CHIP_OK:
+        raise ChipError(rc, "chip_debug_multi_plan")
     return out.as_dict()
 
 

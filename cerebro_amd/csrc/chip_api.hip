@@ -579,7 +579,7 @@ static int tick_submit(Ctx *c, int64_t k, int64_t l, const chip_dot_params *p, c
 //   * a scan running: park; the T_max-th parked tick sends all of them off as one pass;
 //   * nothing stays parked while its caller can no longer release it -- see coalesce_flush's callers (listed in cerebro_hip.h).
 // Only long scans (beyond scan_overlap_bytes: the launches that run alone on the scan stream) of a plain single-GPU ctx on its
-// own streams, float rows.  The synchronous tick, the fused / resident short ticks and the paced figures never come here.
+// own streams, float or double rows (scan_multi_plan says which D).  The synchronous tick, the fused / resident short ticks and the paced figures never come here.
 int coalesce_decide(int n_parked, int t_max, bool scan_running)
 {
     if (t_max < 2) return kCoalesceLaunch;
@@ -597,7 +597,7 @@ static int coalesce_ticks_max(const Ctx *c, int64_t k, bool sync_tick)
     return t >= 2 ? t : 0;
 }
 
-// T >= 2 parked ticks as one pass: one launch of db_scan_topk_multi on the scan stream, then K2 once per tick on the ctx stream,
+// T >= 2 parked ticks as one pass: one launch of db_scan_topk_multi / db_scan_shared_f64 on the scan stream, then K2 once per tick on the ctx stream,
 // each on its own block of lists and followed by its slot's completion event.
 static int coalesce_submit(Ctx *c, int T)
 {
@@ -1415,6 +1415,15 @@ int chip_debug_scan_plan(int32_t D, int32_t elem, int32_t nq, int32_t K, int64_t
     chip_tick_result dummy;
     if (scan_tick_fused(c.get(), same_stream, a, tick, nq)) { a.K = 1; a.fused_result = &dummy; }
     return scan_select(c.get(), a, nq, grid, out);
+}
+
+// The shared pass of n_ticks pipelined ticks without a device: scan_multi_plan, the function launch_scan_multi sizes itself with, for a plain
+// single-GPU ctx of n_cus compute units.
+int chip_debug_multi_plan(int32_t D, int32_t elem, int32_t n_ticks, int32_t K, int32_t n_cus, chip_debug_scan_launch *out)
+{
+    if (!out || D <= 0 || (elem != 4 && elem != 8) || n_ticks < 1 || K < 1 || K > CHIP_MAX_TOPK || n_cus < 1) return CHIP_ERR_INVALID_ARG;
+    if (D % 4 != 0 || (size_t)D * 4 * CHIP_MAX_NQ > 160 * 1024 || (elem == 8 && (size_t)D * 8 * 2 > 160 * 1024)) return CHIP_ERR_UNSUPPORTED;   // (ctx_create)
+    return scan_multi_plan(D, elem, n_ticks, K, n_cus < 512 ? n_cus : 512, out);
 }
 
 // Tuning aid, not part of the ABI (no declaration in cerebro_hip.h): with CHIP_SCAN_STAMPS=1 the row-batched scan kernel leaves four

@@ -75,16 +75,16 @@ struct ResidentArgs {
 };
 
 // ---- several ticks in one DB pass (kernels.hip db_scan_topk_multi, chip_api.hip coalesce_*) ----
-constexpr int kMultiMaxTicks = 3;                   // ticks of 3 queries each that one pass can serve (9 fp32 queries of 4096 elements = 144 KiB of LDS)
+constexpr int kMultiMaxTicks = 3;                   // ticks of 3 queries each that one pass can serve (9 fp32 queries of 4096 elements = 144 KiB of LDS; double rows: 2)
 struct MultiScanArgs {
-    const void *const *seg_table;                   // as ScanArgs (plain single-GPU ctx, float rows: global index == local row)
+    const void *const *seg_table;                   // as ScanArgs (plain single-GPU ctx: global index == local row)
     int32_t seg_shift;
     int64_t seg_mask;
     int64_t n_rows;                                 // rows [0, n_rows) are read: the longest prefix of the pass
     int32_t D;
     int32_t K;
     int64_t k[kMultiMaxTicks];                      // tick t sees rows [0, k[t])
-    const void *q[3 * kMultiMaxTicks];              // queries of tick t: q[3 t .. 3 t + 2] (device, float, D each, 16-B aligned)
+    const void *q[3 * kMultiMaxTicks];              // queries of tick t: q[3 t .. 3 t + 2] (device, the rows' type, D each, 16-B aligned)
     chip_topk_entry *partial;                       // [tick][gridDim.x][3][K]: every tick's block of lists is what ONE launch of db_scan_topk leaves
 };
 
@@ -145,7 +145,9 @@ private:
 int launch_resident(Ctx *c, hipStream_t s, const ResidentArgs &ra, int grid);   // CHIP_ERR_UNSUPPORTED in a build without the rows form
 int launch_scan(Ctx *c, hipStream_t s, const ScanArgs &a, int nq, int grid);
 int launch_merge(Ctx *c, hipStream_t s, const MergeArgs &a, int nq);
-int scan_multi_max_ticks(const Ctx *c);   // ticks one pass of db_scan_topk_multi can serve on this ctx (0 / 2 / 3: storage type, D, LDS)
+int scan_multi_max_ticks(const Ctx *c);   // ticks one shared pass can serve on this ctx (0 / 2 / 3: storage type, D, LDS)
+// the shared pass for n_ticks ticks over rows of D elements of elem bytes: staged (q64, double rows) / in-place (NG) queries, LDS, shape -- or CHIP_ERR_UNSUPPORTED
+int scan_multi_plan(int D, int elem, int n_ticks, int K, int grid, chip_debug_scan_launch *f);
 int scan_multi_grid(const Ctx *c);
 int launch_scan_multi(Ctx *c, hipStream_t s, const MultiScanArgs &a, int n_ticks, int grid);
 int scan_grid_for(const Ctx *c, int64_t n_rows, int nq, bool q64);

@@ -607,6 +607,225 @@ __global__ __launch_bounds__(kMultiBlock) __attribute__((amdgpu_num_vgpr(kMultiV
                          [&](int q) { return a.partial + (((int64_t)(q / 3) * gridDim.x + blockIdx.x) * 3 + q % 3) * K; });
 }
 
+// ------------------------------------------------------------------------------------------------ K1, several ticks per pass, double rows
+// db_scan_shared_f64<T, NG>: the shared pass for DOUBLE rows (ReljaNetVLAD: 32 KiB rows at D = 4096, twice the bytes of a float tick).  Blocking,
+// row -> wave map, load slots, lists, thresholds and output are db_scan_topk_multi's; a 1 KiB slot holds 2 doubles per lane, a batch 512 elements.
+//   * same bits: lane L accumulates elements j*128 + 2L + c (j ascending, c = 0, 1) by fma into one fp64 accumulator -- rows_dot<double>'s order,
+//     the oracle's orc_dot_tree_f64 -- then the same transposed pairing tree as the float kernel;
+//   * no conversion: the statement that waits for a slot copies it out (2 x v_mov_b64) and the slot is loaded again in the next statement;
+//   * the 3T fp64 queries do not fit the LDS (T x 96 KiB at D = 4096).  The first NS = 3T - NG are staged ([NS][D] doubles, ds_read_b128, read two
+//     vectors ahead); the last NG are read IN PLACE from global memory, as db_scan_topk_wide does: every wave of the launch reads the same bytes, so
+//     they come out of the L2, in the same per-lane element order, hence the same bits.  Vector loads return in order and share vmcnt with the row
+//     stream, so an in-place query vector is one more slot OF that stream: its 1 KiB for (batch, KiB u) sits in asm-owned registers below the row
+//     slots (v[192 - 16 NG ..]), is issued right behind the four row slots of the same (batch, u) -- one batch ahead of its use, like them -- and
+//     is loaded again in the statement after the one that copied it out.  The stream of a wave is r0 r1 r2 r3 g0 .. g(NG-1) per KiB, L = 4 (4 + NG)
+//     loads in flight, and EVERY wait of the loop is vmcnt(L - 1): the load waited for is always the oldest one.
+// Registers: the compiler owns v[0 .. 160): acc[4][3T] (48 at T = 2) + the 16 of a row KiB + 4 of a query vector + 12 of the LDS read-ahead.
+// T = 3 needs NG = 5 at D = 4096: 80 registers of query slots leave the compiler v[0 .. 112) for 72 of accumulators and everything else.  Compiled
+// that way the kernel spills 90 registers (560 bytes of scratch per lane); a scratch access drains the stream, so it is dropped (kSharedF64MaxTicks).
+constexpr int kSharedMaxNG = 2;          // in-place queries of the instantiations that are built: D <= 4608 at T = 2
+constexpr int kSharedF64MaxTicks = 2;
+constexpr int kSharedVgprBase = kMultiVgprBase - 4 * kMultiU * kSharedMaxNG;   // 160: what the compiler owns in every instantiation (the attribute takes no template argument)
+__host__ __device__ constexpr int shared_qslot_base(int ng) { return kMultiVgprBase - 4 * kMultiU * ng; }
+// KiB u of the batch of in-place query g -> v[reg : reg + 3]
+__host__ __device__ constexpr int shared_qslot_reg(int ng, int u, int g) { return shared_qslot_base(ng) + 4 * (u * ng + g); }
+
+// 1 KiB (16 bytes per lane) into a slot: rows non-temporal (read once), in-place queries cached (every wave reads them)
+template <int REG, int OFF, bool NTL>
+__device__ __forceinline__ void shared_issue(uint32_t voff, const double *base_uniform)
+{
+    if constexpr (NTL)
+        asm volatile("global_load_dwordx4 v[%2:%3], %0, %1 offset:%4 nt" ::"v"(voff), "s"(base_uniform), "n"(REG), "n"(REG + 3), "n"(OFF) : "memory");
+    else
+        asm volatile("global_load_dwordx4 v[%2:%3], %0, %1 offset:%4" ::"v"(voff), "s"(base_uniform), "n"(REG), "n"(REG + 3), "n"(OFF) : "memory");
+}
+// wait until at most CNT loads of the stream are outstanding, then hand the slot's two doubles to the compiler: the slot may be loaded again
+template <int REG, int CNT>
+__device__ __forceinline__ void shared_take(double (&d)[2])
+{
+    asm volatile("s_waitcnt vmcnt(%2)\n\tv_mov_b64 %0, v[%3:%4]\n\tv_mov_b64 %1, v[%5:%6]"
+                 : "=&v"(d[0]), "=&v"(d[1])
+                 : "n"(CNT), "n"(REG), "n"(REG + 1), "n"(REG + 2), "n"(REG + 3)
+                 : "memory");
+}
+
+template <int NTICKS, int NG>
+__global__ __launch_bounds__(kMultiBlock) __attribute__((amdgpu_num_vgpr(kSharedVgprBase / 2))) void db_scan_shared_f64(MultiScanArgs a)
+{
+    constexpr int NQ = 3 * NTICKS, NS = NQ - NG, R = kMultiR, U = kMultiU;
+    constexpr int L = U * (R + NG);        // loads of the stream in flight
+    static_assert(NG >= 0 && NG <= kSharedMaxNG && NS >= 2 && L <= 64, "at least two staged queries (the LDS read-ahead), vmcnt counts to 63");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    asm volatile("" ::: CHIP_MULTI_CLOBBERS);                       // makes the code object allocate the asm-owned registers
+    double *qs = reinterpret_cast<double *>(smem);  // [NS][D]
+    const int D = a.D;
+    const int K = a.K;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wpb = blockDim.x >> 6;
+
+    for (int e = tid * 2; e < D; e += blockDim.x * 2) {
+        f64x2 w[NS];
+#pragma unroll
+        for (int q = 0; q < NS; q++) w[q] = *as_global(reinterpret_cast<const f64x2 *>(static_cast<const double *>(a.q[q]) + e));
+#pragma unroll
+        for (int q = 0; q < NS; q++) *reinterpret_cast<f64x2 *>(qs + q * D + e) = w[q];
+    }
+    __syncthreads();
+    const double *qg[NG > 0 ? NG : 1];   // the queries read in place (SGPRs)
+#pragma unroll
+    for (int g = 0; g < NG; g++) qg[g] = uniform_ptr(static_cast<const double *>(a.q[NS + g]));
+
+    chip_topk_entry *lists = reinterpret_cast<chip_topk_entry *>(smem + (size_t)NS * D * sizeof(double));   // [wave][3T][K], as db_scan_topk_multi
+    chip_topk_entry *mylists = lists + (size_t)wave * NQ * K;
+    double thr_s[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; q++) {
+        thr_s[q] = -INFINITY;
+        if (lane < K) { chip_topk_entry t; t.score = -INFINITY; t.idx = -1; mylists[q * K + lane] = t; }
+    }
+
+    // The (group, batch) walk of db_scan_topk_multi.  Nothing is loaded from outside rows [0, n_rows) and the NG query vectors: every row base comes
+    // from row_of(), every offset (rows and queries alike: both are D doubles) is below one row's length.
+    const int64_t tw = (int64_t)gridDim.x * wpb;
+    const int64_t rbase = (int64_t)blockIdx.x * wpb + wave;
+    const int nb = D / (128 * U);
+    const int ngroups = rbase < a.n_rows ? (int)((a.n_rows - 1 - rbase) / (R * tw)) + 1 : 0;
+    const int total = ngroups * nb;
+    const uint32_t lane_off = (uint32_t)lane * 16u;
+    const int e0 = lane * 2;
+    auto row_of = [&](int group, int rr) {
+        const int64_t r = rbase + ((int64_t)group * R + rr) * tw;
+        return uniform_ptr(row_base_uniform<double>(a, r < a.n_rows ? r : rbase));
+    };
+    const double *row[R], *nrow[R];
+#define CHIP_SHARED_ISSUE_ROW(u, rr, voff) shared_issue<multi_slot_reg(u, rr), (u) * 1024, true>(voff, row[rr])
+#define CHIP_SHARED_ISSUE_Q(u, g, voff) do { if constexpr ((g) < NG) shared_issue<shared_qslot_reg(NG, u, (g) < NG ? (g) : 0), (u) * 1024, false>(voff, qg[(g) < NG ? (g) : 0]); } while (0)
+#define CHIP_SHARED_ISSUE_SLOT(u, voff) do { CHIP_SHARED_ISSUE_ROW(u, 0, voff); CHIP_SHARED_ISSUE_ROW(u, 1, voff); CHIP_SHARED_ISSUE_ROW(u, 2, voff); CHIP_SHARED_ISSUE_ROW(u, 3, voff); \
+                                             CHIP_SHARED_ISSUE_Q(u, 0, voff); CHIP_SHARED_ISSUE_Q(u, 1, voff); } while (0)
+    static_assert(kSharedMaxNG == 2, "CHIP_SHARED_ISSUE_SLOT / CHIP_SHARED_TAKE_QS name the in-place queries one by one");
+    if (total > 0) {
+#pragma unroll
+        for (int rr = 0; rr < R; rr++) { row[rr] = row_of(0, rr); nrow[rr] = row[rr]; }
+        if (ngroups > 1) {
+#pragma unroll
+            for (int rr = 0; rr < R; rr++) nrow[rr] = row_of(1, rr);
+        }
+        CHIP_SHARED_ISSUE_SLOT(0, lane_off); CHIP_SHARED_ISSUE_SLOT(1, lane_off); CHIP_SHARED_ISSUE_SLOT(2, lane_off); CHIP_SHARED_ISSUE_SLOT(3, lane_off);
+    }
+
+    double acc[R][NQ];
+#pragma unroll
+    for (int rr = 0; rr < R; rr++)
+#pragma unroll
+        for (int q = 0; q < NQ; q++) acc[rr][q] = 0.0;
+
+    // One batch per iteration; what the slots load next is what db_scan_topk_multi's load next (the next batch of the group, the first batch of the
+    // next group, at the wave's last batch the first KiBs of its rows and queries once more).  Per KiB u: the four row slots are taken and loaded
+    // again, the NS staged queries are multiplied in, then each in-place query is taken, loaded again and multiplied in.
+    int b = 0, group = 0;
+    for (int t = 0; t < total; t++) {
+        const int base = b * (128 * U);
+        uint32_t noff = (uint32_t)(base + 128 * U) * 8u;
+        if (b + 1 == nb) {
+            noff = 0;
+            if (group + 1 < ngroups) {
+#pragma unroll
+                for (int rr = 0; rr < R; rr++) row[rr] = nrow[rr];
+                if (group + 2 < ngroups) {
+#pragma unroll
+                    for (int rr = 0; rr < R; rr++) nrow[rr] = row_of(group + 2, rr);
+                }
+            }
+        }
+        {
+            constexpr int S = U * NQ, SS = U * NS;
+            const double *qv = qs + base + e0;
+            const uint32_t voff = noff + lane_off;
+            f64x2 w[SS];        // staged query vectors in the order they are used: (u, q < NS)
+            w[0] = *reinterpret_cast<const f64x2 *>(qv);
+            w[1] = *reinterpret_cast<const f64x2 *>(qv + D);
+            double x[R][2];
+#pragma unroll
+            for (int s = 0; s < S; s++) {
+                const int u = s / NQ, q = s % NQ;
+                if (q == 0) {
+#define CHIP_SHARED_TAKE_ROW(uu, rr) if (u == uu) { shared_take<multi_slot_reg(uu, rr), L - 1>(x[rr]); CHIP_SHARED_ISSUE_ROW(uu, rr, voff); }
+#define CHIP_SHARED_TAKE_SLOT(uu) CHIP_SHARED_TAKE_ROW(uu, 0) CHIP_SHARED_TAKE_ROW(uu, 1) CHIP_SHARED_TAKE_ROW(uu, 2) CHIP_SHARED_TAKE_ROW(uu, 3)
+                    CHIP_SHARED_TAKE_SLOT(0) CHIP_SHARED_TAKE_SLOT(1) CHIP_SHARED_TAKE_SLOT(2) CHIP_SHARED_TAKE_SLOT(3)
+#undef CHIP_SHARED_TAKE_SLOT
+#undef CHIP_SHARED_TAKE_ROW
+                }
+                double wd[2];
+                if (q < NS) {
+                    const int i = u * NS + q;
+                    if (i + 2 < SS) w[i + 2] = *reinterpret_cast<const f64x2 *>(qv + ((i + 2) % NS) * D + ((i + 2) / NS) * 128);
+                    wd[0] = w[i][0];
+                    wd[1] = w[i][1];
+                } else {
+#define CHIP_SHARED_TAKE_Q(uu, gg) if constexpr ((gg) < NG) { if (u == uu && q - NS == (gg)) { shared_take<shared_qslot_reg(NG, uu, (gg) < NG ? (gg) : 0), L - 1>(wd); CHIP_SHARED_ISSUE_Q(uu, gg, voff); } }
+#define CHIP_SHARED_TAKE_QS(uu) CHIP_SHARED_TAKE_Q(uu, 0) CHIP_SHARED_TAKE_Q(uu, 1)
+                    CHIP_SHARED_TAKE_QS(0) CHIP_SHARED_TAKE_QS(1) CHIP_SHARED_TAKE_QS(2) CHIP_SHARED_TAKE_QS(3)
+#undef CHIP_SHARED_TAKE_QS
+#undef CHIP_SHARED_TAKE_Q
+                }
+#pragma unroll
+                for (int c = 0; c < 2; c++) {
+#pragma unroll
+                    for (int rr = 0; rr < R; rr++) acc[rr][q] = __builtin_fma(wd[c], x[rr][c], acc[rr][q]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        if (++b == nb) {
+            // the rows of this group are complete: db_scan_topk_multi's transposed pairing tree and its offers, statement for statement
+            static_assert(R == 4, "the transposed reduction folds four rows into the four 16-lane rows of a wave");
+            double s[NQ];
+#pragma unroll
+            for (int q = 0; q < NQ; q++) {
+                swap32_f64(acc[0][q], acc[2][q]);
+                swap32_f64(acc[1][q], acc[3][q]);
+                double p02 = acc[0][q] + acc[2][q], p13 = acc[1][q] + acc[3][q];
+                swap16_f64(p02, p13);
+                double v = p02 + p13;
+                v = v + dpp_f64<0x128>(v);
+                v = v + dpp_f64<0x124>(v);
+                v = v + dpp_f64<0x4E>(v);
+                v = v + dpp_f64<0xB1>(v);
+                s[q] = v;
+            }
+            unsigned long long hit = 0;
+#pragma unroll
+            for (int q = 0; q < NQ; q++) hit |= __ballot(s[q] >= thr_s[q]);
+            if (hit) {
+#pragma unroll
+                for (int rr = 0; rr < R; rr++) {
+                    const int64_t r = rbase + ((int64_t)group * R + rr) * tw;
+                    if (r < a.n_rows) {
+#pragma unroll
+                        for (int q = 0; q < NQ; q++)
+                            if (r < a.k[q / 3]) multi_offer(readlane_f64(s[q], 16 * rr), r, K, lane, mylists + q * K, thr_s[q]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int rr = 0; rr < R; rr++)
+#pragma unroll
+                for (int q = 0; q < NQ; q++) acc[rr][q] = 0.0;
+            b = 0;
+            group++;
+        }
+    }
+#undef CHIP_SHARED_ISSUE_SLOT
+#undef CHIP_SHARED_ISSUE_Q
+#undef CHIP_SHARED_ISSUE_ROW
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the read-ahead of the wave's last batch
+
+    block_merge_cand<NQ>(lists, K, lane, wave, wpb,
+                         [&](int q) { return a.partial + (((int64_t)(q / 3) * gridDim.x + blockIdx.x) * 3 + q % 3) * K; });
+}
+
 // ------------------------------------------------------------------------------------------------ K1, wide double rows
 // Double rows whose NQ query descriptors do not fit the 160 KiB of LDS (the reference's default D = 8192, src/Cerebro.cpp:1021, as a
 // MatrixXd of genuine float64 values: 3 x 8192 x 8 B = 192 KiB).  The first NQ - NG queries are staged as usual; the last NG are read
@@ -1597,49 +1816,83 @@ int launch_scan(Ctx *c, hipStream_t s, const ScanArgs &a, int nq, int grid)
     return CHIP_OK;
 }
 
-// Several ticks per pass (db_scan_topk_multi).  How many ticks one pass can serve on this ctx: float rows of whole 4 KiB batches
-// on a plain ctx whose 3 T staged fp32 queries fit the LDS (D = 4096: 3; D = 8192: none) -- 0 when there is no such form.
-int scan_multi_max_ticks(const Ctx *c)
+// Several ticks per pass (db_scan_topk_multi for float rows, db_scan_shared_f64 for double rows).  The ONE place that sizes such a pass: which
+// queries are staged and how much LDS the launch asks for, from D, the storage type, the ticks and K alone -- launch_scan_multi launches what
+// this says, scan_multi_max_ticks asks it which T a ctx can be served with, chip_debug_multi_plan hands it out without a device.
+//   float rows : whole 4 KiB batches; all 3 T queries staged as fp32 (D = 4096: T <= 3; D = 8192: none);
+//   double rows: whole 4 KiB batches (D % 512 == 0), T = 2; as many of the 6 fp64 queries staged as fit next to the lists, the other NG <= 2
+//                read in place (D <= 3072: NG = 0; D = 3584: 1; D = 4096, 4608: 2; wider rows: no such form).
+int scan_multi_plan(int D, int elem, int n_ticks, int K, int grid, chip_debug_scan_launch *f)
 {
-    if (c->elem != 4 || (int64_t)c->D * 4 % 4096 != 0 || c->nranks != 1 || c->scan_variant != 0 || c->scan_rows > 0) return 0;
-    // per tick: 3 fp32 queries and the 8 waves' 3 running lists of CHIP_DEFAULT_TOPK entries (the K the tick path asks for)
-    const int fit = (int)((160 * 1024) / ((size_t)3 * c->D * 4 + (size_t)(kMultiBlock / 64) * 3 * CHIP_DEFAULT_TOPK * sizeof(chip_topk_entry)));
-    return fit >= kMultiMaxTicks ? kMultiMaxTicks : (fit >= 2 ? fit : 0);
+    *f = chip_debug_scan_launch{};
+    if (D < 1 || (elem != 4 && elem != 8) || n_ticks < 2 || n_ticks > kMultiMaxTicks || K < 1 || K > CHIP_MAX_TOPK || grid < 1 || grid > 512 ||
+        (int64_t)D * elem % 4096 != 0)
+        return CHIP_ERR_UNSUPPORTED;
+    const int nq = 3 * n_ticks;
+    const size_t kLds = 160 * 1024, lists = (size_t)(kMultiBlock / 64) * nq * K * sizeof(chip_topk_entry);   // [wave][3T][K] behind the queries
+    int staged = nq;
+    if (elem == 8) {
+        if (n_ticks > kSharedF64MaxTicks) return CHIP_ERR_UNSUPPORTED;
+        const size_t fit = (kLds - lists) / ((size_t)D * 8);
+        if (fit < (size_t)nq) staged = (int)fit;
+        if (nq - staged > kSharedMaxNG) return CHIP_ERR_UNSUPPORTED;   // wider rows: more in-place queries than an instantiation exists for
+    }
+    const size_t lds = (size_t)staged * D * elem + lists;
+    if (lds > kLds) return CHIP_ERR_UNSUPPORTED;
+    f->family = CHIP_SCAN_FAMILY_MULTI;
+    f->elem = elem;
+    f->nq = nq;
+    f->K = K;
+    f->U = kMultiU;
+    f->FULL = 1;
+    f->R = kMultiR;
+    f->NTL = 1;
+    f->ticks = n_ticks;
+    f->q64 = elem == 8 ? staged : 0;   // queries staged as fp64 (float rows stage fp32)
+    f->NG = nq - staged;
+    f->grid = grid;
+    f->block = kMultiBlock;
+    f->wg_per_cu = 1;
+    f->lds_bytes = (int32_t)lds;
+    return CHIP_OK;
 }
 
 int scan_multi_grid(const Ctx *c) { return c->n_cus < c->max_grid ? c->n_cus : c->max_grid; }   // one 8-wave workgroup per CU
 
-template <int NTICKS>
-static int launch_scan_multi_t(Ctx *c, hipStream_t s, const MultiScanArgs &a, int grid, size_t lds)
+// How many ticks one pass can serve on this ctx, with the K the tick path asks for: 0 when there is no such form.
+int scan_multi_max_ticks(const Ctx *c)
 {
-    CHIP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(db_scan_topk_multi<NTICKS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((db_scan_topk_multi<NTICKS>), dim3(grid), dim3(kMultiBlock), lds, s, a);
+    if (c->nranks != 1 || c->scan_variant != 0 || c->scan_rows > 0) return 0;
+    chip_debug_scan_launch f;
+    for (int t = kMultiMaxTicks; t >= 2; t--)
+        if (scan_multi_plan(c->D, c->elem, t, CHIP_DEFAULT_TOPK, scan_multi_grid(c), &f) == CHIP_OK) return t;
+    return 0;
+}
+
+template <class Kernel>
+static int launch_scan_multi_k(Ctx *c, hipStream_t s, Kernel kernel, const MultiScanArgs &a, int grid, int lds)
+{
+    CHIP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kMultiBlock), lds, s, a);
     CHIP_HIP(c, hipGetLastError());
     return CHIP_OK;
 }
 
 int launch_scan_multi(Ctx *c, hipStream_t s, const MultiScanArgs &a, int n_ticks, int grid)
 {
-    // the staged queries and, behind them, the waves' running lists ([wave][3T][K]: 9 KiB at T = 3, K = 8; a K that does not fit is refused)
-    const size_t lds = (size_t)3 * n_ticks * a.D * 4 + (size_t)(kMultiBlock / 64) * 3 * n_ticks * a.K * sizeof(chip_topk_entry);
-    if (n_ticks < 2 || n_ticks > scan_multi_max_ticks(c) || lds > 160 * 1024 || grid < 1 || grid > c->max_grid || a.K < 1 || a.K > CHIP_MAX_TOPK)
+    chip_debug_scan_launch f;
+    if (n_ticks > scan_multi_max_ticks(c) || grid > c->max_grid || scan_multi_plan(c->D, c->elem, n_ticks, a.K, grid, &f) != CHIP_OK)
         return CHIP_ERR_UNSUPPORTED;
-    const int rc = n_ticks == 2 ? launch_scan_multi_t<2>(c, s, a, grid, lds) : launch_scan_multi_t<3>(c, s, a, grid, lds);
+    int rc = CHIP_ERR_UNSUPPORTED;
+    if (c->elem == 4) {
+        rc = n_ticks == 2 ? launch_scan_multi_k(c, s, db_scan_topk_multi<2>, a, grid, f.lds_bytes) : launch_scan_multi_k(c, s, db_scan_topk_multi<3>, a, grid, f.lds_bytes);
+    } else if (n_ticks == 2) {
+        static_assert(kSharedF64MaxTicks == 2 && kSharedMaxNG == 2, "the instantiations below");
+        if (f.NG == 0) rc = launch_scan_multi_k(c, s, db_scan_shared_f64<2, 0>, a, grid, f.lds_bytes);
+        else if (f.NG == 1) rc = launch_scan_multi_k(c, s, db_scan_shared_f64<2, 1>, a, grid, f.lds_bytes);
+        else if (f.NG == 2) rc = launch_scan_multi_k(c, s, db_scan_shared_f64<2, 2>, a, grid, f.lds_bytes);
+    }
     if (rc != CHIP_OK) return rc;
-    chip_debug_scan_launch f{};
-    f.family = CHIP_SCAN_FAMILY_MULTI;
-    f.elem = 4;
-    f.nq = 3 * n_ticks;
-    f.K = a.K;
-    f.U = kMultiU;
-    f.FULL = 1;
-    f.R = kMultiR;
-    f.NTL = 1;
-    f.ticks = n_ticks;
-    f.grid = grid;
-    f.block = kMultiBlock;
-    f.wg_per_cu = 1;
-    f.lds_bytes = (int32_t)lds;
     f.n_rows = a.n_rows;
     f.launches = c->last_scan.launches + 1;
     c->last_scan = f;

@@ -256,10 +256,12 @@ int chip_resident_resume(chip_ctx *ctx);
  * back to back on an internal stream; the one-workgroup merge of tick i (ctx stream) overlaps the scan of tick i+1.
  *
  * Ticks that share a DB pass.  Queued ticks do not depend on one another (status and last_l are settled at enqueue, the queries
- * are published rows), so on a plain single-GPU ctx with float rows, on its own streams, an enqueue over a LONG prefix (beyond
+ * are published rows), so on a plain single-GPU ctx with float or double rows, on its own streams, an enqueue over a LONG prefix (beyond
  * CHIP_SCAN_OVERLAP_GIB, 8 GiB) that finds a scan of the ctx still running PARKS its tick instead of launching it; parked ticks
  * leave together as ONE pass over [0, max k) with 3 T queries (T <= CHIP_TICK_COALESCE, default 3; 0 = off), every tick seeing
- * only its own prefix [0, k_t).  Results, status codes, CHIP_ERR_BUSY, last_l, chip_loop_reset, skipped / too-short ticks in
+ * only its own prefix [0, k_t).  Which rows: whole 4 KiB batches -- float rows with D % 1024 == 0 whose 3 T queries fit the LDS (D = 4096:
+ * T <= 3), double rows with D % 512 == 0 up to D = 4608, T = 2 (the queries that do not fit the LDS are read in place, out of the L2);
+ * chip_debug_multi_plan says what a given shape gets.  Every other ctx launches its ticks one by one.  Results, status codes, CHIP_ERR_BUSY, last_l, chip_loop_reset, skipped / too-short ticks in
  * between, appends between enqueue and collect and out-of-order collects are exactly those of ticks launched one by one.  A tick
  * that arrives while no scan is running is launched at once, alone; chip_loop_tick, short prefixes and caller-supplied streams
  * (chip_set_stream) never park.  Nothing stays parked while its caller cannot release it.  Parked ticks are submitted by:
@@ -296,7 +298,7 @@ int chip_debug_coalesce_decide(int32_t n_parked, int32_t t_max, int32_t scan_run
 #define CHIP_SCAN_FAMILY_ONE_ROW 1   /* db_scan_topk<T, NQ, U, FULL, NT, 1>: one row per wave at a time                          */
 #define CHIP_SCAN_FAMILY_WIDE    2   /* db_scan_topk_wide<NQ, NG, FULL>: double rows, NG of the NQ queries read in place           */
 #define CHIP_SCAN_FAMILY_ROWS    3   /* db_scan_topk_rows<T, NQ, R, NTL>: R rows per wave in flight; carries the fused tick        */
-#define CHIP_SCAN_FAMILY_MULTI   4   /* db_scan_topk_multi<T>: `ticks` pipelined ticks of three queries share one pass             */
+#define CHIP_SCAN_FAMILY_MULTI   4   /* db_scan_topk_multi<T> / db_scan_shared_f64<T, NG>: `ticks` pipelined ticks share one pass     */
 #define CHIP_SCAN_CALL_QUERY      0  /* chip_query_rows / chip_query_vectors_*: lists out                                         */
 #define CHIP_SCAN_CALL_TICK       1  /* chip_loop_tick_enqueue: a pipelined tick                                                   */
 #define CHIP_SCAN_CALL_TICK_SYNC  2  /* chip_loop_tick: the synchronous tick                                                       */
@@ -306,10 +308,10 @@ typedef struct {
     int32_t nq, K;         /* queries of the launch (multi: 3 per tick) and list entries kept per query (a fused tick keeps 1)     */
     int32_t U, NT, FULL;   /* one-row: 16-byte loads per lane and batch, load path (1 builtin, 6 asm-issued, 8 asm-issued with fp64-staged
                               queries), rows of whole batches;  wide / multi: FULL / U alone                                       */
-    int32_t NG;            /* wide: queries read in place                                                                          */
+    int32_t NG;            /* wide / multi (double rows): queries read in place                                                    */
     int32_t R, NTL;        /* rows / multi: rows per wave and pass;  rows: 1 non-temporal loads                                    */
     int32_t ticks;         /* multi: ticks served by the pass                                                                      */
-    int32_t q64;           /* queries staged in LDS as fp64                                                                        */
+    int32_t q64;           /* queries staged in LDS as fp64 (multi, double rows: how many of the nq)                               */
     int32_t claimed;       /* rows: the waves of a workgroup claim their rows from a counter instead of the static map            */
     int32_t fused;         /* rows: the launch writes the tick's decision record itself, no merge kernel follows                   */
     int32_t grid, block;   /* workgroups, threads per workgroup                                                                    */
@@ -321,6 +323,11 @@ typedef struct {
 int chip_debug_last_scan(chip_ctx *ctx, chip_debug_scan_launch *out);
 int chip_debug_scan_plan(int32_t D, int32_t elem, int32_t nq, int32_t K, int64_t n_rows, int32_t call, int32_t n_cus,
                          chip_debug_scan_launch *out);
+/* The shared pass of n_ticks pipelined ticks (family CHIP_SCAN_FAMILY_MULTI) without a device or a ctx, from the function the launch
+ * sizes itself with: nq = 3 n_ticks, ticks, R, q64 = queries staged in LDS as fp64 (double rows; float rows stage all of theirs as fp32),
+ * NG = queries read in place, lds_bytes (queries + the waves' lists of K entries), grid (one workgroup per compute unit) and block.
+ * CHIP_ERR_UNSUPPORTED where a plain single-GPU ctx of that shape has no such pass and launches its ticks one by one (ABI 7, additive). */
+int chip_debug_multi_plan(int32_t D, int32_t elem, int32_t n_ticks, int32_t K, int32_t n_cus, chip_debug_scan_launch *out);
 
 /* Sharded tick, three phases (host does the exchange between 1 and 2):
  *  1. chip_scan_local: scan this rank's share of rows [0,k), k = l - lag, for the three queries l-1,l-2,l-3 and

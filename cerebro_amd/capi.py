@@ -177,6 +177,7 @@ _SIGS = {
     "chip_query_vectors_f64": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P]),
     "chip_query_scores": (C.c_int, [_P, C.c_int64, C.c_int64, _P]),
     "chip_query_batch_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P]),
+    "chip_query_batch_cast_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P]),
     "chip_dot_params_default": (None, [C.POINTER(DotParams)]),
     "chip_loop_tick": (C.c_int, [_P, C.c_int64, C.POINTER(DotParams), C.POINTER(TickResult)]),
     "chip_resident_pause": (C.c_int, [_P]),
@@ -489,13 +490,15 @@ class Chip:
                   "chip_query_vectors_f32")
         return sc, ix
 
-    def query_batch(self, k: int, q: np.ndarray, topk: int = CHIP_DEFAULT_TOPK):
-        """many-query fp32 MFMA mode: returns (scores float32 [Q, topk], idx int64 [Q, topk])"""
+    def query_batch(self, k: int, q: np.ndarray, topk: int = CHIP_DEFAULT_TOPK, cast_rows: bool = False):
+        """many-query fp32 MFMA mode: returns (scores float32 [Q, topk], idx int64 [Q, topk]).  cast_rows=True goes through
+        chip_query_batch_cast_f32: a double-row DB is accepted, its rows narrowed to float (RNE) in the GEMM's loader."""
         q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self.D)
         Q = q.shape[0]
         sc = np.empty((Q, topk), dtype=np.float32)
         ix = np.empty((Q, topk), dtype=np.int64)
-        self._chk(self.lib.chip_query_batch_f32(self.h, k, _ptr(q), Q, topk, _ptr(sc), _ptr(ix)), "chip_query_batch_f32")
+        name = "chip_query_batch_cast_f32" if cast_rows else "chip_query_batch_f32"
+        self._chk(getattr(self.lib, name)(self.h, k, _ptr(q), Q, topk, _ptr(sc), _ptr(ix)), name)
         return sc, ix
 
     # -- tick

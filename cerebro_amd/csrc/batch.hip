@@ -31,6 +31,8 @@ namespace chip {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 constexpr int BM = 128;              // queries are padded to a multiple of the small tile
 constexpr int CT_LD = 128 + 1;      // score tile in LDS [tile queries][129]: 128 DB rows per epilogue pass
@@ -43,7 +45,7 @@ constexpr int kMaxQTiles = 4096;    // query tiles per call (grid.y); 4096 x 128
 __device__ __forceinline__ constexpr int b_row_off(int row) { return (row >> 3) * kBBlock + ((row >> 3) & 3) + (row & 7) * 32; }
 
 struct BatchArgs {
-    const float *const *seg_table;
+    const void *const *seg_table;   // rows of the ctx's storage type: float, or double (the cast form of the kernel)
     int32_t seg_shift;
     int64_t seg_mask;
     int64_t n_rows;         // local rows [0, n_rows)
@@ -136,6 +138,30 @@ __device__ __forceinline__ void wait_loads_and_barrier()
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+// Double rows (chip_query_batch_cast_f32): the B side of the same LDS image, filled through registers.  The reference's faiss variants
+// index X.cast<float>() of its MatrixXd DB (Cerebro.cpp:422,569,807), so a double-row DB enters this GEMM as (float)x per element
+// (v_cvt_f32_f64, round to nearest even) and everything behind the loader -- image, fragment reads, MFMA order, epilogue -- is the float
+// kernel's, hence the same fmaf chain.  LDS-DMA cannot convert, and a raw double tile (64 KiB per stage at 256 rows) does not fit
+// beside the A ring, so a thread loads the 32 source bytes of each 16-byte slot its lane's DMA would have filled (2 x
+// global_load_dwordx4), converts and stores the slot.  The slot's address is lane-linear in a block ROTATED by (wave & 3) floats:
+// 16-byte aligned on waves 0 and 4 only, 8-byte on rotation 2, 4-byte on the odd ones -- and a DS access wider than 4 bytes off its
+// natural alignment is replayed (tens of cycles per wave instruction).  The rotation is wave-uniform, so a scalar branch picks
+// the widest store the wave's rotation allows: one ds_write_b128, two ds_write_b64, or two ds_write2_b32 (each 12-13 LDS cycles
+// per wave instruction; no replay).
+template <int ALIGN>
+__device__ __forceinline__ void lds_store_slot(float *d, float x, float y, float z, float w)
+{
+    if constexpr (ALIGN == 16) {
+        *reinterpret_cast<f32x4 *>(__builtin_assume_aligned(d, 16)) = f32x4{x, y, z, w};
+    } else if constexpr (ALIGN == 8) {
+        f32x2 *d2 = reinterpret_cast<f32x2 *>(__builtin_assume_aligned(d, 8));
+        d2[0] = f32x2{x, y};
+        d2[1] = f32x2{z, w};
+    } else {
+        d[0] = x; d[1] = y; d[2] = z; d[3] = w;
+    }
+}
+
 // Qt[qtile][chunk][k][row] <- Q[qtile * TM + row][chunk * KC + k], TM = rows of a query tile (128 or 256)
 // (one thread per element; Q is a few MB at most)
 __global__ __launch_bounds__(256) void transpose_queries(const float *__restrict__ Q, float *__restrict__ Qt, int Qpad, int D, int tm_shift)
@@ -154,9 +180,12 @@ __global__ __launch_bounds__(256) void transpose_queries(const float *__restrict
 
 // WN = waves along the DB rows of a tile (2 or 4); a wave owns WN x 2 MFMA 32x32 blocks (64 WN queries x 64 DB rows), the
 // workgroup tile is 64 WN x 64 WN (128 x 128 with 4 waves, 256 x 256 with 8), 2 x WN waves, 8 LDS-DMA per wave per chunk either way.
-template <int KC, int WN, int KL>
+// ROW = float: DB rows by LDS-DMA; ROW = double: rows narrowed to float on their way into the same image (see above).
+template <int KC, int WN, int KL, typename ROW>
 __global__ __launch_bounds__(128 * WN) void db_gemm_topk(BatchArgs a)
 {
+    constexpr bool CAST = std::is_same<ROW, double>::value;
+    static_assert(CAST || std::is_same<ROW, float>::value, "float or double rows");
     static_assert(KC == 32, "one K-chunk = 8 slots of 4 floats per DB row");
     static_assert(WN == 2 || WN == 4, "tile 128 x 128 or 256 x 256");
     constexpr int TM = 64 * WN, TN = 64 * WN;            // tile: queries x DB rows
@@ -218,11 +247,26 @@ __global__ __launch_bounds__(128 * WN) void db_gemm_topk(BatchArgs a)
         unsigned claimed = 0;
         if (tid == 0) claimed = __hip_atomic_fetch_add(a.tile_ctr + blockIdx.y, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const float *brow[4];
+        // double rows: a tile lies within one segment (seg_rows is a multiple of TN: batch_local_enqueue), so its rows are a
+        // workgroup-uniform base plus 32-bit byte offsets (segments are at most 1 GiB); rows past the end read the tile's first row
+        const char *seg = nullptr;
+        uint32_t boff[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             const int64_t br = n0 + u * (8 * WAVES) + l_row;
-            const int64_t brc = br < a.n_rows ? br : 0;   // rows past the end: any valid row (their columns are never scanned)
-            brow[u] = a.seg_table[brc >> a.seg_shift] + (brc & a.seg_mask) * (int64_t)D + l_k4;
+            if constexpr (CAST) {
+                const int64_t brc = br < a.n_rows ? br : n0;
+                boff[u] = (uint32_t)(((brc & a.seg_mask) * (int64_t)D + l_k4) * 8);
+            } else {
+                const int64_t brc = br < a.n_rows ? br : 0;   // rows past the end: any valid row (their columns are never scanned)
+                brow[u] = reinterpret_cast<const float *const *>(a.seg_table)[brc >> a.seg_shift] + (brc & a.seg_mask) * (int64_t)D + l_k4;
+            }
+        }
+        if constexpr (CAST) {
+            const uint64_t sp = (uint64_t)reinterpret_cast<const char *const *>(a.seg_table)[n0 >> a.seg_shift];
+            // (readfirstlane returns int: each half goes through uint32_t, or a low word with bit 31 set would sign-extend over the high one)
+            const uint32_t sp_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(sp >> 32)), sp_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)sp);
+            seg = (const char *)(((uint64_t)sp_hi << 32) | sp_lo);
         }
         f32x16 acc[WN][2];
 #pragma unroll
@@ -236,14 +280,43 @@ __global__ __launch_bounds__(128 * WN) void db_gemm_topk(BatchArgs a)
         auto stage_load_one = [&](int c, int j) {
             const uint32_t st = lds_base + (uint32_t)((c % NST) * STAGE) * 4u;
             const int u = j >> 1;
-            if (j & 1) glds16(brow[u] + c * KC, st + (uint32_t)(TILE + b_row_off((u * WAVES + wave) * 8)) * 4u);
-            else glds16(a_src + (int64_t)c * TILE + u * (WAVES * 256), st + (uint32_t)((u * WAVES + wave) * 256) * 4u);
+            if (j & 1) {
+                if constexpr (!CAST) glds16(brow[u] + c * KC, st + (uint32_t)(TILE + b_row_off((u * WAVES + wave) * 8)) * 4u);
+            } else glds16(a_src + (int64_t)c * TILE + u * (WAVES * 256), st + (uint32_t)((u * WAVES + wave) * 256) * 4u);
         };
         auto stage_load = [&](int c) {
 #pragma unroll
             for (int j = 0; j < 8; j++) stage_load_one(c, j);
         };
-        if (n_chunks > 0) stage_load(0);
+        // double rows: slot u of chunk c through registers (the slots of a thread are lane-linear in block u * WAVES + wave)
+        auto cast_load = [&](int c, int u, f64x2 *r) {
+            if constexpr (CAST) {
+                const auto *chunk = (const __attribute__((address_space(1))) char *)seg + (int64_t)c * (KC * 8);
+                const auto *p = (const __attribute__((address_space(1))) f64x2 *)(chunk + boff[u]);
+                r[0] = p[0];
+                r[1] = p[1];
+            }
+        };
+        auto cast_store = [&](int c, int u, const f64x2 *r) {
+            if constexpr (CAST) {
+                float *d = S0 + (c % NST) * STAGE + TILE + b_row_off((u * WAVES + wave) * 8) + lane * 4;
+                const float x = (float)r[0][0], y = (float)r[0][1], z = (float)r[1][0], w = (float)r[1][1];
+                if ((wave & 3) == 0) lds_store_slot<16>(d, x, y, z, w);
+                else if ((wave & 3) == 2) lds_store_slot<8>(d, x, y, z, w);
+                else lds_store_slot<4>(d, x, y, z, w);
+            }
+        };
+        if (n_chunks > 0) {
+            stage_load(0);
+            if constexpr (CAST) {
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    f64x2 r[2];
+                    cast_load(0, u, r);
+                    cast_store(0, u, r);
+                }
+            }
+        }
         wait_loads_and_barrier();   // chunk 0 has landed
         // the K loop, instantiated for whole tiles (NRB = WN row blocks per wave) and for query halves (NRB = WN / 2)
         auto k_loop = [&](auto nrb_tag) {
@@ -255,8 +328,13 @@ __global__ __launch_bounds__(128 * WN) void db_gemm_topk(BatchArgs a)
                 //   128 tile  all 8 at once at the top (the other workgroup's wave fills the gap: 119.4 TF vs 114.8 spread);
                 //   256 tile  two in front of each of MFMA groups 1..4 (both waves of a SIMD belong to this workgroup and burst
                 //             together: 0.814 of peak vs 0.792 for the burst, 0.805 for groups 0..3, 0.76 for one per group).
+                //   double rows, both tiles: a thread's four slots in two halves through 16 staging registers -- slots 0, 1 loaded in
+                //             front of group 0 and stored in front of group 3, where slots 2, 3 are loaded, stored in front of group 7;
+                //             the A-side DMA in front of groups 0 and 1 (a store waits for every load issued before it: all of them
+                //             are two groups old by then).
                 const bool prefetch = c + 1 < n_chunks;
-                if (WN == 2 && prefetch) stage_load(c + 1);
+                if (!CAST && WN == 2 && prefetch) stage_load(c + 1);
+                f64x2 raw[2][2];
                 // fragments of k-steps (2 k4, 2 k4 + 1) in f[k4 & 1]: [2 i + t] = A row block i, [2 WN + 2 j + t] = B block j;
                 // the next pair is read before this pair's 4 WN MFMAs are issued
                 float f[2][2 * WN + 4];
@@ -274,7 +352,14 @@ __global__ __launch_bounds__(128 * WN) void db_gemm_topk(BatchArgs a)
                 __builtin_amdgcn_sched_group_barrier(0x100, NRB + 2, 0);  // the reads of the first pair
 #pragma unroll
                 for (int k4 = 0; k4 < KC / 4; k4++) {
-                    if (WN == 4 && prefetch && k4 >= 1 && k4 <= 4) { stage_load_one(c + 1, 2 * k4 - 2); stage_load_one(c + 1, 2 * k4 - 1); }
+                    if (!CAST && WN == 4 && prefetch && k4 >= 1 && k4 <= 4) { stage_load_one(c + 1, 2 * k4 - 2); stage_load_one(c + 1, 2 * k4 - 1); }
+                    if (CAST && prefetch && k4 == 0) { cast_load(c + 1, 0, raw[0]); cast_load(c + 1, 1, raw[1]); }
+                    if (CAST && prefetch && k4 <= 1) { stage_load_one(c + 1, 4 * k4); stage_load_one(c + 1, 4 * k4 + 2); }
+                    if (CAST && prefetch && k4 == 3) {
+                        cast_store(c + 1, 0, raw[0]); cast_store(c + 1, 1, raw[1]);
+                        cast_load(c + 1, 2, raw[0]); cast_load(c + 1, 3, raw[1]);
+                    }
+                    if (CAST && prefetch && k4 == 7) { cast_store(c + 1, 2, raw[0]); cast_store(c + 1, 3, raw[1]); }
                     if (k4 + 1 < KC / 4) rd(k4 + 1, f[(k4 + 1) & 1]);
 #pragma unroll
                     for (int t = 0; t < 2; t++) {
@@ -299,6 +384,10 @@ __global__ __launch_bounds__(128 * WN) void db_gemm_topk(BatchArgs a)
         // ---- epilogue: the score tile through LDS, 128 DB rows (two of the WN wave columns) per pass (the stages are free:
         // the K loop ended with a barrier); C/D layout of the MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
         const int ncols = (a.n_rows - n0) < TN ? (int)(a.n_rows - n0) : TN;
+        // double rows: the epilogue's addresses are recomputed per tile from an opaque copy of the lane -- hoisted out of the tile loop
+        // they would sit in registers the staging needs through the K loop (and spill)
+        int elane = lane, eoq = oq;
+        if constexpr (CAST) asm volatile("" : "+v"(elane), "+v"(eoq));
 #pragma unroll
         for (int h = 0; h < WN / 2; h++) {
             if (h > 0) __syncthreads();   // the previous pass's scan is done with Ct
@@ -310,8 +399,8 @@ __global__ __launch_bounds__(128 * WN) void db_gemm_topk(BatchArgs a)
                     for (int jt = 0; jt < 2; jt++)
 #pragma unroll
                         for (int e = 0; e < 16; e++) {
-                            const int row = qrow0 + it * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);   // query within the tile
-                            const int col = (wn & 1) * 64 + jt * 32 + (lane & 31);                                  // DB row within the pass
+                            const int row = qrow0 + it * 32 + (e & 3) + 8 * (e >> 2) + 4 * (elane >> 5);   // query within the tile
+                            const int col = (wn & 1) * 64 + jt * 32 + (elane & 31);                                  // DB row within the pass
                             Ct[row * CT_LD + col] = acc[it][jt][e];
                         }
                 }
@@ -321,10 +410,10 @@ __global__ __launch_bounds__(128 * WN) void db_gemm_topk(BatchArgs a)
             int32_t tr;
             list_kth(L, K, ts, tr);
             const int pass_cols = ncols - h * 128;         // columns of this pass that exist
-            const bool mine = !half_unit || (oq >= qhalf * (TM / 2) && oq < (qhalf + 1) * (TM / 2));   // a query half: only its queries have scores
+            const bool mine = !half_unit || (eoq >= qhalf * (TM / 2) && eoq < (qhalf + 1) * (TM / 2));   // a query half: only its queries have scores
             const int c_hi = !mine ? 0 : pass_cols < (och + 1) * 64 ? pass_cols : (och + 1) * 64;
             for (int c = och * 64; c < c_hi; c++) {
-                const float s = Ct[oq * CT_LD + c];
+                const float s = Ct[eoq * CT_LD + c];
                 const int32_t row = (int32_t)(n0 + h * 128 + c);
                 if (fkey_gt(s, row, ts, tr)) {   // NaN never enters
                     list_push(L, K, s, row);
@@ -335,7 +424,8 @@ __global__ __launch_bounds__(128 * WN) void db_gemm_topk(BatchArgs a)
         // next tile: published by thread 0, read by everyone after the barrier that also ends this tile's use of Ct
         if (tid == 0) next_tile_slot = gridDim.x + claimed;
         __syncthreads();
-        unit = next_tile_slot;
+        if constexpr (CAST) unit = __builtin_amdgcn_readfirstlane(next_tile_slot);   // (registers: the tile's bookkeeping stays scalar)
+        else unit = next_tile_slot;
     }
     // fold the two column-half lists of a query into one (through LDS, once per workgroup): one list per (partition, query)
     __syncthreads();
@@ -404,6 +494,8 @@ int32_t batch_qpad(int32_t Q) { return (Q + BM - 1) / BM * BM; }
 // This ctx's share of a many-query call, enqueued on its scan stream: Q queries (host, Q x D fp32) against its LOCAL rows of the global
 // prefix [0, k) -- the whole prefix on a plain ctx, rows i % G == rank of it on a shard -- leaving one sorted [Qpad][topk] list of
 // (score, GLOBAL index) entries in device memory (*out_dev).  No host synchronisation.  Caller: query lock held, device current.
+// The ctx's storage type picks the kernel: float rows by LDS-DMA, double rows narrowed to float in the loader -- the caller has
+// checked that its entry point allows that (chip_query_batch_cast_f32).
 int batch_local_enqueue(Ctx *c, int64_t k, const float *queries, int32_t Q, int32_t topk, chip_topk_entry **out_dev, int32_t *Qpad_out)
 {
     if (!c->batch_state) {
@@ -417,7 +509,9 @@ int batch_local_enqueue(Ctx *c, int64_t k, const float *queries, int32_t Q, int3
     const int64_t n_rows = local_count(c, k);
     // Tile shape: 256 x 256 with 8 waves (one workgroup per CU: 16 MFMAs per 6 fragment reads, one barrier per 128 MFMAs, the DB
     // streamed once per 256 queries) when the padded query count is a multiple of 256, else 128 x 128 with 4 waves.
-    const bool wide = Qpad % 256 == 0;
+    // Double rows with the long lists (topk > 8) keep to the small tile: next to 128 accumulator registers, 32 list registers and
+    // the staging of the cast loader the 256 x 256 form does not fit 256 registers per wave (it would spill inside the tile loop).
+    const bool wide = Qpad % 256 == 0 && !(c->elem == 8 && topk > 8);
     const int TM = wide ? 256 : BM, TN = TM;
     const int qtiles = Qpad / TM;
     const int wgs = wide ? 1 : 2;            // workgroups per CU
@@ -450,7 +544,7 @@ int batch_local_enqueue(Ctx *c, int64_t k, const float *queries, int32_t Q, int3
     }
 
     BatchArgs a;
-    a.seg_table = reinterpret_cast<const float *const *>(c->seg_table_dev.get()); a.seg_shift = c->seg_shift; a.seg_mask = c->seg_rows - 1;
+    a.seg_table = reinterpret_cast<const void *const *>(c->seg_table_dev.get()); a.seg_shift = c->seg_shift; a.seg_mask = c->seg_rows - 1;
     a.n_rows = n_rows; a.D = D; a.Q = st->Q; a.Qt = st->Qt; a.Qpad = Qpad; a.K = topk; a.tile_ctr = st->tile_ctr;
     a.idx_mul = c->nranks; a.idx_add = c->nranks == 1 ? 0 : c->rank; a.partial = st->partial;
     constexpr int KCsel = 32;
@@ -459,7 +553,7 @@ int batch_local_enqueue(Ctx *c, int64_t k, const float *queries, int32_t Q, int3
     const size_t lds = lds_gemm > lds_ct ? lds_gemm : lds_ct;
     hipEvent_t e1 = nullptr;
     if (c->prof_on) {
-        const int prc = prof_begin(c, s, (double)n_rows * D * 4.0 * qtiles, &e1);   // the DB is streamed once per query tile
+        const int prc = prof_begin(c, s, (double)n_rows * D * c->elem * qtiles, &e1);   // the DB is streamed once per query tile
         if (prc != CHIP_OK) return prc;
     }
     auto launch = [&](auto kernel, int threads) -> int {
@@ -468,8 +562,12 @@ int batch_local_enqueue(Ctx *c, int64_t k, const float *queries, int32_t Q, int3
         return CHIP_OK;
     };
     int lrc;
-    if (topk <= 8) lrc = wide ? launch(db_gemm_topk<KCsel, 4, 8>, 512) : launch(db_gemm_topk<KCsel, 2, 8>, 256);
-    else lrc = wide ? launch(db_gemm_topk<KCsel, 4, CHIP_MAX_TOPK>, 512) : launch(db_gemm_topk<KCsel, 2, CHIP_MAX_TOPK>, 256);
+    if (c->elem == 8) {
+        if (c->seg_rows % TN != 0) return CHIP_ERR_UNSUPPORTED;   // the cast loader addresses a tile within ONE segment (never the case: segments are >= 8192 rows)
+        if (topk <= 8) lrc = wide ? launch(db_gemm_topk<KCsel, 4, 8, double>, 512) : launch(db_gemm_topk<KCsel, 2, 8, double>, 256);
+        else lrc = launch(db_gemm_topk<KCsel, 2, CHIP_MAX_TOPK, double>, 256);
+    } else if (topk <= 8) lrc = wide ? launch(db_gemm_topk<KCsel, 4, 8, float>, 512) : launch(db_gemm_topk<KCsel, 2, 8, float>, 256);
+    else lrc = wide ? launch(db_gemm_topk<KCsel, 4, CHIP_MAX_TOPK, float>, 512) : launch(db_gemm_topk<KCsel, 2, CHIP_MAX_TOPK, float>, 256);
     if (lrc != CHIP_OK) return lrc;
     CHIP_HIP(c, hipGetLastError());
     if (e1) CHIP_HIP(c, hipEventRecord(e1, s));
@@ -529,13 +627,14 @@ int batch_merge_lists(Ctx *c, hipStream_t s, const chip_topk_entry *in, int n_li
 
 using namespace chip;
 
-extern "C" int chip_query_batch_f32(chip_ctx *c, int64_t k, const float *queries, int32_t Q, int32_t topk, float *scores, int64_t *idx)
+// cast_rows: the caller came through chip_query_batch_cast_f32 and accepts double rows narrowed to float
+static int query_batch(chip_ctx *c, int64_t k, const float *queries, int32_t Q, int32_t topk, float *scores, int64_t *idx, bool cast_rows)
 {
     if (!c || !queries || Q < 1) return CHIP_ERR_INVALID_ARG;
     if (topk < 1 || topk > CHIP_MAX_TOPK || c->D % 32 != 0) return CHIP_ERR_UNSUPPORTED;
     if ((int64_t)(Q + BM - 1) / BM > kMaxQTiles) return CHIP_ERR_UNSUPPORTED;
-    if (c->group) return group_query_batch(c, k, queries, Q, topk, scores, idx);   // G per-device passes -> one merge on devices[0]
-    if (c->elem != 4) return CHIP_ERR_UNSUPPORTED;   // fp32 GEMM over float rows (faiss casts to float, Cerebro.cpp:422)
+    if (c->group) return group_query_batch(c, k, queries, Q, topk, scores, idx, cast_rows);   // G per-device passes -> one merge on devices[0]
+    if (c->elem != 4 && !cast_rows) return CHIP_ERR_UNSUPPORTED;   // fp32 GEMM over float rows; the cast of double rows (faiss: Cerebro.cpp:422) is opt-in
     int64_t n_global;
     {
         std::lock_guard<std::mutex> lk(c->mu);
@@ -546,10 +645,20 @@ extern "C" int chip_query_batch_f32(chip_ctx *c, int64_t k, const float *queries
     if (k > n_global && !collective) return CHIP_ERR_RANGE;
     std::lock_guard<std::mutex> qlk(c->query_mu);
     CHIP_HIP(c, hipSetDevice(c->device));
-    if (collective) return xchg_query_batch(c, k, queries, Q, topk, scores, idx, k > n_global);
+    if (collective) return xchg_query_batch(c, k, queries, Q, topk, scores, idx, k > n_global, cast_rows);
     chip_topk_entry *out = nullptr;
     int32_t Qpad = 0;
     const int rc = batch_local_enqueue(c, k, queries, Q, topk, &out, &Qpad);
     if (rc != CHIP_OK) return rc;
     return batch_deliver(c, out, Q, topk, scores, idx);
+}
+
+extern "C" int chip_query_batch_f32(chip_ctx *c, int64_t k, const float *queries, int32_t Q, int32_t topk, float *scores, int64_t *idx)
+{
+    return query_batch(c, k, queries, Q, topk, scores, idx, false);
+}
+
+extern "C" int chip_query_batch_cast_f32(chip_ctx *c, int64_t k, const float *queries, int32_t Q, int32_t topk, float *scores, int64_t *idx)
+{
+    return query_batch(c, k, queries, Q, topk, scores, idx, true);
 }

@@ -768,7 +768,7 @@ int group_scores(Ctx *gc, int64_t k, int64_t query_row, double *u)
 // sorted [Qpad][topk] list; the root pulls the G lists side by side (device / peer copies behind events -- Q x topk x 16 B per
 // device, 32 KiB at Q = 256, topk = 8: the transport does not matter) and merges them with the same exact selection that merges
 // the workgroups of one device (topk_merge_batch): the result is that of one device holding the whole DB, bit for bit.
-int group_query_batch(Ctx *gc, int64_t k, const float *queries, int32_t Q, int32_t topk, float *scores, int64_t *idx)
+int group_query_batch(Ctx *gc, int64_t k, const float *queries, int32_t Q, int32_t topk, float *scores, int64_t *idx, bool cast_rows)
 {
     Group *G = gc->group;
     Ctx *root = G->subs[0];
@@ -781,7 +781,7 @@ int group_query_batch(Ctx *gc, int64_t k, const float *queries, int32_t Q, int32
         n = gc->rows_global;
         elem = gc->elem;
     }
-    if (elem != 4) return CHIP_ERR_UNSUPPORTED;
+    if (elem != 4 && !cast_rows) return CHIP_ERR_UNSUPPORTED;   // double rows only through chip_query_batch_cast_f32
     if (k < 0 || k > n) return CHIP_ERR_RANGE;
     const int ng = (int)G->subs.size();
     std::vector<chip_topk_entry *> lists((size_t)ng, nullptr);
@@ -845,10 +845,10 @@ static int xchg_agree(Ctx *c, bool ok_local, bool *all_ok)
 // ncclAllGather of the [Qpad][topk] lists -> merge on every rank (collective: every rank makes the same call).  A rank whose own
 // arguments are out of range, whose allocations fail or whose enqueue fails says so in the agreement round: then NO rank posts the
 // large all-gather, the failing rank returns its own status and the others CHIP_ERR_SHARD_FAILED -- the communicator stays in step.
-int xchg_query_batch(Ctx *c, int64_t k, const float *queries, int32_t Q, int32_t topk, float *scores, int64_t *idx, bool fail_local)
+int xchg_query_batch(Ctx *c, int64_t k, const float *queries, int32_t Q, int32_t topk, float *scores, int64_t *idx, bool fail_local, bool cast_rows)
 {
     Exchange *x = c->xchg;
-    if (c->elem != 4) return CHIP_ERR_UNSUPPORTED;      // the storage type is the same on every rank (same append stream)
+    if (c->elem != 4 && !cast_rows) return CHIP_ERR_UNSUPPORTED;      // the storage type is the same on every rank (same append stream)
     if (test_fail_now(x)) fail_local = true;
     chip_topk_entry *mine = nullptr, *gathered = nullptr, *merged = nullptr;
     int32_t Qpad = batch_qpad(Q);

@@ -207,6 +207,19 @@ int chip_query_scores(chip_ctx *ctx, int64_t k, int64_t query_row, double *u);
 int chip_query_batch_f32(chip_ctx *ctx, int64_t k, const float *queries, int32_t Q, int32_t topk,
                          float *scores /* Q x topk */, int64_t *idx /* Q x topk */);
 
+/* The same mode on a DOUBLE-row DB, with the rows narrowed to float on their way into the GEMM.  The reference's DB is always
+ * MatrixXd and its faiss variants index X.cast<float>() and search with the cast query (src/Cerebro.cpp:422,455,569,604,807,840):
+ * every row element x enters as (float)x -- IEEE round to nearest even, what Eigen's cast<float>() and numpy's astype(float32) do --
+ * and then the semantics of chip_query_batch_f32 apply unchanged (one k-ordered fmaf chain, (score desc, index desc)).  The cast is
+ * lossy, and this library never rounds silently (CHIP_ERR_NOT_F32, CHIP_APPEND_ALLOW_ROUNDING): it is opt-in through THIS entry
+ * point, and chip_query_batch_f32 keeps returning CHIP_ERR_UNSUPPORTED on double rows.  On a float-row ctx the two calls are the same
+ * code path and return the same bits.  Arguments, limits (D % 32 == 0, topk, Q), CHIP_ERR_RANGE, group contexts and sharded contexts
+ * with and without an exchange (collective behaviour, agreement round, failure mark) exactly as chip_query_batch_f32.
+ * Covered by the tests: doubles whose cast is a normal float or zero; nothing is promised here for elements whose cast overflows
+ * or is subnormal.  With topk > 8 a double-row DB is always scanned with the 128 x 128 tile (the DB is streamed once per 128 queries). */
+int chip_query_batch_cast_f32(chip_ctx *ctx, int64_t k, const float *queries, int32_t Q, int32_t topk,
+                              float *scores /* Q x topk */, int64_t *idx /* Q x topk */);
+
 /* ------------------------------------------------------------------------------------------ the tick
  * One pass of the while-loop body of Cerebro::descrip_N__dot__descrip_0_N (src/Cerebro.cpp:956-1100) for
  * l = wholeImageComputedList_size().  Defaults (chip_dot_params_default): LOCALITY_THRESH 12 (:912),

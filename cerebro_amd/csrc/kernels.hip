@@ -318,7 +318,7 @@ __global__ __launch_bounds__(1024) void db_scan_topk(ScanArgs a)
 //     3T x (1 conversion + 4 fma) = 49 VALU instructions at T = 3 against 16 (4 + 12) for one tick in db_scan_topk;
 //   * per-tick prefix: a row is offered to tick t's lists only if row < k_t (wave-uniform compare); the running lists sit in LDS
 //     behind the queries ([wave][3T][K] entries), the admission thresholds in SGPRs; one vector compare per query tells whether any
-//     row of a group can enter a list at all;
+//     row of a group can enter a list at all, and the offers of such a group are walked list by list;
 //   * output [tick][workgroup][3][K]: the merge + decision kernel runs unchanged, once per tick, on its own block of lists.
 constexpr int kMultiR = 4, kMultiU = 4, kMultiBlock = 512;
 
@@ -574,20 +574,28 @@ __global__ __launch_bounds__(kMultiBlock) __attribute__((amdgpu_num_vgpr(kMultiV
             }
             // Offers.  One vector compare per query first: s[q] holds the four rows' scores against query q, and a threshold only rises
             // while the group is offered, so a score that the loop below would admit is >= the threshold the group starts with (NaN on
-            // neither side).  No lane set: nothing of this group enters any list.  Otherwise the rows are offered one by one, in
+            // neither side).  No lane set: nothing of this group enters any list.  Otherwise each list is offered its rows one by one, in
             // order, each against the threshold as it stands then.  (A lane may be set by a row some tick must not see, or by the stand-in
             // of a row beyond the pass: that costs the walk below, which tests both, and nothing else.)
             unsigned long long hit = 0;
 #pragma unroll
             for (int q = 0; q < NQ; q++) hit |= __ballot(s[q] >= thr_s[q]);
             if (hit) {
+                // The lists are independent of one another; only the rows offered to ONE list must come in ascending order.  So the walk goes
+                // query first: the query's own compare once more (one vector instruction; nine masks kept from the pre-check do not fit
+                // the SGPRs), and a query none of whose four scores reaches its threshold is stepped over as a whole.  thr_s[q] changes
+                // only inside q's own turn, so the compare is still against the threshold the group started with.  The empty asm below is
+                // what makes it a second compare: without it the compiler reuses the pre-check's nine masks, keeps them live across the
+                // walk and spills SGPRs, which tests/test_codeobj_multi.py refuses.
 #pragma unroll
-                for (int rr = 0; rr < R; rr++) {
-                    const int64_t r = rbase + ((int64_t)group * R + rr) * tw;
-                    if (r < a.n_rows) {
+                for (int q = 0; q < NQ; q++) {
+                    asm volatile("" : "+v"(s[q]));   // a value the pre-check has not seen: the compare is made again, not kept
+                    if (__ballot(s[q] >= thr_s[q])) {
 #pragma unroll
-                        for (int q = 0; q < NQ; q++)
-                            if (r < a.k[q / 3]) multi_offer(readlane_f64(s[q], 16 * rr), r, K, lane, mylists + q * K, thr_s[q]);
+                        for (int rr = 0; rr < R; rr++) {
+                            const int64_t r = rbase + ((int64_t)group * R + rr) * tw;
+                            if (r < a.n_rows && r < a.k[q / 3]) multi_offer(readlane_f64(s[q], 16 * rr), r, K, lane, mylists + q * K, thr_s[q]);
+                        }
                     }
                 }
             }

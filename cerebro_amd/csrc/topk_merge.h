@@ -39,10 +39,13 @@ __device__ __forceinline__ int64_t readlane_i64(int64_t v, int j)
     return ((int64_t)hi << 32) | (unsigned int)lo;
 }
 
-// Order-preserving integer image of a finite (or -inf) double: a > b  <=>  okey(a) > okey(b).
+// Order-preserving integer image of a double that is not NaN (NaN scores never reach a list): a > b  <=>  okey(a) > okey(b), for
+// finite scores and for +-inf (the fp32 chain of the many-query mode overflows to either).  -0.0 takes the image of +0.0: the two
+// compare EQUAL as scores (key_gt then orders by index), and wave_rank's fast path decides on the upper half of this image alone.
 __device__ __forceinline__ unsigned long long okey(double s)
 {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(s);
+    const unsigned long long b0 = (unsigned long long)__double_as_longlong(s);
+    const unsigned long long b = b0 == 0x8000000000000000ull ? 0ull : b0;
     return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 

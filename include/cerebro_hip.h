@@ -95,7 +95,7 @@ void chip_destroy(chip_ctx *ctx);
  * Double rows: scores are fp64 FMA chains (one rounding per term) in the fixed order of DESIGN.md 3 with 2 elements per lane
  * per 128-element chunk; D <= 10 240 as for float rows (two double queries fit the 160 KiB of LDS; where the three of a
  * tick do not -- D > 6824, e.g. the reference's default 8192 -- the rest is read in place, same bits); the MFMA many-query
- * mode is float-only.                                                                                                   */
+ * mode reads double rows only through chip_query_batch_cast_f32 (rows narrowed to float in the loader, opt-in).          */
 #define CHIP_CREATE_STORE_F32 1u
 #define CHIP_CREATE_STORE_F64 2u
 int  chip_create_ex(chip_ctx **out, int32_t D, int64_t capacity_hint, int32_t device, int32_t shard_rank, int32_t shard_count,
@@ -203,7 +203,12 @@ int chip_query_scores(chip_ctx *ctx, int64_t k, int64_t query_row, double *u);
  * Sharded DBs: a chip_create_multi ctx runs one pass per device over the rows it owns and merges the per-device lists on
  * devices[0]; a sharded ctx with an attached communicator does the same collectively (ncclAllGather of Q x topk entries per rank,
  * the same result on every rank); a sharded ctx WITHOUT an exchange answers for its own rows only (global indices) -- the host
- * merges.  Results are those of one device holding the whole DB, bit for bit (exact selection under a total order).            */
+ * merges.  Results are those of one device holding the whole DB, bit for bit (exact selection under a total order).
+ * Outside the normal range the chain is IEEE fp32, step by step (tests/test_batch_edges_gpu.py): it overflows to +-inf where a
+ * chained fmaf does (finite rows and queries never give NaN), subnormal inputs, products and partial sums are not flushed, and
+ * the sign of a zero score is the chain's (-0.0 only where it ends in a negative underflow; +0.0 and -0.0 tie, index desc).
+ * Queries are NOT validated: a NaN score (a NaN query element, 0 x inf, inf - inf) never enters a list, so such a query gets
+ * fewer than topk entries (a NaN query: none); a real row scoring -inf precedes an unused slot (-inf, -1).                     */
 int chip_query_batch_f32(chip_ctx *ctx, int64_t k, const float *queries, int32_t Q, int32_t topk,
                          float *scores /* Q x topk */, int64_t *idx /* Q x topk */);
 
@@ -215,8 +220,9 @@ int chip_query_batch_f32(chip_ctx *ctx, int64_t k, const float *queries, int32_t
  * point, and chip_query_batch_f32 keeps returning CHIP_ERR_UNSUPPORTED on double rows.  On a float-row ctx the two calls are the same
  * code path and return the same bits.  Arguments, limits (D % 32 == 0, topk, Q), CHIP_ERR_RANGE, group contexts and sharded contexts
  * with and without an exchange (collective behaviour, agreement round, failure mark) exactly as chip_query_batch_f32.
- * Covered by the tests: doubles whose cast is a normal float or zero; nothing is promised here for elements whose cast overflows
- * or is subnormal.  With topk > 8 a double-row DB is always scanned with the 128 x 128 tile (the DB is streamed once per 128 queries). */
+ * The cast is v_cvt_f32_f64, bit for bit numpy's astype(float32) over the whole double range (tests/test_batch_edges_gpu.py): beyond
+ * the halfway point above FLT_MAX it gives +-inf (the scores then follow the IEEE rules above), into the subnormal range it rounds
+ * to nearest even without flushing, a non-zero double below half the smallest subnormal gives a zero of its sign.  With topk > 8 a double-row DB is always scanned with the 128 x 128 tile (the DB is streamed once per 128 queries). */
 int chip_query_batch_cast_f32(chip_ctx *ctx, int64_t k, const float *queries, int32_t Q, int32_t topk,
                               float *scores /* Q x topk */, int64_t *idx /* Q x topk */);
 

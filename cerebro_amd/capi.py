@@ -65,6 +65,7 @@ SCAN_FAMILY_NAMES = {0: "none", 1: "one_row", 2: "wide", 3: "rows", 4: "multi"}
 
 CHIP_TICK_SKIPPED, CHIP_TICK_TOO_SHORT, CHIP_TICK_SCANNED = 0, 1, 2
 CHIP_MATCH_MAX_KEYPOINTS = 16384
+CHIP_MATCH_MAX_BATCH = 16
 CHIP_ORB_DESC_BYTES = 32
 CHIP_SET_AB, CHIP_SET_BA = 0, 1
 
@@ -216,6 +217,11 @@ _SIGS = {
     "chip_match_read_sets": (C.c_int, [_P, C.POINTER(MatchSetsOut)]),
     "chip_pnp_ransac_matched": (C.c_int, [_P, C.c_int32, C.POINTER(RansacParams), _P, C.POINTER(C.c_float), _P, C.POINTER(RansacSummary)]),
     "chip_icp_ransac_matched": (C.c_int, [_P, C.POINTER(RansacParams), _P, C.POINTER(C.c_float), _P, C.POINTER(RansacSummary)]),
+    "chip_build_has_match_batch": (C.c_int, []),
+    "chip_match_batch": (C.c_int, [_P, C.POINTER(MatchFrame), C.POINTER(MatchFrame), C.c_int32, _P, C.POINTER(MatchSummary)]),
+    "chip_match_select": (C.c_int, [_P, C.c_int32]),
+    "chip_match_batch_read_matches": (C.c_int, [_P, C.c_int32, _P, _P]),
+    "chip_pnp_ransac_matched_batch": (C.c_int, [_P, C.c_int32, _P, _P, C.POINTER(RansacParams), _P, _P, _P, _P, _P, _P]),
     "chip_get_info": (C.c_int, [_P, C.POINTER(Info)]),
     "chip_profile_enable": (C.c_int, [_P, C.c_int32]),
     "chip_profile_reset": (C.c_int, [_P]),
@@ -764,6 +770,55 @@ class Chip:
         summ = RansacSummary()
         st = self.lib.chip_icp_ransac_matched(self.h, C.byref(p), _ptr(T), C.byref(conf), _ptr(mask), C.byref(summ))
         return self._matched(st, "chip_icp_ransac_matched", N, T, conf, mask, summ)
+
+    # -- one query frame against several candidate frames
+    def match_batch(self, frame_a: dict, frames_b, Kinv: np.ndarray) -> list:
+        """chip_match_batch: frame_a against every frame of frames_b (at most CHIP_MATCH_MAX_BATCH) -> the list of MatchSummary, one
+        per candidate.  The sets of all candidates stay on the device; candidate 0 is selected (match_select)."""
+        fa, keep_a = self._match_frame(frame_a)
+        made = [self._match_frame(f) for f in frames_b]
+        B = len(made)
+        fb = (MatchFrame * max(B, 1))(*[m[0] for m in made])
+        Ki = np.ascontiguousarray(Kinv, dtype=np.float64).reshape(9)
+        sm = (MatchSummary * max(B, 1))()
+        self._chk(self.lib.chip_match_batch(self.h, C.byref(fa), fb, B, _ptr(Ki), sm), "chip_match_batch")
+        self._match_batch_n1 = fa.n
+        return [MatchSummary.from_buffer_copy(sm[j]) for j in range(B)]
+
+    def match_select(self, j: int):
+        """make candidate j of the last match_batch the one match_read_sets / pnp_matched / icp_matched work on"""
+        self._chk(self.lib.chip_match_select(self.h, j), "chip_match_select")
+
+    def match_batch_matches(self, j: int):
+        """-> (train_idx, distance) int32 of candidate j of the last match_batch: the brute-force matches before GMS"""
+        n1 = getattr(self, "_match_batch_n1", 0)
+        idx = np.full(max(n1, 1), -1, dtype=np.int32)
+        dist = np.full(max(n1, 1), -1, dtype=np.int32)
+        self._chk(self.lib.chip_match_batch_read_matches(self.h, j, _ptr(idx), _ptr(dist)), "chip_match_batch_read_matches")
+        return idx[:n1].copy(), dist[:n1].copy()
+
+    def pnp_matched_batch(self, problems, params: RansacParams | None = None, seeds=None) -> list:
+        """chip_pnp_ransac_matched_batch.  problems: list of (candidate, which, N) with N = that set's count (it sizes the mask).
+        Entry i is what pnp_matched(which, N) returns after match_select(candidate) with seed seeds[i] (default: params.seed)."""
+        P = len(problems)
+        p = params or default_ransac_params()
+        cand = np.array([q[0] for q in problems], dtype=np.int32).reshape(P)
+        which = np.array([q[1] for q in problems], dtype=np.int32).reshape(P)
+        Ns = [int(q[2]) for q in problems]
+        T = np.empty((max(P, 1), 16), dtype=np.float64)
+        conf = np.zeros(max(P, 1), dtype=np.float32)
+        masks = [np.zeros(max(n, 1), dtype=np.uint8) for n in Ns]
+        mp = (C.c_void_p * max(P, 1))(*[m.ctypes.data for m in masks])
+        summ = (RansacSummary * max(P, 1))()
+        status = np.zeros(max(P, 1), dtype=np.int32)
+        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+        self._chk(self.lib.chip_pnp_ransac_matched_batch(self.h, P, _ptr(cand), _ptr(which), C.byref(p), None if sd is None else _ptr(sd), _ptr(T),
+                                                         _ptr(conf), mp, summ, _ptr(status)), "chip_pnp_ransac_matched_batch")
+        out = []
+        for i in range(P):
+            cf, s = C.c_float(float(conf[i])), RansacSummary.from_buffer_copy(summ[i])
+            out.append(self._matched(int(status[i]), "chip_pnp_ransac_matched_batch", Ns[i], T[i], cf, masks[i], s))
+        return out
 
     # -- introspection / profiling
     def info(self) -> dict:

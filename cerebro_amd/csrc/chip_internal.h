@@ -548,6 +548,8 @@ void match_destroy(Ctx *c);   // match.hip
 // host-pointer entries chip_pnp_ransac / chip_icp_ransac; the caller has validated the arguments and holds match_mu
 int pnp_ransac_device(Ctx *c, const double *X_dev, const double *uv_dev, int32_t N, const chip_ransac_params *p, double *T_colmajor,
                       float *confidence, uint8_t *inlier_mask, chip_ransac_summary *summary);
+int pnp_ransac_device_batch(Ctx *c, int32_t P, const double *const *X_dev, const double *const *uv_dev, const int32_t *N, const chip_ransac_params *p,
+                            const uint64_t *seeds, double *T_colmajor, float *confidence, uint8_t *const *inlier_mask, chip_ransac_summary *summary);
 int icp_ransac_device(Ctx *c, const double *A_dev, const double *B_dev, int32_t N, const chip_ransac_params *p, double *T_colmajor,
                       float *confidence, uint8_t *inlier_mask, chip_ransac_summary *summary);
 // chip_debug_ransac_record's ICP leg (icp.hip; the PnP leg lives with its state in pnp.hip): c is a plain ctx, every output may be null

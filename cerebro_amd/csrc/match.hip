@@ -14,12 +14,20 @@
 //                     make_3d_3d_collection__using__pfmatches_and_disparity (PointFeatureMatching.cpp:95-195) as ONE ordered stream
 //                     compaction (ballot + prefix popcount per wave, scan across the 16 waves): outputs are in match order, in the
 //                     layout pnp.hip / icp.hip take.
+//   chip_match_batch: one query frame against B <= 16 candidates -- hamming_match_split, gms_batch and pose_sets_batch are the three kernels
+//                     with a candidate dimension in the grid, sharing the loop, the GMS pass (gms_pass) and the compaction
+//                     (pose_sets_body) with them; the train tiles of a candidate are separate workgroups whose partial minima meet in
+//                     one 64-bit unsigned atomic minimum of distance << 32 | index.  chip_match_pair keeps its own three kernels.
 //
 // Nothing here rounds twice: float division / multiplication, the float -> double widenings, fp64 add / multiply / divide / sqrt are
 // single IEEE operations (-ffp-contract=off), the rest is integer.  tests/np_mirror_match.py restates all of it in numpy and
 // tests/test_match_gpu.py compares byte for byte.
 #include "chip_internal.h"
+#include "ransac_common.h"
 #include <climits>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 
@@ -104,74 +112,86 @@ __device__ __forceinline__ int gms_cell_right(float px, float py)
 // table entries are written by atomics (performed in L2) and read back by other lanes of the workgroup: read them at agent scope too
 __device__ __forceinline__ int32_t table_load(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-__global__ __launch_bounds__(kOneWg) void gms_filter(GmsArgs a)
+// One grid type of gms_matcher::run (gms_matcher.cpp:161-177) by ONE workgroup of kOneWg threads: match(i, &lp, &rp) fetches the keypoints of
+// match i, mark(i, hit) receives whether its cell pair is the accepted pair of its left cell.  gms_filter runs the four types one after
+// another on one table, gms_batch one type per workgroup on a table of its own.
+template <class Match, class Mark>
+__device__ __forceinline__ void gms_pass(int type, int n, int32_t *table, float fw1, float fh1, float fw2, float fh2, Match match, Mark mark)
 {
     __shared__ int32_t cnt[kCells];      // mNumberPointsInPerCellLeft
     __shared__ int32_t pair[kCells];     // mCellPairs
-    __shared__ int32_t total;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float fw1 = (float)a.w1, fh1 = (float)a.h1, fw2 = (float)a.w2, fh2 = (float)a.h2;
+    // ---- :161-163
+    for (int e = tid; e < kCells * kCells / 4; e += kOneWg) reinterpret_cast<int4 *>(table)[e] = make_int4(0, 0, 0, 0);
+    for (int e = tid; e < kCells; e += kOneWg) { cnt[e] = 0; pair[e] = -1; }
+    __threadfence();
+    __syncthreads();
+    // ---- AssignMatchPairs (:73-98); NormalizePoints (gms_matcher.h:126-139): float / int -> one float division
+    for (int i = tid; i < n; i += kOneWg) {
+        float2 lp, rp;
+        match(i, &lp, &rp);
+        const int l = gms_cell_left(__fdiv_rn(lp.x, fw1), __fdiv_rn(lp.y, fh1), type);
+        const int r = gms_cell_right(__fdiv_rn(rp.x, fw2), __fdiv_rn(rp.y, fh2));
+        if (l < 0 || r < 0) continue;                     // :92
+        atomicAdd(&table[l * kCells + r], 1);             // :94
+        atomicAdd(&cnt[l], 1);                            // :95
+    }
+    __threadfence();
+    __syncthreads();
+    // ---- VerifyCellPairs, first half (:106-121): per non-empty row the first column of maximal count.  One wave per row.
+    for (int row = wave; row < kCells; row += kOneWg / 64) {
+        if (cnt[row] == 0) continue;                      // sum(row) == 0 (:106): every increment of the row also counted in cnt
+        int bv = 0, bj = INT_MAX;
+        for (int j = lane; j < kCells; j += 64) {
+            const int v = table_load(&table[row * kCells + j]);
+            if (v > bv) { bv = v; bj = j; }
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            const int ov = __shfl_xor(bv, m, 64), oj = __shfl_xor(bj, m, 64);
+            if (ov > bv || (ov == bv && oj < bj)) { bv = ov; bj = oj; }
+        }
+        if (lane == 0) pair[row] = bj;
+    }
+    __syncthreads();
+    // ---- second half (:123-146): 3 x 3 neighbourhood score (GetNB9, gms_matcher.h:197-217; rotation pattern 1: same offset both sides)
+    if (tid < kCells && pair[tid] >= 0) {
+        const int lx = tid % kGrid, ly = tid / kGrid, rx = pair[tid] % kGrid, ry = pair[tid] / kGrid;
+        int score = 0, tsum = 0, numpair = 0;
+        for (int dy = -1; dy <= 1; dy++)
+            for (int dx = -1; dx <= 1; dx++) {
+                const int llx = lx + dx, lly = ly + dy, rrx = rx + dx, rry = ry + dy;
+                if (llx < 0 || llx >= kGrid || lly < 0 || lly >= kGrid || rrx < 0 || rrx >= kGrid || rry < 0 || rry >= kGrid) continue;   // :136
+                const int ll = llx + lly * kGrid, rr = rrx + rry * kGrid;
+                score += table_load(&table[ll * kCells + rr]);
+                tsum += cnt[ll];
+                numpair++;
+            }
+        const double thresh = 6.0 * sqrt((double)tsum / (double)numpair);   // THRESH_FACTOR (gms_matcher.h:9), :143
+        if ((double)score < thresh) pair[tid] = -2;                            // :145-146 (only this lane reads pair[tid] before the barrier)
+    }
+    __syncthreads();
+    // ---- mark (:169-177)
+    for (int i = tid; i < n; i += kOneWg) {
+        float2 lp, rp;
+        match(i, &lp, &rp);
+        const int l = gms_cell_left(__fdiv_rn(lp.x, fw1), __fdiv_rn(lp.y, fh1), type);
+        const int r = gms_cell_right(__fdiv_rn(rp.x, fw2), __fdiv_rn(rp.y, fh2));
+        mark(i, l >= 0 && r >= 0 && pair[l] == r);
+    }
+    __syncthreads();                                      // pair / cnt are rewritten by the next pass
+}
+
+__global__ __launch_bounds__(kOneWg) void gms_filter(GmsArgs a)
+{
+    __shared__ int32_t total;
+    const int tid = threadIdx.x, lane = tid & 63;
     if (tid == 0) total = 0;
     for (int i = tid; i < a.n; i += kOneWg) a.inlier[i] = 0;   // mvbInlierMask.assign(false) (gms_matcher.cpp:152); own bytes, same lane later
-    for (int type = 1; type <= 4; type++) {                   // :158
-        // ---- :161-163
-        for (int e = tid; e < kCells * kCells / 4; e += kOneWg) reinterpret_cast<int4 *>(a.table)[e] = make_int4(0, 0, 0, 0);
-        for (int e = tid; e < kCells; e += kOneWg) { cnt[e] = 0; pair[e] = -1; }
-        __threadfence();
-        __syncthreads();
-        // ---- AssignMatchPairs (:73-98); NormalizePoints (gms_matcher.h:126-139): float / int -> one float division
-        for (int i = tid; i < a.n; i += kOneWg) {
-            const float2 lp = a.kp1[a.qidx ? a.qidx[i] : i], rp = a.kp2[a.tidx[i]];
-            const int l = gms_cell_left(__fdiv_rn(lp.x, fw1), __fdiv_rn(lp.y, fh1), type);
-            const int r = gms_cell_right(__fdiv_rn(rp.x, fw2), __fdiv_rn(rp.y, fh2));
-            if (l < 0 || r < 0) continue;                     // :92
-            atomicAdd(&a.table[l * kCells + r], 1);           // :94
-            atomicAdd(&cnt[l], 1);                            // :95
-        }
-        __threadfence();
-        __syncthreads();
-        // ---- VerifyCellPairs, first half (:106-121): per non-empty row the first column of maximal count.  One wave per row.
-        for (int row = wave; row < kCells; row += kOneWg / 64) {
-            if (cnt[row] == 0) continue;                      // sum(row) == 0 (:106): every increment of the row also counted in cnt
-            int bv = 0, bj = INT_MAX;
-            for (int j = lane; j < kCells; j += 64) {
-                const int v = table_load(&a.table[row * kCells + j]);
-                if (v > bv) { bv = v; bj = j; }
-            }
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-                const int ov = __shfl_xor(bv, m, 64), oj = __shfl_xor(bj, m, 64);
-                if (ov > bv || (ov == bv && oj < bj)) { bv = ov; bj = oj; }
-            }
-            if (lane == 0) pair[row] = bj;
-        }
-        __syncthreads();
-        // ---- second half (:123-146): 3 x 3 neighbourhood score (GetNB9, gms_matcher.h:197-217; rotation pattern 1: same offset both sides)
-        if (tid < kCells && pair[tid] >= 0) {
-            const int lx = tid % kGrid, ly = tid / kGrid, rx = pair[tid] % kGrid, ry = pair[tid] / kGrid;
-            int score = 0, tsum = 0, numpair = 0;
-            for (int dy = -1; dy <= 1; dy++)
-                for (int dx = -1; dx <= 1; dx++) {
-                    const int llx = lx + dx, lly = ly + dy, rrx = rx + dx, rry = ry + dy;
-                    if (llx < 0 || llx >= kGrid || lly < 0 || lly >= kGrid || rrx < 0 || rrx >= kGrid || rry < 0 || rry >= kGrid) continue;   // :136
-                    const int ll = llx + lly * kGrid, rr = rrx + rry * kGrid;
-                    score += table_load(&a.table[ll * kCells + rr]);
-                    tsum += cnt[ll];
-                    numpair++;
-                }
-            const double thresh = 6.0 * sqrt((double)tsum / (double)numpair);   // THRESH_FACTOR (gms_matcher.h:9), :143
-            if ((double)score < thresh) pair[tid] = -2;                            // :145-146 (only this lane reads pair[tid] before the barrier)
-        }
-        __syncthreads();
-        // ---- mark (:169-177)
-        for (int i = tid; i < a.n; i += kOneWg) {
-            const float2 lp = a.kp1[a.qidx ? a.qidx[i] : i], rp = a.kp2[a.tidx[i]];
-            const int l = gms_cell_left(__fdiv_rn(lp.x, fw1), __fdiv_rn(lp.y, fh1), type);
-            const int r = gms_cell_right(__fdiv_rn(rp.x, fw2), __fdiv_rn(rp.y, fh2));
-            if (l >= 0 && r >= 0 && pair[l] == r) a.inlier[i] = 1;
-        }
-        __syncthreads();                                      // pair / cnt are rewritten by the next pass
-    }
+    for (int type = 1; type <= 4; type++)                     // :158
+        gms_pass(type, a.n, a.table, (float)a.w1, (float)a.h1, (float)a.w2, (float)a.h2,
+                 [&](int i, float2 *lp, float2 *rp) { *lp = a.kp1[a.qidx ? a.qidx[i] : i]; *rp = a.kp2[a.tidx[i]]; },
+                 [&](int i, bool hit) { if (hit) a.inlier[i] = 1; });
     int mine = 0;
     for (int i = tid; i < a.n; i += kOneWg) mine += a.inlier[i];
 #pragma unroll
@@ -207,7 +227,10 @@ __device__ __forceinline__ bool pixel_of(float2 p, int w, int h, int *x, int *y)
 // the depth gate of :122 / :182: "z < 0.1 || z > 25." with the float z widened to double
 __device__ __forceinline__ bool depth_ok(float z) { return !((double)z < 0.1 || (double)z > 25.); }
 
-__global__ __launch_bounds__(kOneWg) void pose_sets_build(SetsArgs a)
+// The ordered compaction by ONE workgroup of kOneWg threads; inlier(i) / train(i): the GMS mark and the train index of match i
+// (pose_sets_build: the arrays of a; pose_sets_batch: the four planes of gms_batch and the merged keys)
+template <class Inlier, class Train>
+__device__ __forceinline__ void pose_sets_body(const SetsArgs &a, Inlier inlier, Train train)
 {
     __shared__ int32_t wtot[kNSets][kOneWg / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -218,8 +241,8 @@ __global__ __launch_bounds__(kOneWg) void pose_sets_build(SetsArgs a)
         float2 pa = make_float2(0.f, 0.f), pb = pa;
         int t = 0;
         size_t oa = 0, ob = 0;
-        if (i < a.n && a.inlier[i]) {
-            t = a.tidx[i];
+        if (i < a.n && inlier(i)) {
+            t = train(i);
             pa = a.kp1[i]; pb = a.kp2[t];
             int xa, ya, xb, yb;
             const bool in_a = pixel_of(pa, a.w1, a.h1, &xa, &ya), in_b = pixel_of(pb, a.w2, a.h2, &xb, &yb);
@@ -271,6 +294,110 @@ __global__ __launch_bounds__(kOneWg) void pose_sets_build(SetsArgs a)
     if (tid < kNSets) a.counts[tid] = run[tid];
 }
 
+__global__ __launch_bounds__(kOneWg) void pose_sets_build(SetsArgs a)
+{
+    pose_sets_body(a, [&](int i) { return a.inlier[i] != 0; }, [&](int i) { return a.tidx[i]; });
+}
+
+// ------------------------------------------------------------------------------------------------ one query frame, B candidates
+// chip_match_batch: the three kernels above with a candidate dimension in the grid.  Candidate j's descriptors, keypoints, 3-D image and
+// sizes travel in the kernel arguments; all B pairs read ONE device copy of the query frame.
+constexpr int kMaxBatch = CHIP_MATCH_MAX_BATCH;
+struct BatchCand {
+    const uint4 *desc;            // n x 2
+    const float2 *kp;             // n
+    const float *xyz;             // h x w x 3
+    int32_t n, w, h, pad_;
+};
+struct BatchCands { BatchCand c[kMaxBatch]; };
+
+// A partial minimum as ONE unsigned 64-bit key, distance << 32 | train index: the unsigned minimum over the tiles of a (query, candidate)
+// is the smallest distance and, among equal distances, the LOWEST index -- the tie rule of orb_bf_match, whichever tile arrives first.
+// All ones (the preset) decodes to index -1, distance -1: no train descriptors.
+__device__ __forceinline__ int32_t key_train(unsigned long long k) { return (int32_t)(uint32_t)k; }
+
+// grid (query blocks of 256, train tiles of 1024, B): orb_bf_match's loop over ONE tile; a tile past the candidate's n leaves at once
+__global__ __launch_bounds__(kBfThreads) void hamming_match_split(const uint4 *__restrict__ query, int n1, BatchCands cands,
+                                                                  unsigned long long *__restrict__ keys /* [B][n1] */)
+{
+    __shared__ uint4 tile[2 * kBfTile];
+    const int z = blockIdx.z, base = blockIdx.y * kBfTile, n2 = cands.c[z].n;
+    if (base >= n2) return;                                   // workgroup-uniform
+    const uint4 *__restrict__ train = cands.c[z].desc;
+    const int cnt = n2 - base < kBfTile ? n2 - base : kBfTile;
+    const int i = blockIdx.x * kBfThreads + threadIdx.x;
+    const int qi = i < n1 ? i : n1 - 1;                       // n1 >= 1: the tail lanes scan a valid descriptor and store nothing
+    const uint4 q0 = query[2 * (size_t)qi], q1 = query[2 * (size_t)qi + 1];
+    for (int e = threadIdx.x; e < 2 * cnt; e += kBfThreads) tile[e] = train[2 * (size_t)base + e];
+    __syncthreads();
+    int best = INT_MAX, bidx = -1;
+#pragma unroll 4
+    for (int j = 0; j < cnt; j++) {
+        const uint4 a = tile[2 * j], b = tile[2 * j + 1];      // wave-uniform address: one broadcast read
+        const int d = __popc(q0.x ^ a.x) + __popc(q0.y ^ a.y) + __popc(q0.z ^ a.z) + __popc(q0.w ^ a.w) +
+                      __popc(q1.x ^ b.x) + __popc(q1.y ^ b.y) + __popc(q1.z ^ b.z) + __popc(q1.w ^ b.w);
+        if (d < best) { best = d; bidx = base + j; }          // strict: the first minimum of the tile stays
+    }
+    if (i < n1)                                               // cnt >= 1: bidx >= 0.  One native 64-bit unsigned minimum per lane and tile
+        __hip_atomic_fetch_min(&keys[(size_t)z * n1 + i], ((unsigned long long)(uint32_t)best << 32) | (uint32_t)bidx, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+}
+
+struct GmsBatchArgs {
+    const float2 *kp1;                    // the query frame's keypoints; match i of candidate j = (i, train index of keys[j][i])
+    int32_t n1, w1, h1;
+    const unsigned long long *keys;       // [B][n1]
+    int32_t *table;                       // [B][4][400][400]
+    uint8_t *plane;                       // [B][4][n1]: the marks of ONE grid type each (pose_sets_batch takes their OR)
+    BatchCands cands;
+};
+// grid (4 grid types, B): gms_filter's pass, one workgroup per (type, candidate) on its own table, writing its own byte plane
+__global__ __launch_bounds__(kOneWg) void gms_batch(GmsBatchArgs a)
+{
+    const int type = blockIdx.x + 1, z = blockIdx.y;
+    if (a.cands.c[z].n == 0) return;                          // no matches: pose_sets_batch does not read this candidate's planes
+    const float2 *kp2 = a.cands.c[z].kp;
+    const unsigned long long *keys = a.keys + (size_t)z * a.n1;
+    uint8_t *plane = a.plane + ((size_t)z * 4 + blockIdx.x) * a.n1;
+    gms_pass(type, a.n1, a.table + ((size_t)z * 4 + blockIdx.x) * (kCells * kCells), (float)a.w1, (float)a.h1, (float)a.cands.c[z].w,
+             (float)a.cands.c[z].h, [&](int i, float2 *lp, float2 *rp) { *lp = a.kp1[i]; *rp = kp2[key_train(keys[i])]; },
+             [&](int i, bool hit) { plane[i] = hit ? 1 : 0; });
+}
+
+struct SetsBatchArgs {
+    const float2 *kp1;
+    const float *xyz_a;
+    int32_t n1, w1, h1;
+    const unsigned long long *keys;       // [B][n1]
+    const uint8_t *plane;                 // [B][4][n1]
+    double Kinv[9];
+    double *uv, *uv_d, *X_ab, *uvn_ab, *X_ba, *uvn_ba, *A, *B;   // slabs of n1 rows per candidate
+    int32_t *mq, *mt;
+    int32_t *counts;                      // [B][kNSets]
+    BatchCands cands;
+};
+// grid B: pose_sets_build for candidate blockIdx.x, inlier = the OR of its four planes, outputs into its slabs
+__global__ __launch_bounds__(kOneWg) void pose_sets_batch(SetsBatchArgs b)
+{
+    const int z = blockIdx.x;
+    if (b.cands.c[z].n == 0) {
+        if (threadIdx.x < kNSets) b.counts[z * kNSets + threadIdx.x] = 0;
+        return;
+    }
+    const size_t row = (size_t)z * b.n1;
+    SetsArgs a;
+    a.kp1 = b.kp1; a.kp2 = b.cands.c[z].kp; a.tidx = nullptr; a.inlier = nullptr; a.n = b.n1;
+    a.xyz_a = b.xyz_a; a.xyz_b = b.cands.c[z].xyz; a.w1 = b.w1; a.h1 = b.h1; a.w2 = b.cands.c[z].w; a.h2 = b.cands.c[z].h;
+    for (int k = 0; k < 9; k++) a.Kinv[k] = b.Kinv[k];
+    a.uv = b.uv + 2 * row; a.uv_d = b.uv_d + 2 * row; a.X_ab = b.X_ab + 3 * row; a.uvn_ab = b.uvn_ab + 2 * row;
+    a.X_ba = b.X_ba + 3 * row; a.uvn_ba = b.uvn_ba + 2 * row; a.A = b.A + 3 * row; a.B = b.B + 3 * row;
+    a.mq = b.mq + row; a.mt = b.mt + row; a.counts = b.counts + z * kNSets;
+    const unsigned long long *keys = b.keys + row;
+    const uint8_t *p = b.plane + 4 * row;
+    const size_t n1 = (size_t)b.n1;
+    pose_sets_body(a, [&](int i) { return (p[i] | p[n1 + i] | p[2 * n1 + i] | p[3 * n1 + i]) != 0; }, [&](int i) { return key_train(keys[i]); });
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 struct MatchState {
     // inputs / intermediates, sized for kMatchMax keypoints once
@@ -283,12 +410,43 @@ struct MatchState {
     DevBuf<int32_t> mq, mt;
     DevBuf<float> xyz_a, xyz_b;                 // grown on demand
     PinnedBuf<int32_t> h_counts;
+    // chip_match_batch: the candidates' frames, the merged keys, one table and one plane per (candidate, grid type) and the five sets in
+    // slabs of n1 rows per candidate; all grown on demand (batch_reserve)
+    DevBuf<uint8_t> b_desc;                     // candidate j at b_desc + 32 * (n of the candidates before it), b_kp alike
+    DevBuf<float2> b_kp;
+    DevBuf<float> b_xyz;
+    DevBuf<unsigned long long> b_keys;
+    DevBuf<int32_t> b_table, b_counts;
+    DevBuf<uint8_t> b_plane;
+    DevBuf<double> b_uv, b_uv_d, b_X_ab, b_uvn_ab, b_X_ba, b_uvn_ba, b_A, b_B;
+    DevBuf<int32_t> b_mq, b_mt;
+    PinnedBuf<int32_t> h_bcounts;
+    std::vector<unsigned long long> h_keys;     // chip_match_batch_read_matches: one candidate's keys on their way out
+    hipEvent_t b_ev[4] = {};                    // tuning only (CHIP_MATCH_BATCH_TIMING=1): around the three launches of a batch
+    // what the last chip_match_pair / chip_match_batch left: n_cand candidates (a pair: one), of which ONE is selected -- the pointers and
+    // counts chip_match_read_sets and the _matched solvers work on
+    struct Sets { double *uv, *uv_d, *X_ab, *uvn_ab, *X_ba, *uvn_ba, *A, *B; int32_t *mq, *mt; };
     bool have_sets = false;
-    chip_match_summary last{};
+    bool from_batch = false;                    // the candidates are chip_match_batch's (slabs of batch_n1 rows)
+    int32_t n_cand = 0, batch_n1 = 0;
+    chip_match_summary cand_sm[CHIP_MATCH_MAX_BATCH] = {};
+    Sets cur{};
+    chip_match_summary last{};                  // the selected candidate's summary
+
+    void select(int32_t j)                      // 0 <= j < n_cand
+    {
+        const size_t r = from_batch ? (size_t)j * (size_t)batch_n1 : 0;
+        if (from_batch) cur = Sets{b_uv + 2 * r, b_uv_d + 2 * r, b_X_ab + 3 * r, b_uvn_ab + 2 * r, b_X_ba + 3 * r, b_uvn_ba + 2 * r, b_A + 3 * r, b_B + 3 * r, b_mq + r, b_mt + r};
+        else cur = Sets{uv, uv_d, X_ab, uvn_ab, X_ba, uvn_ba, A, B, mq, mt};
+        last = cand_sm[j];
+    }
 };
 
 void match_destroy(Ctx *c)
 {
+    if (c->match_state)
+        for (hipEvent_t e : c->match_state->b_ev)
+            if (e) (void)hipEventDestroy(e);
     delete c->match_state;
     c->match_state = nullptr;
 }
@@ -359,6 +517,38 @@ static int check_frame(const chip_match_frame *f)
     if (f->n > 0 && (!f->desc || !f->kp_xy)) return CHIP_ERR_INVALID_ARG;
     if (f->n > kMatchMax || f->width > kMaxImageSide || f->height > kMaxImageSide) return CHIP_ERR_UNSUPPORTED;
     return CHIP_OK;
+}
+
+// chip_match_batch's buffers for B candidates of a query frame of n1 keypoints: tot_n keypoints and tot_px pixels over all candidates.
+// Whatever has to grow grows inside ONE pause (as match_state).
+static int batch_reserve(Ctx *c, MatchState *st, size_t B, size_t n1, size_t tot_n, size_t tot_px, size_t px_a)
+{
+    const size_t rows = B * n1;
+    const bool fits = st->xyz_a.capacity() >= 3 * px_a && st->b_desc.capacity() >= tot_n * CHIP_ORB_DESC_BYTES && st->b_kp.capacity() >= tot_n &&
+                      st->b_xyz.capacity() >= 3 * tot_px && st->b_keys.capacity() >= rows && st->b_table.capacity() >= B * 4 * kCells * kCells &&
+                      st->b_plane.capacity() >= 4 * rows && st->b_uv.capacity() >= 2 * rows && st->b_counts.capacity() && st->h_bcounts.capacity();
+    if (fits) return CHIP_OK;   // the set buffers grow together with b_uv
+    ResidentPause paused(c);
+    int rc = st->xyz_a.reserve(c, 3 * px_a);
+    if (rc == CHIP_OK) rc = st->b_desc.reserve(c, tot_n * CHIP_ORB_DESC_BYTES);
+    if (rc == CHIP_OK) rc = st->b_kp.reserve(c, tot_n);
+    if (rc == CHIP_OK) rc = st->b_xyz.reserve(c, 3 * tot_px);
+    if (rc == CHIP_OK) rc = st->b_keys.reserve(c, rows);
+    if (rc == CHIP_OK) rc = st->b_table.reserve(c, B * 4 * kCells * kCells);
+    if (rc == CHIP_OK) rc = st->b_plane.reserve(c, 4 * rows);
+    if (rc == CHIP_OK) rc = st->b_uv_d.reserve(c, 2 * rows);
+    if (rc == CHIP_OK) rc = st->b_X_ab.reserve(c, 3 * rows);
+    if (rc == CHIP_OK) rc = st->b_uvn_ab.reserve(c, 2 * rows);
+    if (rc == CHIP_OK) rc = st->b_X_ba.reserve(c, 3 * rows);
+    if (rc == CHIP_OK) rc = st->b_uvn_ba.reserve(c, 2 * rows);
+    if (rc == CHIP_OK) rc = st->b_A.reserve(c, 3 * rows);
+    if (rc == CHIP_OK) rc = st->b_B.reserve(c, 3 * rows);
+    if (rc == CHIP_OK) rc = st->b_mq.reserve(c, rows);
+    if (rc == CHIP_OK) rc = st->b_mt.reserve(c, rows);
+    if (rc == CHIP_OK) rc = st->b_counts.reserve(c, kMaxBatch * kNSets);
+    if (rc == CHIP_OK) rc = st->h_bcounts.reserve(c, kMaxBatch * kNSets);
+    if (rc == CHIP_OK) rc = st->b_uv.reserve(c, 2 * rows);   // last: its capacity stands for the whole group of set buffers
+    return rc;
 }
 
 }  // namespace chip
@@ -465,7 +655,10 @@ extern "C" int chip_match_pair(chip_ctx *c, const chip_match_frame *a, const chi
         sm.n_3d3d = st->h_counts.host()[kSet33];
         sm.n_out_of_image = st->h_counts.host()[kSetOut];
     }
-    st->last = sm;
+    st->from_batch = false;
+    st->n_cand = 1;
+    st->cand_sm[0] = sm;
+    st->select(0);
     st->have_sets = true;
     *summary = sm;
     return CHIP_OK;
@@ -485,16 +678,16 @@ extern "C" int chip_match_read_sets(chip_ctx *c, chip_match_sets_out *out)
         return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
     };
     const size_t g = (size_t)m.n_matches_gms, ab = (size_t)m.n_3d2d_ab, ba = (size_t)m.n_3d2d_ba, dd = (size_t)m.n_3d3d;
-    CHIP_HIP(c, fetch(out->uv, st->uv, g * 2 * sizeof(double)));
-    CHIP_HIP(c, fetch(out->uv_d, st->uv_d, g * 2 * sizeof(double)));
-    CHIP_HIP(c, fetch(out->X_ab, st->X_ab, ab * 3 * sizeof(double)));
-    CHIP_HIP(c, fetch(out->uvn_ab, st->uvn_ab, ab * 2 * sizeof(double)));
-    CHIP_HIP(c, fetch(out->X_ba, st->X_ba, ba * 3 * sizeof(double)));
-    CHIP_HIP(c, fetch(out->uvn_ba, st->uvn_ba, ba * 2 * sizeof(double)));
-    CHIP_HIP(c, fetch(out->A_3d3d, st->A, dd * 3 * sizeof(double)));
-    CHIP_HIP(c, fetch(out->B_3d3d, st->B, dd * 3 * sizeof(double)));
-    CHIP_HIP(c, fetch(out->match_query_idx, st->mq, g * sizeof(int32_t)));
-    CHIP_HIP(c, fetch(out->match_train_idx, st->mt, g * sizeof(int32_t)));
+    CHIP_HIP(c, fetch(out->uv, st->cur.uv, g * 2 * sizeof(double)));
+    CHIP_HIP(c, fetch(out->uv_d, st->cur.uv_d, g * 2 * sizeof(double)));
+    CHIP_HIP(c, fetch(out->X_ab, st->cur.X_ab, ab * 3 * sizeof(double)));
+    CHIP_HIP(c, fetch(out->uvn_ab, st->cur.uvn_ab, ab * 2 * sizeof(double)));
+    CHIP_HIP(c, fetch(out->X_ba, st->cur.X_ba, ba * 3 * sizeof(double)));
+    CHIP_HIP(c, fetch(out->uvn_ba, st->cur.uvn_ba, ba * 2 * sizeof(double)));
+    CHIP_HIP(c, fetch(out->A_3d3d, st->cur.A, dd * 3 * sizeof(double)));
+    CHIP_HIP(c, fetch(out->B_3d3d, st->cur.B, dd * 3 * sizeof(double)));
+    CHIP_HIP(c, fetch(out->match_query_idx, st->cur.mq, g * sizeof(int32_t)));
+    CHIP_HIP(c, fetch(out->match_train_idx, st->cur.mt, g * sizeof(int32_t)));
     CHIP_HIP(c, hipStreamSynchronize(s));
     return CHIP_OK;
 }
@@ -507,8 +700,8 @@ extern "C" int chip_pnp_ransac_matched(chip_ctx *c, int32_t which, const chip_ra
     std::lock_guard<std::mutex> lk(c->match_mu);
     MatchState *st = c->match_state;
     if (!st || !st->have_sets) return CHIP_ERR_BUSY;
-    if (which == CHIP_SET_AB) return pnp_ransac_device(c, st->X_ab, st->uvn_ab, st->last.n_3d2d_ab, p, T_colmajor, confidence, inlier_mask, summary);
-    return pnp_ransac_device(c, st->X_ba, st->uvn_ba, st->last.n_3d2d_ba, p, T_colmajor, confidence, inlier_mask, summary);
+    if (which == CHIP_SET_AB) return pnp_ransac_device(c, st->cur.X_ab, st->cur.uvn_ab, st->last.n_3d2d_ab, p, T_colmajor, confidence, inlier_mask, summary);
+    return pnp_ransac_device(c, st->cur.X_ba, st->cur.uvn_ba, st->last.n_3d2d_ba, p, T_colmajor, confidence, inlier_mask, summary);
 }
 
 extern "C" int chip_icp_ransac_matched(chip_ctx *c, const chip_ransac_params *p, double T_colmajor[16], float *confidence, uint8_t *inlier_mask,
@@ -519,5 +712,204 @@ extern "C" int chip_icp_ransac_matched(chip_ctx *c, const chip_ransac_params *p,
     std::lock_guard<std::mutex> lk(c->match_mu);
     MatchState *st = c->match_state;
     if (!st || !st->have_sets) return CHIP_ERR_BUSY;
-    return icp_ransac_device(c, st->A, st->B, st->last.n_3d3d, p, T_colmajor, confidence, inlier_mask, summary);
+    return icp_ransac_device(c, st->cur.A, st->cur.B, st->last.n_3d3d, p, T_colmajor, confidence, inlier_mask, summary);
+}
+
+// ------------------------------------------------------------------------------------------------ one query frame against B candidates
+extern "C" int chip_build_has_match_batch(void) { return 1; }
+
+extern "C" int chip_match_batch(chip_ctx *c, const chip_match_frame *a, const chip_match_frame *b, int32_t B, const double Kinv[9],
+                                chip_match_summary *summary)
+{
+    if (!c) return CHIP_ERR_INVALID_ARG;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    if (c->match_state) c->match_state->have_sets = false;   // a failed call, refused arguments included, leaves nothing selected
+    if (!a || !b || !Kinv || !summary || B < 1) return CHIP_ERR_INVALID_ARG;
+    if (B > kMaxBatch) return CHIP_ERR_UNSUPPORTED;
+    int rc = check_frame(a);
+    for (int j = 0; j < B && rc == CHIP_OK; j++) rc = check_frame(&b[j]);
+    if (rc != CHIP_OK) return rc;
+    CHIP_HIP(c, hipSetDevice(c->device));
+    MatchState *st = nullptr;
+    rc = match_state(c, &st);
+    if (rc != CHIP_OK) return rc;
+    st->have_sets = false;
+    const int n1 = a->n;
+    int max_n2 = 0;
+    size_t tot_n = 0, tot_px = 0;
+    for (int j = 0; j < B; j++) {
+        if (b[j].n == 0) continue;               // an empty candidate is not uploaded
+        max_n2 = b[j].n > max_n2 ? b[j].n : max_n2;
+        tot_n += (size_t)b[j].n;
+        tot_px += (size_t)b[j].width * b[j].height;
+    }
+    for (int j = 0; j < B; j++) std::memset(&st->cand_sm[j], 0, sizeof(chip_match_summary));
+    if (n1 > 0) {
+        const size_t px_a = (size_t)a->width * a->height;
+        rc = batch_reserve(c, st, (size_t)B, (size_t)n1, tot_n, tot_px, px_a);
+        if (rc != CHIP_OK) return rc;
+        hipStream_t s = match_stream(c);
+        CHIP_HIP(c, hipMemsetAsync(st->b_keys, 0xff, (size_t)B * n1 * sizeof(unsigned long long), s));   // all ones: no match yet
+        if (max_n2 > 0) {
+            CHIP_HIP(c, hipMemcpyAsync(st->d1, a->desc, (size_t)n1 * CHIP_ORB_DESC_BYTES, hipMemcpyHostToDevice, s));
+            CHIP_HIP(c, hipMemcpyAsync(st->kp1, a->kp_xy, (size_t)n1 * sizeof(float2), hipMemcpyHostToDevice, s));
+            CHIP_HIP(c, hipMemcpyAsync(st->xyz_a, a->xyz, 3 * px_a * sizeof(float), hipMemcpyHostToDevice, s));
+            BatchCands cands;
+            std::memset(&cands, 0, sizeof cands);
+            size_t off_n = 0, off_px = 0;
+            for (int j = 0; j < B; j++) {
+                const int n2 = b[j].n;
+                if (n2 == 0) continue;
+                const size_t px = (size_t)b[j].width * b[j].height;
+                uint8_t *dd = st->b_desc + off_n * CHIP_ORB_DESC_BYTES;
+                float2 *dk = st->b_kp + off_n;
+                float *dx = st->b_xyz + 3 * off_px;
+                CHIP_HIP(c, hipMemcpyAsync(dd, b[j].desc, (size_t)n2 * CHIP_ORB_DESC_BYTES, hipMemcpyHostToDevice, s));
+                CHIP_HIP(c, hipMemcpyAsync(dk, b[j].kp_xy, (size_t)n2 * sizeof(float2), hipMemcpyHostToDevice, s));
+                CHIP_HIP(c, hipMemcpyAsync(dx, b[j].xyz, 3 * px * sizeof(float), hipMemcpyHostToDevice, s));
+                cands.c[j] = BatchCand{reinterpret_cast<const uint4 *>(dd), dk, dx, n2, b[j].width, b[j].height, 0};
+                off_n += (size_t)n2; off_px += px;
+            }
+            // tuning only (CHIP_MATCH_BATCH_TIMING=1): device time of each of the three kernels by events, averaged, printed at process exit
+            struct KernelTiming {
+                double acc[3] = {0, 0, 0}; long n = 0; bool on = std::getenv("CHIP_MATCH_BATCH_TIMING") != nullptr;
+                ~KernelTiming() { if (on && n) std::fprintf(stderr, "match batch kernel timing over %ld calls (us): hamming_match_split %.1f, gms_batch %.1f, pose_sets_batch %.1f\n",
+                                                            n, 1e3 * acc[0] / n, 1e3 * acc[1] / n, 1e3 * acc[2] / n); }
+            };
+            static KernelTiming kt;
+            if (kt.on)
+                for (hipEvent_t &e : st->b_ev)
+                    if (!e) CHIP_HIP(c, hipEventCreate(&e));
+            if (kt.on) CHIP_HIP(c, hipEventRecord(st->b_ev[0], s));
+            hipLaunchKernelGGL(hamming_match_split, dim3((n1 + kBfThreads - 1) / kBfThreads, (max_n2 + kBfTile - 1) / kBfTile, B), dim3(kBfThreads), 0, s,
+                               reinterpret_cast<const uint4 *>(st->d1.get()), n1, cands, st->b_keys.get());
+            CHIP_HIP(c, hipGetLastError());
+            if (kt.on) CHIP_HIP(c, hipEventRecord(st->b_ev[1], s));
+            GmsBatchArgs ga;
+            ga.kp1 = st->kp1; ga.n1 = n1; ga.w1 = a->width; ga.h1 = a->height; ga.keys = st->b_keys; ga.table = st->b_table; ga.plane = st->b_plane;
+            ga.cands = cands;
+            hipLaunchKernelGGL(gms_batch, dim3(4, B), dim3(kOneWg), 0, s, ga);
+            CHIP_HIP(c, hipGetLastError());
+            if (kt.on) CHIP_HIP(c, hipEventRecord(st->b_ev[2], s));
+            SetsBatchArgs sa;
+            sa.kp1 = st->kp1; sa.xyz_a = st->xyz_a; sa.n1 = n1; sa.w1 = a->width; sa.h1 = a->height; sa.keys = st->b_keys; sa.plane = st->b_plane;
+            for (int i = 0; i < 9; i++) sa.Kinv[i] = Kinv[i];
+            sa.uv = st->b_uv; sa.uv_d = st->b_uv_d; sa.X_ab = st->b_X_ab; sa.uvn_ab = st->b_uvn_ab; sa.X_ba = st->b_X_ba; sa.uvn_ba = st->b_uvn_ba;
+            sa.A = st->b_A; sa.B = st->b_B; sa.mq = st->b_mq; sa.mt = st->b_mt; sa.counts = st->b_counts; sa.cands = cands;
+            hipLaunchKernelGGL(pose_sets_batch, dim3(B), dim3(kOneWg), 0, s, sa);
+            CHIP_HIP(c, hipGetLastError());
+            if (kt.on) CHIP_HIP(c, hipEventRecord(st->b_ev[3], s));
+            CHIP_HIP(c, hipMemcpyAsync(st->h_bcounts.host(), st->b_counts, (size_t)B * kNSets * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            CHIP_HIP(c, hipStreamSynchronize(s));
+            for (int k = 0; k < 3 && kt.on; k++) {
+                float ms = 0.f;
+                CHIP_HIP(c, hipEventElapsedTime(&ms, st->b_ev[k], st->b_ev[k + 1]));
+                kt.acc[k] += ms;
+            }
+            kt.n += kt.on;
+        }
+        CHIP_HIP(c, hipStreamSynchronize(s));
+        for (int j = 0; j < B && max_n2 > 0; j++) {
+            if (b[j].n == 0) continue;
+            const int32_t *h = st->h_bcounts.host() + j * kNSets;
+            chip_match_summary &sm = st->cand_sm[j];
+            sm.n_matches_all = n1;
+            sm.n_matches_gms = h[kSetUv]; sm.n_3d2d_ab = h[kSetAb]; sm.n_3d2d_ba = h[kSetBa]; sm.n_3d3d = h[kSet33]; sm.n_out_of_image = h[kSetOut];
+        }
+    }
+    st->from_batch = true;
+    st->n_cand = B;
+    st->batch_n1 = n1;
+    st->select(0);
+    st->have_sets = true;
+    for (int j = 0; j < B; j++) summary[j] = st->cand_sm[j];
+    return CHIP_OK;
+}
+
+extern "C" int chip_match_select(chip_ctx *c, int32_t j)
+{
+    if (!c) return CHIP_ERR_INVALID_ARG;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    MatchState *st = c->match_state;
+    if (!st || !st->have_sets) return CHIP_ERR_BUSY;
+    if (j < 0 || j >= st->n_cand) return CHIP_ERR_RANGE;
+    st->select(j);
+    return CHIP_OK;
+}
+
+extern "C" int chip_match_batch_read_matches(chip_ctx *c, int32_t j, int32_t *train_idx, int32_t *distance)
+{
+    if (!c || !train_idx || !distance) return CHIP_ERR_INVALID_ARG;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    MatchState *st = c->match_state;
+    if (!st || !st->have_sets || !st->from_batch) return CHIP_ERR_BUSY;   // the keys are chip_match_batch's: not after a chip_match_pair
+    if (j < 0 || j >= st->n_cand) return CHIP_ERR_RANGE;
+    const size_t n1 = (size_t)st->batch_n1;
+    if (n1 == 0) return CHIP_OK;
+    CHIP_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = match_stream(c);
+    st->h_keys.resize(n1);
+    CHIP_HIP(c, hipMemcpyAsync(st->h_keys.data(), st->b_keys + (size_t)j * n1, n1 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    CHIP_HIP(c, hipStreamSynchronize(s));
+    for (size_t i = 0; i < n1; i++) {   // all ones -> -1 / -1
+        train_idx[i] = (int32_t)(uint32_t)st->h_keys[i];
+        distance[i] = (int32_t)(uint32_t)(st->h_keys[i] >> 32);
+    }
+    return CHIP_OK;
+}
+
+extern "C" int chip_pnp_ransac_matched_batch(chip_ctx *c, int32_t P, const int32_t *cand, const int32_t *which, const chip_ransac_params *p,
+                                             const uint64_t *seeds, double *T_colmajor, float *confidence, uint8_t *const *inlier_mask,
+                                             chip_ransac_summary *summary, int32_t *status)
+{
+    if (!c || P < 0 || !p || (P > 0 && (!cand || !which || !T_colmajor || !confidence || !status))) return CHIP_ERR_INVALID_ARG;
+    for (int i = 0; i < P; i++)
+        if (which[i] != CHIP_SET_AB && which[i] != CHIP_SET_BA) return CHIP_ERR_INVALID_ARG;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    MatchState *st = c->match_state;
+    if (!st || !st->have_sets) return CHIP_ERR_BUSY;
+    for (int i = 0; i < P; i++)
+        if (cand[i] < 0 || cand[i] >= st->n_cand) return CHIP_ERR_RANGE;
+    // the runnable problems, gathered: their slab pointers, seeds and masks; the others are answered here
+    std::vector<const double *> X, uv;
+    std::vector<int32_t> N, at;
+    std::vector<uint64_t> sd;
+    std::vector<uint8_t *> masks;
+    const MatchState::Sets keep = st->cur;
+    const chip_match_summary keep_sm = st->last;
+    for (int i = 0; i < P; i++) {
+        st->select(cand[i]);
+        const bool ab = which[i] == CHIP_SET_AB;
+        const int32_t n = ab ? st->last.n_3d2d_ab : st->last.n_3d2d_ba;
+        status[i] = ransac_check_params(p, n);
+        if (status[i] != CHIP_OK) {
+            for (int k = 0; k < 16; k++) T_colmajor[16 * (size_t)i + k] = NAN;
+            confidence[i] = -1.f;
+            if (summary) { std::memset(&summary[i], 0, sizeof summary[i]); summary[i].best_hypothesis = -1; }
+            continue;
+        }
+        X.push_back(ab ? st->cur.X_ab : st->cur.X_ba);
+        uv.push_back(ab ? st->cur.uvn_ab : st->cur.uvn_ba);
+        N.push_back(n); at.push_back(i);
+        sd.push_back(seeds ? seeds[i] : p->seed);
+        masks.push_back(inlier_mask ? inlier_mask[i] : nullptr);
+    }
+    st->cur = keep; st->last = keep_sm;          // the selection is chip_match_select's alone
+    const int R = (int)at.size();
+    if (R == 0) return CHIP_OK;
+    std::vector<double> T(16 * (size_t)R);
+    std::vector<float> conf((size_t)R);
+    std::vector<chip_ransac_summary> summ((size_t)R);
+    const int rc = pnp_ransac_device_batch(c, R, X.data(), uv.data(), N.data(), p, sd.data(), T.data(), conf.data(), masks.data(), summ.data());
+    if (rc != CHIP_OK) return rc;
+    for (int r = 0; r < R; r++) {
+        std::memcpy(T_colmajor + 16 * (size_t)at[r], T.data() + 16 * (size_t)r, 16 * sizeof(double));
+        confidence[at[r]] = conf[r];
+        if (summary) summary[at[r]] = summ[r];
+    }
+    return CHIP_OK;
 }

@@ -2498,6 +2498,24 @@ int pnp_ransac_device(Ctx *c, const double *X_dev, const double *uv_dev, int32_t
     return pnp_run(c, st, 1, &X_dev, &uv_dev, &N, p, nullptr, T_colmajor, confidence, masks, summary, true);
 }
 
+// P validated problems on device-resident sets (match.hip's slabs), in launches of up to kPnpMaxBatch; problem i is bit-identical to
+// pnp_ransac_device with seed seeds[i]
+int pnp_ransac_device_batch(Ctx *c, int32_t P, const double *const *X_dev, const double *const *uv_dev, const int32_t *N, const chip_ransac_params *p,
+                            const uint64_t *seeds, double *T_colmajor, float *confidence, uint8_t *const *inlier_mask, chip_ransac_summary *summary)
+{
+    std::lock_guard<std::mutex> lk(c->pnp_mu);
+    CHIP_HIP(c, hipSetDevice(c->device));
+    PnpState *st = c->pnp_state;
+    if (!st) return CHIP_ERR_INVALID_ARG;
+    for (int i0 = 0; i0 < P; i0 += kPnpMaxBatch) {
+        const int n = P - i0 < kPnpMaxBatch ? P - i0 : kPnpMaxBatch;
+        const int rc = pnp_run(c, st, n, X_dev + i0, uv_dev + i0, N + i0, p, seeds + i0, T_colmajor + 16 * (size_t)i0, confidence + i0, inlier_mask + i0,
+                               summary + i0, true);
+        if (rc != CHIP_OK) return rc;
+    }
+    return CHIP_OK;
+}
+
 }  // namespace chip
 
 using namespace chip;

@@ -567,6 +567,58 @@ bool verify_candidate(chip_ctx *ctx, const chip_match_frame &frame_a, const chip
     return true;
 }
 
+bool verify_candidates(chip_ctx *ctx, const chip_match_frame &frame_a, const chip_match_frame *frames_b, int B, const double Kinv[9],
+                       ProcessedLoopCandidate *pc, bool *accepted, const uint64_t *seeds, chip_match_summary *summaries)
+{
+    if (!frames_b || !pc || !accepted || B < 1 || B > CHIP_MATCH_MAX_BATCH) return false;
+    for (int j = 0; j < B; j++) accepted[j] = false;
+    chip_match_summary sm[CHIP_MATCH_MAX_BATCH] = {};
+    const int rc = chip_match_batch(ctx, &frame_a, frames_b, B, Kinv, sm);
+    if (summaries) for (int j = 0; j < B; j++) summaries[j] = sm[j];
+    if (rc != CHIP_OK) return false;
+    chip_ransac_params pp, pi;
+    chip_ransac_params_default(&pp);
+    chip_icp_params_default(&pi);
+    const uint64_t pp_seed = pp.seed, pi_seed = pi.seed;
+    // the survivors of Cerebro.cpp:1487-1493, two PnP problems each (:1518 a->b, :1572 b->a) in one call
+    int32_t cand[2 * CHIP_MATCH_MAX_BATCH], which[2 * CHIP_MATCH_MAX_BATCH], status[2 * CHIP_MATCH_MAX_BATCH], slot[CHIP_MATCH_MAX_BATCH];
+    uint64_t sd[2 * CHIP_MATCH_MAX_BATCH];
+    double T[2 * CHIP_MATCH_MAX_BATCH * 16];
+    float conf[2 * CHIP_MATCH_MAX_BATCH];
+    int P = 0;
+    for (int j = 0; j < B; j++) {
+        slot[j] = -1;
+        if (sm[j].n_matches_gms < 150) continue;
+        pc[j].pf_matches = sm[j].n_matches_gms;                     // :1505
+        const uint64_t s0 = seeds && seeds[j] ? seeds[j] : pp_seed; // the seeds of verify_candidate
+        slot[j] = P;
+        cand[P] = j; which[P] = CHIP_SET_AB; sd[P] = s0; P++;
+        cand[P] = j; which[P] = CHIP_SET_BA; sd[P] = s0 + 1; P++;
+    }
+    if (P == 0) return true;
+    if (chip_pnp_ransac_matched_batch(ctx, P, cand, which, &pp, sd, T, conf, nullptr, nullptr, status) != CHIP_OK) return false;
+    for (int j = 0; j < B; j++) {
+        if (slot[j] < 0) continue;
+        const int k = slot[j];
+        std::array<double, 16> op1{}, op2_a_T_b{}, op2{}, icp{};
+        float g1 = -1.f, g2 = -1.f, g3 = -1.f;
+        if (status[k] == CHIP_OK) { for (int i = 0; i < 16; i++) op1[i] = T[16 * k + i]; g1 = conf[k]; }
+        if (status[k + 1] == CHIP_OK) { for (int i = 0; i < 16; i++) op2_a_T_b[i] = T[16 * (k + 1) + i]; g2 = conf[k + 1]; }
+        matrix4_inverse_rigid(op2_a_T_b.data(), op2.data());        // :1582
+        pi.seed = seeds && seeds[j] ? seeds[j] ^ 0x9E3779B97F4A7C15ull : pi_seed;
+        if (chip_match_select(ctx, j) != CHIP_OK) return false;
+        if (chip_icp_ransac_matched(ctx, &pi, icp.data(), &g3, nullptr, nullptr) != CHIP_OK) g3 = -1.f;   // :1629
+        bool nan = false;
+        for (int i = 0; i < 16; i++)                                // :1678
+            if (op1[i] != op1[i] || op2[i] != op2[i] || icp[i] != icp[i]) nan = true;
+        if (nan || g1 < 0 || g2 < 0 || g3 < 0) continue;
+        pc[j].opX_b_T_a = {op1, op2, icp};                          // :1706-1719
+        pc[j].opX_goodness = {g1, g2, g3};
+        accepted[j] = true;
+    }
+    return true;
+}
+
 void matrix4_to_pose(const double T[16], double position[3], double q[4])
 {
     position[0] = T[12]; position[1] = T[13]; position[2] = T[14];

@@ -210,6 +210,13 @@ struct StaticPointFeatureMatching {
 // compute_three_way_pose) -> NaN gate (:1678).  One upload; nothing but counts and poses returns to the host.
 bool verify_candidate(chip_ctx *ctx, const chip_match_frame &frame_a, const chip_match_frame &frame_b, const double Kinv[9],
                       ProcessedLoopCandidate &proc_candi, uint64_t seed = 0, chip_match_summary *summary = nullptr);
+// B candidates of one keyframe (B <= CHIP_MATCH_MAX_BATCH): ONE chip_match_batch (frame_a uploaded once, all pairs in three launches),
+// the "< 150 matches" reject per candidate, ONE chip_pnp_ransac_matched_batch over the survivors' a->b and b->a sets (seeds seeds[j],
+// seeds[j] + 1; nullptr: the default seed), then per survivor chip_match_select + chip_icp_ransac_matched and the NaN / goodness gate.
+// pc[j] / accepted[j] are what verify_candidate(ctx, frame_a, frames_b[j], Kinv, pc[j], seeds[j]) gives, field for field.  Returns false
+// only if a library call failed (then every accepted[j] is false).
+bool verify_candidates(chip_ctx *ctx, const chip_match_frame &frame_a, const chip_match_frame *frames_b, int B, const double Kinv[9],
+                       ProcessedLoopCandidate *pc, bool *accepted, const uint64_t *seeds = nullptr, chip_match_summary *summaries = nullptr);
 
 // PoseManipUtils::R2ypr (src/utils/PoseManipUtils.cpp:148-163), degrees, from a column-major 4x4
 void matrix4_to_rawyprt(const double T_colmajor[16], double ypr_deg[3], double t[3]);

@@ -565,6 +565,40 @@ int chip_pnp_ransac_matched(chip_ctx *ctx, int32_t which, const chip_ransac_para
 int chip_icp_ransac_matched(chip_ctx *ctx, const chip_ransac_params *p, double T_colmajor[16], float *confidence,
                             uint8_t *inlier_mask, chip_ransac_summary *summary /* may be NULL */);
 
+/* ---- one query frame against B candidate frames (top-K lists, the clique policy, three queries per tick, a replay's backlog): the
+ * query frame is uploaded once and all B pairs share three launches -- hamming_match_split (grid: query blocks of 256 x train tiles of
+ * 1024 x B; the partial minima of a (query, candidate) meet as the unsigned 64-bit key distance << 32 | train index, whose minimum is
+ * the smallest distance and then the LOWEST train index, the tie rule above, whichever tile arrives first), gms_batch (one workgroup
+ * per (grid type, candidate) on a table and a byte plane of its own) and pose_sets_batch (one workgroup per candidate; inlier = the
+ * OR of its four planes).  The sets of all B candidates stay on the device in slabs of a->n rows.  ONE of them is "selected": the
+ * one chip_match_read_sets, chip_pnp_ransac_matched and chip_icp_ransac_matched work on.
+ * Status: B < 1 or a NULL pointer CHIP_ERR_INVALID_ARG; B > CHIP_MATCH_MAX_BATCH, a group ctx or a frame beyond chip_match_pair's
+ * limits CHIP_ERR_UNSUPPORTED; j or cand[i] outside the last batch CHIP_ERR_RANGE; before any match CHIP_ERR_BUSY.  An empty
+ * query frame or an empty candidate gives that candidate a zero summary, as chip_match_pair.  A failed call leaves nothing
+ * selected.  chip_match_pair keeps its own kernels and results.                                                                   */
+#define CHIP_MATCH_MAX_BATCH 16            /* = the library's top-K bound */
+int chip_build_has_match_batch(void);      /* 1 */
+/* frame a against b[0..B): summary[j] and the five sets of candidate j are those of chip_match_pair(a, &b[j]) byte for byte.
+ * One upload of a, one of each b[j], nothing returns to the host but the B x 6 counts.  Afterwards candidate 0 is selected. */
+int chip_match_batch(chip_ctx *ctx, const chip_match_frame *a, const chip_match_frame *b, int32_t B,
+                     const double Kinv_rowmajor[9], chip_match_summary *summary /* B */);
+/* make candidate j of the last chip_match_batch the one that chip_match_read_sets, chip_pnp_ransac_matched and
+ * chip_icp_ransac_matched work on.  After chip_match_pair there is one candidate, index 0. */
+int chip_match_select(chip_ctx *ctx, int32_t j);
+/* matches_all of candidate j (BFMatcher output before GMS): n1 = a->n train indices and distances, -1 / -1 where b[j].n == 0.
+ * CHIP_ERR_BUSY unless the last match call of the ctx was a chip_match_batch. */
+int chip_match_batch_read_matches(chip_ctx *ctx, int32_t j, int32_t *train_idx, int32_t *distance);
+/* P PnP estimations on device-resident sets in launches of up to 8 problems: problem i is set which[i] (CHIP_SET_AB / _BA)
+ * of candidate cand[i], seed seeds[i] (NULL: p->seed).  status[i] is what chip_pnp_ransac_matched would return after
+ * chip_match_select(cand[i]).  A set with fewer than 20 points gets CHIP_ERR_TOO_FEW_POINTS and is left out of the launch.
+ * Its T is NaN, its confidence -1, its summary zero with best_hypothesis -1, and its mask is untouched.  The other problems
+ * are bit-identical to the single call with that seed.  The call itself fails only on bad arguments or a HIP / allocation
+ * error.  The selection is not changed.  ICP stays one candidate at a time: chip_match_select, then chip_icp_ransac_matched. */
+int chip_pnp_ransac_matched_batch(chip_ctx *ctx, int32_t P, const int32_t *cand, const int32_t *which,
+                                  const chip_ransac_params *p, const uint64_t *seeds, double *T_colmajor /* P x 16 */,
+                                  float *confidence /* P */, uint8_t *const *inlier_mask /* may be NULL */,
+                                  chip_ransac_summary *summary /* P or NULL */, int32_t *status /* P */);
+
 /* ------------------------------------------------------------------------------------------ introspection */
 typedef struct {
     int32_t abi_version;

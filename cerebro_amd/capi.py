@@ -61,7 +61,7 @@ CHIP_SAMPLER_FRESH, CHIP_SAMPLER_THEIA_PERSISTENT = 0, 1
 CHIP_RANSAC_LEG_PNP, CHIP_RANSAC_LEG_ICP = 0, 1
 CHIP_SCAN_FAMILY_NONE, CHIP_SCAN_FAMILY_ONE_ROW, CHIP_SCAN_FAMILY_WIDE, CHIP_SCAN_FAMILY_ROWS, CHIP_SCAN_FAMILY_MULTI = 0, 1, 2, 3, 4
 CHIP_SCAN_CALL_QUERY, CHIP_SCAN_CALL_TICK, CHIP_SCAN_CALL_TICK_SYNC = 0, 1, 2
-SCAN_FAMILY_NAMES = {0: "none", 1: "one_row", 2: "wide", 3: "rows", 4: "multi"}
+SCAN_FAMILY_NAMES = {0: "none", 1: "one_row", 2: "wide", 3: "rows", 4: "multi", 5: "prefilter"}
 
 CHIP_TICK_SKIPPED, CHIP_TICK_TOO_SHORT, CHIP_TICK_SCANNED = 0, 1, 2
 CHIP_MATCH_MAX_KEYPOINTS = 16384
@@ -145,7 +145,8 @@ class Info(C.Structure):
                 ("shard_count", C.c_int32), ("n_cus", C.c_int32), ("rows_global", C.c_int64),
                 ("rows_local", C.c_int64), ("capacity_local", C.c_int64), ("lossy_rows", C.c_int64),
                 ("arch", C.c_char * 32), ("storage_bytes", C.c_int32), ("n_devices", C.c_int32), ("exchange", C.c_int32),
-                ("comm_ranks", C.c_int32), ("comm_init_abandoned", C.c_int32), ("scan_forms", C.c_int32), ("test_hooks", C.c_int32)]
+                ("comm_ranks", C.c_int32), ("comm_init_abandoned", C.c_int32), ("scan_forms", C.c_int32), ("test_hooks", C.c_int32),
+                ("row_norm_max", C.c_double)]
 
 
 # every symbol include/cerebro_hip.h declares: name -> (restype, argtypes)
@@ -210,6 +211,8 @@ _SIGS = {
     "chip_debug_last_scan": (C.c_int, [_P, C.POINTER(ScanLaunch)]),
     "chip_debug_scan_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(ScanLaunch)]),
     "chip_debug_multi_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(ScanLaunch)]),
+    "chip_debug_prefilter_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(ScanLaunch)]),
+    "chip_debug_prefilter_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "chip_orb_match": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P]),
     "chip_gms_filter": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P,
                                   C.POINTER(C.c_int32)]),
@@ -333,6 +336,18 @@ def multi_plan(D: int, elem: int, n_ticks: int, K: int = CHIP_DEFAULT_TOPK, n_cu
         return rc, out.as_dict()
     if rc != CHIP_OK:
         raise ChipError(rc, "chip_debug_multi_plan")
+    return out.as_dict()
+
+
+def prefilter_plan(D: int, elem: int = 4, K: int = CHIP_DEFAULT_TOPK, n_cus: int = 256, check: bool = True):
+    """chip_debug_prefilter_plan: the fp32 prefilter pass that serves four pipelined ticks together (float rows), as ScanLaunch.as_dict()
+    (NG = queries read in place, the other 12 - NG staged in LDS) -- no device needed.  check=False: (status, dict) instead of raising."""
+    out = ScanLaunch()
+    rc = load_library().chip_debug_prefilter_plan(D, elem, K, n_cus, C.byref(out))
+    if not check:
+        return rc, out.as_dict()
+    if rc != CHIP_OK:
+        raise ChipError(rc, "chip_debug_prefilter_plan")
     return out.as_dict()
 
 
@@ -540,6 +555,13 @@ class Chip:
         passes, ticks = C.c_int64(), C.c_int64()
         self._chk(self.lib.chip_debug_coalesce_stats(self.h, C.byref(passes), C.byref(ticks)), "chip_debug_coalesce_stats")
         return passes.value, ticks.value
+
+    def prefilter_stats(self) -> tuple[int, int, int]:
+        """(prefilter passes, ticks they served, ticks among them run again alone because their certificate did not hold) --
+        chip_debug_prefilter_stats"""
+        passes, ticks, unc = C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self.lib.chip_debug_prefilter_stats(self.h, C.byref(passes), C.byref(ticks), C.byref(unc)), "chip_debug_prefilter_stats")
+        return passes.value, ticks.value, unc.value
 
     def coalesce_force(self, on: bool):
         """tests: while on, a pipelined tick that may share a pass parks even when no scan of the ctx is running"""

@@ -229,7 +229,11 @@ static int create_impl(chip_ctx *c, int64_t capacity_hint, int elem)
     rc = c->stage_dev.alloc(c, c->stage_bytes);
     if (rc == CHIP_OK) rc = c->flags_dev.alloc(c, 1);
     if (rc == CHIP_OK) rc = c->flags_host.alloc(c, 1);
+    if (rc == CHIP_OK) rc = c->norm2_dev.alloc(c, 1);
+    if (rc == CHIP_OK) rc = c->norm2_host.alloc(c, 1);
     if (rc != CHIP_OK) return rc;
+    CHIP_HIP(c, hipMemset(c->norm2_dev, 0, sizeof(unsigned long long)));
+    *c->norm2_host.host() = 0;
 
     scan_read_knobs(c);
     CHIP_HIP(c, hipStreamCreateWithFlags(&c->s_scan, hipStreamNonBlocking));
@@ -244,9 +248,11 @@ static int create_impl(chip_ctx *c, int64_t capacity_hint, int elem)
             if (ns >= 3 + i) CHIP_HIP(c, hipStreamCreateWithFlags(&c->s_scan_x[i], hipStreamNonBlocking));
     }
     for (int i = 0; i < Ctx::kRing; i++) {
-        // [max_grid][CHIP_MAX_NQ][CHIP_MAX_TOPK] of one launch, or [kMultiMaxTicks][max_grid][3][CHIP_MAX_TOPK] of a pass that serves several ticks
-        constexpr size_t kListsPerGroup = 3 * kMultiMaxTicks > CHIP_MAX_NQ ? 3 * kMultiMaxTicks : CHIP_MAX_NQ;
-        rc = c->partial_dev[i].alloc(c, (size_t)c->max_grid * kListsPerGroup * CHIP_MAX_TOPK);
+        // [max_grid][CHIP_MAX_NQ][CHIP_MAX_TOPK] of one launch, or [ticks][max_grid][3][CHIP_MAX_TOPK] of a pass that serves several ticks (up to
+        // kPrefilterTicks), and behind them the [kPrefilterTicks][3][CHIP_MAX_TOPK] exact lists tick_rescore leaves for the merge (coalesce_submit)
+        constexpr size_t kListsPerGroup = 3 * kPrefilterTicks > CHIP_MAX_NQ ? 3 * kPrefilterTicks : CHIP_MAX_NQ;
+        static_assert(kPrefilterTicks >= kMultiMaxTicks, "the list buffers are sized for the deepest pass");
+        rc = c->partial_dev[i].alloc(c, ((size_t)c->max_grid + 1) * kListsPerGroup * CHIP_MAX_TOPK);
         if (rc != CHIP_OK) return rc;
         CHIP_HIP(c, hipEventCreateWithFlags(&c->ev_scan[i], hipEventDisableTiming));
         CHIP_HIP(c, hipEventCreateWithFlags(&c->ev_merged[i], hipEventDisableTiming));
@@ -255,14 +261,18 @@ static int create_impl(chip_ctx *c, int64_t capacity_hint, int elem)
     if (rc != CHIP_OK) return rc;
     CHIP_HIP(c, hipMemset(c->tickets_dev, 0, Ctx::kRing * sizeof(int32_t)));
     // pipelined ticks that arrive while a long scan is running share one DB pass: at most this many per pass (0 = never; coalesce_* below)
-    c->coalesce_max = env_int("CHIP_TICK_COALESCE", kMultiMaxTicks);
+    // (4: float rows whose shape has the prefilter pass; every other ctx stops at what scan_multi_plan gives it)
+    c->coalesce_max = env_int("CHIP_TICK_COALESCE", kPrefilterTicks);
     if (c->coalesce_max < 2) c->coalesce_max = 0;
-    if (c->coalesce_max > kMultiMaxTicks) c->coalesce_max = kMultiMaxTicks;
+    if (c->coalesce_max > kPrefilterTicks) c->coalesce_max = kPrefilterTicks;
     c->tick_poll = env_int("CHIP_TICK_POLL", 1) != 0;
     resident_read_knobs(c);
     rc = c->seq_all.alloc(c, CHIP_MAX_INFLIGHT);
     if (rc != CHIP_OK) return rc;
     std::memset(c->seq_all.host(), 0, sizeof(unsigned long long) * CHIP_MAX_INFLIGHT);
+    rc = c->cert_all.alloc(c, CHIP_MAX_INFLIGHT * 4);
+    if (rc != CHIP_OK) return rc;
+    std::memset(c->cert_all.host(), 0, sizeof(uint32_t) * CHIP_MAX_INFLIGHT * 4);
     rc = c->topk.alloc(c, (size_t)CHIP_MAX_NQ * CHIP_MAX_TOPK);
     if (rc != CHIP_OK) return rc;
     for (Slot &s : c->slots) {
@@ -272,6 +282,8 @@ static int create_impl(chip_ctx *c, int64_t capacity_hint, int elem)
         if (rc != CHIP_OK) return rc;
         s.seq_host = c->seq_all.host() + (&s - c->slots);
         s.seq_dev = c->seq_all.dev() + (&s - c->slots);
+        s.cert_host = c->cert_all.host() + 4 * (&s - c->slots);
+        s.cert_dev = c->cert_all.dev() + 4 * (&s - c->slots);
     }
     if (env_int("CHIP_SCAN_STAMPS", 0)) {
         rc = c->stamps_dev.alloc(c, (size_t)c->max_grid * 16 * 4 + 64);   // (+ 8 launch-wide stamps behind the waves')
@@ -540,6 +552,7 @@ int tick_begin(Slot &s, int64_t n_rows, int64_t *last_l, int64_t l, const chip_d
     const int rc = tick_prepare(n_rows, *last_l, l, p, status, k);
     if (rc != CHIP_OK) return rc;
     s.prev_last_l = *last_l;
+    s.prefilter = false;
     s.tick_l = l;
     s.last_l_ptr = last_l;
     if (*status != CHIP_TICK_SCANNED) {
@@ -592,40 +605,73 @@ static int coalesce_ticks_max(const Ctx *c, int64_t k, bool sync_tick)
 {
     if (c->coalesce_max < 2 || sync_tick || c->nranks != 1 || c->xchg || c->parent || c->group || !c->own_query_stream) return 0;
     if ((double)k * c->D * c->elem <= c->scan_overlap_bytes) return 0;
-    const int fit = scan_multi_max_ticks(c);
+    int fit = scan_multi_max_ticks(c);
+    if (c->coalesce_max >= kPrefilterTicks && scan_prefilter_usable(c)) fit = kPrefilterTicks;   // four leave as one prefilter pass
     const int t = fit < c->coalesce_max ? fit : c->coalesce_max;
     return t >= 2 ? t : 0;
 }
 
 // T >= 2 parked ticks as one pass: one launch of db_scan_topk_multi / db_scan_shared_f64 on the scan stream, then K2 once per tick on the ctx stream,
 // each on its own block of lists and followed by its slot's completion event.
+// T == kPrefilterTicks: the pass is db_scan_prefilter, and on the ctx stream ONE launch of tick_rescore (certificate + exact scores of the
+// proven candidates -> one list per tick and query) goes in front of the ticks' K2 launches; the slot remembers the tick, and a collect
+// that finds a certificate word that does not say "holds" runs the tick again alone (tick_collect_slot).
 static int coalesce_submit(Ctx *c, int T)
 {
     const int b = (int)(c->n_enqueued++ % Ctx::kRing);
     const int K = CHIP_DEFAULT_TOPK;
+    const bool prefilter = T == kPrefilterTicks;
+    static_assert(kPrefilterTicks > kMultiMaxTicks, "a pass of kPrefilterTicks ticks is the prefilter's");
     MultiScanArgs a{};
+    PrefilterArgs pa{};
     scan_args_db(c, &a);
-    a.K = K;
-    a.partial = c->partial_dev[b];
+    scan_args_db(c, &pa);
+    a.K = pa.K = K;
+    a.partial = pa.partial = c->partial_dev[b];
     for (int t = 0; t < T; t++) {
-        a.k[t] = c->parked[t].k;
-        if (a.k[t] > a.n_rows) a.n_rows = a.k[t];
-        for (int i = 0; i < 3; i++) a.q[3 * t + i] = c->parked[t].q[i];
+        const int64_t k = c->parked[t].k;
+        if (k > a.n_rows) a.n_rows = pa.n_rows = k;
+        if (prefilter) pa.k[t] = k; else a.k[t] = k;
+        for (int i = 0; i < 3; i++) (prefilter ? pa.q : a.q)[3 * t + i] = c->parked[t].q[i];
     }
     const int grid = scan_multi_grid(c);
+    double E = 0.0;
+    if (prefilter) {
+        std::lock_guard<std::mutex> lk(c->mu);
+        E = prefilter_error_bound(c->D, c->row_norm_max);
+    }
     if (hipEventQuery(c->ev_merged[b]) != hipSuccess) CHIP_HIP(c, hipStreamWaitEvent(c->s_scan, c->ev_merged[b], 0));
     hipEvent_t e1 = nullptr;   // one event pair per pass; a pass reads the prefix once
     int rc = c->prof_on ? prof_begin(c, c->s_scan, (double)a.n_rows * c->D * c->elem, &e1) : CHIP_OK;
-    if (rc == CHIP_OK) rc = launch_scan_multi(c, c->s_scan, a, T, grid);
+    if (rc == CHIP_OK) rc = prefilter ? launch_scan_prefilter(c, c->s_scan, pa, grid) : launch_scan_multi(c, c->s_scan, a, T, grid);
     if (rc != CHIP_OK) return rc;
     if (e1) CHIP_HIP(c, hipEventRecord(e1, c->s_scan));
     CHIP_HIP(c, hipEventRecord(c->ev_scan[b], c->s_scan));
     c->pass_ev = c->ev_scan[b];
     c->pass_no++;
     CHIP_HIP(c, hipStreamWaitEvent(c->s_query, c->ev_scan[b], 0));
+    chip_topk_entry *exact = c->partial_dev[b] + (size_t)kPrefilterTicks * grid * 3 * K;   // [tick][3][K], behind the pass's lists
+    if (prefilter) {
+        RescoreArgs ra{};
+        ra.seg_table = pa.seg_table; ra.seg_shift = pa.seg_shift; ra.seg_mask = pa.seg_mask; ra.D = pa.D; ra.K = K;
+        ra.in = c->partial_dev[b]; ra.n_lists = grid; ra.wpb = 8;   // (kMultiBlock / 64 waves per workgroup)
+        ra.E = E;
+        ra.out = exact;
+        for (int t = 0; t < T; t++) {
+            const Ctx::ParkedTick &pt = c->parked[t];
+            Slot &s = *pt.slot;
+            ra.k[t] = pt.k;
+            for (int i = 0; i < 3; i++) { ra.q[3 * t + i] = s.pf_q[i] = pt.q[i]; s.cert_host[i] = 0; }
+            ra.cert[t] = s.cert_dev;
+            s.prefilter = true; s.pf_k = pt.k; s.pf_p = pt.p;
+        }
+        rc = launch_rescore(c, c->s_query, ra);
+        if (rc != CHIP_OK) return rc;
+    }
     for (int t = 0; t < T; t++) {
         const Ctx::ParkedTick &pt = c->parked[t];
-        rc = launch_merge(c, c->s_query, merge_args(c->partial_dev[b] + (size_t)t * grid * 3 * K, grid, K, nullptr, pt.slot->rec.dev(), pt.l, &pt.p), 3);
+        if (prefilter) rc = launch_merge(c, c->s_query, merge_args(exact + (size_t)t * 3 * K, 1, K, nullptr, pt.slot->rec.dev(), pt.l, &pt.p), 3);
+        else rc = launch_merge(c, c->s_query, merge_args(c->partial_dev[b] + (size_t)t * grid * 3 * K, grid, K, nullptr, pt.slot->rec.dev(), pt.l, &pt.p), 3);
         if (rc != CHIP_OK) return rc;
         CHIP_HIP(c, hipEventRecord(pt.slot->done, c->s_query));
         pt.slot->wait_ev = pt.slot->done;
@@ -635,6 +681,7 @@ static int coalesce_submit(Ctx *c, int T)
     CHIP_HIP(c, hipEventRecord(c->ev_merged[b], c->s_query));
     c->coalesce_passes++;
     c->coalesce_ticks += T;
+    if (prefilter) { c->prefilter_passes++; c->prefilter_ticks += T; }
     return CHIP_OK;
 }
 
@@ -644,7 +691,14 @@ int coalesce_flush(Ctx *c)
     if (T == 0) return CHIP_OK;
     c->n_parked = 0;
     const Ctx::ParkedTick &p0 = c->parked[0];
-    const int rc = T == 1 ? tick_submit(c, p0.k, p0.l, &p0.p, p0.q, false, *p0.slot) : coalesce_submit(c, T);
+    int rc;
+    if (T == kPrefilterTicks && !scan_prefilter_usable(c)) {   // a row appended since they parked took the norm bound out of range: three and one
+        const Ctx::ParkedTick &pl = c->parked[T - 1];
+        rc = coalesce_submit(c, T - 1);
+        if (rc == CHIP_OK) rc = tick_submit(c, pl.k, pl.l, &pl.p, pl.q, false, *pl.slot);
+    } else {
+        rc = T == 1 ? tick_submit(c, p0.k, p0.l, &p0.p, p0.q, false, *p0.slot) : coalesce_submit(c, T);
+    }
     for (int t = 0; t < T && rc != CHIP_OK; t++) {   // the enqueue has long returned: the tick's collect reports it
         c->parked[t].slot->state = SlotState::Failed;
         c->parked[t].slot->err = rc;
@@ -736,6 +790,19 @@ int tick_collect_slot(Ctx *c, Slot &s, chip_tick_result *out)
         CHIP_HIP(c, hipEventSynchronize(s.wait_ev));   // (a failure leaves the slot as it is)
         break;
     }
+    if (s.prefilter) {
+        // The tick left with a prefilter pass.  Its record stands if tick_rescore proved, for all three queries, that the rows it scored
+        // exactly hold the exact top-K; if not (scores closer together than the fp32 error bound, or more candidates than it scores), the
+        // tick runs again alone through the exact scan, and that record is the caller's.
+        s.prefilter = false;
+        if (s.cert_host[0] != 1u || s.cert_host[1] != 1u || s.cert_host[2] != 1u) {
+            c->prefilter_uncertified++;
+            (void)coalesce_flush(c);   // submission order stays call order
+            const int rc = tick_submit(c, s.pf_k, s.tick_l, &s.pf_p, s.pf_q, false, s);
+            if (rc != CHIP_OK) { s.state = SlotState::Free; return rc; }
+            CHIP_HIP(c, hipEventSynchronize(s.wait_ev));
+        }
+    }
     *out = *s.rec.host();
     s.state = SlotState::Free;
     if (out->status == CHIP_TICK_FAILED) {   // a shard could not take part: the tick had no effect (:1098 was not reached)
@@ -812,6 +879,7 @@ int append_store_db(Ctx *c, const void *desc, int src_elem, int64_t first, int64
 {
     *c->flags_host.host() = 0;
     CHIP_HIP(c, hipMemsetAsync(c->flags_dev, 0, sizeof(uint32_t), c->s_append));
+    CHIP_HIP(c, hipMemsetAsync(c->norm2_dev, 0, sizeof(unsigned long long), c->s_append));   // the rows of this call alone: append_publish folds them in
     int rc;
     if (owner_only && c->nranks > 1) {
         const int64_t G = c->nranks;
@@ -823,6 +891,7 @@ int append_store_db(Ctx *c, const void *desc, int src_elem, int64_t first, int64
     }
     if (rc != CHIP_OK) return rc;
     CHIP_HIP(c, hipMemcpyAsync(c->flags_host.host(), c->flags_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_append));
+    CHIP_HIP(c, hipMemcpyAsync(c->norm2_host.host(), c->norm2_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_append));
     CHIP_HIP(c, hipStreamSynchronize(c->s_append));
     *bad = *c->flags_host.host();
     return CHIP_OK;
@@ -844,6 +913,12 @@ void append_publish(Ctx *c, int64_t new_total, bool lossy, int64_t n)
     std::lock_guard<std::mutex> lk(c->mu);  // publish the new length only now (rows fully resident)
     c->rows_global = new_total;
     c->rows_local = local_count(c, c->rows_global);
+    if (c->elem == 4 && c->norm2_host.host()) {   // the largest sum of squares among the rows this call stored (append_store_db / synth_generate waited for it)
+        double ss;
+        std::memcpy(&ss, c->norm2_host.host(), sizeof ss);
+        const double nrm = std::sqrt(ss) * (1.0 + std::ldexp(1.0, -30));
+        if (!(nrm <= c->row_norm_max)) c->row_norm_max = nrm;   // (a NaN would stick, and switch the prefilter off)
+    }
     if (lossy) c->lossy_rows += n;   // upper bound: rows of this call
     c->store_auto = false;           // the storage type is final once the DB holds a row
 }
@@ -910,8 +985,11 @@ int synth_generate(Ctx *c, int64_t first, int64_t n, uint64_t seed, const int64_
         CHIP_HIP(c, hipMemcpyAsync(pk, plant_kind, n_plant * sizeof(int32_t), hipMemcpyHostToDevice, c->s_append));
     }
     int rc = ring_begin_append(c, first + n);   // same ordering against in-flight scans as ctx_append
+    hipError_t e0 = hipMemsetAsync(c->norm2_dev, 0, sizeof(unsigned long long), c->s_append);
     if (rc == CHIP_OK) rc = launch_synth(c, c->s_append, first, n, seed, pd, ps, pk, n_plant, unit);
+    if (e0 == hipSuccess) e0 = hipMemcpyAsync(c->norm2_host.host(), c->norm2_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_append);
     hipError_t e = hipStreamSynchronize(c->s_append);   // before the plant arrays go
+    if (e == hipSuccess) e = e0;
     if (rc != CHIP_OK) return rc;
     CHIP_HIP(c, e);
     return CHIP_OK;
@@ -1347,6 +1425,7 @@ int chip_get_info(const chip_ctx *c, chip_info *info)
     info->comm_init_abandoned = c->comm_init_abandoned;
     info->scan_forms = scan_forms_built();
     info->test_hooks = chip_build_test_hooks();
+    info->row_norm_max = r->row_norm_max;
     return CHIP_OK;
 }
 
@@ -1358,6 +1437,18 @@ int chip_debug_coalesce_stats(chip_ctx *c, int64_t *passes, int64_t *ticks)
     std::lock_guard<std::mutex> qlk(c->query_mu);
     *passes = c->coalesce_passes;
     *ticks = c->coalesce_ticks;
+    return CHIP_OK;
+}
+
+// Prefilter passes (four ticks, db_scan_prefilter + tick_rescore), their ticks, and the ticks among them that a collect has run again alone
+// because their certificate did not hold.
+int chip_debug_prefilter_stats(chip_ctx *c, int64_t *passes, int64_t *ticks, int64_t *uncertified)
+{
+    if (!c || !passes || !ticks || !uncertified || c->group) return CHIP_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> qlk(c->query_mu);
+    *passes = c->prefilter_passes;
+    *ticks = c->prefilter_ticks;
+    *uncertified = c->prefilter_uncertified;
     return CHIP_OK;
 }
 
@@ -1424,6 +1515,14 @@ int chip_debug_multi_plan(int32_t D, int32_t elem, int32_t n_ticks, int32_t K, i
     if (!out || D <= 0 || (elem != 4 && elem != 8) || n_ticks < 1 || K < 1 || K > CHIP_MAX_TOPK || n_cus < 1) return CHIP_ERR_INVALID_ARG;
     if (D % 4 != 0 || (size_t)D * 4 * CHIP_MAX_NQ > 160 * 1024 || (elem == 8 && (size_t)D * 8 * 2 > 160 * 1024)) return CHIP_ERR_UNSUPPORTED;   // (ctx_create)
     return scan_multi_plan(D, elem, n_ticks, K, n_cus < 512 ? n_cus : 512, out);
+}
+
+// The prefilter pass without a device: scan_prefilter_plan, the function launch_scan_prefilter sizes itself with.
+int chip_debug_prefilter_plan(int32_t D, int32_t elem, int32_t K, int32_t n_cus, chip_debug_scan_launch *out)
+{
+    if (!out || D <= 0 || (elem != 4 && elem != 8) || K < 1 || K > CHIP_MAX_TOPK || n_cus < 1) return CHIP_ERR_INVALID_ARG;
+    if (D % 4 != 0 || (size_t)D * 4 * CHIP_MAX_NQ > 160 * 1024 || (elem == 8 && (size_t)D * 8 * 2 > 160 * 1024)) return CHIP_ERR_UNSUPPORTED;   // (ctx_create)
+    return scan_prefilter_plan(D, elem, K, n_cus < 512 ? n_cus : 512, out);
 }
 
 // Tuning aid, not part of the ABI (no declaration in cerebro_hip.h): with CHIP_SCAN_STAMPS=1 the row-batched scan kernel leaves four

@@ -88,6 +88,36 @@ struct MultiScanArgs {
     chip_topk_entry *partial;                       // [tick][gridDim.x][3][K]: every tick's block of lists is what ONE launch of db_scan_topk leaves
 };
 
+// ---- four ticks in one DB pass: fp32 prefilter + certified exact rescoring (kernels.hip db_scan_prefilter / tick_rescore) ----
+constexpr int kPrefilterTicks = 4;                  // ticks of the prefilter pass: 12 fp32 queries, those the LDS does not hold are read in place
+constexpr int kRescoreCap = 32;                     // rows per query that tick_rescore scores exactly; more candidates than that: uncertified
+struct PrefilterArgs {
+    const void *const *seg_table;                   // as MultiScanArgs (float rows, plain single-GPU ctx)
+    int32_t seg_shift;
+    int64_t seg_mask;
+    int64_t n_rows;
+    int32_t D;
+    int32_t K;
+    int64_t k[kPrefilterTicks];
+    const void *q[3 * kPrefilterTicks];
+    chip_topk_entry *partial;                       // [tick][gridDim.x][3][K]: (fp32 score widened to double, row) sorted by score desc, index desc
+};
+struct RescoreArgs {                                // one launch per pass: workgroup 3 t + i serves query i of tick t
+    const void *const *seg_table;
+    int32_t seg_shift;
+    int64_t seg_mask;
+    int32_t D;
+    int32_t K;
+    const chip_topk_entry *in;                      // [tick][n_lists][3][K]: the prefilter's lists
+    int32_t n_lists;
+    int32_t wpb;                                    // waves per workgroup of the pass: with a tick's prefix, how many rows a workgroup owned
+    int64_t k[kPrefilterTicks];
+    const void *q[3 * kPrefilterTicks];
+    double E;                                       // bound on |fp32 score - exact score| of every pair of published rows, rounded up
+    chip_topk_entry *out;                           // [tick][3][K] exact lists: a tick's block is what topk_merge reads as ONE workgroup's lists
+    uint32_t *cert[kPrefilterTicks];                // per tick three words in pinned host memory: 1 the query's certificate holds, 2 it does not
+};
+
 struct MergeArgs {
     const chip_topk_entry *in;      // [n_lists][NQ][K]
     int32_t n_lists;
@@ -150,6 +180,12 @@ int scan_multi_max_ticks(const Ctx *c);   // ticks one shared pass can serve on 
 int scan_multi_plan(int D, int elem, int n_ticks, int K, int grid, chip_debug_scan_launch *f);
 int scan_multi_grid(const Ctx *c);
 int launch_scan_multi(Ctx *c, hipStream_t s, const MultiScanArgs &a, int n_ticks, int grid);
+// the prefilter pass of kPrefilterTicks ticks over float rows of D elements: staged / in-place (NG) queries, LDS, shape -- or CHIP_ERR_UNSUPPORTED
+int scan_prefilter_plan(int D, int elem, int K, int grid, chip_debug_scan_launch *f);
+bool scan_prefilter_usable(const Ctx *c);           // this ctx may serve four parked ticks with the prefilter pass (row norms included)
+double prefilter_error_bound(int D, double row_norm_max);   // E of DESIGN.md 3, rounded up
+int launch_scan_prefilter(Ctx *c, hipStream_t s, const PrefilterArgs &a, int grid);
+int launch_rescore(Ctx *c, hipStream_t s, const RescoreArgs &a);
 int scan_grid_for(const Ctx *c, int64_t n_rows, int nq, bool q64);
 bool scan_q64(const Ctx *c, int nq, bool long_scan);
 int scan_rows_form(const Ctx *c, int64_t n_rows, int nq, int grid, bool q64, bool sync_tick = false);
@@ -185,6 +221,12 @@ struct Slot {
     unsigned long long seq_want = 0;    // value the fused tick in flight will store there
     uint64_t pass_no = 0;               // Ctx::pass_no of the long scan that serves this tick
     int32_t err = 0;                    // SlotState::Failed: what collect returns
+    // a tick served by the prefilter pass: what collect needs to run it again alone if its certificate did not hold
+    bool prefilter = false;
+    uint32_t *cert_host = nullptr, *cert_dev = nullptr;   // this slot's three words in Ctx::cert_all (one per query): 1 certified, 2 not
+    int64_t pf_k = 0;
+    chip_dot_params pf_p{};
+    const void *pf_q[3] = {};
     int64_t *last_l_ptr = nullptr;      // ... and where to restore it if the tick comes back CHIP_TICK_FAILED (only while no newer
                                         //     tick has been enqueued: *last_l_ptr == tick_l)
 };
@@ -267,6 +309,9 @@ struct Ctx {
     size_t stage_bytes = 0;
     DevBuf<uint32_t> flags_dev;          // bit0: not-f32-representable, bit1: non-finite
     PinnedBuf<uint32_t> flags_host;
+    DevBuf<unsigned long long> norm2_dev;     // float rows: bits of the largest fp64 sum of squares among the rows the running append has stored
+    PinnedBuf<unsigned long long> norm2_host;
+    double row_norm_max = 0.0;                // upper bound on the L2 norm of every published row (float rows; mu): sqrt of the above, times 1 + 2^-30
 
     // --- query scratch ---
     // Scans run back-to-back on s_scan; the merge of tick i runs on the ctx stream (s_query) behind ev_scan[b], so
@@ -312,13 +357,15 @@ struct Ctx {
 
     // --- several pipelined ticks per DB pass (chip_api.hip coalesce_*; query_mu) ---
     struct ParkedTick { Slot *slot; int64_t k, l; chip_dot_params p; const void *q[3]; };
-    int32_t coalesce_max = 3;            // CHIP_TICK_COALESCE: 0 = every tick is a pass of its own, 2 / 3 = at most that many ticks per pass
+    int32_t coalesce_max = 4;            // CHIP_TICK_COALESCE: 0 = every tick is a pass of its own, 2 / 3 / 4 = at most that many ticks per pass
     bool coalesce_force = false;         // chip_debug_coalesce_force: park even when no scan is running (tests)
-    ParkedTick parked[kMultiMaxTicks];
+    ParkedTick parked[kPrefilterTicks];
     int32_t n_parked = 0;
     hipEvent_t pass_ev = nullptr;        // end of the newest long scan submitted (one of ev_scan[])
     uint64_t pass_no = 0;                // long scans submitted so far
     int64_t coalesce_passes = 0, coalesce_ticks = 0;   // passes of more than one tick / the ticks they served (chip_debug_coalesce_stats)
+    int64_t prefilter_passes = 0, prefilter_ticks = 0, prefilter_uncertified = 0;   // prefilter passes / their ticks / those of them run again alone
+    PinnedBuf<uint32_t> cert_all;        // [CHIP_MAX_INFLIGHT][4] certificate words of the slots (three used)
     chip_debug_scan_launch last_scan{};  // the last top-k scan launched (launch_scan / launch_scan_multi; query_mu): chip_debug_last_scan
 
     // --- scan tuning (resolved at create; CHIP_SCAN_* env overrides for A/B runs) ---

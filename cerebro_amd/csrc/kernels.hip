@@ -834,6 +834,384 @@ __global__ __launch_bounds__(kMultiBlock) __attribute__((amdgpu_num_vgpr(kShared
                          [&](int q) { return a.partial + (((int64_t)(q / 3) * gridDim.x + blockIdx.x) * 3 + q % 3) * K; });
 }
 
+// ------------------------------------------------------------------------------------------------ K1, four ticks per pass, fp32 prefilter
+// db_scan_prefilter<NG>: ONE pass over float rows answers FOUR queued ticks (12 queries) -- in fp32.  Its lists do not decide anything: they
+// are the candidate sets from which tick_rescore below PROVES which rows can be in each exact top-K and scores only those in fp64, in
+// rows_dot's order (|fp32 score - exact score| <= E for every pair of published rows, whatever the order of the fp32 sum).
+// Blocking, row -> wave map, load slots v[192..255], lists in LDS, per-tick prefix test and output layout are db_scan_topk_multi's.  What differs:
+//   * arithmetic: v_pk_fma_f32 straight on the loaded registers -- per (row vector, query) two instructions, no conversion; lane L keeps
+//     one accumulator PAIR per (row, query): elements 4L, 4L + 2 of every 256 go to its low half, 4L + 1, 4L + 3 to its high half.  A slot
+//     is therefore loaded again only when all 12 queries have read it: per KiB u the wave waits for its four row slots at once, multiplies
+//     the staged queries in, then the in-place ones, then issues the slots of u for the next batch (12 of the 16 row KiB stay in flight);
+//   * queries: the first NS = 12 - NG are staged in LDS as fp32 (D = 4096: 9, 144 KiB), the last NG are read IN PLACE through the load stream
+//     as db_scan_shared_f64 does (asm-owned registers v[192 - 16 NG ..] below the row slots, issued behind the row slots of the same KiB,
+//     every wave reads the same bytes: L2 hits).  The stream of a wave is r0 r1 r2 r3 g0 .. g(NG-1) per KiB, L = 4 (4 + NG) loads;
+//   * reduction: low + high half, then the transposed pairing tree of the fp64 kernel on single registers;
+//   * lists: (score widened to double -- exact --, row), thresholds as fp32 in SGPRs.  A workgroup's merged list of K holds its K best rows
+//     by fp32 score; its K-th score bounds every row the workgroup dropped (each wave dropped only rows at or below its own K-th).
+// Nothing is loaded from outside rows [0, n_rows) and the NG query vectors: every row base comes from row_of(), every offset is below one row's length.
+constexpr int kPrefilterMaxNG = 3;
+constexpr int kPrefilterVgprBase = kMultiVgprBase - 4 * kMultiU * kPrefilterMaxNG;   // 144: what the compiler owns in every instantiation
+#define CHIP_PREFILTER_CLOBBERS                                                                                                         \
+    "v144", "v145", "v146", "v147", "v148", "v149", "v150", "v151", "v152", "v153", "v154", "v155", "v156", "v157", "v158", "v159",     \
+    "v160", "v161", "v162", "v163", "v164", "v165", "v166", "v167", "v168", "v169", "v170", "v171", "v172", "v173", "v174", "v175",     \
+    "v176", "v177", "v178", "v179", "v180", "v181", "v182", "v183", "v184", "v185", "v186", "v187", "v188", "v189", "v190", "v191"
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+template <int REG, int OFF, bool NTL>
+__device__ __forceinline__ void prefilter_issue(uint32_t voff, const float *base_uniform)
+{
+    if constexpr (NTL)
+        asm volatile("global_load_dwordx4 v[%2:%3], %0, %1 offset:%4 nt" ::"v"(voff), "s"(base_uniform), "n"(REG), "n"(REG + 3), "n"(OFF) : "memory");
+    else
+        asm volatile("global_load_dwordx4 v[%2:%3], %0, %1 offset:%4" ::"v"(voff), "s"(base_uniform), "n"(REG), "n"(REG + 3), "n"(OFF) : "memory");
+}
+template <int CNT>
+__device__ __forceinline__ void prefilter_wait()
+{
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CNT) : "memory");
+}
+// acc += (elements HALF, HALF + 1 of the row slot at REG) * w, both halves at once
+template <int REG>
+__device__ __forceinline__ void prefilter_fma(f32x2 &acc, f32x2 w)
+{
+    asm volatile("v_pk_fma_f32 %0, v[%2:%3], %1, %0" : "+v"(acc) : "v"(w), "n"(REG), "n"(REG + 1));
+}
+// the same with the query pair in a slot of its own
+template <int REG, int QREG>
+__device__ __forceinline__ void prefilter_fma_slot(f32x2 &acc)
+{
+    asm volatile("v_pk_fma_f32 %0, v[%1:%2], v[%3:%4], %0" : "+v"(acc) : "n"(REG), "n"(REG + 1), "n"(QREG), "n"(QREG + 1));
+}
+
+__device__ __forceinline__ void swap32_f32(float &a, float &b)
+{
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    a = __uint_as_float(r[0]);
+    b = __uint_as_float(r[1]);
+}
+__device__ __forceinline__ void swap16_f32(float &a, float &b)
+{
+    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    a = __uint_as_float(r[0]);
+    b = __uint_as_float(r[1]);
+}
+template <int CTRL>
+__device__ __forceinline__ float dpp_f32(float v)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+}
+
+// multi_offer with the score and the threshold in fp32 (the list entry is the same value as a double)
+__device__ __forceinline__ void prefilter_offer(float s_uniform, int64_t gi, int K, int lane, chip_topk_entry *list, float &thr_s)
+{
+    if (s_uniform >= thr_s) {
+        asm volatile("" : "+v"(lane));
+        const double s = (double)s_uniform;
+        chip_topk_entry me, up;
+        me.score = -INFINITY; me.idx = -1; up = me;
+        if (lane < K) { me = list[lane]; if (lane > 0) up = list[lane - 1]; }
+        const bool worse = key_gt(s, gi, me.score, me.idx);
+        const unsigned long long m = __ballot(worse) & ((1ull << K) - 1ull);
+        const int pos = __builtin_ctzll(m);
+        if (lane < K) {
+            if (lane > pos) me = up;
+            else if (lane == pos) { me.score = s; me.idx = gi; }
+            list[lane] = me;      // every read of the old list precedes this write in program order (one wave, in-order LDS)
+        }
+        thr_s = (float)readlane_f64(me.score, K - 1);   // exact: every score of the list is a widened float
+    }
+}
+
+template <int NG>
+__global__ __launch_bounds__(kMultiBlock) __attribute__((amdgpu_num_vgpr(kPrefilterVgprBase / 2))) void db_scan_prefilter(PrefilterArgs a)
+{
+    constexpr int NQ = 3 * kPrefilterTicks, NS = NQ - NG, R = kMultiR, U = kMultiU;
+    constexpr int L = U * (R + NG);        // loads of the stream in flight
+    constexpr int QB = kMultiVgprBase - 4 * U * NG;   // first register of the in-place query slots: KiB u of query g at QB + 4 (u NG + g)
+    static_assert(NG >= 0 && NG <= kPrefilterMaxNG && NS >= 2 && L <= 64 && R == 4, "query slots, LDS read-ahead, vmcnt counts to 63");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    asm volatile("" ::: CHIP_MULTI_CLOBBERS, CHIP_PREFILTER_CLOBBERS);   // makes the code object allocate the asm-owned registers
+    float *qs = reinterpret_cast<float *>(smem);  // [NS][D]
+    const int D = a.D;
+    const int K = a.K;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wpb = blockDim.x >> 6;
+
+    for (int e = tid * 4; e < D; e += blockDim.x * 4) {
+        f32x4 w[NS];
+#pragma unroll
+        for (int q = 0; q < NS; q++) w[q] = *as_global(reinterpret_cast<const f32x4 *>(static_cast<const float *>(a.q[q]) + e));
+#pragma unroll
+        for (int q = 0; q < NS; q++) *reinterpret_cast<f32x4 *>(qs + q * D + e) = w[q];
+    }
+    __syncthreads();
+    const float *qg[NG > 0 ? NG : 1];   // the queries read in place (SGPRs)
+#pragma unroll
+    for (int g = 0; g < NG; g++) qg[g] = uniform_ptr(static_cast<const float *>(a.q[NS + g]));
+
+    chip_topk_entry *lists = reinterpret_cast<chip_topk_entry *>(smem + (size_t)NS * D * sizeof(float));   // [wave][12][K], as db_scan_topk_multi
+    chip_topk_entry *mylists = lists + (size_t)wave * NQ * K;
+    float thr_s[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; q++) {
+        thr_s[q] = -INFINITY;
+        if (lane < K) { chip_topk_entry t; t.score = -INFINITY; t.idx = -1; mylists[q * K + lane] = t; }
+    }
+
+    const int64_t tw = (int64_t)gridDim.x * wpb;
+    const int64_t rbase = (int64_t)blockIdx.x * wpb + wave;
+    const int nb = D / (256 * U);
+    const int ngroups = rbase < a.n_rows ? (int)((a.n_rows - 1 - rbase) / (R * tw)) + 1 : 0;
+    const int total = ngroups * nb;
+    const uint32_t lane_off = (uint32_t)lane * 16u;
+    const int e0 = lane * 4;
+    auto row_of = [&](int group, int rr) {
+        const int64_t r = rbase + ((int64_t)group * R + rr) * tw;
+        return uniform_ptr(row_base_uniform<float>(a, r < a.n_rows ? r : rbase));
+    };
+    const float *row[R], *nrow[R];
+#define CHIP_PF_ISSUE_ROW(u, rr, voff) prefilter_issue<multi_slot_reg(u, rr), (u) * 1024, true>(voff, row[rr])
+#define CHIP_PF_ISSUE_Q(u, g, voff) do { if constexpr ((g) < NG) prefilter_issue<QB + 4 * ((u) * NG + ((g) < NG ? (g) : 0)), (u) * 1024, false>(voff, qg[(g) < NG ? (g) : 0]); } while (0)
+#define CHIP_PF_ISSUE_SLOT(u, voff) do { CHIP_PF_ISSUE_ROW(u, 0, voff); CHIP_PF_ISSUE_ROW(u, 1, voff); CHIP_PF_ISSUE_ROW(u, 2, voff); CHIP_PF_ISSUE_ROW(u, 3, voff); \
+                                         CHIP_PF_ISSUE_Q(u, 0, voff); CHIP_PF_ISSUE_Q(u, 1, voff); CHIP_PF_ISSUE_Q(u, 2, voff); } while (0)
+    static_assert(kPrefilterMaxNG == 3, "CHIP_PF_ISSUE_SLOT / CHIP_PF_FMA_QS name the in-place queries one by one");
+    if (total > 0) {
+#pragma unroll
+        for (int rr = 0; rr < R; rr++) { row[rr] = row_of(0, rr); nrow[rr] = row[rr]; }
+        if (ngroups > 1) {
+#pragma unroll
+            for (int rr = 0; rr < R; rr++) nrow[rr] = row_of(1, rr);
+        }
+        CHIP_PF_ISSUE_SLOT(0, lane_off); CHIP_PF_ISSUE_SLOT(1, lane_off); CHIP_PF_ISSUE_SLOT(2, lane_off); CHIP_PF_ISSUE_SLOT(3, lane_off);
+    }
+
+    f32x2 acc[R][NQ];
+#pragma unroll
+    for (int rr = 0; rr < R; rr++)
+#pragma unroll
+        for (int q = 0; q < NQ; q++) acc[rr][q] = (f32x2){0.0f, 0.0f};
+
+    // One batch per iteration; what the slots load next is what db_scan_topk_multi's load next (the next batch of the group, the first batch of the
+    // next group, at the wave's last batch the first KiBs of its rows and queries once more).
+    int b = 0, group = 0;
+    for (int t = 0; t < total; t++) {
+        const int base = b * (256 * U);
+        uint32_t noff = (uint32_t)(base + 256 * U) * 4u;
+        if (b + 1 == nb) {
+            noff = 0;
+            if (group + 1 < ngroups) {
+#pragma unroll
+                for (int rr = 0; rr < R; rr++) row[rr] = nrow[rr];
+                if (group + 2 < ngroups) {
+#pragma unroll
+                    for (int rr = 0; rr < R; rr++) nrow[rr] = row_of(group + 2, rr);
+                }
+            }
+        }
+        {
+            constexpr int SS = U * NS;
+            const float *qv = qs + base + e0;
+            const uint32_t voff = noff + lane_off;
+            f32x4 w[SS];        // staged query vectors in the order they are used: (u, q < NS), read two ahead
+            w[0] = *reinterpret_cast<const f32x4 *>(qv);
+            w[1] = *reinterpret_cast<const f32x4 *>(qv + D);
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+#define CHIP_PF_U(uu) if (u == uu) {                                                                                                    \
+                    prefilter_wait<L - R>();                      /* the four row slots of this KiB are the oldest loads of the stream */ \
+                    _Pragma("unroll") for (int q = 0; q < NS; q++) {                                                                    \
+                        const int i = uu * NS + q;                                                                                      \
+                        if (i + 2 < SS) w[i + 2] = *reinterpret_cast<const f32x4 *>(qv + ((i + 2) % NS) * D + ((i + 2) / NS) * 256);     \
+                        const f32x2 wl = __builtin_shufflevector(w[i], w[i], 0, 1), wh = __builtin_shufflevector(w[i], w[i], 2, 3);     \
+                        prefilter_fma<multi_slot_reg(uu, 0)>(acc[0][q], wl); prefilter_fma<multi_slot_reg(uu, 1)>(acc[1][q], wl);       \
+                        prefilter_fma<multi_slot_reg(uu, 2)>(acc[2][q], wl); prefilter_fma<multi_slot_reg(uu, 3)>(acc[3][q], wl);       \
+                        prefilter_fma<multi_slot_reg(uu, 0) + 2>(acc[0][q], wh); prefilter_fma<multi_slot_reg(uu, 1) + 2>(acc[1][q], wh); \
+                        prefilter_fma<multi_slot_reg(uu, 2) + 2>(acc[2][q], wh); prefilter_fma<multi_slot_reg(uu, 3) + 2>(acc[3][q], wh); \
+                        __builtin_amdgcn_sched_barrier(0);                                                                              \
+                    }                                                                                                                   \
+                    CHIP_PF_FMA_Q(uu, 0) CHIP_PF_FMA_Q(uu, 1) CHIP_PF_FMA_Q(uu, 2)                                                      \
+                    CHIP_PF_ISSUE_SLOT(uu, voff);                                                                                       \
+                }
+#define CHIP_PF_FMA_Q(uu, gg) if constexpr ((gg) < NG) {                                                                                \
+                    constexpr int QR = QB + 4 * ((uu) * NG + ((gg) < NG ? (gg) : 0));                                                   \
+                    prefilter_wait<L - R - 1 - (gg)>();                                                                                 \
+                    prefilter_fma_slot<multi_slot_reg(uu, 0), QR>(acc[0][NS + (gg)]); prefilter_fma_slot<multi_slot_reg(uu, 1), QR>(acc[1][NS + (gg)]); \
+                    prefilter_fma_slot<multi_slot_reg(uu, 2), QR>(acc[2][NS + (gg)]); prefilter_fma_slot<multi_slot_reg(uu, 3), QR>(acc[3][NS + (gg)]); \
+                    prefilter_fma_slot<multi_slot_reg(uu, 0) + 2, QR + 2>(acc[0][NS + (gg)]); prefilter_fma_slot<multi_slot_reg(uu, 1) + 2, QR + 2>(acc[1][NS + (gg)]); \
+                    prefilter_fma_slot<multi_slot_reg(uu, 2) + 2, QR + 2>(acc[2][NS + (gg)]); prefilter_fma_slot<multi_slot_reg(uu, 3) + 2, QR + 2>(acc[3][NS + (gg)]); \
+                }
+                CHIP_PF_U(0) CHIP_PF_U(1) CHIP_PF_U(2) CHIP_PF_U(3)
+#undef CHIP_PF_FMA_Q
+#undef CHIP_PF_U
+            }
+        }
+        if (++b == nb) {
+            // the rows of this group are complete: low + high half, then the transposed pairing tree of db_scan_topk_multi on single registers
+            // (any tree will do here; this one leaves row rr's sum in all 16 lanes of the wave's 16-lane row rr)
+            float s[NQ];
+#pragma unroll
+            for (int q = 0; q < NQ; q++) {
+                float a0 = acc[0][q][0] + acc[0][q][1], a1 = acc[1][q][0] + acc[1][q][1], a2 = acc[2][q][0] + acc[2][q][1], a3 = acc[3][q][0] + acc[3][q][1];
+                swap32_f32(a0, a2);
+                swap32_f32(a1, a3);
+                float p02 = a0 + a2, p13 = a1 + a3;
+                swap16_f32(p02, p13);
+                float v = p02 + p13;
+                v = v + dpp_f32<0x128>(v);
+                v = v + dpp_f32<0x124>(v);
+                v = v + dpp_f32<0x4E>(v);
+                v = v + dpp_f32<0xB1>(v);
+                s[q] = v;
+            }
+            unsigned long long hit = 0;
+#pragma unroll
+            for (int q = 0; q < NQ; q++) hit |= __ballot(s[q] >= thr_s[q]);
+            if (hit) {
+#pragma unroll
+                for (int q = 0; q < NQ; q++) {
+                    asm volatile("" : "+v"(s[q]));   // as db_scan_topk_multi: the compare is made again, the pre-check's masks are not kept
+                    if (__ballot(s[q] >= thr_s[q])) {
+#pragma unroll
+                        for (int rr = 0; rr < R; rr++) {
+                            const int64_t r = rbase + ((int64_t)group * R + rr) * tw;
+                            if (r < a.n_rows && r < a.k[q / 3])
+                                prefilter_offer(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(s[q]), 16 * rr)), r, K, lane, mylists + q * K, thr_s[q]);
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int rr = 0; rr < R; rr++)
+#pragma unroll
+                for (int q = 0; q < NQ; q++) acc[rr][q] = (f32x2){0.0f, 0.0f};
+            b = 0;
+            group++;
+        }
+    }
+#undef CHIP_PF_ISSUE_SLOT
+#undef CHIP_PF_ISSUE_Q
+#undef CHIP_PF_ISSUE_ROW
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the read-ahead of the wave's last batch
+
+    block_merge_cand<NQ>(lists, K, lane, wave, wpb,
+                         [&](int q) { return a.partial + (((int64_t)(q / 3) * gridDim.x + blockIdx.x) * 3 + q % 3) * K; });
+}
+
+// ------------------------------------------------------------------------------------------------ exact rescoring of one prefiltered tick
+// tick_rescore: ONE launch per pass, one workgroup per (tick, query), in front of the ticks' K2 launches.  (The pass fills every CU's register
+// file, so whatever follows it on the ctx stream runs in the gap between two passes: a chain of one launch per tick did not fit there and
+// stalled the pipeline.)  Per query, from the n_lists workgroup lists of db_scan_prefilter
+// (C = all their entries):  G = the K-th largest fp32 score of C (-inf with fewer than K rows),  M = the largest K-th score of a list whose
+// workgroup owned more than K rows of the prefix (-inf if there is none: nothing was dropped),  R = { r in C : score >= G - 2E }.  Certificate: M < G - 2E (or nothing dropped)
+// and |R| <= kRescoreCap -- then the exact top-K is the top-K of R by exact score.  The rows of R are scored by rows_dot + butterfly_sum (the
+// bits of every other scan kernel) and written as ONE sorted list per query, which topk_merge reads as a launch of one workgroup's lists.
+__device__ __forceinline__ void block_best(double &bs, int64_t &bi, double *red_s, int64_t *red_i, int lane, int wave)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const double os = __shfl_xor(bs, m, 64);
+        const int64_t oi = __shfl_xor(bi, m, 64);
+        if (key_gt(os, oi, bs, bi)) { bs = os; bi = oi; }
+    }
+    __syncthreads();   // (red_* of the previous round has been read by everybody)
+    if (lane == 0) { red_s[wave] = bs; red_i[wave] = bi; }
+    __syncthreads();
+    bs = red_s[0]; bi = red_i[0];
+#pragma unroll
+    for (int w = 1; w < 8; w++)
+        if (key_gt(red_s[w], red_i[w], bs, bi)) { bs = red_s[w]; bi = red_i[w]; }
+}
+
+__global__ __launch_bounds__(512) void tick_rescore(RescoreArgs a)
+{
+    constexpr int MAXH = 512 * CHIP_MAX_TOPK / 512;   // entries per thread: n_lists <= 512 lists of K <= CHIP_MAX_TOPK
+    __shared__ double red_s[8];
+    __shared__ int64_t red_i[8];
+    __shared__ chip_topk_entry cand[kRescoreCap];
+    __shared__ int n_cand;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tick = blockIdx.x / 3, q = blockIdx.x % 3;     // one workgroup per (tick of the pass, query of the tick)
+    const int K = a.K, n = a.n_lists * K;
+    const chip_topk_entry *in = a.in + (int64_t)tick * a.n_lists * 3 * K;
+    const int64_t k = a.k[tick];
+    if (tid == 0) n_cand = 0;
+    double es[MAXH];
+    int64_t ei[MAXH];
+#pragma unroll
+    for (int h = 0; h < MAXH; h++) {
+        const int c = tid + 512 * h;
+        es[h] = -INFINITY; ei[h] = -1;
+        if (c < n) { const chip_topk_entry t = in[((int64_t)(c / K) * 3 + q) * K + (c % K)]; es[h] = t.score; ei[h] = t.idx; }
+    }
+    // M: the K-th entries of the lists whose workgroup owned more than K rows of the prefix (the others dropped nothing).  Workgroup b
+    // owns the rows r with r mod tw in [b wpb, (b + 1) wpb), tw = n_lists wpb (db_scan_prefilter's row -> wave map).
+    double ms = -INFINITY;
+    int64_t mi = -1;
+    const int64_t tw = (int64_t)a.n_lists * a.wpb;
+#pragma unroll
+    for (int h = 0; h < MAXH; h++) {
+        const int c = tid + 512 * h;
+        if (c % K != K - 1 || ei[h] < 0) continue;
+        int64_t part = k % tw - (int64_t)(c / K) * a.wpb;
+        part = part < 0 ? 0 : part > a.wpb ? a.wpb : part;
+        if ((k / tw) * a.wpb + part > K && es[h] > ms) { ms = es[h]; mi = 0; }
+    }
+    block_best(ms, mi, red_s, red_i, lane, wave);
+    // G: K rounds of "the best entry strictly below the previous one"
+    double gs = INFINITY;
+    int64_t gi = INT64_MAX;
+    for (int j = 0; j < K; j++) {
+        double bs = -INFINITY;
+        int64_t bi = -1;
+#pragma unroll
+        for (int h = 0; h < MAXH; h++)
+            if (key_gt(gs, gi, es[h], ei[h]) && key_gt(es[h], ei[h], bs, bi)) { bs = es[h]; bi = ei[h]; }
+        block_best(bs, bi, red_s, red_i, lane, wave);
+        gs = bs; gi = bi;
+    }
+    double thr = gs - 2.0 * a.E;
+    thr -= fabs(thr) * 0x1p-51;   // at least one ulp below the rounded difference: R can only grow, the certificate can only fail
+    const bool ok = mi < 0 || ms < thr;
+#pragma unroll
+    for (int h = 0; h < MAXH; h++)
+        if (ei[h] >= 0 && es[h] >= thr) {
+            const int at = atomicAdd(&n_cand, 1);
+            if (at < kRescoreCap) { chip_topk_entry t; t.score = es[h]; t.idx = ei[h]; cand[at] = t; }
+        }
+    __syncthreads();
+    const int nc = n_cand < kRescoreCap ? n_cand : kRescoreCap;
+    // exact scores: one wave per candidate row
+    const float *qrow = static_cast<const float *>(a.q[3 * tick + q]);
+    for (int j = wave; j < nc; j += 8) {
+        const int64_t r = cand[j].idx;
+        const float *row[1] = {static_cast<const float *>(a.seg_table[r >> a.seg_shift]) + (r & a.seg_mask) * (int64_t)a.D};
+        double acc[1][1];
+        rows_dot<float, 1, 4, true, 1, 1>(row, qrow, a.D, lane, acc);
+        const double s = butterfly_sum(acc[0][0]);
+        if (lane == 0) cand[j].score = s;
+    }
+    __syncthreads();
+    if (wave == 0) {
+        static_assert(kRescoreCap <= 64, "one lane per candidate");
+        chip_topk_entry *out = a.out + (int64_t)(3 * tick + q) * K;
+        chip_topk_entry me;
+        me.score = -INFINITY; me.idx = -1;
+        if (lane < nc) me = cand[lane];
+        int rank = 0;
+        for (int j = 0; j < nc; j++) {
+            const chip_topk_entry o = cand[j];
+            rank += key_gt(o.score, o.idx, me.score, me.idx) ? 1 : 0;
+        }
+        if (lane < nc && rank < K) out[rank] = me;
+        if (lane >= nc && lane < K) out[lane] = me;   // fewer candidates than K: the list ends in empty entries
+        if (lane == 0) a.cert[tick][q] = ok && n_cand <= kRescoreCap ? 1u : 2u;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ K1, wide double rows
 // Double rows whose NQ query descriptors do not fit the 160 KiB of LDS (the reference's default D = 8192, src/Cerebro.cpp:1021, as a
 // MatrixXd of genuine float64 values: 3 x 8192 x 8 B = 192 KiB).  The first NQ - NG queries are staged as usual; the last NG are read
@@ -1907,6 +2285,81 @@ int launch_scan_multi(Ctx *c, hipStream_t s, const MultiScanArgs &a, int n_ticks
     return CHIP_OK;
 }
 
+// The prefilter pass (db_scan_prefilter): four ticks over float rows of whole 4 KiB batches.  The ONE place that sizes it: as many of the 12 fp32
+// queries staged as fit the LDS next to the lists, the other NG read in place -- NG = 0 (D <= 3072) or 3 (D = 4096) are built; every other shape
+// (wider rows, K = 16 at D = 4096, double rows) has no such pass.
+int scan_prefilter_plan(int D, int elem, int K, int grid, chip_debug_scan_launch *f)
+{
+    *f = chip_debug_scan_launch{};
+    if (D < 1 || elem != 4 || K < 1 || K > CHIP_MAX_TOPK || grid < 1 || grid > 512 || (int64_t)D * elem % 4096 != 0) return CHIP_ERR_UNSUPPORTED;
+    const int nq = 3 * kPrefilterTicks;
+    const size_t kLds = 160 * 1024, lists = (size_t)(kMultiBlock / 64) * nq * K * sizeof(chip_topk_entry);
+    const size_t fit = (kLds - lists) / ((size_t)D * 4);
+    const int staged = fit < (size_t)nq ? (int)fit : nq;
+    const int ng = nq - staged;
+    if (ng != 0 && ng != kPrefilterMaxNG) return CHIP_ERR_UNSUPPORTED;
+    f->family = CHIP_SCAN_FAMILY_PREFILTER;
+    f->elem = elem;
+    f->nq = nq;
+    f->K = K;
+    f->U = kMultiU;
+    f->FULL = 1;
+    f->R = kMultiR;
+    f->NTL = 1;
+    f->ticks = kPrefilterTicks;
+    f->NG = ng;
+    f->grid = grid;
+    f->block = kMultiBlock;
+    f->wg_per_cu = 1;
+    f->lds_bytes = (int32_t)((size_t)staged * D * 4 + lists);
+    return CHIP_OK;
+}
+
+// E of DESIGN.md 3: (gamma_32 + gamma_64) N^2 + D 2^-148 with gamma_32 = 2 D u / (1 - 2 D u), u = 2^-24, gamma_64 = (D + 8) 2^-53 / (1 - (D + 8) 2^-53),
+// evaluated in fp64 and rounded up (a handful of roundings, each below 2^-52 relative: the factor 1 + 2^-40 covers them).
+double prefilter_error_bound(int D, double row_norm_max)
+{
+    const double u32 = 2.0 * D * std::ldexp(1.0, -24), u64 = (D + 8.0) * std::ldexp(1.0, -53);
+    const double g = u32 / (1.0 - u32) + u64 / (1.0 - u64);
+    return (g * row_norm_max * row_norm_max + D * std::ldexp(1.0, -148)) * (1.0 + std::ldexp(1.0, -40));
+}
+
+bool scan_prefilter_usable(const Ctx *c)
+{
+    if (c->elem != 4 || c->nranks != 1 || c->scan_variant != 0 || c->scan_rows > 0) return false;
+    chip_debug_scan_launch f;
+    if (scan_prefilter_plan(c->D, c->elem, CHIP_DEFAULT_TOPK, scan_multi_grid(c), &f) != CHIP_OK) return false;
+    double n;
+    { std::lock_guard<std::mutex> lk(c->mu); n = c->row_norm_max; }
+    return n * n <= std::ldexp(1.0, 120) && 2.0 * c->D * std::ldexp(1.0, -24) < 0.5;   // no overflow of an fp32 partial sum (false for NaN as well)
+}
+
+int launch_scan_prefilter(Ctx *c, hipStream_t s, const PrefilterArgs &a, int grid)
+{
+    chip_debug_scan_launch f;
+    if (grid > c->max_grid || scan_prefilter_plan(c->D, c->elem, a.K, grid, &f) != CHIP_OK) return CHIP_ERR_UNSUPPORTED;
+    auto go = [&](auto kernel) -> int {
+        CHIP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, f.lds_bytes));
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kMultiBlock), f.lds_bytes, s, a);
+        CHIP_HIP(c, hipGetLastError());
+        return CHIP_OK;
+    };
+    const int rc = f.NG == 0 ? go(db_scan_prefilter<0>) : go(db_scan_prefilter<kPrefilterMaxNG>);
+    if (rc != CHIP_OK) return rc;
+    f.n_rows = a.n_rows;
+    f.launches = c->last_scan.launches + 1;
+    c->last_scan = f;
+    return CHIP_OK;
+}
+
+int launch_rescore(Ctx *c, hipStream_t s, const RescoreArgs &a)
+{
+    if (a.n_lists > 512 || a.K > CHIP_MAX_TOPK) return CHIP_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(tick_rescore, dim3(3 * kPrefilterTicks), dim3(512), 0, s, a);
+    CHIP_HIP(c, hipGetLastError());
+    return CHIP_OK;
+}
+
 int launch_resident(Ctx *c, hipStream_t s, const ResidentArgs &ra, int grid)
 {
 #ifdef CHIP_NO_ROWS_FORM
@@ -2061,6 +2514,37 @@ __global__ __launch_bounds__(256) void convert_rows(StoreArgs a, const S *__rest
     if (bad) atomicOr(a.flags, bad);
 }
 
+// Row-norm bound of a float-row DB (Ctx::row_norm_max, what the prefilter's error bound E is made of): one wave per row just stored, its
+// sum of squares in fp64 (the squares of fp32 values are exact), combined over rows by an atomic max on the bits of a non-negative double.
+__global__ __launch_bounds__(256) void rows_norm2_max(StoreArgs a, unsigned long long *out)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t nw = (int64_t)gridDim.x * 4;
+    for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < a.n; r += nw) {
+        const int64_t g = a.first_global + r * a.row_stride;
+        if (a.nranks != 1 && (g % a.nranks) != a.rank) continue;
+        const int64_t loc = a.nranks == 1 ? g : g / a.nranks;
+        const float *row = static_cast<const float *>(a.seg_table[loc >> a.seg_shift]) + (loc & a.seg_mask) * (int64_t)a.D;
+        double ss = 0.0;
+        for (int e = lane * 4; e < a.D; e += 256) {
+            const f32x4 v = *reinterpret_cast<const f32x4 *>(row + e);
+#pragma unroll
+            for (int c = 0; c < 4; c++) ss = __builtin_fma((double)v[c], (double)v[c], ss);
+        }
+        ss = butterfly_sum(ss);
+        if (lane == 0 && ss > 0.0) atomicMax(out, (unsigned long long)__double_as_longlong(ss));   // (NaN: refused by the append's own check)
+    }
+}
+
+static int launch_norm2(Ctx *c, hipStream_t s, const StoreArgs &a)
+{
+    if (c->elem != 4 || !c->norm2_dev.get() || a.n <= 0) return CHIP_OK;
+    const int64_t blocks = (a.n + 3) / 4, cap = (int64_t)c->n_cus * 8;
+    hipLaunchKernelGGL(rows_norm2_max, dim3((int)(blocks < cap ? blocks : cap)), dim3(256), 0, s, a, c->norm2_dev.get());
+    CHIP_HIP(c, hipGetLastError());
+    return CHIP_OK;
+}
+
 static StoreArgs make_store_args(Ctx *c, int64_t first_global, int64_t n, uint32_t *flags, bool write_ring = true)
 {
     StoreArgs a;
@@ -2100,7 +2584,7 @@ int launch_store_rows(Ctx *c, hipStream_t s, const void *src, int src_elem, int6
     else if (c->elem == 4) hipLaunchKernelGGL((convert_rows<float, float>), grid, block, 0, s, a, static_cast<const float *>(src));
     else hipLaunchKernelGGL((convert_rows<float, double>), grid, block, 0, s, a, static_cast<const float *>(src));
     CHIP_HIP(c, hipGetLastError());
-    return CHIP_OK;
+    return write_ring ? CHIP_OK : launch_norm2(c, s, a);   // (the ring pass stores rows the DB pass has stored, and measured, already)
 }
 
 // ------------------------------------------------------------------------------------------------ synth
@@ -2232,7 +2716,7 @@ int launch_synth(Ctx *c, hipStream_t s, int64_t first_global, int64_t n, uint64_
     } else if (c->elem == 8) hipLaunchKernelGGL(synth_rows<double>, dim3(grid_for_elems(c, n * (c->D / 4))), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(synth_rows<float>, dim3(grid_for_elems(c, n * (c->D / 4))), dim3(256), 0, s, a);
     CHIP_HIP(c, hipGetLastError());
-    return CHIP_OK;
+    return launch_norm2(c, s, a.st);   // generated rows and plants alike
 }
 
 }  // namespace chip

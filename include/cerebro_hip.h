@@ -277,10 +277,13 @@ int chip_resident_resume(chip_ctx *ctx);
  * Ticks that share a DB pass.  Queued ticks do not depend on one another (status and last_l are settled at enqueue, the queries
  * are published rows), so on a plain single-GPU ctx with float or double rows, on its own streams, an enqueue over a LONG prefix (beyond
  * CHIP_SCAN_OVERLAP_GIB, 8 GiB) that finds a scan of the ctx still running PARKS its tick instead of launching it; parked ticks
- * leave together as ONE pass over [0, max k) with 3 T queries (T <= CHIP_TICK_COALESCE, default 3; 0 = off), every tick seeing
+ * leave together as ONE pass over [0, max k) with 3 T queries (T <= CHIP_TICK_COALESCE, default 4; 0 = off), every tick seeing
  * only its own prefix [0, k_t).  Which rows: whole 4 KiB batches -- float rows with D % 1024 == 0 whose 3 T queries fit the LDS (D = 4096:
  * T <= 3), double rows with D % 512 == 0 up to D = 4608, T = 2 (the queries that do not fit the LDS are read in place, out of the L2);
- * chip_debug_multi_plan says what a given shape gets.  Every other ctx launches its ticks one by one.  Results, status codes, CHIP_ERR_BUSY, last_l, chip_loop_reset, skipped / too-short ticks in
+ * chip_debug_multi_plan says what a given shape gets.  FOUR ticks (float rows up to D = 4096, chip_debug_prefilter_plan) leave as a pass
+ * that scores in fp32 and then proves, per query, which rows can be in the exact top-8 and scores those in fp64 in the usual order:
+ * same records; a tick whose proof does not go through (scores closer together than the fp32 error bound taken from
+ * chip_info.row_norm_max) runs again alone at its collect.  CHIP_TICK_COALESCE=2 / 3 are what they were.  Every other ctx launches its ticks one by one.  Results, status codes, CHIP_ERR_BUSY, last_l, chip_loop_reset, skipped / too-short ticks in
  * between, appends between enqueue and collect and out-of-order collects are exactly those of ticks launched one by one.  A tick
  * that arrives while no scan is running is launched at once, alone; chip_loop_tick, short prefixes and caller-supplied streams
  * (chip_set_stream) never park.  Nothing stays parked while its caller cannot release it.  Parked ticks are submitted by:
@@ -318,6 +321,7 @@ int chip_debug_coalesce_decide(int32_t n_parked, int32_t t_max, int32_t scan_run
 #define CHIP_SCAN_FAMILY_WIDE    2   /* db_scan_topk_wide<NQ, NG, FULL>: double rows, NG of the NQ queries read in place           */
 #define CHIP_SCAN_FAMILY_ROWS    3   /* db_scan_topk_rows<T, NQ, R, NTL>: R rows per wave in flight; carries the fused tick        */
 #define CHIP_SCAN_FAMILY_MULTI   4   /* db_scan_topk_multi<T> / db_scan_shared_f64<T, NG>: `ticks` pipelined ticks share one pass     */
+#define CHIP_SCAN_FAMILY_PREFILTER 5 /* db_scan_prefilter<NG>: four pipelined ticks share one fp32 pass; tick_rescore scores the proven candidates exactly */
 #define CHIP_SCAN_CALL_QUERY      0  /* chip_query_rows / chip_query_vectors_*: lists out                                         */
 #define CHIP_SCAN_CALL_TICK       1  /* chip_loop_tick_enqueue: a pipelined tick                                                   */
 #define CHIP_SCAN_CALL_TICK_SYNC  2  /* chip_loop_tick: the synchronous tick                                                       */
@@ -347,6 +351,13 @@ int chip_debug_scan_plan(int32_t D, int32_t elem, int32_t nq, int32_t K, int64_t
  * NG = queries read in place, lds_bytes (queries + the waves' lists of K entries), grid (one workgroup per compute unit) and block.
  * CHIP_ERR_UNSUPPORTED where a plain single-GPU ctx of that shape has no such pass and launches its ticks one by one (ABI 7, additive). */
 int chip_debug_multi_plan(int32_t D, int32_t elem, int32_t n_ticks, int32_t K, int32_t n_cus, chip_debug_scan_launch *out);
+/* The prefilter pass of four pipelined ticks (family CHIP_SCAN_FAMILY_PREFILTER, float rows) the same way: nq = 12, ticks = 4, NG = queries read
+ * in place (the others are staged in LDS as fp32), lds_bytes, grid, block.  CHIP_ERR_UNSUPPORTED where a ctx of that shape has no such pass and
+ * releases at most three ticks together (ABI 7, additive). */
+int chip_debug_prefilter_plan(int32_t D, int32_t elem, int32_t K, int32_t n_cus, chip_debug_scan_launch *out);
+/* Prefilter passes submitted, the ticks they served, and those of them whose certificate did not hold (counted at collect: such a tick was run
+ * again alone, and its caller got that record). */
+int chip_debug_prefilter_stats(chip_ctx *ctx, int64_t *passes, int64_t *ticks, int64_t *uncertified);
 
 /* Sharded tick, three phases (host does the exchange between 1 and 2):
  *  1. chip_scan_local: scan this rank's share of rows [0,k), k = l - lag, for the three queries l-1,l-2,l-3 and
@@ -628,6 +639,9 @@ typedef struct {
                                    CHIP_TEST_* / CHIP_PNP_BACKSUB / CHIP_PNP_DEBUG_STOP environment variables are never read.
                                    1: the test build (-DCHIP_TEST_HOOKS, `make testlibs` -> cerebro_amd/lib/hooks/), which only
                                    tests/ load -- never deploy it (ABI 6)                                                       */
+    double  row_norm_max;       /* float rows: an upper bound on the L2 norm of every published row (the largest fp64 row norm, times
+                                   1 + 2^-30); 0 for an empty DB and for double rows.  The prefilter pass takes its error bound from it
+                                   (ABI 7, additive: the last field)                                                              */
 } chip_info;
 enum { CHIP_SCAN_FORM_ONE_ROW = 1, CHIP_SCAN_FORM_ROWS = 2 };
 /* the same bits without a ctx (what `make verify` and the build log ask) */

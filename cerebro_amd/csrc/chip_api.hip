@@ -622,17 +622,14 @@ static int coalesce_submit(Ctx *c, int T)
     const int K = CHIP_DEFAULT_TOPK;
     const bool prefilter = T == kPrefilterTicks;
     static_assert(kPrefilterTicks > kMultiMaxTicks, "a pass of kPrefilterTicks ticks is the prefilter's");
-    MultiScanArgs a{};
-    PrefilterArgs pa{};
+    PassArgs a{};
     scan_args_db(c, &a);
-    scan_args_db(c, &pa);
-    a.K = pa.K = K;
-    a.partial = pa.partial = c->partial_dev[b];
+    a.K = K;
+    a.partial = c->partial_dev[b];
     for (int t = 0; t < T; t++) {
-        const int64_t k = c->parked[t].k;
-        if (k > a.n_rows) a.n_rows = pa.n_rows = k;
-        if (prefilter) pa.k[t] = k; else a.k[t] = k;
-        for (int i = 0; i < 3; i++) (prefilter ? pa.q : a.q)[3 * t + i] = c->parked[t].q[i];
+        a.k[t] = c->parked[t].k;
+        if (a.k[t] > a.n_rows) a.n_rows = a.k[t];
+        for (int i = 0; i < 3; i++) a.q[3 * t + i] = c->parked[t].q[i];
     }
     const int grid = scan_multi_grid(c);
     double E = 0.0;
@@ -643,7 +640,7 @@ static int coalesce_submit(Ctx *c, int T)
     if (hipEventQuery(c->ev_merged[b]) != hipSuccess) CHIP_HIP(c, hipStreamWaitEvent(c->s_scan, c->ev_merged[b], 0));
     hipEvent_t e1 = nullptr;   // one event pair per pass; a pass reads the prefix once
     int rc = c->prof_on ? prof_begin(c, c->s_scan, (double)a.n_rows * c->D * c->elem, &e1) : CHIP_OK;
-    if (rc == CHIP_OK) rc = prefilter ? launch_scan_prefilter(c, c->s_scan, pa, grid) : launch_scan_multi(c, c->s_scan, a, T, grid);
+    if (rc == CHIP_OK) rc = prefilter ? launch_scan_prefilter(c, c->s_scan, a, grid) : launch_scan_multi(c, c->s_scan, a, T, grid);
     if (rc != CHIP_OK) return rc;
     if (e1) CHIP_HIP(c, hipEventRecord(e1, c->s_scan));
     CHIP_HIP(c, hipEventRecord(c->ev_scan[b], c->s_scan));
@@ -653,7 +650,7 @@ static int coalesce_submit(Ctx *c, int T)
     chip_topk_entry *exact = c->partial_dev[b] + (size_t)kPrefilterTicks * grid * 3 * K;   // [tick][3][K], behind the pass's lists
     if (prefilter) {
         RescoreArgs ra{};
-        ra.seg_table = pa.seg_table; ra.seg_shift = pa.seg_shift; ra.seg_mask = pa.seg_mask; ra.D = pa.D; ra.K = K;
+        ra.seg_table = a.seg_table; ra.seg_shift = a.seg_shift; ra.seg_mask = a.seg_mask; ra.D = a.D; ra.K = K;
         ra.in = c->partial_dev[b]; ra.n_lists = grid; ra.wpb = 8;   // (kMultiBlock / 64 waves per workgroup)
         ra.E = E;
         ra.out = exact;

@@ -74,33 +74,22 @@ struct ResidentArgs {
                                       //    nothing but its own decision to leave
 };
 
-// ---- several ticks in one DB pass (kernels.hip db_scan_topk_multi, chip_api.hip coalesce_*) ----
-constexpr int kMultiMaxTicks = 3;                   // ticks of 3 queries each that one pass can serve (9 fp32 queries of 4096 elements = 144 KiB of LDS; double rows: 2)
-struct MultiScanArgs {
+// ---- several ticks in one DB pass (kernels.hip shared_pass: db_scan_topk_multi / db_scan_shared_f64 / db_scan_prefilter; chip_api.hip coalesce_*) ----
+constexpr int kMultiMaxTicks = 3;                   // ticks of 3 queries each that one exact pass can serve (9 fp32 queries of 4096 elements = 144 KiB of LDS; double rows: 2)
+// four ticks in one DB pass: fp32 prefilter + certified exact rescoring (kernels.hip db_scan_prefilter / tick_rescore)
+constexpr int kPrefilterTicks = 4;                  // ticks of the prefilter pass: 12 fp32 queries, those the LDS does not hold are read in place
+constexpr int kRescoreCap = 32;                     // rows per query that tick_rescore scores exactly; more candidates than that: uncertified
+struct PassArgs {                                   // one shared pass of T <= kPrefilterTicks ticks, whichever kernel serves it
     const void *const *seg_table;                   // as ScanArgs (plain single-GPU ctx: global index == local row)
     int32_t seg_shift;
     int64_t seg_mask;
     int64_t n_rows;                                 // rows [0, n_rows) are read: the longest prefix of the pass
     int32_t D;
     int32_t K;
-    int64_t k[kMultiMaxTicks];                      // tick t sees rows [0, k[t])
-    const void *q[3 * kMultiMaxTicks];              // queries of tick t: q[3 t .. 3 t + 2] (device, the rows' type, D each, 16-B aligned)
+    int64_t k[kPrefilterTicks];                     // tick t sees rows [0, k[t])
+    const void *q[3 * kPrefilterTicks];             // queries of tick t: q[3 t .. 3 t + 2] (device, the rows' type, D each, 16-B aligned)
     chip_topk_entry *partial;                       // [tick][gridDim.x][3][K]: every tick's block of lists is what ONE launch of db_scan_topk leaves
-};
-
-// ---- four ticks in one DB pass: fp32 prefilter + certified exact rescoring (kernels.hip db_scan_prefilter / tick_rescore) ----
-constexpr int kPrefilterTicks = 4;                  // ticks of the prefilter pass: 12 fp32 queries, those the LDS does not hold are read in place
-constexpr int kRescoreCap = 32;                     // rows per query that tick_rescore scores exactly; more candidates than that: uncertified
-struct PrefilterArgs {
-    const void *const *seg_table;                   // as MultiScanArgs (float rows, plain single-GPU ctx)
-    int32_t seg_shift;
-    int64_t seg_mask;
-    int64_t n_rows;
-    int32_t D;
-    int32_t K;
-    int64_t k[kPrefilterTicks];
-    const void *q[3 * kPrefilterTicks];
-    chip_topk_entry *partial;                       // [tick][gridDim.x][3][K]: (fp32 score widened to double, row) sorted by score desc, index desc
+                                                    // (prefilter: fp32 score widened to double, row; sorted by score desc, index desc)
 };
 struct RescoreArgs {                                // one launch per pass: workgroup 3 t + i serves query i of tick t
     const void *const *seg_table;
@@ -179,12 +168,12 @@ int scan_multi_max_ticks(const Ctx *c);   // ticks one shared pass can serve on 
 // the shared pass for n_ticks ticks over rows of D elements of elem bytes: staged (q64, double rows) / in-place (NG) queries, LDS, shape -- or CHIP_ERR_UNSUPPORTED
 int scan_multi_plan(int D, int elem, int n_ticks, int K, int grid, chip_debug_scan_launch *f);
 int scan_multi_grid(const Ctx *c);
-int launch_scan_multi(Ctx *c, hipStream_t s, const MultiScanArgs &a, int n_ticks, int grid);
+int launch_scan_multi(Ctx *c, hipStream_t s, const PassArgs &a, int n_ticks, int grid);
 // the prefilter pass of kPrefilterTicks ticks over float rows of D elements: staged / in-place (NG) queries, LDS, shape -- or CHIP_ERR_UNSUPPORTED
 int scan_prefilter_plan(int D, int elem, int K, int grid, chip_debug_scan_launch *f);
 bool scan_prefilter_usable(const Ctx *c);           // this ctx may serve four parked ticks with the prefilter pass (row norms included)
 double prefilter_error_bound(int D, double row_norm_max);   // E of DESIGN.md 3, rounded up
-int launch_scan_prefilter(Ctx *c, hipStream_t s, const PrefilterArgs &a, int grid);
+int launch_scan_prefilter(Ctx *c, hipStream_t s, const PassArgs &a, int grid);
 int launch_rescore(Ctx *c, hipStream_t s, const RescoreArgs &a);
 int scan_grid_for(const Ctx *c, int64_t n_rows, int nq, bool q64);
 bool scan_q64(const Ctx *c, int nq, bool long_scan);
@@ -469,7 +458,7 @@ struct ScanReceipt {
 int enqueue_scan_merge(Ctx *c, const ScanRequest &rq, ScanReceipt *rcpt = nullptr);
 // "This tick's merge stays on the scan's stream", from facts (enqueue_scan_merge and, on a ctx without streams, chip_debug_scan_plan)
 bool tick_merge_on_scan_stream(const Ctx *c, bool tick, bool short_scan, bool second_tick_stream, bool caller_accepts);
-template <class Args> inline void scan_args_db(const Ctx *c, Args *a)   // the segment-table / D part of a ScanArgs / MultiScanArgs
+template <class Args> inline void scan_args_db(const Ctx *c, Args *a)   // the segment-table / D part of a ScanArgs / PassArgs
 {
     a->seg_table = c->seg_table_dev; a->seg_shift = c->seg_shift; a->seg_mask = c->seg_rows - 1; a->D = c->D;
 }

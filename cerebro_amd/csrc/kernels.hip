@@ -16,6 +16,7 @@
 #include "chip_internal.h"
 #include "topk_merge.h"
 #include <cmath>
+#include <type_traits>
 
 namespace chip {
 
@@ -307,54 +308,102 @@ __global__ __launch_bounds__(1024) void db_scan_topk(ScanArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------ K1, several ticks per pass
-// db_scan_topk_multi<T>: ONE pass over rows [0, max k_t) answers T queued ticks of 3 queries each (chip_api.hip coalesce_*): the
-// pass is as HBM-bound as a one-tick launch, so T ticks cost one DB read.  Float rows of whole 4 KiB batches, plain ctx.
-//   * same bits: per (row, query) exactly rows_dot's order -- lane L accumulates elements j*256 + 4L + c (j ascending, c = 0..3)
-//     into one fp64 accumulator by fma, then the xor butterfly's pairing tree (formed transposed for the four rows of a group at
-//     once, on gfx950's lane swaps: see the reduction below); the queries sit in LDS as fp32 ([3T][D], 144 KiB at T = 3,
-//     D = 4096) and are converted at use (fp32 x fp32 is exact in fp64 wherever the conversion happens);
-//   * register blocking: R = 4 rows per wave in flight, U = 4 KiB of each per batch (16 KiB per wave, one workgroup of 8 waves per
-//     CU), every query vector read (ds_read_b128) and converted ONCE per 4 rows: per row vector and lane 4 row conversions +
-//     3T x (1 conversion + 4 fma) = 49 VALU instructions at T = 3 against 16 (4 + 12) for one tick in db_scan_topk;
+// ONE pass over rows [0, max k_t) answers T queued ticks of 3 queries each (chip_api.hip coalesce_*): the pass is as HBM-bound as a
+// one-tick launch, so T ticks cost one DB read.  Three kernels, ONE skeleton (shared_pass below) and one arithmetic policy each:
+//   db_scan_topk_multi<T>     float rows,  T = 2, 3, fp64 arithmetic (PassF64<float, T, 0>): every query staged in LDS;
+//   db_scan_shared_f64<T, NG> double rows, T = 2,    fp64 arithmetic (PassF64<double, T, NG>): NG queries read in place;
+//   db_scan_prefilter<NG>     float rows,  T = 4,    fp32 arithmetic (PassF32<NG>): candidates for tick_rescore, NG queries in place.
+// What the skeleton owns, whatever the arithmetic:
+//   * register blocking: R = 4 rows per wave in flight, U = 4 KiB of each per batch (16 KiB per wave, one workgroup of 8 waves per CU),
+//     rows of whole 4 KiB batches, plain ctx;
+//   * queries: the first NS = 3T - NG staged in LDS in the rows' type ([NS][D]), read by ds_read_b128 two vectors ahead of their use;
+//     the last NG (those the LDS does not hold) read IN PLACE from global memory: every wave of the launch reads the same bytes, so they
+//     come out of the L2.  Vector loads return in order and share vmcnt with the row stream, so an in-place query vector is one more
+//     slot OF that stream: the stream of a wave is r0 r1 r2 r3 g0 .. g(NG-1) per KiB, L = 4 (4 + NG) loads in flight;
 //   * per-tick prefix: a row is offered to tick t's lists only if row < k_t (wave-uniform compare); the running lists sit in LDS
 //     behind the queries ([wave][3T][K] entries), the admission thresholds in SGPRs; one vector compare per query tells whether any
 //     row of a group can enter a list at all, and the offers of such a group are walked list by list;
 //   * output [tick][workgroup][3][K]: the merge + decision kernel runs unchanged, once per tick, on its own block of lists.
 constexpr int kMultiR = 4, kMultiU = 4, kMultiBlock = 512;
 
-// The R x U = 16 load slots of a wave (1 KiB each) are PHYSICAL registers v[kMultiVgprBase ..] that the compiler does not own, as in
-// db_scan_topk_rows below (same reason, same technique: amdgpu_num_vgpr leaves the top of the file to the asm statements, which name
-// their targets literally and convert out of them in the statement that waits; tests/test_codeobj_multi.py checks the partition).
+// The load slots of a wave (1 KiB each) are PHYSICAL registers that the compiler does not own, as in db_scan_topk_rows below (same
+// reason, same technique: amdgpu_num_vgpr leaves the top of the file to the asm statements, which name their targets literally;
+// tests/test_codeobj_multi.py, test_codeobj_shared_f64.py check the partition).  One map for all three kernels:
+//   rows   : slot (u, rr), KiB u of the batch of row rr      -> v[192 + 4 (4 u + rr) ..]: v[192..255];
+//   queries: slot (u, g),  KiB u of the batch of in-place g  -> v[192 - 16 NG + 4 (NG u + g) ..], right below the row slots.
+// A kernel's attribute takes no template argument, so the compiler's share is what the widest instantiation of the kernel leaves.
 constexpr int kMultiVgprBase = 192;
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "db_scan_topk_multi names physical VGPRs: gfx950 (MI355X) only -- build with --offload-arch=gfx950"
+#error "the shared-pass kernels name physical VGPRs: gfx950 (MI355X) only -- build with --offload-arch=gfx950"
 #endif
-#define CHIP_MULTI_CLOBBERS                                                                                                             \
+#define CHIP_PASS_SLOTS_192_255                                                                                                         \
     "v192", "v193", "v194", "v195", "v196", "v197", "v198", "v199", "v200", "v201", "v202", "v203", "v204", "v205", "v206", "v207",     \
     "v208", "v209", "v210", "v211", "v212", "v213", "v214", "v215", "v216", "v217", "v218", "v219", "v220", "v221", "v222", "v223",     \
     "v224", "v225", "v226", "v227", "v228", "v229", "v230", "v231", "v232", "v233", "v234", "v235", "v236", "v237", "v238", "v239",     \
     "v240", "v241", "v242", "v243", "v244", "v245", "v246", "v247", "v248", "v249", "v250", "v251", "v252", "v253", "v254", "v255"
-// slot (u, rr): KiB u of the batch of row rr -> v[reg : reg + 3]
-__host__ __device__ constexpr int multi_slot_reg(int u, int rr) { return kMultiVgprBase + 4 * (u * kMultiR + rr); }
+#define CHIP_PASS_SLOTS_160_191                                                                                                         \
+    "v160", "v161", "v162", "v163", "v164", "v165", "v166", "v167", "v168", "v169", "v170", "v171", "v172", "v173", "v174", "v175",     \
+    "v176", "v177", "v178", "v179", "v180", "v181", "v182", "v183", "v184", "v185", "v186", "v187", "v188", "v189", "v190", "v191"
+#define CHIP_PASS_SLOTS_144_159                                                                                                         \
+    "v144", "v145", "v146", "v147", "v148", "v149", "v150", "v151", "v152", "v153", "v154", "v155", "v156", "v157", "v158", "v159"
+__host__ __device__ constexpr int pass_row_slot(int u, int rr) { return kMultiVgprBase + 4 * (u * kMultiR + rr); }
+__host__ __device__ constexpr int pass_query_slot(int ng, int u, int g) { return kMultiVgprBase - 4 * kMultiU * ng + 4 * (u * ng + g); }
+__host__ __device__ constexpr int pass_vgpr_base(int max_ng) { return kMultiVgprBase - 4 * kMultiU * max_ng; }   // what the compiler owns
 
-// 1 KiB of a row (16 bytes per lane) into a slot: wave-uniform row base in an SGPR pair, one shared 32-bit lane offset
-template <int REG, int OFF>
-__device__ __forceinline__ void multi_issue(uint32_t voff, const float *row_uniform)
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose counter names registers (template arguments of the asm statements)
+template <int N, int I = 0, class F>
+__device__ __forceinline__ void static_for(F &&f)
 {
-    asm volatile("global_load_dwordx4 v[%2:%3], %0, %1 offset:%4 nt" ::"v"(voff), "s"(row_uniform), "n"(REG), "n"(REG + 3), "n"(OFF) : "memory");
+    if constexpr (I < N) {
+        f(std::integral_constant<int, I>{});
+        static_for<N, I + 1>(f);
+    }
 }
-// wait until at most CNT row loads are outstanding (they return in order), then hand the slot's four elements to the compiler as fp64:
-// once this statement has been issued the slot may be loaded again
+#define CHIP_INLINE_LAMBDA __attribute__((always_inline))
+
+// 1 KiB (16 bytes per lane) into a slot: wave-uniform base in an SGPR pair, one shared 32-bit lane offset; rows non-temporal (read once),
+// in-place queries cached (every wave reads them)
+template <int REG, int OFF, bool NTL>
+__device__ __forceinline__ void slot_issue(uint32_t voff, const void *base_uniform)
+{
+    if constexpr (NTL)
+        asm volatile("global_load_dwordx4 v[%2:%3], %0, %1 offset:%4 nt" ::"v"(voff), "s"(base_uniform), "n"(REG), "n"(REG + 3), "n"(OFF) : "memory");
+    else
+        asm volatile("global_load_dwordx4 v[%2:%3], %0, %1 offset:%4" ::"v"(voff), "s"(base_uniform), "n"(REG), "n"(REG + 3), "n"(OFF) : "memory");
+}
+// KiB U_ of a batch, in the stream's order: the four row slots, then the NG query slots
+template <int U_, int NG, typename T>
+__device__ __forceinline__ void slots_issue_kib(uint32_t voff, const T *const (&row)[kMultiR], const T *const (&qg)[NG > 0 ? NG : 1])
+{
+    static_for<kMultiR>([&](auto rr) CHIP_INLINE_LAMBDA { slot_issue<pass_row_slot(U_, rr), U_ * 1024, true>(voff, row[rr]); });
+    static_for<NG>([&](auto g) CHIP_INLINE_LAMBDA { slot_issue<pass_query_slot(NG, U_, g), U_ * 1024, false>(voff, qg[g]); });
+}
+// wait until at most CNT loads of the stream are outstanding (they return in order) ...
+template <int CNT>
+__device__ __forceinline__ void slot_wait()
+{
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CNT) : "memory");
+}
+// ... and hand the slot's elements to the compiler as fp64 in the same statement: once it has been issued the slot may be loaded again.
+// Four floats are converted (fp32 x fp32 is exact in fp64 wherever the conversion happens), two doubles are copied out.
 template <int REG, int CNT>
-__device__ __forceinline__ void multi_take(double (&d)[4])
+__device__ __forceinline__ void slot_take(double (&d)[4])
 {
     asm volatile("s_waitcnt vmcnt(%4)\n\tv_cvt_f64_f32 %0, v[%5]\n\tv_cvt_f64_f32 %1, v[%6]\n\tv_cvt_f64_f32 %2, v[%7]\n\tv_cvt_f64_f32 %3, v[%8]"
                  : "=v"(d[0]), "=v"(d[1]), "=v"(d[2]), "=v"(d[3])
                  : "n"(CNT), "n"(REG), "n"(REG + 1), "n"(REG + 2), "n"(REG + 3)
                  : "memory");
 }
+template <int REG, int CNT>
+__device__ __forceinline__ void slot_take(double (&d)[2])
+{
+    asm volatile("s_waitcnt vmcnt(%2)\n\tv_mov_b64 %0, v[%3:%4]\n\tv_mov_b64 %1, v[%5:%6]"
+                 : "=&v"(d[0]), "=&v"(d[1])
+                 : "n"(CNT), "n"(REG), "n"(REG + 1), "n"(REG + 2), "n"(REG + 3)
+                 : "memory");
+}
 
-// The running top-K lists of the multi-tick and the row-batched kernels live in LDS behind the staged queries, only the admission
+// The running top-K lists of the shared-pass and the row-batched kernels live in LDS behind the staged queries, only the admission
 // threshold (the K-th entry) stays in SGPRs: after warm-up an offer is rare, and lists held in VGPRs (as in db_scan_topk) would cost
 // 4 NQ registers of kernels that keep 16 load slots per wave in flight.
 __device__ __forceinline__ void wave_topk_offer_lds(double s, int64_t gi, int K, int lane, chip_topk_entry *list, double &thr_s, int64_t &thr_i)
@@ -376,534 +425,89 @@ __device__ __forceinline__ void wave_topk_offer_lds(double s, int64_t gi, int K,
     }
 }
 
-// the value of the lane that the DPP control CTRL pairs this lane with (all lanes active).  The controls used here (row_ror, quad_perm)
-// read a valid lane for every lane, so the `old` operand never shows: bound_ctrl saves the compiler the move that would fill it in.
+// Lane exchanges of the transposed reduction, on a double (both dwords) or a float.  dpp: the value of the lane that the DPP control
+// CTRL pairs this lane with (all lanes active).  The controls used here (row_ror, quad_perm) read a valid lane for every lane, so the
+// `old` operand never shows: bound_ctrl saves the compiler the move that would fill it in.
 template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v)
+__device__ __forceinline__ float dpp(float v)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+}
+template <int CTRL>
+__device__ __forceinline__ double dpp(double v)
 {
     const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, true);
     const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, true);
     return __hiloint2double(hi, lo);
 }
-
-// gfx950's half exchanges on both dwords of a pair of doubles.  swap32: lanes 32-63 of a change places with lanes 0-31 of b;
-// swap16: the odd 16-lane rows of a with the even rows of b.  (Builtins: the compiler places the wait states a VALU write of an operand needs.)
-__device__ __forceinline__ void swap32_f64(double &a, double &b)
+// gfx950's half exchanges.  WIDTH 32: lanes 32-63 of a change places with lanes 0-31 of b; WIDTH 16: the odd 16-lane rows of a with the
+// even rows of b.  (Builtins: the compiler places the wait states a VALU write of an operand needs.)
+template <int WIDTH>
+__device__ __forceinline__ void lane_swap(unsigned &a, unsigned &b)
 {
-    const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
-    const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
-    a = __hiloint2double((int)hi[0], (int)lo[0]);
-    b = __hiloint2double((int)hi[1], (int)lo[1]);
+    static_assert(WIDTH == 32 || WIDTH == 16, "v_permlane32_swap / v_permlane16_swap");
+    if constexpr (WIDTH == 32) {
+        const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
+        a = r[0];
+        b = r[1];
+    } else {
+        const auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
+        a = r[0];
+        b = r[1];
+    }
 }
-__device__ __forceinline__ void swap16_f64(double &a, double &b)
+template <int WIDTH>
+__device__ __forceinline__ void lane_swap(float &a, float &b)
 {
-    const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
-    const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
-    a = __hiloint2double((int)hi[0], (int)lo[0]);
-    b = __hiloint2double((int)hi[1], (int)lo[1]);
+    unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
+    lane_swap<WIDTH>(ua, ub);
+    a = __uint_as_float(ua);
+    b = __uint_as_float(ub);
+}
+template <int WIDTH>
+__device__ __forceinline__ void lane_swap(double &a, double &b)
+{
+    unsigned la = (unsigned)__double2loint(a), lb = (unsigned)__double2loint(b), ha = (unsigned)__double2hiint(a), hb = (unsigned)__double2hiint(b);
+    lane_swap<WIDTH>(la, lb);
+    lane_swap<WIDTH>(ha, hb);
+    a = __hiloint2double((int)ha, (int)la);
+    b = __hiloint2double((int)hb, (int)lb);
+}
+__device__ __forceinline__ double lane_value(double v, int l) { return readlane_f64(v, l); }
+__device__ __forceinline__ float lane_value(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+
+// The lane sums a0 .. a3 of four rows against one query -> one register whose 16-lane row k holds, in all 16 lanes, the sum of data row k.
+// Per row the xor butterfly's pairing tree (m = 32, 16, 8, 4, 2, 1: lane l with lane l ^ m) is computed TRANSPOSED, each row's tree in a
+// quarter of the lanes, without LDS:
+//   step 32: swap32(rows 0, 2), one addition: lanes 0-31 hold row 0's a[l] + a[l ^ 32], lanes 32-63 row 2's; likewise rows 1, 3;
+//   step 16: swap16 of the two results, one addition: 16-lane row k holds the sums of data row k after steps 32 and 16;
+//   steps 8, 4, 2, 1 stay inside a 16-lane row and take the partner's value by DPP: row_ror:8 IS lane ^ 8; after step 8 a value
+//     depends on lane & 7 only, so row_ror:4 delivers the bits of lane ^ 4, and the quad permutations are lane ^ 2 and lane ^ 1.
+// The same pairs as butterfly_sum, and a + b == b + a: all 16 lanes of row k end with the bits lane 0 of the full tree holds.
+template <typename S>
+__device__ __forceinline__ S reduce_rows4(S a0, S a1, S a2, S a3)
+{
+    static_assert(kMultiR == 4, "the transposed reduction folds four rows into the four 16-lane rows of a wave");
+    lane_swap<32>(a0, a2);
+    lane_swap<32>(a1, a3);
+    S p02 = a0 + a2, p13 = a1 + a3;
+    lane_swap<16>(p02, p13);
+    S v = p02 + p13;
+    v = v + dpp<0x128>(v);
+    v = v + dpp<0x124>(v);
+    v = v + dpp<0x4E>(v);
+    v = v + dpp<0xB1>(v);
+    return v;
 }
 
-// Admission of a row to one running list of the multi-tick kernel.  The score comes in SGPRs (all 16 lanes of the row's share of the wave hold the same bits
-// after the reduction), so the compare is a scalar branch and the threshold stays in SGPRs.  A wave meets its rows in ascending order, so gi is
+// Admission of a row to one running list of a shared pass; S is the type of score and threshold (the list entry is a double either way:
+// a float widens exactly).  The score comes in SGPRs (all 16 lanes of the row's share of the wave hold the same bits after the
+// reduction), so the compare is a scalar branch and the threshold stays in SGPRs.  A wave meets its rows in ascending order, so gi is
 // larger than every index already in its lists and key_gt(s, gi, thr_s, thr_i) is just s >= thr_s (false for NaN, which never
 // enters): the K-th index need not be kept.  The list's LDS address is formed inside the branch (hoisted out of the scan loop, the
 // 3T x 2 addresses would be held in registers for an insertion that is rare after the first rows).
-__device__ __forceinline__ void multi_offer(double s_uniform, int64_t gi, int K, int lane, chip_topk_entry *list, double &thr_s)
-{
-    if (s_uniform >= thr_s) {
-        asm volatile("" : "+v"(lane));
-        chip_topk_entry me, up;
-        me.score = -INFINITY; me.idx = -1; up = me;
-        if (lane < K) { me = list[lane]; if (lane > 0) up = list[lane - 1]; }
-        const bool worse = key_gt(s_uniform, gi, me.score, me.idx);
-        const unsigned long long m = __ballot(worse) & ((1ull << K) - 1ull);
-        const int pos = __builtin_ctzll(m);
-        if (lane < K) {
-            if (lane > pos) me = up;
-            else if (lane == pos) { me.score = s_uniform; me.idx = gi; }
-            list[lane] = me;      // every read of the old list precedes this write in program order (one wave, in-order LDS)
-        }
-        thr_s = readlane_f64(me.score, K - 1);
-    }
-}
-
-template <int NTICKS>
-__global__ __launch_bounds__(kMultiBlock) __attribute__((amdgpu_num_vgpr(kMultiVgprBase / 2))) void db_scan_topk_multi(MultiScanArgs a)
-{
-    constexpr int NQ = 3 * NTICKS, R = kMultiR, U = kMultiU;
-    static_assert(kMultiVgprBase + 4 * R * U <= 256, "load slots beyond the register file of an 8-wave workgroup");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    asm volatile("" ::: CHIP_MULTI_CLOBBERS);                       // makes the code object allocate the asm-owned registers
-    float *qs = reinterpret_cast<float *>(smem);  // [NQ][D]
-    const int D = a.D;
-    const int K = a.K;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wpb = blockDim.x >> 6;
-
-    for (int e = tid * 4; e < D; e += blockDim.x * 4) {   // all 3T loads of a lane in flight together (L2-resident after the first workgroup)
-        f32x4 w[NQ];
-#pragma unroll
-        for (int q = 0; q < NQ; q++) w[q] = *as_global(reinterpret_cast<const f32x4 *>(static_cast<const float *>(a.q[q]) + e));
-#pragma unroll
-        for (int q = 0; q < NQ; q++) *reinterpret_cast<f32x4 *>(qs + q * D + e) = w[q];
-    }
-    __syncthreads();
-
-    // running top-K lists: LDS behind the queries, [wave][3T][K] (this wave's lists are touched by this wave only until the merge)
-    chip_topk_entry *lists = reinterpret_cast<chip_topk_entry *>(smem + (size_t)NQ * D * sizeof(float));
-    chip_topk_entry *mylists = lists + (size_t)wave * NQ * K;
-    double thr_s[NQ];   // score of the K-th entry of each list (SGPRs)
-#pragma unroll
-    for (int q = 0; q < NQ; q++) {
-        thr_s[q] = -INFINITY;
-        if (lane < K) { chip_topk_entry t; t.score = -INFINITY; t.idx = -1; mylists[q * K + lane] = t; }
-    }
-
-    // Row -> wave map: as db_scan_topk (wave g owns rows g, g + tw, ...), four consecutive rows of that sequence (a GROUP) at a time --
-    // all waves together read one window of 4 tw consecutive rows that slides through the DB.  A row of a group that falls beyond the
-    // pass is replaced by the wave's first row (in bounds, never offered).
-    //
-    // The wave walks the (group, 4 KiB batch) sequence of its rows as ONE stream: slot (u, rr) is loaded again -- for the next batch of
-    // the group, or the first batch of the next group -- in the statement after the one that converted its contents, so 15-16 KiB per
-    // wave are in flight through the arithmetic, through the butterflies and through the offers, and every wait is vmcnt(15).
-    // Nothing is ever loaded from outside rows [0, n_rows): every base comes from row_of() below, i.e. from a row < n_rows through
-    // the segment table, and every offset is below one row's length.
-    const int64_t tw = (int64_t)gridDim.x * wpb;
-    const int64_t rbase = (int64_t)blockIdx.x * wpb + wave;
-    const int nb = D / (256 * U);                                                             // batches per row
-    const int ngroups = rbase < a.n_rows ? (int)((a.n_rows - 1 - rbase) / (R * tw)) + 1 : 0;  // groups of this wave (wave-uniform)
-    const int total = ngroups * nb;
-    const uint32_t lane_off = (uint32_t)lane * 16u;
-    const int e0 = lane * 4;
-    auto row_of = [&](int group, int rr) {
-        const int64_t r = rbase + ((int64_t)group * R + rr) * tw;
-        return uniform_ptr(row_base_uniform<float>(a, r < a.n_rows ? r : rbase));
-    };
-    const float *row[R], *nrow[R];   // bases the NEXT loads read from, and those of the group after (looked up one group ahead; SGPRs)
-    if (total > 0) {
-#pragma unroll
-        for (int rr = 0; rr < R; rr++) { row[rr] = row_of(0, rr); nrow[rr] = row[rr]; }
-        if (ngroups > 1) {
-#pragma unroll
-            for (int rr = 0; rr < R; rr++) nrow[rr] = row_of(1, rr);
-        }
-#define CHIP_MULTI_ISSUE_ROW(u, rr, voff) multi_issue<multi_slot_reg(u, rr), (u) * 1024>(voff, row[rr])
-#define CHIP_MULTI_ISSUE_SLOT(u, voff) do { CHIP_MULTI_ISSUE_ROW(u, 0, voff); CHIP_MULTI_ISSUE_ROW(u, 1, voff); CHIP_MULTI_ISSUE_ROW(u, 2, voff); CHIP_MULTI_ISSUE_ROW(u, 3, voff); } while (0)
-        CHIP_MULTI_ISSUE_SLOT(0, lane_off); CHIP_MULTI_ISSUE_SLOT(1, lane_off); CHIP_MULTI_ISSUE_SLOT(2, lane_off); CHIP_MULTI_ISSUE_SLOT(3, lane_off);
-    }
-
-    double acc[R][NQ];
-#pragma unroll
-    for (int rr = 0; rr < R; rr++)
-#pragma unroll
-        for (int q = 0; q < NQ; q++) acc[rr][q] = 0.0;
-
-    // One batch per iteration.  Per KiB u: each row's slot is taken (converted) and loaded again at byte offset noff of row[]; then the
-    // 3T query vectors, each read from LDS two vectors ahead of its use (counted lgkmcnt waits), converted once and multiplied into
-    // the four rows.  Per (row, query): j ascending, c = 0..3 -- rows_dot's order.  What the slots load next: the next batch of the
-    // group; at the group's last batch the first batch of the wave's next group; at the wave's last batch the first KiBs of the rows
-    // it has just read once more (in bounds, taken by nobody), so that one loop body and one wait count serve the whole stream.
-    int b = 0, group = 0;
-    for (int t = 0; t < total; t++) {
-        const int base = b * (256 * U);
-        uint32_t noff = (uint32_t)(base + 256 * U) * 4u;
-        if (b + 1 == nb) {
-            noff = 0;
-            if (group + 1 < ngroups) {   // the slots start on the next group; its successor's bases are looked up for the boundary after
-#pragma unroll
-                for (int rr = 0; rr < R; rr++) row[rr] = nrow[rr];
-                if (group + 2 < ngroups) {
-#pragma unroll
-                    for (int rr = 0; rr < R; rr++) nrow[rr] = row_of(group + 2, rr);
-                }
-            }
-        }
-        {
-            constexpr int S = U * NQ;
-            const float *qv = qs + base + e0;
-            const uint32_t voff = noff + lane_off;
-            f32x4 w[S];
-            w[0] = *reinterpret_cast<const f32x4 *>(qv);
-            w[1] = *reinterpret_cast<const f32x4 *>(qv + D);
-            double x[R][4];
-#pragma unroll
-            for (int s = 0; s < S; s++) {
-                const int u = s / NQ, q = s % NQ;
-                if (q == 0) {
-#define CHIP_MULTI_TAKE_ROW(uu, rr) if (u == uu) { multi_take<multi_slot_reg(uu, rr), R * U - 1>(x[rr]); CHIP_MULTI_ISSUE_ROW(uu, rr, voff); }
-#define CHIP_MULTI_TAKE_SLOT(uu) CHIP_MULTI_TAKE_ROW(uu, 0) CHIP_MULTI_TAKE_ROW(uu, 1) CHIP_MULTI_TAKE_ROW(uu, 2) CHIP_MULTI_TAKE_ROW(uu, 3)
-                    CHIP_MULTI_TAKE_SLOT(0) CHIP_MULTI_TAKE_SLOT(1) CHIP_MULTI_TAKE_SLOT(2) CHIP_MULTI_TAKE_SLOT(3)
-#undef CHIP_MULTI_TAKE_SLOT
-#undef CHIP_MULTI_TAKE_ROW
-                }
-                if (s + 2 < S) w[s + 2] = *reinterpret_cast<const f32x4 *>(qv + ((s + 2) % NQ) * D + ((s + 2) / NQ) * 256);
-#pragma unroll
-                for (int c = 0; c < 4; c++) {
-                    const double wd = (double)w[s][c];
-#pragma unroll
-                    for (int rr = 0; rr < R; rr++) acc[rr][q] = __builtin_fma(wd, x[rr][c], acc[rr][q]);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        if (++b == nb) {
-            // The rows of this group are complete: R x 3T lane sums, all in one basic block ahead of the offers' branches.  Per query the
-            // xor butterfly's pairing tree (m = 32, 16, 8, 4, 2, 1: lane l with lane l ^ m) is computed TRANSPOSED, each row's tree in a
-            // quarter of the lanes, without LDS:
-            //   step 32: swap32(rows 0, 2), one addition: lanes 0-31 hold row 0's a[l] + a[l ^ 32], lanes 32-63 row 2's; likewise rows 1, 3;
-            //   step 16: swap16 of the two results, one addition: 16-lane row k of s[q] holds the sums of data row k after steps 32 and 16;
-            //   steps 8, 4, 2, 1 stay inside a 16-lane row and take the partner's value by DPP: row_ror:8 IS lane ^ 8; after step 8 a value
-            //     depends on lane & 7 only, so row_ror:4 delivers the bits of lane ^ 4, and the quad permutations are lane ^ 2 and lane ^ 1.
-            // The same pairs as butterfly_sum, and a + b == b + a: all 16 lanes of row k end with the bits lane 0 of the full tree holds.
-            static_assert(R == 4, "the transposed reduction folds four rows into the four 16-lane rows of a wave");
-            double s[NQ];
-#pragma unroll
-            for (int q = 0; q < NQ; q++) {
-                swap32_f64(acc[0][q], acc[2][q]);
-                swap32_f64(acc[1][q], acc[3][q]);
-                double p02 = acc[0][q] + acc[2][q], p13 = acc[1][q] + acc[3][q];
-                swap16_f64(p02, p13);
-                double v = p02 + p13;
-                v = v + dpp_f64<0x128>(v);
-                v = v + dpp_f64<0x124>(v);
-                v = v + dpp_f64<0x4E>(v);
-                v = v + dpp_f64<0xB1>(v);
-                s[q] = v;
-            }
-            // Offers.  One vector compare per query first: s[q] holds the four rows' scores against query q, and a threshold only rises
-            // while the group is offered, so a score that the loop below would admit is >= the threshold the group starts with (NaN on
-            // neither side).  No lane set: nothing of this group enters any list.  Otherwise each list is offered its rows one by one, in
-            // order, each against the threshold as it stands then.  (A lane may be set by a row some tick must not see, or by the stand-in
-            // of a row beyond the pass: that costs the walk below, which tests both, and nothing else.)
-            unsigned long long hit = 0;
-#pragma unroll
-            for (int q = 0; q < NQ; q++) hit |= __ballot(s[q] >= thr_s[q]);
-            if (hit) {
-                // The lists are independent of one another; only the rows offered to ONE list must come in ascending order.  So the walk goes
-                // query first: the query's own compare once more (one vector instruction; nine masks kept from the pre-check do not fit
-                // the SGPRs), and a query none of whose four scores reaches its threshold is stepped over as a whole.  thr_s[q] changes
-                // only inside q's own turn, so the compare is still against the threshold the group started with.  The empty asm below is
-                // what makes it a second compare: without it the compiler reuses the pre-check's nine masks, keeps them live across the
-                // walk and spills SGPRs, which tests/test_codeobj_multi.py refuses.
-#pragma unroll
-                for (int q = 0; q < NQ; q++) {
-                    asm volatile("" : "+v"(s[q]));   // a value the pre-check has not seen: the compare is made again, not kept
-                    if (__ballot(s[q] >= thr_s[q])) {
-#pragma unroll
-                        for (int rr = 0; rr < R; rr++) {
-                            const int64_t r = rbase + ((int64_t)group * R + rr) * tw;
-                            if (r < a.n_rows && r < a.k[q / 3]) multi_offer(readlane_f64(s[q], 16 * rr), r, K, lane, mylists + q * K, thr_s[q]);
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int rr = 0; rr < R; rr++)
-#pragma unroll
-                for (int q = 0; q < NQ; q++) acc[rr][q] = 0.0;
-            b = 0;
-            group++;
-        }
-    }
-#undef CHIP_MULTI_ISSUE_SLOT
-#undef CHIP_MULTI_ISSUE_ROW
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the read-ahead of the wave's last batch
-
-    block_merge_cand<NQ>(lists, K, lane, wave, wpb,
-                         [&](int q) { return a.partial + (((int64_t)(q / 3) * gridDim.x + blockIdx.x) * 3 + q % 3) * K; });
-}
-
-// ------------------------------------------------------------------------------------------------ K1, several ticks per pass, double rows
-// db_scan_shared_f64<T, NG>: the shared pass for DOUBLE rows (ReljaNetVLAD: 32 KiB rows at D = 4096, twice the bytes of a float tick).  Blocking,
-// row -> wave map, load slots, lists, thresholds and output are db_scan_topk_multi's; a 1 KiB slot holds 2 doubles per lane, a batch 512 elements.
-//   * same bits: lane L accumulates elements j*128 + 2L + c (j ascending, c = 0, 1) by fma into one fp64 accumulator -- rows_dot<double>'s order,
-//     the oracle's orc_dot_tree_f64 -- then the same transposed pairing tree as the float kernel;
-//   * no conversion: the statement that waits for a slot copies it out (2 x v_mov_b64) and the slot is loaded again in the next statement;
-//   * the 3T fp64 queries do not fit the LDS (T x 96 KiB at D = 4096).  The first NS = 3T - NG are staged ([NS][D] doubles, ds_read_b128, read two
-//     vectors ahead); the last NG are read IN PLACE from global memory, as db_scan_topk_wide does: every wave of the launch reads the same bytes, so
-//     they come out of the L2, in the same per-lane element order, hence the same bits.  Vector loads return in order and share vmcnt with the row
-//     stream, so an in-place query vector is one more slot OF that stream: its 1 KiB for (batch, KiB u) sits in asm-owned registers below the row
-//     slots (v[192 - 16 NG ..]), is issued right behind the four row slots of the same (batch, u) -- one batch ahead of its use, like them -- and
-//     is loaded again in the statement after the one that copied it out.  The stream of a wave is r0 r1 r2 r3 g0 .. g(NG-1) per KiB, L = 4 (4 + NG)
-//     loads in flight, and EVERY wait of the loop is vmcnt(L - 1): the load waited for is always the oldest one.
-// Registers: the compiler owns v[0 .. 160): acc[4][3T] (48 at T = 2) + the 16 of a row KiB + 4 of a query vector + 12 of the LDS read-ahead.
-// T = 3 needs NG = 5 at D = 4096: 80 registers of query slots leave the compiler v[0 .. 112) for 72 of accumulators and everything else.  Compiled
-// that way the kernel spills 90 registers (560 bytes of scratch per lane); a scratch access drains the stream, so it is dropped (kSharedF64MaxTicks).
-constexpr int kSharedMaxNG = 2;          // in-place queries of the instantiations that are built: D <= 4608 at T = 2
-constexpr int kSharedF64MaxTicks = 2;
-constexpr int kSharedVgprBase = kMultiVgprBase - 4 * kMultiU * kSharedMaxNG;   // 160: what the compiler owns in every instantiation (the attribute takes no template argument)
-__host__ __device__ constexpr int shared_qslot_base(int ng) { return kMultiVgprBase - 4 * kMultiU * ng; }
-// KiB u of the batch of in-place query g -> v[reg : reg + 3]
-__host__ __device__ constexpr int shared_qslot_reg(int ng, int u, int g) { return shared_qslot_base(ng) + 4 * (u * ng + g); }
-
-// 1 KiB (16 bytes per lane) into a slot: rows non-temporal (read once), in-place queries cached (every wave reads them)
-template <int REG, int OFF, bool NTL>
-__device__ __forceinline__ void shared_issue(uint32_t voff, const double *base_uniform)
-{
-    if constexpr (NTL)
-        asm volatile("global_load_dwordx4 v[%2:%3], %0, %1 offset:%4 nt" ::"v"(voff), "s"(base_uniform), "n"(REG), "n"(REG + 3), "n"(OFF) : "memory");
-    else
-        asm volatile("global_load_dwordx4 v[%2:%3], %0, %1 offset:%4" ::"v"(voff), "s"(base_uniform), "n"(REG), "n"(REG + 3), "n"(OFF) : "memory");
-}
-// wait until at most CNT loads of the stream are outstanding, then hand the slot's two doubles to the compiler: the slot may be loaded again
-template <int REG, int CNT>
-__device__ __forceinline__ void shared_take(double (&d)[2])
-{
-    asm volatile("s_waitcnt vmcnt(%2)\n\tv_mov_b64 %0, v[%3:%4]\n\tv_mov_b64 %1, v[%5:%6]"
-                 : "=&v"(d[0]), "=&v"(d[1])
-                 : "n"(CNT), "n"(REG), "n"(REG + 1), "n"(REG + 2), "n"(REG + 3)
-                 : "memory");
-}
-
-template <int NTICKS, int NG>
-__global__ __launch_bounds__(kMultiBlock) __attribute__((amdgpu_num_vgpr(kSharedVgprBase / 2))) void db_scan_shared_f64(MultiScanArgs a)
-{
-    constexpr int NQ = 3 * NTICKS, NS = NQ - NG, R = kMultiR, U = kMultiU;
-    constexpr int L = U * (R + NG);        // loads of the stream in flight
-    static_assert(NG >= 0 && NG <= kSharedMaxNG && NS >= 2 && L <= 64, "at least two staged queries (the LDS read-ahead), vmcnt counts to 63");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    asm volatile("" ::: CHIP_MULTI_CLOBBERS);                       // makes the code object allocate the asm-owned registers
-    double *qs = reinterpret_cast<double *>(smem);  // [NS][D]
-    const int D = a.D;
-    const int K = a.K;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wpb = blockDim.x >> 6;
-
-    for (int e = tid * 2; e < D; e += blockDim.x * 2) {
-        f64x2 w[NS];
-#pragma unroll
-        for (int q = 0; q < NS; q++) w[q] = *as_global(reinterpret_cast<const f64x2 *>(static_cast<const double *>(a.q[q]) + e));
-#pragma unroll
-        for (int q = 0; q < NS; q++) *reinterpret_cast<f64x2 *>(qs + q * D + e) = w[q];
-    }
-    __syncthreads();
-    const double *qg[NG > 0 ? NG : 1];   // the queries read in place (SGPRs)
-#pragma unroll
-    for (int g = 0; g < NG; g++) qg[g] = uniform_ptr(static_cast<const double *>(a.q[NS + g]));
-
-    chip_topk_entry *lists = reinterpret_cast<chip_topk_entry *>(smem + (size_t)NS * D * sizeof(double));   // [wave][3T][K], as db_scan_topk_multi
-    chip_topk_entry *mylists = lists + (size_t)wave * NQ * K;
-    double thr_s[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; q++) {
-        thr_s[q] = -INFINITY;
-        if (lane < K) { chip_topk_entry t; t.score = -INFINITY; t.idx = -1; mylists[q * K + lane] = t; }
-    }
-
-    // The (group, batch) walk of db_scan_topk_multi.  Nothing is loaded from outside rows [0, n_rows) and the NG query vectors: every row base comes
-    // from row_of(), every offset (rows and queries alike: both are D doubles) is below one row's length.
-    const int64_t tw = (int64_t)gridDim.x * wpb;
-    const int64_t rbase = (int64_t)blockIdx.x * wpb + wave;
-    const int nb = D / (128 * U);
-    const int ngroups = rbase < a.n_rows ? (int)((a.n_rows - 1 - rbase) / (R * tw)) + 1 : 0;
-    const int total = ngroups * nb;
-    const uint32_t lane_off = (uint32_t)lane * 16u;
-    const int e0 = lane * 2;
-    auto row_of = [&](int group, int rr) {
-        const int64_t r = rbase + ((int64_t)group * R + rr) * tw;
-        return uniform_ptr(row_base_uniform<double>(a, r < a.n_rows ? r : rbase));
-    };
-    const double *row[R], *nrow[R];
-#define CHIP_SHARED_ISSUE_ROW(u, rr, voff) shared_issue<multi_slot_reg(u, rr), (u) * 1024, true>(voff, row[rr])
-#define CHIP_SHARED_ISSUE_Q(u, g, voff) do { if constexpr ((g) < NG) shared_issue<shared_qslot_reg(NG, u, (g) < NG ? (g) : 0), (u) * 1024, false>(voff, qg[(g) < NG ? (g) : 0]); } while (0)
-#define CHIP_SHARED_ISSUE_SLOT(u, voff) do { CHIP_SHARED_ISSUE_ROW(u, 0, voff); CHIP_SHARED_ISSUE_ROW(u, 1, voff); CHIP_SHARED_ISSUE_ROW(u, 2, voff); CHIP_SHARED_ISSUE_ROW(u, 3, voff); \
-                                             CHIP_SHARED_ISSUE_Q(u, 0, voff); CHIP_SHARED_ISSUE_Q(u, 1, voff); } while (0)
-    static_assert(kSharedMaxNG == 2, "CHIP_SHARED_ISSUE_SLOT / CHIP_SHARED_TAKE_QS name the in-place queries one by one");
-    if (total > 0) {
-#pragma unroll
-        for (int rr = 0; rr < R; rr++) { row[rr] = row_of(0, rr); nrow[rr] = row[rr]; }
-        if (ngroups > 1) {
-#pragma unroll
-            for (int rr = 0; rr < R; rr++) nrow[rr] = row_of(1, rr);
-        }
-        CHIP_SHARED_ISSUE_SLOT(0, lane_off); CHIP_SHARED_ISSUE_SLOT(1, lane_off); CHIP_SHARED_ISSUE_SLOT(2, lane_off); CHIP_SHARED_ISSUE_SLOT(3, lane_off);
-    }
-
-    double acc[R][NQ];
-#pragma unroll
-    for (int rr = 0; rr < R; rr++)
-#pragma unroll
-        for (int q = 0; q < NQ; q++) acc[rr][q] = 0.0;
-
-    // One batch per iteration; what the slots load next is what db_scan_topk_multi's load next (the next batch of the group, the first batch of the
-    // next group, at the wave's last batch the first KiBs of its rows and queries once more).  Per KiB u: the four row slots are taken and loaded
-    // again, the NS staged queries are multiplied in, then each in-place query is taken, loaded again and multiplied in.
-    int b = 0, group = 0;
-    for (int t = 0; t < total; t++) {
-        const int base = b * (128 * U);
-        uint32_t noff = (uint32_t)(base + 128 * U) * 8u;
-        if (b + 1 == nb) {
-            noff = 0;
-            if (group + 1 < ngroups) {
-#pragma unroll
-                for (int rr = 0; rr < R; rr++) row[rr] = nrow[rr];
-                if (group + 2 < ngroups) {
-#pragma unroll
-                    for (int rr = 0; rr < R; rr++) nrow[rr] = row_of(group + 2, rr);
-                }
-            }
-        }
-        {
-            constexpr int S = U * NQ, SS = U * NS;
-            const double *qv = qs + base + e0;
-            const uint32_t voff = noff + lane_off;
-            f64x2 w[SS];        // staged query vectors in the order they are used: (u, q < NS)
-            w[0] = *reinterpret_cast<const f64x2 *>(qv);
-            w[1] = *reinterpret_cast<const f64x2 *>(qv + D);
-            double x[R][2];
-#pragma unroll
-            for (int s = 0; s < S; s++) {
-                const int u = s / NQ, q = s % NQ;
-                if (q == 0) {
-#define CHIP_SHARED_TAKE_ROW(uu, rr) if (u == uu) { shared_take<multi_slot_reg(uu, rr), L - 1>(x[rr]); CHIP_SHARED_ISSUE_ROW(uu, rr, voff); }
-#define CHIP_SHARED_TAKE_SLOT(uu) CHIP_SHARED_TAKE_ROW(uu, 0) CHIP_SHARED_TAKE_ROW(uu, 1) CHIP_SHARED_TAKE_ROW(uu, 2) CHIP_SHARED_TAKE_ROW(uu, 3)
-                    CHIP_SHARED_TAKE_SLOT(0) CHIP_SHARED_TAKE_SLOT(1) CHIP_SHARED_TAKE_SLOT(2) CHIP_SHARED_TAKE_SLOT(3)
-#undef CHIP_SHARED_TAKE_SLOT
-#undef CHIP_SHARED_TAKE_ROW
-                }
-                double wd[2];
-                if (q < NS) {
-                    const int i = u * NS + q;
-                    if (i + 2 < SS) w[i + 2] = *reinterpret_cast<const f64x2 *>(qv + ((i + 2) % NS) * D + ((i + 2) / NS) * 128);
-                    wd[0] = w[i][0];
-                    wd[1] = w[i][1];
-                } else {
-#define CHIP_SHARED_TAKE_Q(uu, gg) if constexpr ((gg) < NG) { if (u == uu && q - NS == (gg)) { shared_take<shared_qslot_reg(NG, uu, (gg) < NG ? (gg) : 0), L - 1>(wd); CHIP_SHARED_ISSUE_Q(uu, gg, voff); } }
-#define CHIP_SHARED_TAKE_QS(uu) CHIP_SHARED_TAKE_Q(uu, 0) CHIP_SHARED_TAKE_Q(uu, 1)
-                    CHIP_SHARED_TAKE_QS(0) CHIP_SHARED_TAKE_QS(1) CHIP_SHARED_TAKE_QS(2) CHIP_SHARED_TAKE_QS(3)
-#undef CHIP_SHARED_TAKE_QS
-#undef CHIP_SHARED_TAKE_Q
-                }
-#pragma unroll
-                for (int c = 0; c < 2; c++) {
-#pragma unroll
-                    for (int rr = 0; rr < R; rr++) acc[rr][q] = __builtin_fma(wd[c], x[rr][c], acc[rr][q]);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        if (++b == nb) {
-            // the rows of this group are complete: db_scan_topk_multi's transposed pairing tree and its offers, statement for statement
-            static_assert(R == 4, "the transposed reduction folds four rows into the four 16-lane rows of a wave");
-            double s[NQ];
-#pragma unroll
-            for (int q = 0; q < NQ; q++) {
-                swap32_f64(acc[0][q], acc[2][q]);
-                swap32_f64(acc[1][q], acc[3][q]);
-                double p02 = acc[0][q] + acc[2][q], p13 = acc[1][q] + acc[3][q];
-                swap16_f64(p02, p13);
-                double v = p02 + p13;
-                v = v + dpp_f64<0x128>(v);
-                v = v + dpp_f64<0x124>(v);
-                v = v + dpp_f64<0x4E>(v);
-                v = v + dpp_f64<0xB1>(v);
-                s[q] = v;
-            }
-            unsigned long long hit = 0;
-#pragma unroll
-            for (int q = 0; q < NQ; q++) hit |= __ballot(s[q] >= thr_s[q]);
-            if (hit) {
-#pragma unroll
-                for (int rr = 0; rr < R; rr++) {
-                    const int64_t r = rbase + ((int64_t)group * R + rr) * tw;
-                    if (r < a.n_rows) {
-#pragma unroll
-                        for (int q = 0; q < NQ; q++)
-                            if (r < a.k[q / 3]) multi_offer(readlane_f64(s[q], 16 * rr), r, K, lane, mylists + q * K, thr_s[q]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int rr = 0; rr < R; rr++)
-#pragma unroll
-                for (int q = 0; q < NQ; q++) acc[rr][q] = 0.0;
-            b = 0;
-            group++;
-        }
-    }
-#undef CHIP_SHARED_ISSUE_SLOT
-#undef CHIP_SHARED_ISSUE_Q
-#undef CHIP_SHARED_ISSUE_ROW
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the read-ahead of the wave's last batch
-
-    block_merge_cand<NQ>(lists, K, lane, wave, wpb,
-                         [&](int q) { return a.partial + (((int64_t)(q / 3) * gridDim.x + blockIdx.x) * 3 + q % 3) * K; });
-}
-
-// ------------------------------------------------------------------------------------------------ K1, four ticks per pass, fp32 prefilter
-// db_scan_prefilter<NG>: ONE pass over float rows answers FOUR queued ticks (12 queries) -- in fp32.  Its lists do not decide anything: they
-// are the candidate sets from which tick_rescore below PROVES which rows can be in each exact top-K and scores only those in fp64, in
-// rows_dot's order (DESIGN.md 3: |fp32 score - exact score| <= E for every pair of published rows, whatever the order of the fp32 sum).
-// Blocking, row -> wave map, load slots v[192..255], lists in LDS, per-tick prefix test and output layout are db_scan_topk_multi's.  What differs:
-//   * arithmetic: v_pk_fma_f32 straight on the loaded registers -- per (row vector, query) two instructions, no conversion; lane L keeps
-//     one accumulator PAIR per (row, query): elements 4L, 4L + 2 of every 256 go to its low half, 4L + 1, 4L + 3 to its high half.  A slot
-//     is therefore loaded again only when all 12 queries have read it: per KiB u the wave waits for its four row slots at once, multiplies
-//     the staged queries in, then the in-place ones, then issues the slots of u for the next batch (12 of the 16 row KiB stay in flight);
-//   * queries: the first NS = 12 - NG are staged in LDS as fp32 (D = 4096: 9, 144 KiB), the last NG are read IN PLACE through the load stream
-//     as db_scan_shared_f64 does (asm-owned registers v[192 - 16 NG ..] below the row slots, issued behind the row slots of the same KiB,
-//     every wave reads the same bytes: L2 hits).  The stream of a wave is r0 r1 r2 r3 g0 .. g(NG-1) per KiB, L = 4 (4 + NG) loads;
-//   * reduction: low + high half, then the transposed pairing tree of the fp64 kernel on single registers;
-//   * lists: (score widened to double -- exact --, row), thresholds as fp32 in SGPRs.  A workgroup's merged list of K holds its K best rows
-//     by fp32 score; its K-th score bounds every row the workgroup dropped (each wave dropped only rows at or below its own K-th).
-// Nothing is loaded from outside rows [0, n_rows) and the NG query vectors: every row base comes from row_of(), every offset is below one row's length.
-constexpr int kPrefilterMaxNG = 3;
-constexpr int kPrefilterVgprBase = kMultiVgprBase - 4 * kMultiU * kPrefilterMaxNG;   // 144: what the compiler owns in every instantiation
-#define CHIP_PREFILTER_CLOBBERS                                                                                                         \
-    "v144", "v145", "v146", "v147", "v148", "v149", "v150", "v151", "v152", "v153", "v154", "v155", "v156", "v157", "v158", "v159",     \
-    "v160", "v161", "v162", "v163", "v164", "v165", "v166", "v167", "v168", "v169", "v170", "v171", "v172", "v173", "v174", "v175",     \
-    "v176", "v177", "v178", "v179", "v180", "v181", "v182", "v183", "v184", "v185", "v186", "v187", "v188", "v189", "v190", "v191"
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-template <int REG, int OFF, bool NTL>
-__device__ __forceinline__ void prefilter_issue(uint32_t voff, const float *base_uniform)
-{
-    if constexpr (NTL)
-        asm volatile("global_load_dwordx4 v[%2:%3], %0, %1 offset:%4 nt" ::"v"(voff), "s"(base_uniform), "n"(REG), "n"(REG + 3), "n"(OFF) : "memory");
-    else
-        asm volatile("global_load_dwordx4 v[%2:%3], %0, %1 offset:%4" ::"v"(voff), "s"(base_uniform), "n"(REG), "n"(REG + 3), "n"(OFF) : "memory");
-}
-template <int CNT>
-__device__ __forceinline__ void prefilter_wait()
-{
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CNT) : "memory");
-}
-// acc += (elements HALF, HALF + 1 of the row slot at REG) * w, both halves at once
-template <int REG>
-__device__ __forceinline__ void prefilter_fma(f32x2 &acc, f32x2 w)
-{
-    asm volatile("v_pk_fma_f32 %0, v[%2:%3], %1, %0" : "+v"(acc) : "v"(w), "n"(REG), "n"(REG + 1));
-}
-// the same with the query pair in a slot of its own
-template <int REG, int QREG>
-__device__ __forceinline__ void prefilter_fma_slot(f32x2 &acc)
-{
-    asm volatile("v_pk_fma_f32 %0, v[%1:%2], v[%3:%4], %0" : "+v"(acc) : "n"(REG), "n"(REG + 1), "n"(QREG), "n"(QREG + 1));
-}
-
-__device__ __forceinline__ void swap32_f32(float &a, float &b)
-{
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    a = __uint_as_float(r[0]);
-    b = __uint_as_float(r[1]);
-}
-__device__ __forceinline__ void swap16_f32(float &a, float &b)
-{
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    a = __uint_as_float(r[0]);
-    b = __uint_as_float(r[1]);
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_f32(float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-
-// multi_offer with the score and the threshold in fp32 (the list entry is the same value as a double)
-__device__ __forceinline__ void prefilter_offer(float s_uniform, int64_t gi, int K, int lane, chip_topk_entry *list, float &thr_s)
+template <typename S>
+__device__ __forceinline__ void pass_offer(S s_uniform, int64_t gi, int K, int lane, chip_topk_entry *list, S &thr_s)
 {
     if (s_uniform >= thr_s) {
         asm volatile("" : "+v"(lane));
@@ -919,20 +523,27 @@ __device__ __forceinline__ void prefilter_offer(float s_uniform, int64_t gi, int
             else if (lane == pos) { me.score = s; me.idx = gi; }
             list[lane] = me;      // every read of the old list precedes this write in program order (one wave, in-order LDS)
         }
-        thr_s = (float)readlane_f64(me.score, K - 1);   // exact: every score of the list is a widened float
+        thr_s = (S)readlane_f64(me.score, K - 1);   // exact: every score of the list came in as an S
     }
 }
 
-template <int NG>
-__global__ __launch_bounds__(kMultiBlock) __attribute__((amdgpu_num_vgpr(kPrefilterVgprBase / 2))) void db_scan_prefilter(PrefilterArgs a)
+// The skeleton.  A policy P says what one batch does to the accumulators (P::batch: takes and re-issues every slot of the batch once, in the
+// stream's order) and how a lane's accumulator becomes its sum (P::lane_sum); everything else is here, once.
+template <class P>
+__device__ __forceinline__ void shared_pass(const PassArgs &a)
 {
-    constexpr int NQ = 3 * kPrefilterTicks, NS = NQ - NG, R = kMultiR, U = kMultiU;
-    constexpr int L = U * (R + NG);        // loads of the stream in flight
-    constexpr int QB = kMultiVgprBase - 4 * U * NG;   // first register of the in-place query slots: KiB u of query g at QB + 4 (u NG + g)
-    static_assert(NG >= 0 && NG <= kPrefilterMaxNG && NS >= 2 && L <= 64 && R == 4, "query slots, LDS read-ahead, vmcnt counts to 63");
+    typedef typename P::Elem T;          // rows and queries as stored
+    typedef typename P::Score S;         // scores and thresholds
+    typedef typename Vec16<T>::type V;
+    constexpr int NQ = P::NQ, NG = P::NG, NS = NQ - NG, R = kMultiR, U = kMultiU, N = Vec16<T>::N;
+    constexpr int BATCH = 64 * N * U;    // elements of a 4 KiB batch
+    static_assert(pass_vgpr_base(NG) >= P::kVgprBase && pass_row_slot(U - 1, R - 1) + 4 <= 256, "load slots inside the asm's share of the register file");
+    static_assert(NG >= 0 && NS >= 2 && P::L == U * (R + NG) && P::L <= 64, "at least two staged queries (the LDS read-ahead), vmcnt counts to 63");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    asm volatile("" ::: CHIP_MULTI_CLOBBERS, CHIP_PREFILTER_CLOBBERS);   // makes the code object allocate the asm-owned registers
-    float *qs = reinterpret_cast<float *>(smem);  // [NS][D]
+    asm volatile("" ::: CHIP_PASS_SLOTS_192_255);                    // makes the code object allocate the asm-owned registers
+    if constexpr (P::kVgprBase <= 160) asm volatile("" ::: CHIP_PASS_SLOTS_160_191);
+    if constexpr (P::kVgprBase <= 144) asm volatile("" ::: CHIP_PASS_SLOTS_144_159);
+    T *qs = reinterpret_cast<T *>(smem);  // [NS][D]
     const int D = a.D;
     const int K = a.K;
     const int tid = threadIdx.x;
@@ -940,44 +551,49 @@ __global__ __launch_bounds__(kMultiBlock) __attribute__((amdgpu_num_vgpr(kPrefil
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wpb = blockDim.x >> 6;
 
-    for (int e = tid * 4; e < D; e += blockDim.x * 4) {
-        f32x4 w[NS];
+    for (int e = tid * N; e < D; e += blockDim.x * N) {   // all NS loads of a lane in flight together (L2-resident after the first workgroup)
+        V w[NS];
 #pragma unroll
-        for (int q = 0; q < NS; q++) w[q] = *as_global(reinterpret_cast<const f32x4 *>(static_cast<const float *>(a.q[q]) + e));
+        for (int q = 0; q < NS; q++) w[q] = *as_global(reinterpret_cast<const V *>(static_cast<const T *>(a.q[q]) + e));
 #pragma unroll
-        for (int q = 0; q < NS; q++) *reinterpret_cast<f32x4 *>(qs + q * D + e) = w[q];
+        for (int q = 0; q < NS; q++) *reinterpret_cast<V *>(qs + q * D + e) = w[q];
     }
     __syncthreads();
-    const float *qg[NG > 0 ? NG : 1];   // the queries read in place (SGPRs)
+    const T *qg[NG > 0 ? NG : 1];   // the queries read in place (SGPRs)
 #pragma unroll
-    for (int g = 0; g < NG; g++) qg[g] = uniform_ptr(static_cast<const float *>(a.q[NS + g]));
+    for (int g = 0; g < NG; g++) qg[g] = uniform_ptr(static_cast<const T *>(a.q[NS + g]));
 
-    chip_topk_entry *lists = reinterpret_cast<chip_topk_entry *>(smem + (size_t)NS * D * sizeof(float));   // [wave][12][K], as db_scan_topk_multi
+    // running top-K lists: LDS behind the queries, [wave][3T][K] (this wave's lists are touched by this wave only until the merge)
+    chip_topk_entry *lists = reinterpret_cast<chip_topk_entry *>(smem + (size_t)NS * D * sizeof(T));
     chip_topk_entry *mylists = lists + (size_t)wave * NQ * K;
-    float thr_s[NQ];
+    S thr_s[NQ];   // score of the K-th entry of each list (SGPRs)
 #pragma unroll
     for (int q = 0; q < NQ; q++) {
         thr_s[q] = -INFINITY;
         if (lane < K) { chip_topk_entry t; t.score = -INFINITY; t.idx = -1; mylists[q * K + lane] = t; }
     }
 
+    // Row -> wave map: as db_scan_topk (wave g owns rows g, g + tw, ...), four consecutive rows of that sequence (a GROUP) at a time --
+    // all waves together read one window of 4 tw consecutive rows that slides through the DB.  A row of a group that falls beyond the
+    // pass is replaced by the wave's first row (in bounds, never offered).
+    //
+    // The wave walks the (group, 4 KiB batch) sequence of its rows as ONE stream: a slot is loaded again -- for the next batch of
+    // the group, or the first batch of the next group -- right behind the statement that took its contents, so nearly all L KiB per
+    // wave are in flight through the arithmetic, through the reduction and through the offers, and every wait is counted.
+    // Nothing is ever loaded from outside rows [0, n_rows) and the NG query vectors: every row base comes from row_of() below, i.e. from
+    // a row < n_rows through the segment table, and every offset (rows and queries alike: both are D elements) is below one row's length.
     const int64_t tw = (int64_t)gridDim.x * wpb;
     const int64_t rbase = (int64_t)blockIdx.x * wpb + wave;
-    const int nb = D / (256 * U);
-    const int ngroups = rbase < a.n_rows ? (int)((a.n_rows - 1 - rbase) / (R * tw)) + 1 : 0;
+    const int nb = D / BATCH;                                                                 // batches per row
+    const int ngroups = rbase < a.n_rows ? (int)((a.n_rows - 1 - rbase) / (R * tw)) + 1 : 0;  // groups of this wave (wave-uniform)
     const int total = ngroups * nb;
     const uint32_t lane_off = (uint32_t)lane * 16u;
-    const int e0 = lane * 4;
+    const int e0 = lane * N;
     auto row_of = [&](int group, int rr) {
         const int64_t r = rbase + ((int64_t)group * R + rr) * tw;
-        return uniform_ptr(row_base_uniform<float>(a, r < a.n_rows ? r : rbase));
+        return uniform_ptr(row_base_uniform<T>(a, r < a.n_rows ? r : rbase));
     };
-    const float *row[R], *nrow[R];
-#define CHIP_PF_ISSUE_ROW(u, rr, voff) prefilter_issue<multi_slot_reg(u, rr), (u) * 1024, true>(voff, row[rr])
-#define CHIP_PF_ISSUE_Q(u, g, voff) do { if constexpr ((g) < NG) prefilter_issue<QB + 4 * ((u) * NG + ((g) < NG ? (g) : 0)), (u) * 1024, false>(voff, qg[(g) < NG ? (g) : 0]); } while (0)
-#define CHIP_PF_ISSUE_SLOT(u, voff) do { CHIP_PF_ISSUE_ROW(u, 0, voff); CHIP_PF_ISSUE_ROW(u, 1, voff); CHIP_PF_ISSUE_ROW(u, 2, voff); CHIP_PF_ISSUE_ROW(u, 3, voff); \
-                                         CHIP_PF_ISSUE_Q(u, 0, voff); CHIP_PF_ISSUE_Q(u, 1, voff); CHIP_PF_ISSUE_Q(u, 2, voff); } while (0)
-    static_assert(kPrefilterMaxNG == 3, "CHIP_PF_ISSUE_SLOT / CHIP_PF_FMA_QS name the in-place queries one by one");
+    const T *row[R], *nrow[R];   // bases the NEXT loads read from, and those of the group after (looked up one group ahead; SGPRs)
     if (total > 0) {
 #pragma unroll
         for (int rr = 0; rr < R; rr++) { row[rr] = row_of(0, rr); nrow[rr] = row[rr]; }
@@ -985,24 +601,26 @@ __global__ __launch_bounds__(kMultiBlock) __attribute__((amdgpu_num_vgpr(kPrefil
 #pragma unroll
             for (int rr = 0; rr < R; rr++) nrow[rr] = row_of(1, rr);
         }
-        CHIP_PF_ISSUE_SLOT(0, lane_off); CHIP_PF_ISSUE_SLOT(1, lane_off); CHIP_PF_ISSUE_SLOT(2, lane_off); CHIP_PF_ISSUE_SLOT(3, lane_off);
+        static_assert(U == 4, "the prologue names the KiBs of the first batch one by one");
+        slots_issue_kib<0, NG>(lane_off, row, qg); slots_issue_kib<1, NG>(lane_off, row, qg); slots_issue_kib<2, NG>(lane_off, row, qg); slots_issue_kib<3, NG>(lane_off, row, qg);
     }
 
-    f32x2 acc[R][NQ];
+    typename P::Acc acc[R][NQ];
 #pragma unroll
     for (int rr = 0; rr < R; rr++)
 #pragma unroll
-        for (int q = 0; q < NQ; q++) acc[rr][q] = (f32x2){0.0f, 0.0f};
+        for (int q = 0; q < NQ; q++) acc[rr][q] = P::zero();
 
-    // One batch per iteration; what the slots load next is what db_scan_topk_multi's load next (the next batch of the group, the first batch of the
-    // next group, at the wave's last batch the first KiBs of its rows and queries once more).
+    // One batch per iteration.  What the slots load next (at byte offset noff of row[] and qg[]): the next batch of the group; at the
+    // group's last batch the first batch of the wave's next group; at the wave's last batch the first KiBs of the rows (and in-place
+    // queries) it has just read once more (in bounds, taken by nobody), so that one loop body and one set of wait counts serve the whole stream.
     int b = 0, group = 0;
     for (int t = 0; t < total; t++) {
-        const int base = b * (256 * U);
-        uint32_t noff = (uint32_t)(base + 256 * U) * 4u;
+        const int base = b * BATCH;
+        uint32_t noff = (uint32_t)(base + BATCH) * (uint32_t)sizeof(T);
         if (b + 1 == nb) {
             noff = 0;
-            if (group + 1 < ngroups) {
+            if (group + 1 < ngroups) {   // the slots start on the next group; its successor's bases are looked up for the boundary after
 #pragma unroll
                 for (int rr = 0; rr < R; rr++) row[rr] = nrow[rr];
                 if (group + 2 < ngroups) {
@@ -1011,74 +629,35 @@ __global__ __launch_bounds__(kMultiBlock) __attribute__((amdgpu_num_vgpr(kPrefil
                 }
             }
         }
-        {
-            constexpr int SS = U * NS;
-            const float *qv = qs + base + e0;
-            const uint32_t voff = noff + lane_off;
-            f32x4 w[SS];        // staged query vectors in the order they are used: (u, q < NS), read two ahead
-            w[0] = *reinterpret_cast<const f32x4 *>(qv);
-            w[1] = *reinterpret_cast<const f32x4 *>(qv + D);
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-#define CHIP_PF_U(uu) if (u == uu) {                                                                                                    \
-                    prefilter_wait<L - R>();                      /* the four row slots of this KiB are the oldest loads of the stream */ \
-                    _Pragma("unroll") for (int q = 0; q < NS; q++) {                                                                    \
-                        const int i = uu * NS + q;                                                                                      \
-                        if (i + 2 < SS) w[i + 2] = *reinterpret_cast<const f32x4 *>(qv + ((i + 2) % NS) * D + ((i + 2) / NS) * 256);     \
-                        const f32x2 wl = __builtin_shufflevector(w[i], w[i], 0, 1), wh = __builtin_shufflevector(w[i], w[i], 2, 3);     \
-                        prefilter_fma<multi_slot_reg(uu, 0)>(acc[0][q], wl); prefilter_fma<multi_slot_reg(uu, 1)>(acc[1][q], wl);       \
-                        prefilter_fma<multi_slot_reg(uu, 2)>(acc[2][q], wl); prefilter_fma<multi_slot_reg(uu, 3)>(acc[3][q], wl);       \
-                        prefilter_fma<multi_slot_reg(uu, 0) + 2>(acc[0][q], wh); prefilter_fma<multi_slot_reg(uu, 1) + 2>(acc[1][q], wh); \
-                        prefilter_fma<multi_slot_reg(uu, 2) + 2>(acc[2][q], wh); prefilter_fma<multi_slot_reg(uu, 3) + 2>(acc[3][q], wh); \
-                        __builtin_amdgcn_sched_barrier(0);                                                                              \
-                    }                                                                                                                   \
-                    CHIP_PF_FMA_Q(uu, 0) CHIP_PF_FMA_Q(uu, 1) CHIP_PF_FMA_Q(uu, 2)                                                      \
-                    CHIP_PF_ISSUE_SLOT(uu, voff);                                                                                       \
-                }
-#define CHIP_PF_FMA_Q(uu, gg) if constexpr ((gg) < NG) {                                                                                \
-                    constexpr int QR = QB + 4 * ((uu) * NG + ((gg) < NG ? (gg) : 0));                                                   \
-                    prefilter_wait<L - R - 1 - (gg)>();                                                                                 \
-                    prefilter_fma_slot<multi_slot_reg(uu, 0), QR>(acc[0][NS + (gg)]); prefilter_fma_slot<multi_slot_reg(uu, 1), QR>(acc[1][NS + (gg)]); \
-                    prefilter_fma_slot<multi_slot_reg(uu, 2), QR>(acc[2][NS + (gg)]); prefilter_fma_slot<multi_slot_reg(uu, 3), QR>(acc[3][NS + (gg)]); \
-                    prefilter_fma_slot<multi_slot_reg(uu, 0) + 2, QR + 2>(acc[0][NS + (gg)]); prefilter_fma_slot<multi_slot_reg(uu, 1) + 2, QR + 2>(acc[1][NS + (gg)]); \
-                    prefilter_fma_slot<multi_slot_reg(uu, 2) + 2, QR + 2>(acc[2][NS + (gg)]); prefilter_fma_slot<multi_slot_reg(uu, 3) + 2, QR + 2>(acc[3][NS + (gg)]); \
-                }
-                CHIP_PF_U(0) CHIP_PF_U(1) CHIP_PF_U(2) CHIP_PF_U(3)
-#undef CHIP_PF_FMA_Q
-#undef CHIP_PF_U
-            }
-        }
+        P::batch(acc, qs + base + e0, D, noff + lane_off, row, qg);
         if (++b == nb) {
-            // the rows of this group are complete: low + high half, then the transposed pairing tree of db_scan_topk_multi on single registers
-            // (any tree will do here; this one leaves row rr's sum in all 16 lanes of the wave's 16-lane row rr)
-            float s[NQ];
+            // The rows of this group are complete: R x 3T lane sums, all in one basic block ahead of the offers' branches.
+            S s[NQ];
 #pragma unroll
-            for (int q = 0; q < NQ; q++) {
-                float a0 = acc[0][q][0] + acc[0][q][1], a1 = acc[1][q][0] + acc[1][q][1], a2 = acc[2][q][0] + acc[2][q][1], a3 = acc[3][q][0] + acc[3][q][1];
-                swap32_f32(a0, a2);
-                swap32_f32(a1, a3);
-                float p02 = a0 + a2, p13 = a1 + a3;
-                swap16_f32(p02, p13);
-                float v = p02 + p13;
-                v = v + dpp_f32<0x128>(v);
-                v = v + dpp_f32<0x124>(v);
-                v = v + dpp_f32<0x4E>(v);
-                v = v + dpp_f32<0xB1>(v);
-                s[q] = v;
-            }
+            for (int q = 0; q < NQ; q++) s[q] = reduce_rows4<S>(P::lane_sum(acc[0][q]), P::lane_sum(acc[1][q]), P::lane_sum(acc[2][q]), P::lane_sum(acc[3][q]));
+            // Offers.  One vector compare per query first: s[q] holds the four rows' scores against query q, and a threshold only rises
+            // while the group is offered, so a score that the loop below would admit is >= the threshold the group starts with (NaN on
+            // neither side).  No lane set: nothing of this group enters any list.  Otherwise each list is offered its rows one by one, in
+            // order, each against the threshold as it stands then.  (A lane may be set by a row some tick must not see, or by the stand-in
+            // of a row beyond the pass: that costs the walk below, which tests both, and nothing else.)
             unsigned long long hit = 0;
 #pragma unroll
             for (int q = 0; q < NQ; q++) hit |= __ballot(s[q] >= thr_s[q]);
             if (hit) {
+                // The lists are independent of one another; only the rows offered to ONE list must come in ascending order.  So the walk goes
+                // query first: the query's own compare once more (one vector instruction; 3T masks kept from the pre-check do not fit
+                // the SGPRs), and a query none of whose four scores reaches its threshold is stepped over as a whole.  thr_s[q] changes
+                // only inside q's own turn, so the compare is still against the threshold the group started with.  The empty asm below is
+                // what makes it a second compare: without it the compiler reuses the pre-check's masks, keeps them live across the
+                // walk and spills SGPRs, which tests/test_codeobj_multi.py refuses.
 #pragma unroll
                 for (int q = 0; q < NQ; q++) {
-                    asm volatile("" : "+v"(s[q]));   // as db_scan_topk_multi: the compare is made again, the pre-check's masks are not kept
+                    asm volatile("" : "+v"(s[q]));   // a value the pre-check has not seen: the compare is made again, not kept
                     if (__ballot(s[q] >= thr_s[q])) {
 #pragma unroll
                         for (int rr = 0; rr < R; rr++) {
                             const int64_t r = rbase + ((int64_t)group * R + rr) * tw;
-                            if (r < a.n_rows && r < a.k[q / 3])
-                                prefilter_offer(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(s[q]), 16 * rr)), r, K, lane, mylists + q * K, thr_s[q]);
+                            if (r < a.n_rows && r < a.k[q / 3]) pass_offer<S>(lane_value(s[q], 16 * rr), r, K, lane, mylists + q * K, thr_s[q]);
                         }
                     }
                 }
@@ -1086,18 +665,154 @@ __global__ __launch_bounds__(kMultiBlock) __attribute__((amdgpu_num_vgpr(kPrefil
 #pragma unroll
             for (int rr = 0; rr < R; rr++)
 #pragma unroll
-                for (int q = 0; q < NQ; q++) acc[rr][q] = (f32x2){0.0f, 0.0f};
+                for (int q = 0; q < NQ; q++) acc[rr][q] = P::zero();
             b = 0;
             group++;
         }
     }
-#undef CHIP_PF_ISSUE_SLOT
-#undef CHIP_PF_ISSUE_Q
-#undef CHIP_PF_ISSUE_ROW
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the read-ahead of the wave's last batch
 
     block_merge_cand<NQ>(lists, K, lane, wave, wpb,
                          [&](int q) { return a.partial + (((int64_t)(q / 3) * gridDim.x + blockIdx.x) * 3 + q % 3) * K; });
+}
+
+// fp64 arithmetic, the bits of the one-tick kernels: per (row, query) exactly rows_dot's order -- lane L accumulates elements
+// j*64N + N L + c (j ascending, c = 0 .. N - 1; N = 4 floats or 2 doubles per lane and KiB) into one fp64 accumulator by fma, then the
+// pairing tree above.  Float rows are converted by the statement that takes their slot, their queries (fp32 in LDS) at use; doubles are
+// copied out (2 x v_mov_b64): either way the slot is loaded again in the next statement, and EVERY wait of the loop is vmcnt(L - 1): the
+// load waited for is always the oldest one.  Per KiB u: the four row slots, then the queries in order, each read (staged: two vectors
+// ahead, counted lgkmcnt waits) or taken and re-issued (in place) once per 4 rows and multiplied into the four rows.
+// Registers, double rows: the compiler owns v[0 .. 160): acc[4][3T] (48 at T = 2) + the 16 of a row KiB + 4 of a query vector + 12 of
+// the LDS read-ahead.  T = 3 needs NG = 5 at D = 4096: 80 registers of query slots leave the compiler v[0 .. 112) for 72 of accumulators
+// and everything else.  Compiled that way the kernel spills 90 registers (560 bytes of scratch per lane); a scratch access drains the
+// stream, so it is dropped (kSharedF64MaxTicks).
+constexpr int kSharedMaxNG = 2;          // in-place queries of the double instantiations that are built: D <= 4608 at T = 2
+constexpr int kSharedF64MaxTicks = 2;
+template <typename T, int NTICKS, int NG_, int MAX_NG>
+struct PassF64 {
+    typedef T Elem;
+    typedef double Score;
+    typedef double Acc;
+    static constexpr int NQ = 3 * NTICKS, NG = NG_, NS = NQ - NG, R = kMultiR, U = kMultiU, L = U * (R + NG), kVgprBase = pass_vgpr_base(MAX_NG);
+    static __device__ __forceinline__ Acc zero() { return 0.0; }
+    static __device__ __forceinline__ double lane_sum(Acc v) { return v; }
+    static __device__ __forceinline__ void batch(Acc (&acc)[R][NQ], const T *qv, int D, uint32_t voff, const T *const (&row)[R], const T *const (&qg)[NG > 0 ? NG : 1])
+    {
+        typedef typename Vec16<T>::type V;
+        constexpr int N = Vec16<T>::N, SS = U * NS;
+        V w[SS];            // staged query vectors in the order they are used: (u, q < NS)
+        w[0] = *reinterpret_cast<const V *>(qv);
+        w[1] = *reinterpret_cast<const V *>(qv + D);
+        double x[R][N];
+        static_for<U * NQ>([&](auto sc) CHIP_INLINE_LAMBDA {
+            constexpr int u = sc / NQ, q = sc % NQ;
+            if constexpr (q == 0)
+                static_for<R>([&](auto rr) CHIP_INLINE_LAMBDA {
+                    slot_take<pass_row_slot(u, rr), L - 1>(x[rr]);
+                    slot_issue<pass_row_slot(u, rr), u * 1024, true>(voff, row[rr]);
+                });
+            double wd[N];
+            if constexpr (q < NS) {
+                constexpr int i = u * NS + q;
+                if constexpr (i + 2 < SS) w[i + 2] = *reinterpret_cast<const V *>(qv + ((i + 2) % NS) * D + ((i + 2) / NS) * (64 * N));
+            } else {
+                slot_take<pass_query_slot(NG, u, q - NS), L - 1>(wd);
+                slot_issue<pass_query_slot(NG, u, q - NS), u * 1024, false>(voff, qg[q - NS]);
+            }
+#pragma unroll
+            for (int c = 0; c < N; c++) {
+                if constexpr (q < NS) wd[c] = (double)w[u * NS + q][c];
+#pragma unroll
+                for (int rr = 0; rr < R; rr++) acc[rr][q] = __builtin_fma(wd[c], x[rr][c], acc[rr][q]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        });
+    }
+};
+
+template <int NTICKS>
+__global__ __launch_bounds__(kMultiBlock) __attribute__((amdgpu_num_vgpr(pass_vgpr_base(0) / 2))) void db_scan_topk_multi(PassArgs a)
+{
+    shared_pass<PassF64<float, NTICKS, 0, 0>>(a);
+}
+
+template <int NTICKS, int NG>
+__global__ __launch_bounds__(kMultiBlock) __attribute__((amdgpu_num_vgpr(pass_vgpr_base(kSharedMaxNG) / 2))) void db_scan_shared_f64(PassArgs a)
+{
+    static_assert(NG <= kSharedMaxNG, "the compiler's share is sized for kSharedMaxNG query slots per KiB");
+    shared_pass<PassF64<double, NTICKS, NG, kSharedMaxNG>>(a);
+}
+
+// ------------------------------------------------------------------------------------------------ K1, four ticks per pass, fp32 prefilter
+// db_scan_prefilter<NG>: the shared pass over float rows for FOUR queued ticks (12 queries) -- in fp32.  Its lists do not decide anything:
+// they are the candidate sets from which tick_rescore below PROVES which rows can be in each exact top-K and scores only those in fp64, in
+// rows_dot's order (DESIGN.md 3: |fp32 score - exact score| <= E for every pair of published rows, whatever the order of the fp32 sum).
+// What differs from the fp64 policy:
+//   * arithmetic: v_pk_fma_f32 straight on the loaded registers -- per (row vector, query) two instructions, no conversion; lane L keeps
+//     one accumulator PAIR per (row, query): elements 4L, 4L + 2 of every 256 go to its low half, 4L + 1, 4L + 3 to its high half.  A slot
+//     is therefore loaded again only when all 12 queries have read it: per KiB u the wave waits for its four row slots at once, multiplies
+//     the staged queries in, then the in-place ones (one more counted wait each), then issues the slots of u for the next batch (12 of the
+//     16 row KiB stay in flight);
+//   * queries: D = 4096 stages 9 (144 KiB) and reads NG = 3 in place;
+//   * reduction: low + high half, then the pairing tree on single registers (any tree will do here);
+//   * lists: (score widened to double -- exact --, row), thresholds as fp32 in SGPRs.  A workgroup's merged list of K holds its K best rows
+//     by fp32 score; its K-th score bounds every row the workgroup dropped (each wave dropped only rows at or below its own K-th).
+constexpr int kPrefilterMaxNG = 3;
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// acc += (the element pair at REG of a row slot) * w, both halves at once; w in compiler registers or in a query slot at QREG
+template <int REG>
+__device__ __forceinline__ void prefilter_fma(f32x2 &acc, f32x2 w)
+{
+    asm volatile("v_pk_fma_f32 %0, v[%2:%3], %1, %0" : "+v"(acc) : "v"(w), "n"(REG), "n"(REG + 1));
+}
+template <int REG, int QREG>
+__device__ __forceinline__ void prefilter_fma_slot(f32x2 &acc)
+{
+    asm volatile("v_pk_fma_f32 %0, v[%1:%2], v[%3:%4], %0" : "+v"(acc) : "n"(REG), "n"(REG + 1), "n"(QREG), "n"(QREG + 1));
+}
+
+template <int NG_>
+struct PassF32 {
+    typedef float Elem;
+    typedef float Score;
+    typedef f32x2 Acc;
+    static constexpr int NQ = 3 * kPrefilterTicks, NG = NG_, NS = NQ - NG, R = kMultiR, U = kMultiU, L = U * (R + NG), kVgprBase = pass_vgpr_base(kPrefilterMaxNG);
+    static __device__ __forceinline__ Acc zero() { return (f32x2){0.0f, 0.0f}; }
+    static __device__ __forceinline__ float lane_sum(Acc v) { return v[0] + v[1]; }
+    static __device__ __forceinline__ void batch(Acc (&acc)[R][NQ], const float *qv, int D, uint32_t voff, const float *const (&row)[R], const float *const (&qg)[NG > 0 ? NG : 1])
+    {
+        constexpr int SS = U * NS;
+        f32x4 w[SS];        // staged query vectors in the order they are used: (u, q < NS), read two ahead
+        w[0] = *reinterpret_cast<const f32x4 *>(qv);
+        w[1] = *reinterpret_cast<const f32x4 *>(qv + D);
+        static_for<U>([&](auto uc) CHIP_INLINE_LAMBDA {
+            constexpr int u = uc;
+            slot_wait<L - R>();                      // the four row slots of this KiB are the oldest loads of the stream
+            static_for<NS>([&](auto qc) CHIP_INLINE_LAMBDA {
+                constexpr int q = qc, i = u * NS + q;
+                if constexpr (i + 2 < SS) w[i + 2] = *reinterpret_cast<const f32x4 *>(qv + ((i + 2) % NS) * D + ((i + 2) / NS) * 256);
+                const f32x2 wl = __builtin_shufflevector(w[i], w[i], 0, 1), wh = __builtin_shufflevector(w[i], w[i], 2, 3);
+                static_for<R>([&](auto rr) CHIP_INLINE_LAMBDA { prefilter_fma<pass_row_slot(u, rr)>(acc[rr][q], wl); });
+                static_for<R>([&](auto rr) CHIP_INLINE_LAMBDA { prefilter_fma<pass_row_slot(u, rr) + 2>(acc[rr][q], wh); });
+                __builtin_amdgcn_sched_barrier(0);
+            });
+            static_for<NG>([&](auto gc) CHIP_INLINE_LAMBDA {
+                constexpr int g = gc, QR = pass_query_slot(NG, u, g);
+                slot_wait<L - R - 1 - g>();
+                static_for<R>([&](auto rr) CHIP_INLINE_LAMBDA { prefilter_fma_slot<pass_row_slot(u, rr), QR>(acc[rr][NS + g]); });
+                static_for<R>([&](auto rr) CHIP_INLINE_LAMBDA { prefilter_fma_slot<pass_row_slot(u, rr) + 2, QR + 2>(acc[rr][NS + g]); });
+            });
+            slots_issue_kib<u, NG>(voff, row, qg);
+        });
+    }
+};
+
+template <int NG>
+__global__ __launch_bounds__(kMultiBlock) __attribute__((amdgpu_num_vgpr(pass_vgpr_base(kPrefilterMaxNG) / 2))) void db_scan_prefilter(PassArgs a)
+{
+    static_assert(NG <= kPrefilterMaxNG, "the compiler's share is sized for kPrefilterMaxNG query slots per KiB");
+    shared_pass<PassF32<NG>>(a);
 }
 
 // ------------------------------------------------------------------------------------------------ exact rescoring of one prefiltered tick
@@ -2202,30 +1917,29 @@ int launch_scan(Ctx *c, hipStream_t s, const ScanArgs &a, int nq, int grid)
     return CHIP_OK;
 }
 
-// Several ticks per pass (db_scan_topk_multi for float rows, db_scan_shared_f64 for double rows).  The ONE place that sizes such a pass: which
-// queries are staged and how much LDS the launch asks for, from D, the storage type, the ticks and K alone -- launch_scan_multi launches what
-// this says, scan_multi_max_ticks asks it which T a ctx can be served with, chip_debug_multi_plan hands it out without a device.
-//   float rows : whole 4 KiB batches; all 3 T queries staged as fp32 (D = 4096: T <= 3; D = 8192: none);
-//   double rows: whole 4 KiB batches (D % 512 == 0), T = 2; as many of the 6 fp64 queries staged as fit next to the lists, the other NG <= 2
-//                read in place (D <= 3072: NG = 0; D = 3584: 1; D = 4096, 4608: 2; wider rows: no such form).
-int scan_multi_plan(int D, int elem, int n_ticks, int K, int grid, chip_debug_scan_launch *f)
+// The shared passes (db_scan_topk_multi / db_scan_shared_f64: family MULTI; db_scan_prefilter: family PREFILTER).  The ONE place that sizes such
+// a pass: which queries are staged and how much LDS the launch asks for, from D, the storage type, the ticks and K alone -- launch_pass
+// launches what this says, scan_multi_max_ticks / scan_prefilter_usable ask it what a ctx can be served with, chip_debug_multi_plan and
+// chip_debug_prefilter_plan hand it out without a device.  Rows of whole 4 KiB batches; as many of the 3 T queries staged in the rows' type
+// as fit the LDS next to the lists, the other NG read in place where an instantiation exists for that NG:
+//   MULTI, float rows : T = 2, 3; NG = 0 only (D = 4096: T <= 3; D = 8192: none);
+//   MULTI, double rows: T = 2; NG <= 2 (D <= 3072: NG = 0; D = 3584: 1; D = 4096, 4608: 2; wider rows: no such form);
+//   PREFILTER         : float rows, T = 4; NG = 0 (D <= 3072) or 3 (D = 4096); wider rows, K = 16 at D = 4096 and double rows have no such pass.
+static int pass_plan(int family, int D, int elem, int n_ticks, int K, int grid, chip_debug_scan_launch *f)
 {
     *f = chip_debug_scan_launch{};
-    if (D < 1 || (elem != 4 && elem != 8) || n_ticks < 2 || n_ticks > kMultiMaxTicks || K < 1 || K > CHIP_MAX_TOPK || grid < 1 || grid > 512 ||
-        (int64_t)D * elem % 4096 != 0)
-        return CHIP_ERR_UNSUPPORTED;
+    const bool prefilter = family == CHIP_SCAN_FAMILY_PREFILTER;
+    if (D < 1 || (elem != 4 && elem != 8) || K < 1 || K > CHIP_MAX_TOPK || grid < 1 || grid > 512 || (int64_t)D * elem % 4096 != 0) return CHIP_ERR_UNSUPPORTED;
+    if (prefilter ? elem != 4 : n_ticks < 2 || n_ticks > (elem == 8 ? kSharedF64MaxTicks : kMultiMaxTicks)) return CHIP_ERR_UNSUPPORTED;
     const int nq = 3 * n_ticks;
     const size_t kLds = 160 * 1024, lists = (size_t)(kMultiBlock / 64) * nq * K * sizeof(chip_topk_entry);   // [wave][3T][K] behind the queries
-    int staged = nq;
-    if (elem == 8) {
-        if (n_ticks > kSharedF64MaxTicks) return CHIP_ERR_UNSUPPORTED;
-        const size_t fit = (kLds - lists) / ((size_t)D * 8);
-        if (fit < (size_t)nq) staged = (int)fit;
-        if (nq - staged > kSharedMaxNG) return CHIP_ERR_UNSUPPORTED;   // wider rows: more in-place queries than an instantiation exists for
-    }
+    const int max_ng = prefilter ? kPrefilterMaxNG : elem == 8 ? kSharedMaxNG : 0;
+    const size_t fit = max_ng > 0 ? (kLds - lists) / ((size_t)D * elem) : (size_t)nq;
+    const int staged = fit < (size_t)nq ? (int)fit : nq, ng = nq - staged;
+    if (prefilter ? ng != 0 && ng != kPrefilterMaxNG : ng > max_ng) return CHIP_ERR_UNSUPPORTED;   // an NG no instantiation exists for
     const size_t lds = (size_t)staged * D * elem + lists;
     if (lds > kLds) return CHIP_ERR_UNSUPPORTED;
-    f->family = CHIP_SCAN_FAMILY_MULTI;
+    f->family = family;
     f->elem = elem;
     f->nq = nq;
     f->K = K;
@@ -2235,13 +1949,15 @@ int scan_multi_plan(int D, int elem, int n_ticks, int K, int grid, chip_debug_sc
     f->NTL = 1;
     f->ticks = n_ticks;
     f->q64 = elem == 8 ? staged : 0;   // queries staged as fp64 (float rows stage fp32)
-    f->NG = nq - staged;
+    f->NG = ng;
     f->grid = grid;
     f->block = kMultiBlock;
     f->wg_per_cu = 1;
     f->lds_bytes = (int32_t)lds;
     return CHIP_OK;
 }
+int scan_multi_plan(int D, int elem, int n_ticks, int K, int grid, chip_debug_scan_launch *f) { return pass_plan(CHIP_SCAN_FAMILY_MULTI, D, elem, n_ticks, K, grid, f); }
+int scan_prefilter_plan(int D, int elem, int K, int grid, chip_debug_scan_launch *f) { return pass_plan(CHIP_SCAN_FAMILY_PREFILTER, D, elem, kPrefilterTicks, K, grid, f); }
 
 int scan_multi_grid(const Ctx *c) { return c->n_cus < c->max_grid ? c->n_cus : c->max_grid; }   // one 8-wave workgroup per CU
 
@@ -2253,66 +1969,6 @@ int scan_multi_max_ticks(const Ctx *c)
     for (int t = kMultiMaxTicks; t >= 2; t--)
         if (scan_multi_plan(c->D, c->elem, t, CHIP_DEFAULT_TOPK, scan_multi_grid(c), &f) == CHIP_OK) return t;
     return 0;
-}
-
-template <class Kernel>
-static int launch_scan_multi_k(Ctx *c, hipStream_t s, Kernel kernel, const MultiScanArgs &a, int grid, int lds)
-{
-    CHIP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kMultiBlock), lds, s, a);
-    CHIP_HIP(c, hipGetLastError());
-    return CHIP_OK;
-}
-
-int launch_scan_multi(Ctx *c, hipStream_t s, const MultiScanArgs &a, int n_ticks, int grid)
-{
-    chip_debug_scan_launch f;
-    if (n_ticks > scan_multi_max_ticks(c) || grid > c->max_grid || scan_multi_plan(c->D, c->elem, n_ticks, a.K, grid, &f) != CHIP_OK)
-        return CHIP_ERR_UNSUPPORTED;
-    int rc = CHIP_ERR_UNSUPPORTED;
-    if (c->elem == 4) {
-        rc = n_ticks == 2 ? launch_scan_multi_k(c, s, db_scan_topk_multi<2>, a, grid, f.lds_bytes) : launch_scan_multi_k(c, s, db_scan_topk_multi<3>, a, grid, f.lds_bytes);
-    } else if (n_ticks == 2) {
-        static_assert(kSharedF64MaxTicks == 2 && kSharedMaxNG == 2, "the instantiations below");
-        if (f.NG == 0) rc = launch_scan_multi_k(c, s, db_scan_shared_f64<2, 0>, a, grid, f.lds_bytes);
-        else if (f.NG == 1) rc = launch_scan_multi_k(c, s, db_scan_shared_f64<2, 1>, a, grid, f.lds_bytes);
-        else if (f.NG == 2) rc = launch_scan_multi_k(c, s, db_scan_shared_f64<2, 2>, a, grid, f.lds_bytes);
-    }
-    if (rc != CHIP_OK) return rc;
-    f.n_rows = a.n_rows;
-    f.launches = c->last_scan.launches + 1;
-    c->last_scan = f;
-    return CHIP_OK;
-}
-
-// The prefilter pass (db_scan_prefilter): four ticks over float rows of whole 4 KiB batches.  The ONE place that sizes it: as many of the 12 fp32
-// queries staged as fit the LDS next to the lists, the other NG read in place -- NG = 0 (D <= 3072) or 3 (D = 4096) are built; every other shape
-// (wider rows, K = 16 at D = 4096, double rows) has no such pass.
-int scan_prefilter_plan(int D, int elem, int K, int grid, chip_debug_scan_launch *f)
-{
-    *f = chip_debug_scan_launch{};
-    if (D < 1 || elem != 4 || K < 1 || K > CHIP_MAX_TOPK || grid < 1 || grid > 512 || (int64_t)D * elem % 4096 != 0) return CHIP_ERR_UNSUPPORTED;
-    const int nq = 3 * kPrefilterTicks;
-    const size_t kLds = 160 * 1024, lists = (size_t)(kMultiBlock / 64) * nq * K * sizeof(chip_topk_entry);
-    const size_t fit = (kLds - lists) / ((size_t)D * 4);
-    const int staged = fit < (size_t)nq ? (int)fit : nq;
-    const int ng = nq - staged;
-    if (ng != 0 && ng != kPrefilterMaxNG) return CHIP_ERR_UNSUPPORTED;
-    f->family = CHIP_SCAN_FAMILY_PREFILTER;
-    f->elem = elem;
-    f->nq = nq;
-    f->K = K;
-    f->U = kMultiU;
-    f->FULL = 1;
-    f->R = kMultiR;
-    f->NTL = 1;
-    f->ticks = kPrefilterTicks;
-    f->NG = ng;
-    f->grid = grid;
-    f->block = kMultiBlock;
-    f->wg_per_cu = 1;
-    f->lds_bytes = (int32_t)((size_t)staged * D * 4 + lists);
-    return CHIP_OK;
 }
 
 // E of DESIGN.md 3: (gamma_32 + gamma_64) N^2 + D 2^-148 with gamma_32 = 2 D u / (1 - 2 D u), u = 2^-24, gamma_64 = (D + 8) 2^-53 / (1 - (D + 8) 2^-53),
@@ -2334,22 +1990,36 @@ bool scan_prefilter_usable(const Ctx *c)
     return n * n <= std::ldexp(1.0, 120) && 2.0 * c->D * std::ldexp(1.0, -24) < 0.5;   // no overflow of an fp32 partial sum (false for NaN as well)
 }
 
-int launch_scan_prefilter(Ctx *c, hipStream_t s, const PrefilterArgs &a, int grid)
+// a shared pass as planned: the launch and the record of it (Ctx::last_scan)
+template <class Kernel>
+static int launch_pass(Ctx *c, hipStream_t s, Kernel kernel, const PassArgs &a, chip_debug_scan_launch f)
 {
-    chip_debug_scan_launch f;
-    if (grid > c->max_grid || scan_prefilter_plan(c->D, c->elem, a.K, grid, &f) != CHIP_OK) return CHIP_ERR_UNSUPPORTED;
-    auto go = [&](auto kernel) -> int {
-        CHIP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, f.lds_bytes));
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kMultiBlock), f.lds_bytes, s, a);
-        CHIP_HIP(c, hipGetLastError());
-        return CHIP_OK;
-    };
-    const int rc = f.NG == 0 ? go(db_scan_prefilter<0>) : go(db_scan_prefilter<kPrefilterMaxNG>);
-    if (rc != CHIP_OK) return rc;
+    CHIP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, f.lds_bytes));
+    hipLaunchKernelGGL(kernel, dim3(f.grid), dim3(kMultiBlock), f.lds_bytes, s, a);
+    CHIP_HIP(c, hipGetLastError());
     f.n_rows = a.n_rows;
     f.launches = c->last_scan.launches + 1;
     c->last_scan = f;
     return CHIP_OK;
+}
+
+int launch_scan_multi(Ctx *c, hipStream_t s, const PassArgs &a, int n_ticks, int grid)
+{
+    chip_debug_scan_launch f;
+    if (n_ticks > scan_multi_max_ticks(c) || grid > c->max_grid || scan_multi_plan(c->D, c->elem, n_ticks, a.K, grid, &f) != CHIP_OK)
+        return CHIP_ERR_UNSUPPORTED;
+    if (c->elem == 4) return n_ticks == 2 ? launch_pass(c, s, db_scan_topk_multi<2>, a, f) : launch_pass(c, s, db_scan_topk_multi<3>, a, f);
+    static_assert(kSharedF64MaxTicks == 2 && kSharedMaxNG == 2, "the instantiations below");
+    if (f.NG == 0) return launch_pass(c, s, db_scan_shared_f64<2, 0>, a, f);
+    if (f.NG == 1) return launch_pass(c, s, db_scan_shared_f64<2, 1>, a, f);
+    return launch_pass(c, s, db_scan_shared_f64<2, 2>, a, f);
+}
+
+int launch_scan_prefilter(Ctx *c, hipStream_t s, const PassArgs &a, int grid)
+{
+    chip_debug_scan_launch f;
+    if (grid > c->max_grid || scan_prefilter_plan(c->D, c->elem, a.K, grid, &f) != CHIP_OK) return CHIP_ERR_UNSUPPORTED;
+    return f.NG == 0 ? launch_pass(c, s, db_scan_prefilter<0>, a, f) : launch_pass(c, s, db_scan_prefilter<kPrefilterMaxNG>, a, f);
 }
 
 int launch_rescore(Ctx *c, hipStream_t s, const RescoreArgs &a)

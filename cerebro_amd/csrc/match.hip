@@ -1,23 +1,25 @@
 // match.hip -- the candidate verification front end on gfx950: what the reference's loop-candidate consumer runs per candidate between
 // the descriptor scan and the three pose solves (include/cerebro_hip.h, "candidate verification front end", has the definitions):
 //
-//   orb_bf_match    : cv::BFMatcher(NORM_HAMMING).match(d1, d2) (src/utils/PointFeatureMatching.cpp:38-41).  One query descriptor per
-//                     lane in 8 VGPRs, the train descriptors staged through LDS in tiles of 1024 (32 KiB); every lane of a wave reads the
-//                     SAME LDS address (a broadcast, conflict-free), xor + popcount, running (distance, index) per lane; the scan goes
-//                     in index order with a strict <, so ties keep the lowest train index.  One launch, ceil(n1 / 256) workgroups.
+//   hamming_match_split : cv::BFMatcher(NORM_HAMMING).match(d1, d2) (src/utils/PointFeatureMatching.cpp:38-41).  One query descriptor per
+//                     lane in 8 VGPRs, one tile of 1024 train descriptors (32 KiB) staged through LDS per workgroup; every lane of a wave
+//                     reads the SAME LDS address (a broadcast, conflict-free), xor + popcount, running (distance, index) per lane; the
+//                     scan goes in index order with a strict <, and the tiles of a candidate meet in one 64-bit unsigned atomic minimum
+//                     of distance << 32 | index, so ties keep the lowest train index.  Grid: query blocks of 256 x train tiles x candidates.
 //   gms_filter      : gms_matcher::GetInlierMask(.., false, false) (src/utils/GMSMatcher/gms_matcher.cpp:9-15 -> run(1), :150-181) in ONE
 //                     workgroup: per grid type 1..4 (:158) the 400 x 400 motion-statistics table (global scratch of the ctx; integer
 //                     atomicAdd, order-independent) and the per-left-cell counts (LDS) of AssignMatchPairs (:73-98), then
 //                     VerifyCellPairs (:100-148, rotation pattern 1 = identity) with one wave per table row for the first-maximum
 //                     search and one lane per left cell for the 3 x 3 score against 6 * sqrt(mean count), then the inlier marks (:169-177).
-//   pose_sets_build : MiscUtils::dmatch_2_eigen (src/utils/MiscUtils.cpp:121-143) + the two make_3d_2d_collection__ calls and
+//   gms_batch       : the same pass (gms_pass) with one workgroup per (grid type, candidate), on the matcher's keys.
+//   pose_sets_batch : MiscUtils::dmatch_2_eigen (src/utils/MiscUtils.cpp:121-143) + the two make_3d_2d_collection__ calls and
 //                     make_3d_3d_collection__using__pfmatches_and_disparity (PointFeatureMatching.cpp:95-195) as ONE ordered stream
-//                     compaction (ballot + prefix popcount per wave, scan across the 16 waves): outputs are in match order, in the
-//                     layout pnp.hip / icp.hip take.
-//   chip_match_batch: one query frame against B <= 16 candidates -- hamming_match_split, gms_batch and pose_sets_batch are the three kernels
-//                     with a candidate dimension in the grid, sharing the loop, the GMS pass (gms_pass) and the compaction
-//                     (pose_sets_body) with them; the train tiles of a candidate are separate workgroups whose partial minima meet in
-//                     one 64-bit unsigned atomic minimum of distance << 32 | index.  chip_match_pair keeps its own three kernels.
+//                     compaction per candidate (ballot + prefix popcount per wave, scan across the 16 waves): outputs are in match
+//                     order, in the layout pnp.hip / icp.hip take.
+//
+// There is ONE device pipeline, match_run: one query frame against B <= 16 candidates through hamming_match_split, gms_batch and
+// pose_sets_batch.  chip_match_batch is that; chip_match_pair is a batch of one; chip_orb_match is the first kernel alone with one
+// candidate and keys of its own.  gms_filter serves chip_gms_filter alone (an arbitrary match list, which the keys cannot express).
 //
 // Nothing here rounds twice: float division / multiplication, the float -> double widenings, fp64 add / multiply / divide / sqrt are
 // single IEEE operations (-ffp-contract=off), the rest is integer.  tests/np_mirror_match.py restates all of it in numpy and
@@ -38,40 +40,14 @@ constexpr int kBfThreads = 256;
 constexpr int kBfTile = 1024;            // train descriptors per LDS tile: 1024 x 32 B = 32 KiB
 constexpr int kGrid = 20;                // mGridSizeLeft = Size(20, 20) (gms_matcher.h:62); right grid = left x the scale ratio of index 0 = 1.0 (:46, :230-231)
 constexpr int kCells = kGrid * kGrid;    // 400
-constexpr int kOneWg = 1024;             // gms_filter / pose_sets_build: one workgroup of 16 waves
+constexpr int kOneWg = 1024;             // the GMS and set-building kernels: one workgroup of 16 waves
 constexpr int kMaxImageSide = 16384;
-
-// ------------------------------------------------------------------------------------------------ orb_bf_match
-__global__ __launch_bounds__(kBfThreads) void orb_bf_match(const uint4 *__restrict__ query, int n1, const uint4 *__restrict__ train, int n2,
-                                                           int32_t *__restrict__ train_idx, int32_t *__restrict__ distance)
-{
-    __shared__ uint4 tile[2 * kBfTile];
-    const int i = blockIdx.x * kBfThreads + threadIdx.x;
-    const int qi = i < n1 ? i : n1 - 1;                       // n1 >= 1: the tail lanes scan a valid descriptor and store nothing
-    const uint4 q0 = query[2 * (size_t)qi], q1 = query[2 * (size_t)qi + 1];
-    int best = INT_MAX, bidx = -1;
-    for (int base = 0; base < n2; base += kBfTile) {
-        const int cnt = n2 - base < kBfTile ? n2 - base : kBfTile;
-        __syncthreads();                                      // the previous tile has been read by every wave
-        for (int e = threadIdx.x; e < 2 * cnt; e += kBfThreads) tile[e] = train[2 * (size_t)base + e];
-        __syncthreads();
-#pragma unroll 4
-        for (int j = 0; j < cnt; j++) {
-            const uint4 a = tile[2 * j], b = tile[2 * j + 1];  // wave-uniform address: one broadcast read
-            const int d = __popc(q0.x ^ a.x) + __popc(q0.y ^ a.y) + __popc(q0.z ^ a.z) + __popc(q0.w ^ a.w) +
-                          __popc(q1.x ^ b.x) + __popc(q1.y ^ b.y) + __popc(q1.z ^ b.z) + __popc(q1.w ^ b.w);
-            if (d < best) { best = d; bidx = base + j; }      // strict: the first minimum stays
-        }
-    }
-    if (i < n1) { train_idx[i] = bidx; distance[i] = bidx >= 0 ? best : -1; }
-}
 
 // ------------------------------------------------------------------------------------------------ gms_filter
 struct GmsArgs {
     const float2 *kp1, *kp2;
     int32_t w1, h1, w2, h2;
-    const int32_t *qidx;        // nullptr: match i is (i, tidx[i]) -- the output of orb_bf_match
-    const int32_t *tidx;
+    const int32_t *qidx, *tidx; // match i is (qidx[i], tidx[i])
     int32_t n;
     int32_t *table;             // [400][400] motion statistics (mMotionStatistics, gms_matcher.h:93)
     uint8_t *inlier;            // [n]
@@ -182,6 +158,7 @@ __device__ __forceinline__ void gms_pass(int type, int n, int32_t *table, float 
     __syncthreads();                                      // pair / cnt are rewritten by the next pass
 }
 
+// chip_gms_filter alone: the four grid types on an explicit (qidx, tidx) list, which the pipeline's keys (match i = query i) cannot express
 __global__ __launch_bounds__(kOneWg) void gms_filter(GmsArgs a)
 {
     __shared__ int32_t total;
@@ -190,7 +167,7 @@ __global__ __launch_bounds__(kOneWg) void gms_filter(GmsArgs a)
     for (int i = tid; i < a.n; i += kOneWg) a.inlier[i] = 0;   // mvbInlierMask.assign(false) (gms_matcher.cpp:152); own bytes, same lane later
     for (int type = 1; type <= 4; type++)                     // :158
         gms_pass(type, a.n, a.table, (float)a.w1, (float)a.h1, (float)a.w2, (float)a.h2,
-                 [&](int i, float2 *lp, float2 *rp) { *lp = a.kp1[a.qidx ? a.qidx[i] : i]; *rp = a.kp2[a.tidx[i]]; },
+                 [&](int i, float2 *lp, float2 *rp) { *lp = a.kp1[a.qidx[i]]; *rp = a.kp2[a.tidx[i]]; },
                  [&](int i, bool hit) { if (hit) a.inlier[i] = 1; });
     int mine = 0;
     for (int i = tid; i < a.n; i += kOneWg) mine += a.inlier[i];
@@ -201,12 +178,10 @@ __global__ __launch_bounds__(kOneWg) void gms_filter(GmsArgs a)
     if (tid == 0) *a.n_inliers = total;                       // :179
 }
 
-// ------------------------------------------------------------------------------------------------ pose_sets_build
+// ------------------------------------------------------------------------------------------------ the correspondence sets
 enum { kSetUv = 0, kSetAb = 1, kSetBa = 2, kSet33 = 3, kSetOut = 4, kNSets = 5 };
 struct SetsArgs {
     const float2 *kp1, *kp2;
-    const int32_t *tidx;          // match i = (i, tidx[i])
-    const uint8_t *inlier;
     int32_t n;
     const float *xyz_a, *xyz_b;   // H x W x 3
     int32_t w1, h1, w2, h2;
@@ -228,7 +203,7 @@ __device__ __forceinline__ bool pixel_of(float2 p, int w, int h, int *x, int *y)
 __device__ __forceinline__ bool depth_ok(float z) { return !((double)z < 0.1 || (double)z > 25.); }
 
 // The ordered compaction by ONE workgroup of kOneWg threads; inlier(i) / train(i): the GMS mark and the train index of match i
-// (pose_sets_build: the arrays of a; pose_sets_batch: the four planes of gms_batch and the merged keys)
+// (pose_sets_batch: the four planes of gms_batch and the merged keys)
 template <class Inlier, class Train>
 __device__ __forceinline__ void pose_sets_body(const SetsArgs &a, Inlier inlier, Train train)
 {
@@ -294,14 +269,9 @@ __device__ __forceinline__ void pose_sets_body(const SetsArgs &a, Inlier inlier,
     if (tid < kNSets) a.counts[tid] = run[tid];
 }
 
-__global__ __launch_bounds__(kOneWg) void pose_sets_build(SetsArgs a)
-{
-    pose_sets_body(a, [&](int i) { return a.inlier[i] != 0; }, [&](int i) { return a.tidx[i]; });
-}
-
 // ------------------------------------------------------------------------------------------------ one query frame, B candidates
-// chip_match_batch: the three kernels above with a candidate dimension in the grid.  Candidate j's descriptors, keypoints, 3-D image and
-// sizes travel in the kernel arguments; all B pairs read ONE device copy of the query frame.
+// The three kernels of the pipeline have a candidate dimension in the grid.  Candidate j's descriptors, keypoints, 3-D image and sizes
+// travel in the kernel arguments; all B pairs read ONE device copy of the query frame.
 constexpr int kMaxBatch = CHIP_MATCH_MAX_BATCH;
 struct BatchCand {
     const uint4 *desc;            // n x 2
@@ -312,11 +282,11 @@ struct BatchCand {
 struct BatchCands { BatchCand c[kMaxBatch]; };
 
 // A partial minimum as ONE unsigned 64-bit key, distance << 32 | train index: the unsigned minimum over the tiles of a (query, candidate)
-// is the smallest distance and, among equal distances, the LOWEST index -- the tie rule of orb_bf_match, whichever tile arrives first.
+// is the smallest distance and, among equal distances, the LOWEST index -- BFMatcher's tie rule, whichever tile arrives first.
 // All ones (the preset) decodes to index -1, distance -1: no train descriptors.
 __device__ __forceinline__ int32_t key_train(unsigned long long k) { return (int32_t)(uint32_t)k; }
 
-// grid (query blocks of 256, train tiles of 1024, B): orb_bf_match's loop over ONE tile; a tile past the candidate's n leaves at once
+// grid (query blocks of 256, train tiles of 1024, B): one workgroup scans ONE tile; a tile past the candidate's n leaves at once
 __global__ __launch_bounds__(kBfThreads) void hamming_match_split(const uint4 *__restrict__ query, int n1, BatchCands cands,
                                                                   unsigned long long *__restrict__ keys /* [B][n1] */)
 {
@@ -376,7 +346,7 @@ struct SetsBatchArgs {
     int32_t *counts;                      // [B][kNSets]
     BatchCands cands;
 };
-// grid B: pose_sets_build for candidate blockIdx.x, inlier = the OR of its four planes, outputs into its slabs
+// grid B: the sets of candidate blockIdx.x, inlier = the OR of its four planes, outputs into its slabs
 __global__ __launch_bounds__(kOneWg) void pose_sets_batch(SetsBatchArgs b)
 {
     const int z = blockIdx.x;
@@ -386,7 +356,7 @@ __global__ __launch_bounds__(kOneWg) void pose_sets_batch(SetsBatchArgs b)
     }
     const size_t row = (size_t)z * b.n1;
     SetsArgs a;
-    a.kp1 = b.kp1; a.kp2 = b.cands.c[z].kp; a.tidx = nullptr; a.inlier = nullptr; a.n = b.n1;
+    a.kp1 = b.kp1; a.kp2 = b.cands.c[z].kp; a.n = b.n1;
     a.xyz_a = b.xyz_a; a.xyz_b = b.cands.c[z].xyz; a.w1 = b.w1; a.h1 = b.h1; a.w2 = b.cands.c[z].w; a.h2 = b.cands.c[z].h;
     for (int k = 0; k < 9; k++) a.Kinv[k] = b.Kinv[k];
     a.uv = b.uv + 2 * row; a.uv_d = b.uv_d + 2 * row; a.X_ab = b.X_ab + 3 * row; a.uvn_ab = b.uvn_ab + 2 * row;
@@ -400,44 +370,43 @@ __global__ __launch_bounds__(kOneWg) void pose_sets_batch(SetsBatchArgs b)
 
 // ------------------------------------------------------------------------------------------------ host side
 struct MatchState {
-    // inputs / intermediates, sized for kMatchMax keypoints once
-    DevBuf<uint8_t> d1, d2;
-    DevBuf<float2> kp1, kp2;
-    DevBuf<int32_t> qidx, tidx, dist, table, counts;
+    // the stand-alone calls, sized for kMatchMax keypoints once; d1 / kp1 also hold the query frame of a pipeline run, and nothing that
+    // a run leaves for later calls (keys, sets, summaries) is in this group
+    DevBuf<uint8_t> d1, d2;                     // d2: chip_orb_match's train descriptors
+    DevBuf<unsigned long long> orb_keys;        // chip_orb_match's own keys, never the slab of a run
+    DevBuf<float2> kp1, kp2;                    // kp2, qidx, tidx, inlier: chip_gms_filter's
+    DevBuf<int32_t> qidx, tidx;
     DevBuf<uint8_t> inlier;
-    // the five sets chip_match_pair leaves on the device
+    DevBuf<int32_t> counts;                     // [kMaxBatch][kNSets] of a run; chip_gms_filter's inlier count borrows [0]
+    PinnedBuf<int32_t> h_counts;
+    // a pipeline run: the frames, the merged keys, one table and one plane per (candidate, grid type) and the five sets in slabs of n1
+    // rows per candidate; all grown on demand (batch_reserve)
+    DevBuf<float> xyz_a;
+    DevBuf<uint8_t> desc;                       // candidate j at desc + 32 * (n of the candidates before it), kp alike
+    DevBuf<float2> kp;
+    DevBuf<float> xyz;
+    DevBuf<unsigned long long> keys;
+    DevBuf<int32_t> table;                      // match_state() reserves the one table of chip_gms_filter
+    DevBuf<uint8_t> plane;
     DevBuf<double> uv, uv_d, X_ab, uvn_ab, X_ba, uvn_ba, A, B;
     DevBuf<int32_t> mq, mt;
-    DevBuf<float> xyz_a, xyz_b;                 // grown on demand
-    PinnedBuf<int32_t> h_counts;
-    // chip_match_batch: the candidates' frames, the merged keys, one table and one plane per (candidate, grid type) and the five sets in
-    // slabs of n1 rows per candidate; all grown on demand (batch_reserve)
-    DevBuf<uint8_t> b_desc;                     // candidate j at b_desc + 32 * (n of the candidates before it), b_kp alike
-    DevBuf<float2> b_kp;
-    DevBuf<float> b_xyz;
-    DevBuf<unsigned long long> b_keys;
-    DevBuf<int32_t> b_table, b_counts;
-    DevBuf<uint8_t> b_plane;
-    DevBuf<double> b_uv, b_uv_d, b_X_ab, b_uvn_ab, b_X_ba, b_uvn_ba, b_A, b_B;
-    DevBuf<int32_t> b_mq, b_mt;
-    PinnedBuf<int32_t> h_bcounts;
-    std::vector<unsigned long long> h_keys;     // chip_match_batch_read_matches: one candidate's keys on their way out
-    hipEvent_t b_ev[4] = {};                    // tuning only (CHIP_MATCH_BATCH_TIMING=1): around the three launches of a batch
-    // what the last chip_match_pair / chip_match_batch left: n_cand candidates (a pair: one), of which ONE is selected -- the pointers and
-    // counts chip_match_read_sets and the _matched solvers work on
+    std::vector<unsigned long long> h_keys;     // fetch_matches: keys on their way out
+    hipEvent_t ev[4] = {};                      // tuning only (CHIP_MATCH_BATCH_TIMING=1): around the three launches of a run
+    // what the last run left: n_cand candidates of a query frame of n1 keypoints, of which ONE is selected -- the pointers and counts
+    // chip_match_read_sets and the _matched solvers work on
     struct Sets { double *uv, *uv_d, *X_ab, *uvn_ab, *X_ba, *uvn_ba, *A, *B; int32_t *mq, *mt; };
     bool have_sets = false;
-    bool from_batch = false;                    // the candidates are chip_match_batch's (slabs of batch_n1 rows)
-    int32_t n_cand = 0, batch_n1 = 0;
+    bool keys_readable = false;                 // API behaviour, not a buffer selector: chip_match_batch_read_matches answers only after a
+                                                // chip_match_batch, CHIP_ERR_BUSY after a chip_match_pair
+    int32_t n_cand = 0, n1 = 0;
     chip_match_summary cand_sm[CHIP_MATCH_MAX_BATCH] = {};
     Sets cur{};
     chip_match_summary last{};                  // the selected candidate's summary
 
     void select(int32_t j)                      // 0 <= j < n_cand
     {
-        const size_t r = from_batch ? (size_t)j * (size_t)batch_n1 : 0;
-        if (from_batch) cur = Sets{b_uv + 2 * r, b_uv_d + 2 * r, b_X_ab + 3 * r, b_uvn_ab + 2 * r, b_X_ba + 3 * r, b_uvn_ba + 2 * r, b_A + 3 * r, b_B + 3 * r, b_mq + r, b_mt + r};
-        else cur = Sets{uv, uv_d, X_ab, uvn_ab, X_ba, uvn_ba, A, B, mq, mt};
+        const size_t r = (size_t)j * (size_t)n1;
+        cur = Sets{uv + 2 * r, uv_d + 2 * r, X_ab + 3 * r, uvn_ab + 2 * r, X_ba + 3 * r, uvn_ba + 2 * r, A + 3 * r, B + 3 * r, mq + r, mt + r};
         last = cand_sm[j];
     }
 };
@@ -445,7 +414,7 @@ struct MatchState {
 void match_destroy(Ctx *c)
 {
     if (c->match_state)
-        for (hipEvent_t e : c->match_state->b_ev)
+        for (hipEvent_t e : c->match_state->ev)
             if (e) (void)hipEventDestroy(e);
     delete c->match_state;
     c->match_state = nullptr;
@@ -464,25 +433,15 @@ static int match_state(Ctx *c, MatchState **out)
     const size_t n = kMatchMax;
     int rc = st->d1.reserve(c, n * CHIP_ORB_DESC_BYTES);
     if (rc == CHIP_OK) rc = st->d2.reserve(c, n * CHIP_ORB_DESC_BYTES);
+    if (rc == CHIP_OK) rc = st->orb_keys.reserve(c, n);
     if (rc == CHIP_OK) rc = st->kp1.reserve(c, n);
     if (rc == CHIP_OK) rc = st->kp2.reserve(c, n);
     if (rc == CHIP_OK) rc = st->qidx.reserve(c, n);
     if (rc == CHIP_OK) rc = st->tidx.reserve(c, n);
-    if (rc == CHIP_OK) rc = st->dist.reserve(c, n);
-    if (rc == CHIP_OK) rc = st->table.reserve(c, (size_t)kCells * kCells);
-    if (rc == CHIP_OK) rc = st->counts.reserve(c, 8);
     if (rc == CHIP_OK) rc = st->inlier.reserve(c, n);
-    if (rc == CHIP_OK) rc = st->uv.reserve(c, n * 2);
-    if (rc == CHIP_OK) rc = st->uv_d.reserve(c, n * 2);
-    if (rc == CHIP_OK) rc = st->X_ab.reserve(c, n * 3);
-    if (rc == CHIP_OK) rc = st->uvn_ab.reserve(c, n * 2);
-    if (rc == CHIP_OK) rc = st->X_ba.reserve(c, n * 3);
-    if (rc == CHIP_OK) rc = st->uvn_ba.reserve(c, n * 2);
-    if (rc == CHIP_OK) rc = st->A.reserve(c, n * 3);
-    if (rc == CHIP_OK) rc = st->B.reserve(c, n * 3);
-    if (rc == CHIP_OK) rc = st->mq.reserve(c, n);
-    if (rc == CHIP_OK) rc = st->mt.reserve(c, n);
-    if (rc == CHIP_OK) rc = st->h_counts.reserve(c, 8);
+    if (rc == CHIP_OK) rc = st->table.reserve(c, (size_t)kCells * kCells);
+    if (rc == CHIP_OK) rc = st->counts.reserve(c, kMaxBatch * kNSets);
+    if (rc == CHIP_OK) rc = st->h_counts.reserve(c, kMaxBatch * kNSets);
     return rc;
 }
 
@@ -492,22 +451,25 @@ static hipStream_t match_stream(Ctx *c)
     return c->s_query;
 }
 
-static int launch_bf(Ctx *c, hipStream_t s, MatchState *st, int n1, int n2)
+// n1 >= 1 queries against B candidates of at most max_n2 >= 1 train descriptors; keys [B][n1] preset to all ones
+static int launch_matcher(Ctx *c, hipStream_t s, const uint8_t *query, int n1, const BatchCands &cands, int max_n2, int B, unsigned long long *keys)
 {
-    hipLaunchKernelGGL(orb_bf_match, dim3((n1 + kBfThreads - 1) / kBfThreads), dim3(kBfThreads), 0, s,
-                       reinterpret_cast<const uint4 *>(st->d1.get()), n1, reinterpret_cast<const uint4 *>(st->d2.get()), n2, st->tidx.get(), st->dist.get());
+    hipLaunchKernelGGL(hamming_match_split, dim3((n1 + kBfThreads - 1) / kBfThreads, (max_n2 + kBfTile - 1) / kBfTile, B), dim3(kBfThreads), 0, s,
+                       reinterpret_cast<const uint4 *>(query), n1, cands, keys);
     CHIP_HIP(c, hipGetLastError());
     return CHIP_OK;
 }
 
-static int launch_gms(Ctx *c, hipStream_t s, MatchState *st, bool identity_queries, int n, int w1, int h1, int w2, int h2)
+// n keys off the device as BFMatcher's (trainIdx, distance); all ones -> -1 / -1: no train descriptors
+static int fetch_matches(Ctx *c, hipStream_t s, MatchState *st, const unsigned long long *keys, size_t n, int32_t *train_idx, int32_t *distance)
 {
-    GmsArgs g;
-    g.kp1 = st->kp1; g.kp2 = st->kp2; g.w1 = w1; g.h1 = h1; g.w2 = w2; g.h2 = h2;
-    g.qidx = identity_queries ? nullptr : st->qidx; g.tidx = st->tidx; g.n = n;
-    g.table = st->table; g.inlier = st->inlier; g.n_inliers = st->counts + 7;
-    hipLaunchKernelGGL(gms_filter, dim3(1), dim3(kOneWg), 0, s, g);
-    CHIP_HIP(c, hipGetLastError());
+    st->h_keys.resize(n);
+    CHIP_HIP(c, hipMemcpyAsync(st->h_keys.data(), keys, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    CHIP_HIP(c, hipStreamSynchronize(s));
+    for (size_t i = 0; i < n; i++) {
+        train_idx[i] = (int32_t)(uint32_t)st->h_keys[i];
+        distance[i] = (int32_t)(uint32_t)(st->h_keys[i] >> 32);
+    }
     return CHIP_OK;
 }
 
@@ -519,36 +481,127 @@ static int check_frame(const chip_match_frame *f)
     return CHIP_OK;
 }
 
-// chip_match_batch's buffers for B candidates of a query frame of n1 keypoints: tot_n keypoints and tot_px pixels over all candidates.
+// The buffers of a run for B candidates of a query frame of n1 keypoints: tot_n keypoints and tot_px pixels over all candidates.
 // Whatever has to grow grows inside ONE pause (as match_state).
 static int batch_reserve(Ctx *c, MatchState *st, size_t B, size_t n1, size_t tot_n, size_t tot_px, size_t px_a)
 {
     const size_t rows = B * n1;
-    const bool fits = st->xyz_a.capacity() >= 3 * px_a && st->b_desc.capacity() >= tot_n * CHIP_ORB_DESC_BYTES && st->b_kp.capacity() >= tot_n &&
-                      st->b_xyz.capacity() >= 3 * tot_px && st->b_keys.capacity() >= rows && st->b_table.capacity() >= B * 4 * kCells * kCells &&
-                      st->b_plane.capacity() >= 4 * rows && st->b_uv.capacity() >= 2 * rows && st->b_counts.capacity() && st->h_bcounts.capacity();
-    if (fits) return CHIP_OK;   // the set buffers grow together with b_uv
+    const bool fits = st->xyz_a.capacity() >= 3 * px_a && st->desc.capacity() >= tot_n * CHIP_ORB_DESC_BYTES && st->kp.capacity() >= tot_n &&
+                      st->xyz.capacity() >= 3 * tot_px && st->keys.capacity() >= rows && st->table.capacity() >= B * 4 * kCells * kCells &&
+                      st->plane.capacity() >= 4 * rows && st->uv.capacity() >= 2 * rows;
+    if (fits) return CHIP_OK;   // the set buffers grow together with uv
     ResidentPause paused(c);
     int rc = st->xyz_a.reserve(c, 3 * px_a);
-    if (rc == CHIP_OK) rc = st->b_desc.reserve(c, tot_n * CHIP_ORB_DESC_BYTES);
-    if (rc == CHIP_OK) rc = st->b_kp.reserve(c, tot_n);
-    if (rc == CHIP_OK) rc = st->b_xyz.reserve(c, 3 * tot_px);
-    if (rc == CHIP_OK) rc = st->b_keys.reserve(c, rows);
-    if (rc == CHIP_OK) rc = st->b_table.reserve(c, B * 4 * kCells * kCells);
-    if (rc == CHIP_OK) rc = st->b_plane.reserve(c, 4 * rows);
-    if (rc == CHIP_OK) rc = st->b_uv_d.reserve(c, 2 * rows);
-    if (rc == CHIP_OK) rc = st->b_X_ab.reserve(c, 3 * rows);
-    if (rc == CHIP_OK) rc = st->b_uvn_ab.reserve(c, 2 * rows);
-    if (rc == CHIP_OK) rc = st->b_X_ba.reserve(c, 3 * rows);
-    if (rc == CHIP_OK) rc = st->b_uvn_ba.reserve(c, 2 * rows);
-    if (rc == CHIP_OK) rc = st->b_A.reserve(c, 3 * rows);
-    if (rc == CHIP_OK) rc = st->b_B.reserve(c, 3 * rows);
-    if (rc == CHIP_OK) rc = st->b_mq.reserve(c, rows);
-    if (rc == CHIP_OK) rc = st->b_mt.reserve(c, rows);
-    if (rc == CHIP_OK) rc = st->b_counts.reserve(c, kMaxBatch * kNSets);
-    if (rc == CHIP_OK) rc = st->h_bcounts.reserve(c, kMaxBatch * kNSets);
-    if (rc == CHIP_OK) rc = st->b_uv.reserve(c, 2 * rows);   // last: its capacity stands for the whole group of set buffers
+    if (rc == CHIP_OK) rc = st->desc.reserve(c, tot_n * CHIP_ORB_DESC_BYTES);
+    if (rc == CHIP_OK) rc = st->kp.reserve(c, tot_n);
+    if (rc == CHIP_OK) rc = st->xyz.reserve(c, 3 * tot_px);
+    if (rc == CHIP_OK) rc = st->keys.reserve(c, rows);
+    if (rc == CHIP_OK) rc = st->table.reserve(c, B * 4 * kCells * kCells);
+    if (rc == CHIP_OK) rc = st->plane.reserve(c, 4 * rows);
+    if (rc == CHIP_OK) rc = st->uv_d.reserve(c, 2 * rows);
+    if (rc == CHIP_OK) rc = st->X_ab.reserve(c, 3 * rows);
+    if (rc == CHIP_OK) rc = st->uvn_ab.reserve(c, 2 * rows);
+    if (rc == CHIP_OK) rc = st->X_ba.reserve(c, 3 * rows);
+    if (rc == CHIP_OK) rc = st->uvn_ba.reserve(c, 2 * rows);
+    if (rc == CHIP_OK) rc = st->A.reserve(c, 3 * rows);
+    if (rc == CHIP_OK) rc = st->B.reserve(c, 3 * rows);
+    if (rc == CHIP_OK) rc = st->mq.reserve(c, rows);
+    if (rc == CHIP_OK) rc = st->mt.reserve(c, rows);
+    if (rc == CHIP_OK) rc = st->uv.reserve(c, 2 * rows);   // last: its capacity stands for the whole group of set buffers
     return rc;
+}
+
+// The pipeline: frame a against the candidates b[0 .. B) -- uploads, three launches, the counts back -- leaves the keys and the five sets
+// of every candidate in its slab, cand_sm[0 .. B) filled and candidate 0 selected.  match_mu held, the arguments checked, have_sets false.
+static int match_run(Ctx *c, MatchState *st, const chip_match_frame *a, const chip_match_frame *b, int B, const double Kinv[9])
+{
+    const int n1 = a->n;
+    int max_n2 = 0;
+    size_t tot_n = 0, tot_px = 0;
+    for (int j = 0; j < B; j++) {
+        if (b[j].n == 0) continue;               // an empty candidate is not uploaded: no matches (BFMatcher on an empty descriptor matrix)
+        max_n2 = b[j].n > max_n2 ? b[j].n : max_n2;
+        tot_n += (size_t)b[j].n;
+        tot_px += (size_t)b[j].width * b[j].height;
+    }
+    for (int j = 0; j < B; j++) std::memset(&st->cand_sm[j], 0, sizeof(chip_match_summary));
+    if (n1 > 0) {
+        const size_t px_a = (size_t)a->width * a->height;
+        int rc = batch_reserve(c, st, (size_t)B, (size_t)n1, tot_n, tot_px, px_a);
+        if (rc != CHIP_OK) return rc;
+        hipStream_t s = match_stream(c);
+        CHIP_HIP(c, hipMemsetAsync(st->keys, 0xff, (size_t)B * n1 * sizeof(unsigned long long), s));   // all ones: no match yet
+        if (max_n2 > 0) {
+            CHIP_HIP(c, hipMemcpyAsync(st->d1, a->desc, (size_t)n1 * CHIP_ORB_DESC_BYTES, hipMemcpyHostToDevice, s));
+            CHIP_HIP(c, hipMemcpyAsync(st->kp1, a->kp_xy, (size_t)n1 * sizeof(float2), hipMemcpyHostToDevice, s));
+            CHIP_HIP(c, hipMemcpyAsync(st->xyz_a, a->xyz, 3 * px_a * sizeof(float), hipMemcpyHostToDevice, s));
+            BatchCands cands;
+            std::memset(&cands, 0, sizeof cands);
+            size_t off_n = 0, off_px = 0;
+            for (int j = 0; j < B; j++) {
+                const int n2 = b[j].n;
+                if (n2 == 0) continue;
+                const size_t px = (size_t)b[j].width * b[j].height;
+                uint8_t *dd = st->desc + off_n * CHIP_ORB_DESC_BYTES;
+                float2 *dk = st->kp + off_n;
+                float *dx = st->xyz + 3 * off_px;
+                CHIP_HIP(c, hipMemcpyAsync(dd, b[j].desc, (size_t)n2 * CHIP_ORB_DESC_BYTES, hipMemcpyHostToDevice, s));
+                CHIP_HIP(c, hipMemcpyAsync(dk, b[j].kp_xy, (size_t)n2 * sizeof(float2), hipMemcpyHostToDevice, s));
+                CHIP_HIP(c, hipMemcpyAsync(dx, b[j].xyz, 3 * px * sizeof(float), hipMemcpyHostToDevice, s));
+                cands.c[j] = BatchCand{reinterpret_cast<const uint4 *>(dd), dk, dx, n2, b[j].width, b[j].height, 0};
+                off_n += (size_t)n2; off_px += px;
+            }
+            // tuning only (CHIP_MATCH_BATCH_TIMING=1): device time of each of the three kernels by events, averaged, printed at process exit
+            struct KernelTiming {
+                double acc[3] = {0, 0, 0}; long n = 0; bool on = std::getenv("CHIP_MATCH_BATCH_TIMING") != nullptr;
+                ~KernelTiming() { if (on && n) std::fprintf(stderr, "match batch kernel timing over %ld calls (us): hamming_match_split %.1f, gms_batch %.1f, pose_sets_batch %.1f\n",
+                                                            n, 1e3 * acc[0] / n, 1e3 * acc[1] / n, 1e3 * acc[2] / n); }
+            };
+            static KernelTiming kt;
+            if (kt.on)
+                for (hipEvent_t &e : st->ev)
+                    if (!e) CHIP_HIP(c, hipEventCreate(&e));
+            if (kt.on) CHIP_HIP(c, hipEventRecord(st->ev[0], s));
+            rc = launch_matcher(c, s, st->d1, n1, cands, max_n2, B, st->keys);
+            if (rc != CHIP_OK) return rc;
+            if (kt.on) CHIP_HIP(c, hipEventRecord(st->ev[1], s));
+            GmsBatchArgs ga;
+            ga.kp1 = st->kp1; ga.n1 = n1; ga.w1 = a->width; ga.h1 = a->height; ga.keys = st->keys; ga.table = st->table; ga.plane = st->plane;
+            ga.cands = cands;
+            hipLaunchKernelGGL(gms_batch, dim3(4, B), dim3(kOneWg), 0, s, ga);
+            CHIP_HIP(c, hipGetLastError());
+            if (kt.on) CHIP_HIP(c, hipEventRecord(st->ev[2], s));
+            SetsBatchArgs sa;
+            sa.kp1 = st->kp1; sa.xyz_a = st->xyz_a; sa.n1 = n1; sa.w1 = a->width; sa.h1 = a->height; sa.keys = st->keys; sa.plane = st->plane;
+            for (int i = 0; i < 9; i++) sa.Kinv[i] = Kinv[i];
+            sa.uv = st->uv; sa.uv_d = st->uv_d; sa.X_ab = st->X_ab; sa.uvn_ab = st->uvn_ab; sa.X_ba = st->X_ba; sa.uvn_ba = st->uvn_ba;
+            sa.A = st->A; sa.B = st->B; sa.mq = st->mq; sa.mt = st->mt; sa.counts = st->counts; sa.cands = cands;
+            hipLaunchKernelGGL(pose_sets_batch, dim3(B), dim3(kOneWg), 0, s, sa);
+            CHIP_HIP(c, hipGetLastError());
+            if (kt.on) CHIP_HIP(c, hipEventRecord(st->ev[3], s));
+            CHIP_HIP(c, hipMemcpyAsync(st->h_counts.host(), st->counts, (size_t)B * kNSets * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            CHIP_HIP(c, hipStreamSynchronize(s));
+            for (int k = 0; k < 3 && kt.on; k++) {
+                float ms = 0.f;
+                CHIP_HIP(c, hipEventElapsedTime(&ms, st->ev[k], st->ev[k + 1]));
+                kt.acc[k] += ms;
+            }
+            kt.n += kt.on;
+        }
+        CHIP_HIP(c, hipStreamSynchronize(s));
+        for (int j = 0; j < B && max_n2 > 0; j++) {
+            if (b[j].n == 0) continue;
+            const int32_t *h = st->h_counts.host() + j * kNSets;
+            chip_match_summary &sm = st->cand_sm[j];
+            sm.n_matches_all = n1;
+            sm.n_matches_gms = h[kSetUv]; sm.n_3d2d_ab = h[kSetAb]; sm.n_3d2d_ba = h[kSetBa]; sm.n_3d3d = h[kSet33]; sm.n_out_of_image = h[kSetOut];
+        }
+    }
+    st->n_cand = B;
+    st->n1 = n1;
+    st->select(0);
+    st->have_sets = true;
+    return CHIP_OK;
 }
 
 }  // namespace chip
@@ -568,14 +621,18 @@ extern "C" int chip_orb_match(chip_ctx *c, const uint8_t *d1, int32_t n1, const 
     int rc = match_state(c, &st);
     if (rc != CHIP_OK) return rc;
     hipStream_t s = match_stream(c);
-    CHIP_HIP(c, hipMemcpyAsync(st->d1, d1, (size_t)n1 * CHIP_ORB_DESC_BYTES, hipMemcpyHostToDevice, s));
-    if (n2 > 0) CHIP_HIP(c, hipMemcpyAsync(st->d2, d2, (size_t)n2 * CHIP_ORB_DESC_BYTES, hipMemcpyHostToDevice, s));
-    rc = launch_bf(c, s, st, n1, n2);
-    if (rc != CHIP_OK) return rc;
-    CHIP_HIP(c, hipMemcpyAsync(train_idx, st->tidx, (size_t)n1 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    CHIP_HIP(c, hipMemcpyAsync(distance, st->dist, (size_t)n1 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    CHIP_HIP(c, hipStreamSynchronize(s));
-    return CHIP_OK;
+    CHIP_HIP(c, hipMemsetAsync(st->orb_keys, 0xff, (size_t)n1 * sizeof(unsigned long long), s));   // all ones: no match yet
+    if (n2 > 0) {
+        CHIP_HIP(c, hipMemcpyAsync(st->d1, d1, (size_t)n1 * CHIP_ORB_DESC_BYTES, hipMemcpyHostToDevice, s));
+        CHIP_HIP(c, hipMemcpyAsync(st->d2, d2, (size_t)n2 * CHIP_ORB_DESC_BYTES, hipMemcpyHostToDevice, s));
+        BatchCands one;                        // the matcher reads desc and n of a candidate only
+        std::memset(&one, 0, sizeof one);
+        one.c[0].desc = reinterpret_cast<const uint4 *>(st->d2.get());
+        one.c[0].n = n2;
+        rc = launch_matcher(c, s, st->d1, n1, one, n2, 1, st->orb_keys);
+        if (rc != CHIP_OK) return rc;
+    }
+    return fetch_matches(c, s, st, st->orb_keys, (size_t)n1, train_idx, distance);
 }
 
 extern "C" int chip_gms_filter(chip_ctx *c, const float *kp1_xy, int32_t n1, int32_t w1, int32_t h1, const float *kp2_xy, int32_t n2, int32_t w2,
@@ -598,15 +655,20 @@ extern "C" int chip_gms_filter(chip_ctx *c, const float *kp1_xy, int32_t n1, int
     CHIP_HIP(c, hipMemcpyAsync(st->kp2, kp2_xy, (size_t)n2 * sizeof(float2), hipMemcpyHostToDevice, s));
     CHIP_HIP(c, hipMemcpyAsync(st->qidx, query_idx, (size_t)n_matches * sizeof(int32_t), hipMemcpyHostToDevice, s));
     CHIP_HIP(c, hipMemcpyAsync(st->tidx, train_idx, (size_t)n_matches * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    rc = launch_gms(c, s, st, false, n_matches, w1, h1, w2, h2);
-    if (rc != CHIP_OK) return rc;
+    GmsArgs g;
+    g.kp1 = st->kp1; g.kp2 = st->kp2; g.w1 = w1; g.h1 = h1; g.w2 = w2; g.h2 = h2;
+    g.qidx = st->qidx; g.tidx = st->tidx; g.n = n_matches;
+    g.table = st->table; g.inlier = st->inlier; g.n_inliers = st->counts;
+    hipLaunchKernelGGL(gms_filter, dim3(1), dim3(kOneWg), 0, s, g);
+    CHIP_HIP(c, hipGetLastError());
     CHIP_HIP(c, hipMemcpyAsync(inlier, st->inlier, (size_t)n_matches, hipMemcpyDeviceToHost, s));
-    CHIP_HIP(c, hipMemcpyAsync(st->h_counts.host(), st->counts + 7, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    CHIP_HIP(c, hipMemcpyAsync(st->h_counts.host(), st->counts, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     CHIP_HIP(c, hipStreamSynchronize(s));
     *n_inliers = st->h_counts.host()[0];
     return CHIP_OK;
 }
 
+// a batch of one
 extern "C" int chip_match_pair(chip_ctx *c, const chip_match_frame *a, const chip_match_frame *b, const double Kinv[9], chip_match_summary *summary)
 {
     if (!c || !Kinv || !summary) return CHIP_ERR_INVALID_ARG;
@@ -620,47 +682,10 @@ extern "C" int chip_match_pair(chip_ctx *c, const chip_match_frame *a, const chi
     rc = match_state(c, &st);
     if (rc != CHIP_OK) return rc;
     st->have_sets = false;
-    chip_match_summary sm;
-    std::memset(&sm, 0, sizeof sm);
-    const int n1 = a->n, n2 = b->n;
-    if (n1 > 0 && n2 > 0) {                    // an empty train set gives no matches (BFMatcher on an empty descriptor matrix)
-        const size_t fa = 3 * (size_t)a->width * a->height, fb = 3 * (size_t)b->width * b->height;
-        rc = st->xyz_a.reserve(c, fa);
-        if (rc == CHIP_OK) rc = st->xyz_b.reserve(c, fb);
-        if (rc != CHIP_OK) return rc;
-        hipStream_t s = match_stream(c);
-        CHIP_HIP(c, hipMemcpyAsync(st->d1, a->desc, (size_t)n1 * CHIP_ORB_DESC_BYTES, hipMemcpyHostToDevice, s));
-        CHIP_HIP(c, hipMemcpyAsync(st->d2, b->desc, (size_t)n2 * CHIP_ORB_DESC_BYTES, hipMemcpyHostToDevice, s));
-        CHIP_HIP(c, hipMemcpyAsync(st->kp1, a->kp_xy, (size_t)n1 * sizeof(float2), hipMemcpyHostToDevice, s));
-        CHIP_HIP(c, hipMemcpyAsync(st->kp2, b->kp_xy, (size_t)n2 * sizeof(float2), hipMemcpyHostToDevice, s));
-        CHIP_HIP(c, hipMemcpyAsync(st->xyz_a, a->xyz, fa * sizeof(float), hipMemcpyHostToDevice, s));
-        CHIP_HIP(c, hipMemcpyAsync(st->xyz_b, b->xyz, fb * sizeof(float), hipMemcpyHostToDevice, s));
-        rc = launch_bf(c, s, st, n1, n2);
-        if (rc == CHIP_OK) rc = launch_gms(c, s, st, true, n1, a->width, a->height, b->width, b->height);
-        if (rc != CHIP_OK) return rc;
-        SetsArgs sa;
-        sa.kp1 = st->kp1; sa.kp2 = st->kp2; sa.tidx = st->tidx; sa.inlier = st->inlier; sa.n = n1;
-        sa.xyz_a = st->xyz_a; sa.xyz_b = st->xyz_b; sa.w1 = a->width; sa.h1 = a->height; sa.w2 = b->width; sa.h2 = b->height;
-        for (int i = 0; i < 9; i++) sa.Kinv[i] = Kinv[i];
-        sa.uv = st->uv; sa.uv_d = st->uv_d; sa.X_ab = st->X_ab; sa.uvn_ab = st->uvn_ab; sa.X_ba = st->X_ba; sa.uvn_ba = st->uvn_ba;
-        sa.A = st->A; sa.B = st->B; sa.mq = st->mq; sa.mt = st->mt; sa.counts = st->counts;
-        hipLaunchKernelGGL(pose_sets_build, dim3(1), dim3(kOneWg), 0, s, sa);
-        CHIP_HIP(c, hipGetLastError());
-        CHIP_HIP(c, hipMemcpyAsync(st->h_counts.host(), st->counts, kNSets * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        CHIP_HIP(c, hipStreamSynchronize(s));
-        sm.n_matches_all = n1;
-        sm.n_matches_gms = st->h_counts.host()[kSetUv];
-        sm.n_3d2d_ab = st->h_counts.host()[kSetAb];
-        sm.n_3d2d_ba = st->h_counts.host()[kSetBa];
-        sm.n_3d3d = st->h_counts.host()[kSet33];
-        sm.n_out_of_image = st->h_counts.host()[kSetOut];
-    }
-    st->from_batch = false;
-    st->n_cand = 1;
-    st->cand_sm[0] = sm;
-    st->select(0);
-    st->have_sets = true;
-    *summary = sm;
+    rc = match_run(c, st, a, b, 1, Kinv);
+    if (rc != CHIP_OK) return rc;
+    st->keys_readable = false;
+    *summary = st->cand_sm[0];
     return CHIP_OK;
 }
 
@@ -735,94 +760,9 @@ extern "C" int chip_match_batch(chip_ctx *c, const chip_match_frame *a, const ch
     rc = match_state(c, &st);
     if (rc != CHIP_OK) return rc;
     st->have_sets = false;
-    const int n1 = a->n;
-    int max_n2 = 0;
-    size_t tot_n = 0, tot_px = 0;
-    for (int j = 0; j < B; j++) {
-        if (b[j].n == 0) continue;               // an empty candidate is not uploaded
-        max_n2 = b[j].n > max_n2 ? b[j].n : max_n2;
-        tot_n += (size_t)b[j].n;
-        tot_px += (size_t)b[j].width * b[j].height;
-    }
-    for (int j = 0; j < B; j++) std::memset(&st->cand_sm[j], 0, sizeof(chip_match_summary));
-    if (n1 > 0) {
-        const size_t px_a = (size_t)a->width * a->height;
-        rc = batch_reserve(c, st, (size_t)B, (size_t)n1, tot_n, tot_px, px_a);
-        if (rc != CHIP_OK) return rc;
-        hipStream_t s = match_stream(c);
-        CHIP_HIP(c, hipMemsetAsync(st->b_keys, 0xff, (size_t)B * n1 * sizeof(unsigned long long), s));   // all ones: no match yet
-        if (max_n2 > 0) {
-            CHIP_HIP(c, hipMemcpyAsync(st->d1, a->desc, (size_t)n1 * CHIP_ORB_DESC_BYTES, hipMemcpyHostToDevice, s));
-            CHIP_HIP(c, hipMemcpyAsync(st->kp1, a->kp_xy, (size_t)n1 * sizeof(float2), hipMemcpyHostToDevice, s));
-            CHIP_HIP(c, hipMemcpyAsync(st->xyz_a, a->xyz, 3 * px_a * sizeof(float), hipMemcpyHostToDevice, s));
-            BatchCands cands;
-            std::memset(&cands, 0, sizeof cands);
-            size_t off_n = 0, off_px = 0;
-            for (int j = 0; j < B; j++) {
-                const int n2 = b[j].n;
-                if (n2 == 0) continue;
-                const size_t px = (size_t)b[j].width * b[j].height;
-                uint8_t *dd = st->b_desc + off_n * CHIP_ORB_DESC_BYTES;
-                float2 *dk = st->b_kp + off_n;
-                float *dx = st->b_xyz + 3 * off_px;
-                CHIP_HIP(c, hipMemcpyAsync(dd, b[j].desc, (size_t)n2 * CHIP_ORB_DESC_BYTES, hipMemcpyHostToDevice, s));
-                CHIP_HIP(c, hipMemcpyAsync(dk, b[j].kp_xy, (size_t)n2 * sizeof(float2), hipMemcpyHostToDevice, s));
-                CHIP_HIP(c, hipMemcpyAsync(dx, b[j].xyz, 3 * px * sizeof(float), hipMemcpyHostToDevice, s));
-                cands.c[j] = BatchCand{reinterpret_cast<const uint4 *>(dd), dk, dx, n2, b[j].width, b[j].height, 0};
-                off_n += (size_t)n2; off_px += px;
-            }
-            // tuning only (CHIP_MATCH_BATCH_TIMING=1): device time of each of the three kernels by events, averaged, printed at process exit
-            struct KernelTiming {
-                double acc[3] = {0, 0, 0}; long n = 0; bool on = std::getenv("CHIP_MATCH_BATCH_TIMING") != nullptr;
-                ~KernelTiming() { if (on && n) std::fprintf(stderr, "match batch kernel timing over %ld calls (us): hamming_match_split %.1f, gms_batch %.1f, pose_sets_batch %.1f\n",
-                                                            n, 1e3 * acc[0] / n, 1e3 * acc[1] / n, 1e3 * acc[2] / n); }
-            };
-            static KernelTiming kt;
-            if (kt.on)
-                for (hipEvent_t &e : st->b_ev)
-                    if (!e) CHIP_HIP(c, hipEventCreate(&e));
-            if (kt.on) CHIP_HIP(c, hipEventRecord(st->b_ev[0], s));
-            hipLaunchKernelGGL(hamming_match_split, dim3((n1 + kBfThreads - 1) / kBfThreads, (max_n2 + kBfTile - 1) / kBfTile, B), dim3(kBfThreads), 0, s,
-                               reinterpret_cast<const uint4 *>(st->d1.get()), n1, cands, st->b_keys.get());
-            CHIP_HIP(c, hipGetLastError());
-            if (kt.on) CHIP_HIP(c, hipEventRecord(st->b_ev[1], s));
-            GmsBatchArgs ga;
-            ga.kp1 = st->kp1; ga.n1 = n1; ga.w1 = a->width; ga.h1 = a->height; ga.keys = st->b_keys; ga.table = st->b_table; ga.plane = st->b_plane;
-            ga.cands = cands;
-            hipLaunchKernelGGL(gms_batch, dim3(4, B), dim3(kOneWg), 0, s, ga);
-            CHIP_HIP(c, hipGetLastError());
-            if (kt.on) CHIP_HIP(c, hipEventRecord(st->b_ev[2], s));
-            SetsBatchArgs sa;
-            sa.kp1 = st->kp1; sa.xyz_a = st->xyz_a; sa.n1 = n1; sa.w1 = a->width; sa.h1 = a->height; sa.keys = st->b_keys; sa.plane = st->b_plane;
-            for (int i = 0; i < 9; i++) sa.Kinv[i] = Kinv[i];
-            sa.uv = st->b_uv; sa.uv_d = st->b_uv_d; sa.X_ab = st->b_X_ab; sa.uvn_ab = st->b_uvn_ab; sa.X_ba = st->b_X_ba; sa.uvn_ba = st->b_uvn_ba;
-            sa.A = st->b_A; sa.B = st->b_B; sa.mq = st->b_mq; sa.mt = st->b_mt; sa.counts = st->b_counts; sa.cands = cands;
-            hipLaunchKernelGGL(pose_sets_batch, dim3(B), dim3(kOneWg), 0, s, sa);
-            CHIP_HIP(c, hipGetLastError());
-            if (kt.on) CHIP_HIP(c, hipEventRecord(st->b_ev[3], s));
-            CHIP_HIP(c, hipMemcpyAsync(st->h_bcounts.host(), st->b_counts, (size_t)B * kNSets * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            CHIP_HIP(c, hipStreamSynchronize(s));
-            for (int k = 0; k < 3 && kt.on; k++) {
-                float ms = 0.f;
-                CHIP_HIP(c, hipEventElapsedTime(&ms, st->b_ev[k], st->b_ev[k + 1]));
-                kt.acc[k] += ms;
-            }
-            kt.n += kt.on;
-        }
-        CHIP_HIP(c, hipStreamSynchronize(s));
-        for (int j = 0; j < B && max_n2 > 0; j++) {
-            if (b[j].n == 0) continue;
-            const int32_t *h = st->h_bcounts.host() + j * kNSets;
-            chip_match_summary &sm = st->cand_sm[j];
-            sm.n_matches_all = n1;
-            sm.n_matches_gms = h[kSetUv]; sm.n_3d2d_ab = h[kSetAb]; sm.n_3d2d_ba = h[kSetBa]; sm.n_3d3d = h[kSet33]; sm.n_out_of_image = h[kSetOut];
-        }
-    }
-    st->from_batch = true;
-    st->n_cand = B;
-    st->batch_n1 = n1;
-    st->select(0);
-    st->have_sets = true;
+    rc = match_run(c, st, a, b, B, Kinv);
+    if (rc != CHIP_OK) return rc;
+    st->keys_readable = true;
     for (int j = 0; j < B; j++) summary[j] = st->cand_sm[j];
     return CHIP_OK;
 }
@@ -845,20 +785,12 @@ extern "C" int chip_match_batch_read_matches(chip_ctx *c, int32_t j, int32_t *tr
     if (c->group) return CHIP_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> lk(c->match_mu);
     MatchState *st = c->match_state;
-    if (!st || !st->have_sets || !st->from_batch) return CHIP_ERR_BUSY;   // the keys are chip_match_batch's: not after a chip_match_pair
+    if (!st || !st->have_sets || !st->keys_readable) return CHIP_ERR_BUSY;   // not after a chip_match_pair
     if (j < 0 || j >= st->n_cand) return CHIP_ERR_RANGE;
-    const size_t n1 = (size_t)st->batch_n1;
+    const size_t n1 = (size_t)st->n1;
     if (n1 == 0) return CHIP_OK;
     CHIP_HIP(c, hipSetDevice(c->device));
-    hipStream_t s = match_stream(c);
-    st->h_keys.resize(n1);
-    CHIP_HIP(c, hipMemcpyAsync(st->h_keys.data(), st->b_keys + (size_t)j * n1, n1 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    CHIP_HIP(c, hipStreamSynchronize(s));
-    for (size_t i = 0; i < n1; i++) {   // all ones -> -1 / -1
-        train_idx[i] = (int32_t)(uint32_t)st->h_keys[i];
-        distance[i] = (int32_t)(uint32_t)(st->h_keys[i] >> 32);
-    }
-    return CHIP_OK;
+    return fetch_matches(c, match_stream(c), st, st->keys + (size_t)j * n1, n1, train_idx, distance);
 }
 
 extern "C" int chip_pnp_ransac_matched_batch(chip_ctx *c, int32_t P, const int32_t *cand, const int32_t *which, const chip_ransac_params *p,

@@ -539,34 +539,6 @@ bool StaticPointFeatureMatching::make_3d_3d_collection__using__pfmatches_and_dis
     return true;
 }
 
-bool verify_candidate(chip_ctx *ctx, const chip_match_frame &frame_a, const chip_match_frame &frame_b, const double Kinv[9],
-                      ProcessedLoopCandidate &pc, uint64_t seed, chip_match_summary *summary)
-{
-    chip_match_summary sm{};
-    const int rc = chip_match_pair(ctx, &frame_a, &frame_b, Kinv, &sm);
-    if (summary) *summary = sm;
-    if (rc != CHIP_OK) return false;
-    if (sm.n_matches_gms < 150) return false;                       // Cerebro.cpp:1487-1493
-    pc.pf_matches = sm.n_matches_gms;                               // :1505
-    chip_ransac_params pp, pi;
-    chip_ransac_params_default(&pp);
-    chip_icp_params_default(&pi);
-    if (seed) { pp.seed = seed; pi.seed = seed ^ 0x9E3779B97F4A7C15ull; }   // the seeds of compute_three_way_pose
-    std::array<double, 16> op1{}, op2_a_T_b{}, op2{}, icp{};
-    float g1 = -1.f, g2 = -1.f, g3 = -1.f;
-    if (chip_pnp_ransac_matched(ctx, CHIP_SET_AB, &pp, op1.data(), &g1, nullptr, nullptr) != CHIP_OK) g1 = -1.f;            // :1518
-    pp.seed += 1;
-    if (chip_pnp_ransac_matched(ctx, CHIP_SET_BA, &pp, op2_a_T_b.data(), &g2, nullptr, nullptr) != CHIP_OK) g2 = -1.f;      // :1572
-    matrix4_inverse_rigid(op2_a_T_b.data(), op2.data());                                                                    // :1582
-    if (chip_icp_ransac_matched(ctx, &pi, icp.data(), &g3, nullptr, nullptr) != CHIP_OK) g3 = -1.f;                          // :1629
-    for (int i = 0; i < 16; i++)                                    // :1678
-        if (op1[i] != op1[i] || op2[i] != op2[i] || icp[i] != icp[i]) return false;
-    if (g1 < 0 || g2 < 0 || g3 < 0) return false;
-    pc.opX_b_T_a = {op1, op2, icp};                                 // :1706-1719
-    pc.opX_goodness = {g1, g2, g3};
-    return true;
-}
-
 bool verify_candidates(chip_ctx *ctx, const chip_match_frame &frame_a, const chip_match_frame *frames_b, int B, const double Kinv[9],
                        ProcessedLoopCandidate *pc, bool *accepted, const uint64_t *seeds, chip_match_summary *summaries)
 {
@@ -590,7 +562,7 @@ bool verify_candidates(chip_ctx *ctx, const chip_match_frame &frame_a, const chi
         slot[j] = -1;
         if (sm[j].n_matches_gms < 150) continue;
         pc[j].pf_matches = sm[j].n_matches_gms;                     // :1505
-        const uint64_t s0 = seeds && seeds[j] ? seeds[j] : pp_seed; // the seeds of verify_candidate
+        const uint64_t s0 = seeds && seeds[j] ? seeds[j] : pp_seed; // the seeds of compute_three_way_pose
         slot[j] = P;
         cand[P] = j; which[P] = CHIP_SET_AB; sd[P] = s0; P++;
         cand[P] = j; which[P] = CHIP_SET_BA; sd[P] = s0 + 1; P++;
@@ -617,6 +589,13 @@ bool verify_candidates(chip_ctx *ctx, const chip_match_frame &frame_a, const chi
         accepted[j] = true;
     }
     return true;
+}
+
+bool verify_candidate(chip_ctx *ctx, const chip_match_frame &frame_a, const chip_match_frame &frame_b, const double Kinv[9],
+                      ProcessedLoopCandidate &pc, uint64_t seed, chip_match_summary *summary)
+{
+    bool accepted = false;                                          // a batch of one
+    return verify_candidates(ctx, frame_a, &frame_b, 1, Kinv, &pc, &accepted, &seed, summary) && accepted;
 }
 
 void matrix4_to_pose(const double T[16], double position[3], double q[4])

@@ -205,9 +205,9 @@ struct StaticPointFeatureMatching {
                                                                       std::vector<std::array<double, 3>> &uv_X,
                                                                       std::vector<std::array<double, 3>> &uvd_Y);
 };
-// One candidate, "keypoints + descriptors + 3-D images in, ready for makeLoopEdgeMsgWithConsistencyCheck out": chip_match_pair ->
-// the "< 150 matches" reject (Cerebro.cpp:1487) -> pf_matches (:1505) -> the three poses on the device-resident sets (seeds as
-// compute_three_way_pose) -> NaN gate (:1678).  One upload; nothing but counts and poses returns to the host.
+// One candidate, "keypoints + descriptors + 3-D images in, ready for makeLoopEdgeMsgWithConsistencyCheck out": verify_candidates (below)
+// with B = 1 -- the match stage, the "< 150 matches" reject (Cerebro.cpp:1487) -> pf_matches (:1505) -> the three poses on the
+// device-resident sets (seeds as compute_three_way_pose) -> NaN gate (:1678).  One upload; nothing but counts and poses returns to the host.
 bool verify_candidate(chip_ctx *ctx, const chip_match_frame &frame_a, const chip_match_frame &frame_b, const double Kinv[9],
                       ProcessedLoopCandidate &proc_candi, uint64_t seed = 0, chip_match_summary *summary = nullptr);
 // B candidates of one keyframe (B <= CHIP_MATCH_MAX_BATCH): ONE chip_match_batch (frame_a uploaded once, all pairs in three launches),

@@ -586,7 +586,7 @@ int chip_icp_ransac_matched(chip_ctx *ctx, const chip_ransac_params *p, double T
  * Status: B < 1 or a NULL pointer CHIP_ERR_INVALID_ARG; B > CHIP_MATCH_MAX_BATCH, a group ctx or a frame beyond chip_match_pair's
  * limits CHIP_ERR_UNSUPPORTED; j or cand[i] outside the last batch CHIP_ERR_RANGE; before any match CHIP_ERR_BUSY.  An empty
  * query frame or an empty candidate gives that candidate a zero summary, as chip_match_pair.  A failed call leaves nothing
- * selected.  chip_match_pair keeps its own kernels and results.                                                                   */
+ * selected.  chip_match_pair is this pipeline with one candidate.                                                                 */
 #define CHIP_MATCH_MAX_BATCH 16            /* = the library's top-K bound */
 int chip_build_has_match_batch(void);      /* 1 */
 /* frame a against b[0..B): summary[j] and the five sets of candidate j are those of chip_match_pair(a, &b[j]) byte for byte.

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Measures the batched match stage against the single-pair path of the same build (profiles/match_batch.md is this script's output).
+"""Measures chip_match_batch against sequential chip_match_pair calls of the same build (profiles/match_batch.md holds this script's
+output, one section per visit; to compare two builds run it from each tree in turn with --out).
 
   python scripts/gpu_match_batch_perf.py [--reps 30] [--out profiles/match_batch.md]
 
@@ -9,7 +10,8 @@ medians of --reps runs:
      candidates are the scene's b frame B times -- the work does not depend on which candidate it is);
   2. the three kernels alone by hipEvents (CHIP_MATCH_BATCH_TIMING=1, a child process per B: the knob is read once);
   3. the whole verification, verify_candidates against B x verify_candidate (examples/verify_candidates.cc on its own 5000-point scene:
-     B - 2 views that pass, one unrelated and one empty candidate)."""
+     B - 2 views that pass, one unrelated and one empty candidate);
+  4. chip_orb_match alone on the same descriptors."""
 from __future__ import annotations
 
 import argparse
@@ -91,6 +93,15 @@ def main():
             for _ in range(args.reps):                               # the two paths alternate inside the timed window
                 tp.append(median_ms(pairs, 1)); tb.append(median_ms(batch, 1))
             rows.append([B, statistics.median(tp), statistics.median(tb)])
+        d1, d2 = (np.ascontiguousarray(sc[k]["desc"], dtype=np.uint8) for k in "ab")
+        idx, dist = np.empty(n1, np.int32), np.empty(n1, np.int32)
+
+        def orb():
+            assert chip.lib.chip_orb_match(chip.h, capi._ptr(d1), n1, capi._ptr(d2), n2, capi._ptr(idx), capi._ptr(dist)) == 0
+
+        for _ in range(3):
+            orb()
+        t_orb = median_ms(orb, args.reps)
     for r in rows:
         env = dict(os.environ, CHIP_MATCH_BATCH_TIMING="1")
         p = subprocess.run([sys.executable, __file__, "--kernels-child", str(r[0]), "--reps", str(args.reps)], env=env, capture_output=True, text=True, timeout=600)
@@ -104,7 +115,7 @@ def main():
         m = re.search(r"timing B=(\d+) n=(\d+) reps=\d+: \d+ x verify_candidate ([\d.]+) ms, verify_candidates ([\d.]+) ms", p.stdout)
         assert p.returncode == 0 and m, p.stdout + p.stderr
         whole.append((B, int(m.group(2)), float(m.group(3)), float(m.group(4))))
-    out = [f"# Batched match stage against the single-pair path ({arch}, medians of {args.reps}, scripts/gpu_match_batch_perf.py)", "",
+    out = [f"# chip_match_batch against sequential chip_match_pair calls ({arch}, medians of {args.reps}, scripts/gpu_match_batch_perf.py)", "",
            f"Frames: {n1} / {n2} keypoints at 752 x 480 (full_5000_5000).  Host wall time of the calls, uploads included; kernel columns: device time by events.", "",
            "| B | B x chip_match_pair (ms) | chip_match_batch (ms) | ratio | hamming_match_split (us) | gms_batch (us) | pose_sets_batch (us) |",
            "|---|---|---|---|---|---|---|"]
@@ -114,6 +125,7 @@ def main():
             "| B | keypoints of the query | B x verify_candidate (ms) | verify_candidates (ms) | ratio |", "|---|---|---|---|---|"]
     for B, n, t1, tb in whole:
         out.append(f"| {B} | {n} | {t1:.3f} | {tb:.3f} | {t1 / tb:.2f} |")
+    out += ["", f"chip_orb_match alone, {n1} x {n2} descriptors: {t_orb:.3f} ms"]
     text = "\n".join(out) + "\n"
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     Path(args.out).write_text(text)

@@ -1,13 +1,14 @@
-"""Build-time look at the batched match stage (cerebro_amd/csrc/match.hip: hamming_match_split, gms_batch, pose_sets_batch) in the gfx950
-code object of the built libcerebro_hip.so (no GPU needed): the three kernels exist, none of them spills or uses a flat_ memory
-instruction (the per-candidate pointers come out of the kernel arguments as global pointers), and the matcher keeps orb_bf_match's
-loop: LDS broadcast reads of 16 bytes, xor + popcount."""
+"""Build-time look at the match stage (cerebro_amd/csrc/match.hip: hamming_match_split, gms_batch, pose_sets_batch, and gms_filter of
+chip_gms_filter) in the gfx950 code object of the built libcerebro_hip.so (no GPU needed): the three kernels of the pipeline exist, none
+of them spills or uses a flat_ memory instruction (the per-candidate pointers come out of the kernel arguments as global pointers), the
+matcher's loop is LDS broadcast reads of 16 bytes, xor + popcount, and the kernels of the former pair-only path are gone."""
 import pytest
 
 from test_codeobj_registers import LLVM, SO, _kernel_listings
 
 pytestmark = pytest.mark.needs_hip_build
 KERNELS = ("hamming_match_split", "gms_batch", "pose_sets_batch")
+DELETED = ("orb_bf_match", "pose_sets_build")
 
 
 @pytest.fixture(scope="module")
@@ -16,7 +17,7 @@ def listings(tmp_path_factory):
         pytest.skip("llvm-objdump not available")
     if not SO.exists():
         pytest.skip("libcerebro_hip.so not built")
-    ks = _kernel_listings(tmp_path_factory.mktemp("co"), lambda k: any(n in k for n in KERNELS))
+    ks = _kernel_listings(tmp_path_factory.mktemp("co"), lambda k: any(n in k for n in KERNELS + DELETED + ("gms_filter",)))
     return {k: [t.split(None, 1)[0] for t in v if t] for k, v in ks.items() if not k.endswith(".kd")}
 
 
@@ -38,5 +39,10 @@ def test_matcher_loop_and_merge(listings):
     assert not [o for o in ops if "cmpswap" in o]
 
 
-def test_matcher_name_does_not_collide_with_the_pair_kernel(listings):
-    assert not [k for k in listings if "orb_bf_match" in k]          # test_codeobj_match.py expects exactly one kernel of that name
+def test_gms_filter_is_in_the_product_library(listings):
+    assert len([k for k in listings if "gms_filter" in k]) == 1, sorted(listings)
+
+
+def test_no_pair_only_kernel_is_left(listings):
+    assert [k for k in listings if "hamming_match_split" in k]       # the listing does see match.hip's kernels ...
+    assert not [k for k in listings if any(n in k for n in DELETED)], sorted(listings)   # ... and none of the deleted ones

@@ -126,6 +126,7 @@ def test_all_duplicate_candidate_between_two_ordinary_ones(chip, five):
 def test_batch_sizes_1_2_16_and_17(chip, five):
     a, cands, Kinv = five["a"], five["cands"], five["Kinv"]
     pair = chip.match_pair(a, cands[1], Kinv)
+    assert_same_result(pair, five["mirror"][1], "pair")             # the pair call is a run of one: the mirror is the independent witness
     one = batch_all(chip, a, [cands[1]], Kinv)
     assert_same_result(one[0], pair, "B=1")
     two = batch_all(chip, a, [cands[3], cands[1]], Kinv)
@@ -179,6 +180,7 @@ def test_state_across_batches_and_pair_calls(chip, five):
     for j in range(2):
         assert_same_result(small[j], M.match_pair(sa, sc[j], sK), j)
     p = chip.match_pair(a, cands[3], Kinv)
+    assert_same_result(p, five["mirror"][3], "pair/mirror")
     chip.match_select(0)                                            # after a pair call there is one candidate
     assert_same_result(dict(summary=p["summary"], **chip.match_read_sets(capi.MatchSummary(**p["summary"]))), p, "pair")
     with pytest.raises(capi.ChipError) as e:
@@ -188,6 +190,35 @@ def test_state_across_batches_and_pair_calls(chip, five):
         chip.match_batch_matches(0)
     assert e.value.status == capi.CHIP_ERR_BUSY
     assert blob(batch_all(chip, a, cands, Kinv)) == first
+
+
+def test_stand_alone_calls_leave_the_last_batch_alone(chip):
+    """chip_orb_match has keys of its own and chip_gms_filter its own lists: what a batch left reads the same after them"""
+    sa, sc, sK = cases.small_frames(2)
+    before = batch_all(chip, sa, sc, sK)
+    p = capi.default_ransac_params(); p.seed = 5
+    pnp_before = {}
+    for j in (1, 0):
+        chip.match_select(j)
+        pnp_before[j] = chip.pnp_matched(capi.CHIP_SET_AB, before[j]["summary"]["n_3d2d_ab"], p)
+        assert pnp_before[j]["status"] == 0
+    rng = np.random.default_rng(77)
+    q = rng.integers(0, 256, (257, 32), dtype=np.uint8)             # one query block and one lane
+    t = rng.integers(0, 256, (1025, 32), dtype=np.uint8)            # one train tile and one descriptor
+    t[1024] = q[256]
+    idx, dist = chip.orb_match(q, t)
+    want = cases.hamming_search(q, t)
+    assert same_bytes(idx, want[0]) and same_bytes(dist, want[1]) and idx[256] == 1024 and dist[256] == 0
+    kp1 = rng.uniform(0, 64, (40, 2)).astype(np.float32)
+    mask = chip.gms_filter(kp1, (64, 48), kp1[::-1].copy(), (64, 48), np.arange(40), np.arange(40)[::-1].copy())
+    assert mask.shape == (40,)
+    for j in (1, 0):                                                # without another run
+        chip.match_select(j)
+        sm = capi.MatchSummary(**before[j]["summary"])
+        after = dict(summary=before[j]["summary"], **chip.match_read_sets(sm))
+        after["train_idx"], after["distance"] = chip.match_batch_matches(j)
+        assert blob([after]) == blob([before[j]]), j
+        _same_estimate(chip.pnp_matched(capi.CHIP_SET_AB, sm.n_3d2d_ab, p), pnp_before[j], j)
 
 
 def _same_estimate(d: dict, h: dict, what):

@@ -225,6 +225,13 @@ _SIGS = {
     "chip_match_select": (C.c_int, [_P, C.c_int32]),
     "chip_match_batch_read_matches": (C.c_int, [_P, C.c_int32, _P, _P]),
     "chip_pnp_ransac_matched_batch": (C.c_int, [_P, C.c_int32, _P, _P, C.POINTER(RansacParams), _P, _P, _P, _P, _P, _P]),
+    "chip_build_has_frame_store": (C.c_int, []),
+    "chip_frame_store_reserve": (C.c_int, [_P, C.c_int32, C.c_int32]),
+    "chip_frame_store_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "chip_frame_put": (C.c_int, [_P, C.c_int64, C.POINTER(MatchFrame)]),
+    "chip_frame_drop": (C.c_int, [_P, C.c_int64]),
+    "chip_frame_read": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P, _P]),
+    "chip_match_batch_stored": (C.c_int, [_P, C.c_int64, _P, C.c_int32, _P, C.POINTER(MatchSummary)]),
     "chip_get_info": (C.c_int, [_P, C.POINTER(Info)]),
     "chip_profile_enable": (C.c_int, [_P, C.c_int32]),
     "chip_profile_reset": (C.c_int, [_P]),
@@ -841,6 +848,51 @@ class Chip:
             cf, s = C.c_float(float(conf[i])), RansacSummary.from_buffer_copy(summ[i])
             out.append(self._matched(int(status[i]), "chip_pnp_ransac_matched_batch", Ns[i], T[i], cf, masks[i], s))
         return out
+
+    # -- frames kept on the device (the frame store)
+    def frame_store_reserve(self, n_slots: int, slot_keypoints: int):
+        """chip_frame_store_reserve: n_slots slots of slot_keypoints keypoints each, 56 bytes of device memory per keypoint"""
+        self._chk(self.lib.chip_frame_store_reserve(self.h, n_slots, slot_keypoints), "chip_frame_store_reserve")
+
+    def frame_store_info(self) -> dict:
+        v = [C.c_int32() for _ in range(3)]
+        self._chk(self.lib.chip_frame_store_info(self.h, *[C.byref(x) for x in v]), "chip_frame_store_info")
+        return dict(n_slots=v[0].value, slot_keypoints=v[1].value, n_frames=v[2].value)
+
+    def frame_put(self, id: int, frame: dict):
+        """chip_frame_put: store (or replace) the frame dict(desc, kp, xyz) under id; the arrays are free again on return"""
+        f, keep = self._match_frame(frame)
+        self._chk(self.lib.chip_frame_put(self.h, id, C.byref(f)), "chip_frame_put")
+
+    def frame_drop(self, id: int):
+        self._chk(self.lib.chip_frame_drop(self.h, id), "chip_frame_drop")
+
+    def frame_read(self, id: int) -> dict:
+        """chip_frame_read -> dict(n, width, height, desc (n, 32) uint8, kp (n, 2) float32, pts (n, 4) float32: the point records)"""
+        v = [C.c_int32() for _ in range(3)]
+        self._chk(self.lib.chip_frame_read(self.h, id, *[C.byref(x) for x in v], None, None, None), "chip_frame_read")
+        n = v[0].value
+        desc = np.zeros((n, CHIP_ORB_DESC_BYTES), dtype=np.uint8)
+        kp = np.zeros((n, 2), dtype=np.float32)
+        pts = np.zeros((n, 4), dtype=np.float32)
+        if n:
+            self._chk(self.lib.chip_frame_read(self.h, id, None, None, None, _ptr(desc), _ptr(kp), _ptr(pts)), "chip_frame_read")
+        return dict(n=n, width=v[1].value, height=v[2].value, desc=desc, kp=kp, pts=pts)
+
+    def match_batch_stored(self, a_id: int, b_ids, Kinv: np.ndarray) -> list:
+        """chip_match_batch_stored: the stored frame a_id against the stored frames b_ids, nothing uploaded -> what match_batch returns
+        on the host frames that were put under those ids; match_select / match_read_sets / match_batch_matches and the _matched
+        solvers work on the result."""
+        ids = np.ascontiguousarray(b_ids, dtype=np.int64).reshape(-1)
+        B = len(ids)
+        Ki = np.ascontiguousarray(Kinv, dtype=np.float64).reshape(9)
+        sm = (MatchSummary * max(B, 1))()
+        self._match_batch_n1 = 0
+        self._chk(self.lib.chip_match_batch_stored(self.h, a_id, _ptr(ids) if B else None, B, _ptr(Ki), sm), "chip_match_batch_stored")
+        n1 = C.c_int32()
+        self._chk(self.lib.chip_frame_read(self.h, a_id, C.byref(n1), None, None, None, None, None), "chip_frame_read")
+        self._match_batch_n1 = n1.value
+        return [MatchSummary.from_buffer_copy(sm[j]) for j in range(B)]
 
     # -- introspection / profiling
     def info(self) -> dict:

@@ -32,6 +32,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <unordered_map>
 
 namespace chip {
 
@@ -183,8 +184,6 @@ enum { kSetUv = 0, kSetAb = 1, kSetBa = 2, kSet33 = 3, kSetOut = 4, kNSets = 5 }
 struct SetsArgs {
     const float2 *kp1, *kp2;
     int32_t n;
-    const float *xyz_a, *xyz_b;   // H x W x 3
-    int32_t w1, h1, w2, h2;
     double Kinv[9];               // row-major
     double *uv, *uv_d, *X_ab, *uvn_ab, *X_ba, *uvn_ba, *A, *B;
     int32_t *mq, *mt;
@@ -202,10 +201,45 @@ __device__ __forceinline__ bool pixel_of(float2 p, int w, int h, int *x, int *y)
 // the depth gate of :122 / :182: "z < 0.1 || z > 25." with the float z widened to double
 __device__ __forceinline__ bool depth_ok(float z) { return !((double)z < 0.1 || (double)z > 25.); }
 
+// Where a keypoint's 3-D point comes from.  in_a(i, p, &r) / in_b(t, p, &r): keypoint i of frame a / t of frame b at p has a pixel in its
+// image, r then refers to its point; a(r, k) / b(r, k): coordinate k of that point.
+// ImagePoints: the frames' 3-D images (H x W x 3), r = the pixel's offset.
+struct ImagePoints {
+    const float *xyz_a, *xyz_b;
+    int32_t w1, h1, w2, h2;
+    typedef size_t Ref;
+    __device__ __forceinline__ bool in_a(int, float2 p, Ref *r) const
+    {
+        int x, y;
+        if (!pixel_of(p, w1, h1, &x, &y)) return false;
+        *r = 3 * ((size_t)y * w1 + x);
+        return true;
+    }
+    __device__ __forceinline__ bool in_b(int, float2 p, Ref *r) const
+    {
+        int x, y;
+        if (!pixel_of(p, w2, h2, &x, &y)) return false;
+        *r = 3 * ((size_t)y * w2 + x);
+        return true;
+    }
+    __device__ __forceinline__ float a(Ref r, int k) const { return xyz_a[r + k]; }
+    __device__ __forceinline__ float b(Ref r, int k) const { return xyz_b[r + k]; }
+};
+// RecordPoints: the frame store's point records, one float4 per keypoint (frame_gather): (x, y, z, 1.0f) copied from the image at put
+// time, or (0, 0, 0, 0.0f) for a keypoint outside it; r = the record.
+struct RecordPoints {
+    const float4 *rec_a, *rec_b;
+    typedef float4 Ref;
+    __device__ __forceinline__ bool in_a(int i, float2, Ref *r) const { *r = rec_a[i]; return r->w != 0.0f; }
+    __device__ __forceinline__ bool in_b(int t, float2, Ref *r) const { *r = rec_b[t]; return r->w != 0.0f; }
+    __device__ __forceinline__ float a(const Ref &r, int k) const { return k == 0 ? r.x : k == 1 ? r.y : r.z; }
+    __device__ __forceinline__ float b(const Ref &r, int k) const { return a(r, k); }
+};
+
 // The ordered compaction by ONE workgroup of kOneWg threads; inlier(i) / train(i): the GMS mark and the train index of match i
-// (pose_sets_batch: the four planes of gms_batch and the merged keys)
-template <class Inlier, class Train>
-__device__ __forceinline__ void pose_sets_body(const SetsArgs &a, Inlier inlier, Train train)
+// (the four planes of gms_batch and the merged keys); pts: ImagePoints (pose_sets_batch) or RecordPoints (pose_sets_stored_batch)
+template <class Inlier, class Train, class Points>
+__device__ __forceinline__ void pose_sets_body(const SetsArgs &a, Inlier inlier, Train train, const Points &pts)
 {
     __shared__ int32_t wtot[kNSets][kOneWg / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -215,15 +249,14 @@ __device__ __forceinline__ void pose_sets_body(const SetsArgs &a, Inlier inlier,
         bool f[kNSets] = {false, false, false, false, false};
         float2 pa = make_float2(0.f, 0.f), pb = pa;
         int t = 0;
-        size_t oa = 0, ob = 0;
+        typename Points::Ref oa{}, ob{};
         if (i < a.n && inlier(i)) {
             t = train(i);
             pa = a.kp1[i]; pb = a.kp2[t];
-            int xa, ya, xb, yb;
-            const bool in_a = pixel_of(pa, a.w1, a.h1, &xa, &ya), in_b = pixel_of(pb, a.w2, a.h2, &xb, &yb);
+            const bool in_a = pts.in_a(i, pa, &oa), in_b = pts.in_b(t, pb, &ob);
             bool za = false, zb = false;
-            if (in_a) { oa = 3 * ((size_t)ya * a.w1 + xa); za = depth_ok(a.xyz_a[oa + 2]); }
-            if (in_b) { ob = 3 * ((size_t)yb * a.w2 + xb); zb = depth_ok(a.xyz_b[ob + 2]); }
+            if (in_a) za = depth_ok(pts.a(oa, 2));
+            if (in_b) zb = depth_ok(pts.b(ob, 2));
             f[kSetUv] = true; f[kSetAb] = za; f[kSetBa] = zb; f[kSet33] = za && zb; f[kSetOut] = !in_a || !in_b;
         }
         int pos[kNSets];
@@ -251,19 +284,19 @@ __device__ __forceinline__ void pose_sets_body(const SetsArgs &a, Inlier inlier,
         // K.inverse() * uv (PointFeatureMatching.cpp:114-115), rows 0 and 1 of the 3 x 3 by 3 x 1 product, left to right
         if (f[kSetAb]) {                                      // make_3d_2d(uv, a_3dImage, uv_d) (Cerebro.cpp:1512): a's point, b's normalised pixel
             const int o = pos[kSetAb];
-            for (int k = 0; k < 3; k++) a.X_ab[3 * o + k] = (double)a.xyz_a[oa + k];
+            for (int k = 0; k < 3; k++) a.X_ab[3 * o + k] = (double)pts.a(oa, k);
             a.uvn_ab[2 * o] = (a.Kinv[0] * ub + a.Kinv[1] * vb) + a.Kinv[2];
             a.uvn_ab[2 * o + 1] = (a.Kinv[3] * ub + a.Kinv[4] * vb) + a.Kinv[5];
         }
         if (f[kSetBa]) {                                      // make_3d_2d(uv_d, b_3dImage, uv) (Cerebro.cpp:1566)
             const int o = pos[kSetBa];
-            for (int k = 0; k < 3; k++) a.X_ba[3 * o + k] = (double)a.xyz_b[ob + k];
+            for (int k = 0; k < 3; k++) a.X_ba[3 * o + k] = (double)pts.b(ob, k);
             a.uvn_ba[2 * o] = (a.Kinv[0] * ua + a.Kinv[1] * va) + a.Kinv[2];
             a.uvn_ba[2 * o + 1] = (a.Kinv[3] * ua + a.Kinv[4] * va) + a.Kinv[5];
         }
         if (f[kSet33]) {                                      // make_3d_3d (Cerebro.cpp:1624)
             const int o = pos[kSet33];
-            for (int k = 0; k < 3; k++) { a.A[3 * o + k] = (double)a.xyz_a[oa + k]; a.B[3 * o + k] = (double)a.xyz_b[ob + k]; }
+            for (int k = 0; k < 3; k++) { a.A[3 * o + k] = (double)pts.a(oa, k); a.B[3 * o + k] = (double)pts.b(ob, k); }
         }
     }
     if (tid < kNSets) a.counts[tid] = run[tid];
@@ -346,18 +379,13 @@ struct SetsBatchArgs {
     int32_t *counts;                      // [B][kNSets]
     BatchCands cands;
 };
-// grid B: the sets of candidate blockIdx.x, inlier = the OR of its four planes, outputs into its slabs
-__global__ __launch_bounds__(kOneWg) void pose_sets_batch(SetsBatchArgs b)
+// the sets of candidate z, inlier = the OR of its four planes, outputs into its slabs
+template <class Points>
+__device__ __forceinline__ void pose_sets_candidate(const SetsBatchArgs &b, int z, const Points &pts)
 {
-    const int z = blockIdx.x;
-    if (b.cands.c[z].n == 0) {
-        if (threadIdx.x < kNSets) b.counts[z * kNSets + threadIdx.x] = 0;
-        return;
-    }
     const size_t row = (size_t)z * b.n1;
     SetsArgs a;
     a.kp1 = b.kp1; a.kp2 = b.cands.c[z].kp; a.n = b.n1;
-    a.xyz_a = b.xyz_a; a.xyz_b = b.cands.c[z].xyz; a.w1 = b.w1; a.h1 = b.h1; a.w2 = b.cands.c[z].w; a.h2 = b.cands.c[z].h;
     for (int k = 0; k < 9; k++) a.Kinv[k] = b.Kinv[k];
     a.uv = b.uv + 2 * row; a.uv_d = b.uv_d + 2 * row; a.X_ab = b.X_ab + 3 * row; a.uvn_ab = b.uvn_ab + 2 * row;
     a.X_ba = b.X_ba + 3 * row; a.uvn_ba = b.uvn_ba + 2 * row; a.A = b.A + 3 * row; a.B = b.B + 3 * row;
@@ -365,7 +393,56 @@ __global__ __launch_bounds__(kOneWg) void pose_sets_batch(SetsBatchArgs b)
     const unsigned long long *keys = b.keys + row;
     const uint8_t *p = b.plane + 4 * row;
     const size_t n1 = (size_t)b.n1;
-    pose_sets_body(a, [&](int i) { return (p[i] | p[n1 + i] | p[2 * n1 + i] | p[3 * n1 + i]) != 0; }, [&](int i) { return key_train(keys[i]); });
+    pose_sets_body(a, [&](int i) { return (p[i] | p[n1 + i] | p[2 * n1 + i] | p[3 * n1 + i]) != 0; }, [&](int i) { return key_train(keys[i]); }, pts);
+}
+// grid B: candidate blockIdx.x on the 3-D images of the two frames
+__global__ __launch_bounds__(kOneWg) void pose_sets_batch(SetsBatchArgs b)
+{
+    const int z = blockIdx.x;
+    if (b.cands.c[z].n == 0) {
+        if (threadIdx.x < kNSets) b.counts[z * kNSets + threadIdx.x] = 0;
+        return;
+    }
+    pose_sets_candidate(b, z, ImagePoints{b.xyz_a, b.cands.c[z].xyz, b.w1, b.h1, b.cands.c[z].w, b.cands.c[z].h});
+}
+
+// ------------------------------------------------------------------------------------------------ frames kept on the device
+// frame_gather: a frame's point records at put time, one thread per keypoint; afterwards the staged image is not needed again
+struct GatherArgs {
+    const float2 *kp;             // n, in the frame's slot
+    const float *xyz;             // h x w x 3, staged
+    float4 *rec;                  // n, in the frame's slot
+    int32_t n, w, h;
+};
+constexpr int kGatherThreads = 256;
+__global__ __launch_bounds__(kGatherThreads) void frame_gather(GatherArgs g)
+{
+    const int i = blockIdx.x * kGatherThreads + threadIdx.x;
+    if (i >= g.n) return;
+    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+    int x, y;
+    if (pixel_of(g.kp[i], g.w, g.h, &x, &y)) {
+        const size_t o = 3 * ((size_t)y * g.w + x);
+        r = make_float4(g.xyz[o], g.xyz[o + 1], g.xyz[o + 2], 1.0f);
+    }
+    g.rec[i] = r;
+}
+
+// pose_sets_batch on stored frames: the candidates' descriptors and keypoints (b.cands) point into the store, b.xyz_a and the candidates'
+// xyz are null, the points are the records.  The argument block of pose_sets_batch is b unchanged.
+struct SetsStoredArgs {
+    SetsBatchArgs b;
+    const float4 *rec_a;
+    const float4 *rec[kMaxBatch];
+};
+__global__ __launch_bounds__(kOneWg) void pose_sets_stored_batch(SetsStoredArgs s)
+{
+    const int z = blockIdx.x;
+    if (s.b.cands.c[z].n == 0) {
+        if (threadIdx.x < kNSets) s.b.counts[z * kNSets + threadIdx.x] = 0;
+        return;
+    }
+    pose_sets_candidate(s.b, z, RecordPoints{s.rec_a, s.rec[z]});
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -391,6 +468,16 @@ struct MatchState {
     DevBuf<double> uv, uv_d, X_ab, uvn_ab, X_ba, uvn_ba, A, B;
     DevBuf<int32_t> mq, mt;
     std::vector<unsigned long long> h_keys;     // fetch_matches: keys on their way out
+    // the frame store (chip_frame_store_reserve): n_slots slots of slot_kp keypoints each, 56 bytes per keypoint; rows never move after the
+    // reserve.  Slot k: desc + 32 * k * slot_kp, kp + k * slot_kp, rec + k * slot_kp.  stage_xyz: the image of the put in flight.
+    struct StoredFrame { int64_t id = 0; int32_t n = 0, w = 0, h = 0; bool used = false; };
+    DevBuf<uint8_t> store_desc;
+    DevBuf<float2> store_kp;
+    DevBuf<float4> store_rec;
+    DevBuf<float> stage_xyz;
+    int32_t n_slots = 0, slot_kp = 0, n_frames = 0;
+    std::vector<StoredFrame> slots;
+    std::unordered_map<int64_t, int32_t> slot_of;   // id -> slot
     hipEvent_t ev[4] = {};                      // tuning only (CHIP_MATCH_BATCH_TIMING=1): around the three launches of a run
     // what the last run left: n_cand candidates of a query frame of n1 keypoints, of which ONE is selected -- the pointers and counts
     // chip_match_read_sets and the _matched solvers work on
@@ -481,20 +568,25 @@ static int check_frame(const chip_match_frame *f)
     return CHIP_OK;
 }
 
-// The buffers of a run for B candidates of a query frame of n1 keypoints: tot_n keypoints and tot_px pixels over all candidates.
-// Whatever has to grow grows inside ONE pause (as match_state).
-static int batch_reserve(Ctx *c, MatchState *st, size_t B, size_t n1, size_t tot_n, size_t tot_px, size_t px_a)
+// The buffers of a run for B candidates of a query frame of n1 keypoints; with uploads, the frames as well: tot_n keypoints and tot_px
+// pixels over all candidates (a run on stored frames uploads nothing and has no such buffers).  Whatever has to grow grows inside ONE
+// pause (as match_state).
+static int batch_reserve(Ctx *c, MatchState *st, size_t B, size_t n1, bool uploads, size_t tot_n, size_t tot_px, size_t px_a)
 {
     const size_t rows = B * n1;
-    const bool fits = st->xyz_a.capacity() >= 3 * px_a && st->desc.capacity() >= tot_n * CHIP_ORB_DESC_BYTES && st->kp.capacity() >= tot_n &&
-                      st->xyz.capacity() >= 3 * tot_px && st->keys.capacity() >= rows && st->table.capacity() >= B * 4 * kCells * kCells &&
+    const bool frames_fit = !uploads || (st->xyz_a.capacity() >= 3 * px_a && st->desc.capacity() >= tot_n * CHIP_ORB_DESC_BYTES &&
+                                         st->kp.capacity() >= tot_n && st->xyz.capacity() >= 3 * tot_px);
+    const bool fits = frames_fit && st->keys.capacity() >= rows && st->table.capacity() >= B * 4 * kCells * kCells &&
                       st->plane.capacity() >= 4 * rows && st->uv.capacity() >= 2 * rows;
     if (fits) return CHIP_OK;   // the set buffers grow together with uv
     ResidentPause paused(c);
-    int rc = st->xyz_a.reserve(c, 3 * px_a);
-    if (rc == CHIP_OK) rc = st->desc.reserve(c, tot_n * CHIP_ORB_DESC_BYTES);
-    if (rc == CHIP_OK) rc = st->kp.reserve(c, tot_n);
-    if (rc == CHIP_OK) rc = st->xyz.reserve(c, 3 * tot_px);
+    int rc = CHIP_OK;
+    if (uploads) {
+        rc = st->xyz_a.reserve(c, 3 * px_a);
+        if (rc == CHIP_OK) rc = st->desc.reserve(c, tot_n * CHIP_ORB_DESC_BYTES);
+        if (rc == CHIP_OK) rc = st->kp.reserve(c, tot_n);
+        if (rc == CHIP_OK) rc = st->xyz.reserve(c, 3 * tot_px);
+    }
     if (rc == CHIP_OK) rc = st->keys.reserve(c, rows);
     if (rc == CHIP_OK) rc = st->table.reserve(c, B * 4 * kCells * kCells);
     if (rc == CHIP_OK) rc = st->plane.reserve(c, 4 * rows);
@@ -511,32 +603,121 @@ static int batch_reserve(Ctx *c, MatchState *st, size_t B, size_t n1, size_t tot
     return rc;
 }
 
-// The pipeline: frame a against the candidates b[0 .. B) -- uploads, three launches, the counts back -- leaves the keys and the five sets
-// of every candidate in its slab, cand_sm[0 .. B) filled and candidate 0 selected.  match_mu held, the arguments checked, have_sets false.
+// A run's frames as the kernels see them, once their device pointers are known: uploaded host frames (xyz_a and cands.c[j].xyz, the
+// image policy) or slots of the frame store (rec_a and rec[j], the record policy).  A candidate with n == 0 takes no part.
+struct RunFrames {
+    const uint8_t *desc_a = nullptr;
+    const float2 *kp_a = nullptr;
+    int32_t n1 = 0, w1 = 0, h1 = 0;
+    const float *xyz_a = nullptr;
+    const float4 *rec_a = nullptr;
+    bool stored = false;
+    BatchCands cands;
+    const float4 *rec[kMaxBatch];
+    int32_t max_n2 = 0;
+    RunFrames() { std::memset(&cands, 0, sizeof cands); std::memset(rec, 0, sizeof rec); }
+};
+
+// tuning only (CHIP_MATCH_BATCH_TIMING=1): device time of each of the three kernels by events, averaged, printed at process exit; runs on
+// host frames and runs on stored frames are kept apart
+struct KernelTiming {
+    const char *what, *sets;
+    double acc[3] = {0, 0, 0}; long n = 0; bool on = std::getenv("CHIP_MATCH_BATCH_TIMING") != nullptr;
+    KernelTiming(const char *w, const char *k) : what(w), sets(k) {}
+    ~KernelTiming() { if (on && n) std::fprintf(stderr, "%s kernel timing over %ld calls (us): hamming_match_split %.1f, gms_batch %.1f, %s %.1f\n",
+                                                what, n, 1e3 * acc[0] / n, 1e3 * acc[1] / n, sets, 1e3 * acc[2] / n); }
+};
+
+// The device part of a run, for both kinds of frames (f.n1 >= 1, the slabs reserved): the keys preset, three launches, the counts back,
+// cand_sm[0 .. B) filled.
+static int match_launch(Ctx *c, MatchState *st, hipStream_t s, const RunFrames &f, int B, const double Kinv[9])
+{
+    const int n1 = f.n1;
+    CHIP_HIP(c, hipMemsetAsync(st->keys, 0xff, (size_t)B * n1 * sizeof(unsigned long long), s));   // all ones: no match yet
+    if (f.max_n2 > 0) {
+        static KernelTiming kt_host("match batch", "pose_sets_batch"), kt_stored("match batch stored", "pose_sets_stored_batch");
+        KernelTiming &kt = f.stored ? kt_stored : kt_host;
+        if (kt.on)
+            for (hipEvent_t &e : st->ev)
+                if (!e) CHIP_HIP(c, hipEventCreate(&e));
+        if (kt.on) CHIP_HIP(c, hipEventRecord(st->ev[0], s));
+        int rc = launch_matcher(c, s, f.desc_a, n1, f.cands, f.max_n2, B, st->keys);
+        if (rc != CHIP_OK) return rc;
+        if (kt.on) CHIP_HIP(c, hipEventRecord(st->ev[1], s));
+        GmsBatchArgs ga;
+        ga.kp1 = f.kp_a; ga.n1 = n1; ga.w1 = f.w1; ga.h1 = f.h1; ga.keys = st->keys; ga.table = st->table; ga.plane = st->plane;
+        ga.cands = f.cands;
+        hipLaunchKernelGGL(gms_batch, dim3(4, B), dim3(kOneWg), 0, s, ga);
+        CHIP_HIP(c, hipGetLastError());
+        if (kt.on) CHIP_HIP(c, hipEventRecord(st->ev[2], s));
+        SetsStoredArgs ss;
+        SetsBatchArgs &sa = ss.b;
+        sa.kp1 = f.kp_a; sa.xyz_a = f.xyz_a; sa.n1 = n1; sa.w1 = f.w1; sa.h1 = f.h1; sa.keys = st->keys; sa.plane = st->plane;
+        for (int i = 0; i < 9; i++) sa.Kinv[i] = Kinv[i];
+        sa.uv = st->uv; sa.uv_d = st->uv_d; sa.X_ab = st->X_ab; sa.uvn_ab = st->uvn_ab; sa.X_ba = st->X_ba; sa.uvn_ba = st->uvn_ba;
+        sa.A = st->A; sa.B = st->B; sa.mq = st->mq; sa.mt = st->mt; sa.counts = st->counts; sa.cands = f.cands;
+        if (f.stored) {
+            ss.rec_a = f.rec_a;
+            for (int j = 0; j < kMaxBatch; j++) ss.rec[j] = f.rec[j];
+            hipLaunchKernelGGL(pose_sets_stored_batch, dim3(B), dim3(kOneWg), 0, s, ss);
+        } else {
+            hipLaunchKernelGGL(pose_sets_batch, dim3(B), dim3(kOneWg), 0, s, sa);
+        }
+        CHIP_HIP(c, hipGetLastError());
+        if (kt.on) CHIP_HIP(c, hipEventRecord(st->ev[3], s));
+        CHIP_HIP(c, hipMemcpyAsync(st->h_counts.host(), st->counts, (size_t)B * kNSets * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        CHIP_HIP(c, hipStreamSynchronize(s));
+        for (int k = 0; k < 3 && kt.on; k++) {
+            float ms = 0.f;
+            CHIP_HIP(c, hipEventElapsedTime(&ms, st->ev[k], st->ev[k + 1]));
+            kt.acc[k] += ms;
+        }
+        kt.n += kt.on;
+    }
+    CHIP_HIP(c, hipStreamSynchronize(s));
+    for (int j = 0; j < B && f.max_n2 > 0; j++) {
+        if (f.cands.c[j].n == 0) continue;
+        const int32_t *h = st->h_counts.host() + j * kNSets;
+        chip_match_summary &sm = st->cand_sm[j];
+        sm.n_matches_all = n1;
+        sm.n_matches_gms = h[kSetUv]; sm.n_3d2d_ab = h[kSetAb]; sm.n_3d2d_ba = h[kSetBa]; sm.n_3d3d = h[kSet33]; sm.n_out_of_image = h[kSetOut];
+    }
+    return CHIP_OK;
+}
+
+// what every run leaves: B candidates of a query frame of n1 keypoints, candidate 0 selected
+static void match_finish(MatchState *st, int B, int n1)
+{
+    st->n_cand = B;
+    st->n1 = n1;
+    st->select(0);
+    st->have_sets = true;
+}
+
+// The pipeline on host frames: frame a against the candidates b[0 .. B) -- uploads, three launches, the counts back -- leaves the keys and
+// the five sets of every candidate in its slab, cand_sm[0 .. B) filled and candidate 0 selected.  match_mu held, the arguments checked,
+// have_sets false.
 static int match_run(Ctx *c, MatchState *st, const chip_match_frame *a, const chip_match_frame *b, int B, const double Kinv[9])
 {
     const int n1 = a->n;
-    int max_n2 = 0;
+    RunFrames f;
     size_t tot_n = 0, tot_px = 0;
     for (int j = 0; j < B; j++) {
         if (b[j].n == 0) continue;               // an empty candidate is not uploaded: no matches (BFMatcher on an empty descriptor matrix)
-        max_n2 = b[j].n > max_n2 ? b[j].n : max_n2;
+        f.max_n2 = b[j].n > f.max_n2 ? b[j].n : f.max_n2;
         tot_n += (size_t)b[j].n;
         tot_px += (size_t)b[j].width * b[j].height;
     }
     for (int j = 0; j < B; j++) std::memset(&st->cand_sm[j], 0, sizeof(chip_match_summary));
     if (n1 > 0) {
         const size_t px_a = (size_t)a->width * a->height;
-        int rc = batch_reserve(c, st, (size_t)B, (size_t)n1, tot_n, tot_px, px_a);
+        int rc = batch_reserve(c, st, (size_t)B, (size_t)n1, true, tot_n, tot_px, px_a);
         if (rc != CHIP_OK) return rc;
         hipStream_t s = match_stream(c);
-        CHIP_HIP(c, hipMemsetAsync(st->keys, 0xff, (size_t)B * n1 * sizeof(unsigned long long), s));   // all ones: no match yet
-        if (max_n2 > 0) {
+        if (f.max_n2 > 0) {
             CHIP_HIP(c, hipMemcpyAsync(st->d1, a->desc, (size_t)n1 * CHIP_ORB_DESC_BYTES, hipMemcpyHostToDevice, s));
             CHIP_HIP(c, hipMemcpyAsync(st->kp1, a->kp_xy, (size_t)n1 * sizeof(float2), hipMemcpyHostToDevice, s));
             CHIP_HIP(c, hipMemcpyAsync(st->xyz_a, a->xyz, 3 * px_a * sizeof(float), hipMemcpyHostToDevice, s));
-            BatchCands cands;
-            std::memset(&cands, 0, sizeof cands);
             size_t off_n = 0, off_px = 0;
             for (int j = 0; j < B; j++) {
                 const int n2 = b[j].n;
@@ -548,59 +729,44 @@ static int match_run(Ctx *c, MatchState *st, const chip_match_frame *a, const ch
                 CHIP_HIP(c, hipMemcpyAsync(dd, b[j].desc, (size_t)n2 * CHIP_ORB_DESC_BYTES, hipMemcpyHostToDevice, s));
                 CHIP_HIP(c, hipMemcpyAsync(dk, b[j].kp_xy, (size_t)n2 * sizeof(float2), hipMemcpyHostToDevice, s));
                 CHIP_HIP(c, hipMemcpyAsync(dx, b[j].xyz, 3 * px * sizeof(float), hipMemcpyHostToDevice, s));
-                cands.c[j] = BatchCand{reinterpret_cast<const uint4 *>(dd), dk, dx, n2, b[j].width, b[j].height, 0};
+                f.cands.c[j] = BatchCand{reinterpret_cast<const uint4 *>(dd), dk, dx, n2, b[j].width, b[j].height, 0};
                 off_n += (size_t)n2; off_px += px;
             }
-            // tuning only (CHIP_MATCH_BATCH_TIMING=1): device time of each of the three kernels by events, averaged, printed at process exit
-            struct KernelTiming {
-                double acc[3] = {0, 0, 0}; long n = 0; bool on = std::getenv("CHIP_MATCH_BATCH_TIMING") != nullptr;
-                ~KernelTiming() { if (on && n) std::fprintf(stderr, "match batch kernel timing over %ld calls (us): hamming_match_split %.1f, gms_batch %.1f, pose_sets_batch %.1f\n",
-                                                            n, 1e3 * acc[0] / n, 1e3 * acc[1] / n, 1e3 * acc[2] / n); }
-            };
-            static KernelTiming kt;
-            if (kt.on)
-                for (hipEvent_t &e : st->ev)
-                    if (!e) CHIP_HIP(c, hipEventCreate(&e));
-            if (kt.on) CHIP_HIP(c, hipEventRecord(st->ev[0], s));
-            rc = launch_matcher(c, s, st->d1, n1, cands, max_n2, B, st->keys);
-            if (rc != CHIP_OK) return rc;
-            if (kt.on) CHIP_HIP(c, hipEventRecord(st->ev[1], s));
-            GmsBatchArgs ga;
-            ga.kp1 = st->kp1; ga.n1 = n1; ga.w1 = a->width; ga.h1 = a->height; ga.keys = st->keys; ga.table = st->table; ga.plane = st->plane;
-            ga.cands = cands;
-            hipLaunchKernelGGL(gms_batch, dim3(4, B), dim3(kOneWg), 0, s, ga);
-            CHIP_HIP(c, hipGetLastError());
-            if (kt.on) CHIP_HIP(c, hipEventRecord(st->ev[2], s));
-            SetsBatchArgs sa;
-            sa.kp1 = st->kp1; sa.xyz_a = st->xyz_a; sa.n1 = n1; sa.w1 = a->width; sa.h1 = a->height; sa.keys = st->keys; sa.plane = st->plane;
-            for (int i = 0; i < 9; i++) sa.Kinv[i] = Kinv[i];
-            sa.uv = st->uv; sa.uv_d = st->uv_d; sa.X_ab = st->X_ab; sa.uvn_ab = st->uvn_ab; sa.X_ba = st->X_ba; sa.uvn_ba = st->uvn_ba;
-            sa.A = st->A; sa.B = st->B; sa.mq = st->mq; sa.mt = st->mt; sa.counts = st->counts; sa.cands = cands;
-            hipLaunchKernelGGL(pose_sets_batch, dim3(B), dim3(kOneWg), 0, s, sa);
-            CHIP_HIP(c, hipGetLastError());
-            if (kt.on) CHIP_HIP(c, hipEventRecord(st->ev[3], s));
-            CHIP_HIP(c, hipMemcpyAsync(st->h_counts.host(), st->counts, (size_t)B * kNSets * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            CHIP_HIP(c, hipStreamSynchronize(s));
-            for (int k = 0; k < 3 && kt.on; k++) {
-                float ms = 0.f;
-                CHIP_HIP(c, hipEventElapsedTime(&ms, st->ev[k], st->ev[k + 1]));
-                kt.acc[k] += ms;
-            }
-            kt.n += kt.on;
         }
-        CHIP_HIP(c, hipStreamSynchronize(s));
-        for (int j = 0; j < B && max_n2 > 0; j++) {
-            if (b[j].n == 0) continue;
-            const int32_t *h = st->h_counts.host() + j * kNSets;
-            chip_match_summary &sm = st->cand_sm[j];
-            sm.n_matches_all = n1;
-            sm.n_matches_gms = h[kSetUv]; sm.n_3d2d_ab = h[kSetAb]; sm.n_3d2d_ba = h[kSetBa]; sm.n_3d3d = h[kSet33]; sm.n_out_of_image = h[kSetOut];
-        }
+        f.desc_a = st->d1; f.kp_a = st->kp1; f.n1 = n1; f.w1 = a->width; f.h1 = a->height; f.xyz_a = st->xyz_a;
+        rc = match_launch(c, st, s, f, B, Kinv);
+        if (rc != CHIP_OK) return rc;
     }
-    st->n_cand = B;
-    st->n1 = n1;
-    st->select(0);
-    st->have_sets = true;
+    match_finish(st, B, n1);
+    return CHIP_OK;
+}
+
+// The pipeline on stored frames: slot sa against the slots sb[0 .. B), nothing uploaded.  Same state afterwards as match_run.
+static int match_run_stored(Ctx *c, MatchState *st, int32_t sa, const int32_t *sb, int B, const double Kinv[9])
+{
+    const MatchState::StoredFrame &a = st->slots[(size_t)sa];
+    const size_t kp = (size_t)st->slot_kp;
+    RunFrames f;
+    f.stored = true;
+    for (int j = 0; j < B; j++) {
+        const MatchState::StoredFrame &b = st->slots[(size_t)sb[j]];
+        std::memset(&st->cand_sm[j], 0, sizeof(chip_match_summary));
+        if (b.n == 0) continue;
+        const size_t at = (size_t)sb[j] * kp;
+        f.max_n2 = b.n > f.max_n2 ? b.n : f.max_n2;
+        f.cands.c[j] = BatchCand{reinterpret_cast<const uint4 *>(st->store_desc + at * CHIP_ORB_DESC_BYTES), st->store_kp + at, nullptr, b.n, b.w, b.h, 0};
+        f.rec[j] = st->store_rec + at;
+    }
+    if (a.n > 0) {
+        int rc = batch_reserve(c, st, (size_t)B, (size_t)a.n, false, 0, 0, 0);
+        if (rc != CHIP_OK) return rc;
+        const size_t at = (size_t)sa * kp;
+        f.desc_a = st->store_desc + at * CHIP_ORB_DESC_BYTES; f.kp_a = st->store_kp + at; f.rec_a = st->store_rec + at;
+        f.n1 = a.n; f.w1 = a.w; f.h1 = a.h;
+        rc = match_launch(c, st, match_stream(c), f, B, Kinv);
+        if (rc != CHIP_OK) return rc;
+    }
+    match_finish(st, B, a.n);
     return CHIP_OK;
 }
 
@@ -843,5 +1009,164 @@ extern "C" int chip_pnp_ransac_matched_batch(chip_ctx *c, int32_t P, const int32
         confidence[at[r]] = conf[r];
         if (summary) summary[at[r]] = summ[r];
     }
+    return CHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the frame store
+extern "C" int chip_build_has_frame_store(void) { return 1; }
+
+extern "C" int chip_frame_store_reserve(chip_ctx *c, int32_t n_slots, int32_t slot_keypoints)
+{
+    if (!c || n_slots < 1 || slot_keypoints < 1 || slot_keypoints > kMatchMax) return CHIP_ERR_INVALID_ARG;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    CHIP_HIP(c, hipSetDevice(c->device));
+    MatchState *st = nullptr;
+    int rc = match_state(c, &st);
+    if (rc != CHIP_OK) return rc;
+    if (st->n_slots == n_slots && st->slot_kp == slot_keypoints) return CHIP_OK;
+    if (st->n_frames > 0) return CHIP_ERR_BUSY;
+    ResidentPause paused(c);                 // the frees and the three allocations inside one pause
+    CHIP_HIP(c, hipStreamSynchronize(match_stream(c)));
+    st->store_desc.release(); st->store_kp.release(); st->store_rec.release();
+    st->n_slots = st->slot_kp = 0;
+    st->slots.clear();
+    const size_t rows = (size_t)n_slots * (size_t)slot_keypoints;
+    rc = st->store_desc.alloc(c, rows * CHIP_ORB_DESC_BYTES);
+    if (rc == CHIP_OK) rc = st->store_kp.alloc(c, rows);
+    if (rc == CHIP_OK) rc = st->store_rec.alloc(c, rows);
+    if (rc != CHIP_OK) {                     // no store rather than part of one
+        st->store_desc.release(); st->store_kp.release(); st->store_rec.release();
+        return rc;
+    }
+    st->slots.assign((size_t)n_slots, MatchState::StoredFrame());
+    st->n_slots = n_slots; st->slot_kp = slot_keypoints;
+    return CHIP_OK;
+}
+
+extern "C" int chip_frame_store_info(chip_ctx *c, int32_t *n_slots, int32_t *slot_keypoints, int32_t *n_frames)
+{
+    if (!c) return CHIP_ERR_INVALID_ARG;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    const MatchState *st = c->match_state;
+    if (n_slots) *n_slots = st ? st->n_slots : 0;
+    if (slot_keypoints) *slot_keypoints = st ? st->slot_kp : 0;
+    if (n_frames) *n_frames = st ? st->n_frames : 0;
+    return CHIP_OK;
+}
+
+extern "C" int chip_frame_put(chip_ctx *c, int64_t id, const chip_match_frame *f)
+{
+    if (!c) return CHIP_ERR_INVALID_ARG;
+    int rc = check_frame(f);
+    if (rc != CHIP_OK) return rc;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    MatchState *st = c->match_state;
+    if (!st || st->n_slots == 0) return CHIP_ERR_BUSY;
+    if (f->n > st->slot_kp) return CHIP_ERR_UNSUPPORTED;
+    const auto known = st->slot_of.find(id);
+    int32_t k = known != st->slot_of.end() ? known->second : -1;
+    const bool replace = k >= 0;
+    for (int32_t j = 0; k < 0 && j < st->n_slots; j++)
+        if (!st->slots[(size_t)j].used) k = j;
+    if (k < 0) return CHIP_ERR_OOM;
+    CHIP_HIP(c, hipSetDevice(c->device));
+    const size_t px = (size_t)f->width * f->height, at = (size_t)k * (size_t)st->slot_kp;
+    if (f->n > 0) {
+        rc = st->stage_xyz.reserve(c, 3 * px);   // the last step that can fail before the slot is written
+        if (rc != CHIP_OK) return rc;
+        hipStream_t s = match_stream(c);
+        GatherArgs g;
+        g.kp = st->store_kp + at; g.xyz = st->stage_xyz; g.rec = st->store_rec + at; g.n = f->n; g.w = f->width; g.h = f->height;
+        hipError_t e = hipMemcpyAsync(st->store_desc + at * CHIP_ORB_DESC_BYTES, f->desc, (size_t)f->n * CHIP_ORB_DESC_BYTES, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(st->store_kp + at, f->kp_xy, (size_t)f->n * sizeof(float2), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(st->stage_xyz, f->xyz, 3 * px * sizeof(float), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(frame_gather, dim3((f->n + kGatherThreads - 1) / kGatherThreads), dim3(kGatherThreads), 0, s, g);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(s);   // the caller's arrays are free again; a later match is ordered behind the put anyway
+        if (e != hipSuccess) {
+            if (replace) {                   // the slot's rows are undefined now: the id leaves the store
+                st->slots[(size_t)k] = MatchState::StoredFrame();
+                st->slot_of.erase(id);
+                st->n_frames--;
+            }
+            CHIP_HIP(c, e);
+        }
+    }
+    MatchState::StoredFrame &slot = st->slots[(size_t)k];
+    slot.id = id; slot.n = f->n; slot.w = f->width; slot.h = f->height; slot.used = true;
+    if (!replace) {
+        st->slot_of[id] = k;
+        st->n_frames++;
+    }
+    return CHIP_OK;
+}
+
+extern "C" int chip_frame_drop(chip_ctx *c, int64_t id)
+{
+    if (!c) return CHIP_ERR_INVALID_ARG;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    MatchState *st = c->match_state;
+    if (!st) return CHIP_ERR_RANGE;
+    const auto known = st->slot_of.find(id);
+    if (known == st->slot_of.end()) return CHIP_ERR_RANGE;
+    st->slots[(size_t)known->second] = MatchState::StoredFrame();
+    st->slot_of.erase(known);
+    st->n_frames--;
+    return CHIP_OK;
+}
+
+extern "C" int chip_frame_read(chip_ctx *c, int64_t id, int32_t *n, int32_t *width, int32_t *height, uint8_t *desc, float *kp_xy, float *pts)
+{
+    if (!c) return CHIP_ERR_INVALID_ARG;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    MatchState *st = c->match_state;
+    if (!st || st->n_slots == 0) return CHIP_ERR_BUSY;
+    const auto known = st->slot_of.find(id);
+    if (known == st->slot_of.end()) return CHIP_ERR_RANGE;
+    const MatchState::StoredFrame &slot = st->slots[(size_t)known->second];
+    if (n) *n = slot.n;
+    if (width) *width = slot.w;
+    if (height) *height = slot.h;
+    if (slot.n == 0 || (!desc && !kp_xy && !pts)) return CHIP_OK;
+    CHIP_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = match_stream(c);
+    const size_t at = (size_t)known->second * (size_t)st->slot_kp, m = (size_t)slot.n;
+    if (desc) CHIP_HIP(c, hipMemcpyAsync(desc, st->store_desc + at * CHIP_ORB_DESC_BYTES, m * CHIP_ORB_DESC_BYTES, hipMemcpyDeviceToHost, s));
+    if (kp_xy) CHIP_HIP(c, hipMemcpyAsync(kp_xy, st->store_kp + at, m * sizeof(float2), hipMemcpyDeviceToHost, s));
+    if (pts) CHIP_HIP(c, hipMemcpyAsync(pts, st->store_rec + at, m * sizeof(float4), hipMemcpyDeviceToHost, s));
+    CHIP_HIP(c, hipStreamSynchronize(s));
+    return CHIP_OK;
+}
+
+extern "C" int chip_match_batch_stored(chip_ctx *c, int64_t a_id, const int64_t *b_ids, int32_t B, const double Kinv[9], chip_match_summary *summary)
+{
+    if (!c) return CHIP_ERR_INVALID_ARG;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    MatchState *st = c->match_state;
+    if (st) st->have_sets = false;           // a failed call, refused arguments included, leaves nothing selected
+    if (!b_ids || !Kinv || !summary || B < 1) return CHIP_ERR_INVALID_ARG;
+    if (B > kMaxBatch) return CHIP_ERR_UNSUPPORTED;
+    if (!st || st->n_slots == 0) return CHIP_ERR_BUSY;
+    int32_t sb[kMaxBatch];
+    const auto fa = st->slot_of.find(a_id);
+    if (fa == st->slot_of.end()) return CHIP_ERR_RANGE;
+    for (int j = 0; j < B; j++) {
+        const auto fb = st->slot_of.find(b_ids[j]);
+        if (fb == st->slot_of.end()) return CHIP_ERR_RANGE;
+        sb[j] = fb->second;
+    }
+    CHIP_HIP(c, hipSetDevice(c->device));
+    const int rc = match_run_stored(c, st, fa->second, sb, B, Kinv);
+    if (rc != CHIP_OK) return rc;
+    st->keys_readable = true;
+    for (int j = 0; j < B; j++) summary[j] = st->cand_sm[j];
     return CHIP_OK;
 }

@@ -539,15 +539,10 @@ bool StaticPointFeatureMatching::make_3d_3d_collection__using__pfmatches_and_dis
     return true;
 }
 
-bool verify_candidates(chip_ctx *ctx, const chip_match_frame &frame_a, const chip_match_frame *frames_b, int B, const double Kinv[9],
-                       ProcessedLoopCandidate *pc, bool *accepted, const uint64_t *seeds, chip_match_summary *summaries)
+// Everything after the match call of verify_candidates / verify_candidates_stored, on the B candidates the call left on the device
+// (sm: their summaries): the "< 150 matches" reject, ONE chip_pnp_ransac_matched_batch over the survivors, ICP per survivor, the gates.
+static bool verify_matched(chip_ctx *ctx, const chip_match_summary *sm, int B, ProcessedLoopCandidate *pc, bool *accepted, const uint64_t *seeds)
 {
-    if (!frames_b || !pc || !accepted || B < 1 || B > CHIP_MATCH_MAX_BATCH) return false;
-    for (int j = 0; j < B; j++) accepted[j] = false;
-    chip_match_summary sm[CHIP_MATCH_MAX_BATCH] = {};
-    const int rc = chip_match_batch(ctx, &frame_a, frames_b, B, Kinv, sm);
-    if (summaries) for (int j = 0; j < B; j++) summaries[j] = sm[j];
-    if (rc != CHIP_OK) return false;
     chip_ransac_params pp, pi;
     chip_ransac_params_default(&pp);
     chip_icp_params_default(&pi);
@@ -589,6 +584,30 @@ bool verify_candidates(chip_ctx *ctx, const chip_match_frame &frame_a, const chi
         accepted[j] = true;
     }
     return true;
+}
+
+bool verify_candidates(chip_ctx *ctx, const chip_match_frame &frame_a, const chip_match_frame *frames_b, int B, const double Kinv[9],
+                       ProcessedLoopCandidate *pc, bool *accepted, const uint64_t *seeds, chip_match_summary *summaries)
+{
+    if (!frames_b || !pc || !accepted || B < 1 || B > CHIP_MATCH_MAX_BATCH) return false;
+    for (int j = 0; j < B; j++) accepted[j] = false;
+    chip_match_summary sm[CHIP_MATCH_MAX_BATCH] = {};
+    const int rc = chip_match_batch(ctx, &frame_a, frames_b, B, Kinv, sm);
+    if (summaries) for (int j = 0; j < B; j++) summaries[j] = sm[j];
+    if (rc != CHIP_OK) return false;
+    return verify_matched(ctx, sm, B, pc, accepted, seeds);
+}
+
+bool verify_candidates_stored(chip_ctx *ctx, int64_t a_id, const int64_t *b_ids, int B, const double Kinv[9], ProcessedLoopCandidate *pc,
+                              bool *accepted, const uint64_t *seeds, chip_match_summary *summaries)
+{
+    if (!b_ids || !pc || !accepted || B < 1 || B > CHIP_MATCH_MAX_BATCH) return false;
+    for (int j = 0; j < B; j++) accepted[j] = false;
+    chip_match_summary sm[CHIP_MATCH_MAX_BATCH] = {};
+    const int rc = chip_match_batch_stored(ctx, a_id, b_ids, B, Kinv, sm);
+    if (summaries) for (int j = 0; j < B; j++) summaries[j] = sm[j];
+    if (rc != CHIP_OK) return false;
+    return verify_matched(ctx, sm, B, pc, accepted, seeds);
 }
 
 bool verify_candidate(chip_ctx *ctx, const chip_match_frame &frame_a, const chip_match_frame &frame_b, const double Kinv[9],

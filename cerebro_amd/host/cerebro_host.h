@@ -217,6 +217,11 @@ bool verify_candidate(chip_ctx *ctx, const chip_match_frame &frame_a, const chip
 // only if a library call failed (then every accepted[j] is false).
 bool verify_candidates(chip_ctx *ctx, const chip_match_frame &frame_a, const chip_match_frame *frames_b, int B, const double Kinv[9],
                        ProcessedLoopCandidate *pc, bool *accepted, const uint64_t *seeds = nullptr, chip_match_summary *summaries = nullptr);
+// The same on frames kept on the device (chip_frame_put under the ids a_id / b_ids[j]): ONE chip_match_batch_stored -- nothing is
+// uploaded -- then the same tail as verify_candidates (one copy of it).  Field for field what verify_candidates gives on the host
+// frames that were put under those ids, with the same seeds.  An unknown id is a failed library call (false).
+bool verify_candidates_stored(chip_ctx *ctx, int64_t a_id, const int64_t *b_ids, int B, const double Kinv[9], ProcessedLoopCandidate *pc,
+                              bool *accepted, const uint64_t *seeds = nullptr, chip_match_summary *summaries = nullptr);
 
 // PoseManipUtils::R2ypr (src/utils/PoseManipUtils.cpp:148-163), degrees, from a column-major 4x4
 void matrix4_to_rawyprt(const double T_colmajor[16], double ypr_deg[3], double t[3]);

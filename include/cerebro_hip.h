@@ -610,6 +610,58 @@ int chip_pnp_ransac_matched_batch(chip_ctx *ctx, int32_t P, const int32_t *cand,
                                   float *confidence /* P */, uint8_t *const *inlier_mask /* may be NULL */,
                                   chip_ransac_summary *summary /* P or NULL */, int32_t *status /* P */);
 
+/* ---- frames kept on the device: the match stage without uploads.  chip_match_batch spends most of its time copying 3-D images of
+ * which the sets read ONE pixel per keypoint, and the same keyframes come back call after call (three queries per tick, top-K lists
+ * of neighbouring places, the query of now is a candidate later).  A frame is therefore PUT once under a caller-chosen 64-bit id
+ * (DataNode / the data_map rank): its descriptors and keypoints stay on the device, the kernel frame_gather reads its 3-D points at
+ * the keypoints, and the image is dropped.  chip_match_batch_stored then runs the pipeline above on stored frames by id.
+ *
+ * Definitions:
+ *   - store layout: n_slots slots of slot_keypoints keypoints each, 1 <= slot_keypoints <= CHIP_MATCH_MAX_KEYPOINTS, 56 bytes per
+ *     keypoint (32 descriptor, 8 keypoint, 16 point record): device memory = n_slots x slot_keypoints x 56 B, allocated once by
+ *     chip_frame_store_reserve inside one pause of the resident scan (as the other buffers of the stage); rows never move after
+ *     the reserve, as the DB segments.  The same two numbers again: a no-op.  Other numbers: allowed only while the store holds
+ *     no frame (the store is then allocated anew), otherwise CHIP_ERR_BUSY.  n_slots < 1 or slot_keypoints out of range:
+ *     CHIP_ERR_INVALID_ARG.  chip_destroy frees the store;
+ *   - before any reserve: put, read and match_batch_stored return CHIP_ERR_BUSY, drop CHIP_ERR_RANGE, info reports 0 / 0 / 0;
+ *   - chip_frame_put: the frame rules of chip_match_pair (NULL pointers CHIP_ERR_INVALID_ARG, sizes beyond its limits
+ *     CHIP_ERR_UNSUPPORTED), then f->n > slot_keypoints CHIP_ERR_UNSUPPORTED (the caller keeps using host frames for such a frame).
+ *     Descriptors and keypoints are uploaded into the slot, the image into a staging buffer (grown on demand, never part of the
+ *     store); frame_gather runs on the ctx stream; n, width and height are kept with the slot.  The call returns when the copies
+ *     and the kernel are complete: the caller's arrays are free again.  An id already stored is REPLACED in its own slot.  No free
+ *     slot: CHIP_ERR_OOM -- nothing is evicted silently, eviction is the integrator's policy (chip_frame_drop).  A frame with
+ *     n == 0 is stored.  A failed put leaves the store as it was and a failed replace keeps the old frame: every check and
+ *     allocation precedes the first write to the slot.  The one exception is a HIP error AFTER the copies of a replace began
+ *     (CHIP_ERR_HIP): the slot's rows are undefined then, and the id leaves the store;
+ *   - point record: one float4 per keypoint.  The pixel is the one the sets use (truncation; (-1, w) maps into [0, w - 1]; NaN and
+ *     everything else is outside).  Pixel in the image: (x, y, z, 1.0f), the three floats copied bit for bit from the image;
+ *     otherwise (0, 0, 0, 0.0f).  The flag is a lane of its own because a NaN z passes the depth gate, as in the reference: no
+ *     value of z can mean "outside";
+ *   - chip_frame_drop: unknown id CHIP_ERR_RANGE; the slot is free for the next put.  Sets and keys an earlier match left stay
+ *     valid (they live in the run's slabs, not in the store);
+ *   - chip_frame_read: a read-back (tests, checkpoints): desc and kp_xy are the bytes that were put, pts the records; any pointer
+ *     may be NULL; unknown id CHIP_ERR_RANGE;
+ *   - chip_match_batch_stored: the status rules of chip_match_batch, and an unknown a_id or b_ids[j] CHIP_ERR_RANGE (nothing is
+ *     selected, as after any failed call).  b_ids may repeat an id and may contain a_id.  An empty query frame or an empty
+ *     candidate gives a zero summary.  summary[j], the ten arrays of chip_match_read_sets after chip_match_select(j) and
+ *     chip_match_batch_read_matches(j) are byte for byte what chip_match_batch gives on the host frames that were put under those
+ *     ids (pose_sets_stored_batch is pose_sets_batch with the records in place of the images; the other two kernels run as they
+ *     are, on pointers into the store).  Afterwards candidate 0 is selected and chip_match_batch_read_matches answers;
+ *     chip_match_select, chip_match_read_sets, chip_pnp_ransac_matched, chip_icp_ransac_matched and chip_pnp_ransac_matched_batch
+ *     work on the result unchanged;
+ *   - cost: no host-to-device copy of frame data; three launches and the B x 5 counts back.
+ * Not on chip_create_multi ctxs (CHIP_ERR_UNSUPPORTED).  These calls belong to the one matching thread of the ctx and use the ctx
+ * stream: a put is ordered before a later match.                                                                                   */
+int chip_build_has_frame_store(void);      /* 1 */
+int chip_frame_store_reserve(chip_ctx *ctx, int32_t n_slots, int32_t slot_keypoints);
+int chip_frame_store_info(chip_ctx *ctx, int32_t *n_slots, int32_t *slot_keypoints, int32_t *n_frames /* each may be NULL */);
+int chip_frame_put(chip_ctx *ctx, int64_t id, const chip_match_frame *f);
+int chip_frame_drop(chip_ctx *ctx, int64_t id);
+int chip_frame_read(chip_ctx *ctx, int64_t id, int32_t *n, int32_t *width, int32_t *height,
+                    uint8_t *desc /* n x 32 */, float *kp_xy /* n x 2 */, float *pts /* n x 4 */);
+int chip_match_batch_stored(chip_ctx *ctx, int64_t a_id, const int64_t *b_ids, int32_t B,
+                            const double Kinv_rowmajor[9], chip_match_summary *summary /* B */);
+
 /* ------------------------------------------------------------------------------------------ introspection */
 typedef struct {
     int32_t abi_version;

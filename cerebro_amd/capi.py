@@ -66,6 +66,7 @@ SCAN_FAMILY_NAMES = {0: "none", 1: "one_row", 2: "wide", 3: "rows", 4: "multi", 
 CHIP_TICK_SKIPPED, CHIP_TICK_TOO_SHORT, CHIP_TICK_SCANNED = 0, 1, 2
 CHIP_MATCH_MAX_KEYPOINTS = 16384
 CHIP_MATCH_MAX_BATCH = 16
+CHIP_ICP_MAX_BATCH = 16
 CHIP_ORB_DESC_BYTES = 32
 CHIP_SET_AB, CHIP_SET_BA = 0, 1
 
@@ -200,6 +201,8 @@ _SIGS = {
                                   C.POINTER(RansacSummary)]),
     "chip_icp_ransac_enqueue": (C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(RansacParams)]),
     "chip_icp_ransac_collect": (C.c_int, [_P, _P, C.POINTER(C.c_float), _P, C.POINTER(RansacSummary)]),
+    "chip_build_has_icp_batch": (C.c_int, []),
+    "chip_icp_ransac_batch": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.POINTER(RansacParams), _P, _P, _P, _P, _P]),
     "chip_debug_ransac_record": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(RansacShape), _P, _P, _P, _P, _P, _P, _P]),
     "chip_debug_pnp_stage": (C.c_int, [_P, C.c_int32, _P, _P, _P]),
     "chip_debug_pnp_keep_stage": (C.c_int, [_P, C.c_int32]),
@@ -225,6 +228,9 @@ _SIGS = {
     "chip_match_select": (C.c_int, [_P, C.c_int32]),
     "chip_match_batch_read_matches": (C.c_int, [_P, C.c_int32, _P, _P]),
     "chip_pnp_ransac_matched_batch": (C.c_int, [_P, C.c_int32, _P, _P, C.POINTER(RansacParams), _P, _P, _P, _P, _P, _P]),
+    "chip_icp_ransac_matched_batch_enqueue": (C.c_int, [_P, C.c_int32, _P, C.POINTER(RansacParams), _P, _P]),
+    "chip_icp_ransac_matched_batch_collect": (C.c_int, [_P, _P, _P, _P, _P]),
+    "chip_icp_ransac_matched_batch": (C.c_int, [_P, C.c_int32, _P, C.POINTER(RansacParams), _P, _P, _P, _P, _P, _P]),
     "chip_build_has_frame_store": (C.c_int, []),
     "chip_frame_store_reserve": (C.c_int, [_P, C.c_int32, C.c_int32]),
     "chip_frame_store_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -682,10 +688,32 @@ class Chip:
                     summary=dict(n_iterations=summ.n_iterations, n_inliers=summ.n_inliers,
                                  best_hypothesis=summ.best_hypothesis, n_models=summ.n_models, best_cost=summ.best_cost))
 
+    def icp_ransac_batch(self, problems, params: RansacParams | None = None, seeds=None):
+        """problems: list of (A (N_i,3), B (N_i,3)), at most CHIP_ICP_MAX_BATCH.  One pair of launches for the whole list; entry i equals
+        icp_ransac(A_i, B_i) run with seed seeds[i] (default: params.seed for all)."""
+        P = len(problems)
+        As = [np.ascontiguousarray(A, dtype=np.float64).reshape(-1, 3) for A, _ in problems]
+        Bs = [np.ascontiguousarray(B, dtype=np.float64).reshape(-1, 3) for _, B in problems]
+        Ns = np.array([a.shape[0] for a in As], dtype=np.int32)
+        p = params or default_icp_params()
+        T = np.empty((max(P, 1), 16), dtype=np.float64)
+        conf = np.zeros(max(P, 1), dtype=np.float32)
+        masks = [np.zeros(max(int(n), 1), dtype=np.uint8) for n in Ns]
+        summ = (RansacSummary * max(P, 1))()
+        Ap = (C.c_void_p * max(P, 1))(*[a.ctypes.data for a in As])
+        Bp = (C.c_void_p * max(P, 1))(*[b.ctypes.data for b in Bs])
+        mp = (C.c_void_p * max(P, 1))(*[m.ctypes.data for m in masks])
+        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+        st = self.lib.chip_icp_ransac_batch(self.h, P, Ap, Bp, _ptr(Ns), C.byref(p), None if sd is None else _ptr(sd), _ptr(T), _ptr(conf), mp, summ)
+        self._chk(st, "chip_icp_ransac_batch")
+        return [dict(status=st, confidence=float(conf[i]), T=T[i].reshape(4, 4).T.copy(), mask=masks[i][:Ns[i]].copy(),
+                     summary=dict(n_iterations=summ[i].n_iterations, n_inliers=summ[i].n_inliers, best_hypothesis=summ[i].best_hypothesis,
+                                  n_models=summ[i].n_models, best_cost=summ[i].best_cost)) for i in range(P)]
+
     # -- test aids: every hypothesis of the last estimation
     def ransac_record(self, leg: int = CHIP_RANSAC_LEG_PNP, problem: int = 0) -> dict:
-        """chip_debug_ransac_record: the record of every hypothesis of the last PnP launch (problem `problem` of it) or of the last collected
-        ICP estimation: P, H, N, words, S, sampler and valid[H], cost[H], nin[H], T[H, 16] (column-major), mask[H, words] (uint64);
+        """chip_debug_ransac_record: the record of every hypothesis of problem `problem` of the last PnP launch or of the last collected
+        ICP launch (a single call: problem 0 of 1; a matched batch: the problems that ran): P, H, N, words, S, sampler and valid[H], cost[H], nin[H], T[H, 16] (column-major), mask[H, words] (uint64);
         PnP also nsol[H] and sample[H, S].  Rejected hypotheses: T = NaN, mask row 0."""
         sh = self.ransac_record_shape(leg, problem)
         H, W, S = sh["H"], sh["words"], sh["S"]
@@ -848,6 +876,60 @@ class Chip:
             cf, s = C.c_float(float(conf[i])), RansacSummary.from_buffer_copy(summ[i])
             out.append(self._matched(int(status[i]), "chip_pnp_ransac_matched_batch", Ns[i], T[i], cf, masks[i], s))
         return out
+
+    def _icp_batch_out(self, Ns, status, T, conf, masks, summ) -> list:
+        out = []
+        for i in range(len(Ns)):
+            cf, s = C.c_float(float(conf[i])), RansacSummary.from_buffer_copy(summ[i])
+            r = self._matched(int(status[i]), "chip_icp_ransac_matched_batch", Ns[i], T[i], cf, masks[i], s)
+            if status[i] != 0:
+                r["raw"] = dict(T=T[i].copy(), confidence=float(conf[i]), mask=masks[i].copy(),
+                                summary=dict(n_iterations=s.n_iterations, n_inliers=s.n_inliers, best_hypothesis=s.best_hypothesis,
+                                             n_models=s.n_models, best_cost=s.best_cost))
+            out.append(r)
+        return out
+
+    def icp_matched_batch_enqueue(self, problems, params: RansacParams | None = None, seeds=None):
+        """chip_icp_ransac_matched_batch_enqueue.  problems: list of (candidate, N) with N = that candidate's n_3d3d (it sizes the mask).
+        Returns at once with the ticket icp_matched_batch_collect takes."""
+        P = len(problems)
+        p = params or default_icp_params()
+        cand = np.array([q[0] for q in problems], dtype=np.int32).reshape(P)
+        status = np.zeros(max(P, 1), dtype=np.int32)
+        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+        self._chk(self.lib.chip_icp_ransac_matched_batch_enqueue(self.h, P, _ptr(cand), C.byref(p), None if sd is None else _ptr(sd), _ptr(status)),
+                  "chip_icp_ransac_matched_batch_enqueue")
+        return dict(Ns=[int(q[1]) for q in problems], status=status)
+
+    def icp_matched_batch_collect(self, ticket) -> list:
+        """chip_icp_ransac_matched_batch_collect -> entry i is what icp_matched(N) returns after match_select(candidate) with that seed;
+        a left-out problem (status CHIP_ERR_TOO_FEW_POINTS) additionally carries `raw`: the T, confidence, summary and mask as delivered"""
+        Ns, status = ticket["Ns"], ticket["status"]
+        P = len(Ns)
+        T = np.zeros((max(P, 1), 16), dtype=np.float64)
+        conf = np.zeros(max(P, 1), dtype=np.float32)
+        masks = [np.full(max(n, 1), 0xAB, dtype=np.uint8) for n in Ns]
+        mp = (C.c_void_p * max(P, 1))(*[m.ctypes.data for m in masks])
+        summ = (RansacSummary * max(P, 1))()
+        self._chk(self.lib.chip_icp_ransac_matched_batch_collect(self.h, _ptr(T), _ptr(conf), mp, summ), "chip_icp_ransac_matched_batch_collect")
+        return self._icp_batch_out(Ns, status, T, conf, masks, summ)
+
+    def icp_matched_batch(self, problems, params: RansacParams | None = None, seeds=None) -> list:
+        """chip_icp_ransac_matched_batch (enqueue + collect in one call); see icp_matched_batch_enqueue / _collect"""
+        P = len(problems)
+        p = params or default_icp_params()
+        cand = np.array([q[0] for q in problems], dtype=np.int32).reshape(P)
+        Ns = [int(q[1]) for q in problems]
+        T = np.zeros((max(P, 1), 16), dtype=np.float64)
+        conf = np.zeros(max(P, 1), dtype=np.float32)
+        masks = [np.full(max(n, 1), 0xAB, dtype=np.uint8) for n in Ns]
+        mp = (C.c_void_p * max(P, 1))(*[m.ctypes.data for m in masks])
+        summ = (RansacSummary * max(P, 1))()
+        status = np.zeros(max(P, 1), dtype=np.int32)
+        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+        self._chk(self.lib.chip_icp_ransac_matched_batch(self.h, P, _ptr(cand), C.byref(p), None if sd is None else _ptr(sd), _ptr(T), _ptr(conf), mp,
+                                                         summ, _ptr(status)), "chip_icp_ransac_matched_batch")
+        return self._icp_batch_out(Ns, status, T, conf, masks, summ)
 
     # -- frames kept on the device (the frame store)
     def frame_store_reserve(self, n_slots: int, slot_keypoints: int):

@@ -588,8 +588,14 @@ int pnp_ransac_device_batch(Ctx *c, int32_t P, const double *const *X_dev, const
                             const uint64_t *seeds, double *T_colmajor, float *confidence, uint8_t *const *inlier_mask, chip_ransac_summary *summary);
 int icp_ransac_device(Ctx *c, const double *A_dev, const double *B_dev, int32_t N, const chip_ransac_params *p, double *T_colmajor,
                       float *confidence, uint8_t *inlier_mask, chip_ransac_summary *summary);
+// the enqueue half of chip_icp_ransac_matched_batch: R validated problems on device-resident sets, one pair of launches on the ICP
+// stream; problem r is answer at[r] of the `total` that chip_icp_ransac_matched_batch_collect delivers.  The caller holds match_mu.
+int icp_enqueue_device_batch(Ctx *c, int32_t R, const double *const *A_dev, const double *const *B_dev, const int32_t *N, const chip_ransac_params *p,
+                             const uint64_t *seeds, int32_t total, const int32_t *at);
+// before a match call rewrites the slabs: waits for the kernels of a pending matched ICP batch (which stays collectable).  match_mu held.
+int icp_wait_matched(Ctx *c);
 // chip_debug_ransac_record's ICP leg (icp.hip; the PnP leg lives with its state in pnp.hip): c is a plain ctx, every output may be null
-int icp_debug_record(Ctx *c, chip_debug_ransac_shape *shape, int32_t *valid, double *cost, int32_t *nin, double *T_colmajor,
+int icp_debug_record(Ctx *c, int32_t problem, chip_debug_ransac_shape *shape, int32_t *valid, double *cost, int32_t *nin, double *T_colmajor,
                      unsigned long long *mask);
 
 }  // namespace chip

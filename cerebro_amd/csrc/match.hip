@@ -699,6 +699,8 @@ static void match_finish(MatchState *st, int B, int n1)
 // have_sets false.
 static int match_run(Ctx *c, MatchState *st, const chip_match_frame *a, const chip_match_frame *b, int B, const double Kinv[9])
 {
+    int rc0 = icp_wait_matched(c);               // a pending matched ICP batch reads the slabs this run rewrites
+    if (rc0 != CHIP_OK) return rc0;
     const int n1 = a->n;
     RunFrames f;
     size_t tot_n = 0, tot_px = 0;
@@ -744,6 +746,8 @@ static int match_run(Ctx *c, MatchState *st, const chip_match_frame *a, const ch
 // The pipeline on stored frames: slot sa against the slots sb[0 .. B), nothing uploaded.  Same state afterwards as match_run.
 static int match_run_stored(Ctx *c, MatchState *st, int32_t sa, const int32_t *sb, int B, const double Kinv[9])
 {
+    int rc0 = icp_wait_matched(c);               // as match_run
+    if (rc0 != CHIP_OK) return rc0;
     const MatchState::StoredFrame &a = st->slots[(size_t)sa];
     const size_t kp = (size_t)st->slot_kp;
     RunFrames f;
@@ -1010,6 +1014,45 @@ extern "C" int chip_pnp_ransac_matched_batch(chip_ctx *c, int32_t P, const int32
         if (summary) summary[at[r]] = summ[r];
     }
     return CHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ ICP on the sets of several candidates
+extern "C" int chip_icp_ransac_matched_batch_enqueue(chip_ctx *c, int32_t P, const int32_t *cand, const chip_ransac_params *p, const uint64_t *seeds,
+                                                     int32_t *status)
+{
+    if (!c || P < 1 || !cand || !p || !status) return CHIP_ERR_INVALID_ARG;
+    if (P > CHIP_ICP_MAX_BATCH) return CHIP_ERR_UNSUPPORTED;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    MatchState *st = c->match_state;
+    if (!st || !st->have_sets) return CHIP_ERR_BUSY;
+    for (int i = 0; i < P; i++)
+        if (cand[i] < 0 || cand[i] >= st->n_cand) return CHIP_ERR_RANGE;
+    // the runnable problems, gathered: their slab pointers, counts and seeds, read in place; the selection is not touched
+    const double *A[CHIP_ICP_MAX_BATCH], *B[CHIP_ICP_MAX_BATCH];
+    int32_t N[CHIP_ICP_MAX_BATCH], at[CHIP_ICP_MAX_BATCH];
+    uint64_t sd[CHIP_ICP_MAX_BATCH];
+    int R = 0;
+    for (int i = 0; i < P; i++) {
+        const int32_t n = st->cand_sm[cand[i]].n_3d3d;
+        status[i] = ransac_check_params(p, n);
+        if (status[i] != CHIP_OK) continue;       // left out of the launch; the collect gives it the left-out answer
+        const size_t r = (size_t)cand[i] * (size_t)st->n1;
+        A[R] = st->A + 3 * r; B[R] = st->B + 3 * r;
+        N[R] = n; at[R] = i; sd[R] = seeds ? seeds[i] : p->seed;
+        R++;
+    }
+    return icp_enqueue_device_batch(c, R, A, B, N, p, sd, P, at);
+}
+
+extern "C" int chip_icp_ransac_matched_batch(chip_ctx *c, int32_t P, const int32_t *cand, const chip_ransac_params *p, const uint64_t *seeds,
+                                             double *T_colmajor, float *confidence, uint8_t *const *inlier_mask, chip_ransac_summary *summary,
+                                             int32_t *status)
+{
+    if (!T_colmajor || !confidence) return CHIP_ERR_INVALID_ARG;
+    const int rc = chip_icp_ransac_matched_batch_enqueue(c, P, cand, p, seeds, status);
+    if (rc != CHIP_OK) return rc;
+    return chip_icp_ransac_matched_batch_collect(c, T_colmajor, confidence, inlier_mask, summary);
 }
 
 // ------------------------------------------------------------------------------------------------ the frame store

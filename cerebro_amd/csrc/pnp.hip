@@ -2566,8 +2566,8 @@ extern "C" int chip_debug_ransac_record(chip_ctx *c, int32_t leg, int32_t proble
     if (!c || (leg != CHIP_RANSAC_LEG_PNP && leg != CHIP_RANSAC_LEG_ICP)) return CHIP_ERR_INVALID_ARG;
     if (c->group) c = static_cast<chip_ctx *>(chip::group_root(c));
     if (leg == CHIP_RANSAC_LEG_ICP) {
-        if (problem != 0 || nsol || sample) return CHIP_ERR_INVALID_ARG;
-        return icp_debug_record(c, shape, valid, cost, nin, T_colmajor, reinterpret_cast<unsigned long long *>(mask));
+        if (nsol || sample) return CHIP_ERR_INVALID_ARG;
+        return icp_debug_record(c, problem, shape, valid, cost, nin, T_colmajor, reinterpret_cast<unsigned long long *>(mask));
     }
     std::lock_guard<std::mutex> lk(c->pnp_mu);
     PnpState *st = nullptr;

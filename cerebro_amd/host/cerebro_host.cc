@@ -540,19 +540,24 @@ bool StaticPointFeatureMatching::make_3d_3d_collection__using__pfmatches_and_dis
 }
 
 // Everything after the match call of verify_candidates / verify_candidates_stored, on the B candidates the call left on the device
-// (sm: their summaries): the "< 150 matches" reject, ONE chip_pnp_ransac_matched_batch over the survivors, ICP per survivor, the gates.
+// (sm: their summaries): the "< 150 matches" reject, then for the survivors ONE matched ICP batch enqueued, ONE
+// chip_pnp_ransac_matched_batch underneath which it runs, the ICP collected, the gates.
 static bool verify_matched(chip_ctx *ctx, const chip_match_summary *sm, int B, ProcessedLoopCandidate *pc, bool *accepted, const uint64_t *seeds)
 {
     chip_ransac_params pp, pi;
     chip_ransac_params_default(&pp);
     chip_icp_params_default(&pi);
     const uint64_t pp_seed = pp.seed, pi_seed = pi.seed;
-    // the survivors of Cerebro.cpp:1487-1493, two PnP problems each (:1518 a->b, :1572 b->a) in one call
+    // the survivors of Cerebro.cpp:1487-1493, two PnP problems each (:1518 a->b, :1572 b->a) in one call and one ICP problem each (:1629)
     int32_t cand[2 * CHIP_MATCH_MAX_BATCH], which[2 * CHIP_MATCH_MAX_BATCH], status[2 * CHIP_MATCH_MAX_BATCH], slot[CHIP_MATCH_MAX_BATCH];
     uint64_t sd[2 * CHIP_MATCH_MAX_BATCH];
     double T[2 * CHIP_MATCH_MAX_BATCH * 16];
     float conf[2 * CHIP_MATCH_MAX_BATCH];
-    int P = 0;
+    int32_t icp_cand[CHIP_ICP_MAX_BATCH], icp_status[CHIP_ICP_MAX_BATCH];
+    uint64_t icp_sd[CHIP_ICP_MAX_BATCH];
+    double icp_T[CHIP_ICP_MAX_BATCH * 16];
+    float icp_conf[CHIP_ICP_MAX_BATCH];
+    int P = 0, Q = 0;
     for (int j = 0; j < B; j++) {
         slot[j] = -1;
         if (sm[j].n_matches_gms < 150) continue;
@@ -561,20 +566,22 @@ static bool verify_matched(chip_ctx *ctx, const chip_match_summary *sm, int B, P
         slot[j] = P;
         cand[P] = j; which[P] = CHIP_SET_AB; sd[P] = s0; P++;
         cand[P] = j; which[P] = CHIP_SET_BA; sd[P] = s0 + 1; P++;
+        icp_cand[Q] = j; icp_sd[Q] = seeds && seeds[j] ? seeds[j] ^ 0x9E3779B97F4A7C15ull : pi_seed; Q++;
     }
     if (P == 0) return true;
-    if (chip_pnp_ransac_matched_batch(ctx, P, cand, which, &pp, sd, T, conf, nullptr, nullptr, status) != CHIP_OK) return false;
+    if (chip_icp_ransac_matched_batch_enqueue(ctx, Q, icp_cand, &pi, icp_sd, icp_status) != CHIP_OK) return false;
+    const int pnp_rc = chip_pnp_ransac_matched_batch(ctx, P, cand, which, &pp, sd, T, conf, nullptr, nullptr, status);
+    const int icp_rc = chip_icp_ransac_matched_batch_collect(ctx, icp_T, icp_conf, nullptr, nullptr);   // collected whatever the PnP call said
+    if (pnp_rc != CHIP_OK || icp_rc != CHIP_OK) return false;
     for (int j = 0; j < B; j++) {
         if (slot[j] < 0) continue;
-        const int k = slot[j];
+        const int k = slot[j], q = k / 2;
         std::array<double, 16> op1{}, op2_a_T_b{}, op2{}, icp{};
         float g1 = -1.f, g2 = -1.f, g3 = -1.f;
         if (status[k] == CHIP_OK) { for (int i = 0; i < 16; i++) op1[i] = T[16 * k + i]; g1 = conf[k]; }
         if (status[k + 1] == CHIP_OK) { for (int i = 0; i < 16; i++) op2_a_T_b[i] = T[16 * (k + 1) + i]; g2 = conf[k + 1]; }
         matrix4_inverse_rigid(op2_a_T_b.data(), op2.data());        // :1582
-        pi.seed = seeds && seeds[j] ? seeds[j] ^ 0x9E3779B97F4A7C15ull : pi_seed;
-        if (chip_match_select(ctx, j) != CHIP_OK) return false;
-        if (chip_icp_ransac_matched(ctx, &pi, icp.data(), &g3, nullptr, nullptr) != CHIP_OK) g3 = -1.f;   // :1629
+        if (icp_status[q] == CHIP_OK) { for (int i = 0; i < 16; i++) icp[i] = icp_T[16 * q + i]; g3 = icp_conf[q]; }   // :1629
         bool nan = false;
         for (int i = 0; i < 16; i++)                                // :1678
             if (op1[i] != op1[i] || op2[i] != op2[i] || icp[i] != icp[i]) nan = true;

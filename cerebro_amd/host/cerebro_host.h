@@ -211,8 +211,11 @@ struct StaticPointFeatureMatching {
 bool verify_candidate(chip_ctx *ctx, const chip_match_frame &frame_a, const chip_match_frame &frame_b, const double Kinv[9],
                       ProcessedLoopCandidate &proc_candi, uint64_t seed = 0, chip_match_summary *summary = nullptr);
 // B candidates of one keyframe (B <= CHIP_MATCH_MAX_BATCH): ONE chip_match_batch (frame_a uploaded once, all pairs in three launches),
-// the "< 150 matches" reject per candidate, ONE chip_pnp_ransac_matched_batch over the survivors' a->b and b->a sets (seeds seeds[j],
-// seeds[j] + 1; nullptr: the default seed), then per survivor chip_match_select + chip_icp_ransac_matched and the NaN / goodness gate.
+// the "< 150 matches" reject per candidate, ONE matched ICP batch over the survivors enqueued (chip_icp_ransac_matched_batch_enqueue),
+// ONE chip_pnp_ransac_matched_batch over their a->b and b->a sets (seeds seeds[j], seeds[j] + 1; nullptr: the default seed) underneath
+// which the ICP runs, the ICP collected, and the NaN / goodness gate.  Which candidate is selected afterwards is unspecified.  The ICP
+// of the survivors is ONE call: if its enqueue or collect fails (a HIP or allocation error; too few points is a per-candidate status,
+// not a failure) the whole verification returns false, as it does for the PnP call.
 // pc[j] / accepted[j] are what verify_candidate(ctx, frame_a, frames_b[j], Kinv, pc[j], seeds[j]) gives, field for field.  Returns false
 // only if a library call failed (then every accepted[j] is false).
 bool verify_candidates(chip_ctx *ctx, const chip_match_frame &frame_a, const chip_match_frame *frames_b, int B, const double Kinv[9],

@@ -448,10 +448,25 @@ int chip_icp_ransac(chip_ctx *ctx, const double *A, const double *B, int32_t N, 
  * PNP(a->b), PNP(b->a) and P3P_ICP for one image pair (src/Cerebro.cpp:1518,1572,1629), and the ICP kernel is tiny:
  *   chip_icp_ransac_enqueue : copies A, B (the call returns once they are staged) and launches on the ctx's ICP stream;
  *   chip_icp_ransac_collect : waits for it and delivers exactly what chip_icp_ransac would have returned.
- * One estimation may be pending per ctx (a second enqueue, or a collect without enqueue: CHIP_ERR_BUSY).                 */
+ * One estimation may be pending per ctx, single or batch (chip_icp_ransac_matched_batch_enqueue below): any ICP enqueue or
+ * blocking ICP call while one is pending, a collect without an enqueue, and chip_icp_ransac_collect on a pending batch return
+ * CHIP_ERR_BUSY.                                                                                                          */
 int chip_icp_ransac_enqueue(chip_ctx *ctx, const double *A, const double *B, int32_t N, const chip_ransac_params *p);
 int chip_icp_ransac_collect(chip_ctx *ctx, double T_colmajor[16], float *confidence, uint8_t *inlier_mask /* may be NULL */,
                             chip_ransac_summary *summary /* may be NULL */);
+
+/* P independent estimations in ONE pair of launches (ABI 7, additive): the twin of chip_pnp_ransac_batch.  icp_models_batch runs on a
+ * grid of ceil(H / 64) x P, icp_score_batch on H x P; what differs per problem (A, B, N, the seed, the sampler's multipliers) comes
+ * from a table the ctx owns, copied to device memory in-stream and read through uniform loads (P = 1 launches the single pair).  All problems share *p; problem i draws from seeds[i] (NULL: p->seed for every problem)
+ * and its outputs (T_colmajor + 16 i, confidence[i], inlier_mask[i] (N[i] bytes; the array or any entry may be NULL), summary[i])
+ * are bit-identical to chip_icp_ransac(A[i], B[i], N[i]) with that seed, whatever P and whoever its neighbours are.  chip_icp_ransac
+ * is this call with P = 1.  Any N[i] < 20 fails the whole call with CHIP_ERR_TOO_FEW_POINTS before anything runs; P < 1 or a NULL
+ * pointer: CHIP_ERR_INVALID_ARG; P > CHIP_ICP_MAX_BATCH: CHIP_ERR_UNSUPPORTED.  Group ctxs: devices[0].                          */
+#define CHIP_ICP_MAX_BATCH 16              /* = CHIP_MATCH_MAX_BATCH */
+int chip_build_has_icp_batch(void);        /* 1 */
+int chip_icp_ransac_batch(chip_ctx *ctx, int32_t P, const double *const *A, const double *const *B, const int32_t *N,
+                          const chip_ransac_params *p, const uint64_t *seeds, double *T_colmajor /* P x 16 */,
+                          float *confidence /* P */, uint8_t *const *inlier_mask, chip_ransac_summary *summary /* P or NULL */);
 
 /* Test aids (ABI 7, additive): the record of EVERY hypothesis of the most recent estimation of a ctx, not only of its winner.
  * Both kernel pairs leave valid / cost / inlier count / pose / inlier mask per hypothesis (and the selection rule is replayed over
@@ -460,7 +475,8 @@ int chip_icp_ransac_collect(chip_ctx *ctx, double T_colmajor[16], float *confide
  *   chip_debug_ransac_record  leg CHIP_RANSAC_LEG_PNP: problem `problem` of the last LAUNCH of chip_pnp_ransac / _batch / _matched
  *                             (a batch of more than 8 problems runs as several launches of up to 8; the record is that of the last
  *                             launch, its problems numbered from 0); leg CHIP_RANSAC_LEG_ICP: the last collected chip_icp_ransac /
- *                             _collect / _matched (problem 0).  *shape first (it sizes the arrays), then any of
+ *                             _collect / _matched (problem 0 of 1) or problem `problem` of the last collected chip_icp_ransac_batch /
+ *                             _matched_batch (of a matched batch: the problems that RAN, numbered from 0).  *shape first (it sizes the arrays), then any of
  *                               valid[H], cost[H], nin[H], T[H][16] column-major, mask[H][words] (bit i & 63 of word i >> 6 = point i),
  *                               PnP only: nsol[H] (cheirality-valid solutions; -1 singular system, -2 eigenvalue iteration gave up),
  *                                         sample[H][S] (the sampler's indices as pnp_build_solve used them).
@@ -604,10 +620,31 @@ int chip_match_batch_read_matches(chip_ctx *ctx, int32_t j, int32_t *train_idx, 
  * chip_match_select(cand[i]).  A set with fewer than 20 points gets CHIP_ERR_TOO_FEW_POINTS and is left out of the launch.
  * Its T is NaN, its confidence -1, its summary zero with best_hypothesis -1, and its mask is untouched.  The other problems
  * are bit-identical to the single call with that seed.  The call itself fails only on bad arguments or a HIP / allocation
- * error.  The selection is not changed.  ICP stays one candidate at a time: chip_match_select, then chip_icp_ransac_matched. */
+ * error.  The selection is not changed.                                                                                   */
 int chip_pnp_ransac_matched_batch(chip_ctx *ctx, int32_t P, const int32_t *cand, const int32_t *which,
                                   const chip_ransac_params *p, const uint64_t *seeds, double *T_colmajor /* P x 16 */,
                                   float *confidence /* P */, uint8_t *const *inlier_mask /* may be NULL */,
+                                  chip_ransac_summary *summary /* P or NULL */, int32_t *status /* P */);
+/* P ICP estimations on the device-resident 3-D / 3-D sets (A_3d3d, B_3d3d, n_3d3d) of candidates cand[i] of the last match call, read
+ * in place, in ONE pair of launches on the ctx's ICP stream -- split into enqueue and collect so that they run underneath the PnP call
+ * of the same candidates (nothing in them depends on it):
+ *   _enqueue : status[i] is what chip_icp_ransac_matched would return after chip_match_select(cand[i]); a set with fewer than 20
+ *              points gets CHIP_ERR_TOO_FEW_POINTS and is left out of the launch.  Problem i draws from seeds[i] (NULL: p->seed).
+ *              cand may repeat and be in any order.  Returns without waiting.  With no runnable problem it still succeeds.
+ *   _collect : waits and delivers the P answers.  A problem that ran is bit-identical to the single call with that seed; a left-out
+ *              one has T = NaN, confidence -1, a zero summary with best_hypothesis -1 and an untouched mask.
+ *   chip_icp_ransac_matched_batch = enqueue + collect.
+ * The selection is not changed.  Status: before any match CHIP_ERR_BUSY; cand[i] outside the batch CHIP_ERR_RANGE; a group ctx or
+ * P > CHIP_ICP_MAX_BATCH CHIP_ERR_UNSUPPORTED; P < 1 or a NULL pointer CHIP_ERR_INVALID_ARG; an ICP estimation already pending, or a
+ * collect without a batch enqueue, CHIP_ERR_BUSY.  The sets outlive the kernels: chip_match_pair, chip_match_batch and
+ * chip_match_batch_stored wait for the ICP stream first when a matched batch is pending; they still succeed and the batch stays
+ * collectable (its results are in pinned memory by then).                                                                         */
+int chip_icp_ransac_matched_batch_enqueue(chip_ctx *ctx, int32_t P, const int32_t *cand, const chip_ransac_params *p,
+                                          const uint64_t *seeds, int32_t *status /* P */);
+int chip_icp_ransac_matched_batch_collect(chip_ctx *ctx, double *T_colmajor /* P x 16 */, float *confidence /* P */,
+                                          uint8_t *const *inlier_mask /* may be NULL */, chip_ransac_summary *summary /* P or NULL */);
+int chip_icp_ransac_matched_batch(chip_ctx *ctx, int32_t P, const int32_t *cand, const chip_ransac_params *p, const uint64_t *seeds,
+                                  double *T_colmajor /* P x 16 */, float *confidence /* P */, uint8_t *const *inlier_mask /* may be NULL */,
                                   chip_ransac_summary *summary /* P or NULL */, int32_t *status /* P */);
 
 /* ---- frames kept on the device: the match stage without uploads.  chip_match_batch spends most of its time copying 3-D images of
@@ -647,8 +684,8 @@ int chip_pnp_ransac_matched_batch(chip_ctx *ctx, int32_t P, const int32_t *cand,
  *     chip_match_batch_read_matches(j) are byte for byte what chip_match_batch gives on the host frames that were put under those
  *     ids (pose_sets_stored_batch is pose_sets_batch with the records in place of the images; the other two kernels run as they
  *     are, on pointers into the store).  Afterwards candidate 0 is selected and chip_match_batch_read_matches answers;
- *     chip_match_select, chip_match_read_sets, chip_pnp_ransac_matched, chip_icp_ransac_matched and chip_pnp_ransac_matched_batch
- *     work on the result unchanged;
+ *     chip_match_select, chip_match_read_sets, chip_pnp_ransac_matched, chip_icp_ransac_matched, chip_pnp_ransac_matched_batch
+ *     and chip_icp_ransac_matched_batch work on the result unchanged;
  *   - cost: no host-to-device copy of frame data; three launches and the B x 5 counts back.
  * Not on chip_create_multi ctxs (CHIP_ERR_UNSUPPORTED).  These calls belong to the one matching thread of the ctx and use the ctx
  * stream: a put is ordered before a later match.                                                                                   */

@@ -192,6 +192,8 @@ _SIGS = {
     "chip_scan_local": (C.c_int, [_P, C.c_int64, C.POINTER(DotParams), C.c_int32, _P, C.POINTER(C.c_int32)]),
     "chip_merge_decide": (C.c_int, [_P, C.c_int64, C.POINTER(DotParams), _P, C.c_int32, C.c_int32, C.POINTER(TickResult)]),
     "chip_merge_decide_enqueue": (C.c_int, [_P, C.c_int64, C.POINTER(DotParams), _P, C.c_int32, C.c_int32, C.c_int32]),
+    "chip_debug_merge_lists": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, C.POINTER(DotParams),
+                                         C.POINTER(TickResult)]),
     "chip_ransac_params_default": (None, [C.POINTER(RansacParams)]),
     "chip_pnp_ransac": (C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(RansacParams), _P, C.POINTER(C.c_float), _P,
                                   C.POINTER(RansacSummary)]),
@@ -606,6 +608,24 @@ class Chip:
         p = params or default_dot_params()
         self._chk(self.lib.chip_merge_decide_enqueue(self.h, l, C.byref(p), C.c_void_p(dev_gathered_ptr), n_lists, topk, slot),
                   "chip_merge_decide_enqueue")
+
+    def debug_merge_lists(self, form: int, scores: np.ndarray, idx: np.ndarray, l: int = 0, params: DotParams | None = None,
+                          record: bool = False):
+        """chip_debug_merge_lists: scores float64 / idx int64 [n_lists, nq, K] through topk_merge<nq> (form 0) or topk_merge_batch
+        (form 1) -> (scores [nq, K], idx [nq, K], TickResult or None), as the kernel wrote them (idx[0, 0] == -2: a failed list)."""
+        scores = np.ascontiguousarray(scores, dtype=np.float64)
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        assert scores.ndim == 3 and scores.shape == idx.shape
+        n_lists, nq, K = scores.shape
+        lists = np.empty((n_lists, nq, K, 2), dtype=np.float64)
+        lists[..., 0] = scores
+        lists[..., 1] = idx.view(np.float64)
+        out = np.empty((nq, K, 2), dtype=np.float64)
+        r = TickResult() if record else None
+        p = params or default_dot_params()
+        self._chk(self.lib.chip_debug_merge_lists(self.h, form, _ptr(lists), n_lists, nq, K, _ptr(out), l, C.byref(p),
+                                                  C.byref(r) if record else None), "chip_debug_merge_lists")
+        return out[..., 0].copy(), out[..., 1].copy().view(np.int64), r
 
     # -- PnP
     def pnp_ransac(self, X: np.ndarray, uv: np.ndarray, params: RansacParams | None = None):

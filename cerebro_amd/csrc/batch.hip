@@ -477,6 +477,9 @@ struct BatchState {
     PinnedBuf<chip_topk_entry> h_out;
     // sharded DBs (chip_multi.hip): every shard's [Qpad][K] list side by side, and the merged result of the whole DB
     DevBuf<chip_topk_entry> gathered, merged;
+    // chip_debug_merge_lists: the caller's lists, the merged lists, the record
+    DevBuf<chip_topk_entry> dbg_in, dbg_out;
+    DevBuf<chip_tick_result> dbg_rec;
     hipEvent_t ev_done = nullptr;     // this shard's list is complete (recorded on its scan stream)
 };
 
@@ -620,6 +623,40 @@ int batch_merge_lists(Ctx *c, hipStream_t s, const chip_topk_entry *in, int n_li
     m.in = in; m.n_lists = n_lists; m.Qpad = Qpad; m.K = topk; m.out = out;
     hipLaunchKernelGGL(topk_merge_batch, dim3((Q + 3) / 4), dim3(512), 0, s, m);
     CHIP_HIP(c, hipGetLastError());
+    return CHIP_OK;
+}
+
+// chip_debug_merge_lists: host lists [n_lists][nq][K] through the merge kernel of `form` exactly as the product paths launch it (launch_merge
+// for topk_merge<nq>, batch_merge_lists for topk_merge_batch with Qpad = Q = nq), result to the host.  Caller: arguments checked, query lock
+// held, device current.  `out` and the record are filled with a byte pattern first, so that an entry the kernel does not write is no entry at all.
+int debug_merge_lists(Ctx *c, int form, const chip_topk_entry *lists, int32_t n_lists, int32_t nq, int32_t K, chip_topk_entry *out, int64_t l,
+                      const chip_dot_params *p, chip_tick_result *result)
+{
+    if (!c->batch_state) {
+        c->batch_state = new (std::nothrow) BatchState();
+        if (!c->batch_state) return CHIP_ERR_OOM;
+    }
+    BatchState *st = c->batch_state;
+    const size_t n_in = (size_t)n_lists * nq * K, n_out = (size_t)nq * K;
+    {
+        // one pause over the group: hipFree waits for the whole device, no resident scan instance on it until the last allocation is done
+        ResidentPause paused(c, n_in > st->dbg_in.capacity() || n_out > st->dbg_out.capacity() || !st->dbg_rec.capacity());
+        int rc = st->dbg_in.reserve(c, n_in);
+        if (rc == CHIP_OK) rc = st->dbg_out.reserve(c, n_out);
+        if (rc == CHIP_OK) rc = st->dbg_rec.reserve(c, 1);
+        if (rc != CHIP_OK) return rc;
+    }
+    hipStream_t s = c->s_query;
+    CHIP_HIP(c, hipMemcpyAsync(st->dbg_in, lists, sizeof(chip_topk_entry) * n_in, hipMemcpyHostToDevice, s));
+    CHIP_HIP(c, hipMemsetAsync(st->dbg_out, 0xA5, sizeof(chip_topk_entry) * n_out, s));
+    CHIP_HIP(c, hipMemsetAsync(st->dbg_rec, 0xA5, sizeof(chip_tick_result), s));
+    int rc;
+    if (form == 0) rc = launch_merge(c, s, merge_args(st->dbg_in, n_lists, K, st->dbg_out, result ? st->dbg_rec.get() : nullptr, l, p), nq);
+    else rc = batch_merge_lists(c, s, st->dbg_in, n_lists, nq, nq, K, st->dbg_out);
+    if (rc != CHIP_OK) return rc;
+    CHIP_HIP(c, hipMemcpyAsync(out, st->dbg_out, sizeof(chip_topk_entry) * n_out, hipMemcpyDeviceToHost, s));
+    if (result) CHIP_HIP(c, hipMemcpyAsync(result, st->dbg_rec, sizeof(chip_tick_result), hipMemcpyDeviceToHost, s));
+    CHIP_HIP(c, hipStreamSynchronize(s));
     return CHIP_OK;
 }
 

@@ -1397,6 +1397,22 @@ int chip_merge_decide_enqueue(chip_ctx *c, int64_t l, const chip_dot_params *p, 
     return merge_enqueue_slot(c, l, p, dev_gathered, n_lists, topk, c->slots[slot]);
 }
 
+// The two list-merge kernels alone, on the caller's lists (test aid; batch.hip debug_merge_lists).
+int chip_debug_merge_lists(chip_ctx *c, int32_t form, const chip_topk_entry *lists, int32_t n_lists, int32_t nq, int32_t K, chip_topk_entry *out,
+                           int64_t l, const chip_dot_params *p, chip_tick_result *result)
+{
+    if (!c || !lists || !out || n_lists < 1 || (result && !p)) return CHIP_ERR_INVALID_ARG;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    if (K < 1 || K > CHIP_MAX_TOPK || n_lists > 512) return CHIP_ERR_UNSUPPORTED;
+    const bool form_ok = form == 0 ? nq >= 1 && nq <= CHIP_MAX_NQ                          // topk_merge<nq>
+                                   : form == 1 && nq >= 4 && nq % 4 == 0 && nq <= 4096 && !result;   // topk_merge_batch: four queries per workgroup, no record
+    if (!form_ok) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> qlk(c->query_mu);
+    CHIP_HIP(c, hipSetDevice(c->device));
+    (void)coalesce_flush(c);
+    return debug_merge_lists(c, form, lists, n_lists, nq, K, out, l, p, result);
+}
+
 // ------------------------------------------------------------------------------------------------ introspection
 int chip_get_info(const chip_ctx *c, chip_info *info)
 {

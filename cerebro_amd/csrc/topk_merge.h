@@ -15,10 +15,14 @@ __device__ __forceinline__ bool key_gt(double s, int64_t i, double s2, int64_t i
 // accept rule of Cerebro.cpp:1056.  Selection instead of K serial block-wide argmax rounds:
 //   1. thread t loads the HEAD of list t;                       2. every wave ranks its 64 heads (v_readlane loops)
 //   and posts its K best to LDS;  3. one wave per query ranks those <= 8K heads: T1 = K-th best head overall.
-//   Every global top-K entry is >= T1 (K heads already are), and only the K lists whose head >= T1 can contribute,
-//   each at most K entries => at most K*K <= 256 survivors;     4. survivors are appended to an LDS list (LDS atomic
-//   cursor) and ranked by one wave per query; rank r < K is written to out[r].  Keys (score desc, idx desc) are
-//   unique for valid entries (indices are), so ranks are a permutation and the result is partition independent.
+//   Every global top-K entry is >= T1 (K heads already are), and only the K lists whose head >= T1 can contribute:
+//   the list whose head IS T1 that head alone (keys are unique), the other K-1 at most K entries each => at most
+//   K(K-1)+1 <= 241 survivors.  kSurvCap = 256 is the size of the LDS list; the clamps against it are a guard only, no
+//   input that keeps the contract (sorted lists, indices unique per query, no NaN) reaches them;
+//   4. survivors are appended to an LDS list (LDS atomic cursor) and ranked by one wave per query; rank r < K is
+//   written to out[r].  Keys (score desc, idx desc) are unique for valid entries (indices are), so ranks are a
+//   permutation and the result is partition independent.
+//   tests/test_merge_gpu.py runs both kernels on crafted list sets (tests/merge_cases.py) through chip_debug_merge_lists.
 // `in` is [n_lists][list_stride queries][K]; this workgroup merges queries q_off .. q_off+NQ-1 into out[0..NQ)[K].
 // smem: kMergeSmem bytes.
 constexpr int kMergeSmem = 28 * 1024;
@@ -181,7 +185,7 @@ __device__ __forceinline__ void merge_sorted_lists(const chip_topk_entry *in, in
     if (w < NQ) {
         const int q = w;
         int n = cnt[q];
-        if (n > kSurvCap) n = kSurvCap;  // cannot happen (<= K*K), keeps the loops bounded
+        if (n > kSurvCap) n = kSurvCap;  // cannot happen (<= K(K-1)+1), keeps the loops bounded
         double cs[4];
         int64_t ci[4];
         int rk[4];

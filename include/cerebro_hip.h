@@ -376,6 +376,19 @@ int chip_merge_decide(chip_ctx *ctx, int64_t l, const chip_dot_params *p, const 
                       int32_t topk, chip_tick_result *out);
 int chip_merge_decide_enqueue(chip_ctx *ctx, int64_t l, const chip_dot_params *p, const void *dev_gathered, int32_t n_lists,
                               int32_t topk, int32_t slot);
+/* Test aid (ABI 7, additive): the list merge alone, on lists the caller writes.  Every scan result leaves through one of two kernels;
+ * this call copies `lists` (host, [n_lists][nq][K]: each list sorted by (score descending, index descending), indices unique per query,
+ * no NaN, unused slots (-inf, -1), a failed shard's list (-inf, -2) in every entry) to device memory, launches
+ *   form 0: topk_merge<nq>, nq = 1 .. CHIP_MAX_NQ, through the launch helper of the tick, the query and the exchange paths; with `result`
+ *           non-NULL the kernel also writes the decision record of tick l under p (as chip_merge_decide does; p must be given then);
+ *   form 1: topk_merge_batch, the merge of the many-query mode, nq a multiple of 4: one workgroup per four queries, list stride nq;
+ *           no record (result must be NULL),
+ * waits, and copies the merged [nq][K] lists to `out` (host) as the kernel wrote them: a failed list's mark is out[0].idx == -2 (form 1:
+ * in the first entry of each workgroup's four queries).
+ * tests/test_merge_gpu.py runs tests/merge_cases.py through it.  Synchronous, takes the query lock.  CHIP_ERR_UNSUPPORTED: group ctx,
+ * K outside 1 .. CHIP_MAX_TOPK, n_lists > 512, an nq or a form that does not exist; CHIP_ERR_INVALID_ARG: NULL pointers, n_lists < 1. */
+int chip_debug_merge_lists(chip_ctx *ctx, int32_t form, const chip_topk_entry *lists, int32_t n_lists, int32_t nq, int32_t K,
+                           chip_topk_entry *out, int64_t l, const chip_dot_params *p, chip_tick_result *result);
 
 /* ------------------------------------------------------------------------------------------ PnP-RANSAC
  * Replaces the body of StaticTheiaPoseCompute::PNP (src/DlsPnpWithRansac.cpp:192-240): theia::Ransac over

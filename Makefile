@@ -1,6 +1,6 @@
 # Build of the MI355X loop-detection core (gfx950 only) and of the CPU oracle (test infrastructure).
 #   make            -> cerebro_amd/lib/libcerebro_hip.so  + oracle/_build/liboracle.so  (+ oracle/_ref/libgms_ref.so, see `ref`)
-#   make lib / make oracle / make ref / make clean
+#   make lib / make oracle / make ref / make ref_modes / make clean
 ROCM       ?= /opt/rocm
 HIPCC      ?= $(ROCM)/bin/hipcc
 ARCH       ?= gfx950
@@ -17,10 +17,10 @@ HIP_SRCS   := $(CSRC)/kernels.hip $(CSRC)/chip_api.hip $(CSRC)/resident.hip $(CS
 HIP_OBJS   := $(HIP_SRCS:$(CSRC)/%.hip=$(LIBDIR)/%.o)
 ORC_SRCS   := $(wildcard oracle/*.c)
 
-all: lib oracle host testlibs verify ref
+all: lib oracle host testlibs verify ref ref_modes
 lib: $(LIBDIR)/libcerebro_hip.so
 oracle: oracle/_build/liboracle.so oracle/_build/liboracle_eispack.so oracle/_build/liboracle_stats.so oracle/_build/liboracle_flops.so
-host: $(LIBDIR)/libcerebro_host.so $(LIBDIR)/cerebro_replay $(LIBDIR)/minimal_loop_detector $(LIBDIR)/sync_tick_latency $(LIBDIR)/verify_candidate $(LIBDIR)/verify_candidates $(LIBDIR)/verify_candidates_stored $(LIBDIR)/verify_candidates_composed
+host: $(LIBDIR)/libcerebro_host.so $(LIBDIR)/cerebro_replay $(LIBDIR)/minimal_loop_detector $(LIBDIR)/sync_tick_latency $(LIBDIR)/verify_candidate $(LIBDIR)/verify_candidates $(LIBDIR)/verify_candidates_stored $(LIBDIR)/verify_candidates_composed $(LIBDIR)/verify_candidates_modes
 # test infrastructure that needs hipcc: the shared-memory stand-in for librccl (N ranks on one device, tests/test_fakerccl_gpu.py)
 testlibs: tests/fakerccl/_build/libfakerccl.so $(LIBDIR)/norows/libcerebro_hip.so $(LIBDIR)/hooks/libcerebro_hip.so
 # The TEST build of the library (-DCHIP_TEST_HOOKS): the fault-injection hooks (CHIP_TEST_COMM_INIT, CHIP_TEST_FAIL_SHARD,
@@ -115,6 +115,10 @@ $(LIBDIR)/verify_candidates_stored: examples/verify_candidates_stored.cc $(LIBDI
 $(LIBDIR)/verify_candidates_composed: examples/verify_candidates_composed.cc $(LIBDIR)/libcerebro_host.so
 	$(CXX) -O2 -std=c++17 -Wall -Wextra examples/verify_candidates_composed.cc -o $@ -L$(LIBDIR) -lcerebro_host -lcerebro_hip -Wl,-rpath,'$$ORIGIN' -lpthread
 
+# ---- the stored path with GMS scale / rotation (gms_modes = 3) against the same call with 0, on candidates that include a rolled one
+$(LIBDIR)/verify_candidates_modes: examples/verify_candidates_modes.cc $(LIBDIR)/libcerebro_host.so
+	$(CXX) -O2 -std=c++17 -Wall -Wextra examples/verify_candidates_modes.cc -o $@ -L$(LIBDIR) -lcerebro_host -lcerebro_hip -Wl,-rpath,'$$ORIGIN' -lpthread
+
 # ---- the reference's own GMS matcher as a compiled checker (test infrastructure: tests/gms_ref_lib.py, tests/test_gms_ref_mirror.py).
 # gms_matcher.{h,cpp} are compiled BY PATH from the reference tree against the stand-in oracle/ref_gms/opencv2/opencv.hpp; nothing of
 # them is in this repository and oracle/_ref/ is git-ignored.  Plain IEEE arithmetic: no contraction, no fast-math, no -march.
@@ -128,12 +132,20 @@ ref: oracle/_ref/libgms_ref.so
 oracle/_ref/libgms_ref.so: oracle/ref_gms/gms_ref.cc oracle/ref_gms/opencv2/opencv.hpp $(REF_GMS)/gms_matcher.cpp $(REF_GMS)/gms_matcher.h
 	@mkdir -p oracle/_ref
 	$(CXX) $(REFFLAGS) -shared -Ioracle/ref_gms -I$(REF_GMS) oracle/ref_gms/gms_ref.cc $(REF_GMS)/gms_matcher.cpp -o $@
+# the same matcher with its scale / rotation variants (tests/gms_modes_ref_lib.py, tests/test_gms_modes_mirror.py): this project's own
+# wrapper tests/ref_gms_modes/gms_ref_modes.cc, the same two reference files by path, the same stand-in header
+ref_modes: oracle/_ref/libgms_ref_modes.so
+oracle/_ref/libgms_ref_modes.so: tests/ref_gms_modes/gms_ref_modes.cc oracle/ref_gms/opencv2/opencv.hpp $(REF_GMS)/gms_matcher.cpp $(REF_GMS)/gms_matcher.h
+	@mkdir -p oracle/_ref
+	$(CXX) $(REFFLAGS) -shared -Ioracle/ref_gms -I$(REF_GMS) tests/ref_gms_modes/gms_ref_modes.cc $(REF_GMS)/gms_matcher.cpp -o $@
 else
 ref:
 	@echo "make ref: no reference tree at $(REFERENCE): nothing to build"
+ref_modes:
+	@echo "make ref_modes: no reference tree at $(REFERENCE): nothing to build"
 endif
 
 clean:
 	rm -rf $(LIBDIR) oracle/_build tests/fakerccl/_build
 
-.PHONY: all lib oracle host testlibs verify ref clean
+.PHONY: all lib oracle host testlibs verify ref ref_modes clean

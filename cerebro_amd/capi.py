@@ -120,6 +120,18 @@ class MatchSummary(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+CHIP_GMS_WITH_SCALE, CHIP_GMS_WITH_ROTATION = 1, 2
+
+
+class GmsChoice(C.Structure):
+    """chip_gms_choice: which (scale index, rotation type) GMS with scale / rotation kept, and the inlier count of every hypothesis"""
+    _fields_ = [("scale", C.c_int32), ("rotation", C.c_int32), ("n_inliers", C.c_int32), ("counts", (C.c_int32 * 8) * 5)]
+
+    def as_dict(self):
+        return dict(scale=self.scale, rotation=self.rotation, n_inliers=self.n_inliers,
+                    counts=np.array([list(row) for row in self.counts], dtype=np.int32))
+
+
 class MatchSetsOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("uv", "uv_d", "X_ab", "uvn_ab", "X_ba", "uvn_ba", "A_3d3d", "B_3d3d",
                                           "match_query_idx", "match_train_idx")]
@@ -225,6 +237,12 @@ _SIGS = {
     "chip_match_read_sets": (C.c_int, [_P, C.POINTER(MatchSetsOut)]),
     "chip_pnp_ransac_matched": (C.c_int, [_P, C.c_int32, C.POINTER(RansacParams), _P, C.POINTER(C.c_float), _P, C.POINTER(RansacSummary)]),
     "chip_icp_ransac_matched": (C.c_int, [_P, C.POINTER(RansacParams), _P, C.POINTER(C.c_float), _P, C.POINTER(RansacSummary)]),
+    "chip_build_has_gms_modes": (C.c_int, []),
+    "chip_gms_filter_modes": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32,
+                                        C.c_uint32, _P, C.POINTER(C.c_int32), C.POINTER(GmsChoice)]),
+    "chip_match_batch_modes": (C.c_int, [_P, C.POINTER(MatchFrame), C.POINTER(MatchFrame), C.c_int32, _P, C.c_uint32, C.POINTER(MatchSummary),
+                                         C.POINTER(GmsChoice)]),
+    "chip_match_batch_stored_modes": (C.c_int, [_P, C.c_int64, _P, C.c_int32, _P, C.c_uint32, C.POINTER(MatchSummary), C.POINTER(GmsChoice)]),
     "chip_build_has_match_batch": (C.c_int, []),
     "chip_match_batch": (C.c_int, [_P, C.POINTER(MatchFrame), C.POINTER(MatchFrame), C.c_int32, _P, C.POINTER(MatchSummary)]),
     "chip_match_select": (C.c_int, [_P, C.c_int32]),
@@ -774,8 +792,9 @@ class Chip:
         self._chk(self.lib.chip_orb_match(self.h, _ptr(d1), n1, _ptr(d2), n2, _ptr(idx), _ptr(dist)), "chip_orb_match")
         return idx[:n1].copy(), dist[:n1].copy()
 
-    def gms_filter(self, kp1: np.ndarray, size1, kp2: np.ndarray, size2, query_idx, train_idx) -> np.ndarray:
-        """size = (width, height) -> uint8 inlier mask in match order"""
+    def gms_filter(self, kp1: np.ndarray, size1, kp2: np.ndarray, size2, query_idx, train_idx, modes=None):
+        """size = (width, height) -> uint8 inlier mask in match order.  modes (CHIP_GMS_WITH_SCALE | CHIP_GMS_WITH_ROTATION, or 0):
+        chip_gms_filter_modes -> (mask, choice dict(scale, rotation, n_inliers, counts (5, 8)))"""
         kp1 = np.ascontiguousarray(kp1, dtype=np.float32).reshape(-1, 2)
         kp2 = np.ascontiguousarray(kp2, dtype=np.float32).reshape(-1, 2)
         q = np.ascontiguousarray(query_idx, dtype=np.int32)
@@ -784,6 +803,13 @@ class Chip:
         n = q.shape[0]
         mask = np.zeros(max(n, 1), dtype=np.uint8)
         cnt = C.c_int32()
+        if modes is not None:
+            ch = GmsChoice()
+            self._chk(self.lib.chip_gms_filter_modes(self.h, _ptr(kp1), kp1.shape[0], size1[0], size1[1], _ptr(kp2), kp2.shape[0], size2[0],
+                                                     size2[1], _ptr(q), _ptr(t), n, modes, _ptr(mask), C.byref(cnt), C.byref(ch)),
+                      "chip_gms_filter_modes")
+            assert cnt.value == int(mask[:n].sum()) == ch.n_inliers
+            return mask[:n].copy(), ch.as_dict()
         self._chk(self.lib.chip_gms_filter(self.h, _ptr(kp1), kp1.shape[0], size1[0], size1[1], _ptr(kp2), kp2.shape[0], size2[0], size2[1],
                                            _ptr(q), _ptr(t), n, _ptr(mask), C.byref(cnt)), "chip_gms_filter")
         assert cnt.value == int(mask[:n].sum())
@@ -849,15 +875,21 @@ class Chip:
         return self._matched(st, "chip_icp_ransac_matched", N, T, conf, mask, summ)
 
     # -- one query frame against several candidate frames
-    def match_batch(self, frame_a: dict, frames_b, Kinv: np.ndarray) -> list:
+    def match_batch(self, frame_a: dict, frames_b, Kinv: np.ndarray, modes=None):
         """chip_match_batch: frame_a against every frame of frames_b (at most CHIP_MATCH_MAX_BATCH) -> the list of MatchSummary, one
-        per candidate.  The sets of all candidates stay on the device; candidate 0 is selected (match_select)."""
+        per candidate.  The sets of all candidates stay on the device; candidate 0 is selected (match_select).
+        modes (CHIP_GMS_WITH_SCALE | CHIP_GMS_WITH_ROTATION, or 0): chip_match_batch_modes -> (summaries, list of choice dicts)"""
         fa, keep_a = self._match_frame(frame_a)
         made = [self._match_frame(f) for f in frames_b]
         B = len(made)
         fb = (MatchFrame * max(B, 1))(*[m[0] for m in made])
         Ki = np.ascontiguousarray(Kinv, dtype=np.float64).reshape(9)
         sm = (MatchSummary * max(B, 1))()
+        if modes is not None:
+            ch = (GmsChoice * max(B, 1))()
+            self._chk(self.lib.chip_match_batch_modes(self.h, C.byref(fa), fb, B, _ptr(Ki), modes, sm, ch), "chip_match_batch_modes")
+            self._match_batch_n1 = fa.n
+            return [MatchSummary.from_buffer_copy(sm[j]) for j in range(B)], [ch[j].as_dict() for j in range(B)]
         self._chk(self.lib.chip_match_batch(self.h, C.byref(fa), fb, B, _ptr(Ki), sm), "chip_match_batch")
         self._match_batch_n1 = fa.n
         return [MatchSummary.from_buffer_copy(sm[j]) for j in range(B)]
@@ -981,20 +1013,26 @@ class Chip:
             self._chk(self.lib.chip_frame_read(self.h, id, None, None, None, _ptr(desc), _ptr(kp), _ptr(pts)), "chip_frame_read")
         return dict(n=n, width=v[1].value, height=v[2].value, desc=desc, kp=kp, pts=pts)
 
-    def match_batch_stored(self, a_id: int, b_ids, Kinv: np.ndarray) -> list:
+    def match_batch_stored(self, a_id: int, b_ids, Kinv: np.ndarray, modes=None):
         """chip_match_batch_stored: the stored frame a_id against the stored frames b_ids, nothing uploaded -> what match_batch returns
         on the host frames that were put under those ids; match_select / match_read_sets / match_batch_matches and the _matched
-        solvers work on the result."""
+        solvers work on the result.  modes (or 0): chip_match_batch_stored_modes -> (summaries, list of choice dicts)"""
         ids = np.ascontiguousarray(b_ids, dtype=np.int64).reshape(-1)
         B = len(ids)
         Ki = np.ascontiguousarray(Kinv, dtype=np.float64).reshape(9)
         sm = (MatchSummary * max(B, 1))()
         self._match_batch_n1 = 0
-        self._chk(self.lib.chip_match_batch_stored(self.h, a_id, _ptr(ids) if B else None, B, _ptr(Ki), sm), "chip_match_batch_stored")
+        ch = (GmsChoice * max(B, 1))()
+        if modes is not None:
+            self._chk(self.lib.chip_match_batch_stored_modes(self.h, a_id, _ptr(ids) if B else None, B, _ptr(Ki), modes, sm, ch),
+                      "chip_match_batch_stored_modes")
+        else:
+            self._chk(self.lib.chip_match_batch_stored(self.h, a_id, _ptr(ids) if B else None, B, _ptr(Ki), sm), "chip_match_batch_stored")
         n1 = C.c_int32()
         self._chk(self.lib.chip_frame_read(self.h, a_id, C.byref(n1), None, None, None, None, None), "chip_frame_read")
         self._match_batch_n1 = n1.value
-        return [MatchSummary.from_buffer_copy(sm[j]) for j in range(B)]
+        summaries = [MatchSummary.from_buffer_copy(sm[j]) for j in range(B)]
+        return (summaries, [ch[j].as_dict() for j in range(B)]) if modes is not None else summaries
 
     # -- introspection / profiling
     def info(self) -> dict:

@@ -12,6 +12,10 @@
 //                     VerifyCellPairs (:100-148, rotation pattern 1 = identity) with one wave per table row for the first-maximum
 //                     search and one lane per left cell for the 3 x 3 score against 6 * sqrt(mean count), then the inlier marks (:169-177).
 //   gms_batch       : the same pass (gms_pass) with one workgroup per (grid type, candidate), on the matcher's keys.
+//   gms_grid_modes  : GetInlierMask(.., WithScale, WithRotation) (gms_matcher.cpp:17-68), the optional form (modes != 0): one workgroup per
+//                     (scale, grid type, candidate) builds table and column search once and scores the 400 x 8 (left cell, rotation) items;
+//   gms_mode_select : one workgroup per candidate counts the up to 40 hypotheses, applies the choice and writes the winner's mask where
+//                     gms_batch writes its planes.  Both also serve chip_gms_filter_modes (B = 1, the explicit list).
 //   pose_sets_batch : MiscUtils::dmatch_2_eigen (src/utils/MiscUtils.cpp:121-143) + the two make_3d_2d_collection__ calls and
 //                     make_3d_3d_collection__using__pfmatches_and_disparity (PointFeatureMatching.cpp:95-195) as ONE ordered stream
 //                     compaction per candidate (ballot + prefix popcount per wave, scan across the 16 waves): outputs are in match
@@ -445,6 +449,184 @@ __global__ __launch_bounds__(kOneWg) void pose_sets_stored_batch(SetsStoredArgs 
     pose_sets_candidate(s.b, z, RecordPoints{s.rec_a, s.rec[z]});
 }
 
+// ------------------------------------------------------------------------------------------------ GMS with scale and rotation
+// gms_matcher::GetInlierMask(.., WithScale, WithRotation) (gms_matcher.cpp:17-68): run(RotationType) under SetScale(Scale) for up to
+// 5 x 8 hypotheses, of which the first with the strictly largest inlier count stays.  The table and the first-maximum column search of a
+// (scale, grid type) do not depend on the rotation -- only the 3 x 3 score does -- so ONE workgroup per (scale, grid type, candidate)
+// builds them once and scores all eight rotations; a second kernel counts the hypotheses and applies the choice.
+constexpr int kScales = 5, kRotations = 8;
+// right grid side at scale index s: (int)(20 * ratio), ratios 1, 1/2, 1/sqrt(2), sqrt(2), 2 in double (gms_matcher.h:47, :230-234)
+__host__ __device__ constexpr int mode_side(int s) { return s == 0 ? 20 : s == 1 ? 10 : s == 2 ? 14 : s == 3 ? 28 : 40; }
+// table columns of the scales before s: the prefix sums of side^2 = 400, 100, 196, 784, 1600
+__host__ __device__ constexpr int mode_cols_before(int s) { return s == 0 ? 0 : s == 1 ? 400 : s == 2 ? 500 : s == 3 ? 696 : s == 4 ? 1480 : 3080; }
+// the eight outer positions of a row-major 3 x 3 neighbourhood, clockwise from the top-left, one per nibble (ring position 0 lowest):
+// 0, 1, 2, 5, 8, 7, 6, 3.  Rotation type r pairs the left neighbour at ring position k with the right one at (k - (r - 1)) mod 8
+// (the eight patterns of gms_matcher.h:12-44 restated), centre with centre.
+constexpr uint32_t kRing = 0x36785210u;
+
+// GetGridIndexRight under SetScale (gms_matcher.h:184-189, :230-234): floorf(p * (float)side) per axis, x + y * side, no range check on
+// x or y; outside [0, side^2) the match has no right cell
+__device__ __forceinline__ int mode_cell_right(float px, float py, int side)
+{
+    const double x = (double)floorf(px * (float)side), y = (double)floorf(py * (float)side);
+    if (!(x >= -kCoordLim && x <= kCoordLim) || !(y >= -kCoordLim && y <= kCoordLim)) return -1;
+    const int idx = (int)x + (int)y * side;
+    return idx >= 0 && idx < side * side ? idx : -1;
+}
+
+struct GmsModesArgs {
+    const float2 *kp1;
+    int32_t n, w1, h1;                    // n matches per candidate
+    const unsigned long long *keys;       // [B][n]: match i of candidate j = (i, train index of keys[j][i]) ...
+    const int32_t *qidx, *tidx;           // ... or, when not null (B = 1), match i = (qidx[i], tidx[i])
+    int32_t *table;                       // [B][S][4][400][N_s]
+    uint8_t *plane;                       // [B][S][4][n]: per match the accepted-rotation bits (bit r - 1 = rotation r) of ONE (scale, grid type)
+    int32_t n_scales, n_rot;              // 1 or 5, 1 or 8
+    BatchCands cands;                     // kp, n, w, h of the candidates
+};
+// grid (4 grid types x S scales, B)
+__global__ __launch_bounds__(kOneWg) void gms_grid_modes(GmsModesArgs a)
+{
+    __shared__ int32_t cnt[kCells];      // mNumberPointsInPerCellLeft
+    __shared__ int32_t pair[kCells];     // mCellPairs before the threshold: the first column of maximal count, -1 for an empty row
+    __shared__ int32_t acc[kCells];      // per left cell: bit r - 1 set iff rotation r accepts its pair
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = blockIdx.x >> 2, type = (blockIdx.x & 3) + 1, z = blockIdx.y;
+    if (a.cands.c[z].n == 0) return;                          // no matches: gms_mode_select does not read this candidate's planes
+    const int side = mode_side(s), N = side * side, n = a.n;
+    const size_t per_cand = (size_t)4 * kCells * mode_cols_before(a.n_scales);
+    int32_t *table = a.table + (size_t)z * per_cand + (size_t)4 * kCells * mode_cols_before(s) + (size_t)(type - 1) * kCells * N;
+    uint8_t *plane = a.plane + (((size_t)z * a.n_scales + s) * 4 + (type - 1)) * (size_t)n;
+    const float2 *kp2 = a.cands.c[z].kp;
+    const unsigned long long *keys = a.keys ? a.keys + (size_t)z * n : nullptr;
+    const float fw1 = (float)a.w1, fh1 = (float)a.h1, fw2 = (float)a.cands.c[z].w, fh2 = (float)a.cands.c[z].h;
+    const bool listed = a.qidx != nullptr;                    // uniform
+    // the cell pair of match i under this (scale, grid type); NormalizePoints (gms_matcher.h:126-139): one float division per coordinate
+    const auto cells = [&](int i, int *l, int *r) {
+        const float2 lp = a.kp1[listed ? a.qidx[i] : i], rp = kp2[listed ? a.tidx[i] : key_train(keys[i])];
+        *l = gms_cell_left(__fdiv_rn(lp.x, fw1), __fdiv_rn(lp.y, fh1), type);
+        *r = mode_cell_right(__fdiv_rn(rp.x, fw2), __fdiv_rn(rp.y, fh2), side);
+    };
+    // ---- gms_matcher.cpp:161-163 (N is a multiple of 4 and so is every table offset)
+    for (int e = tid; e < kCells * N / 4; e += kOneWg) reinterpret_cast<int4 *>(table)[e] = make_int4(0, 0, 0, 0);
+    for (int e = tid; e < kCells; e += kOneWg) { cnt[e] = 0; pair[e] = -1; }
+    __threadfence();
+    __syncthreads();
+    // ---- AssignMatchPairs (:73-98)
+    for (int i = tid; i < n; i += kOneWg) {
+        int l, r;
+        cells(i, &l, &r);
+        if (l < 0 || r < 0) continue;                         // :92
+        atomicAdd(&table[l * N + r], 1);                      // :94
+        atomicAdd(&cnt[l], 1);                                // :95
+    }
+    __threadfence();
+    __syncthreads();
+    // ---- VerifyCellPairs, first half (:106-121), shared by the eight rotations: one wave per row over N columns
+    for (int row = wave; row < kCells; row += kOneWg / 64) {
+        if (cnt[row] == 0) continue;
+        int bv = 0, bj = INT_MAX;
+        for (int j = lane; j < N; j += 64) {
+            const int v = table_load(&table[row * N + j]);
+            if (v > bv) { bv = v; bj = j; }
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            const int ov = __shfl_xor(bv, m, 64), oj = __shfl_xor(bj, m, 64);
+            if (ov > bv || (ov == bv && oj < bj)) { bv = ov; bj = oj; }
+        }
+        if (lane == 0) pair[row] = bj;
+    }
+    __syncthreads();
+    // ---- second half (:123-146) for every (left cell, rotation) as one work item: 8 adjacent lanes hold the rotations of a cell
+    for (int item = tid; item < kCells * kRotations; item += kOneWg) {   // 3200 = 3 x 1024 + 128: whole waves enter every round
+        const int cell = item >> 3, rot = item & 7, pr = pair[cell];
+        bool ok = false;
+        if (pr >= 0 && rot < a.n_rot) {
+            const int lx = cell % kGrid, ly = cell / kGrid, rx = pr % side, ry = pr / side;
+            int score = table_load(&table[cell * N + pr]), tsum = cnt[cell], numpair = 1;   // centre with centre
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const int lp = (int)(kRing >> (4 * k)) & 15, rp = (int)(kRing >> (4 * ((k - rot) & 7))) & 15;
+                const int llx = lx + lp % 3 - 1, lly = ly + lp / 3 - 1, rrx = rx + rp % 3 - 1, rry = ry + rp / 3 - 1;
+                if (llx < 0 || llx >= kGrid || lly < 0 || lly >= kGrid || rrx < 0 || rrx >= side || rry < 0 || rry >= side) continue;   // :136
+                const int ll = llx + lly * kGrid;
+                score += table_load(&table[ll * N + rrx + rry * side]);
+                tsum += cnt[ll];
+                numpair++;
+            }
+            const double thresh = 6.0 * sqrt((double)tsum / (double)numpair);   // :143, over the pairs that remain
+            ok = !((double)score < thresh);                                       // :145-146
+        }
+        const unsigned long long m = __ballot(ok);
+        if (rot == 0) acc[cell] = (int32_t)((m >> (lane & 56)) & 0xffull);
+    }
+    __syncthreads();
+    // ---- mark (:169-177), for the eight rotations at once
+    for (int i = tid; i < n; i += kOneWg) {
+        int l, r;
+        cells(i, &l, &r);
+        plane[i] = l >= 0 && r >= 0 && pair[l] == r ? (uint8_t)acc[l] : (uint8_t)0;
+    }
+}
+
+struct GmsSelectArgs {
+    const uint8_t *plane;                 // [B][S][4][n] of gms_grid_modes
+    int32_t n, n_scales, n_rot;
+    uint8_t *mask;                        // candidate z: n bytes (0 / 1) at mask + z * mask_stride ...
+    size_t mask_stride;
+    int32_t zero_slots;                   // ... followed by 3 x n zero bytes: the [B][4][n] planes pose_sets_batch ORs
+    chip_gms_choice *choice;              // [B]
+    int32_t live[kMaxBatch];              // 0: an empty candidate, nothing to read or write but the choice
+};
+// grid B: the counts of the S x R hypotheses of candidate blockIdx.x, the choice (gms_matcher.cpp:19-33,38-48,54-66) and the winner's mask
+__global__ __launch_bounds__(kOneWg) void gms_mode_select(GmsSelectArgs a)
+{
+    __shared__ int32_t counts[kScales * kRotations];
+    __shared__ int32_t win[2];
+    const int tid = threadIdx.x, lane = tid & 63, z = blockIdx.x, n = a.n;
+    const bool live = a.live[z] != 0;                        // uniform
+    if (tid < kScales * kRotations) counts[tid] = (tid >> 3) < a.n_scales && (tid & 7) < a.n_rot ? 0 : -1;
+    __syncthreads();
+    const uint8_t *planes = a.plane + (size_t)z * a.n_scales * 4 * (size_t)n;
+    for (int s = 0; live && s < a.n_scales; s++) {
+        const uint8_t *p = planes + (size_t)s * 4 * (size_t)n;
+        int mine[kRotations] = {0, 0, 0, 0, 0, 0, 0, 0};    // wave-uniform
+        for (int base = 0; base < n; base += kOneWg) {
+            const int i = base + tid;
+            const int b = i < n ? p[i] | p[(size_t)n + i] | p[2 * (size_t)n + i] | p[3 * (size_t)n + i] : 0;
+#pragma unroll
+            for (int r = 0; r < kRotations; r++) mine[r] += __popcll(__ballot((b >> r) & 1));
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int r = 0; r < kRotations; r++)
+                if (r < a.n_rot) atomicAdd(&counts[s * kRotations + r], mine[r]);
+        }
+    }
+    __syncthreads();
+    chip_gms_choice *ch = a.choice + z;
+    if (tid == 0) {                                           // scales ascending, rotations inside: the first strictly larger count stays
+        int best = 0, bs = -1, br = 0;
+        for (int s = 0; s < a.n_scales; s++)
+            for (int r = 0; r < a.n_rot; r++)
+                if (counts[s * kRotations + r] > best) { best = counts[s * kRotations + r]; bs = s; br = r + 1; }
+        win[0] = bs; win[1] = br;
+        ch->scale = bs; ch->rotation = br; ch->n_inliers = best;
+    }
+    if (tid < kScales * kRotations) ch->counts[tid >> 3][tid & 7] = counts[tid];
+    __syncthreads();
+    if (!live) return;
+    uint8_t *out = a.mask + (size_t)z * a.mask_stride;
+    const int ws = win[0], shift = ws >= 0 ? win[1] - 1 : 0;
+    const uint8_t *p = planes + (size_t)(ws < 0 ? 0 : ws) * 4 * (size_t)n;
+    for (int i = tid; i < n; i += kOneWg) {
+        const int b = p[i] | p[(size_t)n + i] | p[2 * (size_t)n + i] | p[3 * (size_t)n + i];
+        out[i] = ws >= 0 ? (uint8_t)((b >> shift) & 1) : (uint8_t)0;   // no choice: the mask is all zero
+        if (a.zero_slots) out[(size_t)n + i] = out[2 * (size_t)n + i] = out[3 * (size_t)n + i] = 0;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 struct MatchState {
     // the stand-alone calls, sized for kMatchMax keypoints once; d1 / kp1 also hold the query frame of a pipeline run, and nothing that
@@ -468,6 +650,11 @@ struct MatchState {
     DevBuf<double> uv, uv_d, X_ab, uvn_ab, X_ba, uvn_ba, A, B;
     DevBuf<int32_t> mq, mt;
     std::vector<unsigned long long> h_keys;     // fetch_matches: keys on their way out
+    // GMS with scale / rotation: nothing of this exists before the first call with modes != 0 (modes_reserve)
+    DevBuf<int32_t> mode_table;                 // [B][S][4][400][N_s]
+    DevBuf<uint8_t> mode_plane;                 // [B][S][4][n]
+    DevBuf<chip_gms_choice> mode_choice;        // [kMaxBatch]
+    PinnedBuf<chip_gms_choice> h_choice;
     // the frame store (chip_frame_store_reserve): n_slots slots of slot_kp keypoints each, 56 bytes per keypoint; rows never move after the
     // reserve.  Slot k: desc + 32 * k * slot_kp, kp + k * slot_kp, rec + k * slot_kp.  stage_xyz: the image of the put in flight.
     struct StoredFrame { int64_t id = 0; int32_t n = 0, w = 0, h = 0; bool used = false; };
@@ -478,7 +665,7 @@ struct MatchState {
     int32_t n_slots = 0, slot_kp = 0, n_frames = 0;
     std::vector<StoredFrame> slots;
     std::unordered_map<int64_t, int32_t> slot_of;   // id -> slot
-    hipEvent_t ev[4] = {};                      // tuning only (CHIP_MATCH_BATCH_TIMING=1): around the three launches of a run
+    hipEvent_t ev[5] = {};                      // tuning only (CHIP_MATCH_BATCH_TIMING=1): around the three (with GMS modes: four) launches of a run
     // what the last run left: n_cand candidates of a query frame of n1 keypoints, of which ONE is selected -- the pointers and counts
     // chip_match_read_sets and the _matched solvers work on
     struct Sets { double *uv, *uv_d, *X_ab, *uvn_ab, *X_ba, *uvn_ba, *A, *B; int32_t *mq, *mt; };
@@ -487,6 +674,7 @@ struct MatchState {
                                                 // chip_match_batch, CHIP_ERR_BUSY after a chip_match_pair
     int32_t n_cand = 0, n1 = 0;
     chip_match_summary cand_sm[CHIP_MATCH_MAX_BATCH] = {};
+    chip_gms_choice cand_choice[CHIP_MATCH_MAX_BATCH] = {};   // of the last run, whatever its modes
     Sets cur{};
     chip_match_summary last{};                  // the selected candidate's summary
 
@@ -618,25 +806,86 @@ struct RunFrames {
     RunFrames() { std::memset(&cands, 0, sizeof cands); std::memset(rec, 0, sizeof rec); }
 };
 
-// tuning only (CHIP_MATCH_BATCH_TIMING=1): device time of each of the three kernels by events, averaged, printed at process exit; runs on
-// host frames and runs on stored frames are kept apart
+// tuning only (CHIP_MATCH_BATCH_TIMING=1): device time of each kernel of a run by events, averaged, printed at process exit; runs on
+// host frames, runs on stored frames and runs with GMS modes (four kernels) are kept apart
 struct KernelTiming {
-    const char *what, *sets;
-    double acc[3] = {0, 0, 0}; long n = 0; bool on = std::getenv("CHIP_MATCH_BATCH_TIMING") != nullptr;
-    KernelTiming(const char *w, const char *k) : what(w), sets(k) {}
-    ~KernelTiming() { if (on && n) std::fprintf(stderr, "%s kernel timing over %ld calls (us): hamming_match_split %.1f, gms_batch %.1f, %s %.1f\n",
-                                                what, n, 1e3 * acc[0] / n, 1e3 * acc[1] / n, sets, 1e3 * acc[2] / n); }
+    const char *what;
+    const char *name[4];
+    int k;
+    double acc[4] = {0, 0, 0, 0}; long n = 0; bool on = std::getenv("CHIP_MATCH_BATCH_TIMING") != nullptr;
+    KernelTiming(const char *w, const char *sets) : what(w), name{"hamming_match_split", "gms_batch", sets, nullptr}, k(3) {}
+    KernelTiming(const char *w, const char *sets, bool) : what(w), name{"hamming_match_split", "gms_grid_modes", "gms_mode_select", sets}, k(4) {}
+    ~KernelTiming()
+    {
+        if (!on || !n) return;
+        std::fprintf(stderr, "%s kernel timing over %ld calls (us):", what, n);
+        for (int i = 0; i < k; i++) std::fprintf(stderr, "%s %s %.1f", i ? "," : "", name[i], 1e3 * acc[i] / n);
+        std::fprintf(stderr, "\n");
+    }
 };
 
-// The device part of a run, for both kinds of frames (f.n1 >= 1, the slabs reserved): the keys preset, three launches, the counts back,
-// cand_sm[0 .. B) filled.
-static int match_launch(Ctx *c, MatchState *st, hipStream_t s, const RunFrames &f, int B, const double Kinv[9])
+// What a call with no hypothesis to choose from reports (no matches at all): nothing chosen, 0 for the combinations the modes try
+static void choice_none(chip_gms_choice *ch, uint32_t modes)
+{
+    ch->scale = -1; ch->rotation = 0; ch->n_inliers = 0;
+    const int S = modes & CHIP_GMS_WITH_SCALE ? kScales : 1, R = modes & CHIP_GMS_WITH_ROTATION ? kRotations : 1;
+    for (int s = 0; s < kScales; s++)
+        for (int r = 0; r < kRotations; r++) ch->counts[s][r] = s < S && r < R ? 0 : -1;
+}
+// modes == 0: the one hypothesis (scale 0, rotation 1) with the plain count
+static void choice_plain(chip_gms_choice *ch, int32_t n_inliers)
+{
+    choice_none(ch, 0);
+    ch->scale = 0; ch->rotation = 1; ch->n_inliers = ch->counts[0][0] = n_inliers;
+}
+
+// The tables, planes and choice records of a call with modes != 0: B candidates, S scales, n matches each.  Whatever has to grow grows
+// inside ONE pause (as batch_reserve); a process that never passes modes != 0 never comes here.
+static int modes_reserve(Ctx *c, MatchState *st, size_t B, int S, size_t n)
+{
+    const size_t tab = B * 4 * kCells * (size_t)mode_cols_before(S), pl = B * (size_t)S * 4 * n;
+    if (st->mode_table.capacity() >= tab && st->mode_plane.capacity() >= pl && st->h_choice.capacity()) return CHIP_OK;
+    ResidentPause paused(c);
+    int rc = st->mode_table.reserve(c, tab);
+    if (rc == CHIP_OK) rc = st->mode_plane.reserve(c, pl);
+    if (rc == CHIP_OK) rc = st->mode_choice.reserve(c, kMaxBatch);
+    if (rc == CHIP_OK) rc = st->h_choice.reserve(c, kMaxBatch);
+    return rc;
+}
+// the two launches of the mode on B candidates of n matches: ga filled but for table / plane / n_scales / n_rot
+static int launch_modes(Ctx *c, MatchState *st, hipStream_t s, GmsModesArgs &ga, int B, uint32_t modes, uint8_t *mask, size_t mask_stride,
+                        bool zero_slots, hipEvent_t between)
+{
+    ga.n_scales = modes & CHIP_GMS_WITH_SCALE ? kScales : 1;
+    ga.n_rot = modes & CHIP_GMS_WITH_ROTATION ? kRotations : 1;
+    ga.table = st->mode_table; ga.plane = st->mode_plane;
+    hipLaunchKernelGGL(gms_grid_modes, dim3(4 * ga.n_scales, B), dim3(kOneWg), 0, s, ga);
+    CHIP_HIP(c, hipGetLastError());
+    if (between) CHIP_HIP(c, hipEventRecord(between, s));
+    GmsSelectArgs sa;
+    sa.plane = st->mode_plane; sa.n = ga.n; sa.n_scales = ga.n_scales; sa.n_rot = ga.n_rot;
+    sa.mask = mask; sa.mask_stride = mask_stride; sa.zero_slots = zero_slots ? 1 : 0; sa.choice = st->mode_choice;
+    for (int j = 0; j < kMaxBatch; j++) sa.live[j] = j < B && ga.cands.c[j].n > 0;
+    hipLaunchKernelGGL(gms_mode_select, dim3(B), dim3(kOneWg), 0, s, sa);
+    CHIP_HIP(c, hipGetLastError());
+    return CHIP_OK;
+}
+
+// The device part of a run, for both kinds of frames (f.n1 >= 1, the slabs reserved): the keys preset, three launches (with GMS modes
+// four: gms_grid_modes + gms_mode_select in the place of gms_batch), the counts back, cand_sm[0 .. B) and cand_choice[0 .. B) filled.
+static int match_launch(Ctx *c, MatchState *st, hipStream_t s, const RunFrames &f, int B, const double Kinv[9], uint32_t modes)
 {
     const int n1 = f.n1;
+    if (modes && f.max_n2 > 0) {
+        const int rc = modes_reserve(c, st, (size_t)B, modes & CHIP_GMS_WITH_SCALE ? kScales : 1, (size_t)n1);
+        if (rc != CHIP_OK) return rc;
+    }
     CHIP_HIP(c, hipMemsetAsync(st->keys, 0xff, (size_t)B * n1 * sizeof(unsigned long long), s));   // all ones: no match yet
     if (f.max_n2 > 0) {
         static KernelTiming kt_host("match batch", "pose_sets_batch"), kt_stored("match batch stored", "pose_sets_stored_batch");
-        KernelTiming &kt = f.stored ? kt_stored : kt_host;
+        static KernelTiming km_host("match batch modes", "pose_sets_batch", true), km_stored("match batch stored modes", "pose_sets_stored_batch", true);
+        KernelTiming &kt = modes ? (f.stored ? km_stored : km_host) : (f.stored ? kt_stored : kt_host);
+        const int last = kt.k;                   // ev[last]: after the sets kernel
         if (kt.on)
             for (hipEvent_t &e : st->ev)
                 if (!e) CHIP_HIP(c, hipEventCreate(&e));
@@ -644,12 +893,19 @@ static int match_launch(Ctx *c, MatchState *st, hipStream_t s, const RunFrames &
         int rc = launch_matcher(c, s, f.desc_a, n1, f.cands, f.max_n2, B, st->keys);
         if (rc != CHIP_OK) return rc;
         if (kt.on) CHIP_HIP(c, hipEventRecord(st->ev[1], s));
-        GmsBatchArgs ga;
-        ga.kp1 = f.kp_a; ga.n1 = n1; ga.w1 = f.w1; ga.h1 = f.h1; ga.keys = st->keys; ga.table = st->table; ga.plane = st->plane;
-        ga.cands = f.cands;
-        hipLaunchKernelGGL(gms_batch, dim3(4, B), dim3(kOneWg), 0, s, ga);
-        CHIP_HIP(c, hipGetLastError());
-        if (kt.on) CHIP_HIP(c, hipEventRecord(st->ev[2], s));
+        if (modes) {                             // the winner's mask goes where gms_batch's planes go: slot 0 the mask, slots 1-3 zero
+            GmsModesArgs ma;
+            ma.kp1 = f.kp_a; ma.n = n1; ma.w1 = f.w1; ma.h1 = f.h1; ma.keys = st->keys; ma.qidx = ma.tidx = nullptr; ma.cands = f.cands;
+            rc = launch_modes(c, st, s, ma, B, modes, st->plane, 4 * (size_t)n1, true, kt.on ? st->ev[2] : nullptr);
+            if (rc != CHIP_OK) return rc;
+        } else {
+            GmsBatchArgs ga;
+            ga.kp1 = f.kp_a; ga.n1 = n1; ga.w1 = f.w1; ga.h1 = f.h1; ga.keys = st->keys; ga.table = st->table; ga.plane = st->plane;
+            ga.cands = f.cands;
+            hipLaunchKernelGGL(gms_batch, dim3(4, B), dim3(kOneWg), 0, s, ga);
+            CHIP_HIP(c, hipGetLastError());
+        }
+        if (kt.on) CHIP_HIP(c, hipEventRecord(st->ev[last - 1], s));
         SetsStoredArgs ss;
         SetsBatchArgs &sa = ss.b;
         sa.kp1 = f.kp_a; sa.xyz_a = f.xyz_a; sa.n1 = n1; sa.w1 = f.w1; sa.h1 = f.h1; sa.keys = st->keys; sa.plane = st->plane;
@@ -664,10 +920,11 @@ static int match_launch(Ctx *c, MatchState *st, hipStream_t s, const RunFrames &
             hipLaunchKernelGGL(pose_sets_batch, dim3(B), dim3(kOneWg), 0, s, sa);
         }
         CHIP_HIP(c, hipGetLastError());
-        if (kt.on) CHIP_HIP(c, hipEventRecord(st->ev[3], s));
+        if (kt.on) CHIP_HIP(c, hipEventRecord(st->ev[last], s));
         CHIP_HIP(c, hipMemcpyAsync(st->h_counts.host(), st->counts, (size_t)B * kNSets * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (modes) CHIP_HIP(c, hipMemcpyAsync(st->h_choice.host(), st->mode_choice, (size_t)B * sizeof(chip_gms_choice), hipMemcpyDeviceToHost, s));
         CHIP_HIP(c, hipStreamSynchronize(s));
-        for (int k = 0; k < 3 && kt.on; k++) {
+        for (int k = 0; k < last && kt.on; k++) {
             float ms = 0.f;
             CHIP_HIP(c, hipEventElapsedTime(&ms, st->ev[k], st->ev[k + 1]));
             kt.acc[k] += ms;
@@ -678,6 +935,8 @@ static int match_launch(Ctx *c, MatchState *st, hipStream_t s, const RunFrames &
     for (int j = 0; j < B && f.max_n2 > 0; j++) {
         if (f.cands.c[j].n == 0) continue;
         const int32_t *h = st->h_counts.host() + j * kNSets;
+        if (modes) st->cand_choice[j] = st->h_choice.host()[j];
+        else choice_plain(&st->cand_choice[j], h[kSetUv]);
         chip_match_summary &sm = st->cand_sm[j];
         sm.n_matches_all = n1;
         sm.n_matches_gms = h[kSetUv]; sm.n_3d2d_ab = h[kSetAb]; sm.n_3d2d_ba = h[kSetBa]; sm.n_3d3d = h[kSet33]; sm.n_out_of_image = h[kSetOut];
@@ -697,7 +956,7 @@ static void match_finish(MatchState *st, int B, int n1)
 // The pipeline on host frames: frame a against the candidates b[0 .. B) -- uploads, three launches, the counts back -- leaves the keys and
 // the five sets of every candidate in its slab, cand_sm[0 .. B) filled and candidate 0 selected.  match_mu held, the arguments checked,
 // have_sets false.
-static int match_run(Ctx *c, MatchState *st, const chip_match_frame *a, const chip_match_frame *b, int B, const double Kinv[9])
+static int match_run(Ctx *c, MatchState *st, const chip_match_frame *a, const chip_match_frame *b, int B, const double Kinv[9], uint32_t modes = 0)
 {
     int rc0 = icp_wait_matched(c);               // a pending matched ICP batch reads the slabs this run rewrites
     if (rc0 != CHIP_OK) return rc0;
@@ -710,7 +969,10 @@ static int match_run(Ctx *c, MatchState *st, const chip_match_frame *a, const ch
         tot_n += (size_t)b[j].n;
         tot_px += (size_t)b[j].width * b[j].height;
     }
-    for (int j = 0; j < B; j++) std::memset(&st->cand_sm[j], 0, sizeof(chip_match_summary));
+    for (int j = 0; j < B; j++) {
+        std::memset(&st->cand_sm[j], 0, sizeof(chip_match_summary));
+        choice_none(&st->cand_choice[j], modes);   // what an empty query frame or candidate keeps
+    }
     if (n1 > 0) {
         const size_t px_a = (size_t)a->width * a->height;
         int rc = batch_reserve(c, st, (size_t)B, (size_t)n1, true, tot_n, tot_px, px_a);
@@ -736,7 +998,7 @@ static int match_run(Ctx *c, MatchState *st, const chip_match_frame *a, const ch
             }
         }
         f.desc_a = st->d1; f.kp_a = st->kp1; f.n1 = n1; f.w1 = a->width; f.h1 = a->height; f.xyz_a = st->xyz_a;
-        rc = match_launch(c, st, s, f, B, Kinv);
+        rc = match_launch(c, st, s, f, B, Kinv, modes);
         if (rc != CHIP_OK) return rc;
     }
     match_finish(st, B, n1);
@@ -744,7 +1006,7 @@ static int match_run(Ctx *c, MatchState *st, const chip_match_frame *a, const ch
 }
 
 // The pipeline on stored frames: slot sa against the slots sb[0 .. B), nothing uploaded.  Same state afterwards as match_run.
-static int match_run_stored(Ctx *c, MatchState *st, int32_t sa, const int32_t *sb, int B, const double Kinv[9])
+static int match_run_stored(Ctx *c, MatchState *st, int32_t sa, const int32_t *sb, int B, const double Kinv[9], uint32_t modes)
 {
     int rc0 = icp_wait_matched(c);               // as match_run
     if (rc0 != CHIP_OK) return rc0;
@@ -755,6 +1017,7 @@ static int match_run_stored(Ctx *c, MatchState *st, int32_t sa, const int32_t *s
     for (int j = 0; j < B; j++) {
         const MatchState::StoredFrame &b = st->slots[(size_t)sb[j]];
         std::memset(&st->cand_sm[j], 0, sizeof(chip_match_summary));
+        choice_none(&st->cand_choice[j], modes);
         if (b.n == 0) continue;
         const size_t at = (size_t)sb[j] * kp;
         f.max_n2 = b.n > f.max_n2 ? b.n : f.max_n2;
@@ -767,7 +1030,7 @@ static int match_run_stored(Ctx *c, MatchState *st, int32_t sa, const int32_t *s
         const size_t at = (size_t)sa * kp;
         f.desc_a = st->store_desc + at * CHIP_ORB_DESC_BYTES; f.kp_a = st->store_kp + at; f.rec_a = st->store_rec + at;
         f.n1 = a.n; f.w1 = a.w; f.h1 = a.h;
-        rc = match_launch(c, st, match_stream(c), f, B, Kinv);
+        rc = match_launch(c, st, match_stream(c), f, B, Kinv, modes);
         if (rc != CHIP_OK) return rc;
     }
     match_finish(st, B, a.n);
@@ -805,15 +1068,19 @@ extern "C" int chip_orb_match(chip_ctx *c, const uint8_t *d1, int32_t n1, const 
     return fetch_matches(c, s, st, st->orb_keys, (size_t)n1, train_idx, distance);
 }
 
-extern "C" int chip_gms_filter(chip_ctx *c, const float *kp1_xy, int32_t n1, int32_t w1, int32_t h1, const float *kp2_xy, int32_t n2, int32_t w2,
-                               int32_t h2, const int32_t *query_idx, const int32_t *train_idx, int32_t n_matches, uint8_t *inlier, int32_t *n_inliers)
+// chip_gms_filter (modes == 0: gms_filter, one launch) and chip_gms_filter_modes (the two kernels of the mode with B = 1 on the list)
+static int gms_filter_call(chip_ctx *c, const float *kp1_xy, int32_t n1, int32_t w1, int32_t h1, const float *kp2_xy, int32_t n2, int32_t w2,
+                           int32_t h2, const int32_t *query_idx, const int32_t *train_idx, int32_t n_matches, uint32_t modes, uint8_t *inlier,
+                           int32_t *n_inliers, chip_gms_choice *choice)
 {
+    if (modes & ~(uint32_t)(CHIP_GMS_WITH_SCALE | CHIP_GMS_WITH_ROTATION)) return CHIP_ERR_INVALID_ARG;
     if (!c || n1 < 0 || n2 < 0 || n_matches < 0 || w1 <= 0 || h1 <= 0 || w2 <= 0 || h2 <= 0 || !n_inliers) return CHIP_ERR_INVALID_ARG;
     if ((n1 > 0 && !kp1_xy) || (n2 > 0 && !kp2_xy) || (n_matches > 0 && (!query_idx || !train_idx || !inlier))) return CHIP_ERR_INVALID_ARG;
     if (c->group || n1 > kMatchMax || n2 > kMatchMax || n_matches > kMatchMax) return CHIP_ERR_UNSUPPORTED;
     for (int32_t i = 0; i < n_matches; i++)   // the kernel indexes the keypoints with these
         if (query_idx[i] < 0 || query_idx[i] >= n1 || train_idx[i] < 0 || train_idx[i] >= n2) return CHIP_ERR_RANGE;
     *n_inliers = 0;
+    if (choice) choice_none(choice, modes);
     if (n_matches == 0) return CHIP_OK;
     std::lock_guard<std::mutex> lk(c->match_mu);
     CHIP_HIP(c, hipSetDevice(c->device));
@@ -825,6 +1092,22 @@ extern "C" int chip_gms_filter(chip_ctx *c, const float *kp1_xy, int32_t n1, int
     CHIP_HIP(c, hipMemcpyAsync(st->kp2, kp2_xy, (size_t)n2 * sizeof(float2), hipMemcpyHostToDevice, s));
     CHIP_HIP(c, hipMemcpyAsync(st->qidx, query_idx, (size_t)n_matches * sizeof(int32_t), hipMemcpyHostToDevice, s));
     CHIP_HIP(c, hipMemcpyAsync(st->tidx, train_idx, (size_t)n_matches * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (modes) {
+        rc = modes_reserve(c, st, 1, modes & CHIP_GMS_WITH_SCALE ? kScales : 1, (size_t)n_matches);
+        if (rc != CHIP_OK) return rc;
+        GmsModesArgs ma;
+        std::memset(&ma.cands, 0, sizeof ma.cands);
+        ma.kp1 = st->kp1; ma.n = n_matches; ma.w1 = w1; ma.h1 = h1; ma.keys = nullptr; ma.qidx = st->qidx; ma.tidx = st->tidx;
+        ma.cands.c[0].kp = st->kp2; ma.cands.c[0].n = n2; ma.cands.c[0].w = w2; ma.cands.c[0].h = h2;   // n2 >= 1: there is a match
+        rc = launch_modes(c, st, s, ma, 1, modes, st->inlier, 0, false, nullptr);
+        if (rc != CHIP_OK) return rc;
+        CHIP_HIP(c, hipMemcpyAsync(inlier, st->inlier, (size_t)n_matches, hipMemcpyDeviceToHost, s));
+        CHIP_HIP(c, hipMemcpyAsync(st->h_choice.host(), st->mode_choice, sizeof(chip_gms_choice), hipMemcpyDeviceToHost, s));
+        CHIP_HIP(c, hipStreamSynchronize(s));
+        *n_inliers = st->h_choice.host()[0].n_inliers;
+        if (choice) *choice = st->h_choice.host()[0];
+        return CHIP_OK;
+    }
     GmsArgs g;
     g.kp1 = st->kp1; g.kp2 = st->kp2; g.w1 = w1; g.h1 = h1; g.w2 = w2; g.h2 = h2;
     g.qidx = st->qidx; g.tidx = st->tidx; g.n = n_matches;
@@ -835,7 +1118,23 @@ extern "C" int chip_gms_filter(chip_ctx *c, const float *kp1_xy, int32_t n1, int
     CHIP_HIP(c, hipMemcpyAsync(st->h_counts.host(), st->counts, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     CHIP_HIP(c, hipStreamSynchronize(s));
     *n_inliers = st->h_counts.host()[0];
+    if (choice) choice_plain(choice, *n_inliers);
     return CHIP_OK;
+}
+
+extern "C" int chip_gms_filter(chip_ctx *c, const float *kp1_xy, int32_t n1, int32_t w1, int32_t h1, const float *kp2_xy, int32_t n2, int32_t w2,
+                               int32_t h2, const int32_t *query_idx, const int32_t *train_idx, int32_t n_matches, uint8_t *inlier, int32_t *n_inliers)
+{
+    return gms_filter_call(c, kp1_xy, n1, w1, h1, kp2_xy, n2, w2, h2, query_idx, train_idx, n_matches, 0, inlier, n_inliers, nullptr);
+}
+
+extern "C" int chip_build_has_gms_modes(void) { return 1; }
+
+extern "C" int chip_gms_filter_modes(chip_ctx *c, const float *kp1_xy, int32_t n1, int32_t w1, int32_t h1, const float *kp2_xy, int32_t n2,
+                                     int32_t w2, int32_t h2, const int32_t *query_idx, const int32_t *train_idx, int32_t n_matches, uint32_t modes,
+                                     uint8_t *inlier, int32_t *n_inliers, chip_gms_choice *choice)
+{
+    return gms_filter_call(c, kp1_xy, n1, w1, h1, kp2_xy, n2, w2, h2, query_idx, train_idx, n_matches, modes, inlier, n_inliers, choice);
 }
 
 // a batch of one
@@ -913,14 +1212,14 @@ extern "C" int chip_icp_ransac_matched(chip_ctx *c, const chip_ransac_params *p,
 // ------------------------------------------------------------------------------------------------ one query frame against B candidates
 extern "C" int chip_build_has_match_batch(void) { return 1; }
 
-extern "C" int chip_match_batch(chip_ctx *c, const chip_match_frame *a, const chip_match_frame *b, int32_t B, const double Kinv[9],
-                                chip_match_summary *summary)
+static int match_batch_call(chip_ctx *c, const chip_match_frame *a, const chip_match_frame *b, int32_t B, const double Kinv[9], uint32_t modes,
+                            chip_match_summary *summary, chip_gms_choice *choice)
 {
     if (!c) return CHIP_ERR_INVALID_ARG;
     if (c->group) return CHIP_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> lk(c->match_mu);
     if (c->match_state) c->match_state->have_sets = false;   // a failed call, refused arguments included, leaves nothing selected
-    if (!a || !b || !Kinv || !summary || B < 1) return CHIP_ERR_INVALID_ARG;
+    if (!a || !b || !Kinv || !summary || B < 1 || (modes & ~(uint32_t)(CHIP_GMS_WITH_SCALE | CHIP_GMS_WITH_ROTATION))) return CHIP_ERR_INVALID_ARG;
     if (B > kMaxBatch) return CHIP_ERR_UNSUPPORTED;
     int rc = check_frame(a);
     for (int j = 0; j < B && rc == CHIP_OK; j++) rc = check_frame(&b[j]);
@@ -930,11 +1229,24 @@ extern "C" int chip_match_batch(chip_ctx *c, const chip_match_frame *a, const ch
     rc = match_state(c, &st);
     if (rc != CHIP_OK) return rc;
     st->have_sets = false;
-    rc = match_run(c, st, a, b, B, Kinv);
+    rc = match_run(c, st, a, b, B, Kinv, modes);
     if (rc != CHIP_OK) return rc;
     st->keys_readable = true;
     for (int j = 0; j < B; j++) summary[j] = st->cand_sm[j];
+    for (int j = 0; j < B && choice; j++) choice[j] = st->cand_choice[j];
     return CHIP_OK;
+}
+
+extern "C" int chip_match_batch(chip_ctx *c, const chip_match_frame *a, const chip_match_frame *b, int32_t B, const double Kinv[9],
+                                chip_match_summary *summary)
+{
+    return match_batch_call(c, a, b, B, Kinv, 0, summary, nullptr);
+}
+
+extern "C" int chip_match_batch_modes(chip_ctx *c, const chip_match_frame *a, const chip_match_frame *b, int32_t B, const double Kinv[9],
+                                      uint32_t modes, chip_match_summary *summary, chip_gms_choice *choice)
+{
+    return match_batch_call(c, a, b, B, Kinv, modes, summary, choice);
 }
 
 extern "C" int chip_match_select(chip_ctx *c, int32_t j)
@@ -1188,14 +1500,15 @@ extern "C" int chip_frame_read(chip_ctx *c, int64_t id, int32_t *n, int32_t *wid
     return CHIP_OK;
 }
 
-extern "C" int chip_match_batch_stored(chip_ctx *c, int64_t a_id, const int64_t *b_ids, int32_t B, const double Kinv[9], chip_match_summary *summary)
+static int match_batch_stored_call(chip_ctx *c, int64_t a_id, const int64_t *b_ids, int32_t B, const double Kinv[9], uint32_t modes,
+                                   chip_match_summary *summary, chip_gms_choice *choice)
 {
     if (!c) return CHIP_ERR_INVALID_ARG;
     if (c->group) return CHIP_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> lk(c->match_mu);
     MatchState *st = c->match_state;
     if (st) st->have_sets = false;           // a failed call, refused arguments included, leaves nothing selected
-    if (!b_ids || !Kinv || !summary || B < 1) return CHIP_ERR_INVALID_ARG;
+    if (!b_ids || !Kinv || !summary || B < 1 || (modes & ~(uint32_t)(CHIP_GMS_WITH_SCALE | CHIP_GMS_WITH_ROTATION))) return CHIP_ERR_INVALID_ARG;
     if (B > kMaxBatch) return CHIP_ERR_UNSUPPORTED;
     if (!st || st->n_slots == 0) return CHIP_ERR_BUSY;
     int32_t sb[kMaxBatch];
@@ -1207,9 +1520,21 @@ extern "C" int chip_match_batch_stored(chip_ctx *c, int64_t a_id, const int64_t 
         sb[j] = fb->second;
     }
     CHIP_HIP(c, hipSetDevice(c->device));
-    const int rc = match_run_stored(c, st, fa->second, sb, B, Kinv);
+    const int rc = match_run_stored(c, st, fa->second, sb, B, Kinv, modes);
     if (rc != CHIP_OK) return rc;
     st->keys_readable = true;
     for (int j = 0; j < B; j++) summary[j] = st->cand_sm[j];
+    for (int j = 0; j < B && choice; j++) choice[j] = st->cand_choice[j];
     return CHIP_OK;
+}
+
+extern "C" int chip_match_batch_stored(chip_ctx *c, int64_t a_id, const int64_t *b_ids, int32_t B, const double Kinv[9], chip_match_summary *summary)
+{
+    return match_batch_stored_call(c, a_id, b_ids, B, Kinv, 0, summary, nullptr);
+}
+
+extern "C" int chip_match_batch_stored_modes(chip_ctx *c, int64_t a_id, const int64_t *b_ids, int32_t B, const double Kinv[9], uint32_t modes,
+                                             chip_match_summary *summary, chip_gms_choice *choice)
+{
+    return match_batch_stored_call(c, a_id, b_ids, B, Kinv, modes, summary, choice);
 }

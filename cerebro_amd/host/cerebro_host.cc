@@ -594,34 +594,35 @@ static bool verify_matched(chip_ctx *ctx, const chip_match_summary *sm, int B, P
 }
 
 bool verify_candidates(chip_ctx *ctx, const chip_match_frame &frame_a, const chip_match_frame *frames_b, int B, const double Kinv[9],
-                       ProcessedLoopCandidate *pc, bool *accepted, const uint64_t *seeds, chip_match_summary *summaries)
+                       ProcessedLoopCandidate *pc, bool *accepted, const uint64_t *seeds, chip_match_summary *summaries, uint32_t gms_modes,
+                       chip_gms_choice *choices)
 {
     if (!frames_b || !pc || !accepted || B < 1 || B > CHIP_MATCH_MAX_BATCH) return false;
     for (int j = 0; j < B; j++) accepted[j] = false;
     chip_match_summary sm[CHIP_MATCH_MAX_BATCH] = {};
-    const int rc = chip_match_batch(ctx, &frame_a, frames_b, B, Kinv, sm);
+    const int rc = chip_match_batch_modes(ctx, &frame_a, frames_b, B, Kinv, gms_modes, sm, choices);   // gms_modes == 0: chip_match_batch
     if (summaries) for (int j = 0; j < B; j++) summaries[j] = sm[j];
     if (rc != CHIP_OK) return false;
     return verify_matched(ctx, sm, B, pc, accepted, seeds);
 }
 
 bool verify_candidates_stored(chip_ctx *ctx, int64_t a_id, const int64_t *b_ids, int B, const double Kinv[9], ProcessedLoopCandidate *pc,
-                              bool *accepted, const uint64_t *seeds, chip_match_summary *summaries)
+                              bool *accepted, const uint64_t *seeds, chip_match_summary *summaries, uint32_t gms_modes, chip_gms_choice *choices)
 {
     if (!b_ids || !pc || !accepted || B < 1 || B > CHIP_MATCH_MAX_BATCH) return false;
     for (int j = 0; j < B; j++) accepted[j] = false;
     chip_match_summary sm[CHIP_MATCH_MAX_BATCH] = {};
-    const int rc = chip_match_batch_stored(ctx, a_id, b_ids, B, Kinv, sm);
+    const int rc = chip_match_batch_stored_modes(ctx, a_id, b_ids, B, Kinv, gms_modes, sm, choices);   // gms_modes == 0: chip_match_batch_stored
     if (summaries) for (int j = 0; j < B; j++) summaries[j] = sm[j];
     if (rc != CHIP_OK) return false;
     return verify_matched(ctx, sm, B, pc, accepted, seeds);
 }
 
 bool verify_candidate(chip_ctx *ctx, const chip_match_frame &frame_a, const chip_match_frame &frame_b, const double Kinv[9],
-                      ProcessedLoopCandidate &pc, uint64_t seed, chip_match_summary *summary)
+                      ProcessedLoopCandidate &pc, uint64_t seed, chip_match_summary *summary, uint32_t gms_modes)
 {
     bool accepted = false;                                          // a batch of one
-    return verify_candidates(ctx, frame_a, &frame_b, 1, Kinv, &pc, &accepted, &seed, summary) && accepted;
+    return verify_candidates(ctx, frame_a, &frame_b, 1, Kinv, &pc, &accepted, &seed, summary, gms_modes) && accepted;
 }
 
 void matrix4_to_pose(const double T[16], double position[3], double q[4])

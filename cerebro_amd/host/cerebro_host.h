@@ -209,7 +209,7 @@ struct StaticPointFeatureMatching {
 // with B = 1 -- the match stage, the "< 150 matches" reject (Cerebro.cpp:1487) -> pf_matches (:1505) -> the three poses on the
 // device-resident sets (seeds as compute_three_way_pose) -> NaN gate (:1678).  One upload; nothing but counts and poses returns to the host.
 bool verify_candidate(chip_ctx *ctx, const chip_match_frame &frame_a, const chip_match_frame &frame_b, const double Kinv[9],
-                      ProcessedLoopCandidate &proc_candi, uint64_t seed = 0, chip_match_summary *summary = nullptr);
+                      ProcessedLoopCandidate &proc_candi, uint64_t seed = 0, chip_match_summary *summary = nullptr, uint32_t gms_modes = 0);
 // B candidates of one keyframe (B <= CHIP_MATCH_MAX_BATCH): ONE chip_match_batch (frame_a uploaded once, all pairs in three launches),
 // the "< 150 matches" reject per candidate, ONE matched ICP batch over the survivors enqueued (chip_icp_ransac_matched_batch_enqueue),
 // ONE chip_pnp_ransac_matched_batch over their a->b and b->a sets (seeds seeds[j], seeds[j] + 1; nullptr: the default seed) underneath
@@ -218,13 +218,17 @@ bool verify_candidate(chip_ctx *ctx, const chip_match_frame &frame_a, const chip
 // not a failure) the whole verification returns false, as it does for the PnP call.
 // pc[j] / accepted[j] are what verify_candidate(ctx, frame_a, frames_b[j], Kinv, pc[j], seeds[j]) gives, field for field.  Returns false
 // only if a library call failed (then every accepted[j] is false).
+// gms_modes: the two booleans of GetInlierMask(mask, WithScale, WithRotation) (PointFeatureMatching.cpp:52-53) as CHIP_GMS_WITH_SCALE |
+// CHIP_GMS_WITH_ROTATION; 0, the default, is the reference's call site (false, false).  choices[j]: which (scale, rotation) GMS kept.
 bool verify_candidates(chip_ctx *ctx, const chip_match_frame &frame_a, const chip_match_frame *frames_b, int B, const double Kinv[9],
-                       ProcessedLoopCandidate *pc, bool *accepted, const uint64_t *seeds = nullptr, chip_match_summary *summaries = nullptr);
+                       ProcessedLoopCandidate *pc, bool *accepted, const uint64_t *seeds = nullptr, chip_match_summary *summaries = nullptr,
+                       uint32_t gms_modes = 0, chip_gms_choice *choices = nullptr);
 // The same on frames kept on the device (chip_frame_put under the ids a_id / b_ids[j]): ONE chip_match_batch_stored -- nothing is
 // uploaded -- then the same tail as verify_candidates (one copy of it).  Field for field what verify_candidates gives on the host
 // frames that were put under those ids, with the same seeds.  An unknown id is a failed library call (false).
 bool verify_candidates_stored(chip_ctx *ctx, int64_t a_id, const int64_t *b_ids, int B, const double Kinv[9], ProcessedLoopCandidate *pc,
-                              bool *accepted, const uint64_t *seeds = nullptr, chip_match_summary *summaries = nullptr);
+                              bool *accepted, const uint64_t *seeds = nullptr, chip_match_summary *summaries = nullptr,
+                              uint32_t gms_modes = 0, chip_gms_choice *choices = nullptr);
 
 // PoseManipUtils::R2ypr (src/utils/PoseManipUtils.cpp:148-163), degrees, from a column-major 4x4
 void matrix4_to_rawyprt(const double T_colmajor[16], double ypr_deg[3], double t[3]);

@@ -50,7 +50,7 @@ def pinhole(focal=458.0, width=752, height=480):
 
 
 def make_match_scene(n_true=2000, n_outlier_a=200, n_outlier_b=200, flip_rate=0.04, n_duplicates=0, n_border=0, seed=1,
-                     width=752, height=480, focal=458.0, yaw_deg=2.0, t=(0.15, 0.02, 0.05), depth=(3.0, 12.0), all_duplicate=False):
+                     width=752, height=480, focal=458.0, yaw_deg=2.0, t=(0.15, 0.02, 0.05), depth=(3.0, 12.0), all_duplicate=False, roll_deg=0.0):
     """Input of the candidate verification front end (chip_match_pair): two views a, b of ONE random 3-D point cloud with a known
     relative pose b_T_a.  Per view: keypoints (float32 pixels), 256-bit descriptors, the 3-D image (H x W x 3 float32, the point of a
     keypoint stored at its truncated pixel, depth 0 elsewhere -- what the 0.1 m gate drops).
@@ -59,11 +59,15 @@ def make_match_scene(n_true=2000, n_outlier_a=200, n_outlier_b=200, flip_rate=0.
       duplicates  : n_duplicates extra keypoints of b that carry the exact descriptor of an earlier b keypoint (ties: the lowest index wins)
       border      : n_border of a's keypoints sit exactly on cell borders of the GMS grids (x * 20 / width integral or integral + 0.5)
       all_duplicate: every descriptor of both views is the same 32 bytes (every distance 0, every match -> train index 0)
+      roll_deg    : non-zero: view b is also rolled about the optical axis, R = Ry(yaw) . Rz(roll) (what GMS needs its rotation types for)
     Returns dict(a=frame, b=frame, K, Kinv, T=b_T_a (4x4), pairs=(ia, ib) indices of the true pairs); frame = dict(desc, kp, xyz)."""
     rng = np.random.default_rng(seed)
     K, Kinv = pinhole(focal, width, height)
     yaw = np.deg2rad(yaw_deg)
     R = np.array([[np.cos(yaw), 0, np.sin(yaw)], [0, 1, 0], [-np.sin(yaw), 0, np.cos(yaw)]])
+    if roll_deg != 0.0:                                              # only then: with the default every array stays byte-identical
+        roll = np.deg2rad(roll_deg)
+        R = R @ np.array([[np.cos(roll), -np.sin(roll), 0], [np.sin(roll), np.cos(roll), 0], [0, 0, 1]])
     tv = np.asarray(t, np.float64)
     T = np.eye(4); T[:3, :3] = R; T[:3, 3] = tv
     # a's keypoints: distinct integer pixels (one 3-D point per pixel of the 3-D image) + a fraction

@@ -712,6 +712,61 @@ int chip_frame_read(chip_ctx *ctx, int64_t id, int32_t *n, int32_t *width, int32
 int chip_match_batch_stored(chip_ctx *ctx, int64_t a_id, const int64_t *b_ids, int32_t B,
                             const double Kinv_rowmajor[9], chip_match_summary *summary /* B */);
 
+/* ---- GMS with scale and rotation (ABI 7, additive): gms_matcher::GetInlierMask(mask, WithScale, WithRotation), the two booleans of
+ * src/utils/PointFeatureMatching.cpp:52-53, as the bit set `modes`.  modes == 0 is the filter above, byte for byte; the plain form
+ * keeps nothing of a candidate seen under a rolled camera or from half the distance.
+ *
+ * Definitions (restating src/utils/GMSMatcher/gms_matcher.{h,cpp}; everything not named here is as in the block above):
+ *   - scales: index s = 0..4 has the ratios 1, 1/2, 1/sqrt(2), sqrt(2), 2 (gms_matcher.h:47); the right grid side is (int)(20 * ratio)
+ *     with the product in double = 20, 10, 14, 28, 40 (:230-234), N_s = side^2 columns.  Without CHIP_GMS_WITH_SCALE only s = 0.  The
+ *     left grid stays 20 x 20 with its four passes;
+ *   - right cell at scale s: x = floorf(px * (float)side), y alike, index x + y * side (:185-190), no range check on x or y (x = width
+ *     aliases into the next row, as at scale 0).  An index outside [0, N_s) -- where the reference leaves its tables -- has no right
+ *     cell; non-finite or absurd coordinates have none either;
+ *   - per (scale, pass): the 400 x N_s table, the left-cell counts and per non-empty left cell the first column of maximal count;
+ *   - rotation types r = 1..8 (without CHIP_GMS_WITH_ROTATION: r = 1).  Number the 3 x 3 neighbourhood row-major 0..8 and take the
+ *     ring of its eight outer positions clockwise from the top-left: (0, 1, 2, 5, 8, 7, 6, 3).  Pattern r pairs the left neighbour at
+ *     ring position k with the right neighbour at ring position (k - (r - 1)) mod 8, and centre with centre; each step is 45 degrees,
+ *     r = 1 is "same offset on both sides" (gms_matcher.h:12-44, used at gms_matcher.cpp:132-141).  A pair is skipped when either
+ *     neighbour is outside its grid (left 20 x 20, right side x side).  score = sum of table[ll][rr] over the remaining pairs,
+ *     threshold = 6.0 * sqrt(double(sum of cnt[ll]) / double(number of pairs)) over THE SAME pairs -- at a border of either grid both
+ *     depend on the rotation; the left cell is rejected iff (double)score < threshold;
+ *   - mask of (s, r): the OR over the four passes of "my cell pair is the accepted pair of my left cell";
+ *   - choice: s ascending and r ascending inside it, the first (s, r) whose inlier count is strictly greater than every earlier one,
+ *     starting from 0 (gms_matcher.cpp:19-33,38-48,54-66).  If every count is 0 nothing is chosen: the mask is all zero, n_inliers 0,
+ *     scale -1, rotation 0 (the reference leaves the caller's vector untouched, i.e. empty);
+ *   - chip_gms_choice.counts[s][r - 1]: the inlier count of (s, r), -1 for the combinations the modes did not try.  modes == 0:
+ *     scale 0, rotation 1, counts[0][0] = the plain count.  No matches at all (n_matches == 0, an empty query frame or candidate):
+ *     scale -1, rotation 0, 0 for the combinations the modes try;
+ *   - kernels: gms_grid_modes, one workgroup per (scale, pass, candidate), builds table and column search once and scores the
+ *     400 x 8 (left cell, rotation) items; gms_mode_select, one workgroup per candidate, counts the hypotheses, chooses, and writes the
+ *     winner's mask where gms_batch writes its planes, so pose_sets_batch and everything behind run unchanged.  Four launches per
+ *     batch, whatever B, the scales and the rotations;
+ *   - memory: the tables are [B][S][4][400][N_s] int32 -- 2.56 MB per candidate without scale, 19.7 MB with (315 MB at B = 16) --
+ *     plus S x 4 bytes per match, reserved on the first call with modes != 0 inside one pause of the resident scan.  A process that
+ *     never passes modes != 0 allocates nothing of it.
+ * Statuses, limits, selection and state are those of the calls they extend; a bit outside CHIP_GMS_WITH_SCALE | CHIP_GMS_WITH_ROTATION
+ * is CHIP_ERR_INVALID_ARG.  Afterwards candidate 0 is selected, and chip_match_select, chip_match_read_sets,
+ * chip_match_batch_read_matches, chip_pnp_ransac_matched[_batch] and chip_icp_ransac_matched[_batch[_enqueue]] work as after
+ * chip_match_batch.  choice may be NULL.                                                                                            */
+enum { CHIP_GMS_WITH_SCALE = 1, CHIP_GMS_WITH_ROTATION = 2 };
+typedef struct {
+    int32_t scale;            /* 0..4, -1: nothing chosen                                     */
+    int32_t rotation;         /* 1..8,  0: nothing chosen                                     */
+    int32_t n_inliers;
+    int32_t counts[5][8];
+} chip_gms_choice;
+int chip_build_has_gms_modes(void);        /* 1 */
+int chip_gms_filter_modes(chip_ctx *ctx, const float *kp1_xy, int32_t n1, int32_t w1, int32_t h1,
+                          const float *kp2_xy, int32_t n2, int32_t w2, int32_t h2,
+                          const int32_t *query_idx, const int32_t *train_idx, int32_t n_matches, uint32_t modes,
+                          uint8_t *inlier /* n_matches */, int32_t *n_inliers, chip_gms_choice *choice /* or NULL */);
+int chip_match_batch_modes(chip_ctx *ctx, const chip_match_frame *a, const chip_match_frame *b, int32_t B,
+                           const double Kinv_rowmajor[9], uint32_t modes, chip_match_summary *summary /* B */,
+                           chip_gms_choice *choice /* B or NULL */);
+int chip_match_batch_stored_modes(chip_ctx *ctx, int64_t a_id, const int64_t *b_ids, int32_t B, const double Kinv_rowmajor[9],
+                                  uint32_t modes, chip_match_summary *summary /* B */, chip_gms_choice *choice /* B or NULL */);
+
 /* ------------------------------------------------------------------------------------------ introspection */
 typedef struct {
     int32_t abi_version;

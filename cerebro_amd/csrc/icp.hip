@@ -13,11 +13,13 @@
 //                   Both kernels keep the operation order of oracle/icp_ransac.c, so poses, costs and masks are the bits of
 //                   rounds 1-4 (tests/test_icp_gpu.py); the model work per call drops 64-fold (8000 hypotheses: 168 -> see
 //                   profiles/r05_icp.txt), the reference-mode call (<= 50 hypotheses = one wave of icp_models) keeps its latency.
-//   icp_models_batch / icp_score_batch are the same two bodies with a PROBLEM dimension (blockIdx.y; ceil(H / 64) x P and H x P): up
-//   to CHIP_ICP_MAX_BATCH independent estimations -- the 3-D / 3-D sets of all surviving candidates of a keyframe -- share one pair
-//   of launches.  What differs per problem is read from a table in device memory (IcpProblem) through uniform loads; the bits of a
-//   problem depend neither on P nor on its position nor on its neighbours (tests/test_icp_batch_gpu.py).  A single estimation keeps
-//   its own pair, untouched.
+//   The two bodies are stated once, icp_model_lane and icp_score_wave, on a row index and on A / B / N / seed / multipliers handed in.
+//   Two entry pairs call them and differ only in where those per-problem values come from.  icp_models / icp_score: one estimation,
+//   the values travel in the kernel argument block (no table, no copy), row = hypothesis.  icp_models_batch / icp_score_batch add a
+//   PROBLEM dimension (blockIdx.y; ceil(H / 64) x P and H x P): up to CHIP_ICP_MAX_BATCH independent estimations -- the 3-D / 3-D sets
+//   of all surviving candidates of a keyframe -- share one pair of launches, and a wave reads its problem's values from a table in
+//   device memory (IcpProblem) through uniform loads.  The bits of a problem depend neither on P nor on its position nor on its
+//   neighbours (tests/test_icp_batch_gpu.py).
 //   K7 on the host: ransac_common.h (shared with PnP).
 // fp64, -ffp-contract=off, same operation order as oracle/icp_ransac.c => bit-identical poses and masks.
 #include "ransac_common.h"
@@ -27,29 +29,8 @@
 
 namespace chip {
 
-// A single estimation (icp_models / icp_score): everything travels in the kernel argument block.
-struct IcpArgs {
-    const double *A;   // N x 3 (frame a)
-    const double *B;   // N x 3 (frame b)
-    int32_t N, S;
-    uint64_t seed;
-    double thresh;
-    int32_t use_mle;
-    int32_t mask_words;
-    double *T_out;     // [H][16]
-    double *cost;      // [H]
-    int32_t *nin;      // [H]
-    int32_t *valid;    // [H]
-    unsigned long long *mask;  // [H][mask_words]
-    int32_t H;
-    uint64_t magic[kSampleMax];   // floor(2^64 / (N - i)): the sampler's 64-bit modulo as a multiply-high (the divisors depend on i only)
-    const int32_t *sample_in;   // CHIP_SAMPLER_THEIA_PERSISTENT: [H][kSampleMax] sequenced by the host (pinned, device-mapped); else nullptr
-    double *T_dev;     // [H][16] device copy of the models: icp_score reads it (T_out is pinned HOST memory)
-    int32_t *valid_dev;// [H]
-};
-
-// A batched launch (icp_models_batch / icp_score_batch).  IcpLaunch: the per-hypothesis arrays and the parameters all problems share;
-// problem p, hypothesis h has row p * H + h in every array.
+// IcpLaunch: the per-hypothesis arrays and the parameters all problems of a launch share; problem p, hypothesis h has row p * H + h in
+// every array (a single estimation is problem 0).
 struct IcpLaunch {
     int32_t S, H;
     double thresh;
@@ -61,18 +42,24 @@ struct IcpLaunch {
     int32_t *valid;    // [P * H]
     unsigned long long *mask;  // [P * H][mask_words]
     const int32_t *sample_in;   // CHIP_SAMPLER_THEIA_PERSISTENT: [P * H][kSampleMax] sequenced by the host (pinned, device-mapped); else nullptr
-    double *T_dev;     // [P * H][16] device copy of the models: icp_score_batch reads it (T_out is pinned HOST memory)
+    double *T_dev;     // [P * H][16] device copy of the models: the score kernel reads it (T_out is pinned HOST memory)
     int32_t *valid_dev;// [P * H]
 };
-// IcpProblem: what differs between the problems, one row of a table in DEVICE memory (the enqueue copies it there in-stream); a wave
-// reads its row, blockIdx.y, through uniform (scalar) loads.
+// IcpProblem: what differs between the problems
 struct IcpProblem {
     const double *A;   // N x 3 (frame a)
     const double *B;   // N x 3 (frame b)
     int32_t N, pad_;
     uint64_t seed;
-    uint64_t magic[kSampleMax];   // as IcpArgs::magic
+    uint64_t magic[kSampleMax];   // floor(2^64 / (N - i)): the sampler's 64-bit modulo as a multiply-high (the divisors depend on i only)
 };
+// A single estimation (icp_models / icp_score): its problem travels in the kernel argument block
+struct IcpArgs {
+    IcpProblem pr;
+    IcpLaunch l;
+};
+// A batched launch (icp_models_batch / icp_score_batch): one row per problem of a table in DEVICE memory (the enqueue copies it there
+// in-stream); a wave reads its row, blockIdx.y, through uniform (scalar) loads
 struct IcpBatchArgs {
     const IcpProblem *prob;          // [P]
     IcpLaunch l;
@@ -149,132 +136,6 @@ __device__ __forceinline__ void ransac_sample_lane(uint64_t seed, int hyp, int N
     }
 }
 
-__global__ __launch_bounds__(64) void icp_models(IcpArgs a)
-{
-    const int hyp = blockIdx.x * 64 + threadIdx.x;
-    if (hyp >= a.H) return;
-    const int n = a.S;
-    int smp[kSampleMax];
-    if (a.sample_in) {
-#pragma unroll
-        for (int i = 0; i < kSampleMax; i++) smp[i] = i < n ? a.sample_in[(size_t)hyp * kSampleMax + i] : 0;
-    } else {
-        ransac_sample_lane(a.seed, hyp, a.N, n, a.magic, smp);
-    }
-
-    // ---- Umeyama on the sample ----
-    double ma[3] = {0.0, 0.0, 0.0}, mb[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-    for (int i = 0; i < kSampleMax; i++)
-        if (i < n)
-            for (int k = 0; k < 3; k++) { ma[k] = ma[k] + a.A[3 * smp[i] + k]; mb[k] = mb[k] + a.B[3 * smp[i] + k]; }
-    for (int k = 0; k < 3; k++) { ma[k] = ma[k] / (double)n; mb[k] = mb[k] / (double)n; }
-    double Sg[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}}, var_a = 0.0;
-#pragma unroll
-    for (int i = 0; i < kSampleMax; i++)
-        if (i < n) {
-            double da[3], db[3];
-            for (int k = 0; k < 3; k++) { da[k] = a.A[3 * smp[i] + k] - ma[k]; db[k] = a.B[3 * smp[i] + k] - mb[k]; }
-            var_a = var_a + ((da[0] * da[0] + da[1] * da[1]) + da[2] * da[2]);
-            for (int r = 0; r < 3; r++)
-                for (int c = 0; c < 3; c++) Sg[r][c] = Sg[r][c] + db[r] * da[c];
-        }
-    var_a = var_a / (double)n;
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) Sg[r][c] = Sg[r][c] / (double)n;
-    double Am[3][3], V[3][3], w[3], sig[3], U[3][3];
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) {
-            Am[r][c] = (Sg[0][r] * Sg[0][c] + Sg[1][r] * Sg[1][c]) + Sg[2][r] * Sg[2][c];
-            V[r][c] = (r == c) ? 1.0 : 0.0;
-        }
-    for (int sweep = 0; sweep < kJacobiSweeps; sweep++) { JROT(0, 1); JROT(0, 2); JROT(1, 2); }
-    w[0] = Am[0][0]; w[1] = Am[1][1]; w[2] = Am[2][2];
-    // descending selection sort (ties keep the lower index first), same comparisons as the oracle
-    if (w[1] > w[0]) COLSWAP(0, 1);
-    if (w[2] > w[0]) COLSWAP(0, 2);
-    if (w[2] > w[1]) COLSWAP(1, 2);
-    {
-        const double det = V[0][0] * (V[1][1] * V[2][2] - V[1][2] * V[2][1]) - V[0][1] * (V[1][0] * V[2][2] - V[1][2] * V[2][0]) +
-                           V[0][2] * (V[1][0] * V[2][1] - V[1][1] * V[2][0]);
-        if (det < 0.0)
-            for (int r = 0; r < 3; r++) V[r][2] = -V[r][2];
-    }
-    for (int k = 0; k < 3; k++) sig[k] = sqrt(w[k] > 0.0 ? w[k] : 0.0);
-    bool ok = (sig[1] > 1e-6 * sig[0]) && (sig[0] > 0.0);
-    double R[9], t[3], scale = 0.0;
-    for (int e = 0; e < 9; e++) R[e] = 0.0;
-    t[0] = t[1] = t[2] = 0.0;
-    if (ok) {
-        for (int k = 0; k < 2; k++)
-            for (int r = 0; r < 3; r++) U[r][k] = ((Sg[r][0] * V[0][k] + Sg[r][1] * V[1][k]) + Sg[r][2] * V[2][k]) / sig[k];
-        double S22 = 1.0;
-        if (sig[2] > 1e-6 * sig[0]) {
-            for (int r = 0; r < 3; r++) U[r][2] = ((Sg[r][0] * V[0][2] + Sg[r][1] * V[1][2]) + Sg[r][2] * V[2][2]) / sig[2];
-            const double detU = U[0][0] * (U[1][1] * U[2][2] - U[1][2] * U[2][1]) - U[0][1] * (U[1][0] * U[2][2] - U[1][2] * U[2][0]) +
-                                U[0][2] * (U[1][0] * U[2][1] - U[1][1] * U[2][0]);
-            if (detU < 0.0) S22 = -1.0;
-        } else {
-            U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
-            U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
-            U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
-        }
-        for (int r = 0; r < 3; r++)
-            for (int c = 0; c < 3; c++) R[3 * r + c] = (U[r][0] * V[c][0] + U[r][1] * V[c][1]) + (S22 * U[r][2]) * V[c][2];
-        scale = ((sig[0] + sig[1]) + S22 * sig[2]) / var_a;
-        for (int r = 0; r < 3; r++) t[r] = mb[r] - scale * ((R[3 * r] * ma[0] + R[3 * r + 1] * ma[1]) + R[3 * r + 2] * ma[2]);
-        const double inv = 1.0 / scale;
-        ok = (scale < inv ? scale : inv) > 0.9;   // DlsPnpWithRansac.h:137
-    }
-    a.valid_dev[hyp] = ok ? 1 : 0;
-    if (!ok) { a.valid[hyp] = 0; a.nin[hyp] = 0; a.cost[hyp] = INFINITY; return; }
-    double T[16];
-    T[0] = R[0]; T[1] = R[3]; T[2] = R[6]; T[3] = 0.0;
-    T[4] = R[1]; T[5] = R[4]; T[6] = R[7]; T[7] = 0.0;
-    T[8] = R[2]; T[9] = R[5]; T[10] = R[8]; T[11] = 0.0;
-    T[12] = t[0]; T[13] = t[1]; T[14] = t[2]; T[15] = 1.0;
-    for (int e = 0; e < 16; e++) { a.T_dev[(size_t)hyp * 16 + e] = T[e]; a.T_out[(size_t)hyp * 16 + e] = T[e]; }
-}
-
-__global__ __launch_bounds__(64) void icp_score(IcpArgs a)
-{
-    const int lane = threadIdx.x;
-    const int hyp = blockIdx.x;
-    if (!a.valid_dev[hyp]) return;       // wave-uniform; icp_models has written valid / nin / cost of a rejected hypothesis
-    double T[16];
-    for (int e = 0; e < 16; e++) T[e] = a.T_dev[(size_t)hyp * 16 + e];
-    // ---- Error (L2, DlsPnpWithRansac.h:152-164) over all N + MLE cost ----
-    double acc = 0.0;
-    int cnt = 0;
-    for (int base = 0; base < a.N; base += 64) {
-        const int i = base + lane;
-        bool in = false;
-        if (i < a.N) {
-            const double a0 = a.A[3 * i], a1 = a.A[3 * i + 1], a2 = a.A[3 * i + 2];
-            const double x = ((T[0] * a0 + T[4] * a1) + T[8] * a2) + T[12];
-            const double y = ((T[1] * a0 + T[5] * a1) + T[9] * a2) + T[13];
-            const double z = ((T[2] * a0 + T[6] * a1) + T[10] * a2) + T[14];
-            const double dx = x - a.B[3 * i], dy = y - a.B[3 * i + 1], dz = z - a.B[3 * i + 2];
-            const double rr = sqrt((dx * dx + dy * dy) + dz * dz);
-            in = rr < a.thresh;
-            acc = acc + (in ? rr : a.thresh);
-        }
-        const unsigned long long bw = __ballot(in);
-        cnt += __popcll(bw);
-        if (lane == 0) a.mask[(size_t)hyp * a.mask_words + (base >> 6)] = bw;
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) acc = acc + __shfl_xor(acc, m, 64);
-    if (lane == 0) {
-        a.valid[hyp] = 1;
-        a.nin[hyp] = cnt;
-        a.cost[hyp] = a.use_mle ? acc : (double)(a.N - cnt);
-    }
-}
-
-// ---- the batched pair: the two kernels above with a problem dimension.  The single pair stays as it is, instruction for instruction
-// (a single estimation must cost what it cost), so its two bodies are restated here, statement by statement, on a row index and on
-// A / B / N / seed / multipliers handed in.
 // One hypothesis of one problem by ONE lane: sample, Umeyama, scale gate, pose -> row `row` of the launch's arrays.
 __device__ __forceinline__ void icp_model_lane(const double *A, const double *B, int N, uint64_t seed, const uint64_t *magic, int hyp, size_t row,
                                                const IcpLaunch &a)
@@ -362,20 +223,6 @@ __device__ __forceinline__ void icp_model_lane(const double *A, const double *B,
     for (int e = 0; e < 16; e++) { a.T_dev[row * 16 + e] = T[e]; a.T_out[row * 16 + e] = T[e]; }
 }
 
-__global__ __launch_bounds__(64) void icp_models_batch(IcpBatchArgs a)
-{
-    const IcpProblem &pr = a.prob[blockIdx.y];   // wave-uniform: everything read from it stays in scalar registers
-    const double *const A = pr.A, *const B = pr.B;
-    const int N = pr.N;
-    const uint64_t seed = pr.seed;
-    uint64_t magic[kSampleMax];
-#pragma unroll
-    for (int i = 0; i < kSampleMax; i++) magic[i] = pr.magic[i];
-    const int hyp = blockIdx.x * 64 + threadIdx.x;
-    if (hyp >= a.l.H) return;
-    icp_model_lane(A, B, N, seed, magic, hyp, (size_t)blockIdx.y * (size_t)a.l.H + (size_t)hyp, a.l);
-}
-
 // One hypothesis of one problem by ONE wave: the error of all N correspondences under the model in row `row`
 __device__ __forceinline__ void icp_score_wave(const double *A, const double *B, int N, size_t row, const IcpLaunch &a)
 {
@@ -410,6 +257,32 @@ __device__ __forceinline__ void icp_score_wave(const double *A, const double *B,
         a.nin[row] = cnt;
         a.cost[row] = a.use_mle ? acc : (double)(N - cnt);
     }
+}
+
+__global__ __launch_bounds__(64) void icp_models(IcpArgs a)
+{
+    const int hyp = blockIdx.x * 64 + threadIdx.x;
+    if (hyp >= a.l.H) return;
+    icp_model_lane(a.pr.A, a.pr.B, a.pr.N, a.pr.seed, a.pr.magic, hyp, (size_t)hyp, a.l);
+}
+
+__global__ __launch_bounds__(64) void icp_score(IcpArgs a)
+{
+    icp_score_wave(a.pr.A, a.pr.B, a.pr.N, (size_t)blockIdx.x, a.l);
+}
+
+__global__ __launch_bounds__(64) void icp_models_batch(IcpBatchArgs a)
+{
+    const IcpProblem &pr = a.prob[blockIdx.y];   // wave-uniform: everything read from it stays in scalar registers
+    const double *const A = pr.A, *const B = pr.B;
+    const int N = pr.N;
+    const uint64_t seed = pr.seed;
+    uint64_t magic[kSampleMax];
+#pragma unroll
+    for (int i = 0; i < kSampleMax; i++) magic[i] = pr.magic[i];
+    const int hyp = blockIdx.x * 64 + threadIdx.x;
+    if (hyp >= a.l.H) return;
+    icp_model_lane(A, B, N, seed, magic, hyp, (size_t)blockIdx.y * (size_t)a.l.H + (size_t)hyp, a.l);
 }
 
 __global__ __launch_bounds__(64) void icp_score_batch(IcpBatchArgs a)
@@ -535,12 +408,9 @@ static int icp_enqueue_locked(Ctx *c, int P, const double *const *A, const doubl
             }
             l.sample_in = st->res.sample_in.dev();
         }
-        if (P == 1) {   // a single estimation: everything in the argument block, no table, no copy
+        if (P == 1) {   // a single estimation: everything in the argument block, no table, no copy (which costs a call 3 - 4 us: profiles/icp_batch.md)
             IcpArgs a;
-            a.A = tab[0].A; a.B = tab[0].B; a.N = tab[0].N; a.S = S; a.seed = tab[0].seed; a.thresh = l.thresh; a.use_mle = l.use_mle;
-            a.mask_words = words; a.T_out = l.T_out; a.cost = l.cost; a.nin = l.nin; a.valid = l.valid; a.mask = l.mask;
-            a.H = H; a.T_dev = l.T_dev; a.valid_dev = l.valid_dev; a.sample_in = l.sample_in;
-            for (int k = 0; k < kSampleMax; k++) a.magic[k] = tab[0].magic[k];
+            a.pr = tab[0]; a.l = l;
             hipLaunchKernelGGL(icp_models, dim3((H + 63) / 64), dim3(64), 0, s, a);    // lane = hypothesis
             CHIP_HIP(c, hipGetLastError());
             hipLaunchKernelGGL(icp_score, dim3(H), dim3(64), 0, s, a);                 // wave = hypothesis

@@ -66,6 +66,7 @@ SCAN_FAMILY_NAMES = {0: "none", 1: "one_row", 2: "wide", 3: "rows", 4: "multi", 
 CHIP_TICK_SKIPPED, CHIP_TICK_TOO_SHORT, CHIP_TICK_SCANNED = 0, 1, 2
 CHIP_MATCH_MAX_KEYPOINTS = 16384
 CHIP_MATCH_MAX_BATCH = 16
+CHIP_MATCH_MAX_PAIRS = CHIP_MATCH_MAX_BATCH
 CHIP_ICP_MAX_BATCH = 16
 CHIP_ORB_DESC_BYTES = 32
 CHIP_SET_AB, CHIP_SET_BA = 0, 1
@@ -258,6 +259,8 @@ _SIGS = {
     "chip_frame_drop": (C.c_int, [_P, C.c_int64]),
     "chip_frame_read": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P, _P]),
     "chip_match_batch_stored": (C.c_int, [_P, C.c_int64, _P, C.c_int32, _P, C.POINTER(MatchSummary)]),
+    "chip_build_has_match_pairs": (C.c_int, []),
+    "chip_match_pairs_stored": (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_uint32, C.POINTER(MatchSummary), C.POINTER(GmsChoice)]),
     "chip_get_info": (C.c_int, [_P, C.POINTER(Info)]),
     "chip_profile_enable": (C.c_int, [_P, C.c_int32]),
     "chip_profile_reset": (C.c_int, [_P]),
@@ -901,6 +904,8 @@ class Chip:
     def match_batch_matches(self, j: int):
         """-> (train_idx, distance) int32 of candidate j of the last match_batch: the brute-force matches before GMS"""
         n1 = getattr(self, "_match_batch_n1", 0)
+        if isinstance(n1, list):                  # after match_pairs_stored: every pair has a query frame of its own
+            n1 = n1[j] if 0 <= j < len(n1) else 0
         idx = np.full(max(n1, 1), -1, dtype=np.int32)
         dist = np.full(max(n1, 1), -1, dtype=np.int32)
         self._chk(self.lib.chip_match_batch_read_matches(self.h, j, _ptr(idx), _ptr(dist)), "chip_match_batch_read_matches")
@@ -1033,6 +1038,30 @@ class Chip:
         self._match_batch_n1 = n1.value
         summaries = [MatchSummary.from_buffer_copy(sm[j]) for j in range(B)]
         return (summaries, [ch[j].as_dict() for j in range(B)]) if modes is not None else summaries
+
+    def match_pairs_stored(self, a_ids, b_ids, Kinv: np.ndarray, modes=None):
+        """chip_match_pairs_stored: the stored frames a_ids[j] against b_ids[j], pair by pair in the launches of one batch -> what
+        match_batch_stored returns, with the pair index in the place of the candidate's (match_select / match_read_sets /
+        match_batch_matches and the _matched solvers).  modes (or 0): -> (summaries, list of choice dicts)"""
+        ia = np.ascontiguousarray(a_ids, dtype=np.int64).reshape(-1)
+        ib = np.ascontiguousarray(b_ids, dtype=np.int64).reshape(-1)
+        if len(ia) != len(ib):
+            raise ValueError("match_pairs_stored: a_ids and b_ids differ in length")
+        P = len(ia)
+        Ki = np.ascontiguousarray(Kinv, dtype=np.float64).reshape(9)
+        sm = (MatchSummary * max(P, 1))()
+        ch = (GmsChoice * max(P, 1))()
+        self._match_batch_n1 = 0
+        self._chk(self.lib.chip_match_pairs_stored(self.h, _ptr(ia) if P else None, _ptr(ib) if P else None, P, _ptr(Ki), modes or 0, sm, ch),
+                  "chip_match_pairs_stored")
+        n1 = []
+        for a in ia:
+            n = C.c_int32()
+            self._chk(self.lib.chip_frame_read(self.h, int(a), C.byref(n), None, None, None, None, None), "chip_frame_read")
+            n1.append(n.value)
+        self._match_batch_n1 = n1
+        summaries = [MatchSummary.from_buffer_copy(sm[j]) for j in range(P)]
+        return (summaries, [ch[j].as_dict() for j in range(P)]) if modes is not None else summaries
 
     # -- introspection / profiling
     def info(self) -> dict:

@@ -24,6 +24,10 @@
 // There is ONE device pipeline, match_run: one query frame against B <= 16 candidates through hamming_match_split, gms_batch and
 // pose_sets_batch.  chip_match_batch is that; chip_match_pair is a batch of one; chip_orb_match is the first kernel alone with one
 // candidate and keys of its own.  gms_filter serves chip_gms_filter alone (an arbitrary match list, which the keys cannot express).
+// chip_match_pairs_stored runs the same pipeline on a LIST of (query, candidate) pairs of stored frames, every pair with a query frame
+// of its own: hamming_match_pairs, pairs_gms (with GMS modes pairs_grid_modes + pairs_mode_select) and pose_sets_stored_pairs are the
+// bodies of the kernels above -- each stated once as a __device__ function -- with the pair's query frame taken from a second table in
+// the kernel arguments, and with a count (the pair's own keypoints) apart from the stride of the rows (the widest query of the list).
 //
 // Nothing here rounds twice: float division / multiplication, the float -> double widenings, fp64 add / multiply / divide / sqrt are
 // single IEEE operations (-ffp-contract=off), the rest is integer.  tests/np_mirror_match.py restates all of it in numpy and
@@ -323,14 +327,14 @@ struct BatchCands { BatchCand c[kMaxBatch]; };
 // All ones (the preset) decodes to index -1, distance -1: no train descriptors.
 __device__ __forceinline__ int32_t key_train(unsigned long long k) { return (int32_t)(uint32_t)k; }
 
-// grid (query blocks of 256, train tiles of 1024, B): one workgroup scans ONE tile; a tile past the candidate's n leaves at once
-__global__ __launch_bounds__(kBfThreads) void hamming_match_split(const uint4 *__restrict__ query, int n1, BatchCands cands,
-                                                                  unsigned long long *__restrict__ keys /* [B][n1] */)
+// One workgroup of kBfThreads: query block blockIdx.x of the n1 >= 1 query descriptors against train tile blockIdx.y of the n2 train
+// descriptors, merged into keys[0 .. n1), the row of this (query frame, candidate); a tile past n2 leaves at once
+__device__ __forceinline__ void hamming_tile(const uint4 *__restrict__ query, int n1, const uint4 *__restrict__ train, int n2,
+                                             unsigned long long *__restrict__ keys)
 {
     __shared__ uint4 tile[2 * kBfTile];
-    const int z = blockIdx.z, base = blockIdx.y * kBfTile, n2 = cands.c[z].n;
+    const int base = blockIdx.y * kBfTile;
     if (base >= n2) return;                                   // workgroup-uniform
-    const uint4 *__restrict__ train = cands.c[z].desc;
     const int cnt = n2 - base < kBfTile ? n2 - base : kBfTile;
     const int i = blockIdx.x * kBfThreads + threadIdx.x;
     const int qi = i < n1 ? i : n1 - 1;                       // n1 >= 1: the tail lanes scan a valid descriptor and store nothing
@@ -346,8 +350,36 @@ __global__ __launch_bounds__(kBfThreads) void hamming_match_split(const uint4 *_
         if (d < best) { best = d; bidx = base + j; }          // strict: the first minimum of the tile stays
     }
     if (i < n1)                                               // cnt >= 1: bidx >= 0.  One native 64-bit unsigned minimum per lane and tile
-        __hip_atomic_fetch_min(&keys[(size_t)z * n1 + i], ((unsigned long long)(uint32_t)best << 32) | (uint32_t)bidx, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_min(&keys[i], ((unsigned long long)(uint32_t)best << 32) | (uint32_t)bidx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// grid (query blocks of 256, train tiles of 1024, B): one workgroup scans ONE tile; a tile past the candidate's n leaves at once
+__global__ __launch_bounds__(kBfThreads) void hamming_match_split(const uint4 *__restrict__ query, int n1, BatchCands cands,
+                                                                  unsigned long long *__restrict__ keys /* [B][n1] */)
+{
+    const int z = blockIdx.z;
+    hamming_tile(query, n1, cands.c[z].desc, cands.c[z].n, keys + (size_t)z * n1);
+}
+
+// ---- a list of (query, candidate) pairs: pair z carries its query frame next to its candidate, a second table in the kernel arguments
+// read through wave-uniform loads like the first.  Keys, planes and slabs are rows of `stride` = the largest query of the list per pair;
+// pair z uses the first q[z].n of its row.  A pair with an empty frame on either side has n = 0 in BOTH tables and takes no part.
+struct PairQuery {
+    const uint4 *desc;            // n x 2
+    const float2 *kp;             // n
+    const float4 *rec;            // n: the point records (frame_gather)
+    int32_t n, w, h, pad_;
+};
+struct PairQueries { PairQuery q[kMaxBatch]; };
+
+// grid (query blocks of 256 over the stride, train tiles of 1024, P): a workgroup whose query block starts at or beyond its own pair's
+// n1, or whose tile starts beyond its n2, leaves at once -- both tests are workgroup-uniform and come before the barrier
+__global__ __launch_bounds__(kBfThreads) void hamming_match_pairs(PairQueries qs, BatchCands cands, int stride,
+                                                                  unsigned long long *__restrict__ keys /* [P][stride] */)
+{
+    const int z = blockIdx.z, n1 = qs.q[z].n;
+    if ((int)(blockIdx.x * kBfThreads) >= n1) return;
+    hamming_tile(qs.q[z].desc, n1, cands.c[z].desc, cands.c[z].n, keys + (size_t)z * stride);
 }
 
 struct GmsBatchArgs {
@@ -371,6 +403,27 @@ __global__ __launch_bounds__(kOneWg) void gms_batch(GmsBatchArgs a)
              [&](int i, bool hit) { plane[i] = hit ? 1 : 0; });
 }
 
+struct GmsPairsArgs {
+    const unsigned long long *keys;       // [P][stride]
+    int32_t *table;                       // [P][4][400][400]
+    uint8_t *plane;                       // [P][4][stride]
+    int32_t stride;
+    PairQueries qs;
+    BatchCands cands;
+};
+// grid (4 grid types, P): gms_batch with the pair's own query keypoints, count and image size
+__global__ __launch_bounds__(kOneWg) void pairs_gms(GmsPairsArgs a)
+{
+    const int type = blockIdx.x + 1, z = blockIdx.y;
+    if (a.cands.c[z].n == 0) return;                          // no matches: pose_sets_stored_pairs does not read this pair's planes
+    const float2 *kp1 = a.qs.q[z].kp, *kp2 = a.cands.c[z].kp;
+    const unsigned long long *keys = a.keys + (size_t)z * a.stride;
+    uint8_t *plane = a.plane + ((size_t)z * 4 + blockIdx.x) * a.stride;
+    gms_pass(type, a.qs.q[z].n, a.table + ((size_t)z * 4 + blockIdx.x) * (kCells * kCells), (float)a.qs.q[z].w, (float)a.qs.q[z].h,
+             (float)a.cands.c[z].w, (float)a.cands.c[z].h, [&](int i, float2 *lp, float2 *rp) { *lp = kp1[i]; *rp = kp2[key_train(keys[i])]; },
+             [&](int i, bool hit) { plane[i] = hit ? 1 : 0; });
+}
+
 struct SetsBatchArgs {
     const float2 *kp1;
     const float *xyz_a;
@@ -383,21 +436,27 @@ struct SetsBatchArgs {
     int32_t *counts;                      // [B][kNSets]
     BatchCands cands;
 };
-// the sets of candidate z, inlier = the OR of its four planes, outputs into its slabs
+// the sets of candidate z, inlier = the OR of its four planes, outputs into its slabs: n matches of the query keypoints kp1 in rows of
+// `stride` (one query frame: n = stride = b.n1; a pair list: the pair's own n and kp1)
 template <class Points>
-__device__ __forceinline__ void pose_sets_candidate(const SetsBatchArgs &b, int z, const Points &pts)
+__device__ __forceinline__ void pose_sets_rows(const SetsBatchArgs &b, int z, const float2 *kp1, int n, size_t stride, const Points &pts)
 {
-    const size_t row = (size_t)z * b.n1;
+    const size_t row = (size_t)z * stride;
     SetsArgs a;
-    a.kp1 = b.kp1; a.kp2 = b.cands.c[z].kp; a.n = b.n1;
+    a.kp1 = kp1; a.kp2 = b.cands.c[z].kp; a.n = n;
     for (int k = 0; k < 9; k++) a.Kinv[k] = b.Kinv[k];
     a.uv = b.uv + 2 * row; a.uv_d = b.uv_d + 2 * row; a.X_ab = b.X_ab + 3 * row; a.uvn_ab = b.uvn_ab + 2 * row;
     a.X_ba = b.X_ba + 3 * row; a.uvn_ba = b.uvn_ba + 2 * row; a.A = b.A + 3 * row; a.B = b.B + 3 * row;
     a.mq = b.mq + row; a.mt = b.mt + row; a.counts = b.counts + z * kNSets;
     const unsigned long long *keys = b.keys + row;
     const uint8_t *p = b.plane + 4 * row;
-    const size_t n1 = (size_t)b.n1;
-    pose_sets_body(a, [&](int i) { return (p[i] | p[n1 + i] | p[2 * n1 + i] | p[3 * n1 + i]) != 0; }, [&](int i) { return key_train(keys[i]); }, pts);
+    pose_sets_body(a, [&](int i) { return (p[i] | p[stride + i] | p[2 * stride + i] | p[3 * stride + i]) != 0; },
+                   [&](int i) { return key_train(keys[i]); }, pts);
+}
+template <class Points>
+__device__ __forceinline__ void pose_sets_candidate(const SetsBatchArgs &b, int z, const Points &pts)
+{
+    pose_sets_rows(b, z, b.kp1, b.n1, (size_t)b.n1, pts);
 }
 // grid B: candidate blockIdx.x on the 3-D images of the two frames
 __global__ __launch_bounds__(kOneWg) void pose_sets_batch(SetsBatchArgs b)
@@ -448,6 +507,20 @@ __global__ __launch_bounds__(kOneWg) void pose_sets_stored_batch(SetsStoredArgs 
     }
     pose_sets_candidate(s.b, z, RecordPoints{s.rec_a, s.rec[z]});
 }
+// the same for a pair list: s.b.n1 is the stride, s.b.kp1 and s.rec_a are not read, pair z has its query in qs.q[z]
+struct SetsPairsArgs {
+    SetsStoredArgs s;
+    PairQueries qs;
+};
+__global__ __launch_bounds__(kOneWg) void pose_sets_stored_pairs(SetsPairsArgs p)
+{
+    const int z = blockIdx.x;
+    if (p.s.b.cands.c[z].n == 0) {
+        if (threadIdx.x < kNSets) p.s.b.counts[z * kNSets + threadIdx.x] = 0;
+        return;
+    }
+    pose_sets_rows(p.s.b, z, p.qs.q[z].kp, p.qs.q[z].n, (size_t)p.s.b.n1, RecordPoints{p.qs.q[z].rec, p.s.rec[z]});
+}
 
 // ------------------------------------------------------------------------------------------------ GMS with scale and rotation
 // gms_matcher::GetInlierMask(.., WithScale, WithRotation) (gms_matcher.cpp:17-68): run(RotationType) under SetScale(Scale) for up to
@@ -484,8 +557,9 @@ struct GmsModesArgs {
     int32_t n_scales, n_rot;              // 1 or 5, 1 or 8
     BatchCands cands;                     // kp, n, w, h of the candidates
 };
-// grid (4 grid types x S scales, B)
-__global__ __launch_bounds__(kOneWg) void gms_grid_modes(GmsModesArgs a)
+// One workgroup of kOneWg threads: (scale, grid type) blockIdx.x of candidate blockIdx.y on n matches of the query keypoints kp1 (image
+// w1 x h1), planes and keys in rows of `stride` (one query frame: a's own kp1, n = stride = a.n, w1, h1; a pair list: the pair's)
+__device__ __forceinline__ void gms_grid_modes_body(const GmsModesArgs &a, const float2 *kp1, int n, size_t stride, int w1, int h1)
 {
     __shared__ int32_t cnt[kCells];      // mNumberPointsInPerCellLeft
     __shared__ int32_t pair[kCells];     // mCellPairs before the threshold: the first column of maximal count, -1 for an empty row
@@ -493,17 +567,17 @@ __global__ __launch_bounds__(kOneWg) void gms_grid_modes(GmsModesArgs a)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int s = blockIdx.x >> 2, type = (blockIdx.x & 3) + 1, z = blockIdx.y;
     if (a.cands.c[z].n == 0) return;                          // no matches: gms_mode_select does not read this candidate's planes
-    const int side = mode_side(s), N = side * side, n = a.n;
+    const int side = mode_side(s), N = side * side;
     const size_t per_cand = (size_t)4 * kCells * mode_cols_before(a.n_scales);
     int32_t *table = a.table + (size_t)z * per_cand + (size_t)4 * kCells * mode_cols_before(s) + (size_t)(type - 1) * kCells * N;
-    uint8_t *plane = a.plane + (((size_t)z * a.n_scales + s) * 4 + (type - 1)) * (size_t)n;
+    uint8_t *plane = a.plane + (((size_t)z * a.n_scales + s) * 4 + (type - 1)) * stride;
     const float2 *kp2 = a.cands.c[z].kp;
-    const unsigned long long *keys = a.keys ? a.keys + (size_t)z * n : nullptr;
-    const float fw1 = (float)a.w1, fh1 = (float)a.h1, fw2 = (float)a.cands.c[z].w, fh2 = (float)a.cands.c[z].h;
+    const unsigned long long *keys = a.keys ? a.keys + (size_t)z * stride : nullptr;
+    const float fw1 = (float)w1, fh1 = (float)h1, fw2 = (float)a.cands.c[z].w, fh2 = (float)a.cands.c[z].h;
     const bool listed = a.qidx != nullptr;                    // uniform
     // the cell pair of match i under this (scale, grid type); NormalizePoints (gms_matcher.h:126-139): one float division per coordinate
     const auto cells = [&](int i, int *l, int *r) {
-        const float2 lp = a.kp1[listed ? a.qidx[i] : i], rp = kp2[listed ? a.tidx[i] : key_train(keys[i])];
+        const float2 lp = kp1[listed ? a.qidx[i] : i], rp = kp2[listed ? a.tidx[i] : key_train(keys[i])];
         *l = gms_cell_left(__fdiv_rn(lp.x, fw1), __fdiv_rn(lp.y, fh1), type);
         *r = mode_cell_right(__fdiv_rn(rp.x, fw2), __fdiv_rn(rp.y, fh2), side);
     };
@@ -569,6 +643,21 @@ __global__ __launch_bounds__(kOneWg) void gms_grid_modes(GmsModesArgs a)
         plane[i] = l >= 0 && r >= 0 && pair[l] == r ? (uint8_t)acc[l] : (uint8_t)0;
     }
 }
+// grid (4 grid types x S scales, B)
+__global__ __launch_bounds__(kOneWg) void gms_grid_modes(GmsModesArgs a)
+{
+    gms_grid_modes_body(a, a.kp1, a.n, (size_t)a.n, a.w1, a.h1);
+}
+// grid (4 grid types x S scales, P) on a pair list: a.n is the stride, a.kp1 / w1 / h1 are not read, a.qidx / tidx are null
+struct GmsModesPairsArgs {
+    GmsModesArgs a;
+    PairQueries qs;
+};
+__global__ __launch_bounds__(kOneWg) void pairs_grid_modes(GmsModesPairsArgs p)
+{
+    const PairQuery &q = p.qs.q[blockIdx.y];
+    gms_grid_modes_body(p.a, q.kp, q.n, (size_t)p.a.n, q.w, q.h);
+}
 
 struct GmsSelectArgs {
     const uint8_t *plane;                 // [B][S][4][n] of gms_grid_modes
@@ -579,22 +668,24 @@ struct GmsSelectArgs {
     chip_gms_choice *choice;              // [B]
     int32_t live[kMaxBatch];              // 0: an empty candidate, nothing to read or write but the choice
 };
-// grid B: the counts of the S x R hypotheses of candidate blockIdx.x, the choice (gms_matcher.cpp:19-33,38-48,54-66) and the winner's mask
-__global__ __launch_bounds__(kOneWg) void gms_mode_select(GmsSelectArgs a)
+// One workgroup of kOneWg threads: the counts of the S x R hypotheses of candidate blockIdx.x over its n matches, the choice
+// (gms_matcher.cpp:19-33,38-48,54-66) and the winner's mask; the planes and the zeroed slots are rows of `stride` (a pair list: n is
+// the pair's own count, otherwise n = stride = a.n)
+__device__ __forceinline__ void gms_mode_select_body(const GmsSelectArgs &a, int n, size_t stride)
 {
     __shared__ int32_t counts[kScales * kRotations];
     __shared__ int32_t win[2];
-    const int tid = threadIdx.x, lane = tid & 63, z = blockIdx.x, n = a.n;
+    const int tid = threadIdx.x, lane = tid & 63, z = blockIdx.x;
     const bool live = a.live[z] != 0;                        // uniform
     if (tid < kScales * kRotations) counts[tid] = (tid >> 3) < a.n_scales && (tid & 7) < a.n_rot ? 0 : -1;
     __syncthreads();
-    const uint8_t *planes = a.plane + (size_t)z * a.n_scales * 4 * (size_t)n;
+    const uint8_t *planes = a.plane + (size_t)z * a.n_scales * 4 * stride;
     for (int s = 0; live && s < a.n_scales; s++) {
-        const uint8_t *p = planes + (size_t)s * 4 * (size_t)n;
+        const uint8_t *p = planes + (size_t)s * 4 * stride;
         int mine[kRotations] = {0, 0, 0, 0, 0, 0, 0, 0};    // wave-uniform
         for (int base = 0; base < n; base += kOneWg) {
             const int i = base + tid;
-            const int b = i < n ? p[i] | p[(size_t)n + i] | p[2 * (size_t)n + i] | p[3 * (size_t)n + i] : 0;
+            const int b = i < n ? p[i] | p[stride + i] | p[2 * stride + i] | p[3 * stride + i] : 0;
 #pragma unroll
             for (int r = 0; r < kRotations; r++) mine[r] += __popcll(__ballot((b >> r) & 1));
         }
@@ -619,12 +710,26 @@ __global__ __launch_bounds__(kOneWg) void gms_mode_select(GmsSelectArgs a)
     if (!live) return;
     uint8_t *out = a.mask + (size_t)z * a.mask_stride;
     const int ws = win[0], shift = ws >= 0 ? win[1] - 1 : 0;
-    const uint8_t *p = planes + (size_t)(ws < 0 ? 0 : ws) * 4 * (size_t)n;
+    const uint8_t *p = planes + (size_t)(ws < 0 ? 0 : ws) * 4 * stride;
     for (int i = tid; i < n; i += kOneWg) {
-        const int b = p[i] | p[(size_t)n + i] | p[2 * (size_t)n + i] | p[3 * (size_t)n + i];
+        const int b = p[i] | p[stride + i] | p[2 * stride + i] | p[3 * stride + i];
         out[i] = ws >= 0 ? (uint8_t)((b >> shift) & 1) : (uint8_t)0;   // no choice: the mask is all zero
-        if (a.zero_slots) out[(size_t)n + i] = out[2 * (size_t)n + i] = out[3 * (size_t)n + i] = 0;
+        if (a.zero_slots) out[stride + i] = out[2 * stride + i] = out[3 * stride + i] = 0;
     }
+}
+// grid B
+__global__ __launch_bounds__(kOneWg) void gms_mode_select(GmsSelectArgs a)
+{
+    gms_mode_select_body(a, a.n, (size_t)a.n);
+}
+// grid P on a pair list: a.n is the stride, n[z] the count of pair z
+struct GmsSelectPairsArgs {
+    GmsSelectArgs a;
+    int32_t n[kMaxBatch];
+};
+__global__ __launch_bounds__(kOneWg) void pairs_mode_select(GmsSelectPairsArgs p)
+{
+    gms_mode_select_body(p.a, p.n[blockIdx.x], (size_t)p.a.n);
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -672,7 +777,8 @@ struct MatchState {
     bool have_sets = false;
     bool keys_readable = false;                 // API behaviour, not a buffer selector: chip_match_batch_read_matches answers only after a
                                                 // chip_match_batch, CHIP_ERR_BUSY after a chip_match_pair
-    int32_t n_cand = 0, n1 = 0;
+    int32_t n_cand = 0, n1 = 0;                 // n1: the rows of a candidate's slab = the query frame's keypoints (a pair list: the most)
+    int32_t cand_n1[CHIP_MATCH_MAX_BATCH] = {}; // the query keypoints of candidate j: n1, on a pair list the pair's own
     chip_match_summary cand_sm[CHIP_MATCH_MAX_BATCH] = {};
     chip_gms_choice cand_choice[CHIP_MATCH_MAX_BATCH] = {};   // of the last run, whatever its modes
     Sets cur{};
@@ -803,7 +909,10 @@ struct RunFrames {
     BatchCands cands;
     const float4 *rec[kMaxBatch];
     int32_t max_n2 = 0;
-    RunFrames() { std::memset(&cands, 0, sizeof cands); std::memset(rec, 0, sizeof rec); }
+    // a pair list (stored frames only): n1 is the stride, desc_a / kp_a / rec_a / w1 / h1 are unused and pair j has its query in qs.q[j]
+    bool pairs = false;
+    PairQueries qs;
+    RunFrames() { std::memset(&cands, 0, sizeof cands); std::memset(rec, 0, sizeof rec); std::memset(&qs, 0, sizeof qs); }
 };
 
 // tuning only (CHIP_MATCH_BATCH_TIMING=1): device time of each kernel of a run by events, averaged, printed at process exit; runs on
@@ -815,6 +924,7 @@ struct KernelTiming {
     double acc[4] = {0, 0, 0, 0}; long n = 0; bool on = std::getenv("CHIP_MATCH_BATCH_TIMING") != nullptr;
     KernelTiming(const char *w, const char *sets) : what(w), name{"hamming_match_split", "gms_batch", sets, nullptr}, k(3) {}
     KernelTiming(const char *w, const char *sets, bool) : what(w), name{"hamming_match_split", "gms_grid_modes", "gms_mode_select", sets}, k(4) {}
+    KernelTiming(const char *w, const char *n0, const char *n1, const char *n2, const char *n3) : what(w), name{n0, n1, n2, n3}, k(n3 ? 4 : 3) {}
     ~KernelTiming()
     {
         if (!on || !n) return;
@@ -852,27 +962,42 @@ static int modes_reserve(Ctx *c, MatchState *st, size_t B, int S, size_t n)
     if (rc == CHIP_OK) rc = st->h_choice.reserve(c, kMaxBatch);
     return rc;
 }
-// the two launches of the mode on B candidates of n matches: ga filled but for table / plane / n_scales / n_rot
+// the two launches of the mode on B candidates of n matches: ga filled but for table / plane / n_scales / n_rot.  qs: a pair list, ga.n
+// is then the stride and pair j has qs->q[j].n matches
 static int launch_modes(Ctx *c, MatchState *st, hipStream_t s, GmsModesArgs &ga, int B, uint32_t modes, uint8_t *mask, size_t mask_stride,
-                        bool zero_slots, hipEvent_t between)
+                        bool zero_slots, hipEvent_t between, const PairQueries *qs = nullptr)
 {
     ga.n_scales = modes & CHIP_GMS_WITH_SCALE ? kScales : 1;
     ga.n_rot = modes & CHIP_GMS_WITH_ROTATION ? kRotations : 1;
     ga.table = st->mode_table; ga.plane = st->mode_plane;
-    hipLaunchKernelGGL(gms_grid_modes, dim3(4 * ga.n_scales, B), dim3(kOneWg), 0, s, ga);
+    if (qs) {
+        GmsModesPairsArgs gp;
+        gp.a = ga; gp.qs = *qs;
+        hipLaunchKernelGGL(pairs_grid_modes, dim3(4 * ga.n_scales, B), dim3(kOneWg), 0, s, gp);
+    } else {
+        hipLaunchKernelGGL(gms_grid_modes, dim3(4 * ga.n_scales, B), dim3(kOneWg), 0, s, ga);
+    }
     CHIP_HIP(c, hipGetLastError());
     if (between) CHIP_HIP(c, hipEventRecord(between, s));
     GmsSelectArgs sa;
     sa.plane = st->mode_plane; sa.n = ga.n; sa.n_scales = ga.n_scales; sa.n_rot = ga.n_rot;
     sa.mask = mask; sa.mask_stride = mask_stride; sa.zero_slots = zero_slots ? 1 : 0; sa.choice = st->mode_choice;
     for (int j = 0; j < kMaxBatch; j++) sa.live[j] = j < B && ga.cands.c[j].n > 0;
-    hipLaunchKernelGGL(gms_mode_select, dim3(B), dim3(kOneWg), 0, s, sa);
+    if (qs) {
+        GmsSelectPairsArgs sp;
+        sp.a = sa;
+        for (int j = 0; j < kMaxBatch; j++) sp.n[j] = qs->q[j].n;
+        hipLaunchKernelGGL(pairs_mode_select, dim3(B), dim3(kOneWg), 0, s, sp);
+    } else {
+        hipLaunchKernelGGL(gms_mode_select, dim3(B), dim3(kOneWg), 0, s, sa);
+    }
     CHIP_HIP(c, hipGetLastError());
     return CHIP_OK;
 }
 
 // The device part of a run, for both kinds of frames (f.n1 >= 1, the slabs reserved): the keys preset, three launches (with GMS modes
 // four: gms_grid_modes + gms_mode_select in the place of gms_batch), the counts back, cand_sm[0 .. B) and cand_choice[0 .. B) filled.
+// A pair list (f.pairs) takes the _pairs form of every kernel: the same launches, f.n1 the stride of the rows.
 static int match_launch(Ctx *c, MatchState *st, hipStream_t s, const RunFrames &f, int B, const double Kinv[9], uint32_t modes)
 {
     const int n1 = f.n1;
@@ -884,20 +1009,34 @@ static int match_launch(Ctx *c, MatchState *st, hipStream_t s, const RunFrames &
     if (f.max_n2 > 0) {
         static KernelTiming kt_host("match batch", "pose_sets_batch"), kt_stored("match batch stored", "pose_sets_stored_batch");
         static KernelTiming km_host("match batch modes", "pose_sets_batch", true), km_stored("match batch stored modes", "pose_sets_stored_batch", true);
-        KernelTiming &kt = modes ? (f.stored ? km_stored : km_host) : (f.stored ? kt_stored : kt_host);
+        static KernelTiming kt_pairs("match pairs stored", "hamming_match_pairs", "pairs_gms", "pose_sets_stored_pairs", nullptr);
+        static KernelTiming km_pairs("match pairs stored modes", "hamming_match_pairs", "pairs_grid_modes", "pairs_mode_select", "pose_sets_stored_pairs");
+        KernelTiming &kt = f.pairs ? (modes ? km_pairs : kt_pairs) : modes ? (f.stored ? km_stored : km_host) : (f.stored ? kt_stored : kt_host);
         const int last = kt.k;                   // ev[last]: after the sets kernel
         if (kt.on)
             for (hipEvent_t &e : st->ev)
                 if (!e) CHIP_HIP(c, hipEventCreate(&e));
         if (kt.on) CHIP_HIP(c, hipEventRecord(st->ev[0], s));
-        int rc = launch_matcher(c, s, f.desc_a, n1, f.cands, f.max_n2, B, st->keys);
-        if (rc != CHIP_OK) return rc;
+        int rc = CHIP_OK;
+        if (f.pairs) {
+            hipLaunchKernelGGL(hamming_match_pairs, dim3((n1 + kBfThreads - 1) / kBfThreads, (f.max_n2 + kBfTile - 1) / kBfTile, B), dim3(kBfThreads), 0,
+                               s, f.qs, f.cands, n1, st->keys.get());
+            CHIP_HIP(c, hipGetLastError());
+        } else {
+            rc = launch_matcher(c, s, f.desc_a, n1, f.cands, f.max_n2, B, st->keys);
+            if (rc != CHIP_OK) return rc;
+        }
         if (kt.on) CHIP_HIP(c, hipEventRecord(st->ev[1], s));
         if (modes) {                             // the winner's mask goes where gms_batch's planes go: slot 0 the mask, slots 1-3 zero
             GmsModesArgs ma;
             ma.kp1 = f.kp_a; ma.n = n1; ma.w1 = f.w1; ma.h1 = f.h1; ma.keys = st->keys; ma.qidx = ma.tidx = nullptr; ma.cands = f.cands;
-            rc = launch_modes(c, st, s, ma, B, modes, st->plane, 4 * (size_t)n1, true, kt.on ? st->ev[2] : nullptr);
+            rc = launch_modes(c, st, s, ma, B, modes, st->plane, 4 * (size_t)n1, true, kt.on ? st->ev[2] : nullptr, f.pairs ? &f.qs : nullptr);
             if (rc != CHIP_OK) return rc;
+        } else if (f.pairs) {
+            GmsPairsArgs ga;
+            ga.keys = st->keys; ga.table = st->table; ga.plane = st->plane; ga.stride = n1; ga.qs = f.qs; ga.cands = f.cands;
+            hipLaunchKernelGGL(pairs_gms, dim3(4, B), dim3(kOneWg), 0, s, ga);
+            CHIP_HIP(c, hipGetLastError());
         } else {
             GmsBatchArgs ga;
             ga.kp1 = f.kp_a; ga.n1 = n1; ga.w1 = f.w1; ga.h1 = f.h1; ga.keys = st->keys; ga.table = st->table; ga.plane = st->plane;
@@ -915,7 +1054,13 @@ static int match_launch(Ctx *c, MatchState *st, hipStream_t s, const RunFrames &
         if (f.stored) {
             ss.rec_a = f.rec_a;
             for (int j = 0; j < kMaxBatch; j++) ss.rec[j] = f.rec[j];
-            hipLaunchKernelGGL(pose_sets_stored_batch, dim3(B), dim3(kOneWg), 0, s, ss);
+            if (f.pairs) {
+                SetsPairsArgs sp;
+                sp.s = ss; sp.qs = f.qs;
+                hipLaunchKernelGGL(pose_sets_stored_pairs, dim3(B), dim3(kOneWg), 0, s, sp);
+            } else {
+                hipLaunchKernelGGL(pose_sets_stored_batch, dim3(B), dim3(kOneWg), 0, s, ss);
+            }
         } else {
             hipLaunchKernelGGL(pose_sets_batch, dim3(B), dim3(kOneWg), 0, s, sa);
         }
@@ -938,7 +1083,7 @@ static int match_launch(Ctx *c, MatchState *st, hipStream_t s, const RunFrames &
         if (modes) st->cand_choice[j] = st->h_choice.host()[j];
         else choice_plain(&st->cand_choice[j], h[kSetUv]);
         chip_match_summary &sm = st->cand_sm[j];
-        sm.n_matches_all = n1;
+        sm.n_matches_all = f.pairs ? f.qs.q[j].n : n1;
         sm.n_matches_gms = h[kSetUv]; sm.n_3d2d_ab = h[kSetAb]; sm.n_3d2d_ba = h[kSetBa]; sm.n_3d3d = h[kSet33]; sm.n_out_of_image = h[kSetOut];
     }
     return CHIP_OK;
@@ -949,6 +1094,7 @@ static void match_finish(MatchState *st, int B, int n1)
 {
     st->n_cand = B;
     st->n1 = n1;
+    for (int j = 0; j < B; j++) st->cand_n1[j] = n1;
     st->select(0);
     st->have_sets = true;
 }
@@ -1034,6 +1180,41 @@ static int match_run_stored(Ctx *c, MatchState *st, int32_t sa, const int32_t *s
         if (rc != CHIP_OK) return rc;
     }
     match_finish(st, B, a.n);
+    return CHIP_OK;
+}
+
+// The pipeline on a list of stored pairs: slot sa[j] against slot sb[j], every pair with a query frame of its own, in the same three
+// (four) launches.  The rows of keys, planes and slabs have the stride of the widest query frame; a pair with an empty frame on either
+// side takes no part.  Same state afterwards as match_run, with the pair index in the place of the candidate's.
+static int match_run_pairs_stored(Ctx *c, MatchState *st, const int32_t *sa, const int32_t *sb, int P, const double Kinv[9], uint32_t modes)
+{
+    int rc0 = icp_wait_matched(c);               // as match_run
+    if (rc0 != CHIP_OK) return rc0;
+    const size_t kp = (size_t)st->slot_kp;
+    RunFrames f;
+    f.stored = f.pairs = true;
+    int32_t n_a[kMaxBatch];
+    for (int j = 0; j < P; j++) {
+        const MatchState::StoredFrame &a = st->slots[(size_t)sa[j]], &b = st->slots[(size_t)sb[j]];
+        std::memset(&st->cand_sm[j], 0, sizeof(chip_match_summary));
+        choice_none(&st->cand_choice[j], modes);
+        n_a[j] = a.n;
+        f.n1 = a.n > f.n1 ? a.n : f.n1;          // the stride counts an empty candidate's query too: its keys are readable (all -1)
+        if (a.n == 0 || b.n == 0) continue;
+        const size_t at_a = (size_t)sa[j] * kp, at_b = (size_t)sb[j] * kp;
+        f.max_n2 = b.n > f.max_n2 ? b.n : f.max_n2;
+        f.qs.q[j] = PairQuery{reinterpret_cast<const uint4 *>(st->store_desc + at_a * CHIP_ORB_DESC_BYTES), st->store_kp + at_a, st->store_rec + at_a, a.n, a.w, a.h, 0};
+        f.cands.c[j] = BatchCand{reinterpret_cast<const uint4 *>(st->store_desc + at_b * CHIP_ORB_DESC_BYTES), st->store_kp + at_b, nullptr, b.n, b.w, b.h, 0};
+        f.rec[j] = st->store_rec + at_b;
+    }
+    if (f.n1 > 0) {
+        int rc = batch_reserve(c, st, (size_t)P, (size_t)f.n1, false, 0, 0, 0);
+        if (rc != CHIP_OK) return rc;
+        rc = match_launch(c, st, match_stream(c), f, P, Kinv, modes);
+        if (rc != CHIP_OK) return rc;
+    }
+    match_finish(st, P, f.n1);
+    for (int j = 0; j < P; j++) st->cand_n1[j] = n_a[j];
     return CHIP_OK;
 }
 
@@ -1269,10 +1450,10 @@ extern "C" int chip_match_batch_read_matches(chip_ctx *c, int32_t j, int32_t *tr
     MatchState *st = c->match_state;
     if (!st || !st->have_sets || !st->keys_readable) return CHIP_ERR_BUSY;   // not after a chip_match_pair
     if (j < 0 || j >= st->n_cand) return CHIP_ERR_RANGE;
-    const size_t n1 = (size_t)st->n1;
-    if (n1 == 0) return CHIP_OK;
+    const size_t n = (size_t)st->cand_n1[j];    // of the row's st->n1
+    if (n == 0) return CHIP_OK;
     CHIP_HIP(c, hipSetDevice(c->device));
-    return fetch_matches(c, match_stream(c), st, st->keys + (size_t)j * n1, n1, train_idx, distance);
+    return fetch_matches(c, match_stream(c), st, st->keys + (size_t)j * (size_t)st->n1, n, train_idx, distance);
 }
 
 extern "C" int chip_pnp_ransac_matched_batch(chip_ctx *c, int32_t P, const int32_t *cand, const int32_t *which, const chip_ransac_params *p,
@@ -1537,4 +1718,33 @@ extern "C" int chip_match_batch_stored_modes(chip_ctx *c, int64_t a_id, const in
                                              chip_match_summary *summary, chip_gms_choice *choice)
 {
     return match_batch_stored_call(c, a_id, b_ids, B, Kinv, modes, summary, choice);
+}
+
+// ------------------------------------------------------------------------------------------------ a list of stored pairs
+extern "C" int chip_build_has_match_pairs(void) { return 1; }
+
+extern "C" int chip_match_pairs_stored(chip_ctx *c, const int64_t *a_ids, const int64_t *b_ids, int32_t P, const double Kinv[9], uint32_t modes,
+                                       chip_match_summary *summary, chip_gms_choice *choice)
+{
+    if (!c) return CHIP_ERR_INVALID_ARG;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    MatchState *st = c->match_state;
+    if (st) st->have_sets = false;           // a failed call, refused arguments included, leaves nothing selected
+    if (!a_ids || !b_ids || !Kinv || !summary || P < 1 || (modes & ~(uint32_t)(CHIP_GMS_WITH_SCALE | CHIP_GMS_WITH_ROTATION))) return CHIP_ERR_INVALID_ARG;
+    if (P > CHIP_MATCH_MAX_PAIRS) return CHIP_ERR_UNSUPPORTED;
+    if (!st || st->n_slots == 0) return CHIP_ERR_BUSY;
+    int32_t sa[kMaxBatch], sb[kMaxBatch];
+    for (int j = 0; j < P; j++) {
+        const auto fa = st->slot_of.find(a_ids[j]), fb = st->slot_of.find(b_ids[j]);
+        if (fa == st->slot_of.end() || fb == st->slot_of.end()) return CHIP_ERR_RANGE;
+        sa[j] = fa->second; sb[j] = fb->second;
+    }
+    CHIP_HIP(c, hipSetDevice(c->device));
+    const int rc = match_run_pairs_stored(c, st, sa, sb, P, Kinv, modes);
+    if (rc != CHIP_OK) return rc;
+    st->keys_readable = true;
+    for (int j = 0; j < P; j++) summary[j] = st->cand_sm[j];
+    for (int j = 0; j < P && choice; j++) choice[j] = st->cand_choice[j];
+    return CHIP_OK;
 }

@@ -539,7 +539,7 @@ bool StaticPointFeatureMatching::make_3d_3d_collection__using__pfmatches_and_dis
     return true;
 }
 
-// Everything after the match call of verify_candidates / verify_candidates_stored, on the B candidates the call left on the device
+// Everything after the match call of verify_candidates / verify_candidates_stored / verify_pairs_stored, on the B candidates (pairs) the call left on the device
 // (sm: their summaries): the "< 150 matches" reject, then for the survivors ONE matched ICP batch enqueued, ONE
 // chip_pnp_ransac_matched_batch underneath which it runs, the ICP collected, the gates.
 static bool verify_matched(chip_ctx *ctx, const chip_match_summary *sm, int B, ProcessedLoopCandidate *pc, bool *accepted, const uint64_t *seeds)
@@ -616,6 +616,18 @@ bool verify_candidates_stored(chip_ctx *ctx, int64_t a_id, const int64_t *b_ids,
     if (summaries) for (int j = 0; j < B; j++) summaries[j] = sm[j];
     if (rc != CHIP_OK) return false;
     return verify_matched(ctx, sm, B, pc, accepted, seeds);
+}
+
+bool verify_pairs_stored(chip_ctx *ctx, const int64_t *a_ids, const int64_t *b_ids, int P, const double Kinv[9], ProcessedLoopCandidate *pc,
+                         bool *accepted, const uint64_t *seeds, chip_match_summary *summaries, uint32_t gms_modes, chip_gms_choice *choices)
+{
+    if (!a_ids || !b_ids || !pc || !accepted || P < 1 || P > CHIP_MATCH_MAX_PAIRS) return false;
+    for (int j = 0; j < P; j++) accepted[j] = false;
+    chip_match_summary sm[CHIP_MATCH_MAX_PAIRS] = {};
+    const int rc = chip_match_pairs_stored(ctx, a_ids, b_ids, P, Kinv, gms_modes, sm, choices);
+    if (summaries) for (int j = 0; j < P; j++) summaries[j] = sm[j];
+    if (rc != CHIP_OK) return false;
+    return verify_matched(ctx, sm, P, pc, accepted, seeds);   // the pair index is the candidate index of the batched solvers
 }
 
 bool verify_candidate(chip_ctx *ctx, const chip_match_frame &frame_a, const chip_match_frame &frame_b, const double Kinv[9],

@@ -229,6 +229,13 @@ bool verify_candidates(chip_ctx *ctx, const chip_match_frame &frame_a, const chi
 bool verify_candidates_stored(chip_ctx *ctx, int64_t a_id, const int64_t *b_ids, int B, const double Kinv[9], ProcessedLoopCandidate *pc,
                               bool *accepted, const uint64_t *seeds = nullptr, chip_match_summary *summaries = nullptr,
                               uint32_t gms_modes = 0, chip_gms_choice *choices = nullptr);
+// A backlog of the consumer thread (Cerebro.cpp:1224-1232: foundLoops[prev .. new), every entry a pair with a current frame of its own),
+// P <= CHIP_MATCH_MAX_PAIRS stored pairs (a_ids[j], b_ids[j]): ONE chip_match_pairs_stored, then the same tail (one copy of it), so the
+// whole backlog shares one matched ICP batch and one matched PnP batch.  pc[j] / accepted[j] are what
+// verify_candidates_stored(ctx, a_ids[j], &b_ids[j], 1, Kinv, &pc[j], &accepted[j], &seeds[j]) gives, field for field.
+bool verify_pairs_stored(chip_ctx *ctx, const int64_t *a_ids, const int64_t *b_ids, int P, const double Kinv[9], ProcessedLoopCandidate *pc,
+                         bool *accepted, const uint64_t *seeds = nullptr, chip_match_summary *summaries = nullptr, uint32_t gms_modes = 0,
+                         chip_gms_choice *choices = nullptr);
 
 // PoseManipUtils::R2ypr (src/utils/PoseManipUtils.cpp:148-163), degrees, from a column-major 4x4
 void matrix4_to_rawyprt(const double T_colmajor[16], double ypr_deg[3], double t[3]);

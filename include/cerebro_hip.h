@@ -605,7 +605,8 @@ int chip_pnp_ransac_matched(chip_ctx *ctx, int32_t which, const chip_ransac_para
 int chip_icp_ransac_matched(chip_ctx *ctx, const chip_ransac_params *p, double T_colmajor[16], float *confidence,
                             uint8_t *inlier_mask, chip_ransac_summary *summary /* may be NULL */);
 
-/* ---- one query frame against B candidate frames (top-K lists, the clique policy, three queries per tick, a replay's backlog): the
+/* ---- one query frame against B candidate frames (top-K lists, the clique policy, three queries per tick; a replay's backlog is a list
+ * of PAIRS with a query frame each: chip_match_pairs_stored below): the
  * query frame is uploaded once and all B pairs share three launches -- hamming_match_split (grid: query blocks of 256 x train tiles of
  * 1024 x B; the partial minima of a (query, candidate) meet as the unsigned 64-bit key distance << 32 | train index, whose minimum is
  * the smallest distance and then the LOWEST train index, the tie rule above, whichever tile arrives first), gms_batch (one workgroup
@@ -626,7 +627,8 @@ int chip_match_batch(chip_ctx *ctx, const chip_match_frame *a, const chip_match_
  * chip_icp_ransac_matched work on.  After chip_match_pair there is one candidate, index 0. */
 int chip_match_select(chip_ctx *ctx, int32_t j);
 /* matches_all of candidate j (BFMatcher output before GMS): n1 = a->n train indices and distances, -1 / -1 where b[j].n == 0.
- * CHIP_ERR_BUSY unless the last match call of the ctx was a chip_match_batch. */
+ * CHIP_ERR_BUSY unless the last match call of the ctx was a chip_match_batch[_stored] or a chip_match_pairs_stored (then j is the pair
+ * index and n1 the n of THAT pair's query frame). */
 int chip_match_batch_read_matches(chip_ctx *ctx, int32_t j, int32_t *train_idx, int32_t *distance);
 /* P PnP estimations on device-resident sets in launches of up to 8 problems: problem i is set which[i] (CHIP_SET_AB / _BA)
  * of candidate cand[i], seed seeds[i] (NULL: p->seed).  status[i] is what chip_pnp_ransac_matched would return after
@@ -766,6 +768,35 @@ int chip_match_batch_modes(chip_ctx *ctx, const chip_match_frame *a, const chip_
                            chip_gms_choice *choice /* B or NULL */);
 int chip_match_batch_stored_modes(chip_ctx *ctx, int64_t a_id, const int64_t *b_ids, int32_t B, const double Kinv_rowmajor[9],
                                   uint32_t modes, chip_match_summary *summary /* B */, chip_gms_choice *choice /* B or NULL */);
+
+/* ---- a list of (query, candidate) pairs on stored frames (ABI 7, additive).  The batched calls above share ONE query frame; a replay's
+ * backlog does not have that shape: the reference's consumer thread walks foundLoops[prev .. new) (src/Cerebro.cpp:1224-1232) and every
+ * entry is a pair (t_curr, t_prev) with a current frame of its own.  chip_match_pairs_stored runs P such pairs in the launches of ONE
+ * batch, so that the batched PnP and ICP calls reach a backlog too.
+ *
+ * Definitions:
+ *   - for every j, summary[j], choice[j], the ten arrays of chip_match_read_sets after chip_match_select(j) and
+ *     chip_match_batch_read_matches(j) are byte for byte what chip_match_batch_stored_modes(ctx, a_ids[j], &b_ids[j], 1, Kinv, modes, ..)
+ *     gives (modes == 0: chip_match_batch_stored).  chip_match_batch_read_matches(j) delivers the n of frame a_ids[j] entries;
+ *   - a_ids may repeat, b_ids may repeat, a pair may be (x, x).  An empty query frame or an empty candidate gives that pair a zero
+ *     summary and the "nothing chosen" choice and disturbs no other pair;
+ *   - kernels: hamming_match_pairs (grid: query blocks of 256 over the widest query frame x train tiles of 1024 x P; a workgroup
+ *     beyond its own pair's query frame or candidate leaves at once), pairs_gms (or pairs_grid_modes + pairs_mode_select) and
+ *     pose_sets_stored_pairs: the bodies of the batch kernels with the pair's own query frame, which travels next to its candidate
+ *     in the kernel arguments.  Three launches (four with modes != 0) whatever P and however many distinct query frames.  Keys,
+ *     planes and slabs are rows of max_j n(a_ids[j]) per pair;
+ *   - afterwards pair 0 is selected and chip_match_batch_read_matches answers; chip_match_select, chip_match_read_sets,
+ *     chip_pnp_ransac_matched[_batch] and chip_icp_ransac_matched[_batch[_enqueue / _collect]] work on the result unchanged, with
+ *     cand[i] the pair index.  A pending matched ICP batch is waited for first, as in the other runs;
+ *   - status: P < 1 or a NULL a_ids / b_ids / Kinv / summary, or a modes bit outside the two defined, CHIP_ERR_INVALID_ARG;
+ *     P > CHIP_MATCH_MAX_PAIRS or a group ctx CHIP_ERR_UNSUPPORTED; before any chip_frame_store_reserve CHIP_ERR_BUSY; an unknown id
+ *     on either side CHIP_ERR_RANGE (nothing is selected afterwards, as after any failed call).
+ * There is no pair list on host frames: it would upload a query frame per pair, which the store exists to avoid.  A backlog longer
+ * than CHIP_MATCH_MAX_PAIRS is the caller's loop.                                                                                   */
+#define CHIP_MATCH_MAX_PAIRS CHIP_MATCH_MAX_BATCH      /* 16 */
+int chip_build_has_match_pairs(void);      /* 1 */
+int chip_match_pairs_stored(chip_ctx *ctx, const int64_t *a_ids, const int64_t *b_ids, int32_t P, const double Kinv_rowmajor[9],
+                            uint32_t modes, chip_match_summary *summary /* P */, chip_gms_choice *choice /* P or NULL */);
 
 /* ------------------------------------------------------------------------------------------ introspection */
 typedef struct {

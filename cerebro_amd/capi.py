@@ -70,6 +70,7 @@ CHIP_MATCH_MAX_PAIRS = CHIP_MATCH_MAX_BATCH
 CHIP_ICP_MAX_BATCH = 16
 CHIP_ORB_DESC_BYTES = 32
 CHIP_SET_AB, CHIP_SET_BA = 0, 1
+CHIP_DISP_S16, CHIP_DISP_F32 = 0, 1
 
 
 class ChipError(RuntimeError):
@@ -261,6 +262,9 @@ _SIGS = {
     "chip_match_batch_stored": (C.c_int, [_P, C.c_int64, _P, C.c_int32, _P, C.POINTER(MatchSummary)]),
     "chip_build_has_match_pairs": (C.c_int, []),
     "chip_match_pairs_stored": (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_uint32, C.POINTER(MatchSummary), C.POINTER(GmsChoice)]),
+    "chip_build_has_disparity": (C.c_int, []),
+    "chip_frame_put_disparity": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
+    "chip_disparity_to_xyz": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "chip_get_info": (C.c_int, [_P, C.POINTER(Info)]),
     "chip_profile_enable": (C.c_int, [_P, C.c_int32]),
     "chip_profile_reset": (C.c_int, [_P]),
@@ -1002,6 +1006,33 @@ class Chip:
         """chip_frame_put: store (or replace) the frame dict(desc, kp, xyz) under id; the arrays are free again on return"""
         f, keep = self._match_frame(frame)
         self._chk(self.lib.chip_frame_put(self.h, id, C.byref(f)), "chip_frame_put")
+
+    @staticmethod
+    def _disparity(disparity):
+        """-> (contiguous (H, W) int16 or float32 array, CHIP_DISP_*): int16 (CV_16SC1) stays, every other dtype goes as float32"""
+        d = np.asarray(disparity)
+        d = np.ascontiguousarray(d, dtype=np.int16 if d.dtype == np.int16 else np.float32)
+        assert d.ndim == 2
+        return d, CHIP_DISP_S16 if d.dtype == np.int16 else CHIP_DISP_F32
+
+    def frame_put_disparity(self, id: int, frame: dict, disparity, Q: np.ndarray):
+        """chip_frame_put_disparity: store (or replace) the frame dict(desc, kp) under id with the 3-D points of its keypoints computed
+        on the device from the (H, W) disparity (int16: CV_16SC1 raw, otherwise float32 in the same units) and the 4 x 4 Q"""
+        desc = np.ascontiguousarray(frame["desc"], dtype=np.uint8).reshape(-1, CHIP_ORB_DESC_BYTES)
+        kp = np.ascontiguousarray(frame["kp"], dtype=np.float32).reshape(-1, 2)
+        assert desc.shape[0] == kp.shape[0]
+        d, kind = self._disparity(disparity)
+        Qd = np.ascontiguousarray(Q, dtype=np.float64).reshape(16)
+        self._chk(self.lib.chip_frame_put_disparity(self.h, id, _ptr(desc), _ptr(kp), kp.shape[0], d.shape[1], d.shape[0], _ptr(d), kind, _ptr(Qd)),
+                  "chip_frame_put_disparity")
+
+    def disparity_to_xyz(self, disparity, Q: np.ndarray) -> np.ndarray:
+        """chip_disparity_to_xyz -> the (H, W, 3) float32 3-D image of the (H, W) disparity under the 4 x 4 Q"""
+        d, kind = self._disparity(disparity)
+        Qd = np.ascontiguousarray(Q, dtype=np.float64).reshape(16)
+        xyz = np.zeros(d.shape + (3,), dtype=np.float32)
+        self._chk(self.lib.chip_disparity_to_xyz(self.h, _ptr(d), kind, d.shape[1], d.shape[0], _ptr(Qd), _ptr(xyz)), "chip_disparity_to_xyz")
+        return xyz
 
     def frame_drop(self, id: int):
         self._chk(self.lib.chip_frame_drop(self.h, id), "chip_frame_drop")

@@ -491,6 +491,85 @@ __global__ __launch_bounds__(kGatherThreads) void frame_gather(GatherArgs g)
     g.rec[i] = r;
 }
 
+// A pixel's 3-D point from its disparity: StereoGeometry::disparity_to_3DPoints (src/utils/CameraGeometry.cpp:485-523) restated.  The
+// five floats are Q(0,3), (1,3), (2,3), (3,2), (3,3) narrowed on the host (:494-498); d is the disparity as a float, 16 x pixels.
+// pw: every operation in fp64 in the reference's order, an IEEE divide, one narrowing (:511); d / 16 * Q32 is exact, the two additions
+// and the divide round.  x, y, z: fp32 products (:520-522); the file is compiled with -ffp-contract=off, nothing here may fuse.
+struct DispQ { float q03, q13, q23, q32, q33; };
+__device__ __forceinline__ float3 point_of_disparity(float d, int j, int i, const DispQ &q)
+{
+    const float pw = (float)(1.0 / ((((double)d / 16.0) * (double)q.q32 + (double)q.q33) + 1e-6));
+    return make_float3(((float)j + q.q03) * pw, ((float)i + q.q13) * pw, q.q23 * pw);
+}
+
+// disparity_gather: frame_gather for a frame that arrives as its disparity map -- the record of a keypoint is computed from the ONE
+// disparity value at its pixel
+struct GatherDispArgs {
+    const float2 *kp;             // n, in the frame's slot
+    const void *disp;             // h x w, staged: int16 (CHIP_DISP_S16) or float (CHIP_DISP_F32)
+    float4 *rec;                  // n, in the frame's slot
+    int32_t n, w, h, type;
+    DispQ q;
+};
+__global__ __launch_bounds__(kGatherThreads) void disparity_gather(GatherDispArgs g)
+{
+    const int i = blockIdx.x * kGatherThreads + threadIdx.x;
+    if (i >= g.n) return;
+    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+    int x, y;
+    if (pixel_of(g.kp[i], g.w, g.h, &x, &y)) {
+        const size_t o = (size_t)y * g.w + x;
+        const float d = g.type == CHIP_DISP_S16 ? (float)static_cast<const int16_t *>(g.disp)[o] : static_cast<const float *>(g.disp)[o];
+        const float3 p = point_of_disparity(d, x, y, g.q);
+        r = make_float4(p.x, p.y, p.z, 1.0f);
+    }
+    g.rec[i] = r;
+}
+
+// disparity_to_xyz: the dense out3D (:482-524).  A thread takes four consecutive pixels of a row: where the four are inside the row and
+// their first is a multiple of four in the image (the rows of a width that is none start anywhere) with both pointers 16-byte aligned,
+// ONE load of 8 (int16) or 16 (float) bytes and three 16-byte stores for the 48 contiguous bytes; otherwise pixel by pixel.
+struct DenseDispArgs {
+    const void *disp;             // h x w
+    float *xyz;                   // h x w x 3
+    int32_t w, h, type, quads;    // quads: (w + 3) / 4 threads per row
+    DispQ q;
+};
+constexpr int kDenseThreads = 256;
+__global__ __launch_bounds__(kDenseThreads) void disparity_to_xyz(DenseDispArgs a)
+{
+    const size_t t = (size_t)blockIdx.x * kDenseThreads + threadIdx.x;
+    const int i = (int)(t / (size_t)a.quads), j0 = 4 * (int)(t % (size_t)a.quads);
+    if (i >= a.h) return;
+    const size_t p0 = (size_t)i * a.w + j0;
+    const int16_t *s16 = static_cast<const int16_t *>(a.disp);
+    const float *f32 = static_cast<const float *>(a.disp);
+    const bool aligned = (((uintptr_t)a.disp | (uintptr_t)a.xyz) & 15) == 0;
+    if (j0 + 4 <= a.w && (p0 & 3) == 0 && aligned) {
+        float d[4];
+        if (a.type == CHIP_DISP_S16) {
+            const short4 v = *reinterpret_cast<const short4 *>(s16 + p0);
+            d[0] = (float)v.x; d[1] = (float)v.y; d[2] = (float)v.z; d[3] = (float)v.w;
+        } else {
+            const float4 v = *reinterpret_cast<const float4 *>(f32 + p0);
+            d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+        }
+        float3 p[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) p[k] = point_of_disparity(d[k], j0 + k, i, a.q);
+        float4 *o = reinterpret_cast<float4 *>(a.xyz + 3 * p0);
+        o[0] = make_float4(p[0].x, p[0].y, p[0].z, p[1].x);
+        o[1] = make_float4(p[1].y, p[1].z, p[2].x, p[2].y);
+        o[2] = make_float4(p[2].z, p[3].x, p[3].y, p[3].z);
+        return;
+    }
+    for (int j = j0; j < j0 + 4 && j < a.w; j++) {
+        const size_t p = (size_t)i * a.w + j;
+        const float3 v = point_of_disparity(a.type == CHIP_DISP_S16 ? (float)s16[p] : f32[p], j, i, a.q);
+        a.xyz[3 * p] = v.x; a.xyz[3 * p + 1] = v.y; a.xyz[3 * p + 2] = v.z;
+    }
+}
+
 // pose_sets_batch on stored frames: the candidates' descriptors and keypoints (b.cands) point into the store, b.xyz_a and the candidates'
 // xyz are null, the points are the records.  The argument block of pose_sets_batch is b unchanged.
 struct SetsStoredArgs {
@@ -761,12 +840,13 @@ struct MatchState {
     DevBuf<chip_gms_choice> mode_choice;        // [kMaxBatch]
     PinnedBuf<chip_gms_choice> h_choice;
     // the frame store (chip_frame_store_reserve): n_slots slots of slot_kp keypoints each, 56 bytes per keypoint; rows never move after the
-    // reserve.  Slot k: desc + 32 * k * slot_kp, kp + k * slot_kp, rec + k * slot_kp.  stage_xyz: the image of the put in flight.
+    // reserve.  Slot k: desc + 32 * k * slot_kp, kp + k * slot_kp, rec + k * slot_kp.  stage_xyz: the image of the put in flight, or its
+    // disparity (bytes; also the input of chip_disparity_to_xyz, whose dense image is dense_xyz until it is copied out).
     struct StoredFrame { int64_t id = 0; int32_t n = 0, w = 0, h = 0; bool used = false; };
     DevBuf<uint8_t> store_desc;
     DevBuf<float2> store_kp;
     DevBuf<float4> store_rec;
-    DevBuf<float> stage_xyz;
+    DevBuf<float> stage_xyz, dense_xyz;
     int32_t n_slots = 0, slot_kp = 0, n_frames = 0;
     std::vector<StoredFrame> slots;
     std::unordered_map<int64_t, int32_t> slot_of;   // id -> slot
@@ -1592,11 +1672,11 @@ extern "C" int chip_frame_store_info(chip_ctx *c, int32_t *n_slots, int32_t *slo
     return CHIP_OK;
 }
 
-extern "C" int chip_frame_put(chip_ctx *c, int64_t id, const chip_match_frame *f)
+// The body of chip_frame_put and chip_frame_put_disparity: f checked, f->xyz the image (q null) or the disparity of disp_type (q its
+// five floats); what differs is the bytes staged and the kernel that writes the records.
+static int frame_put(chip_ctx *c, int64_t id, const chip_match_frame *f, int32_t disp_type, const DispQ *q)
 {
-    if (!c) return CHIP_ERR_INVALID_ARG;
-    int rc = check_frame(f);
-    if (rc != CHIP_OK) return rc;
+    int rc = CHIP_OK;
     if (c->group) return CHIP_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> lk(c->match_mu);
     MatchState *st = c->match_state;
@@ -1611,16 +1691,25 @@ extern "C" int chip_frame_put(chip_ctx *c, int64_t id, const chip_match_frame *f
     CHIP_HIP(c, hipSetDevice(c->device));
     const size_t px = (size_t)f->width * f->height, at = (size_t)k * (size_t)st->slot_kp;
     if (f->n > 0) {
-        rc = st->stage_xyz.reserve(c, 3 * px);   // the last step that can fail before the slot is written
+        // the staging buffer holds bytes: the image, or a disparity, which never needs more than the image of the same size
+        const size_t bytes = !q ? 3 * px * sizeof(float) : disp_type == CHIP_DISP_S16 ? px * sizeof(int16_t) : px * sizeof(float);
+        rc = st->stage_xyz.reserve(c, (bytes + sizeof(float) - 1) / sizeof(float));   // the last step that can fail before the slot is written
         if (rc != CHIP_OK) return rc;
         hipStream_t s = match_stream(c);
-        GatherArgs g;
-        g.kp = st->store_kp + at; g.xyz = st->stage_xyz; g.rec = st->store_rec + at; g.n = f->n; g.w = f->width; g.h = f->height;
+        const dim3 grid((f->n + kGatherThreads - 1) / kGatherThreads);
         hipError_t e = hipMemcpyAsync(st->store_desc + at * CHIP_ORB_DESC_BYTES, f->desc, (size_t)f->n * CHIP_ORB_DESC_BYTES, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(st->store_kp + at, f->kp_xy, (size_t)f->n * sizeof(float2), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(st->stage_xyz, f->xyz, 3 * px * sizeof(float), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(frame_gather, dim3((f->n + kGatherThreads - 1) / kGatherThreads), dim3(kGatherThreads), 0, s, g);
+        if (e == hipSuccess) e = hipMemcpyAsync(st->stage_xyz, f->xyz, bytes, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess && !q) {
+            GatherArgs g;
+            g.kp = st->store_kp + at; g.xyz = st->stage_xyz; g.rec = st->store_rec + at; g.n = f->n; g.w = f->width; g.h = f->height;
+            hipLaunchKernelGGL(frame_gather, grid, dim3(kGatherThreads), 0, s, g);
+            e = hipGetLastError();
+        } else if (e == hipSuccess) {
+            GatherDispArgs g;
+            g.kp = st->store_kp + at; g.disp = st->stage_xyz; g.rec = st->store_rec + at; g.n = f->n; g.w = f->width; g.h = f->height;
+            g.type = disp_type; g.q = *q;
+            hipLaunchKernelGGL(disparity_gather, grid, dim3(kGatherThreads), 0, s, g);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipStreamSynchronize(s);   // the caller's arrays are free again; a later match is ordered behind the put anyway
@@ -1639,6 +1728,65 @@ extern "C" int chip_frame_put(chip_ctx *c, int64_t id, const chip_match_frame *f
         st->slot_of[id] = k;
         st->n_frames++;
     }
+    return CHIP_OK;
+}
+
+extern "C" int chip_frame_put(chip_ctx *c, int64_t id, const chip_match_frame *f)
+{
+    if (!c) return CHIP_ERR_INVALID_ARG;
+    const int rc = check_frame(f);
+    if (rc != CHIP_OK) return rc;
+    return frame_put(c, id, f, 0, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------ frames from their disparity maps
+extern "C" int chip_build_has_disparity(void) { return 1; }
+
+// Q(0,3), (1,3), (2,3), (3,2), (3,3) of the row-major 4 x 4, each narrowed to float as CameraGeometry.cpp:494-498 does
+static DispQ disp_q(const double Q[16])
+{
+    return DispQ{(float)Q[3], (float)Q[7], (float)Q[11], (float)Q[14], (float)Q[15]};
+}
+
+extern "C" int chip_frame_put_disparity(chip_ctx *c, int64_t id, const uint8_t *desc, const float *kp_xy, int32_t n, int32_t width, int32_t height,
+                                        const void *disparity, int32_t disp_type, const double Q_rowmajor[16])
+{
+    if (!c) return CHIP_ERR_INVALID_ARG;
+    const chip_match_frame f{desc, kp_xy, n, width, height, static_cast<const float *>(disparity)};   // the frame rules, on the disparity
+    const int rc = check_frame(&f);
+    if (rc != CHIP_OK) return rc;
+    if ((disp_type != CHIP_DISP_S16 && disp_type != CHIP_DISP_F32) || !Q_rowmajor) return CHIP_ERR_INVALID_ARG;
+    const DispQ q = disp_q(Q_rowmajor);
+    return frame_put(c, id, &f, disp_type, &q);
+}
+
+extern "C" int chip_disparity_to_xyz(chip_ctx *c, const void *disparity, int32_t disp_type, int32_t width, int32_t height,
+                                     const double Q_rowmajor[16], float *xyz)
+{
+    if (!c || !disparity || !Q_rowmajor || !xyz || width <= 0 || height <= 0) return CHIP_ERR_INVALID_ARG;
+    if (disp_type != CHIP_DISP_S16 && disp_type != CHIP_DISP_F32) return CHIP_ERR_INVALID_ARG;
+    if (width > kMaxImageSide || height > kMaxImageSide) return CHIP_ERR_UNSUPPORTED;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    CHIP_HIP(c, hipSetDevice(c->device));
+    MatchState *st = nullptr;
+    int rc = match_state(c, &st);
+    if (rc != CHIP_OK) return rc;
+    const size_t px = (size_t)width * height;
+    const size_t bytes = disp_type == CHIP_DISP_S16 ? px * sizeof(int16_t) : px * sizeof(float);
+    rc = st->stage_xyz.reserve(c, (bytes + sizeof(float) - 1) / sizeof(float));
+    if (rc == CHIP_OK) rc = st->dense_xyz.reserve(c, 3 * px);
+    if (rc != CHIP_OK) return rc;
+    hipStream_t s = match_stream(c);
+    DenseDispArgs a;
+    a.disp = st->stage_xyz; a.xyz = st->dense_xyz; a.w = width; a.h = height; a.type = disp_type; a.quads = (width + 3) / 4;
+    a.q = disp_q(Q_rowmajor);
+    const size_t threads = (size_t)height * (size_t)a.quads;
+    CHIP_HIP(c, hipMemcpyAsync(st->stage_xyz, disparity, bytes, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(disparity_to_xyz, dim3((unsigned)((threads + kDenseThreads - 1) / kDenseThreads)), dim3(kDenseThreads), 0, s, a);
+    CHIP_HIP(c, hipGetLastError());
+    CHIP_HIP(c, hipMemcpyAsync(xyz, st->dense_xyz, 3 * px * sizeof(float), hipMemcpyDeviceToHost, s));
+    CHIP_HIP(c, hipStreamSynchronize(s));
     return CHIP_OK;
 }
 

@@ -798,6 +798,47 @@ int chip_build_has_match_pairs(void);      /* 1 */
 int chip_match_pairs_stored(chip_ctx *ctx, const int64_t *a_ids, const int64_t *b_ids, int32_t P, const double Kinv_rowmajor[9],
                             uint32_t modes, chip_match_summary *summary /* P */, chip_gms_choice *choice /* P or NULL */);
 
+/* ---- a frame from its disparity map: the 3-D points computed on the device (ABI 7, additive).  chip_frame_put wants the frame's
+ * complete CV_32FC3 3-D image, of which frame_gather reads one pixel per keypoint; the reference makes that image on the host, over
+ * all w x h pixels, with StereoGeometry::disparity_to_3DPoints (src/utils/CameraGeometry.cpp:459-524; the consumer thread reaches it
+ * through :728-742 from src/Cerebro.cpp:1459,1472), and it is six times the bytes of cv::StereoBM's CV_16SC1 disparity (:81,:416).
+ * That function is plain arithmetic on five entries of Q, so it is restated here and computed where it is used.
+ *
+ * Definitions (restating CameraGeometry.cpp:485-523):
+ *   - Q_rowmajor: the 4 x 4 double Q (cv::stereoRectify), row-major.  Five entries count: Q03, Q13, Q23, Q32, Q33 = (0,3), (1,3),
+ *     (2,3), (3,2), (3,3), each narrowed to float ON THE HOST (the CV_64F branch, :494-498; a CV_32F Q widened to double narrows back
+ *     exactly).  Every other entry is ignored (:484);
+ *   - disparity: height x width, dense rows, CHIP_DISP_S16 (CV_16SC1, StereoBM / SGBM raw: 16 x the disparity in pixels) or
+ *     CHIP_DISP_F32 (CV_32FC1 in the same units).  d = the value as a float; an int16 converts exactly (convertTo, :472-473);
+ *   - pw = (float)(1.0 / ((((double)d / 16.0) * (double)Q32 + (double)Q33) + 1e-6)): every operation in fp64 in that order, an IEEE
+ *     fp64 divide, ONE narrowing to float at the end (:511).  d / 16 * Q32 is exact in fp64 (24 x 24 significant bits);
+ *   - pixel (row i, column j): x = ((float)j + Q03) * pw, y = ((float)i + Q13) * pw, z = Q23 * pw, in fp32 without contraction
+ *     (:520-522; the reference is built without FMA);
+ *   - a NaN result is a NaN: its sign and payload are NOT defined (x86 and gfx950 differ there).  Everything else is bit for bit
+ *     what the reference's loop gives, infinities and signed zeros included.
+ *   - chip_frame_put_disparity: chip_frame_put with the disparity in the place of f->xyz.  Every rule of chip_frame_put holds
+ *     (statuses in its order, replace in the own slot, n == 0 is stored, CHIP_ERR_OOM when the store is full, n > slot_keypoints
+ *     and a group ctx CHIP_ERR_UNSUPPORTED, CHIP_ERR_BUSY before a reserve, a failed put leaves the store as it was, the call
+ *     returns when the copies and the kernel are complete); in addition an unknown disp_type or a NULL Q_rowmajor is
+ *     CHIP_ERR_INVALID_ARG.  The disparity goes into the staging buffer of chip_frame_put (bytes; grown on demand, a put never
+ *     shrinks it).  The kernel disparity_gather, one thread per keypoint, takes the pixel frame_gather takes and writes the record
+ *     (x, y, z, 1.0f) of that pixel's disparity, otherwise (0, 0, 0, 0.0f).  Record layout and every reader of it are unchanged: a
+ *     frame put this way and the same frame put through chip_frame_put with the image of chip_disparity_to_xyz are
+ *     indistinguishable afterwards;
+ *   - chip_disparity_to_xyz: the dense out3D of :482-524 into host memory, for callers that stay on host frames (chip_match_batch,
+ *     frames larger than a slot).  Kernel disparity_to_xyz: a thread takes four consecutive pixels of a row -- one 8- or 16-byte
+ *     load and three 16-byte stores where the row position and the pointers allow, pixel by pixel otherwise.  Needs no frame
+ *     store; runs on the ctx stream, serialised with the other calls of the stage.  NULL ctx / disparity / Q_rowmajor / xyz, a
+ *     size < 1 or an unknown disp_type CHIP_ERR_INVALID_ARG; a side beyond the image limit of chip_match_pair or a group ctx
+ *     CHIP_ERR_UNSUPPORTED.  The valid-point matrix of the reference (fill_eigen_matrix, :551-618) is not built.               */
+enum { CHIP_DISP_S16 = 0, CHIP_DISP_F32 = 1 };
+int chip_build_has_disparity(void);        /* 1 */
+int chip_frame_put_disparity(chip_ctx *ctx, int64_t id, const uint8_t *desc /* n x 32 */, const float *kp_xy /* n x 2 */, int32_t n,
+                             int32_t width, int32_t height, const void *disparity /* height x width, dense rows */,
+                             int32_t disp_type, const double Q_rowmajor[16]);
+int chip_disparity_to_xyz(chip_ctx *ctx, const void *disparity /* height x width */, int32_t disp_type, int32_t width, int32_t height,
+                          const double Q_rowmajor[16], float *xyz /* height x width x 3, host */);
+
 /* ------------------------------------------------------------------------------------------ introspection */
 typedef struct {
     int32_t abi_version;

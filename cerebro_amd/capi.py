@@ -71,6 +71,9 @@ CHIP_ICP_MAX_BATCH = 16
 CHIP_ORB_DESC_BYTES = 32
 CHIP_SET_AB, CHIP_SET_BA = 0, 1
 CHIP_DISP_S16, CHIP_DISP_F32 = 0, 1
+# chip_stereo_bm_params' defaults: cv::StereoBM::create(64, 21)
+CHIP_STEREO_BM_NUM_DISPARITIES, CHIP_STEREO_BM_BLOCK_SIZE, CHIP_STEREO_BM_PREFILTER_CAP = 64, 21, 31
+CHIP_STEREO_BM_TEXTURE_THRESHOLD, CHIP_STEREO_BM_UNIQUENESS_RATIO = 10, 15
 
 
 class ChipError(RuntimeError):
@@ -107,6 +110,11 @@ class RansacParams(C.Structure):
 class RansacSummary(C.Structure):
     _fields_ = [("n_iterations", C.c_int32), ("n_inliers", C.c_int32), ("best_hypothesis", C.c_int32),
                 ("n_models", C.c_int32), ("best_cost", C.c_double)]
+
+
+class StereoBmParams(C.Structure):
+    _fields_ = [("num_disparities", C.c_int32), ("block_size", C.c_int32), ("prefilter_cap", C.c_int32),
+                ("texture_threshold", C.c_int32), ("uniqueness_ratio", C.c_int32)]
 
 
 class MatchFrame(C.Structure):
@@ -265,6 +273,10 @@ _SIGS = {
     "chip_build_has_disparity": (C.c_int, []),
     "chip_frame_put_disparity": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
     "chip_disparity_to_xyz": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "chip_stereo_bm_params_default": (None, [C.POINTER(StereoBmParams)]),
+    "chip_build_has_stereo_bm": (C.c_int, []),
+    "chip_stereo_bm": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.POINTER(StereoBmParams), _P]),
+    "chip_frame_put_stereo": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(StereoBmParams), _P]),
     "chip_get_info": (C.c_int, [_P, C.POINTER(Info)]),
     "chip_profile_enable": (C.c_int, [_P, C.c_int32]),
     "chip_profile_reset": (C.c_int, [_P]),
@@ -340,6 +352,16 @@ def _ptr(a: np.ndarray):
 def default_dot_params() -> DotParams:
     p = DotParams()
     load_library().chip_dot_params_default(C.byref(p))
+    return p
+
+
+def default_stereo_bm_params(**fields) -> StereoBmParams:
+    """chip_stereo_bm_params_default, with the given fields replaced"""
+    p = StereoBmParams()
+    load_library().chip_stereo_bm_params_default(C.byref(p))
+    for k, v in fields.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
     return p
 
 
@@ -1033,6 +1055,33 @@ class Chip:
         xyz = np.zeros(d.shape + (3,), dtype=np.float32)
         self._chk(self.lib.chip_disparity_to_xyz(self.h, _ptr(d), kind, d.shape[1], d.shape[0], _ptr(Qd), _ptr(xyz)), "chip_disparity_to_xyz")
         return xyz
+
+    @staticmethod
+    def _stereo_pair(left, right, params):
+        """-> (contiguous (H, W) uint8 left, right, the parameter pointer or None): params a StereoBmParams, a dict of its fields or None"""
+        l, r = np.ascontiguousarray(left, dtype=np.uint8), np.ascontiguousarray(right, dtype=np.uint8)
+        assert l.ndim == 2 and l.shape == r.shape
+        if isinstance(params, dict):
+            params = default_stereo_bm_params(**params)
+        return l, r, None if params is None else C.byref(params)
+
+    def stereo_bm(self, left, right, params=None) -> np.ndarray:
+        """chip_stereo_bm -> the (H, W) int16 disparity (sixteenths of a pixel, -16: none) of the rectified (H, W) uint8 pair"""
+        l, r, p = self._stereo_pair(left, right, params)
+        disp = np.zeros(l.shape, dtype=np.int16)
+        self._chk(self.lib.chip_stereo_bm(self.h, _ptr(l), _ptr(r), l.shape[1], l.shape[0], p, _ptr(disp)), "chip_stereo_bm")
+        return disp
+
+    def frame_put_stereo(self, id: int, frame: dict, left, right, Q: np.ndarray, params=None):
+        """chip_frame_put_stereo: store (or replace) the frame dict(desc, kp) under id with the 3-D points of its keypoints computed on
+        the device from the rectified (H, W) uint8 pair (block matcher at the keypoints) and the 4 x 4 Q"""
+        desc = np.ascontiguousarray(frame["desc"], dtype=np.uint8).reshape(-1, CHIP_ORB_DESC_BYTES)
+        kp = np.ascontiguousarray(frame["kp"], dtype=np.float32).reshape(-1, 2)
+        assert desc.shape[0] == kp.shape[0]
+        l, r, p = self._stereo_pair(left, right, params)
+        Qd = np.ascontiguousarray(Q, dtype=np.float64).reshape(16)
+        self._chk(self.lib.chip_frame_put_stereo(self.h, id, _ptr(desc), _ptr(kp), kp.shape[0], l.shape[1], l.shape[0], _ptr(l), _ptr(r), p, _ptr(Qd)),
+                  "chip_frame_put_stereo")
 
     def frame_drop(self, id: int):
         self._chk(self.lib.chip_frame_drop(self.h, id), "chip_frame_drop")

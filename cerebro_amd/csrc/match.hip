@@ -570,6 +570,161 @@ __global__ __launch_bounds__(kDenseThreads) void disparity_to_xyz(DenseDispArgs 
     }
 }
 
+// ------------------------------------------------------------------------------------------------ the block matcher
+// The definition is in include/cerebro_hip.h ("a frame from its rectified stereo pair"): this project's own, modelled on cv::StereoBM
+// with PREFILTER_XSOBEL, all in int32.  r = block_size / 2.
+struct BmParams { int32_t nd, r, cap, tex, ratio; };
+constexpr int kBmInvalid = -16;        // (minDisparity - 1) * 16
+constexpr int kBmRowDwords = 6;        // a window row: at most 21 bytes, padded to whole dwords
+constexpr int kBmPad = 16;             // bytes behind the prefiltered pair: a row read in whole dwords ends at most 7 bytes behind its window
+constexpr int kBmThreads = 256;
+constexpr int kBmWaves = kBmThreads / 64;
+
+// bm_prefilter: both images in one launch -- the staged pair is 2 h rows of w bytes, the prefiltered pair the same.  A thread takes four
+// consecutive pixels of a row: the column sums s(x) = I[y-][x] + 2 I[y][x] + I[y+][x] at the six columns around them (v = s(x + 1) -
+// s(x - 1), exact in int32), then ONE 32-bit store where the four are inside the row and their address is a multiple of four (a width
+// that is none shifts every row), byte by byte otherwise.
+struct PrefilterArgs {
+    const uint8_t *img;           // 2 h x w: left, right
+    uint8_t *pre;                 // 2 h x w
+    int32_t w, h, quads, cap;     // quads: (w + 3) / 4 threads per row
+};
+__global__ __launch_bounds__(kBmThreads) void bm_prefilter(PrefilterArgs a)
+{
+    const size_t t = (size_t)blockIdx.x * kBmThreads + threadIdx.x;
+    const size_t row = t / (size_t)a.quads;                          // of the pair
+    const int x0 = 4 * (int)(t % (size_t)a.quads);
+    if (row >= 2 * (size_t)a.h) return;
+    const int y = (int)(row % (size_t)a.h);                          // of its image
+    const uint8_t *I = a.img + (row - (size_t)y) * (size_t)a.w;
+    const int ym = y > 0 ? y - 1 : (a.h > 1 ? 1 : 0), yp = y + 1 < a.h ? y + 1 : (a.h > 1 ? a.h - 2 : 0);   // reflected rows
+    const uint8_t *r0 = I + (size_t)ym * a.w, *r1 = I + (size_t)y * a.w, *r2 = I + (size_t)yp * a.w;
+    int s[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        const int x = x0 - 1 + k;
+        s[k] = x >= 0 && x < a.w ? (int)r0[x] + 2 * (int)r1[x] + (int)r2[x] : 0;
+    }
+    uint32_t out[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int x = x0 + k;
+        out[k] = x == 0 || x >= a.w - 1 ? (uint32_t)a.cap : (uint32_t)(min(max(s[k + 2] - s[k], -a.cap), a.cap) + a.cap);
+    }
+    const size_t o = row * (size_t)a.w + (size_t)x0;                 // a.pre is aligned: the offset decides
+    if (x0 + 4 <= a.w && (o & 3) == 0) {
+        *reinterpret_cast<uint32_t *>(a.pre + o) = out[0] | out[1] << 8 | out[2] << 16 | out[3] << 24;
+        return;
+    }
+    for (int k = 0; k < 4 && x0 + k < a.w; k++) a.pre[o + k] = (uint8_t)out[k];
+}
+
+__device__ __forceinline__ bool bm_defined(int x, int y, int w, int h, const BmParams &b)
+{
+    return y >= b.r && y <= h - 1 - b.r && x >= b.nd - 1 + b.r && x <= w - 1 - b.r;
+}
+
+// The nw <= 6 dwords of a window row that starts at byte o (any alignment) of the prefiltered pair: nw + 1 aligned dword loads, each
+// dword of the row formed from two neighbours with v_alignbyte_b32.  The last load ends at most 7 bytes behind the row (kBmPad).
+__device__ __forceinline__ void bm_row(const uint32_t *pre, size_t o, int nw, uint32_t row[kBmRowDwords])
+{
+    const uint32_t *a = pre + (o >> 2);
+    const uint32_t sh = (uint32_t)o & 3;
+    uint32_t wd[kBmRowDwords + 1];
+#pragma unroll
+    for (int k = 0; k <= kBmRowDwords; k++) wd[k] = k <= nw ? a[k] : 0u;
+#pragma unroll
+    for (int k = 0; k < kBmRowDwords; k++) row[k] = __builtin_amdgcn_alignbyte(wd[k + 1], wd[k], sh);
+}
+
+// bm_pixel: the disparity of the defined pixel (x, y), by one wave; lane = disparity d, every lane returns the value.  Per window row the
+// left segment is the same for all lanes and lane d's right segment starts one byte below lane d - 1's; both are read in place (the
+// strip of a wave is (2r + 1) x (nd + 2r) bytes, it stays in the cache).  The (2r + 1)-byte row is padded to whole dwords with zero bytes
+// on both sides, so v_sad_u8 sums four absolute differences at a time; T comes from the same left dwords against cap in every byte.
+// The minimum with its tie rule is one wave reduction on SAD << 8 | (63 - d): smallest SAD, then largest d (SAD <= 441 * 126 < 2^16).
+// Lanes >= nd read what lane nd - 1 reads and carry the largest key.
+__device__ __forceinline__ int bm_pixel(const uint8_t *pre8, size_t px, int w, int x, int y, const BmParams &b, int lane)
+{
+    const uint32_t *pre = reinterpret_cast<const uint32_t *>(pre8);
+    const int nb = 2 * b.r + 1, nw = (nb + 3) >> 2;
+    const uint32_t tail = 0xffffffffu >> (8 * (4 * nw - nb));        // nb is odd: one or three bytes of the last dword count
+    const uint32_t capw = (uint32_t)b.cap * 0x01010101u;
+    const int d = min(lane, b.nd - 1);
+    uint32_t sad = 0, T = 0;
+    for (int dy = -b.r; dy <= b.r; dy++) {
+        const size_t ol = (size_t)(y + dy) * (size_t)w + (size_t)(x - b.r);
+        uint32_t L[kBmRowDwords], R[kBmRowDwords];
+        bm_row(pre, ol, nw, L);
+        bm_row(pre, px + ol - (size_t)d, nw, R);
+#pragma unroll
+        for (int k = 0; k < kBmRowDwords; k++) {
+            if (k >= nw) break;
+            const uint32_t mask = k == nw - 1 ? tail : 0xffffffffu;
+            const uint32_t l = L[k] & mask;
+            sad = __builtin_amdgcn_sad_u8(l, R[k] & mask, sad);
+            T = __builtin_amdgcn_sad_u8(l, capw & mask, T);
+        }
+    }
+    uint32_t key = lane < b.nd ? sad << 8 | (uint32_t)(63 - lane) : 0xffffffffu;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) key = min(key, (uint32_t)__shfl_xor((int)key, o));
+    key = __builtin_amdgcn_readfirstlane(key);
+    const int m = (int)(key >> 8), D = 63 - (int)(key & 255u);
+    if ((int)T < b.tex) return kBmInvalid;
+    if (b.ratio > 0) {
+        const int thresh = m + m * b.ratio / 100;                     // m * ratio <= 55 566 * 100
+        if (__ballot(lane < b.nd && abs(lane - D) > 1 && (int)sad <= thresh) != 0) return kBmInvalid;
+    }
+    const int at_p = D == 0 ? 1 : D == b.nd - 1 ? b.nd - 2 : D - 1, at_n = D == 0 ? 1 : D == b.nd - 1 ? b.nd - 2 : D + 1;
+    const int p = (int)__builtin_amdgcn_readlane(sad, at_p), n = (int)__builtin_amdgcn_readlane(sad, at_n);
+    const int q = p + n - 2 * m + abs(p - n);
+    return (D * 256 + (q != 0 ? (p - n) * 256 / q : 0) + 15) >> 4;    // `/` truncates toward zero; the sum is never negative
+}
+
+// bm_keypoints: disparity_gather for a frame that arrives as its rectified pair -- one wave per keypoint computes the disparity at the
+// keypoint's pixel, lane 0 writes the record
+struct BmKeypointArgs {
+    const float2 *kp;             // n, in the frame's slot
+    const uint8_t *pre;           // 2 h x w: the prefiltered pair
+    float4 *rec;                  // n, in the frame's slot
+    int32_t n, w, h;
+    BmParams b;
+    DispQ q;
+};
+__global__ __launch_bounds__(kBmThreads) void bm_keypoints(BmKeypointArgs g)
+{
+    const int i = blockIdx.x * kBmWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= g.n) return;
+    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+    int x, y;
+    if (pixel_of(g.kp[i], g.w, g.h, &x, &y)) {
+        int v = kBmInvalid;
+        if (bm_defined(x, y, g.w, g.h, g.b)) v = bm_pixel(g.pre, (size_t)g.w * g.h, g.w, x, y, g.b, lane);
+        const float3 p = point_of_disparity((float)v, x, y, g.q);
+        r = make_float4(p.x, p.y, p.z, 1.0f);
+    }
+    if (lane == 0) g.rec[i] = r;
+}
+
+// bm_dense: the same body at every pixel, one wave per pixel (the definition made callable: chip_stereo_bm; not a hot path)
+struct BmDenseArgs {
+    const uint8_t *pre;           // 2 h x w
+    int16_t *disp;                // h x w
+    int32_t w, h;
+    BmParams b;
+};
+__global__ __launch_bounds__(kBmThreads) void bm_dense(BmDenseArgs g)
+{
+    const size_t px = (size_t)g.w * g.h;
+    const size_t i = (size_t)blockIdx.x * kBmWaves + (size_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (i >= px) return;
+    const int y = (int)(i / (size_t)g.w), x = (int)(i % (size_t)g.w);
+    int v = kBmInvalid;
+    if (bm_defined(x, y, g.w, g.h, g.b)) v = bm_pixel(g.pre, px, g.w, x, y, g.b, lane);
+    if (lane == 0) g.disp[i] = (int16_t)v;
+}
+
 // pose_sets_batch on stored frames: the candidates' descriptors and keypoints (b.cands) point into the store, b.xyz_a and the candidates'
 // xyz are null, the points are the records.  The argument block of pose_sets_batch is b unchanged.
 struct SetsStoredArgs {
@@ -841,12 +996,14 @@ struct MatchState {
     PinnedBuf<chip_gms_choice> h_choice;
     // the frame store (chip_frame_store_reserve): n_slots slots of slot_kp keypoints each, 56 bytes per keypoint; rows never move after the
     // reserve.  Slot k: desc + 32 * k * slot_kp, kp + k * slot_kp, rec + k * slot_kp.  stage_xyz: the image of the put in flight, or its
-    // disparity (bytes; also the input of chip_disparity_to_xyz, whose dense image is dense_xyz until it is copied out).
+    // disparity, or its rectified pair (bytes; also the input of chip_disparity_to_xyz and chip_stereo_bm, whose dense image / map is
+    // dense_xyz until it is copied out).
     struct StoredFrame { int64_t id = 0; int32_t n = 0, w = 0, h = 0; bool used = false; };
     DevBuf<uint8_t> store_desc;
     DevBuf<float2> store_kp;
     DevBuf<float4> store_rec;
     DevBuf<float> stage_xyz, dense_xyz;
+    DevBuf<uint8_t> bm_pre;                     // the prefiltered pair of the stereo put (or of chip_stereo_bm) in flight, kBmPad bytes behind it
     int32_t n_slots = 0, slot_kp = 0, n_frames = 0;
     std::vector<StoredFrame> slots;
     std::unordered_map<int64_t, int32_t> slot_of;   // id -> slot
@@ -1672,9 +1829,21 @@ extern "C" int chip_frame_store_info(chip_ctx *c, int32_t *n_slots, int32_t *slo
     return CHIP_OK;
 }
 
-// The body of chip_frame_put and chip_frame_put_disparity: f checked, f->xyz the image (q null) or the disparity of disp_type (q its
-// five floats); what differs is the bytes staged and the kernel that writes the records.
-static int frame_put(chip_ctx *c, int64_t id, const chip_match_frame *f, int32_t disp_type, const DispQ *q)
+// the prefilter of the pair staged in stage_xyz into bm_pre (reserved by the caller)
+static hipError_t launch_bm_prefilter(MatchState *st, hipStream_t s, int32_t w, int32_t h, const BmParams &b)
+{
+    PrefilterArgs a;
+    a.img = reinterpret_cast<const uint8_t *>(st->stage_xyz.get()); a.pre = st->bm_pre; a.w = w; a.h = h; a.quads = (w + 3) / 4; a.cap = b.cap;
+    const size_t threads = 2 * (size_t)h * (size_t)a.quads;
+    hipLaunchKernelGGL(bm_prefilter, dim3((unsigned)((threads + kBmThreads - 1) / kBmThreads)), dim3(kBmThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+// The body of chip_frame_put, chip_frame_put_disparity and chip_frame_put_stereo: f checked, f->xyz the image (q null), the disparity
+// of disp_type (q its five floats) or the left image of the pair (right and bm given as well); what differs is the bytes staged and the
+// kernels that write the records.
+static int frame_put(chip_ctx *c, int64_t id, const chip_match_frame *f, int32_t disp_type, const DispQ *q, const uint8_t *right = nullptr,
+                     const BmParams *bm = nullptr)
 {
     int rc = CHIP_OK;
     if (c->group) return CHIP_ERR_UNSUPPORTED;
@@ -1692,15 +1861,27 @@ static int frame_put(chip_ctx *c, int64_t id, const chip_match_frame *f, int32_t
     const size_t px = (size_t)f->width * f->height, at = (size_t)k * (size_t)st->slot_kp;
     if (f->n > 0) {
         // the staging buffer holds bytes: the image, or a disparity, which never needs more than the image of the same size
-        const size_t bytes = !q ? 3 * px * sizeof(float) : disp_type == CHIP_DISP_S16 ? px * sizeof(int16_t) : px * sizeof(float);
+        // (a pair: two images of px bytes, the int16 map's size)
+        const size_t bytes = !q ? 3 * px * sizeof(float) : bm ? 2 * px : disp_type == CHIP_DISP_S16 ? px * sizeof(int16_t) : px * sizeof(float);
         rc = st->stage_xyz.reserve(c, (bytes + sizeof(float) - 1) / sizeof(float));   // the last step that can fail before the slot is written
+        if (rc == CHIP_OK && bm) rc = st->bm_pre.reserve(c, 2 * px + kBmPad);          // (a regrow pauses the resident scan by itself)
         if (rc != CHIP_OK) return rc;
         hipStream_t s = match_stream(c);
         const dim3 grid((f->n + kGatherThreads - 1) / kGatherThreads);
         hipError_t e = hipMemcpyAsync(st->store_desc + at * CHIP_ORB_DESC_BYTES, f->desc, (size_t)f->n * CHIP_ORB_DESC_BYTES, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(st->store_kp + at, f->kp_xy, (size_t)f->n * sizeof(float2), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(st->stage_xyz, f->xyz, bytes, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess && !q) {
+        if (e == hipSuccess) e = hipMemcpyAsync(st->stage_xyz, f->xyz, bm ? px : bytes, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess && bm) {
+            e = hipMemcpyAsync(reinterpret_cast<uint8_t *>(st->stage_xyz.get()) + px, right, px, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = launch_bm_prefilter(st, s, f->width, f->height, *bm);
+            if (e == hipSuccess) {
+                BmKeypointArgs g;
+                g.kp = st->store_kp + at; g.pre = st->bm_pre; g.rec = st->store_rec + at; g.n = f->n; g.w = f->width; g.h = f->height;
+                g.b = *bm; g.q = *q;
+                hipLaunchKernelGGL(bm_keypoints, dim3((f->n + kBmWaves - 1) / kBmWaves), dim3(kBmThreads), 0, s, g);
+                e = hipGetLastError();
+            }
+        } else if (e == hipSuccess && !q) {
             GatherArgs g;
             g.kp = st->store_kp + at; g.xyz = st->stage_xyz; g.rec = st->store_rec + at; g.n = f->n; g.w = f->width; g.h = f->height;
             hipLaunchKernelGGL(frame_gather, grid, dim3(kGatherThreads), 0, s, g);
@@ -1786,6 +1967,76 @@ extern "C" int chip_disparity_to_xyz(chip_ctx *c, const void *disparity, int32_t
     hipLaunchKernelGGL(disparity_to_xyz, dim3((unsigned)((threads + kDenseThreads - 1) / kDenseThreads)), dim3(kDenseThreads), 0, s, a);
     CHIP_HIP(c, hipGetLastError());
     CHIP_HIP(c, hipMemcpyAsync(xyz, st->dense_xyz, 3 * px * sizeof(float), hipMemcpyDeviceToHost, s));
+    CHIP_HIP(c, hipStreamSynchronize(s));
+    return CHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ frames from their rectified pairs
+extern "C" int chip_build_has_stereo_bm(void) { return 1; }
+
+extern "C" void chip_stereo_bm_params_default(chip_stereo_bm_params *p)
+{
+    if (p) *p = chip_stereo_bm_params{64, 21, 31, 10, 15};           // cv::StereoBM::create(64, 21)
+}
+
+// the parameter table of the header; p null: the defaults
+static int bm_params(const chip_stereo_bm_params *p, BmParams *b)
+{
+    chip_stereo_bm_params d;
+    chip_stereo_bm_params_default(&d);
+    if (p) d = *p;
+    if (d.num_disparities != 16 && d.num_disparities != 32 && d.num_disparities != 48 && d.num_disparities != 64) return CHIP_ERR_UNSUPPORTED;
+    if (d.block_size < 5 || d.block_size > 4 * kBmRowDwords - 3 || d.block_size % 2 == 0) return CHIP_ERR_UNSUPPORTED;
+    if (d.prefilter_cap < 1 || d.prefilter_cap > 63 || d.texture_threshold < 0) return CHIP_ERR_UNSUPPORTED;
+    if (d.uniqueness_ratio < 0 || d.uniqueness_ratio > 100) return CHIP_ERR_UNSUPPORTED;
+    *b = BmParams{d.num_disparities, d.block_size / 2, d.prefilter_cap, d.texture_threshold, d.uniqueness_ratio};
+    return CHIP_OK;
+}
+
+extern "C" int chip_frame_put_stereo(chip_ctx *c, int64_t id, const uint8_t *desc, const float *kp_xy, int32_t n, int32_t width, int32_t height,
+                                     const uint8_t *left, const uint8_t *right, const chip_stereo_bm_params *p, const double Q_rowmajor[16])
+{
+    if (!c) return CHIP_ERR_INVALID_ARG;
+    const chip_match_frame f{desc, kp_xy, n, width, height, reinterpret_cast<const float *>(left)};   // the frame rules, on the left image
+    int rc = check_frame(&f);
+    if (rc != CHIP_OK) return rc;
+    if (!right || !Q_rowmajor) return CHIP_ERR_INVALID_ARG;
+    BmParams b;
+    rc = bm_params(p, &b);
+    if (rc != CHIP_OK) return rc;
+    const DispQ q = disp_q(Q_rowmajor);
+    return frame_put(c, id, &f, CHIP_DISP_S16, &q, right, &b);
+}
+
+extern "C" int chip_stereo_bm(chip_ctx *c, const uint8_t *left, const uint8_t *right, int32_t width, int32_t height,
+                              const chip_stereo_bm_params *p, int16_t *disparity)
+{
+    if (!c || !left || !right || !disparity || width <= 0 || height <= 0) return CHIP_ERR_INVALID_ARG;
+    if (width > kMaxImageSide || height > kMaxImageSide) return CHIP_ERR_UNSUPPORTED;
+    BmParams b;
+    int rc = bm_params(p, &b);
+    if (rc != CHIP_OK) return rc;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    CHIP_HIP(c, hipSetDevice(c->device));
+    MatchState *st = nullptr;
+    rc = match_state(c, &st);
+    if (rc != CHIP_OK) return rc;
+    const size_t px = (size_t)width * height;
+    rc = st->stage_xyz.reserve(c, (2 * px + sizeof(float) - 1) / sizeof(float));
+    if (rc == CHIP_OK) rc = st->bm_pre.reserve(c, 2 * px + kBmPad);
+    if (rc == CHIP_OK) rc = st->dense_xyz.reserve(c, (px * sizeof(int16_t) + sizeof(float) - 1) / sizeof(float));   // the map, as bytes
+    if (rc != CHIP_OK) return rc;
+    hipStream_t s = match_stream(c);
+    uint8_t *stage = reinterpret_cast<uint8_t *>(st->stage_xyz.get());
+    BmDenseArgs a;
+    a.pre = st->bm_pre; a.disp = reinterpret_cast<int16_t *>(st->dense_xyz.get()); a.w = width; a.h = height; a.b = b;
+    CHIP_HIP(c, hipMemcpyAsync(stage, left, px, hipMemcpyHostToDevice, s));
+    CHIP_HIP(c, hipMemcpyAsync(stage + px, right, px, hipMemcpyHostToDevice, s));
+    CHIP_HIP(c, launch_bm_prefilter(st, s, width, height, b));
+    hipLaunchKernelGGL(bm_dense, dim3((unsigned)((px + kBmWaves - 1) / kBmWaves)), dim3(kBmThreads), 0, s, a);
+    CHIP_HIP(c, hipGetLastError());
+    CHIP_HIP(c, hipMemcpyAsync(disparity, a.disp, px * sizeof(int16_t), hipMemcpyDeviceToHost, s));
     CHIP_HIP(c, hipStreamSynchronize(s));
     return CHIP_OK;
 }

@@ -839,6 +839,61 @@ int chip_frame_put_disparity(chip_ctx *ctx, int64_t id, const uint8_t *desc /* n
 int chip_disparity_to_xyz(chip_ctx *ctx, const void *disparity /* height x width */, int32_t disp_type, int32_t width, int32_t height,
                           const double Q_rowmajor[16], float *xyz /* height x width x 3, host */);
 
+/* ---- a frame from its rectified stereo pair: the block matcher on the device, at the keypoints (ABI 7, additive).  The disparity map
+ * chip_frame_put_disparity takes is made by cv::StereoBM::create(64, 21) on the rectified 8-bit pair (src/utils/CameraGeometry.cpp:81,
+ * 416; twice per candidate from src/Cerebro.cpp:1459,1472): 64 disparities x a 21 x 21 window at every pixel on a host core, of
+ * which the stage reads one pixel per keypoint.  A block matcher's answer at a pixel depends on a small 8-bit neighbourhood only, and
+ * the two images are exactly the bytes of the int16 map (2 w h), so the disparity is computed here, at the keypoints, on the put.
+ *
+ * THE DEFINITION IS THIS PROJECT'S OWN, modelled on cv::StereoBM with PREFILTER_XSOBEL.  OpenCV's source is not part of this project,
+ * so parity against it is UNPINNED (DESIGN.md 6 lists the known departures).  All arithmetic is int32.
+ *   - parameters (chip_stereo_bm_params, five int32_t, 20 bytes; defaults = StereoBM::create(64, 21)); a value outside is
+ *     CHIP_ERR_UNSUPPORTED:  num_disparities 64 (16, 32, 48, 64);  block_size 21 (odd, 5 .. 21);  prefilter_cap 31 (1 .. 63);
+ *     texture_threshold 10 (>= 0);  uniqueness_ratio 15 (0 .. 100, 0 = off).  Minimum disparity 0; no speckle filter, no
+ *     left-right check (StereoBM's defaults; the reference sets neither).  Below r = block_size / 2, nd = num_disparities,
+ *     cap = prefilter_cap;
+ *   - prefilter of an image I (uint8, h x w, dense rows) into P: for 1 <= x <= w - 2
+ *       v = (I[y-][x+1] - I[y-][x-1]) + 2 (I[y][x+1] - I[y][x-1]) + (I[y+][x+1] - I[y+][x-1]),  P[y][x] = min(max(v, -cap), cap) + cap
+ *     with reflected rows (y- = y - 1, row -1 is row 1; y+ = y + 1, row h is row h - 2; with h == 1 both are row 0); columns 0 and
+ *     w - 1: P = cap.  P lies in [0, 2 cap];
+ *   - defined pixels: r <= y <= h - 1 - r and nd - 1 + r <= x <= w - 1 - r (every byte of every window inside the images).  Every
+ *     other pixel has the value -16 = (minDisparity - 1) * 16, StereoBM's "no disparity";
+ *   - at a defined pixel, windows over dy, dx in [-r, r]:  T = sum |PL[y+dy][x+dx] - cap|;  SAD(d) = sum |PL[y+dy][x+dx] -
+ *     PR[y+dy][x+dx-d]|, d = 0 .. nd - 1;  m = min SAD;  D = the LARGEST d with SAD(d) == m;
+ *       texture:    T < texture_threshold -> -16;
+ *       uniqueness: (ratio > 0) thresh = m + m * ratio / 100 (integer division); some d with |d - D| > 1 and SAD(d) <= thresh -> -16;
+ *       sub-pixel:  p = SAD(D - 1), n = SAD(D + 1); at D == 0 both are SAD(1), at D == nd - 1 both are SAD(nd - 2);
+ *                   q = p + n - 2 m + |p - n|;  value = (D * 256 + (q != 0 ? (p - n) * 256 / q : 0) + 15) >> 4, `/` truncating
+ *                   toward zero (the sum is never negative): an int16 in sixteenths of a pixel, exactly CHIP_DISP_S16;
+ *   - chip_stereo_bm: the dense map into host memory (kernels bm_prefilter, bm_dense: one wave per pixel, the definition made
+ *     callable, not a hot path).  NULL ctx / left / right / disparity or a size < 1 CHIP_ERR_INVALID_ARG; a side beyond the image
+ *     limit of chip_match_pair, a group ctx or a refused parameter CHIP_ERR_UNSUPPORTED.  Images too small to hold a defined pixel
+ *     are no error: the map is all -16.  Needs no frame store; runs on the ctx stream, serialised with the other calls of the stage;
+ *   - chip_frame_put_stereo: chip_frame_put_disparity with the pair in the place of the map.  Every rule of chip_frame_put holds
+ *     (statuses in its order, replace in the own slot, n == 0 is stored, CHIP_ERR_OOM when the store is full, n > slot_keypoints
+ *     and a group ctx CHIP_ERR_UNSUPPORTED, CHIP_ERR_BUSY before a reserve, a failed put leaves the store as it was, the call
+ *     returns when the copies and the kernels are complete); in addition a NULL left / right / Q_rowmajor is CHIP_ERR_INVALID_ARG
+ *     and a refused parameter CHIP_ERR_UNSUPPORTED, both before anything touches the ctx's device.  The two images go into the
+ *     staging buffer of chip_frame_put (2 w h bytes: what the int16 map takes), bm_prefilter writes the prefiltered pair into a
+ *     buffer of its own, and bm_keypoints -- one wave per keypoint, lane = disparity, four absolute byte differences per
+ *     instruction -- takes the pixel frame_gather takes, computes its disparity by the definition and writes the record
+ *     (x, y, z, 1.0f) of point_of_disparity of that value, otherwise (0, 0, 0, 0.0f).  A frame put this way and the same frame put
+ *     through chip_frame_put_disparity with CHIP_DISP_S16 and the map of chip_stereo_bm are indistinguishable afterwards.         */
+typedef struct {
+    int32_t num_disparities;     /* 64: 16, 32, 48 or 64 */
+    int32_t block_size;          /* 21: odd, 5 .. 21 */
+    int32_t prefilter_cap;       /* 31: 1 .. 63 */
+    int32_t texture_threshold;   /* 10: >= 0 */
+    int32_t uniqueness_ratio;    /* 15: 0 .. 100, 0 = off */
+} chip_stereo_bm_params;
+void chip_stereo_bm_params_default(chip_stereo_bm_params *p);
+int chip_build_has_stereo_bm(void);        /* 1 */
+int chip_stereo_bm(chip_ctx *ctx, const uint8_t *left, const uint8_t *right /* height x width each, dense rows */, int32_t width,
+                   int32_t height, const chip_stereo_bm_params *p /* NULL: the defaults */, int16_t *disparity /* height x width, host */);
+int chip_frame_put_stereo(chip_ctx *ctx, int64_t id, const uint8_t *desc /* n x 32 */, const float *kp_xy /* n x 2 */, int32_t n,
+                          int32_t width, int32_t height, const uint8_t *left, const uint8_t *right /* height x width each */,
+                          const chip_stereo_bm_params *p /* NULL: the defaults */, const double Q_rowmajor[16]);
+
 /* ------------------------------------------------------------------------------------------ introspection */
 typedef struct {
     int32_t abi_version;

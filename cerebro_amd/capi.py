@@ -74,6 +74,9 @@ CHIP_DISP_S16, CHIP_DISP_F32 = 0, 1
 # chip_stereo_bm_params' defaults: cv::StereoBM::create(64, 21)
 CHIP_STEREO_BM_NUM_DISPARITIES, CHIP_STEREO_BM_BLOCK_SIZE, CHIP_STEREO_BM_PREFILTER_CAP = 64, 21, 31
 CHIP_STEREO_BM_TEXTURE_THRESHOLD, CHIP_STEREO_BM_UNIQUENESS_RATIO = 10, 15
+# chip_orb_params' defaults: cv::ORB::create(5000) with setFastThreshold(0)
+CHIP_ORB_MAX_LEVELS, CHIP_ORB_MAX_SIDE = 8, 4096
+CHIP_ORB_N_FEATURES, CHIP_ORB_N_LEVELS, CHIP_ORB_FAST_THRESHOLD, CHIP_ORB_BORDER = 5000, 8, 0, 31
 
 
 class ChipError(RuntimeError):
@@ -115,6 +118,28 @@ class RansacSummary(C.Structure):
 class StereoBmParams(C.Structure):
     _fields_ = [("num_disparities", C.c_int32), ("block_size", C.c_int32), ("prefilter_cap", C.c_int32),
                 ("texture_threshold", C.c_int32), ("uniqueness_ratio", C.c_int32)]
+
+
+class OrbParams(C.Structure):
+    _fields_ = [("n_features", C.c_int32), ("n_levels", C.c_int32), ("fast_threshold", C.c_int32), ("border", C.c_int32)]
+
+
+class OrbKeypoint(C.Structure):
+    _fields_ = [("response", C.c_int64), ("x", C.c_float), ("y", C.c_float), ("m10", C.c_int32), ("m01", C.c_int32),
+                ("x_level", C.c_uint16), ("y_level", C.c_uint16), ("level", C.c_uint16), ("zero", C.c_uint16)]
+
+
+class OrbLevel(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("quota", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32),
+                ("x1", C.c_int32), ("y1", C.c_int32), ("scale", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# chip_orb_keypoint as a numpy record
+ORB_KEYPOINT_DTYPE = np.dtype([("response", "<i8"), ("x", "<f4"), ("y", "<f4"), ("m10", "<i4"), ("m01", "<i4"), ("x_level", "<u2"),
+                               ("y_level", "<u2"), ("level", "<u2"), ("zero", "<u2")])
 
 
 class MatchFrame(C.Structure):
@@ -277,6 +302,11 @@ _SIGS = {
     "chip_build_has_stereo_bm": (C.c_int, []),
     "chip_stereo_bm": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.POINTER(StereoBmParams), _P]),
     "chip_frame_put_stereo": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(StereoBmParams), _P]),
+    "chip_orb_params_default": (None, [C.POINTER(OrbParams)]),
+    "chip_build_has_orb_detect": (C.c_int, []),
+    "chip_orb_plan": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(OrbParams), C.POINTER(OrbLevel)]),
+    "chip_orb_detect": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(OrbParams), _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "chip_debug_orb_level": (C.c_int, [_P, C.c_int32, _P, _P]),
     "chip_get_info": (C.c_int, [_P, C.POINTER(Info)]),
     "chip_profile_enable": (C.c_int, [_P, C.c_int32]),
     "chip_profile_reset": (C.c_int, [_P]),
@@ -363,6 +393,35 @@ def default_stereo_bm_params(**fields) -> StereoBmParams:
         assert hasattr(p, k), k
         setattr(p, k, v)
     return p
+
+
+def default_orb_params(**fields) -> OrbParams:
+    """chip_orb_params_default, with the given fields replaced"""
+    p = OrbParams()
+    load_library().chip_orb_params_default(C.byref(p))
+    for k, v in fields.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def _orb_params(params):
+    """a parameter pointer or None from an OrbParams, a dict of its fields or None"""
+    if isinstance(params, dict):
+        params = default_orb_params(**params)
+    return params, (None if params is None else C.byref(params))
+
+
+def orb_plan(width: int, height: int, params=None) -> list:
+    """chip_orb_plan -> the level table of a detect on a width x height image: n_levels dicts (width, height, quota, x0, y0, x1, y1,
+    scale).  Needs no ctx and no device."""
+    params, p = _orb_params(params)
+    lv = (OrbLevel * CHIP_ORB_MAX_LEVELS)()
+    rc = load_library().chip_orb_plan(width, height, p, lv)
+    if rc != CHIP_OK:
+        raise ChipError(rc, "chip_orb_plan")
+    n = CHIP_ORB_N_LEVELS if params is None else params.n_levels
+    return [lv[l].as_dict() for l in range(n)]
 
 
 def default_ransac_params() -> RansacParams:
@@ -1082,6 +1141,28 @@ class Chip:
         Qd = np.ascontiguousarray(Q, dtype=np.float64).reshape(16)
         self._chk(self.lib.chip_frame_put_stereo(self.h, id, _ptr(desc), _ptr(kp), kp.shape[0], l.shape[1], l.shape[0], _ptr(l), _ptr(r), p, _ptr(Qd)),
                   "chip_frame_put_stereo")
+
+    def orb_detect(self, image, params=None):
+        """chip_orb_detect on the (H, W) uint8 image -> (the records as an ORB_KEYPOINT_DTYPE array, level_counts[8]); params an
+        OrbParams, a dict of its fields or None"""
+        img = np.ascontiguousarray(image, dtype=np.uint8)
+        assert img.ndim == 2
+        params, p = _orb_params(params)
+        cap = CHIP_ORB_N_FEATURES if params is None else max(int(params.n_features), 1)
+        kp = np.zeros(cap, dtype=ORB_KEYPOINT_DTYPE)
+        n = C.c_int32()
+        counts = (C.c_int32 * CHIP_ORB_MAX_LEVELS)()
+        self._chk(self.lib.chip_orb_detect(self.h, _ptr(img), img.shape[1], img.shape[0], p, _ptr(kp), cap, C.byref(n), counts), "chip_orb_detect")
+        return kp[:n.value].copy(), list(counts)
+
+    def orb_level(self, level: int, width: int, height: int):
+        """chip_debug_orb_level -> (the (height, width) uint8 pyramid level, the (height, width) int16 FAST score plane, -256 where the
+        score is not defined) the last orb_detect left behind; width and height are that level's (orb_plan)"""
+        img = np.zeros((height, width), dtype=np.uint8)
+        score = np.zeros((height, width), dtype=np.int16)
+        self._chk(self.lib.chip_debug_orb_level(self.h, level, _ptr(img) if img.size else None, _ptr(score) if score.size else None),
+                  "chip_debug_orb_level")
+        return img, score
 
     def frame_drop(self, id: int):
         self._chk(self.lib.chip_frame_drop(self.h, id), "chip_frame_drop")

@@ -256,6 +256,7 @@ struct PnpState;   // pnp.hip / icp.hip / batch.hip / match.hip: a unit's scratc
 struct IcpState;
 struct BatchState;
 struct MatchState;
+struct OrbState;
 struct Exchange;   // chip_multi.hip: how a sharded ctx trades its per-shard top-k lists (RCCL communicator / device copies)
 struct Group;      // chip_multi.hip: a ctx made of G per-device sub-contexts driven from one process
 
@@ -383,6 +384,7 @@ struct Ctx {
     IcpState *icp_state = nullptr;
     BatchState *batch_state = nullptr;
     MatchState *match_state = nullptr;
+    OrbState *orb_state = nullptr;   // orb.hip: created by the first chip_orb_detect; its calls take match_mu
     std::mutex match_mu;         // serialises the matching calls of a ctx; taken BEFORE pnp_mu / icp_mu (chip_*_ransac_matched)
 
     mutable hipError_t last_hip = hipSuccess;
@@ -582,6 +584,7 @@ void pnp_destroy(Ctx *c);
 void icp_destroy(Ctx *c);
 void batch_destroy(Ctx *c);
 void match_destroy(Ctx *c);   // match.hip
+void orb_destroy(Ctx *c);     // orb.hip
 // the solvers on correspondence sets that already are in device memory (match.hip's sets): same kernels, same results as the
 // host-pointer entries chip_pnp_ransac / chip_icp_ransac; the caller has validated the arguments and holds match_mu
 int pnp_ransac_device(Ctx *c, const double *X_dev, const double *uv_dev, int32_t N, const chip_ransac_params *p, double *T_colmajor,

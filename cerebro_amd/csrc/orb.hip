@@ -1,0 +1,608 @@
+// orb.hip -- the detector half of ORB on gfx950: what cv::ORB::create(5000) with setFastThreshold(0) does before it describes
+// (src/utils/PointFeatureMatching.cpp:16-22).  include/cerebro_hip.h, "ORB keypoint detection on the device", has the definition; it is
+// this project's own, all-integer, and restated in tests/np_mirror_orb_detect.py, which the device equals bit for bit.
+//
+//   orb_pyramid    : level l from level l - 1, fixed-point bilinear at pixel centres.  One launch per level above 0 (a level needs the one
+//                    before); a thread makes four pixels of a row and stores one dword.
+//   orb_fast_score : all levels in one launch (level = blockIdx.z).  A workgroup stages 22 rows x 136 bytes (a tile of 128 x 16 pixels with
+//                    its halo of 3, rows as whole dwords) in LDS; a thread reads 7 rows x 4 dwords, makes the score of eight pixels (16
+//                    differences, the nine-wide cyclic minimum and maximum by doubling: 2, 4, 8, 8 + 1) and stores them as one 16-byte store.
+//   orb_candidates : all levels (blockIdx.y).  A workgroup owns a strip of two rows of the detection rectangle: threshold and 3 x 3 strict
+//                    maximum, ordered compaction (ballot + prefix popcount, running base across the waves) of the survivors' raster
+//                    indices into LDS, then the 7 x 7 Harris sums for the survivors only, one per thread.  A strip holds at most one strict
+//                    maximum per 2 x 2 block, which bounds its segment of the level's candidate list; the strip's count goes next to it.
+//   orb_select     : one workgroup per level.  Scan of the strip counts, the segments closed up in place into one list in raster order (a
+//                    bisection in LDS per candidate, once), radix select of the quota-th largest R (8 bits a pass, LDS histogram, four
+//                    loads in flight), then one ordered pass that keeps R > R* and the first ties in raster order.  Writes the kept list
+//                    at the level's quota prefix and the kept count.
+//   orb_moments    : one wave per kept keypoint over all levels: the level of output i from the eight kept counts, the 31 rows of the
+//                    patch as aligned dwords, one wave reduction, two 16-byte stores per record.
+//
+// Nothing returns to the host between the stages; the records and the eight counts leave in ONE copy at the end.
+#include "chip_internal.h"
+#include <cmath>
+#include <cstring>
+#include <new>
+
+namespace chip {
+
+constexpr int kOrbLevels = CHIP_ORB_MAX_LEVELS;
+constexpr int kOrbMaxSide = CHIP_ORB_MAX_SIDE;
+constexpr int kOrbThreads = 256;
+constexpr int kScoreTileW = 128, kScoreTileH = 16;       // pixels of a score tile: 16 x 16 threads of eight pixels in a row each
+constexpr int kScoreLdsRows = kScoreTileH + 6;           // 22
+constexpr int kScoreLdsPairs = (kScoreTileW + 8) / 8;    // 17 uint2 a row: the tile's columns - 4 .. + 131
+constexpr int kStripRows = 2;
+constexpr int kStripMaxCand = (kOrbMaxSide - 32 + 1) / 2;   // 2032: one strict maximum per 2 x 2 block, border >= 16
+constexpr int kMaxStrips = (kOrbMaxSide - 32 + 1) / 2;      // 2032 strips of two rows
+constexpr int kSelectThreads = 1024;
+static_assert(kMaxStrips <= 2 * kSelectThreads, "orb_select scans two strips a thread");
+constexpr int kOutHeader = 32;                           // bytes: the eight kept counts in front of the records
+
+struct OrbLevel {
+    int32_t w, h, pitch, spitch;       // image row pitch in bytes (a multiple of 4), score row pitch in elements (a multiple of 8)
+    int32_t x0, y0, x1, y1;            // detection rectangle, empty: x1 < x0
+    int32_t quota, qprefix;            // kept list of the level: [qprefix, qprefix + quota)
+    int32_t cap, nstrips;              // candidate segment of a strip, strips of the level
+    uint32_t img_off, score_off, cand_off, strip_off;   // into the ctx's buffers, in elements
+    double scale;
+};
+struct OrbTable {
+    int32_t n_levels, n_features, threshold, pad;
+    OrbLevel l[kOrbLevels];
+};
+struct OrbCand { long long R; int32_t raster, pad; };    // 16 bytes
+struct OrbArgs {
+    uint8_t *img;
+    int16_t *score;
+    OrbCand *cand;
+    int32_t *strip_count;
+    OrbCand *kept;
+    uint8_t *out;                      // kOutHeader bytes of counts, then the records
+    OrbTable t;
+};
+
+// ------------------------------------------------------------------------------------------------ orb_pyramid
+__device__ __forceinline__ void orb_axis(int x, int n_src, int n_dst, int *i0, int *i1, uint32_t *frac)
+{
+    long long X = ((long long)(2 * x + 1) * n_src * 1024) / n_dst - 1024;
+    const long long hi = (long long)(n_src - 1) * 2048;
+    X = X < 0 ? 0 : (X > hi ? hi : X);
+    *i0 = (int)(X >> 11);
+    *frac = (uint32_t)(X & 2047);
+    *i1 = min(*i0 + 1, n_src - 1);
+}
+// grid (ceil(pitch / 4 / 64), ceil(h / 4)), block (64, 4): level lv from level lv - 1
+__global__ __launch_bounds__(kOrbThreads) void orb_pyramid(OrbArgs a, int lv)
+{
+    const OrbLevel &d = a.t.l[lv], &s = a.t.l[lv - 1];
+    const int xq = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    if (4 * xq >= d.w || y >= d.h) return;
+    const uint8_t *src = a.img + s.img_off;
+    int y0, y1;
+    uint32_t b;
+    orb_axis(y, s.h, d.h, &y0, &y1, &b);
+    const uint8_t *r0 = src + (size_t)y0 * s.pitch, *r1 = src + (size_t)y1 * s.pitch;
+    uint32_t packed = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int x = min(4 * xq + i, d.w - 1);           // the pad bytes of a row repeat its last pixel
+        int x0, x1;
+        uint32_t f;
+        orb_axis(x, s.w, d.w, &x0, &x1, &f);
+        const uint32_t v = (r0[x0] * (2048u - f) * (2048u - b) + r0[x1] * f * (2048u - b) + r1[x0] * (2048u - f) * b + r1[x1] * f * b +
+                            (1u << 21)) >> 22;
+        packed |= v << (8 * i);
+    }
+    *reinterpret_cast<uint32_t *>(a.img + d.img_off + (size_t)y * d.pitch + 4 * xq) = packed;
+}
+
+// ------------------------------------------------------------------------------------------------ orb_fast_score
+// byte c (0 .. 15) of the four dwords of a row
+#define ORB_BYTE(r, c) (int)(((r)[(c) >> 2] >> (8 * ((c) & 3))) & 255u)
+// grid (tiles in x of the widest level, tiles in y of the tallest, n_levels), block 256
+__global__ __launch_bounds__(kOrbThreads) void orb_fast_score(OrbArgs a)
+{
+    __shared__ uint2 tile[kScoreLdsRows][kScoreLdsPairs];
+    const OrbLevel &L = a.t.l[blockIdx.z];
+    const int tx0 = blockIdx.x * kScoreTileW, ty0 = blockIdx.y * kScoreTileH;
+    if (tx0 >= L.spitch || ty0 >= L.h) return;            // wave-uniform: the whole workgroup leaves
+    const uint8_t *img = a.img + L.img_off;
+    uint32_t *flat = reinterpret_cast<uint32_t *>(&tile[0][0]);
+    for (int i = threadIdx.x; i < kScoreLdsRows * 2 * kScoreLdsPairs; i += kOrbThreads) {
+        const int r = i / (2 * kScoreLdsPairs), cq = i - r * (2 * kScoreLdsPairs);
+        const int gy = ty0 - 3 + r, gx = tx0 - 4 + 4 * cq;
+        uint32_t v = 0;
+        if (gy >= 0 && gy < L.h && gx >= 0 && gx < L.pitch) v = *reinterpret_cast<const uint32_t *>(img + (size_t)gy * L.pitch + gx);
+        flat[i] = v;
+    }
+    __syncthreads();
+    const int lx = threadIdx.x & 15, ly = threadIdx.x >> 4;
+    const int x = tx0 + 8 * lx, y = ty0 + ly;
+    if (x >= L.spitch || y >= L.h) return;
+    uint32_t rows[7][4];                                  // rows y - 3 .. y + 3, columns x - 4 .. x + 11
+#pragma unroll
+    for (int r = 0; r < 7; r++) {
+        const uint2 p = tile[ly + r][lx], q = tile[ly + r][lx + 1];
+        rows[r][0] = p.x; rows[r][1] = p.y; rows[r][2] = q.x; rows[r][3] = q.y;
+    }
+    constexpr int ring_dx[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
+    constexpr int ring_dy[16] = {-3, -3, -2, -1, 0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3};
+    uint32_t packed[4];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const int ip = ORB_BYTE(rows[3], 4 + i);
+        int d[16], lo[16], hi[16], t[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) d[k] = ORB_BYTE(rows[3 + ring_dy[k]], 4 + i + ring_dx[k]) - ip;
+        // minimum and maximum over the nine ring pixels k .. k + 8, for every k: windows of 2, 4, 8, then the ninth
+#pragma unroll
+        for (int k = 0; k < 16; k++) { lo[k] = min(d[k], d[(k + 1) & 15]); hi[k] = max(d[k], d[(k + 1) & 15]); }
+#pragma unroll
+        for (int k = 0; k < 16; k++) t[k] = min(lo[k], lo[(k + 2) & 15]);
+#pragma unroll
+        for (int k = 0; k < 16; k++) lo[k] = min(t[k], t[(k + 4) & 15]);
+#pragma unroll
+        for (int k = 0; k < 16; k++) t[k] = max(hi[k], hi[(k + 2) & 15]);
+#pragma unroll
+        for (int k = 0; k < 16; k++) hi[k] = max(t[k], t[(k + 4) & 15]);
+        int b = -256, dk = 256;
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            b = max(b, min(lo[k], d[(k + 8) & 15]));      // brighter: the largest arc minimum of I_k - I_p
+            dk = min(dk, max(hi[k], d[(k + 8) & 15]));    // darker: I_p - I_k, so minus the smallest arc maximum
+        }
+        int S = max(b, -dk) - 1;
+        const int px = x + i;
+        if (px < 3 || px > L.w - 4 || y < 3 || y > L.h - 4) S = -256;
+        const uint32_t s16 = (uint32_t)S & 0xffffu;
+        if (i & 1) packed[i >> 1] |= s16 << 16; else packed[i >> 1] = s16;
+    }
+    *reinterpret_cast<uint4 *>(a.score + L.score_off + (size_t)y * L.spitch + x) = make_uint4(packed[0], packed[1], packed[2], packed[3]);
+}
+
+// ------------------------------------------------------------------------------------------------ orb_candidates
+__device__ __forceinline__ long long orb_harris(const uint8_t *img, int pitch, int x, int y)
+{
+    int a = 0, bb = 0, c = 0;
+    for (int dy = -3; dy <= 3; dy++) {
+        const uint8_t *m = img + (size_t)(y + dy) * pitch + x, *u = m - pitch, *d = m + pitch;
+        for (int dx = -3; dx <= 3; dx++) {
+            const int ul = u[dx - 1], uc = u[dx], ur = u[dx + 1], ml = m[dx - 1], mr = m[dx + 1], dl = d[dx - 1], dc = d[dx], dr = d[dx + 1];
+            const int ix = 2 * (mr - ml) + (ur - ul) + (dr - dl);
+            const int iy = 2 * (dc - uc) + (dl - ul) + (dr - ur);
+            a += ix * ix; bb += iy * iy; c += ix * iy;
+        }
+    }
+    const long long A = a, B = bb, C = c;
+    return 25 * (A * B - C * C) - (A + B) * (A + B);
+}
+// grid (strips of the level with the most, n_levels), block 256
+__global__ __launch_bounds__(kOrbThreads) void orb_candidates(OrbArgs a)
+{
+    __shared__ int32_t list[kStripMaxCand];
+    __shared__ int32_t wave_n[kOrbThreads / 64];
+    const OrbLevel &L = a.t.l[blockIdx.y];
+    const int strip = blockIdx.x;
+    if (strip >= L.nstrips) return;
+    const int16_t *sc = a.score + L.score_off;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int thr = a.t.threshold;
+    int base = 0;                                         // survivors so far, the same in every thread
+    for (int r = 0; r < kStripRows; r++) {
+        const int y = L.y0 + kStripRows * strip + r;
+        if (y > L.y1) break;
+        for (int xc = L.x0; xc <= L.x1; xc += kOrbThreads) {
+            const int x = xc + (int)threadIdx.x;
+            bool keep = false;
+            if (x <= L.x1) {
+                const int16_t *p = sc + (size_t)y * L.spitch + x;
+                const int s = p[0];
+                if (s >= thr) {
+                    const int16_t *u = p - L.spitch, *d = p + L.spitch;
+                    const int m = max(max(max((int)u[-1], (int)u[0]), max((int)u[1], (int)p[-1])), max(max((int)p[1], (int)d[-1]), max((int)d[0], (int)d[1])));
+                    keep = s > m;
+                }
+            }
+            const unsigned long long votes = __ballot(keep);
+            if (lane == 0) wave_n[wave] = __popcll(votes);
+            __syncthreads();
+            int before = 0, total = 0;
+#pragma unroll
+            for (int w = 0; w < kOrbThreads / 64; w++) { const int n = wave_n[w]; total += n; if (w < wave) before += n; }
+            if (keep) {
+                const int at = base + before + __popcll(votes & ((1ull << lane) - 1ull));
+                if (at < L.cap) list[at] = y * L.w + x;  // (always: one strict maximum per 2 x 2 block)
+            }
+            base += total;
+            __syncthreads();
+        }
+    }
+    const int n = min(base, L.cap);
+    OrbCand *seg = a.cand + L.cand_off + (size_t)strip * L.cap;
+    const uint8_t *img = a.img + L.img_off;
+    for (int i = threadIdx.x; i < n; i += kOrbThreads) {
+        const int raster = list[i], y = raster / L.w, x = raster - y * L.w;
+        const long long R = orb_harris(img, L.pitch, x, y);
+        *reinterpret_cast<uint4 *>(seg + i) = make_uint4((uint32_t)(unsigned long long)R, (uint32_t)((unsigned long long)R >> 32), (uint32_t)raster, 0u);
+    }
+    if (threadIdx.x == 0) a.strip_count[L.strip_off + strip] = n;
+}
+
+// ------------------------------------------------------------------------------------------------ orb_select
+// exclusive sum of v over the threads of the workgroup in thread order, and the total; scratch: one int per wave
+__device__ __forceinline__ int orb_block_excl(int v, int32_t *scratch, int *total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(inc, off); if (lane >= off) inc += t; }
+    __syncthreads();                                      // the scratch of the call before has been read
+    if (lane == 63) scratch[wave] = inc;
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < kSelectThreads / 64; w++) { const int n = scratch[w]; all += n; if (w < wave) before += n; }
+    *total = all;
+    return before + inc - v;
+}
+// grid CHIP_ORB_MAX_LEVELS, block 1024
+__global__ __launch_bounds__(kSelectThreads) void orb_select(OrbArgs a)
+{
+    __shared__ int32_t start[2 * kSelectThreads + 1];     // start[s]: candidates of the level before strip s (kMaxStrips <= 2048)
+    __shared__ __align__(16) int32_t hist[256];
+    __shared__ int32_t scratch[kSelectThreads / 64];
+    __shared__ unsigned long long sel_prefix;
+    __shared__ int32_t sel_k;
+    const int lv = blockIdx.x, tid = threadIdx.x;
+    const OrbLevel &L = a.t.l[lv];
+    int32_t *counts_out = reinterpret_cast<int32_t *>(a.out);
+    if (lv >= a.t.n_levels) { if (tid == 0) counts_out[lv] = 0; return; }
+    const int32_t *sn = a.strip_count + L.strip_off;
+    int C;
+    {   // scan of the strip counts, two strips a thread
+        const int s = 2 * tid;
+        const int c0 = s < L.nstrips ? sn[s] : 0, c1 = s + 1 < L.nstrips ? sn[s + 1] : 0;
+        const int e = orb_block_excl(c0 + c1, scratch, &C);
+        start[s] = e;
+        start[s + 1] = e + c0;
+        if (tid == kSelectThreads - 1) start[2 * kSelectThreads] = C;
+        __syncthreads();
+    }
+    OrbCand *cand = a.cand + L.cand_off;
+    uint4 *flat = reinterpret_cast<uint4 *>(cand);
+    // The segments close up in place, so that candidate g of the level in raster order is entry g: 1024 at a time, each found by a
+    // bisection over the strip ranges, read, and after a barrier written.  Entry g never lies behind its source, a chunk writes
+    // [g0, g0 + 1024) and the sources of every later chunk lie at or behind g0 + 1024, so nothing unread is overwritten.
+    for (int g0 = 0; g0 < C; g0 += kSelectThreads) {
+        const int g = g0 + tid;
+        uint4 raw = make_uint4(0u, 0u, 0u, 0u);
+        if (g < C) {
+            int lo = 0, hi = L.nstrips;                   // start[lo] <= g < start[hi]
+            while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (start[mid] <= g) lo = mid; else hi = mid; }
+            raw = flat[(size_t)lo * L.cap + (g - start[lo])];
+        }
+        __syncthreads();
+        if (g < C) flat[g] = raw;
+    }
+    __syncthreads();
+    const bool all = C <= L.quota;
+    unsigned long long star = 0;                          // key of R*: R with the sign bit flipped, so that unsigned order is R's
+    int need = 0;                                         // ties of R* to keep
+    if (!all) {
+        if (tid == 0) { sel_prefix = 0; sel_k = L.quota; }
+        for (int shift = 56; shift >= 0; shift -= 8) {
+            if (tid < 256) hist[tid] = 0;
+            __syncthreads();
+            const unsigned long long prefix = sel_prefix;
+            for (int g = tid; g < C; g += 4 * kSelectThreads) {           // four loads in flight
+                unsigned long long key[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) key[j] = (unsigned long long)cand[min(g + j * kSelectThreads, C - 1)].R ^ 0x8000000000000000ull;
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    if (g + j * kSelectThreads < C && (shift == 56 || (key[j] >> (shift + 8)) == (prefix >> (shift + 8))))
+                        atomicAdd(&hist[(int)((key[j] >> shift) & 255)], 1);
+            }
+            __syncthreads();
+            if (tid < 64) {                               // the bin of the k-th largest among the keys that share the prefix: four bins a lane
+                const int4 h = *reinterpret_cast<const int4 *>(&hist[4 * tid]);
+                const int mine = h.x + h.y + h.z + h.w, k = sel_k;
+                int from_here = mine;                     // keys in the bins of this lane and of the lanes above
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_down(from_here, off); if (tid + off < 64) from_here += t; }
+                const int above = from_here - mine;
+                const bool holds = above < k && k <= from_here;
+                if (__ballot(holds) == 0ull) {            // k == 0 (a quota of 0): nothing is kept, whatever the bin
+                    if (tid == 0) sel_prefix = prefix | (255ull << shift);
+                } else if (holds) {
+                    int kk = k - above, bin = 3;
+                    if (h.w < kk) { kk -= h.w; bin = 2; if (h.z < kk) { kk -= h.z; bin = 1; if (h.y < kk) { kk -= h.y; bin = 0; } } }
+                    sel_prefix = prefix | ((unsigned long long)(4 * tid + bin) << shift);
+                    sel_k = kk;
+                }
+            }
+            __syncthreads();
+        }
+        star = sel_prefix;
+        need = sel_k;
+    }
+    uint4 *kept = reinterpret_cast<uint4 *>(a.kept + L.qprefix);
+    int n_kept = 0, n_ties = 0;
+    for (int g0 = 0; g0 < C; g0 += kSelectThreads) {
+        const int g = g0 + tid;
+        uint4 raw = make_uint4(0u, 0u, 0u, 0u);
+        bool keep = false, tie = false;
+        if (g < C) {
+            raw = flat[g];
+            const unsigned long long key = (((unsigned long long)raw.y << 32) | raw.x) ^ 0x8000000000000000ull;
+            keep = all || key > star;
+            tie = !all && key == star;
+        }
+        int ties_here, kept_here;
+        const int tie_rank = orb_block_excl(tie ? 1 : 0, scratch, &ties_here);
+        if (tie && n_ties + tie_rank < need) keep = true;
+        const int pos = orb_block_excl(keep ? 1 : 0, scratch, &kept_here);
+        if (keep && n_kept + pos < L.quota) kept[n_kept + pos] = raw;
+        n_ties += ties_here;
+        n_kept += kept_here;
+    }
+    if (tid == 0) counts_out[lv] = min(n_kept, L.quota);
+}
+
+// ------------------------------------------------------------------------------------------------ orb_moments
+// grid ceil(n_features / 4), block 256: wave i makes record i
+__global__ __launch_bounds__(kOrbThreads) void orb_moments(OrbArgs a)
+{
+    const int lane = threadIdx.x & 63;
+    const int i = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (kOrbThreads / 64) + (threadIdx.x >> 6)));
+    const int32_t *counts = reinterpret_cast<const int32_t *>(a.out);
+    int lv = -1, j = i;
+#pragma unroll
+    for (int l = 0; l < kOrbLevels; l++) {
+        const int n = counts[l];
+        if (lv < 0) { if (j < n) lv = l; else j -= n; }
+    }
+    if (lv < 0) return;                                   // wave-uniform
+    const OrbLevel &L = a.t.l[lv];
+    const uint4 c = *reinterpret_cast<const uint4 *>(a.kept + L.qprefix + j);   // R low, R high, raster
+    const int y = (int)c.z / L.w, x = (int)c.z - y * L.w;
+    const uint8_t *img = a.img + L.img_off;
+    const int xa = (x - 15) & ~3;                         // the aligned dword that holds column x - 15; nine dwords cover the row at most
+    const unsigned long long umax = 0x3689abcddeeeffffull;   // umax[|v|] = nibble |v|
+    int m10 = 0, m01 = 0;
+    for (int it = lane; it < 31 * 9; it += 64) {
+        const int r = it / 9, q = it - 9 * r, v = r - 15, col = xa + 4 * q;
+        if (col > x + 15) continue;
+        const uint32_t w = *reinterpret_cast<const uint32_t *>(img + (size_t)(y + v) * L.pitch + col);
+        const int um = (int)((umax >> (4 * (v < 0 ? -v : v))) & 15ull);
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const int u = col + b - x, I = (int)((w >> (8 * b)) & 255u);
+            if (u >= -um && u <= um) { m10 += u * I; m01 += v * I; }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { m10 += __shfl_xor(m10, off); m01 += __shfl_xor(m01, off); }
+    if (lane == 0) {
+        const float fx = (float)((double)x * L.scale), fy = (float)((double)y * L.scale);
+        uint4 *rec = reinterpret_cast<uint4 *>(a.out + kOutHeader + (size_t)i * sizeof(chip_orb_keypoint));
+        rec[0] = make_uint4(c.x, c.y, __float_as_uint(fx), __float_as_uint(fy));
+        rec[1] = make_uint4((uint32_t)m10, (uint32_t)m01, (uint32_t)x | ((uint32_t)y << 16), (uint32_t)lv);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+struct OrbState {
+    DevBuf<uint8_t> img;               // the levels, rows of pitch bytes
+    DevBuf<int16_t> score;             // the score planes, rows of spitch elements
+    DevBuf<OrbCand> cand;              // per level nstrips segments of cap candidates
+    DevBuf<int32_t> strip_count;
+    DevBuf<OrbCand> kept;              // CHIP_MATCH_MAX_KEYPOINTS
+    DevBuf<uint8_t> out;               // kOutHeader + CHIP_MATCH_MAX_KEYPOINTS records
+    PinnedBuf<uint8_t> h_out;
+    PinnedBuf<uint8_t> h_img;          // level 0 with its row pitch, for widths that are no multiple of 4
+    bool have = false;                 // a detect has finished: t describes what the buffers hold
+    OrbTable t{};
+};
+
+void orb_destroy(Ctx *c)
+{
+    delete c->orb_state;
+    c->orb_state = nullptr;
+}
+
+static int orb_params(const chip_orb_params *p, chip_orb_params *d)
+{
+    chip_orb_params_default(d);
+    if (p) *d = *p;
+    if (d->n_features < 1 || d->n_features > CHIP_MATCH_MAX_KEYPOINTS || d->n_levels < 1 || d->n_levels > kOrbLevels) return CHIP_ERR_UNSUPPORTED;
+    if (d->fast_threshold < 0 || d->fast_threshold > 255 || d->border < 16 || d->border > 64) return CHIP_ERR_UNSUPPORTED;
+    return CHIP_OK;
+}
+
+// the table of the header; the one place that decides sizes, quotas and rectangles
+static void orb_plan(int32_t width, int32_t height, const chip_orb_params &p, chip_orb_level lv[kOrbLevels])
+{
+    std::memset(lv, 0, sizeof(chip_orb_level) * kOrbLevels);
+    const double f = 1.0 / 1.2;
+    double g = 1.0;
+    for (int l = 0; l < p.n_levels; l++) g *= f;
+    double nd = (double)p.n_features * (1.0 - f) / (1.0 - g), s = 1.0;
+    int sum = 0;
+    for (int l = 0; l < p.n_levels; l++) {
+        if (l > 0) s *= 1.2;
+        chip_orb_level &L = lv[l];
+        L.scale = s;
+        L.width = (int32_t)std::floor((double)width / s + 0.5);
+        L.height = (int32_t)std::floor((double)height / s + 0.5);
+        if (l < p.n_levels - 1) {
+            L.quota = (int32_t)std::floor(nd + 0.5);
+            if (L.quota > p.n_features - sum) L.quota = p.n_features - sum;   // the rounded quotas never exceed n_features together
+            sum += L.quota;
+            nd *= f;
+        } else {
+            L.quota = p.n_features - sum > 0 ? p.n_features - sum : 0;
+        }
+        L.x0 = L.y0 = p.border; L.x1 = L.width - 1 - p.border; L.y1 = L.height - 1 - p.border;
+        if (L.x1 < L.x0 || L.y1 < L.y0) { L.x0 = L.y0 = 0; L.x1 = L.y1 = -1; }
+    }
+}
+
+static hipStream_t orb_stream(Ctx *c)
+{
+    std::lock_guard<std::mutex> lk(c->query_mu);   // chip_set_stream swaps the ctx stream under this lock
+    return c->s_query;
+}
+
+}  // namespace chip
+
+using namespace chip;
+
+extern "C" int chip_build_has_orb_detect(void) { return 1; }
+
+extern "C" void chip_orb_params_default(chip_orb_params *p)
+{
+    if (p) *p = chip_orb_params{5000, 8, 0, 31};   // cv::ORB::create(5000), setFastThreshold(0)
+}
+
+static int orb_check_size(int32_t width, int32_t height, const chip_orb_params *p, chip_orb_params *d)
+{
+    if (width < 1 || height < 1) return CHIP_ERR_INVALID_ARG;
+    const int rc = orb_params(p, d);
+    if (rc != CHIP_OK) return rc;
+    if (width > kOrbMaxSide || height > kOrbMaxSide) return CHIP_ERR_UNSUPPORTED;
+    return CHIP_OK;
+}
+
+extern "C" int chip_orb_plan(int32_t width, int32_t height, const chip_orb_params *p, chip_orb_level levels[8])
+{
+    if (!levels) return CHIP_ERR_INVALID_ARG;
+    chip_orb_params d;
+    const int rc = orb_check_size(width, height, p, &d);
+    if (rc != CHIP_OK) return rc;
+    orb_plan(width, height, d, levels);
+    return CHIP_OK;
+}
+
+extern "C" int chip_orb_detect(chip_ctx *c, const uint8_t *image, int32_t width, int32_t height, const chip_orb_params *p,
+                               chip_orb_keypoint *kp, int32_t capacity, int32_t *n, int32_t level_counts[8])
+{
+    if (!c || !image || !kp || !n) return CHIP_ERR_INVALID_ARG;
+    chip_orb_params d;
+    int rc = orb_check_size(width, height, p, &d);
+    if (rc != CHIP_OK) return rc;
+    if (capacity < d.n_features) return CHIP_ERR_INVALID_ARG;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    chip_orb_level plan[kOrbLevels];
+    orb_plan(width, height, d, plan);
+    // the launch table: where every level lives in the ctx's buffers
+    OrbTable t{};
+    t.n_levels = d.n_levels; t.n_features = d.n_features; t.threshold = d.fast_threshold;
+    size_t img_n = 0, score_n = 0, cand_n = 0, strip_n = 0;
+    int qprefix = 0, max_w = 0, max_h = 0, max_strips = 0;
+    for (int l = 0; l < d.n_levels; l++) {
+        OrbLevel &L = t.l[l];
+        L.w = plan[l].width; L.h = plan[l].height; L.scale = plan[l].scale;
+        L.pitch = (L.w + 3) & ~3; L.spitch = (L.w + 7) & ~7;
+        L.x0 = plan[l].x0; L.y0 = plan[l].y0; L.x1 = plan[l].x1; L.y1 = plan[l].y1;
+        L.quota = plan[l].quota; L.qprefix = qprefix; qprefix += L.quota;
+        const bool area = L.x1 >= L.x0;
+        L.cap = area ? (L.x1 - L.x0 + 2) / 2 : 0;
+        L.nstrips = area ? (L.y1 - L.y0 + kStripRows) / kStripRows : 0;
+        L.img_off = (uint32_t)img_n; L.score_off = (uint32_t)score_n; L.cand_off = (uint32_t)cand_n; L.strip_off = (uint32_t)strip_n;
+        img_n += ((size_t)L.pitch * L.h + 15) & ~(size_t)15;
+        score_n += (size_t)L.spitch * L.h;               // a multiple of 8 elements: every plane starts on 16 bytes
+        cand_n += (size_t)L.cap * L.nstrips;
+        strip_n += (size_t)L.nstrips;
+        max_w = L.spitch > max_w ? L.spitch : max_w; max_h = L.h > max_h ? L.h : max_h;
+        max_strips = L.nstrips > max_strips ? L.nstrips : max_strips;
+    }
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    CHIP_HIP(c, hipSetDevice(c->device));
+    if (!c->orb_state) {
+        c->orb_state = new (std::nothrow) OrbState();
+        if (!c->orb_state) return CHIP_ERR_OOM;
+    }
+    OrbState *st = c->orb_state;
+    st->have = false;
+    const size_t out_bytes = kOutHeader + (size_t)CHIP_MATCH_MAX_KEYPOINTS * sizeof(chip_orb_keypoint);
+    const size_t h_img_n = t.l[0].pitch == t.l[0].w ? 0 : (size_t)t.l[0].pitch * t.l[0].h;   // a width that is no multiple of 4 only
+    if (st->img.capacity() < img_n || st->score.capacity() < score_n || st->cand.capacity() < cand_n + 1 || st->strip_count.capacity() < strip_n + 1 ||
+        !st->h_out.capacity() || st->h_img.capacity() < h_img_n) {
+        ResidentPause paused(c);   // one pause over the group, as the GMS mode tables
+        rc = st->img.reserve(c, img_n);
+        if (rc == CHIP_OK) rc = st->score.reserve(c, score_n);
+        if (rc == CHIP_OK) rc = st->cand.reserve(c, cand_n + 1);
+        if (rc == CHIP_OK) rc = st->strip_count.reserve(c, strip_n + 1);
+        if (rc == CHIP_OK) rc = st->kept.reserve(c, CHIP_MATCH_MAX_KEYPOINTS);
+        if (rc == CHIP_OK) rc = st->out.reserve(c, out_bytes);
+        if (rc == CHIP_OK) rc = st->h_out.reserve(c, out_bytes);
+        if (rc == CHIP_OK) rc = st->h_img.reserve(c, h_img_n);
+        if (rc != CHIP_OK) return rc;
+    }
+    OrbArgs a;
+    a.img = st->img; a.score = st->score; a.cand = st->cand; a.strip_count = st->strip_count; a.kept = st->kept; a.out = st->out; a.t = t;
+    hipStream_t s = orb_stream(c);
+    const OrbLevel &L0 = t.l[0];
+    if (L0.pitch == L0.w) {
+        CHIP_HIP(c, hipMemcpyAsync(a.img, image, (size_t)width * height, hipMemcpyHostToDevice, s));
+    } else {   // rows of pitch bytes are made on the host, in pinned memory (the previous call has finished: every call ends in a wait)
+        uint8_t *rows = st->h_img.host();
+        for (int y = 0; y < height; y++) std::memcpy(rows + (size_t)y * L0.pitch, image + (size_t)y * width, (size_t)width);
+        CHIP_HIP(c, hipMemcpyAsync(a.img, rows, (size_t)L0.pitch * height, hipMemcpyHostToDevice, s));
+    }
+    for (int l = 1; l < d.n_levels; l++) {
+        const OrbLevel &L = t.l[l];
+        if (L.w < 1 || L.h < 1) break;                    // sizes only shrink: nothing above either
+        hipLaunchKernelGGL(orb_pyramid, dim3((L.pitch / 4 + 63) / 64, (L.h + 3) / 4), dim3(64, 4), 0, s, a, l);
+        CHIP_HIP(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(orb_fast_score, dim3((max_w + kScoreTileW - 1) / kScoreTileW, (max_h + kScoreTileH - 1) / kScoreTileH, d.n_levels),
+                       dim3(kOrbThreads), 0, s, a);
+    CHIP_HIP(c, hipGetLastError());
+    if (max_strips > 0) {
+        hipLaunchKernelGGL(orb_candidates, dim3(max_strips, d.n_levels), dim3(kOrbThreads), 0, s, a);
+        CHIP_HIP(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(orb_select, dim3(kOrbLevels), dim3(kSelectThreads), 0, s, a);
+    CHIP_HIP(c, hipGetLastError());
+    hipLaunchKernelGGL(orb_moments, dim3((d.n_features + kOrbThreads / 64 - 1) / (kOrbThreads / 64)), dim3(kOrbThreads), 0, s, a);
+    CHIP_HIP(c, hipGetLastError());
+    const size_t back = kOutHeader + (size_t)d.n_features * sizeof(chip_orb_keypoint);
+    CHIP_HIP(c, hipMemcpyAsync(st->h_out.host(), a.out, back, hipMemcpyDeviceToHost, s));
+    CHIP_HIP(c, hipStreamSynchronize(s));
+    const int32_t *counts = reinterpret_cast<const int32_t *>(st->h_out.host());
+    int32_t total = 0;
+    for (int l = 0; l < kOrbLevels; l++) {
+        total += counts[l];
+        if (level_counts) level_counts[l] = counts[l];
+    }
+    if (total < 0 || total > d.n_features) return CHIP_ERR_HIP;   // cannot happen: the kept lists are bounded by the quotas
+    std::memcpy(kp, st->h_out.host() + kOutHeader, (size_t)total * sizeof(chip_orb_keypoint));
+    *n = total;
+    st->t = t;
+    st->have = true;
+    return CHIP_OK;
+}
+
+extern "C" int chip_debug_orb_level(chip_ctx *c, int32_t level, uint8_t *image_out, int16_t *score_out)
+{
+    if (!c) return CHIP_ERR_INVALID_ARG;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    OrbState *st = c->orb_state;
+    if (!st || !st->have) return CHIP_ERR_BUSY;
+    if (level < 0 || level >= st->t.n_levels) return CHIP_ERR_RANGE;
+    const OrbLevel &L = st->t.l[level];
+    if (L.w < 1 || L.h < 1) return CHIP_OK;               // an empty level: nothing to deliver
+    CHIP_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = orb_stream(c);
+    if (image_out)
+        CHIP_HIP(c, hipMemcpy2DAsync(image_out, (size_t)L.w, st->img.get() + L.img_off, (size_t)L.pitch, (size_t)L.w, (size_t)L.h, hipMemcpyDeviceToHost, s));
+    if (score_out)
+        CHIP_HIP(c, hipMemcpy2DAsync(score_out, (size_t)L.w * 2, st->score.get() + L.score_off, (size_t)L.spitch * 2, (size_t)L.w * 2, (size_t)L.h,
+                                     hipMemcpyDeviceToHost, s));
+    CHIP_HIP(c, hipStreamSynchronize(s));
+    return CHIP_OK;
+}

@@ -528,7 +528,8 @@ int chip_debug_pnp_keep_stage(chip_ctx *ctx, int32_t on);
  *   the "< 150 matches" reject and pf_matches                           src/Cerebro.cpp:1487,1505
  *   make_3d_2d_collection__using__pfmatches_and_disparity (a->b, b->a)  PointFeatureMatching.cpp:95-154, Cerebro.cpp:1512,1566
  *   make_3d_3d_collection__using__pfmatches_and_disparity               PointFeatureMatching.cpp:159-195, Cerebro.cpp:1624
- * ORB detection / description, rectification and the depth images stay with the caller (OpenCV).  Everything here is integer or
+ * ORB description (cv::ORB::compute) and rectification stay with the caller (OpenCV); detection is chip_orb_detect and the depth
+ * images are chip_frame_put_disparity / chip_frame_put_stereo, all below.  Everything here is integer or
  * single-operation IEEE arithmetic: the device results equal a CPU restatement (tests/np_mirror_match.py) bit for bit.
  *
  * Definitions (this library's, stated where the reference leans on OpenCV or leaves behaviour undefined):
@@ -893,6 +894,89 @@ int chip_stereo_bm(chip_ctx *ctx, const uint8_t *left, const uint8_t *right /* h
 int chip_frame_put_stereo(chip_ctx *ctx, int64_t id, const uint8_t *desc /* n x 32 */, const float *kp_xy /* n x 2 */, int32_t n,
                           int32_t width, int32_t height, const uint8_t *left, const uint8_t *right /* height x width each */,
                           const chip_stereo_bm_params *p /* NULL: the defaults */, const double Q_rowmajor[16]);
+
+/* ---- ORB keypoint detection on the device: FAST-9, Harris ranking, up to 8 pyramid levels (ABI 7, additive).  The kp_xy every
+ * chip_frame_put* takes is the detector half of cv::ORB::create(5000) with setFastThreshold(0) on the rectified left image
+ * (src/utils/PointFeatureMatching.cpp:16-22, on both frames of every candidate).  chip_orb_detect is that half: the pyramid, the FAST
+ * score, the Harris ranking with per-level quotas and the patch moments the orientation is made of.  The descriptor half (blur,
+ * steered BRIEF) is NOT built: the caller runs cv::ORB::compute on these keypoints.
+ *
+ * THE DEFINITION IS THIS PROJECT'S OWN, modelled on cv::ORB::detect with HARRIS_SCORE.  OpenCV's source is not part of this project,
+ * so parity against it is UNPINNED (DESIGN.md 6 lists the known departures).  All image arithmetic is integer; the device results
+ * equal a CPU restatement (tests/np_mirror_orb_detect.py) bit for bit.
+ *   - parameters (chip_orb_params, four int32_t, 16 bytes); a value outside is CHIP_ERR_UNSUPPORTED:  n_features 5000
+ *     (1 .. CHIP_MATCH_MAX_KEYPOINTS);  n_levels 8 (1 .. CHIP_ORB_MAX_LEVELS; the scale factor is fixed at 1.2);  fast_threshold 0
+ *     (PointFeatureMatching.cpp:18; 0 .. 255);  border 31 (ORB's edgeThreshold; 16 .. 64);
+ *   - levels: s_0 = 1.0, s_l = s_(l-1) * 1.2 in double; w_l = (int)floor(w / s_l + 0.5), h_l alike (a level may have a side of 0: it
+ *     holds nothing);
+ *   - quotas: f = 1.0 / 1.2; g = 1.0 multiplied by f n_levels times (no pow); nd = n_features * (1 - f) / (1 - g); for l < n_levels - 1
+ *     quota_l = min((int)floor(nd + 0.5), n_features - sum), then nd *= f; the last level gets n_features - sum: the quotas sum to
+ *     n_features (without the min the rounding gives 8 for n_features = 7 on 8 levels, the one such case up to 16384).  A level
+ *     without a detection area keeps its quota: nothing is redistributed;
+ *   - chip_orb_plan: exactly the table a launch uses, without a ctx or a device: width, height, quota, the detection rectangle
+ *     border <= x <= w_l - 1 - border, border <= y <= h_l - 1 - border as x0, y0, x1, y1 (an empty one is 0, 0, -1, -1) and s_l.
+ *     Entries from n_levels on are zero.  The statuses are those of chip_orb_detect for width, height and p;
+ *   - pyramid: level 0 is the image.  Level l is made from level l - 1 by fixed-point bilinear sampling at pixel centres:
+ *     X = ((2x + 1) * w_(l-1) * 1024) / w_l - 1024 (a 64-bit integer division; units of 1/2048 pixel), clamped to
+ *     [0, (w_(l-1) - 1) * 2048]; x0 = X >> 11, a = X & 2047, x1 = min(x0 + 1, w_(l-1) - 1); the same in y with b;
+ *     value = (I[y0][x0] (2048 - a)(2048 - b) + I[y0][x1] a (2048 - b) + I[y1][x0] (2048 - a) b + I[y1][x1] a b + (1 << 21)) >> 22;
+ *   - FAST score S, at every pixel at least 3 from each edge of its level.  The ring k = 0..15 as (dx, dy):
+ *       (0,-3) (1,-3) (2,-2) (3,-1) (3,0) (3,1) (2,2) (1,3) (0,3) (-1,3) (-2,2) (-3,1) (-3,0) (-3,-1) (-2,-2) (-1,-3)
+ *     b = the maximum over the 16 cyclic arcs of 9 consecutive ring pixels of the minimum over the arc of I_k - I_p, d = the same with
+ *     I_p - I_k, S = max(b, d) - 1 in [-256, 254].  A pixel is a corner at threshold t iff S >= t; a flat region has S = -1.  Where S
+ *     is not defined the score plane holds -256;
+ *   - candidates: the pixels of the detection rectangle with S >= fast_threshold and S strictly greater than the S of all eight
+ *     neighbours (a plateau of equal scores keeps nothing);
+ *   - Harris key: Ix = 2 (I[y][x+1] - I[y][x-1]) + (I[y-1][x+1] - I[y-1][x-1]) + (I[y+1][x+1] - I[y+1][x-1]), Iy = Ix transposed;
+ *     a = sum Ix^2, bb = sum Iy^2, c = sum Ix Iy over the 7 x 7 block centred on the candidate (int32); R = 25 (a bb - c c) -
+ *     (a + bb)^2 exactly in int64: Harris with k = 0.04, times 25;
+ *   - selection: per level the quota_l candidates of largest R, or all if there are fewer; ties go to the lower raster index
+ *     y w_l + x.  Output order: level ascending, raster order inside a level.  level_counts: the kept count per level (0 from
+ *     n_levels on);
+ *   - moments: m10 = sum u I, m01 = sum v I over v in [-15, 15], u in [-umax(|v|), umax(|v|)],
+ *     umax[0..15] = 15 15 15 15 14 14 14 13 13 12 11 10 9 8 6 3 (749 pixels), int32.  The caller's orientation is
+ *     atan2(m01, m10); the library computes no angle;
+ *   - record (chip_orb_keypoint, 32 bytes): response = R; x, y = (float)((double)x_level * s_l), (float)((double)y_level * s_l);
+ *     m10, m01; x_level, y_level, level; zero = 0;
+ *   - kernels: orb_pyramid (one launch per level above 0: a level needs the one before), then four launches whatever n_levels, with
+ *     the level table in the kernel arguments and the level on a grid axis: orb_fast_score (LDS tile of 128 x 16 pixels with a halo,
+ *     eight pixels per thread, one 16-byte store each), orb_candidates (one workgroup per strip of two rows of the detection
+ *     rectangle: ordered compaction of the strict maxima, Harris for those only), orb_select (one workgroup per level: radix select
+ *     of the quota_l-th largest R over LDS histograms, ordered compaction) and orb_moments (one wave per kept keypoint, two 16-byte
+ *     stores per record).  Counts and thresholds stay in device memory; one device-to-host copy of records and counts ends the call;
+ *   - statuses, all decided before anything touches the device: NULL ctx / image / kp / n, a side < 1 or capacity < n_features
+ *     CHIP_ERR_INVALID_ARG; a parameter outside its range, a side above CHIP_ORB_MAX_SIDE or a group ctx CHIP_ERR_UNSUPPORTED.  An
+ *     image too small to hold a detection area is no error: *n = 0;
+ *   - chip_debug_orb_level: the pyramid level (h_l x w_l, dense rows) and the FAST score plane (h_l x w_l int16) the last
+ *     chip_orb_detect of the ctx left behind; either pointer may be NULL.  CHIP_ERR_BUSY if there is none, CHIP_ERR_RANGE for a
+ *     level that call did not have.  It launches nothing.
+ * Needs no frame store; runs on the ctx stream, serialised with the other calls of the stage.  The device buffers are grown on first
+ * use or on a larger image inside one pause of the resident scan; a process that never calls it allocates nothing.                 */
+#define CHIP_ORB_MAX_LEVELS 8
+#define CHIP_ORB_MAX_SIDE 4096
+typedef struct {
+    int32_t n_features;          /* 5000: 1 .. CHIP_MATCH_MAX_KEYPOINTS */
+    int32_t n_levels;            /* 8: 1 .. CHIP_ORB_MAX_LEVELS; scale factor fixed at 1.2 */
+    int32_t fast_threshold;      /* 0 (PointFeatureMatching.cpp:18): 0 .. 255 */
+    int32_t border;              /* 31 (ORB's edgeThreshold): 16 .. 64 */
+} chip_orb_params;
+typedef struct {
+    int64_t response;            /* R, exact */
+    float x, y;                  /* level-0 coordinates: (float)((double)x_level * s_l) */
+    int32_t m10, m01;            /* patch moments */
+    uint16_t x_level, y_level, level, zero;
+} chip_orb_keypoint;
+typedef struct {
+    int32_t width, height, quota, x0, y0, x1, y1;
+    double scale;
+} chip_orb_level;
+void chip_orb_params_default(chip_orb_params *p);
+int chip_build_has_orb_detect(void);       /* 1 */
+int chip_orb_plan(int32_t width, int32_t height, const chip_orb_params *p /* NULL: the defaults */, chip_orb_level levels[8]);
+int chip_orb_detect(chip_ctx *ctx, const uint8_t *image /* height x width, dense rows */, int32_t width, int32_t height,
+                    const chip_orb_params *p /* NULL: the defaults */, chip_orb_keypoint *kp, int32_t capacity, int32_t *n,
+                    int32_t level_counts[8] /* may be NULL */);
+int chip_debug_orb_level(chip_ctx *ctx, int32_t level, uint8_t *image_out /* h_l x w_l */, int16_t *score_out /* h_l x w_l */);
 
 /* ------------------------------------------------------------------------------------------ introspection */
 typedef struct {

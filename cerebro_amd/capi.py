@@ -76,6 +76,7 @@ CHIP_STEREO_BM_NUM_DISPARITIES, CHIP_STEREO_BM_BLOCK_SIZE, CHIP_STEREO_BM_PREFIL
 CHIP_STEREO_BM_TEXTURE_THRESHOLD, CHIP_STEREO_BM_UNIQUENESS_RATIO = 10, 15
 # chip_orb_params' defaults: cv::ORB::create(5000) with setFastThreshold(0)
 CHIP_ORB_MAX_LEVELS, CHIP_ORB_MAX_SIDE = 8, 4096
+CHIP_ORB_BINS = 32
 CHIP_ORB_N_FEATURES, CHIP_ORB_N_LEVELS, CHIP_ORB_FAST_THRESHOLD, CHIP_ORB_BORDER = 5000, 8, 0, 31
 
 
@@ -307,6 +308,14 @@ _SIGS = {
     "chip_orb_plan": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(OrbParams), C.POINTER(OrbLevel)]),
     "chip_orb_detect": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(OrbParams), _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "chip_debug_orb_level": (C.c_int, [_P, C.c_int32, _P, _P]),
+    "chip_build_has_orb_describe": (C.c_int, []),
+    "chip_orb_bin": (C.c_int, [C.c_int32, C.c_int32]),
+    "chip_orb_pattern": (C.c_int, [_P, _P]),
+    "chip_orb_detect_describe": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(OrbParams), _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                           _P]),
+    "chip_debug_orb_blur": (C.c_int, [_P, C.c_int32, _P]),
+    "chip_frame_put_orb_stereo": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.POINTER(OrbParams), C.POINTER(StereoBmParams), _P,
+                                            C.POINTER(C.c_int32)]),
     "chip_get_info": (C.c_int, [_P, C.POINTER(Info)]),
     "chip_profile_enable": (C.c_int, [_P, C.c_int32]),
     "chip_profile_reset": (C.c_int, [_P]),
@@ -410,6 +419,20 @@ def _orb_params(params):
     if isinstance(params, dict):
         params = default_orb_params(**params)
     return params, (None if params is None else C.byref(params))
+
+
+def orb_bin(m10: int, m01: int) -> int:
+    """chip_orb_bin: the orientation bin (0 .. 31) of a keypoint's moments; no ctx, no device"""
+    return int(load_library().chip_orb_bin(m10, m01))
+
+
+def orb_pattern():
+    """chip_orb_pattern -> (the (256, 4) int8 pairs x1, y1, x2, y2, the (32, 256, 4) int8 steered table); no ctx, no device"""
+    pattern, steered = np.zeros((256, 4), dtype=np.int8), np.zeros((CHIP_ORB_BINS, 256, 4), dtype=np.int8)
+    rc = load_library().chip_orb_pattern(_ptr(pattern), _ptr(steered))
+    if rc != CHIP_OK:
+        raise ChipError(rc, "chip_orb_pattern")
+    return pattern, steered
 
 
 def orb_plan(width: int, height: int, params=None) -> list:
@@ -1163,6 +1186,39 @@ class Chip:
         self._chk(self.lib.chip_debug_orb_level(self.h, level, _ptr(img) if img.size else None, _ptr(score) if score.size else None),
                   "chip_debug_orb_level")
         return img, score
+
+    def orb_detect_describe(self, image, params=None):
+        """chip_orb_detect_describe on the (H, W) uint8 image -> (the records of orb_detect, level_counts[8], the (n, 32) uint8
+        descriptors, row i that of record i)"""
+        img = np.ascontiguousarray(image, dtype=np.uint8)
+        assert img.ndim == 2
+        params, p = _orb_params(params)
+        cap = CHIP_ORB_N_FEATURES if params is None else max(int(params.n_features), 1)
+        kp = np.zeros(cap, dtype=ORB_KEYPOINT_DTYPE)
+        desc = np.zeros((cap, CHIP_ORB_DESC_BYTES), dtype=np.uint8)
+        n = C.c_int32()
+        counts = (C.c_int32 * CHIP_ORB_MAX_LEVELS)()
+        self._chk(self.lib.chip_orb_detect_describe(self.h, _ptr(img), img.shape[1], img.shape[0], p, _ptr(kp), cap, C.byref(n), counts, _ptr(desc)),
+                  "chip_orb_detect_describe")
+        return kp[:n.value].copy(), list(counts), desc[:n.value].copy()
+
+    def orb_blur(self, level: int, width: int, height: int) -> np.ndarray:
+        """chip_debug_orb_blur -> the (height, width) uint8 blurred plane of a level the last orb_detect_describe or
+        frame_put_orb_stereo left behind; width and height are that level's (orb_plan)"""
+        out = np.zeros((height, width), dtype=np.uint8)
+        self._chk(self.lib.chip_debug_orb_blur(self.h, level, _ptr(out) if out.size else None), "chip_debug_orb_blur")
+        return out
+
+    def frame_put_orb_stereo(self, id: int, left, right, Q: np.ndarray, orb=None, bm=None) -> int:
+        """chip_frame_put_orb_stereo: store (or replace) under id the frame the detector and the descriptor make of the rectified (H, W)
+        uint8 left image, with the 3-D points the block matcher makes at its keypoints -> the number of keypoints kept"""
+        l, r, b = self._stereo_pair(left, right, bm)
+        _, o = _orb_params(orb)
+        Qd = np.ascontiguousarray(Q, dtype=np.float64).reshape(16)
+        n = C.c_int32()
+        self._chk(self.lib.chip_frame_put_orb_stereo(self.h, id, l.shape[1], l.shape[0], _ptr(l), _ptr(r), o, b, _ptr(Qd), C.byref(n)),
+                  "chip_frame_put_orb_stereo")
+        return n.value
 
     def frame_drop(self, id: int):
         self._chk(self.lib.chip_frame_drop(self.h, id), "chip_frame_drop")

@@ -585,6 +585,15 @@ void icp_destroy(Ctx *c);
 void batch_destroy(Ctx *c);
 void match_destroy(Ctx *c);   // match.hip
 void orb_destroy(Ctx *c);     // orb.hip
+// orb.hip in pieces, so that match.hip can put a frame straight from its pair (chip_frame_put_orb_stereo).  orb_check: the statuses of
+// chip_orb_detect for the size and the parameters, d the parameters in force.  orb_enqueue: the detector and (describe) the descriptor of
+// one image -- host memory, or device memory with dense rows -- enqueued on s up to the copy of the first `back` bytes of its output
+// (eight int32 kept counts, then the records) into pinned memory; orb_describe writes to desc_dev / kp_dev (null: the state's own
+// buffer / nowhere).  orb_finished, once s has drained: the kept total and the counts.  The caller holds match_mu throughout.
+int orb_check(int32_t width, int32_t height, const chip_orb_params *p, chip_orb_params *d);
+int orb_enqueue(Ctx *c, hipStream_t s, const uint8_t *image, const uint8_t *image_dev, int32_t width, int32_t height, const chip_orb_params &d,
+                bool describe, uint8_t *desc_dev, float2 *kp_dev, size_t back);
+int orb_finished(Ctx *c, bool describe, int32_t n_features, int32_t *total, int32_t level_counts[8]);
 // the solvers on correspondence sets that already are in device memory (match.hip's sets): same kernels, same results as the
 // host-pointer entries chip_pnp_ransac / chip_icp_ransac; the caller has validated the arguments and holds match_mu
 int pnp_ransac_device(Ctx *c, const double *X_dev, const double *uv_dev, int32_t N, const chip_ransac_params *p, double *T_colmajor,

@@ -2008,6 +2008,78 @@ extern "C" int chip_frame_put_stereo(chip_ctx *c, int64_t id, const uint8_t *des
     return frame_put(c, id, &f, CHIP_DISP_S16, &q, right, &b);
 }
 
+// A frame from its rectified pair and nothing else: the detector and the descriptor (orb.hip) run on the left image where the pair is
+// staged, orb_describe writes the slot's descriptor and keypoint rows, and the block matcher makes the records as in frame_put.  What
+// comes back is the eight kept counts.
+extern "C" int chip_frame_put_orb_stereo(chip_ctx *c, int64_t id, int32_t width, int32_t height, const uint8_t *left, const uint8_t *right,
+                                         const chip_orb_params *orb, const chip_stereo_bm_params *bm, const double Q_rowmajor[16], int32_t *n)
+{
+    if (!c || !left || !right || !Q_rowmajor || !n) return CHIP_ERR_INVALID_ARG;
+    chip_orb_params d;
+    int rc = orb_check(width, height, orb, &d);
+    if (rc != CHIP_OK) return rc;
+    BmParams b;
+    rc = bm_params(bm, &b);
+    if (rc != CHIP_OK) return rc;
+    const DispQ q = disp_q(Q_rowmajor);
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    MatchState *st = c->match_state;
+    if (!st || st->n_slots == 0) return CHIP_ERR_BUSY;
+    if (d.n_features > st->slot_kp) return CHIP_ERR_UNSUPPORTED;   // the slot must hold whatever the detector keeps
+    const auto known = st->slot_of.find(id);
+    int32_t k = known != st->slot_of.end() ? known->second : -1;
+    const bool replace = k >= 0;
+    for (int32_t j = 0; k < 0 && j < st->n_slots; j++)
+        if (!st->slots[(size_t)j].used) k = j;
+    if (k < 0) return CHIP_ERR_OOM;
+    CHIP_HIP(c, hipSetDevice(c->device));
+    const size_t px = (size_t)width * height, at = (size_t)k * (size_t)st->slot_kp;
+    rc = st->stage_xyz.reserve(c, (2 * px + sizeof(float) - 1) / sizeof(float));
+    if (rc == CHIP_OK) rc = st->bm_pre.reserve(c, 2 * px + kBmPad);
+    if (rc != CHIP_OK) return rc;
+    hipStream_t s = match_stream(c);
+    uint8_t *stage = reinterpret_cast<uint8_t *>(st->stage_xyz.get());
+    int32_t total = 0;
+    const auto run = [&]() -> int {
+        CHIP_HIP(c, hipMemcpyAsync(stage, left, px, hipMemcpyHostToDevice, s));
+        CHIP_HIP(c, hipMemcpyAsync(stage + px, right, px, hipMemcpyHostToDevice, s));
+        const int e = orb_enqueue(c, s, nullptr, stage, width, height, d, true, st->store_desc + at * CHIP_ORB_DESC_BYTES, st->store_kp + at,
+                                  8 * sizeof(int32_t));
+        if (e != CHIP_OK) return e;
+        CHIP_HIP(c, launch_bm_prefilter(st, s, width, height, b));   // runs while the counts travel
+        CHIP_HIP(c, hipStreamSynchronize(s));
+        const int f = orb_finished(c, true, d.n_features, &total, nullptr);
+        if (f != CHIP_OK || total == 0) return f;
+        BmKeypointArgs g;
+        g.kp = st->store_kp + at; g.pre = st->bm_pre; g.rec = st->store_rec + at; g.n = total; g.w = width; g.h = height;
+        g.b = b; g.q = q;
+        hipLaunchKernelGGL(bm_keypoints, dim3((total + kBmWaves - 1) / kBmWaves), dim3(kBmThreads), 0, s, g);
+        CHIP_HIP(c, hipGetLastError());
+        CHIP_HIP(c, hipStreamSynchronize(s));
+        return CHIP_OK;
+    };
+    rc = run();
+    if (rc != CHIP_OK) {
+        // CHIP_ERR_OOM: a buffer of the detector could not grow, which is decided before its first launch -- the slot is as it was.
+        // Anything else: the slot's rows are undefined now, and the id leaves the store
+        if (replace && rc != CHIP_ERR_OOM) {
+            st->slots[(size_t)k] = MatchState::StoredFrame();
+            st->slot_of.erase(id);
+            st->n_frames--;
+        }
+        return rc;
+    }
+    MatchState::StoredFrame &slot = st->slots[(size_t)k];
+    slot.id = id; slot.n = total; slot.w = width; slot.h = height; slot.used = true;
+    if (!replace) {
+        st->slot_of[id] = k;
+        st->n_frames++;
+    }
+    *n = total;
+    return CHIP_OK;
+}
+
 extern "C" int chip_stereo_bm(chip_ctx *c, const uint8_t *left, const uint8_t *right, int32_t width, int32_t height,
                               const chip_stereo_bm_params *p, int16_t *disparity)
 {

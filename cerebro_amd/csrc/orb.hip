@@ -18,11 +18,24 @@
 //   orb_moments    : one wave per kept keypoint over all levels: the level of output i from the eight kept counts, the 31 rows of the
 //                    patch as aligned dwords, one wave reduction, two 16-byte stores per record.
 //
-// Nothing returns to the host between the stages; the records and the eight counts leave in ONE copy at the end.
+//
+// ... and the descriptor half ("ORB descriptors on the device" in the header; tests/np_mirror_orb_describe.py), after orb_moments on the
+// same stream, only in a describing call (chip_orb_detect_describe, chip_frame_put_orb_stereo):
+//   orb_blur       : all levels in one launch (level = blockIdx.z).  A workgroup stages 38 rows x 136 bytes (a tile of 128 x 32 pixels with
+//                    its halo of 3, rows as whole dwords, the clamps applied while staging) in LDS, makes the 16-bit horizontal sums of
+//                    the 38 rows into a second LDS plane, then a thread sums seven rows for 16 pixels and stores them as one 16-byte store
+//                    (the blurred planes have a pitch of their own, a multiple of 16).
+//   orb_describe   : one wave per kept keypoint: the bin from the record's moments (lanes 0 .. 31 one int64 product sum each, one wave
+//                    reduction), the lane's four steered pairs in one 16-byte load, eight byte gathers, four ballots, two 16-byte stores.
+//
+// Nothing returns to the host between the stages; the records and the eight counts leave in ONE copy at the end (the descriptors of
+// chip_orb_detect_describe in one more).
 #include "chip_internal.h"
 #include <cmath>
 #include <cstring>
+#include <mutex>
 #include <new>
+#include <vector>
 
 namespace chip {
 
@@ -392,6 +405,136 @@ __global__ __launch_bounds__(kOrbThreads) void orb_moments(OrbArgs a)
     }
 }
 
+// ------------------------------------------------------------------------------------------------ orb_blur
+constexpr int kBlurTileW = 128, kBlurTileH = 32;         // pixels of a blur tile: 8 x 32 threads of sixteen pixels in a row each
+constexpr int kBlurRows = kBlurTileH + 6;                // 38
+constexpr int kBlurDwords = (kBlurTileW + 8) / 4;        // 34 dwords a row: the tile's columns - 4 .. + 131
+constexpr int kBlurHPitch = kBlurTileW + 8;              // uint16 a row of horizontal sums; + 8: rows start 16 bytes apart in the banks
+constexpr int kDescWaves = kOrbThreads / 64;
+constexpr int kOrbTabHeader = 256;                       // bytes: C[32], S[32] as int32 in front of the steered table
+struct OrbBlurLevel { int32_t w, h, pitch, bpitch; uint32_t img_off, blur_off; };   // bpitch: a multiple of 16; the offsets in bytes
+struct OrbBlurArgs {
+    const uint8_t *img;
+    uint8_t *blur;
+    OrbBlurLevel l[kOrbLevels];
+};
+// the dword of row `row` (pitch bytes, w pixels) at columns gx .. gx + 3 with the column clamped into the row; gx is a multiple of 4
+__device__ __forceinline__ uint32_t orb_clamped_dword(const uint8_t *row, int gx, int w)
+{
+    const int last_at = (w - 1) & ~3;
+    const uint32_t d = *reinterpret_cast<const uint32_t *>(row + min(max(gx, 0), last_at));
+    if (gx < 0) return (d & 255u) * 0x01010101u;
+    if (gx + 3 < w) return d;
+    const uint32_t last = (*reinterpret_cast<const uint32_t *>(row + last_at) >> (8 * ((w - 1) & 3))) & 255u;
+    uint32_t v = 0;
+#pragma unroll
+    for (int b = 0; b < 4; b++) v |= (gx + b < w ? (d >> (8 * b)) & 255u : last) << (8 * b);
+    return v;
+}
+// grid (tiles in x of the widest level, tiles in y of the tallest, n_levels), block 256
+__global__ __launch_bounds__(kOrbThreads) void orb_blur(OrbBlurArgs a)
+{
+    __shared__ uint32_t tile[kBlurRows][kBlurDwords];
+    __shared__ __align__(16) uint16_t hsum[kBlurRows][kBlurHPitch];
+    const OrbBlurLevel &L = a.l[blockIdx.z];
+    const int tx0 = blockIdx.x * kBlurTileW, ty0 = blockIdx.y * kBlurTileH;
+    if (tx0 >= L.bpitch || ty0 >= L.h) return;            // wave-uniform: the whole workgroup leaves (an empty level has h = 0)
+    const uint8_t *img = a.img + L.img_off;
+    for (int i = threadIdx.x; i < kBlurRows * kBlurDwords; i += kOrbThreads) {
+        const int r = i / kBlurDwords, cq = i - r * kBlurDwords;
+        const int gy = min(max(ty0 - 3 + r, 0), L.h - 1);
+        tile[r][cq] = orb_clamped_dword(img + (size_t)gy * L.pitch, tx0 - 4 + 4 * cq, L.w);
+    }
+    __syncthreads();
+    // horizontal: four sums an item from three dwords (columns 4q - 4 .. 4q + 7 of the tile); 128 * 255 < 2^16
+    for (int i = threadIdx.x; i < kBlurRows * (kBlurTileW / 4); i += kOrbThreads) {
+        const int r = i / (kBlurTileW / 4), q = i - r * (kBlurTileW / 4);
+        const uint32_t d0 = tile[r][q], d1 = tile[r][q + 1], d2 = tile[r][q + 2];
+        uint32_t px[12];
+#pragma unroll
+        for (int b = 0; b < 4; b++) { px[b] = (d0 >> (8 * b)) & 255u; px[4 + b] = (d1 >> (8 * b)) & 255u; px[8 + b] = (d2 >> (8 * b)) & 255u; }
+        uint32_t s[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++)                       // pixel 4q + k is px[4 + k]
+            s[k] = 9u * (px[1 + k] + px[7 + k]) + 17u * (px[2 + k] + px[6 + k]) + 24u * (px[3 + k] + px[5 + k]) + 28u * px[4 + k];
+        *reinterpret_cast<uint2 *>(&hsum[r][4 * q]) = make_uint2(s[0] | s[1] << 16, s[2] | s[3] << 16);
+    }
+    __syncthreads();
+    const int lx = threadIdx.x & 7, ly = threadIdx.x >> 3;
+    const int x = tx0 + 16 * lx, y = ty0 + ly;
+    if (x >= L.bpitch || y >= L.h) return;
+    uint32_t acc[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) acc[k] = 8192u;
+    constexpr uint32_t g[7] = {9u, 17u, 24u, 28u, 24u, 17u, 9u};
+#pragma unroll
+    for (int j = 0; j < 7; j++) {
+        const uint4 p = *reinterpret_cast<const uint4 *>(&hsum[ly + j][16 * lx]), q = *reinterpret_cast<const uint4 *>(&hsum[ly + j][16 * lx + 8]);
+        const uint32_t d[8] = {p.x, p.y, p.z, p.w, q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int k = 0; k < 8; k++) { acc[2 * k] += g[j] * (d[k] & 0xffffu); acc[2 * k + 1] += g[j] * (d[k] >> 16); }
+    }
+    uint32_t out[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        out[k] = (acc[4 * k] >> 14) | (acc[4 * k + 1] >> 14) << 8 | (acc[4 * k + 2] >> 14) << 16 | (acc[4 * k + 3] >> 14) << 24;
+    *reinterpret_cast<uint4 *>(a.blur + L.blur_off + (size_t)y * L.bpitch + x) = make_uint4(out[0], out[1], out[2], out[3]);
+}
+
+// ------------------------------------------------------------------------------------------------ orb_describe
+struct OrbDescArgs {
+    const uint8_t *blur;
+    const uint8_t *out;                // the eight kept counts and the records, as orb_moments left them
+    const uint8_t *tab;                // kOrbTabHeader bytes of C and S, then the steered table [bin][lane][pairs lane, 64 + lane, 128 + lane, 192 + lane][4]
+    uint8_t *desc;                     // 32 bytes per keypoint: the call's buffer or a slot of the frame store
+    float2 *kp;                        // (x, y) per keypoint in a slot of the frame store, or null
+    int32_t bpitch[kOrbLevels];
+    uint32_t blur_off[kOrbLevels];
+};
+// grid ceil(n_features / 4), block 256: wave i makes descriptor i
+__global__ __launch_bounds__(kOrbThreads) void orb_describe(OrbDescArgs a)
+{
+    const int lane = threadIdx.x & 63;
+    const int i = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kDescWaves + (threadIdx.x >> 6)));
+    const int32_t *counts = reinterpret_cast<const int32_t *>(a.out);
+    int total = 0;
+#pragma unroll
+    for (int l = 0; l < kOrbLevels; l++) total += counts[l];
+    if (i >= total) return;                               // wave-uniform
+    const uint4 *rec = reinterpret_cast<const uint4 *>(a.out + kOutHeader + (size_t)i * sizeof(chip_orb_keypoint));
+    const uint4 m = rec[1];                               // m10, m01, x | y << 16, level
+    const int x = (int)(m.z & 0xffffu), y = (int)(m.z >> 16), lv = (int)(m.w & 7u);
+    const int32_t *cs = reinterpret_cast<const int32_t *>(a.tab);
+    const int k = lane & 31;
+    long long v = (long long)(int32_t)m.x * cs[k] + (long long)(int32_t)m.y * cs[32 + k];
+    int best = k;
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) {              // the largest sum, the lowest bin among equals; lanes 32 .. 63 repeat 0 .. 31
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)(unsigned long long)v, off), hi = (uint32_t)__shfl_xor((int)((unsigned long long)v >> 32), off);
+        const long long ov = (long long)(((unsigned long long)hi << 32) | lo);
+        const int ob = __shfl_xor(best, off);
+        if (ov > v || (ov == v && ob < best)) { v = ov; best = ob; }
+    }
+    best = __builtin_amdgcn_readfirstlane(best);
+    const uint4 t = *reinterpret_cast<const uint4 *>(a.tab + kOrbTabHeader + ((size_t)best * 64 + lane) * 16);
+    const uint8_t *B = a.blur + a.blur_off[lv] + (size_t)y * a.bpitch[lv] + x;
+    const int bp = a.bpitch[lv];
+    const uint32_t tw[4] = {t.x, t.y, t.z, t.w};
+    unsigned long long bits[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int rx1 = (int8_t)(tw[j] & 255u), ry1 = (int8_t)((tw[j] >> 8) & 255u), rx2 = (int8_t)((tw[j] >> 16) & 255u), ry2 = (int8_t)(tw[j] >> 24);
+        const int p = B[ry1 * bp + rx1], q = B[ry2 * bp + rx2];
+        bits[j] = __ballot(p < q);                        // bit `lane` is pair 64 j + lane: bytes 8 j .. 8 j + 7, LSB first
+    }
+    if (lane == 0) {
+        uint4 *d = reinterpret_cast<uint4 *>(a.desc + (size_t)i * CHIP_ORB_DESC_BYTES);
+        d[0] = make_uint4((uint32_t)bits[0], (uint32_t)(bits[0] >> 32), (uint32_t)bits[1], (uint32_t)(bits[1] >> 32));
+        d[1] = make_uint4((uint32_t)bits[2], (uint32_t)(bits[2] >> 32), (uint32_t)bits[3], (uint32_t)(bits[3] >> 32));
+        if (a.kp) a.kp[i] = make_float2(__uint_as_float(rec[0].z), __uint_as_float(rec[0].w));
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 struct OrbState {
     DevBuf<uint8_t> img;               // the levels, rows of pitch bytes
@@ -402,14 +545,86 @@ struct OrbState {
     DevBuf<uint8_t> out;               // kOutHeader + CHIP_MATCH_MAX_KEYPOINTS records
     PinnedBuf<uint8_t> h_out;
     PinnedBuf<uint8_t> h_img;          // level 0 with its row pitch, for widths that are no multiple of 4
+    // the descriptor half: nothing of this exists before the first describing call
+    DevBuf<uint8_t> blur;              // the blurred levels, rows of bpitch bytes
+    DevBuf<uint8_t> tab;               // C, S and the steered table in the lanes' order, uploaded once
+    DevBuf<uint8_t> desc;              // CHIP_MATCH_MAX_KEYPOINTS descriptors of chip_orb_detect_describe on their way out
+    PinnedBuf<uint8_t> h_desc;
+    bool tab_loaded = false;
     bool have = false;                 // a detect has finished: t describes what the buffers hold
+    bool have_blur = false;            // ... and it was a describing one: bl describes the blurred planes
     OrbTable t{};
+    OrbBlurLevel bl[kOrbLevels] = {};
 };
 
 void orb_destroy(Ctx *c)
 {
     delete c->orb_state;
     c->orb_state = nullptr;
+}
+
+// ---- the descriptor's tables, made once on the host from the generator of the header
+constexpr int kOrbPairs = 256;
+static const int32_t kOrbQuarter[9] = {16384, 16069, 15137, 13623, 11585, 9102, 6270, 3196, 0};   // C[0 .. 8]; S[k] = C[8 - k]
+struct OrbTables {
+    int32_t C[CHIP_ORB_BINS], S[CHIP_ORB_BINS];
+    int8_t pattern[kOrbPairs][4];                        // x1, y1, x2, y2
+    int8_t steered[CHIP_ORB_BINS][kOrbPairs][4];         // rx1, ry1, rx2, ry2
+    std::vector<uint8_t> device;                         // what orb_describe reads: kOrbTabHeader bytes of C, S, then [bin][lane][4 pairs][4]
+};
+static const OrbTables &orb_tables()
+{
+    static OrbTables T;
+    static std::once_flag once;
+    std::call_once(once, [] {
+        for (int k = 0; k <= 8; k++) { T.C[k] = kOrbQuarter[k]; T.S[k] = kOrbQuarter[8 - k]; }
+        for (int k = 0; k + 8 < CHIP_ORB_BINS; k++) { T.C[k + 8] = -T.S[k]; T.S[k + 8] = T.C[k]; }
+        uint64_t s = 0x4F52425F42524945ull;
+        auto draw = [&s]() { s = s * 6364136223846793005ull + 1442695040888963407ull; return (int)((s >> 33) % 11u) - 5; };
+        auto coord = [&draw]() { const int a = draw(), b = draw(), c = draw(); return a + b + c; };
+        int n = 0;
+        while (n < kOrbPairs) {
+            const int x1 = coord(), y1 = coord(), x2 = coord(), y2 = coord();   // always twelve draws, in this order
+            if (x1 * x1 + y1 * y1 > 169 || x2 * x2 + y2 * y2 > 169) continue;
+            if ((x1 - x2) * (x1 - x2) + (y1 - y2) * (y1 - y2) < 9) continue;
+            bool seen = false;
+            for (int j = 0; j < n && !seen; j++) {
+                const int8_t *q = T.pattern[j];
+                seen = (q[0] == x1 && q[1] == y1 && q[2] == x2 && q[3] == y2) || (q[0] == x2 && q[1] == y2 && q[2] == x1 && q[3] == y1);
+            }
+            if (seen) continue;
+            T.pattern[n][0] = (int8_t)x1; T.pattern[n][1] = (int8_t)y1; T.pattern[n][2] = (int8_t)x2; T.pattern[n][3] = (int8_t)y2;
+            n++;
+        }
+        for (int k = 0; k < CHIP_ORB_BINS; k++)
+            for (int p = 0; p < kOrbPairs; p++)
+                for (int e = 0; e < 4; e += 2) {
+                    const int x = T.pattern[p][e], y = T.pattern[p][e + 1];
+                    T.steered[k][p][e] = (int8_t)((x * T.C[k] - y * T.S[k] + 8192) >> 14);       // arithmetic shifts
+                    T.steered[k][p][e + 1] = (int8_t)((x * T.S[k] + y * T.C[k] + 8192) >> 14);
+                }
+        T.device.assign(kOrbTabHeader + sizeof T.steered, 0);
+        std::memcpy(T.device.data(), T.C, sizeof T.C);
+        std::memcpy(T.device.data() + sizeof T.C, T.S, sizeof T.S);
+        for (int k = 0; k < CHIP_ORB_BINS; k++)
+            for (int lane = 0; lane < 64; lane++)
+                for (int j = 0; j < 4; j++)
+                    std::memcpy(T.device.data() + kOrbTabHeader + (((size_t)k * 64 + lane) * 4 + j) * 4, T.steered[k][64 * j + lane], 4);
+    });
+    return T;
+}
+static_assert(kOrbTabHeader == 2 * CHIP_ORB_BINS * sizeof(int32_t), "C and S in front of the steered table");
+
+static int orb_bin_of(int32_t m10, int32_t m01)
+{
+    const OrbTables &T = orb_tables();
+    int best = 0;
+    long long top = 0;
+    for (int k = 0; k < CHIP_ORB_BINS; k++) {
+        const long long v = (long long)m10 * T.C[k] + (long long)m01 * T.S[k];
+        if (k == 0 || v > top) { top = v; best = k; }
+    }
+    return best;
 }
 
 static int orb_params(const chip_orb_params *p, chip_orb_params *d)
@@ -455,17 +670,6 @@ static hipStream_t orb_stream(Ctx *c)
     return c->s_query;
 }
 
-}  // namespace chip
-
-using namespace chip;
-
-extern "C" int chip_build_has_orb_detect(void) { return 1; }
-
-extern "C" void chip_orb_params_default(chip_orb_params *p)
-{
-    if (p) *p = chip_orb_params{5000, 8, 0, 31};   // cv::ORB::create(5000), setFastThreshold(0)
-}
-
 static int orb_check_size(int32_t width, int32_t height, const chip_orb_params *p, chip_orb_params *d)
 {
     if (width < 1 || height < 1) return CHIP_ERR_INVALID_ARG;
@@ -475,32 +679,23 @@ static int orb_check_size(int32_t width, int32_t height, const chip_orb_params *
     return CHIP_OK;
 }
 
-extern "C" int chip_orb_plan(int32_t width, int32_t height, const chip_orb_params *p, chip_orb_level levels[8])
-{
-    if (!levels) return CHIP_ERR_INVALID_ARG;
-    chip_orb_params d;
-    const int rc = orb_check_size(width, height, p, &d);
-    if (rc != CHIP_OK) return rc;
-    orb_plan(width, height, d, levels);
-    return CHIP_OK;
-}
+int orb_check(int32_t width, int32_t height, const chip_orb_params *p, chip_orb_params *d) { return orb_check_size(width, height, p, d); }
 
-extern "C" int chip_orb_detect(chip_ctx *c, const uint8_t *image, int32_t width, int32_t height, const chip_orb_params *p,
-                               chip_orb_keypoint *kp, int32_t capacity, int32_t *n, int32_t level_counts[8])
+// The detector and, if describe, the descriptor of one image, enqueued on s up to the copy of the first `back` bytes of the output (the
+// eight counts, then the records) into h_out; nothing is waited for.  The image is `image` (host) or `image_dev` (device), dense rows.
+// desc_dev / kp_dev: where orb_describe writes (desc_dev null: the state's own buffer; kp_dev may be null).  The caller holds match_mu,
+// has selected the device, and calls orb_finished once the stream has drained.
+int orb_enqueue(Ctx *c, hipStream_t s, const uint8_t *image, const uint8_t *image_dev, int32_t width, int32_t height, const chip_orb_params &d,
+                bool describe, uint8_t *desc_dev, float2 *kp_dev, size_t back)
 {
-    if (!c || !image || !kp || !n) return CHIP_ERR_INVALID_ARG;
-    chip_orb_params d;
-    int rc = orb_check_size(width, height, p, &d);
-    if (rc != CHIP_OK) return rc;
-    if (capacity < d.n_features) return CHIP_ERR_INVALID_ARG;
-    if (c->group) return CHIP_ERR_UNSUPPORTED;
     chip_orb_level plan[kOrbLevels];
     orb_plan(width, height, d, plan);
     // the launch table: where every level lives in the ctx's buffers
     OrbTable t{};
+    OrbBlurLevel bl[kOrbLevels] = {};
     t.n_levels = d.n_levels; t.n_features = d.n_features; t.threshold = d.fast_threshold;
-    size_t img_n = 0, score_n = 0, cand_n = 0, strip_n = 0;
-    int qprefix = 0, max_w = 0, max_h = 0, max_strips = 0;
+    size_t img_n = 0, score_n = 0, cand_n = 0, strip_n = 0, blur_n = 0;
+    int qprefix = 0, max_w = 0, max_h = 0, max_strips = 0, max_bw = 0;
     for (int l = 0; l < d.n_levels; l++) {
         OrbLevel &L = t.l[l];
         L.w = plan[l].width; L.h = plan[l].height; L.scale = plan[l].scale;
@@ -511,23 +706,25 @@ extern "C" int chip_orb_detect(chip_ctx *c, const uint8_t *image, int32_t width,
         L.cap = area ? (L.x1 - L.x0 + 2) / 2 : 0;
         L.nstrips = area ? (L.y1 - L.y0 + kStripRows) / kStripRows : 0;
         L.img_off = (uint32_t)img_n; L.score_off = (uint32_t)score_n; L.cand_off = (uint32_t)cand_n; L.strip_off = (uint32_t)strip_n;
+        bl[l] = OrbBlurLevel{L.w, L.h, L.pitch, (L.w + 15) & ~15, L.img_off, (uint32_t)blur_n};
         img_n += ((size_t)L.pitch * L.h + 15) & ~(size_t)15;
         score_n += (size_t)L.spitch * L.h;               // a multiple of 8 elements: every plane starts on 16 bytes
         cand_n += (size_t)L.cap * L.nstrips;
         strip_n += (size_t)L.nstrips;
+        blur_n += (size_t)bl[l].bpitch * L.h;             // a multiple of 16 bytes
         max_w = L.spitch > max_w ? L.spitch : max_w; max_h = L.h > max_h ? L.h : max_h;
         max_strips = L.nstrips > max_strips ? L.nstrips : max_strips;
+        max_bw = bl[l].bpitch > max_bw ? bl[l].bpitch : max_bw;
     }
-    std::lock_guard<std::mutex> lk(c->match_mu);
-    CHIP_HIP(c, hipSetDevice(c->device));
     if (!c->orb_state) {
         c->orb_state = new (std::nothrow) OrbState();
         if (!c->orb_state) return CHIP_ERR_OOM;
     }
     OrbState *st = c->orb_state;
-    st->have = false;
+    st->have = st->have_blur = false;
+    int rc = CHIP_OK;
     const size_t out_bytes = kOutHeader + (size_t)CHIP_MATCH_MAX_KEYPOINTS * sizeof(chip_orb_keypoint);
-    const size_t h_img_n = t.l[0].pitch == t.l[0].w ? 0 : (size_t)t.l[0].pitch * t.l[0].h;   // a width that is no multiple of 4 only
+    const size_t h_img_n = !image || t.l[0].pitch == t.l[0].w ? 0 : (size_t)t.l[0].pitch * t.l[0].h;   // a host image whose width is no multiple of 4
     if (st->img.capacity() < img_n || st->score.capacity() < score_n || st->cand.capacity() < cand_n + 1 || st->strip_count.capacity() < strip_n + 1 ||
         !st->h_out.capacity() || st->h_img.capacity() < h_img_n) {
         ResidentPause paused(c);   // one pause over the group, as the GMS mode tables
@@ -541,16 +738,31 @@ extern "C" int chip_orb_detect(chip_ctx *c, const uint8_t *image, int32_t width,
         if (rc == CHIP_OK) rc = st->h_img.reserve(c, h_img_n);
         if (rc != CHIP_OK) return rc;
     }
+    const OrbTables &tables = orb_tables();
+    const size_t desc_bytes = (size_t)CHIP_MATCH_MAX_KEYPOINTS * CHIP_ORB_DESC_BYTES;
+    if (describe && (st->blur.capacity() < blur_n + 1 || !st->h_desc.capacity())) {
+        ResidentPause paused(c);
+        rc = st->blur.reserve(c, blur_n + 1);
+        if (rc == CHIP_OK) rc = st->tab.reserve(c, tables.device.size());
+        if (rc == CHIP_OK) rc = st->desc.reserve(c, desc_bytes);
+        if (rc == CHIP_OK) rc = st->h_desc.reserve(c, desc_bytes);
+        if (rc != CHIP_OK) return rc;
+    }
     OrbArgs a;
     a.img = st->img; a.score = st->score; a.cand = st->cand; a.strip_count = st->strip_count; a.kept = st->kept; a.out = st->out; a.t = t;
-    hipStream_t s = orb_stream(c);
     const OrbLevel &L0 = t.l[0];
-    if (L0.pitch == L0.w) {
+    if (image_dev) {
+        CHIP_HIP(c, hipMemcpy2DAsync(a.img, (size_t)L0.pitch, image_dev, (size_t)width, (size_t)width, (size_t)height, hipMemcpyDeviceToDevice, s));
+    } else if (L0.pitch == L0.w) {
         CHIP_HIP(c, hipMemcpyAsync(a.img, image, (size_t)width * height, hipMemcpyHostToDevice, s));
     } else {   // rows of pitch bytes are made on the host, in pinned memory (the previous call has finished: every call ends in a wait)
         uint8_t *rows = st->h_img.host();
         for (int y = 0; y < height; y++) std::memcpy(rows + (size_t)y * L0.pitch, image + (size_t)y * width, (size_t)width);
         CHIP_HIP(c, hipMemcpyAsync(a.img, rows, (size_t)L0.pitch * height, hipMemcpyHostToDevice, s));
+    }
+    if (describe && !st->tab_loaded) {                    // the tables outlive the copy: they are static
+        CHIP_HIP(c, hipMemcpyAsync(st->tab, tables.device.data(), tables.device.size(), hipMemcpyHostToDevice, s));
+        st->tab_loaded = true;
     }
     for (int l = 1; l < d.n_levels; l++) {
         const OrbLevel &L = t.l[l];
@@ -567,22 +779,136 @@ extern "C" int chip_orb_detect(chip_ctx *c, const uint8_t *image, int32_t width,
     }
     hipLaunchKernelGGL(orb_select, dim3(kOrbLevels), dim3(kSelectThreads), 0, s, a);
     CHIP_HIP(c, hipGetLastError());
-    hipLaunchKernelGGL(orb_moments, dim3((d.n_features + kOrbThreads / 64 - 1) / (kOrbThreads / 64)), dim3(kOrbThreads), 0, s, a);
+    const dim3 per_keypoint((d.n_features + kOrbThreads / 64 - 1) / (kOrbThreads / 64));
+    hipLaunchKernelGGL(orb_moments, per_keypoint, dim3(kOrbThreads), 0, s, a);
     CHIP_HIP(c, hipGetLastError());
-    const size_t back = kOutHeader + (size_t)d.n_features * sizeof(chip_orb_keypoint);
+    if (describe) {
+        OrbBlurArgs b;
+        b.img = st->img; b.blur = st->blur;
+        OrbDescArgs g;
+        g.blur = st->blur; g.out = st->out; g.tab = st->tab; g.desc = desc_dev ? desc_dev : st->desc.get(); g.kp = kp_dev;
+        for (int l = 0; l < kOrbLevels; l++) { b.l[l] = bl[l]; g.bpitch[l] = bl[l].bpitch; g.blur_off[l] = bl[l].blur_off; }
+        if (max_bw > 0 && max_h > 0) {
+            hipLaunchKernelGGL(orb_blur, dim3((max_bw + kBlurTileW - 1) / kBlurTileW, (max_h + kBlurTileH - 1) / kBlurTileH, d.n_levels),
+                               dim3(kOrbThreads), 0, s, b);
+            CHIP_HIP(c, hipGetLastError());
+        }
+        hipLaunchKernelGGL(orb_describe, per_keypoint, dim3(kOrbThreads), 0, s, g);
+        CHIP_HIP(c, hipGetLastError());
+    }
     CHIP_HIP(c, hipMemcpyAsync(st->h_out.host(), a.out, back, hipMemcpyDeviceToHost, s));
-    CHIP_HIP(c, hipStreamSynchronize(s));
+    st->t = t;
+    for (int l = 0; l < kOrbLevels; l++) st->bl[l] = bl[l];
+    return CHIP_OK;
+}
+
+// the stream has drained after an orb_enqueue: the counts (checked against n_features) and what the debug calls may read
+int orb_finished(Ctx *c, bool describe, int32_t n_features, int32_t *total_out, int32_t level_counts[8])
+{
+    OrbState *st = c->orb_state;
     const int32_t *counts = reinterpret_cast<const int32_t *>(st->h_out.host());
     int32_t total = 0;
     for (int l = 0; l < kOrbLevels; l++) {
         total += counts[l];
         if (level_counts) level_counts[l] = counts[l];
     }
-    if (total < 0 || total > d.n_features) return CHIP_ERR_HIP;   // cannot happen: the kept lists are bounded by the quotas
-    std::memcpy(kp, st->h_out.host() + kOutHeader, (size_t)total * sizeof(chip_orb_keypoint));
-    *n = total;
-    st->t = t;
+    if (total < 0 || total > n_features) return CHIP_ERR_HIP;   // cannot happen: the kept lists are bounded by the quotas
+    *total_out = total;
     st->have = true;
+    st->have_blur = describe;
+    return CHIP_OK;
+}
+
+}  // namespace chip
+
+using namespace chip;
+
+extern "C" int chip_build_has_orb_detect(void) { return 1; }
+
+extern "C" void chip_orb_params_default(chip_orb_params *p)
+{
+    if (p) *p = chip_orb_params{5000, 8, 0, 31};   // cv::ORB::create(5000), setFastThreshold(0)
+}
+
+extern "C" int chip_orb_plan(int32_t width, int32_t height, const chip_orb_params *p, chip_orb_level levels[8])
+{
+    if (!levels) return CHIP_ERR_INVALID_ARG;
+    chip_orb_params d;
+    const int rc = orb_check_size(width, height, p, &d);
+    if (rc != CHIP_OK) return rc;
+    orb_plan(width, height, d, levels);
+    return CHIP_OK;
+}
+
+// chip_orb_detect and chip_orb_detect_describe: desc null is the former
+static int orb_detect_call(chip_ctx *c, const uint8_t *image, int32_t width, int32_t height, const chip_orb_params *p, chip_orb_keypoint *kp,
+                           int32_t capacity, int32_t *n, int32_t level_counts[8], uint8_t *desc)
+{
+    chip_orb_params d;
+    int rc = orb_check_size(width, height, p, &d);
+    if (rc != CHIP_OK) return rc;
+    if (capacity < d.n_features) return CHIP_ERR_INVALID_ARG;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    CHIP_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = orb_stream(c);
+    const size_t back = kOutHeader + (size_t)d.n_features * sizeof(chip_orb_keypoint);
+    rc = orb_enqueue(c, s, image, nullptr, width, height, d, desc != nullptr, nullptr, nullptr, back);
+    if (rc != CHIP_OK) return rc;
+    OrbState *st = c->orb_state;
+    if (desc) CHIP_HIP(c, hipMemcpyAsync(st->h_desc.host(), st->desc, (size_t)d.n_features * CHIP_ORB_DESC_BYTES, hipMemcpyDeviceToHost, s));
+    CHIP_HIP(c, hipStreamSynchronize(s));
+    int32_t total = 0;
+    rc = orb_finished(c, desc != nullptr, d.n_features, &total, level_counts);
+    if (rc != CHIP_OK) return rc;
+    std::memcpy(kp, st->h_out.host() + kOutHeader, (size_t)total * sizeof(chip_orb_keypoint));
+    if (desc) std::memcpy(desc, st->h_desc.host(), (size_t)total * CHIP_ORB_DESC_BYTES);
+    *n = total;
+    return CHIP_OK;
+}
+
+extern "C" int chip_orb_detect(chip_ctx *c, const uint8_t *image, int32_t width, int32_t height, const chip_orb_params *p,
+                               chip_orb_keypoint *kp, int32_t capacity, int32_t *n, int32_t level_counts[8])
+{
+    if (!c || !image || !kp || !n) return CHIP_ERR_INVALID_ARG;
+    return orb_detect_call(c, image, width, height, p, kp, capacity, n, level_counts, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------ the descriptor half
+extern "C" int chip_build_has_orb_describe(void) { return 1; }
+
+extern "C" int chip_orb_bin(int32_t m10, int32_t m01) { return orb_bin_of(m10, m01); }
+
+extern "C" int chip_orb_pattern(int8_t pattern[1024], int8_t steered[32768])
+{
+    if (!pattern && !steered) return CHIP_ERR_INVALID_ARG;
+    const OrbTables &T = orb_tables();
+    if (pattern) std::memcpy(pattern, T.pattern, sizeof T.pattern);
+    if (steered) std::memcpy(steered, T.steered, sizeof T.steered);
+    return CHIP_OK;
+}
+
+extern "C" int chip_orb_detect_describe(chip_ctx *c, const uint8_t *image, int32_t width, int32_t height, const chip_orb_params *p,
+                                        chip_orb_keypoint *kp, int32_t capacity, int32_t *n, int32_t level_counts[8], uint8_t *desc)
+{
+    if (!c || !image || !kp || !n || !desc) return CHIP_ERR_INVALID_ARG;
+    return orb_detect_call(c, image, width, height, p, kp, capacity, n, level_counts, desc);
+}
+
+extern "C" int chip_debug_orb_blur(chip_ctx *c, int32_t level, uint8_t *out)
+{
+    if (!c) return CHIP_ERR_INVALID_ARG;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    OrbState *st = c->orb_state;
+    if (!st || !st->have || !st->have_blur) return CHIP_ERR_BUSY;
+    if (level < 0 || level >= st->t.n_levels) return CHIP_ERR_RANGE;
+    const OrbBlurLevel &L = st->bl[level];
+    if (L.w < 1 || L.h < 1 || !out) return CHIP_OK;       // an empty level: nothing to deliver
+    CHIP_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = orb_stream(c);
+    CHIP_HIP(c, hipMemcpy2DAsync(out, (size_t)L.w, st->blur.get() + L.blur_off, (size_t)L.bpitch, (size_t)L.w, (size_t)L.h, hipMemcpyDeviceToHost, s));
+    CHIP_HIP(c, hipStreamSynchronize(s));
     return CHIP_OK;
 }
 

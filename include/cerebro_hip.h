@@ -528,7 +528,7 @@ int chip_debug_pnp_keep_stage(chip_ctx *ctx, int32_t on);
  *   the "< 150 matches" reject and pf_matches                           src/Cerebro.cpp:1487,1505
  *   make_3d_2d_collection__using__pfmatches_and_disparity (a->b, b->a)  PointFeatureMatching.cpp:95-154, Cerebro.cpp:1512,1566
  *   make_3d_3d_collection__using__pfmatches_and_disparity               PointFeatureMatching.cpp:159-195, Cerebro.cpp:1624
- * ORB description (cv::ORB::compute) and rectification stay with the caller (OpenCV); detection is chip_orb_detect and the depth
+ * Rectification stays with the caller (OpenCV); detection is chip_orb_detect, description chip_orb_detect_describe, and the depth
  * images are chip_frame_put_disparity / chip_frame_put_stereo, all below.  Everything here is integer or
  * single-operation IEEE arithmetic: the device results equal a CPU restatement (tests/np_mirror_match.py) bit for bit.
  *
@@ -899,7 +899,7 @@ int chip_frame_put_stereo(chip_ctx *ctx, int64_t id, const uint8_t *desc /* n x 
  * chip_frame_put* takes is the detector half of cv::ORB::create(5000) with setFastThreshold(0) on the rectified left image
  * (src/utils/PointFeatureMatching.cpp:16-22, on both frames of every candidate).  chip_orb_detect is that half: the pyramid, the FAST
  * score, the Harris ranking with per-level quotas and the patch moments the orientation is made of.  The descriptor half (blur,
- * steered BRIEF) is NOT built: the caller runs cv::ORB::compute on these keypoints.
+ * steered BRIEF) is built as well: "ORB descriptors on the device", below (chip_orb_detect_describe).
  *
  * THE DEFINITION IS THIS PROJECT'S OWN, modelled on cv::ORB::detect with HARRIS_SCORE.  OpenCV's source is not part of this project,
  * so parity against it is UNPINNED (DESIGN.md 6 lists the known departures).  All image arithmetic is integer; the device results
@@ -977,6 +977,67 @@ int chip_orb_detect(chip_ctx *ctx, const uint8_t *image /* height x width, dense
                     const chip_orb_params *p /* NULL: the defaults */, chip_orb_keypoint *kp, int32_t capacity, int32_t *n,
                     int32_t level_counts[8] /* may be NULL */);
 int chip_debug_orb_level(chip_ctx *ctx, int32_t level, uint8_t *image_out /* h_l x w_l */, int16_t *score_out /* h_l x w_l */);
+
+/* ---- ORB descriptors on the device: blur, 32 orientation bins, steered BRIEF (ABI 7, additive).  chip_orb_detect_describe is
+ * detectAndCompute in one call (src/utils/PointFeatureMatching.cpp:21-22); chip_frame_put_orb_stereo puts a frame into the store from
+ * its rectified 8-bit pair and nothing else: 2 w h bytes go up, one count comes down.
+ *
+ * THE DEFINITION IS THIS PROJECT'S OWN, all-integer, restated in tests/np_mirror_orb_describe.py (which the device equals bit for
+ * bit) and UNPINNED against OpenCV: the pattern below is not cv::ORB's learned table.  Descriptors are only ever compared with
+ * descriptors made by the same code; an integrator who must keep OpenCV's bits keeps orb->compute.
+ *   - blurred level: for every pyramid level l, B_l has the level's size.  With g = 9 17 24 28 24 17 9 (sum 128):
+ *       H[y][x] = sum_{i=-3..3} g[i+3] I[y][clamp(x + i, 0, w_l - 1)]
+ *       B[y][x] = (sum_{j=-3..3} g[j+3] H[clamp(y + j, 0, h_l - 1)][x] + 8192) >> 14      in 0 .. 255
+ *     The clamps make the plane defined everywhere; with border >= 16 no descriptor reads a clamped tap (reach, below);
+ *   - orientation bin: CHIP_ORB_BINS = 32 bins of 11.25 degrees.  C[k] = round(16384 cos(2 pi k / 32)), S[k] alike, as literals:
+ *       C[0..8] = 16384 16069 15137 13623 11585 9102 6270 3196 0      S[0..8] = 0 3196 6270 9102 11585 13623 15137 16069 16384
+ *       C[(k + 8) mod 32] = -S[k], S[(k + 8) mod 32] = C[k]           (the nearest defining product lies 0.037 from a rounding half)
+ *     bin(m10, m01) = the k that maximises m10 C[k] + m01 S[k], computed in int64, ties to the lowest k: (0, 0) gives 0,
+ *     (3196, 315) ties bins 0 and 1 exactly and gives 0.  No float, no atan2.  chip_orb_bin is this function on the host;
+ *   - pattern: 256 pairs (x1, y1, x2, y2) from a generator.  State s = 0x4F52425F42524945; a draw is
+ *     s = s * 6364136223846793005 + 1442695040888963407 (mod 2^64), value (s >> 33) % 11 - 5; a coordinate is the sum of three
+ *     draws; an attempt draws x1, y1, x2, y2 in that order (always 12 draws) and is rejected if either point has x^2 + y^2 > 169,
+ *     if (x1 - x2)^2 + (y1 - y2)^2 < 9, or if the pair, in either order, was already accepted.  303 attempts give the 256 pairs;
+ *     pairs 0, 1, 2 are (-6,-10,-4,0) (-7,-3,2,-5) (-1,-5,5,3), pair 255 is (-9,-2,-2,-6); sha256 of the 1024 int8 bytes
+ *     [pair][x1,y1,x2,y2] is 0a170a01e941c47e3dc21a502fbec04104b548ddedf269114180a0504526a179;
+ *   - steered table: T[k][pair] = (rx1, ry1, rx2, ry2), rx = (x C[k] - y S[k] + 8192) >> 14, ry = (x S[k] + y C[k] + 8192) >> 14
+ *     (arithmetic shifts).  Every entry lies in -13 .. 13, no product hits an exact half, no pair collapses onto one pixel under any
+ *     bin, and T[k + 8] is exactly T[k] turned by 90 degrees, (rx, ry) -> (-ry, rx): an image turned by a quarter turn gives the same
+ *     descriptors.  sha256 of the 32768 int8 bytes [k][pair][rx1,ry1,rx2,ry2] is
+ *     489d64ba52aef79c6fa46391b51cc6fe2e3764aa946f9283360aca763ba5969f.  The library builds both tables once, in plain host C++ from
+ *     the generator, and uploads them on first use; chip_orb_pattern hands them out (either pointer may be NULL, both NULL is
+ *     CHIP_ERR_INVALID_ARG; no ctx, no device);
+ *   - descriptor: a keypoint has level l, position (x, y) = (x_level, y_level) and bin k = bin(m10, m01).  Bit p is 1 iff
+ *     B_l[y + ry1][x + rx1] < B_l[y + ry2][x + rx2]; byte j holds the pairs 8j .. 8j + 7, LSB first: CHIP_ORB_DESC_BYTES = 32 bytes;
+ *   - reach: the taps go +-13 and the blur +-3 beyond them; the detector's border is at least 16, so every read is inside the level;
+ *   - kernels, both after orb_moments on the same stream and only in a describing call: orb_blur (all levels in one launch, the level
+ *     on a grid axis; rows read as whole dwords into an LDS tile of 128 x 32 pixels with a halo of 3, 16-bit horizontal sums, 16-byte
+ *     stores) and orb_describe (one wave per kept keypoint: the bin from the record's moments, the lane's four pairs in one 16-byte
+ *     load, eight byte gathers, four ballots, two 16-byte stores; its output pointers are arguments);
+ *   - chip_orb_detect_describe: the records and counts are byte for byte those of chip_orb_detect on the same input, desc[i] belongs
+ *     to kp[i]; desc holds capacity x 32 bytes, of which the first *n x 32 are written.  Statuses: those of chip_orb_detect, and
+ *     CHIP_ERR_INVALID_ARG for a NULL desc.  One device-to-host copy more than chip_orb_detect, for the descriptors;
+ *   - chip_debug_orb_blur: the blurred plane (h_l x w_l, dense rows) of the last describing call of the ctx.  CHIP_ERR_BUSY if there
+ *     is none (also after a plain chip_orb_detect), CHIP_ERR_RANGE for a level that call did not have.  It launches nothing;
+ *   - chip_frame_put_orb_stereo: detect + describe on `left`, where the pair is staged for the block matcher; orb_describe writes
+ *     the descriptors and the records' (x, y) straight into the slot's rows; then bm_prefilter and bm_keypoints as in
+ *     chip_frame_put_stereo.  The only copy back is the eight kept counts, giving *n; each image crosses the bus once.  The frame is
+ *     indistinguishable from chip_orb_detect_describe -> chip_frame_put_stereo with kp_xy from the records.  All statuses are decided
+ *     before the device is touched: the checks of chip_orb_detect (NULL left / right / Q / n: CHIP_ERR_INVALID_ARG) and of
+ *     chip_frame_put_stereo's parameters; a group ctx CHIP_ERR_UNSUPPORTED; no reserve CHIP_ERR_BUSY; n_features > slot_keypoints
+ *     CHIP_ERR_UNSUPPORTED (the slot must hold whatever is kept); a full store CHIP_ERR_OOM.  The replace, failure and id rules are
+ *     those of chip_frame_put; an image that keeps nothing is stored as an empty frame (*n = 0).                                    */
+#define CHIP_ORB_BINS 32
+int chip_build_has_orb_describe(void);     /* 1 */
+int chip_orb_bin(int32_t m10, int32_t m01);
+int chip_orb_pattern(int8_t pattern[1024] /* may be NULL */, int8_t steered[32768] /* may be NULL */);
+int chip_orb_detect_describe(chip_ctx *ctx, const uint8_t *image /* height x width, dense rows */, int32_t width, int32_t height,
+                             const chip_orb_params *p /* NULL: the defaults */, chip_orb_keypoint *kp, int32_t capacity, int32_t *n,
+                             int32_t level_counts[8] /* may be NULL */, uint8_t *desc /* capacity x 32 */);
+int chip_debug_orb_blur(chip_ctx *ctx, int32_t level, uint8_t *out /* h_l x w_l */);
+int chip_frame_put_orb_stereo(chip_ctx *ctx, int64_t id, int32_t width, int32_t height, const uint8_t *left, const uint8_t *right,
+                              const chip_orb_params *orb /* NULL: the defaults */, const chip_stereo_bm_params *bm /* NULL: the defaults */,
+                              const double Q_rowmajor[16], int32_t *n);
 
 /* ------------------------------------------------------------------------------------------ introspection */
 typedef struct {

@@ -225,7 +225,7 @@ __global__ __launch_bounds__(kOrbThreads) void orb_candidates(OrbArgs a)
             for (int w = 0; w < kOrbThreads / 64; w++) { const int n = wave_n[w]; total += n; if (w < wave) before += n; }
             if (keep) {
                 const int at = base + before + __popcll(votes & ((1ull << lane) - 1ull));
-                if (at < L.cap) list[at] = y * L.w + x;  // (always: one strict maximum per 2 x 2 block)
+                if (at < L.cap) list[at] = y * L.w + x;  // (always: one strict maximum per 2 x 2 block; filled to cap by tests/test_orb_limits_gpu.py)
             }
             base += total;
             __syncthreads();

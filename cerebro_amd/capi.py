@@ -78,6 +78,8 @@ CHIP_STEREO_BM_TEXTURE_THRESHOLD, CHIP_STEREO_BM_UNIQUENESS_RATIO = 10, 15
 CHIP_ORB_MAX_LEVELS, CHIP_ORB_MAX_SIDE = 8, 4096
 CHIP_ORB_BINS = 32
 CHIP_ORB_N_FEATURES, CHIP_ORB_N_LEVELS, CHIP_ORB_FAST_THRESHOLD, CHIP_ORB_BORDER = 5000, 8, 0, 31
+# rectification: map values are quantised to 1/32 pixel (5 fraction bits) inside [-2, 32768]; NaN gives -64
+CHIP_RECTIFY_FRACTION_BITS, CHIP_RECTIFY_MAP_MIN, CHIP_RECTIFY_MAP_MAX, CHIP_RECTIFY_NAN_Q = 5, -2.0, 32768.0, -64
 
 
 class ChipError(RuntimeError):
@@ -316,6 +318,13 @@ _SIGS = {
     "chip_debug_orb_blur": (C.c_int, [_P, C.c_int32, _P]),
     "chip_frame_put_orb_stereo": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.POINTER(OrbParams), C.POINTER(StereoBmParams), _P,
                                             C.POINTER(C.c_int32)]),
+    "chip_build_has_rectify": (C.c_int, []),
+    "chip_rectify_quantize": (C.c_int, [_P, C.c_int64, _P]),
+    "chip_remap": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    "chip_rectify_set_maps": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "chip_rectify_pair": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
+    "chip_frame_put_raw_orb_stereo": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.POINTER(OrbParams), C.POINTER(StereoBmParams), _P,
+                                                C.POINTER(C.c_int32)]),
     "chip_get_info": (C.c_int, [_P, C.POINTER(Info)]),
     "chip_profile_enable": (C.c_int, [_P, C.c_int32]),
     "chip_profile_reset": (C.c_int, [_P]),
@@ -433,6 +442,16 @@ def orb_pattern():
     if rc != CHIP_OK:
         raise ChipError(rc, "chip_orb_pattern")
     return pattern, steered
+
+
+def rectify_quantize(map) -> np.ndarray:
+    """chip_rectify_quantize: the float map values in 1/32 pixel -> an int32 array of the map's shape; no ctx, no device"""
+    m = np.ascontiguousarray(map, dtype=np.float32)
+    q = np.zeros(m.shape, dtype=np.int32)
+    rc = load_library().chip_rectify_quantize(_ptr(m), m.size, _ptr(q))
+    if rc != CHIP_OK:
+        raise ChipError(rc, "chip_rectify_quantize")
+    return q
 
 
 def orb_plan(width: int, height: int, params=None) -> list:
@@ -1218,6 +1237,44 @@ class Chip:
         n = C.c_int32()
         self._chk(self.lib.chip_frame_put_orb_stereo(self.h, id, l.shape[1], l.shape[0], _ptr(l), _ptr(r), o, b, _ptr(Qd), C.byref(n)),
                   "chip_frame_put_orb_stereo")
+        return n.value
+
+    def remap(self, image, map_x, map_y) -> np.ndarray:
+        """chip_remap -> the (H, W) uint8 image sampled through the (H, W) float32 maps: one stage of the rectification's definition"""
+        img = np.ascontiguousarray(image, dtype=np.uint8)
+        mx, my = np.ascontiguousarray(map_x, dtype=np.float32), np.ascontiguousarray(map_y, dtype=np.float32)
+        assert img.ndim == 2 and mx.shape == img.shape and my.shape == img.shape
+        out = np.zeros(img.shape, dtype=np.uint8)
+        self._chk(self.lib.chip_remap(self.h, _ptr(img), img.shape[1], img.shape[0], _ptr(mx), _ptr(my), _ptr(out)), "chip_remap")
+        return out
+
+    def rectify_set_maps(self, left, right):
+        """chip_rectify_set_maps: left and right are (x1, y1) for one stage or (x1, y1, x2, y2) for two, (H, W) float32 maps each (the
+        reference's map_x, map_y, map1_x, map1_y and map_x, map_y, map2_x, map2_y); they replace the maps the ctx had"""
+        if len(left) != len(right) or len(left) not in (2, 4):
+            raise ValueError("rectify_set_maps: two or four maps per eye, as many left as right")
+        maps = [np.ascontiguousarray(m, dtype=np.float32) for m in tuple(left) + tuple(right)]
+        assert maps[0].ndim == 2 and all(m.shape == maps[0].shape for m in maps)
+        k = len(left)
+        p = [_ptr(m) for m in maps[:k]] + [None] * (4 - k) + [_ptr(m) for m in maps[k:]] + [None] * (4 - k)
+        self._chk(self.lib.chip_rectify_set_maps(self.h, maps[0].shape[1], maps[0].shape[0], *p), "chip_rectify_set_maps")
+
+    def rectify_pair(self, left_raw, right_raw):
+        """chip_rectify_pair -> (left, right): the (H, W) uint8 raw pair through the ctx's maps"""
+        l, r, _ = self._stereo_pair(left_raw, right_raw, None)
+        lo, ro = np.zeros(l.shape, dtype=np.uint8), np.zeros(l.shape, dtype=np.uint8)
+        self._chk(self.lib.chip_rectify_pair(self.h, _ptr(l), _ptr(r), l.shape[1], l.shape[0], _ptr(lo), _ptr(ro)), "chip_rectify_pair")
+        return lo, ro
+
+    def frame_put_raw_orb_stereo(self, id: int, left_raw, right_raw, Q: np.ndarray, orb=None, bm=None) -> int:
+        """chip_frame_put_raw_orb_stereo: frame_put_orb_stereo with the cameras' raw (H, W) uint8 pair, rectified on the device through
+        the ctx's maps -> the number of keypoints kept"""
+        l, r, b = self._stereo_pair(left_raw, right_raw, bm)
+        _, o = _orb_params(orb)
+        Qd = np.ascontiguousarray(Q, dtype=np.float64).reshape(16)
+        n = C.c_int32()
+        self._chk(self.lib.chip_frame_put_raw_orb_stereo(self.h, id, l.shape[1], l.shape[0], _ptr(l), _ptr(r), o, b, _ptr(Qd), C.byref(n)),
+                  "chip_frame_put_raw_orb_stereo")
         return n.value
 
     def frame_drop(self, id: int):

@@ -725,6 +725,77 @@ __global__ __launch_bounds__(kBmThreads) void bm_dense(BmDenseArgs g)
     if (lane == 0) g.disp[i] = (int16_t)v;
 }
 
+// ------------------------------------------------------------------------------------------------ rectification
+// The definition is in include/cerebro_hip.h ("a frame from its raw stereo pair"): this project's own, modelled on cv::remap with
+// INTER_LINEAR, float maps and BORDER_CONSTANT 0; all in int32 once the host has quantised the maps to 1/32 pixel.
+constexpr int kRectPix = 4;            // consecutive pixels of a row per thread: one 32-bit store
+constexpr int kRectLanes = 64;         // threads along a row: a workgroup spans kRectLanes * kRectPix = 256 pixels of a row ...
+constexpr int kRectRows = 4;           // ... on four rows
+constexpr int kRectThreads = kRectLanes * kRectRows;
+
+// S(I, qx, qy) of the header: four bytes, each 0 outside the image, weighed in 1/32 and rounded half up
+__device__ __forceinline__ int rect_sample(const uint8_t *I, int w, int h, int qx, int qy)
+{
+    const int x0 = qx >> 5, a = qx & 31, y0 = qy >> 5, b = qy & 31;
+    const bool xi0 = (unsigned)x0 < (unsigned)w, xi1 = (unsigned)(x0 + 1) < (unsigned)w;
+    const bool yi0 = (unsigned)y0 < (unsigned)h, yi1 = (unsigned)(y0 + 1) < (unsigned)h;
+    const uint8_t *r0 = I + ((ptrdiff_t)y0 * w + x0), *r1 = r0 + w;     // dereferenced only where the tap is inside
+    const int p00 = yi0 && xi0 ? (int)r0[0] : 0, p01 = yi0 && xi1 ? (int)r0[1] : 0;
+    const int p10 = yi1 && xi0 ? (int)r1[0] : 0, p11 = yi1 && xi1 ? (int)r1[1] : 0;
+    return (p00 * (32 - a) * (32 - b) + p01 * a * (32 - b) + p10 * (32 - a) * b + p11 * a * b + 512) >> 10;
+}
+
+// rectify_pair: both eyes (grid z) and both stages in one launch.  The quantised maps lie interleaved, (qx, qy) per pixel: eye e has
+// `stages` planes of w h entries at q + e * stages * w h, stage 1 first.  With two stages an output pixel reads its stage-2 entry and
+// makes each of its four taps of the undistorted image U -- never written anywhere -- from that tap's stage-1 entry and four raw bytes,
+// rounded to a byte as the two-pass form rounds it, so the result is the two-pass result bit for bit.  A thread makes kRectPix pixels
+// and stores them as bm_prefilter does: one dword where they are inside the row and the address allows, bytes otherwise.
+struct RectifyArgs {
+    const uint8_t *raw;           // eyes x h x w
+    uint8_t *out;                 // eyes x h x w
+    const int2 *q;                // eyes x stages x h x w
+    int32_t w, h, stages;
+};
+__global__ __launch_bounds__(kRectThreads) void rectify_pair(RectifyArgs g)
+{
+    const int x0 = kRectPix * (int)(blockIdx.x * kRectLanes + (threadIdx.x & (kRectLanes - 1)));
+    const int y = (int)(blockIdx.y * kRectRows + threadIdx.x / kRectLanes);
+    if (x0 >= g.w || y >= g.h) return;
+    const size_t px = (size_t)g.w * g.h, eye = blockIdx.z;
+    const uint8_t *raw = g.raw + eye * px;
+    const int2 *q1 = g.q + eye * (size_t)g.stages * px, *q2 = q1 + px;
+    const size_t row = (size_t)y * g.w;
+    uint32_t out[kRectPix];
+#pragma unroll
+    for (int k = 0; k < kRectPix; k++) {
+        const int x = min(x0 + k, g.w - 1);                               // a tail repeats the row's last pixel and stores nothing of it
+        if (g.stages == 1) {
+            const int2 m = q1[row + x];
+            out[k] = (uint32_t)rect_sample(raw, g.w, g.h, m.x, m.y);
+            continue;
+        }
+        const int2 m = q2[row + x];
+        const int tx = m.x >> 5, a = m.x & 31, ty = m.y >> 5, b = m.y & 31;
+        int u[4];
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const int ux = tx + (t & 1), uy = ty + (t >> 1);
+            u[t] = 0;
+            if ((unsigned)ux < (unsigned)g.w && (unsigned)uy < (unsigned)g.h) {
+                const int2 m1 = q1[(size_t)uy * g.w + ux];
+                u[t] = rect_sample(raw, g.w, g.h, m1.x, m1.y);
+            }
+        }
+        out[k] = (uint32_t)((u[0] * (32 - a) * (32 - b) + u[1] * a * (32 - b) + u[2] * (32 - a) * b + u[3] * a * b + 512) >> 10);
+    }
+    const size_t o = eye * px + row + (size_t)x0;                         // g.out is aligned: the offset decides
+    if (x0 + kRectPix <= g.w && (o & 3) == 0) {
+        *reinterpret_cast<uint32_t *>(g.out + o) = out[0] | out[1] << 8 | out[2] << 16 | out[3] << 24;
+        return;
+    }
+    for (int k = 0; k < kRectPix && x0 + k < g.w; k++) g.out[o + k] = (uint8_t)out[k];
+}
+
 // pose_sets_batch on stored frames: the candidates' descriptors and keypoints (b.cands) point into the store, b.xyz_a and the candidates'
 // xyz are null, the points are the records.  The argument block of pose_sets_batch is b unchanged.
 struct SetsStoredArgs {
@@ -1004,6 +1075,11 @@ struct MatchState {
     DevBuf<float4> store_rec;
     DevBuf<float> stage_xyz, dense_xyz;
     DevBuf<uint8_t> bm_pre;                     // the prefiltered pair of the stereo put (or of chip_stereo_bm) in flight, kBmPad bytes behind it
+    // rectification: the quantised maps of chip_rectify_set_maps, [eye][stage][h][w] entries (qx, qy), and the one plane of the
+    // chip_remap in flight.  Nothing of this exists before the first of those calls.  A raw pair is staged behind the rectified one.
+    DevBuf<int2> rect_maps, remap_q;
+    std::vector<int2> h_rect;                   // the maps on their way up
+    int32_t rect_w = 0, rect_h = 0, rect_stages = 0;   // rect_stages == 0: no maps
     int32_t n_slots = 0, slot_kp = 0, n_frames = 0;
     std::vector<StoredFrame> slots;
     std::unordered_map<int64_t, int32_t> slot_of;   // id -> slot
@@ -2010,9 +2086,19 @@ extern "C" int chip_frame_put_stereo(chip_ctx *c, int64_t id, const uint8_t *des
 
 // A frame from its rectified pair and nothing else: the detector and the descriptor (orb.hip) run on the left image where the pair is
 // staged, orb_describe writes the slot's descriptor and keypoint rows, and the block matcher makes the records as in frame_put.  What
-// comes back is the eight kept counts.
-extern "C" int chip_frame_put_orb_stereo(chip_ctx *c, int64_t id, int32_t width, int32_t height, const uint8_t *left, const uint8_t *right,
-                                         const chip_orb_params *orb, const chip_stereo_bm_params *bm, const double Q_rowmajor[16], int32_t *n)
+// comes back is the eight kept counts.  raw: the pair is the cameras' own (chip_frame_put_raw_orb_stereo) -- it is staged behind the
+// place of the rectified pair, rectify_pair writes that pair through the ctx's maps, and the rest is the same.
+static hipError_t launch_rectify(hipStream_t s, const uint8_t *raw, uint8_t *out, const int2 *q, int32_t w, int32_t h, int32_t stages, int32_t eyes)
+{
+    RectifyArgs a;
+    a.raw = raw; a.out = out; a.q = q; a.w = w; a.h = h; a.stages = stages;
+    const dim3 grid((unsigned)((w + kRectLanes * kRectPix - 1) / (kRectLanes * kRectPix)), (unsigned)((h + kRectRows - 1) / kRectRows), (unsigned)eyes);
+    hipLaunchKernelGGL(rectify_pair, grid, dim3(kRectThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+static int put_orb_stereo(chip_ctx *c, int64_t id, int32_t width, int32_t height, const uint8_t *left, const uint8_t *right,
+                          const chip_orb_params *orb, const chip_stereo_bm_params *bm, const double Q_rowmajor[16], int32_t *n, bool raw)
 {
     if (!c || !left || !right || !Q_rowmajor || !n) return CHIP_ERR_INVALID_ARG;
     chip_orb_params d;
@@ -2026,6 +2112,8 @@ extern "C" int chip_frame_put_orb_stereo(chip_ctx *c, int64_t id, int32_t width,
     std::lock_guard<std::mutex> lk(c->match_mu);
     MatchState *st = c->match_state;
     if (!st || st->n_slots == 0) return CHIP_ERR_BUSY;
+    if (raw && st->rect_stages == 0) return CHIP_ERR_BUSY;         // no maps
+    if (raw && (width != st->rect_w || height != st->rect_h)) return CHIP_ERR_INVALID_ARG;
     if (d.n_features > st->slot_kp) return CHIP_ERR_UNSUPPORTED;   // the slot must hold whatever the detector keeps
     const auto known = st->slot_of.find(id);
     int32_t k = known != st->slot_of.end() ? known->second : -1;
@@ -2035,15 +2123,17 @@ extern "C" int chip_frame_put_orb_stereo(chip_ctx *c, int64_t id, int32_t width,
     if (k < 0) return CHIP_ERR_OOM;
     CHIP_HIP(c, hipSetDevice(c->device));
     const size_t px = (size_t)width * height, at = (size_t)k * (size_t)st->slot_kp;
-    rc = st->stage_xyz.reserve(c, (2 * px + sizeof(float) - 1) / sizeof(float));
+    rc = st->stage_xyz.reserve(c, ((raw ? 4 : 2) * px + sizeof(float) - 1) / sizeof(float));
     if (rc == CHIP_OK) rc = st->bm_pre.reserve(c, 2 * px + kBmPad);
     if (rc != CHIP_OK) return rc;
     hipStream_t s = match_stream(c);
     uint8_t *stage = reinterpret_cast<uint8_t *>(st->stage_xyz.get());
+    uint8_t *in = raw ? stage + 2 * px : stage;                    // where the caller's pair goes
     int32_t total = 0;
     const auto run = [&]() -> int {
-        CHIP_HIP(c, hipMemcpyAsync(stage, left, px, hipMemcpyHostToDevice, s));
-        CHIP_HIP(c, hipMemcpyAsync(stage + px, right, px, hipMemcpyHostToDevice, s));
+        CHIP_HIP(c, hipMemcpyAsync(in, left, px, hipMemcpyHostToDevice, s));
+        CHIP_HIP(c, hipMemcpyAsync(in + px, right, px, hipMemcpyHostToDevice, s));
+        if (raw) CHIP_HIP(c, launch_rectify(s, in, stage, st->rect_maps, width, height, st->rect_stages, 2));
         const int e = orb_enqueue(c, s, nullptr, stage, width, height, d, true, st->store_desc + at * CHIP_ORB_DESC_BYTES, st->store_kp + at,
                                   8 * sizeof(int32_t));
         if (e != CHIP_OK) return e;
@@ -2078,6 +2168,122 @@ extern "C" int chip_frame_put_orb_stereo(chip_ctx *c, int64_t id, int32_t width,
     }
     *n = total;
     return CHIP_OK;
+}
+
+extern "C" int chip_frame_put_orb_stereo(chip_ctx *c, int64_t id, int32_t width, int32_t height, const uint8_t *left, const uint8_t *right,
+                                         const chip_orb_params *orb, const chip_stereo_bm_params *bm, const double Q_rowmajor[16], int32_t *n)
+{
+    return put_orb_stereo(c, id, width, height, left, right, orb, bm, Q_rowmajor, n, false);
+}
+
+// ------------------------------------------------------------------------------------------------ frames from their raw pairs
+extern "C" int chip_build_has_rectify(void) { return 1; }
+
+// Q of the header: a map value in 1/32 pixel.  The product is exact in float; rintf rounds to nearest, ties to even (the default mode)
+static inline int32_t rect_quantize(float m)
+{
+    if (m != m) return -64;
+    return (int32_t)rintf(32.0f * fminf(fmaxf(m, -2.0f), 32768.0f));
+}
+
+extern "C" int chip_rectify_quantize(const float *map, int64_t count, int32_t *q)
+{
+    if (!map || !q || count < 0) return CHIP_ERR_INVALID_ARG;
+    for (int64_t i = 0; i < count; i++) q[i] = rect_quantize(map[i]);
+    return CHIP_OK;
+}
+
+static void rect_quantize_plane(const float *mx, const float *my, size_t px, int2 *q)
+{
+    for (size_t i = 0; i < px; i++) q[i] = make_int2(rect_quantize(mx[i]), rect_quantize(my[i]));
+}
+
+extern "C" int chip_remap(chip_ctx *c, const uint8_t *image, int32_t width, int32_t height, const float *map_x, const float *map_y, uint8_t *out)
+{
+    if (!c || !image || !map_x || !map_y || !out || width < 1 || height < 1) return CHIP_ERR_INVALID_ARG;
+    if (width > kMaxImageSide || height > kMaxImageSide) return CHIP_ERR_UNSUPPORTED;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    CHIP_HIP(c, hipSetDevice(c->device));
+    MatchState *st = nullptr;
+    int rc = match_state(c, &st);
+    if (rc != CHIP_OK) return rc;
+    const size_t px = (size_t)width * height;
+    rc = st->stage_xyz.reserve(c, (2 * px + sizeof(float) - 1) / sizeof(float));   // the result, the image behind it
+    if (rc == CHIP_OK) rc = st->remap_q.reserve(c, px);
+    if (rc != CHIP_OK) return rc;
+    try { st->h_rect.resize(px); } catch (const std::bad_alloc &) { return CHIP_ERR_OOM; }
+    rect_quantize_plane(map_x, map_y, px, st->h_rect.data());
+    hipStream_t s = match_stream(c);
+    uint8_t *stage = reinterpret_cast<uint8_t *>(st->stage_xyz.get());
+    CHIP_HIP(c, hipMemcpyAsync(st->remap_q, st->h_rect.data(), px * sizeof(int2), hipMemcpyHostToDevice, s));
+    CHIP_HIP(c, hipMemcpyAsync(stage + px, image, px, hipMemcpyHostToDevice, s));
+    CHIP_HIP(c, launch_rectify(s, stage + px, stage, st->remap_q, width, height, 1, 1));
+    CHIP_HIP(c, hipMemcpyAsync(out, stage, px, hipMemcpyDeviceToHost, s));
+    CHIP_HIP(c, hipStreamSynchronize(s));
+    return CHIP_OK;
+}
+
+extern "C" int chip_rectify_set_maps(chip_ctx *c, int32_t width, int32_t height, const float *lx1, const float *ly1, const float *lx2,
+                                     const float *ly2, const float *rx1, const float *ry1, const float *rx2, const float *ry2)
+{
+    if (!c || !lx1 || !ly1 || !rx1 || !ry1 || width < 1 || height < 1) return CHIP_ERR_INVALID_ARG;
+    const int n2 = (lx2 != nullptr) + (ly2 != nullptr) + (rx2 != nullptr) + (ry2 != nullptr);
+    if (n2 != 0 && n2 != 4) return CHIP_ERR_INVALID_ARG;
+    if (width > CHIP_ORB_MAX_SIDE || height > CHIP_ORB_MAX_SIDE) return CHIP_ERR_UNSUPPORTED;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    CHIP_HIP(c, hipSetDevice(c->device));
+    MatchState *st = nullptr;
+    int rc = match_state(c, &st);
+    if (rc != CHIP_OK) return rc;
+    const int32_t stages = n2 ? 2 : 1;
+    const size_t px = (size_t)width * height, entries = 2 * (size_t)stages * px;
+    try { st->h_rect.resize(entries); } catch (const std::bad_alloc &) { return CHIP_ERR_OOM; }
+    st->rect_stages = 0;                     // from here on the old maps are gone, whatever happens
+    rc = st->rect_maps.reserve(c, entries);  // (a regrow pauses the resident scan by itself)
+    if (rc != CHIP_OK) return rc;
+    int2 *q = st->h_rect.data();
+    rect_quantize_plane(lx1, ly1, px, q);
+    if (n2) rect_quantize_plane(lx2, ly2, px, q + px);
+    rect_quantize_plane(rx1, ry1, px, q + (size_t)stages * px);
+    if (n2) rect_quantize_plane(rx2, ry2, px, q + (size_t)stages * px + px);
+    hipStream_t s = match_stream(c);
+    CHIP_HIP(c, hipMemcpyAsync(st->rect_maps, q, entries * sizeof(int2), hipMemcpyHostToDevice, s));
+    CHIP_HIP(c, hipStreamSynchronize(s));
+    st->rect_w = width; st->rect_h = height; st->rect_stages = stages;
+    return CHIP_OK;
+}
+
+extern "C" int chip_rectify_pair(chip_ctx *c, const uint8_t *left_raw, const uint8_t *right_raw, int32_t width, int32_t height,
+                                 uint8_t *left_out, uint8_t *right_out)
+{
+    if (!c || !left_raw || !right_raw || !left_out || !right_out || width < 1 || height < 1) return CHIP_ERR_INVALID_ARG;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    MatchState *st = c->match_state;
+    if (!st || st->rect_stages == 0) return CHIP_ERR_BUSY;
+    if (width != st->rect_w || height != st->rect_h) return CHIP_ERR_INVALID_ARG;
+    CHIP_HIP(c, hipSetDevice(c->device));
+    const size_t px = (size_t)width * height;
+    const int rc = st->stage_xyz.reserve(c, (4 * px + sizeof(float) - 1) / sizeof(float));   // the rectified pair, the raw one behind it
+    if (rc != CHIP_OK) return rc;
+    hipStream_t s = match_stream(c);
+    uint8_t *stage = reinterpret_cast<uint8_t *>(st->stage_xyz.get());
+    CHIP_HIP(c, hipMemcpyAsync(stage + 2 * px, left_raw, px, hipMemcpyHostToDevice, s));
+    CHIP_HIP(c, hipMemcpyAsync(stage + 3 * px, right_raw, px, hipMemcpyHostToDevice, s));
+    CHIP_HIP(c, launch_rectify(s, stage + 2 * px, stage, st->rect_maps, width, height, st->rect_stages, 2));
+    CHIP_HIP(c, hipMemcpyAsync(left_out, stage, px, hipMemcpyDeviceToHost, s));
+    CHIP_HIP(c, hipMemcpyAsync(right_out, stage + px, px, hipMemcpyDeviceToHost, s));
+    CHIP_HIP(c, hipStreamSynchronize(s));
+    return CHIP_OK;
+}
+
+extern "C" int chip_frame_put_raw_orb_stereo(chip_ctx *c, int64_t id, int32_t width, int32_t height, const uint8_t *left_raw,
+                                             const uint8_t *right_raw, const chip_orb_params *orb, const chip_stereo_bm_params *bm,
+                                             const double Q_rowmajor[16], int32_t *n)
+{
+    return put_orb_stereo(c, id, width, height, left_raw, right_raw, orb, bm, Q_rowmajor, n, true);
 }
 
 extern "C" int chip_stereo_bm(chip_ctx *c, const uint8_t *left, const uint8_t *right, int32_t width, int32_t height,

@@ -1039,6 +1039,65 @@ int chip_frame_put_orb_stereo(chip_ctx *ctx, int64_t id, int32_t width, int32_t 
                               const chip_orb_params *orb /* NULL: the defaults */, const chip_stereo_bm_params *bm /* NULL: the defaults */,
                               const double Q_rowmajor[16], int32_t *n);
 
+/* ---- a frame from its raw stereo pair: rectification on the device (ABI 7, additive).  The pair chip_frame_put_orb_stereo takes is
+ * the RECTIFIED one.  The reference receives the cameras' raw images and makes that pair on a host core, for both frames of every
+ * candidate: StereoGeometry::do_stereo_rectification_of_raw_images (src/utils/CameraGeometry.cpp:387-402) is four
+ * cv::remap(.., CV_INTER_LINEAR) per pair -- raw -> undistorted through the camera model's maps (:39-43, :361-372), undistorted ->
+ * stereo-rectified through the cv::initUndistortRectifyMap maps of cv::stereoRectify (:348-349, :377-383) -- 4 w h bilinear gathers
+ * through float maps.  The maps are calibration data: made once per calibration by camodocal / OpenCV code that stays on the host and
+ * handed over once (chip_rectify_set_maps).  The raw pair is the same 2 w h bytes the rectified one is.
+ *
+ * THE DEFINITION IS THIS PROJECT'S OWN, all-integer after the quantiser, modelled on cv::remap with INTER_LINEAR, float maps and
+ * BORDER_CONSTANT 0, restated in tests/np_mirror_rectify.py (which the device equals bit for bit).  OpenCV's source is not part of this
+ * project, so parity against it is UNPINNED (DESIGN.md 6 lists the known departures).
+ *   - quantiser: a map value m (float) becomes q = Q(m), an int32 in 1/32 pixel.  NaN gives -64; otherwise
+ *       q = (int32) rint(32.0f * min(max(m, -2.0f), 32768.0f)),  rounding to nearest, ties to even
+ *     (the product is exact in float; -0.0 gives 0; +-inf clamp; 3.015625 -> 96, 3.046875 -> 98).  A coordinate at or beyond a clamp
+ *     has every tap outside any supported image, so no sentinel is needed.  x0 = q >> 5 (arithmetic shift), a = q & 31; the same in
+ *     y gives y0 and b.  chip_rectify_quantize is Q on the host;
+ *   - sample: with I[y][x] = 0 outside [0, h) x [0, w),
+ *       S(I, qx, qy) = (I[y0][x0] (32-a)(32-b) + I[y0][x0+1] a (32-b) + I[y0+1][x0] (32-a) b + I[y0+1][x0+1] a b + 512) >> 10
+ *     the exact bilinear value at 1/32-pixel resolution, rounded half up;
+ *   - one stage:  R[y][x] = S(raw, q1x[y][x], q1y[y][x]);
+ *   - two stages (the reference's shape):  U[y][x] = S(raw, q1x[y][x], q1y[y][x]), a uint8 as the undistorted image is in the
+ *     reference, and  R[y][x] = S(U, q2x[y][x], q2y[y][x]).  All images and maps have one size w x h;
+ *   - kernel rectify_pair: ONE launch for both eyes (a grid axis) and both stages.  U is never written: an output pixel reads its
+ *     stage-2 entry and evaluates stage 1 at each of its four U taps that lies inside the image, from that tap's stage-1 entry and
+ *     four raw bytes, rounded to uint8 before stage 2 weighs it -- a U pixel is a pure function of (raw, q1) at that pixel, so the
+ *     result is bit for bit the two-pass one.  A thread makes four consecutive pixels of a row and stores them as one dword where the
+ *     row's alignment allows.  The quantised maps lie interleaved (qx, qy) on the device; the header fixes only the arithmetic;
+ *   - chip_remap: one stage with the caller's maps into host memory (the definition made callable, the same kernel on one image with
+ *     a per-call map upload; not a hot path).  NULL ctx / image / map_x / map_y / out or a side < 1 CHIP_ERR_INVALID_ARG; a side
+ *     beyond the image limit of chip_match_pair or a group ctx CHIP_ERR_UNSUPPORTED; all decided before the device is touched.
+ *     Needs no frame store and no maps; runs on the ctx stream, serialised with the other calls of the stage;
+ *   - chip_rectify_set_maps: quantises the maps on the host and uploads them once.  They replace any maps the ctx had (after a
+ *     failure behind the argument checks the ctx has none) and are freed with the ctx.  The stage-1 maps of both eyes are required;
+ *     the four stage-2 pointers are all non-NULL (two stages) or all NULL (one stage), a mix is CHIP_ERR_INVALID_ARG as are a NULL
+ *     ctx and a side < 1; a side above CHIP_ORB_MAX_SIDE or a group ctx CHIP_ERR_UNSUPPORTED.  Needs no frame store; a process that
+ *     never calls it allocates nothing.  With the reference's names the eight arguments are the left camera's map_x, map_y,
+ *     map1_x, map1_y and the right camera's map_x, map_y, map2_x, map2_y;
+ *   - chip_rectify_pair: the dense rectified pair into host memory through the ctx's maps, for callers that stay on host frames.
+ *     NULLs or a side < 1 CHIP_ERR_INVALID_ARG, a group ctx CHIP_ERR_UNSUPPORTED, no maps set CHIP_ERR_BUSY, a size other than the
+ *     maps' CHIP_ERR_INVALID_ARG;
+ *   - chip_frame_put_raw_orb_stereo: chip_frame_put_orb_stereo with the raw pair in the place of the rectified one.  The raw pair is
+ *     staged behind the place where chip_frame_put_orb_stereo stages its pair, rectify_pair writes the rectified pair there, and from
+ *     there on the call IS the other one (one body).  Every rule, status and failure behaviour of chip_frame_put_orb_stereo holds,
+ *     in its order; in addition, behind the CHIP_ERR_BUSY of a missing reserve, no maps set is CHIP_ERR_BUSY and a size other than
+ *     the maps' CHIP_ERR_INVALID_ARG.  All statuses are decided before the device is touched; each image crosses the bus once; one
+ *     count comes back.  The frame is indistinguishable from chip_rectify_pair -> chip_frame_put_orb_stereo.                       */
+int chip_build_has_rectify(void);          /* 1 */
+int chip_rectify_quantize(const float *map, int64_t count, int32_t *q /* count */);
+int chip_remap(chip_ctx *ctx, const uint8_t *image /* height x width, dense rows */, int32_t width, int32_t height,
+               const float *map_x, const float *map_y /* height x width each */, uint8_t *out /* height x width, host */);
+int chip_rectify_set_maps(chip_ctx *ctx, int32_t width, int32_t height, const float *lx1, const float *ly1,
+                          const float *lx2, const float *ly2 /* both NULL: one stage */, const float *rx1, const float *ry1,
+                          const float *rx2, const float *ry2 /* as lx2, ly2 */);
+int chip_rectify_pair(chip_ctx *ctx, const uint8_t *left_raw, const uint8_t *right_raw, int32_t width, int32_t height,
+                      uint8_t *left_out, uint8_t *right_out /* height x width each, host */);
+int chip_frame_put_raw_orb_stereo(chip_ctx *ctx, int64_t id, int32_t width, int32_t height, const uint8_t *left_raw,
+                                  const uint8_t *right_raw, const chip_orb_params *orb /* NULL: the defaults */,
+                                  const chip_stereo_bm_params *bm /* NULL: the defaults */, const double Q_rowmajor[16], int32_t *n);
+
 /* ------------------------------------------------------------------------------------------ introspection */
 typedef struct {
     int32_t abi_version;

@@ -80,6 +80,8 @@ CHIP_ORB_BINS = 32
 CHIP_ORB_N_FEATURES, CHIP_ORB_N_LEVELS, CHIP_ORB_FAST_THRESHOLD, CHIP_ORB_BORDER = 5000, 8, 0, 31
 # rectification: map values are quantised to 1/32 pixel (5 fraction bits) inside [-2, 32768]; NaN gives -64
 CHIP_RECTIFY_FRACTION_BITS, CHIP_RECTIFY_MAP_MIN, CHIP_RECTIFY_MAP_MAX, CHIP_RECTIFY_NAN_Q = 5, -2.0, 32768.0, -64
+# descriptor projection: the matrix's element type; in_dim % 256 == 0, 256 <= in_dim <= CHIP_PROJ_MAX_IN_DIM
+CHIP_PROJ_F32, CHIP_PROJ_F64, CHIP_PROJ_MAX_IN_DIM = 1, 2, 32768
 
 
 class ChipError(RuntimeError):
@@ -325,6 +327,12 @@ _SIGS = {
     "chip_rectify_pair": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
     "chip_frame_put_raw_orb_stereo": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.POINTER(OrbParams), C.POINTER(StereoBmParams), _P,
                                                 C.POINTER(C.c_int32)]),
+    "chip_build_has_project": (C.c_int, []),
+    "chip_project_set": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P]),
+    "chip_project_clear": (C.c_int, [_P]),
+    "chip_project_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "chip_project": (C.c_int, [_P, _P, C.c_int64, _P]),
+    "chip_db_append_projected_f32": (C.c_int, [_P, _P, C.c_int64, C.c_uint32, C.POINTER(C.c_int64)]),
     "chip_get_info": (C.c_int, [_P, C.POINTER(Info)]),
     "chip_profile_enable": (C.c_int, [_P, C.c_int32]),
     "chip_profile_reset": (C.c_int, [_P]),
@@ -611,6 +619,53 @@ class Chip:
         desc = np.ascontiguousarray(desc, dtype=np.float32).reshape(-1, self.D)
         first = C.c_int64()
         self._chk(self.lib.chip_db_append_f32(self.h, _ptr(desc), desc.shape[0], C.byref(first)), "chip_db_append_f32")
+        return first.value
+
+    # -- descriptor projection: z = normalise(Mt x + b) made on the device (include/cerebro_hip.h "descriptor projection")
+    def project_set(self, Mt: np.ndarray, bias=None):
+        """chip_project_set: Mt is (D, in_dim), one row per OUTPUT component (np.ascontiguousarray(WPCA_M.T)), float32 or float64 --
+        its dtype is the matrix type; bias: D doubles or None"""
+        Mt = np.asarray(Mt)
+        if Mt.dtype not in (np.float32, np.float64) or Mt.ndim != 2 or Mt.shape[0] != self.D:
+            raise ValueError("project_set: Mt must be a (D, in_dim) float32 or float64 array")
+        Mt = np.ascontiguousarray(Mt)
+        b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float64).reshape(self.D)
+        self._chk(self.lib.chip_project_set(self.h, Mt.shape[1], _ptr(Mt), CHIP_PROJ_F32 if Mt.dtype == np.float32 else CHIP_PROJ_F64,
+                                            None if b is None else _ptr(b)), "chip_project_set")
+
+    def project_clear(self):
+        self._chk(self.lib.chip_project_clear(self.h), "chip_project_clear")
+
+    def project_info(self) -> dict:
+        """chip_project_info: in_dim 0 when no projection is set"""
+        v = [C.c_int32(), C.c_int32(), C.c_int32()]
+        self._chk(self.lib.chip_project_info(self.h, *(C.byref(x) for x in v)), "chip_project_info")
+        return dict(in_dim=v[0].value, matrix_type=v[1].value, has_bias=bool(v[2].value))
+
+    def _raw_descriptors(self, x, n):
+        """(pointer, n, what keeps it alive) of raw descriptors: a numpy array of n x in_dim float32 values, or an integer device address
+        (memory of the ctx's device that the caller has waited for) together with n"""
+        if isinstance(x, (int, np.integer)):
+            if n is None:
+                raise ValueError("a device address needs n")
+            return C.c_void_p(int(x)), int(n), None
+        in_dim = self.project_info()["in_dim"]
+        a = np.ascontiguousarray(x, dtype=np.float32)
+        a = a.reshape(-1, in_dim) if in_dim else a.reshape(1, -1)      # (without a projection the call reports CHIP_ERR_BUSY itself)
+        return _ptr(a), a.shape[0], a
+
+    def project(self, x, n: int | None = None) -> np.ndarray:
+        """chip_project -> (n, D) float64: the rows an append_projected of the same x would store in a double-row DB"""
+        p, n, keep = self._raw_descriptors(x, n)
+        z = np.empty((n, self.D), dtype=np.float64)
+        self._chk(self.lib.chip_project(self.h, p, n, _ptr(z)), "chip_project")
+        return z
+
+    def append_projected(self, x, flags: int = 0, n: int | None = None) -> int:
+        """chip_db_append_projected_f32 -> the index of the first row appended"""
+        p, n, keep = self._raw_descriptors(x, n)
+        first = C.c_int64()
+        self._chk(self.lib.chip_db_append_projected_f32(self.h, p, n, flags, C.byref(first)), "chip_db_append_projected_f32")
         return first.value
 
     def append_synthetic(self, n: int, seed: int, plants=(), unit: bool = False):

@@ -852,18 +852,25 @@ static int ring_begin_append(Ctx *c, int64_t new_total)
 int append_reserve(Ctx *c, int64_t first, int64_t n) { return ensure_capacity(c, local_count(c, first + n)); }
 
 // Upload rows [from, from + count) of the call (step > 1: every step-th row, i.e. one shard's rows) in staging-sized chunks and
-// run K3 on them.  ring: mirror into the replicated ring as well.
-static int append_pass(Ctx *c, const void *desc, int src_elem, int64_t first, int64_t from, int64_t count, int64_t step, bool ring)
+// run K3 on them.  ring: mirror into the replicated ring as well.  A projected append (src.raw) makes each chunk's rows on the device
+// instead of copying them: the raw descriptors are staged already (ctx_append), the rows are doubles.
+static int append_pass(Ctx *c, const AppendSrc &src, int64_t first, int64_t from, int64_t count, int64_t step, bool ring)
 {
+    const int src_elem = src.elem;
     const size_t row_bytes = (size_t)c->D * src_elem;
     const int64_t chunk_rows = (int64_t)(c->stage_bytes / row_bytes);
     for (int64_t done = 0; done < count; done += chunk_rows) {
         const int64_t m = (count - done) < chunk_rows ? (count - done) : chunk_rows;
-        const char *src = static_cast<const char *>(desc) + (size_t)(from + done * step) * row_bytes;
-        if (step == 1)
-            CHIP_HIP(c, hipMemcpyAsync(c->stage_dev, src, (size_t)m * row_bytes, hipMemcpyHostToDevice, c->s_append));
-        else   // one shard's rows: a strided gather out of the caller's batch, one row per pitch line
-            CHIP_HIP(c, hipMemcpy2DAsync(c->stage_dev, row_bytes, src, (size_t)step * row_bytes, row_bytes, (size_t)m, hipMemcpyHostToDevice, c->s_append));
+        if (src.raw) {   // (plain single-GPU ctx: step == 1)
+            const int r = project_chunk(c, from + done, m);
+            if (r != CHIP_OK) return r;
+        } else {
+            const char *host = static_cast<const char *>(src.desc) + (size_t)(from + done * step) * row_bytes;
+            if (step == 1)
+                CHIP_HIP(c, hipMemcpyAsync(c->stage_dev, host, (size_t)m * row_bytes, hipMemcpyHostToDevice, c->s_append));
+            else   // one shard's rows: a strided gather out of the caller's batch, one row per pitch line
+                CHIP_HIP(c, hipMemcpy2DAsync(c->stage_dev, row_bytes, host, (size_t)step * row_bytes, row_bytes, (size_t)m, hipMemcpyHostToDevice, c->s_append));
+        }
         const int r = launch_store_rows(c, c->s_append, c->stage_dev, src_elem, m, first + from + done * step, c->flags_dev, ring, step);
         if (r != CHIP_OK) return r;
         // the staging buffer is reused by the next chunk: stream order serialises copy -> kernel -> copy
@@ -873,7 +880,7 @@ static int append_pass(Ctx *c, const void *desc, int src_elem, int64_t first, in
 
 // DB rows only (rows past the published length are invisible to queries); *bad gets the validation bits of THIS ctx's share:
 // bit0 = a value that is not float32-representable went into float rows, bit1 = NaN / Inf.
-int append_store_db(Ctx *c, const void *desc, int src_elem, int64_t first, int64_t n, bool owner_only, uint32_t *bad)
+int append_store_db(Ctx *c, const AppendSrc &src, int64_t first, int64_t n, bool owner_only, uint32_t *bad)
 {
     *c->flags_host.host() = 0;
     CHIP_HIP(c, hipMemsetAsync(c->flags_dev, 0, sizeof(uint32_t), c->s_append));
@@ -883,9 +890,9 @@ int append_store_db(Ctx *c, const void *desc, int src_elem, int64_t first, int64
         const int64_t G = c->nranks;
         const int64_t i0 = ((c->rank - first) % G + G) % G;               // first row of the batch this shard owns
         const int64_t cnt = n > i0 ? (n - i0 + G - 1) / G : 0;
-        rc = append_pass(c, desc, src_elem, first, i0, cnt, G, false);
+        rc = append_pass(c, src, first, i0, cnt, G, false);
     } else {
-        rc = append_pass(c, desc, src_elem, first, 0, n, 1, false);
+        rc = append_pass(c, src, first, 0, n, 1, false);
     }
     if (rc != CHIP_OK) return rc;
     CHIP_HIP(c, hipMemcpyAsync(c->flags_host.host(), c->flags_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_append));
@@ -921,13 +928,13 @@ void append_publish(Ctx *c, int64_t new_total, bool lossy, int64_t n)
     c->store_auto = false;           // the storage type is final once the DB holds a row
 }
 
-int append_ring_publish(Ctx *c, const void *desc, int src_elem, int64_t first, int64_t n, bool lossy)
+int append_ring_publish(Ctx *c, const AppendSrc &src, int64_t first, int64_t n, bool lossy)
 {
     if (c->ring_dev) {  // sharded: mirror the newest rows into the replicated ring (the DB store of owned rows is idempotent)
         int rc = ring_begin_append(c, first + n);
         if (rc != CHIP_OK) return rc;
         const int64_t m = n < CHIP_RING_ROWS ? n : CHIP_RING_ROWS;
-        rc = append_pass(c, desc, src_elem, first, n - m, m, 1, true);
+        rc = append_pass(c, src, first, n - m, m, 1, true);
         if (rc != CHIP_OK) return rc;
         CHIP_HIP(c, hipStreamSynchronize(c->s_append));
     }
@@ -935,21 +942,25 @@ int append_ring_publish(Ctx *c, const void *desc, int src_elem, int64_t first, i
     return CHIP_OK;
 }
 
-int ctx_append(Ctx *c, const void *desc, int src_elem, int64_t n, uint32_t flags, int64_t *first_index)
+int ctx_append(Ctx *c, const AppendSrc &src, int64_t n, uint32_t flags, int64_t *first_index)
 {
-    if (!c || !desc || n < 0) return CHIP_ERR_INVALID_ARG;
+    if (!c || !(src.raw ? (const void *)src.raw : src.desc) || n < 0) return CHIP_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> alk(c->append_mu);
+    if (src.raw && !c->proj.in_dim) return CHIP_ERR_BUSY;   // a projected append without a projection
     CHIP_HIP(c, hipSetDevice(c->device));
     const int64_t first = published_rows(c);
     if (first_index) *first_index = first;
     if (n == 0) return CHIP_OK;
+    // a projected append launches kernels that fill every CU and do not fit beside the resident scan instance (project.hip project_chunk)
+    ResidentPause paused(c, src.raw != nullptr);
     int rc = append_reserve(c, first, n);
+    if (rc == CHIP_OK && src.raw) rc = project_stage_input(c, src.raw, n);   // once: a retry below projects the staged descriptors again
     if (rc != CHIP_OK) return rc;
     // A ctx that is fed the whole stream by its own caller (single GPU, or one process per GPU) validates the WHOLE batch, so that
     // every rank takes the same storage-type / rejection decision without talking to the others.
     uint32_t bad = 0;
     for (int attempt = 0; attempt < 2; attempt++) {
-        rc = append_store_db(c, desc, src_elem, first, n, false, &bad);
+        rc = append_store_db(c, src, first, n, false, &bad);
         if (rc != CHIP_OK) return rc;
         if (bad & 2u) return CHIP_ERR_NONFINITE;
         if (!(bad & 1u)) break;
@@ -965,7 +976,7 @@ int ctx_append(Ctx *c, const void *desc, int src_elem, int64_t n, uint32_t flags
         }
         return CHIP_ERR_NOT_F32;
     }
-    return append_ring_publish(c, desc, src_elem, first, n, (bad & 1u) != 0);
+    return append_ring_publish(c, src, first, n, (bad & 1u) != 0);
 }
 
 int synth_generate(Ctx *c, int64_t first, int64_t n, uint64_t seed, const int64_t *plant_dst, const int64_t *plant_src, const int32_t *plant_kind, int64_t n_plant, int unit)
@@ -1172,13 +1183,21 @@ int chip_synchronize(chip_ctx *c)
 int chip_db_append_f64(chip_ctx *c, const double *desc, int64_t n, uint32_t flags, int64_t *first_index)
 {
     if (!c) return CHIP_ERR_INVALID_ARG;
-    return c->group ? group_append(c, desc, 8, n, flags, first_index) : ctx_append(c, desc, 8, n, flags, first_index);
+    return c->group ? group_append(c, desc, 8, n, flags, first_index) : ctx_append(c, AppendSrc{desc, 8}, n, flags, first_index);
+}
+
+// chip_db_append_f64 with the rows made on the device from raw descriptors (project.hip): the same phases, a second kind of source
+int chip_db_append_projected_f32(chip_ctx *c, const float *x, int64_t n, uint32_t flags, int64_t *first_index)
+{
+    if (!c || !x || n < 0) return CHIP_ERR_INVALID_ARG;
+    if (c->group || c->nranks > 1) return CHIP_ERR_UNSUPPORTED;
+    return ctx_append(c, AppendSrc{nullptr, 8, x}, n, flags, first_index);
 }
 
 int chip_db_append_f32(chip_ctx *c, const float *desc, int64_t n, int64_t *first_index)
 {
     if (!c) return CHIP_ERR_INVALID_ARG;
-    return c->group ? group_append(c, desc, 4, n, 0, first_index) : ctx_append(c, desc, 4, n, 0, first_index);
+    return c->group ? group_append(c, desc, 4, n, 0, first_index) : ctx_append(c, AppendSrc{desc, 4}, n, 0, first_index);
 }
 
 int64_t chip_db_size(const chip_ctx *c)

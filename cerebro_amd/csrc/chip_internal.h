@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <mutex>
+#include <utility>
 #include <condition_variable>
 #include <vector>
 #include "../../include/cerebro_hip.h"
@@ -136,6 +137,7 @@ public:
     int alloc(Ctx *c, size_t n);
     int reserve(Ctx *c, size_t n);
     void release() { if (p_) (void)hipFree(p_); p_ = nullptr; cap_ = 0; }
+    void swap(DevBuf &o) { std::swap(p_, o.p_); std::swap(cap_, o.cap_); }   // (the caller frees what it got inside a pause of its own)
     T *get() const { return p_; }
     operator T *() const { return p_; }
     size_t capacity() const { return cap_; }
@@ -159,6 +161,29 @@ private:
     T *h_ = nullptr, *d_ = nullptr;
     size_t cap_ = 0;
 };
+
+// ---- descriptor projection (project.hip): z = normalise(Mt x + b) made on the device, for chip_project and the projected append.
+// Everything is guarded by append_mu: the calls are appends, or share the append's stream and staging buffer.
+struct Projection {
+    DevBuf<char> buf;                 // [matrix: D rows of in_dim elements][bias: D doubles][y: D doubles], replaced as a whole
+    DevBuf<float> x;                  // the raw descriptors of the running call (n x in_dim), grown on demand
+    size_t mat_bytes = 0;
+    int32_t in_dim = 0;               // 0: no projection set
+    int32_t matrix_type = 0;          // CHIP_PROJ_F32 / CHIP_PROJ_F64
+    int32_t D = 0;
+    bool has_bias = false;
+    double *bias() const { return reinterpret_cast<double *>(buf.get() + mat_bytes); }
+    double *y() const { return bias() + D; }
+};
+// Where the rows of an append come from: host rows of `elem` bytes per value, or (raw != null) n raw descriptors for the ctx's
+// projection -- host memory or memory of the ctx's device -- whose rows are made in the staging buffer as doubles (elem == 8).
+struct AppendSrc {
+    const void *desc;
+    int elem;
+    const float *raw = nullptr;
+};
+int project_stage_input(Ctx *c, const float *x, int64_t n);   // raw descriptors -> Projection::x, enqueued on s_append
+int project_chunk(Ctx *c, int64_t from, int64_t m);           // staged descriptors [from, from + m) -> rows 0 .. m-1 of stage_dev, on s_append
 
 // kernels.hip
 int launch_resident(Ctx *c, hipStream_t s, const ResidentArgs &ra, int grid);   // CHIP_ERR_UNSUPPORTED in a build without the rows form
@@ -385,6 +410,7 @@ struct Ctx {
     BatchState *batch_state = nullptr;
     MatchState *match_state = nullptr;
     OrbState *orb_state = nullptr;   // orb.hip: created by the first chip_orb_detect; its calls take match_mu
+    Projection proj;                 // project.hip (append_mu)
     std::mutex match_mu;         // serialises the matching calls of a ctx; taken BEFORE pnp_mu / icp_mu (chip_*_ransac_matched)
 
     mutable hipError_t last_hip = hipSuccess;
@@ -421,15 +447,15 @@ struct RingGuard {   // sharded ctx: residency check .. scan event recorded, vs 
 };
 int ctx_create(chip_ctx **out, int32_t D, int64_t capacity_hint, int32_t device, int32_t rank, int32_t nranks, uint32_t flags);
 void ctx_destroy(chip_ctx *c);
-int ctx_append(Ctx *c, const void *desc, int src_elem, int64_t n, uint32_t flags, int64_t *first_index);
+int ctx_append(Ctx *c, const AppendSrc &src, int64_t n, uint32_t flags, int64_t *first_index);
 // the phases of an append, for callers that must take the same decision on several contexts (group_append): reserve -> store the
 // DB rows (unpublished; owner_only: upload only the rows this shard owns) -> [switch an empty undecided DB to double rows] ->
 // mirror the newest rows into the ring and publish the length.  The caller holds the append lock.
 int append_reserve(Ctx *c, int64_t first, int64_t n);
-int append_store_db(Ctx *c, const void *desc, int src_elem, int64_t first, int64_t n, bool owner_only, uint32_t *bad);
+int append_store_db(Ctx *c, const AppendSrc &src, int64_t first, int64_t n, bool owner_only, uint32_t *bad);
 bool append_can_switch_to_double(const Ctx *c, int64_t first);
 int append_switch_to_double(Ctx *c, int64_t n);
-int append_ring_publish(Ctx *c, const void *desc, int src_elem, int64_t first, int64_t n, bool lossy);
+int append_ring_publish(Ctx *c, const AppendSrc &src, int64_t first, int64_t n, bool lossy);
 int synth_generate(Ctx *c, int64_t first, int64_t n, uint64_t seed, const int64_t *plant_dst, const int64_t *plant_src, const int32_t *plant_kind, int64_t n_plant, int unit);
 void append_publish(Ctx *c, int64_t new_total, bool lossy, int64_t n);
 int64_t published_rows(const Ctx *c);

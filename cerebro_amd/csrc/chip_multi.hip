@@ -489,7 +489,7 @@ int group_append(Ctx *gc, const void *desc, int src_elem, int64_t n, uint32_t fl
     for (int attempt = 0; attempt < 2; attempt++) {
         int rc = run_all(G, [&](int g) { return on_dev(g, [&](Ctx *c) { return append_reserve(c, first, n); }); });
         if (rc != CHIP_OK) return rc;
-        rc = run_all(G, [&](int g) { return on_dev(g, [&](Ctx *c) { return append_store_db(c, desc, src_elem, first, n, true, &bad[(size_t)g]); }); });
+        rc = run_all(G, [&](int g) { return on_dev(g, [&](Ctx *c) { return append_store_db(c, AppendSrc{desc, src_elem}, first, n, true, &bad[(size_t)g]); }); });
         if (rc != CHIP_OK) return rc;
         any_bad = 0;
         for (uint32_t b : bad) any_bad |= b;
@@ -504,7 +504,7 @@ int group_append(Ctx *gc, const void *desc, int src_elem, int64_t n, uint32_t fl
         return CHIP_ERR_NOT_F32;
     }
     const bool lossy = (any_bad & 1u) != 0;
-    const int rc = run_all(G, [&](int g) { return on_dev(g, [&](Ctx *c) { return append_ring_publish(c, desc, src_elem, first, n, lossy); }); });
+    const int rc = run_all(G, [&](int g) { return on_dev(g, [&](Ctx *c) { return append_ring_publish(c, AppendSrc{desc, src_elem}, first, n, lossy); }); });
     if (rc != CHIP_OK) return group_break(G, rc);
     mirror_state(gc);
     return CHIP_OK;

@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <limits>
 #include <sstream>
 #include <thread>
 #include <unordered_map>
@@ -41,6 +42,38 @@ bool Cerebro::descriptor_available(const Time &stamp, const double *desc, int n)
     status_ = chip_db_append_f64(ctx_, desc, 1, 0, &first);  // float64[] -> device row (Cerebro.cpp:268-274)
     if (status_ != CHIP_OK) return false;
     std::lock_guard<std::mutex> lk(m_wholeImageComputedList);  // Cerebro.cpp:321-326
+    wholeImageComputedList.push_back(stamp);
+    return (int64_t)wholeImageComputedList.size() == first + 1;
+}
+
+bool Cerebro::set_descriptor_projection(int in_dim, const void *Mt, int matrix_type, const double *bias)
+{
+    if (!ctx_) { status_ = CHIP_ERR_NO_DEVICE; return false; }
+    status_ = chip_project_set(ctx_, in_dim, Mt, matrix_type, bias);
+    if (status_ != CHIP_OK) return false;
+    proj_in_dim_ = in_dim;
+    return true;
+}
+
+bool Cerebro::raw_descriptor_available(const Time &stamp, const double *raw, int n)
+{
+    if (!raw || n <= 0) { status_ = CHIP_ERR_INVALID_ARG; return false; }
+    raw_f32_.resize((size_t)n);
+    for (int i = 0; i < n; i++) {
+        // not what a float32 network emitted: beyond float's range (decided BEFORE the conversion, which is undefined there), a NaN,
+        // or a value that the conversion rounds
+        if (!(std::fabs(raw[i]) <= (double)std::numeric_limits<float>::max())) { status_ = CHIP_ERR_NOT_F32; return false; }
+        const float f = (float)raw[i];
+        if ((double)f != raw[i]) { status_ = CHIP_ERR_NOT_F32; return false; }
+        raw_f32_[(size_t)i] = f;
+    }
+    if (!ctx_) { status_ = CHIP_ERR_NO_DEVICE; return false; }
+    if (proj_in_dim_ == 0) { status_ = CHIP_ERR_BUSY; return false; }
+    if (n != proj_in_dim_) { status_ = CHIP_ERR_INVALID_ARG; return false; }
+    int64_t first = -1;
+    status_ = chip_db_append_projected_f32(ctx_, raw_f32_.data(), 1, 0, &first);
+    if (status_ != CHIP_OK) return false;
+    std::lock_guard<std::mutex> lk(m_wholeImageComputedList);  // as descriptor_available
     wholeImageComputedList.push_back(stamp);
     return (int64_t)wholeImageComputedList.size() == first + 1;
 }

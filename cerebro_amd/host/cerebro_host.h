@@ -56,6 +56,18 @@ public:
 
     // ---- producer side (desc_th): Cerebro.cpp:268-275 = setWholeImageDescriptor + wholeImageComputedList_pushback
     bool descriptor_available(const Time &stamp, const double *desc, int n);
+    // The same step for a model whose descriptor is a projection of what the network emits (ReljaNetVLAD: whitening PCA + L2 norm,
+    // whole_image_desc_compute_server.py:145-149): the server sends the network's raw vector and the device makes the row
+    // (chip_project_set / chip_db_append_projected_f32).  Mt: D x in_dim, one row per OUTPUT component; matrix_type CHIP_PROJ_F32 /
+    // CHIP_PROJ_F64; bias: D doubles or null.  Returns false with last_status() set (no ctx: CHIP_ERR_NO_DEVICE).
+    bool set_descriptor_projection(int in_dim, const void *Mt, int matrix_type, const double *bias);
+    int projection_in_dim() const { return proj_in_dim_; }   // 0: none set
+    // raw: the n == in_dim values of the .srv wire type (float64[]) that carry the network's float32 output; they are narrowed on the
+    // host, and a value that is not a float32 ((double)(float)v != v; a NaN too) is CHIP_ERR_NOT_F32 with nothing registered.
+    // Otherwise the bookkeeping of descriptor_available.  (A caller that routes by length, as ros_adapter does, sends EVERY response
+    // here when in_dim equals the descriptor size -- the limits allow 4096 -> 4096 --: with such a projection set there is no finished-
+    // descriptor route.)
+    bool raw_descriptor_available(const Time &stamp, const double *raw, int n);
 
     // Cold start from a checkpoint written by DataManager::saveStateToDisk: every node that carries a descriptor is
     // appended in file (= time-stamp) order, as Cerebro rebuilds wholeImageComputedList after loadStateFromDisk
@@ -112,6 +124,8 @@ public:
 
 private:
     chip_ctx *ctx_ = nullptr;
+    int proj_in_dim_ = 0;
+    std::vector<float> raw_f32_;   // raw_descriptor_available's narrowed copy (the producer thread's alone)
     int status_ = 0;
     int D_ = 0;
     std::string error_;

@@ -173,6 +173,63 @@ int chip_db_append_synthetic(chip_ctx *ctx, int64_t n, uint64_t seed,
 int chip_db_append_synthetic_unit(chip_ctx *ctx, int64_t n, uint64_t seed,
                                   const int64_t *plant_dst, const int64_t *plant_src, const int32_t *plant_kind, int64_t n_plant);
 
+/* ------------------------------------------------------------------------------------------ descriptor projection
+ * (ABI 7, additive.)  For the reference's one 4096-D model, ReljaNetVLAD, the descriptor is not what the network emits: the server
+ * takes the 32768-D float32 VLAD vector and applies the whitening PCA and an L2 normalisation on a host core
+ * (scripts/whole_image_desc_compute_server.py:145-149), a 32768 x 4096 matrix streamed through a CPU for every keyframe.  These
+ * entries keep that matrix on the device and make the row there: z = (Mt x + b) / |Mt x + b|, appended without a host round trip.
+ *
+ * The definition.  Inputs: x, in_dim float32 values (what model.predict returns); Mt, D x in_dim, one contiguous row per OUTPUT
+ * component, Mt[j][i] = WPCA_M[i][j], i.e. np.ascontiguousarray(WPCA_M.T), of element type CHIP_PROJ_F32 or CHIP_PROJ_F64; b, D
+ * doubles or NULL; D the ctx's descriptor size.
+ *   - CHIP_PROJ_F32:  t_j = orc_dot_tree_f32(x, Mt[j], in_dim): lane L of 64 accumulates elements k*256 + 4L + c (k ascending,
+ *     c = 0..3) by fma into one fp64 accumulator -- the products of two float32 values are exact in fp64 -- then the xor butterfly
+ *     acc[L] += acc[L ^ m], m = 32..1.
+ *   - CHIP_PROJ_F64:  t_j = orc_dot_tree_f64((double)x, Mt[j], in_dim): elements k*128 + 2L + c (c = 0, 1), ONE fused multiply-add
+ *     per term (its single rounding is part of the definition), the same butterfly.
+ *     These are exactly the orders of DESIGN.md 3 for DB rows of that type: y = Mt x is the score vector of one query against a
+ *     database of D rows of in_dim elements.
+ *   - y_j = t_j + b_j, one IEEE addition; with b == NULL y_j = t_j and nothing is added.
+ *   - s = orc_dot_tree_f64(y, y, D);  r = sqrt(s), correctly rounded;  z_j = y_j / r, IEEE division.  The row is z.
+ *   - Nothing is special-cased: r == 0 gives NaN, a NaN or Inf anywhere in x, Mt or b reaches z, and the append's own check
+ *     refuses the row (CHIP_ERR_NONFINITE).
+ *   - Limits: in_dim % 256 == 0, 256 <= in_dim <= CHIP_PROJ_MAX_IN_DIM (x stays in the LDS as float32: 128 of its 160 KiB); any
+ *     D a ctx accepts.
+ * UNPINNED against numpy: np.matmul sums in the order of whatever BLAS numpy was built with (float32 sgemv if both operands are
+ * float32), np.linalg.norm likewise, and the dtype of the reference's .mat files is on no machine of this project.  What the tests
+ * prove is device == this definition, bit for bit, and that the definition lies within the standard gamma bound of the exact
+ * rational result.
+ *
+ *   - chip_project_set uploads the matrix once (in_dim * D * 4 or * 8 bytes of device memory, the bias next to it as doubles); it
+ *     lives until chip_project_clear or chip_destroy.  A second call replaces the projection; the new matrix is complete on the device
+ *     before the old one goes, so both exist for the duration of the call and CHIP_ERR_OOM leaves the earlier projection in place.
+ *   - chip_project_info: in_dim 0 and matrix_type 0 when none is set; any output pointer may be NULL.
+ *   - chip_project: the definition made callable (the reference also keeps the descriptor in its DataNode and its state.json):
+ *     n raw descriptors -> z, n x D doubles in host memory.  One pass over the matrix per descriptor.
+ *   - chip_db_append_projected_f32 is chip_db_append_f64 with the rows made on the device: every rule of that call holds (validation,
+ *     the storage type decided by an empty undecided DB -- which becomes a double-row DB --, CHIP_ERR_NOT_F32 on a float-row DB with
+ *     nothing appended, CHIP_APPEND_ALLOW_ROUNDING, lossy_rows, row_norm_max, publication when the rows are resident), and the DB
+ *     afterwards is indistinguishable from chip_db_append_f64(ctx, z of chip_project, n, flags, ..).
+ *   - x may be host memory, or device memory of the ctx's device (e.g. the data_ptr() of a torch tensor when the backbone runs
+ *     under PyTorch-ROCm in the same process): it is copied with hipMemcpyDefault on the append stream, and the CALLER vouches
+ *     that x is complete -- whatever produced it on another stream has been waited for.
+ *   - These calls are appends: they serialise with chip_db_append_* of the ctx and may run beside its queries and ticks.  With
+ *     CHIP_TICK_RESIDENT=1, chip_project and chip_db_append_projected_f32 pause the resident scan instance for their duration (as
+ *     chip_resident_pause does: ticks that arrive meanwhile are launched, the next one afterwards starts a new instance): project_rows
+ *     needs a workgroup with up to 128 KiB of LDS on every CU, which cannot be placed beside the instance's.
+ * Status, in this order: a NULL ctx / Mt / x / z or n < 0 CHIP_ERR_INVALID_ARG; in_dim outside the limits or an unknown matrix_type
+ * CHIP_ERR_UNSUPPORTED (both before the ctx is touched); a chip_create_multi ctx or a sharded ctx (shard_count > 1)
+ * CHIP_ERR_UNSUPPORTED; no projection set CHIP_ERR_BUSY; n == 0 CHIP_OK (first_index is filled).                              */
+#define CHIP_PROJ_F32 1
+#define CHIP_PROJ_F64 2
+#define CHIP_PROJ_MAX_IN_DIM 32768
+int chip_build_has_project(void);          /* 1 */
+int chip_project_set(chip_ctx *ctx, int32_t in_dim, const void *Mt, int32_t matrix_type, const double *bias /* may be NULL */);
+int chip_project_clear(chip_ctx *ctx);
+int chip_project_info(const chip_ctx *ctx, int32_t *in_dim, int32_t *matrix_type, int32_t *has_bias);
+int chip_project(chip_ctx *ctx, const float *x, int64_t n, double *z /* n x D, host */);
+int chip_db_append_projected_f32(chip_ctx *ctx, const float *x, int64_t n, uint32_t flags, int64_t *first_index);
+
 /* ------------------------------------------------------------------------------------------ scan + top-k
  * Replaces  u = v.transpose() * M.leftCols(k); maxCoeff(); last-index argmax  (src/Cerebro.cpp:1026-1043)
  * generalised to top-K (the compiled-out faiss variants use K=5, src/Cerebro.cpp:460).

@@ -30,6 +30,10 @@ LoopEdge to_msg(const cerebro_hip::LoopEdgePOD &e);
 
 // The descriptor thread's step (Cerebro.cpp:260-275): hand the service response's float64[] to the device DB.
 // Also registers the frame in the data_map mirror, so that foundLoops_as_JSON reports the reference's global_a / global_b.
+// With a projection set (Cerebro::set_descriptor_projection) a response of its INPUT length is the network's raw vector and goes to
+// Cerebro::raw_descriptor_available; a response of the descriptor size goes to descriptor_available as before.  Routing is by length
+// alone: a projection whose input length EQUALS the descriptor size takes the raw route for every response (a server that sends
+// finished descriptors must then not be paired with a projection).
 bool descriptor_from_response(cerebro_hip::Cerebro &cer, const ros::Time &stamp, const WholeImageDescriptorCompute::Response &res);
 
 // Every camera frame (DataManager's image callback inserts a node per frame): keeps global_a / global_b reference-compatible.

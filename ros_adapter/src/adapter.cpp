@@ -23,6 +23,10 @@ bool descriptor_from_response(cerebro_hip::Cerebro &cer, const ros::Time &stamp,
 {
     if (res.desc.empty()) return false;           // Cerebro.cpp:262: the reference asserts desc.size() > 0
     cer.data_map_insert(from_ros(stamp));
+    // a server that sends the network's raw vector (a projection is set, and the response has its input length): the row is made on the
+    // device.  The raw route comes first: with in_dim == descriptor size every response is a raw vector (adapter.h)
+    if (cer.projection_in_dim() > 0 && (int)res.desc.size() == cer.projection_in_dim())
+        return cer.raw_descriptor_available(from_ros(stamp), res.desc.data(), (int)res.desc.size());
     return cer.descriptor_available(from_ros(stamp), res.desc.data(), (int)res.desc.size());
 }
 

@@ -13,7 +13,7 @@ ORCFLAGS   ?= -O2 -mfma -ffp-contract=off -fopenmp -fPIC -Wall -Wextra
 
 LIBDIR     := cerebro_amd/lib
 CSRC       := cerebro_amd/csrc
-HIP_SRCS   := $(CSRC)/kernels.hip $(CSRC)/chip_api.hip $(CSRC)/resident.hip $(CSRC)/chip_multi.hip $(CSRC)/pnp.hip $(CSRC)/icp.hip $(CSRC)/batch.hip $(CSRC)/match.hip $(CSRC)/orb.hip $(CSRC)/project.hip
+HIP_SRCS   := $(CSRC)/kernels.hip $(CSRC)/chip_api.hip $(CSRC)/resident.hip $(CSRC)/chip_multi.hip $(CSRC)/pnp.hip $(CSRC)/icp.hip $(CSRC)/batch.hip $(CSRC)/match.hip $(CSRC)/frames.hip $(CSRC)/orb.hip $(CSRC)/project.hip
 HIP_OBJS   := $(HIP_SRCS:$(CSRC)/%.hip=$(LIBDIR)/%.o)
 ORC_SRCS   := $(wildcard oracle/*.c)
 
@@ -29,7 +29,7 @@ testlibs: tests/fakerccl/_build/libfakerccl.so $(LIBDIR)/norows/libcerebro_hip.s
 # tests/ load this one for the tests that inject faults (cerebro_amd.capi.use_hooks_library).  Never deploy it.
 HOOK_SRCS  := chip_api resident chip_multi pnp
 HOOK_OBJS  := $(HOOK_SRCS:%=$(LIBDIR)/hooks/%.o)
-$(LIBDIR)/hooks/%.o: $(CSRC)/%.hip $(CSRC)/chip_internal.h $(CSRC)/ransac_common.h $(CSRC)/topk_merge.h include/cerebro_hip.h
+$(LIBDIR)/hooks/%.o: $(CSRC)/%.hip $(CSRC)/chip_internal.h $(CSRC)/frame_store.h $(CSRC)/ransac_common.h $(CSRC)/topk_merge.h include/cerebro_hip.h
 	@mkdir -p $(LIBDIR)/hooks
 	$(HIPCC) $(HIPFLAGS) -DCHIP_TEST_HOOKS -c $< -o $@
 $(LIBDIR)/hooks/libcerebro_hip.so: $(HOOK_OBJS) $(HIP_OBJS)
@@ -44,7 +44,7 @@ tests/fakerccl/_build/libfakerccl.so: tests/fakerccl/fakerccl.cc
 	@mkdir -p tests/fakerccl/_build
 	$(HIPCC) -O2 -std=c++17 -fPIC -shared $< -o $@ -lrt -lpthread
 
-$(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC)/chip_internal.h $(CSRC)/ransac_common.h $(CSRC)/topk_merge.h include/cerebro_hip.h
+$(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC)/chip_internal.h $(CSRC)/frame_store.h $(CSRC)/ransac_common.h $(CSRC)/topk_merge.h include/cerebro_hip.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

@@ -164,6 +164,7 @@ void ctx_destroy(chip_ctx *c)
     icp_destroy(c);
     batch_destroy(c);
     match_destroy(c);
+    frame_store_destroy(c);
     orb_destroy(c);
     for (void *p : c->segs) (void)hipFree(p);
     for (int i = 0; i < Ctx::kRing; i++) {

@@ -281,6 +281,7 @@ struct PnpState;   // pnp.hip / icp.hip / batch.hip / match.hip: a unit's scratc
 struct IcpState;
 struct BatchState;
 struct MatchState;
+struct FrameStore; // frame_store.h: the frame store and the buffers of the calls that fill it
 struct OrbState;
 struct Exchange;   // chip_multi.hip: how a sharded ctx trades its per-shard top-k lists (RCCL communicator / device copies)
 struct Group;      // chip_multi.hip: a ctx made of G per-device sub-contexts driven from one process
@@ -409,6 +410,7 @@ struct Ctx {
     IcpState *icp_state = nullptr;
     BatchState *batch_state = nullptr;
     MatchState *match_state = nullptr;
+    FrameStore *frame_store = nullptr;   // frames.hip: created by the first frame call that needs it; guarded by match_mu
     OrbState *orb_state = nullptr;   // orb.hip: created by the first chip_orb_detect; its calls take match_mu
     Projection proj;                 // project.hip (append_mu)
     std::mutex match_mu;         // serialises the matching calls of a ctx; taken BEFORE pnp_mu / icp_mu (chip_*_ransac_matched)
@@ -610,8 +612,9 @@ void pnp_destroy(Ctx *c);
 void icp_destroy(Ctx *c);
 void batch_destroy(Ctx *c);
 void match_destroy(Ctx *c);   // match.hip
+void frame_store_destroy(Ctx *c);   // frames.hip
 void orb_destroy(Ctx *c);     // orb.hip
-// orb.hip in pieces, so that match.hip can put a frame straight from its pair (chip_frame_put_orb_stereo).  orb_check: the statuses of
+// orb.hip in pieces, so that frames.hip can put a frame straight from its pair (chip_frame_put_orb_stereo).  orb_check: the statuses of
 // chip_orb_detect for the size and the parameters, d the parameters in force.  orb_enqueue: the detector and (describe) the descriptor of
 // one image -- host memory, or device memory with dense rows -- enqueued on s up to the copy of the first `back` bytes of its output
 // (eight int32 kept counts, then the records) into pinned memory; orb_describe writes to desc_dev / kp_dev (null: the state's own

@@ -28,11 +28,14 @@
 // of its own: hamming_match_pairs, pairs_gms (with GMS modes pairs_grid_modes + pairs_mode_select) and pose_sets_stored_pairs are the
 // bodies of the kernels above -- each stated once as a __device__ function -- with the pair's query frame taken from a second table in
 // the kernel arguments, and with a count (the pair's own keypoints) apart from the stride of the rows (the widest query of the list).
+// The frame store that the _stored entries read, and everything that fills it, is frames.hip: a run reaches a stored frame through
+// FrameStore::rows (frame_store.h) and reads its point records (RecordPoints) where a run on host frames reads the 3-D images.
 //
 // Nothing here rounds twice: float division / multiplication, the float -> double widenings, fp64 add / multiply / divide / sqrt are
 // single IEEE operations (-ffp-contract=off), the rest is integer.  tests/np_mirror_match.py restates all of it in numpy and
 // tests/test_match_gpu.py compares byte for byte.
 #include "chip_internal.h"
+#include "frame_store.h"
 #include "ransac_common.h"
 #include <climits>
 #include <cmath>
@@ -40,17 +43,14 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
-#include <unordered_map>
 
 namespace chip {
 
-constexpr int kMatchMax = CHIP_MATCH_MAX_KEYPOINTS;
 constexpr int kBfThreads = 256;
 constexpr int kBfTile = 1024;            // train descriptors per LDS tile: 1024 x 32 B = 32 KiB
 constexpr int kGrid = 20;                // mGridSizeLeft = Size(20, 20) (gms_matcher.h:62); right grid = left x the scale ratio of index 0 = 1.0 (:46, :230-231)
 constexpr int kCells = kGrid * kGrid;    // 400
 constexpr int kOneWg = 1024;             // the GMS and set-building kernels: one workgroup of 16 waves
-constexpr int kMaxImageSide = 16384;
 
 // ------------------------------------------------------------------------------------------------ gms_filter
 struct GmsArgs {
@@ -198,14 +198,7 @@ struct SetsArgs {
     int32_t *counts;              // [kNSets]: n_matches_gms, n_3d2d_ab, n_3d2d_ba, n_3d3d, n_out_of_image
 };
 
-// pixel of a keypoint as the reference indexes the 3-D image: (int)uv(1,k), (int)uv(0,k) (PointFeatureMatching.cpp:121,180) -- truncation
-// of the float keypoint (exact as a double).  (-1, w) truncates into [0, w - 1]; anything else (NaN too) is outside the image.
-__device__ __forceinline__ bool pixel_of(float2 p, int w, int h, int *x, int *y)
-{
-    if (!(p.x > -1.0f && p.x < (float)w && p.y > -1.0f && p.y < (float)h)) return false;
-    *x = (int)p.x; *y = (int)p.y;
-    return true;
-}
+// (pixel_of, the pixel of a keypoint as the reference indexes the 3-D image, is in frame_store.h: frame_gather uses it too)
 // the depth gate of :122 / :182: "z < 0.1 || z > 25." with the float z widened to double
 __device__ __forceinline__ bool depth_ok(float z) { return !((double)z < 0.1 || (double)z > 25.); }
 
@@ -233,7 +226,7 @@ struct ImagePoints {
     __device__ __forceinline__ float a(Ref r, int k) const { return xyz_a[r + k]; }
     __device__ __forceinline__ float b(Ref r, int k) const { return xyz_b[r + k]; }
 };
-// RecordPoints: the frame store's point records, one float4 per keypoint (frame_gather): (x, y, z, 1.0f) copied from the image at put
+// RecordPoints: the frame store's point records, one float4 per keypoint (frame_gather, frames.hip): (x, y, z, 1.0f) copied from the image at put
 // time, or (0, 0, 0, 0.0f) for a keypoint outside it; r = the record.
 struct RecordPoints {
     const float4 *rec_a, *rec_b;
@@ -470,332 +463,6 @@ __global__ __launch_bounds__(kOneWg) void pose_sets_batch(SetsBatchArgs b)
 }
 
 // ------------------------------------------------------------------------------------------------ frames kept on the device
-// frame_gather: a frame's point records at put time, one thread per keypoint; afterwards the staged image is not needed again
-struct GatherArgs {
-    const float2 *kp;             // n, in the frame's slot
-    const float *xyz;             // h x w x 3, staged
-    float4 *rec;                  // n, in the frame's slot
-    int32_t n, w, h;
-};
-constexpr int kGatherThreads = 256;
-__global__ __launch_bounds__(kGatherThreads) void frame_gather(GatherArgs g)
-{
-    const int i = blockIdx.x * kGatherThreads + threadIdx.x;
-    if (i >= g.n) return;
-    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-    int x, y;
-    if (pixel_of(g.kp[i], g.w, g.h, &x, &y)) {
-        const size_t o = 3 * ((size_t)y * g.w + x);
-        r = make_float4(g.xyz[o], g.xyz[o + 1], g.xyz[o + 2], 1.0f);
-    }
-    g.rec[i] = r;
-}
-
-// A pixel's 3-D point from its disparity: StereoGeometry::disparity_to_3DPoints (src/utils/CameraGeometry.cpp:485-523) restated.  The
-// five floats are Q(0,3), (1,3), (2,3), (3,2), (3,3) narrowed on the host (:494-498); d is the disparity as a float, 16 x pixels.
-// pw: every operation in fp64 in the reference's order, an IEEE divide, one narrowing (:511); d / 16 * Q32 is exact, the two additions
-// and the divide round.  x, y, z: fp32 products (:520-522); the file is compiled with -ffp-contract=off, nothing here may fuse.
-struct DispQ { float q03, q13, q23, q32, q33; };
-__device__ __forceinline__ float3 point_of_disparity(float d, int j, int i, const DispQ &q)
-{
-    const float pw = (float)(1.0 / ((((double)d / 16.0) * (double)q.q32 + (double)q.q33) + 1e-6));
-    return make_float3(((float)j + q.q03) * pw, ((float)i + q.q13) * pw, q.q23 * pw);
-}
-
-// disparity_gather: frame_gather for a frame that arrives as its disparity map -- the record of a keypoint is computed from the ONE
-// disparity value at its pixel
-struct GatherDispArgs {
-    const float2 *kp;             // n, in the frame's slot
-    const void *disp;             // h x w, staged: int16 (CHIP_DISP_S16) or float (CHIP_DISP_F32)
-    float4 *rec;                  // n, in the frame's slot
-    int32_t n, w, h, type;
-    DispQ q;
-};
-__global__ __launch_bounds__(kGatherThreads) void disparity_gather(GatherDispArgs g)
-{
-    const int i = blockIdx.x * kGatherThreads + threadIdx.x;
-    if (i >= g.n) return;
-    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-    int x, y;
-    if (pixel_of(g.kp[i], g.w, g.h, &x, &y)) {
-        const size_t o = (size_t)y * g.w + x;
-        const float d = g.type == CHIP_DISP_S16 ? (float)static_cast<const int16_t *>(g.disp)[o] : static_cast<const float *>(g.disp)[o];
-        const float3 p = point_of_disparity(d, x, y, g.q);
-        r = make_float4(p.x, p.y, p.z, 1.0f);
-    }
-    g.rec[i] = r;
-}
-
-// disparity_to_xyz: the dense out3D (:482-524).  A thread takes four consecutive pixels of a row: where the four are inside the row and
-// their first is a multiple of four in the image (the rows of a width that is none start anywhere) with both pointers 16-byte aligned,
-// ONE load of 8 (int16) or 16 (float) bytes and three 16-byte stores for the 48 contiguous bytes; otherwise pixel by pixel.
-struct DenseDispArgs {
-    const void *disp;             // h x w
-    float *xyz;                   // h x w x 3
-    int32_t w, h, type, quads;    // quads: (w + 3) / 4 threads per row
-    DispQ q;
-};
-constexpr int kDenseThreads = 256;
-__global__ __launch_bounds__(kDenseThreads) void disparity_to_xyz(DenseDispArgs a)
-{
-    const size_t t = (size_t)blockIdx.x * kDenseThreads + threadIdx.x;
-    const int i = (int)(t / (size_t)a.quads), j0 = 4 * (int)(t % (size_t)a.quads);
-    if (i >= a.h) return;
-    const size_t p0 = (size_t)i * a.w + j0;
-    const int16_t *s16 = static_cast<const int16_t *>(a.disp);
-    const float *f32 = static_cast<const float *>(a.disp);
-    const bool aligned = (((uintptr_t)a.disp | (uintptr_t)a.xyz) & 15) == 0;
-    if (j0 + 4 <= a.w && (p0 & 3) == 0 && aligned) {
-        float d[4];
-        if (a.type == CHIP_DISP_S16) {
-            const short4 v = *reinterpret_cast<const short4 *>(s16 + p0);
-            d[0] = (float)v.x; d[1] = (float)v.y; d[2] = (float)v.z; d[3] = (float)v.w;
-        } else {
-            const float4 v = *reinterpret_cast<const float4 *>(f32 + p0);
-            d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-        }
-        float3 p[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) p[k] = point_of_disparity(d[k], j0 + k, i, a.q);
-        float4 *o = reinterpret_cast<float4 *>(a.xyz + 3 * p0);
-        o[0] = make_float4(p[0].x, p[0].y, p[0].z, p[1].x);
-        o[1] = make_float4(p[1].y, p[1].z, p[2].x, p[2].y);
-        o[2] = make_float4(p[2].z, p[3].x, p[3].y, p[3].z);
-        return;
-    }
-    for (int j = j0; j < j0 + 4 && j < a.w; j++) {
-        const size_t p = (size_t)i * a.w + j;
-        const float3 v = point_of_disparity(a.type == CHIP_DISP_S16 ? (float)s16[p] : f32[p], j, i, a.q);
-        a.xyz[3 * p] = v.x; a.xyz[3 * p + 1] = v.y; a.xyz[3 * p + 2] = v.z;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ the block matcher
-// The definition is in include/cerebro_hip.h ("a frame from its rectified stereo pair"): this project's own, modelled on cv::StereoBM
-// with PREFILTER_XSOBEL, all in int32.  r = block_size / 2.
-struct BmParams { int32_t nd, r, cap, tex, ratio; };
-constexpr int kBmInvalid = -16;        // (minDisparity - 1) * 16
-constexpr int kBmRowDwords = 6;        // a window row: at most 21 bytes, padded to whole dwords
-constexpr int kBmPad = 16;             // bytes behind the prefiltered pair: a row read in whole dwords ends at most 7 bytes behind its window
-constexpr int kBmThreads = 256;
-constexpr int kBmWaves = kBmThreads / 64;
-
-// bm_prefilter: both images in one launch -- the staged pair is 2 h rows of w bytes, the prefiltered pair the same.  A thread takes four
-// consecutive pixels of a row: the column sums s(x) = I[y-][x] + 2 I[y][x] + I[y+][x] at the six columns around them (v = s(x + 1) -
-// s(x - 1), exact in int32), then ONE 32-bit store where the four are inside the row and their address is a multiple of four (a width
-// that is none shifts every row), byte by byte otherwise.
-struct PrefilterArgs {
-    const uint8_t *img;           // 2 h x w: left, right
-    uint8_t *pre;                 // 2 h x w
-    int32_t w, h, quads, cap;     // quads: (w + 3) / 4 threads per row
-};
-__global__ __launch_bounds__(kBmThreads) void bm_prefilter(PrefilterArgs a)
-{
-    const size_t t = (size_t)blockIdx.x * kBmThreads + threadIdx.x;
-    const size_t row = t / (size_t)a.quads;                          // of the pair
-    const int x0 = 4 * (int)(t % (size_t)a.quads);
-    if (row >= 2 * (size_t)a.h) return;
-    const int y = (int)(row % (size_t)a.h);                          // of its image
-    const uint8_t *I = a.img + (row - (size_t)y) * (size_t)a.w;
-    const int ym = y > 0 ? y - 1 : (a.h > 1 ? 1 : 0), yp = y + 1 < a.h ? y + 1 : (a.h > 1 ? a.h - 2 : 0);   // reflected rows
-    const uint8_t *r0 = I + (size_t)ym * a.w, *r1 = I + (size_t)y * a.w, *r2 = I + (size_t)yp * a.w;
-    int s[6];
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-        const int x = x0 - 1 + k;
-        s[k] = x >= 0 && x < a.w ? (int)r0[x] + 2 * (int)r1[x] + (int)r2[x] : 0;
-    }
-    uint32_t out[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int x = x0 + k;
-        out[k] = x == 0 || x >= a.w - 1 ? (uint32_t)a.cap : (uint32_t)(min(max(s[k + 2] - s[k], -a.cap), a.cap) + a.cap);
-    }
-    const size_t o = row * (size_t)a.w + (size_t)x0;                 // a.pre is aligned: the offset decides
-    if (x0 + 4 <= a.w && (o & 3) == 0) {
-        *reinterpret_cast<uint32_t *>(a.pre + o) = out[0] | out[1] << 8 | out[2] << 16 | out[3] << 24;
-        return;
-    }
-    for (int k = 0; k < 4 && x0 + k < a.w; k++) a.pre[o + k] = (uint8_t)out[k];
-}
-
-__device__ __forceinline__ bool bm_defined(int x, int y, int w, int h, const BmParams &b)
-{
-    return y >= b.r && y <= h - 1 - b.r && x >= b.nd - 1 + b.r && x <= w - 1 - b.r;
-}
-
-// The nw <= 6 dwords of a window row that starts at byte o (any alignment) of the prefiltered pair: nw + 1 aligned dword loads, each
-// dword of the row formed from two neighbours with v_alignbyte_b32.  The last load ends at most 7 bytes behind the row (kBmPad).
-__device__ __forceinline__ void bm_row(const uint32_t *pre, size_t o, int nw, uint32_t row[kBmRowDwords])
-{
-    const uint32_t *a = pre + (o >> 2);
-    const uint32_t sh = (uint32_t)o & 3;
-    uint32_t wd[kBmRowDwords + 1];
-#pragma unroll
-    for (int k = 0; k <= kBmRowDwords; k++) wd[k] = k <= nw ? a[k] : 0u;
-#pragma unroll
-    for (int k = 0; k < kBmRowDwords; k++) row[k] = __builtin_amdgcn_alignbyte(wd[k + 1], wd[k], sh);
-}
-
-// bm_pixel: the disparity of the defined pixel (x, y), by one wave; lane = disparity d, every lane returns the value.  Per window row the
-// left segment is the same for all lanes and lane d's right segment starts one byte below lane d - 1's; both are read in place (the
-// strip of a wave is (2r + 1) x (nd + 2r) bytes, it stays in the cache).  The (2r + 1)-byte row is padded to whole dwords with zero bytes
-// on both sides, so v_sad_u8 sums four absolute differences at a time; T comes from the same left dwords against cap in every byte.
-// The minimum with its tie rule is one wave reduction on SAD << 8 | (63 - d): smallest SAD, then largest d (SAD <= 441 * 126 < 2^16).
-// Lanes >= nd read what lane nd - 1 reads and carry the largest key.
-__device__ __forceinline__ int bm_pixel(const uint8_t *pre8, size_t px, int w, int x, int y, const BmParams &b, int lane)
-{
-    const uint32_t *pre = reinterpret_cast<const uint32_t *>(pre8);
-    const int nb = 2 * b.r + 1, nw = (nb + 3) >> 2;
-    const uint32_t tail = 0xffffffffu >> (8 * (4 * nw - nb));        // nb is odd: one or three bytes of the last dword count
-    const uint32_t capw = (uint32_t)b.cap * 0x01010101u;
-    const int d = min(lane, b.nd - 1);
-    uint32_t sad = 0, T = 0;
-    for (int dy = -b.r; dy <= b.r; dy++) {
-        const size_t ol = (size_t)(y + dy) * (size_t)w + (size_t)(x - b.r);
-        uint32_t L[kBmRowDwords], R[kBmRowDwords];
-        bm_row(pre, ol, nw, L);
-        bm_row(pre, px + ol - (size_t)d, nw, R);
-#pragma unroll
-        for (int k = 0; k < kBmRowDwords; k++) {
-            if (k >= nw) break;
-            const uint32_t mask = k == nw - 1 ? tail : 0xffffffffu;
-            const uint32_t l = L[k] & mask;
-            sad = __builtin_amdgcn_sad_u8(l, R[k] & mask, sad);
-            T = __builtin_amdgcn_sad_u8(l, capw & mask, T);
-        }
-    }
-    uint32_t key = lane < b.nd ? sad << 8 | (uint32_t)(63 - lane) : 0xffffffffu;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) key = min(key, (uint32_t)__shfl_xor((int)key, o));
-    key = __builtin_amdgcn_readfirstlane(key);
-    const int m = (int)(key >> 8), D = 63 - (int)(key & 255u);
-    if ((int)T < b.tex) return kBmInvalid;
-    if (b.ratio > 0) {
-        const int thresh = m + m * b.ratio / 100;                     // m * ratio <= 55 566 * 100
-        if (__ballot(lane < b.nd && abs(lane - D) > 1 && (int)sad <= thresh) != 0) return kBmInvalid;
-    }
-    const int at_p = D == 0 ? 1 : D == b.nd - 1 ? b.nd - 2 : D - 1, at_n = D == 0 ? 1 : D == b.nd - 1 ? b.nd - 2 : D + 1;
-    const int p = (int)__builtin_amdgcn_readlane(sad, at_p), n = (int)__builtin_amdgcn_readlane(sad, at_n);
-    const int q = p + n - 2 * m + abs(p - n);
-    return (D * 256 + (q != 0 ? (p - n) * 256 / q : 0) + 15) >> 4;    // `/` truncates toward zero; the sum is never negative
-}
-
-// bm_keypoints: disparity_gather for a frame that arrives as its rectified pair -- one wave per keypoint computes the disparity at the
-// keypoint's pixel, lane 0 writes the record
-struct BmKeypointArgs {
-    const float2 *kp;             // n, in the frame's slot
-    const uint8_t *pre;           // 2 h x w: the prefiltered pair
-    float4 *rec;                  // n, in the frame's slot
-    int32_t n, w, h;
-    BmParams b;
-    DispQ q;
-};
-__global__ __launch_bounds__(kBmThreads) void bm_keypoints(BmKeypointArgs g)
-{
-    const int i = blockIdx.x * kBmWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (i >= g.n) return;
-    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-    int x, y;
-    if (pixel_of(g.kp[i], g.w, g.h, &x, &y)) {
-        int v = kBmInvalid;
-        if (bm_defined(x, y, g.w, g.h, g.b)) v = bm_pixel(g.pre, (size_t)g.w * g.h, g.w, x, y, g.b, lane);
-        const float3 p = point_of_disparity((float)v, x, y, g.q);
-        r = make_float4(p.x, p.y, p.z, 1.0f);
-    }
-    if (lane == 0) g.rec[i] = r;
-}
-
-// bm_dense: the same body at every pixel, one wave per pixel (the definition made callable: chip_stereo_bm; not a hot path)
-struct BmDenseArgs {
-    const uint8_t *pre;           // 2 h x w
-    int16_t *disp;                // h x w
-    int32_t w, h;
-    BmParams b;
-};
-__global__ __launch_bounds__(kBmThreads) void bm_dense(BmDenseArgs g)
-{
-    const size_t px = (size_t)g.w * g.h;
-    const size_t i = (size_t)blockIdx.x * kBmWaves + (size_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (i >= px) return;
-    const int y = (int)(i / (size_t)g.w), x = (int)(i % (size_t)g.w);
-    int v = kBmInvalid;
-    if (bm_defined(x, y, g.w, g.h, g.b)) v = bm_pixel(g.pre, px, g.w, x, y, g.b, lane);
-    if (lane == 0) g.disp[i] = (int16_t)v;
-}
-
-// ------------------------------------------------------------------------------------------------ rectification
-// The definition is in include/cerebro_hip.h ("a frame from its raw stereo pair"): this project's own, modelled on cv::remap with
-// INTER_LINEAR, float maps and BORDER_CONSTANT 0; all in int32 once the host has quantised the maps to 1/32 pixel.
-constexpr int kRectPix = 4;            // consecutive pixels of a row per thread: one 32-bit store
-constexpr int kRectLanes = 64;         // threads along a row: a workgroup spans kRectLanes * kRectPix = 256 pixels of a row ...
-constexpr int kRectRows = 4;           // ... on four rows
-constexpr int kRectThreads = kRectLanes * kRectRows;
-
-// S(I, qx, qy) of the header: four bytes, each 0 outside the image, weighed in 1/32 and rounded half up
-__device__ __forceinline__ int rect_sample(const uint8_t *I, int w, int h, int qx, int qy)
-{
-    const int x0 = qx >> 5, a = qx & 31, y0 = qy >> 5, b = qy & 31;
-    const bool xi0 = (unsigned)x0 < (unsigned)w, xi1 = (unsigned)(x0 + 1) < (unsigned)w;
-    const bool yi0 = (unsigned)y0 < (unsigned)h, yi1 = (unsigned)(y0 + 1) < (unsigned)h;
-    const uint8_t *r0 = I + ((ptrdiff_t)y0 * w + x0), *r1 = r0 + w;     // dereferenced only where the tap is inside
-    const int p00 = yi0 && xi0 ? (int)r0[0] : 0, p01 = yi0 && xi1 ? (int)r0[1] : 0;
-    const int p10 = yi1 && xi0 ? (int)r1[0] : 0, p11 = yi1 && xi1 ? (int)r1[1] : 0;
-    return (p00 * (32 - a) * (32 - b) + p01 * a * (32 - b) + p10 * (32 - a) * b + p11 * a * b + 512) >> 10;
-}
-
-// rectify_pair: both eyes (grid z) and both stages in one launch.  The quantised maps lie interleaved, (qx, qy) per pixel: eye e has
-// `stages` planes of w h entries at q + e * stages * w h, stage 1 first.  With two stages an output pixel reads its stage-2 entry and
-// makes each of its four taps of the undistorted image U -- never written anywhere -- from that tap's stage-1 entry and four raw bytes,
-// rounded to a byte as the two-pass form rounds it, so the result is the two-pass result bit for bit.  A thread makes kRectPix pixels
-// and stores them as bm_prefilter does: one dword where they are inside the row and the address allows, bytes otherwise.
-struct RectifyArgs {
-    const uint8_t *raw;           // eyes x h x w
-    uint8_t *out;                 // eyes x h x w
-    const int2 *q;                // eyes x stages x h x w
-    int32_t w, h, stages;
-};
-__global__ __launch_bounds__(kRectThreads) void rectify_pair(RectifyArgs g)
-{
-    const int x0 = kRectPix * (int)(blockIdx.x * kRectLanes + (threadIdx.x & (kRectLanes - 1)));
-    const int y = (int)(blockIdx.y * kRectRows + threadIdx.x / kRectLanes);
-    if (x0 >= g.w || y >= g.h) return;
-    const size_t px = (size_t)g.w * g.h, eye = blockIdx.z;
-    const uint8_t *raw = g.raw + eye * px;
-    const int2 *q1 = g.q + eye * (size_t)g.stages * px, *q2 = q1 + px;
-    const size_t row = (size_t)y * g.w;
-    uint32_t out[kRectPix];
-#pragma unroll
-    for (int k = 0; k < kRectPix; k++) {
-        const int x = min(x0 + k, g.w - 1);                               // a tail repeats the row's last pixel and stores nothing of it
-        if (g.stages == 1) {
-            const int2 m = q1[row + x];
-            out[k] = (uint32_t)rect_sample(raw, g.w, g.h, m.x, m.y);
-            continue;
-        }
-        const int2 m = q2[row + x];
-        const int tx = m.x >> 5, a = m.x & 31, ty = m.y >> 5, b = m.y & 31;
-        int u[4];
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            const int ux = tx + (t & 1), uy = ty + (t >> 1);
-            u[t] = 0;
-            if ((unsigned)ux < (unsigned)g.w && (unsigned)uy < (unsigned)g.h) {
-                const int2 m1 = q1[(size_t)uy * g.w + ux];
-                u[t] = rect_sample(raw, g.w, g.h, m1.x, m1.y);
-            }
-        }
-        out[k] = (uint32_t)((u[0] * (32 - a) * (32 - b) + u[1] * a * (32 - b) + u[2] * (32 - a) * b + u[3] * a * b + 512) >> 10);
-    }
-    const size_t o = eye * px + row + (size_t)x0;                         // g.out is aligned: the offset decides
-    if (x0 + kRectPix <= g.w && (o & 3) == 0) {
-        *reinterpret_cast<uint32_t *>(g.out + o) = out[0] | out[1] << 8 | out[2] << 16 | out[3] << 24;
-        return;
-    }
-    for (int k = 0; k < kRectPix && x0 + k < g.w; k++) g.out[o + k] = (uint8_t)out[k];
-}
-
 // pose_sets_batch on stored frames: the candidates' descriptors and keypoints (b.cands) point into the store, b.xyz_a and the candidates'
 // xyz are null, the points are the records.  The argument block of pose_sets_batch is b unchanged.
 struct SetsStoredArgs {
@@ -1065,24 +732,7 @@ struct MatchState {
     DevBuf<uint8_t> mode_plane;                 // [B][S][4][n]
     DevBuf<chip_gms_choice> mode_choice;        // [kMaxBatch]
     PinnedBuf<chip_gms_choice> h_choice;
-    // the frame store (chip_frame_store_reserve): n_slots slots of slot_kp keypoints each, 56 bytes per keypoint; rows never move after the
-    // reserve.  Slot k: desc + 32 * k * slot_kp, kp + k * slot_kp, rec + k * slot_kp.  stage_xyz: the image of the put in flight, or its
-    // disparity, or its rectified pair (bytes; also the input of chip_disparity_to_xyz and chip_stereo_bm, whose dense image / map is
-    // dense_xyz until it is copied out).
-    struct StoredFrame { int64_t id = 0; int32_t n = 0, w = 0, h = 0; bool used = false; };
-    DevBuf<uint8_t> store_desc;
-    DevBuf<float2> store_kp;
-    DevBuf<float4> store_rec;
-    DevBuf<float> stage_xyz, dense_xyz;
-    DevBuf<uint8_t> bm_pre;                     // the prefiltered pair of the stereo put (or of chip_stereo_bm) in flight, kBmPad bytes behind it
-    // rectification: the quantised maps of chip_rectify_set_maps, [eye][stage][h][w] entries (qx, qy), and the one plane of the
-    // chip_remap in flight.  Nothing of this exists before the first of those calls.  A raw pair is staged behind the rectified one.
-    DevBuf<int2> rect_maps, remap_q;
-    std::vector<int2> h_rect;                   // the maps on their way up
-    int32_t rect_w = 0, rect_h = 0, rect_stages = 0;   // rect_stages == 0: no maps
-    int32_t n_slots = 0, slot_kp = 0, n_frames = 0;
-    std::vector<StoredFrame> slots;
-    std::unordered_map<int64_t, int32_t> slot_of;   // id -> slot
+    // (the frames a run on stored frames reads are the FrameStore's, frame_store.h)
     hipEvent_t ev[5] = {};                      // tuning only (CHIP_MATCH_BATCH_TIMING=1): around the three (with GMS modes: four) launches of a run
     // what the last run left: n_cand candidates of a query frame of n1 keypoints, of which ONE is selected -- the pointers and counts
     // chip_match_read_sets and the _matched solvers work on
@@ -1114,7 +764,7 @@ void match_destroy(Ctx *c)
     c->match_state = nullptr;
 }
 
-static int match_state(Ctx *c, MatchState **out)
+int match_state(Ctx *c, MatchState **out)
 {
     if (!c->match_state) {
         c->match_state = new (std::nothrow) MatchState();
@@ -1139,7 +789,7 @@ static int match_state(Ctx *c, MatchState **out)
     return rc;
 }
 
-static hipStream_t match_stream(Ctx *c)
+hipStream_t match_stream(Ctx *c)
 {
     std::lock_guard<std::mutex> lk(c->query_mu);   // chip_set_stream swaps the ctx stream under this lock
     return c->s_query;
@@ -1167,12 +817,16 @@ static int fetch_matches(Ctx *c, hipStream_t s, MatchState *st, const unsigned l
     return CHIP_OK;
 }
 
-static int check_frame(const chip_match_frame *f)
+int check_frame(const uint8_t *desc, const float *kp_xy, int32_t n, int32_t width, int32_t height, const void *image)
 {
-    if (!f || f->n < 0 || f->width <= 0 || f->height <= 0 || !f->xyz) return CHIP_ERR_INVALID_ARG;
-    if (f->n > 0 && (!f->desc || !f->kp_xy)) return CHIP_ERR_INVALID_ARG;
-    if (f->n > kMatchMax || f->width > kMaxImageSide || f->height > kMaxImageSide) return CHIP_ERR_UNSUPPORTED;
+    if (n < 0 || width <= 0 || height <= 0 || !image) return CHIP_ERR_INVALID_ARG;
+    if (n > 0 && (!desc || !kp_xy)) return CHIP_ERR_INVALID_ARG;
+    if (n > kMatchMax || width > kMaxImageSide || height > kMaxImageSide) return CHIP_ERR_UNSUPPORTED;
     return CHIP_OK;
+}
+int check_frame(const chip_match_frame *f)
+{
+    return f ? check_frame(f->desc, f->kp_xy, f->n, f->width, f->height, f->xyz) : CHIP_ERR_INVALID_ARG;
 }
 
 // The buffers of a run for B candidates of a query frame of n1 keypoints; with uploads, the frames as well: tot_n keypoints and tot_px
@@ -1465,29 +1119,26 @@ static int match_run(Ctx *c, MatchState *st, const chip_match_frame *a, const ch
 }
 
 // The pipeline on stored frames: slot sa against the slots sb[0 .. B), nothing uploaded.  Same state afterwards as match_run.
-static int match_run_stored(Ctx *c, MatchState *st, int32_t sa, const int32_t *sb, int B, const double Kinv[9], uint32_t modes)
+static int match_run_stored(Ctx *c, MatchState *st, const FrameStore *fs, int32_t sa, const int32_t *sb, int B, const double Kinv[9], uint32_t modes)
 {
     int rc0 = icp_wait_matched(c);               // as match_run
     if (rc0 != CHIP_OK) return rc0;
-    const MatchState::StoredFrame &a = st->slots[(size_t)sa];
-    const size_t kp = (size_t)st->slot_kp;
+    const FrameStore::Rows a = fs->rows(sa);
     RunFrames f;
     f.stored = true;
     for (int j = 0; j < B; j++) {
-        const MatchState::StoredFrame &b = st->slots[(size_t)sb[j]];
+        const FrameStore::Rows b = fs->rows(sb[j]);
         std::memset(&st->cand_sm[j], 0, sizeof(chip_match_summary));
         choice_none(&st->cand_choice[j], modes);
         if (b.n == 0) continue;
-        const size_t at = (size_t)sb[j] * kp;
         f.max_n2 = b.n > f.max_n2 ? b.n : f.max_n2;
-        f.cands.c[j] = BatchCand{reinterpret_cast<const uint4 *>(st->store_desc + at * CHIP_ORB_DESC_BYTES), st->store_kp + at, nullptr, b.n, b.w, b.h, 0};
-        f.rec[j] = st->store_rec + at;
+        f.cands.c[j] = BatchCand{reinterpret_cast<const uint4 *>(b.desc), b.kp, nullptr, b.n, b.w, b.h, 0};
+        f.rec[j] = b.rec;
     }
     if (a.n > 0) {
         int rc = batch_reserve(c, st, (size_t)B, (size_t)a.n, false, 0, 0, 0);
         if (rc != CHIP_OK) return rc;
-        const size_t at = (size_t)sa * kp;
-        f.desc_a = st->store_desc + at * CHIP_ORB_DESC_BYTES; f.kp_a = st->store_kp + at; f.rec_a = st->store_rec + at;
+        f.desc_a = a.desc; f.kp_a = a.kp; f.rec_a = a.rec;
         f.n1 = a.n; f.w1 = a.w; f.h1 = a.h;
         rc = match_launch(c, st, match_stream(c), f, B, Kinv, modes);
         if (rc != CHIP_OK) return rc;
@@ -1499,26 +1150,25 @@ static int match_run_stored(Ctx *c, MatchState *st, int32_t sa, const int32_t *s
 // The pipeline on a list of stored pairs: slot sa[j] against slot sb[j], every pair with a query frame of its own, in the same three
 // (four) launches.  The rows of keys, planes and slabs have the stride of the widest query frame; a pair with an empty frame on either
 // side takes no part.  Same state afterwards as match_run, with the pair index in the place of the candidate's.
-static int match_run_pairs_stored(Ctx *c, MatchState *st, const int32_t *sa, const int32_t *sb, int P, const double Kinv[9], uint32_t modes)
+static int match_run_pairs_stored(Ctx *c, MatchState *st, const FrameStore *fs, const int32_t *sa, const int32_t *sb, int P, const double Kinv[9],
+                                  uint32_t modes)
 {
     int rc0 = icp_wait_matched(c);               // as match_run
     if (rc0 != CHIP_OK) return rc0;
-    const size_t kp = (size_t)st->slot_kp;
     RunFrames f;
     f.stored = f.pairs = true;
     int32_t n_a[kMaxBatch];
     for (int j = 0; j < P; j++) {
-        const MatchState::StoredFrame &a = st->slots[(size_t)sa[j]], &b = st->slots[(size_t)sb[j]];
+        const FrameStore::Rows a = fs->rows(sa[j]), b = fs->rows(sb[j]);
         std::memset(&st->cand_sm[j], 0, sizeof(chip_match_summary));
         choice_none(&st->cand_choice[j], modes);
         n_a[j] = a.n;
         f.n1 = a.n > f.n1 ? a.n : f.n1;          // the stride counts an empty candidate's query too: its keys are readable (all -1)
         if (a.n == 0 || b.n == 0) continue;
-        const size_t at_a = (size_t)sa[j] * kp, at_b = (size_t)sb[j] * kp;
         f.max_n2 = b.n > f.max_n2 ? b.n : f.max_n2;
-        f.qs.q[j] = PairQuery{reinterpret_cast<const uint4 *>(st->store_desc + at_a * CHIP_ORB_DESC_BYTES), st->store_kp + at_a, st->store_rec + at_a, a.n, a.w, a.h, 0};
-        f.cands.c[j] = BatchCand{reinterpret_cast<const uint4 *>(st->store_desc + at_b * CHIP_ORB_DESC_BYTES), st->store_kp + at_b, nullptr, b.n, b.w, b.h, 0};
-        f.rec[j] = st->store_rec + at_b;
+        f.qs.q[j] = PairQuery{reinterpret_cast<const uint4 *>(a.desc), a.kp, a.rec, a.n, a.w, a.h, 0};
+        f.cands.c[j] = BatchCand{reinterpret_cast<const uint4 *>(b.desc), b.kp, nullptr, b.n, b.w, b.h, 0};
+        f.rec[j] = b.rec;
     }
     if (f.n1 > 0) {
         int rc = batch_reserve(c, st, (size_t)P, (size_t)f.n1, false, 0, 0, 0);
@@ -1861,503 +1511,8 @@ extern "C" int chip_icp_ransac_matched_batch(chip_ctx *c, int32_t P, const int32
     return chip_icp_ransac_matched_batch_collect(c, T_colmajor, confidence, inlier_mask, summary);
 }
 
-// ------------------------------------------------------------------------------------------------ the frame store
-extern "C" int chip_build_has_frame_store(void) { return 1; }
-
-extern "C" int chip_frame_store_reserve(chip_ctx *c, int32_t n_slots, int32_t slot_keypoints)
-{
-    if (!c || n_slots < 1 || slot_keypoints < 1 || slot_keypoints > kMatchMax) return CHIP_ERR_INVALID_ARG;
-    if (c->group) return CHIP_ERR_UNSUPPORTED;
-    std::lock_guard<std::mutex> lk(c->match_mu);
-    CHIP_HIP(c, hipSetDevice(c->device));
-    MatchState *st = nullptr;
-    int rc = match_state(c, &st);
-    if (rc != CHIP_OK) return rc;
-    if (st->n_slots == n_slots && st->slot_kp == slot_keypoints) return CHIP_OK;
-    if (st->n_frames > 0) return CHIP_ERR_BUSY;
-    ResidentPause paused(c);                 // the frees and the three allocations inside one pause
-    CHIP_HIP(c, hipStreamSynchronize(match_stream(c)));
-    st->store_desc.release(); st->store_kp.release(); st->store_rec.release();
-    st->n_slots = st->slot_kp = 0;
-    st->slots.clear();
-    const size_t rows = (size_t)n_slots * (size_t)slot_keypoints;
-    rc = st->store_desc.alloc(c, rows * CHIP_ORB_DESC_BYTES);
-    if (rc == CHIP_OK) rc = st->store_kp.alloc(c, rows);
-    if (rc == CHIP_OK) rc = st->store_rec.alloc(c, rows);
-    if (rc != CHIP_OK) {                     // no store rather than part of one
-        st->store_desc.release(); st->store_kp.release(); st->store_rec.release();
-        return rc;
-    }
-    st->slots.assign((size_t)n_slots, MatchState::StoredFrame());
-    st->n_slots = n_slots; st->slot_kp = slot_keypoints;
-    return CHIP_OK;
-}
-
-extern "C" int chip_frame_store_info(chip_ctx *c, int32_t *n_slots, int32_t *slot_keypoints, int32_t *n_frames)
-{
-    if (!c) return CHIP_ERR_INVALID_ARG;
-    if (c->group) return CHIP_ERR_UNSUPPORTED;
-    std::lock_guard<std::mutex> lk(c->match_mu);
-    const MatchState *st = c->match_state;
-    if (n_slots) *n_slots = st ? st->n_slots : 0;
-    if (slot_keypoints) *slot_keypoints = st ? st->slot_kp : 0;
-    if (n_frames) *n_frames = st ? st->n_frames : 0;
-    return CHIP_OK;
-}
-
-// the prefilter of the pair staged in stage_xyz into bm_pre (reserved by the caller)
-static hipError_t launch_bm_prefilter(MatchState *st, hipStream_t s, int32_t w, int32_t h, const BmParams &b)
-{
-    PrefilterArgs a;
-    a.img = reinterpret_cast<const uint8_t *>(st->stage_xyz.get()); a.pre = st->bm_pre; a.w = w; a.h = h; a.quads = (w + 3) / 4; a.cap = b.cap;
-    const size_t threads = 2 * (size_t)h * (size_t)a.quads;
-    hipLaunchKernelGGL(bm_prefilter, dim3((unsigned)((threads + kBmThreads - 1) / kBmThreads)), dim3(kBmThreads), 0, s, a);
-    return hipGetLastError();
-}
-
-// The body of chip_frame_put, chip_frame_put_disparity and chip_frame_put_stereo: f checked, f->xyz the image (q null), the disparity
-// of disp_type (q its five floats) or the left image of the pair (right and bm given as well); what differs is the bytes staged and the
-// kernels that write the records.
-static int frame_put(chip_ctx *c, int64_t id, const chip_match_frame *f, int32_t disp_type, const DispQ *q, const uint8_t *right = nullptr,
-                     const BmParams *bm = nullptr)
-{
-    int rc = CHIP_OK;
-    if (c->group) return CHIP_ERR_UNSUPPORTED;
-    std::lock_guard<std::mutex> lk(c->match_mu);
-    MatchState *st = c->match_state;
-    if (!st || st->n_slots == 0) return CHIP_ERR_BUSY;
-    if (f->n > st->slot_kp) return CHIP_ERR_UNSUPPORTED;
-    const auto known = st->slot_of.find(id);
-    int32_t k = known != st->slot_of.end() ? known->second : -1;
-    const bool replace = k >= 0;
-    for (int32_t j = 0; k < 0 && j < st->n_slots; j++)
-        if (!st->slots[(size_t)j].used) k = j;
-    if (k < 0) return CHIP_ERR_OOM;
-    CHIP_HIP(c, hipSetDevice(c->device));
-    const size_t px = (size_t)f->width * f->height, at = (size_t)k * (size_t)st->slot_kp;
-    if (f->n > 0) {
-        // the staging buffer holds bytes: the image, or a disparity, which never needs more than the image of the same size
-        // (a pair: two images of px bytes, the int16 map's size)
-        const size_t bytes = !q ? 3 * px * sizeof(float) : bm ? 2 * px : disp_type == CHIP_DISP_S16 ? px * sizeof(int16_t) : px * sizeof(float);
-        rc = st->stage_xyz.reserve(c, (bytes + sizeof(float) - 1) / sizeof(float));   // the last step that can fail before the slot is written
-        if (rc == CHIP_OK && bm) rc = st->bm_pre.reserve(c, 2 * px + kBmPad);          // (a regrow pauses the resident scan by itself)
-        if (rc != CHIP_OK) return rc;
-        hipStream_t s = match_stream(c);
-        const dim3 grid((f->n + kGatherThreads - 1) / kGatherThreads);
-        hipError_t e = hipMemcpyAsync(st->store_desc + at * CHIP_ORB_DESC_BYTES, f->desc, (size_t)f->n * CHIP_ORB_DESC_BYTES, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(st->store_kp + at, f->kp_xy, (size_t)f->n * sizeof(float2), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(st->stage_xyz, f->xyz, bm ? px : bytes, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess && bm) {
-            e = hipMemcpyAsync(reinterpret_cast<uint8_t *>(st->stage_xyz.get()) + px, right, px, hipMemcpyHostToDevice, s);
-            if (e == hipSuccess) e = launch_bm_prefilter(st, s, f->width, f->height, *bm);
-            if (e == hipSuccess) {
-                BmKeypointArgs g;
-                g.kp = st->store_kp + at; g.pre = st->bm_pre; g.rec = st->store_rec + at; g.n = f->n; g.w = f->width; g.h = f->height;
-                g.b = *bm; g.q = *q;
-                hipLaunchKernelGGL(bm_keypoints, dim3((f->n + kBmWaves - 1) / kBmWaves), dim3(kBmThreads), 0, s, g);
-                e = hipGetLastError();
-            }
-        } else if (e == hipSuccess && !q) {
-            GatherArgs g;
-            g.kp = st->store_kp + at; g.xyz = st->stage_xyz; g.rec = st->store_rec + at; g.n = f->n; g.w = f->width; g.h = f->height;
-            hipLaunchKernelGGL(frame_gather, grid, dim3(kGatherThreads), 0, s, g);
-            e = hipGetLastError();
-        } else if (e == hipSuccess) {
-            GatherDispArgs g;
-            g.kp = st->store_kp + at; g.disp = st->stage_xyz; g.rec = st->store_rec + at; g.n = f->n; g.w = f->width; g.h = f->height;
-            g.type = disp_type; g.q = *q;
-            hipLaunchKernelGGL(disparity_gather, grid, dim3(kGatherThreads), 0, s, g);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(s);   // the caller's arrays are free again; a later match is ordered behind the put anyway
-        if (e != hipSuccess) {
-            if (replace) {                   // the slot's rows are undefined now: the id leaves the store
-                st->slots[(size_t)k] = MatchState::StoredFrame();
-                st->slot_of.erase(id);
-                st->n_frames--;
-            }
-            CHIP_HIP(c, e);
-        }
-    }
-    MatchState::StoredFrame &slot = st->slots[(size_t)k];
-    slot.id = id; slot.n = f->n; slot.w = f->width; slot.h = f->height; slot.used = true;
-    if (!replace) {
-        st->slot_of[id] = k;
-        st->n_frames++;
-    }
-    return CHIP_OK;
-}
-
-extern "C" int chip_frame_put(chip_ctx *c, int64_t id, const chip_match_frame *f)
-{
-    if (!c) return CHIP_ERR_INVALID_ARG;
-    const int rc = check_frame(f);
-    if (rc != CHIP_OK) return rc;
-    return frame_put(c, id, f, 0, nullptr);
-}
-
-// ------------------------------------------------------------------------------------------------ frames from their disparity maps
-extern "C" int chip_build_has_disparity(void) { return 1; }
-
-// Q(0,3), (1,3), (2,3), (3,2), (3,3) of the row-major 4 x 4, each narrowed to float as CameraGeometry.cpp:494-498 does
-static DispQ disp_q(const double Q[16])
-{
-    return DispQ{(float)Q[3], (float)Q[7], (float)Q[11], (float)Q[14], (float)Q[15]};
-}
-
-extern "C" int chip_frame_put_disparity(chip_ctx *c, int64_t id, const uint8_t *desc, const float *kp_xy, int32_t n, int32_t width, int32_t height,
-                                        const void *disparity, int32_t disp_type, const double Q_rowmajor[16])
-{
-    if (!c) return CHIP_ERR_INVALID_ARG;
-    const chip_match_frame f{desc, kp_xy, n, width, height, static_cast<const float *>(disparity)};   // the frame rules, on the disparity
-    const int rc = check_frame(&f);
-    if (rc != CHIP_OK) return rc;
-    if ((disp_type != CHIP_DISP_S16 && disp_type != CHIP_DISP_F32) || !Q_rowmajor) return CHIP_ERR_INVALID_ARG;
-    const DispQ q = disp_q(Q_rowmajor);
-    return frame_put(c, id, &f, disp_type, &q);
-}
-
-extern "C" int chip_disparity_to_xyz(chip_ctx *c, const void *disparity, int32_t disp_type, int32_t width, int32_t height,
-                                     const double Q_rowmajor[16], float *xyz)
-{
-    if (!c || !disparity || !Q_rowmajor || !xyz || width <= 0 || height <= 0) return CHIP_ERR_INVALID_ARG;
-    if (disp_type != CHIP_DISP_S16 && disp_type != CHIP_DISP_F32) return CHIP_ERR_INVALID_ARG;
-    if (width > kMaxImageSide || height > kMaxImageSide) return CHIP_ERR_UNSUPPORTED;
-    if (c->group) return CHIP_ERR_UNSUPPORTED;
-    std::lock_guard<std::mutex> lk(c->match_mu);
-    CHIP_HIP(c, hipSetDevice(c->device));
-    MatchState *st = nullptr;
-    int rc = match_state(c, &st);
-    if (rc != CHIP_OK) return rc;
-    const size_t px = (size_t)width * height;
-    const size_t bytes = disp_type == CHIP_DISP_S16 ? px * sizeof(int16_t) : px * sizeof(float);
-    rc = st->stage_xyz.reserve(c, (bytes + sizeof(float) - 1) / sizeof(float));
-    if (rc == CHIP_OK) rc = st->dense_xyz.reserve(c, 3 * px);
-    if (rc != CHIP_OK) return rc;
-    hipStream_t s = match_stream(c);
-    DenseDispArgs a;
-    a.disp = st->stage_xyz; a.xyz = st->dense_xyz; a.w = width; a.h = height; a.type = disp_type; a.quads = (width + 3) / 4;
-    a.q = disp_q(Q_rowmajor);
-    const size_t threads = (size_t)height * (size_t)a.quads;
-    CHIP_HIP(c, hipMemcpyAsync(st->stage_xyz, disparity, bytes, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(disparity_to_xyz, dim3((unsigned)((threads + kDenseThreads - 1) / kDenseThreads)), dim3(kDenseThreads), 0, s, a);
-    CHIP_HIP(c, hipGetLastError());
-    CHIP_HIP(c, hipMemcpyAsync(xyz, st->dense_xyz, 3 * px * sizeof(float), hipMemcpyDeviceToHost, s));
-    CHIP_HIP(c, hipStreamSynchronize(s));
-    return CHIP_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ frames from their rectified pairs
-extern "C" int chip_build_has_stereo_bm(void) { return 1; }
-
-extern "C" void chip_stereo_bm_params_default(chip_stereo_bm_params *p)
-{
-    if (p) *p = chip_stereo_bm_params{64, 21, 31, 10, 15};           // cv::StereoBM::create(64, 21)
-}
-
-// the parameter table of the header; p null: the defaults
-static int bm_params(const chip_stereo_bm_params *p, BmParams *b)
-{
-    chip_stereo_bm_params d;
-    chip_stereo_bm_params_default(&d);
-    if (p) d = *p;
-    if (d.num_disparities != 16 && d.num_disparities != 32 && d.num_disparities != 48 && d.num_disparities != 64) return CHIP_ERR_UNSUPPORTED;
-    if (d.block_size < 5 || d.block_size > 4 * kBmRowDwords - 3 || d.block_size % 2 == 0) return CHIP_ERR_UNSUPPORTED;
-    if (d.prefilter_cap < 1 || d.prefilter_cap > 63 || d.texture_threshold < 0) return CHIP_ERR_UNSUPPORTED;
-    if (d.uniqueness_ratio < 0 || d.uniqueness_ratio > 100) return CHIP_ERR_UNSUPPORTED;
-    *b = BmParams{d.num_disparities, d.block_size / 2, d.prefilter_cap, d.texture_threshold, d.uniqueness_ratio};
-    return CHIP_OK;
-}
-
-extern "C" int chip_frame_put_stereo(chip_ctx *c, int64_t id, const uint8_t *desc, const float *kp_xy, int32_t n, int32_t width, int32_t height,
-                                     const uint8_t *left, const uint8_t *right, const chip_stereo_bm_params *p, const double Q_rowmajor[16])
-{
-    if (!c) return CHIP_ERR_INVALID_ARG;
-    const chip_match_frame f{desc, kp_xy, n, width, height, reinterpret_cast<const float *>(left)};   // the frame rules, on the left image
-    int rc = check_frame(&f);
-    if (rc != CHIP_OK) return rc;
-    if (!right || !Q_rowmajor) return CHIP_ERR_INVALID_ARG;
-    BmParams b;
-    rc = bm_params(p, &b);
-    if (rc != CHIP_OK) return rc;
-    const DispQ q = disp_q(Q_rowmajor);
-    return frame_put(c, id, &f, CHIP_DISP_S16, &q, right, &b);
-}
-
-// A frame from its rectified pair and nothing else: the detector and the descriptor (orb.hip) run on the left image where the pair is
-// staged, orb_describe writes the slot's descriptor and keypoint rows, and the block matcher makes the records as in frame_put.  What
-// comes back is the eight kept counts.  raw: the pair is the cameras' own (chip_frame_put_raw_orb_stereo) -- it is staged behind the
-// place of the rectified pair, rectify_pair writes that pair through the ctx's maps, and the rest is the same.
-static hipError_t launch_rectify(hipStream_t s, const uint8_t *raw, uint8_t *out, const int2 *q, int32_t w, int32_t h, int32_t stages, int32_t eyes)
-{
-    RectifyArgs a;
-    a.raw = raw; a.out = out; a.q = q; a.w = w; a.h = h; a.stages = stages;
-    const dim3 grid((unsigned)((w + kRectLanes * kRectPix - 1) / (kRectLanes * kRectPix)), (unsigned)((h + kRectRows - 1) / kRectRows), (unsigned)eyes);
-    hipLaunchKernelGGL(rectify_pair, grid, dim3(kRectThreads), 0, s, a);
-    return hipGetLastError();
-}
-
-static int put_orb_stereo(chip_ctx *c, int64_t id, int32_t width, int32_t height, const uint8_t *left, const uint8_t *right,
-                          const chip_orb_params *orb, const chip_stereo_bm_params *bm, const double Q_rowmajor[16], int32_t *n, bool raw)
-{
-    if (!c || !left || !right || !Q_rowmajor || !n) return CHIP_ERR_INVALID_ARG;
-    chip_orb_params d;
-    int rc = orb_check(width, height, orb, &d);
-    if (rc != CHIP_OK) return rc;
-    BmParams b;
-    rc = bm_params(bm, &b);
-    if (rc != CHIP_OK) return rc;
-    const DispQ q = disp_q(Q_rowmajor);
-    if (c->group) return CHIP_ERR_UNSUPPORTED;
-    std::lock_guard<std::mutex> lk(c->match_mu);
-    MatchState *st = c->match_state;
-    if (!st || st->n_slots == 0) return CHIP_ERR_BUSY;
-    if (raw && st->rect_stages == 0) return CHIP_ERR_BUSY;         // no maps
-    if (raw && (width != st->rect_w || height != st->rect_h)) return CHIP_ERR_INVALID_ARG;
-    if (d.n_features > st->slot_kp) return CHIP_ERR_UNSUPPORTED;   // the slot must hold whatever the detector keeps
-    const auto known = st->slot_of.find(id);
-    int32_t k = known != st->slot_of.end() ? known->second : -1;
-    const bool replace = k >= 0;
-    for (int32_t j = 0; k < 0 && j < st->n_slots; j++)
-        if (!st->slots[(size_t)j].used) k = j;
-    if (k < 0) return CHIP_ERR_OOM;
-    CHIP_HIP(c, hipSetDevice(c->device));
-    const size_t px = (size_t)width * height, at = (size_t)k * (size_t)st->slot_kp;
-    rc = st->stage_xyz.reserve(c, ((raw ? 4 : 2) * px + sizeof(float) - 1) / sizeof(float));
-    if (rc == CHIP_OK) rc = st->bm_pre.reserve(c, 2 * px + kBmPad);
-    if (rc != CHIP_OK) return rc;
-    hipStream_t s = match_stream(c);
-    uint8_t *stage = reinterpret_cast<uint8_t *>(st->stage_xyz.get());
-    uint8_t *in = raw ? stage + 2 * px : stage;                    // where the caller's pair goes
-    int32_t total = 0;
-    const auto run = [&]() -> int {
-        CHIP_HIP(c, hipMemcpyAsync(in, left, px, hipMemcpyHostToDevice, s));
-        CHIP_HIP(c, hipMemcpyAsync(in + px, right, px, hipMemcpyHostToDevice, s));
-        if (raw) CHIP_HIP(c, launch_rectify(s, in, stage, st->rect_maps, width, height, st->rect_stages, 2));
-        const int e = orb_enqueue(c, s, nullptr, stage, width, height, d, true, st->store_desc + at * CHIP_ORB_DESC_BYTES, st->store_kp + at,
-                                  8 * sizeof(int32_t));
-        if (e != CHIP_OK) return e;
-        CHIP_HIP(c, launch_bm_prefilter(st, s, width, height, b));   // runs while the counts travel
-        CHIP_HIP(c, hipStreamSynchronize(s));
-        const int f = orb_finished(c, true, d.n_features, &total, nullptr);
-        if (f != CHIP_OK || total == 0) return f;
-        BmKeypointArgs g;
-        g.kp = st->store_kp + at; g.pre = st->bm_pre; g.rec = st->store_rec + at; g.n = total; g.w = width; g.h = height;
-        g.b = b; g.q = q;
-        hipLaunchKernelGGL(bm_keypoints, dim3((total + kBmWaves - 1) / kBmWaves), dim3(kBmThreads), 0, s, g);
-        CHIP_HIP(c, hipGetLastError());
-        CHIP_HIP(c, hipStreamSynchronize(s));
-        return CHIP_OK;
-    };
-    rc = run();
-    if (rc != CHIP_OK) {
-        // CHIP_ERR_OOM: a buffer of the detector could not grow, which is decided before its first launch -- the slot is as it was.
-        // Anything else: the slot's rows are undefined now, and the id leaves the store
-        if (replace && rc != CHIP_ERR_OOM) {
-            st->slots[(size_t)k] = MatchState::StoredFrame();
-            st->slot_of.erase(id);
-            st->n_frames--;
-        }
-        return rc;
-    }
-    MatchState::StoredFrame &slot = st->slots[(size_t)k];
-    slot.id = id; slot.n = total; slot.w = width; slot.h = height; slot.used = true;
-    if (!replace) {
-        st->slot_of[id] = k;
-        st->n_frames++;
-    }
-    *n = total;
-    return CHIP_OK;
-}
-
-extern "C" int chip_frame_put_orb_stereo(chip_ctx *c, int64_t id, int32_t width, int32_t height, const uint8_t *left, const uint8_t *right,
-                                         const chip_orb_params *orb, const chip_stereo_bm_params *bm, const double Q_rowmajor[16], int32_t *n)
-{
-    return put_orb_stereo(c, id, width, height, left, right, orb, bm, Q_rowmajor, n, false);
-}
-
-// ------------------------------------------------------------------------------------------------ frames from their raw pairs
-extern "C" int chip_build_has_rectify(void) { return 1; }
-
-// Q of the header: a map value in 1/32 pixel.  The product is exact in float; rintf rounds to nearest, ties to even (the default mode)
-static inline int32_t rect_quantize(float m)
-{
-    if (m != m) return -64;
-    return (int32_t)rintf(32.0f * fminf(fmaxf(m, -2.0f), 32768.0f));
-}
-
-extern "C" int chip_rectify_quantize(const float *map, int64_t count, int32_t *q)
-{
-    if (!map || !q || count < 0) return CHIP_ERR_INVALID_ARG;
-    for (int64_t i = 0; i < count; i++) q[i] = rect_quantize(map[i]);
-    return CHIP_OK;
-}
-
-static void rect_quantize_plane(const float *mx, const float *my, size_t px, int2 *q)
-{
-    for (size_t i = 0; i < px; i++) q[i] = make_int2(rect_quantize(mx[i]), rect_quantize(my[i]));
-}
-
-extern "C" int chip_remap(chip_ctx *c, const uint8_t *image, int32_t width, int32_t height, const float *map_x, const float *map_y, uint8_t *out)
-{
-    if (!c || !image || !map_x || !map_y || !out || width < 1 || height < 1) return CHIP_ERR_INVALID_ARG;
-    if (width > kMaxImageSide || height > kMaxImageSide) return CHIP_ERR_UNSUPPORTED;
-    if (c->group) return CHIP_ERR_UNSUPPORTED;
-    std::lock_guard<std::mutex> lk(c->match_mu);
-    CHIP_HIP(c, hipSetDevice(c->device));
-    MatchState *st = nullptr;
-    int rc = match_state(c, &st);
-    if (rc != CHIP_OK) return rc;
-    const size_t px = (size_t)width * height;
-    rc = st->stage_xyz.reserve(c, (2 * px + sizeof(float) - 1) / sizeof(float));   // the result, the image behind it
-    if (rc == CHIP_OK) rc = st->remap_q.reserve(c, px);
-    if (rc != CHIP_OK) return rc;
-    try { st->h_rect.resize(px); } catch (const std::bad_alloc &) { return CHIP_ERR_OOM; }
-    rect_quantize_plane(map_x, map_y, px, st->h_rect.data());
-    hipStream_t s = match_stream(c);
-    uint8_t *stage = reinterpret_cast<uint8_t *>(st->stage_xyz.get());
-    CHIP_HIP(c, hipMemcpyAsync(st->remap_q, st->h_rect.data(), px * sizeof(int2), hipMemcpyHostToDevice, s));
-    CHIP_HIP(c, hipMemcpyAsync(stage + px, image, px, hipMemcpyHostToDevice, s));
-    CHIP_HIP(c, launch_rectify(s, stage + px, stage, st->remap_q, width, height, 1, 1));
-    CHIP_HIP(c, hipMemcpyAsync(out, stage, px, hipMemcpyDeviceToHost, s));
-    CHIP_HIP(c, hipStreamSynchronize(s));
-    return CHIP_OK;
-}
-
-extern "C" int chip_rectify_set_maps(chip_ctx *c, int32_t width, int32_t height, const float *lx1, const float *ly1, const float *lx2,
-                                     const float *ly2, const float *rx1, const float *ry1, const float *rx2, const float *ry2)
-{
-    if (!c || !lx1 || !ly1 || !rx1 || !ry1 || width < 1 || height < 1) return CHIP_ERR_INVALID_ARG;
-    const int n2 = (lx2 != nullptr) + (ly2 != nullptr) + (rx2 != nullptr) + (ry2 != nullptr);
-    if (n2 != 0 && n2 != 4) return CHIP_ERR_INVALID_ARG;
-    if (width > CHIP_ORB_MAX_SIDE || height > CHIP_ORB_MAX_SIDE) return CHIP_ERR_UNSUPPORTED;
-    if (c->group) return CHIP_ERR_UNSUPPORTED;
-    std::lock_guard<std::mutex> lk(c->match_mu);
-    CHIP_HIP(c, hipSetDevice(c->device));
-    MatchState *st = nullptr;
-    int rc = match_state(c, &st);
-    if (rc != CHIP_OK) return rc;
-    const int32_t stages = n2 ? 2 : 1;
-    const size_t px = (size_t)width * height, entries = 2 * (size_t)stages * px;
-    try { st->h_rect.resize(entries); } catch (const std::bad_alloc &) { return CHIP_ERR_OOM; }
-    st->rect_stages = 0;                     // from here on the old maps are gone, whatever happens
-    rc = st->rect_maps.reserve(c, entries);  // (a regrow pauses the resident scan by itself)
-    if (rc != CHIP_OK) return rc;
-    int2 *q = st->h_rect.data();
-    rect_quantize_plane(lx1, ly1, px, q);
-    if (n2) rect_quantize_plane(lx2, ly2, px, q + px);
-    rect_quantize_plane(rx1, ry1, px, q + (size_t)stages * px);
-    if (n2) rect_quantize_plane(rx2, ry2, px, q + (size_t)stages * px + px);
-    hipStream_t s = match_stream(c);
-    CHIP_HIP(c, hipMemcpyAsync(st->rect_maps, q, entries * sizeof(int2), hipMemcpyHostToDevice, s));
-    CHIP_HIP(c, hipStreamSynchronize(s));
-    st->rect_w = width; st->rect_h = height; st->rect_stages = stages;
-    return CHIP_OK;
-}
-
-extern "C" int chip_rectify_pair(chip_ctx *c, const uint8_t *left_raw, const uint8_t *right_raw, int32_t width, int32_t height,
-                                 uint8_t *left_out, uint8_t *right_out)
-{
-    if (!c || !left_raw || !right_raw || !left_out || !right_out || width < 1 || height < 1) return CHIP_ERR_INVALID_ARG;
-    if (c->group) return CHIP_ERR_UNSUPPORTED;
-    std::lock_guard<std::mutex> lk(c->match_mu);
-    MatchState *st = c->match_state;
-    if (!st || st->rect_stages == 0) return CHIP_ERR_BUSY;
-    if (width != st->rect_w || height != st->rect_h) return CHIP_ERR_INVALID_ARG;
-    CHIP_HIP(c, hipSetDevice(c->device));
-    const size_t px = (size_t)width * height;
-    const int rc = st->stage_xyz.reserve(c, (4 * px + sizeof(float) - 1) / sizeof(float));   // the rectified pair, the raw one behind it
-    if (rc != CHIP_OK) return rc;
-    hipStream_t s = match_stream(c);
-    uint8_t *stage = reinterpret_cast<uint8_t *>(st->stage_xyz.get());
-    CHIP_HIP(c, hipMemcpyAsync(stage + 2 * px, left_raw, px, hipMemcpyHostToDevice, s));
-    CHIP_HIP(c, hipMemcpyAsync(stage + 3 * px, right_raw, px, hipMemcpyHostToDevice, s));
-    CHIP_HIP(c, launch_rectify(s, stage + 2 * px, stage, st->rect_maps, width, height, st->rect_stages, 2));
-    CHIP_HIP(c, hipMemcpyAsync(left_out, stage, px, hipMemcpyDeviceToHost, s));
-    CHIP_HIP(c, hipMemcpyAsync(right_out, stage + px, px, hipMemcpyDeviceToHost, s));
-    CHIP_HIP(c, hipStreamSynchronize(s));
-    return CHIP_OK;
-}
-
-extern "C" int chip_frame_put_raw_orb_stereo(chip_ctx *c, int64_t id, int32_t width, int32_t height, const uint8_t *left_raw,
-                                             const uint8_t *right_raw, const chip_orb_params *orb, const chip_stereo_bm_params *bm,
-                                             const double Q_rowmajor[16], int32_t *n)
-{
-    return put_orb_stereo(c, id, width, height, left_raw, right_raw, orb, bm, Q_rowmajor, n, true);
-}
-
-extern "C" int chip_stereo_bm(chip_ctx *c, const uint8_t *left, const uint8_t *right, int32_t width, int32_t height,
-                              const chip_stereo_bm_params *p, int16_t *disparity)
-{
-    if (!c || !left || !right || !disparity || width <= 0 || height <= 0) return CHIP_ERR_INVALID_ARG;
-    if (width > kMaxImageSide || height > kMaxImageSide) return CHIP_ERR_UNSUPPORTED;
-    BmParams b;
-    int rc = bm_params(p, &b);
-    if (rc != CHIP_OK) return rc;
-    if (c->group) return CHIP_ERR_UNSUPPORTED;
-    std::lock_guard<std::mutex> lk(c->match_mu);
-    CHIP_HIP(c, hipSetDevice(c->device));
-    MatchState *st = nullptr;
-    rc = match_state(c, &st);
-    if (rc != CHIP_OK) return rc;
-    const size_t px = (size_t)width * height;
-    rc = st->stage_xyz.reserve(c, (2 * px + sizeof(float) - 1) / sizeof(float));
-    if (rc == CHIP_OK) rc = st->bm_pre.reserve(c, 2 * px + kBmPad);
-    if (rc == CHIP_OK) rc = st->dense_xyz.reserve(c, (px * sizeof(int16_t) + sizeof(float) - 1) / sizeof(float));   // the map, as bytes
-    if (rc != CHIP_OK) return rc;
-    hipStream_t s = match_stream(c);
-    uint8_t *stage = reinterpret_cast<uint8_t *>(st->stage_xyz.get());
-    BmDenseArgs a;
-    a.pre = st->bm_pre; a.disp = reinterpret_cast<int16_t *>(st->dense_xyz.get()); a.w = width; a.h = height; a.b = b;
-    CHIP_HIP(c, hipMemcpyAsync(stage, left, px, hipMemcpyHostToDevice, s));
-    CHIP_HIP(c, hipMemcpyAsync(stage + px, right, px, hipMemcpyHostToDevice, s));
-    CHIP_HIP(c, launch_bm_prefilter(st, s, width, height, b));
-    hipLaunchKernelGGL(bm_dense, dim3((unsigned)((px + kBmWaves - 1) / kBmWaves)), dim3(kBmThreads), 0, s, a);
-    CHIP_HIP(c, hipGetLastError());
-    CHIP_HIP(c, hipMemcpyAsync(disparity, a.disp, px * sizeof(int16_t), hipMemcpyDeviceToHost, s));
-    CHIP_HIP(c, hipStreamSynchronize(s));
-    return CHIP_OK;
-}
-
-extern "C" int chip_frame_drop(chip_ctx *c, int64_t id)
-{
-    if (!c) return CHIP_ERR_INVALID_ARG;
-    if (c->group) return CHIP_ERR_UNSUPPORTED;
-    std::lock_guard<std::mutex> lk(c->match_mu);
-    MatchState *st = c->match_state;
-    if (!st) return CHIP_ERR_RANGE;
-    const auto known = st->slot_of.find(id);
-    if (known == st->slot_of.end()) return CHIP_ERR_RANGE;
-    st->slots[(size_t)known->second] = MatchState::StoredFrame();
-    st->slot_of.erase(known);
-    st->n_frames--;
-    return CHIP_OK;
-}
-
-extern "C" int chip_frame_read(chip_ctx *c, int64_t id, int32_t *n, int32_t *width, int32_t *height, uint8_t *desc, float *kp_xy, float *pts)
-{
-    if (!c) return CHIP_ERR_INVALID_ARG;
-    if (c->group) return CHIP_ERR_UNSUPPORTED;
-    std::lock_guard<std::mutex> lk(c->match_mu);
-    MatchState *st = c->match_state;
-    if (!st || st->n_slots == 0) return CHIP_ERR_BUSY;
-    const auto known = st->slot_of.find(id);
-    if (known == st->slot_of.end()) return CHIP_ERR_RANGE;
-    const MatchState::StoredFrame &slot = st->slots[(size_t)known->second];
-    if (n) *n = slot.n;
-    if (width) *width = slot.w;
-    if (height) *height = slot.h;
-    if (slot.n == 0 || (!desc && !kp_xy && !pts)) return CHIP_OK;
-    CHIP_HIP(c, hipSetDevice(c->device));
-    hipStream_t s = match_stream(c);
-    const size_t at = (size_t)known->second * (size_t)st->slot_kp, m = (size_t)slot.n;
-    if (desc) CHIP_HIP(c, hipMemcpyAsync(desc, st->store_desc + at * CHIP_ORB_DESC_BYTES, m * CHIP_ORB_DESC_BYTES, hipMemcpyDeviceToHost, s));
-    if (kp_xy) CHIP_HIP(c, hipMemcpyAsync(kp_xy, st->store_kp + at, m * sizeof(float2), hipMemcpyDeviceToHost, s));
-    if (pts) CHIP_HIP(c, hipMemcpyAsync(pts, st->store_rec + at, m * sizeof(float4), hipMemcpyDeviceToHost, s));
-    CHIP_HIP(c, hipStreamSynchronize(s));
-    return CHIP_OK;
-}
-
+// ------------------------------------------------------------------------------------------------ one stored frame against B stored candidates
+// (the store itself -- reserve, the puts, drop, read -- is frames.hip; chip_frame_store_reserve creates the match state with it)
 static int match_batch_stored_call(chip_ctx *c, int64_t a_id, const int64_t *b_ids, int32_t B, const double Kinv[9], uint32_t modes,
                                    chip_match_summary *summary, chip_gms_choice *choice)
 {
@@ -2365,20 +1520,21 @@ static int match_batch_stored_call(chip_ctx *c, int64_t a_id, const int64_t *b_i
     if (c->group) return CHIP_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> lk(c->match_mu);
     MatchState *st = c->match_state;
+    const FrameStore *fs = c->frame_store;
     if (st) st->have_sets = false;           // a failed call, refused arguments included, leaves nothing selected
     if (!b_ids || !Kinv || !summary || B < 1 || (modes & ~(uint32_t)(CHIP_GMS_WITH_SCALE | CHIP_GMS_WITH_ROTATION))) return CHIP_ERR_INVALID_ARG;
     if (B > kMaxBatch) return CHIP_ERR_UNSUPPORTED;
-    if (!st || st->n_slots == 0) return CHIP_ERR_BUSY;
+    if (!st || !fs || fs->n_slots == 0) return CHIP_ERR_BUSY;
     int32_t sb[kMaxBatch];
-    const auto fa = st->slot_of.find(a_id);
-    if (fa == st->slot_of.end()) return CHIP_ERR_RANGE;
+    const auto fa = fs->slot_of.find(a_id);
+    if (fa == fs->slot_of.end()) return CHIP_ERR_RANGE;
     for (int j = 0; j < B; j++) {
-        const auto fb = st->slot_of.find(b_ids[j]);
-        if (fb == st->slot_of.end()) return CHIP_ERR_RANGE;
+        const auto fb = fs->slot_of.find(b_ids[j]);
+        if (fb == fs->slot_of.end()) return CHIP_ERR_RANGE;
         sb[j] = fb->second;
     }
     CHIP_HIP(c, hipSetDevice(c->device));
-    const int rc = match_run_stored(c, st, fa->second, sb, B, Kinv, modes);
+    const int rc = match_run_stored(c, st, fs, fa->second, sb, B, Kinv, modes);
     if (rc != CHIP_OK) return rc;
     st->keys_readable = true;
     for (int j = 0; j < B; j++) summary[j] = st->cand_sm[j];
@@ -2407,18 +1563,19 @@ extern "C" int chip_match_pairs_stored(chip_ctx *c, const int64_t *a_ids, const 
     if (c->group) return CHIP_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> lk(c->match_mu);
     MatchState *st = c->match_state;
+    const FrameStore *fs = c->frame_store;
     if (st) st->have_sets = false;           // a failed call, refused arguments included, leaves nothing selected
     if (!a_ids || !b_ids || !Kinv || !summary || P < 1 || (modes & ~(uint32_t)(CHIP_GMS_WITH_SCALE | CHIP_GMS_WITH_ROTATION))) return CHIP_ERR_INVALID_ARG;
     if (P > CHIP_MATCH_MAX_PAIRS) return CHIP_ERR_UNSUPPORTED;
-    if (!st || st->n_slots == 0) return CHIP_ERR_BUSY;
+    if (!st || !fs || fs->n_slots == 0) return CHIP_ERR_BUSY;
     int32_t sa[kMaxBatch], sb[kMaxBatch];
     for (int j = 0; j < P; j++) {
-        const auto fa = st->slot_of.find(a_ids[j]), fb = st->slot_of.find(b_ids[j]);
-        if (fa == st->slot_of.end() || fb == st->slot_of.end()) return CHIP_ERR_RANGE;
+        const auto fa = fs->slot_of.find(a_ids[j]), fb = fs->slot_of.find(b_ids[j]);
+        if (fa == fs->slot_of.end() || fb == fs->slot_of.end()) return CHIP_ERR_RANGE;
         sa[j] = fa->second; sb[j] = fb->second;
     }
     CHIP_HIP(c, hipSetDevice(c->device));
-    const int rc = match_run_pairs_stored(c, st, sa, sb, P, Kinv, modes);
+    const int rc = match_run_pairs_stored(c, st, fs, sa, sb, P, Kinv, modes);
     if (rc != CHIP_OK) return rc;
     st->keys_readable = true;
     for (int j = 0; j < P; j++) summary[j] = st->cand_sm[j];

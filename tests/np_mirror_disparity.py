@@ -1,4 +1,4 @@
-"""CPU restatement in numpy scalar types of the disparity -> 3-D step (cerebro_amd/csrc/match.hip: point_of_disparity, used by
+"""CPU restatement in numpy scalar types of the disparity -> 3-D step (cerebro_amd/csrc/frames.hip: point_of_disparity, used by
 disparity_gather and disparity_to_xyz; definitions in include/cerebro_hip.h, "a frame from its disparity map"), i.e. of
 StereoGeometry::disparity_to_3DPoints, src/utils/CameraGeometry.cpp:485-523 of the reference:
 

@@ -1,5 +1,5 @@
-"""CPU restatement in numpy of what the frame store adds to the match stage (cerebro_amd/csrc/match.hip: frame_gather,
-pose_sets_stored_batch; definitions in include/cerebro_hip.h, "frames kept on the device"): the point record of a keypoint, and the
+"""CPU restatement in numpy of what the frame store adds to the match stage (frame_gather in cerebro_amd/csrc/frames.hip,
+pose_sets_stored_batch in match.hip; definitions in include/cerebro_hip.h, "frames kept on the device"): the point record of a keypoint, and the
 five correspondence sets built FROM RECORDS instead of from the 3-D images.  Everything else is np_mirror_match's."""
 from __future__ import annotations
 

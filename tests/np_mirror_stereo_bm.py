@@ -1,4 +1,4 @@
-"""CPU restatement in numpy integers of the block matcher (cerebro_amd/csrc/match.hip: bm_prefilter, bm_pixel behind bm_keypoints and
+"""CPU restatement in numpy integers of the block matcher (cerebro_amd/csrc/frames.hip: bm_prefilter, bm_pixel behind bm_keypoints and
 bm_dense; definition in include/cerebro_hip.h, "a frame from its rectified stereo pair").  The definition is this project's own,
 modelled on cv::StereoBM with PREFILTER_XSOBEL; it is NOT pinned against OpenCV.  All arithmetic is int32:
 

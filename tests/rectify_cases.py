@@ -7,7 +7,7 @@ import numpy as np
 
 import np_mirror_rectify as R
 
-# cerebro_amd/csrc/match.hip: kRectPix pixels of a row per thread, kRectLanes * kRectPix pixels of a row and kRectRows rows per workgroup
+# cerebro_amd/csrc/frames.hip: kRectPix pixels of a row per thread, kRectLanes * kRectPix pixels of a row and kRectRows rows per workgroup
 PIXELS_PER_THREAD = 4
 WG_ROW_SPAN = 256
 WG_ROWS = 4

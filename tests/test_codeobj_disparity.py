@@ -1,4 +1,4 @@
-"""Build-time look at the two kernels of the disparity -> 3-D step (cerebro_amd/csrc/match.hip: disparity_gather, disparity_to_xyz)
+"""Build-time look at the two kernels of the disparity -> 3-D step (cerebro_amd/csrc/frames.hip: disparity_gather, disparity_to_xyz)
 in the gfx950 code object of the built libcerebro_hip.so (no GPU needed): both exist once, neither spills nor uses a flat_ memory
 instruction, the record of a keypoint leaves in ONE 16-byte store, the dense kernel loads four pixels at once and stores 16 bytes at
 a time, the fp64 sum is two additions (no fused multiply-add outside the divide's own sequence) -- and frame_gather next to them has

@@ -1,4 +1,4 @@
-"""Build-time look at the frame store's two kernels (cerebro_amd/csrc/match.hip: frame_gather, pose_sets_stored_batch) in the gfx950
+"""Build-time look at the frame store's two kernels (frame_gather in cerebro_amd/csrc/frames.hip, pose_sets_stored_batch in match.hip) in the gfx950
 code object of the built libcerebro_hip.so (no GPU needed): both exist, neither spills nor uses a flat_ memory instruction (every
 pointer comes out of the kernel arguments as a global pointer), the gather loads a keypoint's 8 bytes and the 12 bytes of its pixel and makes ONE 16-byte store per
 keypoint, and the stored set kernel reads its points as 16-byte records."""

@@ -1,6 +1,6 @@
 """Build-time look at the five kernels of the ORB detector (cerebro_amd/csrc/orb.hip) in the gfx950 code object of the built
 libcerebro_hip.so (no GPU needed): each exists once, none spills or uses a flat_ memory instruction, a record leaves orb_moments in
-one pair of 16-byte stores, the score plane is written in 16-byte stores -- and the kernels of match.hip whose registers the other
+one pair of 16-byte stores, the score plane is written in 16-byte stores -- and the kernels of frames.hip whose registers the other
 code-object tests record have them still (they are in another translation unit and must not move)."""
 import pytest
 

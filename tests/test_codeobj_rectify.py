@@ -1,4 +1,4 @@
-"""Build-time look at the kernel of the rectification (cerebro_amd/csrc/match.hip: rectify_pair) in the gfx950 code object of the built
+"""Build-time look at the kernel of the rectification (cerebro_amd/csrc/frames.hip: rectify_pair) in the gfx950 code object of the built
 libcerebro_hip.so (no GPU needed): it exists once, does not spill or use a flat_ memory instruction, stores four pixels as one dword
 (bytes only for tails and odd alignments) -- and the ORB and block-matcher kernels have the registers they had without it."""
 import pytest

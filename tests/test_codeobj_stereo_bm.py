@@ -1,4 +1,4 @@
-"""Build-time look at the three kernels of the block matcher (cerebro_amd/csrc/match.hip: bm_prefilter, bm_keypoints, bm_dense) in the
+"""Build-time look at the three kernels of the block matcher (cerebro_amd/csrc/frames.hip: bm_prefilter, bm_keypoints, bm_dense) in the
 gfx950 code object of the built libcerebro_hip.so (no GPU needed): each exists once, none spills or uses a flat_ memory instruction,
 the record of a keypoint leaves in ONE 16-byte store, the sums of absolute differences are byte-SAD instructions -- and frame_gather
 and disparity_gather next to them have the registers they had before."""

@@ -1,4 +1,4 @@
-"""GPU parity of the disparity -> 3-D step (cerebro_amd/csrc/match.hip: disparity_gather behind chip_frame_put_disparity,
+"""GPU parity of the disparity -> 3-D step (cerebro_amd/csrc/frames.hip: disparity_gather behind chip_frame_put_disparity,
 disparity_to_xyz behind chip_disparity_to_xyz) through ctypes -> C ABI against the numpy restatement (tests/np_mirror_disparity.py).
 Floats are compared on their uint32 view, a NaN matches any NaN.  A frame put from its disparity must be indistinguishable from the
 same frame put through chip_frame_put with the restated 3-D image: same records, same match results, same poses.  The case set is

@@ -1,7 +1,8 @@
-"""GPU parity of the frame store (cerebro_amd/csrc/match.hip: chip_frame_store_reserve, chip_frame_put / _drop / _read,
+"""GPU parity of the frame store (cerebro_amd/csrc/frames.hip: chip_frame_store_reserve, chip_frame_put / _drop / _read; match.hip:
 chip_match_batch_stored) through ctypes -> C ABI.  Frames are put once under an id; a match on stored frames gives, per candidate, the
 bytes of chip_match_batch on the host frames that were put AND of the numpy restatement; chip_frame_read gives the numpy gather.
 Small images (64 x 48) wherever the case is not about the 752 x 480 scene."""
+import functools
 import subprocess
 from pathlib import Path
 
@@ -347,6 +348,61 @@ def test_resident_tick_mode_allocates_inside_a_pause(five, monkeypatch):
         c.loop_tick(400)
     for j, (g, m) in enumerate(zip(got, five["mirror"])):
         assert_same_result(g, m, j)
+
+
+@functools.lru_cache(maxsize=None)
+def _first_use_calls() -> dict:
+    """the four calls of test_first_use_order_of_frame_and_match_state, name -> call(ctx) -> dict of arrays / summaries; shapes of cases
+    the other GPU tests use (stereo_bm: 43 x 11, rectification: 80 x 70, host frames: 64 x 48 with 257 keypoints)"""
+    import rectify_cases as RC
+    import stereo_bm_cases as SC
+    left, right, _ = SC.tiled_pair(np.random.default_rng(43), 43, 11, tile=16, lo=0, hi=31)
+    bm = SC.case("first_use", left, right, 32, 7)["params"]
+    w, h = 80, 70
+    lraw, rraw = RC.image(w, h), RC.image(w, h, 1)
+    lm, rm = RC.radtan(w, h) + RC.rotation(w, h), RC.random_map(w, h, 3) + RC.random_map(w, h, 4)
+    rng = np.random.default_rng(257)
+    a = fc.frame(rng, 257, plant_at=(0, 63, 64, 256))
+    b = fc.view_of(rng, a, extra=20)
+
+    def rectify(c):
+        c.rectify_set_maps(lm, rm)
+        lo, ro = c.rectify_pair(lraw, rraw)
+        return dict(left=lo, right=ro)
+
+    def put(c):
+        c.frame_store_reserve(2, 512)
+        c.frame_put(7, a)
+        return c.frame_read(7)
+
+    return dict(stereo_bm=lambda c: dict(disp=c.stereo_bm(left, right, bm)), rectify=rectify, match_pair=lambda c: c.match_pair(a, b, KINV), put=put)
+
+
+def _first_use_run(first: str) -> bytes:
+    """a fresh ctx runs `first`, then the other three calls in their listed order, then the put frame against itself: every output, as bytes"""
+    calls = _first_use_calls()
+    got = {}
+    with capi.Chip(4096) as c:
+        for name in [first] + [n for n in calls if n != first]:
+            got[name] = calls[name](c)
+        got["stored"] = stored_all(c, 7, [7], KINV)[0]
+    assert got["match_pair"]["summary"]["n_matches_gms"] > 0 and got["stored"]["summary"]["n_matches_gms"] > 0 and got["put"]["n"] == 257
+    assert (got["stereo_bm"]["disp"] != -16).any() and got["rectify"]["left"].any()
+    return b"".join(name.encode() + k.encode() + (np.ascontiguousarray(v).tobytes() if isinstance(v, np.ndarray) else repr(v).encode())
+                    for name in sorted(got) for k, v in sorted(got[name].items()))
+
+
+@pytest.fixture(scope="module")
+def first_use_listed_order():
+    return _first_use_run("stereo_bm")
+
+
+@pytest.mark.parametrize("first", ["stereo_bm", "rectify", "match_pair", "put"])
+def test_first_use_order_of_frame_and_match_state(first_use_listed_order, first):
+    """The frame state and the match state of a ctx come into being apart, each on the first call that needs it: whichever call is the
+    first on a fresh ctx -- a dense block matcher call or the rectification (frame state alone), a match of host frames (match state
+    alone), the reserve (both) -- every later output equals, bit for bit, what one ctx running the four in the listed order returns."""
+    assert _first_use_run(first) == first_use_listed_order
 
 
 def test_verify_candidates_stored_example():

@@ -1,4 +1,4 @@
-"""GPU parity of the rectification (cerebro_amd/csrc/match.hip: rectify_pair behind chip_remap, chip_rectify_pair and
+"""GPU parity of the rectification (cerebro_amd/csrc/frames.hip: rectify_pair behind chip_remap, chip_rectify_pair and
 chip_frame_put_raw_orb_stereo) through ctypes -> C ABI against the numpy restatement (tests/np_mirror_rectify.py).  Everything is
 compared for equality: images byte for byte, a frame put from its raw pair against the same frame put from the pair chip_rectify_pair
 makes of it, row for row.  The definition is this project's own and is not pinned against OpenCV."""
@@ -137,7 +137,7 @@ def test_statuses_without_maps_and_on_a_group_ctx():
     l, r = RC.image(w, h), RC.image(w, h, 1)
     m = RC.identity(w, h)
     with capi.Chip(4096) as ctx:
-        assert status_of(ctx.rectify_pair, l, r) == capi.CHIP_ERR_BUSY                           # no match state at all
+        assert status_of(ctx.rectify_pair, l, r) == capi.CHIP_ERR_BUSY                           # no frame state at all
         assert same_bytes(ctx.remap(l, *m), l)                                                   # needs no maps and no store
         assert status_of(ctx.rectify_pair, l, r) == capi.CHIP_ERR_BUSY                           # no maps
         ctx.frame_store_reserve(2, 400)

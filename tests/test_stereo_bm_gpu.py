@@ -1,4 +1,4 @@
-"""GPU parity of the block matcher (cerebro_amd/csrc/match.hip: bm_prefilter, bm_dense behind chip_stereo_bm, bm_keypoints behind
+"""GPU parity of the block matcher (cerebro_amd/csrc/frames.hip: bm_prefilter, bm_dense behind chip_stereo_bm, bm_keypoints behind
 chip_frame_put_stereo) through ctypes -> C ABI against the numpy restatement (tests/np_mirror_stereo_bm.py), element for element.
 A frame put from its rectified pair must be indistinguishable from the same frame put through chip_frame_put_disparity with
 CHIP_DISP_S16 and the map of chip_stereo_bm: same records, same match results, same poses.  The case set is tests/stereo_bm_cases.py;

@@ -13,14 +13,14 @@ ORCFLAGS   ?= -O2 -mfma -ffp-contract=off -fopenmp -fPIC -Wall -Wextra
 
 LIBDIR     := cerebro_amd/lib
 CSRC       := cerebro_amd/csrc
-HIP_SRCS   := $(CSRC)/kernels.hip $(CSRC)/chip_api.hip $(CSRC)/resident.hip $(CSRC)/chip_multi.hip $(CSRC)/pnp.hip $(CSRC)/icp.hip $(CSRC)/batch.hip $(CSRC)/match.hip $(CSRC)/frames.hip $(CSRC)/orb.hip $(CSRC)/project.hip
+HIP_SRCS   := $(CSRC)/kernels.hip $(CSRC)/chip_api.hip $(CSRC)/resident.hip $(CSRC)/chip_multi.hip $(CSRC)/pnp.hip $(CSRC)/icp.hip $(CSRC)/batch.hip $(CSRC)/match.hip $(CSRC)/frames.hip $(CSRC)/orb.hip $(CSRC)/project.hip $(CSRC)/vlad.hip
 HIP_OBJS   := $(HIP_SRCS:$(CSRC)/%.hip=$(LIBDIR)/%.o)
 ORC_SRCS   := $(wildcard oracle/*.c)
 
 all: lib oracle host testlibs verify ref ref_modes
 lib: $(LIBDIR)/libcerebro_hip.so
 oracle: oracle/_build/liboracle.so oracle/_build/liboracle_eispack.so oracle/_build/liboracle_stats.so oracle/_build/liboracle_flops.so
-host: $(LIBDIR)/libcerebro_host.so $(LIBDIR)/cerebro_replay $(LIBDIR)/minimal_loop_detector $(LIBDIR)/sync_tick_latency $(LIBDIR)/verify_candidate $(LIBDIR)/verify_candidates $(LIBDIR)/verify_candidates_stored $(LIBDIR)/verify_candidates_composed $(LIBDIR)/verify_candidates_modes $(LIBDIR)/verify_pairs_stored $(LIBDIR)/frame_put_disparity $(LIBDIR)/frame_put_stereo $(LIBDIR)/orb_detect $(LIBDIR)/orb_frame_put $(LIBDIR)/frame_put_raw_stereo $(LIBDIR)/append_projected
+host: $(LIBDIR)/libcerebro_host.so $(LIBDIR)/cerebro_replay $(LIBDIR)/minimal_loop_detector $(LIBDIR)/sync_tick_latency $(LIBDIR)/verify_candidate $(LIBDIR)/verify_candidates $(LIBDIR)/verify_candidates_stored $(LIBDIR)/verify_candidates_composed $(LIBDIR)/verify_candidates_modes $(LIBDIR)/verify_pairs_stored $(LIBDIR)/frame_put_disparity $(LIBDIR)/frame_put_stereo $(LIBDIR)/orb_detect $(LIBDIR)/orb_frame_put $(LIBDIR)/frame_put_raw_stereo $(LIBDIR)/append_projected $(LIBDIR)/append_vlad
 # test infrastructure that needs hipcc: the shared-memory stand-in for librccl (N ranks on one device, tests/test_fakerccl_gpu.py)
 testlibs: tests/fakerccl/_build/libfakerccl.so $(LIBDIR)/norows/libcerebro_hip.so $(LIBDIR)/hooks/libcerebro_hip.so
 # The TEST build of the library (-DCHIP_TEST_HOOKS): the fault-injection hooks (CHIP_TEST_COMM_INIT, CHIP_TEST_FAIL_SHARD,
@@ -151,6 +151,12 @@ $(LIBDIR)/frame_put_raw_stereo: examples/frame_put_raw_stereo.cc $(LIBDIR)/libce
 # the definition and chip_db_append_f64: same rows, same ticks (and, with an argument, the time of both at 32768 -> 4096).
 # -ffp-contract=off: the restatement fuses where it says std::fma and nowhere else
 $(LIBDIR)/append_projected: examples/append_projected.cc include/cerebro_hip.h $(LIBDIR)/libcerebro_hip.so
+	$(CXX) -O2 -std=c++17 -ffp-contract=off -Wall -Wextra -Iinclude $< -o $@ -L$(LIBDIR) -lcerebro_hip -Wl,-rpath,'$$ORIGIN'
+
+# ---- the NetVLAD pooling: a DB appended through chip_db_append_vlad_f32 (directly, and through a projection) and, next to it, through a
+# plain C++ restatement of the definition and chip_db_append_f64 / chip_db_append_projected_f32: same rows, same ticks (and, with an
+# argument, the time of both).  -ffp-contract=off: the restatement fuses where it says std::fma and nowhere else
+$(LIBDIR)/append_vlad: examples/append_vlad.cc include/cerebro_hip.h $(LIBDIR)/libcerebro_hip.so
 	$(CXX) -O2 -std=c++17 -ffp-contract=off -Wall -Wextra -Iinclude $< -o $@ -L$(LIBDIR) -lcerebro_hip -Wl,-rpath,'$$ORIGIN'
 
 # ---- the reference's own GMS matcher as a compiled checker (test infrastructure: tests/gms_ref_lib.py, tests/test_gms_ref_mirror.py).

@@ -82,6 +82,8 @@ CHIP_ORB_N_FEATURES, CHIP_ORB_N_LEVELS, CHIP_ORB_FAST_THRESHOLD, CHIP_ORB_BORDER
 CHIP_RECTIFY_FRACTION_BITS, CHIP_RECTIFY_MAP_MIN, CHIP_RECTIFY_MAP_MAX, CHIP_RECTIFY_NAN_Q = 5, -2.0, 32768.0, -64
 # descriptor projection: the matrix's element type; in_dim % 256 == 0, 256 <= in_dim <= CHIP_PROJ_MAX_IN_DIM
 CHIP_PROJ_F32, CHIP_PROJ_F64, CHIP_PROJ_MAX_IN_DIM = 1, 2, 32768
+# NetVLAD pooling: the layout of a feature map, the positions per aggregation block (part of the definition), the most positions
+CHIP_VLAD_NHWC, CHIP_VLAD_NCHW, CHIP_VLAD_BLOCK, CHIP_VLAD_MAX_POSITIONS = 1, 2, 64, 16384
 
 
 class ChipError(RuntimeError):
@@ -333,6 +335,13 @@ _SIGS = {
     "chip_project_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "chip_project": (C.c_int, [_P, _P, C.c_int64, _P]),
     "chip_db_append_projected_f32": (C.c_int, [_P, _P, C.c_int64, C.c_uint32, C.POINTER(C.c_int64)]),
+    "chip_build_has_vlad": (C.c_int, []),
+    "chip_vlad_set": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "chip_vlad_clear": (C.c_int, [_P]),
+    "chip_vlad_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "chip_vlad": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
+    "chip_db_append_vlad_f32": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_int64)]),
+    "chip_debug_vlad_stage": (C.c_int, [_P, _P, _P, _P]),
     "chip_get_info": (C.c_int, [_P, C.POINTER(Info)]),
     "chip_profile_enable": (C.c_int, [_P, C.c_int32]),
     "chip_profile_reset": (C.c_int, [_P]),
@@ -667,6 +676,63 @@ class Chip:
         first = C.c_int64()
         self._chk(self.lib.chip_db_append_projected_f32(self.h, p, n, flags, C.byref(first)), "chip_db_append_projected_f32")
         return first.value
+
+    # -- NetVLAD pooling: the trunk's feature map -> the pooled float32 vector on the device (include/cerebro_hip.h "NetVLAD pooling")
+    def vlad_set(self, Wt, bias, centres):
+        """chip_vlad_set: Wt (K+G, C), bias (K+G), centres (K, C), all float32; K = centres.shape[0], the other rows are ghosts"""
+        Wt = np.ascontiguousarray(Wt, dtype=np.float32)
+        centres = np.ascontiguousarray(centres, dtype=np.float32)
+        bias = np.ascontiguousarray(bias, dtype=np.float32).reshape(-1)
+        if Wt.ndim != 2 or centres.ndim != 2 or centres.shape[1] != Wt.shape[1] or bias.size != Wt.shape[0] or centres.shape[0] > Wt.shape[0]:
+            raise ValueError("vlad_set: Wt (K+G, C), bias (K+G), centres (K, C)")
+        K, G = centres.shape[0], Wt.shape[0] - centres.shape[0]
+        self._chk(self.lib.chip_vlad_set(self.h, Wt.shape[1], K, G, _ptr(Wt), _ptr(bias), _ptr(centres)), "chip_vlad_set")
+
+    def vlad_clear(self):
+        self._chk(self.lib.chip_vlad_clear(self.h), "chip_vlad_clear")
+
+    def vlad_info(self) -> dict:
+        """chip_vlad_info: all 0 when no weights are set"""
+        v = [C.c_int32(), C.c_int32(), C.c_int32()]
+        self._chk(self.lib.chip_vlad_info(self.h, *(C.byref(x) for x in v)), "chip_vlad_info")
+        return dict(channels=v[0].value, clusters=v[1].value, ghost=v[2].value)
+
+    def _feature_map(self, fmap, positions, layout):
+        """(pointer, positions, what keeps it alive): a numpy array -- (N, C) for CHIP_VLAD_NHWC, (C, N) for CHIP_VLAD_NCHW, leading axes
+        of one flattened -- or an integer device address (memory of the ctx's device that the caller has waited for) with positions"""
+        if isinstance(fmap, (int, np.integer)):
+            if positions is None:
+                raise ValueError("a device address needs positions")
+            return C.c_void_p(int(fmap)), int(positions), None
+        a = np.ascontiguousarray(fmap, dtype=np.float32)
+        ch = self.vlad_info()["channels"]
+        if positions is None:
+            positions = a.size // ch if ch else a.size     # (without weights the call reports CHIP_ERR_BUSY itself)
+        return _ptr(a), int(positions), a
+
+    def vlad(self, fmap, layout: int = CHIP_VLAD_NHWC, positions: int | None = None) -> np.ndarray:
+        """chip_vlad -> the pooled vector, (K * C,) float32"""
+        p, n, keep = self._feature_map(fmap, positions, layout)
+        i = self.vlad_info()
+        v = np.empty(max(i["clusters"] * i["channels"], 1), dtype=np.float32)
+        self._chk(self.lib.chip_vlad(self.h, p, n, layout, _ptr(v)), "chip_vlad")
+        return v
+
+    def append_vlad(self, fmap, layout: int = CHIP_VLAD_NHWC, flags: int = 0, positions: int | None = None) -> int:
+        """chip_db_append_vlad_f32 -> the index of the row appended"""
+        p, n, keep = self._feature_map(fmap, positions, layout)
+        first = C.c_int64()
+        self._chk(self.lib.chip_db_append_vlad_f32(self.h, p, n, layout, flags, C.byref(first)), "chip_db_append_vlad_f32")
+        return first.value
+
+    def debug_vlad_stage(self, positions: int) -> dict:
+        """chip_debug_vlad_stage after a pooling call over `positions` positions -> a (N, K+G), V (K, C), A (K,), float64"""
+        i = self.vlad_info()
+        a = np.empty((int(positions), i["clusters"] + i["ghost"]))
+        V = np.empty((i["clusters"], i["channels"]))
+        A = np.empty(i["clusters"])
+        self._chk(self.lib.chip_debug_vlad_stage(self.h, _ptr(a), _ptr(V), _ptr(A)), "chip_debug_vlad_stage")
+        return dict(a=a, V=V, A=A)
 
     def append_synthetic(self, n: int, seed: int, plants=(), unit: bool = False):
         """unit=True: the rows normalised to unit L2 norm (chip_db_append_synthetic_unit, SURVEY.md 8d's data)."""

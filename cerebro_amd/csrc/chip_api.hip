@@ -854,7 +854,8 @@ int append_reserve(Ctx *c, int64_t first, int64_t n) { return ensure_capacity(c,
 
 // Upload rows [from, from + count) of the call (step > 1: every step-th row, i.e. one shard's rows) in staging-sized chunks and
 // run K3 on them.  ring: mirror into the replicated ring as well.  A projected append (src.raw) makes each chunk's rows on the device
-// instead of copying them: the raw descriptors are staged already (ctx_append), the rows are doubles.
+// instead of copying them: the raw descriptors are staged already (ctx_append), the rows are doubles.  A pooled append (src.fmap) makes
+// its one row from the staged feature map the same way (vlad.hip vlad_chunk).
 static int append_pass(Ctx *c, const AppendSrc &src, int64_t first, int64_t from, int64_t count, int64_t step, bool ring)
 {
     const int src_elem = src.elem;
@@ -864,6 +865,9 @@ static int append_pass(Ctx *c, const AppendSrc &src, int64_t first, int64_t from
         const int64_t m = (count - done) < chunk_rows ? (count - done) : chunk_rows;
         if (src.raw) {   // (plain single-GPU ctx: step == 1)
             const int r = project_chunk(c, from + done, m);
+            if (r != CHIP_OK) return r;
+        } else if (src.fmap) {   // (count == 1)
+            const int r = vlad_chunk(c);
             if (r != CHIP_OK) return r;
         } else {
             const char *host = static_cast<const char *>(src.desc) + (size_t)(from + done * step) * row_bytes;
@@ -945,17 +949,23 @@ int append_ring_publish(Ctx *c, const AppendSrc &src, int64_t first, int64_t n, 
 
 int ctx_append(Ctx *c, const AppendSrc &src, int64_t n, uint32_t flags, int64_t *first_index)
 {
-    if (!c || !(src.raw ? (const void *)src.raw : src.desc) || n < 0) return CHIP_ERR_INVALID_ARG;
+    if (!c || !(src.raw ? (const void *)src.raw : src.fmap ? (const void *)src.fmap : src.desc) || n < 0) return CHIP_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> alk(c->append_mu);
     if (src.raw && !c->proj.in_dim) return CHIP_ERR_BUSY;   // a projected append without a projection
+    if (src.fmap) {                                         // a pooled append: weights, then the pooled vector's length against what takes it
+        if (!c->vlad.C) return CHIP_ERR_BUSY;
+        if (c->vlad.K * c->vlad.C != (c->proj.in_dim ? c->proj.in_dim : c->D)) return CHIP_ERR_UNSUPPORTED;
+    }
     CHIP_HIP(c, hipSetDevice(c->device));
     const int64_t first = published_rows(c);
     if (first_index) *first_index = first;
     if (n == 0) return CHIP_OK;
     // a projected append launches kernels that fill every CU and do not fit beside the resident scan instance (project.hip project_chunk)
-    ResidentPause paused(c, src.raw != nullptr);
+    // (a pooled append: vlad.hip vlad_chunk says why it pauses too)
+    ResidentPause paused(c, src.raw != nullptr || src.fmap != nullptr);
     int rc = append_reserve(c, first, n);
     if (rc == CHIP_OK && src.raw) rc = project_stage_input(c, src.raw, n);   // once: a retry below projects the staged descriptors again
+    if (rc == CHIP_OK && src.fmap) rc = vlad_stage_input(c, src.fmap, src.positions, src.layout);   // likewise
     if (rc != CHIP_OK) return rc;
     // A ctx that is fed the whole stream by its own caller (single GPU, or one process per GPU) validates the WHOLE batch, so that
     // every rank takes the same storage-type / rejection decision without talking to the others.
@@ -1193,6 +1203,19 @@ int chip_db_append_projected_f32(chip_ctx *c, const float *x, int64_t n, uint32_
     if (!c || !x || n < 0) return CHIP_ERR_INVALID_ARG;
     if (c->group || c->nranks > 1) return CHIP_ERR_UNSUPPORTED;
     return ctx_append(c, AppendSrc{nullptr, 8, x}, n, flags, first_index);
+}
+
+// chip_db_append_f64 of ONE row pooled on the device from a feature map (vlad.hip): a third kind of source
+int chip_db_append_vlad_f32(chip_ctx *c, const float *fmap, int32_t positions, int32_t layout, uint32_t flags, int64_t *first_index)
+{
+    if (!c || !fmap) return CHIP_ERR_INVALID_ARG;
+    if (positions < 1 || positions > CHIP_VLAD_MAX_POSITIONS || (layout != CHIP_VLAD_NHWC && layout != CHIP_VLAD_NCHW)) return CHIP_ERR_UNSUPPORTED;
+    if (c->group || c->nranks > 1) return CHIP_ERR_UNSUPPORTED;
+    AppendSrc src{nullptr, 8};
+    src.fmap = fmap;
+    src.positions = positions;
+    src.layout = layout;
+    return ctx_append(c, src, 1, flags, first_index);
 }
 
 int chip_db_append_f32(chip_ctx *c, const float *desc, int64_t n, int64_t *first_index)

@@ -181,9 +181,31 @@ struct AppendSrc {
     const void *desc;
     int elem;
     const float *raw = nullptr;
+    const float *fmap = nullptr;      // a third kind (vlad.hip): ONE feature map of `positions` positions in `layout`, pooled into one row
+    int32_t positions = 0;            // -- directly (clusters * channels == D) or through the ctx's projection (== its in_dim)
+    int32_t layout = 0;
 };
 int project_stage_input(Ctx *c, const float *x, int64_t n);   // raw descriptors -> Projection::x, enqueued on s_append
 int project_chunk(Ctx *c, int64_t from, int64_t m);           // staged descriptors [from, from + m) -> rows 0 .. m-1 of stage_dev, on s_append
+
+// ---- NetVLAD pooling (vlad.hip): feature map -> pooled float32 vector, for chip_vlad and the pooled append.  Guarded by append_mu.
+struct Vlad {
+    DevBuf<char> w;                   // [bias: K+G doubles, padded to an even count][Wt: (K+G) x C floats][centres: K x C floats], replaced as a whole
+    DevBuf<float> raw;                // a CHIP_VLAD_NCHW map as it came, before the transposing stage-in
+    DevBuf<float> x;                  // the map of the running call, N x C
+    DevBuf<double> a;                 // soft assignment, N x (K+G)
+    DevBuf<double> part;              // [P_j: blocks x K x C][S_j: blocks x K]
+    DevBuf<double> vu;                // [V: K x C][U: K x C][A: K]
+    DevBuf<float> out;                // chip_vlad: [v: K x C floats][flag word]
+    int32_t C = 0, K = 0, G = 0;      // C == 0: no weights set
+    int32_t last_n = 0;               // positions of the last pooling call whose stages a, V, A are on the device (0: none)
+    int bias_count() const { return (K + G + 1) & ~1; }
+    double *bias() const { return reinterpret_cast<double *>(w.get()); }
+    float *Wt() const { return reinterpret_cast<float *>(w.get() + (size_t)bias_count() * sizeof(double)); }
+    float *centres() const { return Wt() + (size_t)(K + G) * C; }
+};
+int vlad_stage_input(Ctx *c, const float *fmap, int32_t positions, int32_t layout);   // the map -> Vlad::x (N x C), enqueued on s_append
+int vlad_chunk(Ctx *c);                                       // the staged map -> row 0 of stage_dev (directly, or through project_chunk), on s_append
 
 // kernels.hip
 int launch_resident(Ctx *c, hipStream_t s, const ResidentArgs &ra, int grid);   // CHIP_ERR_UNSUPPORTED in a build without the rows form
@@ -413,6 +435,7 @@ struct Ctx {
     FrameStore *frame_store = nullptr;   // frames.hip: created by the first frame call that needs it; guarded by match_mu
     OrbState *orb_state = nullptr;   // orb.hip: created by the first chip_orb_detect; its calls take match_mu
     Projection proj;                 // project.hip (append_mu)
+    Vlad vlad;                       // vlad.hip (append_mu)
     std::mutex match_mu;         // serialises the matching calls of a ctx; taken BEFORE pnp_mu / icp_mu (chip_*_ransac_matched)
 
     mutable hipError_t last_hip = hipSuccess;

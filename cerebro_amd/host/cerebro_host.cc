@@ -78,6 +78,28 @@ bool Cerebro::raw_descriptor_available(const Time &stamp, const double *raw, int
     return (int64_t)wholeImageComputedList.size() == first + 1;
 }
 
+bool Cerebro::set_descriptor_pooling(int channels, int clusters, int ghost, const float *Wt, const float *bias, const float *centres)
+{
+    if (!ctx_) { status_ = CHIP_ERR_NO_DEVICE; return false; }
+    status_ = chip_vlad_set(ctx_, channels, clusters, ghost, Wt, bias, centres);
+    if (status_ != CHIP_OK) return false;
+    pool_dim_ = clusters * channels;
+    return true;
+}
+
+bool Cerebro::feature_map_available(const Time &stamp, const float *fmap, int positions, int layout)
+{
+    if (!fmap || positions <= 0) { status_ = CHIP_ERR_INVALID_ARG; return false; }
+    if (!ctx_) { status_ = CHIP_ERR_NO_DEVICE; return false; }
+    if (pool_dim_ == 0) { status_ = CHIP_ERR_BUSY; return false; }
+    int64_t first = -1;
+    status_ = chip_db_append_vlad_f32(ctx_, fmap, positions, layout, 0, &first);
+    if (status_ != CHIP_OK) return false;
+    std::lock_guard<std::mutex> lk(m_wholeImageComputedList);  // as descriptor_available
+    wholeImageComputedList.push_back(stamp);
+    return (int64_t)wholeImageComputedList.size() == first + 1;
+}
+
 int64_t Cerebro::loadStateFromDisk(const std::string &path)
 {
     if (!ctx_) return -1;

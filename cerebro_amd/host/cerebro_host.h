@@ -68,6 +68,14 @@ public:
     // here when in_dim equals the descriptor size -- the limits allow 4096 -> 4096 --: with such a projection set there is no finished-
     // descriptor route.)
     bool raw_descriptor_available(const Time &stamp, const double *raw, int n);
+    // One step further up: the producer hands over the trunk's last feature map and the device does the NetVLAD / GhostVLAD pooling
+    // (scripts/predict_utils.py NetVLADLayer; chip_vlad_set / chip_db_append_vlad_f32), then the projection if one is set.  Wt:
+    // (clusters + ghost) x channels, bias: clusters + ghost, centres: clusters x channels, float32 (include/cerebro_hip.h "NetVLAD
+    // pooling").  fmap: positions x channels (CHIP_VLAD_NHWC) or channels x positions (CHIP_VLAD_NCHW) float32, host memory or memory
+    // of the ctx's device that the caller has waited for.  Otherwise the bookkeeping of descriptor_available.
+    bool set_descriptor_pooling(int channels, int clusters, int ghost, const float *Wt, const float *bias, const float *centres);
+    int pooling_vector_dim() const { return pool_dim_; }   // clusters * channels; 0: none set
+    bool feature_map_available(const Time &stamp, const float *fmap, int positions, int layout);
 
     // Cold start from a checkpoint written by DataManager::saveStateToDisk: every node that carries a descriptor is
     // appended in file (= time-stamp) order, as Cerebro rebuilds wholeImageComputedList after loadStateFromDisk
@@ -125,6 +133,7 @@ public:
 private:
     chip_ctx *ctx_ = nullptr;
     int proj_in_dim_ = 0;
+    int pool_dim_ = 0;
     std::vector<float> raw_f32_;   // raw_descriptor_available's narrowed copy (the producer thread's alone)
     int status_ = 0;
     int D_ = 0;

@@ -230,6 +230,75 @@ int chip_project_info(const chip_ctx *ctx, int32_t *in_dim, int32_t *matrix_type
 int chip_project(chip_ctx *ctx, const float *x, int64_t n, double *z /* n x D, host */);
 int chip_db_append_projected_f32(chip_ctx *ctx, const float *x, int64_t n, uint32_t flags, int64_t *first_index);
 
+/* ------------------------------------------------------------------------------------------ NetVLAD pooling
+ * (ABI 7, additive.)  The one non-stock layer of both of the reference's models is its custom Keras layer NetVLADLayer / GhostVLADLayer
+ * (scripts/predict_utils.py:11-64, 83-141): NetVLADImageDescriptor = MobileNet conv_pw_7_relu, K = 16, 8192-D, the default
+ * (whole_image_desc_compute_server.py:206-218); ReljaNetVLAD = VGG16 block5_pool, K = 64, 32768-D, then the projection above.  These
+ * entries take the trunk's last feature map and make the pooled vector -- and the DB row -- on the device: map -> v -> row, or
+ * map -> v -> projection -> row, without a host round trip.  The CNN trunk itself stays the producer's.
+ *
+ * The definition.  THIS PROJECT'S OWN: IEEE fp64 basic operations in stated orders, nothing fused unless it says orc_dot_tree_*; the
+ * device reproduces it bit for bit (tests/np_mirror_vlad.py restates it).  UNPINNED against Keras/TF: a TF build's convolution, softmax,
+ * exp and reduction orders are not a definition and no TF exists on any machine of this project (DESIGN.md 6 lists the departures).
+ * Inputs: x, N positions x C channels of float32, n = row * W + col; Wt, (K+G) x C float32, one contiguous row per cluster
+ * (kernel[0,0].T); bias, K+G float32; centres, K x C float32 (C[0,0,0].T, the first K rows), which the layer ADDS, as the reference
+ * does (predict_utils.py:48).  K kept clusters, G ghost clusters (0 for NetVLADLayer).
+ *   1. Scores, k < K+G:  s[n][k] = orc_dot_tree_f32(x[n], Wt[k], C) + (double)bias[k]: lane L of 64 accumulates elements
+ *      j*256 + 4L + c (j ascending, c = 0..3; elements past C are skipped) by fma -- the products are exact in fp64 --, then the xor
+ *      butterfly acc[L] += acc[L ^ m], m = 32..1; then one IEEE addition.  (The score vector of one query against a DB of K+G rows.)
+ *   2. Softmax:  m = s[n][0]; for k = 1..: if (s[n][k] > m) m = s[n][k];  e_k = vlad_exp(s[n][k] - m);  Z = ((0.0 + e_0) + e_1) + ...
+ *      ascending;  a[n][k] = e_k / Z, IEEE division.
+ *   3. vlad_exp(t), t <= 0:  t < -700.0 gives +0.0.  Otherwise kf = rint(t * LOG2E), ties to even;
+ *      r = (t - kf * LN2_HI) - kf * LN2_LO;  p = c_13; for i = 12..0: p = p * r + c_i, each * and + rounded;  the result is p * 2^kf,
+ *      an exact scaling (kf >= -1010: the power, built from its bit pattern, and the result are normal).
+ *      LOG2E = 0x1.71547652b82fep+0, LN2_HI = 0x1.62e42fee00000p-1, LN2_LO = 0x1.a39ef35793c76p-33, c_i = 1.0 / (double)i! (the double
+ *      nearest 1/i! for i <= 13).  Within 2 ulp of exp on [-700, 0] (1.08 measured), vlad_exp(0) == 1.0.
+ *   4. Aggregation in blocks of CHIP_VLAD_BLOCK = 64 positions -- part of the definition, independent of grid and device.  Block j holds
+ *      positions 64j .. min(64j + 63, N - 1).  For k < K only (ghost rows are never formed):  P_j[k][c] is the ascending chain over
+ *      the block's n, from 0.0, of acc = acc + (a[n][k] * (double)x[n][c]), product rounded, sum rounded;  S_j[k] the ascending chain
+ *      of acc + a[n][k];  V[k][c] and A[k] the ascending chains over j of P_j and S_j, from 0.0.
+ *   5. Centres:  Wv[k][c] = V[k][c] + (A[k] * (double)centres[k][c]) -- the factored form of sum a (x + C), a stated departure from
+ *      the reference's per-term float32 sum.
+ *   6. Intra-normalisation:  q_k = orc_dot_tree_f64(Wv[k], Wv[k], C) (lane L: elements j*128 + 2L + c, c = 0, 1, one fma per term, the
+ *      same butterfly);  r_k = sqrt(q_k > 1e-12 ? q_k : 1e-12) (Keras' l2_normalize epsilon);  U[k][c] = Wv[k][c] / r_k.
+ *   7. q = orc_dot_tree_f64(U, U, K*C) over the k-major flattening;  r = sqrt(q > 1e-12 ? q : 1e-12);
+ *      v[k*C + c] = (float)(U[k][c] / r), rounded to nearest even.  The pooled vector is float32, as the Keras layer's output is.
+ * Non-finite values: chip_vlad_set refuses a NaN or Inf in Wt, bias or centres (a host check, CHIP_ERR_NONFINITE).  A non-finite score
+ * s[n][k] -- which every NaN or Inf of the map produces -- makes the call return CHIP_ERR_NONFINITE with nothing appended and v
+ * unspecified.  Everything else is finite by construction: an all-zero map with zero centres gives an all-zero vector through the
+ * epsilon, and it is appended like any finite row.
+ * Limits: C % 4 == 0, 4 <= C <= 1024; K >= 1, G >= 0, K + G <= 128; (K+G) * C <= 32768; K * C <= CHIP_PROJ_MAX_IN_DIM;
+ * 1 <= positions <= CHIP_VLAD_MAX_POSITIONS.
+ *
+ *   - chip_vlad_set uploads the weights once; they live until chip_vlad_clear or chip_destroy.  A second call replaces them only once
+ *     the new ones are complete on the device (as chip_project_set).  chip_vlad_info: all 0 when none are set; pointers may be NULL.
+ *   - chip_vlad: the definition made callable, one map -> v, K*C floats in host memory.
+ *   - chip_db_append_vlad_f32 appends ONE row made from one map.  With a projection set, its in_dim must equal K*C: the kernels write v
+ *     where chip_db_append_projected_f32 stages its input and the call goes on as that one, so the row is indistinguishable from
+ *     chip_db_append_projected_f32(v of chip_vlad).  With none set, K*C must equal D, and the row is indistinguishable from
+ *     chip_db_append_f64((double)v of chip_vlad): every rule of that call holds (storage decision, row_norm_max, publication); a float32
+ *     value always passes the float-row check.
+ *   - fmap may be host memory or memory of the ctx's device (a torch tensor's data_ptr(): CHIP_VLAD_NCHW is what a torch trunk emits
+ *     for a batch of one): copied with hipMemcpyDefault on the append stream, the CALLER vouches that the map is complete.
+ *   - chip_debug_vlad_stage: a (N x (K+G)), V (K x C), A (K) of the ctx's last pooling call, any pointer may be NULL; it launches nothing.
+ *   - These calls are appends (they serialise with chip_db_append_*).  With CHIP_TICK_RESIDENT=1 chip_vlad and chip_db_append_vlad_f32
+ *     pause the resident scan instance for their duration, as chip_project does.
+ * Status, in this order: a NULL ctx / array CHIP_ERR_INVALID_ARG; the limits or an unknown layout CHIP_ERR_UNSUPPORTED (both before
+ * the ctx is touched); a chip_create_multi or sharded ctx CHIP_ERR_UNSUPPORTED; chip_vlad_set: a non-finite weight
+ * CHIP_ERR_NONFINITE; no weights set CHIP_ERR_BUSY (chip_debug_vlad_stage: also no pooling call yet); K*C against D / in_dim
+ * CHIP_ERR_UNSUPPORTED.                                                                                                         */
+#define CHIP_VLAD_NHWC 1   /* x[n][c]: Keras channels_last                      */
+#define CHIP_VLAD_NCHW 2   /* x[c][n]: what a torch trunk emits (batch of one)  */
+#define CHIP_VLAD_BLOCK 64
+#define CHIP_VLAD_MAX_POSITIONS 16384
+int chip_build_has_vlad(void);             /* 1 */
+int chip_vlad_set(chip_ctx *ctx, int32_t channels, int32_t clusters, int32_t ghost, const float *Wt, const float *bias, const float *centres);
+int chip_vlad_clear(chip_ctx *ctx);
+int chip_vlad_info(const chip_ctx *ctx, int32_t *channels, int32_t *clusters, int32_t *ghost);
+int chip_vlad(chip_ctx *ctx, const float *fmap, int32_t positions, int32_t layout, float *v /* clusters*channels, host */);
+int chip_db_append_vlad_f32(chip_ctx *ctx, const float *fmap, int32_t positions, int32_t layout, uint32_t flags, int64_t *first_index);
+int chip_debug_vlad_stage(chip_ctx *ctx, double *a /* N x (K+G) */, double *V /* K x C */, double *A /* K */);
+
 /* ------------------------------------------------------------------------------------------ scan + top-k
  * Replaces  u = v.transpose() * M.leftCols(k); maxCoeff(); last-index argmax  (src/Cerebro.cpp:1026-1043)
  * generalised to top-K (the compiled-out faiss variants use K=5, src/Cerebro.cpp:460).

@@ -342,6 +342,10 @@ _SIGS = {
     "chip_vlad": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
     "chip_db_append_vlad_f32": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_int64)]),
     "chip_debug_vlad_stage": (C.c_int, [_P, _P, _P, _P]),
+    "chip_project_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, _P]),
+    "chip_debug_project_last": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "chip_vlad_batch": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "chip_db_append_vlad_batch_f32": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_int64)]),
     "chip_get_info": (C.c_int, [_P, C.POINTER(Info)]),
     "chip_profile_enable": (C.c_int, [_P, C.c_int32]),
     "chip_profile_reset": (C.c_int, [_P]),
@@ -481,6 +485,22 @@ def orb_plan(width: int, height: int, params=None) -> list:
         raise ChipError(rc, "chip_orb_plan")
     n = CHIP_ORB_N_LEVELS if params is None else params.n_levels
     return [lv[l].as_dict() for l in range(n)]
+
+
+class ProjectPlan(C.Structure):
+    """chip_project_plan_out"""
+    _fields_ = [("width", C.c_int32), ("slab", C.c_int32), ("lds_bytes", C.c_int32), ("single_lds_bytes", C.c_int32), ("block", C.c_int32),
+                ("reserved", C.c_int32), ("passes", C.c_int64), ("shared_passes", C.c_int64), ("single_launches", C.c_int64)]
+
+
+def project_plan(in_dim: int, matrix_type: int, n: int) -> dict:
+    """chip_project_plan -> what a projecting call over n descriptors launches: width, passes (= shared_passes + single_launches), slab,
+    lds_bytes, single_lds_bytes, block.  Needs no ctx and no device."""
+    out = ProjectPlan()
+    rc = load_library().chip_project_plan(in_dim, matrix_type, n, C.byref(out))
+    if rc != CHIP_OK:
+        raise ChipError(rc, "chip_project_plan")
+    return {name: getattr(out, name) for name, _ in ProjectPlan._fields_ if name != "reserved"}
 
 
 def default_ransac_params() -> RansacParams:
@@ -677,6 +697,13 @@ class Chip:
         self._chk(self.lib.chip_db_append_projected_f32(self.h, p, n, flags, C.byref(first)), "chip_db_append_projected_f32")
         return first.value
 
+    def debug_project_last(self) -> dict:
+        """chip_debug_project_last: what the last projecting call launched -- shared passes and single launches, counted apart"""
+        passes, descs, width = (C.c_int64 * 2)(), (C.c_int64 * 2)(), C.c_int32()
+        self._chk(self.lib.chip_debug_project_last(self.h, passes, descs, C.byref(width)), "chip_debug_project_last")
+        return dict(shared_passes=passes[0], single_launches=passes[1], shared_descriptors=descs[0], single_descriptors=descs[1],
+                    width=width.value)
+
     # -- NetVLAD pooling: the trunk's feature map -> the pooled float32 vector on the device (include/cerebro_hip.h "NetVLAD pooling")
     def vlad_set(self, Wt, bias, centres):
         """chip_vlad_set: Wt (K+G, C), bias (K+G), centres (K, C), all float32; K = centres.shape[0], the other rows are ghosts"""
@@ -723,6 +750,37 @@ class Chip:
         p, n, keep = self._feature_map(fmap, positions, layout)
         first = C.c_int64()
         self._chk(self.lib.chip_db_append_vlad_f32(self.h, p, n, layout, flags, C.byref(first)), "chip_db_append_vlad_f32")
+        return first.value
+
+    def _feature_maps(self, fmaps, n_maps, positions):
+        """(pointer, n_maps, positions, what keeps it alive) of a batch: a numpy array whose first axis counts the maps -- (B, N, C) or
+        (B, H, W, C) for CHIP_VLAD_NHWC, (B, C, N) or (B, C, H, W) for CHIP_VLAD_NCHW -- or an integer device address with both counts"""
+        if isinstance(fmaps, (int, np.integer)):
+            if positions is None or n_maps is None:
+                raise ValueError("a device address needs n_maps and positions")
+            return C.c_void_p(int(fmaps)), int(n_maps), int(positions), None
+        a = np.ascontiguousarray(fmaps, dtype=np.float32)
+        if n_maps is None:
+            n_maps = a.shape[0]
+        ch = self.vlad_info()["channels"]
+        if positions is None:
+            positions = a.size // (ch * n_maps) if ch and n_maps else 1
+        return _ptr(a), int(n_maps), int(positions), a
+
+    def vlad_batch(self, fmaps, layout: int = CHIP_VLAD_NHWC, n_maps: int | None = None, positions: int | None = None) -> np.ndarray:
+        """chip_vlad_batch -> (n_maps, K * C) float32: row m is vlad(map m)"""
+        p, b, n, keep = self._feature_maps(fmaps, n_maps, positions)
+        i = self.vlad_info()
+        v = np.empty((b, max(i["clusters"] * i["channels"], 1)), dtype=np.float32)
+        self._chk(self.lib.chip_vlad_batch(self.h, p, b, n, layout, _ptr(v)), "chip_vlad_batch")
+        return v
+
+    def append_vlad_batch(self, fmaps, layout: int = CHIP_VLAD_NHWC, flags: int = 0, n_maps: int | None = None,
+                          positions: int | None = None) -> int:
+        """chip_db_append_vlad_batch_f32 -> the index of the first row appended"""
+        p, b, n, keep = self._feature_maps(fmaps, n_maps, positions)
+        first = C.c_int64()
+        self._chk(self.lib.chip_db_append_vlad_batch_f32(self.h, p, b, n, layout, flags, C.byref(first)), "chip_db_append_vlad_batch_f32")
         return first.value
 
     def debug_vlad_stage(self, positions: int) -> dict:

@@ -855,7 +855,7 @@ int append_reserve(Ctx *c, int64_t first, int64_t n) { return ensure_capacity(c,
 // Upload rows [from, from + count) of the call (step > 1: every step-th row, i.e. one shard's rows) in staging-sized chunks and
 // run K3 on them.  ring: mirror into the replicated ring as well.  A projected append (src.raw) makes each chunk's rows on the device
 // instead of copying them: the raw descriptors are staged already (ctx_append), the rows are doubles.  A pooled append (src.fmap) makes
-// its one row from the staged feature map the same way (vlad.hip vlad_chunk).
+// the chunk's rows from the caller's feature maps the same way (vlad.hip vlad_chunk).
 static int append_pass(Ctx *c, const AppendSrc &src, int64_t first, int64_t from, int64_t count, int64_t step, bool ring)
 {
     const int src_elem = src.elem;
@@ -866,8 +866,8 @@ static int append_pass(Ctx *c, const AppendSrc &src, int64_t first, int64_t from
         if (src.raw) {   // (plain single-GPU ctx: step == 1)
             const int r = project_chunk(c, from + done, m);
             if (r != CHIP_OK) return r;
-        } else if (src.fmap) {   // (count == 1)
-            const int r = vlad_chunk(c);
+        } else if (src.fmap) {   // (plain single-GPU ctx: step == 1)
+            const int r = vlad_chunk(c, src, from + done, m);
             if (r != CHIP_OK) return r;
         } else {
             const char *host = static_cast<const char *>(src.desc) + (size_t)(from + done * step) * row_bytes;
@@ -965,12 +965,12 @@ int ctx_append(Ctx *c, const AppendSrc &src, int64_t n, uint32_t flags, int64_t 
     ResidentPause paused(c, src.raw != nullptr || src.fmap != nullptr);
     int rc = append_reserve(c, first, n);
     if (rc == CHIP_OK && src.raw) rc = project_stage_input(c, src.raw, n);   // once: a retry below projects the staged descriptors again
-    if (rc == CHIP_OK && src.fmap) rc = vlad_stage_input(c, src.fmap, src.positions, src.layout);   // likewise
     if (rc != CHIP_OK) return rc;
     // A ctx that is fed the whole stream by its own caller (single GPU, or one process per GPU) validates the WHOLE batch, so that
     // every rank takes the same storage-type / rejection decision without talking to the others.
     uint32_t bad = 0;
     for (int attempt = 0; attempt < 2; attempt++) {
+        if (src.raw || src.fmap) project_count_reset(c);   // chip_debug_project_last: what THIS run of the call launches
         rc = append_store_db(c, src, first, n, false, &bad);
         if (rc != CHIP_OK) return rc;
         if (bad & 2u) return CHIP_ERR_NONFINITE;
@@ -1205,17 +1205,24 @@ int chip_db_append_projected_f32(chip_ctx *c, const float *x, int64_t n, uint32_
     return ctx_append(c, AppendSrc{nullptr, 8, x}, n, flags, first_index);
 }
 
-// chip_db_append_f64 of ONE row pooled on the device from a feature map (vlad.hip): a third kind of source
-int chip_db_append_vlad_f32(chip_ctx *c, const float *fmap, int32_t positions, int32_t layout, uint32_t flags, int64_t *first_index)
+// chip_db_append_f64 of n_maps rows pooled on the device from feature maps (vlad.hip): a third kind of source
+int chip_db_append_vlad_batch_f32(chip_ctx *c, const float *fmaps, int32_t n_maps, int32_t positions, int32_t layout, uint32_t flags, int64_t *first_index)
 {
-    if (!c || !fmap) return CHIP_ERR_INVALID_ARG;
+    if (!c || !fmaps || n_maps < 0) return CHIP_ERR_INVALID_ARG;
     if (positions < 1 || positions > CHIP_VLAD_MAX_POSITIONS || (layout != CHIP_VLAD_NHWC && layout != CHIP_VLAD_NCHW)) return CHIP_ERR_UNSUPPORTED;
     if (c->group || c->nranks > 1) return CHIP_ERR_UNSUPPORTED;
     AppendSrc src{nullptr, 8};
-    src.fmap = fmap;
+    src.fmap = fmaps;
     src.positions = positions;
     src.layout = layout;
-    return ctx_append(c, src, 1, flags, first_index);
+    src.n_maps = n_maps;
+    return ctx_append(c, src, n_maps, flags, first_index);
+}
+
+// the single call: a batch of one
+int chip_db_append_vlad_f32(chip_ctx *c, const float *fmap, int32_t positions, int32_t layout, uint32_t flags, int64_t *first_index)
+{
+    return chip_db_append_vlad_batch_f32(c, fmap, 1, positions, layout, flags, first_index);
 }
 
 int chip_db_append_f32(chip_ctx *c, const float *desc, int64_t n, int64_t *first_index)

@@ -165,13 +165,14 @@ private:
 // ---- descriptor projection (project.hip): z = normalise(Mt x + b) made on the device, for chip_project and the projected append.
 // Everything is guarded by append_mu: the calls are appends, or share the append's stream and staging buffer.
 struct Projection {
-    DevBuf<char> buf;                 // [matrix: D rows of in_dim elements][bias: D doubles][y: D doubles], replaced as a whole
+    DevBuf<char> buf;                 // [matrix: D rows of in_dim elements][bias: D doubles][y: one group's descriptors x D doubles], replaced as a whole
     DevBuf<float> x;                  // the raw descriptors of the running call (n x in_dim), grown on demand
     size_t mat_bytes = 0;
     int32_t in_dim = 0;               // 0: no projection set
     int32_t matrix_type = 0;          // CHIP_PROJ_F32 / CHIP_PROJ_F64
     int32_t D = 0;
     bool has_bias = false;
+    int64_t last_passes = 0, last_singles = 0, last_pass_descriptors = 0;   // what the last projecting call launched (chip_debug_project_last)
     double *bias() const { return reinterpret_cast<double *>(buf.get() + mat_bytes); }
     double *y() const { return bias() + D; }
 };
@@ -181,31 +182,34 @@ struct AppendSrc {
     const void *desc;
     int elem;
     const float *raw = nullptr;
-    const float *fmap = nullptr;      // a third kind (vlad.hip): ONE feature map of `positions` positions in `layout`, pooled into one row
-    int32_t positions = 0;            // -- directly (clusters * channels == D) or through the ctx's projection (== its in_dim)
-    int32_t layout = 0;
+    const float *fmap = nullptr;      // a third kind (vlad.hip): n_maps feature maps of `positions` positions in `layout`, one after the other,
+    int32_t positions = 0;            // each pooled into one row -- directly (clusters * channels == D) or through the ctx's projection
+    int32_t layout = 0;               // (== its in_dim)
+    int32_t n_maps = 0;
 };
 int project_stage_input(Ctx *c, const float *x, int64_t n);   // raw descriptors -> Projection::x, enqueued on s_append
 int project_chunk(Ctx *c, int64_t from, int64_t m);           // staged descriptors [from, from + m) -> rows 0 .. m-1 of stage_dev, on s_append
+void project_count_reset(Ctx *c);                             // a projecting call begins: chip_debug_project_last counts from here
 
 // ---- NetVLAD pooling (vlad.hip): feature map -> pooled float32 vector, for chip_vlad and the pooled append.  Guarded by append_mu.
 struct Vlad {
     DevBuf<char> w;                   // [bias: K+G doubles, padded to an even count][Wt: (K+G) x C floats][centres: K x C floats], replaced as a whole
-    DevBuf<float> raw;                // a CHIP_VLAD_NCHW map as it came, before the transposing stage-in
-    DevBuf<float> x;                  // the map of the running call, N x C
-    DevBuf<double> a;                 // soft assignment, N x (K+G)
-    DevBuf<double> part;              // [P_j: blocks x K x C][S_j: blocks x K]
-    DevBuf<double> vu;                // [V: K x C][U: K x C][A: K]
-    DevBuf<float> out;                // chip_vlad: [v: K x C floats][flag word]
+    // the scratch of one GROUP of maps (vlad.hip vlad_group; a single call is a group of one), every array map-major:
+    DevBuf<float> raw;                // CHIP_VLAD_NCHW maps as they came, before the transposing stage-in
+    DevBuf<float> x;                  // the maps of the running group, maps x N x C
+    DevBuf<double> a;                 // soft assignment, maps x N x (K+G)
+    DevBuf<double> part;              // [P_j: maps x blocks x K x C][S_j: maps x blocks x K]
+    DevBuf<double> vu;                // [V: maps x K x C][U: maps x K x C][A: maps x K]
+    DevBuf<float> out;                // chip_vlad_batch: [v: maps x K x C floats][flag word]
     int32_t C = 0, K = 0, G = 0;      // C == 0: no weights set
-    int32_t last_n = 0;               // positions of the last pooling call whose stages a, V, A are on the device (0: none)
+    int32_t last_n = 0;               // positions per map of the last pooled group whose stages a, V, A are on the device (0: none)
+    int32_t last_maps = 0;            // and its maps: chip_debug_vlad_stage reads the last one's
     int bias_count() const { return (K + G + 1) & ~1; }
     double *bias() const { return reinterpret_cast<double *>(w.get()); }
     float *Wt() const { return reinterpret_cast<float *>(w.get() + (size_t)bias_count() * sizeof(double)); }
     float *centres() const { return Wt() + (size_t)(K + G) * C; }
 };
-int vlad_stage_input(Ctx *c, const float *fmap, int32_t positions, int32_t layout);   // the map -> Vlad::x (N x C), enqueued on s_append
-int vlad_chunk(Ctx *c);                                       // the staged map -> row 0 of stage_dev (directly, or through project_chunk), on s_append
+int vlad_chunk(Ctx *c, const AppendSrc &src, int64_t from, int64_t m);   // maps [from, from + m) -> rows 0 .. m-1 of stage_dev (directly, or through project_chunk), on s_append
 
 // kernels.hip
 int launch_resident(Ctx *c, hipStream_t s, const ResidentArgs &ra, int grid);   // CHIP_ERR_UNSUPPORTED in a build without the rows form

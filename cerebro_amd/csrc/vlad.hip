@@ -14,8 +14,11 @@
 //   vlad_reduce    : one workgroup per kept cluster: the chains over j, the centres, q_k by wave 0 (the project_finish idiom) -> V, A, U
 //   vlad_finish    : one workgroup, a launch of its own (U is complete at the kernel boundary): q, v as float32 into
 //                    Projection::x / chip_vlad's buffer, or (double)v into the append's staging buffer
+// Every launch serves a GROUP of maps of one shape (the batched calls; a single call is a group of one): the positions of the group lie one
+// map after the other, vlad_assign walks them all, the others take their map from a grid axis -- the 64-position blocks of the definition
+// are per map and never straddle two.
 // The host side owns the ctx's weights and scratch (Vlad, chip_internal.h) and the calls that need nothing of the DB; the pooled append
-// is ctx_append with a third kind of source (chip_api.hip append_pass), which comes back here through vlad_stage_input / vlad_chunk.
+// is ctx_append with a third kind of source (chip_api.hip append_pass), which comes back here through vlad_chunk.
 #include "chip_internal.h"
 #include <cmath>
 #include <cstring>
@@ -29,7 +32,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x2 __attribute__((ext_vector_type(2)));
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
-struct VladArgs {            // wave-uniform
+struct VladArgs {            // wave-uniform; the arrays of a group's maps lie one after the other
     const float *x;          // N x C
     const float *Wt;         // (K+G) x C
     const double *bias;      // K+G
@@ -41,7 +44,8 @@ struct VladArgs {            // wave-uniform
     double *U;               // K x C
     double *A;               // K
     uint32_t *flag;          // bit1 (2u) is raised by a non-finite score: the append's flag word, or chip_vlad's own
-    int32_t N, C, K, KG, blocks;
+    int32_t N, C, K, KG, blocks;   // positions and 64-position blocks of ONE map
+    int32_t maps;
 };
 
 constexpr int kVladAssignBlock = 256;   // four positions per workgroup
@@ -81,10 +85,12 @@ __device__ __forceinline__ double vlad_exp(double t)
     return p * __builtin_bit_cast(double, bits);
 }
 
-// x[c][n] (C x N) -> y[n][c] (N x C): 32 x 32 tiles, the LDS rows padded by one float
+// x[c][n] (C x N) -> y[n][c] (N x C) of map blockIdx.z: 32 x 32 tiles, the LDS rows padded by one float
 __global__ __launch_bounds__(256) void vlad_transpose(const float *x, float *y, int32_t N, int32_t C)
 {
     __shared__ float tile[32][33];
+    x += (size_t)blockIdx.z * N * C;
+    y += (size_t)blockIdx.z * N * C;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int n0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
 #pragma unroll
@@ -109,7 +115,8 @@ __global__ __launch_bounds__(kVladAssignBlock) void vlad_assign(VladArgs p)
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int waves = kVladAssignBlock / 64;
     const bool h0 = lane < p.KG, h1 = lane + 64 < p.KG;
-    for (int n = blockIdx.x * waves + wave; n < p.N; n += (int)gridDim.x * waves) {
+    const int total = p.N * p.maps;   // a score is per position: the group's maps are walked as one
+    for (int n = blockIdx.x * waves + wave; n < total; n += (int)gridDim.x * waves) {
         f32x4 xv[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) {
@@ -168,12 +175,13 @@ __global__ __launch_bounds__(kVladAssignBlock) void vlad_assign(VladArgs p)
     }
 }
 
-// P_j[k][c] and S_j[k] of position block j = blockIdx.x for channel blockIdx.y * 64 + lane and clusters blockIdx.z * 8 .. + 7 (k < K:
+// P_j[k][c] and S_j[k] of position block j = blockIdx.x % blocks of map blockIdx.x / blocks for channel blockIdx.y * 64 + lane and clusters blockIdx.z * 8 .. + 7 (k < K:
 // ghost rows are never formed): acc = acc + (a[n][k] * (double)x[n][c]), product rounded, sum rounded, n ascending from 0.0.
 __global__ __launch_bounds__(64) void vlad_aggregate(VladArgs p)
 {
-    const int j = blockIdx.x, c = blockIdx.y * 64 + (int)threadIdx.x, k0 = blockIdx.z * kVladKT;
-    const int n0 = j * CHIP_VLAD_BLOCK, n1 = n0 + CHIP_VLAD_BLOCK < p.N ? n0 + CHIP_VLAD_BLOCK : p.N;
+    const int j = blockIdx.x, c = blockIdx.y * 64 + (int)threadIdx.x, k0 = blockIdx.z * kVladKT;   // j counts the blocks of all maps: P, S
+    const int map = j / p.blocks, first = map * p.N, last = first + p.N;                             // are indexed by it as they are
+    const int n0 = first + (j - map * p.blocks) * CHIP_VLAD_BLOCK, n1 = n0 + CHIP_VLAD_BLOCK < last ? n0 + CHIP_VLAD_BLOCK : last;
     const bool live = c < p.C, sums = blockIdx.y == 0;
     // the block's assignments of these eight clusters, staged once (4 KiB; a cluster past K or a position past the block reads 0.0 and
     // is never stored): the walk below is then bound by its 64 dependent additions, not by 64 trips to the L2
@@ -221,13 +229,19 @@ __global__ __launch_bounds__(64) void vlad_aggregate(VladArgs p)
     }
 }
 
-// Cluster k = blockIdx.x: V[k][c] and A[k] (the chains over j), Wv = V + (A * (double)centres), q_k = orc_dot_tree_f64(Wv, Wv, C) by
+// Cluster k = blockIdx.x of map blockIdx.y: V[k][c] and A[k] (the chains over j), Wv = V + (A * (double)centres), q_k = orc_dot_tree_f64(Wv, Wv, C) by
 // wave 0 (lane L: elements base + 2L + c, base in steps of 128; C % 4 == 0), U = Wv / sqrt(q_k > 1e-12 ? q_k : 1e-12).
 __global__ __launch_bounds__(kVladReduceBlock) void vlad_reduce(VladArgs p)
 {
     __shared__ double wv[1024];
     __shared__ double s_q;
     const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const size_t KC = (size_t)p.K * p.C;
+    p.P += (size_t)blockIdx.y * p.blocks * KC;
+    p.S += (size_t)blockIdx.y * p.blocks * p.K;
+    p.V += (size_t)blockIdx.y * KC;
+    p.U += (size_t)blockIdx.y * KC;
+    p.A += (size_t)blockIdx.y * p.K;
     double A = 0.0;
     for (int j = 0; j < p.blocks; j++) A = A + p.S[(size_t)j * p.K + k];
     if (tid == 0) p.A[k] = A;
@@ -258,11 +272,15 @@ __global__ __launch_bounds__(kVladReduceBlock) void vlad_reduce(VladArgs p)
 }
 
 // q = orc_dot_tree_f64(U, U, n) over the k-major flattening by wave 0, v = (float)(U / sqrt(q > 1e-12 ? q : 1e-12)); the vector goes out
-// as float32 (vf) and / or as the doubles the append's staging buffer holds (vd), whichever is not null.
+// as float32 (vf) and / or as the doubles the append's staging buffer holds (vd), whichever is not null.  One workgroup per map of the
+// group: U, vf and vd of map blockIdx.x are n elements further on.
 __global__ __launch_bounds__(kVladFinishBlock) void vlad_finish(const double *U, float *vf, double *vd, int32_t n)
 {
     __shared__ double s_q;
     const int tid = threadIdx.x, lane = tid & 63;
+    U += (size_t)blockIdx.x * n;
+    if (vf) vf += (size_t)blockIdx.x * n;
+    if (vd) vd += (size_t)blockIdx.x * n;
     if (tid < 64) {
         double acc = 0.0;
         constexpr int UF = 16;   // 1-KiB wave loads in flight: the chain is 2 n / 128 fmas long, the trips to the L2 are what it waits for
@@ -301,45 +319,41 @@ static bool vlad_limits_ok(int32_t C, int32_t K, int32_t G)
     return (K + G) * C <= 32768 && K * C <= CHIP_PROJ_MAX_IN_DIM;
 }
 
-// The map of one call -> Vlad::x as N x C (the append lock is held).  fmap: host memory, or device memory of the ctx's device.
-int vlad_stage_input(Ctx *c, const float *fmap, int32_t N, int32_t layout)
+// A group: as many maps as keep its positions <= 32768, at least 1 and at most 16.  The scratch is sized for one group, and a group
+// costs the launches one map costs.
+static int vlad_group_maps(int32_t N)
 {
-    Vlad &v = c->vlad;
-    const size_t count = (size_t)N * v.C;
-    int rc = v.x.reserve(c, count);
-    if (rc != CHIP_OK) return rc;
-    v.last_n = 0;
-    if (layout == CHIP_VLAD_NHWC) {
-        CHIP_HIP(c, hipMemcpyAsync(v.x, fmap, count * sizeof(float), hipMemcpyDefault, c->s_append));
-    } else {
-        rc = v.raw.reserve(c, count);
-        if (rc != CHIP_OK) return rc;
-        CHIP_HIP(c, hipMemcpyAsync(v.raw, fmap, count * sizeof(float), hipMemcpyDefault, c->s_append));
-        hipLaunchKernelGGL(vlad_transpose, dim3((N + 31) / 32, (v.C + 31) / 32), dim3(256), 0, c->s_append, (const float *)v.raw.get(), v.x.get(), N, v.C);
-        CHIP_HIP(c, hipGetLastError());
-    }
-    v.last_n = -N;   // staged, not pooled yet
-    return CHIP_OK;
+    const int g = 32768 / N;
+    return g < 1 ? 1 : g > 16 ? 16 : g;
 }
 
-// The staged map pooled: v as float32 into vf and / or as doubles into vd; a non-finite score raises bit1 of *flag.  Four launches on
-// s_append.  Every caller holds a ResidentPause, and this is the argument for it.  vlad_assign (256 threads, no LDS), vlad_aggregate (64
+// `maps` maps of N positions each, one after the other in `layout` at fmaps (host memory, or device memory of the ctx's device) -> Vlad::x
+// as maps x N x C, then pooled: map m's v as float32 into vf + m * K*C and / or as doubles into vd + m * K*C; a non-finite score raises
+// bit1 of *flag.  The append lock is held.  A copy (NCHW: and the transposing launch), then four launches on s_append.
+// Every caller holds a ResidentPause, and this is the argument for it.  vlad_assign (256 threads, no LDS), vlad_aggregate (64
 // threads, 4 KiB) and vlad_reduce (256 threads, 8 KiB) would find room beside the resident scan instance's one workgroup per CU on any CU
 // with four free wave slots and their registers -- but that is a statement about the instance's register allocation, which this file
 // does not own, and vlad_finish is a 1024-thread workgroup, which has no room beside another of that size.  A launch that cannot be
 // placed waits for as long as ticks renew the instance's lease (project.hip project_chunk), so the pooling does not clearly fit and
 // pauses: correctness first.  The route through a projection pauses for project_rows anyway.
-static int vlad_pool(Ctx *c, float *vf, double *vd, uint32_t *flag)
+static int vlad_group(Ctx *c, const float *fmaps, int maps, int32_t N, int32_t layout, float *vf, double *vd, uint32_t *flag)
 {
     Vlad &v = c->vlad;
-    if (v.last_n == 0) return CHIP_ERR_BUSY;   // nothing staged
-    const int N = v.last_n < 0 ? -v.last_n : v.last_n;
     const int KG = v.K + v.G, blocks = (N + CHIP_VLAD_BLOCK - 1) / CHIP_VLAD_BLOCK;
-    const size_t KC = (size_t)v.K * v.C;
-    int rc = v.a.reserve(c, (size_t)N * KG);
-    if (rc == CHIP_OK) rc = v.part.reserve(c, (size_t)blocks * (KC + v.K));
-    if (rc == CHIP_OK) rc = v.vu.reserve(c, 2 * KC + v.K);
+    const size_t KC = (size_t)v.K * v.C, count = (size_t)maps * N * v.C;
+    v.last_n = 0;
+    int rc = v.x.reserve(c, count);
+    if (rc == CHIP_OK && layout != CHIP_VLAD_NHWC) rc = v.raw.reserve(c, count);
+    if (rc == CHIP_OK) rc = v.a.reserve(c, (size_t)maps * N * KG);
+    if (rc == CHIP_OK) rc = v.part.reserve(c, (size_t)maps * blocks * (KC + v.K));
+    if (rc == CHIP_OK) rc = v.vu.reserve(c, (size_t)maps * (2 * KC + v.K));
     if (rc != CHIP_OK) return rc;
+    if (layout == CHIP_VLAD_NHWC) {
+        CHIP_HIP(c, hipMemcpyAsync(v.x, fmaps, count * sizeof(float), hipMemcpyDefault, c->s_append));
+    } else {
+        CHIP_HIP(c, hipMemcpyAsync(v.raw, fmaps, count * sizeof(float), hipMemcpyDefault, c->s_append));
+        hipLaunchKernelGGL(vlad_transpose, dim3((N + 31) / 32, (v.C + 31) / 32, maps), dim3(256), 0, c->s_append, (const float *)v.raw.get(), v.x.get(), N, v.C);
+    }
     VladArgs p;
     p.x = v.x;
     p.Wt = v.Wt();
@@ -347,40 +361,54 @@ static int vlad_pool(Ctx *c, float *vf, double *vd, uint32_t *flag)
     p.centres = v.centres();
     p.a = v.a;
     p.P = v.part;
-    p.S = v.part + (size_t)blocks * KC;
+    p.S = v.part + (size_t)maps * blocks * KC;
     p.V = v.vu;
-    p.U = v.vu + KC;
-    p.A = v.vu + 2 * KC;
+    p.U = v.vu + (size_t)maps * KC;
+    p.A = v.vu + 2 * (size_t)maps * KC;
     p.flag = flag;
     p.N = N;
     p.C = v.C;
     p.K = v.K;
     p.KG = KG;
     p.blocks = blocks;
+    p.maps = maps;
     const int waves = kVladAssignBlock / 64;
-    int grid = (N + waves - 1) / waves;
+    int grid = (maps * N + waves - 1) / waves;
     if (grid > c->n_cus * 8) grid = c->n_cus * 8;
     hipLaunchKernelGGL(vlad_assign, dim3(grid), dim3(kVladAssignBlock), 0, c->s_append, p);
-    hipLaunchKernelGGL(vlad_aggregate, dim3(blocks, (v.C + 63) / 64, (v.K + kVladKT - 1) / kVladKT), dim3(64), 0, c->s_append, p);
-    hipLaunchKernelGGL(vlad_reduce, dim3(v.K), dim3(kVladReduceBlock), 0, c->s_append, p);
-    hipLaunchKernelGGL(vlad_finish, dim3(1), dim3(kVladFinishBlock), 0, c->s_append, (const double *)p.U, vf, vd, (int32_t)KC);
+    hipLaunchKernelGGL(vlad_aggregate, dim3(maps * blocks, (v.C + 63) / 64, (v.K + kVladKT - 1) / kVladKT), dim3(64), 0, c->s_append, p);
+    hipLaunchKernelGGL(vlad_reduce, dim3(v.K, maps), dim3(kVladReduceBlock), 0, c->s_append, p);
+    hipLaunchKernelGGL(vlad_finish, dim3(maps), dim3(kVladFinishBlock), 0, c->s_append, (const double *)p.U, vf, vd, (int32_t)KC);
     CHIP_HIP(c, hipGetLastError());
     v.last_n = N;
+    v.last_maps = maps;
     return CHIP_OK;
 }
 
-// The staged map -> row 0 of stage_dev (append_pass; ctx_append has checked the shapes and holds the pause).  With a projection the
-// pooled vector is written where project_stage_input would have put it and the call goes on as the projected append does; without
-// one the last kernel writes (double)v into the staging buffer.  The flag word is the append's own: store_rows reads it next.
-int vlad_chunk(Ctx *c)
+// Maps [from, from + m) of a pooled append -> rows 0 .. m-1 of stage_dev (append_pass; ctx_append has checked the shapes and holds the
+// pause), group by group.  With a projection the pooled vectors are written where project_stage_input would have put them -- the chunk's
+// own m descriptors, from 0 -- and the chunk goes on as the projected append does, its groups sharing the passes over the matrix;
+// without one the last kernel writes (double)v into the staging buffer.  The flag word is the append's own: store_rows reads it next.
+// The maps are read from the caller's memory here, so a call that is run twice (an empty undecided DB that becomes a double-row DB)
+// copies them twice.
+int vlad_chunk(Ctx *c, const AppendSrc &src, int64_t from, int64_t m)
 {
     Vlad &v = c->vlad;
-    if (c->proj.in_dim) {
-        int rc = c->proj.x.reserve(c, (size_t)v.K * v.C);
-        if (rc == CHIP_OK) rc = vlad_pool(c, c->proj.x, nullptr, c->flags_dev);
-        return rc == CHIP_OK ? project_chunk(c, 0, 1) : rc;
+    const size_t KC = (size_t)v.K * v.C, map_elems = (size_t)src.positions * v.C;
+    const bool through = c->proj.in_dim != 0;
+    if (through) {
+        const int rc = c->proj.x.reserve(c, (size_t)m * KC);
+        if (rc != CHIP_OK) return rc;
     }
-    return vlad_pool(c, nullptr, reinterpret_cast<double *>(c->stage_dev.get()), c->flags_dev);
+    double *stage = reinterpret_cast<double *>(c->stage_dev.get());
+    const int gmax = vlad_group_maps(src.positions);
+    for (int64_t i = 0; i < m; i += gmax) {
+        const int g = (int)(m - i < gmax ? m - i : gmax);
+        const int rc = vlad_group(c, src.fmap + (size_t)(from + i) * map_elems, g, src.positions, src.layout,
+                                  through ? c->proj.x + (size_t)i * KC : nullptr, through ? nullptr : stage + (size_t)i * KC, c->flags_dev);
+        if (rc != CHIP_OK) return rc;
+    }
+    return through ? project_chunk(c, 0, m) : CHIP_OK;
 }
 
 static int check_poolable(const Ctx *c) { return (c->group || c->nranks > 1) ? CHIP_ERR_UNSUPPORTED : CHIP_OK; }
@@ -467,33 +495,46 @@ int chip_vlad_info(const chip_ctx *cc, int32_t *channels, int32_t *clusters, int
     return CHIP_OK;
 }
 
-int chip_vlad(chip_ctx *c, const float *fmap, int32_t positions, int32_t layout, float *out)
+int chip_vlad_batch(chip_ctx *c, const float *fmaps, int32_t n_maps, int32_t positions, int32_t layout, float *out)
 {
-    if (!c || !fmap || !out) return CHIP_ERR_INVALID_ARG;
+    if (!c || !fmaps || !out || n_maps < 0) return CHIP_ERR_INVALID_ARG;
     if (positions < 1 || positions > CHIP_VLAD_MAX_POSITIONS || (layout != CHIP_VLAD_NHWC && layout != CHIP_VLAD_NCHW)) return CHIP_ERR_UNSUPPORTED;
     int rc = check_poolable(c);
     if (rc != CHIP_OK) return rc;
     std::lock_guard<std::mutex> alk(c->append_mu);
     Vlad &v = c->vlad;
     if (!v.C) return CHIP_ERR_BUSY;
+    if (n_maps == 0) return CHIP_OK;
     CHIP_HIP(c, hipSetDevice(c->device));
-    ResidentPause paused(c);   // vlad_pool says why
-    const size_t KC = (size_t)v.K * v.C;
-    rc = v.out.reserve(c, KC + 1);
-    if (rc == CHIP_OK) rc = vlad_stage_input(c, fmap, positions, layout);
+    ResidentPause paused(c);   // vlad_group says why
+    const size_t KC = (size_t)v.K * v.C, map_elems = (size_t)positions * v.C;
+    const int gmax = vlad_group_maps(positions), g0 = n_maps < gmax ? n_maps : gmax;
+    rc = v.out.reserve(c, (size_t)g0 * KC + 1);   // a group's vectors and the flag word behind them
     if (rc != CHIP_OK) return rc;
-    uint32_t *flag = reinterpret_cast<uint32_t *>(v.out.get() + KC);
+    uint32_t *flag = reinterpret_cast<uint32_t *>(v.out.get() + (size_t)g0 * KC);
     CHIP_HIP(c, hipMemsetAsync(flag, 0, sizeof(uint32_t), c->s_append));
-    rc = vlad_pool(c, v.out, nullptr, flag);
-    if (rc != CHIP_OK) return rc;
-    std::vector<float> host(KC + 1);   // the vector and the flag word behind it: one copy
-    CHIP_HIP(c, hipMemcpyAsync(host.data(), v.out, (KC + 1) * sizeof(float), hipMemcpyDeviceToHost, c->s_append));
+    std::vector<float> host((size_t)n_maps * KC + 1);   // v is written only once every map is known to be finite
+    for (int i = 0; i < n_maps; i += gmax) {
+        const int g = n_maps - i < gmax ? n_maps - i : gmax;
+        rc = vlad_group(c, fmaps + (size_t)i * map_elems, g, positions, layout, v.out, nullptr, flag);
+        if (rc != CHIP_OK) return rc;
+        // the last group of full size takes the flag word along: a call of one group is one copy
+        const bool with_flag = i + g == n_maps && g == g0;
+        CHIP_HIP(c, hipMemcpyAsync(host.data() + (size_t)i * KC, v.out, ((size_t)g * KC + (with_flag ? 1 : 0)) * sizeof(float), hipMemcpyDeviceToHost, c->s_append));
+        if (i + g == n_maps && !with_flag)
+            CHIP_HIP(c, hipMemcpyAsync(host.data() + (size_t)n_maps * KC, flag, sizeof(float), hipMemcpyDeviceToHost, c->s_append));
+    }
     CHIP_HIP(c, hipStreamSynchronize(c->s_append));
     uint32_t bad;
-    std::memcpy(&bad, &host[KC], sizeof bad);
+    std::memcpy(&bad, &host[(size_t)n_maps * KC], sizeof bad);
     if (bad & 2u) return CHIP_ERR_NONFINITE;
-    std::memcpy(out, host.data(), KC * sizeof(float));
+    std::memcpy(out, host.data(), (size_t)n_maps * KC * sizeof(float));
     return CHIP_OK;
+}
+
+int chip_vlad(chip_ctx *c, const float *fmap, int32_t positions, int32_t layout, float *out)
+{
+    return chip_vlad_batch(c, fmap, 1, positions, layout, out);
 }
 
 int chip_debug_vlad_stage(chip_ctx *c, double *a, double *V, double *A)
@@ -505,10 +546,10 @@ int chip_debug_vlad_stage(chip_ctx *c, double *a, double *V, double *A)
     Vlad &v = c->vlad;
     if (!v.C || v.last_n <= 0) return CHIP_ERR_BUSY;
     CHIP_HIP(c, hipSetDevice(c->device));
-    const size_t KC = (size_t)v.K * v.C;
-    if (a) CHIP_HIP(c, hipMemcpyAsync(a, v.a, (size_t)v.last_n * (v.K + v.G) * sizeof(double), hipMemcpyDeviceToHost, c->s_append));
-    if (V) CHIP_HIP(c, hipMemcpyAsync(V, v.vu, KC * sizeof(double), hipMemcpyDeviceToHost, c->s_append));
-    if (A) CHIP_HIP(c, hipMemcpyAsync(A, v.vu + 2 * KC, (size_t)v.K * sizeof(double), hipMemcpyDeviceToHost, c->s_append));
+    const size_t KC = (size_t)v.K * v.C, an = (size_t)v.last_n * (v.K + v.G), m = (size_t)v.last_maps - 1;   // the last map of the last group
+    if (a) CHIP_HIP(c, hipMemcpyAsync(a, v.a + m * an, an * sizeof(double), hipMemcpyDeviceToHost, c->s_append));
+    if (V) CHIP_HIP(c, hipMemcpyAsync(V, v.vu + m * KC, KC * sizeof(double), hipMemcpyDeviceToHost, c->s_append));
+    if (A) CHIP_HIP(c, hipMemcpyAsync(A, v.vu + 2 * (m + 1) * KC + m * v.K, (size_t)v.K * sizeof(double), hipMemcpyDeviceToHost, c->s_append));
     CHIP_HIP(c, hipStreamSynchronize(c->s_append));
     return CHIP_OK;
 }

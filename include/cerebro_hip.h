@@ -205,7 +205,8 @@ int chip_db_append_synthetic_unit(chip_ctx *ctx, int64_t n, uint64_t seed,
  *     before the old one goes, so both exist for the duration of the call and CHIP_ERR_OOM leaves the earlier projection in place.
  *   - chip_project_info: in_dim 0 and matrix_type 0 when none is set; any output pointer may be NULL.
  *   - chip_project: the definition made callable (the reference also keeps the descriptor in its DataNode and its state.json):
- *     n raw descriptors -> z, n x D doubles in host memory.  One pass over the matrix per descriptor.
+ *     n raw descriptors -> z, n x D doubles in host memory.  One pass over the matrix per descriptor, or per group of descriptors
+ *     where n > 1 ("batched ingest" below): the same bits either way.
  *   - chip_db_append_projected_f32 is chip_db_append_f64 with the rows made on the device: every rule of that call holds (validation,
  *     the storage type decided by an empty undecided DB -- which becomes a double-row DB --, CHIP_ERR_NOT_F32 on a float-row DB with
  *     nothing appended, CHIP_APPEND_ALLOW_ROUNDING, lossy_rows, row_norm_max, publication when the rows are resident), and the DB
@@ -298,6 +299,58 @@ int chip_vlad_info(const chip_ctx *ctx, int32_t *channels, int32_t *clusters, in
 int chip_vlad(chip_ctx *ctx, const float *fmap, int32_t positions, int32_t layout, float *v /* clusters*channels, host */);
 int chip_db_append_vlad_f32(chip_ctx *ctx, const float *fmap, int32_t positions, int32_t layout, uint32_t flags, int64_t *first_index);
 int chip_debug_vlad_stage(chip_ctx *ctx, double *a /* N x (K+G) */, double *V /* K x C */, double *A /* K */);
+
+/* ------------------------------------------------------------------------------------------ batched ingest
+ * (ABI 7, additive.)  The two sections above make one DB row per call.  A map rebuilt from a recorded run, a server that takes keyframes
+ * from several agents, a trunk that runs at batch B hand over many at once; these entries take them in one call.  Nothing of the
+ * definitions changes: every row has the bits the single call gives for it.
+ *
+ * Several descriptors per pass over the matrix.  chip_project and chip_db_append_projected_f32 with n > 1 walk their descriptors in
+ * groups of `width`; a group shares ONE pass over the matrix (kernel project_pass: per output row and descriptor the accumulation order of
+ * the definition, so the bits of n single calls), a group of one is the single launch it always was.  The matrix is read
+ * ceil(n / width) times instead of n (per staging-sized chunk of rows, 64 MiB of doubles, where n is larger than that).
+ *   - chip_project_plan: what a call over n descriptors launches, without a ctx or a device, from the function the launch sizes itself
+ *     with: width; passes = ceil(n / width) reads of the matrix, of which shared_passes are project_pass launches and single_launches
+ *     (0 or 1: a trailing group of one; n == 1) the single kernel; slab, the elements of x per descriptor the shared pass keeps in the LDS
+ *     at a time (twice over: the next slab is loaded while this one is used), a whole number of 1-KiB chunks of a matrix row;
+ *     lds_bytes and block of the shared pass; single_lds_bytes of the single launch.  A NULL out or n < 0 CHIP_ERR_INVALID_ARG; in_dim
+ *     or matrix_type outside chip_project_set's limits CHIP_ERR_UNSUPPORTED.
+ *   - chip_debug_project_last: what the ctx's last projecting call (chip_project, chip_db_append_projected_f32, a pooled append through
+ *     a projection) launched, counted apart: passes[0] shared passes and passes[1] single launches, descriptors[0] and descriptors[1] the
+ *     descriptors each kind served; width as chip_project_plan has it.  Any pointer may be NULL.  A call that was run twice (an empty
+ *     undecided DB that became a double-row DB) reports its second run.
+ *
+ * Several maps per call.  Map m starts at fmaps + m * positions * C, each in `layout`: a torch [B, H, W, C] (CHIP_VLAD_NHWC) or
+ * [B, C, H, W] (CHIP_VLAD_NCHW) tensor's data_ptr(), or host memory.
+ *   - chip_vlad_batch: row m of v is chip_vlad(map m), n_maps x K*C floats in host memory.
+ *   - chip_db_append_vlad_batch_f32 is ONE append of n_maps rows: row m is byte for byte what chip_db_append_vlad_f32(map m) would
+ *     have appended at that place, directly or through the projection -- there the pooled vectors of a group go where
+ *     chip_db_append_projected_f32 stages its input, and share the matrix passes above.  Every rule of the single calls holds
+ *     (CHIP_APPEND_ALLOW_ROUNDING, the storage-type decision, row_norm_max, lossy_rows, publication when all rows are resident, the pause
+ *     of the resident scan instance).  A non-finite score in ANY map refuses the whole call with CHIP_ERR_NONFINITE: nothing is appended,
+ *     v is not written.
+ *   - The library walks the maps in groups: as many maps as keep the group's positions <= 32768, at least 1 and at most 16; its scratch
+ *     is sized for one group, and a group costs the launches one map costs.  The 64-position blocks of the definition are per map.
+ *   - After a batched call chip_debug_vlad_stage reads the stages of the call's LAST map.  The single calls are batches of one.
+ * Status, in this order: a NULL ctx / fmaps / v or n_maps < 0 CHIP_ERR_INVALID_ARG; positions or layout outside chip_vlad's limits
+ * CHIP_ERR_UNSUPPORTED (both before the ctx is touched); a chip_create_multi or sharded ctx CHIP_ERR_UNSUPPORTED; no weights set
+ * CHIP_ERR_BUSY; K*C against D / in_dim CHIP_ERR_UNSUPPORTED (the append); n_maps == 0 CHIP_OK (first_index is filled).          */
+typedef struct chip_project_plan_out {
+    int32_t width;             /* descriptors one shared pass serves                                          */
+    int32_t slab;              /* elements of x per descriptor and slab                                       */
+    int32_t lds_bytes;         /* dynamic LDS of a shared pass: 2 slabs x width descriptors x slab x 4 bytes  */
+    int32_t single_lds_bytes;  /* dynamic LDS of a single launch: in_dim x 4 bytes                            */
+    int32_t block;             /* threads per workgroup, both kernels                                         */
+    int32_t reserved;
+    int64_t passes;            /* reads of the matrix: shared_passes + single_launches                        */
+    int64_t shared_passes;
+    int64_t single_launches;
+} chip_project_plan_out;
+int chip_project_plan(int32_t in_dim, int32_t matrix_type, int64_t n, chip_project_plan_out *out);
+int chip_debug_project_last(chip_ctx *ctx, int64_t passes[2], int64_t descriptors[2], int32_t *width);
+int chip_vlad_batch(chip_ctx *ctx, const float *fmaps, int32_t n_maps, int32_t positions, int32_t layout, float *v /* n_maps x clusters*channels, host */);
+int chip_db_append_vlad_batch_f32(chip_ctx *ctx, const float *fmaps, int32_t n_maps, int32_t positions, int32_t layout, uint32_t flags,
+                                  int64_t *first_index);
 
 /* ------------------------------------------------------------------------------------------ scan + top-k
  * Replaces  u = v.transpose() * M.leftCols(k); maxCoeff(); last-index argmax  (src/Cerebro.cpp:1026-1043)

@@ -20,7 +20,7 @@ ORC_SRCS   := $(wildcard oracle/*.c)
 all: lib oracle host testlibs verify ref ref_modes
 lib: $(LIBDIR)/libcerebro_hip.so
 oracle: oracle/_build/liboracle.so oracle/_build/liboracle_eispack.so oracle/_build/liboracle_stats.so oracle/_build/liboracle_flops.so
-host: $(LIBDIR)/libcerebro_host.so $(LIBDIR)/cerebro_replay $(LIBDIR)/minimal_loop_detector $(LIBDIR)/sync_tick_latency $(LIBDIR)/verify_candidate $(LIBDIR)/verify_candidates $(LIBDIR)/verify_candidates_stored $(LIBDIR)/verify_candidates_composed $(LIBDIR)/verify_candidates_modes $(LIBDIR)/verify_pairs_stored $(LIBDIR)/frame_put_disparity $(LIBDIR)/frame_put_stereo $(LIBDIR)/orb_detect $(LIBDIR)/orb_frame_put $(LIBDIR)/frame_put_raw_stereo $(LIBDIR)/append_projected $(LIBDIR)/append_vlad $(LIBDIR)/append_batch
+host: $(LIBDIR)/libcerebro_host.so $(LIBDIR)/cerebro_replay $(LIBDIR)/minimal_loop_detector $(LIBDIR)/sync_tick_latency $(LIBDIR)/verify_candidate $(LIBDIR)/verify_candidates $(LIBDIR)/verify_candidates_stored $(LIBDIR)/verify_candidates_composed $(LIBDIR)/verify_candidates_modes $(LIBDIR)/verify_pairs_stored $(LIBDIR)/frame_put_disparity $(LIBDIR)/frame_put_stereo $(LIBDIR)/orb_detect $(LIBDIR)/orb_frame_put $(LIBDIR)/frame_put_raw_stereo $(LIBDIR)/frame_put_batch $(LIBDIR)/append_projected $(LIBDIR)/append_vlad $(LIBDIR)/append_batch
 # test infrastructure that needs hipcc: the shared-memory stand-in for librccl (N ranks on one device, tests/test_fakerccl_gpu.py)
 testlibs: tests/fakerccl/_build/libfakerccl.so $(LIBDIR)/norows/libcerebro_hip.so $(LIBDIR)/hooks/libcerebro_hip.so
 # The TEST build of the library (-DCHIP_TEST_HOOKS): the fault-injection hooks (CHIP_TEST_COMM_INIT, CHIP_TEST_FAIL_SHARD,
@@ -29,7 +29,7 @@ testlibs: tests/fakerccl/_build/libfakerccl.so $(LIBDIR)/norows/libcerebro_hip.s
 # tests/ load this one for the tests that inject faults (cerebro_amd.capi.use_hooks_library).  Never deploy it.
 HOOK_SRCS  := chip_api resident chip_multi pnp
 HOOK_OBJS  := $(HOOK_SRCS:%=$(LIBDIR)/hooks/%.o)
-$(LIBDIR)/hooks/%.o: $(CSRC)/%.hip $(CSRC)/chip_internal.h $(CSRC)/frame_store.h $(CSRC)/ransac_common.h $(CSRC)/topk_merge.h include/cerebro_hip.h
+$(LIBDIR)/hooks/%.o: $(CSRC)/%.hip $(CSRC)/chip_internal.h $(CSRC)/frame_store.h $(CSRC)/ransac_common.h $(CSRC)/topk_merge.h $(wildcard $(CSRC)/*.inc) include/cerebro_hip.h
 	@mkdir -p $(LIBDIR)/hooks
 	$(HIPCC) $(HIPFLAGS) -DCHIP_TEST_HOOKS -c $< -o $@
 $(LIBDIR)/hooks/libcerebro_hip.so: $(HOOK_OBJS) $(HIP_OBJS)
@@ -44,7 +44,7 @@ tests/fakerccl/_build/libfakerccl.so: tests/fakerccl/fakerccl.cc
 	@mkdir -p tests/fakerccl/_build
 	$(HIPCC) -O2 -std=c++17 -fPIC -shared $< -o $@ -lrt -lpthread
 
-$(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC)/chip_internal.h $(CSRC)/frame_store.h $(CSRC)/ransac_common.h $(CSRC)/topk_merge.h include/cerebro_hip.h
+$(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC)/chip_internal.h $(CSRC)/frame_store.h $(CSRC)/ransac_common.h $(CSRC)/topk_merge.h $(wildcard $(CSRC)/*.inc) include/cerebro_hip.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -146,6 +146,11 @@ $(LIBDIR)/orb_frame_put: examples/orb_frame_put.cc $(LIBDIR)/libcerebro_host.so
 # device) and, next to it, from the pair a plain C++ restatement of the rectification makes of it: same bits
 $(LIBDIR)/frame_put_raw_stereo: examples/frame_put_raw_stereo.cc $(LIBDIR)/libcerebro_host.so
 	$(CXX) -O2 -std=c++17 -Wall -Wextra examples/frame_put_raw_stereo.cc -o $@ -L$(LIBDIR) -lcerebro_host -lcerebro_hip -Wl,-rpath,'$$ORIGIN' -lpthread
+
+# ---- the same backlog put twice: by ONE chip_frame_put_raw_orb_stereo_batch and by the loop of single puts -- same bits, same matches --
+# then read, dropped and put back from its records alone (chip_frame_put_records): the same matches again (with an argument, the times)
+$(LIBDIR)/frame_put_batch: examples/frame_put_batch.cc $(LIBDIR)/libcerebro_host.so
+	$(CXX) -O2 -std=c++17 -Wall -Wextra examples/frame_put_batch.cc -o $@ -L$(LIBDIR) -lcerebro_host -lcerebro_hip -Wl,-rpath,'$$ORIGIN' -lpthread
 
 # ---- the descriptor projection: a DB appended through chip_db_append_projected_f32 and, next to it, through a plain C++ restatement of
 # the definition and chip_db_append_f64: same rows, same ticks (and, with an argument, the time of both at 32768 -> 4096).

@@ -329,6 +329,14 @@ _SIGS = {
     "chip_rectify_pair": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
     "chip_frame_put_raw_orb_stereo": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.POINTER(OrbParams), C.POINTER(StereoBmParams), _P,
                                                 C.POINTER(C.c_int32)]),
+    "chip_build_has_frame_put_batch": (C.c_int, []),
+    "chip_frame_put_plan": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(OrbParams), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "chip_frame_put_orb_stereo_batch": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(OrbParams), C.POINTER(StereoBmParams), _P,
+                                                  _P]),
+    "chip_frame_put_raw_orb_stereo_batch": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(OrbParams),
+                                                      C.POINTER(StereoBmParams), _P, _P]),
+    "chip_frame_put_records": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
+    "chip_debug_frame_put_last": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "chip_build_has_project": (C.c_int, []),
     "chip_project_set": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P]),
     "chip_project_clear": (C.c_int, [_P]),
@@ -473,6 +481,16 @@ def rectify_quantize(map) -> np.ndarray:
     if rc != CHIP_OK:
         raise ChipError(rc, "chip_rectify_quantize")
     return q
+
+
+def frame_put_plan(width: int, height: int, F: int, params=None, raw: bool = False) -> dict:
+    """chip_frame_put_plan -> dict(group, n_groups): how a batched put of F pairs of this size is walked (no ctx, no device)"""
+    _, o = _orb_params(params)
+    g, n = C.c_int32(), C.c_int32()
+    rc = load_library().chip_frame_put_plan(width, height, o, int(raw), F, C.byref(g), C.byref(n))
+    if rc != CHIP_OK:
+        raise ChipError(rc, "chip_frame_put_plan")
+    return dict(group=g.value, n_groups=n.value)
 
 
 def orb_plan(width: int, height: int, params=None) -> list:
@@ -1455,6 +1473,52 @@ class Chip:
         self._chk(self.lib.chip_frame_put_raw_orb_stereo(self.h, id, l.shape[1], l.shape[0], _ptr(l), _ptr(r), o, b, _ptr(Qd), C.byref(n)),
                   "chip_frame_put_raw_orb_stereo")
         return n.value
+
+    def _frame_put_batch(self, fn, name: str, ids, lefts, rights, Q, orb, bm) -> list:
+        idv = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        F = len(idv)
+        if len(lefts) != F or len(rights) != F:
+            raise ValueError(f"{name}: as many left and right images as ids")
+        ls = [np.ascontiguousarray(a, dtype=np.uint8) for a in lefts]
+        rs = [np.ascontiguousarray(a, dtype=np.uint8) for a in rights]
+        shape = ls[0].shape if F else (0, 0)
+        assert all(a.ndim == 2 and a.shape == shape for a in ls + rs), "every image of a call has one (H, W)"
+        _, o = _orb_params(orb)
+        if isinstance(bm, dict):
+            bm = default_stereo_bm_params(**bm)
+        lp = (C.c_void_p * max(F, 1))(*[a.ctypes.data for a in ls])
+        rp = (C.c_void_p * max(F, 1))(*[a.ctypes.data for a in rs])
+        Qd = np.ascontiguousarray(Q, dtype=np.float64).reshape(16)
+        n = np.full(max(F, 1), -2, dtype=np.int32)
+        self._chk(fn(self.h, _ptr(idv) if F else None, F, shape[1], shape[0], lp, rp, o, None if bm is None else C.byref(bm), _ptr(Qd), _ptr(n)), name)
+        return [int(v) for v in n[:F]]
+
+    def frame_put_orb_stereo_batch(self, ids, lefts, rights, Q: np.ndarray, orb=None, bm=None) -> list:
+        """chip_frame_put_orb_stereo_batch: frame_put_orb_stereo for F rectified pairs of one rig in one call -- every stage one launch
+        per group of frames, one host wait per group -> the F kept counts.  The stored rows equal the single call's byte for byte"""
+        return self._frame_put_batch(self.lib.chip_frame_put_orb_stereo_batch, "chip_frame_put_orb_stereo_batch", ids, lefts, rights, Q, orb, bm)
+
+    def frame_put_raw_orb_stereo_batch(self, ids, lefts_raw, rights_raw, Q: np.ndarray, orb=None, bm=None) -> list:
+        """chip_frame_put_raw_orb_stereo_batch: the same with the cameras' raw pairs, rectified on the device through the ctx's maps"""
+        return self._frame_put_batch(self.lib.chip_frame_put_raw_orb_stereo_batch, "chip_frame_put_raw_orb_stereo_batch", ids, lefts_raw, rights_raw,
+                                     Q, orb, bm)
+
+    def frame_put_records(self, id: int, frame: dict):
+        """chip_frame_put_records: what frame_read gave -- dict(desc, kp, pts, width, height) -- back into the store under id: three
+        uploads, no kernel.  The fourth float of every record must be 0.0 or 1.0"""
+        desc = np.ascontiguousarray(frame["desc"], dtype=np.uint8).reshape(-1, CHIP_ORB_DESC_BYTES)
+        kp = np.ascontiguousarray(frame["kp"], dtype=np.float32).reshape(-1, 2)
+        pts = np.ascontiguousarray(frame["pts"], dtype=np.float32).reshape(-1, 4)
+        assert desc.shape[0] == kp.shape[0] == pts.shape[0]
+        keep = np.zeros(4, dtype=np.float32)                          # an empty frame still hands over three addresses
+        a = [_ptr(x) if x.size else _ptr(keep) for x in (desc, kp, pts)]
+        self._chk(self.lib.chip_frame_put_records(self.h, id, *a, kp.shape[0], int(frame["width"]), int(frame["height"])), "chip_frame_put_records")
+
+    def frame_put_last(self) -> dict:
+        """chip_debug_frame_put_last -> dict(groups, launches, waits) of the ctx's last batched put"""
+        v = [C.c_int32() for _ in range(3)]
+        self._chk(self.lib.chip_debug_frame_put_last(self.h, *[C.byref(x) for x in v]), "chip_debug_frame_put_last")
+        return dict(groups=v[0].value, launches=v[1].value, waits=v[2].value)
 
     def frame_drop(self, id: int):
         self._chk(self.lib.chip_frame_drop(self.h, id), "chip_frame_drop")

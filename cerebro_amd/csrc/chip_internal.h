@@ -650,6 +650,17 @@ int orb_check(int32_t width, int32_t height, const chip_orb_params *p, chip_orb_
 int orb_enqueue(Ctx *c, hipStream_t s, const uint8_t *image, const uint8_t *image_dev, int32_t width, int32_t height, const chip_orb_params &d,
                 bool describe, uint8_t *desc_dev, float2 *kp_dev, size_t back);
 int orb_finished(Ctx *c, bool describe, int32_t n_features, int32_t *total, int32_t level_counts[8]);
+// The batched put's half of the same (chip_frame_put_orb_stereo_batch): the G <= kFramePutGroup left images of pairs that lie in device
+// memory (pair f at pairs_dev + f * pair_stride), one launch per stage over all frames, descriptors and keypoints written straight into the
+// rows of slot[f] of the frame store (desc_base / kp_base: slot 0).  The kept counts stay on the device, frame f's eight int32 at
+// *out_dev + f * *out_stride; orb_batch_counts enqueues their one copy into pinned memory.  *launches grows by the launches made.
+constexpr int kFramePutGroup = 16;
+int orb_batch_enqueue(Ctx *c, hipStream_t s, const uint8_t *pairs_dev, size_t pair_stride, int32_t G, int32_t width, int32_t height,
+                      const chip_orb_params &d, uint8_t *desc_base, float2 *kp_base, int32_t slot_kp, const int32_t *slot, int32_t *launches,
+                      const uint8_t **out_dev, size_t *out_stride);
+int orb_batch_counts(Ctx *c, hipStream_t s, int32_t G, const int32_t **counts);
+// the scratch of a group of G frames, grown if it must (inside one pause); probe: allocates nothing and returns 1 if something would grow, else 0
+int orb_batch_reserve(Ctx *c, int32_t G, int32_t width, int32_t height, const chip_orb_params &d, bool probe);
 // the solvers on correspondence sets that already are in device memory (match.hip's sets): same kernels, same results as the
 // host-pointer entries chip_pnp_ransac / chip_icp_ransac; the caller has validated the arguments and holds match_mu
 int pnp_ransac_device(Ctx *c, const double *X_dev, const double *uv_dev, int32_t N, const chip_ransac_params *p, double *T_colmajor,

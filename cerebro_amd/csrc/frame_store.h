@@ -38,6 +38,7 @@ struct FrameStore {
     DevBuf<int2> rect_maps, remap_q;
     std::vector<int2> h_rect;                   // the maps on their way up
     int32_t rect_w = 0, rect_h = 0, rect_stages = 0;   // rect_stages == 0: no maps
+    int32_t last_groups = 0, last_launches = 0, last_waits = 0;   // what the last batched put did (chip_debug_frame_put_last)
 
     // slot k as a match or a read sees it: its rows and its frame (n == 0: an empty frame)
     struct Rows { const uint8_t *desc; const float2 *kp; const float4 *rec; int32_t n, w, h; };

@@ -12,13 +12,20 @@
 //                      the keypoint's pixel (bm_pixel: lane = disparity, v_sad_u8 on window rows read in place), lane 0 writes the record.
 //   bm_dense         : the same body at every pixel (chip_stereo_bm; the definition made callable, not a hot path).
 //   rectify_pair     : both eyes and both stages of the rectification in one launch, on maps the host has quantised to 1/32 pixel.
+//   fb_rectify, fb_prefilter, fb_keypoints : the batch entries of rectify_pair, bm_prefilter and bm_keypoints for the batched puts
+//                      (chip_frame_put_orb_stereo_batch, chip_frame_put_raw_orb_stereo_batch): the frame is a grid axis, the body is the
+//                      single kernel's (a __device__ function on the frame's bases; rectify_pair's an included text).  fb_keypoints reads each frame's kept count in
+//                      device memory and writes the records of its slot through a slot table in the arguments.
 //
 // The host side has ONE slot transaction (SlotPut) around per-source record writers: chip_frame_put, _disparity and _stereo upload the
 // caller's rows and state what they stage and which kernel writes the records (put_frame); the two ORB puts make the rows on the device
-// (put_orb_stereo).  The state is FrameStore (frame_store.h), guarded by match_mu; the dense calls and the rectification create it alone.
+// (put_orb_stereo; put_orb_stereo_batch: many pairs per call in groups of one launch per stage, chip_frame_put_records: the rows back from
+// a checkpoint).  The state is FrameStore (frame_store.h), guarded by match_mu; the dense calls and the rectification create it alone.
 // Nothing here rounds twice (-ffp-contract=off); tests/np_mirror_{frame_store,disparity,stereo_bm,rectify}.py restate it in numpy.
 #include "frame_store.h"
+#include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <new>
 
 namespace chip {
@@ -143,7 +150,9 @@ struct PrefilterArgs {
     uint8_t *pre;                 // 2 h x w
     int32_t w, h, quads, cap;     // quads: (w + 3) / 4 threads per row
 };
-__global__ __launch_bounds__(kBmThreads) void bm_prefilter(PrefilterArgs a)
+// One body per stage and two entries, as in orb.hip: the single call's kernel and the batched put's (fb_*), whose frame comes from the grid
+// and whose bases lie at frame x stride.
+__device__ __forceinline__ void prefilter_frame(const PrefilterArgs &a)
 {
     const size_t t = (size_t)blockIdx.x * kBmThreads + threadIdx.x;
     const size_t row = t / (size_t)a.quads;                          // of the pair
@@ -171,6 +180,16 @@ __global__ __launch_bounds__(kBmThreads) void bm_prefilter(PrefilterArgs a)
         return;
     }
     for (int k = 0; k < 4 && x0 + k < a.w; k++) a.pre[o + k] = (uint8_t)out[k];
+}
+__global__ __launch_bounds__(kBmThreads) void bm_prefilter(PrefilterArgs a) { prefilter_frame(a); }
+// the same grid x frames (blockIdx.y); both strides are multiples of 16 bytes
+struct PrefilterBatchArgs { PrefilterArgs a; size_t img_stride, pre_stride; };
+__global__ __launch_bounds__(kBmThreads) void fb_prefilter(PrefilterBatchArgs g)
+{
+    PrefilterArgs a = g.a;
+    a.img += blockIdx.y * g.img_stride;
+    a.pre += blockIdx.y * g.pre_stride;
+    prefilter_frame(a);
 }
 
 __device__ __forceinline__ bool bm_defined(int x, int y, int w, int h, const BmParams &b)
@@ -245,7 +264,7 @@ struct BmKeypointArgs {
     BmParams b;
     DispQ q;
 };
-__global__ __launch_bounds__(kBmThreads) void bm_keypoints(BmKeypointArgs g)
+__device__ __forceinline__ void keypoints_frame(const BmKeypointArgs &g)
 {
     const int i = blockIdx.x * kBmWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (i >= g.n) return;
@@ -258,6 +277,22 @@ __global__ __launch_bounds__(kBmThreads) void bm_keypoints(BmKeypointArgs g)
         r = make_float4(p.x, p.y, p.z, 1.0f);
     }
     if (lane == 0) g.rec[i] = r;
+}
+__global__ __launch_bounds__(kBmThreads) void bm_keypoints(BmKeypointArgs g) { keypoints_frame(g); }
+// The grid of the largest possible frame x frames (blockIdx.y).  kp / rec: the rows of slot 0 of the store, frame f has those of slot[f];
+// its keypoint count is the sum of the eight kept counts the detector left at out + f * out_stride, read here, so no count travels to the
+// host in mid-call.  A wave beyond the count leaves at once.
+struct BmKeypointBatchArgs { BmKeypointArgs a; const uint8_t *out; size_t pre_stride, out_stride; int32_t slot_kp; uint32_t slot[kFramePutGroup]; };
+__global__ __launch_bounds__(kBmThreads) void fb_keypoints(BmKeypointBatchArgs g)
+{
+    const size_t f = blockIdx.y, at = (size_t)g.slot[f] * (size_t)g.slot_kp;
+    const int32_t *counts = reinterpret_cast<const int32_t *>(g.out + f * g.out_stride);
+    BmKeypointArgs a = g.a;
+    a.n = 0;
+#pragma unroll
+    for (int l = 0; l < CHIP_ORB_MAX_LEVELS; l++) a.n += counts[l];
+    a.kp += at; a.rec += at; a.pre += f * g.pre_stride;
+    keypoints_frame(a);
 }
 
 // bm_dense: the same body at every pixel, one wave per pixel (the definition made callable: chip_stereo_bm; not a hot path)
@@ -310,44 +345,25 @@ struct RectifyArgs {
     const int2 *q;                // eyes x stages x h x w
     int32_t w, h, stages;
 };
+// the body is rectify_pair_body.inc (see there why it is text)
 __global__ __launch_bounds__(kRectThreads) void rectify_pair(RectifyArgs g)
 {
-    const int x0 = kRectPix * (int)(blockIdx.x * kRectLanes + (threadIdx.x & (kRectLanes - 1)));
-    const int y = (int)(blockIdx.y * kRectRows + threadIdx.x / kRectLanes);
-    if (x0 >= g.w || y >= g.h) return;
-    const size_t px = (size_t)g.w * g.h, eye = blockIdx.z;
-    const uint8_t *raw = g.raw + eye * px;
-    const int2 *q1 = g.q + eye * (size_t)g.stages * px, *q2 = q1 + px;
-    const size_t row = (size_t)y * g.w;
-    uint32_t out[kRectPix];
-#pragma unroll
-    for (int k = 0; k < kRectPix; k++) {
-        const int x = min(x0 + k, g.w - 1);                               // a tail repeats the row's last pixel and stores nothing of it
-        if (g.stages == 1) {
-            const int2 m = q1[row + x];
-            out[k] = (uint32_t)rect_sample(raw, g.w, g.h, m.x, m.y);
-            continue;
-        }
-        const int2 m = q2[row + x];
-        const int tx = m.x >> 5, a = m.x & 31, ty = m.y >> 5, b = m.y & 31;
-        int u[4];
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            const int ux = tx + (t & 1), uy = ty + (t >> 1);
-            u[t] = 0;
-            if ((unsigned)ux < (unsigned)g.w && (unsigned)uy < (unsigned)g.h) {
-                const int2 m1 = q1[(size_t)uy * g.w + ux];
-                u[t] = rect_sample(raw, g.w, g.h, m1.x, m1.y);
-            }
-        }
-        out[k] = (uint32_t)((u[0] * (32 - a) * (32 - b) + u[1] * a * (32 - b) + u[2] * (32 - a) * b + u[3] * a * b + 512) >> 10);
-    }
-    const size_t o = eye * px + row + (size_t)x0;                         // g.out is aligned: the offset decides
-    if (x0 + kRectPix <= g.w && (o & 3) == 0) {
-        *reinterpret_cast<uint32_t *>(g.out + o) = out[0] | out[1] << 8 | out[2] << 16 | out[3] << 24;
-        return;
-    }
-    for (int k = 0; k < kRectPix && x0 + k < g.w; k++) g.out[o + k] = (uint8_t)out[k];
+#define RECT_EYE blockIdx.z
+#define RECT_FRAME(p) (p)
+#include "rectify_pair_body.inc"
+#undef RECT_FRAME
+#undef RECT_EYE
+}
+// grid z = eye + 2 * frame: the pairs of all frames through the one set of maps; the stride (both pairs' alike) is a multiple of 16 bytes
+struct RectifyBatchArgs { RectifyArgs a; size_t stride; };
+__global__ __launch_bounds__(kRectThreads) void fb_rectify(RectifyBatchArgs batch)
+{
+    const RectifyArgs &g = batch.a;
+#define RECT_EYE (blockIdx.z & 1)
+#define RECT_FRAME(p) ((p) + (size_t)(blockIdx.z >> 1) * batch.stride)
+#include "rectify_pair_body.inc"
+#undef RECT_FRAME
+#undef RECT_EYE
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -397,13 +413,15 @@ struct SlotPut {
     int32_t k = -1;               // -1: the store is full
     bool replace = false;
     size_t at = 0;
-    SlotPut(FrameStore *store, int64_t frame_id) : fs(store), id(frame_id)
+    // cursor (the puts of one group, none of them committed yet): a new id takes the first free slot at or behind *cursor and moves it on
+    SlotPut(FrameStore *store, int64_t frame_id, int32_t *cursor = nullptr) : fs(store), id(frame_id)
     {
         const auto known = fs->slot_of.find(id);
         replace = known != fs->slot_of.end();
         if (replace) k = known->second;
-        for (int32_t j = 0; k < 0 && j < fs->n_slots; j++)
+        for (int32_t j = cursor ? *cursor : 0; k < 0 && j < fs->n_slots; j++)
             if (!fs->slots[(size_t)j].used) k = j;
+        if (cursor && !replace && k >= 0) *cursor = k + 1;
         if (k >= 0) at = (size_t)k * (size_t)fs->slot_kp;
     }
     void commit(int32_t n, int32_t w, int32_t h)
@@ -527,6 +545,145 @@ static int put_orb_stereo(chip_ctx *c, int64_t id, int32_t width, int32_t height
     }
     put.commit(total, width, height);
     *n = total;
+    return CHIP_OK;
+}
+
+// ---- the batched put: F pairs of one rig, walked in groups of put_group() frames -- ONE launch per stage and ONE wait per group
+static int32_t put_group(int32_t width, int32_t height)
+{
+    const size_t g = ((size_t)1 << 23) / ((size_t)width * (size_t)height);   // level-0 pixels of a group <= 2^23
+    return g < 1 ? 1 : g > (size_t)kFramePutGroup ? kFramePutGroup : (int32_t)g;
+}
+
+// the checks of the batched calls that need neither a ctx nor the pairs: F and the parameters
+static int put_batch_check(int32_t width, int32_t height, const chip_orb_params *orb, int32_t F, chip_orb_params *d)
+{
+    if (F < 1) return CHIP_ERR_INVALID_ARG;
+    if (F > CHIP_FRAME_MAX_PUT) return CHIP_ERR_UNSUPPORTED;
+    return orb_check(width, height, orb, d);
+}
+
+// A group of G frames in flight: pair f is staged at f * pair_stride (a multiple of 16 bytes: every frame's rows keep the alignment the
+// kernels' wide stores ask of frame 0), the raw pairs behind the places of all the rectified ones, the prefiltered pairs likewise at
+// f * pre_stride.  The detector's batch entries write the descriptor and keypoint rows of each frame's slot, fb_keypoints the records
+// from the kept counts it reads in device memory; the G x 8 counts come back in one copy in front of the one wait.
+static int put_orb_stereo_batch(chip_ctx *c, const int64_t *ids, int32_t F, int32_t width, int32_t height, const uint8_t *const *left,
+                                const uint8_t *const *right, const chip_orb_params *orb, const chip_stereo_bm_params *bm,
+                                const double Q_rowmajor[16], int32_t *n, bool raw)
+{
+    if (!c || !ids || !left || !right || !Q_rowmajor || !n || F < 1) return CHIP_ERR_INVALID_ARG;
+    {
+        std::vector<int64_t> sorted;
+        const int32_t look = F > CHIP_FRAME_MAX_PUT ? CHIP_FRAME_MAX_PUT : F;       // (a longer call is refused below whatever it holds)
+        try { sorted.assign(ids, ids + look); } catch (const std::bad_alloc &) { return CHIP_ERR_OOM; }
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return CHIP_ERR_INVALID_ARG;
+        for (int32_t f = 0; f < look; f++)
+            if (!left[f] || !right[f]) return CHIP_ERR_INVALID_ARG;
+    }
+    chip_orb_params d;
+    int rc = put_batch_check(width, height, orb, F, &d);
+    if (rc != CHIP_OK) return rc;
+    BmParams b;
+    rc = bm_params(bm, &b);
+    if (rc != CHIP_OK) return rc;
+    const DispQ q = disp_q(Q_rowmajor);
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    FrameStore *fs = c->frame_store;
+    if (fs && fs->n_slots > 0 && d.n_features > fs->slot_kp) return CHIP_ERR_UNSUPPORTED;   // a slot must hold whatever the detector keeps
+    if (!fs || fs->n_slots == 0) return CHIP_ERR_BUSY;
+    if (raw && fs->rect_stages == 0) return CHIP_ERR_BUSY;         // no maps
+    if (raw && (width != fs->rect_w || height != fs->rect_h)) return CHIP_ERR_INVALID_ARG;
+    int32_t fresh = 0;
+    for (int32_t f = 0; f < F; f++) fresh += fs->slot_of.find(ids[f]) == fs->slot_of.end();
+    if (fresh > fs->n_slots - fs->n_frames) return CHIP_ERR_OOM;   // all or nothing: the store is as it was
+    CHIP_HIP(c, hipSetDevice(c->device));
+    const int32_t group = put_group(width, height), widest = F < group ? F : group;
+    const size_t px = (size_t)width * height;
+    const size_t pair_stride = (2 * px + 15) & ~(size_t)15, pre_stride = (2 * px + kBmPad + 15) & ~(size_t)15;
+    const size_t stage_bytes = (raw ? 2 : 1) * (size_t)widest * pair_stride, pre_bytes = (size_t)widest * pre_stride;
+    {   // everything a group needs, the detector's scratch included, inside one pause
+        const bool grow = fs->stage.capacity() < stage_bytes || fs->bm_pre.capacity() < pre_bytes || orb_batch_reserve(c, widest, width, height, d, true) != 0;
+        ResidentPause paused(c, grow);
+        rc = fs->stage.reserve(c, stage_bytes);
+        if (rc == CHIP_OK) rc = fs->bm_pre.reserve(c, pre_bytes);
+        if (rc == CHIP_OK) rc = orb_batch_reserve(c, widest, width, height, d, false);
+        if (rc != CHIP_OK) return rc;
+    }
+    hipStream_t s = match_stream(c);
+    uint8_t *stage = fs->stage;
+    uint8_t *in = raw ? stage + (size_t)widest * pair_stride : stage;   // where the callers' pairs go
+    fs->last_groups = fs->last_launches = fs->last_waits = 0;
+    for (int32_t f = 0; f < F; f++) n[f] = -1;
+    for (int32_t g0 = 0; g0 < F; g0 += group) {
+        const int32_t G = F - g0 < group ? F - g0 : group;
+        std::vector<SlotPut> puts;
+        try { puts.reserve((size_t)G); } catch (const std::bad_alloc &) { return CHIP_ERR_OOM; }   // (this group and the later ones are untouched)
+        int32_t slot[kFramePutGroup] = {}, cursor = 0;
+        for (int32_t f = 0; f < G; f++) {
+            puts.emplace_back(fs, ids[g0 + f], &cursor);
+            if (puts.back().k < 0) return CHIP_ERR_OOM;               // cannot happen: the free slots were counted above
+            slot[f] = puts.back().k;
+        }
+        const int32_t *counts = nullptr;
+        fs->last_groups++;
+        const auto run = [&]() -> int {
+            for (int32_t f = 0; f < G; f++) {
+                CHIP_HIP(c, hipMemcpyAsync(in + (size_t)f * pair_stride, left[g0 + f], px, hipMemcpyHostToDevice, s));
+                CHIP_HIP(c, hipMemcpyAsync(in + (size_t)f * pair_stride + px, right[g0 + f], px, hipMemcpyHostToDevice, s));
+            }
+            if (raw) {
+                const RectifyBatchArgs a{RectifyArgs{in, stage, fs->rect_maps, width, height, fs->rect_stages}, pair_stride};
+                const dim3 grid((unsigned)((width + kRectLanes * kRectPix - 1) / (kRectLanes * kRectPix)), (unsigned)((height + kRectRows - 1) / kRectRows),
+                                2u * (unsigned)G);
+                hipLaunchKernelGGL(fb_rectify, grid, dim3(kRectThreads), 0, s, a);
+                CHIP_HIP(c, hipGetLastError());
+                fs->last_launches++;
+            }
+            const uint8_t *out = nullptr;
+            size_t out_stride = 0;
+            const int e = orb_batch_enqueue(c, s, stage, pair_stride, G, width, height, d, fs->store_desc, fs->store_kp, fs->slot_kp, slot,
+                                            &fs->last_launches, &out, &out_stride);
+            if (e != CHIP_OK) return e;
+            {
+                const PrefilterBatchArgs a{PrefilterArgs{stage, fs->bm_pre, width, height, (width + 3) / 4, b.cap}, pair_stride, pre_stride};
+                const size_t threads = 2 * (size_t)height * (size_t)a.a.quads;
+                hipLaunchKernelGGL(fb_prefilter, dim3((unsigned)((threads + kBmThreads - 1) / kBmThreads), (unsigned)G), dim3(kBmThreads), 0, s, a);
+                CHIP_HIP(c, hipGetLastError());
+                fs->last_launches++;
+            }
+            {
+                BmKeypointBatchArgs a{BmKeypointArgs{fs->store_kp, fs->bm_pre, fs->store_rec, 0, width, height, b, q}, out, pre_stride, out_stride,
+                                      fs->slot_kp, {}};
+                for (int f = 0; f < kFramePutGroup; f++) a.slot[f] = (uint32_t)slot[f < G ? f : 0];
+                hipLaunchKernelGGL(fb_keypoints, dim3((unsigned)((d.n_features + kBmWaves - 1) / kBmWaves), (unsigned)G), dim3(kBmThreads), 0, s, a);
+                CHIP_HIP(c, hipGetLastError());
+                fs->last_launches++;
+            }
+            const int k = orb_batch_counts(c, s, G, &counts);
+            if (k != CHIP_OK) return k;
+            fs->last_waits++;
+            CHIP_HIP(c, hipStreamSynchronize(s));
+            for (int32_t f = 0; f < G; f++) {
+                int32_t total = 0;
+                for (int l = 0; l < CHIP_ORB_MAX_LEVELS; l++) total += counts[8 * f + l];
+                if (total < 0 || total > d.n_features) return CHIP_ERR_HIP;   // cannot happen: the kept lists are bounded by the quotas
+            }
+            return CHIP_OK;
+        };
+        rc = run();
+        if (rc != CHIP_OK) {                  // the groups before this one stay; this one's ids leave the store; the later ones are untouched
+            for (SlotPut &p : puts) p.abandon();
+            return rc;
+        }
+        for (int32_t f = 0; f < G; f++) {
+            int32_t total = 0;
+            for (int l = 0; l < CHIP_ORB_MAX_LEVELS; l++) total += counts[8 * f + l];
+            puts[(size_t)f].commit(total, width, height);
+            n[g0 + f] = total;
+        }
+    }
     return CHIP_OK;
 }
 
@@ -857,4 +1014,61 @@ extern "C" int chip_frame_put_raw_orb_stereo(chip_ctx *c, int64_t id, int32_t wi
                                              const double Q_rowmajor[16], int32_t *n)
 {
     return put_orb_stereo(c, id, width, height, left_raw, right_raw, orb, bm, Q_rowmajor, n, true);
+}
+
+// ------------------------------------------------------------------------------------------------ many pairs per call
+extern "C" int chip_build_has_frame_put_batch(void) { return 1; }
+
+extern "C" int chip_frame_put_plan(int32_t width, int32_t height, const chip_orb_params *orb, int32_t raw, int32_t F, int32_t *group, int32_t *n_groups)
+{
+    if (!group || !n_groups || (raw != 0 && raw != 1)) return CHIP_ERR_INVALID_ARG;
+    chip_orb_params d;
+    const int rc = put_batch_check(width, height, orb, F, &d);
+    if (rc != CHIP_OK) return rc;
+    *group = put_group(width, height);
+    *n_groups = (F + *group - 1) / *group;
+    return CHIP_OK;
+}
+
+extern "C" int chip_frame_put_orb_stereo_batch(chip_ctx *c, const int64_t *ids, int32_t F, int32_t width, int32_t height, const uint8_t *const *left,
+                                               const uint8_t *const *right, const chip_orb_params *orb, const chip_stereo_bm_params *bm,
+                                               const double Q_rowmajor[16], int32_t *n)
+{
+    return put_orb_stereo_batch(c, ids, F, width, height, left, right, orb, bm, Q_rowmajor, n, false);
+}
+
+extern "C" int chip_frame_put_raw_orb_stereo_batch(chip_ctx *c, const int64_t *ids, int32_t F, int32_t width, int32_t height,
+                                                   const uint8_t *const *left_raw, const uint8_t *const *right_raw, const chip_orb_params *orb,
+                                                   const chip_stereo_bm_params *bm, const double Q_rowmajor[16], int32_t *n)
+{
+    return put_orb_stereo_batch(c, ids, F, width, height, left_raw, right_raw, orb, bm, Q_rowmajor, n, true);
+}
+
+extern "C" int chip_debug_frame_put_last(chip_ctx *c, int32_t *groups, int32_t *launches, int32_t *waits)
+{
+    if (!c) return CHIP_ERR_INVALID_ARG;
+    if (c->group) return CHIP_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(c->match_mu);
+    const FrameStore *fs = c->frame_store;
+    if (groups) *groups = fs ? fs->last_groups : 0;
+    if (launches) *launches = fs ? fs->last_launches : 0;
+    if (waits) *waits = fs ? fs->last_waits : 0;
+    return CHIP_OK;
+}
+
+// the rows chip_frame_read gave, back into a slot: three uploads, no kernel
+extern "C" int chip_frame_put_records(chip_ctx *c, int64_t id, const uint8_t *desc, const float *kp_xy, const float *pts, int32_t n, int32_t width,
+                                      int32_t height)
+{
+    if (!c) return CHIP_ERR_INVALID_ARG;
+    const int rc = check_frame(desc, kp_xy, n, width, height, pts);   // the frame rules, on the records
+    if (rc != CHIP_OK) return rc;
+    for (int32_t i = 0; i < n; i++) {       // the fourth float is what the gather kernels write: 0.0f (no point) or 1.0f, bit for bit
+        uint32_t w;
+        std::memcpy(&w, pts + 4 * (size_t)i + 3, sizeof w);
+        if (w != 0u && w != 0x3f800000u) return CHIP_ERR_INVALID_ARG;
+    }
+    return put_frame(c, id, PutRows{desc, kp_xy, n, width, height}, 0, 0, [&](FrameStore *fs, hipStream_t s, size_t at) {
+        return hipMemcpyAsync(fs->store_rec + at, pts, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, s);
+    });
 }

@@ -28,6 +28,9 @@
 //   orb_describe   : one wave per kept keypoint: the bin from the record's moments (lanes 0 .. 31 one int64 product sum each, one wave
 //                    reduction), the lane's four steered pairs in one 16-byte load, eight byte gathers, four ballots, two 16-byte stores.
 //
+// Every kernel has a batch entry fb_<stage> for the batched frame puts (frames.hip put_orb_stereo_batch): the same body on the bases of
+// one of up to 16 frames, the frame taken from the grid, its scratch at frame x stride in the same buffers (orb_batch_enqueue).
+//
 // Nothing returns to the host between the stages; the records and the eight counts leave in ONE copy at the end (the descriptors of
 // chip_orb_detect_describe in one more).
 #include "chip_internal.h"
@@ -74,6 +77,11 @@ struct OrbArgs {
     uint8_t *out;                      // kOutHeader bytes of counts, then the records
     OrbTable t;
 };
+// The frame axis of a batched put (chip_frame_put_orb_stereo_batch): frame f of a group has its scratch at f * stride behind frame 0's, in
+// elements of each buffer.  The element offsets of OrbLevel stay per frame.
+constexpr int kOrbGroup = kFramePutGroup;
+struct OrbStrides { size_t img, score, cand, strip, kept, out; };
+struct OrbBatchArgs { OrbArgs a; OrbStrides f; };
 
 // ------------------------------------------------------------------------------------------------ orb_pyramid
 __device__ __forceinline__ void orb_axis(int x, int n_src, int n_dst, int *i0, int *i1, uint32_t *frac)
@@ -85,13 +93,14 @@ __device__ __forceinline__ void orb_axis(int x, int n_src, int n_dst, int *i0, i
     *frac = (uint32_t)(X & 2047);
     *i1 = min(*i0 + 1, n_src - 1);
 }
-// grid (ceil(pitch / 4 / 64), ceil(h / 4)), block (64, 4): level lv from level lv - 1
-__global__ __launch_bounds__(kOrbThreads) void orb_pyramid(OrbArgs a, int lv)
+// Every stage has ONE body, a __device__ function on the bases of its frame, and two entries: the single call's kernel (frame 0) and the
+// batched put's (fb_*: the frame from the grid, its bases at frame x stride).
+__device__ __forceinline__ void pyramid_frame(const OrbTable &t, uint8_t *img, int lv)
 {
-    const OrbLevel &d = a.t.l[lv], &s = a.t.l[lv - 1];
+    const OrbLevel &d = t.l[lv], &s = t.l[lv - 1];
     const int xq = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
     if (4 * xq >= d.w || y >= d.h) return;
-    const uint8_t *src = a.img + s.img_off;
+    const uint8_t *src = img + s.img_off;
     int y0, y1;
     uint32_t b;
     orb_axis(y, s.h, d.h, &y0, &y1, &b);
@@ -107,20 +116,23 @@ __global__ __launch_bounds__(kOrbThreads) void orb_pyramid(OrbArgs a, int lv)
                             (1u << 21)) >> 22;
         packed |= v << (8 * i);
     }
-    *reinterpret_cast<uint32_t *>(a.img + d.img_off + (size_t)y * d.pitch + 4 * xq) = packed;
+    *reinterpret_cast<uint32_t *>(img + d.img_off + (size_t)y * d.pitch + 4 * xq) = packed;
 }
+// grid (ceil(pitch / 4 / 64), ceil(h / 4)), block (64, 4): level lv from level lv - 1
+__global__ __launch_bounds__(kOrbThreads) void orb_pyramid(OrbArgs a, int lv) { pyramid_frame(a.t, a.img, lv); }
+// the same grid x frames (blockIdx.z)
+__global__ __launch_bounds__(kOrbThreads) void fb_pyramid(OrbBatchArgs g, int lv) { pyramid_frame(g.a.t, g.a.img + blockIdx.z * g.f.img, lv); }
 
 // ------------------------------------------------------------------------------------------------ orb_fast_score
 // byte c (0 .. 15) of the four dwords of a row
 #define ORB_BYTE(r, c) (int)(((r)[(c) >> 2] >> (8 * ((c) & 3))) & 255u)
-// grid (tiles in x of the widest level, tiles in y of the tallest, n_levels), block 256
-__global__ __launch_bounds__(kOrbThreads) void orb_fast_score(OrbArgs a)
+__device__ __forceinline__ void fast_score_frame(const OrbTable &t, const uint8_t *img0, int16_t *score, int lv)
 {
     __shared__ uint2 tile[kScoreLdsRows][kScoreLdsPairs];
-    const OrbLevel &L = a.t.l[blockIdx.z];
+    const OrbLevel &L = t.l[lv];
     const int tx0 = blockIdx.x * kScoreTileW, ty0 = blockIdx.y * kScoreTileH;
     if (tx0 >= L.spitch || ty0 >= L.h) return;            // wave-uniform: the whole workgroup leaves
-    const uint8_t *img = a.img + L.img_off;
+    const uint8_t *img = img0 + L.img_off;
     uint32_t *flat = reinterpret_cast<uint32_t *>(&tile[0][0]);
     for (int i = threadIdx.x; i < kScoreLdsRows * 2 * kScoreLdsPairs; i += kOrbThreads) {
         const int r = i / (2 * kScoreLdsPairs), cq = i - r * (2 * kScoreLdsPairs);
@@ -171,7 +183,15 @@ __global__ __launch_bounds__(kOrbThreads) void orb_fast_score(OrbArgs a)
         const uint32_t s16 = (uint32_t)S & 0xffffu;
         if (i & 1) packed[i >> 1] |= s16 << 16; else packed[i >> 1] = s16;
     }
-    *reinterpret_cast<uint4 *>(a.score + L.score_off + (size_t)y * L.spitch + x) = make_uint4(packed[0], packed[1], packed[2], packed[3]);
+    *reinterpret_cast<uint4 *>(score + L.score_off + (size_t)y * L.spitch + x) = make_uint4(packed[0], packed[1], packed[2], packed[3]);
+}
+// grid (tiles in x of the widest level, tiles in y of the tallest, n_levels), block 256
+__global__ __launch_bounds__(kOrbThreads) void orb_fast_score(OrbArgs a) { fast_score_frame(a.t, a.img, a.score, blockIdx.z); }
+// grid z = level + n_levels * frame
+__global__ __launch_bounds__(kOrbThreads) void fb_fast_score(OrbBatchArgs g)
+{
+    const int f = blockIdx.z / g.a.t.n_levels;
+    fast_score_frame(g.a.t, g.a.img + f * g.f.img, g.a.score + f * g.f.score, blockIdx.z - f * g.a.t.n_levels);
 }
 
 // ------------------------------------------------------------------------------------------------ orb_candidates
@@ -190,56 +210,20 @@ __device__ __forceinline__ long long orb_harris(const uint8_t *img, int pitch, i
     const long long A = a, B = bb, C = c;
     return 25 * (A * B - C * C) - (A + B) * (A + B);
 }
-// grid (strips of the level with the most, n_levels), block 256
+// grid (strips of the level with the most, n_levels), block 256.  The body is orb_candidates_body.inc (see there why it is text).
 __global__ __launch_bounds__(kOrbThreads) void orb_candidates(OrbArgs a)
 {
-    __shared__ int32_t list[kStripMaxCand];
-    __shared__ int32_t wave_n[kOrbThreads / 64];
-    const OrbLevel &L = a.t.l[blockIdx.y];
-    const int strip = blockIdx.x;
-    if (strip >= L.nstrips) return;
-    const int16_t *sc = a.score + L.score_off;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int thr = a.t.threshold;
-    int base = 0;                                         // survivors so far, the same in every thread
-    for (int r = 0; r < kStripRows; r++) {
-        const int y = L.y0 + kStripRows * strip + r;
-        if (y > L.y1) break;
-        for (int xc = L.x0; xc <= L.x1; xc += kOrbThreads) {
-            const int x = xc + (int)threadIdx.x;
-            bool keep = false;
-            if (x <= L.x1) {
-                const int16_t *p = sc + (size_t)y * L.spitch + x;
-                const int s = p[0];
-                if (s >= thr) {
-                    const int16_t *u = p - L.spitch, *d = p + L.spitch;
-                    const int m = max(max(max((int)u[-1], (int)u[0]), max((int)u[1], (int)p[-1])), max(max((int)p[1], (int)d[-1]), max((int)d[0], (int)d[1])));
-                    keep = s > m;
-                }
-            }
-            const unsigned long long votes = __ballot(keep);
-            if (lane == 0) wave_n[wave] = __popcll(votes);
-            __syncthreads();
-            int before = 0, total = 0;
-#pragma unroll
-            for (int w = 0; w < kOrbThreads / 64; w++) { const int n = wave_n[w]; total += n; if (w < wave) before += n; }
-            if (keep) {
-                const int at = base + before + __popcll(votes & ((1ull << lane) - 1ull));
-                if (at < L.cap) list[at] = y * L.w + x;  // (always: one strict maximum per 2 x 2 block; filled to cap by tests/test_orb_limits_gpu.py)
-            }
-            base += total;
-            __syncthreads();
-        }
-    }
-    const int n = min(base, L.cap);
-    OrbCand *seg = a.cand + L.cand_off + (size_t)strip * L.cap;
-    const uint8_t *img = a.img + L.img_off;
-    for (int i = threadIdx.x; i < n; i += kOrbThreads) {
-        const int raster = list[i], y = raster / L.w, x = raster - y * L.w;
-        const long long R = orb_harris(img, L.pitch, x, y);
-        *reinterpret_cast<uint4 *>(seg + i) = make_uint4((uint32_t)(unsigned long long)R, (uint32_t)((unsigned long long)R >> 32), (uint32_t)raster, 0u);
-    }
-    if (threadIdx.x == 0) a.strip_count[L.strip_off + strip] = n;
+#define ORB_FRAME(p, which) (p)
+#include "orb_candidates_body.inc"
+#undef ORB_FRAME
+}
+// the same grid x frames (blockIdx.z)
+__global__ __launch_bounds__(kOrbThreads) void fb_candidates(OrbBatchArgs g)
+{
+    const OrbArgs &a = g.a;
+#define ORB_FRAME(p, which) ((p) + (size_t)blockIdx.z * g.f.which)
+#include "orb_candidates_body.inc"
+#undef ORB_FRAME
 }
 
 // ------------------------------------------------------------------------------------------------ orb_select
@@ -259,8 +243,7 @@ __device__ __forceinline__ int orb_block_excl(int v, int32_t *scratch, int *tota
     *total = all;
     return before + inc - v;
 }
-// grid CHIP_ORB_MAX_LEVELS, block 1024
-__global__ __launch_bounds__(kSelectThreads) void orb_select(OrbArgs a)
+__device__ __forceinline__ void select_frame(const OrbTable &t, OrbCand *cand0, const int32_t *strip_count, OrbCand *kept0, uint8_t *out)
 {
     __shared__ int32_t start[2 * kSelectThreads + 1];     // start[s]: candidates of the level before strip s (kMaxStrips <= 2048)
     __shared__ __align__(16) int32_t hist[256];
@@ -268,10 +251,10 @@ __global__ __launch_bounds__(kSelectThreads) void orb_select(OrbArgs a)
     __shared__ unsigned long long sel_prefix;
     __shared__ int32_t sel_k;
     const int lv = blockIdx.x, tid = threadIdx.x;
-    const OrbLevel &L = a.t.l[lv];
-    int32_t *counts_out = reinterpret_cast<int32_t *>(a.out);
-    if (lv >= a.t.n_levels) { if (tid == 0) counts_out[lv] = 0; return; }
-    const int32_t *sn = a.strip_count + L.strip_off;
+    const OrbLevel &L = t.l[lv];
+    int32_t *counts_out = reinterpret_cast<int32_t *>(out);
+    if (lv >= t.n_levels) { if (tid == 0) counts_out[lv] = 0; return; }
+    const int32_t *sn = strip_count + L.strip_off;
     int C;
     {   // scan of the strip counts, two strips a thread
         const int s = 2 * tid;
@@ -282,7 +265,7 @@ __global__ __launch_bounds__(kSelectThreads) void orb_select(OrbArgs a)
         if (tid == kSelectThreads - 1) start[2 * kSelectThreads] = C;
         __syncthreads();
     }
-    OrbCand *cand = a.cand + L.cand_off;
+    OrbCand *cand = cand0 + L.cand_off;
     uint4 *flat = reinterpret_cast<uint4 *>(cand);
     // The segments close up in place, so that candidate g of the level in raster order is entry g: 1024 at a time, each found by a
     // bisection over the strip ranges, read, and after a barrier written.  Entry g never lies behind its source, a chunk writes
@@ -340,7 +323,7 @@ __global__ __launch_bounds__(kSelectThreads) void orb_select(OrbArgs a)
         star = sel_prefix;
         need = sel_k;
     }
-    uint4 *kept = reinterpret_cast<uint4 *>(a.kept + L.qprefix);
+    uint4 *kept = reinterpret_cast<uint4 *>(kept0 + L.qprefix);
     int n_kept = 0, n_ties = 0;
     for (int g0 = 0; g0 < C; g0 += kSelectThreads) {
         const int g = g0 + tid;
@@ -362,14 +345,21 @@ __global__ __launch_bounds__(kSelectThreads) void orb_select(OrbArgs a)
     }
     if (tid == 0) counts_out[lv] = min(n_kept, L.quota);
 }
+// grid CHIP_ORB_MAX_LEVELS, block 1024
+__global__ __launch_bounds__(kSelectThreads) void orb_select(OrbArgs a) { select_frame(a.t, a.cand, a.strip_count, a.kept, a.out); }
+// grid (CHIP_ORB_MAX_LEVELS, frames): still one workgroup per (level, frame)
+__global__ __launch_bounds__(kSelectThreads) void fb_select(OrbBatchArgs g)
+{
+    const size_t f = blockIdx.y;
+    select_frame(g.a.t, g.a.cand + f * g.f.cand, g.a.strip_count + f * g.f.strip, g.a.kept + f * g.f.kept, g.a.out + f * g.f.out);
+}
 
 // ------------------------------------------------------------------------------------------------ orb_moments
-// grid ceil(n_features / 4), block 256: wave i makes record i
-__global__ __launch_bounds__(kOrbThreads) void orb_moments(OrbArgs a)
+__device__ __forceinline__ void moments_frame(const OrbTable &t, const uint8_t *img0, const OrbCand *kept, uint8_t *out)
 {
     const int lane = threadIdx.x & 63;
     const int i = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (kOrbThreads / 64) + (threadIdx.x >> 6)));
-    const int32_t *counts = reinterpret_cast<const int32_t *>(a.out);
+    const int32_t *counts = reinterpret_cast<const int32_t *>(out);
     int lv = -1, j = i;
 #pragma unroll
     for (int l = 0; l < kOrbLevels; l++) {
@@ -377,10 +367,10 @@ __global__ __launch_bounds__(kOrbThreads) void orb_moments(OrbArgs a)
         if (lv < 0) { if (j < n) lv = l; else j -= n; }
     }
     if (lv < 0) return;                                   // wave-uniform
-    const OrbLevel &L = a.t.l[lv];
-    const uint4 c = *reinterpret_cast<const uint4 *>(a.kept + L.qprefix + j);   // R low, R high, raster
+    const OrbLevel &L = t.l[lv];
+    const uint4 c = *reinterpret_cast<const uint4 *>(kept + L.qprefix + j);   // R low, R high, raster
     const int y = (int)c.z / L.w, x = (int)c.z - y * L.w;
-    const uint8_t *img = a.img + L.img_off;
+    const uint8_t *img = img0 + L.img_off;
     const int xa = (x - 15) & ~3;                         // the aligned dword that holds column x - 15; nine dwords cover the row at most
     const unsigned long long umax = 0x3689abcddeeeffffull;   // umax[|v|] = nibble |v|
     int m10 = 0, m01 = 0;
@@ -399,10 +389,18 @@ __global__ __launch_bounds__(kOrbThreads) void orb_moments(OrbArgs a)
     for (int off = 32; off > 0; off >>= 1) { m10 += __shfl_xor(m10, off); m01 += __shfl_xor(m01, off); }
     if (lane == 0) {
         const float fx = (float)((double)x * L.scale), fy = (float)((double)y * L.scale);
-        uint4 *rec = reinterpret_cast<uint4 *>(a.out + kOutHeader + (size_t)i * sizeof(chip_orb_keypoint));
+        uint4 *rec = reinterpret_cast<uint4 *>(out + kOutHeader + (size_t)i * sizeof(chip_orb_keypoint));
         rec[0] = make_uint4(c.x, c.y, __float_as_uint(fx), __float_as_uint(fy));
         rec[1] = make_uint4((uint32_t)m10, (uint32_t)m01, (uint32_t)x | ((uint32_t)y << 16), (uint32_t)lv);
     }
+}
+// grid ceil(n_features / 4), block 256: wave i makes record i
+__global__ __launch_bounds__(kOrbThreads) void orb_moments(OrbArgs a) { moments_frame(a.t, a.img, a.kept, a.out); }
+// the same grid x frames (blockIdx.y)
+__global__ __launch_bounds__(kOrbThreads) void fb_moments(OrbBatchArgs g)
+{
+    const size_t f = blockIdx.y;
+    moments_frame(g.a.t, g.a.img + f * g.f.img, g.a.kept + f * g.f.kept, g.a.out + f * g.f.out);
 }
 
 // ------------------------------------------------------------------------------------------------ orb_blur
@@ -418,6 +416,7 @@ struct OrbBlurArgs {
     uint8_t *blur;
     OrbBlurLevel l[kOrbLevels];
 };
+struct OrbBlurBatchArgs { OrbBlurArgs a; size_t img_stride, blur_stride; int32_t n_levels; };
 // the dword of row `row` (pitch bytes, w pixels) at columns gx .. gx + 3 with the column clamped into the row; gx is a multiple of 4
 __device__ __forceinline__ uint32_t orb_clamped_dword(const uint8_t *row, int gx, int w)
 {
@@ -431,54 +430,25 @@ __device__ __forceinline__ uint32_t orb_clamped_dword(const uint8_t *row, int gx
     for (int b = 0; b < 4; b++) v |= (gx + b < w ? (d >> (8 * b)) & 255u : last) << (8 * b);
     return v;
 }
-// grid (tiles in x of the widest level, tiles in y of the tallest, n_levels), block 256
+// grid (tiles in x of the widest level, tiles in y of the tallest, n_levels), block 256.  The body is orb_blur_body.inc (see there why it is text).
 __global__ __launch_bounds__(kOrbThreads) void orb_blur(OrbBlurArgs a)
 {
-    __shared__ uint32_t tile[kBlurRows][kBlurDwords];
-    __shared__ __align__(16) uint16_t hsum[kBlurRows][kBlurHPitch];
-    const OrbBlurLevel &L = a.l[blockIdx.z];
-    const int tx0 = blockIdx.x * kBlurTileW, ty0 = blockIdx.y * kBlurTileH;
-    if (tx0 >= L.bpitch || ty0 >= L.h) return;            // wave-uniform: the whole workgroup leaves (an empty level has h = 0)
-    const uint8_t *img = a.img + L.img_off;
-    for (int i = threadIdx.x; i < kBlurRows * kBlurDwords; i += kOrbThreads) {
-        const int r = i / kBlurDwords, cq = i - r * kBlurDwords;
-        const int gy = min(max(ty0 - 3 + r, 0), L.h - 1);
-        tile[r][cq] = orb_clamped_dword(img + (size_t)gy * L.pitch, tx0 - 4 + 4 * cq, L.w);
-    }
-    __syncthreads();
-    // horizontal: four sums an item from three dwords (columns 4q - 4 .. 4q + 7 of the tile); 128 * 255 < 2^16
-    for (int i = threadIdx.x; i < kBlurRows * (kBlurTileW / 4); i += kOrbThreads) {
-        const int r = i / (kBlurTileW / 4), q = i - r * (kBlurTileW / 4);
-        const uint32_t d0 = tile[r][q], d1 = tile[r][q + 1], d2 = tile[r][q + 2];
-        uint32_t px[12];
-#pragma unroll
-        for (int b = 0; b < 4; b++) { px[b] = (d0 >> (8 * b)) & 255u; px[4 + b] = (d1 >> (8 * b)) & 255u; px[8 + b] = (d2 >> (8 * b)) & 255u; }
-        uint32_t s[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++)                       // pixel 4q + k is px[4 + k]
-            s[k] = 9u * (px[1 + k] + px[7 + k]) + 17u * (px[2 + k] + px[6 + k]) + 24u * (px[3 + k] + px[5 + k]) + 28u * px[4 + k];
-        *reinterpret_cast<uint2 *>(&hsum[r][4 * q]) = make_uint2(s[0] | s[1] << 16, s[2] | s[3] << 16);
-    }
-    __syncthreads();
-    const int lx = threadIdx.x & 7, ly = threadIdx.x >> 3;
-    const int x = tx0 + 16 * lx, y = ty0 + ly;
-    if (x >= L.bpitch || y >= L.h) return;
-    uint32_t acc[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) acc[k] = 8192u;
-    constexpr uint32_t g[7] = {9u, 17u, 24u, 28u, 24u, 17u, 9u};
-#pragma unroll
-    for (int j = 0; j < 7; j++) {
-        const uint4 p = *reinterpret_cast<const uint4 *>(&hsum[ly + j][16 * lx]), q = *reinterpret_cast<const uint4 *>(&hsum[ly + j][16 * lx + 8]);
-        const uint32_t d[8] = {p.x, p.y, p.z, p.w, q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int k = 0; k < 8; k++) { acc[2 * k] += g[j] * (d[k] & 0xffffu); acc[2 * k + 1] += g[j] * (d[k] >> 16); }
-    }
-    uint32_t out[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-        out[k] = (acc[4 * k] >> 14) | (acc[4 * k + 1] >> 14) << 8 | (acc[4 * k + 2] >> 14) << 16 | (acc[4 * k + 3] >> 14) << 24;
-    *reinterpret_cast<uint4 *>(a.blur + L.blur_off + (size_t)y * L.bpitch + x) = make_uint4(out[0], out[1], out[2], out[3]);
+#define ORB_FRAME(p, stride) (p)
+#define ORB_BLUR_LEVEL blockIdx.z
+#include "orb_blur_body.inc"
+#undef ORB_BLUR_LEVEL
+#undef ORB_FRAME
+}
+// grid z = level + n_levels * frame
+__global__ __launch_bounds__(kOrbThreads) void fb_blur(OrbBlurBatchArgs batch)
+{
+    const OrbBlurArgs &a = batch.a;
+    const unsigned frame = blockIdx.z / (unsigned)batch.n_levels;
+#define ORB_FRAME(p, stride) ((p) + (size_t)frame * batch.stride)
+#define ORB_BLUR_LEVEL (blockIdx.z - frame * (unsigned)batch.n_levels)
+#include "orb_blur_body.inc"
+#undef ORB_BLUR_LEVEL
+#undef ORB_FRAME
 }
 
 // ------------------------------------------------------------------------------------------------ orb_describe
@@ -491,17 +461,19 @@ struct OrbDescArgs {
     int32_t bpitch[kOrbLevels];
     uint32_t blur_off[kOrbLevels];
 };
-// grid ceil(n_features / 4), block 256: wave i makes descriptor i
-__global__ __launch_bounds__(kOrbThreads) void orb_describe(OrbDescArgs a)
+// desc / kp of the batch form: the rows of slot 0 of the frame store; frame f writes the rows of slot[f]
+struct OrbDescBatchArgs { OrbDescArgs a; size_t blur_stride, out_stride; int32_t slot_kp; uint32_t slot[kOrbGroup]; };
+// row_at: the first row of the frame's slot behind a.desc / a.kp
+__device__ __forceinline__ void describe_frame(const OrbDescArgs &a, size_t blur_at, size_t out_at, size_t row_at)
 {
     const int lane = threadIdx.x & 63;
     const int i = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kDescWaves + (threadIdx.x >> 6)));
-    const int32_t *counts = reinterpret_cast<const int32_t *>(a.out);
+    const int32_t *counts = reinterpret_cast<const int32_t *>(a.out + out_at);
     int total = 0;
 #pragma unroll
     for (int l = 0; l < kOrbLevels; l++) total += counts[l];
     if (i >= total) return;                               // wave-uniform
-    const uint4 *rec = reinterpret_cast<const uint4 *>(a.out + kOutHeader + (size_t)i * sizeof(chip_orb_keypoint));
+    const uint4 *rec = reinterpret_cast<const uint4 *>(a.out + out_at + kOutHeader + (size_t)i * sizeof(chip_orb_keypoint));
     const uint4 m = rec[1];                               // m10, m01, x | y << 16, level
     const int x = (int)(m.z & 0xffffu), y = (int)(m.z >> 16), lv = (int)(m.w & 7u);
     const int32_t *cs = reinterpret_cast<const int32_t *>(a.tab);
@@ -517,7 +489,7 @@ __global__ __launch_bounds__(kOrbThreads) void orb_describe(OrbDescArgs a)
     }
     best = __builtin_amdgcn_readfirstlane(best);
     const uint4 t = *reinterpret_cast<const uint4 *>(a.tab + kOrbTabHeader + ((size_t)best * 64 + lane) * 16);
-    const uint8_t *B = a.blur + a.blur_off[lv] + (size_t)y * a.bpitch[lv] + x;
+    const uint8_t *B = a.blur + blur_at + a.blur_off[lv] + (size_t)y * a.bpitch[lv] + x;
     const int bp = a.bpitch[lv];
     const uint32_t tw[4] = {t.x, t.y, t.z, t.w};
     unsigned long long bits[4];
@@ -528,11 +500,19 @@ __global__ __launch_bounds__(kOrbThreads) void orb_describe(OrbDescArgs a)
         bits[j] = __ballot(p < q);                        // bit `lane` is pair 64 j + lane: bytes 8 j .. 8 j + 7, LSB first
     }
     if (lane == 0) {
-        uint4 *d = reinterpret_cast<uint4 *>(a.desc + (size_t)i * CHIP_ORB_DESC_BYTES);
+        uint4 *d = reinterpret_cast<uint4 *>(a.desc + (row_at + (size_t)i) * CHIP_ORB_DESC_BYTES);
         d[0] = make_uint4((uint32_t)bits[0], (uint32_t)(bits[0] >> 32), (uint32_t)bits[1], (uint32_t)(bits[1] >> 32));
         d[1] = make_uint4((uint32_t)bits[2], (uint32_t)(bits[2] >> 32), (uint32_t)bits[3], (uint32_t)(bits[3] >> 32));
-        if (a.kp) a.kp[i] = make_float2(__uint_as_float(rec[0].z), __uint_as_float(rec[0].w));
+        if (a.kp) a.kp[row_at + (size_t)i] = make_float2(__uint_as_float(rec[0].z), __uint_as_float(rec[0].w));
     }
+}
+// grid ceil(n_features / 4), block 256: wave i makes descriptor i
+__global__ __launch_bounds__(kOrbThreads) void orb_describe(OrbDescArgs a) { describe_frame(a, 0, 0, 0); }
+// the same grid x frames (blockIdx.y): straight into the frame's slot
+__global__ __launch_bounds__(kOrbThreads) void fb_describe(OrbDescBatchArgs g)
+{
+    const size_t f = blockIdx.y, at = (size_t)g.slot[f] * (size_t)g.slot_kp;
+    describe_frame(g.a, f * g.blur_stride, f * g.out_stride, at);
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -685,17 +665,22 @@ int orb_check(int32_t width, int32_t height, const chip_orb_params *p, chip_orb_
 // eight counts, then the records) into h_out; nothing is waited for.  The image is `image` (host) or `image_dev` (device), dense rows.
 // desc_dev / kp_dev: where orb_describe writes (desc_dev null: the state's own buffer; kp_dev may be null).  The caller holds match_mu,
 // has selected the device, and calls orb_finished once the stream has drained.
-int orb_enqueue(Ctx *c, hipStream_t s, const uint8_t *image, const uint8_t *image_dev, int32_t width, int32_t height, const chip_orb_params &d,
-                bool describe, uint8_t *desc_dev, float2 *kp_dev, size_t back)
+// the launch table: where every level of ONE frame lives in the ctx's buffers, the elements a frame takes of each, and what sizes the grids
+struct OrbLayout {
+    OrbTable t{};
+    OrbBlurLevel bl[kOrbLevels] = {};
+    size_t img_n = 0, score_n = 0, cand_n = 0, strip_n = 0, blur_n = 0;
+    int max_w = 0, max_h = 0, max_strips = 0, max_bw = 0;
+};
+static void orb_layout(int32_t width, int32_t height, const chip_orb_params &d, OrbLayout *lay)
 {
     chip_orb_level plan[kOrbLevels];
     orb_plan(width, height, d, plan);
-    // the launch table: where every level lives in the ctx's buffers
-    OrbTable t{};
-    OrbBlurLevel bl[kOrbLevels] = {};
+    OrbTable &t = lay->t;
+    OrbBlurLevel *bl = lay->bl;
     t.n_levels = d.n_levels; t.n_features = d.n_features; t.threshold = d.fast_threshold;
-    size_t img_n = 0, score_n = 0, cand_n = 0, strip_n = 0, blur_n = 0;
-    int qprefix = 0, max_w = 0, max_h = 0, max_strips = 0, max_bw = 0;
+    size_t &img_n = lay->img_n, &score_n = lay->score_n, &cand_n = lay->cand_n, &strip_n = lay->strip_n, &blur_n = lay->blur_n;
+    int qprefix = 0, &max_w = lay->max_w, &max_h = lay->max_h, &max_strips = lay->max_strips, &max_bw = lay->max_bw;
     for (int l = 0; l < d.n_levels; l++) {
         OrbLevel &L = t.l[l];
         L.w = plan[l].width; L.h = plan[l].height; L.scale = plan[l].scale;
@@ -716,6 +701,17 @@ int orb_enqueue(Ctx *c, hipStream_t s, const uint8_t *image, const uint8_t *imag
         max_strips = L.nstrips > max_strips ? L.nstrips : max_strips;
         max_bw = bl[l].bpitch > max_bw ? bl[l].bpitch : max_bw;
     }
+}
+
+int orb_enqueue(Ctx *c, hipStream_t s, const uint8_t *image, const uint8_t *image_dev, int32_t width, int32_t height, const chip_orb_params &d,
+                bool describe, uint8_t *desc_dev, float2 *kp_dev, size_t back)
+{
+    OrbLayout lay;
+    orb_layout(width, height, d, &lay);
+    const OrbTable &t = lay.t;
+    const OrbBlurLevel *bl = lay.bl;
+    const size_t img_n = lay.img_n, score_n = lay.score_n, cand_n = lay.cand_n, strip_n = lay.strip_n, blur_n = lay.blur_n;
+    const int max_w = lay.max_w, max_h = lay.max_h, max_strips = lay.max_strips, max_bw = lay.max_bw;
     if (!c->orb_state) {
         c->orb_state = new (std::nothrow) OrbState();
         if (!c->orb_state) return CHIP_ERR_OOM;
@@ -799,6 +795,136 @@ int orb_enqueue(Ctx *c, hipStream_t s, const uint8_t *image, const uint8_t *imag
     CHIP_HIP(c, hipMemcpyAsync(st->h_out.host(), a.out, back, hipMemcpyDeviceToHost, s));
     st->t = t;
     for (int l = 0; l < kOrbLevels; l++) st->bl[l] = bl[l];
+    return CHIP_OK;
+}
+
+constexpr size_t kOrbOutBytes = kOutHeader + (size_t)CHIP_MATCH_MAX_KEYPOINTS * sizeof(chip_orb_keypoint);   // header and records of one frame
+constexpr size_t kOrbKeptStride = CHIP_MATCH_MAX_KEYPOINTS;
+
+int orb_batch_reserve(Ctx *c, int32_t G, int32_t width, int32_t height, const chip_orb_params &d, bool probe)
+{
+    if (G < 1 || G > kOrbGroup) return CHIP_ERR_INVALID_ARG;
+    OrbLayout lay;
+    orb_layout(width, height, d, &lay);
+    if (!c->orb_state) {
+        if (probe) return 1;
+        c->orb_state = new (std::nothrow) OrbState();
+        if (!c->orb_state) return CHIP_ERR_OOM;
+    }
+    OrbState *st = c->orb_state;
+    const size_t g = (size_t)G;
+    const size_t desc_bytes = (size_t)CHIP_MATCH_MAX_KEYPOINTS * CHIP_ORB_DESC_BYTES;
+    const OrbTables &tables = orb_tables();
+    const bool fits = st->img.capacity() >= g * lay.img_n && st->score.capacity() >= g * lay.score_n && st->cand.capacity() >= g * lay.cand_n + 1 &&
+                      st->strip_count.capacity() >= g * lay.strip_n + 1 && st->kept.capacity() >= g * kOrbKeptStride &&
+                      st->out.capacity() >= g * kOrbOutBytes && st->h_out.capacity() && st->blur.capacity() >= g * lay.blur_n + 1 &&
+                      st->h_desc.capacity();
+    if (probe) return fits ? 0 : 1;
+    if (fits) return CHIP_OK;
+    ResidentPause paused(c);   // one pause over everything a group needs
+    int rc = st->img.reserve(c, g * lay.img_n);
+    if (rc == CHIP_OK) rc = st->score.reserve(c, g * lay.score_n);
+    if (rc == CHIP_OK) rc = st->cand.reserve(c, g * lay.cand_n + 1);
+    if (rc == CHIP_OK) rc = st->strip_count.reserve(c, g * lay.strip_n + 1);
+    if (rc == CHIP_OK) rc = st->kept.reserve(c, g * kOrbKeptStride);
+    if (rc == CHIP_OK) rc = st->out.reserve(c, g * kOrbOutBytes);
+    if (rc == CHIP_OK) rc = st->h_out.reserve(c, kOrbOutBytes);
+    if (rc == CHIP_OK) rc = st->blur.reserve(c, g * lay.blur_n + 1);
+    if (rc == CHIP_OK) rc = st->tab.reserve(c, tables.device.size());
+    if (rc == CHIP_OK) rc = st->desc.reserve(c, desc_bytes);
+    if (rc == CHIP_OK) rc = st->h_desc.reserve(c, desc_bytes);
+    return rc;
+}
+
+// The detector and the descriptor of the G <= kOrbGroup left images of a batched put, ONE launch per stage (the pyramid: per level) over
+// all frames.  The rectified pairs lie in device memory, pair f at pairs_dev + f * pair_stride, dense rows, left first.  Frame f's scratch
+// lies at f x the single call's size behind frame 0's, in the same buffers, grown inside one pause; orb_describe's batch entry writes the
+// rows of slot[f] of the store (desc_base, kp_base: slot 0, slot_kp rows a slot).  Nothing is waited for and nothing is copied back: the
+// kept counts of frame f stay at *out_dev + f * *out_stride (eight int32) for the block matcher's batch entry and orb_batch_counts.
+// *launches grows by the launches made.  The caller holds match_mu and has selected the device.
+int orb_batch_enqueue(Ctx *c, hipStream_t s, const uint8_t *pairs_dev, size_t pair_stride, int32_t G, int32_t width, int32_t height,
+                      const chip_orb_params &d, uint8_t *desc_base, float2 *kp_base, int32_t slot_kp, const int32_t *slot, int32_t *launches,
+                      const uint8_t **out_dev, size_t *out_stride)
+{
+    int rc = orb_batch_reserve(c, G, width, height, d, false);   // (the caller has done it: nothing grows here)
+    if (rc != CHIP_OK) return rc;
+    OrbLayout lay;
+    orb_layout(width, height, d, &lay);
+    OrbState *st = c->orb_state;
+    st->have = st->have_blur = false;                     // the debug calls read a single call's buffers
+    const size_t g = (size_t)G, out_bytes = kOrbOutBytes, kept_n = kOrbKeptStride;
+    const OrbTables &tables = orb_tables();
+    OrbBatchArgs a;
+    a.a.img = st->img; a.a.score = st->score; a.a.cand = st->cand; a.a.strip_count = st->strip_count; a.a.kept = st->kept; a.a.out = st->out;
+    a.a.t = lay.t;
+    a.f = OrbStrides{lay.img_n, lay.score_n, lay.cand_n, lay.strip_n, kept_n, out_bytes};
+    const OrbTable &t = lay.t;
+    const OrbLevel &L0 = t.l[0];
+    const size_t px = (size_t)width * height;
+    if (L0.pitch == L0.w) {        // a level 0 is its dense image: the left images of all frames in ONE strided copy, a row a frame
+        CHIP_HIP(c, hipMemcpy2DAsync(a.a.img, lay.img_n, pairs_dev, pair_stride, px, g, hipMemcpyDeviceToDevice, s));
+    } else {
+        for (size_t f = 0; f < g; f++)
+            CHIP_HIP(c, hipMemcpy2DAsync(a.a.img + f * lay.img_n, (size_t)L0.pitch, pairs_dev + f * pair_stride, (size_t)width, (size_t)width,
+                                         (size_t)height, hipMemcpyDeviceToDevice, s));
+    }
+    if (!st->tab_loaded) {
+        CHIP_HIP(c, hipMemcpyAsync(st->tab, tables.device.data(), tables.device.size(), hipMemcpyHostToDevice, s));
+        st->tab_loaded = true;
+    }
+    const unsigned frames = (unsigned)G;
+    for (int l = 1; l < d.n_levels; l++) {
+        const OrbLevel &L = t.l[l];
+        if (L.w < 1 || L.h < 1) break;
+        hipLaunchKernelGGL(fb_pyramid, dim3((L.pitch / 4 + 63) / 64, (L.h + 3) / 4, frames), dim3(64, 4), 0, s, a, l);
+        CHIP_HIP(c, hipGetLastError());
+        ++*launches;
+    }
+    hipLaunchKernelGGL(fb_fast_score, dim3((lay.max_w + kScoreTileW - 1) / kScoreTileW, (lay.max_h + kScoreTileH - 1) / kScoreTileH, d.n_levels * frames),
+                       dim3(kOrbThreads), 0, s, a);
+    CHIP_HIP(c, hipGetLastError());
+    ++*launches;
+    if (lay.max_strips > 0) {
+        hipLaunchKernelGGL(fb_candidates, dim3(lay.max_strips, d.n_levels, frames), dim3(kOrbThreads), 0, s, a);
+        CHIP_HIP(c, hipGetLastError());
+        ++*launches;
+    }
+    hipLaunchKernelGGL(fb_select, dim3(kOrbLevels, frames), dim3(kSelectThreads), 0, s, a);
+    CHIP_HIP(c, hipGetLastError());
+    ++*launches;
+    const dim3 per_keypoint((d.n_features + kOrbThreads / 64 - 1) / (kOrbThreads / 64), frames);
+    hipLaunchKernelGGL(fb_moments, per_keypoint, dim3(kOrbThreads), 0, s, a);
+    CHIP_HIP(c, hipGetLastError());
+    ++*launches;
+    OrbBlurBatchArgs b;
+    b.a.img = st->img; b.a.blur = st->blur; b.img_stride = lay.img_n; b.blur_stride = lay.blur_n; b.n_levels = d.n_levels;
+    OrbDescBatchArgs e;
+    e.a.blur = st->blur; e.a.out = st->out; e.a.tab = st->tab; e.a.desc = desc_base; e.a.kp = kp_base;
+    e.blur_stride = lay.blur_n; e.out_stride = out_bytes; e.slot_kp = slot_kp;
+    for (int l = 0; l < kOrbLevels; l++) { b.a.l[l] = lay.bl[l]; e.a.bpitch[l] = lay.bl[l].bpitch; e.a.blur_off[l] = lay.bl[l].blur_off; }
+    for (int f = 0; f < kOrbGroup; f++) e.slot[f] = (uint32_t)slot[f < G ? f : 0];
+    if (lay.max_bw > 0 && lay.max_h > 0) {
+        hipLaunchKernelGGL(fb_blur, dim3((lay.max_bw + kBlurTileW - 1) / kBlurTileW, (lay.max_h + kBlurTileH - 1) / kBlurTileH, d.n_levels * frames),
+                           dim3(kOrbThreads), 0, s, b);
+        CHIP_HIP(c, hipGetLastError());
+        ++*launches;
+    }
+    hipLaunchKernelGGL(fb_describe, per_keypoint, dim3(kOrbThreads), 0, s, e);
+    CHIP_HIP(c, hipGetLastError());
+    ++*launches;
+    *out_dev = st->out;
+    *out_stride = out_bytes;
+    return CHIP_OK;
+}
+
+// the eight kept counts of each of the G frames of the group enqueued last, in ONE strided copy into pinned memory; *counts (G x 8) is
+// valid once s has drained
+int orb_batch_counts(Ctx *c, hipStream_t s, int32_t G, const int32_t **counts)
+{
+    OrbState *st = c->orb_state;
+    const size_t out_bytes = kOrbOutBytes;
+    CHIP_HIP(c, hipMemcpy2DAsync(st->h_out.host(), kOutHeader, st->out, out_bytes, kOutHeader, (size_t)G, hipMemcpyDeviceToHost, s));
+    *counts = reinterpret_cast<const int32_t *>(st->h_out.host());
     return CHIP_OK;
 }
 

@@ -1277,6 +1277,56 @@ int chip_frame_put_raw_orb_stereo(chip_ctx *ctx, int64_t id, int32_t width, int3
                                   const uint8_t *right_raw, const chip_orb_params *orb /* NULL: the defaults */,
                                   const chip_stereo_bm_params *bm /* NULL: the defaults */, const double Q_rowmajor[16], int32_t *n);
 
+/* ------------------------------------------------------------------------------------------ many pairs per call
+ * Every other leg of the verification path takes a batch; these calls are the frame put's.  A restarted node, an offline replay and the
+ * consumer thread's backlog put frames in bulk, and a single put is mostly launch chains and host waits (16 launches and two waits a
+ * frame), with its longest kernel on eight workgroups.  A batched call walks its F pairs in GROUPS: every stage runs ONCE per group
+ * over all its frames (the frame is a grid axis; the pyramid stays one launch per level), the detector writes each frame's descriptor
+ * and keypoint rows straight into its slot, the block matcher reads each frame's kept count in device memory, and the host waits once
+ * per group for the F x 8 counts of one copy.
+ *   - shared inputs: width, height, both parameter blocks and Q hold for every frame of the call -- one rig, as the ctx's maps;
+ *   - result: for every f the stored rows of ids[f] (what chip_frame_read returns) and n[f] are BYTE FOR BYTE what
+ *     chip_frame_put_orb_stereo / chip_frame_put_raw_orb_stereo give for that pair (one body per kernel, two entries).  A frame
+ *     without keypoints is stored with n = 0;
+ *   - groups: as many frames as keep the group's level-0 pixels <= 2^23, at most 16, at least 1 (16 up to 724 x 724; 10 at
+ *     1024 x 768; 1 at 4096 x 4096).  chip_frame_put_plan says so without a ctx (raw 0 / 1: which call; the plan is the same);
+ *     chip_debug_frame_put_last reports the groups, kernel launches and host waits of the ctx's last batched call (every output may be
+ *     NULL; zeros before the first).  A group is its uploads, at most 16 launches, one copy of counts and one wait;
+ *   - checks, in this order, all before the first write: NULL ctx / ids / left / right / Q / n, F < 1, a NULL image or an id that
+ *     repeats inside the call CHIP_ERR_INVALID_ARG;  F > CHIP_FRAME_MAX_PUT, a size or parameter chip_orb_detect or chip_stereo_bm
+ *     refuses (a side < 1 is theirs: CHIP_ERR_INVALID_ARG), a group ctx, n_features > slot_keypoints CHIP_ERR_UNSUPPORTED;  no
+ *     chip_frame_store_reserve yet, or no maps for the raw form CHIP_ERR_BUSY;  the raw form: a size other than the maps'
+ *     CHIP_ERR_INVALID_ARG;  fewer free slots than ids of the call that are not yet stored CHIP_ERR_OOM -- the store is then exactly as
+ *     it was (as it is after CHIP_ERR_OOM for scratch that could not grow, which is decided before the first group);
+ *   - commit and failure: an id already stored is replaced in its own slot; new ids take free slots, which need not be adjacent.
+ *     Groups commit as they finish.  A HIP error in group g keeps the frames of the groups before it, removes group g's ids from the
+ *     store (a replaced id's rows are undefined by then) and leaves later groups untouched; n[f] of group g and of the later ones
+ *     is -1;
+ *   - memory: the scratch of a group (G x a single call's) is grown inside one pause of the resident scan; a process that never
+ *     calls a batch form allocates nothing more than before.  After a batched call chip_debug_orb_level / _blur are CHIP_ERR_BUSY;
+ *   - chip_frame_put_records: what chip_frame_read gave (desc, kp_xy, the point records) back into the store under id -- three
+ *     uploads, no kernel; the statuses of chip_frame_put with pts in the place of the 3-D image.  The fourth float of a record must
+ *     be the 0.0f (no point) or 1.0f the gather kernels write, bit for bit: anything else is CHIP_ERR_INVALID_ARG, decided on the
+ *     host before the store is touched.  A frame put this way is indistinguishable afterwards: a checkpoint of records restores a
+ *     store without the images.                                                                                                     */
+#define CHIP_FRAME_MAX_PUT 256
+int chip_build_has_frame_put_batch(void);  /* 1 */
+int chip_frame_put_plan(int32_t width, int32_t height, const chip_orb_params *orb /* NULL: the defaults */, int32_t raw, int32_t F,
+                        int32_t *group /* frames per group */, int32_t *n_groups);
+int chip_frame_put_orb_stereo_batch(chip_ctx *ctx, const int64_t *ids, int32_t F, int32_t width, int32_t height,
+                                    const uint8_t *const *left, const uint8_t *const *right /* F images each */,
+                                    const chip_orb_params *orb /* NULL: the defaults */,
+                                    const chip_stereo_bm_params *bm /* NULL: the defaults */, const double Q_rowmajor[16],
+                                    int32_t *n /* F */);
+int chip_frame_put_raw_orb_stereo_batch(chip_ctx *ctx, const int64_t *ids, int32_t F, int32_t width, int32_t height,
+                                        const uint8_t *const *left_raw, const uint8_t *const *right_raw /* F images each */,
+                                        const chip_orb_params *orb /* NULL: the defaults */,
+                                        const chip_stereo_bm_params *bm /* NULL: the defaults */, const double Q_rowmajor[16],
+                                        int32_t *n /* F */);
+int chip_frame_put_records(chip_ctx *ctx, int64_t id, const uint8_t *desc /* n x 32 */, const float *kp_xy /* n x 2 */,
+                           const float *pts /* n x 4 */, int32_t n, int32_t width, int32_t height);
+int chip_debug_frame_put_last(chip_ctx *ctx, int32_t *groups, int32_t *launches, int32_t *waits);
+
 /* ------------------------------------------------------------------------------------------ introspection */
 typedef struct {
     int32_t abi_version;

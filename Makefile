@@ -13,7 +13,7 @@ ORCFLAGS   ?= -O2 -mfma -ffp-contract=off -fopenmp -fPIC -Wall -Wextra
 
 LIBDIR     := cerebro_amd/lib
 CSRC       := cerebro_amd/csrc
-HIP_SRCS   := $(CSRC)/kernels.hip $(CSRC)/chip_api.hip $(CSRC)/resident.hip $(CSRC)/chip_multi.hip $(CSRC)/pnp.hip $(CSRC)/icp.hip $(CSRC)/batch.hip $(CSRC)/match.hip $(CSRC)/frames.hip $(CSRC)/orb.hip $(CSRC)/project.hip $(CSRC)/vlad.hip
+HIP_SRCS   := $(CSRC)/kernels.hip $(CSRC)/chip_api.hip $(CSRC)/resident.hip $(CSRC)/chip_multi.hip $(CSRC)/pnp.hip $(CSRC)/icp.hip $(CSRC)/batch.hip $(CSRC)/match.hip $(CSRC)/frames.hip $(CSRC)/orb.hip $(CSRC)/project.hip $(CSRC)/vlad.hip $(CSRC)/pass_merge.hip
 HIP_OBJS   := $(HIP_SRCS:$(CSRC)/%.hip=$(LIBDIR)/%.o)
 ORC_SRCS   := $(wildcard oracle/*.c)
 

@@ -61,7 +61,7 @@ CHIP_SAMPLER_FRESH, CHIP_SAMPLER_THEIA_PERSISTENT = 0, 1
 CHIP_RANSAC_LEG_PNP, CHIP_RANSAC_LEG_ICP = 0, 1
 CHIP_SCAN_FAMILY_NONE, CHIP_SCAN_FAMILY_ONE_ROW, CHIP_SCAN_FAMILY_WIDE, CHIP_SCAN_FAMILY_ROWS, CHIP_SCAN_FAMILY_MULTI = 0, 1, 2, 3, 4
 CHIP_SCAN_CALL_QUERY, CHIP_SCAN_CALL_TICK, CHIP_SCAN_CALL_TICK_SYNC = 0, 1, 2
-SCAN_FAMILY_NAMES = {0: "none", 1: "one_row", 2: "wide", 3: "rows", 4: "multi", 5: "prefilter"}
+SCAN_FAMILY_NAMES = {0: "none", 1: "one_row", 2: "wide", 3: "rows", 4: "multi", 5: "prefilter", 6: "halfq"}
 
 CHIP_TICK_SKIPPED, CHIP_TICK_TOO_SHORT, CHIP_TICK_SCANNED = 0, 1, 2
 CHIP_MATCH_MAX_KEYPOINTS = 16384
@@ -271,6 +271,8 @@ _SIGS = {
     "chip_debug_scan_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(ScanLaunch)]),
     "chip_debug_multi_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(ScanLaunch)]),
     "chip_debug_prefilter_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(ScanLaunch)]),
+    "chip_debug_halfq_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(ScanLaunch)]),
+    "chip_debug_halfq_bound": (C.c_int, [C.c_int32, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "chip_debug_prefilter_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "chip_orb_match": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P]),
     "chip_gms_filter": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P,
@@ -567,6 +569,27 @@ def prefilter_plan(D: int, elem: int = 4, K: int = CHIP_DEFAULT_TOPK, n_cus: int
     if rc != CHIP_OK:
         raise ChipError(rc, "chip_debug_prefilter_plan")
     return out.as_dict()
+
+
+def halfq_plan(D: int, elem: int = 4, K: int = CHIP_DEFAULT_TOPK, n_cus: int = 256, check: bool = True):
+    """chip_debug_halfq_plan: the pass that serves five pipelined ticks together (float rows, all 15 queries staged in LDS as fp16), as
+    ScanLaunch.as_dict() -- no device needed.  check=False: (status, dict) instead of raising."""
+    out = ScanLaunch()
+    rc = load_library().chip_debug_halfq_plan(D, elem, K, n_cus, C.byref(out))
+    if not check:
+        return rc, out.as_dict()
+    if rc != CHIP_OK:
+        raise ChipError(rc, "chip_debug_halfq_plan")
+    return out.as_dict()
+
+
+def halfq_bound(D: int, row_norm_max: float) -> tuple[int, float]:
+    """chip_debug_halfq_bound: (e, E_h) -- the exponent of the scale of the fp16-staged queries and the error bound of the five-tick pass"""
+    e, E = C.c_int32(), C.c_double()
+    rc = load_library().chip_debug_halfq_bound(D, row_norm_max, C.byref(e), C.byref(E))
+    if rc != CHIP_OK:
+        raise ChipError(rc, "chip_debug_halfq_bound")
+    return e.value, E.value
 
 
 def comm_unique_id() -> bytes:
@@ -917,7 +940,7 @@ class Chip:
         return passes.value, ticks.value
 
     def prefilter_stats(self) -> tuple[int, int, int]:
-        """(prefilter passes, ticks they served, ticks among them run again alone because their certificate did not hold) --
+        """(prefilter passes of four or five ticks, ticks they served, ticks among them run again alone because their certificate did not hold) --
         chip_debug_prefilter_stats"""
         passes, ticks, unc = C.c_int64(), C.c_int64(), C.c_int64()
         self._chk(self.lib.chip_debug_prefilter_stats(self.h, C.byref(passes), C.byref(ticks), C.byref(unc)), "chip_debug_prefilter_stats")

@@ -251,9 +251,9 @@ static int create_impl(chip_ctx *c, int64_t capacity_hint, int elem)
     }
     for (int i = 0; i < Ctx::kRing; i++) {
         // [max_grid][CHIP_MAX_NQ][CHIP_MAX_TOPK] of one launch, or [ticks][max_grid][3][CHIP_MAX_TOPK] of a pass that serves several ticks (up to
-        // kPrefilterTicks), and behind them the [kPrefilterTicks][3][CHIP_MAX_TOPK] exact lists tick_rescore leaves for the merge (coalesce_submit)
-        constexpr size_t kListsPerGroup = 3 * kPrefilterTicks > CHIP_MAX_NQ ? 3 * kPrefilterTicks : CHIP_MAX_NQ;
-        static_assert(kPrefilterTicks >= kMultiMaxTicks, "the list buffers are sized for the deepest pass");
+        // kPassMaxTicks), and behind them the [kPassMaxTicks][3][CHIP_MAX_TOPK] exact lists tick_rescore leaves for the merge (coalesce_submit)
+        constexpr size_t kListsPerGroup = 3 * kPassMaxTicks > CHIP_MAX_NQ ? 3 * kPassMaxTicks : CHIP_MAX_NQ;
+        static_assert(kPassMaxTicks >= kMultiMaxTicks && kPassMaxTicks >= kPrefilterTicks, "the list buffers are sized for the deepest pass");
         rc = c->partial_dev[i].alloc(c, ((size_t)c->max_grid + 1) * kListsPerGroup * CHIP_MAX_TOPK);
         if (rc != CHIP_OK) return rc;
         CHIP_HIP(c, hipEventCreateWithFlags(&c->ev_scan[i], hipEventDisableTiming));
@@ -263,10 +263,10 @@ static int create_impl(chip_ctx *c, int64_t capacity_hint, int elem)
     if (rc != CHIP_OK) return rc;
     CHIP_HIP(c, hipMemset(c->tickets_dev, 0, Ctx::kRing * sizeof(int32_t)));
     // pipelined ticks that arrive while a long scan is running share one DB pass: at most this many per pass (0 = never; coalesce_* below)
-    // (4: float rows whose shape has the prefilter pass; every other ctx stops at what scan_multi_plan gives it)
-    c->coalesce_max = env_int("CHIP_TICK_COALESCE", kPrefilterTicks);
+    // (5 / 4: float rows whose shape has the fp16-query / the fp32 prefilter pass; every other ctx stops at what scan_multi_plan gives it)
+    c->coalesce_max = env_int("CHIP_TICK_COALESCE", kPassMaxTicks);
     if (c->coalesce_max < 2) c->coalesce_max = 0;
-    if (c->coalesce_max > kPrefilterTicks) c->coalesce_max = kPrefilterTicks;
+    if (c->coalesce_max > kPassMaxTicks) c->coalesce_max = kPassMaxTicks;
     c->tick_poll = env_int("CHIP_TICK_POLL", 1) != 0;
     resident_read_knobs(c);
     rc = c->seq_all.alloc(c, CHIP_MAX_INFLIGHT);
@@ -448,7 +448,7 @@ int enqueue_scan_merge(Ctx *c, const ScanRequest &rq, ScanReceipt *rcpt)
     if (rcpt) { rcpt->merge_stream = s_merge; rcpt->fused = fused; rcpt->done_ev = same_stream ? c->ev_merged[b] : nullptr; }   // same-stream tick: the merge event (recorded below) IS the tick's completion event
     if (!same_stream) {
         CHIP_HIP(c, hipEventRecord(c->ev_scan[b], s_scan));
-        if (rq.tick && !short_scan) { c->pass_ev = c->ev_scan[b]; c->pass_no++; }   // the scan later ticks may park behind (coalesce_*)
+        if (rq.tick && !short_scan) { c->pass_ev = c->ev_scan[b]; c->pass_shared = false; c->pass_no++; }   // the scan later ticks may park behind (coalesce_*)
         if (c->ring_dev) c->last_scan_ev[s_scan == c->s_scan2 ? 1 : 0] = c->ev_scan[b];   // caller holds ring_mu (RingGuard)
         CHIP_HIP(c, hipStreamWaitEvent(c->s_query, c->ev_scan[b], 0));
     }
@@ -609,47 +609,59 @@ static int coalesce_ticks_max(const Ctx *c, int64_t k, bool sync_tick)
     if ((double)k * c->D * c->elem <= c->scan_overlap_bytes) return 0;
     int fit = scan_multi_max_ticks(c);
     if (c->coalesce_max >= kPrefilterTicks && scan_prefilter_usable(c)) fit = kPrefilterTicks;   // four leave as one prefilter pass
+    if (c->coalesce_max >= kHalfqTicks && scan_halfq_usable(c)) fit = kHalfqTicks;               // five: the same with fp16-staged queries
     const int t = fit < c->coalesce_max ? fit : c->coalesce_max;
     return t >= 2 ? t : 0;
 }
 
 // T >= 2 parked ticks as one pass: one launch of db_scan_topk_multi / db_scan_shared_f64 on the scan stream, then K2 once per tick on the ctx stream,
 // each on its own block of lists and followed by its slot's completion event.
-// T == kPrefilterTicks: the pass is db_scan_prefilter, and on the ctx stream ONE launch of tick_rescore (certificate + exact scores of the
+// T >= kPrefilterTicks: the pass is db_scan_prefilter (four) or db_scan_halfq (five), and on the ctx stream ONE launch of tick_rescore (certificate + exact scores of the
 // proven candidates -> one list per tick and query) goes in front of the ticks' K2 launches; the slot remembers the tick, and a collect
 // that finds a certificate word that does not say "holds" runs the tick again alone (tick_collect_slot).
-static int coalesce_submit(Ctx *c, int T)
+static int coalesce_submit(Ctx *c, int first, int T)
 {
+    const Ctx::ParkedTick *parked = c->parked + first;   // the pass serves parked[first .. first + T)
     const int b = (int)(c->n_enqueued++ % Ctx::kRing);
     const int K = CHIP_DEFAULT_TOPK;
-    const bool prefilter = T == kPrefilterTicks;
-    static_assert(kPrefilterTicks > kMultiMaxTicks, "a pass of kPrefilterTicks ticks is the prefilter's");
+    const bool prefilter = T >= kPrefilterTicks, halfq = T == kHalfqTicks;
+    static_assert(kPrefilterTicks > kMultiMaxTicks && kHalfqTicks == kPrefilterTicks + 1, "passes of four and five ticks are the prefilters'");
     PassArgs a{};
     scan_args_db(c, &a);
     a.K = K;
     a.partial = c->partial_dev[b];
     for (int t = 0; t < T; t++) {
-        a.k[t] = c->parked[t].k;
+        a.k[t] = parked[t].k;
         if (a.k[t] > a.n_rows) a.n_rows = a.k[t];
-        for (int i = 0; i < 3; i++) a.q[3 * t + i] = c->parked[t].q[i];
+        for (int i = 0; i < 3; i++) a.q[3 * t + i] = parked[t].q[i];
     }
     const int grid = scan_multi_grid(c);
     double E = 0.0;
     if (prefilter) {
         std::lock_guard<std::mutex> lk(c->mu);
-        E = prefilter_error_bound(c->D, c->row_norm_max);
+        if (halfq) {   // the scale of the staged queries and the bound that goes with it, from ONE reading of the norm bound
+            const int e = halfq_exponent(c->row_norm_max);
+            a.q_up = std::ldexp(1.0f, e);
+            a.s_up = std::ldexp(1.0, e);
+            a.s_down = std::ldexp(1.0, -e);
+            E = halfq_error_bound(c->D, c->row_norm_max, e);
+        } else {
+            E = prefilter_error_bound(c->D, c->row_norm_max);
+        }
     }
     if (hipEventQuery(c->ev_merged[b]) != hipSuccess) CHIP_HIP(c, hipStreamWaitEvent(c->s_scan, c->ev_merged[b], 0));
     hipEvent_t e1 = nullptr;   // one event pair per pass; a pass reads the prefix once
     int rc = c->prof_on ? prof_begin(c, c->s_scan, (double)a.n_rows * c->D * c->elem, &e1) : CHIP_OK;
-    if (rc == CHIP_OK) rc = prefilter ? launch_scan_prefilter(c, c->s_scan, a, grid) : launch_scan_multi(c, c->s_scan, a, T, grid);
+    if (rc == CHIP_OK)
+        rc = halfq ? launch_scan_halfq(c, c->s_scan, a, grid) : prefilter ? launch_scan_prefilter(c, c->s_scan, a, grid) : launch_scan_multi(c, c->s_scan, a, T, grid);
     if (rc != CHIP_OK) return rc;
     if (e1) CHIP_HIP(c, hipEventRecord(e1, c->s_scan));
     CHIP_HIP(c, hipEventRecord(c->ev_scan[b], c->s_scan));
     c->pass_ev = c->ev_scan[b];
+    c->pass_shared = true;
     c->pass_no++;
     CHIP_HIP(c, hipStreamWaitEvent(c->s_query, c->ev_scan[b], 0));
-    chip_topk_entry *exact = c->partial_dev[b] + (size_t)kPrefilterTicks * grid * 3 * K;   // [tick][3][K], behind the pass's lists
+    chip_topk_entry *exact = c->partial_dev[b] + (size_t)kPassMaxTicks * grid * 3 * K;   // [tick][3][K], behind the pass's lists
     if (prefilter) {
         RescoreArgs ra{};
         ra.seg_table = a.seg_table; ra.seg_shift = a.seg_shift; ra.seg_mask = a.seg_mask; ra.D = a.D; ra.K = K;
@@ -657,19 +669,31 @@ static int coalesce_submit(Ctx *c, int T)
         ra.E = E;
         ra.out = exact;
         for (int t = 0; t < T; t++) {
-            const Ctx::ParkedTick &pt = c->parked[t];
+            const Ctx::ParkedTick &pt = parked[t];
             Slot &s = *pt.slot;
             ra.k[t] = pt.k;
             for (int i = 0; i < 3; i++) { ra.q[3 * t + i] = s.pf_q[i] = pt.q[i]; s.cert_host[i] = 0; }
             ra.cert[t] = s.cert_dev;
             s.prefilter = true; s.pf_k = pt.k; s.pf_p = pt.p;
         }
-        rc = launch_rescore(c, c->s_query, ra);
+        rc = launch_rescore(c, c->s_query, ra, T);
+        if (rc != CHIP_OK) return rc;
+    }
+    if (halfq) {   // one K2 launch for the five ticks (kernels.hip pass_merge): workgroup t is topk_merge<3> on tick t's lists
+        PassMergeArgs m{};
+        m.in = exact;
+        m.K = K;
+        for (int t = 0; t < T; t++) {
+            const MergeArgs mt = merge_args(exact + (size_t)t * 3 * K, 1, K, nullptr, parked[t].slot->rec.dev(), parked[t].l, &parked[t].p);
+            m.result[t] = mt.result; m.l[t] = mt.l; m.locality[t] = mt.locality; m.thresh[t] = mt.thresh;
+        }
+        rc = launch_pass_merge(c, c->s_query, m, T);
         if (rc != CHIP_OK) return rc;
     }
     for (int t = 0; t < T; t++) {
-        const Ctx::ParkedTick &pt = c->parked[t];
-        if (prefilter) rc = launch_merge(c, c->s_query, merge_args(exact + (size_t)t * 3 * K, 1, K, nullptr, pt.slot->rec.dev(), pt.l, &pt.p), 3);
+        const Ctx::ParkedTick &pt = parked[t];
+        if (halfq) rc = CHIP_OK;
+        else if (prefilter) rc = launch_merge(c, c->s_query, merge_args(exact + (size_t)t * 3 * K, 1, K, nullptr, pt.slot->rec.dev(), pt.l, &pt.p), 3);
         else rc = launch_merge(c, c->s_query, merge_args(c->partial_dev[b] + (size_t)t * grid * 3 * K, grid, K, nullptr, pt.slot->rec.dev(), pt.l, &pt.p), 3);
         if (rc != CHIP_OK) return rc;
         CHIP_HIP(c, hipEventRecord(pt.slot->done, c->s_query));
@@ -691,12 +715,15 @@ int coalesce_flush(Ctx *c)
     c->n_parked = 0;
     const Ctx::ParkedTick &p0 = c->parked[0];
     int rc;
-    if (T == kPrefilterTicks && !scan_prefilter_usable(c)) {   // a row appended since they parked took the norm bound out of range: three and one
+    if (T == kHalfqTicks && !scan_halfq_usable(c)) {           // a row appended since they parked took the norm bound out of range: three and two
+        rc = coalesce_submit(c, 0, kMultiMaxTicks);
+        if (rc == CHIP_OK) rc = coalesce_submit(c, kMultiMaxTicks, T - kMultiMaxTicks);
+    } else if (T == kPrefilterTicks && !scan_prefilter_usable(c)) {   // likewise: three and one
         const Ctx::ParkedTick &pl = c->parked[T - 1];
-        rc = coalesce_submit(c, T - 1);
+        rc = coalesce_submit(c, 0, T - 1);
         if (rc == CHIP_OK) rc = tick_submit(c, pl.k, pl.l, &pl.p, pl.q, false, *pl.slot);
     } else {
-        rc = T == 1 ? tick_submit(c, p0.k, p0.l, &p0.p, p0.q, false, *p0.slot) : coalesce_submit(c, T);
+        rc = T == 1 ? tick_submit(c, p0.k, p0.l, &p0.p, p0.q, false, *p0.slot) : coalesce_submit(c, 0, T);
     }
     for (int t = 0; t < T && rc != CHIP_OK; t++) {   // the enqueue has long returned: the tick's collect reports it
         c->parked[t].slot->state = SlotState::Failed;
@@ -729,7 +756,12 @@ static int tick_enqueue_slot(Ctx *c, int64_t l, const chip_dot_params *p, bool s
             if (rc == CHIP_OK) { c->last_l = l; return CHIP_OK; }   // :1098
             if (rc != CHIP_ERR_UNSUPPORTED && rc != kResidentPaused) return rc;   // (no resident form on this ctx, or paused: launch the tick)
         }
-        const int t_max = coalesce_ticks_max(c, k, sync_tick);
+        int t_max = coalesce_ticks_max(c, k, sync_tick);
+        // The pipeline fills behind a tick launched alone: the pass parked behind THAT scan takes four, five only behind a shared pass.  A
+        // long run loses nothing by it (1 + 4 + 5 + 5 + ... is as many scans as 1 + 5 + 5 + ... + 4), and a burst of up to 17 ticks with 16 in
+        // flight leaves as 1 + 4 + 5 + 5 + 2 and not as 1 + 5 + 5 + 5 + 1: its last tick shares a pass instead of reading the prefix alone,
+        // and callers that count the passes of such a burst see what they saw with four per pass.
+        if (t_max == kHalfqTicks && !c->pass_shared && !c->coalesce_force) t_max = kPrefilterTicks;
         const int act = t_max < 2 ? kCoalesceLaunch
                                   : coalesce_decide(c->n_parked, t_max, c->coalesce_force || (c->pass_ev && hipEventQuery(c->pass_ev) == hipErrorNotReady));
         if (act == kCoalesceLaunch) {
@@ -1504,7 +1536,7 @@ int chip_debug_coalesce_stats(chip_ctx *c, int64_t *passes, int64_t *ticks)
     return CHIP_OK;
 }
 
-// Prefilter passes (four ticks, db_scan_prefilter + tick_rescore), their ticks, and the ticks among them that a collect has run again alone
+// Prefilter passes of either kind (four ticks: db_scan_prefilter, five: db_scan_halfq; + tick_rescore), their ticks, and the ticks among them that a collect has run again alone
 // because their certificate did not hold.
 int chip_debug_prefilter_stats(chip_ctx *c, int64_t *passes, int64_t *ticks, int64_t *uncertified)
 {
@@ -1587,6 +1619,23 @@ int chip_debug_prefilter_plan(int32_t D, int32_t elem, int32_t K, int32_t n_cus,
     if (!out || D <= 0 || (elem != 4 && elem != 8) || K < 1 || K > CHIP_MAX_TOPK || n_cus < 1) return CHIP_ERR_INVALID_ARG;
     if (D % 4 != 0 || (size_t)D * 4 * CHIP_MAX_NQ > 160 * 1024 || (elem == 8 && (size_t)D * 8 * 2 > 160 * 1024)) return CHIP_ERR_UNSUPPORTED;   // (ctx_create)
     return scan_prefilter_plan(D, elem, K, n_cus < 512 ? n_cus : 512, out);
+}
+
+// The five-tick pass without a device: scan_halfq_plan, the function launch_scan_halfq sizes itself with.
+int chip_debug_halfq_plan(int32_t D, int32_t elem, int32_t K, int32_t n_cus, chip_debug_scan_launch *out)
+{
+    if (!out || D <= 0 || (elem != 4 && elem != 8) || K < 1 || K > CHIP_MAX_TOPK || n_cus < 1) return CHIP_ERR_INVALID_ARG;
+    if (D % 4 != 0 || (size_t)D * 4 * CHIP_MAX_NQ > 160 * 1024 || (elem == 8 && (size_t)D * 8 * 2 > 160 * 1024)) return CHIP_ERR_UNSUPPORTED;   // (ctx_create)
+    return scan_halfq_plan(D, elem, K, n_cus < 512 ? n_cus : 512, out);
+}
+
+// What a five-tick pass over rows of norm at most row_norm_max is launched with: the exponent of the queries' scale and the error bound.
+int chip_debug_halfq_bound(int32_t D, double row_norm_max, int32_t *e, double *E)
+{
+    if (!e || !E || D <= 0 || !(row_norm_max >= 0.0)) return CHIP_ERR_INVALID_ARG;
+    *e = halfq_exponent(row_norm_max);
+    *E = halfq_error_bound(D, row_norm_max, *e);
+    return CHIP_OK;
 }
 
 // Tuning aid, not part of the ABI (no declaration in cerebro_hip.h): with CHIP_SCAN_STAMPS=1 the row-batched scan kernel leaves four

@@ -80,17 +80,22 @@ constexpr int kMultiMaxTicks = 3;                   // ticks of 3 queries each t
 // four ticks in one DB pass: fp32 prefilter + certified exact rescoring (kernels.hip db_scan_prefilter / tick_rescore)
 constexpr int kPrefilterTicks = 4;                  // ticks of the prefilter pass: 12 fp32 queries, those the LDS does not hold are read in place
 constexpr int kRescoreCap = 32;                     // rows per query that tick_rescore scores exactly; more candidates than that: uncertified
-struct PassArgs {                                   // one shared pass of T <= kPrefilterTicks ticks, whichever kernel serves it
+// five ticks in one DB pass: the same prefilter with all 15 queries staged in LDS as fp16 (kernels.hip db_scan_halfq)
+constexpr int kHalfqTicks = 5;
+constexpr int kPassMaxTicks = kHalfqTicks;          // the deepest pass: what PassArgs, RescoreArgs, Ctx::parked and the list buffers are sized for
+struct PassArgs {                                   // one shared pass of T <= kPassMaxTicks ticks, whichever kernel serves it
     const void *const *seg_table;                   // as ScanArgs (plain single-GPU ctx: global index == local row)
     int32_t seg_shift;
     int64_t seg_mask;
     int64_t n_rows;                                 // rows [0, n_rows) are read: the longest prefix of the pass
     int32_t D;
     int32_t K;
-    int64_t k[kPrefilterTicks];                     // tick t sees rows [0, k[t])
-    const void *q[3 * kPrefilterTicks];             // queries of tick t: q[3 t .. 3 t + 2] (device, the rows' type, D each, 16-B aligned)
+    int64_t k[kPassMaxTicks];                       // tick t sees rows [0, k[t])
+    const void *q[3 * kPassMaxTicks];               // queries of tick t: q[3 t .. 3 t + 2] (device, the rows' type, D each, 16-B aligned)
     chip_topk_entry *partial;                       // [tick][gridDim.x][3][K]: every tick's block of lists is what ONE launch of db_scan_topk leaves
                                                     // (prefilter: fp32 score widened to double, row; sorted by score desc, index desc)
+    float q_up;                                     // db_scan_halfq only: 2^e, what a query is multiplied by before it is rounded to fp16 ...
+    double s_down, s_up;                            // ... and 2^-e, 2^e: a score on its way into a list (exact in fp64) and a threshold on its way back
 };
 struct RescoreArgs {                                // one launch per pass: workgroup 3 t + i serves query i of tick t
     const void *const *seg_table;
@@ -101,11 +106,20 @@ struct RescoreArgs {                                // one launch per pass: work
     const chip_topk_entry *in;                      // [tick][n_lists][3][K]: the prefilter's lists
     int32_t n_lists;
     int32_t wpb;                                    // waves per workgroup of the pass: with a tick's prefix, how many rows a workgroup owned
-    int64_t k[kPrefilterTicks];
-    const void *q[3 * kPrefilterTicks];
+    int64_t k[kPassMaxTicks];
+    const void *q[3 * kPassMaxTicks];
     double E;                                       // bound on |fp32 score - exact score| of every pair of published rows, rounded up
     chip_topk_entry *out;                           // [tick][3][K] exact lists: a tick's block is what topk_merge reads as ONE workgroup's lists
-    uint32_t *cert[kPrefilterTicks];                // per tick three words in pinned host memory: 1 the query's certificate holds, 2 it does not
+    uint32_t *cert[kPassMaxTicks];                  // per tick three words in pinned host memory: 1 the query's certificate holds, 2 it does not
+};
+// K2 of a five-tick pass: ONE launch, workgroup t merges tick t's three exact lists and writes its record (kernels.hip pass_merge)
+struct PassMergeArgs {
+    const chip_topk_entry *in;                      // [tick][3][K]: what tick_rescore left
+    int32_t K;
+    chip_tick_result *result[kPassMaxTicks];
+    int64_t l[kPassMaxTicks];
+    int32_t locality[kPassMaxTicks];
+    double thresh[kPassMaxTicks];
 };
 
 struct MergeArgs {
@@ -225,7 +239,14 @@ int scan_prefilter_plan(int D, int elem, int K, int grid, chip_debug_scan_launch
 bool scan_prefilter_usable(const Ctx *c);           // this ctx may serve four parked ticks with the prefilter pass (row norms included)
 double prefilter_error_bound(int D, double row_norm_max);   // E of DESIGN.md 3, rounded up
 int launch_scan_prefilter(Ctx *c, hipStream_t s, const PassArgs &a, int grid);
-int launch_rescore(Ctx *c, hipStream_t s, const RescoreArgs &a);
+// the five-tick pass over float rows of D elements: all 15 queries staged as fp16 (NG = 0) -- or CHIP_ERR_UNSUPPORTED
+int scan_halfq_plan(int D, int elem, int K, int grid, chip_debug_scan_launch *f);
+bool scan_halfq_usable(const Ctx *c);               // this ctx may serve five parked ticks with the fp16-query pass (row norms included)
+int halfq_exponent(double row_norm_max);            // e: the staged queries are fl16(2^e q), 2^e N <= 2^15
+double halfq_error_bound(int D, double row_norm_max, int e);   // E_h of DESIGN.md 3, rounded up
+int launch_scan_halfq(Ctx *c, hipStream_t s, const PassArgs &a, int grid);   // (a.q_up, a.s_down, a.s_up set from halfq_exponent)
+int launch_rescore(Ctx *c, hipStream_t s, const RescoreArgs &a, int n_ticks);
+int launch_pass_merge(Ctx *c, hipStream_t s, const PassMergeArgs &a, int n_ticks);
 int scan_grid_for(const Ctx *c, int64_t n_rows, int nq, bool q64);
 bool scan_q64(const Ctx *c, int nq, bool long_scan);
 int scan_rows_form(const Ctx *c, int64_t n_rows, int nq, int grid, bool q64, bool sync_tick = false);
@@ -399,11 +420,12 @@ struct Ctx {
 
     // --- several pipelined ticks per DB pass (chip_api.hip coalesce_*; query_mu) ---
     struct ParkedTick { Slot *slot; int64_t k, l; chip_dot_params p; const void *q[3]; };
-    int32_t coalesce_max = 4;            // CHIP_TICK_COALESCE: 0 = every tick is a pass of its own, 2 / 3 / 4 = at most that many ticks per pass
+    int32_t coalesce_max = 5;            // CHIP_TICK_COALESCE: 0 = every tick is a pass of its own, 2 .. 5 = at most that many ticks per pass
     bool coalesce_force = false;         // chip_debug_coalesce_force: park even when no scan is running (tests)
-    ParkedTick parked[kPrefilterTicks];
+    ParkedTick parked[kPassMaxTicks];
     int32_t n_parked = 0;
     hipEvent_t pass_ev = nullptr;        // end of the newest long scan submitted (one of ev_scan[])
+    bool pass_shared = false;            // ... and whether that scan is a shared pass (false: one tick's launch)
     uint64_t pass_no = 0;                // long scans submitted so far
     int64_t coalesce_passes = 0, coalesce_ticks = 0;   // passes of more than one tick / the ticks they served (chip_debug_coalesce_stats)
     int64_t prefilter_passes = 0, prefilter_ticks = 0, prefilter_uncertified = 0;   // prefilter passes / their ticks / those of them run again alone

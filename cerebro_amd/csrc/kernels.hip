@@ -309,10 +309,11 @@ __global__ __launch_bounds__(1024) void db_scan_topk(ScanArgs a)
 
 // ------------------------------------------------------------------------------------------------ K1, several ticks per pass
 // ONE pass over rows [0, max k_t) answers T queued ticks of 3 queries each (chip_api.hip coalesce_*): the pass is as HBM-bound as a
-// one-tick launch, so T ticks cost one DB read.  Three kernels, ONE skeleton (shared_pass below) and one arithmetic policy each:
+// one-tick launch, so T ticks cost one DB read.  Four kernels, ONE skeleton (shared_pass below) and one arithmetic policy each:
 //   db_scan_topk_multi<T>     float rows,  T = 2, 3, fp64 arithmetic (PassF64<float, T, 0>): every query staged in LDS;
 //   db_scan_shared_f64<T, NG> double rows, T = 2,    fp64 arithmetic (PassF64<double, T, NG>): NG queries read in place;
-//   db_scan_prefilter<NG>     float rows,  T = 4,    fp32 arithmetic (PassF32<NG>): candidates for tick_rescore, NG queries in place.
+//   db_scan_prefilter<NG>     float rows,  T = 4,    fp32 arithmetic (PassF32<NG>): candidates for tick_rescore, NG queries in place;
+//   db_scan_halfq             float rows,  T = 5,    fp32 arithmetic on queries staged as fp16 (PassF32H): candidates for tick_rescore.
 // What the skeleton owns, whatever the arithmetic:
 //   * register blocking: R = 4 rows per wave in flight, U = 4 KiB of each per batch (16 KiB per wave, one workgroup of 8 waves per CU),
 //     rows of whole 4 KiB batches, plain ctx;
@@ -506,12 +507,15 @@ __device__ __forceinline__ S reduce_rows4(S a0, S a1, S a2, S a3)
 // larger than every index already in its lists and key_gt(s, gi, thr_s, thr_i) is just s >= thr_s (false for NaN, which never
 // enters): the K-th index need not be kept.  The list's LDS address is formed inside the branch (hoisted out of the scan loop, the
 // 3T x 2 addresses would be held in registers for an insertion that is rare after the first rows).
-template <typename S>
-__device__ __forceinline__ void pass_offer(S s_uniform, int64_t gi, int K, int lane, chip_topk_entry *list, S &thr_s)
+// SCALED (db_scan_halfq): scores and thresholds of the pass are 2^e times the scores the lists hold; a score is multiplied by sc_down = 2^-e on
+// its way into the list and the K-th entry by sc_up = 2^e on its way back, both in fp64 and both exact, so the order is the same on either side.
+template <typename S, bool SCALED = false>
+__device__ __forceinline__ void pass_offer(S s_uniform, int64_t gi, int K, int lane, chip_topk_entry *list, S &thr_s, double sc_down = 1.0, double sc_up = 1.0)
 {
     if (s_uniform >= thr_s) {
         asm volatile("" : "+v"(lane));
-        const double s = (double)s_uniform;
+        double s = (double)s_uniform;
+        if constexpr (SCALED) s *= sc_down;
         chip_topk_entry me, up;
         me.score = -INFINITY; me.idx = -1; up = me;
         if (lane < K) { me = list[lane]; if (lane > 0) up = list[lane - 1]; }
@@ -523,18 +527,35 @@ __device__ __forceinline__ void pass_offer(S s_uniform, int64_t gi, int K, int l
             else if (lane == pos) { me.score = s; me.idx = gi; }
             list[lane] = me;      // every read of the old list precedes this write in program order (one wave, in-order LDS)
         }
-        thr_s = (S)readlane_f64(me.score, K - 1);   // exact: every score of the list came in as an S
+        if constexpr (SCALED) thr_s = (S)(readlane_f64(me.score, K - 1) * sc_up);
+        else thr_s = (S)readlane_f64(me.score, K - 1);   // exact: every score of the list came in as an S
     }
 }
 
-// The skeleton.  A policy P says what one batch does to the accumulators (P::batch: takes and re-issues every slot of the batch once, in the
+// Staging as most policies do it: the first NS queries copied into LDS as they are, [NS][D] in the rows' type.
+template <typename T, int NS>
+__device__ __forceinline__ void pass_stage_copy(T *qs, const PassArgs &a, int tid)
+{
+    typedef typename Vec16<T>::type V;
+    constexpr int N = Vec16<T>::N;
+    const int D = a.D;
+    for (int e = tid * N; e < D; e += blockDim.x * N) {   // all NS loads of a lane in flight together (L2-resident after the first workgroup)
+        V w[NS];
+#pragma unroll
+        for (int q = 0; q < NS; q++) w[q] = *as_global(reinterpret_cast<const V *>(static_cast<const T *>(a.q[q]) + e));
+#pragma unroll
+        for (int q = 0; q < NS; q++) *reinterpret_cast<V *>(qs + q * D + e) = w[q];
+    }
+}
+
+// The skeleton.  A policy P says how the staged queries look in LDS (P::Staged, P::stage), what one batch does to the accumulators (P::batch: takes and re-issues every slot of the batch once, in the
 // stream's order) and how a lane's accumulator becomes its sum (P::lane_sum); everything else is here, once.
 template <class P>
 __device__ __forceinline__ void shared_pass(const PassArgs &a)
 {
     typedef typename P::Elem T;          // rows and queries as stored
     typedef typename P::Score S;         // scores and thresholds
-    typedef typename Vec16<T>::type V;
+    typedef typename P::Staged Q;        // a staged query element in LDS
     constexpr int NQ = P::NQ, NG = P::NG, NS = NQ - NG, R = kMultiR, U = kMultiU, N = Vec16<T>::N;
     constexpr int BATCH = 64 * N * U;    // elements of a 4 KiB batch
     static_assert(pass_vgpr_base(NG) >= P::kVgprBase && pass_row_slot(U - 1, R - 1) + 4 <= 256, "load slots inside the asm's share of the register file");
@@ -543,7 +564,7 @@ __device__ __forceinline__ void shared_pass(const PassArgs &a)
     asm volatile("" ::: CHIP_PASS_SLOTS_192_255);                    // makes the code object allocate the asm-owned registers
     if constexpr (P::kVgprBase <= 160) asm volatile("" ::: CHIP_PASS_SLOTS_160_191);
     if constexpr (P::kVgprBase <= 144) asm volatile("" ::: CHIP_PASS_SLOTS_144_159);
-    T *qs = reinterpret_cast<T *>(smem);  // [NS][D]
+    Q *qs = reinterpret_cast<Q *>(smem);  // [NS][D]
     const int D = a.D;
     const int K = a.K;
     const int tid = threadIdx.x;
@@ -551,20 +572,14 @@ __device__ __forceinline__ void shared_pass(const PassArgs &a)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wpb = blockDim.x >> 6;
 
-    for (int e = tid * N; e < D; e += blockDim.x * N) {   // all NS loads of a lane in flight together (L2-resident after the first workgroup)
-        V w[NS];
-#pragma unroll
-        for (int q = 0; q < NS; q++) w[q] = *as_global(reinterpret_cast<const V *>(static_cast<const T *>(a.q[q]) + e));
-#pragma unroll
-        for (int q = 0; q < NS; q++) *reinterpret_cast<V *>(qs + q * D + e) = w[q];
-    }
+    P::stage(qs, a, tid);
     __syncthreads();
     const T *qg[NG > 0 ? NG : 1];   // the queries read in place (SGPRs)
 #pragma unroll
     for (int g = 0; g < NG; g++) qg[g] = uniform_ptr(static_cast<const T *>(a.q[NS + g]));
 
     // running top-K lists: LDS behind the queries, [wave][3T][K] (this wave's lists are touched by this wave only until the merge)
-    chip_topk_entry *lists = reinterpret_cast<chip_topk_entry *>(smem + (size_t)NS * D * sizeof(T));
+    chip_topk_entry *lists = reinterpret_cast<chip_topk_entry *>(smem + (size_t)NS * D * sizeof(Q));
     chip_topk_entry *mylists = lists + (size_t)wave * NQ * K;
     S thr_s[NQ];   // score of the K-th entry of each list (SGPRs)
 #pragma unroll
@@ -657,7 +672,7 @@ __device__ __forceinline__ void shared_pass(const PassArgs &a)
 #pragma unroll
                         for (int rr = 0; rr < R; rr++) {
                             const int64_t r = rbase + ((int64_t)group * R + rr) * tw;
-                            if (r < a.n_rows && r < a.k[q / 3]) pass_offer<S>(lane_value(s[q], 16 * rr), r, K, lane, mylists + q * K, thr_s[q]);
+                            if (r < a.n_rows && r < a.k[q / 3]) pass_offer<S, P::kScaled>(lane_value(s[q], 16 * rr), r, K, lane, mylists + q * K, thr_s[q], P::kScaled ? a.s_down : 1.0, P::kScaled ? a.s_up : 1.0);
                         }
                     }
                 }
@@ -691,9 +706,12 @@ constexpr int kSharedF64MaxTicks = 2;
 template <typename T, int NTICKS, int NG_, int MAX_NG>
 struct PassF64 {
     typedef T Elem;
+    typedef T Staged;
     typedef double Score;
     typedef double Acc;
+    static constexpr bool kScaled = false;
     static constexpr int NQ = 3 * NTICKS, NG = NG_, NS = NQ - NG, R = kMultiR, U = kMultiU, L = U * (R + NG), kVgprBase = pass_vgpr_base(MAX_NG);
+    static __device__ __forceinline__ void stage(T *qs, const PassArgs &a, int tid) { pass_stage_copy<T, NS>(qs, a, tid); }
     static __device__ __forceinline__ Acc zero() { return 0.0; }
     static __device__ __forceinline__ double lane_sum(Acc v) { return v; }
     static __device__ __forceinline__ void batch(Acc (&acc)[R][NQ], const T *qv, int D, uint32_t voff, const T *const (&row)[R], const T *const (&qg)[NG > 0 ? NG : 1])
@@ -775,9 +793,12 @@ __device__ __forceinline__ void prefilter_fma_slot(f32x2 &acc)
 template <int NG_>
 struct PassF32 {
     typedef float Elem;
+    typedef float Staged;
     typedef float Score;
     typedef f32x2 Acc;
+    static constexpr bool kScaled = false;
     static constexpr int NQ = 3 * kPrefilterTicks, NG = NG_, NS = NQ - NG, R = kMultiR, U = kMultiU, L = U * (R + NG), kVgprBase = pass_vgpr_base(kPrefilterMaxNG);
+    static __device__ __forceinline__ void stage(float *qs, const PassArgs &a, int tid) { pass_stage_copy<float, NS>(qs, a, tid); }
     static __device__ __forceinline__ Acc zero() { return (f32x2){0.0f, 0.0f}; }
     static __device__ __forceinline__ float lane_sum(Acc v) { return v[0] + v[1]; }
     static __device__ __forceinline__ void batch(Acc (&acc)[R][NQ], const float *qv, int D, uint32_t voff, const float *const (&row)[R], const float *const (&qg)[NG > 0 ? NG : 1])
@@ -813,6 +834,71 @@ __global__ __launch_bounds__(kMultiBlock) __attribute__((amdgpu_num_vgpr(pass_vg
 {
     static_assert(NG <= kPrefilterMaxNG, "the compiler's share is sized for kPrefilterMaxNG query slots per KiB");
     shared_pass<PassF32<NG>>(a);
+}
+
+// ------------------------------------------------------------------------------------------------ K1, five ticks per pass, queries staged as fp16
+// db_scan_halfq: the prefilter pass for FIVE queued ticks (15 queries).  What keeps a fifth tick out of db_scan_prefilter is LDS bytes per
+// query, not arithmetic: here every query is staged as fp16, [15][D] halves (120 KiB at D = 4096), and none is read in place.  The
+// certificate is the one of the four-tick pass with a larger error bound (E_h): the lists only propose, tick_rescore decides.
+//   * staging: every workgroup reads the 15 fp32 query rows once and stores fl16(2^e q), round to nearest even.  2^e (PassArgs::q_up) is
+//     chosen by the host from the row-norm bound N so that 2^e N <= 2^15: no element of a published row overflows fp16, small norms keep
+//     their bits above the fp16 subnormals;
+//   * batch step: per KiB the four row slots are waited for once; per query one ds_read_b64 (four halves, read two vectors ahead), four
+//     conversions to fp32 (exact) and eight v_pk_fma_f32 on the slot registers -- the accumulator pairs and their element order are
+//     PassF32's; then the KiB's slots are issued again;
+//   * scores and thresholds stay 2^e times too large inside the pass; pass_offer scales what enters a list by 2^-e in fp64 (exact).
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+struct PassF32H {
+    typedef float Elem;
+    typedef _Float16 Staged;
+    typedef float Score;
+    typedef f32x2 Acc;
+    static constexpr bool kScaled = true;
+    static constexpr int NQ = 3 * kHalfqTicks, NG = 0, NS = NQ, R = kMultiR, U = kMultiU, L = U * R, kVgprBase = pass_vgpr_base(0);
+    static __device__ __forceinline__ void stage(_Float16 *qs, const PassArgs &a, int tid)
+    {
+        const int D = a.D;
+        const float up = a.q_up;
+        for (int e = tid * 4; e < D; e += blockDim.x * 4) {
+            f32x4 w[NS];
+#pragma unroll
+            for (int q = 0; q < NS; q++) w[q] = *as_global(reinterpret_cast<const f32x4 *>(static_cast<const float *>(a.q[q]) + e));
+#pragma unroll
+            for (int q = 0; q < NS; q++) {
+                f16x4 h;
+#pragma unroll
+                for (int c = 0; c < 4; c++) h[c] = (_Float16)(w[q][c] * up);   // the product is exact (a power of two), the conversion rounds to nearest even
+                *reinterpret_cast<f16x4 *>(qs + q * D + e) = h;
+            }
+        }
+    }
+    static __device__ __forceinline__ Acc zero() { return (f32x2){0.0f, 0.0f}; }
+    static __device__ __forceinline__ float lane_sum(Acc v) { return v[0] + v[1]; }
+    static __device__ __forceinline__ void batch(Acc (&acc)[R][NQ], const _Float16 *qv, int D, uint32_t voff, const float *const (&row)[R], const float *const (&qg)[1])
+    {
+        constexpr int SS = U * NS;
+        f16x4 w[SS];        // staged query vectors in the order they are used: (u, q), read two ahead
+        w[0] = *reinterpret_cast<const f16x4 *>(qv);
+        w[1] = *reinterpret_cast<const f16x4 *>(qv + D);
+        static_for<U>([&](auto uc) CHIP_INLINE_LAMBDA {
+            constexpr int u = uc;
+            slot_wait<L - R>();                      // the four row slots of this KiB are the oldest loads of the stream
+            static_for<NS>([&](auto qc) CHIP_INLINE_LAMBDA {
+                constexpr int q = qc, i = u * NS + q;
+                if constexpr (i + 2 < SS) w[i + 2] = *reinterpret_cast<const f16x4 *>(qv + ((i + 2) % NS) * D + ((i + 2) / NS) * 256);
+                const f32x2 wl = {(float)w[i][0], (float)w[i][1]}, wh = {(float)w[i][2], (float)w[i][3]};
+                static_for<R>([&](auto rr) CHIP_INLINE_LAMBDA { prefilter_fma<pass_row_slot(u, rr)>(acc[rr][q], wl); });
+                static_for<R>([&](auto rr) CHIP_INLINE_LAMBDA { prefilter_fma<pass_row_slot(u, rr) + 2>(acc[rr][q], wh); });
+                __builtin_amdgcn_sched_barrier(0);
+            });
+            slots_issue_kib<u, 0>(voff, row, qg);
+        });
+    }
+};
+
+__global__ __launch_bounds__(kMultiBlock) __attribute__((amdgpu_num_vgpr(pass_vgpr_base(0) / 2))) void db_scan_halfq(PassArgs a)
+{
+    shared_pass<PassF32H>(a);
 }
 
 // ------------------------------------------------------------------------------------------------ exact rescoring of one prefiltered tick
@@ -1924,20 +2010,22 @@ int launch_scan(Ctx *c, hipStream_t s, const ScanArgs &a, int nq, int grid)
 // as fit the LDS next to the lists, the other NG read in place where an instantiation exists for that NG:
 //   MULTI, float rows : T = 2, 3; NG = 0 only (D = 4096: T <= 3; D = 8192: none);
 //   MULTI, double rows: T = 2; NG <= 2 (D <= 3072: NG = 0; D = 3584: 1; D = 4096, 4608: 2; wider rows: no such form);
-//   PREFILTER         : float rows, T = 4; NG = 0 (D <= 3072) or 3 (D = 4096); wider rows, K = 16 at D = 4096 and double rows have no such pass.
+//   PREFILTER         : float rows, T = 4; NG = 0 (D <= 3072) or 3 (D = 4096); wider rows, K = 16 at D = 4096 and double rows have no such pass;
+//   HALFQ             : float rows, T = 5; every query staged as fp16 (2 bytes per element), NG = 0 only: D <= 4096.
 static int pass_plan(int family, int D, int elem, int n_ticks, int K, int grid, chip_debug_scan_launch *f)
 {
     *f = chip_debug_scan_launch{};
-    const bool prefilter = family == CHIP_SCAN_FAMILY_PREFILTER;
+    const bool prefilter = family == CHIP_SCAN_FAMILY_PREFILTER, halfq = family == CHIP_SCAN_FAMILY_HALFQ;
     if (D < 1 || (elem != 4 && elem != 8) || K < 1 || K > CHIP_MAX_TOPK || grid < 1 || grid > 512 || (int64_t)D * elem % 4096 != 0) return CHIP_ERR_UNSUPPORTED;
-    if (prefilter ? elem != 4 : n_ticks < 2 || n_ticks > (elem == 8 ? kSharedF64MaxTicks : kMultiMaxTicks)) return CHIP_ERR_UNSUPPORTED;
+    if (prefilter || halfq ? elem != 4 : n_ticks < 2 || n_ticks > (elem == 8 ? kSharedF64MaxTicks : kMultiMaxTicks)) return CHIP_ERR_UNSUPPORTED;
     const int nq = 3 * n_ticks;
     const size_t kLds = 160 * 1024, lists = (size_t)(kMultiBlock / 64) * nq * K * sizeof(chip_topk_entry);   // [wave][3T][K] behind the queries
     const int max_ng = prefilter ? kPrefilterMaxNG : elem == 8 ? kSharedMaxNG : 0;
-    const size_t fit = max_ng > 0 ? (kLds - lists) / ((size_t)D * elem) : (size_t)nq;
+    const size_t staged_elem = halfq ? sizeof(_Float16) : (size_t)elem;
+    const size_t fit = max_ng > 0 ? (kLds - lists) / ((size_t)D * staged_elem) : (size_t)nq;
     const int staged = fit < (size_t)nq ? (int)fit : nq, ng = nq - staged;
     if (prefilter ? ng != 0 && ng != kPrefilterMaxNG : ng > max_ng) return CHIP_ERR_UNSUPPORTED;   // an NG no instantiation exists for
-    const size_t lds = (size_t)staged * D * elem + lists;
+    const size_t lds = (size_t)staged * D * staged_elem + lists;
     if (lds > kLds) return CHIP_ERR_UNSUPPORTED;
     f->family = family;
     f->elem = elem;
@@ -1958,6 +2046,8 @@ static int pass_plan(int family, int D, int elem, int n_ticks, int K, int grid, 
 }
 int scan_multi_plan(int D, int elem, int n_ticks, int K, int grid, chip_debug_scan_launch *f) { return pass_plan(CHIP_SCAN_FAMILY_MULTI, D, elem, n_ticks, K, grid, f); }
 int scan_prefilter_plan(int D, int elem, int K, int grid, chip_debug_scan_launch *f) { return pass_plan(CHIP_SCAN_FAMILY_PREFILTER, D, elem, kPrefilterTicks, K, grid, f); }
+
+int scan_halfq_plan(int D, int elem, int K, int grid, chip_debug_scan_launch *f) { return pass_plan(CHIP_SCAN_FAMILY_HALFQ, D, elem, kHalfqTicks, K, grid, f); }
 
 int scan_multi_grid(const Ctx *c) { return c->n_cus < c->max_grid ? c->n_cus : c->max_grid; }   // one 8-wave workgroup per CU
 
@@ -1988,6 +2078,39 @@ bool scan_prefilter_usable(const Ctx *c)
     double n;
     { std::lock_guard<std::mutex> lk(c->mu); n = c->row_norm_max; }
     return n * n <= std::ldexp(1.0, 120) && 2.0 * c->D * std::ldexp(1.0, -24) < 0.5;   // no overflow of an fp32 partial sum (false for NaN as well)
+}
+
+// The five-tick pass.  e: the largest exponent with 2^e N <= 2^15 for the row-norm bound N -- an element of a published row is
+// at most N in magnitude, so no staged half overflows (fp16 holds up to 65504) -- kept inside [-100, 100] so that 2^e and 2^-e are
+// normal floats whatever N is (a smaller e than the largest is always safe; halfq_error_bound is evaluated with the e that is used).
+int halfq_exponent(double row_norm_max)
+{
+    int x = 0;
+    if (row_norm_max > 0.0 && std::isfinite(row_norm_max) && std::frexp(row_norm_max, &x) == 0.5) x--;   // N = m 2^x, 1/2 <= m < 1: N <= 2^x (a power of two: N = 2^(x-1))
+    const int e = 15 - x;
+    return e > 100 ? 100 : e < -100 ? -100 : e;
+}
+
+// E_h of DESIGN.md 3: gamma_64 N^2 + (gamma_32 (1 + 2^-11) + 2^-11) N^2 + (1 + gamma_32) N sqrt(D) 2^(-25-e) + D 2^(-149-e), gamma_32 and gamma_64
+// as in prefilter_error_bound, evaluated in fp64 and rounded up.
+double halfq_error_bound(int D, double row_norm_max, int e)
+{
+    const double u32 = 2.0 * D * std::ldexp(1.0, -24), u64 = (D + 8.0) * std::ldexp(1.0, -53);
+    const double g32 = u32 / (1.0 - u32), g64 = u64 / (1.0 - u64), h = std::ldexp(1.0, -11), n2 = row_norm_max * row_norm_max;
+    const double E = g64 * n2 + (g32 * (1.0 + h) + h) * n2 + (1.0 + g32) * row_norm_max * std::sqrt((double)D) * std::ldexp(1.0, -25 - e) +
+                     D * std::ldexp(1.0, -149 - e);
+    return E * (1.0 + std::ldexp(1.0, -40));
+}
+
+// N < 2^105: then e >= -90 and 2^e N^2 (1 + 2^-11) <= 2^121 bounds every fp32 partial sum of the scaled pass (false for NaN as well)
+bool scan_halfq_usable(const Ctx *c)
+{
+    if (c->elem != 4 || c->nranks != 1 || c->scan_variant != 0 || c->scan_rows > 0) return false;
+    chip_debug_scan_launch f;
+    if (scan_halfq_plan(c->D, c->elem, CHIP_DEFAULT_TOPK, scan_multi_grid(c), &f) != CHIP_OK) return false;
+    double n;
+    { std::lock_guard<std::mutex> lk(c->mu); n = c->row_norm_max; }
+    return n < std::ldexp(1.0, 105) && 2.0 * c->D * std::ldexp(1.0, -24) < 0.5;
 }
 
 // a shared pass as planned: the launch and the record of it (Ctx::last_scan)
@@ -2022,10 +2145,17 @@ int launch_scan_prefilter(Ctx *c, hipStream_t s, const PassArgs &a, int grid)
     return f.NG == 0 ? launch_pass(c, s, db_scan_prefilter<0>, a, f) : launch_pass(c, s, db_scan_prefilter<kPrefilterMaxNG>, a, f);
 }
 
-int launch_rescore(Ctx *c, hipStream_t s, const RescoreArgs &a)
+int launch_scan_halfq(Ctx *c, hipStream_t s, const PassArgs &a, int grid)
 {
-    if (a.n_lists > 512 || a.K > CHIP_MAX_TOPK) return CHIP_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(tick_rescore, dim3(3 * kPrefilterTicks), dim3(512), 0, s, a);
+    chip_debug_scan_launch f;
+    if (grid > c->max_grid || scan_halfq_plan(c->D, c->elem, a.K, grid, &f) != CHIP_OK || !(a.q_up > 0.0f)) return CHIP_ERR_UNSUPPORTED;
+    return launch_pass(c, s, db_scan_halfq, a, f);
+}
+
+int launch_rescore(Ctx *c, hipStream_t s, const RescoreArgs &a, int n_ticks)
+{
+    if (a.n_lists > 512 || a.K > CHIP_MAX_TOPK || n_ticks < 1 || n_ticks > kPassMaxTicks) return CHIP_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(tick_rescore, dim3(3 * n_ticks), dim3(512), 0, s, a);
     CHIP_HIP(c, hipGetLastError());
     return CHIP_OK;
 }

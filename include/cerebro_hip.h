@@ -456,13 +456,15 @@ int chip_resident_resume(chip_ctx *ctx);
  * Ticks that share a DB pass.  Queued ticks do not depend on one another (status and last_l are settled at enqueue, the queries
  * are published rows), so on a plain single-GPU ctx with float or double rows, on its own streams, an enqueue over a LONG prefix (beyond
  * CHIP_SCAN_OVERLAP_GIB, 8 GiB) that finds a scan of the ctx still running PARKS its tick instead of launching it; parked ticks
- * leave together as ONE pass over [0, max k) with 3 T queries (T <= CHIP_TICK_COALESCE, default 4; 0 = off), every tick seeing
+ * leave together as ONE pass over [0, max k) with 3 T queries (T <= CHIP_TICK_COALESCE, default 5; 0 = off), every tick seeing
  * only its own prefix [0, k_t).  Which rows: whole 4 KiB batches -- float rows with D % 1024 == 0 whose 3 T queries fit the LDS (D = 4096:
  * T <= 3), double rows with D % 512 == 0 up to D = 4608, T = 2 (the queries that do not fit the LDS are read in place, out of the L2);
  * chip_debug_multi_plan says what a given shape gets.  FOUR ticks (float rows up to D = 4096, chip_debug_prefilter_plan) leave as a pass
  * that scores in fp32 and then proves, per query, which rows can be in the exact top-8 and scores those in fp64 in the usual order:
  * same records; a tick whose proof does not go through (scores closer together than the fp32 error bound taken from
- * chip_info.row_norm_max) runs again alone at its collect.  CHIP_TICK_COALESCE=2 / 3 are what they were.  Every other ctx launches its ticks one by one.  Results, status codes, CHIP_ERR_BUSY, last_l, chip_loop_reset, skipped / too-short ticks in
+ * chip_info.row_norm_max) runs again alone at its collect.  FIVE ticks (the same shapes, chip_debug_halfq_plan) leave as a pass of the
+ * same kind whose 15 queries are staged in LDS as fp16, scaled by a power of two taken from row_norm_max: same proof with a larger error
+ * bound, same records; the pass parked behind a tick that was launched alone takes four, five only behind a shared pass.  CHIP_TICK_COALESCE=2 / 3 / 4 are what they were (4: passes of four through the fp32 pass, never the fp16-query one).  Every other ctx launches its ticks one by one.  Results, status codes, CHIP_ERR_BUSY, last_l, chip_loop_reset, skipped / too-short ticks in
  * between, appends between enqueue and collect and out-of-order collects are exactly those of ticks launched one by one.  A tick
  * that arrives while no scan is running is launched at once, alone; chip_loop_tick, short prefixes and caller-supplied streams
  * (chip_set_stream) never park.  Nothing stays parked while its caller cannot release it.  Parked ticks are submitted by:
@@ -501,6 +503,7 @@ int chip_debug_coalesce_decide(int32_t n_parked, int32_t t_max, int32_t scan_run
 #define CHIP_SCAN_FAMILY_ROWS    3   /* db_scan_topk_rows<T, NQ, R, NTL>: R rows per wave in flight; carries the fused tick        */
 #define CHIP_SCAN_FAMILY_MULTI   4   /* db_scan_topk_multi<T> / db_scan_shared_f64<T, NG>: `ticks` pipelined ticks share one pass     */
 #define CHIP_SCAN_FAMILY_PREFILTER 5 /* db_scan_prefilter<NG>: four pipelined ticks share one fp32 pass; tick_rescore scores the proven candidates exactly */
+#define CHIP_SCAN_FAMILY_HALFQ   6   /* db_scan_halfq: five pipelined ticks share one fp32 pass over queries staged as fp16; tick_rescore as above */
 #define CHIP_SCAN_CALL_QUERY      0  /* chip_query_rows / chip_query_vectors_*: lists out                                         */
 #define CHIP_SCAN_CALL_TICK       1  /* chip_loop_tick_enqueue: a pipelined tick                                                   */
 #define CHIP_SCAN_CALL_TICK_SYNC  2  /* chip_loop_tick: the synchronous tick                                                       */
@@ -534,7 +537,13 @@ int chip_debug_multi_plan(int32_t D, int32_t elem, int32_t n_ticks, int32_t K, i
  * in place (the others are staged in LDS as fp32), lds_bytes, grid, block.  CHIP_ERR_UNSUPPORTED where a ctx of that shape has no such pass and
  * releases at most three ticks together (ABI 7, additive). */
 int chip_debug_prefilter_plan(int32_t D, int32_t elem, int32_t K, int32_t n_cus, chip_debug_scan_launch *out);
-/* Prefilter passes submitted, the ticks they served, and those of them whose certificate did not hold (counted at collect: such a tick was run
+/* The five-tick pass (family CHIP_SCAN_FAMILY_HALFQ, float rows) the same way: nq = 15, ticks = 5, NG = 0 (every query staged in LDS as fp16),
+ * lds_bytes, grid, block.  CHIP_ERR_UNSUPPORTED where a ctx of that shape has no such pass and releases at most four ticks together (additive). */
+int chip_debug_halfq_plan(int32_t D, int32_t elem, int32_t K, int32_t n_cus, chip_debug_scan_launch *out);
+/* The scale and the error bound such a pass over rows of norm at most row_norm_max is launched with: the staged queries are fl16(2^e q), and
+ * |score of the pass - exact score| <= E for every pair of published rows.  No device needed (additive). */
+int chip_debug_halfq_bound(int32_t D, double row_norm_max, int32_t *e, double *E);
+/* Prefilter passes of either kind (four ticks, five ticks) submitted, the ticks they served, and those of them whose certificate did not hold (counted at collect: such a tick was run
  * again alone, and its caller got that record). */
 int chip_debug_prefilter_stats(chip_ctx *ctx, int64_t *passes, int64_t *ticks, int64_t *uncertified);
 

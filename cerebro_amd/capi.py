@@ -190,6 +190,11 @@ class ScanLaunch(C.Structure):
         return d
 
 
+class PassInfo(C.Structure):
+    """chip_debug_pass_info: what the last prefilter pass was launched with (test aid)"""
+    _fields_ = [(n, C.c_int32) for n in ("family", "ticks", "grid", "wpb", "K", "e")] + [("k", C.c_int64 * 5), ("E", C.c_double)]
+
+
 class RansacShape(C.Structure):
     """chip_debug_ransac_shape: the launch a per-hypothesis record belongs to (test aid)"""
     _fields_ = [(n, C.c_int32) for n in ("P", "H", "N", "words", "S", "sampler")]
@@ -248,6 +253,7 @@ _SIGS = {
     "chip_merge_decide_enqueue": (C.c_int, [_P, C.c_int64, C.POINTER(DotParams), _P, C.c_int32, C.c_int32, C.c_int32]),
     "chip_debug_merge_lists": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, C.POINTER(DotParams),
                                          C.POINTER(TickResult)]),
+    "chip_debug_last_pass": (C.c_int, [_P, C.POINTER(PassInfo), _P, _P, _P]),
     "chip_ransac_params_default": (None, [C.POINTER(RansacParams)]),
     "chip_pnp_ransac": (C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(RansacParams), _P, C.POINTER(C.c_float), _P,
                                   C.POINTER(RansacSummary)]),
@@ -955,6 +961,21 @@ class Chip:
         out = ScanLaunch()
         self._chk(self.lib.chip_debug_last_scan(self.h, C.byref(out)), "chip_debug_last_scan")
         return out.as_dict()
+
+    def last_pass(self) -> dict:
+        """chip_debug_last_pass: the ctx's last prefilter pass (four ticks or five) read back -- family, ticks, grid, wpb, K, k (list), E, e,
+        cand_s float64 / cand_i int64 [T, grid, 3, K] (the pass's lists), exact_s / exact_i [T, 3, K] (tick_rescore's lists),
+        cert uint32 [T, 3] (1 certified, 2 not)"""
+        info = PassInfo()
+        self._chk(self.lib.chip_debug_last_pass(self.h, C.byref(info), None, None, None), "chip_debug_last_pass")
+        T, grid, K = info.ticks, info.grid, info.K
+        cand = np.empty((T, grid, 3, K, 2), dtype=np.float64)
+        exact = np.empty((T, 3, K, 2), dtype=np.float64)
+        cert = np.zeros((T, 3), dtype=np.uint32)
+        self._chk(self.lib.chip_debug_last_pass(self.h, C.byref(info), _ptr(cand), _ptr(exact), _ptr(cert)), "chip_debug_last_pass")
+        return dict(family=SCAN_FAMILY_NAMES[info.family], ticks=T, grid=grid, wpb=int(info.wpb), K=K, k=[int(x) for x in info.k[:T]],
+                    E=float(info.E), e=int(info.e), cand_s=cand[..., 0].copy(), cand_i=cand[..., 1].copy().view(np.int64),
+                    exact_s=exact[..., 0].copy(), exact_i=exact[..., 1].copy().view(np.int64), cert=cert)
 
     def scan_local(self, l: int, dev_out_ptr: int, topk: int = CHIP_DEFAULT_TOPK, params: DotParams | None = None) -> int:
         p = params or default_dot_params()

@@ -637,10 +637,11 @@ static int coalesce_submit(Ctx *c, int first, int T)
     }
     const int grid = scan_multi_grid(c);
     double E = 0.0;
+    int e = 0;
     if (prefilter) {
         std::lock_guard<std::mutex> lk(c->mu);
         if (halfq) {   // the scale of the staged queries and the bound that goes with it, from ONE reading of the norm bound
-            const int e = halfq_exponent(c->row_norm_max);
+            e = halfq_exponent(c->row_norm_max);
             a.q_up = std::ldexp(1.0f, e);
             a.s_up = std::ldexp(1.0, e);
             a.s_down = std::ldexp(1.0, -e);
@@ -678,6 +679,10 @@ static int coalesce_submit(Ctx *c, int first, int T)
         }
         rc = launch_rescore(c, c->s_query, ra, T);
         if (rc != CHIP_OK) return rc;
+        Ctx::LastPass &lp = c->last_pass;   // what chip_debug_last_pass reads back
+        lp.family = halfq ? CHIP_SCAN_FAMILY_HALFQ : CHIP_SCAN_FAMILY_PREFILTER;
+        lp.ticks = T; lp.grid = grid; lp.wpb = ra.wpb; lp.K = K; lp.e = e; lp.ring = b; lp.E = E;
+        for (int t = 0; t < T; t++) { lp.k[t] = parked[t].k; lp.cert[t] = parked[t].slot->cert_host; }
     }
     if (halfq) {   // one K2 launch for the five ticks (kernels.hip pass_merge): workgroup t is topk_merge<3> on tick t's lists
         PassMergeArgs m{};
@@ -1545,6 +1550,33 @@ int chip_debug_prefilter_stats(chip_ctx *c, int64_t *passes, int64_t *ticks, int
     *passes = c->prefilter_passes;
     *ticks = c->prefilter_ticks;
     *uncertified = c->prefilter_uncertified;
+    return CHIP_OK;
+}
+
+// What the last prefilter pass of this ctx (four ticks or five) left in device memory, and what it was launched with.  Launches nothing and
+// submits nothing (parked ticks stay parked): waits for the ctx's own streams, then copies.  The pass's list buffer is not reused before
+// Ctx::kRing further enqueues, and a tick that runs again alone takes another buffer: valid after the collects of the pass's window.
+int chip_debug_last_pass(chip_ctx *c, chip_debug_pass_info *info, chip_topk_entry *cand, chip_topk_entry *exact, uint32_t *cert)
+{
+    if (!c || c->group) return CHIP_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> qlk(c->query_mu);
+    const Ctx::LastPass &lp = c->last_pass;
+    if (lp.family == 0) return CHIP_ERR_BUSY;
+    CHIP_HIP(c, hipSetDevice(c->device));
+    CHIP_HIP(c, hipStreamSynchronize(c->s_scan));
+    CHIP_HIP(c, hipStreamSynchronize(c->s_query));
+    if (info) {
+        std::memset(info, 0, sizeof *info);
+        info->family = lp.family; info->ticks = lp.ticks; info->grid = lp.grid; info->wpb = lp.wpb; info->K = lp.K; info->e = lp.e; info->E = lp.E;
+        for (int t = 0; t < lp.ticks; t++) info->k[t] = lp.k[t];
+    }
+    const chip_topk_entry *lists = c->partial_dev[lp.ring];
+    const size_t n_cand = (size_t)lp.ticks * lp.grid * 3 * lp.K, n_exact = (size_t)lp.ticks * 3 * lp.K;
+    if (cand) CHIP_HIP(c, hipMemcpy(cand, lists, n_cand * sizeof(chip_topk_entry), hipMemcpyDeviceToHost));
+    if (exact) CHIP_HIP(c, hipMemcpy(exact, lists + (size_t)kPassMaxTicks * lp.grid * 3 * lp.K, n_exact * sizeof(chip_topk_entry), hipMemcpyDeviceToHost));
+    if (cert)
+        for (int t = 0; t < lp.ticks; t++)
+            for (int i = 0; i < 3; i++) cert[3 * t + i] = lp.cert[t][i];
     return CHIP_OK;
 }
 

@@ -431,6 +431,10 @@ struct Ctx {
     int64_t prefilter_passes = 0, prefilter_ticks = 0, prefilter_uncertified = 0;   // prefilter passes / their ticks / those of them run again alone
     PinnedBuf<uint32_t> cert_all;        // [CHIP_MAX_INFLIGHT][4] certificate words of the slots (three used)
     chip_debug_scan_launch last_scan{};  // the last top-k scan launched (launch_scan / launch_scan_multi; query_mu): chip_debug_last_scan
+    // the last prefilter pass submitted (coalesce_submit; query_mu): where its lists are and what it was launched with -- chip_debug_last_pass.
+    // The list buffer is not reused before kRing further enqueues; the certificate words are the slots' own (pinned host memory), which
+    // only the next prefilter pass through the same slot overwrites.
+    struct LastPass { int32_t family = 0, ticks = 0, grid = 0, wpb = 0, K = 0, e = 0, ring = 0; double E = 0.0; int64_t k[kPassMaxTicks] = {}; const uint32_t *cert[kPassMaxTicks] = {}; } last_pass;
 
     // --- scan tuning (resolved at create; CHIP_SCAN_* env overrides for A/B runs) ---
     int32_t scan_block = 0;       // 0 = auto

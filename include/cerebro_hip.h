@@ -577,6 +577,27 @@ int chip_merge_decide_enqueue(chip_ctx *ctx, int64_t l, const chip_dot_params *p
  * K outside 1 .. CHIP_MAX_TOPK, n_lists > 512, an nq or a form that does not exist; CHIP_ERR_INVALID_ARG: NULL pointers, n_lists < 1. */
 int chip_debug_merge_lists(chip_ctx *ctx, int32_t form, const chip_topk_entry *lists, int32_t n_lists, int32_t nq, int32_t K,
                            chip_topk_entry *out, int64_t l, const chip_dot_params *p, chip_tick_result *result);
+/* Test aid (ABI 7, additive): what the ctx's last prefilter pass (CHIP_SCAN_FAMILY_PREFILTER, four ticks, or _HALFQ, five) left in device
+ * memory, so that tests/test_pass_lists_gpu.py and tests/test_rescore_gpu.py can hold the pass's own scores, lists and certificates to the
+ * oracle's mirrors and not only the records that come out behind them.  It launches nothing and submits nothing (parked ticks stay parked):
+ * it waits for the ctx's own streams, then copies.
+ *   info   family, ticks T, grid (workgroups = lists per tick and query), wpb (waves per workgroup: workgroup b owns the rows r with
+ *          r mod (grid wpb) in [b wpb, (b + 1) wpb)), K, the prefixes k[t], the error bound E handed to tick_rescore and, for _HALFQ, the
+ *          exponent e of the queries' scale (0 otherwise);
+ *   cand   [T][grid][3][K]: the pass's lists, (pass score widened to double, row), sorted by (score descending, index descending), unused
+ *          entries (-inf, -1);
+ *   exact  [T][3][K]: the lists tick_rescore wrote, exact scores of the candidates it kept;
+ *   cert   [T][3]: 1 the query's certificate holds, 2 it does not.
+ * Any output pointer may be NULL.  The list buffer is not reused before 64 further scans are enqueued and a tick that runs again alone takes
+ * another buffer, so the copy is valid after the collects of the pass's window.  CHIP_ERR_BUSY before the first such pass,
+ * CHIP_ERR_INVALID_ARG for a NULL or chip_create_multi ctx.  Synchronous, takes the query lock. */
+typedef struct {
+    int32_t family, ticks, grid, wpb, K;
+    int32_t e;
+    int64_t k[5];
+    double E;
+} chip_debug_pass_info;
+int chip_debug_last_pass(chip_ctx *ctx, chip_debug_pass_info *info, chip_topk_entry *cand, chip_topk_entry *exact, uint32_t *cert);
 
 /* ------------------------------------------------------------------------------------------ PnP-RANSAC
  * Replaces the body of StaticTheiaPoseCompute::PNP (src/DlsPnpWithRansac.cpp:192-240): theia::Ransac over

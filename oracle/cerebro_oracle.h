@@ -47,6 +47,19 @@ void     orc_scan_topk_f64(const double *db, int64_t k, int32_t D, const double 
                            double *out_scores, int64_t *out_idx, int32_t nthreads);
 /* all scores of one query over rows [0,k); elem = 4 (float rows / float query) or 8 */
 void     orc_scores(const void *db, int32_t elem, int64_t k, int32_t D, const void *query, double *u, int32_t nthreads);
+/* Mirrors of the prefilter passes' own fp32 arithmetic (the device's db_scan_prefilter / db_scan_halfq), operation by operation:
+ * lane L keeps a low and a high fp32 accumulator, per 256 elements lo = fmaf(row[4L], q[4L], lo), hi = fmaf(row[4L+1], q[4L+1], hi),
+ * lo = fmaf(row[4L+2], ...), hi = fmaf(row[4L+3], ...); lo + hi; the xor-butterfly pairing tree in fp32.  D a multiple of 256.
+ * _halfq: the query replaced by fl16(2^e q) (round to nearest even on the bits, subnormal halves kept) widened to fp32, the result
+ * times 2^-e in fp64.  orc_pass_scores: out[q * k + i] for rows [0, k) and nq queries, threaded over rows; halfq = 0 / 1. */
+float    orc_pass_score_f32(const float *row, const float *q, int32_t D);
+double   orc_pass_score_halfq(const float *row, const float *q, int32_t D, int32_t e);
+uint16_t orc_f16_bits_rne(float x);
+float    orc_f16_bits_to_f32(uint16_t h);
+void     orc_f16_round_bits(const float *x, int64_t n, uint16_t *out);
+void     orc_halfq_stage(const float *q, int32_t D, int32_t e, float *staged);
+void     orc_pass_scores(const float *db, int64_t k, int32_t D, const float *queries, int32_t nq, int32_t halfq, int32_t e, double *out,
+                         int32_t nthreads);
 /* Plain left-to-right fp64 dot (the most literal reading of v^T * M.col(i), Cerebro.cpp:1026). */
 double   orc_dot_seq_f64(const double *q, const double *col, int32_t D);
 

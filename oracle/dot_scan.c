@@ -283,6 +283,118 @@ void orc_scores(const void *db, int32_t elem, int64_t k, int32_t D, const void *
                          : orc_dot_tree_f32((const float *)query, (const float *)db + (size_t)i * D, D);
 }
 
+/* ---------------------------------------------------------------- mirrors of the prefilter passes' own arithmetic
+ * The four-tick and the five-tick pass (kernels.hip db_scan_prefilter / db_scan_halfq) score in fp32; their scores decide nothing, but the
+ * certificate of DESIGN.md 3 rests on what they are.  These functions restate, operation by operation, what one (row, query) pair goes
+ * through there, so that a test can hold the device's lists to them bit for bit:
+ *   PassF32::batch / PassF32H::batch + prefilter_fma: lane L (0..63) keeps an accumulator PAIR; per 256 elements (one KiB of the row, KiBs and
+ *     4 KiB batches in ascending order) v_pk_fma_f32 on elements 4L, 4L + 1 (low, high half), then on 4L + 2, 4L + 3 (low, high half): four
+ *     fused multiply-adds, row element x query element + accumulator, one rounding each;
+ *   lane_sum: low + high half;
+ *   reduce_rows4: the xor butterfly's pairing tree over the 64 lane sums in fp32, m = 32, 16, 8, 4, 2, 1 (a + b == b + a: every lane ends
+ *     with the bits of lane 0).
+ * fmaf is correctly rounded and fp32 subnormals are kept, as on the device.  D must be a multiple of 256 (the passes take rows of whole
+ * 4 KiB batches only). */
+static float pass_tree_f32(const float *row, const float *q, int32_t D)
+{
+    float lo[64], hi[64];
+    for (int L = 0; L < 64; L++) lo[L] = hi[L] = 0.0f;
+    for (int32_t base = 0; base + 256 <= D; base += 256)
+        for (int L = 0; L < 64; L++) {
+            const int32_t e = base + 4 * L;
+            lo[L] = __builtin_fmaf(row[e], q[e], lo[L]);
+            hi[L] = __builtin_fmaf(row[e + 1], q[e + 1], hi[L]);
+            lo[L] = __builtin_fmaf(row[e + 2], q[e + 2], lo[L]);
+            hi[L] = __builtin_fmaf(row[e + 3], q[e + 3], hi[L]);
+        }
+    float s[64];
+    for (int L = 0; L < 64; L++) s[L] = lo[L] + hi[L];
+    for (int m = 32; m >= 1; m >>= 1)
+        for (int L = 0; L < m; L++) s[L] = s[L] + s[L ^ m];   /* lane L < m of the full butterfly; the lanes above are copies */
+    return s[0];
+}
+
+float orc_pass_score_f32(const float *row, const float *q, int32_t D) { return pass_tree_f32(row, q, D); }
+
+/* fl16(x), round to nearest even, written out on the bits: subnormal halves kept (spacing 2^-24, |x| <= 2^-25 becomes a signed zero),
+ * 65520 and above become infinity, NaN stays NaN.  The device's conversion is v_cvt_f16_f32 in the default rounding mode. */
+uint16_t orc_f16_bits_rne(float x)
+{
+    uint32_t u;
+    memcpy(&u, &x, 4);
+    const uint16_t sign = (uint16_t)((u >> 16) & 0x8000u);
+    const uint32_t a = u & 0x7FFFFFFFu;
+    if (a > 0x7F800000u) return (uint16_t)(sign | 0x7E00u);
+    if (a >= 0x47800000u) return (uint16_t)(sign | 0x7C00u);            /* 2^16 and above, infinity */
+    if (a >= 0x38800000u) {                                              /* 2^-14 and above: a normal half unless the rounding carries into infinity */
+        const uint32_t m = a - 0x38000000u;                              /* exponent rebiased 127 -> 15 */
+        return (uint16_t)(sign | ((m + 0xFFFu + ((m >> 13) & 1u)) >> 13));
+    }
+    if (a <= 0x33000000u) return sign;                                   /* 2^-25 and below: zero (2^-25 itself is the tie with the even 0) */
+    const uint32_t shift = 126u - (a >> 23);                             /* 14 .. 24: the units of 2^-24 in a 24-bit significand */
+    const uint32_t mant = (a & 0x7FFFFFu) | 0x800000u;
+    uint32_t h = mant >> shift;
+    const uint32_t rem = mant & ((1u << shift) - 1u), half = 1u << (shift - 1u);
+    if (rem > half || (rem == half && (h & 1u))) h++;                    /* may reach 0x400: the smallest normal half */
+    return (uint16_t)(sign | h);
+}
+
+float orc_f16_bits_to_f32(uint16_t h)
+{
+    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, ex = (h >> 10) & 31u, man = h & 1023u;
+    uint32_t u;
+    float f;
+    if (ex == 0) {
+        f = (float)man * 0x1p-24f;                                       /* exact */
+        memcpy(&u, &f, 4);
+        u |= sign;
+    } else if (ex == 31) u = sign | 0x7F800000u | (man << 13);
+    else u = sign | ((ex + 112u) << 23) | (man << 13);
+    memcpy(&f, &u, 4);
+    return f;
+}
+
+void orc_f16_round_bits(const float *x, int64_t n, uint16_t *out)
+{
+    for (int64_t i = 0; i < n; i++) out[i] = orc_f16_bits_rne(x[i]);
+}
+
+/* what a workgroup of db_scan_halfq stages for one query: fl16(2^e q) per element (the product in fp32, exact unless it leaves fp32's
+ * range), widened back to fp32 (exact) */
+void orc_halfq_stage(const float *q, int32_t D, int32_t e, float *staged)
+{
+    const float up = ldexpf(1.0f, e);
+    for (int32_t j = 0; j < D; j++) staged[j] = orc_f16_bits_to_f32(orc_f16_bits_rne(q[j] * up));
+}
+
+/* the score db_scan_halfq puts into a list: the fp32 pass score over the staged query, times 2^-e in fp64 (exact) */
+double orc_pass_score_halfq(const float *row, const float *q, int32_t D, int32_t e)
+{
+    float *h = (float *)malloc(sizeof(float) * (size_t)D);
+    orc_halfq_stage(q, D, e, h);
+    const double s = (double)pass_tree_f32(row, h, D) * ldexp(1.0, -e);
+    free(h);
+    return s;
+}
+
+/* Both, over a whole prefix: out[q * k + i] = the score of row i against query q as the pass's lists hold it (a double: the fp32 score
+ * widened, halfq: scaled back).  halfq = 0: db_scan_prefilter (e is ignored); 1: db_scan_halfq. */
+void orc_pass_scores(const float *db, int64_t k, int32_t D, const float *queries, int32_t nq, int32_t halfq, int32_t e, double *out, int32_t nthreads)
+{
+    if (nthreads <= 0) nthreads = 1;
+    float *staged = NULL;
+    if (halfq) {
+        staged = (float *)malloc(sizeof(float) * (size_t)nq * D);
+        for (int32_t q = 0; q < nq; q++) orc_halfq_stage(queries + (size_t)q * D, D, e, staged + (size_t)q * D);
+        queries = staged;
+    }
+    const double down = halfq ? ldexp(1.0, -e) : 1.0;
+#pragma omp parallel for schedule(static) num_threads(nthreads)
+    for (int64_t i = 0; i < k; i++)
+        for (int32_t q = 0; q < nq; q++) out[(size_t)q * k + i] = (double)pass_tree_f32(db + (size_t)i * D, queries + (size_t)q * D, D) * down;
+    free(staged);
+}
+
 /* ---------------------------------------------------------------- the tick */
 void orc_dot_params_default(orc_dot_params *p)
 {

@@ -226,6 +226,67 @@ def scores(db: np.ndarray, k: int, query: np.ndarray, nthreads: int = 1) -> np.n
     return u
 
 
+def _bind_pass():
+    lib = load()
+    if getattr(lib, "_pass_bound", False):
+        return lib
+    V = C.c_void_p
+    lib.orc_pass_score_f32.restype = C.c_float
+    lib.orc_pass_score_f32.argtypes = [V, V, C.c_int32]
+    lib.orc_pass_score_halfq.restype = C.c_double
+    lib.orc_pass_score_halfq.argtypes = [V, V, C.c_int32, C.c_int32]
+    lib.orc_f16_round_bits.restype = None
+    lib.orc_f16_round_bits.argtypes = [V, C.c_int64, V]
+    lib.orc_halfq_stage.restype = None
+    lib.orc_halfq_stage.argtypes = [V, C.c_int32, C.c_int32, V]
+    lib.orc_pass_scores.restype = None
+    lib.orc_pass_scores.argtypes = [V, C.c_int64, C.c_int32, V, C.c_int32, C.c_int32, C.c_int32, V, C.c_int32]
+    lib._pass_bound = True
+    return lib
+
+
+def pass_score_f32(row: np.ndarray, q: np.ndarray) -> np.float32:
+    """the fp32 score db_scan_prefilter computes for one (row, query) pair (orc_pass_score_f32)"""
+    row = np.ascontiguousarray(row, dtype=np.float32)
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    assert row.size == q.size and row.size % 256 == 0
+    return np.float32(_bind_pass().orc_pass_score_f32(_p(row), _p(q), row.size))
+
+
+def pass_score_halfq(row: np.ndarray, q: np.ndarray, e: int) -> float:
+    """the score db_scan_halfq puts into a list for one (row, query) pair: fp16-staged query, fp32 sum, 2^-e in fp64 (orc_pass_score_halfq)"""
+    row = np.ascontiguousarray(row, dtype=np.float32)
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    assert row.size == q.size and row.size % 256 == 0
+    return float(_bind_pass().orc_pass_score_halfq(_p(row), _p(q), row.size, e))
+
+
+def f16_round_bits(x: np.ndarray) -> np.ndarray:
+    """fl16(x), round to nearest even, as uint16 bit patterns: the oracle's integer arithmetic, not numpy's conversion"""
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    out = np.empty(x.size, dtype=np.uint16)
+    _bind_pass().orc_f16_round_bits(_p(x), x.size, _p(out))
+    return out
+
+
+def halfq_stage(q: np.ndarray, e: int) -> np.ndarray:
+    """fl16(2^e q) widened to float32: what db_scan_halfq stages for a query"""
+    q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1)
+    out = np.empty(q.size, dtype=np.float32)
+    _bind_pass().orc_halfq_stage(_p(q), q.size, e, _p(out))
+    return out
+
+
+def pass_scores(db: np.ndarray, k: int, queries: np.ndarray, halfq: bool = False, e: int = 0, nthreads: int = 16) -> np.ndarray:
+    """float64 [nq, k]: the score of every row of [0, k) against every query as the lists of db_scan_prefilter (halfq=False) or
+    db_scan_halfq (halfq=True, exponent e) hold it"""
+    assert db.dtype == np.float32 and db.flags.c_contiguous and db.shape[1] % 256 == 0 and k <= len(db)
+    queries = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, db.shape[1])
+    out = np.empty((queries.shape[0], k), dtype=np.float64)
+    _bind_pass().orc_pass_scores(_p(db), k, db.shape[1], _p(queries), queries.shape[0], 1 if halfq else 0, e, _p(out), nthreads)
+    return out
+
+
 def ref_scan_f64_colmajor(M: np.ndarray, k: int, v, vm, vmm):
     """M: (cols, D) float64 array whose row i is column i of the reference's column-major M."""
     D = M.shape[1]

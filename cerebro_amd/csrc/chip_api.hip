@@ -921,7 +921,7 @@ static int append_pass(Ctx *c, const AppendSrc &src, int64_t first, int64_t from
 }
 
 // DB rows only (rows past the published length are invisible to queries); *bad gets the validation bits of THIS ctx's share:
-// bit0 = a value that is not float32-representable went into float rows, bit1 = NaN / Inf.
+// bit0 = a value that is not float32-representable went into float rows, bit1 = NaN / Inf, bit2 (with bit0) = a finite value became +-Inf.
 int append_store_db(Ctx *c, const AppendSrc &src, int64_t first, int64_t n, bool owner_only, uint32_t *bad)
 {
     *c->flags_host.host() = 0;
@@ -1016,7 +1016,11 @@ int ctx_append(Ctx *c, const AppendSrc &src, int64_t n, uint32_t flags, int64_t 
         // with" (a state.json checkpoint holds 15-digit decimal text, RawFileIO.cpp:330-459): they are rounded to the float rows they
         // came from, also in an empty undecided DB.  Without the flag the data decides: an empty undecided DB takes values that are
         // not float32-representable as they are (double rows); anywhere else they are refused.
-        if (flags & CHIP_APPEND_ALLOW_ROUNDING) break;
+        // Rounding is to a float32 VALUE: a finite wire value beyond the float range (bit2) would be stored as +-Inf, and a DB never holds one.
+        if (flags & CHIP_APPEND_ALLOW_ROUNDING) {
+            if (bad & 4u) return CHIP_ERR_NONFINITE;
+            break;
+        }
         if (attempt == 0 && append_can_switch_to_double(c, first)) {
             rc = append_switch_to_double(c, n);
             if (rc != CHIP_OK) return rc;

@@ -370,7 +370,7 @@ struct Ctx {
     // --- append staging ---
     DevBuf<char> stage_dev;              // staging for host descriptors
     size_t stage_bytes = 0;
-    DevBuf<uint32_t> flags_dev;          // bit0: not-f32-representable, bit1: non-finite
+    DevBuf<uint32_t> flags_dev;          // bit0: not-f32-representable, bit1: non-finite, bit2: finite but +-Inf as a float
     PinnedBuf<uint32_t> flags_host;
     DevBuf<unsigned long long> norm2_dev;     // float rows: bits of the largest fp64 sum of squares among the rows the running append has stored
     PinnedBuf<unsigned long long> norm2_host;

@@ -2281,9 +2281,15 @@ __device__ __forceinline__ void store_row4(const StoreArgs &a, int64_t g, int e,
     }
 }
 
+// 4u (flag bit2) if the float a finite double narrowed to is +-Inf: exponent field 0xff, by integer arithmetic on the bits (no compare: the
+// kernel keeps the registers recorded in profiles/project.md)
+__device__ __forceinline__ uint32_t inf_bit2(float v) { return (((__float_as_uint(v) & 0x7fffffffu) + 0x00800000u) >> 31) << 2; }
+__device__ __forceinline__ uint32_t inf_bit2(double) { return 0u; }
+
 // M.col(_s) = desc (Cerebro.cpp:1005-1006): wire type S (float64[] of the .srv, or float) -> storage type T.
 //   double -> float : round-to-nearest-even, flag bit0 unless (double)(float)x == x (lossless narrowing is the contract)
 //   float  -> double, same -> same : exact.        NaN / Inf in any combination: flag bit1.
+//   double -> float of a finite |x| >= 0x1.ffffffp+127: the float is +-Inf; bit0 and bit2 (ctx_append: refused with or without the flag)
 template <typename S, typename T>
 __global__ __launch_bounds__(256) void convert_rows(StoreArgs a, const S *__restrict__ src)
 {
@@ -2307,7 +2313,7 @@ __global__ __launch_bounds__(256) void convert_rows(StoreArgs a, const S *__rest
         for (int c = 0; c < 4; c++) {
             v[c] = (T)x[c];
             if (!(fabs((double)x[c]) <= 1.79769313486231570e308)) bad |= 2u;   // NaN / Inf
-            else if (sizeof(T) < sizeof(S) && (S)v[c] != x[c]) bad |= 1u;        // not fp32-representable (incl. overflow)
+            else if (sizeof(T) < sizeof(S) && (S)v[c] != x[c]) bad |= 1u | inf_bit2(v[c]);   // not fp32-representable (incl. overflow)
         }
         store_row4<T>(a, a.first_global + r * a.row_stride, e, v);
     }

@@ -152,7 +152,9 @@ int  chip_synchronize(chip_ctx *ctx);
 #define CHIP_APPEND_ALLOW_ROUNDING 1u   /* the caller vouches that the values ARE float32 descriptors up to the precision they were
                                            printed / transmitted with (a state.json checkpoint: 15-digit text): round to nearest
                                            instead of failing -- also in an empty undecided DB, which then stays a float DB; sets
-                                           info.lossy_rows.  Without the flag the data decides (chip_create above).             */
+                                           info.lossy_rows.  Without the flag the data decides (chip_create above).  The flag
+                                           never stores an Inf: a finite value whose nearest float32 is +-Inf (|x| >= 0x1.ffffffp+127)
+                                           is CHIP_ERR_NONFINITE with it (without it CHIP_ERR_NOT_F32, or double rows, as before).  */
 int chip_db_append_f64(chip_ctx *ctx, const double *desc, int64_t n, uint32_t flags, int64_t *first_index);
 int chip_db_append_f32(chip_ctx *ctx, const float *desc, int64_t n, int64_t *first_index);
 int64_t chip_db_size(const chip_ctx *ctx);           /* global number of appended rows (== l)             */

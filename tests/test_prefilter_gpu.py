@@ -3,6 +3,8 @@ tick_rescore proves per query which rows can be in the exact top-8 and scores th
 test_tick_coalesce_gpu.py: every 64-byte decision record of a window of four forced-parked ticks equals, byte for byte, the record of the
 same tick issued alone with coalescing off, one per window the CPU oracle's -- where the certificate holds AND where it does not (such a
 tick runs again alone).  CHIP_SCAN_OVERLAP_GIB=0 makes every scan a long one, parking is forced, coalescing is at its default."""
+import math
+
 import numpy as np
 import pytest
 
@@ -187,20 +189,21 @@ def test_all_rows_equal_never_certifies(monkeypatch):
 
 def test_row_norm_max_follows_every_append(monkeypatch):
     D = 1024
-    norm = lambda x: float(np.sqrt((np.asarray(x, dtype=np.float64) ** 2).sum(axis=1)).max())
+    # the correctly rounded norm of the heaviest row (exact squares, math.fsum); N is at most 1 + 2^-29 of it: tests/ingest_cases.py TIGHT
+    norm = lambda x: max(math.sqrt(math.fsum((r * r).tolist())) for r in np.asarray(x, dtype=np.float64))
     monkeypatch.delenv("CHIP_TICK_COALESCE", raising=False)
     with capi.Chip(D, capacity_hint=4096) as chip:
         assert chip.info()["row_norm_max"] == 0.0
         a = np.ascontiguousarray(oracle_lib.synth_rows(SEED, range(300), D), dtype=np.float32) * np.float32(0.5)
         chip.append_f32(a)
         want = norm(a)
-        assert want <= chip.info()["row_norm_max"] <= want * (1 + 1e-6)
+        assert want <= chip.info()["row_norm_max"] <= want * (1 + 2.0 ** -29)
         plants = [(310, 5, 1), (320, 6, 2)]
         chip.append_synthetic(200, SEED, plants)                 # rows 300 .. 499: generated rows and both kinds of plants
         want = max(want, norm(oracle_lib.synth_rows(SEED, range(300, 500), D, plants)))
-        assert want <= chip.info()["row_norm_max"] <= want * (1 + 1e-6)
+        assert want <= chip.info()["row_norm_max"] <= want * (1 + 2.0 ** -29)
         c = np.ascontiguousarray(oracle_lib.synth_rows(SEED + 1, range(40), D), dtype=np.float32).astype(np.float64) * 2.0
         chip.append_f64(c)                                       # float64 on the wire, float rows in the DB
         assert chip.info()["storage_bytes"] == 4
         want = max(want, norm(c))
-        assert want <= chip.info()["row_norm_max"] <= want * (1 + 1e-6)
+        assert want <= chip.info()["row_norm_max"] <= want * (1 + 2.0 ** -29)

@@ -240,6 +240,13 @@ _SIGS = {
     "chip_query_scores": (C.c_int, [_P, C.c_int64, C.c_int64, _P]),
     "chip_query_batch_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P]),
     "chip_query_batch_cast_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P]),
+    "chip_build_has_query_prefix": (C.c_int, []),
+    "chip_query_batch_rows_f32": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
+    "chip_query_batch_rows_cast_f32": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
+    "chip_query_batch_prefix_f32": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
+    "chip_query_batch_prefix_cast_f32": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
+    "chip_query_prefix_plan": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "chip_debug_query_prefix_last": (C.c_int, [_P, _P]),
     "chip_dot_params_default": (None, [C.POINTER(DotParams)]),
     "chip_loop_tick": (C.c_int, [_P, C.c_int64, C.POINTER(DotParams), C.POINTER(TickResult)]),
     "chip_resident_pause": (C.c_int, [_P]),
@@ -527,6 +534,35 @@ def project_plan(in_dim: int, matrix_type: int, n: int) -> dict:
     if rc != CHIP_OK:
         raise ChipError(rc, "chip_project_plan")
     return {name: getattr(out, name) for name, _ in ProjectPlan._fields_ if name != "reserved"}
+
+
+CHIP_QUERY_PREFIX_GROUP = 4096
+
+
+class QueryPrefixPlan(C.Structure):
+    """chip_query_prefix_plan_out"""
+    _fields_ = [("group_size", C.c_int32), ("groups", C.c_int32), ("tile_full", C.c_int32), ("tile_last", C.c_int32),
+                ("qtiles", C.c_int64), ("units", C.c_int64), ("units_rect", C.c_int64)]
+
+
+class QueryPrefixLast(C.Structure):
+    """chip_query_prefix_last"""
+    _fields_ = [("groups", C.c_int32), ("launches", C.c_int32), ("waits", C.c_int32), ("reserved", C.c_int32),
+                ("units_claimed", C.c_int64), ("units_planned", C.c_int64)]
+
+
+def query_prefix_plan(k, elem: int = 4, topk: int = 5) -> dict:
+    """chip_query_prefix_plan -> the order and the work of a prefix call over the prefixes k: order (int32 [Q], the caller's position of
+    the i-th query walked), group_size, groups, tile_full, tile_last, qtiles, units, units_rect.  Needs no ctx and no device."""
+    k = np.ascontiguousarray(k, dtype=np.int64).reshape(-1)
+    order = np.empty(k.shape[0], dtype=np.int32)
+    out = QueryPrefixPlan()
+    rc = load_library().chip_query_prefix_plan(_ptr(k), k.shape[0], elem, topk, _ptr(order), C.byref(out))
+    if rc != CHIP_OK:
+        raise ChipError(rc, "chip_query_prefix_plan")
+    d = {name: getattr(out, name) for name, _ in QueryPrefixPlan._fields_}
+    d["order"] = order
+    return d
 
 
 def default_ransac_params() -> RansacParams:
@@ -910,6 +946,47 @@ class Chip:
         name = "chip_query_batch_cast_f32" if cast_rows else "chip_query_batch_f32"
         self._chk(getattr(self.lib, name)(self.h, k, _ptr(q), Q, topk, _ptr(sc), _ptr(ix)), name)
         return sc, ix
+
+    def query_batch_rows(self, rows, k, topk: int = CHIP_DEFAULT_TOPK, cast_rows: bool = False):
+        """many-query mode with a prefix per query, the queries taken from DB rows on the device: query j is row rows[j] against rows
+        [0, k[j]).  Returns (scores float32 [Q, topk], idx int64 [Q, topk]) in the caller's order; entry j is what
+        query_batch(k[j], row rows[j], topk) gives.  cast_rows=True: chip_query_batch_rows_cast_f32 (double rows, narrowed RNE)."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        k = np.ascontiguousarray(k, dtype=np.int64).reshape(-1)
+        if rows.shape != k.shape:
+            raise ValueError("rows and k must have the same length")
+        Q = rows.shape[0]
+        sc = np.empty((Q, topk), dtype=np.float32)
+        ix = np.empty((Q, topk), dtype=np.int64)
+        name = "chip_query_batch_rows_cast_f32" if cast_rows else "chip_query_batch_rows_f32"
+        self._chk(getattr(self.lib, name)(self.h, _ptr(rows), _ptr(k), Q, topk, _ptr(sc), _ptr(ix)), name)
+        return sc, ix
+
+    def query_batch_prefix(self, k, q: np.ndarray, topk: int = CHIP_DEFAULT_TOPK, cast_rows: bool = False):
+        """many-query mode with a prefix per query, host vectors: query j is q[j] against rows [0, k[j]).  Returns as query_batch_rows."""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self.D)
+        k = np.ascontiguousarray(k, dtype=np.int64).reshape(-1)
+        Q = q.shape[0]
+        if k.shape[0] != Q:
+            raise ValueError("k must have one entry per query")
+        sc = np.empty((Q, topk), dtype=np.float32)
+        ix = np.empty((Q, topk), dtype=np.int64)
+        name = "chip_query_batch_prefix_cast_f32" if cast_rows else "chip_query_batch_prefix_f32"
+        self._chk(getattr(self.lib, name)(self.h, _ptr(k), _ptr(q), Q, topk, _ptr(sc), _ptr(ix)), name)
+        return sc, ix
+
+    def self_join(self, first: int, count: int, lag: int, topk: int = CHIP_DEFAULT_TOPK, cast_rows: bool = False):
+        """the causal self-join of rows [first, first + count): row first + j against rows [0, max(0, first + j - lag)) -- one
+        query_batch_rows call."""
+        rows = first + np.arange(count, dtype=np.int64)
+        return self.query_batch_rows(rows, np.maximum(0, rows - lag), topk, cast_rows)
+
+    def debug_query_prefix_last(self) -> dict:
+        """chip_debug_query_prefix_last: groups, launches, host waits of the last prefix call, the DB tiles its kernels walked
+        (units_claimed, from the kernels' own counters) and the tiles the host planned (units_planned)"""
+        out = QueryPrefixLast()
+        self._chk(self.lib.chip_debug_query_prefix_last(self.h, C.byref(out)), "chip_debug_query_prefix_last")
+        return {name: getattr(out, name) for name, _ in QueryPrefixLast._fields_ if name != "reserved"}
 
     # -- tick
     def loop_tick(self, l: int, params: DotParams | None = None) -> TickResult:

@@ -22,7 +22,9 @@
 //   merge_sorted_lists) merges them.
 #include "chip_internal.h"
 #include "topk_merge.h"
+#include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <new>
 #include <type_traits>
 
@@ -128,6 +130,15 @@ __device__ __forceinline__ void glds16(const float *gsrc, uint32_t lds_byte_addr
                  : "v"(gsrc), "s"(lds_byte_addr_wave_uniform)
                  : "memory");
 }
+// the same load addressed as wave-uniform base + 32-bit byte offset per lane (the prefix forms: no 64-bit pointer per lane and load)
+__device__ __forceinline__ void glds16_s(const void *base_wave_uniform, uint32_t byte_off, uint32_t lds_byte_addr_wave_uniform)
+{
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(byte_off), "s"(base_wave_uniform), "s"(lds_byte_addr_wave_uniform)
+                 : "memory");
+}
 __device__ __forceinline__ uint32_t lds_addr(const void *p)
 {
     return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
@@ -136,6 +147,14 @@ __device__ __forceinline__ uint32_t lds_addr(const void *p)
 __device__ __forceinline__ void wait_loads_and_barrier()
 {
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+// the lane number, read anew where it is called (the prefix forms: see db_gemm_body.inc)
+__device__ __forceinline__ int lane_now()
+{
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
 }
 
 // Double rows (chip_query_batch_cast_f32): the B side of the same LDS image, filled through registers.  The reference's faiss variants
@@ -178,284 +197,85 @@ __global__ __launch_bounds__(256) void transpose_queries(const float *__restrict
     }
 }
 
+// The same image made on the device from DB rows (chip_query_batch_rows_f32: the queries of a causal self-join ARE rows of the DB):
+// Qt[qtile][chunk][k][q] <- row rows[qtile * TM + q], elements [chunk * 32 + k], straight through the segment table -- no Q image, no
+// memset, no second launch.  One workgroup per (chunk, query tile): a row's 32 elements of the chunk are read as whole 16-byte vectors
+// along D (8 per float row, 16 per double row), turned through LDS, and written out TM floats per k (coalesced).  Double rows are
+// narrowed with v_cvt_f32_f64, the cast loader's own conversion, so a query row and a DB row round alike.  rows[q] < 0: a padded
+// query, written as zeros.
+struct GatherArgs {
+    const void *const *seg_table;
+    int32_t seg_shift;
+    int64_t seg_mask;
+    int32_t D;
+    const int64_t *rows;    // [Qpad] local rows, -1 for padded queries
+    float *Qt;
+};
+template <typename ROW, int TM>
+__global__ __launch_bounds__(256) void gather_query_tiles(GatherArgs g)
+{
+    constexpr int KC = 32;
+    constexpr bool DBL = std::is_same<ROW, double>::value;
+    static_assert(DBL || std::is_same<ROW, float>::value, "float or double rows");
+    constexpr int VPR = DBL ? 16 : 8;    // 16-byte vectors per row and chunk
+    constexpr int EPV = KC / VPR;        // elements per vector
+    __shared__ float T[KC][TM + 1];
+    const int chunk = blockIdx.x, qt = blockIdx.y, n_chunks = g.D / KC;
+    for (int i = threadIdx.x; i < TM * VPR; i += 256) {
+        const int q = i / VPR, v = i % VPR;
+        const int64_t r = g.rows[(int64_t)qt * TM + q];
+        float x[EPV];
+#pragma unroll
+        for (int e = 0; e < EPV; e++) x[e] = 0.0f;
+        if (r >= 0) {
+            const ROW *src = reinterpret_cast<const ROW *const *>(g.seg_table)[r >> g.seg_shift] + (r & g.seg_mask) * (int64_t)g.D + chunk * KC + v * EPV;
+            if constexpr (DBL) {
+                const f64x2 d = *reinterpret_cast<const f64x2 *>(src);
+                x[0] = (float)d[0]; x[1] = (float)d[1];
+            } else {
+                const f32x4 f = *reinterpret_cast<const f32x4 *>(src);
+                x[0] = f[0]; x[1] = f[1]; x[2] = f[2]; x[3] = f[3];
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < EPV; e++) T[v * EPV + e][q] = x[e];
+    }
+    __syncthreads();
+    float *dst = g.Qt + ((int64_t)qt * n_chunks + chunk) * (KC * TM);
+    for (int i = threadIdx.x; i < KC * TM; i += 256) dst[i] = T[i / TM][i % TM];
+}
+
 // WN = waves along the DB rows of a tile (2 or 4); a wave owns WN x 2 MFMA 32x32 blocks (64 WN queries x 64 DB rows), the
 // workgroup tile is 64 WN x 64 WN (128 x 128 with 4 waves, 256 x 256 with 8), 2 x WN waves, 8 LDS-DMA per wave per chunk either way.
 // ROW = float: DB rows by LDS-DMA; ROW = double: rows narrowed to float on their way into the same image (see above).
+//
+// The body is stated once, for two kernels.  db_gemm_topk (PREFIX = false) scans rows [0, a.n_rows) for every query.  db_gemm_prefixed
+// (PREFIX = true: chip_query_batch_rows_f32 / chip_query_batch_prefix_f32) gives every query a prefix of its own: the tile walk of a query
+// tile ends at lim.tile_limit[blockIdx.y], the largest limit among its queries (0: nothing is walked, the lists stay empty), and the
+// epilogue clips the columns a thread scans by its own query's lim.q_limit.  The K loop, the staging and the lists do not know.
+struct PrefixLimits {
+    const int32_t *q_limit;      // [Qpad] local row limit of each query (0 for padded queries)
+    const int32_t *tile_limit;   // [query tiles] max of q_limit over the tile
+    uint32_t *done;              // [query tiles] work done, in half tiles (zeroed before the launch): what the kernel really walked
+};
+struct PrefixArgs {
+    BatchArgs b;
+    PrefixLimits lim;
+};
 template <int KC, int WN, int KL, typename ROW>
 __global__ __launch_bounds__(128 * WN) void db_gemm_topk(BatchArgs a)
 {
-    constexpr bool CAST = std::is_same<ROW, double>::value;
-    static_assert(CAST || std::is_same<ROW, float>::value, "float or double rows");
-    static_assert(KC == 32, "one K-chunk = 8 slots of 4 floats per DB row");
-    static_assert(WN == 2 || WN == 4, "tile 128 x 128 or 256 x 256");
-    constexpr int TM = 64 * WN, TN = 64 * WN;            // tile: queries x DB rows
-    constexpr int NT = 128 * WN, WAVES = 2 * WN;          // threads, waves
-    constexpr int TILE = TM * KC;                         // floats of the A tile of one stage
-    constexpr int BTILE = (TN / 8) * kBBlock;             // DB tile: TN / 8 blocks of 8 rows, kBBlock floats apart
-    constexpr int STAGE = TILE + BTILE;                   // A tile then B tile
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float *S0 = reinterpret_cast<float *>(smem);        // stage s: A = S0 + s*STAGE, B = A + TILE
-    float *Ct = reinterpret_cast<float *>(smem);         // [TM][CT_LD] (aliases the stages after the K loop)
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WN, wn = wave % WN;
-    const int D = a.D, K = a.K;
-    const int q0 = blockIdx.y * TM;
-    // DB tiles are handed out dynamically: workgroup x of a query tile starts on DB tile x and then takes the next unclaimed one
-    // from a counter (one atomic per tile, ~1 ms of work; fetched at the start of the tile, read at its end).  With a static
-    // split 3907 tiles over 256 workgroups cost 16 tile times on every CU; claimed tiles cost 15.26.  The lists a workgroup
-    // keeps do not care which tiles fed them: the merged top-K is the same set whatever the assignment.
-    __shared__ unsigned next_tile_slot;
-    const int64_t n_tiles = (a.n_rows + TN - 1) / TN;
-
-    // Top-k of the tile scores: ALL threads take part -- thread t owns query q0 + (t % TM) over the 64-column half (t / TM)
-    // of every 128-column epilogue pass, with its sorted list in registers; the two lists of a query are folded at the end.
-    // (Round 1 had 64 owner threads scan 2 x 128 columns while the other three waves -- and, in lockstep, the other workgroup
-    // of the CU -- waited.)
-    const int oq = tid & (TM - 1), och = tid / TM;
-    TopList<KL> L;
-    list_init(L);
-
-    const int n_chunks = D / KC;
-    // A loader: the chunk image is contiguous (TM * 128 B): pass u, wave w copies bytes [(u * WAVES + w) * 1024, + 1024)
-    const float *const a_src = a.Qt + ((int64_t)blockIdx.y * n_chunks) * TILE + (wave * 64 + lane) * 4;
-    // B loader: pass u, wave w, lane i -> 8-row block u * WAVES + w, row i >> 3 of it, slot p = i & 7,
-    // source floats [4 k4, 4 k4 + 4), k4 = p ^ (row & 7)
-    const int l_row = wave * 8 + (lane >> 3), l_p = lane & 7;
-    const int l_k4 = (l_p ^ (lane >> 3)) * 4;
-    // fragment map
-    const int fr = lane & 31, fk = lane >> 5;
-    const int rb0 = wn * 64 + fr, rb1 = rb0 + 32;
-    const int b_off0 = TILE + b_row_off(rb0) + fk, b_off1 = TILE + b_row_off(rb1) + fk, sw0 = rb0 & 7, sw1 = rb1 & 7;
-    const uint32_t lds_base = __builtin_amdgcn_readfirstlane(lds_addr(S0));
-
-    // Units of work: the first n_full = floor(n_tiles / P) * P tiles are whole tiles (P = workgroups of this query tile: full
-    // rounds in which every CU is busy); what remains -- r < P tiles, the round that would leave P - r CUs idle -- is cut
-    // into query halves when 2 r <= P (each wave then owns WN / 2 x 2 blocks and the unit takes half a tile time: 15.5 instead of
-    // 16 tile times for 3907 tiles on 256 CUs).
-    const int64_t n_full = n_tiles / gridDim.x * gridDim.x;
-    const bool halves = 2 * (n_tiles - n_full) <= (int64_t)gridDim.x;
-    const int64_t n_units = halves ? n_full + 2 * (n_tiles - n_full) : n_tiles;
-    for (int64_t unit = blockIdx.x; unit < n_units;) {
-        const bool half_unit = halves && unit >= n_full;
-        const int64_t tile = half_unit ? n_full + ((unit - n_full) >> 1) : unit;
-        const int qhalf = half_unit ? (int)((unit - n_full) & 1) : 0;
-        const int nrb = half_unit ? WN / 2 : WN;                                      // 32-query row blocks per wave in this unit
-        const int qrow0 = half_unit ? qhalf * (TM / 2) + wm * (16 * WN) : wm * (32 * WN);   // first query row of this wave
-        const int a_off = fk * TM + qrow0 + fr;                        // + kk * 2 TM per k-step, + 32 i for row block i
-        const int64_t n0 = tile * TN;
-        unsigned claimed = 0;
-        if (tid == 0) claimed = __hip_atomic_fetch_add(a.tile_ctr + blockIdx.y, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const float *brow[4];
-        // double rows: a tile lies within one segment (seg_rows is a multiple of TN: batch_local_enqueue), so its rows are a
-        // workgroup-uniform base plus 32-bit byte offsets (segments are at most 1 GiB); rows past the end read the tile's first row
-        const char *seg = nullptr;
-        uint32_t boff[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int64_t br = n0 + u * (8 * WAVES) + l_row;
-            if constexpr (CAST) {
-                const int64_t brc = br < a.n_rows ? br : n0;
-                boff[u] = (uint32_t)(((brc & a.seg_mask) * (int64_t)D + l_k4) * 8);
-            } else {
-                const int64_t brc = br < a.n_rows ? br : 0;   // rows past the end: any valid row (their columns are never scanned)
-                brow[u] = reinterpret_cast<const float *const *>(a.seg_table)[brc >> a.seg_shift] + (brc & a.seg_mask) * (int64_t)D + l_k4;
-            }
-        }
-        if constexpr (CAST) {
-            const uint64_t sp = (uint64_t)reinterpret_cast<const char *const *>(a.seg_table)[n0 >> a.seg_shift];
-            // (readfirstlane returns int: each half goes through uint32_t, or a low word with bit 31 set would sign-extend over the high one)
-            const uint32_t sp_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(sp >> 32)), sp_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)sp);
-            seg = (const char *)(((uint64_t)sp_hi << 32) | sp_lo);
-        }
-        f32x16 acc[WN][2];
-#pragma unroll
-        for (int i = 0; i < WN; i++)
-#pragma unroll
-            for (int j = 0; j < 2; j++)
-#pragma unroll
-                for (int e = 0; e < 16; e++) acc[i][j][e] = 0.0f;
-
-        // chunk c -> stage c % NST: 8 LDS-DMA instructions per wave, number j = 2 u + (0: A, 1: B)
-        auto stage_load_one = [&](int c, int j) {
-            const uint32_t st = lds_base + (uint32_t)((c % NST) * STAGE) * 4u;
-            const int u = j >> 1;
-            if (j & 1) {
-                if constexpr (!CAST) glds16(brow[u] + c * KC, st + (uint32_t)(TILE + b_row_off((u * WAVES + wave) * 8)) * 4u);
-            } else glds16(a_src + (int64_t)c * TILE + u * (WAVES * 256), st + (uint32_t)((u * WAVES + wave) * 256) * 4u);
-        };
-        auto stage_load = [&](int c) {
-#pragma unroll
-            for (int j = 0; j < 8; j++) stage_load_one(c, j);
-        };
-        // double rows: slot u of chunk c through registers (the slots of a thread are lane-linear in block u * WAVES + wave)
-        auto cast_load = [&](int c, int u, f64x2 *r) {
-            if constexpr (CAST) {
-                const auto *chunk = (const __attribute__((address_space(1))) char *)seg + (int64_t)c * (KC * 8);
-                const auto *p = (const __attribute__((address_space(1))) f64x2 *)(chunk + boff[u]);
-                r[0] = p[0];
-                r[1] = p[1];
-            }
-        };
-        auto cast_store = [&](int c, int u, const f64x2 *r) {
-            if constexpr (CAST) {
-                float *d = S0 + (c % NST) * STAGE + TILE + b_row_off((u * WAVES + wave) * 8) + lane * 4;
-                const float x = (float)r[0][0], y = (float)r[0][1], z = (float)r[1][0], w = (float)r[1][1];
-                if ((wave & 3) == 0) lds_store_slot<16>(d, x, y, z, w);
-                else if ((wave & 3) == 2) lds_store_slot<8>(d, x, y, z, w);
-                else lds_store_slot<4>(d, x, y, z, w);
-            }
-        };
-        if (n_chunks > 0) {
-            stage_load(0);
-            if constexpr (CAST) {
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    f64x2 r[2];
-                    cast_load(0, u, r);
-                    cast_store(0, u, r);
-                }
-            }
-        }
-        wait_loads_and_barrier();   // chunk 0 has landed
-        // the K loop, instantiated for whole tiles (NRB = WN row blocks per wave) and for query halves (NRB = WN / 2)
-        auto k_loop = [&](auto nrb_tag) {
-            constexpr int NRB = decltype(nrb_tag)::value;
-            for (int c = 0; c < n_chunks; c++) {
-                const float *St = S0 + (c % NST) * STAGE;
-                // chunk c + 1 goes to the stage last read in iteration c-1 (barrier since).  When its 8 LDS-DMA instructions are
-                // issued matters (a burst keeps a wave from issuing MFMAs for ~300 cycles; a late load is waited for at the barrier):
-                //   128 tile  all 8 at once at the top (the other workgroup's wave fills the gap: 119.4 TF vs 114.8 spread);
-                //   256 tile  two in front of each of MFMA groups 1..4 (both waves of a SIMD belong to this workgroup and burst
-                //             together: 0.814 of peak vs 0.792 for the burst, 0.805 for groups 0..3, 0.76 for one per group).
-                //   double rows, both tiles: a thread's four slots in two halves through 16 staging registers -- slots 0, 1 loaded in
-                //             front of group 0 and stored in front of group 3, where slots 2, 3 are loaded, stored in front of group 7;
-                //             the A-side DMA in front of groups 0 and 1 (a store waits for every load issued before it: all of them
-                //             are two groups old by then).
-                const bool prefetch = c + 1 < n_chunks;
-                if (!CAST && WN == 2 && prefetch) stage_load(c + 1);
-                f64x2 raw[2][2];
-                // fragments of k-steps (2 k4, 2 k4 + 1) in f[k4 & 1]: [2 i + t] = A row block i, [2 WN + 2 j + t] = B block j;
-                // the next pair is read before this pair's 4 WN MFMAs are issued
-                float f[2][2 * WN + 4];
-                auto rd = [&](int k4, float *d) {
-#pragma unroll
-                    for (int i = 0; i < NRB; i++) {
-                        d[2 * i] = St[a_off + 32 * i + (2 * k4) * (2 * TM)];
-                        d[2 * i + 1] = St[a_off + 32 * i + (2 * k4 + 1) * (2 * TM)];
-                    }
-                    const int p0 = (k4 ^ sw0) << 2, p1 = (k4 ^ sw1) << 2;
-                    d[2 * WN] = St[b_off0 + p0];     d[2 * WN + 1] = St[b_off0 + p0 + 2];
-                    d[2 * WN + 2] = St[b_off1 + p1]; d[2 * WN + 3] = St[b_off1 + p1 + 2];
-                };
-                rd(0, f[0]);
-                __builtin_amdgcn_sched_group_barrier(0x100, NRB + 2, 0);  // the reads of the first pair
-#pragma unroll
-                for (int k4 = 0; k4 < KC / 4; k4++) {
-                    if (!CAST && WN == 4 && prefetch && k4 >= 1 && k4 <= 4) { stage_load_one(c + 1, 2 * k4 - 2); stage_load_one(c + 1, 2 * k4 - 1); }
-                    if (CAST && prefetch && k4 == 0) { cast_load(c + 1, 0, raw[0]); cast_load(c + 1, 1, raw[1]); }
-                    if (CAST && prefetch && k4 <= 1) { stage_load_one(c + 1, 4 * k4); stage_load_one(c + 1, 4 * k4 + 2); }
-                    if (CAST && prefetch && k4 == 3) {
-                        cast_store(c + 1, 0, raw[0]); cast_store(c + 1, 1, raw[1]);
-                        cast_load(c + 1, 2, raw[0]); cast_load(c + 1, 3, raw[1]);
-                    }
-                    if (CAST && prefetch && k4 == 7) { cast_store(c + 1, 2, raw[0]); cast_store(c + 1, 3, raw[1]); }
-                    if (k4 + 1 < KC / 4) rd(k4 + 1, f[(k4 + 1) & 1]);
-#pragma unroll
-                    for (int t = 0; t < 2; t++) {
-                        const float b0 = f[k4 & 1][2 * WN + t], b1 = f[k4 & 1][2 * WN + 2 + t];
-#pragma unroll
-                        for (int i = 0; i < NRB; i++) {
-                            const float av = f[k4 & 1][2 * i + t];
-                            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b0, acc[i][0], 0, 0, 0);
-                            acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b1, acc[i][1], 0, 0, 0);
-                        }
-                    }
-                    // keep the order "reads of the next pair, then this pair's MFMAs" through the scheduler
-                    __builtin_amdgcn_sched_group_barrier(0x100, NRB + 2, 0);   // DS reads (ds_read2)
-                    __builtin_amdgcn_sched_group_barrier(0x008, 4 * NRB, 0);   // MFMA
-                }
-                // chunk c+1 has landed (no chunk behind it has been issued), every wave is done reading stage c % NST
-                wait_loads_and_barrier();
-            }
-        };
-        if (half_unit) k_loop(std::integral_constant<int, WN / 2>{});
-        else k_loop(std::integral_constant<int, WN>{});
-        // ---- epilogue: the score tile through LDS, 128 DB rows (two of the WN wave columns) per pass (the stages are free:
-        // the K loop ended with a barrier); C/D layout of the MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
-        const int ncols = (a.n_rows - n0) < TN ? (int)(a.n_rows - n0) : TN;
-        // double rows: the epilogue's addresses are recomputed per tile from an opaque copy of the lane -- hoisted out of the tile loop
-        // they would sit in registers the staging needs through the K loop (and spill)
-        int elane = lane, eoq = oq;
-        if constexpr (CAST) asm volatile("" : "+v"(elane), "+v"(eoq));
-#pragma unroll
-        for (int h = 0; h < WN / 2; h++) {
-            if (h > 0) __syncthreads();   // the previous pass's scan is done with Ct
-            if ((wn >> 1) == h) {
-#pragma unroll
-                for (int it = 0; it < WN; it++) {
-                    if (it >= nrb) continue;   // a query half: the upper row blocks hold nothing
-#pragma unroll
-                    for (int jt = 0; jt < 2; jt++)
-#pragma unroll
-                        for (int e = 0; e < 16; e++) {
-                            const int row = qrow0 + it * 32 + (e & 3) + 8 * (e >> 2) + 4 * (elane >> 5);   // query within the tile
-                            const int col = (wn & 1) * 64 + jt * 32 + (elane & 31);                                  // DB row within the pass
-                            Ct[row * CT_LD + col] = acc[it][jt][e];
-                        }
-                }
-            }
-            __syncthreads();
-            float ts;
-            int32_t tr;
-            list_kth(L, K, ts, tr);
-            const int pass_cols = ncols - h * 128;         // columns of this pass that exist
-            const bool mine = !half_unit || (eoq >= qhalf * (TM / 2) && eoq < (qhalf + 1) * (TM / 2));   // a query half: only its queries have scores
-            const int c_hi = !mine ? 0 : pass_cols < (och + 1) * 64 ? pass_cols : (och + 1) * 64;
-            for (int c = och * 64; c < c_hi; c++) {
-                const float s = Ct[eoq * CT_LD + c];
-                const int32_t row = (int32_t)(n0 + h * 128 + c);
-                if (fkey_gt(s, row, ts, tr)) {   // NaN never enters
-                    list_push(L, K, s, row);
-                    list_kth(L, K, ts, tr);
-                }
-            }
-        }
-        // next tile: published by thread 0, read by everyone after the barrier that also ends this tile's use of Ct
-        if (tid == 0) next_tile_slot = gridDim.x + claimed;
-        __syncthreads();
-        if constexpr (CAST) unit = __builtin_amdgcn_readfirstlane(next_tile_slot);   // (registers: the tile's bookkeeping stays scalar)
-        else unit = next_tile_slot;
-    }
-    // fold the two column-half lists of a query into one (through LDS, once per workgroup): one list per (partition, query)
-    __syncthreads();
-    float *const Ls = reinterpret_cast<float *>(smem);                 // [TM][KL]
-    int32_t *const Lr = reinterpret_cast<int32_t *>(Ls + TM * KL);
-    if (och == 1) {
-#pragma unroll
-        for (int j = 0; j < KL; j++) { Ls[oq * KL + j] = L.s[j]; Lr[oq * KL + j] = L.r[j]; }
-    }
-    __syncthreads();
-    if (och == 0) {
-        for (int j = 0; j < K; j++) {
-            const float s = Ls[oq * KL + j];
-            const int32_t row = Lr[oq * KL + j];
-            float ts;
-            int32_t tr;
-            list_kth(L, K, ts, tr);
-            if (row >= 0 && fkey_gt(s, row, ts, tr)) list_push(L, K, s, row);
-        }
-        chip_topk_entry *dst = a.partial + ((int64_t)blockIdx.x * a.Qpad + q0 + oq) * K;
-#pragma unroll
-        for (int j = 0; j < KL; j++)
-            if (j < K) {
-                chip_topk_entry e;
-                e.score = (double)L.s[j];
-                e.idx = L.r[j] >= 0 ? (int64_t)L.r[j] * a.idx_mul + a.idx_add : -1;
-                dst[j] = e;
-            }
-    }
-    (void)NT;
+    constexpr bool PREFIX = false;
+    const PrefixLimits lim{};   // (never read)
+#include "db_gemm_body.inc"
+}
+template <int KC, int WN, int KL, typename ROW>
+__global__ __launch_bounds__(128 * WN) void db_gemm_prefixed(PrefixArgs pa)
+{
+    constexpr bool PREFIX = true;
+    const BatchArgs &a = pa.b;
+    const PrefixLimits lim = pa.lim;
+#include "db_gemm_body.inc"
 }
 
 // one workgroup per 4 queries: merge the P partition lists
@@ -480,7 +300,15 @@ struct BatchState {
     // chip_debug_merge_lists: the caller's lists, the merged lists, the record
     DevBuf<chip_topk_entry> dbg_in, dbg_out;
     DevBuf<chip_tick_result> dbg_rec;
-    hipEvent_t ev_done = nullptr;     // this shard's list is complete (recorded on its scan stream)
+    // prefix calls (query_batch_prefix): a group's query rows and limits (built in pinned memory, one upload), the sorted host vectors of
+    // a group, the kernel's work counters and their copy, what the last call did
+    PinnedBuf<char> h_prefix_in;
+    DevBuf<char> prefix_in;
+    PinnedBuf<float> h_q;
+    DevBuf<uint32_t> prefix_done;
+    PinnedBuf<uint32_t> h_prefix_done;
+    chip_query_prefix_last prefix_last = {};
+    hipEvent_t ev_done = nullptr;    // this shard's list is complete (recorded on its scan stream)
 };
 
 void batch_destroy(Ctx *c)
@@ -493,6 +321,8 @@ void batch_destroy(Ctx *c)
 }
 
 int32_t batch_qpad(int32_t Q) { return (Q + BM - 1) / BM * BM; }
+// the tile shape rule of both modes (see batch_local_enqueue)
+static bool batch_wide(int32_t Qpad, int elem, int topk) { return Qpad % 256 == 0 && !(elem == 8 && topk > 8); }
 
 // This ctx's share of a many-query call, enqueued on its scan stream: Q queries (host, Q x D fp32) against its LOCAL rows of the global
 // prefix [0, k) -- the whole prefix on a plain ctx, rows i % G == rank of it on a shard -- leaving one sorted [Qpad][topk] list of
@@ -514,7 +344,7 @@ int batch_local_enqueue(Ctx *c, int64_t k, const float *queries, int32_t Q, int3
     // streamed once per 256 queries) when the padded query count is a multiple of 256, else 128 x 128 with 4 waves.
     // Double rows with the long lists (topk > 8) keep to the small tile: next to 128 accumulator registers, 32 list registers and
     // the staging of the cast loader the 256 x 256 form does not fit 256 registers per wave (it would spill inside the tile loop).
-    const bool wide = Qpad % 256 == 0 && !(c->elem == 8 && topk > 8);
+    const bool wide = batch_wide(Qpad, c->elem, topk);
     const int TM = wide ? 256 : BM, TN = TM;
     const int qtiles = Qpad / TM;
     const int wgs = wide ? 1 : 2;            // workgroups per CU
@@ -595,6 +425,181 @@ int batch_deliver(Ctx *c, const chip_topk_entry *list_dev, int32_t Q, int32_t to
         if (scores) scores[i] = (float)h_out[i].score;
         if (idx) idx[i] = h_out[i].idx;
     }
+    return CHIP_OK;
+}
+
+// ---- a prefix per query (chip_query_batch_rows_f32, chip_query_batch_prefix_f32 and their cast forms)
+// The walk order of a call: the queries stable-sorted by k ascending, so that the queries of a tile have limits close to each other
+// and the tile walk of a query tile ends at the largest of them.
+// (No exception leaves through the C ABI: an allocation that fails is CHIP_ERR_OOM.)
+static int prefix_order(const int64_t *k, int32_t Q, std::vector<int32_t> &order)
+{
+    try {
+        order.resize((size_t)Q);
+        for (int32_t i = 0; i < Q; i++) order[(size_t)i] = i;
+        std::stable_sort(order.begin(), order.end(), [k](int32_t x, int32_t y) { return k[x] < k[y]; });
+    } catch (const std::bad_alloc &) {
+        return CHIP_ERR_OOM;
+    }
+    return CHIP_OK;
+}
+// One group of the sorted list, queries [first, first + count): its padding and tile shape by the rule of chip_query_batch_f32, and per
+// query tile the largest limit -- the last real query's, the list being sorted (tile_limit, qtiles entries, may be NULL).  The ONE
+// place that decides them: the call and chip_query_prefix_plan both come here.
+struct PrefixGroup {
+    int32_t first, count, Qpad, TM, qtiles;
+    int64_t units;   // DB tiles the group walks: sum over its query tiles of ceil(tile limit / TM)
+};
+static PrefixGroup prefix_group(const int64_t *k, const int32_t *order, int32_t first, int32_t count, int elem, int topk, int32_t *tile_limit)
+{
+    PrefixGroup g;
+    g.first = first; g.count = count; g.Qpad = batch_qpad(count);
+    g.TM = batch_wide(g.Qpad, elem, topk) ? 256 : BM;
+    g.qtiles = g.Qpad / g.TM;
+    g.units = 0;
+    for (int32_t t = 0; t < g.qtiles; t++) {
+        const int32_t end = (t + 1) * g.TM < count ? (t + 1) * g.TM : count;   // (every tile holds a real query: Qpad - count < 128 <= TM)
+        const int64_t lim = k[order[first + end - 1]];
+        if (tile_limit) tile_limit[t] = (int32_t)lim;
+        g.units += (lim + g.TM - 1) / g.TM;
+    }
+    return g;
+}
+
+static void prefix_plan(const int64_t *k, int32_t Q, int elem, int topk, const int32_t *order, chip_query_prefix_plan_out *f)
+{
+    f->group_size = CHIP_QUERY_PREFIX_GROUP; f->groups = 0; f->tile_full = 0; f->tile_last = 0;
+    f->qtiles = 0; f->units = 0; f->units_rect = 0;
+    const int64_t kmax = k[order[Q - 1]];
+    for (int32_t first = 0; first < Q; first += CHIP_QUERY_PREFIX_GROUP) {
+        const int32_t count = Q - first < CHIP_QUERY_PREFIX_GROUP ? Q - first : CHIP_QUERY_PREFIX_GROUP;
+        const PrefixGroup g = prefix_group(k, order, first, count, elem, topk, nullptr);
+        f->groups++;
+        if (count == CHIP_QUERY_PREFIX_GROUP) f->tile_full = g.TM;
+        f->tile_last = g.TM;
+        f->qtiles += g.qtiles;
+        f->units += g.units;
+        f->units_rect += g.qtiles * ((kmax + g.TM - 1) / g.TM);
+    }
+}
+
+// One group of a prefix call on the ctx's scan stream, to the caller's arrays: one gather launch (or memset + upload + transpose_queries
+// for host vectors), one GEMM launch, one merge launch, one copy back, one host wait.  Caller: arguments checked, query lock held, device
+// current, resident scan paused.  query_rows (or, where NULL, queries): the caller's rows or vectors, in the CALLER's order.
+static int prefix_group_run(Ctx *c, BatchState *st, const PrefixGroup &g, const int32_t *tile_limit, const int64_t *k, const int32_t *order,
+                            const int64_t *query_rows, const float *queries, int32_t topk, float *scores, int64_t *idx)
+{
+    const int D = c->D, Qpad = g.Qpad, TM = g.TM, TN = TM, qtiles = g.qtiles;
+    const bool wide = TM == 256, from_rows = query_rows != nullptr;
+    // the group's input image: int64 rows[Qpad] | int32 q_limit[Qpad] | int32 tile_limit[qtiles]
+    const size_t in_bytes = (size_t)Qpad * 12 + (size_t)qtiles * 4;
+    int rc = st->h_prefix_in.reserve(c, in_bytes);
+    if (rc == CHIP_OK) rc = st->prefix_in.reserve(c, in_bytes);
+    if (rc == CHIP_OK) rc = st->Qt.reserve(c, (size_t)Qpad * D);
+    if (rc == CHIP_OK && !from_rows) rc = st->Q.reserve(c, (size_t)Qpad * D);
+    if (rc == CHIP_OK && !from_rows) rc = st->h_q.reserve(c, (size_t)g.count * D);
+    if (rc == CHIP_OK) rc = st->tile_ctr.reserve(c, kMaxQTiles);
+    if (rc == CHIP_OK) rc = st->prefix_done.reserve(c, kMaxQTiles);
+    if (rc == CHIP_OK) rc = st->h_prefix_done.reserve(c, kMaxQTiles);
+    if (rc != CHIP_OK) return rc;
+    int64_t *const h_rows = reinterpret_cast<int64_t *>(st->h_prefix_in.host());
+    int32_t *const h_qlim = reinterpret_cast<int32_t *>(h_rows + Qpad), *const h_tlim = h_qlim + Qpad;
+    for (int32_t i = 0; i < Qpad; i++) {
+        const bool real = i < g.count;
+        const int32_t j = real ? order[g.first + i] : 0;
+        h_rows[i] = real && from_rows ? query_rows[j] : -1;      // (a plain ctx: local row = global row)
+        h_qlim[i] = real ? (int32_t)k[j] : 0;                    // padded queries: limit 0
+    }
+    memcpy(h_tlim, tile_limit, sizeof(int32_t) * (size_t)qtiles);
+    int64_t tiles = (h_tlim[qtiles - 1] + TN - 1) / TN;          // of the group's largest prefix
+    if (tiles < 1) tiles = 1;
+    // workgroups per query tile, as batch_local_enqueue sizes them
+    int64_t P = ((wide ? 1 : 2) * (int64_t)c->n_cus + qtiles - 1) / qtiles;
+    if (P > tiles) P = tiles;
+    if (P > 512) P = 512;
+    const int cap_wgs = env_int("CHIP_BATCH_WGS", 0);
+    if (cap_wgs > 0 && P > cap_wgs) P = cap_wgs;
+    if (P < 1) P = 1;
+    rc = st->partial.reserve(c, (size_t)(P * Qpad * topk));
+    if (rc == CHIP_OK) rc = st->out.reserve(c, (size_t)Qpad * topk);
+    if (rc == CHIP_OK) rc = st->h_out.reserve(c, (size_t)Qpad * topk);
+    if (rc != CHIP_OK) return rc;
+
+    hipStream_t s = c->s_scan;
+    char *const in_dev = st->prefix_in;
+    CHIP_HIP(c, hipMemcpyAsync(in_dev, st->h_prefix_in.host(), in_bytes, hipMemcpyHostToDevice, s));
+    CHIP_HIP(c, hipMemsetAsync(st->tile_ctr, 0, sizeof(uint32_t) * qtiles, s));
+    CHIP_HIP(c, hipMemsetAsync(st->prefix_done, 0, sizeof(uint32_t) * qtiles, s));
+    const void *const *seg_table = reinterpret_cast<const void *const *>(c->seg_table_dev.get());
+    if (from_rows) {
+        GatherArgs ga;
+        ga.seg_table = seg_table; ga.seg_shift = c->seg_shift; ga.seg_mask = c->seg_rows - 1; ga.D = D;
+        ga.rows = reinterpret_cast<const int64_t *>(in_dev); ga.Qt = st->Qt;
+        const dim3 grid((unsigned)(D / 32), (unsigned)qtiles);
+        if (c->elem == 8) {
+            if (wide) hipLaunchKernelGGL((gather_query_tiles<double, 256>), grid, dim3(256), 0, s, ga);
+            else hipLaunchKernelGGL((gather_query_tiles<double, 128>), grid, dim3(256), 0, s, ga);
+        } else {
+            if (wide) hipLaunchKernelGGL((gather_query_tiles<float, 256>), grid, dim3(256), 0, s, ga);
+            else hipLaunchKernelGGL((gather_query_tiles<float, 128>), grid, dim3(256), 0, s, ga);
+        }
+        CHIP_HIP(c, hipGetLastError());
+    } else {
+        float *const h_q = st->h_q.host();
+        for (int32_t i = 0; i < g.count; i++) memcpy(h_q + (size_t)i * D, queries + (size_t)order[g.first + i] * D, sizeof(float) * (size_t)D);
+        if (Qpad > g.count) CHIP_HIP(c, hipMemsetAsync(st->Q + (size_t)g.count * D, 0, sizeof(float) * (size_t)(Qpad - g.count) * D, s));
+        CHIP_HIP(c, hipMemcpyAsync(st->Q, h_q, sizeof(float) * (size_t)g.count * D, hipMemcpyHostToDevice, s));
+        int64_t blocks = ((int64_t)Qpad * D + 255) / 256;
+        if (blocks > (int64_t)c->n_cus * 8) blocks = (int64_t)c->n_cus * 8;
+        hipLaunchKernelGGL(transpose_queries, dim3((unsigned)blocks), dim3(256), 0, s, st->Q, st->Qt, Qpad, D, wide ? 8 : 7);
+        CHIP_HIP(c, hipGetLastError());
+    }
+
+    PrefixArgs a;
+    a.b.seg_table = seg_table; a.b.seg_shift = c->seg_shift; a.b.seg_mask = c->seg_rows - 1;
+    a.b.n_rows = 0 /* unused: the limits say */; a.b.D = D; a.b.Q = nullptr; a.b.Qt = st->Qt; a.b.Qpad = Qpad; a.b.K = topk; a.b.tile_ctr = st->tile_ctr;
+    a.b.idx_mul = 1; a.b.idx_add = 0; a.b.partial = st->partial;
+    a.lim.q_limit = reinterpret_cast<const int32_t *>(in_dev + (size_t)Qpad * 8);
+    a.lim.tile_limit = a.lim.q_limit + Qpad;
+    a.lim.done = st->prefix_done;
+    const size_t lds_gemm = sizeof(float) * NST * ((size_t)TM * 32 + (size_t)(TN / 8) * kBBlock);
+    const size_t lds_ct = sizeof(float) * (size_t)TM * CT_LD;
+    const size_t lds = lds_gemm > lds_ct ? lds_gemm : lds_ct;
+    auto launch = [&](auto kernel, int threads) -> int {
+        CHIP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kernel, dim3((unsigned)P, (unsigned)qtiles), dim3(threads), lds, s, a);
+        return CHIP_OK;
+    };
+    int lrc;
+    if (c->elem == 8) {
+        if (topk <= 8) lrc = wide ? launch(db_gemm_prefixed<32, 4, 8, double>, 512) : launch(db_gemm_prefixed<32, 2, 8, double>, 256);
+        else lrc = launch(db_gemm_prefixed<32, 2, CHIP_MAX_TOPK, double>, 256);   // (batch_wide: never the wide tile)
+    } else if (topk <= 8) lrc = wide ? launch(db_gemm_prefixed<32, 4, 8, float>, 512) : launch(db_gemm_prefixed<32, 2, 8, float>, 256);
+    else lrc = wide ? launch(db_gemm_prefixed<32, 4, CHIP_MAX_TOPK, float>, 512) : launch(db_gemm_prefixed<32, 2, CHIP_MAX_TOPK, float>, 256);
+    if (lrc != CHIP_OK) return lrc;
+    CHIP_HIP(c, hipGetLastError());
+    BatchMergeArgs m;
+    m.in = st->partial; m.n_lists = (int)P; m.Qpad = Qpad; m.K = topk; m.out = st->out;
+    hipLaunchKernelGGL(topk_merge_batch, dim3((g.count + 3) / 4), dim3(512), 0, s, m);
+    CHIP_HIP(c, hipGetLastError());
+    chip_topk_entry *const h_out = st->h_out.host();
+    uint32_t *const h_done = st->h_prefix_done.host();
+    CHIP_HIP(c, hipMemcpyAsync(h_out, st->out, sizeof(chip_topk_entry) * (size_t)g.count * topk, hipMemcpyDeviceToHost, s));
+    CHIP_HIP(c, hipMemcpyAsync(h_done, st->prefix_done, sizeof(uint32_t) * qtiles, hipMemcpyDeviceToHost, s));
+    CHIP_HIP(c, hipStreamSynchronize(s));
+    for (int32_t i = 0; i < g.count; i++) {
+        const size_t to = (size_t)order[g.first + i] * topk, from = (size_t)i * topk;
+        for (int32_t j = 0; j < topk; j++) {
+            scores[to + j] = (float)h_out[from + j].score;
+            idx[to + j] = h_out[from + j].idx;
+        }
+    }
+    chip_query_prefix_last &last = st->prefix_last;
+    last.groups++; last.launches += 3; last.waits++;
+    last.units_planned += g.units;
+    int64_t half_tiles = 0;                                   // the kernel counts half tiles (a query half of a tile is a unit of its own;
+    for (int32_t t = 0; t < qtiles; t++) half_tiles += h_done[t];   // both halves of a tile are walked: the sum of a query tile is even)
+    last.units_claimed += half_tiles / 2;
     return CHIP_OK;
 }
 
@@ -698,4 +703,91 @@ extern "C" int chip_query_batch_f32(chip_ctx *c, int64_t k, const float *queries
 extern "C" int chip_query_batch_cast_f32(chip_ctx *c, int64_t k, const float *queries, int32_t Q, int32_t topk, float *scores, int64_t *idx)
 {
     return query_batch(c, k, queries, Q, topk, scores, idx, true);
+}
+
+// ---- a prefix per query (header: "The same mode with a prefix PER QUERY")
+static int query_batch_prefix(chip_ctx *c, const int64_t *query_rows, const float *queries, bool from_rows, const int64_t *k, int32_t Q, int32_t topk,
+                              float *scores, int64_t *idx, bool cast_rows)
+{
+    if (!c || !k || !scores || !idx || Q < 1 || (from_rows ? !query_rows : !queries)) return CHIP_ERR_INVALID_ARG;
+    if (topk < 1 || topk > CHIP_MAX_TOPK || c->D % 32 != 0) return CHIP_ERR_UNSUPPORTED;
+    if (c->group || c->nranks != 1) return CHIP_ERR_UNSUPPORTED;    // a query row of a sharded DB lives on one rank only: not in this interface yet
+    if (c->elem != 4 && !cast_rows) return CHIP_ERR_UNSUPPORTED;
+    int64_t n_global;
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        n_global = c->rows_global;
+    }
+    for (int32_t j = 0; j < Q; j++) {
+        if (k[j] < 0 || k[j] > n_global) return CHIP_ERR_RANGE;
+        if (from_rows && (query_rows[j] < 0 || query_rows[j] >= n_global)) return CHIP_ERR_RANGE;
+    }
+    if (n_global > INT32_MAX) return CHIP_ERR_UNSUPPORTED;          // the limits travel as int32, like the rows of a list
+    // both loaders of db_gemm_prefixed address a DB tile through ONE segment base and 32-bit offsets: a tile (256 rows at most) must lie
+    // within a segment, whatever the storage type (never otherwise: segments hold at least 8192 rows)
+    if (c->seg_rows % 256 != 0) return CHIP_ERR_UNSUPPORTED;
+    std::vector<int32_t> order;
+    const int orc = prefix_order(k, Q, order);
+    if (orc != CHIP_OK) return orc;
+    std::lock_guard<std::mutex> qlk(c->query_mu);
+    CHIP_HIP(c, hipSetDevice(c->device));
+    if (!c->batch_state) {
+        c->batch_state = new (std::nothrow) BatchState();
+        if (!c->batch_state) return CHIP_ERR_OOM;
+    }
+    BatchState *st = c->batch_state;
+    ResidentPause paused(c);   // as batch_local_enqueue: the scan fills every CU (and may free / allocate)
+    st->prefix_last = chip_query_prefix_last{};
+    int32_t tile_limit[CHIP_QUERY_PREFIX_GROUP / BM];
+    for (int32_t first = 0; first < Q; first += CHIP_QUERY_PREFIX_GROUP) {
+        const int32_t count = Q - first < CHIP_QUERY_PREFIX_GROUP ? Q - first : CHIP_QUERY_PREFIX_GROUP;
+        const PrefixGroup g = prefix_group(k, order.data(), first, count, c->elem, topk, tile_limit);
+        const int rc = prefix_group_run(c, st, g, tile_limit, k, order.data(), from_rows ? query_rows : nullptr, queries, topk, scores, idx);
+        if (rc != CHIP_OK) return rc;
+    }
+    return CHIP_OK;
+}
+
+extern "C" int chip_build_has_query_prefix(void) { return 1; }
+
+extern "C" int chip_query_batch_rows_f32(chip_ctx *c, const int64_t *query_rows, const int64_t *k, int32_t Q, int32_t topk, float *scores, int64_t *idx)
+{
+    return query_batch_prefix(c, query_rows, nullptr, true, k, Q, topk, scores, idx, false);
+}
+
+extern "C" int chip_query_batch_rows_cast_f32(chip_ctx *c, const int64_t *query_rows, const int64_t *k, int32_t Q, int32_t topk, float *scores, int64_t *idx)
+{
+    return query_batch_prefix(c, query_rows, nullptr, true, k, Q, topk, scores, idx, true);
+}
+
+extern "C" int chip_query_batch_prefix_f32(chip_ctx *c, const int64_t *k, const float *queries, int32_t Q, int32_t topk, float *scores, int64_t *idx)
+{
+    return query_batch_prefix(c, nullptr, queries, false, k, Q, topk, scores, idx, false);
+}
+
+extern "C" int chip_query_batch_prefix_cast_f32(chip_ctx *c, const int64_t *k, const float *queries, int32_t Q, int32_t topk, float *scores, int64_t *idx)
+{
+    return query_batch_prefix(c, nullptr, queries, false, k, Q, topk, scores, idx, true);
+}
+
+extern "C" int chip_query_prefix_plan(const int64_t *k, int32_t Q, int32_t elem, int32_t topk, int32_t *order, chip_query_prefix_plan_out *out)
+{
+    if (!k || !out || Q < 1) return CHIP_ERR_INVALID_ARG;
+    if ((elem != 4 && elem != 8) || topk < 1 || topk > CHIP_MAX_TOPK) return CHIP_ERR_UNSUPPORTED;
+    for (int32_t j = 0; j < Q; j++)
+        if (k[j] < 0) return CHIP_ERR_RANGE;
+    std::vector<int32_t> ord;
+    const int orc = prefix_order(k, Q, ord);
+    if (orc != CHIP_OK) return orc;
+    prefix_plan(k, Q, elem, topk, ord.data(), out);
+    if (order) memcpy(order, ord.data(), sizeof(int32_t) * (size_t)Q);
+    return CHIP_OK;
+}
+
+extern "C" int chip_debug_query_prefix_last(chip_ctx *c, chip_query_prefix_last *out)
+{
+    if (!c || !out) return CHIP_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> qlk(c->query_mu);
+    *out = c->batch_state ? c->batch_state->prefix_last : chip_query_prefix_last{};
+    return CHIP_OK;
 }

@@ -407,6 +407,62 @@ int chip_query_batch_f32(chip_ctx *ctx, int64_t k, const float *queries, int32_t
 int chip_query_batch_cast_f32(chip_ctx *ctx, int64_t k, const float *queries, int32_t Q, int32_t topk,
                               float *scores /* Q x topk */, int64_t *idx /* Q x topk */);
 
+/* The same mode with a prefix PER QUERY, and with queries taken from DB rows (ABI 7, additive).  Bulk loop detection is causal: a node
+ * restarted from its state, a replay, a second session searched against a first, the reference's faiss__naive_loopcandidate_generator
+ * and faiss_clique_loopcandidate_generator (src/Cerebro.cpp:415-473, 558-650) all let query row i see rows [0, i - lag) only, and every
+ * query already sits in the DB on the device.
+ *   - chip_query_batch_rows_f32 (Cerebro.cpp:415-473): query j is DB row query_rows[j], gathered on the device, against rows [0, k[j]).
+ *   - chip_query_batch_rows_cast_f32 (Cerebro.cpp:415-473): the same on a double-row DB; DB rows AND query rows enter as (float)x, round to
+ *     nearest even (v_cvt_f32_f64 in both places).
+ *   - chip_query_batch_prefix_f32 / chip_query_batch_prefix_cast_f32 (Cerebro.cpp:415-473): query j is the host vector queries + j * D,
+ *     against rows [0, k[j]).
+ * Definition: entry j of the result is, bit for bit, what chip_query_batch_f32(ctx, k[j], q_j, 1, topk, ..) returns, q_j being the caller's
+ * vector or row query_rows[j] as floats (chip_query_batch_cast_f32 and (float)x on double rows).  Everything else is that mode's: one
+ * k-ordered fp32 fmaf chain, (score desc, index desc), unused slots -inf / -1, a NaN score never enters a list.  k[j] may exceed
+ * query_rows[j]: the row then meets itself.  Results come back in the caller's order.
+ * How a call runs: the queries are stable-sorted by k and walked in groups of at most CHIP_QUERY_PREFIX_GROUP; a group is one gather launch
+ * (or the upload and transpose of host vectors), one GEMM launch, one merge launch, one copy back and at most one host wait.  The GEMM
+ * walks, per query tile, only the DB tiles below the largest prefix of that tile, and clips each query's scan at its own prefix: a causal
+ * self-join costs about half the DB tiles of the rectangle.  A group picks the 256 x 256 or 128 x 128 tile as chip_query_batch_f32 does.
+ * Status, all checked before anything is launched or written: a NULL pointer or Q < 1 CHIP_ERR_INVALID_ARG; D % 32 != 0, topk outside
+ * [1, CHIP_MAX_TOPK], the _f32 entries on double rows, a chip_create_multi or sharded ctx CHIP_ERR_UNSUPPORTED (a query row of a sharded
+ * DB lives on one rank only: prefix calls on group and sharded contexts are not part of this interface yet); k[j] < 0, k[j] > the
+ * published length, or a query row outside [0, published length) CHIP_ERR_RANGE.
+ *   - chip_query_prefix_plan (Cerebro.cpp:415-473; no ctx, no device): the order and the work of a call, from the functions the call sizes
+ *     itself with.  elem: 4 float rows, 8 double rows.  order (Q entries, may be NULL): order[i] = the caller's position of the i-th
+ *     query walked.  units and units_rect count tiles of the shape their group has; a call whose groups differ in shape (a partial last
+ *     group on the 128 tile behind full groups on the 256 tile) sums tiles of two sizes, so units / units_rect is a measure of work
+ *     only where tile_full == tile_last (or there is one group).  A NULL k / out or Q < 1 CHIP_ERR_INVALID_ARG; a negative k[j] CHIP_ERR_RANGE; elem or topk CHIP_ERR_UNSUPPORTED.
+ *   - chip_debug_query_prefix_last (Cerebro.cpp:415-473): what the ctx's last prefix call did.  units_claimed is the sum, over groups and
+ *     query tiles, of the work counters the kernel itself advanced (read back after each launch), so it is the kernel that is shown to
+ *     skip the tiles; units_planned is the host's count, chip_query_prefix_plan's `units`.                                            */
+#define CHIP_QUERY_PREFIX_GROUP 4096   /* queries per group */
+typedef struct chip_query_prefix_plan_out {
+    int32_t group_size;    /* CHIP_QUERY_PREFIX_GROUP                                                                     */
+    int32_t groups;
+    int32_t tile_full;     /* rows of the (square) tile of a full group: 256 or 128; 0 when the call has no full group    */
+    int32_t tile_last;     /* of the last group                                                                           */
+    int64_t qtiles;        /* query tiles, all groups                                                                     */
+    int64_t units;         /* DB tiles walked: sum over query tiles of ceil(max k in the tile / tile rows)                */
+    int64_t units_rect;    /* the same query tiles at ONE k = max over the call: what chip_query_batch_f32 would walk     */
+} chip_query_prefix_plan_out;
+typedef struct chip_query_prefix_last {
+    int32_t groups, launches, waits, reserved;
+    int64_t units_claimed, units_planned;
+} chip_query_prefix_last;
+int chip_build_has_query_prefix(void);   /* 1 */
+int chip_query_batch_rows_f32(chip_ctx *ctx, const int64_t *query_rows, const int64_t *k, int32_t Q, int32_t topk,
+                              float *scores /* Q x topk */, int64_t *idx /* Q x topk */);
+int chip_query_batch_rows_cast_f32(chip_ctx *ctx, const int64_t *query_rows, const int64_t *k, int32_t Q, int32_t topk,
+                                   float *scores /* Q x topk */, int64_t *idx /* Q x topk */);
+int chip_query_batch_prefix_f32(chip_ctx *ctx, const int64_t *k, const float *queries, int32_t Q, int32_t topk,
+                                float *scores /* Q x topk */, int64_t *idx /* Q x topk */);
+int chip_query_batch_prefix_cast_f32(chip_ctx *ctx, const int64_t *k, const float *queries, int32_t Q, int32_t topk,
+                                     float *scores /* Q x topk */, int64_t *idx /* Q x topk */);
+int chip_query_prefix_plan(const int64_t *k, int32_t Q, int32_t elem, int32_t topk, int32_t *order /* Q, may be NULL */,
+                           chip_query_prefix_plan_out *out);
+int chip_debug_query_prefix_last(chip_ctx *ctx, chip_query_prefix_last *out);
+
 /* ------------------------------------------------------------------------------------------ the tick
  * One pass of the while-loop body of Cerebro::descrip_N__dot__descrip_0_N (src/Cerebro.cpp:956-1100) for
  * l = wholeImageComputedList_size().  Defaults (chip_dot_params_default): LOCALITY_THRESH 12 (:912),

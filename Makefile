@@ -20,7 +20,7 @@ ORC_SRCS   := $(wildcard oracle/*.c)
 all: lib oracle host testlibs verify ref ref_modes
 lib: $(LIBDIR)/libcerebro_hip.so
 oracle: oracle/_build/liboracle.so oracle/_build/liboracle_eispack.so oracle/_build/liboracle_stats.so oracle/_build/liboracle_flops.so
-host: $(LIBDIR)/libcerebro_host.so $(LIBDIR)/cerebro_replay $(LIBDIR)/minimal_loop_detector $(LIBDIR)/sync_tick_latency $(LIBDIR)/verify_candidate $(LIBDIR)/verify_candidates $(LIBDIR)/verify_candidates_stored $(LIBDIR)/verify_candidates_composed $(LIBDIR)/verify_candidates_modes $(LIBDIR)/verify_pairs_stored $(LIBDIR)/frame_put_disparity $(LIBDIR)/frame_put_stereo $(LIBDIR)/orb_detect $(LIBDIR)/orb_frame_put $(LIBDIR)/frame_put_raw_stereo $(LIBDIR)/frame_put_batch $(LIBDIR)/append_projected $(LIBDIR)/append_vlad $(LIBDIR)/append_batch $(LIBDIR)/self_join
+host: $(LIBDIR)/libcerebro_host.so $(LIBDIR)/cerebro_replay $(LIBDIR)/minimal_loop_detector $(LIBDIR)/sync_tick_latency $(LIBDIR)/verify_candidate $(LIBDIR)/verify_candidates $(LIBDIR)/verify_candidates_stored $(LIBDIR)/verify_candidates_composed $(LIBDIR)/verify_candidates_modes $(LIBDIR)/verify_pairs_stored $(LIBDIR)/frame_put_disparity $(LIBDIR)/frame_put_stereo $(LIBDIR)/orb_detect $(LIBDIR)/orb_frame_put $(LIBDIR)/frame_put_raw_stereo $(LIBDIR)/frame_put_batch $(LIBDIR)/append_projected $(LIBDIR)/append_vlad $(LIBDIR)/append_batch $(LIBDIR)/self_join $(LIBDIR)/bulk_ticks
 # test infrastructure that needs hipcc: the shared-memory stand-in for librccl (N ranks on one device, tests/test_fakerccl_gpu.py)
 testlibs: tests/fakerccl/_build/libfakerccl.so $(LIBDIR)/norows/libcerebro_hip.so $(LIBDIR)/hooks/libcerebro_hip.so
 # The TEST build of the library (-DCHIP_TEST_HOOKS): the fault-injection hooks (CHIP_TEST_COMM_INIT, CHIP_TEST_FAIL_SHARD,
@@ -172,6 +172,11 @@ $(LIBDIR)/append_batch: examples/append_batch.cc include/cerebro_hip.h $(LIBDIR)
 # ---- the causal self-join of a DB: ONE chip_query_batch_rows_f32 (a prefix per query, the queries gathered from DB rows on the device)
 # against the loop of chip_query_batch_f32 with Q = 1 on rows read back: same bits (and, with an argument, the time of both)
 $(LIBDIR)/self_join: examples/self_join.cc include/cerebro_hip.h $(LIBDIR)/libcerebro_hip.so
+	$(CXX) -O2 -std=c++17 -Wall -Wextra -Iinclude $< -o $@ -L$(LIBDIR) -lcerebro_hip -Wl,-rpath,'$$ORIGIN'
+
+# ---- the tick records of a whole schedule: ONE chip_loop_ticks_bulk (many-query groups, certificate, exact rescoring, the accept rule)
+# against the loop of chip_loop_tick and chip_query_rows: same bits in every field (and, with an argument, the time of both)
+$(LIBDIR)/bulk_ticks: examples/bulk_ticks.cc include/cerebro_hip.h $(LIBDIR)/libcerebro_hip.so
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -Iinclude $< -o $@ -L$(LIBDIR) -lcerebro_hip -Wl,-rpath,'$$ORIGIN'
 
 # ---- the reference's own GMS matcher as a compiled checker (test infrastructure: tests/gms_ref_lib.py, tests/test_gms_ref_mirror.py).

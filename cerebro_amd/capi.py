@@ -247,6 +247,10 @@ _SIGS = {
     "chip_query_batch_prefix_cast_f32": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
     "chip_query_prefix_plan": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "chip_debug_query_prefix_last": (C.c_int, [_P, _P]),
+    "chip_build_has_bulk_ticks": (C.c_int, []),
+    "chip_loop_ticks_bulk": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
+    "chip_bulk_ticks_plan": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int64, _P, _P, _P]),
+    "chip_debug_bulk_ticks_last": (C.c_int, [_P, _P]),
     "chip_dot_params_default": (None, [C.POINTER(DotParams)]),
     "chip_loop_tick": (C.c_int, [_P, C.c_int64, C.POINTER(DotParams), C.POINTER(TickResult)]),
     "chip_resident_pause": (C.c_int, [_P]),
@@ -562,6 +566,42 @@ def query_prefix_plan(k, elem: int = 4, topk: int = 5) -> dict:
         raise ChipError(rc, "chip_query_prefix_plan")
     d = {name: getattr(out, name) for name, _ in QueryPrefixPlan._fields_}
     d["order"] = order
+    return d
+
+
+CHIP_BULK_TICKS_GROUP, CHIP_BULK_TICKS_MAX_TOPK = 1365, 8
+
+
+class BulkTicksPlan(C.Structure):
+    """chip_bulk_ticks_plan_out"""
+    _fields_ = [("group_ticks", C.c_int32), ("groups", C.c_int32), ("tile_full", C.c_int32), ("tile_last", C.c_int32),
+                ("ticks_scanned", C.c_int64), ("ticks_skipped", C.c_int64), ("ticks_too_short", C.c_int64),
+                ("units", C.c_int64), ("units_rect", C.c_int64), ("last_l", C.c_int64)]
+
+
+class BulkTicksLast(C.Structure):
+    """chip_bulk_ticks_last"""
+    _fields_ = [("groups", C.c_int32), ("launches", C.c_int32), ("waits", C.c_int32), ("list_len", C.c_int32),
+                ("certified", C.c_int64), ("uncertified", C.c_int64), ("rescored_rows", C.c_int64),
+                ("exact_reruns", C.c_int64), ("E", C.c_double)]
+
+
+def bulk_ticks_plan(ls, n_rows: int, params: DotParams | None = None, last_l: int = 0) -> dict:
+    """chip_bulk_ticks_plan -> status (int32 [T]) and k (int64 [T], 0 where the tick is not scanned) of the ticks at ls run one after the
+    other from the loop state last_l on a DB of n_rows rows, and the grouping of a chip_loop_ticks_bulk call over them: group_ticks,
+    groups, tile_full, tile_last, ticks_scanned / _skipped / _too_short, units, units_rect, last_l.  Needs no ctx and no device."""
+    ls = np.ascontiguousarray(ls, dtype=np.int64).reshape(-1)
+    T = ls.shape[0]
+    status = np.empty(T, dtype=np.int32)
+    k = np.empty(T, dtype=np.int64)
+    out = BulkTicksPlan()
+    rc = load_library().chip_bulk_ticks_plan(_ptr(ls) if T else None, T, C.byref(params) if params is not None else None, last_l, n_rows,
+                                             _ptr(status), _ptr(k), C.byref(out))
+    if rc != CHIP_OK:
+        raise ChipError(rc, "chip_bulk_ticks_plan")
+    d = {name: getattr(out, name) for name, _ in BulkTicksPlan._fields_}
+    d["status"] = status
+    d["k"] = k
     return d
 
 
@@ -994,6 +1034,28 @@ class Chip:
         r = TickResult()
         self._chk(self.lib.chip_loop_tick(self.h, l, C.byref(p), C.byref(r)), "chip_loop_tick")
         return r
+
+    def loop_ticks_bulk(self, ls, params: DotParams | None = None, last_l: int = 0, topk: int = 1):
+        """chip_loop_ticks_bulk: the records of loop_tick(ls[0]), loop_tick(ls[1]), ... started from the loop state last_l, from many-query
+        passes -- the ctx's own loop state is neither read nor written.  Returns (records: list of TickResult, scores float64
+        [T, 3, topk], idx int64 [T, 3, topk], last_l after the last tick); the lists of a scanned tick are query_rows(l - lag,
+        [l-1, l-2, l-3], topk)'s, of every other tick -inf / -1."""
+        ls = np.ascontiguousarray(ls, dtype=np.int64).reshape(-1)
+        T = ls.shape[0]
+        recs = (TickResult * max(T, 1))()
+        sc = np.empty((T, 3, topk), dtype=np.float64)
+        ix = np.empty((T, 3, topk), dtype=np.int64)
+        last = C.c_int64(last_l)
+        self._chk(self.lib.chip_loop_ticks_bulk(self.h, _ptr(ls) if T else None, T, C.byref(params) if params is not None else None, last_l, topk,
+                                                C.byref(recs), _ptr(sc), _ptr(ix), C.byref(last)), "chip_loop_ticks_bulk")
+        return [recs[t] for t in range(T)], sc, ix, last.value
+
+    def debug_bulk_ticks_last(self) -> dict:
+        """chip_debug_bulk_ticks_last: groups, launches and host waits of the last bulk call, list_len (KL), its certified / uncertified
+        ticks, the rows its finishing launches scored exactly, the ticks it ran again through the exact scan, the error bound E"""
+        out = BulkTicksLast()
+        self._chk(self.lib.chip_debug_bulk_ticks_last(self.h, C.byref(out)), "chip_debug_bulk_ticks_last")
+        return {name: getattr(out, name) for name, _ in BulkTicksLast._fields_}
 
     def resident_pause(self):
         self._chk(self.lib.chip_resident_pause(self.h), "chip_resident_pause")

@@ -308,6 +308,12 @@ struct BatchState {
     DevBuf<uint32_t> prefix_done;
     PinnedBuf<uint32_t> h_prefix_done;
     chip_query_prefix_last prefix_last = {};
+    // chip_loop_ticks_bulk: a group's records, exact lists and words (one block, one copy back), the record of an exact rerun (pinned), what
+    // the last call did
+    DevBuf<char> bulk_out;
+    PinnedBuf<char> h_bulk_out;
+    PinnedBuf<chip_tick_result> bulk_rec;
+    chip_bulk_ticks_last bulk_last = {};
     hipEvent_t ev_done = nullptr;    // this shard's list is complete (recorded on its scan stream)
 };
 
@@ -483,11 +489,13 @@ static void prefix_plan(const int64_t *k, int32_t Q, int elem, int topk, const i
     }
 }
 
-// One group of a prefix call on the ctx's scan stream, to the caller's arrays: one gather launch (or memset + upload + transpose_queries
-// for host vectors), one GEMM launch, one merge launch, one copy back, one host wait.  Caller: arguments checked, query lock held, device
-// current, resident scan paused.  query_rows (or, where NULL, queries): the caller's rows or vectors, in the CALLER's order.
-static int prefix_group_run(Ctx *c, BatchState *st, const PrefixGroup &g, const int32_t *tile_limit, const int64_t *k, const int32_t *order,
-                            const int64_t *query_rows, const float *queries, int32_t topk, float *scores, int64_t *idx)
+// One group of a prefix call enqueued on the ctx's scan stream: one gather launch (or memset + upload + transpose_queries for host vectors),
+// one GEMM launch, one merge launch -- the group's sorted [Qpad][topk] lists are then in st->out on the device, its input image (int64
+// rows[Qpad] | int32 q_limit[Qpad] | int32 tile_limit[qtiles]) in st->prefix_in, the kernel's work counters in st->prefix_done.  No host
+// wait.  Caller: arguments checked, query lock held, device current, resident scan paused.  query_rows (or, where NULL, queries): the
+// caller's rows or vectors, in the CALLER's order.
+static int prefix_group_enqueue(Ctx *c, BatchState *st, const PrefixGroup &g, const int32_t *tile_limit, const int64_t *k, const int32_t *order,
+                                const int64_t *query_rows, const float *queries, int32_t topk)
 {
     const int D = c->D, Qpad = g.Qpad, TM = g.TM, TN = TM, qtiles = g.qtiles;
     const bool wide = TM == 256, from_rows = query_rows != nullptr;
@@ -582,6 +590,17 @@ static int prefix_group_run(Ctx *c, BatchState *st, const PrefixGroup &g, const 
     m.in = st->partial; m.n_lists = (int)P; m.Qpad = Qpad; m.K = topk; m.out = st->out;
     hipLaunchKernelGGL(topk_merge_batch, dim3((g.count + 3) / 4), dim3(512), 0, s, m);
     CHIP_HIP(c, hipGetLastError());
+    return CHIP_OK;
+}
+
+// The same group to the caller's arrays: prefix_group_enqueue, one copy back, one host wait.
+static int prefix_group_run(Ctx *c, BatchState *st, const PrefixGroup &g, const int32_t *tile_limit, const int64_t *k, const int32_t *order,
+                            const int64_t *query_rows, const float *queries, int32_t topk, float *scores, int64_t *idx)
+{
+    const int rc = prefix_group_enqueue(c, st, g, tile_limit, k, order, query_rows, queries, topk);
+    if (rc != CHIP_OK) return rc;
+    const int qtiles = g.qtiles;
+    hipStream_t s = c->s_scan;
     chip_topk_entry *const h_out = st->h_out.host();
     uint32_t *const h_done = st->h_prefix_done.host();
     CHIP_HIP(c, hipMemcpyAsync(h_out, st->out, sizeof(chip_topk_entry) * (size_t)g.count * topk, hipMemcpyDeviceToHost, s));
@@ -768,6 +787,268 @@ extern "C" int chip_query_batch_prefix_f32(chip_ctx *c, const int64_t *k, const 
 extern "C" int chip_query_batch_prefix_cast_f32(chip_ctx *c, const int64_t *k, const float *queries, int32_t Q, int32_t topk, float *scores, int64_t *idx)
 {
     return query_batch_prefix(c, nullptr, queries, false, k, Q, topk, scores, idx, true);
+}
+
+// ---- bulk ticks (header: "Bulk ticks"): a many-query group over the tick queries + bulk_tick_finish (kernels.hip) = the ticks' exact records
+// KL, the length of the fp32 lists the certificate works from: M is the KL-th score, up to KL rows per query are scored exactly.  Runs of
+// near-identical neighbouring keyframes put several rows within 2E of the best, so the longest list the GEMM keeps (profiles/bulk_ticks.md).
+#ifndef CHIP_BULK_LIST_LEN
+#define CHIP_BULK_LIST_LEN CHIP_MAX_TOPK   // (8 builds the other list length the GEMM has, for the comparison in the profile note)
+#endif
+constexpr int kBulkListLen = CHIP_BULK_LIST_LEN;
+static_assert(kBulkListLen == 8 || kBulkListLen == CHIP_MAX_TOPK, "the list lengths db_gemm_prefixed is built for");
+static_assert(3 * CHIP_BULK_TICKS_GROUP <= CHIP_QUERY_PREFIX_GROUP && CHIP_BULK_TICKS_MAX_TOPK <= kBulkListLen, "a tick's queries stay in one group");
+
+// The sequence rule: what chip_loop_tick, called for l[0], l[1], ... from the loop state last_l, would say of each tick (tick_prepare is the
+// tick's own function) and the loop state afterwards.  k[t] = 0 where the tick is not scanned.
+static int bulk_sequence(const int64_t *l, int32_t T, const chip_dot_params *p, int64_t last_l, int64_t n_rows, int32_t *status, int64_t *k, int64_t *last_l_out)
+{
+    for (int32_t t = 0; t < T; t++) {
+        int32_t s = 0;
+        int64_t kt = 0;
+        const int rc = tick_prepare(n_rows, last_l, l[t], p, &s, &kt);
+        if (rc != CHIP_OK) return rc;
+        // one refusal of the bulk call's own (header): a prefix that is no prefix of the DB -- a negative lag, or a min_k below -lag -- which the
+        // tick itself does not check; the many-query pass cannot walk it
+        if (s == CHIP_TICK_SCANNED && (kt < 0 || kt > n_rows)) return CHIP_ERR_RANGE;
+        status[t] = s;
+        k[t] = s == CHIP_TICK_SCANNED ? kt : 0;
+        if (s != CHIP_TICK_SKIPPED) last_l = l[t];   // :1098, and the else-branch of :1022
+    }
+    *last_l_out = last_l;
+    return CHIP_OK;
+}
+
+// The walk order: the scanned ticks stable-sorted by k ascending.
+static int bulk_order(const int32_t *status, const int64_t *k, int32_t T, std::vector<int32_t> &ticks)
+{
+    try {
+        for (int32_t t = 0; t < T; t++)
+            if (status[t] == CHIP_TICK_SCANNED) ticks.push_back(t);
+        std::stable_sort(ticks.begin(), ticks.end(), [k](int32_t x, int32_t y) { return k[x] < k[y]; });
+    } catch (const std::bad_alloc &) {
+        return CHIP_ERR_OOM;
+    }
+    return CHIP_OK;
+}
+
+// One group: ticks[0 .. nt) as 3 nt queries in walk order (query 3 i + j: row l - 1 - j against [0, k)), and its shape by prefix_group.
+struct BulkGroup {
+    std::vector<int64_t> rows, k;
+    std::vector<int32_t> ident;
+    PrefixGroup g;
+};
+static int bulk_group(const int64_t *l, const int64_t *k, const int32_t *ticks, int32_t nt, int32_t *tile_limit, BulkGroup *b)
+{
+    try {
+        b->rows.resize((size_t)3 * nt); b->k.resize((size_t)3 * nt); b->ident.resize((size_t)3 * nt);
+    } catch (const std::bad_alloc &) {
+        return CHIP_ERR_OOM;
+    }
+    for (int32_t i = 0; i < nt; i++)
+        for (int j = 0; j < 3; j++) {
+            b->rows[(size_t)3 * i + j] = l[ticks[i]] - 1 - j;
+            b->k[(size_t)3 * i + j] = k[ticks[i]];
+            b->ident[(size_t)3 * i + j] = 3 * i + j;
+        }
+    b->g = prefix_group(b->k.data(), b->ident.data(), 0, 3 * nt, 4, kBulkListLen, tile_limit);
+    return CHIP_OK;
+}
+
+// A group on the device: gather + db_gemm_prefixed + topk_merge_batch with lists of KL entries, bulk_tick_finish on them, ONE copy back of
+// records, exact lists and words, one host wait.  Ticks whose certificate does not hold are appended to `rerun`.
+static int bulk_group_run(Ctx *c, BatchState *st, const int64_t *l, const int64_t *k, const int32_t *ticks, int32_t nt, const chip_dot_params *p,
+                          int32_t topk, double E, chip_tick_result *out, double *scores, int64_t *idx, std::vector<int32_t> &rerun)
+{
+    int32_t tile_limit[CHIP_QUERY_PREFIX_GROUP / BM];
+    BulkGroup b;
+    int rc = bulk_group(l, k, ticks, nt, tile_limit, &b);
+    if (rc != CHIP_OK) return rc;
+    const size_t rec_bytes = sizeof(chip_tick_result) * (size_t)nt, list_bytes = sizeof(chip_topk_entry) * (size_t)nt * 3 * topk;
+    const size_t bytes = rec_bytes + list_bytes + sizeof(uint32_t) * 2 * (size_t)nt;
+    rc = st->bulk_out.reserve(c, bytes);
+    if (rc == CHIP_OK) rc = st->h_bulk_out.reserve(c, bytes);
+    if (rc == CHIP_OK) rc = prefix_group_enqueue(c, st, b.g, tile_limit, b.k.data(), b.ident.data(), b.rows.data(), nullptr, kBulkListLen);
+    if (rc != CHIP_OK) return rc;
+    hipStream_t s = c->s_scan;
+    char *const dev = st->bulk_out;
+    BulkFinishArgs a;
+    a.seg_table = reinterpret_cast<const void *const *>(c->seg_table_dev.get()); a.seg_shift = c->seg_shift; a.seg_mask = c->seg_rows - 1;
+    a.D = c->D; a.KL = kBulkListLen; a.K = topk;
+    a.lists = st->out; a.rows = reinterpret_cast<const int64_t *>(st->prefix_in.get());
+    a.E = E; a.locality = p->locality; a.thresh = p->thresh;
+    a.rec = reinterpret_cast<chip_tick_result *>(dev);
+    a.out = reinterpret_cast<chip_topk_entry *>(dev + rec_bytes);
+    a.words = reinterpret_cast<uint32_t *>(dev + rec_bytes + list_bytes);
+    rc = launch_bulk_finish(c, s, a, nt);
+    if (rc != CHIP_OK) return rc;
+    const char *const h = st->h_bulk_out.host();
+    CHIP_HIP(c, hipMemcpyAsync(st->h_bulk_out.host(), dev, bytes, hipMemcpyDeviceToHost, s));
+    CHIP_HIP(c, hipStreamSynchronize(s));
+    const chip_tick_result *const h_rec = reinterpret_cast<const chip_tick_result *>(h);
+    const chip_topk_entry *const h_list = reinterpret_cast<const chip_topk_entry *>(h + rec_bytes);
+    const uint32_t *const h_words = reinterpret_cast<const uint32_t *>(h + rec_bytes + list_bytes);
+    chip_bulk_ticks_last &last = st->bulk_last;
+    last.groups++; last.launches += 4; last.waits++;
+    for (int32_t i = 0; i < nt; i++) {
+        const int32_t t = ticks[i];
+        last.rescored_rows += h_words[2 * i + 1];
+        if (h_words[2 * i] != 1u) {
+            last.uncertified++;
+            try { rerun.push_back(t); } catch (const std::bad_alloc &) { return CHIP_ERR_OOM; }
+            continue;
+        }
+        last.certified++;
+        out[t] = h_rec[i];
+        for (int32_t j = 0; j < 3 * topk; j++) {
+            if (scores) scores[(size_t)t * 3 * topk + j] = h_list[(size_t)i * 3 * topk + j].score;
+            if (idx) idx[(size_t)t * 3 * topk + j] = h_list[(size_t)i * 3 * topk + j].idx;
+        }
+    }
+    return CHIP_OK;
+}
+
+// One tick alone through the exact path -- the scan over [0, k) with its three query rows, then the merge with the decision: what
+// chip_scan_local + chip_merge_decide run, without a slot and without the loop state.
+static int bulk_exact_tick(Ctx *c, BatchState *st, int64_t l, int64_t k, const chip_dot_params *p, int32_t topk, chip_tick_result *out, double *scores, int64_t *idx)
+{
+    const int64_t rows[3] = {l - 1, l - 2, l - 3};
+    const void *q[3];
+    RingGuard rg(c);
+    int rc = query_row_ptrs(c, rows, 3, l, q);
+    if (rc != CHIP_OK) return rc;
+    ScanRequest rq;
+    rq.k = k; rq.q = q; rq.nq = 3; rq.K = topk; rq.out = c->topk.dev(); rq.res = st->bulk_rec.dev(); rq.l = l; rq.p = p;
+    rc = enqueue_scan_merge(c, rq);
+    if (rc != CHIP_OK) return rc;
+    rc = sync_topk_out(c, 3, topk, scores, idx);   // (waits for the merge: the record is in pinned memory by then)
+    if (rc != CHIP_OK) return rc;
+    *out = *st->bulk_rec.host();
+    return CHIP_OK;
+}
+
+extern "C" int chip_build_has_bulk_ticks(void) { return 1; }
+
+extern "C" int chip_loop_ticks_bulk(chip_ctx *c, const int64_t *l, int32_t T, const chip_dot_params *p, int64_t last_l, int32_t topk, chip_tick_result *out,
+                                    double *scores, int64_t *idx, int64_t *last_l_out)
+{
+    if (!c || !l || !out || T < 1) return CHIP_ERR_INVALID_ARG;
+    if (topk < 1 || topk > CHIP_BULK_TICKS_MAX_TOPK || c->D % 32 != 0 || c->elem != 4) return CHIP_ERR_UNSUPPORTED;
+    if (c->group || c->parent || c->nranks != 1 || c->xchg) return CHIP_ERR_UNSUPPORTED;
+    chip_dot_params dflt;
+    if (!p) { chip_dot_params_default(&dflt); p = &dflt; }
+    int64_t n_global;
+    double nrm;
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        n_global = c->rows_global;
+        nrm = c->row_norm_max;
+    }
+    if (n_global > INT32_MAX || c->seg_rows % 256 != 0) return CHIP_ERR_UNSUPPORTED;   // as query_batch_prefix
+    std::vector<int32_t> status, ticks, rerun;
+    std::vector<int64_t> k;
+    try {
+        status.resize((size_t)T); k.resize((size_t)T);
+    } catch (const std::bad_alloc &) {
+        return CHIP_ERR_OOM;
+    }
+    int64_t last_after = last_l;
+    int rc = bulk_sequence(l, T, p, last_l, n_global, status.data(), k.data(), &last_after);
+    if (rc == CHIP_OK) rc = bulk_order(status.data(), k.data(), T, ticks);
+    if (rc != CHIP_OK) return rc;
+    std::lock_guard<std::mutex> qlk(c->query_mu);
+    (void)coalesce_flush(c);
+    CHIP_HIP(c, hipSetDevice(c->device));
+    if (!c->batch_state) {
+        c->batch_state = new (std::nothrow) BatchState();
+        if (!c->batch_state) return CHIP_ERR_OOM;
+    }
+    BatchState *st = c->batch_state;
+    ResidentPause paused(c);   // as query_batch_prefix
+    rc = st->bulk_rec.reserve(c, 1);
+    if (rc != CHIP_OK) return rc;
+    // no fp32 partial sum overflows (scan_prefilter_usable's condition; false for NaN as well) -- else every tick takes the exact path
+    const bool norm_ok = nrm * nrm <= std::ldexp(1.0, 120) && 2.0 * c->D * std::ldexp(1.0, -24) < 0.5;
+    const double E = norm_ok ? prefilter_error_bound(c->D, nrm) : 0.0;
+    st->bulk_last = chip_bulk_ticks_last{};
+    st->bulk_last.list_len = kBulkListLen;
+    st->bulk_last.E = E;
+    for (int32_t t = 0; t < T; t++) {
+        fill_immediate(out + t, status[(size_t)t]);
+        for (int32_t j = 0; j < 3 * topk; j++) {
+            if (scores) scores[(size_t)t * 3 * topk + j] = -INFINITY;
+            if (idx) idx[(size_t)t * 3 * topk + j] = -1;
+        }
+    }
+    const int32_t n_scan = (int32_t)ticks.size();
+    if (norm_ok) {
+        for (int32_t first = 0; first < n_scan; first += CHIP_BULK_TICKS_GROUP) {
+            const int32_t nt = n_scan - first < CHIP_BULK_TICKS_GROUP ? n_scan - first : CHIP_BULK_TICKS_GROUP;
+            rc = bulk_group_run(c, st, l, k.data(), ticks.data() + first, nt, p, topk, E, out, scores, idx, rerun);
+            if (rc != CHIP_OK) return rc;
+        }
+    } else {
+        rerun.swap(ticks);
+    }
+    for (const int32_t t : rerun) {
+        const size_t at = (size_t)t * 3 * topk;
+        rc = bulk_exact_tick(c, st, l[t], k[(size_t)t], p, topk, out + t, scores ? scores + at : nullptr, idx ? idx + at : nullptr);
+        if (rc != CHIP_OK) return rc;
+        st->bulk_last.exact_reruns++;
+    }
+    if (last_l_out) *last_l_out = last_after;
+    return CHIP_OK;
+}
+
+extern "C" int chip_bulk_ticks_plan(const int64_t *l, int32_t T, const chip_dot_params *p, int64_t last_l, int64_t n_rows, int32_t *status, int64_t *k,
+                                    chip_bulk_ticks_plan_out *out)
+{
+    if (!l || !status || !k || !out || T < 1 || n_rows < 0) return CHIP_ERR_INVALID_ARG;
+    chip_dot_params dflt;
+    if (!p) { chip_dot_params_default(&dflt); p = &dflt; }
+    chip_bulk_ticks_plan_out f = {};
+    f.group_ticks = CHIP_BULK_TICKS_GROUP;
+    std::vector<int32_t> st, ticks;
+    std::vector<int64_t> kk;
+    try {
+        st.resize((size_t)T); kk.resize((size_t)T);
+    } catch (const std::bad_alloc &) {
+        return CHIP_ERR_OOM;
+    }
+    int rc = bulk_sequence(l, T, p, last_l, n_rows, st.data(), kk.data(), &f.last_l);
+    if (rc == CHIP_OK) rc = bulk_order(st.data(), kk.data(), T, ticks);
+    if (rc != CHIP_OK) return rc;
+    for (int32_t t = 0; t < T; t++) {
+        if (st[(size_t)t] == CHIP_TICK_SKIPPED) f.ticks_skipped++;
+        else if (st[(size_t)t] == CHIP_TICK_TOO_SHORT) f.ticks_too_short++;
+    }
+    const int32_t n_scan = (int32_t)ticks.size();
+    f.ticks_scanned = n_scan;
+    const int64_t kmax = n_scan ? kk[(size_t)ticks[(size_t)n_scan - 1]] : 0;
+    for (int32_t first = 0; first < n_scan; first += CHIP_BULK_TICKS_GROUP) {
+        const int32_t nt = n_scan - first < CHIP_BULK_TICKS_GROUP ? n_scan - first : CHIP_BULK_TICKS_GROUP;
+        BulkGroup b;
+        rc = bulk_group(l, kk.data(), ticks.data() + first, nt, nullptr, &b);
+        if (rc != CHIP_OK) return rc;
+        f.groups++;
+        if (nt == CHIP_BULK_TICKS_GROUP) f.tile_full = b.g.TM;
+        f.tile_last = b.g.TM;
+        f.units += b.g.units;
+        f.units_rect += b.g.qtiles * ((kmax + b.g.TM - 1) / b.g.TM);
+    }
+    memcpy(status, st.data(), sizeof(int32_t) * (size_t)T);
+    memcpy(k, kk.data(), sizeof(int64_t) * (size_t)T);
+    *out = f;
+    return CHIP_OK;
+}
+
+extern "C" int chip_debug_bulk_ticks_last(chip_ctx *c, chip_bulk_ticks_last *out)
+{
+    if (!c || !out) return CHIP_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> qlk(c->query_mu);
+    *out = c->batch_state ? c->batch_state->bulk_last : chip_bulk_ticks_last{};
+    out->list_len = kBulkListLen;   // (a property of the build: said before the first call as well)
+    return CHIP_OK;
 }
 
 extern "C" int chip_query_prefix_plan(const int64_t *k, int32_t Q, int32_t elem, int32_t topk, int32_t *order, chip_query_prefix_plan_out *out)

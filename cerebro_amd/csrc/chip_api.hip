@@ -523,7 +523,7 @@ int upload_query_vectors(Ctx *c, const void *queries, int src_elem, int nq, cons
 // Host part of the tick (Cerebro.cpp:960-966, :1019-1022).  Returns CHIP_TICK_* in *status.  last_l is NOT written here:
 // the caller commits it once the tick has actually been enqueued (or at once for TOO_SHORT), so a failed enqueue leaves the
 // state as the reference's loop would (it only reaches :1098 at the end of an executed pass).
-static int tick_prepare(int64_t n, int64_t last_l, int64_t l, const chip_dot_params *p, int32_t *status, int64_t *k_out)
+int tick_prepare(int64_t n, int64_t last_l, int64_t l, const chip_dot_params *p, int32_t *status, int64_t *k_out)
 {
     if (l < 0 || l > n) return CHIP_ERR_RANGE;
     if (l - last_l < p->min_new) { *status = CHIP_TICK_SKIPPED; return CHIP_OK; }  // :962-966, last_l untouched
@@ -534,7 +534,7 @@ static int tick_prepare(int64_t n, int64_t last_l, int64_t l, const chip_dot_par
     return CHIP_OK;
 }
 
-static void fill_immediate(chip_tick_result *r, int32_t status)
+void fill_immediate(chip_tick_result *r, int32_t status)
 {
     std::memset(r, 0, sizeof *r);
     r->status = status;

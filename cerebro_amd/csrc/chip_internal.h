@@ -133,6 +133,24 @@ struct MergeArgs {
     double thresh;
 };
 
+// bulk ticks (batch.hip chip_loop_ticks_bulk): one launch of bulk_tick_finish (kernels.hip) per group, workgroup t finishes tick t
+struct BulkFinishArgs {
+    const void *const *seg_table;
+    int32_t seg_shift;
+    int64_t seg_mask;
+    int32_t D;
+    int32_t KL;                     // entries per list of the group (the library's own choice, <= CHIP_MAX_TOPK)
+    int32_t K;                      // the caller's topk <= KL
+    const chip_topk_entry *lists;   // [group queries][KL]: what topk_merge_batch left; query 3 t + i is row l_t - 1 - i
+    const int64_t *rows;            // [group queries] the query rows (the gather's image of them)
+    double E;                       // as RescoreArgs
+    int32_t locality;
+    double thresh;
+    chip_tick_result *rec;          // [ticks]
+    chip_topk_entry *out;           // [ticks][3][K] exact lists
+    uint32_t *words;                // [ticks][2]: 1 certified (all three queries) / 2 not, rows scored exactly
+};
+
 struct Ctx;
 
 // ---- owned memory: an array of T in device memory (DevBuf) or in pinned, device-mapped host memory (PinnedBuf).  Freed by the destructor.
@@ -247,6 +265,7 @@ double halfq_error_bound(int D, double row_norm_max, int e);   // E_h of DESIGN.
 int launch_scan_halfq(Ctx *c, hipStream_t s, const PassArgs &a, int grid);   // (a.q_up, a.s_down, a.s_up set from halfq_exponent)
 int launch_rescore(Ctx *c, hipStream_t s, const RescoreArgs &a, int n_ticks);
 int launch_pass_merge(Ctx *c, hipStream_t s, const PassMergeArgs &a, int n_ticks);
+int launch_bulk_finish(Ctx *c, hipStream_t s, const BulkFinishArgs &a, int n_ticks);
 int scan_grid_for(const Ctx *c, int64_t n_rows, int nq, bool q64);
 bool scan_q64(const Ctx *c, int nq, bool long_scan);
 int scan_rows_form(const Ctx *c, int64_t n_rows, int nq, int grid, bool q64, bool sync_tick = false);
@@ -553,6 +572,10 @@ int merge_enqueue_out(Ctx *c, const void *dev_gathered, int32_t n_lists, int nq,
 // The head of every tick: busy check, the reference's bookkeeping against n_rows published rows, what a CHIP_TICK_FAILED rolls back, and for
 // SKIPPED / TOO_SHORT the immediate result with its last_l commit.  CHIP_TICK_SCANNED: the caller enqueues the scan over [0, *k) and commits *last_l.
 int tick_begin(Slot &s, int64_t n_rows, int64_t *last_l, int64_t l, const chip_dot_params *p, int32_t *status, int64_t *k);
+// The rule alone (Cerebro.cpp:960-966, :1019-1022): status and k of a tick at l against n published rows and the loop state last_l, which it does
+// not write.  tick_begin and the bulk call (batch.hip bulk_sequence) both come here.  fill_immediate: the record of a tick that is not scanned.
+int tick_prepare(int64_t n, int64_t last_l, int64_t l, const chip_dot_params *p, int32_t *status, int64_t *k_out);
+void fill_immediate(chip_tick_result *r, int32_t status);
 int tick_collect_slot(Ctx *c, Slot &s, chip_tick_result *out);
 // Parking policy of the pipelined tick (no device needed): what an enqueue does with a tick that could share a pass, given the ticks
 // already parked, the most one pass may serve and whether a scan of this ctx is still running.

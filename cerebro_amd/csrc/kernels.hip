@@ -1013,6 +1013,84 @@ __global__ __launch_bounds__(512) void tick_rescore(RescoreArgs a)
     }
 }
 
+// ------------------------------------------------------------------------------------------------ bulk ticks: exact records from a many-query group
+// bulk_tick_finish: ONE launch per group of chip_loop_ticks_bulk (batch.hip), one workgroup of four waves per tick, behind the group's
+// topk_merge_batch.  Query 3 t + i of the group is row l_t - 1 - i against rows [0, k_t); its sorted list of KL fp32 fmaf-chain scores is read
+// in place.  Per query (wave i, lane = list slot):  G = the topk-th score (-inf where that slot is unused),  M = the KL-th score if that
+// slot is used (else the GEMM dropped nothing),  thr = G - 2E lowered as tick_rescore lowers it,  R = the entries with score >= thr -- a
+// prefix of the list, at most KL rows.  Certificate: nothing dropped, or M < thr.  The rows of R are scored one wave per row
+// by rows_dot + butterfly_sum -- the bits of every other scan kernel -- with the query row read in place, ranked by key_gt, and the
+// topk best written; thread 0 then writes the tick's record with tick_decision.  A workgroup reads its own tick's lists and rows only.
+template <bool FULL>
+__global__ __launch_bounds__(256) void bulk_tick_finish(BulkFinishArgs a)
+{
+    __shared__ chip_topk_entry cand[3][CHIP_MAX_TOPK];
+    __shared__ chip_topk_entry tops[3];
+    __shared__ int n_cand[3], cert[3];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tick = blockIdx.x, KL = a.KL, K = a.K;
+    if (wave < 3) {
+        const int q = wave;
+        chip_topk_entry e;
+        e.score = -INFINITY; e.idx = -1;
+        if (lane < KL) e = a.lists[((int64_t)3 * tick + q) * KL + lane];
+        const double gs = readlane_f64(e.score, K - 1);                 // (an unused slot carries -inf)
+        const double ms = readlane_f64(e.score, KL - 1);
+        const bool dropped = readlane_i64(e.idx, KL - 1) >= 0;
+        double thr = gs - 2.0 * a.E;
+        thr -= fabs(thr) * 0x1p-51;   // as tick_rescore: R can only grow, the certificate can only fail
+        const bool in_r = e.idx >= 0 && e.score >= thr;
+        const unsigned long long mask = __ballot(in_r);
+        if (in_r) cand[q][__popcll(mask & ((1ull << lane) - 1ull))] = e;
+        if (lane == 0) { n_cand[q] = __popcll(mask); cert[q] = !dropped || ms < thr ? 1 : 0; }
+    }
+    __syncthreads();
+    for (int j = wave; j < 3 * KL; j += 4) {   // exact scores: one wave per row of R
+        const int q = j / KL, i = j - q * KL;
+        if (i >= n_cand[q]) continue;
+        const int64_t r = cand[q][i].idx, qr = a.rows[(int64_t)3 * tick + q];
+        const float *row[1] = {static_cast<const float *>(a.seg_table[r >> a.seg_shift]) + (r & a.seg_mask) * (int64_t)a.D};
+        const float *qrow = static_cast<const float *>(a.seg_table[qr >> a.seg_shift]) + (qr & a.seg_mask) * (int64_t)a.D;
+        double acc[1][1];
+        rows_dot<float, 1, 4, FULL, 1, 1>(row, qrow, a.D, lane, acc);
+        const double s = butterfly_sum(acc[0][0]);
+        if (lane == 0) cand[q][i].score = s;
+    }
+    __syncthreads();
+    if (wave < 3) {
+        const int q = wave, nc = n_cand[q];
+        chip_topk_entry *out = a.out + ((int64_t)3 * tick + q) * K;
+        chip_topk_entry me;
+        me.score = -INFINITY; me.idx = -1;
+        if (lane < nc) me = cand[q][lane];
+        int rank = 0;
+        for (int j = 0; j < nc; j++) {
+            const chip_topk_entry o = cand[q][j];
+            rank += key_gt(o.score, o.idx, me.score, me.idx) ? 1 : 0;
+        }
+        if (lane < nc && rank < K) out[rank] = me;
+        if (lane >= nc && lane < K) out[lane] = me;   // fewer rows than topk: the list ends in empty entries
+        if (lane < nc && rank == 0) tops[q] = me;
+        if (lane == 0 && nc == 0) tops[q] = me;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        a.rec[tick] = tick_decision<3>(tops, false, a.rows[(int64_t)3 * tick] + 1, a.locality, a.thresh);
+        a.words[2 * tick] = cert[0] && cert[1] && cert[2] ? 1u : 2u;
+        a.words[2 * tick + 1] = (uint32_t)(n_cand[0] + n_cand[1] + n_cand[2]);
+    }
+}
+
+int launch_bulk_finish(Ctx *c, hipStream_t s, const BulkFinishArgs &a, int n_ticks)
+{
+    if (n_ticks < 1 || a.KL < 1 || a.KL > CHIP_MAX_TOPK || a.K < 1 || a.K > a.KL || a.D % 4 != 0) return CHIP_ERR_UNSUPPORTED;
+    if (a.D % 1024 == 0) hipLaunchKernelGGL(bulk_tick_finish<true>, dim3(n_ticks), dim3(256), 0, s, a);    // whole 4 KiB batches
+    else hipLaunchKernelGGL(bulk_tick_finish<false>, dim3(n_ticks), dim3(256), 0, s, a);
+    CHIP_HIP(c, hipGetLastError());
+    return CHIP_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ K1, wide double rows
 // Double rows whose NQ query descriptors do not fit the 160 KiB of LDS (the reference's default D = 8192, src/Cerebro.cpp:1021, as a
 // MatrixXd of genuine float64 values: 3 x 8192 x 8 B = 192 KiB).  The first NQ - NG queries are staged as usual; the last NG are read

@@ -99,6 +99,37 @@ __device__ __forceinline__ void wave_rank2(const double s[2], const int64_t i[2]
     }
 }
 
+// The record of a tick from the best entry of each of its NQ queries (tops[q]; (-inf, -1) where a query has none): the accept rule of
+// Cerebro.cpp:1056.  The ONE statement of it on the device: merge_sorted_lists and bulk_tick_finish (kernels.hip) both come here.
+template <int NQ>
+__device__ __forceinline__ chip_tick_result tick_decision(const chip_topk_entry *tops, bool failed, int64_t l, int locality, double thresh)
+{
+    chip_tick_result res;
+    res.status = failed ? CHIP_TICK_FAILED : CHIP_TICK_SCANNED;
+    res.found = 0;
+    res.idx_curr = -1;
+    res.idx_prev = -1;
+    res.score = 0.0;
+    for (int q = 0; q < 3; q++) {
+        res.argmax[q] = q < NQ ? tops[q].idx : -1;
+        res.maxv[q] = q < NQ ? tops[q].score : -INFINITY;
+    }
+    if (NQ >= 3 && res.argmax[0] >= 0 && res.argmax[1] >= 0 && res.argmax[2] >= 0) {
+        // Cerebro.cpp:1056  abs(u_argmax-um_argmax) < LOCALITY && abs(u_argmax-umm_argmax) < LOCALITY && u_max > THRESH
+        int64_t d1 = res.argmax[0] - res.argmax[1];
+        int64_t d2 = res.argmax[0] - res.argmax[2];
+        if (d1 < 0) d1 = -d1;
+        if (d2 < 0) d2 = -d2;
+        if (d1 < locality && d2 < locality && res.maxv[0] > thresh) {
+            res.found = 1;
+            res.idx_curr = l - 1;  // Cerebro.cpp:1080
+            res.idx_prev = res.argmax[0];
+            res.score = res.maxv[0];
+        }
+    }
+    return res;
+}
+
 template <int NQ>
 __device__ __forceinline__ void merge_sorted_lists(const chip_topk_entry *in, int n_lists, int list_stride, int q_off, int K, chip_topk_entry *out,
                                                    chip_tick_result *result, int64_t l, int locality, double thresh, char *smem)
@@ -215,32 +246,7 @@ __device__ __forceinline__ void merge_sorted_lists(const chip_topk_entry *in, in
     }
     __syncthreads();
     if (out != nullptr && t == 0 && *failed) out[0].idx = kFailedShardIdx;
-    if (result != nullptr && t == 0) {
-        chip_tick_result res;
-        res.status = *failed ? CHIP_TICK_FAILED : CHIP_TICK_SCANNED;
-        res.found = 0;
-        res.idx_curr = -1;
-        res.idx_prev = -1;
-        res.score = 0.0;
-        for (int q = 0; q < 3; q++) {
-            res.argmax[q] = q < NQ ? tops[q].idx : -1;
-            res.maxv[q] = q < NQ ? tops[q].score : -INFINITY;
-        }
-        if (NQ >= 3 && res.argmax[0] >= 0 && res.argmax[1] >= 0 && res.argmax[2] >= 0) {
-            // Cerebro.cpp:1056  abs(u_argmax-um_argmax) < LOCALITY && abs(u_argmax-umm_argmax) < LOCALITY && u_max > THRESH
-            int64_t d1 = res.argmax[0] - res.argmax[1];
-            int64_t d2 = res.argmax[0] - res.argmax[2];
-            if (d1 < 0) d1 = -d1;
-            if (d2 < 0) d2 = -d2;
-            if (d1 < locality && d2 < locality && res.maxv[0] > thresh) {
-                res.found = 1;
-                res.idx_curr = l - 1;  // Cerebro.cpp:1080
-                res.idx_prev = res.argmax[0];
-                res.score = res.maxv[0];
-            }
-        }
-        *result = res;
-    }
+    if (result != nullptr && t == 0) *result = tick_decision<NQ>(tops, *failed != 0, l, locality, thresh);
 }
 
 

@@ -181,12 +181,34 @@ bool Cerebro::descrip_N__dot__descrip_0_N_once(int64_t l, chip_tick_result *deta
     chip_tick_result r;
     status_ = chip_loop_tick(ctx_, l, &params, &r);  // :962-1056 (skip rule, k = l-50, scan, argmax, accept rule)
     if (detail) *detail = r;
-    if (status_ != CHIP_OK || !r.found) return false;
+    if (status_ != CHIP_OK) return false;
+    return push_found(r);
+}
+
+// what a tick's record does to foundLoops (:1078-1081): the one path of the tick and of the bulk call
+bool Cerebro::push_found(const chip_tick_result &r)
+{
+    if (!r.found) return false;
     const Time t_curr = wholeImageComputedList_at((int)r.idx_curr);   // wholeImageComputedList_at(l-1)
     const Time t_prev = wholeImageComputedList_at((int)r.idx_prev);   // wholeImageComputedList_at(u_argmax)
     std::lock_guard<std::mutex> lk(m_foundLoops);                     // :1078-1081
     foundLoops.push_back(std::make_tuple(t_curr, t_prev, r.score));
     return true;
+}
+
+int64_t Cerebro::descrip_N__dot__descrip_0_N_bulk(int64_t l_first, int64_t l_last, int64_t step)
+{
+    if (!ctx_ || step < 1 || l_last < l_first) { status_ = CHIP_ERR_INVALID_ARG; return -1; }
+    std::vector<int64_t> l;
+    for (int64_t x = l_first; x <= l_last; x += step) l.push_back(x);
+    if (l.size() > (size_t)INT32_MAX) { status_ = CHIP_ERR_UNSUPPORTED; return -1; }
+    std::vector<chip_tick_result> rec(l.size());
+    const int64_t last_l = chip_loop_last_l(ctx_);   // the loop of ticks would start from the ctx's state
+    status_ = chip_loop_ticks_bulk(ctx_, l.data(), (int32_t)l.size(), &params, last_l, 1, rec.data(), nullptr, nullptr, nullptr);
+    if (status_ != CHIP_OK) return -1;
+    int64_t pushed = 0;
+    for (const chip_tick_result &r : rec) pushed += push_found(r) ? 1 : 0;
+    return pushed;
 }
 
 // index.search(1, X_raw, 5, distances, labels) for n_rows query rows against the index prefix [0, ntotal)

@@ -105,6 +105,11 @@ public:
     // l = wholeImageComputedList_size() (or an explicit l when replaying a recorded schedule).  Returns true iff a
     // loop candidate was pushed to foundLoops.
     bool descrip_N__dot__descrip_0_N_once(int64_t l = -1, chip_tick_result *detail = nullptr);
+    // The iterations for l = l_first, l_first + step, ... <= l_last in ONE chip_loop_ticks_bulk (rows that are all there already: a cold
+    // start, a replay): the records of that loop of _once calls, started from the ctx's loop state, pushed to foundLoops in order through
+    // the same path -- foundLoops_as_JSON is the loop's.  The ctx's own loop state is NOT advanced (the call is pure).  Returns the
+    // number of candidates pushed, -1 on failure (last_status(); a multi-device ctx is CHIP_ERR_UNSUPPORTED).
+    int64_t descrip_N__dot__descrip_0_N_bulk(int64_t l_first, int64_t l_last, int64_t step = 3);
     // The thread main (Cerebro.cpp:350-357): polls at `rate_hz` until run_thread_disable().
     void run(double rate_hz = 10.0);
     void run_thread_enable() { b_run_thread = true; }
@@ -141,6 +146,7 @@ private:
     mutable std::mutex m_wholeImageComputedList;
     std::vector<Time> wholeImageComputedList;
     mutable std::mutex m_foundLoops;
+    bool push_found(const chip_tick_result &r);   // a record -> foundLoops (:1078-1081)
     std::vector<std::tuple<Time, Time, double>> foundLoops;
     mutable std::mutex m_data_map;
     mutable std::vector<uint64_t> data_map_;          // all frame stamps (sec << 32 | nsec); sorted lazily

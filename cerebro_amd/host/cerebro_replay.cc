@@ -20,6 +20,8 @@
 
 // --parse-only <state.json> <out.bin>  : no GPU; dumps {u32 D, u64 n, n x u64 stampNSec, n*D x f64} (parser check)
 // --state <state.json> <out.json> [device] : cold start from a checkpoint, then tick every 3 rows from l = 56
+// --bulk --state <state.json> <out.json> [device] : the same ticks in ONE chip_loop_ticks_bulk (Cerebro::descrip_N__dot__descrip_0_N_bulk):
+//                                                    the same file, byte for byte (single device only)
 static int parse_only(const char *in, const char *outp)
 {
     cerebro_hip::StateDescriptors sd;
@@ -40,6 +42,7 @@ static int parse_only(const char *in, const char *outp)
 // --devices a,b,c (first option): run the loop detector over several GPUs of this node from this one process
 // (chip_create_multi; a device named twice = the device-copy exchange, e.g. --devices 0,0,0,0 on a 1-GPU machine).
 static std::vector<int> g_devices;
+static bool g_bulk = false;   // --bulk: the cold start's ticks in one bulk call
 
 static cerebro_hip::Cerebro *make_cerebro(int D, int device, int64_t hint)
 {
@@ -55,9 +58,13 @@ static int from_state(const char *in, const char *outp, int device)
     if (!cer.ok()) { std::fprintf(stderr, "chip_create failed: %s\n", chip_strerror(cer.last_status())); return 3; }
     const int64_t n = cer.loadStateFromDisk(in);
     if (n < 0) { std::fprintf(stderr, "loadStateFromDisk: %s\n", cer.last_error().c_str()); return 4; }
-    for (int64_t l = 56; l <= n; l += 3) {   // SURVEY 8d replay schedule: l advances by 3 from the first productive tick
-        cer.descrip_N__dot__descrip_0_N_once(l);
-        if (cer.last_status() != CHIP_OK) { std::fprintf(stderr, "tick failed: %s\n", chip_strerror(cer.last_status())); return 5; }
+    if (g_bulk) {                            // the schedule below in one call
+        if (n >= 56 && cer.descrip_N__dot__descrip_0_N_bulk(56, n, 3) < 0) { std::fprintf(stderr, "bulk ticks failed: %s\n", chip_strerror(cer.last_status())); return 5; }
+    } else {
+        for (int64_t l = 56; l <= n; l += 3) {   // SURVEY 8d replay schedule: l advances by 3 from the first productive tick
+            cer.descrip_N__dot__descrip_0_N_once(l);
+            if (cer.last_status() != CHIP_OK) { std::fprintf(stderr, "tick failed: %s\n", chip_strerror(cer.last_status())); return 5; }
+        }
     }
     FILE *o = std::fopen(outp, "w");
     if (!o) { std::perror(outp); return 2; }
@@ -271,6 +278,11 @@ int main(int argc, char **argv)
         argv += 2;
         argc -= 2;
     }
+    if (argc >= 2 && std::strcmp(argv[1], "--bulk") == 0) {
+        g_bulk = true;
+        argv += 1;
+        argc -= 1;
+    }
     int policy = 0;
     if (argc >= 5 && std::strcmp(argv[1], "--policy") == 0) {
         policy = std::strcmp(argv[2], "naive") == 0 ? 1 : std::strcmp(argv[2], "clique") == 0 ? 2 : -1;
@@ -284,7 +296,7 @@ int main(int argc, char **argv)
     if (argc >= 3 && std::strcmp(argv[1], "--threeway") == 0) return threeway(argv[2], argc > 3 ? std::atoi(argv[3]) : 0);
     if (argc >= 4 && std::strcmp(argv[1], "--parse-only") == 0) return parse_only(argv[2], argv[3]);
     if (argc >= 4 && std::strcmp(argv[1], "--state") == 0) return from_state(argv[2], argv[3], argc > 4 ? std::atoi(argv[4]) : 0);
-    if (argc < 3) { std::fprintf(stderr, "usage: %s [--policy naive|clique] <stream.bin> <out.json> [device] | --state <state.json> <out.json> [device] | --parse-only <state.json> <out.bin>\n", argv[0]); return 2; }
+    if (argc < 3) { std::fprintf(stderr, "usage: %s [--policy naive|clique] <stream.bin> <out.json> [device] | [--bulk] --state <state.json> <out.json> [device] | --parse-only <state.json> <out.bin>\n", argv[0]); return 2; }
     FILE *f = std::fopen(argv[1], "rb");
     if (!f) { std::perror(argv[1]); return 2; }
     char magic[4];

@@ -528,7 +528,7 @@ int chip_resident_resume(chip_ctx *ctx);
  * (chip_set_stream) never park.  Nothing stays parked while its caller cannot release it.  Parked ticks are submitted by:
  *   chip_loop_tick_enqueue of the T-th tick, or of any tick that does not park;   chip_loop_tick_collect of a parked slot, and a
  *   collect that is about to block on the newest pass submitted;   chip_loop_tick;   chip_query_rows / _vectors_* / _scores;
- *   chip_scan_local, chip_merge_decide[_enqueue];   chip_synchronize, chip_destroy, chip_set_stream / chip_reset_stream,
+ *   chip_scan_local, chip_merge_decide[_enqueue];   chip_loop_ticks_bulk;   chip_synchronize, chip_destroy, chip_set_stream / chip_reset_stream,
  *   chip_resident_pause, chip_profile_enable / _reset / _scan.
  * A HIP failure while a pass is submitted is returned by the collect of each tick it concerned.  With profiling on a pass is one
  * launch: one event pair, bytes_per_launch_last = the bytes of that pass. */
@@ -544,6 +544,58 @@ int chip_build_has_tick_coalesce(void);   /* 1: this build can serve several pip
 int chip_debug_coalesce_stats(chip_ctx *ctx, int64_t *passes, int64_t *ticks);
 int chip_debug_coalesce_force(chip_ctx *ctx, int32_t on);
 int chip_debug_coalesce_decide(int32_t n_parked, int32_t t_max, int32_t scan_running);
+
+/* Bulk ticks (ABI 7, additive): the records of a whole SEQUENCE of ticks from many-query passes -- for a node restarted from its state, a
+ * replay, a second session searched against a first (Cerebro.cpp:956-1100 run over rows that are all there already).
+ * Definition: out[t] is, bit for bit in every field, the record the t-th call of
+ *     chip_loop_tick(ctx, l[0], p, ..), chip_loop_tick(ctx, l[1], p, ..), ...
+ * returns on the same DB, starting from a loop state whose last_l is the argument; *last_l_out the loop state after the last one.  SKIPPED
+ * and TOO_SHORT ticks and the advance of last_l follow the rule of the tick itself (one function serves both).  scores / idx of a SCANNED
+ * tick are what chip_query_rows(ctx, l - lag, {l-1, l-2, l-3}, 3, topk, ..) returns: fp64 scores in the order of DESIGN.md 3, (score
+ * desc, index desc), unused slots -inf / -1; of every other tick -inf / -1.
+ * How a call runs: the scanned ticks are stable-sorted by k and walked in groups of at most CHIP_BULK_TICKS_GROUP ticks (three queries
+ * each, so a tick never straddles a CHIP_QUERY_PREFIX_GROUP).  A group is the gather, the prefixed GEMM and the list merge of
+ * chip_query_batch_rows_f32 with a list length of the library's own, then ONE launch that, per tick, proves from the fp32 lists which
+ * rows can be in each exact top-topk (the certificate of DESIGN.md 3: the GEMM's score is one fp32 chain of D terms, inside the same bound E),
+ * scores those rows in fp64 in the scan's own order, ranks them and applies the accept rule; one copy back, one host wait.  A tick whose
+ * proof does not go through runs again alone through the exact scan after the last group, so the answer never depends on the data.  Where
+ * the row-norm bound is out of the fp32 range (row_norm_max^2 > 2^120) every scanned tick takes the exact path.
+ * State: a pure function of the DB and its arguments.  The ctx's own last_l, slots and parked ticks are neither read nor written (parked
+ * ticks are released first, as by the calls listed above); the query lock is held and the resident scan paused for the call.
+ * Status, all checked before anything is launched or written: NULL ctx / l / out or T < 1 CHIP_ERR_INVALID_ARG; topk outside [1, 8],
+ * D % 32 != 0, double rows, a chip_create_multi or sharded ctx CHIP_ERR_UNSUPPORTED (double rows would need the rounding of the cast folded
+ * into E: deliberately not part of this interface); an l[t] for which the sequential call would return CHIP_ERR_RANGE: CHIP_ERR_RANGE.
+ * One refusal more than the tick has: a scanned tick whose prefix k = l - lag is negative or beyond the published length (only with a
+ * negative lag, or min_k below -lag) is CHIP_ERR_RANGE here and in chip_bulk_ticks_plan; chip_loop_tick does not check it.
+ *   - chip_bulk_ticks_plan (no ctx, no device): status and k of every tick (k[t] = 0 where the tick is not scanned), the final last_l and
+ *     the grouping, from the functions the call itself uses.  units / units_rect count DB tiles as chip_query_prefix_plan does.
+ *   - chip_debug_bulk_ticks_last: what the ctx's last bulk call did.  launches counts the group launches (four per group) and not those
+ *     of the exact reruns; certified / uncertified are ticks; rescored_rows the rows scored exactly by the finishing launches.            */
+#define CHIP_BULK_TICKS_GROUP 1365   /* ticks per group: 4095 queries */
+#define CHIP_BULK_TICKS_MAX_TOPK 8
+typedef struct chip_bulk_ticks_plan_out {
+    int32_t group_ticks;   /* CHIP_BULK_TICKS_GROUP                                                                       */
+    int32_t groups;
+    int32_t tile_full;     /* rows of the tile of a full group (256); 0 when the call has no full group                   */
+    int32_t tile_last;     /* of the last group: 256 or 128; 0 when no tick is scanned                                    */
+    int64_t ticks_scanned, ticks_skipped, ticks_too_short;
+    int64_t units, units_rect;
+    int64_t last_l;        /* the loop state after the last tick                                                          */
+} chip_bulk_ticks_plan_out;
+typedef struct chip_bulk_ticks_last {
+    int32_t groups, launches, waits;
+    int32_t list_len;      /* KL: entries per fp32 list                                                                   */
+    int64_t certified, uncertified, rescored_rows, exact_reruns;
+    double E;              /* the error bound the certificates used (0 where every tick took the exact path)              */
+} chip_bulk_ticks_last;
+int chip_build_has_bulk_ticks(void);   /* 1 */
+int chip_loop_ticks_bulk(chip_ctx *ctx, const int64_t *l, int32_t T, const chip_dot_params *p /* NULL: defaults */,
+                         int64_t last_l, int32_t topk /* 1 .. 8 */,
+                         chip_tick_result *out /* T */, double *scores /* T x 3 x topk, may be NULL */,
+                         int64_t *idx /* T x 3 x topk, may be NULL */, int64_t *last_l_out /* may be NULL */);
+int chip_bulk_ticks_plan(const int64_t *l, int32_t T, const chip_dot_params *p /* NULL: defaults */, int64_t last_l, int64_t n_rows,
+                         int32_t *status /* T */, int64_t *k /* T */, chip_bulk_ticks_plan_out *out);
+int chip_debug_bulk_ticks_last(chip_ctx *ctx, chip_bulk_ticks_last *out);
 
 /* Test aids (ABI 7, additive): WHICH kernel a top-k scan ran.  The scan dispatcher chooses between four kernel families and their
  * template instantiations from the prefix size, the row size, the query count, the kind of call and the CHIP_SCAN_* knobs; all of
